@@ -17,7 +17,12 @@ Workloads (BASELINE.json configs):
                           gathers the gene lists (shard.run_sharded_flat)
   --workload lambda | t4  configs 2-3: one contig (tests/golden/NC_001416.1 48.5 kb / NC_000866.1 169 kb) on one GPU
 
-  python bench.py --gpus 1 --steps 5 --warmup 2
+A plain run sets up, warms up, times the K steps of `value` and prints the line.  --full adds everything else: the certificate,
+host-to-host and two-batches-in-flight regions, the stage table and roofline (with two rocprofv3 --pmc passes), the single-contig
+configs, config 5's batch on one GPU, the CPU baselines and the CLI run.  --dump-outputs DIR writes what the last timed step
+computed (status, offsets and gene records, gathered to rank 0) as DIR/<name>.npy in float64.
+
+  python bench.py --gpus 1 --steps 5 --warmup 2 [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -91,7 +96,7 @@ def pmc_traffic_live(contigs, length, device):
             for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
                 d = os.path.join(td, ctr)
                 cmd = [exe, "--kernel-trace", "--pmc", ctr, "--output-format", "csv", "-d", d, "-o", "p", "--", sys.executable, os.path.abspath(__file__),
-                       "--steps", "1", "--warmup", "0", "--no-extras", "--no-pipeline", "--contigs", str(contigs), "--length", str(length)]
+                       "--steps", "1", "--warmup", "0", "--full", "--no-extras", "--no-pipeline", "--contigs", str(contigs), "--length", str(length)]
                 r = subprocess.run(cmd, cwd=td, env=env, capture_output=True, text=True, timeout=900)
                 files = glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True)
                 if r.returncode != 0 or not files:
@@ -205,6 +210,32 @@ def cli_end_to_end(seqs, device):
         return timing
 
 
+DUMP_LIMIT = 64 << 20
+GENE_FIELDS = ("left", "right", "strand", "frame", "score")
+
+
+def dump_outputs(d, status, offsets, genes):
+    """What a caller of the timed path receives (phx_download_flat: status[n], offsets[n+1], genes[total]) as float64 .npy files,
+    at most DUMP_LIMIT bytes: beyond that a fixed, seeded sample of the gene rows, whose indices go to gene_index.npy."""
+    import numpy as np
+
+    out = {"status": np.asarray(status, np.float64), "offsets": np.asarray(offsets, np.float64)}
+    room = DUMP_LIMIT - 4096 - sum(a.nbytes for a in out.values())  # (4 KiB: the .npy headers)
+    if room < 0:
+        raise RuntimeError("bench.py: the per-contig arrays alone exceed %d bytes" % DUMP_LIMIT)
+    rows = None
+    if len(genes) * 8 * len(GENE_FIELDS) > room:
+        k = room // (8 * (len(GENE_FIELDS) + 1))
+        rows = np.sort(np.random.RandomState(0).choice(len(genes), k, replace=False))
+        out["gene_index"] = rows.astype(np.float64)
+    for f in GENE_FIELDS:
+        col = genes[f] if rows is None else genes[f][rows]
+        out["gene_" + f] = np.asarray(col, np.float64)
+    os.makedirs(d, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -225,7 +256,13 @@ def main():
     ap.add_argument("--dump-merged", default=None, help="rank 0 writes the merged (status, offsets, genes) of the host-to-host region to this .npz (tests)")
     ap.add_argument("--no-pipeline-host", action="store_true", help="skip the host-to-host region of two_batches_in_flight (a kernel trace then ends with the resident steps of the two contexts)")
     ap.add_argument("--no-traffic", action="store_true", help="do not run the two rocprofv3 --pmc passes for roofline.traffic (use profiles/traffic.json)")
+    ap.add_argument("--full", action="store_true", help="measure everything beside `value` as well (see the module docstring); the --no-* switches and --dump-merged apply to it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the status, offsets and gene records of the last timed step to DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_merged and not args.full:
+        ap.error("--dump-merged writes the host-to-host region's result: it needs --full")
 
     import numpy as np
     import torch
@@ -276,8 +313,9 @@ def main():
     # two contexts on this GPU (their own streams; torch is only here for the process group and the barrier): the first one does all
     # the one-batch-at-a-time measurements, both take turns for the `two_batches_in_flight` lines.  (No third context: with more
     # streams than hardware queues the streams of two contexts alias and their kernels stop overlapping.)
-    pipe = pa.Pipeline(device=local_rank, depth=2)
-    ann = pipe.anns[0]
+    # (a plain run needs the first context only)
+    pipe = pa.Pipeline(device=local_rank, depth=2) if args.full else None
+    ann = pipe.anns[0] if args.full else pa.Annotator(device=local_rank)
 
     def barrier():
         if dist is not None:
@@ -305,7 +343,8 @@ def main():
     status, offs, genes = ann.annotate_flat(seqs)  # sizes the context's buffers
     for _ in range(args.warmup):
         ann.run()
-    # untimed pass with every stage bracketed by HIP events: the stage table, and which kernel dominates
+    # untimed pass with every stage bracketed by HIP events: the stage table, and which kernel dominates (a plain run makes it as well:
+    # it picks the stages the timed region brackets, so that `value` is timed as it always was)
     ann.set_profiling(True)
     ann.stage_ms(reset=True)
     for _ in range(3):
@@ -329,6 +368,43 @@ def main():
     dom_total, dom_n = timed[dom]
     sec_total, sec_n = timed[second] if args.workload == "synthetic" else (stages_all[second][0], 3)
     ann.set_profiling(False)
+    bp_total = sum_over_ranks(float(sum(len(s) for s in seqs)))
+    value = bp_total * args.steps / dt / 1e6
+    if args.dump_outputs:
+        # the device's gene lists of the last timed step (phx_run computes no certificate), gathered to rank 0 like the host-to-host region's
+        last = run_sharded_flat(seqs, lambda _: ann.download_flat(exact=False), rank, world, dist, mine=(mine, n_total))
+        if rank == 0:
+            dump_outputs(args.dump_outputs, *last)
+    head = {
+        "metric": "Mbp/s annotated (whole node) on 50 kb synthetic phage contigs" if args.workload == "synthetic" else "Mbp/s annotated, single contig",
+        "value": round(value, 3),
+        "unit": "Mbp/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak" if world == 1 and n_total != 10000 else "strong",
+        "vs_baseline": None,
+        "dtype": "u8 bases / fp64 scores / int64 edge weights / int128 distances",
+        "data": ("synthetic" if args.workload == "synthetic" else "reference test genome (tests/golden)") + (" [SMOKE: all ranks on one GPU, gloo]" if args.smoke_single_device else ""),
+        "value_is": "inputs resident in HBM when the timed region starts (task contract); host ASCII -> host gene lists is `host_to_host` (--full)",
+        "config": {
+            "workload": wl,
+            "contigs_total": n_total,
+            "contigs_rank0": len(seqs),
+            "contig_length": L_,
+            "sharding": "per-contig across %d GPU(s) (phanotate_amd.shard.partition), no collective in the data path" % world,
+        },
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        ann.close()
+        return
     # the certificate (phx_certified: the proof that every gene list is what the reference's Decimal-derived integers give) is computed
     # on demand from the state a run leaves on the device: its cost on top of a run, and how many contigs it covers
     t0 = time.perf_counter()
@@ -339,8 +415,6 @@ def main():
     n_uncert = int(sum_over_ranks(float((cert != 1).sum())))   # not proven on the device
     n_again = int(sum_over_ranks(float((cert == 2).sum())))     # ... and therefore solved again on the host, inside the library
     sz = ann.batch_sizes()
-    bp_total = sum_over_ranks(float(sum(len(s) for s in seqs)))
-    value = bp_total * args.steps / dt / 1e6
 
     # ---- timed region B: host ASCII -> host gene lists: upload, every kernel, download, gather to rank 0 ----
     # (the caller's side of the C-ABI — the contigs' addresses and lengths, phx_upload's arguments — is built once: a C caller has them)
@@ -423,34 +497,16 @@ def main():
         step_achieved = balgo / (kernel_ms_per_step * 1e-3) / 1e9
         kern_of = [int(ann.globals(i).sssp_kernel) for i in range(len(seqs))]
         solver_kernels = {"wavefront_tight": kern_of.count(2), "wavefront_roomy": kern_of.count(3), "workgroup": kern_of.count(1), "global": kern_of.count(0)}
-        out = {
-            "metric": "Mbp/s annotated (whole node) on 50 kb synthetic phage contigs" if args.workload == "synthetic" else "Mbp/s annotated, single contig",
-            "value": round(value, 3),
-            "unit": "Mbp/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak" if world == 1 and n_total != 10000 else "strong",
-            "vs_baseline": None,
-            "dtype": "u8 bases / fp64 scores / int64 edge weights / int128 distances",
-            "data": ("synthetic" if args.workload == "synthetic" else "reference test genome (tests/golden)") + (" [SMOKE: all ranks on one GPU, gloo]" if args.smoke_single_device else ""),
+        out = dict(head, **{
             "value_with_certificate": round(bp_total * args.steps / dt_cert / 1e6, 3),
             "value_with_certificate_is": "the same resident step followed by phx_certified (k_refine + k_certify: the proof that every gene list is the one the reference's Decimal-derived integers give): the rate that carries the bit-identity guarantee; `value` is phx_run alone",
-            "value_is": "inputs resident in HBM when the timed region starts (task contract); host ASCII -> host gene lists is `host_to_host`",
-            "config": {
-                "workload": wl,
-                "contigs_total": n_total,
-                "contigs_rank0": len(seqs),
-                "contig_length": L_,
-                "sharding": "per-contig across %d GPU(s) (phanotate_amd.shard.partition), no collective in the data path" % world,
+            "config": dict(head["config"], **{
                 "genes_called_total": int(len(genes_all)),
                 "contigs_with_error_status": int((st_all < 0).sum()),
                 "int_limbs": int(ann.globals(0).n_limbs),
                 "solver_kernel_contig0": int(ann.globals(0).sssp_kernel),
                 "solver_kernels": solver_kernels,
-            },
+            }),
             "certificate": {"ms_per_step_with_run": round(dt_cert / args.steps * 1e3, 4), "ms_on_top_of_run": round((dt_cert - dt) / args.steps * 1e3, 4), "contigs_not_certified_on_device": n_uncert,
                             "contigs_solved_again_on_host": n_again,
                             "what": "phx_run_async + phx_certified per step: k_refine evaluates the edges fp64 could not place between two integers once more in double-double (bounds on the reference's integers from the error of its own 28-digit chain), k_certify proves per contig, in exact integers, that the gene list is the one the reference's Decimal-derived integers give (phx_refine.inc, phx_certify.inc); a contig it cannot prove is solved again on the host in the reference's own arithmetic, inside the library (phx_exact.inc).  Computed on demand, so `value` does not contain it; `host_to_host` (phx_download_flat asks for it) does"},
@@ -493,7 +549,7 @@ def main():
                               "why": "the exact shortest path (k_sssp_duo; k_sssp_wave<2> beyond 1024 contigs per GPU) and the edge fill (k_edges<true>) take about as long as each other (0.40-0.43 ms per 1000 contigs): which of the two is longer changes from run to run; both are measured with HIP events in the timed region"},
             },
             "stage_ms_per_step": {k: round(v[0] / 3, 4) for k, v in stages_all.items() if v[1] > 0},
-        }
+        })
         ref = reference_python_rate()
         if ref:
             out["reference_python"] = ref

@@ -27,7 +27,7 @@ def test_config5_eight_ranks_on_one_gpu_equal_one_process_and_the_oracle(tmp_pat
     import phanotate_amd as pa
 
     out = tmp_path / "merged.npz"
-    r = _torchrun(8, 29551, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0", "--smoke-single-device", "--no-extras", "--no-pipeline",
+    r = _torchrun(8, 29551, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0", "--smoke-single-device", "--full", "--no-extras", "--no-pipeline",
                   "--dump-merged", str(out))
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 8 and d["scaling"] == "strong" and d["config"]["contigs_total"] == 10000 and d["config"]["contigs_rank0"] == 1250
@@ -89,7 +89,7 @@ def test_first_run_of_a_context_with_eight_processes_on_one_gpu(tmp_path):
 def test_rccl_plus_gloo_group_comes_up_with_one_rank():
     """shard.init_group's production branch ("cpu:gloo,cuda:nccl", device bound): barrier and all_reduce on the GPU over RCCL, the
     gather over gloo — with the single rank a 1-GPU box allows."""
-    r = _torchrun(1, 29552, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "1", "--warmup", "0", "--contigs", "40", "--length", "20000",
+    r = _torchrun(1, 29552, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "1", "--warmup", "0", "--full", "--contigs", "40", "--length", "20000",
                   "--no-extras", "--no-pipeline", timeout=600)
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 1 and d["config"]["contigs_total"] == 40 and d["config"]["contigs_with_error_status"] == 0 and d["value"] > 0

@@ -1122,7 +1122,7 @@ def test_bench_sharded_path_smoke():
     from conftest import ROOT
 
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29541",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--contigs", "120", "--length", "20000", "--smoke-single-device", "--no-extras"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--contigs", "120", "--length", "20000", "--smoke-single-device", "--full", "--no-extras"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -1130,6 +1130,33 @@ def test_bench_sharded_path_smoke():
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["contigs_total"] == 120 and d["config"]["contigs_rank0"] == 60
     assert d["config"]["contigs_with_error_status"] == 0 and d["config"]["genes_called_total"] > 120 * 10
     assert d["value"] > 0 and d["host_to_host"]["value"] > 0
+
+
+def test_bench_plain_line_and_dumped_outputs(pa, tmp_path):
+    """A plain bench.py run (no --full) prints the headline figures only, and --dump-outputs holds what its last timed step
+    computed: the status, offsets and gene records one context gives for the same contigs, as float64."""
+    import json
+    import subprocess
+    import sys
+
+    from conftest import ROOT
+
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--contigs", "40", "--length", "20000",
+           "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "Mbp/s" and d["higher_is_better"] is True
+    assert d["metric"] and d["dtype"] and d["config"]["contigs_total"] == 40
+    assert not {"host_to_host", "certificate", "roofline", "stage_ms_per_step", "cpu_baseline"} & set(d)
+    got = {f[:-4]: np.load(os.path.join(str(tmp_path), f)) for f in os.listdir(str(tmp_path))}
+    assert all(a.dtype == np.float64 for a in got.values())
+    ann = pa.Annotator()
+    st, offs, genes = ann.annotate_flat([pa.synth_contig(i, 20000) for i in range(40)])
+    ann.close()
+    assert "gene_index" not in got and np.array_equal(got["status"], st) and np.array_equal(got["offsets"], offs)
+    for f in ("left", "right", "strand", "frame", "score"):
+        assert np.array_equal(got["gene_" + f], genes[f]), f
 
 
 def test_many_ambiguous_contigs_outgrow_the_tie_scratch(pa, oracle):

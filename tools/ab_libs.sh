@@ -11,7 +11,7 @@ mkdir -p $(dirname $out)
 for r in $(seq 1 $rounds); do
   for l in "${libs[@]}"; do
     cp $l phanotate_amd/libphx.so
-    python bench.py --no-extras --no-traffic --no-pipeline "$@" 2>/dev/null | python -c "
+    python bench.py --full --no-extras --no-traffic --no-pipeline "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$l', d['ms_per_step'], d['certificate']['ms_per_step_with_run'], {k: round(v,3) for k,v in d['stage_ms_per_step'].items()})" >> $out
   done

@@ -8,7 +8,7 @@ cp phanotate_amd/libphx.so /tmp/new.so
 for i in $(seq $r); do
   for v in base new; do
     if [ $v = base ]; then cp phanotate_amd/libphx_base.so phanotate_amd/libphx.so; else cp /tmp/new.so phanotate_amd/libphx.so; fi
-    python bench.py --no-extras "$@" 2>/dev/null | python -c "
+    python bench.py --full --no-extras "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$v', d['ms_per_step'], d['roofline']['avg_launch_ms'])"
   done

@@ -5,7 +5,7 @@ n=${2:-1000}
 for rep in $(seq 1 ${3:-3}); do
 for v in $1; do
   cp tmp_variants/libphx_$v.so phanotate_amd/libphx.so
-  timeout 300 python bench.py --contigs $n --steps 30 --warmup 3 --no-extras --no-cpu --no-traffic --no-pipeline 2>/dev/null | python -c "
+  timeout 300 python bench.py --full --contigs $n --steps 30 --warmup 3 --no-extras --no-cpu --no-traffic --no-pipeline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=d['stage_ms_per_step']
 print('$v n=$n', d['ms_per_step'], ' '.join('%s %.4f' % (k, v) for k, v in s.items()))"
