@@ -33,7 +33,8 @@ extern "C" {
                          *        (phx_download* deliver reference-exact genes; phx_certified reports 2), phx_dump_text, PHX_CREATE_NO_EXACT;
                          *        (0.4.0 also REMOVED phx_rbs_table — an ABI break for a C caller that bound it: the table was a test hook of the Python Decimal
                          *        replay, which moved to tests/decimal_replay.py and computes it itself);
-                         * 0.4.1: phx_run_async puts the certificate kernels behind the run unless exactness is off; env PHX_FRONT_SPINS (tests) */
+                         * 0.4.1: phx_run_async puts the certificate kernels behind the run unless exactness is off; env PHX_FRONT_SPINS (tests);
+                         *        (additions, version unchanged) phx_orf_margin, phx_margins_flat, phx_tap_dist_target, phx_margins_ms, phx_format_margins */
 #define PHX_MAX_CODONS 16
 
 /* library-level errors */
@@ -293,6 +294,41 @@ int phx_tap_path(phx_ctx *ctx, int32_t contig, int32_t *path, int32_t cap, int32
  * an unreached node has a top word >= 2^61 */
 int phx_tap_dist(phx_ctx *ctx, int32_t contig, uint64_t *dist_limbs, int64_t cap_words);
 
+/* ---- per-ORF path margins, on demand after a run ----
+ * For one contig, with W(e) the solver's integer trunc(fp64 w * 1000) of edge e (the integers phx_tap_dist is exact for):
+ *   d_s(v)  the shortest source -> v distance (phx_tap_dist);
+ *   d_t(v)  the shortest v -> target distance, exact, in the contig's limb class; "unreached" when no path leads from v to the target;
+ *   D       = d_s(target) = d_t(source).
+ * An ORF's edge e = (u -> v) runs start -> stop on the forward strand and stop -> start on the reverse strand (functions.py:310-316).
+ *   Delta(e) = d_s(u) + W(e) + d_t(v) - D, an integer >= 0 (no cycle of negative length): how much longer the best source -> target path
+ *   becomes when it is forced through the ORF.  margin = float(Delta) / 1000.0 exactly as Python computes it (the integer correctly rounded
+ *   to a double, then one correctly rounded division), in the units of SCORE.  d_s(u) or d_t(v) unreached: no path runs through the ORF,
+ *   through = 0 and margin = +inf.
+ * These are margins over the device's integers W, not over the reference's trunc(Decimal(w) * 1000): on a contig the certificate proves
+ * (phx_certified 1) every called ORF has margin 0 exactly; on one solved again on the host (phx_certified 2) a called ORF may carry a small
+ * positive margin, bounded by the |D| + eps bounds phx_tap_edges reports over the edges of the device's and the delivered path. */
+typedef struct phx_orf_margin {
+    int32_t left, right, strand, frame; /* as phx_gene (right includes the stop codon) */
+    double score;                       /* the ORF's edge weight, as phx_gene.score */
+    double margin;                      /* float(Delta)/1000, >= 0; +inf when through == 0 */
+    int32_t called;                     /* 1: one of the genes phx_download* delivers for this contig */
+    int32_t through;                    /* 1: some source->target path runs through this ORF */
+} phx_orf_margin;
+/* Margins of every CDS ORF of the batch last run, flat like phx_download_flat (rec == NULL: size query): the records of contig i are
+ * rec[offsets[i] .. offsets[i+1]), in phx_tap_orfs order (the reference's iter_orfs order), so that a caller can zip the two.  status[i]:
+ * the contig's run status when it is an error (< 0, no records; PHX_S_NEGCYCLE among them); PHX_S_OVERFLOW (no records) for a contig
+ * without device distances (path sums beyond 1088 bits, solved on the host); PHX_S_NEGCYCLE (no records) when the reverse pass meets a
+ * cycle of negative length the forward one could not reach; else the run status (0, or PHX_S_NOPATH: records with through = 0).
+ * The first call after a run computes them (out-edge CSR, a reverse shortest-path pass in the contig's wide integers, one thread per ORF:
+ * kernel by kernel on the context's stream, never inside phx_run; buffers allocated at the first call of a context); later calls reuse
+ * them.  Like every entry point it waits for a run in flight; a new upload invalidates the results. */
+int phx_margins_flat(phx_ctx *ctx, phx_orf_margin *rec, int64_t cap, int64_t *offsets /* [n+1] */, int32_t *status /* [n] */, int64_t *total);
+/* exact distance of every node TO the target: n_node x sssp_nl words, like phx_tap_dist (an unreached node has a top word >= 2^61) */
+int phx_tap_dist_target(phx_ctx *ctx, int32_t contig, uint64_t *dist_limbs, int64_t cap_words);
+/* device time of the last computation of the margins (HIP events on the context's stream), ms[4]: out-edge CSR, reverse pass, records,
+ * the copy of the records to the host.  All 0 before the first. */
+int phx_margins_ms(phx_ctx *ctx, float *ms /* [4] */);
+
 /* -d/--dump of the reference (phanotate.py:58,61) for one contig of the batch last run: one line per edge of its graph,
  *     repr(source) TAB repr(target) TAB str(weight * 1000)                                   (edges.py:17-23, nodes.py:14-21)
  * in Graph.iteredges order, the weights as the reference's 28-digit Decimals (the chain replayed by csrc/phx_dec.c on the integers
@@ -375,6 +411,11 @@ void phx_fasta_free(phx_fasta *f);
  * "#id:\t<name>", the column header, then START STOP FRAME CONTIG SCORE per gene ('%E' score; START > STOP on the reverse
  * strand).  Contigs with a negative status are skipped.  *text is malloc'ed (NUL-terminated), release with phx_free_text. */
 int phx_format_tabular(int32_t n, const char *const *names, const phx_gene *genes, const int64_t *offsets, const int32_t *status, char **text, int64_t *text_len);
+/* --margins FILE of the CLI for n contigs from the flat arrays of phx_margins_flat: per contig with status >= 0 "#id:\t<name>", the
+ * header "#START\tSTOP\tFRAME\tCONTIG\tSCORE\tMARGIN\tCALLED", then one row per record with through == 1, ordered by left, right, strand
+ * (START > STOP on the reverse strand, as the tabular writer; SCORE and MARGIN '%E'; CALLED 0 / 1).  Worker threads like
+ * phx_format_tabular.  *text is malloc'ed (NUL-terminated), release with phx_free_text. */
+int phx_format_margins(int32_t n, const char *const *names, const phx_orf_margin *rec, const int64_t *offsets, const int32_t *status, char **text, int64_t *text_len);
 void phx_free_text(char *text);
 
 #ifdef __cplusplus

@@ -329,6 +329,44 @@ class Annotator:
             out.append(None if x >= 1 << (64 * nl - 3) else x)
         return out
 
+    def dist_to_target(self, i):
+        """Exact distance of every node TO the target as python ints (None: no path to the target), device node order
+        (phx_tap_dist_target; the margins' reverse pass, computed on the first call after a run)."""
+        g = self.globals(i)
+        nl, V = max(g.n_limbs, 1), max(g.n_node, 0)
+        a = np.zeros((max(V, 1), nl), np.uint64)
+        self._chk(self.L.phx_tap_dist_target(self.h, i, a.ctypes.data_as(C.c_void_p), a.size), "phx_tap_dist_target")
+        out = []
+        for v in range(V):
+            x = 0
+            for k in range(nl):
+                x |= int(a[v, k]) << (64 * k)
+            if x >> (64 * nl - 1):
+                x -= 1 << (64 * nl)
+            out.append(None if x >= 1 << (64 * nl - 3) else x)
+        return out
+
+    def margins(self):
+        """(status int32[n], offsets int64[n+1], records structured array[total] of _lib.MARGIN_DT): the path margin of every CDS ORF of
+        the batch last run (phx_margins_flat).  The records of contig i are records[offsets[i]:offsets[i+1]], in the order of orfs(i);
+        margin = float(d_s(u) + W + d_t(v) - D) / 1000 (0 for a called ORF of a certified contig, +inf where no path runs through the ORF);
+        status as phx_margins_flat reports it (< 0: no records)."""
+        n = self.n
+        offs = np.zeros(n + 1, np.int64)
+        status = np.zeros(max(n, 1), np.int32)
+        total = C.c_int64(0)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._chk(self.L.phx_margins_flat(self.h, None, 0, vp(offs), vp(status), C.byref(total)), "phx_margins_flat")
+        rec = np.empty(max(int(total.value), 1), _lib.MARGIN_DT)
+        self._chk(self.L.phx_margins_flat(self.h, vp(rec), len(rec), vp(offs), vp(status), C.byref(total)), "phx_margins_flat")
+        return status[:n], offs, rec[: int(total.value)]
+
+    def margins_ms(self):
+        """Device time of the last margins computation in ms: out-edge CSR, reverse pass, records, copy to the host (phx_margins_ms)."""
+        ms = (C.c_float * 4)()
+        self._chk(self.L.phx_margins_ms(self.h, ms), "phx_margins_ms")
+        return dict(zip(("transpose", "reverse", "margins", "download"), [float(x) for x in ms]))
+
     # ---- solver alone (fastpathz boundary) ----
     def solve(self, V, src, dst, weights, source, target, n_limbs=None):
         """Exact shortest path over integer weights (python ints).  Returns (path node ids, distance) or ([], None)."""

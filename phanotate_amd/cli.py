@@ -40,8 +40,14 @@ def get_args(argv=None):
     p.add_argument("--device", type=int, default=None, help="GPU ordinal [LOCAL_RANK or 0]")
     p.add_argument("--gpus", type=int, default=1, help="spread the batches over the first N GPUs of the node, from this one process [1]")
     p.add_argument("--batch-bases", type=int, default=400_000_000, help="bases per GPU batch [4e8]")
+    p.add_argument("--margins", metavar="FILE", default=None, help="also write every ORF some source-to-target path runs through, with its path margin (DESIGN.md §11), to FILE")
     p.add_argument("--single-device-ranks", action="store_true", help=argparse.SUPPRESS)  # tests: every rank of a sharded launch on GPU `--device` (gloo-only group)
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.margins is not None and args.dump:
+        p.error("argument --margins: not allowed with argument -d/--dump")
+    if args.margins is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        p.error("argument --margins: not available under a multi-rank launch")
+    return args
 
 
 def dump_edges(out, ann, i, seq=None, start_codons="atg:0.85,gtg:0.10,ttg:0.05"):
@@ -70,6 +76,32 @@ def format_tabular(names, status, offsets, genes):
     rc = L.phx_format_tabular(n, arr, vp(genes), vp(offsets), vp(status), C.byref(text), C.byref(tlen))
     if rc:
         raise _lib.PhxError(rc, "phx_format_tabular")
+    out = C.string_at(text.value, tlen.value)
+    L.phx_free_text(text)
+    return out
+
+
+def format_margins(names, status, offsets, records):
+    """--margins FILE for a run of contigs, as bytes (libphx's phx_format_margins): per contig with status >= 0 "#id:\t<name>", the
+    header, one row per ORF with through == 1 (START STOP FRAME CONTIG SCORE MARGIN CALLED), ordered by left, right, strand."""
+    import ctypes as C
+
+    import numpy as np
+
+    from . import _lib
+
+    L = _lib.lib()
+    n = len(names)
+    enc = [x.encode() for x in names]
+    arr = (C.c_char_p * max(n, 1))(*enc)
+    status = np.ascontiguousarray(status, np.int32)
+    offsets = np.ascontiguousarray(offsets, np.int64)
+    records = np.ascontiguousarray(records, _lib.MARGIN_DT)
+    text, tlen = C.c_void_p(), C.c_int64()
+    vp = lambda x: x.ctypes.data_as(C.c_void_p)
+    rc = L.phx_format_margins(n, arr, vp(records), vp(offsets), vp(status), C.byref(text), C.byref(tlen))
+    if rc:
+        raise _lib.PhxError(rc, "phx_format_margins")
     out = C.string_at(text.value, tlen.value)
     L.phx_free_text(text)
     return out
@@ -157,6 +189,7 @@ def main(argv=None):
         return 0
 
     n_total = len(fa)
+    margin_parts = []  # --margins: (status, offsets, records) of every batch, in order
     mine = list(range(n_total)) if world == 1 else partition(fa.lens.tolist(), world)[rank]
 
     def annotate_flat(idx):  # this rank's contigs, in batches of --batch-bases, straight from the C buffer of the FASTA reader
@@ -187,6 +220,8 @@ def main(argv=None):
             t2 = time.perf_counter()
             parts = [ann.download_flat()]
             t3 = time.perf_counter()
+            if args.margins is not None:
+                margin_parts.append(ann.margins())
             t_parts["upload_s"] += t1 - t0; t_parts["run_s"] += t2 - t1; t_parts["download_s"] += t3 - t2
         else:  # a stream of batches: two in flight per GPU, the batches round the GPUs (pipeline.Pipeline)
             from .pipeline import Pipeline
@@ -196,8 +231,11 @@ def main(argv=None):
             t1 = time.perf_counter()
             gen = ((fa.ptrs[idx[lo:hi]], fa.lens[idx[lo:hi]], fa, (lambda a=lo, b=hi: trnas_of(idx[a:b]))) for lo, hi in cuts)
             try:
-                parts = list(pipe.run(gen))
+                parts = list(pipe.run(gen, margins=args.margins is not None))
                 t2 = time.perf_counter()
+                if args.margins is not None:
+                    margin_parts.extend(p[3] for p in parts)
+                    parts = [p[:3] for p in parts]
             finally:
                 pipe.close()
             t_parts["contexts_s"] = t1 - t0; t_parts["pipeline_s"] = t2 - t1; t_parts["gpus"] = n_gpu
@@ -231,6 +269,13 @@ def main(argv=None):
                     write(args.outfile, args.format, fa.names[i], fa.seq(i).decode(), genes[offsets[i] : offsets[i + 1]])
             t_fmt = time.perf_counter()
         args.outfile.flush()
+        if args.margins is not None:
+            m_status = np.concatenate([m[0] for m in margin_parts])
+            m_counts = np.concatenate([np.diff(m[1]) for m in margin_parts])
+            m_offsets = np.concatenate([[0], np.cumsum(m_counts)]).astype(np.int64)
+            m_records = np.concatenate([m[2] for m in margin_parts])
+            with open(args.margins, "wb") as fh:
+                fh.write(format_margins(fa.names, m_status, m_offsets, m_records))
     t_end = time.perf_counter()
     if os.environ.get("PHX_CLI_TIMING") and rank == 0:
         sys.stderr.write("PHX_CLI_TIMING " + json.dumps({"parse_s": round(t_parsed - t_start, 4), "gpu_s": round(t_gpu - t_parsed, 4), "format_s": round(t_fmt - t_gpu, 4),

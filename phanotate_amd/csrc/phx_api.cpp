@@ -217,6 +217,14 @@ struct phx_ctx {
     DevBuf b_swin, b_swrole, b_sdist, b_segw;
     int64_t plan_timeouts = 0;     // contigs, over the life of the context, whose solver gave up waiting for the planner it follows (phx_plan_timeouts)
     bool plan_stream_off = false;  // ... after the first of them the solver is launched behind its planner again on this context
+    // per-ORF margins (phx_margins_flat): buffers allocated at the first call, results kept until the next run
+    DevBuf b_mo, b_md, b_mw, b_mdt, b_mrec, b_mstat;
+    bool margins_done = false;       // the records of the run whose results the context holds are in h_mrec / mstat
+    phx_orf_margin *h_mrec = nullptr; size_t h_mrec_cap = 0; // pinned: the device's records (device ORF order)
+    std::vector<int32_t> mstat;      // per contig: the reverse pass did not settle
+    std::vector<DGrp> mgrp;          // the group records (reference order of the ORFs)
+    hipEvent_t mev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    float margins_ms[4] = {0, 0, 0, 0};
     float stage_ms[PHX_N_STAGES] = {0};
     int stage_n[PHX_N_STAGES] = {0};
     std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;
@@ -430,6 +438,7 @@ int set_batch_layout(phx_ctx *c, int32_t n, const int64_t *len_or_null, const in
     c->uploaded = false; c->ran = false; c->graph_valid = false; c->n = 0; // whatever fails below leaves the context without a batch
     c->meta_stale = false;
     c->has_trna = false; c->h_tnode.clear();
+    c->margins_done = false;
     if (n < 0) return PHX_E_ARG;
     if (!c->meta.assign((size_t)n)) { c->err = "hipHostMalloc failed"; return PHX_E_NOMEM; }
     c->ftab.clear(); c->vtotal = 0;
@@ -681,8 +690,11 @@ void phx_destroy(phx_ctx *c) {
     c->in_flight = false;
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     DevBuf *all[] = {&c->b_eref, &c->b_cint, &c->b_csig, &c->b_meta0, &c->b_tie, &c->b_ekey, &c->b_tnode, &c->b_tedge, &c->b_tnid, &c->b_tbits, &c->b_win, &c->b_wrole, &c->b_bridge, &c->b_recs, &c->b_meta, &c->b_tiles, &c->b_nbits, &c->b_nbase, &c->b_cbits, &c->b_orf, &c->b_ostat, &c->b_oweight, &c->b_owi, &c->b_oflag, &c->b_ewf, &c->b_esrcf, &c->b_onode, &c->b_grp, &c->b_bits, &c->b_cpre, &c->b_bpre, &c->b_item, &c->b_iprev,
-                     &c->b_node, &c->b_parent, &c->b_inoff, &c->b_no, &c->b_npos, &c->b_ehit, &c->b_mreach, &c->b_olist, &c->b_dist, &c->b_esrc, &c->b_ew, &c->b_ewl, &c->b_path, &c->b_genes, &c->b_gtot, &c->b_tot, &c->b_lpart, &c->b_res, &c->b_sord, &c->b_gtab, &c->b_erank, &c->b_swin, &c->b_swrole, &c->b_sdist, &c->b_segw};
+                     &c->b_node, &c->b_parent, &c->b_inoff, &c->b_no, &c->b_npos, &c->b_ehit, &c->b_mreach, &c->b_olist, &c->b_dist, &c->b_esrc, &c->b_ew, &c->b_ewl, &c->b_path, &c->b_genes, &c->b_gtot, &c->b_tot, &c->b_lpart, &c->b_res, &c->b_sord, &c->b_gtab, &c->b_erank, &c->b_swin, &c->b_swrole, &c->b_sdist, &c->b_segw,
+                     &c->b_mo, &c->b_md, &c->b_mw, &c->b_mdt, &c->b_mrec, &c->b_mstat};
     for (DevBuf *b : all) release(*b);
+    if (c->h_mrec) (void)hipHostFree(c->h_mrec);
+    for (hipEvent_t e : c->mev) if (e) (void)hipEventDestroy(e);
     if (c->graph_exec) (void)hipGraphExecDestroy(c->graph_exec);
     if (c->graph) (void)hipGraphDestroy(c->graph);
     if (c->h_tot) (void)hipHostFree(c->h_tot);
@@ -1252,6 +1264,7 @@ int push_layout(phx_ctx *c) {
 int launch_once(phx_ctx *c, bool learn) {
     int rc;
     c->tapw_valid = false; c->cert_done = false; c->exact_done = false; c->exact_genes.clear(); c->exact_failed = 0; c->host_only.clear();
+    c->margins_done = false;
     hipStream_t s = c->stream;
     c->eager_now = c->eager_done && !c->meta0_dirty && !c->tiles_dirty; // the first launch after such an upload only: a repeated or retried run does everything
     c->eager_done = false;
@@ -2079,6 +2092,142 @@ int phx_tap_dist(phx_ctx *c, int32_t contig, uint64_t *dist_limbs, int64_t cap_w
     const size_t words = (size_t)m.n_node * (size_t)m.sssp_nl;
     if (!dist_limbs || cap_words < (int64_t)words) return PHX_E_ARG;
     HIPCHK(c, hipMemcpy(dist_limbs, (uint64_t *)c->b_dist.p + (size_t)m.node_off * (size_t)c->n_limbs, words * 8, hipMemcpyDeviceToHost));
+    return PHX_OK;
+}
+
+// ---- per-ORF path margins (phx_margins.inc) ----
+// The device's records of every ORF of the batch (device order) into c->h_mrec and the reverse pass's per-contig verdicts into c->mstat,
+// once per run: kernel by kernel on the context's stream, outside the captured run graph.
+static int ensure_margins(phx_ctx *c) {
+    if (c->margins_done) return PHX_OK;
+    { const int rf = fetch_meta(c); if (rf) return rf; }
+    const size_t n = (size_t)c->n, V = (size_t)c->tot_node, E = (size_t)c->tot_edge, N = (size_t)c->tot_orf, G = (size_t)c->tot_grp;
+    const size_t limbs = (size_t)std::max(c->n_limbs, 2);
+    int nlm = 0; // limb classes of the contigs that have device distances
+    for (size_t i = 0; i < n; i++) {
+        const DMeta &m = c->meta[i];
+        if (m.status < 0 || m.n_node <= 2 || m.sssp_mode == 4) continue;
+        nlm |= m.sssp_nl == 2 ? 1 : m.sssp_nl == 4 ? 2 : m.sssp_nl == 8 ? 4 : 8;
+    }
+    int rc;
+    if ((rc = ensure(c, c->b_mo, (V + n + 1) * 4))) return rc;
+    if ((rc = ensure(c, c->b_md, (E + 1) * 4))) return rc;
+    if ((rc = ensure(c, c->b_mw, (E + 1) * 8))) return rc;
+    if ((rc = ensure(c, c->b_mdt, (V + 1) * limbs * 8))) return rc;
+    if ((rc = ensure(c, c->b_mrec, (N + 1) * sizeof(phx_orf_margin)))) return rc;
+    if ((rc = ensure(c, c->b_mstat, (n + 1) * 4))) return rc;
+    if (c->h_mrec_cap < N + 1) {
+        if (c->h_mrec) HIPCHK(c, hipHostFree(c->h_mrec));
+        c->h_mrec = nullptr; c->h_mrec_cap = 0;
+        const size_t cap = N + N / 4 + 1024;
+        HIPCHK(c, hipHostMalloc((void **)&c->h_mrec, cap * sizeof(phx_orf_margin), hipHostMallocDefault));
+        c->h_mrec_cap = cap;
+    }
+    for (hipEvent_t &e : c->mev) if (!e) HIPCHK(c, hipEventCreate(&e));
+    c->mstat.assign(n, 0);
+    c->mgrp.resize(G);
+    DBatch b;
+    fill_batch(c, &b);
+    DMarg g;
+    g.out_off = (uint32_t *)c->b_mo.p; g.out_dst = (uint32_t *)c->b_md.p; g.out_w = (long long *)c->b_mw.p;
+    g.dist_t = (uint64_t *)c->b_mdt.p; g.rec = (phx_orf_margin *)c->b_mrec.p; g.mstat = (int32_t *)c->b_mstat.p;
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipEventRecord(c->mev[0], s));
+    HIPCHK(c, hipMemsetAsync(c->b_mo.p, 0, (V + n + 1) * 4, s));
+    HIPCHK(c, hipMemsetAsync(c->b_mstat.p, 0, (n + 1) * 4, s));
+    phxk_margins_transpose(&b, &g, s);
+    HIPCHK(c, hipEventRecord(c->mev[1], s));
+    phxk_sssp_rev(&b, &g, nlm, s);
+    HIPCHK(c, hipEventRecord(c->mev[2], s));
+    phxk_margins(&b, &g, nlm, s);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->mev[3], s));
+    if (N) HIPCHK(c, hipMemcpyAsync(c->h_mrec, c->b_mrec.p, N * sizeof(phx_orf_margin), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipEventRecord(c->mev[4], s));
+    if (n) HIPCHK(c, hipMemcpyAsync(c->mstat.data(), c->b_mstat.p, n * 4, hipMemcpyDeviceToHost, s));
+    if (G) HIPCHK(c, hipMemcpyAsync(c->mgrp.data(), c->b_grp.p, G * sizeof(DGrp), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    for (int k = 0; k < 4; k++) { float ms = 0; if (hipEventElapsedTime(&ms, c->mev[k], c->mev[k + 1]) == hipSuccess) c->margins_ms[k] = ms; }
+    c->margins_done = true;
+    return PHX_OK;
+}
+
+// status of contig i's margins (include/phx.h)
+static int32_t margins_status(const phx_ctx *c, int i) {
+    const int32_t r = c->res[(size_t)i].status;
+    if (r < 0) return r;
+    const DMeta &m = c->meta[(size_t)i];
+    if (m.sssp_mode == 4 && m.n_node > 2) return PHX_S_OVERFLOW;
+    if (c->mstat[(size_t)i]) return PHX_S_NEGCYCLE;
+    return r;
+}
+
+int phx_margins_flat(phx_ctx *c, phx_orf_margin *rec, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
+    if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
+    if (c->in_flight) { const int rs = phx_wait(c); if (rs) return rs; }
+    if (!c->ran) return PHX_E_STATE;
+    HIPCHK(c, hipSetDevice(c->device));
+    { const int rx = ensure_exact(c); if (rx) return rx; } // `called` is against the genes phx_download* deliver
+    { const int rm = ensure_margins(c); if (rm) return rm; }
+    try {
+    int64_t total = 0;
+    for (int i = 0; i < c->n; i++) { offsets[i] = total; status[i] = margins_status(c, i); if (status[i] >= 0) total += c->meta[(size_t)i].n_orf; }
+    offsets[c->n] = total;
+    if (total_out) *total_out = total;
+    if (!rec) return PHX_OK; // size query
+    if (cap < total) return PHX_E_ARG;
+    // the delivered genes (as phx_download_flat: the host re-solve's where there was one)
+    int64_t hi = 0;
+    for (int i = 0; i < c->n; i++) { const DRes &m = c->res[(size_t)i]; hi = std::max<int64_t>(hi, m.gene_off + m.n_genes); }
+    { const int rg = ensure_gene_stage(c, (size_t)hi); if (rg) return rg; }
+    if (hi) {
+        HIPCHK(c, hipMemcpyAsync(c->h_genes, (const DGene *)c->b_genes.p + (gene_pack(c) ? gene_half(c) : 0), sizeof(DGene) * (size_t)hi, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    std::vector<uint64_t> keys;
+    auto key = [](int32_t left, int32_t right, int32_t strand) { return ((uint64_t)(uint32_t)left << 33) | ((uint64_t)(uint32_t)right << 1) | (strand < 0 ? 1u : 0u); };
+    std::vector<int> order, ref_rank, ref_first;
+    std::vector<DGrp> grp;
+    for (int i = 0; i < c->n; i++) {
+        if (status[i] < 0) continue;
+        const DMeta &m = c->meta[(size_t)i];
+        const DRes &r = c->res[(size_t)i];
+        const DGene *src = c->h_genes + (size_t)r.gene_off;
+        int64_t ng = r.n_genes;
+        const auto ex = c->exact_genes.find(i);
+        if (ex != c->exact_genes.end()) { src = ex->second.data(); ng = (int64_t)ex->second.size(); }
+        keys.clear();
+        for (int64_t k = 0; k < ng; k++) if (src[k].frame >= -3 && src[k].frame <= 3) keys.push_back(key(src[k].left, src[k].right, src[k].strand)); // (tRNA path edges, frame +-4, are no ORFs)
+        std::sort(keys.begin(), keys.end());
+        // device order -> the reference's iter_orfs order (phx_tap_orfs): groups by ascending DGrp.evkey, the ORFs of a group contiguous in both
+        grp.assign(c->mgrp.begin() + m.grp_off, c->mgrp.begin() + m.grp_off + m.n_grp);
+        reference_order(grp, order, ref_rank, ref_first);
+        phx_orf_margin *dst = rec + offsets[i];
+        const phx_orf_margin *from = c->h_mrec + m.orf_off;
+        for (size_t rr = 0; rr < order.size(); rr++) {
+            const DGrp &G = grp[(size_t)order[rr]];
+            if (G.n > 0) memcpy(dst, from + G.orf_begin, sizeof(phx_orf_margin) * (size_t)G.n);
+            dst += G.n;
+        }
+        for (int64_t k = offsets[i]; k < offsets[i + 1]; k++) rec[k].called = std::binary_search(keys.begin(), keys.end(), key(rec[k].left, rec[k].right, rec[k].strand)) ? 1 : 0;
+    }
+    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_margins_flat"; return PHX_E_NOMEM; }
+    return PHX_OK;
+}
+
+int phx_tap_dist_target(phx_ctx *c, int32_t contig, uint64_t *dist_limbs, int64_t cap_words) {
+    TAP_PRE(c, contig);
+    if (m.status < 0 || m.n_node <= 2 || m.sssp_mode == 4) return PHX_OK;
+    const size_t words = (size_t)m.n_node * (size_t)m.sssp_nl;
+    if (!dist_limbs || cap_words < (int64_t)words) return PHX_E_ARG;
+    { const int rm = ensure_margins(c); if (rm) return rm; }
+    HIPCHK(c, hipMemcpy(dist_limbs, (uint64_t *)c->b_mdt.p + (size_t)m.node_off * (size_t)c->n_limbs, words * 8, hipMemcpyDeviceToHost));
+    return PHX_OK;
+}
+
+int phx_margins_ms(phx_ctx *c, float *ms) {
+    if (!c || !ms) return PHX_E_ARG;
+    for (int k = 0; k < 4; k++) ms[k] = c->margins_ms[k];
     return PHX_OK;
 }
 

@@ -333,6 +333,16 @@ struct DBatch {
     DGene *genes_c;
 };
 
+// Per-ORF path margins (phx_margins.inc), on demand after a run: the context's lazily allocated buffers
+struct DMarg {
+    uint32_t *out_off;   // per contig V + 1 entries at node_off + contig (like in_off): the out-edge CSR of the contig's graph
+    uint32_t *out_dst;   // per out-edge (at edge_off): its head node
+    long long *out_w;    //   and its integer weight, encoded as DBatch.ew
+    uint64_t *dist_t;    // distance of every node TO the target, laid out like DBatch.dist (node_off * dist_stride, the contig's limbs per node)
+    phx_orf_margin *rec; // per ORF (at orf_off, device order): the record phx_margins_flat hands out (`called` is set on the host)
+    int32_t *mstat;      // per contig: 1 the reverse pass did not settle (a cycle of negative length); zeroed by the host
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -370,7 +380,10 @@ void phxk_front(const DBatch *b, void *stream); // small batches: ORF count ... 
 void phxk_seg_merge(const DBatch *b, int vmax, void *stream); // DBatch.seg: after the segment solvers (phxk_sssp mode 2, 128 bits): join + proof + parents
 int phxk_seg_kmax(void);
 void phxk_seg_fallback(const DBatch *b, void *stream); // ... and one sweep (k_wave_plan<2,0>, k_sssp_duo<0>) for the contigs k_seg_join / k_seg_close flagged (DMeta.seg_fail)
-void phxk_results(const DBatch *b, void *stream); // after every solver kernel of the run: parents as the reference's in-place Bellman-Ford leaves them
+void phxk_results(const DBatch *b, void *stream);
+void phxk_margins_transpose(const DBatch *b, const DMarg *g, void *stream); // out_off (zeroed by the caller) / out_dst / out_w from in_off / esrc / ew
+void phxk_sssp_rev(const DBatch *b, const DMarg *g, int nl_mask, void *stream); // dist_t of every contig of the limb classes in nl_mask (bit k: 2, 4, 8, 17 limbs)
+void phxk_margins(const DBatch *b, const DMarg *g, int nl_mask, void *stream); // the ORF records // after every solver kernel of the run: parents as the reference's in-place Bellman-Ford leaves them
 #ifdef __cplusplus
 }
 #endif

@@ -177,6 +177,7 @@ __device__ __forceinline__ int min_idx(int a, int b, int c) { return a > b ? (b 
 #include "phx_inorder.inc"
 #include "phx_refine.inc"
 #include "phx_certify.inc"
+#include "phx_margins.inc"
 
 // ------------------------------------------------------------------------------------------------
 // launchers
@@ -346,6 +347,29 @@ void phxk_seg_fallback(const DBatch *b, void *stream) {
     hipLaunchKernelGGL((k_sssp_duo<0, false>), dim3(b->n_contig), dim3(128), 0, (hipStream_t)stream, *b);
 }
 void phxk_results(const DBatch *b, void *stream) { hipLaunchKernelGGL(k_results, dim3((unsigned)((b->n_contig + LMB_T - 1) / LMB_T)), dim3(LMB_T), 0, (hipStream_t)stream, *b); }
+// per-ORF margins (phx_margins.inc): three launches for the out-edge CSR, one reverse pass per limb class, one for the records
+void phxk_margins_transpose(const DBatch *b, const DMarg *g, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned y = ysplit(b, 4);
+    hipLaunchKernelGGL(k_mg_count, dim3(b->n_contig, y), dim3(NT), 0, s, *b, *g);
+    hipLaunchKernelGGL(k_mg_scan, dim3(b->n_contig), dim3(NT), 0, s, *b, *g);
+    hipLaunchKernelGGL(k_mg_fill, dim3(b->n_contig, y), dim3(NT), 0, s, *b, *g);
+}
+void phxk_sssp_rev(const DBatch *b, const DMarg *g, int nl_mask, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (nl_mask & 1) hipLaunchKernelGGL(k_sssp_rev<2>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g);
+    if (nl_mask & 2) hipLaunchKernelGGL(k_sssp_rev<4>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g);
+    if (nl_mask & 4) hipLaunchKernelGGL(k_sssp_rev<8>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g);
+    if (nl_mask & 8) hipLaunchKernelGGL(k_sssp_rev<17>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g);
+}
+void phxk_margins(const DBatch *b, const DMarg *g, int nl_mask, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(b->n_contig, ysplit(b, 8));
+    if (nl_mask & 1) hipLaunchKernelGGL(k_margins<2>, grid, dim3(NT), 0, s, *b, *g);
+    if (nl_mask & 2) hipLaunchKernelGGL(k_margins<4>, grid, dim3(NT), 0, s, *b, *g);
+    if (nl_mask & 4) hipLaunchKernelGGL(k_margins<8>, grid, dim3(NT), 0, s, *b, *g);
+    if (nl_mask & 8) hipLaunchKernelGGL(k_margins<17>, grid, dim3(NT), 0, s, *b, *g);
+}
 size_t phxk_sssp_lds_bytes(int V, int nl) { return sssp_lds_bytes(V, nl); }
 // one workgroup for up to 1024 contigs; larger batches in two passes of a workgroup per 256 contigs
 void phxk_layout1(const DBatch *b, void *stream) {

@@ -1,0 +1,253 @@
+// phx_margins.inc — per-ORF path margins: the out-edge CSR, k_sssp_rev<NL> and k_margins (included by phx_kernels.hip).
+// ------------------------------------------------------------------------------------------------
+// On demand after a run (phx_margins_flat / phx_tap_dist_target), never inside it.  With d_s the distances the run left in DBatch.dist
+// and d_t(v) the exact distance from v TO the target, an ORF edge e = (u -> v) of weight W gets
+//     Delta(e) = d_s(u) + W + d_t(v) - D,   D = d_s(target)
+// how much longer the best source -> target path becomes when it is forced through e (DESIGN.md §11).
+//
+// Widths: d_s and d_t are bounded by B, the bound on simple-path sums k_layout2 sized the contig's limb class from (|B| < 2^(64 NL - 5));
+// |W| <= B as well (B includes the sum of the ORF weights).  Every partial sum of Delta is therefore below 4 B < 2^(64 NL - 3) in
+// magnitude: the contig's own NL limbs hold Delta in two's complement without an extra limb.
+
+// the contigs the pass covers: a graph, no error, distances on the device (sssp_mode 4: solved on the host, no device distances)
+__device__ __forceinline__ bool mg_contig(const DMeta *m) { return m->status >= 0 && m->n_node > 2 && m->sssp_mode != 4; }
+
+// ---- the out-edge CSR (transpose of in_off / esrc): count, scan, fill ----
+// out_off has V + 1 entries per contig at node_off + contig, like in_off; out-edge records (head node, encoded weight) at edge_off.
+// The host zeroes out_off first.  The fill takes slots from the top of a node's range down (atomicSub on the inclusive sums), so that
+// out_off ends as exclusive offsets without a second array; the order inside a node's range is whatever the atomics give (the pass
+// asks for values only).
+__global__ __launch_bounds__(NT) void k_mg_count(DBatch b, DMarg g) {
+    const DMeta *meta = &b.meta[blockIdx.x];
+    if (!mg_contig(meta)) return;
+    const int V = meta->n_node;
+    const uint32_t *in_off = b.in_off + meta->node_off + blockIdx.x;
+    const uint32_t *esrc = b.esrc + meta->edge_off;
+    uint32_t *oo = g.out_off + meta->node_off + blockIdx.x;
+    for (int v = (int)blockIdx.y * NT + (int)threadIdx.x; v < V; v += (int)gridDim.y * NT)
+        for (uint32_t e = in_off[v], e1 = in_off[v + 1]; e < e1; e++) atomicAdd(&oo[ESRC_NODE(esrc[e])], 1u);
+}
+__global__ __launch_bounds__(NT) void k_mg_scan(DBatch b, DMarg g) {
+    __shared__ uint32_t s_scan[NT / 64 + 1];
+    const DMeta *meta = &b.meta[blockIdx.x];
+    if (!mg_contig(meta)) return;
+    const int n = meta->n_node + 1; // (entry V counts nothing: it ends as the total)
+    uint32_t *oo = g.out_off + meta->node_off + blockIdx.x;
+    const int per = (n + NT - 1) / NT;
+    const int a = (int)threadIdx.x * per, z = a + per < n ? a + per : n;
+    uint32_t sum = 0;
+    for (int v = a; v < z; v++) sum += oo[v];
+    uint32_t tot;
+    uint32_t acc = block_excl_scan<NT>(sum, s_scan, &tot);
+    for (int v = a; v < z; v++) { acc += oo[v]; oo[v] = acc; } // inclusive
+}
+__global__ __launch_bounds__(NT) void k_mg_fill(DBatch b, DMarg g) {
+    const DMeta *meta = &b.meta[blockIdx.x];
+    if (!mg_contig(meta)) return;
+    const int V = meta->n_node;
+    const uint32_t *in_off = b.in_off + meta->node_off + blockIdx.x;
+    const uint32_t *esrc = b.esrc + meta->edge_off;
+    const long long *ew = b.ew + meta->edge_off;
+    const long long *gt = gtab_of(b, meta);
+    uint32_t *oo = g.out_off + meta->node_off + blockIdx.x;
+    uint32_t *od = g.out_dst + meta->edge_off;
+    long long *ow = g.out_w + meta->edge_off;
+    for (int v = (int)blockIdx.y * NT + (int)threadIdx.x; v < V; v += (int)gridDim.y * NT)
+        for (uint32_t e = in_off[v], e1 = in_off[v + 1]; e < e1; e++) {
+            const uint32_t sw = esrc[e];
+            const uint32_t k = atomicSub(&oo[ESRC_NODE(sw)], 1u) - 1u;
+            od[k] = (uint32_t)v;
+            ow[k] = edge_wenc(sw, ew, e, gt); // (a coded gap edge's integer from the contig's gap table: no k_edges_expand launch in front)
+        }
+}
+
+// ---- k_sssp_rev<NL>: d_t, one workgroup per contig ----
+// Sweep order: the target first, then the CDS / tRNA nodes from the right end down, the source last (node ids are position-sorted with
+// source = V-2, target = V-1): edges mostly point right, so a reversed sweep meets a node after nearly all of its out-neighbours.  The
+// sweep goes in chunks of NT nodes, Jacobi inside a chunk until it is stable, on the chunk's values in LDS (the out-edges that leave the
+// chunk are folded in once per visit: nothing outside it changes meanwhile; reads and writes of an iteration are separated by barriers,
+// so no thread ever reads a half-written wide integer).  When a node improves, its in-edges (the predecessors, whose values may now improve)
+// widen the work: a predecessor later in the sweep order raises the end of this sweep (s_hi), one earlier in it goes to the next sweep's
+// range [s_lo_next, s_hi_next].  So the first sweep visits only chunks that the target's distance has reached, and the later ones only
+// what the backward (overlap) edges left open; the pass ends when a sweep leaves nothing open.  At that point no edge can shorten any value:
+// the fixed point of min-plus relaxation, which is the exact distance vector (the values are lengths of walks to the target throughout).
+// No parents, no tie rule: only the values are asked for.  Bounds like k_sssp: a chunk that does not settle in NT + 8 rounds, or more than
+// V + 2 sweeps, is a cycle of negative length (DMarg.mstat = 1: the host reports PHX_S_NEGCYCLE for the contig's margins).
+__device__ __forceinline__ int mg_node(int i, int V) { return i == 0 ? V - 1 : (i == V - 1 ? V - 2 : V - 2 - i); } // sweep index -> node id
+__device__ __forceinline__ int mg_idx(int v, int V) { return v == V - 1 ? 0 : (v == V - 2 ? V - 1 : V - 2 - v); }  // node id -> sweep index
+template <int NL>
+__global__ __launch_bounds__(NT) void k_sssp_rev(DBatch b, DMarg g) {
+    __shared__ int s_flag[2];
+    __shared__ int s_hi, s_lo_next, s_hi_next;
+    __shared__ uint64_t s_d[NT * NL]; // the current chunk's values, by sweep index - c0
+    const DMeta *meta = &b.meta[blockIdx.x];
+    if (!mg_contig(meta) || meta->sssp_nl != NL) return;
+    const int V = meta->n_node, TGT = V - 1;
+    const uint32_t *oo = g.out_off + meta->node_off + blockIdx.x;
+    const uint32_t *od = g.out_dst + meta->edge_off;
+    const long long *ow = g.out_w + meta->edge_off;
+    const uint32_t *in_off = b.in_off + meta->node_off + blockIdx.x;
+    const uint32_t *esrc = b.esrc + meta->edge_off;
+    uint64_t *dt = g.dist_t + (size_t)meta->node_off * b.dist_stride;
+    const int tid = threadIdx.x;
+    for (int v = tid; v < V; v += NT) {
+        WInt<NL> d = wi_inf<NL>();
+        if (v == TGT) {
+#pragma unroll
+            for (int i = 0; i < NL; i++) d.v[i] = 0;
+        }
+        wi_store<NL>(dt + (size_t)v * NL, d);
+    }
+    if (tid == 0) { s_flag[0] = 0; s_flag[1] = 0; s_hi = 0; s_lo_next = V; s_hi_next = -1; }
+    __syncthreads();
+    int start = 0, sweeps = 0, it = 0;
+    bool bad = false;
+    for (;;) {
+        for (int c0 = (start / NT) * NT; c0 < V && c0 <= s_hi && !bad; c0 += NT) {
+            const int i = c0 + tid;
+            const int v = i < V ? mg_node(i, V) : -1;
+            const bool relax = v >= 0 && v != TGT;
+            const uint32_t e0 = relax ? oo[v] : 0u, e1 = relax ? oo[v + 1] : 0u;
+            // nothing outside the chunk changes while it iterates: the out-edges that leave it are folded in once, the ones inside it
+            // read the chunk's values from LDS
+            WInt<NL> cur = wi_inf<NL>();
+            if (v >= 0) cur = wi_load<NL>(dt + (size_t)v * NL);
+            WInt<NL> best = cur;
+            for (uint32_t e = e0; e < e1; e++) {
+                const uint32_t p = (uint32_t)(mg_idx((int)od[e], V) - c0);
+                if (p < (uint32_t)NT) continue;
+                const WInt<NL> dv = wi_load<NL>(dt + (size_t)od[e] * NL);
+                if (wi_is_inf<NL>(dv)) continue;
+                const WInt<NL> cand = wi_add<NL>(dv, ew_decode<NL>(ow[e]));
+                if (wi_lt<NL>(cand, best)) best = cand;
+            }
+            wi_store<NL>(s_d + (size_t)tid * NL, best);
+            __syncthreads();
+            int inner = 0;
+            bool chg = true;
+            while (chg) {
+                bool improved = false;
+                for (uint32_t e = e0; e < e1; e++) {
+                    const uint32_t p = (uint32_t)(mg_idx((int)od[e], V) - c0);
+                    if (p >= (uint32_t)NT) continue;
+                    const WInt<NL> dv = wi_load<NL>(s_d + (size_t)p * NL);
+                    if (wi_is_inf<NL>(dv)) continue;
+                    const WInt<NL> cand = wi_add<NL>(dv, ew_decode<NL>(ow[e]));
+                    if (wi_lt<NL>(cand, best)) { best = cand; improved = true; }
+                }
+                __syncthreads(); // every read of this iteration is done
+                if (improved) { wi_store<NL>(s_d + (size_t)tid * NL, best); s_flag[it & 1] = 1; }
+                if (tid == 0) s_flag[(it + 1) & 1] = 0;
+                __syncthreads();
+                chg = s_flag[it & 1] != 0;
+                it++;
+                if (++inner > NT + 8) { bad = true; break; } // a chunk of NT nodes settles in <= NT rounds unless a cycle is negative
+            }
+            if (v >= 0 && !wi_eq<NL>(best, cur)) { // improved: back to global memory, and the predecessors outside the chunk are open again
+                wi_store<NL>(dt + (size_t)v * NL, best);
+                int lo = V, hl = -1, hr = -1; // before this chunk (next sweep) / behind it (this sweep)
+                for (uint32_t e = in_off[v], x1 = in_off[v + 1]; e < x1; e++) {
+                    const int p = mg_idx((int)ESRC_NODE(esrc[e]), V);
+                    if (p < c0) { lo = p < lo ? p : lo; hl = p > hl ? p : hl; }
+                    else if (p >= c0 + NT) hr = p > hr ? p : hr;
+                }
+                if (hl >= 0) { atomicMin(&s_lo_next, lo); atomicMax(&s_hi_next, hl); }
+                if (hr >= 0) atomicMax(&s_hi, hr);
+            }
+            __syncthreads(); // (the chunk's values are in global memory and s_hi is final before the next chunk looks)
+        }
+        __syncthreads();
+        if (bad || s_lo_next >= V) break;
+        start = s_lo_next;
+        const int hn = s_hi_next;
+        __syncthreads();
+        if (tid == 0) { s_hi = hn; s_lo_next = V; s_hi_next = -1; }
+        __syncthreads();
+        if (++sweeps > V + 2) { bad = true; break; }
+    }
+    if (tid == 0 && bad) g.mstat[blockIdx.x] = 1;
+}
+
+// ---- k_margins: one thread per ORF (its start node, LINK_START) ----
+// (wi_neg: phx_certify.inc)
+// float(x) as Python computes it: the integer correctly rounded to a double (round half to even); beyond the double range: +-inf
+template <int NL>
+__device__ __forceinline__ double wi_to_double_rn(WInt<NL> x) {
+    const bool neg = (int64_t)x.v[NL - 1] < 0;
+    if (neg) x = wi_neg<NL>(x);
+    int p = -1; // bit index of the most significant one
+#pragma unroll
+    for (int i = 0; i < NL; i++)
+        if (x.v[i]) p = 64 * i + 63 - __clzll((long long)x.v[i]);
+    if (p < 0) return 0.0;
+    // the 64 bits from p down (hi64, its bit 63 = bit p of x) and whether anything below them is set
+    uint64_t hi64 = 0;
+    bool sticky = false;
+    const int lo = p - 63;
+    if (lo <= 0) hi64 = x.v[0] << (-lo);
+    else {
+        const int w = lo >> 6, s = lo & 63;
+#pragma unroll
+        for (int i = 0; i < NL; i++) {
+            if (i == w) { hi64 |= x.v[i] >> s; sticky = sticky || (s && (x.v[i] << (64 - s)) != 0); }
+            if (i == w + 1 && s) hi64 |= x.v[i] << (64 - s);
+            if (i < w) sticky = sticky || x.v[i] != 0;
+        }
+    }
+    uint64_t mant = hi64 >> 11;
+    const uint64_t rb = hi64 & 0x7ffull;
+    if (rb > 0x400ull || (rb == 0x400ull && (sticky || (mant & 1ull)))) mant++;
+    // mant <= 2^53 is exact in a double; ldexp scales exactly (or overflows to inf)
+    const double r = ldexp((double)mant, p - 52);
+    return neg ? -r : r;
+}
+
+template <int NL>
+__global__ __launch_bounds__(NT) void k_margins(DBatch b, DMarg g) {
+    const DMeta *meta = &b.meta[blockIdx.x];
+    if (!mg_contig(meta) || meta->sssp_nl != NL || g.mstat[blockIdx.x]) return;
+    const int V = meta->n_node;
+    const DOrf *orf = b.orf + meta->orf_off;
+    const DGrp *grp = b.grp + meta->grp_off;
+    const int32_t *onode = b.onode + meta->orf_off;
+    const double *oweight = b.oweight + meta->orf_off;
+    const DNode *nd = b.node + meta->node_off;
+    const uint32_t *in_off = b.in_off + meta->node_off + blockIdx.x;
+    const uint32_t *esrc = b.esrc + meta->edge_off;
+    const long long *ew = b.ew + meta->edge_off;
+    const long long *gt = gtab_of(b, meta);
+    const uint64_t *ds = b.dist + (size_t)meta->node_off * b.dist_stride;
+    const uint64_t *dt = g.dist_t + (size_t)meta->node_off * b.dist_stride;
+    phx_orf_margin *rec = g.rec + meta->orf_off;
+    const WInt<NL> D = wi_load<NL>(ds + (size_t)(V - 1) * NL);
+    const bool d_ok = !wi_unreached<NL>(D);
+    for (int k = (int)blockIdx.y * NT + (int)threadIdx.x; k < meta->n_orf; k += (int)gridDim.y * NT) {
+        const DOrf o = orf[k];
+        const int sn = onode[k], tn = grp[o.grp].node;
+        const bool fwd = o.frame > 0;
+        const int u = fwd ? sn : tn, v = fwd ? tn : sn; // the edge runs start -> stop on the forward strand, stop -> start on the reverse (functions.py:310-316)
+        const DNode nu = nd[u], nv = nd[v];
+        phx_orf_margin r;
+        r.left = nu.pos; r.right = nv.pos + 2; // as emit_genes (locus.py:29-37)
+        r.frame = NFRAME(nu.info);
+        r.strand = r.frame < 0 ? -1 : 1;
+        r.score = oweight[k];
+        r.called = 0; // (the host's: the delivered genes may come from the host re-solve)
+        r.through = 0;
+        r.margin = __builtin_inf();
+        // the ORF's edge among the in-edges of its right node, by its source
+        uint32_t e = 0xffffffffu;
+        for (uint32_t x = in_off[v], x1 = in_off[v + 1]; x < x1; x++)
+            if (ESRC_NODE(esrc[x]) == (uint32_t)u) { e = x; break; }
+        if (e != 0xffffffffu && d_ok) {
+            const WInt<NL> du = wi_load<NL>(ds + (size_t)u * NL), dv = wi_load<NL>(dt + (size_t)v * NL);
+            if (!wi_unreached<NL>(du) && !wi_unreached<NL>(dv)) {
+                const WInt<NL> w = ew_decode<NL>(edge_wenc(esrc[e], ew, e, gt)); // the edge's own integer, not one recomputed from oweight
+                const WInt<NL> delta = wi_add<NL>(wi_add<NL>(du, w), wi_add<NL>(dv, wi_neg<NL>(D)));
+                r.through = 1;
+                r.margin = wi_to_double_rn<NL>(delta) / 1000.0; // one correctly rounded division, as float(delta) / 1000.0
+            }
+        }
+        rec[k] = r;
+    }
+}

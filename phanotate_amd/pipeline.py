@@ -57,6 +57,7 @@ class Pipeline:
         if not devs:
             raise ValueError("Pipeline needs at least one device")
         self.depth = max(1, int(depth))
+        self._margins = False
         self.lanes = []
         try:
             for j, d in enumerate(devs):
@@ -77,25 +78,31 @@ class Pipeline:
     def __exit__(self, *exc):
         self.close()
 
-    def run(self, batches):
+    def run(self, batches, margins=False):
         """Generator over (status, offsets, genes) of every batch (Annotator.download_flat), in order.  While the caller consumes
-        batch k, the batches behind it are already running."""
+        batch k, the batches behind it are already running.  margins=True: every item gains the batch's (status, offsets, records) of
+        Annotator.margins(), fetched after the download on the same context."""
+        self._margins = bool(margins)
         if len(self.lanes) == 1:
             yield from self._run_one(self.lanes[0], batches)
             return
         yield from self._run_many(batches)
 
+    def _collect(self, a):
+        res = a.download_flat()
+        return res + (a.margins(),) if self._margins else res
+
     def _run_one(self, lane, batches):
         busy = deque()
         for batch in batches:
             if len(busy) == self.depth:
-                yield busy.popleft().download_flat()  # waits for the oldest run; its context is the one the new batch takes
+                yield self._collect(busy.popleft())  # waits for the oldest run; its context is the one the new batch takes
             a = lane.next_ctx()
             _load(a, batch)
             a.run_async()
             busy.append(a)
         while busy:
-            yield busy.popleft().download_flat()
+            yield self._collect(busy.popleft())
 
     def _run_many(self, batches):
         nl = len(self.lanes)
@@ -122,14 +129,14 @@ class Pipeline:
                     k, batch = item
                     if len(busy) == self.depth:
                         kk, a = busy.popleft()
-                        publish(kk, a.download_flat())
+                        publish(kk, self._collect(a))
                     a = lane.next_ctx()
                     _load(a, batch)
                     a.run_async()
                     busy.append((k, a))
                 while busy:
                     kk, a = busy.popleft()
-                    publish(kk, a.download_flat())
+                    publish(kk, self._collect(a))
             except BaseException as e:  # handed to the consumer
                 with cond:
                     errors.append(e)
