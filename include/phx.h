@@ -34,7 +34,8 @@ extern "C" {
                          *        (0.4.0 also REMOVED phx_rbs_table — an ABI break for a C caller that bound it: the table was a test hook of the Python Decimal
                          *        replay, which moved to tests/decimal_replay.py and computes it itself);
                          * 0.4.1: phx_run_async puts the certificate kernels behind the run unless exactness is off; env PHX_FRONT_SPINS (tests);
-                         *        (additions, version unchanged) phx_orf_margin, phx_margins_flat, phx_tap_dist_target, phx_margins_ms, phx_format_margins */
+                         *        (additions, version unchanged) phx_orf_margin, phx_margins_flat, phx_tap_dist_target, phx_margins_ms, phx_format_margins;
+ *        (additions, version unchanged) phx_gene_drop, phx_drop_margins_flat, phx_drop_ms, phx_drop_stats, phx_format_drops */
 #define PHX_MAX_CODONS 16
 
 /* library-level errors */
@@ -329,6 +330,34 @@ int phx_tap_dist_target(phx_ctx *ctx, int32_t contig, uint64_t *dist_limbs, int6
  * the copy of the records to the host.  All 0 before the first. */
 int phx_margins_ms(phx_ctx *ctx, float *ms /* [4] */);
 
+/* ---- gene drop margins, on demand after a run ----
+ * For one contig, with W, d_s, d_t and D as for the margins and P = p_0 (source) ... p_K (target) the device's shortest path (phx_tap_path):
+ * a called gene is a CDS ORF edge of P; its stop node is p_{j+1} of a forward gene (start p_j -> stop p_{j+1}) and p_j of a reverse gene
+ * (stop p_j -> start p_{j+1}).  D_{-g} is the shortest source -> target distance in the graph without that stop node: no ORF that ends at
+ * this stop is called, at any start.  drop = float(D_{-g} - D) / 1000.0 exactly as Python computes it, >= 0 (0: an equal-length path
+ * without the gene exists); bypass = 0 and drop = +inf when no path avoids the stop node. */
+typedef struct phx_gene_drop {
+    int32_t left, right, strand, frame; /* as phx_gene (right includes the stop codon) */
+    double score;                       /* the gene's edge weight, as phx_gene.score */
+    double drop;                        /* float(D_{-g} - D)/1000, >= 0; +inf when bypass == 0 */
+    int32_t called;                     /* 1: one of the genes phx_download* delivers for this contig (on a phx_certified 2 contig the
+                                         *    delivered genes may differ from the device path) */
+    int32_t bypass;                     /* 1: some source->target path avoids the stop node */
+} phx_gene_drop;
+/* Drop margins of every CDS gene of the device path of every contig of the batch last run, flat like phx_margins_flat (rec == NULL: size
+ * query): the records of contig i are rec[offsets[i] .. offsets[i+1]), in path order (left to right).  status[i] as phx_margins_flat:
+ * a run error (< 0), PHX_S_OVERFLOW (sssp_mode 4), PHX_S_NEGCYCLE from the reverse pass, all without records; PHX_S_NOPATH without
+ * records; else 0.  The first call after a run computes them (the margins' out-edge CSR and reverse pass when they are not there yet, then
+ * trees, labels, candidates and fixups: kernel by kernel on the context's stream, never inside phx_run); later calls reuse them.  The
+ * margins of phx_margins_flat are the same whichever of the two calls comes first. */
+int phx_drop_margins_flat(phx_ctx *ctx, phx_gene_drop *rec, int64_t cap, int64_t *offsets /* [n+1] */, int32_t *status /* [n] */, int64_t *total);
+/* device time of the last computation of the drop margins (HIP events), ms[4]: trees + labels, candidates + sparse table, fixups (saturated
+ * slots, cross nodes, records), the copy of the records to the host.  All 0 before the first. */
+int phx_drop_ms(phx_ctx *ctx, float *ms /* [4] */);
+/* counters of the last computation, out[4]: gene slots, slots with cross nodes (step 4 of DESIGN.md §12), saturated slots rescanned
+ * exactly, contigs whose trees were built layer by layer (a zero-length cycle of tight edges, or env PHX_DROP_LAYERED=1) */
+int phx_drop_stats(phx_ctx *ctx, int64_t *out /* [4] */);
+
 /* -d/--dump of the reference (phanotate.py:58,61) for one contig of the batch last run: one line per edge of its graph,
  *     repr(source) TAB repr(target) TAB str(weight * 1000)                                   (edges.py:17-23, nodes.py:14-21)
  * in Graph.iteredges order, the weights as the reference's 28-digit Decimals (the chain replayed by csrc/phx_dec.c on the integers
@@ -416,6 +445,11 @@ int phx_format_tabular(int32_t n, const char *const *names, const phx_gene *gene
  * (START > STOP on the reverse strand, as the tabular writer; SCORE and MARGIN '%E'; CALLED 0 / 1).  Worker threads like
  * phx_format_tabular.  *text is malloc'ed (NUL-terminated), release with phx_free_text. */
 int phx_format_margins(int32_t n, const char *const *names, const phx_orf_margin *rec, const int64_t *offsets, const int32_t *status, char **text, int64_t *text_len);
+/* --drop-margins FILE of the CLI for n contigs from the flat arrays of phx_drop_margins_flat: per contig with status >= 0 "#id:\t<name>",
+ * the header "#START\tSTOP\tFRAME\tCONTIG\tSCORE\tDROP\tCALLED", then one row per record in the given order (START > STOP on the reverse
+ * strand; SCORE and DROP '%E'; CALLED 0 / 1).  Worker threads like phx_format_tabular.  *text is malloc'ed (NUL-terminated), release
+ * with phx_free_text. */
+int phx_format_drops(int32_t n, const char *const *names, const phx_gene_drop *rec, const int64_t *offsets, const int32_t *status, char **text, int64_t *text_len);
 void phx_free_text(char *text);
 
 #ifdef __cplusplus

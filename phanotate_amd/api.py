@@ -367,6 +367,34 @@ class Annotator:
         self._chk(self.L.phx_margins_ms(self.h, ms), "phx_margins_ms")
         return dict(zip(("transpose", "reverse", "margins", "download"), [float(x) for x in ms]))
 
+    def drop_margins(self):
+        """(status int32[n], offsets int64[n+1], records structured array[total] of _lib.DROP_DT): the drop margin of every CDS gene of
+        the device path of every contig of the batch last run (phx_drop_margins_flat), in path order.  drop = float(D_{-g} - D) / 1000,
+        D_{-g} the shortest source -> target distance without the gene's stop node (+inf with bypass = 0 where no path avoids it);
+        called = 1 for the genes download_flat() delivers; status as phx_drop_margins_flat reports it (!= 0: no records)."""
+        n = self.n
+        offs = np.zeros(n + 1, np.int64)
+        status = np.zeros(max(n, 1), np.int32)
+        total = C.c_int64(0)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._chk(self.L.phx_drop_margins_flat(self.h, None, 0, vp(offs), vp(status), C.byref(total)), "phx_drop_margins_flat")
+        rec = np.empty(max(int(total.value), 1), _lib.DROP_DT)
+        self._chk(self.L.phx_drop_margins_flat(self.h, vp(rec), len(rec), vp(offs), vp(status), C.byref(total)), "phx_drop_margins_flat")
+        return status[:n], offs, rec[: int(total.value)]
+
+    def drop_ms(self):
+        """Device time of the last drop-margins computation in ms: trees + labels, candidates, fixups, copy to the host (phx_drop_ms)."""
+        ms = (C.c_float * 4)()
+        self._chk(self.L.phx_drop_ms(self.h, ms), "phx_drop_ms")
+        return dict(zip(("trees", "candidates", "fixups", "download"), [float(x) for x in ms]))
+
+    def drop_stats(self):
+        """Counters of the last drop-margins computation (phx_drop_stats): gene slots, slots with cross nodes, saturated slots rescanned
+        exactly, contigs whose trees were built layer by layer."""
+        out = (C.c_int64 * 4)()
+        self._chk(self.L.phx_drop_stats(self.h, out), "phx_drop_stats")
+        return dict(zip(("slots", "cross", "rescanned", "layered"), [int(x) for x in out]))
+
     # ---- solver alone (fastpathz boundary) ----
     def solve(self, V, src, dst, weights, source, target, n_limbs=None):
         """Exact shortest path over integer weights (python ints).  Returns (path node ids, distance) or ([], None)."""

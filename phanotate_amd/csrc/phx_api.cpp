@@ -225,6 +225,16 @@ struct phx_ctx {
     std::vector<DGrp> mgrp;          // the group records (reference order of the ORFs)
     hipEvent_t mev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     float margins_ms[4] = {0, 0, 0, 0};
+    bool rev_done = false;           // the margins' shared part (out-edge CSR, d_t, mstat) of the run whose results the context holds
+    float rev_ms[2] = {0, 0};        // ... its device time: out-edge CSR, reverse pass
+    // gene drop margins (phx_drop_margins_flat): buffers allocated at the first call, results kept until the next run
+    DevBuf b_dpi, b_djs, b_djt, b_dfi, b_dla, b_dslot, b_dgtab, b_doff, b_dsx, b_dcx, b_dda, b_ddb, b_drec, b_dstats;
+    bool drops_done = false;
+    phx_gene_drop *h_drec = nullptr; size_t h_drec_cap = 0; // pinned: the device's records (a record per pair of the path)
+    std::vector<int64_t> droff;      // per contig (+1): first record in h_drec
+    hipEvent_t dev_[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    float drop_ms[4] = {0, 0, 0, 0};
+    int64_t drop_stats[4] = {0, 0, 0, 0};
     float stage_ms[PHX_N_STAGES] = {0};
     int stage_n[PHX_N_STAGES] = {0};
     std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;
@@ -438,7 +448,7 @@ int set_batch_layout(phx_ctx *c, int32_t n, const int64_t *len_or_null, const in
     c->uploaded = false; c->ran = false; c->graph_valid = false; c->n = 0; // whatever fails below leaves the context without a batch
     c->meta_stale = false;
     c->has_trna = false; c->h_tnode.clear();
-    c->margins_done = false;
+    c->margins_done = false; c->rev_done = false; c->drops_done = false;
     if (n < 0) return PHX_E_ARG;
     if (!c->meta.assign((size_t)n)) { c->err = "hipHostMalloc failed"; return PHX_E_NOMEM; }
     c->ftab.clear(); c->vtotal = 0;
@@ -691,10 +701,13 @@ void phx_destroy(phx_ctx *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     DevBuf *all[] = {&c->b_eref, &c->b_cint, &c->b_csig, &c->b_meta0, &c->b_tie, &c->b_ekey, &c->b_tnode, &c->b_tedge, &c->b_tnid, &c->b_tbits, &c->b_win, &c->b_wrole, &c->b_bridge, &c->b_recs, &c->b_meta, &c->b_tiles, &c->b_nbits, &c->b_nbase, &c->b_cbits, &c->b_orf, &c->b_ostat, &c->b_oweight, &c->b_owi, &c->b_oflag, &c->b_ewf, &c->b_esrcf, &c->b_onode, &c->b_grp, &c->b_bits, &c->b_cpre, &c->b_bpre, &c->b_item, &c->b_iprev,
                      &c->b_node, &c->b_parent, &c->b_inoff, &c->b_no, &c->b_npos, &c->b_ehit, &c->b_mreach, &c->b_olist, &c->b_dist, &c->b_esrc, &c->b_ew, &c->b_ewl, &c->b_path, &c->b_genes, &c->b_gtot, &c->b_tot, &c->b_lpart, &c->b_res, &c->b_sord, &c->b_gtab, &c->b_erank, &c->b_swin, &c->b_swrole, &c->b_sdist, &c->b_segw,
-                     &c->b_mo, &c->b_md, &c->b_mw, &c->b_mdt, &c->b_mrec, &c->b_mstat};
+                     &c->b_mo, &c->b_md, &c->b_mw, &c->b_mdt, &c->b_mrec, &c->b_mstat,
+                     &c->b_dpi, &c->b_djs, &c->b_djt, &c->b_dfi, &c->b_dla, &c->b_dslot, &c->b_dgtab, &c->b_doff, &c->b_dsx, &c->b_dcx, &c->b_dda, &c->b_ddb, &c->b_drec, &c->b_dstats};
     for (DevBuf *b : all) release(*b);
     if (c->h_mrec) (void)hipHostFree(c->h_mrec);
+    if (c->h_drec) (void)hipHostFree(c->h_drec);
     for (hipEvent_t e : c->mev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->dev_) if (e) (void)hipEventDestroy(e);
     if (c->graph_exec) (void)hipGraphExecDestroy(c->graph_exec);
     if (c->graph) (void)hipGraphDestroy(c->graph);
     if (c->h_tot) (void)hipHostFree(c->h_tot);
@@ -1264,7 +1277,7 @@ int push_layout(phx_ctx *c) {
 int launch_once(phx_ctx *c, bool learn) {
     int rc;
     c->tapw_valid = false; c->cert_done = false; c->exact_done = false; c->exact_genes.clear(); c->exact_failed = 0; c->host_only.clear();
-    c->margins_done = false;
+    c->margins_done = false; c->rev_done = false; c->drops_done = false;
     hipStream_t s = c->stream;
     c->eager_now = c->eager_done && !c->meta0_dirty && !c->tiles_dirty; // the first launch after such an upload only: a repeated or retried run does everything
     c->eager_done = false;
@@ -2096,19 +2109,30 @@ int phx_tap_dist(phx_ctx *c, int32_t contig, uint64_t *dist_limbs, int64_t cap_w
 }
 
 // ---- per-ORF path margins (phx_margins.inc) ----
-// The device's records of every ORF of the batch (device order) into c->h_mrec and the reverse pass's per-contig verdicts into c->mstat,
-// once per run: kernel by kernel on the context's stream, outside the captured run graph.
-static int ensure_margins(phx_ctx *c) {
-    if (c->margins_done) return PHX_OK;
-    { const int rf = fetch_meta(c); if (rf) return rf; }
-    const size_t n = (size_t)c->n, V = (size_t)c->tot_node, E = (size_t)c->tot_edge, N = (size_t)c->tot_orf, G = (size_t)c->tot_grp;
-    const size_t limbs = (size_t)std::max(c->n_limbs, 2);
-    int nlm = 0; // limb classes of the contigs that have device distances
-    for (size_t i = 0; i < n; i++) {
+// limb classes of the contigs that have device distances (bit k: 2, 4, 8, 17 limbs)
+static int margins_nl_mask(const phx_ctx *c) {
+    int nlm = 0;
+    for (size_t i = 0; i < (size_t)c->n; i++) {
         const DMeta &m = c->meta[i];
         if (m.status < 0 || m.n_node <= 2 || m.sssp_mode == 4) continue;
         nlm |= m.sssp_nl == 2 ? 1 : m.sssp_nl == 4 ? 2 : m.sssp_nl == 8 ? 4 : 8;
     }
+    return nlm;
+}
+
+static void margins_args(phx_ctx *c, DMarg *g) {
+    g->out_off = (uint32_t *)c->b_mo.p; g->out_dst = (uint32_t *)c->b_md.p; g->out_w = (long long *)c->b_mw.p;
+    g->dist_t = (uint64_t *)c->b_mdt.p; g->rec = (phx_orf_margin *)c->b_mrec.p; g->mstat = (int32_t *)c->b_mstat.p;
+}
+
+// The shared part of the margins and the drop margins, once per run: the out-edge CSR, d_t and the reverse pass's per-contig verdicts
+// (c->mstat), kernel by kernel on the context's stream, outside the captured run graph.
+static int ensure_rev(phx_ctx *c) {
+    if (c->rev_done) return PHX_OK;
+    { const int rf = fetch_meta(c); if (rf) return rf; }
+    const size_t n = (size_t)c->n, V = (size_t)c->tot_node, E = (size_t)c->tot_edge, N = (size_t)c->tot_orf;
+    const size_t limbs = (size_t)std::max(c->n_limbs, 2);
+    const int nlm = margins_nl_mask(c);
     int rc;
     if ((rc = ensure(c, c->b_mo, (V + n + 1) * 4))) return rc;
     if ((rc = ensure(c, c->b_md, (E + 1) * 4))) return rc;
@@ -2116,21 +2140,12 @@ static int ensure_margins(phx_ctx *c) {
     if ((rc = ensure(c, c->b_mdt, (V + 1) * limbs * 8))) return rc;
     if ((rc = ensure(c, c->b_mrec, (N + 1) * sizeof(phx_orf_margin)))) return rc;
     if ((rc = ensure(c, c->b_mstat, (n + 1) * 4))) return rc;
-    if (c->h_mrec_cap < N + 1) {
-        if (c->h_mrec) HIPCHK(c, hipHostFree(c->h_mrec));
-        c->h_mrec = nullptr; c->h_mrec_cap = 0;
-        const size_t cap = N + N / 4 + 1024;
-        HIPCHK(c, hipHostMalloc((void **)&c->h_mrec, cap * sizeof(phx_orf_margin), hipHostMallocDefault));
-        c->h_mrec_cap = cap;
-    }
     for (hipEvent_t &e : c->mev) if (!e) HIPCHK(c, hipEventCreate(&e));
     c->mstat.assign(n, 0);
-    c->mgrp.resize(G);
     DBatch b;
     fill_batch(c, &b);
     DMarg g;
-    g.out_off = (uint32_t *)c->b_mo.p; g.out_dst = (uint32_t *)c->b_md.p; g.out_w = (long long *)c->b_mw.p;
-    g.dist_t = (uint64_t *)c->b_mdt.p; g.rec = (phx_orf_margin *)c->b_mrec.p; g.mstat = (int32_t *)c->b_mstat.p;
+    margins_args(c, &g);
     hipStream_t s = c->stream;
     HIPCHK(c, hipEventRecord(c->mev[0], s));
     HIPCHK(c, hipMemsetAsync(c->b_mo.p, 0, (V + n + 1) * 4, s));
@@ -2138,16 +2153,44 @@ static int ensure_margins(phx_ctx *c) {
     phxk_margins_transpose(&b, &g, s);
     HIPCHK(c, hipEventRecord(c->mev[1], s));
     phxk_sssp_rev(&b, &g, nlm, s);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->mev[2], s));
+    if (n) HIPCHK(c, hipMemcpyAsync(c->mstat.data(), c->b_mstat.p, n * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    for (int k = 0; k < 2; k++) { float ms = 0; if (hipEventElapsedTime(&ms, c->mev[k], c->mev[k + 1]) == hipSuccess) c->rev_ms[k] = ms; }
+    c->rev_done = true;
+    return PHX_OK;
+}
+
+// The device's records of every ORF of the batch (device order) into c->h_mrec, once per run, on top of ensure_rev.
+static int ensure_margins(phx_ctx *c) {
+    if (c->margins_done) return PHX_OK;
+    { const int rr = ensure_rev(c); if (rr) return rr; }
+    const size_t N = (size_t)c->tot_orf, G = (size_t)c->tot_grp;
+    const int nlm = margins_nl_mask(c);
+    if (c->h_mrec_cap < N + 1) {
+        if (c->h_mrec) HIPCHK(c, hipHostFree(c->h_mrec));
+        c->h_mrec = nullptr; c->h_mrec_cap = 0;
+        const size_t cap = N + N / 4 + 1024;
+        HIPCHK(c, hipHostMalloc((void **)&c->h_mrec, cap * sizeof(phx_orf_margin), hipHostMallocDefault));
+        c->h_mrec_cap = cap;
+    }
+    c->mgrp.resize(G);
+    DBatch b;
+    fill_batch(c, &b);
+    DMarg g;
+    margins_args(c, &g);
+    hipStream_t s = c->stream;
     HIPCHK(c, hipEventRecord(c->mev[2], s));
     phxk_margins(&b, &g, nlm, s);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->mev[3], s));
     if (N) HIPCHK(c, hipMemcpyAsync(c->h_mrec, c->b_mrec.p, N * sizeof(phx_orf_margin), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipEventRecord(c->mev[4], s));
-    if (n) HIPCHK(c, hipMemcpyAsync(c->mstat.data(), c->b_mstat.p, n * 4, hipMemcpyDeviceToHost, s));
     if (G) HIPCHK(c, hipMemcpyAsync(c->mgrp.data(), c->b_grp.p, G * sizeof(DGrp), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
-    for (int k = 0; k < 4; k++) { float ms = 0; if (hipEventElapsedTime(&ms, c->mev[k], c->mev[k + 1]) == hipSuccess) c->margins_ms[k] = ms; }
+    c->margins_ms[0] = c->rev_ms[0]; c->margins_ms[1] = c->rev_ms[1];
+    for (int k = 2; k < 4; k++) { float ms = 0; if (hipEventElapsedTime(&ms, c->mev[k], c->mev[k + 1]) == hipSuccess) c->margins_ms[k] = ms; }
     c->margins_done = true;
     return PHX_OK;
 }
@@ -2220,7 +2263,7 @@ int phx_tap_dist_target(phx_ctx *c, int32_t contig, uint64_t *dist_limbs, int64_
     if (m.status < 0 || m.n_node <= 2 || m.sssp_mode == 4) return PHX_OK;
     const size_t words = (size_t)m.n_node * (size_t)m.sssp_nl;
     if (!dist_limbs || cap_words < (int64_t)words) return PHX_E_ARG;
-    { const int rm = ensure_margins(c); if (rm) return rm; }
+    { const int rm = ensure_rev(c); if (rm) return rm; }
     HIPCHK(c, hipMemcpy(dist_limbs, (uint64_t *)c->b_mdt.p + (size_t)m.node_off * (size_t)c->n_limbs, words * 8, hipMemcpyDeviceToHost));
     return PHX_OK;
 }
@@ -2228,6 +2271,153 @@ int phx_tap_dist_target(phx_ctx *c, int32_t contig, uint64_t *dist_limbs, int64_
 int phx_margins_ms(phx_ctx *c, float *ms) {
     if (!c || !ms) return PHX_E_ARG;
     for (int k = 0; k < 4; k++) ms[k] = c->margins_ms[k];
+    return PHX_OK;
+}
+
+// ---- gene drop margins (phx_drop.inc) ----
+// the contigs the drop kernels cover (dp_contig) and their sparse-table size (k_dp_cand)
+static bool drop_contig(const phx_ctx *c, size_t i) {
+    const DMeta &m = c->meta[i];
+    return m.status >= 0 && m.n_node > 2 && m.sssp_mode != 4 && !c->mstat[i] && m.n_path >= 3;
+}
+static int64_t drop_cells(int n_path) { int lv = 1; while ((2 << (lv - 1)) <= n_path) lv++; return (int64_t)n_path * lv; }
+
+// The records of every pair of every device path into c->h_drec (at c->droff), once per run, on top of ensure_rev.
+static int ensure_drops(phx_ctx *c) {
+    if (c->drops_done) return PHX_OK;
+    { const int rr = ensure_rev(c); if (rr) return rr; }
+    const size_t n = (size_t)c->n, V = (size_t)c->tot_node;
+    const size_t limbs = (size_t)std::max(c->n_limbs, 2);
+    const int nlm = margins_nl_mask(c);
+    std::vector<int64_t> off(2 * n + 2, 0); // toff[n], roff[n + 1]
+    c->droff.assign(n + 1, 0);
+    int64_t tcells = 0, R = 0;
+    for (size_t i = 0; i < n; i++) {
+        off[n + i] = R; c->droff[i] = R;
+        if (!drop_contig(c, i)) continue;
+        const int np = c->meta[i].n_path;
+        const int64_t cells = drop_cells(np);
+        if (cells > DP_TAB_LDS) { off[i] = tcells; tcells += cells; }
+        R += (np - 1) / 2;
+    }
+    off[2 * n] = R; c->droff[n] = R;
+    int rc;
+    const size_t nv = (V + n + 1) * 4;
+    if ((rc = ensure(c, c->b_dpi, nv)) || (rc = ensure(c, c->b_djs, nv)) || (rc = ensure(c, c->b_djt, nv)) || (rc = ensure(c, c->b_dfi, nv)) || (rc = ensure(c, c->b_dla, nv))) return rc;
+    if ((rc = ensure(c, c->b_dslot, (V + 1) * 8))) return rc;
+    if ((rc = ensure(c, c->b_dgtab, ((size_t)tcells + 1) * 8))) return rc;
+    if ((rc = ensure(c, c->b_doff, (2 * n + 2) * 8))) return rc;
+    if ((rc = ensure(c, c->b_dsx, ((size_t)R + 1) * limbs * 8)) || (rc = ensure(c, c->b_dcx, ((size_t)R + 1) * limbs * 8))) return rc;
+    if ((rc = ensure(c, c->b_dda, (V + 1) * limbs * 8)) || (rc = ensure(c, c->b_ddb, (V + 1) * limbs * 8))) return rc;
+    if ((rc = ensure(c, c->b_drec, ((size_t)R + 1) * sizeof(phx_gene_drop)))) return rc;
+    if ((rc = ensure(c, c->b_dstats, 4 * 8))) return rc;
+    if (c->h_drec_cap < (size_t)R + 1) {
+        if (c->h_drec) HIPCHK(c, hipHostFree(c->h_drec));
+        c->h_drec = nullptr; c->h_drec_cap = 0;
+        const size_t cap = (size_t)R + (size_t)R / 4 + 1024;
+        HIPCHK(c, hipHostMalloc((void **)&c->h_drec, cap * sizeof(phx_gene_drop), hipHostMallocDefault));
+        c->h_drec_cap = cap;
+    }
+    for (hipEvent_t &e : c->dev_) if (!e) HIPCHK(c, hipEventCreate(&e));
+    DBatch b;
+    fill_batch(c, &b);
+    DMarg g;
+    margins_args(c, &g);
+    DDrop q;
+    q.pidx = (int32_t *)c->b_dpi.p; q.js = (int32_t *)c->b_djs.p; q.jt = (int32_t *)c->b_djt.p; q.first = (int32_t *)c->b_dfi.p; q.last = (int32_t *)c->b_dla.p;
+    q.slot = (uint64_t *)c->b_dslot.p; q.gtab = (uint64_t *)c->b_dgtab.p;
+    q.toff = (const int64_t *)c->b_doff.p; q.roff = (const int64_t *)c->b_doff.p + n;
+    q.sx = (uint64_t *)c->b_dsx.p; q.cx = (uint64_t *)c->b_dcx.p; q.da = (uint64_t *)c->b_dda.p; q.db = (uint64_t *)c->b_ddb.p;
+    q.rec = (phx_gene_drop *)c->b_drec.p; q.stats = (unsigned long long *)c->b_dstats.p;
+    const char *ly = getenv("PHX_DROP_LAYERED");
+    q.layered = ly && *ly && strcmp(ly, "0") != 0 ? 1 : 0;
+    hipStream_t s = c->stream;
+    unsigned long long st[4] = {0, 0, 0, 0};
+    HIPCHK(c, hipEventRecord(c->dev_[0], s));
+    HIPCHK(c, hipMemcpyAsync(c->b_doff.p, off.data(), (2 * n + 2) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(c->b_dstats.p, 0, 4 * 8, s));
+    phxk_drop_trees(&b, &g, &q, nlm, s);
+    HIPCHK(c, hipEventRecord(c->dev_[1], s));
+    phxk_drop_cand(&b, &g, &q, nlm, s);
+    HIPCHK(c, hipEventRecord(c->dev_[2], s));
+    phxk_drop_fix(&b, &g, &q, nlm, s);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->dev_[3], s));
+    if (R) HIPCHK(c, hipMemcpyAsync(c->h_drec, c->b_drec.p, (size_t)R * sizeof(phx_gene_drop), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipEventRecord(c->dev_[4], s));
+    HIPCHK(c, hipMemcpyAsync(st, c->b_dstats.p, sizeof st, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    for (int k = 0; k < 4; k++) { float ms = 0; if (hipEventElapsedTime(&ms, c->dev_[k], c->dev_[k + 1]) == hipSuccess) c->drop_ms[k] = ms; c->drop_stats[k] = (int64_t)st[k]; }
+    c->drops_done = true;
+    return PHX_OK;
+}
+
+int phx_drop_margins_flat(phx_ctx *c, phx_gene_drop *rec, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
+    if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
+    if (c->in_flight) { const int rs = phx_wait(c); if (rs) return rs; }
+    if (!c->ran) return PHX_E_STATE;
+    HIPCHK(c, hipSetDevice(c->device));
+    { const int rx = ensure_exact(c); if (rx) return rx; } // `called` is against the genes phx_download* deliver
+    { const int rd = ensure_drops(c); if (rd) return rd; }
+    try {
+    // the gene pairs of every contig with records (status 0): the pairs of the device path that are CDS genes
+    auto genes_of = [&](int i) -> int64_t {
+        int64_t k = 0;
+        for (int64_t r = c->droff[(size_t)i]; r < c->droff[(size_t)i + 1]; r++) k += c->h_drec[r].called >= 0;
+        return k;
+    };
+    int64_t total = 0;
+    for (int i = 0; i < c->n; i++) {
+        offsets[i] = total;
+        status[i] = margins_status(c, i);
+        if (status[i] == 0 && drop_contig(c, (size_t)i)) total += genes_of(i);
+    }
+    offsets[c->n] = total;
+    if (total_out) *total_out = total;
+    if (!rec) return PHX_OK; // size query
+    if (cap < total) return PHX_E_ARG;
+    // the delivered genes (as phx_download_flat: the host re-solve's where there was one)
+    int64_t hi = 0;
+    for (int i = 0; i < c->n; i++) { const DRes &m = c->res[(size_t)i]; hi = std::max<int64_t>(hi, m.gene_off + m.n_genes); }
+    { const int rg = ensure_gene_stage(c, (size_t)hi); if (rg) return rg; }
+    if (hi) {
+        HIPCHK(c, hipMemcpyAsync(c->h_genes, (const DGene *)c->b_genes.p + (gene_pack(c) ? gene_half(c) : 0), sizeof(DGene) * (size_t)hi, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    std::vector<uint64_t> keys;
+    auto key = [](int32_t left, int32_t right, int32_t strand) { return ((uint64_t)(uint32_t)left << 33) | ((uint64_t)(uint32_t)right << 1) | (strand < 0 ? 1u : 0u); };
+    for (int i = 0; i < c->n; i++) {
+        if (offsets[i + 1] == offsets[i]) continue;
+        const DRes &r = c->res[(size_t)i];
+        const DGene *src = c->h_genes + (size_t)r.gene_off;
+        int64_t ng = r.n_genes;
+        const auto ex = c->exact_genes.find(i);
+        if (ex != c->exact_genes.end()) { src = ex->second.data(); ng = (int64_t)ex->second.size(); }
+        keys.clear();
+        for (int64_t k = 0; k < ng; k++) if (src[k].frame >= -3 && src[k].frame <= 3) keys.push_back(key(src[k].left, src[k].right, src[k].strand));
+        std::sort(keys.begin(), keys.end());
+        phx_gene_drop *dst = rec + offsets[i];
+        for (int64_t k = c->droff[(size_t)i]; k < c->droff[(size_t)i + 1]; k++) {
+            const phx_gene_drop &x = c->h_drec[k];
+            if (x.called < 0) continue;
+            *dst = x;
+            dst->called = std::binary_search(keys.begin(), keys.end(), key(x.left, x.right, x.strand)) ? 1 : 0;
+            dst++;
+        }
+    }
+    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_drop_margins_flat"; return PHX_E_NOMEM; }
+    return PHX_OK;
+}
+
+int phx_drop_ms(phx_ctx *c, float *ms) {
+    if (!c || !ms) return PHX_E_ARG;
+    for (int k = 0; k < 4; k++) ms[k] = c->drop_ms[k];
+    return PHX_OK;
+}
+
+int phx_drop_stats(phx_ctx *c, int64_t *out) {
+    if (!c || !out) return PHX_E_ARG;
+    for (int k = 0; k < 4; k++) out[k] = c->drop_stats[k];
     return PHX_OK;
 }
 

@@ -1,0 +1,455 @@
+// phx_drop.inc — gene drop margins: the exact cost of removing each called gene (included by phx_kernels.hip, after phx_margins.inc).
+// ------------------------------------------------------------------------------------------------
+// On demand after a run and after the margins' shared part (out-edge CSR, d_t: phx_margins.inc), never inside a run.  For one contig with
+// the device path P = p_0 (source) ... p_K (target), D = d_s(target), and a CDS gene of P whose stop node is p_j (p_{j+1} of a forward gene
+// start -> stop, p_j of a reverse gene stop -> start), D_{-g} is the shortest source -> target distance in G without p_j; the record carries
+// float(D_{-g} - D) / 1000 (DESIGN.md §12).
+//
+//   1. k_dp_tree: two shortest-path trees that contain P — T_s (lowest-index tight in-edge) and T_t (tight out-edge to the smallest head id) —
+//      and the labels first(x) (index of the P node x's T_s chain leaves P at) and last(z) (index of the P node z's T_t chain joins P at),
+//      by pointer doubling; a chain that does not reach P (tight edges closing a zero-length cycle) rebuilds that tree layer by layer.
+//   2. k_dp_cand: every edge x -> z with first(x) + 1 <= last(z) - 1 bounds the slots between them by d_s(x) + W + d_t(z) - D: range
+//      minimum by a two-entry sparse table (64-bit atomicMin, saturated at 2^63), pushed down level by level.
+//   3. k_dp_rescan: a gene slot whose minimum saturated is recomputed exactly, one wavefront over the candidates that cover it.
+//   4. k_dp_cross: the nodes y with last(y) <= j <= first(y) (they lie on a cycle through p_j): Bellman-Ford inside that set, seeded from the
+//      edges x -> y with first(x) < j, leaving by edges y -> z with last(z) > j.
+//   5. k_dp_rec: one record per gene pair of P.
+// Widths: d_s, d_t, |W| and D are each below B (|B| < 2^(64 NL - 5), DESIGN.md §11), so a candidate of step 3 is below 4B in magnitude; a
+// settled delta of step 4 is a seed d_s(x) + W plus a simple path inside Y_j (below 3B), its candidates below 6B: the contig's own NL limbs
+// hold every value in two's complement.
+
+#define DP_SAT (1ull << 63)      // a range minimum >= 2^63: recomputed exactly (k_dp_rescan)
+#define DP_NONE (~0ull)          // no candidate covers the slot
+#define DP_CROSS_LDS 64          // cross nodes whose two delta buffers live in LDS; beyond: DDrop.da / db
+
+// the contigs the pass covers: device distances, a settled reverse pass, a path with at least one pair
+__device__ __forceinline__ bool dp_contig(const DBatch &b, const DMarg &g, const DMeta *meta) {
+    return mg_contig(meta) && !g.mstat[meta - b.meta] && meta->n_path >= 3;
+}
+
+// pair i of P (path[2i+1] -> path[2i+2], the genes of file_handling.pairwise): a CDS gene?  *j its stop node's index on P, *k its ORF
+__device__ __forceinline__ bool dp_gene(const DBatch &b, const DMeta *meta, const int32_t *path, int i, int *j, int *k) {
+    const DNode *nd = b.node + meta->node_off;
+    const DOrf *orf = b.orf + meta->orf_off;
+    const DGrp *grp = b.grp + meta->grp_off;
+    const int a = path[2 * i + 1], bb = path[2 * i + 2];
+    const int ta = NTYPE(nd[a].info), fr = NFRAME(nd[a].info);
+    if (ta == 0 && fr > 0 && fr <= 3 && LINK_KIND(nd[a].link) == LINK_START) {
+        const int o = (int)LINK_IDX(nd[a].link);
+        if (grp[orf[o].grp].node == bb) { *j = 2 * i + 2; *k = o; return true; }
+    } else if (ta == 1 && fr < 0 && fr >= -3 && LINK_KIND(nd[bb].link) == LINK_START) {
+        const int o = (int)LINK_IDX(nd[bb].link);
+        if (grp[orf[o].grp].node == a) { *j = 2 * i + 1; *k = o; return true; }
+    }
+    return false;
+}
+
+template <int NL>
+__device__ __forceinline__ WInt<NL> wi_from_u64(uint64_t x) {
+    WInt<NL> r;
+    r.v[0] = x;
+#pragma unroll
+    for (int i = 1; i < NL; i++) r.v[i] = 0;
+    return r;
+}
+// a non-negative candidate as a 64-bit key: itself below 2^63, else DP_SAT
+template <int NL>
+__device__ __forceinline__ uint64_t wi_sat64(const WInt<NL> &x) {
+    bool big = (x.v[0] >> 63) != 0;
+#pragma unroll
+    for (int i = 1; i < NL; i++) big = big || x.v[i] != 0;
+    return big ? DP_SAT : x.v[0];
+}
+// minimum over the 64 lanes of a wavefront (every lane gets it)
+template <int NL>
+__device__ __forceinline__ WInt<NL> wave_min(WInt<NL> x) {
+    for (int m = 32; m >= 1; m >>= 1) {
+        WInt<NL> y;
+#pragma unroll
+        for (int i = 0; i < NL; i++) y.v[i] = (uint64_t)__shfl_xor((unsigned long long)x.v[i], m);
+        if (wi_lt<NL>(y, x)) x = y;
+    }
+    return x;
+}
+__device__ __forceinline__ uint64_t ld_l2(const uint64_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// ---- 1. k_dp_tree<NL>: trees and labels, one workgroup per contig ----
+// DDrop.js / jt: the jump pointers (a node on P points at itself; -1: unreached), then first / last.  The doubling reads and writes js in
+// place: a value read mid-round is a later ancestor on the same chain, so the rounds only get shorter.  ceil(log2 V) + 1 rounds reach P from
+// any chain that reaches it at all; a node whose pointer is then still off P sits on a tight zero-length cycle of the chosen parents, and
+// the tree is rebuilt by layers: round r lets a node join through a tight edge to a node that joined before round r (P itself is layer 0),
+// which cannot close a cycle.  DDrop.layered forces the layered build (env PHX_DROP_LAYERED, the tests).
+template <int NL>
+__global__ __launch_bounds__(NT) void k_dp_tree(DBatch b, DMarg g, DDrop q) {
+    __shared__ int s_fail[2], s_chg;
+    const DMeta *meta = &b.meta[blockIdx.x];
+    if (!dp_contig(b, g, meta) || meta->sssp_nl != NL) return;
+    const int V = meta->n_node, n = meta->n_path, tid = threadIdx.x;
+    const size_t no = (size_t)meta->node_off;
+    const int32_t *path = b.path + no;
+    const uint32_t *in_off = b.in_off + no + blockIdx.x;
+    const uint32_t *esrc = b.esrc + meta->edge_off;
+    const long long *ew = b.ew + meta->edge_off;
+    const long long *gt = gtab_of(b, meta);
+    const uint32_t *oo = g.out_off + no + blockIdx.x;
+    const uint32_t *od = g.out_dst + meta->edge_off;
+    const long long *ow = g.out_w + meta->edge_off;
+    const uint64_t *ds = b.dist + no * b.dist_stride;
+    const uint64_t *dt = g.dist_t + no * b.dist_stride;
+    int32_t *pidx = q.pidx + no, *js = q.js + no, *jt = q.jt + no, *first = q.first + no, *last = q.last + no;
+    for (int v = tid; v < V; v += NT) pidx[v] = -1;
+    if (tid < 2) s_fail[tid] = q.layered;
+    __syncthreads();
+    for (int j = tid; j < n; j += NT) pidx[path[j]] = j;
+    __syncthreads();
+    // parents / successors
+    for (int v = tid; v < V; v += NT) {
+        int ps = -1, ts = -1;
+        if (pidx[v] >= 0) ps = ts = v;
+        else {
+            const WInt<NL> dv = wi_load<NL>(ds + (size_t)v * NL);
+            if (!wi_unreached<NL>(dv)) {
+                ps = -2; // (a reached node without a tight in-edge cannot occur: the layered build then leaves it out)
+                for (uint32_t e = in_off[v], e1 = in_off[v + 1]; e < e1; e++) {
+                    const uint32_t sw = esrc[e];
+                    const WInt<NL> du = wi_load<NL>(ds + (size_t)ESRC_NODE(sw) * NL);
+                    if (!wi_unreached<NL>(du) && wi_eq<NL>(wi_add<NL>(du, ew_decode<NL>(edge_wenc(sw, ew, e, gt))), dv)) { ps = (int)ESRC_NODE(sw); break; }
+                }
+            }
+            const WInt<NL> tv = wi_load<NL>(dt + (size_t)v * NL);
+            if (!wi_unreached<NL>(tv)) {
+                ts = -2;
+                for (uint32_t e = oo[v], e1 = oo[v + 1]; e < e1; e++) {
+                    const int z = (int)od[e];
+                    if (ts >= 0 && z >= ts) continue;
+                    const WInt<NL> tz = wi_load<NL>(dt + (size_t)z * NL);
+                    if (!wi_unreached<NL>(tz) && wi_eq<NL>(wi_add<NL>(tz, ew_decode<NL>(ow[e])), tv)) ts = z;
+                }
+            }
+        }
+        js[v] = ps; jt[v] = ts;
+        if (ps == -2) s_fail[0] = 1;
+        if (ts == -2) s_fail[1] = 1;
+    }
+    __syncthreads();
+    int rounds = 1;
+    for (int x = V; x > 1; x = (x + 1) >> 1) rounds++;
+    for (int r = 0; r < rounds; r++) {
+        for (int v = tid; v < V; v += NT) {
+            const int a = js[v], c = jt[v];
+            if (a >= 0 && pidx[a] < 0) js[v] = js[a];
+            if (c >= 0 && pidx[c] < 0) jt[v] = jt[c];
+        }
+        __syncthreads();
+    }
+    for (int v = tid; v < V; v += NT) {
+        const int a = js[v], c = jt[v];
+        if (a == -2 || (a >= 0 && pidx[a] < 0)) s_fail[0] = 1;
+        if (c == -2 || (c >= 0 && pidx[c] < 0)) s_fail[1] = 1;
+        first[v] = a >= 0 ? pidx[a] : -1;
+        last[v] = c >= 0 ? pidx[c] : -1;
+    }
+    __syncthreads();
+    const bool fs = s_fail[0] != 0, ft = s_fail[1] != 0;
+    if (!fs && !ft) return;
+    if (tid == 0) atomicAdd(&q.stats[3], 1ull);
+    // layered rebuild of the tree(s) that failed: js / jt now hold the layer a node joined in (0: P; INT_MAX: not yet, or unreached)
+    for (int v = tid; v < V; v += NT) {
+        if (fs) { js[v] = pidx[v] >= 0 ? 0 : 0x7fffffff; if (pidx[v] < 0) first[v] = -1; }
+        if (ft) { jt[v] = pidx[v] >= 0 ? 0 : 0x7fffffff; if (pidx[v] < 0) last[v] = -1; }
+    }
+    __syncthreads();
+    for (int r = 1; r <= V + 1; r++) {
+        if (tid == 0) s_chg = 0;
+        __syncthreads();
+        for (int v = tid; v < V; v += NT) {
+            if (fs && js[v] == 0x7fffffff) {
+                const WInt<NL> dv = wi_load<NL>(ds + (size_t)v * NL);
+                if (!wi_unreached<NL>(dv))
+                    for (uint32_t e = in_off[v], e1 = in_off[v + 1]; e < e1; e++) {
+                        const uint32_t sw = esrc[e];
+                        const int u = (int)ESRC_NODE(sw);
+                        if (js[u] >= r) continue;
+                        const WInt<NL> du = wi_load<NL>(ds + (size_t)u * NL);
+                        if (!wi_unreached<NL>(du) && wi_eq<NL>(wi_add<NL>(du, ew_decode<NL>(edge_wenc(sw, ew, e, gt))), dv)) {
+                            first[v] = first[u]; js[v] = r; s_chg = 1;
+                            break;
+                        }
+                    }
+            }
+            if (ft && jt[v] == 0x7fffffff) {
+                const WInt<NL> tv = wi_load<NL>(dt + (size_t)v * NL);
+                if (!wi_unreached<NL>(tv)) {
+                    int best = -1;
+                    for (uint32_t e = oo[v], e1 = oo[v + 1]; e < e1; e++) {
+                        const int z = (int)od[e];
+                        if ((best >= 0 && z >= best) || jt[z] >= r) continue;
+                        const WInt<NL> tz = wi_load<NL>(dt + (size_t)z * NL);
+                        if (!wi_unreached<NL>(tz) && wi_eq<NL>(wi_add<NL>(tz, ew_decode<NL>(ow[e])), tv)) best = z;
+                    }
+                    if (best >= 0) { last[v] = last[best]; jt[v] = r; s_chg = 1; }
+                }
+            }
+        }
+        __syncthreads();
+        if (!s_chg) break;
+        __syncthreads();
+    }
+}
+
+// ---- 2. k_dp_cand<NL>: candidates and the sparse table, one workgroup per contig ----
+// Level k holds n entries; entry i covers slots [i, i + 2^k).  A candidate for the open range (first(x), last(z)) = slots [a, z] goes to
+// level floor(log2(z - a + 1)) at both ends.  The push-down gathers: level k-1 entry i takes the minimum of level k at i and at i - 2^(k-1).
+// The atomics stay per contig: in LDS up to DP_TAB_LDS entries, else in the contig's own slice of DDrop.gtab (read back through L2).
+template <int NL>
+__global__ __launch_bounds__(NT) void k_dp_cand(DBatch b, DMarg g, DDrop q) {
+    __shared__ unsigned long long s_tab[DP_TAB_LDS];
+    const DMeta *meta = &b.meta[blockIdx.x];
+    if (!dp_contig(b, g, meta) || meta->sssp_nl != NL) return;
+    const int V = meta->n_node, n = meta->n_path, tid = threadIdx.x;
+    const size_t no = (size_t)meta->node_off;
+    const uint32_t *in_off = b.in_off + no + blockIdx.x;
+    const uint32_t *esrc = b.esrc + meta->edge_off;
+    const long long *ew = b.ew + meta->edge_off;
+    const long long *gt = gtab_of(b, meta);
+    const uint64_t *ds = b.dist + no * b.dist_stride;
+    const uint64_t *dt = g.dist_t + no * b.dist_stride;
+    const int32_t *first = q.first + no, *last = q.last + no;
+    int lv = 1;
+    while ((2 << (lv - 1)) <= n) lv++; // floor(log2 n) + 1
+    const int cells = n * lv;
+    unsigned long long *tab = cells <= DP_TAB_LDS ? s_tab : (unsigned long long *)(q.gtab + q.toff[blockIdx.x]);
+    for (int i = tid; i < cells; i += NT) tab[i] = DP_NONE;
+    __syncthreads();
+    const WInt<NL> negD = wi_neg<NL>(wi_load<NL>(ds + (size_t)(V - 1) * NL));
+    for (int z = tid; z < V; z += NT) {
+        const int lz = last[z];
+        if (lz < 2) continue; // (no slot strictly between first(x) >= 0 and last(z))
+        const WInt<NL> tz = wi_add<NL>(wi_load<NL>(dt + (size_t)z * NL), negD);
+        for (uint32_t e = in_off[z], e1 = in_off[z + 1]; e < e1; e++) {
+            const uint32_t sw = esrc[e];
+            const int x = (int)ESRC_NODE(sw);
+            const int fx = first[x];
+            if (fx < 0 || fx + 1 > lz - 1) continue;
+            const int a = fx + 1, len = lz - 1 - a + 1;
+            const WInt<NL> c = wi_add<NL>(wi_add<NL>(wi_load<NL>(ds + (size_t)x * NL), ew_decode<NL>(edge_wenc(sw, ew, e, gt))), tz);
+            const unsigned long long key = wi_sat64<NL>(c);
+            const int k = 31 - __clz(len);
+            atomicMin(&tab[k * n + a], key);
+            atomicMin(&tab[k * n + (lz - 1) - (1 << k) + 1], key);
+        }
+    }
+    __syncthreads();
+    for (int k = lv - 1; k >= 1; k--) {
+        const int h = 1 << (k - 1);
+        for (int i = tid; i < n; i += NT) {
+            uint64_t m = ld_l2((const uint64_t *)&tab[k * n + i]);
+            if (i >= h) { const uint64_t m2 = ld_l2((const uint64_t *)&tab[k * n + i - h]); m = m2 < m ? m2 : m; }
+            if (m != DP_NONE) atomicMin(&tab[(k - 1) * n + i], (unsigned long long)m);
+        }
+        __syncthreads();
+    }
+    uint64_t *slot = q.slot + no;
+    for (int i = tid; i < n; i += NT) slot[i] = ld_l2((const uint64_t *)&tab[i]);
+}
+
+// ---- 3. k_dp_rescan<NL>: the gene slots whose range minimum saturated, exactly; a wavefront per slot ----
+template <int NL>
+__global__ __launch_bounds__(NT) void k_dp_rescan(DBatch b, DMarg g, DDrop q) {
+    const DMeta *meta = &b.meta[blockIdx.x];
+    if (!dp_contig(b, g, meta) || meta->sssp_nl != NL) return;
+    const int V = meta->n_node, np = (meta->n_path - 1) / 2;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const size_t no = (size_t)meta->node_off;
+    const int32_t *path = b.path + no;
+    const uint32_t *in_off = b.in_off + no + blockIdx.x;
+    const uint32_t *esrc = b.esrc + meta->edge_off;
+    const long long *ew = b.ew + meta->edge_off;
+    const long long *gt = gtab_of(b, meta);
+    const uint64_t *ds = b.dist + no * b.dist_stride;
+    const uint64_t *dt = g.dist_t + no * b.dist_stride;
+    const int32_t *first = q.first + no, *last = q.last + no;
+    const uint64_t *slot = q.slot + no;
+    const WInt<NL> negD = wi_neg<NL>(wi_load<NL>(ds + (size_t)(V - 1) * NL));
+    for (int i = wv; i < np; i += NT / 64) {
+        int j, k;
+        if (!dp_gene(b, meta, path, i, &j, &k) || slot[j] != DP_SAT) continue;
+        WInt<NL> best = wi_inf<NL>();
+        for (int z = lane; z < V; z += 64) {
+            if (last[z] <= j) continue;
+            const WInt<NL> tz = wi_add<NL>(wi_load<NL>(dt + (size_t)z * NL), negD);
+            for (uint32_t e = in_off[z], e1 = in_off[z + 1]; e < e1; e++) {
+                const uint32_t sw = esrc[e];
+                const int x = (int)ESRC_NODE(sw);
+                const int fx = first[x];
+                if (fx < 0 || fx >= j) continue;
+                const WInt<NL> c = wi_add<NL>(wi_add<NL>(wi_load<NL>(ds + (size_t)x * NL), ew_decode<NL>(edge_wenc(sw, ew, e, gt))), tz);
+                if (wi_lt<NL>(c, best)) best = c;
+            }
+        }
+        best = wave_min<NL>(best);
+        if (lane == 0) {
+            wi_store<NL>(q.sx + ((size_t)q.roff[blockIdx.x] + i) * b.dist_stride, best);
+            atomicAdd(&q.stats[2], 1ull);
+        }
+    }
+}
+
+// ---- 4. k_dp_cross<NL>: the cross nodes of each gene slot, one workgroup per contig ----
+// The cross nodes of the contig (last(y) <= first(y), off P, reached both ways) go to a list (DDrop.js reused) with their list position per
+// node (DDrop.jt reused); Y_j is the part of the list with last(y) <= j <= first(y).  Per gene slot with Y_j non-empty: delta(y) seeded from
+// the edges x -> y with first(x) < j, Jacobi rounds within Y_j on two buffers (LDS up to DP_CROSS_LDS list entries, else DDrop.da / db),
+// then the edges y -> z with last(z) > j give delta(y) + W + d_t(z) - D.  Every gene slot gets its cross minimum (inf: none) in DDrop.cx.
+template <int NL>
+__global__ __launch_bounds__(NT) void k_dp_cross(DBatch b, DMarg g, DDrop q) {
+    __shared__ uint64_t s_d[2][DP_CROSS_LDS * NL];
+    __shared__ uint64_t s_red[NT / 64][NL];
+    __shared__ int s_nc, s_any, s_chg;
+    const DMeta *meta = &b.meta[blockIdx.x];
+    if (!dp_contig(b, g, meta) || meta->sssp_nl != NL) return;
+    const int V = meta->n_node, np = (meta->n_path - 1) / 2, tid = threadIdx.x;
+    const size_t no = (size_t)meta->node_off;
+    const int32_t *path = b.path + no;
+    const uint32_t *in_off = b.in_off + no + blockIdx.x;
+    const uint32_t *esrc = b.esrc + meta->edge_off;
+    const long long *ew = b.ew + meta->edge_off;
+    const long long *gt = gtab_of(b, meta);
+    const uint32_t *oo = g.out_off + no + blockIdx.x;
+    const uint32_t *od = g.out_dst + meta->edge_off;
+    const long long *ow = g.out_w + meta->edge_off;
+    const uint64_t *ds = b.dist + no * b.dist_stride;
+    const uint64_t *dt = g.dist_t + no * b.dist_stride;
+    const int32_t *first = q.first + no, *last = q.last + no, *pidx = q.pidx + no;
+    int32_t *clist = q.js + no, *cpos = q.jt + no;
+    uint64_t *cx = q.cx + (size_t)q.roff[blockIdx.x] * b.dist_stride;
+    if (tid == 0) s_nc = 0;
+    __syncthreads();
+    for (int v = tid; v < V; v += NT) {
+        const int f = first[v], l = last[v];
+        int p = -1;
+        if (pidx[v] < 0 && f >= 0 && l >= 0 && l <= f) { p = atomicAdd(&s_nc, 1); clist[p] = v; }
+        cpos[v] = p;
+    }
+    __syncthreads();
+    const int nc = s_nc;
+    uint64_t *bufA = nc <= DP_CROSS_LDS ? s_d[0] : q.da + no * b.dist_stride, *bufB = nc <= DP_CROSS_LDS ? s_d[1] : q.db + no * b.dist_stride;
+    const WInt<NL> negD = wi_neg<NL>(wi_load<NL>(ds + (size_t)(V - 1) * NL));
+    for (int i = 0; i < np; i++) {
+        int j, k;
+        if (!dp_gene(b, meta, path, i, &j, &k)) continue; // (uniform over the workgroup)
+        if (tid == 0) s_any = 0;
+        __syncthreads();
+        for (int p = tid; p < nc; p += NT) { const int y = clist[p]; if (last[y] <= j && j <= first[y]) s_any = 1; }
+        __syncthreads();
+        const bool any = s_any != 0;
+        __syncthreads(); // (read by all before thread 0 resets it)
+        if (!any) { if (tid == 0) wi_store<NL>(cx + (size_t)i * b.dist_stride, wi_inf<NL>()); continue; }
+        if (tid == 0) atomicAdd(&q.stats[1], 1ull);
+        auto in_y = [&](int y) { return cpos[y] >= 0 && last[y] <= j && j <= first[y]; };
+        // seed
+        for (int p = tid; p < nc; p += NT) {
+            const int y = clist[p];
+            WInt<NL> d = wi_inf<NL>();
+            if (in_y(y))
+                for (uint32_t e = in_off[y], e1 = in_off[y + 1]; e < e1; e++) {
+                    const uint32_t sw = esrc[e];
+                    const int x = (int)ESRC_NODE(sw);
+                    const int fx = first[x];
+                    if (fx < 0 || fx >= j) continue;
+                    const WInt<NL> c = wi_add<NL>(wi_load<NL>(ds + (size_t)x * NL), ew_decode<NL>(edge_wenc(sw, ew, e, gt)));
+                    if (wi_lt<NL>(c, d)) d = c;
+                }
+            wi_store<NL>(bufA + (size_t)p * NL, d);
+        }
+        __syncthreads();
+        // Jacobi within Y_j (no cycle of negative length: settles in |Y_j| rounds)
+        uint64_t *cur = bufA, *nxt = bufB;
+        for (int r = 0; r <= nc + 1; r++) {
+            if (tid == 0) s_chg = 0;
+            __syncthreads();
+            for (int p = tid; p < nc; p += NT) {
+                const int y = clist[p];
+                WInt<NL> d = wi_load<NL>(cur + (size_t)p * NL);
+                if (in_y(y))
+                    for (uint32_t e = in_off[y], e1 = in_off[y + 1]; e < e1; e++) {
+                        const uint32_t sw = esrc[e];
+                        const int x = (int)ESRC_NODE(sw);
+                        if (!in_y(x)) continue;
+                        const WInt<NL> dx = wi_load<NL>(cur + (size_t)cpos[x] * NL);
+                        if (wi_is_inf<NL>(dx)) continue;
+                        const WInt<NL> c = wi_add<NL>(dx, ew_decode<NL>(edge_wenc(sw, ew, e, gt)));
+                        if (wi_lt<NL>(c, d)) { d = c; s_chg = 1; }
+                    }
+                wi_store<NL>(nxt + (size_t)p * NL, d);
+            }
+            __syncthreads();
+            uint64_t *t = cur; cur = nxt; nxt = t;
+            const bool chg = s_chg != 0;
+            __syncthreads();
+            if (!chg) break;
+        }
+        // leave Y_j
+        WInt<NL> best = wi_inf<NL>();
+        for (int p = tid; p < nc; p += NT) {
+            const int y = clist[p];
+            if (!in_y(y)) continue;
+            const WInt<NL> d = wi_load<NL>(cur + (size_t)p * NL);
+            if (wi_is_inf<NL>(d)) continue;
+            for (uint32_t e = oo[y], e1 = oo[y + 1]; e < e1; e++) {
+                const int z = (int)od[e];
+                if (last[z] <= j) continue;
+                const WInt<NL> c = wi_add<NL>(wi_add<NL>(d, ew_decode<NL>(ow[e])), wi_add<NL>(wi_load<NL>(dt + (size_t)z * NL), negD));
+                if (wi_lt<NL>(c, best)) best = c;
+            }
+        }
+        best = wave_min<NL>(best);
+        if ((tid & 63) == 0) wi_store<NL>(s_red[tid >> 6], best);
+        __syncthreads();
+        if (tid == 0) {
+            for (int w = 1; w < NT / 64; w++) { const WInt<NL> o = wi_load<NL>(s_red[w]); if (wi_lt<NL>(o, best)) best = o; }
+            wi_store<NL>(cx + (size_t)i * b.dist_stride, best);
+        }
+        __syncthreads();
+    }
+}
+
+// ---- 5. k_dp_rec<NL>: a record per pair of P (called = -1: no CDS gene, dropped by the host) ----
+template <int NL>
+__global__ __launch_bounds__(NT) void k_dp_rec(DBatch b, DMarg g, DDrop q) {
+    __shared__ int s_cnt;
+    const DMeta *meta = &b.meta[blockIdx.x];
+    if (!dp_contig(b, g, meta) || meta->sssp_nl != NL) return;
+    const int np = (meta->n_path - 1) / 2, tid = threadIdx.x;
+    const size_t no = (size_t)meta->node_off;
+    const int32_t *path = b.path + no;
+    const DNode *nd = b.node + no;
+    const double *oweight = b.oweight + meta->orf_off;
+    const uint64_t *slot = q.slot + no;
+    const int64_t r0 = q.roff[blockIdx.x];
+    if (tid == 0) s_cnt = 0;
+    __syncthreads();
+    int cnt = 0;
+    for (int i = tid; i < np; i += NT) {
+        phx_gene_drop r;
+        const int a = path[2 * i + 1], bb = path[2 * i + 2];
+        r.left = nd[a].pos; r.right = nd[bb].pos + 2; // as emit_genes
+        r.frame = NFRAME(nd[a].info);
+        r.strand = r.frame < 0 ? -1 : 1;
+        r.score = 0.0; r.drop = __builtin_inf(); r.called = -1; r.bypass = 0;
+        int j, k;
+        if (dp_gene(b, meta, path, i, &j, &k)) {
+            cnt++;
+            r.score = oweight[k];
+            r.called = 0; // (the host's)
+            const uint64_t s = slot[j];
+            WInt<NL> best = s == DP_SAT ? wi_load<NL>(q.sx + ((size_t)r0 + i) * b.dist_stride) : (s == DP_NONE ? wi_inf<NL>() : wi_from_u64<NL>(s));
+            const WInt<NL> c = wi_load<NL>(q.cx + ((size_t)r0 + i) * b.dist_stride);
+            if (wi_lt<NL>(c, best)) best = c;
+            if (!wi_is_inf<NL>(best)) { r.bypass = 1; r.drop = wi_to_double_rn<NL>(best) / 1000.0; }
+        }
+        q.rec[r0 + i] = r;
+    }
+    if (cnt) atomicAdd(&s_cnt, cnt);
+    __syncthreads();
+    if (tid == 0 && s_cnt) atomicAdd(&q.stats[0], (unsigned long long)s_cnt);
+}

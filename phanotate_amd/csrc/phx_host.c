@@ -429,6 +429,89 @@ int phx_format_margins(int32_t n, const char *const *names, const phx_orf_margin
     return PHX_OK;
 }
 
+/* ---- --drop-margins FILE: per contig the called genes of the device path with their drop margins (include/phx.h) ---- */
+typedef struct {
+    int32_t c0, c1;
+    const char *const *names;
+    const phx_gene_drop *rec;
+    const int64_t *offsets;
+    const int32_t *status;
+    char *dst;
+    int64_t len;
+} dfmt_job;
+
+static void *dfmt_work(void *arg) {
+    dfmt_job *j = (dfmt_job *)arg;
+    char *p = j->dst;
+    for (int32_t i = j->c0; i < j->c1; i++) {
+        if (j->status[i] < 0) continue;
+        const char *nm = j->names[i];
+        const size_t ln = strlen(nm);
+        memcpy(p, "#id:\t", 5); p += 5;
+        memcpy(p, nm, ln); p += ln;
+        *p++ = '\n';
+        memcpy(p, "#START\tSTOP\tFRAME\tCONTIG\tSCORE\tDROP\tCALLED\n", 43); p += 43;
+        for (int64_t k = j->offsets[i]; k < j->offsets[i + 1]; k++) {
+            const phx_gene_drop *g = &j->rec[k];
+            const int32_t a = g->strand < 0 ? g->right : g->left, z = g->strand < 0 ? g->left : g->right; /* as the tabular writer, locus.py:44-46 */
+            p = put_int(p, a); *p++ = '\t';
+            p = put_int(p, z); *p++ = '\t';
+            *p++ = (char)(44 - g->strand); *p++ = '\t';
+            memcpy(p, nm, ln); p += ln;
+            *p++ = '\t';
+            p += phx_snprintf_c(p, 25, "%E", g->score);
+            *p++ = '\t';
+            p += phx_snprintf_c(p, 25, "%E", g->drop);
+            *p++ = '\t';
+            *p++ = g->called ? '1' : '0';
+            *p++ = '\n';
+        }
+    }
+    j->len = p - j->dst;
+    return NULL;
+}
+
+int phx_format_drops(int32_t n, const char *const *names, const phx_gene_drop *rec, const int64_t *offsets, const int32_t *status, char **text, int64_t *text_len) {
+    if (n < 0 || !text || !text_len || (n > 0 && (!names || !offsets || !status))) return PHX_E_ARG;
+    *text = NULL; *text_len = 0;
+    /* upper bound: header lines + per record two coordinates (11 each), strand, name, two numbers (<= 24 each), the flag, separators */
+    int64_t *bound = (int64_t *)malloc(sizeof(int64_t) * (size_t)(n + 1));
+    if (!bound) return PHX_E_NOMEM;
+    int64_t need = 1;
+    for (int32_t i = 0; i < n; i++) {
+        bound[i] = need;
+        if (status[i] < 0) continue;
+        if (offsets[i + 1] < offsets[i]) { free(bound); return PHX_E_ARG; }
+        const int64_t ln = (int64_t)strlen(names[i]);
+        need += 6 + ln + 1 + 43 + (offsets[i + 1] - offsets[i]) * (11 + 1 + 11 + 1 + 1 + 1 + ln + 1 + 24 + 1 + 24 + 1 + 1 + 1);
+    }
+    bound[n] = need;
+    if (n > 0 && offsets[n] > offsets[0] && !rec) { free(bound); return PHX_E_ARG; }
+    char *b = (char *)malloc((size_t)need);
+    if (!b) { free(bound); return PHX_E_NOMEM; }
+    dfmt_job job[16];
+    const int T = need < (1 << 20) ? 1 : host_threads();
+    int nj = 0;
+    int32_t c = 0;
+    for (int t = 0; t < T && c < n; t++) {
+        const int64_t target = t + 1 == T ? need : bound[0] + (need - bound[0]) / T * (t + 1);
+        int32_t e = c;
+        while (e < n && (bound[e + 1] <= target || e == c)) e++;
+        if (t + 1 == T) e = n;
+        job[nj].c0 = c; job[nj].c1 = e; job[nj].names = names; job[nj].rec = rec; job[nj].offsets = offsets; job[nj].status = status;
+        job[nj].dst = b + (bound[c] - 1); job[nj].len = 0;
+        nj++;
+        c = e;
+    }
+    if (nj) run_threads(dfmt_work, job, sizeof(dfmt_job), nj);
+    free(bound);
+    char *p = b;
+    for (int t = 0; t < nj; t++) { if (job[t].dst != p) memmove(p, job[t].dst, (size_t)job[t].len); p += job[t].len; }
+    *p = 0;
+    *text = b; *text_len = p - b;
+    return PHX_OK;
+}
+
 void phx_free_text(char *text) { free(text); }
 
 /* ---- bases packed for the link and for the kernels (phx_upload): residue-split bit planes ----

@@ -343,6 +343,23 @@ struct DMarg {
     int32_t *mstat;      // per contig: 1 the reverse pass did not settle (a cycle of negative length); zeroed by the host
 };
 
+#define DP_TAB_LDS 4096 // sparse-table entries (n_path x levels) k_dp_cand keeps in LDS (32 KB); beyond: the contig's slice of DDrop.gtab
+// Gene drop margins (phx_drop.inc), on demand after a run and the margins' shared part: the context's lazily allocated buffers
+struct DDrop {
+    int32_t *pidx;        // per node (at node_off): index on the device path, -1 off it
+    int32_t *js, *jt;     // per node: jump pointers of T_s / T_t (layers of the layered build), then k_dp_cross's cross list / list positions
+    int32_t *first, *last; // per node: the labels (-1: unreached from the source / no path to the target)
+    uint64_t *slot;       // per path slot (at node_off): the range minimum of the candidates (DP_SAT: saturated, DP_NONE: none)
+    uint64_t *gtab;       // sparse tables of the contigs whose table does not fit in LDS, at toff
+    const int64_t *toff;  // per contig: offset of its table in gtab
+    const int64_t *roff;  // per contig: first record (one per pair of the path: (n_path - 1) / 2)
+    uint64_t *sx, *cx;    // per record, dist_stride words: the exact rescan of a saturated slot / the cross-node minimum (inf: none)
+    uint64_t *da, *db;    // per node, dist_stride words: k_dp_cross's delta buffers when the cross list exceeds LDS
+    phx_gene_drop *rec;   // per record (called = -1: the pair is no CDS gene)
+    unsigned long long *stats; // [4]: gene slots, slots with cross nodes, saturated slots rescanned, contigs built by layers
+    int32_t layered;      // 1: every tree by layers (env PHX_DROP_LAYERED)
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -384,6 +401,9 @@ void phxk_results(const DBatch *b, void *stream);
 void phxk_margins_transpose(const DBatch *b, const DMarg *g, void *stream); // out_off (zeroed by the caller) / out_dst / out_w from in_off / esrc / ew
 void phxk_sssp_rev(const DBatch *b, const DMarg *g, int nl_mask, void *stream); // dist_t of every contig of the limb classes in nl_mask (bit k: 2, 4, 8, 17 limbs)
 void phxk_margins(const DBatch *b, const DMarg *g, int nl_mask, void *stream); // the ORF records // after every solver kernel of the run: parents as the reference's in-place Bellman-Ford leaves them
+void phxk_drop_trees(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream); // gene drop margins (phx_drop.inc): trees + labels,
+void phxk_drop_cand(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream);  //   candidates + sparse table,
+void phxk_drop_fix(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream);   //   saturated slots, cross nodes, records
 #ifdef __cplusplus
 }
 #endif

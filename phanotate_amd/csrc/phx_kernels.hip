@@ -178,6 +178,7 @@ __device__ __forceinline__ int min_idx(int a, int b, int c) { return a > b ? (b 
 #include "phx_refine.inc"
 #include "phx_certify.inc"
 #include "phx_margins.inc"
+#include "phx_drop.inc"
 
 // ------------------------------------------------------------------------------------------------
 // launchers
@@ -369,6 +370,21 @@ void phxk_margins(const DBatch *b, const DMarg *g, int nl_mask, void *stream) {
     if (nl_mask & 2) hipLaunchKernelGGL(k_margins<4>, grid, dim3(NT), 0, s, *b, *g);
     if (nl_mask & 4) hipLaunchKernelGGL(k_margins<8>, grid, dim3(NT), 0, s, *b, *g);
     if (nl_mask & 8) hipLaunchKernelGGL(k_margins<17>, grid, dim3(NT), 0, s, *b, *g);
+}
+// gene drop margins (phx_drop.inc): a workgroup per contig, one launch per limb class and step
+#define DP_LAUNCH(K, NLM) do { \
+        if ((NLM) & 1) hipLaunchKernelGGL(K<2>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q); \
+        if ((NLM) & 2) hipLaunchKernelGGL(K<4>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q); \
+        if ((NLM) & 4) hipLaunchKernelGGL(K<8>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q); \
+        if ((NLM) & 8) hipLaunchKernelGGL(K<17>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q); \
+    } while (0)
+void phxk_drop_trees(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; DP_LAUNCH(k_dp_tree, nl_mask); }
+void phxk_drop_cand(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; DP_LAUNCH(k_dp_cand, nl_mask); }
+void phxk_drop_fix(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    DP_LAUNCH(k_dp_rescan, nl_mask);
+    DP_LAUNCH(k_dp_cross, nl_mask);
+    DP_LAUNCH(k_dp_rec, nl_mask);
 }
 size_t phxk_sssp_lds_bytes(int V, int nl) { return sssp_lds_bytes(V, nl); }
 // one workgroup for up to 1024 contigs; larger batches in two passes of a workgroup per 256 contigs

@@ -58,6 +58,7 @@ class Pipeline:
             raise ValueError("Pipeline needs at least one device")
         self.depth = max(1, int(depth))
         self._margins = False
+        self._drops = False
         self.lanes = []
         try:
             for j, d in enumerate(devs):
@@ -78,11 +79,13 @@ class Pipeline:
     def __exit__(self, *exc):
         self.close()
 
-    def run(self, batches, margins=False):
+    def run(self, batches, margins=False, drop_margins=False):
         """Generator over (status, offsets, genes) of every batch (Annotator.download_flat), in order.  While the caller consumes
         batch k, the batches behind it are already running.  margins=True: every item gains the batch's (status, offsets, records) of
-        Annotator.margins(), fetched after the download on the same context."""
+        Annotator.margins(), fetched after the download on the same context; drop_margins=True: then the triple of
+        Annotator.drop_margins() (after the margins' when both are asked for)."""
         self._margins = bool(margins)
+        self._drops = bool(drop_margins)
         if len(self.lanes) == 1:
             yield from self._run_one(self.lanes[0], batches)
             return
@@ -90,7 +93,11 @@ class Pipeline:
 
     def _collect(self, a):
         res = a.download_flat()
-        return res + (a.margins(),) if self._margins else res
+        if self._margins:
+            res = res + (a.margins(),)
+        if self._drops:
+            res = res + (a.drop_margins(),)
+        return res
 
     def _run_one(self, lane, batches):
         busy = deque()
