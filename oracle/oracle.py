@@ -102,15 +102,19 @@ def lib():
 
 
 def make_params(start_codons="atg:0.85,gtg:0.10,ttg:0.05", stop_codons="tag,tga,taa", minlen=90):
-    """Mirror of file_handling.py:58-66 in fp64 (weights divided by their max)."""
+    """Mirror of file_handling.py:58-66 in fp64 (weights divided by their max).  The codons go into a dict keyed by the lower-case
+    codon: a repeated codon keeps the position of its first entry and the weight of its last, and the max runs over the dict."""
     p = Params()
     p.minlen = minlen
-    pairs = [x.split(":") for x in start_codons.split(",")]
-    m = max(float(w) for _, w in pairs)
-    p.n_start = len(pairs)
-    for i, (c, w) in enumerate(pairs):
-        p.start[i].value = c.lower().encode()
-        p.start_w[i] = float(w) / m
+    sc = {}
+    for x in start_codons.split(","):
+        c, w = x.split(":")
+        sc[c.lower()] = float(w)
+    m = max(sc.values())
+    p.n_start = len(sc)
+    for i, (c, w) in enumerate(sc.items()):
+        p.start[i].value = c.encode()
+        p.start_w[i] = w / m
     stops = stop_codons.split(",")
     p.n_stop = len(stops)
     for i, c in enumerate(stops):

@@ -642,9 +642,10 @@ __device__ __forceinline__ void b_score(const DBatch &b, const int bx) {
         double s = exp(-S * log1p(-st.pstop));
         if (st.startidx >= 0) s = s * P->start_w[st.startidx];
         s = s * w_rbs;
-        oweight[k] = -s;
-        owi[k] = ew_encode(-s); // what the solver adds (edges.py:22), and whether the reference's integer may differ from it (k_certify)
-        oflag[k] = (uint8_t)((cert_eps_is_zero_fast(-s, cc) ? 0 : 2) | (ew_narrow51(owi[k]) ? 0 : 1));
+        const double w = s != 0.0 ? -s : 0.0; // weight = -s; Decimal's minus of a zero is +0 (a start weight of 0): "0.000000E+00", not "-0..."
+        oweight[k] = w;
+        owi[k] = ew_encode(w); // what the solver adds (edges.py:22), and whether the reference's integer may differ from it (k_certify)
+        oflag[k] = (uint8_t)((cert_eps_is_zero_fast(w, cc) ? 0 : 2) | (ew_narrow51(owi[k]) ? 0 : 1));
         int e;
         frexp(s * 1000.0, &e);
         if (!(s < 1.0e300)) e = 4096; // inf / nan: force the overflow status

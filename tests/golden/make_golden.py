@@ -168,6 +168,14 @@ def make_case(case, name, seq, outdir, trnas=None, **params):
     out["params_start"] = ",".join("%s:%s" % (k, v) for k, v in locus.start_codons.items())
     out["params_stop"] = ",".join(locus.stop_codons)
     out["params_minlen"] = locus.min_orf_len
+    if params:  # the flags as written (tests/test_params_gpu.py hands these to the product)
+        out["flags_start"] = params.get("start_codons", "atg:0.85,gtg:0.10,ttg:0.05")
+        out["flags_stop"] = params.get("stop_codons", "tag,tga,taa")
+        # the suite reads params_start (conftest.golden_params): normalising that text once more must give the same dict
+        again = StubLocus(seq, out["params_start"], out["params_stop"], locus.min_orf_len)
+        assert list(again.start_codons.items()) == list(locus.start_codons.items()), (case, again.start_codons, locus.start_codons)
+        assert again.stop_codons == locus.stop_codons
+        assert all(len(str(v)) < 32 for v in locus.start_codons.values()), case  # libphx holds a weight's text in 31 characters
     try:
         try:
             orfs, graph, cap, times = run_reference(locus)
@@ -338,6 +346,38 @@ def main():
     # non-default flags (file_handling.py:51-53)
     cases.append(("param_minlen60", "param_minlen60", synth(200, 6000), dict(minlen=60)))
     cases.append(("param_codons", "param_codons", synth(201, 6000), dict(start_codons="atg:0.7,gtg:0.2,ttg:0.05,ctg:0.05", stop_codons="tag,taa")))
+    # the flag edges (file_handling.py:51-66, functions.py:186-215, 266): codons in two classes of the elif chain, atg not a start (only
+    # the contig-end fragments that begin with atg train the GC frame plot), one stop, minlen around the multiples of 3 and beyond the
+    # contig, 16 start codons, weights whose fp64 and Decimal quotients differ, the dict semantics of a repeated codon, zero and negative
+    # weights.  The raw flag text is stored as flags_start / flags_stop (params_start is the reference's normalised dict).
+    s21 = synth(421, 2400)
+    # noatg: 100 sense codons behind the first base and in front of the last, on both strands, so that the fragments at the contig ends
+    # (pseudo starts, functions.py:186-190, 241-242) are long ORFs whose first codon is atg: the only ORFs that train pos_max / pos_min
+    wr = np.random.RandomState(13)
+    rc = lambda x: x[::-1].translate(str.maketrans("acgt", "tgca"))
+    orf_a = "atg" + "".join(sense[i] for i in wr.randint(0, len(sense), 100))
+    orf_b = "atg" + "".join(sense[i] for i in wr.randint(0, len(sense), 100))
+    pcases = [
+        ("param_noatg", orf_a + synth(420, 2400) + rc(orf_b), dict(start_codons="gtg:1,ttg:0.5")),
+        ("param_start_is_stop", s21, dict(start_codons="atg:1,tag:0.3")),
+        ("param_start_rc_stop", synth(422, 3000), dict(start_codons="atg:1,cta:0.4,tta:0.2")),
+        ("param_stop_rc_stop", synth(423, 2500), dict(stop_codons="tag,cta,taa")),
+        ("param_one_stop", synth(424, 2000), dict(stop_codons="taa")),
+        ("param_minlen6", synth(425, 1500), dict(minlen=6)),
+        ("param_minlen7", synth(426, 1800), dict(minlen=7)),
+        ("param_minlen91", synth(427, 3500), dict(minlen=91)),
+        ("param_minlen92", synth(428, 3500), dict(minlen=92)),
+        ("param_minlen_gt_contig", synth(429, 2000), dict(minlen=2500)),
+        # (weights whose quotients by 0.8 end: libphx keeps a weight's text in 31 characters, and the suite hands it the normalised text)
+        ("param_16_starts", synth(430, 4000), dict(start_codons="atg:0.8,gtg:0.1,ttg:0.05,ctg:0.04,att:0.02,ata:0.01,aca:0.008,gcc:0.004,"
+                                                                  "cgc:0.002,tgt:0.001,ggg:0.0008,ccc:0.0004,aag:0.0002,gaa:0.0001,cag:0.4,agt:0.2")),
+        ("param_weights_3_1", synth(431, 3000), dict(start_codons="atg:3,gtg:1,ttg:0.7")),
+        ("param_repeated", synth(432, 3000), dict(start_codons="ATG:0.5,gtg:0.1,atg:1e-1,ttg:2E-2")),
+        ("param_zero_weight", synth(433, 2500), dict(start_codons="atg:0.85,gtg:0,ttg:0.05")),
+        ("param_negative_weight", synth(434, 2500), dict(start_codons="atg:0.85,gtg:-0.10,ttg:0.05")),
+    ]
+    for nm, seq, kw in pcases:
+        cases.append((nm, nm, seq, kw))
 
     # tRNA masking (functions.py:457-509, connect branch 388-399) through a fake `aragorn` on PATH: (begin, end, complement)
     tr = {

@@ -10,18 +10,42 @@ from concurrent.futures import ProcessPoolExecutor
 import numpy as np
 from fuzz_gpu import make
 
+CODONS = [a + b + c for a in "acgt" for b in "acgt" for c in "acgt"]
+RC = lambda c: c[::-1].translate(str.maketrans("acgt", "tgca"))
+
 def draw_flags(rng):
-    codons = ["atg", "gtg", "ttg", "ctg", "att", "ata"]
-    k = int(rng.choice([1, 2, 3, 3, 4, 6]))
-    cs = ["atg"] + list(rng.choice(codons[1:], k - 1, replace=False))
-    ws = []
-    for i in range(k):
+    """One flag set: 1 to 16 start codons, some that are also stops or whose reverse complement is a stop (the elif chain of
+    functions.py:198-215), sometimes without atg; repeated codons (dict semantics: first place, last weight), upper case, exponent,
+    zero and negative weights (at least one positive); 1 to 4 stops, sometimes reverse complements of each other; minlen around the
+    multiples of 3."""
+    stops = list(rng.choice(["tag", "tga", "taa", "cta", "tca", "tta", "ttg"], int(rng.randint(1, 5)), replace=False))
+    if rng.rand() < 0.15: stops.append(RC(stops[0]))
+    k = int(rng.choice([1, 2, 3, 3, 4, 6, 9, 16]))
+    pool = ["gtg", "ttg", "ctg", "att", "ata"] + [c for c in CODONS if c not in ("atg", "gtg", "ttg", "ctg", "att", "ata")]
+    odd = [c for c in CODONS if c in stops or RC(c) in stops]  # codons that fall into two classes
+    cs = [] if rng.rand() < 0.15 else ["atg"]
+    if rng.rand() < 0.4: cs.append(str(rng.choice(odd)))
+    while len(cs) < k:
+        c = str(rng.choice(pool[:5] if rng.rand() < 0.5 else pool))
+        if c not in cs: cs.append(c)
+    def weight():
+        f = rng.randint(10)
+        if f == 0: return "%d%s%d" % (rng.randint(1, 10), "eE"[rng.randint(2)], -rng.randint(0, 4))
+        if f == 1: return "0"
+        if f == 2: return "-0.%02d" % rng.randint(1, 100)
+        if f == 3: return str(rng.randint(1, 4))
         nd = int(rng.choice([1, 2, 3, 6]))
-        w = round(float(rng.uniform(0.01, 1.0)), nd)
-        ws.append(("%." + str(nd) + "f") % max(w, 10.0 ** -nd))
-    if rng.rand() < 0.3: ws[0] = "1"
-    stops = str(rng.choice(["tag,tga,taa", "tag,taa", "taa,tga", "taa", "tga,tag,taa"]))
-    return dict(start_codons=",".join(c + ":" + w for c, w in zip(cs, ws)), stop_codons=stops, minlen=int(rng.choice([6, 30, 60, 90, 90, 150, 300])))
+        return ("%." + str(nd) + "f") % max(round(float(rng.uniform(0.01, 1.0)), nd), 10.0 ** -nd)
+    items = [[c, weight()] for c in cs]
+    if rng.rand() < 0.3: items[0][1] = "1"
+    for _ in range(int(rng.choice([0, 0, 1, 2]))):  # a repeated codon
+        items.insert(int(rng.randint(len(items) + 1)), [str(rng.choice(cs)), weight()])
+    last = {}
+    for c, w in items: last[c] = w
+    if not any(float(w) > 0 for w in last.values()): items.append([cs[0], "0.5"])
+    up = lambda c: c.upper() if rng.rand() < 0.2 else c
+    return dict(start_codons=",".join(up(c) + ":" + w for c, w in items), stop_codons=",".join(up(c) for c in stops),
+                minlen=int(rng.choice([6, 7, 8, 61, 90, 91, 92, 301])))
 
 def orc(arg):
     seq, kw = arg
