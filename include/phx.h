@@ -35,7 +35,9 @@ extern "C" {
                          *        replay, which moved to tests/decimal_replay.py and computes it itself);
                          * 0.4.1: phx_run_async puts the certificate kernels behind the run unless exactness is off; env PHX_FRONT_SPINS (tests);
                          *        (additions, version unchanged) phx_orf_margin, phx_margins_flat, phx_tap_dist_target, phx_margins_ms, phx_format_margins;
- *        (additions, version unchanged) phx_gene_drop, phx_drop_margins_flat, phx_drop_ms, phx_drop_stats, phx_format_drops */
+ *        (additions, version unchanged) phx_gene_drop, phx_drop_margins_flat, phx_drop_ms, phx_drop_stats, phx_format_drops;
+ *        (additions, version unchanged) phx_gene_repl, phx_replacements_flat, phx_tap_replacement, phx_replacements_ms,
+ *        phx_replacement_stats, phx_format_replacements */
 #define PHX_MAX_CODONS 16
 
 /* library-level errors */
@@ -358,6 +360,38 @@ int phx_drop_ms(phx_ctx *ctx, float *ms /* [4] */);
  * exactly, contigs whose trees were built layer by layer (a zero-length cycle of tight edges, or env PHX_DROP_LAYERED=1) */
 int phx_drop_stats(phx_ctx *ctx, int64_t *out /* [4] */);
 
+/* ---- drop replacements, on demand after a run ----
+ * For every record of phx_drop_margins_flat with bypass = 1 a replacement path R_g: a simple source -> target path of the device graph
+ * that avoids the gene's stop node p_j and whose integer length is exactly D_{-g}.  It has the form p_0 .. p_a, r_1 .. r_m, p_b .. p_K
+ * (a < j < b, no r_i on the device path P), so its genes (pairs R[2i+1] -> R[2i+2], the rule of phx_download) are P's genes with the
+ * pairs of P between p_a and p_b ("removed", the dropped gene among them) replaced by the pairs of the detour p_a, r_1 .. r_m, p_b
+ * ("added").  Among equal-length witnesses the rule of DESIGN.md §13 picks one, so the bytes do not depend on the batch or the flags. */
+typedef struct phx_gene_repl {
+    int32_t left, right, strand, frame; /* the dropped gene, as phx_gene_drop */
+    double drop;                        /* bit-equal to phx_gene_drop.drop */
+    int32_t called, bypass;             /* as phx_gene_drop */
+    int32_t span_left, span_right;      /* min left / max right over the removed and added genes (bypass = 0: the gene's own) */
+    int32_t n_removed, n_added;         /* genes[gene_off .. + n_removed): P's genes in the span, path order; then n_added genes of the
+                                         * detour, path order (both 0 when bypass = 0) */
+    int64_t gene_off;
+} phx_gene_repl;
+/* Replacements of every record of phx_drop_margins_flat, flat: records rec[offsets[i] .. offsets[i+1]) of contig i as the drop records
+ * (same order, statuses, offsets, drop, called, bypass); their genes in genes[0 .. gene_total), at each record's gene_off.  rec == NULL
+ * or genes == NULL: size query (offsets, status, total, gene_total).  The first call after a run computes them (the drop margins first
+ * when they are not there yet), kernel by kernel on the context's stream, never inside phx_run; later calls reuse them. */
+int phx_replacements_flat(phx_ctx *ctx, phx_gene_repl *rec, int64_t cap, phx_gene *genes, int64_t gene_cap, int64_t *offsets /* [n+1] */,
+                          int32_t *status /* [n] */, int64_t *total, int64_t *gene_total);
+/* R_g of record k of contig `contig` (k counts the contig's records of phx_replacements_flat): device node ids, source first.  path ==
+ * NULL: *n_path only; bypass = 0: *n_path = 0. */
+int phx_tap_replacement(phx_ctx *ctx, int32_t contig, int32_t k, int32_t *path, int32_t cap, int32_t *n_path);
+/* device time of the last computation of the replacements (HIP events around the kernels only), ms[3]: argmin (winners of every slot,
+ * cross winners), walk + genes (counting pass, filling pass with its offsets' upload), the copy to the host.  All 0 before the first. */
+int phx_replacements_ms(phx_ctx *ctx, float *ms /* [3] */);
+/* counters of the last computation of the replacements, out[5]: slots won by a cross candidate (step 4 of DESIGN.md §12), delta-chain
+ * nodes of those winners, cross winners whose path keeps its delta chain, walks whose zero-length loop was cut, 1 when the delta-chain
+ * buffer had to grow (the cross winners were then computed a second time). */
+int phx_replacement_stats(phx_ctx *ctx, int64_t *out /* [5] */);
+
 /* -d/--dump of the reference (phanotate.py:58,61) for one contig of the batch last run: one line per edge of its graph,
  *     repr(source) TAB repr(target) TAB str(weight * 1000)                                   (edges.py:17-23, nodes.py:14-21)
  * in Graph.iteredges order, the weights as the reference's 28-digit Decimals (the chain replayed by csrc/phx_dec.c on the integers
@@ -450,6 +484,12 @@ int phx_format_margins(int32_t n, const char *const *names, const phx_orf_margin
  * strand; SCORE and DROP '%E'; CALLED 0 / 1).  Worker threads like phx_format_tabular.  *text is malloc'ed (NUL-terminated), release
  * with phx_free_text. */
 int phx_format_drops(int32_t n, const char *const *names, const phx_gene_drop *rec, const int64_t *offsets, const int32_t *status, char **text, int64_t *text_len);
+/* --drop-replacements FILE of the CLI from the flat arrays of phx_replacements_flat: per contig with status >= 0 "#id:\t<name>", the
+ * header "#START\tSTOP\tFRAME\tCONTIG\tDROP\tREMOVED\tADDED", then one row per record in the given order (START > STOP on the reverse
+ * strand; DROP '%E'; REMOVED / ADDED comma-separated START..STOP with START > STOP on the reverse strand, "tRNA:" in front of a tRNA pair,
+ * "-" for none).  Worker threads like phx_format_tabular.  *text is malloc'ed (NUL-terminated), release with phx_free_text. */
+int phx_format_replacements(int32_t n, const char *const *names, const phx_gene_repl *rec, const phx_gene *genes, const int64_t *offsets,
+                            const int32_t *status, char **text, int64_t *text_len);
 void phx_free_text(char *text);
 
 #ifdef __cplusplus

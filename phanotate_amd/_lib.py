@@ -49,6 +49,8 @@ ORF_DT = np.dtype([("start", "i4"), ("stop", "i4"), ("frame", "i4"), ("length", 
 NODE_DT = np.dtype([("pos", "i4"), ("type", "i1"), ("frame", "i1"), ("pad", "i2"), ("other", "i4"), ("refidx", "i4"), ("o", "f8")], align=True)
 MARGIN_DT = np.dtype([("left", "i4"), ("right", "i4"), ("strand", "i4"), ("frame", "i4"), ("score", "f8"), ("margin", "f8"), ("called", "i4"), ("through", "i4")], align=True)
 DROP_DT = np.dtype([("left", "i4"), ("right", "i4"), ("strand", "i4"), ("frame", "i4"), ("score", "f8"), ("drop", "f8"), ("called", "i4"), ("bypass", "i4")], align=True)
+REPL_DT = np.dtype([("left", "i4"), ("right", "i4"), ("strand", "i4"), ("frame", "i4"), ("drop", "f8"), ("called", "i4"), ("bypass", "i4"),
+                    ("span_left", "i4"), ("span_right", "i4"), ("n_removed", "i4"), ("n_added", "i4"), ("gene_off", "i8")], align=True)
 EDGE_DT = np.dtype([("src", "i4"), ("dst", "i4"), ("w", "f8"), ("inexact", "i4"), ("pad", "i4"), ("d1", "f8"), ("d2", "f8"), ("err", "f8")], align=True)
 
 _lib = None
@@ -143,6 +145,11 @@ def lib():
         "phx_drop_ms": (C.c_int, [vp, P(C.c_float)]),
         "phx_drop_stats": (C.c_int, [vp, P(i64)]),
         "phx_format_drops": (C.c_int, [i32, vp, vp, vp, vp, P(vp), P(i64)]),
+        "phx_replacements_flat": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, P(i64), P(i64)]),
+        "phx_tap_replacement": (C.c_int, [vp, i32, i32, vp, i32, P(i32)]),
+        "phx_replacements_ms": (C.c_int, [vp, P(C.c_float)]),
+        "phx_replacement_stats": (C.c_int, [vp, P(i64)]),
+        "phx_format_replacements": (C.c_int, [i32, vp, vp, vp, vp, vp, P(vp), P(i64)]),
         "phx_solve": (C.c_int, [vp, i32, i32, vp, vp, vp, i32, i32, i32, vp, i32, P(i32), vp]),
         "phx_set_profiling": (C.c_int, [vp, C.c_int]),
         "phx_set_profiling_stages": (C.c_int, [vp, C.c_uint32]),
@@ -170,6 +177,7 @@ def lib():
     assert GENE_DT.itemsize == C.sizeof(Gene)
     assert MARGIN_DT.itemsize == 40
     assert DROP_DT.itemsize == 40
+    assert REPL_DT.itemsize == 56
     _lib = L
     return L
 
@@ -180,4 +188,6 @@ EXPORTS = ["phx_version", "phx_device_count", "phx_strerror", "phx_last_error", 
            "phx_get_stage_ms", "phx_stage_name", "phx_batch_sizes", "phx_plan_timeouts", "phx_front_runs", "phx_seg_runs", "phx_seg_fallbacks", "phx_seg_stats", "phx_synth_contig", "phx_fasta_read", "phx_fasta_count",
            "phx_fasta_record", "phx_fasta_arrays", "phx_fasta_free", "phx_format_tabular", "phx_free_text",
            "phx_margins_flat", "phx_tap_dist_target", "phx_margins_ms", "phx_format_margins",
-           "phx_drop_margins_flat", "phx_drop_ms", "phx_drop_stats", "phx_format_drops"]
+           "phx_drop_margins_flat", "phx_drop_ms", "phx_drop_stats", "phx_format_drops",
+           "phx_replacements_flat", "phx_tap_replacement", "phx_replacements_ms", "phx_replacement_stats",
+           "phx_format_replacements"]

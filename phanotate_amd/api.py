@@ -388,6 +388,45 @@ class Annotator:
         self._chk(self.L.phx_drop_ms(self.h, ms), "phx_drop_ms")
         return dict(zip(("trees", "candidates", "fixups", "download"), [float(x) for x in ms]))
 
+    def replacements(self):
+        """(status int32[n], offsets int64[n+1], records structured array[total] of _lib.REPL_DT, genes structured array of _lib.GENE_DT):
+        for every record of drop_margins() (same order, statuses and offsets; drop, called and bypass bit-equal) what the best path
+        without the gene calls instead (phx_replacements_flat).  Record r's genes are genes[r.gene_off:][:r.n_removed]
+        (the device path's genes the replacement drops, the gene itself among them), then the next r.n_added (the genes it calls
+        instead), in path order."""
+        n = self.n
+        offs = np.zeros(n + 1, np.int64)
+        status = np.zeros(max(n, 1), np.int32)
+        total, gtotal = C.c_int64(), C.c_int64()
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._chk(self.L.phx_replacements_flat(self.h, None, 0, None, 0, vp(offs), vp(status), C.byref(total), C.byref(gtotal)), "phx_replacements_flat")
+        rec = np.empty(max(int(total.value), 1), _lib.REPL_DT)
+        genes = np.empty(max(int(gtotal.value), 1), _lib.GENE_DT)
+        self._chk(self.L.phx_replacements_flat(self.h, vp(rec), len(rec), vp(genes), len(genes), vp(offs), vp(status), C.byref(total), C.byref(gtotal)),
+                  "phx_replacements_flat")
+        return status[:n], offs, rec[: int(total.value)], genes[: int(gtotal.value)]
+
+    def replacement_path(self, i, k):
+        """R_g of record k of contig i (replacements()[2][offsets[i] + k]): device node ids, source first; empty when bypass = 0."""
+        n = C.c_int32()
+        self._chk(self.L.phx_tap_replacement(self.h, i, k, None, 0, C.byref(n)), "phx_tap_replacement")
+        p = np.zeros(max(n.value, 1), np.int32)
+        self._chk(self.L.phx_tap_replacement(self.h, i, k, p.ctypes.data_as(C.c_void_p), len(p), C.byref(n)), "phx_tap_replacement")
+        return p[: n.value].copy()
+
+    def replacements_ms(self):
+        """Device time of the last replacements computation in ms: argmin, walk + genes, copy to the host (phx_replacements_ms)."""
+        ms = (C.c_float * 3)()
+        self._chk(self.L.phx_replacements_ms(self.h, ms), "phx_replacements_ms")
+        return dict(zip(("argmin", "walk", "download"), [float(x) for x in ms]))
+
+    def replacement_stats(self):
+        """Counters of the last replacements computation (phx_replacement_stats): slots won by a cross candidate, their delta-chain nodes,
+        cross winners whose path keeps its delta chain, walks whose zero-length loop was cut, 1 when the delta-chain buffer had to grow."""
+        out = (C.c_int64 * 5)()
+        self._chk(self.L.phx_replacement_stats(self.h, out), "phx_replacement_stats")
+        return dict(zip(("cross", "chain_nodes", "cross_kept", "cut", "regrown"), [int(x) for x in out]))
+
     def drop_stats(self):
         """Counters of the last drop-margins computation (phx_drop_stats): gene slots, slots with cross nodes, saturated slots rescanned
         exactly, contigs whose trees were built layer by layer."""

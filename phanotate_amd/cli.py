@@ -42,6 +42,7 @@ def get_args(argv=None):
     p.add_argument("--batch-bases", type=int, default=400_000_000, help="bases per GPU batch [4e8]")
     p.add_argument("--margins", metavar="FILE", default=None, help="also write every ORF some source-to-target path runs through, with its path margin (DESIGN.md §11), to FILE")
     p.add_argument("--drop-margins", metavar="FILE", default=None, help="also write every called gene with its drop margin, the cost of the best path without it (DESIGN.md §12), to FILE")
+    p.add_argument("--drop-replacements", metavar="FILE", default=None, help="also write every called gene with what the best path without it calls instead (DESIGN.md §13) to FILE")
     p.add_argument("--single-device-ranks", action="store_true", help=argparse.SUPPRESS)  # tests: every rank of a sharded launch on GPU `--device` (gloo-only group)
     args = p.parse_args(argv)
     if args.margins is not None and args.dump:
@@ -52,6 +53,10 @@ def get_args(argv=None):
         p.error("argument --drop-margins: not allowed with argument -d/--dump")
     if args.drop_margins is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         p.error("argument --drop-margins: not available under a multi-rank launch")
+    if args.drop_replacements is not None and args.dump:
+        p.error("argument --drop-replacements: not allowed with argument -d/--dump")
+    if args.drop_replacements is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        p.error("argument --drop-replacements: not available under a multi-rank launch")
     return args
 
 
@@ -107,6 +112,34 @@ def format_margins(names, status, offsets, records):
     rc = L.phx_format_margins(n, arr, vp(records), vp(offsets), vp(status), C.byref(text), C.byref(tlen))
     if rc:
         raise _lib.PhxError(rc, "phx_format_margins")
+    out = C.string_at(text.value, tlen.value)
+    L.phx_free_text(text)
+    return out
+
+
+def format_replacements(names, status, offsets, records, genes):
+    """--drop-replacements FILE for a run of contigs, as bytes (libphx's phx_format_replacements): per contig with status >= 0
+    "#id:\t<name>", the header, one row per called gene of the device path (START STOP FRAME CONTIG DROP REMOVED ADDED), in path order;
+    records[k]["gene_off"] indexes genes."""
+    import ctypes as C
+
+    import numpy as np
+
+    from . import _lib
+
+    L = _lib.lib()
+    n = len(names)
+    enc = [x.encode() for x in names]
+    arr = (C.c_char_p * max(n, 1))(*enc)
+    status = np.ascontiguousarray(status, np.int32)
+    offsets = np.ascontiguousarray(offsets, np.int64)
+    records = np.ascontiguousarray(records, _lib.REPL_DT)
+    genes = np.ascontiguousarray(genes, _lib.GENE_DT)
+    text, tlen = C.c_void_p(), C.c_int64()
+    vp = lambda x: x.ctypes.data_as(C.c_void_p)
+    rc = L.phx_format_replacements(n, arr, vp(records), vp(genes), vp(offsets), vp(status), C.byref(text), C.byref(tlen))
+    if rc:
+        raise _lib.PhxError(rc, "phx_format_replacements")
     out = C.string_at(text.value, tlen.value)
     L.phx_free_text(text)
     return out
@@ -222,6 +255,7 @@ def main(argv=None):
     n_total = len(fa)
     margin_parts = []  # --margins: (status, offsets, records) of every batch, in order
     drop_parts = []  # --drop-margins: the same of the drop margins
+    repl_parts = []  # --drop-replacements: (status, offsets, records, genes) of every batch, in order
     mine = list(range(n_total)) if world == 1 else partition(fa.lens.tolist(), world)[rank]
 
     def annotate_flat(idx):  # this rank's contigs, in batches of --batch-bases, straight from the C buffer of the FASTA reader
@@ -254,6 +288,8 @@ def main(argv=None):
             t3 = time.perf_counter()
             if args.margins is not None:
                 margin_parts.append(ann.margins())
+            if args.drop_replacements is not None:  # (before the drop margins: they are then computed once)
+                repl_parts.append(ann.replacements())
             if args.drop_margins is not None:
                 drop_parts.append(ann.drop_margins())
             t_parts["upload_s"] += t1 - t0; t_parts["run_s"] += t2 - t1; t_parts["download_s"] += t3 - t2
@@ -265,7 +301,7 @@ def main(argv=None):
             t1 = time.perf_counter()
             gen = ((fa.ptrs[idx[lo:hi]], fa.lens[idx[lo:hi]], fa, (lambda a=lo, b=hi: trnas_of(idx[a:b]))) for lo, hi in cuts)
             try:
-                parts = list(pipe.run(gen, margins=args.margins is not None, drop_margins=args.drop_margins is not None))
+                parts = list(pipe.run(gen, margins=args.margins is not None, drop_margins=args.drop_margins is not None, replacements=args.drop_replacements is not None))
                 t2 = time.perf_counter()
                 k = 3
                 if args.margins is not None:
@@ -273,6 +309,9 @@ def main(argv=None):
                     k += 1
                 if args.drop_margins is not None:
                     drop_parts.extend(p[k] for p in parts)
+                    k += 1
+                if args.drop_replacements is not None:
+                    repl_parts.extend(p[k] for p in parts)
                 parts = [p[:3] for p in parts]
             finally:
                 pipe.close()
@@ -321,6 +360,19 @@ def main(argv=None):
             d_records = np.concatenate([m[2] for m in drop_parts])
             with open(args.drop_margins, "wb") as fh:
                 fh.write(format_drops(fa.names, d_status, d_offsets, d_records))
+        if args.drop_replacements is not None:
+            r_status = np.concatenate([m[0] for m in repl_parts])
+            r_counts = np.concatenate([np.diff(m[1]) for m in repl_parts])
+            r_offsets = np.concatenate([[0], np.cumsum(r_counts)]).astype(np.int64)
+            r_records, r_genes, g0 = [], [], 0
+            for m in repl_parts:  # (each batch's gene_off counts from its own genes)
+                rr = m[2].copy()
+                rr["gene_off"] += g0
+                g0 += len(m[3])
+                r_records.append(rr)
+                r_genes.append(m[3])
+            with open(args.drop_replacements, "wb") as fh:
+                fh.write(format_replacements(fa.names, r_status, r_offsets, np.concatenate(r_records), np.concatenate(r_genes)))
     t_end = time.perf_counter()
     if os.environ.get("PHX_CLI_TIMING") and rank == 0:
         sys.stderr.write("PHX_CLI_TIMING " + json.dumps({"parse_s": round(t_parsed - t_start, 4), "gpu_s": round(t_gpu - t_parsed, 4), "format_s": round(t_fmt - t_gpu, 4),

@@ -31,6 +31,8 @@ thread_local std::string g_create_error;
 enum Stage { ST_MEMSET = 0, ST_FEATURES, ST_ORF_COUNT, ST_ORF_EMIT, ST_ORF_STATS, ST_SCORE, ST_NODES, ST_EDGE_COUNT, ST_EDGE_FILL, ST_SSSP, ST_CERTIFY, ST_COPY, ST_INORDER, ST_WAVE_PLAN };
 const char *kStageName[PHX_N_STAGES] = {"memset", "features", "orf_count", "orf_emit", "orf_stats", "score", "nodes", "edges_count", "edges_fill", "sssp", "certify", "copies", "inorder", "wave_plan"};
 
+#define RP_NCNT 8 // DRepl.cnt: delta-chain nodes, records without a winner, cross winners, cross walks keeping the chain, loops cut
+
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
@@ -235,6 +237,19 @@ struct phx_ctx {
     hipEvent_t dev_[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     float drop_ms[4] = {0, 0, 0, 0};
     int64_t drop_stats[4] = {0, 0, 0, 0};
+    bool drop_trees = false;         // the drop kernels of the run kept the one-hop trees (b_dps / b_dts)
+    // drop replacements (phx_replacements_flat): buffers allocated at the first call, results kept until the next run
+    DevBuf b_dps, b_dts, b_rwin, b_rxs, b_rcoff, b_rcm, b_rchain, b_rrnd, b_rinfo, b_rdoff, b_rdet, b_rgenes, b_rrec, b_rcnt;
+    bool repl_done = false;
+    std::vector<phx_gene_repl> h_rrec; // per device record (as h_drec); gene_off into h_rgenes
+    std::vector<phx_gene> h_rgenes;
+    std::vector<int32_t> h_rdet, h_rinfo; // the detours; per record a, b, m, genes
+    std::vector<int64_t> h_rdoff;     // per record: first detour node in h_rdet
+    std::vector<std::vector<int32_t>> h_rpath; // per contig: its device path, fetched by the first phx_tap_replacement of the run
+    int64_t rchain_cap = 0;           // delta-chain nodes b_rchain has room for
+    hipEvent_t rev_ev[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    float repl_ms[3] = {0, 0, 0};
+    int64_t repl_stats[5] = {0, 0, 0, 0, 0};
     float stage_ms[PHX_N_STAGES] = {0};
     int stage_n[PHX_N_STAGES] = {0};
     std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;
@@ -448,7 +463,7 @@ int set_batch_layout(phx_ctx *c, int32_t n, const int64_t *len_or_null, const in
     c->uploaded = false; c->ran = false; c->graph_valid = false; c->n = 0; // whatever fails below leaves the context without a batch
     c->meta_stale = false;
     c->has_trna = false; c->h_tnode.clear();
-    c->margins_done = false; c->rev_done = false; c->drops_done = false;
+    c->margins_done = false; c->rev_done = false; c->drops_done = false; c->drop_trees = false; c->repl_done = false;
     if (n < 0) return PHX_E_ARG;
     if (!c->meta.assign((size_t)n)) { c->err = "hipHostMalloc failed"; return PHX_E_NOMEM; }
     c->ftab.clear(); c->vtotal = 0;
@@ -702,12 +717,14 @@ void phx_destroy(phx_ctx *c) {
     DevBuf *all[] = {&c->b_eref, &c->b_cint, &c->b_csig, &c->b_meta0, &c->b_tie, &c->b_ekey, &c->b_tnode, &c->b_tedge, &c->b_tnid, &c->b_tbits, &c->b_win, &c->b_wrole, &c->b_bridge, &c->b_recs, &c->b_meta, &c->b_tiles, &c->b_nbits, &c->b_nbase, &c->b_cbits, &c->b_orf, &c->b_ostat, &c->b_oweight, &c->b_owi, &c->b_oflag, &c->b_ewf, &c->b_esrcf, &c->b_onode, &c->b_grp, &c->b_bits, &c->b_cpre, &c->b_bpre, &c->b_item, &c->b_iprev,
                      &c->b_node, &c->b_parent, &c->b_inoff, &c->b_no, &c->b_npos, &c->b_ehit, &c->b_mreach, &c->b_olist, &c->b_dist, &c->b_esrc, &c->b_ew, &c->b_ewl, &c->b_path, &c->b_genes, &c->b_gtot, &c->b_tot, &c->b_lpart, &c->b_res, &c->b_sord, &c->b_gtab, &c->b_erank, &c->b_swin, &c->b_swrole, &c->b_sdist, &c->b_segw,
                      &c->b_mo, &c->b_md, &c->b_mw, &c->b_mdt, &c->b_mrec, &c->b_mstat,
-                     &c->b_dpi, &c->b_djs, &c->b_djt, &c->b_dfi, &c->b_dla, &c->b_dslot, &c->b_dgtab, &c->b_doff, &c->b_dsx, &c->b_dcx, &c->b_dda, &c->b_ddb, &c->b_drec, &c->b_dstats};
+                     &c->b_dpi, &c->b_djs, &c->b_djt, &c->b_dfi, &c->b_dla, &c->b_dslot, &c->b_dgtab, &c->b_doff, &c->b_dsx, &c->b_dcx, &c->b_dda, &c->b_ddb, &c->b_drec, &c->b_dstats,
+                     &c->b_dps, &c->b_dts, &c->b_rwin, &c->b_rxs, &c->b_rcoff, &c->b_rcm, &c->b_rchain, &c->b_rrnd, &c->b_rinfo, &c->b_rdoff, &c->b_rdet, &c->b_rgenes, &c->b_rrec, &c->b_rcnt};
     for (DevBuf *b : all) release(*b);
     if (c->h_mrec) (void)hipHostFree(c->h_mrec);
     if (c->h_drec) (void)hipHostFree(c->h_drec);
     for (hipEvent_t e : c->mev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->dev_) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->rev_ev) if (e) (void)hipEventDestroy(e);
     if (c->graph_exec) (void)hipGraphExecDestroy(c->graph_exec);
     if (c->graph) (void)hipGraphDestroy(c->graph);
     if (c->h_tot) (void)hipHostFree(c->h_tot);
@@ -1277,7 +1294,7 @@ int push_layout(phx_ctx *c) {
 int launch_once(phx_ctx *c, bool learn) {
     int rc;
     c->tapw_valid = false; c->cert_done = false; c->exact_done = false; c->exact_genes.clear(); c->exact_failed = 0; c->host_only.clear();
-    c->margins_done = false; c->rev_done = false; c->drops_done = false;
+    c->margins_done = false; c->rev_done = false; c->drops_done = false; c->drop_trees = false; c->repl_done = false;
     hipStream_t s = c->stream;
     c->eager_now = c->eager_done && !c->meta0_dirty && !c->tiles_dirty; // the first launch after such an upload only: a repeated or retried run does everything
     c->eager_done = false;
@@ -2282,9 +2299,39 @@ static bool drop_contig(const phx_ctx *c, size_t i) {
 }
 static int64_t drop_cells(int n_path) { int lv = 1; while ((2 << (lv - 1)) <= n_path) lv++; return (int64_t)n_path * lv; }
 
-// The records of every pair of every device path into c->h_drec (at c->droff), once per run, on top of ensure_rev.
-static int ensure_drops(phx_ctx *c) {
-    if (c->drops_done) return PHX_OK;
+static void drop_args(phx_ctx *c, DDrop *q) {
+    const size_t n = (size_t)c->n;
+    q->pidx = (int32_t *)c->b_dpi.p; q->js = (int32_t *)c->b_djs.p; q->jt = (int32_t *)c->b_djt.p; q->first = (int32_t *)c->b_dfi.p; q->last = (int32_t *)c->b_dla.p;
+    q->slot = (uint64_t *)c->b_dslot.p; q->gtab = (uint64_t *)c->b_dgtab.p;
+    q->toff = (const int64_t *)c->b_doff.p; q->roff = (const int64_t *)c->b_doff.p + n;
+    q->sx = (uint64_t *)c->b_dsx.p; q->cx = (uint64_t *)c->b_dcx.p; q->da = (uint64_t *)c->b_dda.p; q->db = (uint64_t *)c->b_ddb.p;
+    q->rec = (phx_gene_drop *)c->b_drec.p; q->stats = (unsigned long long *)c->b_dstats.p;
+    const char *ly = getenv("PHX_DROP_LAYERED");
+    q->layered = ly && *ly && strcmp(ly, "0") != 0 ? 1 : 0;
+    q->ps = c->drop_trees ? (int32_t *)c->b_dps.p : nullptr; q->ts = c->drop_trees ? (int32_t *)c->b_dts.p : nullptr;
+}
+
+// The records of every pair of every device path into c->h_drec (at c->droff), once per run, on top of ensure_rev.  trees: the one-hop
+// trees too (DDrop.ps / ts, for the replacements); drops computed without them get k_dp_tree once more, which rewrites the same labels.
+static int ensure_drops(phx_ctx *c, bool trees = false) {
+    if (c->drops_done && (!trees || c->drop_trees)) return PHX_OK;
+    if (c->drops_done) {
+        const size_t nv = ((size_t)c->tot_node + (size_t)c->n + 1) * 4;
+        int rc;
+        if ((rc = ensure(c, c->b_dps, nv)) || (rc = ensure(c, c->b_dts, nv)) || (rc = ensure(c, c->b_rcnt, 2 * RP_NCNT * 8))) return rc;
+        c->drop_trees = true;
+        DBatch b;
+        fill_batch(c, &b);
+        DMarg g;
+        margins_args(c, &g);
+        DDrop q;
+        drop_args(c, &q);
+        q.stats = (unsigned long long *)c->b_rcnt.p + RP_NCNT; // (the drops' own counters stay as they were)
+        phxk_drop_trees(&b, &g, &q, margins_nl_mask(c), c->stream);
+        HIPCHK(c, hipGetLastError());
+        return PHX_OK;
+    }
+    if (trees) c->drop_trees = true;
     { const int rr = ensure_rev(c); if (rr) return rr; }
     const size_t n = (size_t)c->n, V = (size_t)c->tot_node;
     const size_t limbs = (size_t)std::max(c->n_limbs, 2);
@@ -2311,6 +2358,7 @@ static int ensure_drops(phx_ctx *c) {
     if ((rc = ensure(c, c->b_dda, (V + 1) * limbs * 8)) || (rc = ensure(c, c->b_ddb, (V + 1) * limbs * 8))) return rc;
     if ((rc = ensure(c, c->b_drec, ((size_t)R + 1) * sizeof(phx_gene_drop)))) return rc;
     if ((rc = ensure(c, c->b_dstats, 4 * 8))) return rc;
+    if (c->drop_trees && ((rc = ensure(c, c->b_dps, nv)) || (rc = ensure(c, c->b_dts, nv)))) return rc;
     if (c->h_drec_cap < (size_t)R + 1) {
         if (c->h_drec) HIPCHK(c, hipHostFree(c->h_drec));
         c->h_drec = nullptr; c->h_drec_cap = 0;
@@ -2324,13 +2372,7 @@ static int ensure_drops(phx_ctx *c) {
     DMarg g;
     margins_args(c, &g);
     DDrop q;
-    q.pidx = (int32_t *)c->b_dpi.p; q.js = (int32_t *)c->b_djs.p; q.jt = (int32_t *)c->b_djt.p; q.first = (int32_t *)c->b_dfi.p; q.last = (int32_t *)c->b_dla.p;
-    q.slot = (uint64_t *)c->b_dslot.p; q.gtab = (uint64_t *)c->b_dgtab.p;
-    q.toff = (const int64_t *)c->b_doff.p; q.roff = (const int64_t *)c->b_doff.p + n;
-    q.sx = (uint64_t *)c->b_dsx.p; q.cx = (uint64_t *)c->b_dcx.p; q.da = (uint64_t *)c->b_dda.p; q.db = (uint64_t *)c->b_ddb.p;
-    q.rec = (phx_gene_drop *)c->b_drec.p; q.stats = (unsigned long long *)c->b_dstats.p;
-    const char *ly = getenv("PHX_DROP_LAYERED");
-    q.layered = ly && *ly && strcmp(ly, "0") != 0 ? 1 : 0;
+    drop_args(c, &q);
     hipStream_t s = c->stream;
     unsigned long long st[4] = {0, 0, 0, 0};
     HIPCHK(c, hipEventRecord(c->dev_[0], s));
@@ -2418,6 +2460,197 @@ int phx_drop_ms(phx_ctx *c, float *ms) {
 int phx_drop_stats(phx_ctx *c, int64_t *out) {
     if (!c || !out) return PHX_E_ARG;
     for (int k = 0; k < 4; k++) out[k] = c->drop_stats[k];
+    return PHX_OK;
+}
+
+// ---- drop replacements (phx_replace.inc) ----
+// Every device record's replacement into c->h_rrec / h_rgenes / h_rdet, once per run, on top of ensure_drops (with the one-hop trees).
+static int ensure_replacements(phx_ctx *c) {
+    if (c->repl_done) return PHX_OK;
+    { const int rd = ensure_drops(c, true); if (rd) return rd; }
+    const size_t n = (size_t)c->n, V = (size_t)c->tot_node;
+    const size_t R = (size_t)c->droff[n];
+    const int nlm = margins_nl_mask(c);
+    int rc;
+    if ((rc = ensure(c, c->b_rwin, (R + 1) * 8)) || (rc = ensure(c, c->b_rxs, (R + 1) * 4)) || (rc = ensure(c, c->b_rcoff, (R + 1) * 8)) ||
+        (rc = ensure(c, c->b_rcm, (R + 1) * 4)) || (rc = ensure(c, c->b_rrnd, (V + n + 1) * 4)) || (rc = ensure(c, c->b_rinfo, (R + 1) * 16)) ||
+        (rc = ensure(c, c->b_rdoff, (2 * R + 2) * 8)) || (rc = ensure(c, c->b_rrec, (R + 1) * sizeof(phx_gene_repl))) || (rc = ensure(c, c->b_rcnt, 2 * RP_NCNT * 8)))
+        return rc;
+    if (!c->b_rchain.p) { // room for this many delta-chain nodes (env PHX_REPL_CHAIN_CAP, the tests: fewer, so that the regrowth below runs)
+        const char *cc = getenv("PHX_REPL_CHAIN_CAP");
+        c->rchain_cap = cc && *cc ? std::max<int64_t>(1, atoll(cc)) : (int64_t)V + 1;
+        if ((rc = ensure(c, c->b_rchain, ((size_t)c->rchain_cap + 1) * 4))) return rc;
+    }
+    for (hipEvent_t &e : c->rev_ev) if (!e) HIPCHK(c, hipEventCreate(&e));
+    try { c->h_rpath.assign(n, std::vector<int32_t>()); } catch (const std::bad_alloc &) { c->err = "out of memory in phx_replacements_flat"; return PHX_E_NOMEM; }
+    DBatch b;
+    fill_batch(c, &b);
+    DMarg g;
+    margins_args(c, &g);
+    DDrop q;
+    drop_args(c, &q);
+    DRepl r;
+    auto args = [&]() {
+        r.win = (uint64_t *)c->b_rwin.p; r.xs = (int32_t *)c->b_rxs.p; r.coff = (int64_t *)c->b_rcoff.p; r.cm = (int32_t *)c->b_rcm.p;
+        r.chain = (int32_t *)c->b_rchain.p; r.ccap = c->rchain_cap; // (b_rchain was ensured for rchain_cap + 1 entries)
+        r.rnd = (int32_t *)c->b_rrnd.p; r.info = (int32_t *)c->b_rinfo.p;
+        r.doff = (const int64_t *)c->b_rdoff.p; r.goff = (const int64_t *)c->b_rdoff.p + R + 1;
+        r.det = (int32_t *)c->b_rdet.p; r.genes = (phx_gene *)c->b_rgenes.p; r.rec = (phx_gene_repl *)c->b_rrec.p;
+        r.cnt = (unsigned long long *)c->b_rcnt.p;
+    };
+    args();
+    hipStream_t s = c->stream;
+    // The event pairs bracket device work only: the host's read-backs and offsets between the passes fall outside every pair.
+    unsigned long long cnt[RP_NCNT] = {0};
+    hipEvent_t *ev = c->rev_ev;
+    bool regrown = false;
+    HIPCHK(c, hipEventRecord(ev[0], s));
+    HIPCHK(c, hipMemsetAsync(c->b_rcnt.p, 0, RP_NCNT * 8, s));
+    HIPCHK(c, hipMemsetAsync(c->b_rwin.p, 0xff, (R + 1) * 8, s));
+    phxk_repl_pick(&b, &g, &q, &r, nlm, s);
+    phxk_repl_cross(&b, &g, &q, &r, nlm, s);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev[1], s));
+    HIPCHK(c, hipMemcpyAsync(cnt, c->b_rcnt.p, sizeof cnt, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if ((int64_t)cnt[0] > r.ccap) { // the delta chains did not fit: room for all of them, and the cross winners once more
+        c->rchain_cap = (int64_t)cnt[0];
+        if ((rc = ensure(c, c->b_rchain, ((size_t)c->rchain_cap + 1) * 4))) return rc;
+        args();
+        regrown = true;
+        HIPCHK(c, hipEventRecord(ev[2], s));
+        HIPCHK(c, hipMemsetAsync(c->b_rcnt.p, 0, RP_NCNT * 8, s));
+        phxk_repl_cross(&b, &g, &q, &r, nlm, s);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(ev[3], s));
+        HIPCHK(c, hipMemcpyAsync(cnt, c->b_rcnt.p, sizeof cnt, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        if ((int64_t)cnt[0] > r.ccap) { c->err = "drop replacements: the delta chains outgrew their buffer twice"; return PHX_E_STATE; }
+    }
+    // counting pass, offsets, filling pass
+    HIPCHK(c, hipEventRecord(ev[4], s));
+    phxk_repl_walk(&b, &g, &q, &r, 0, s);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev[5], s));
+    c->h_rinfo.resize(4 * R + 4);
+    if (R) HIPCHK(c, hipMemcpyAsync(c->h_rinfo.data(), c->b_rinfo.p, R * 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(cnt, c->b_rcnt.p, sizeof cnt, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (cnt[1]) { c->err = "drop replacements: a slot with a bypass has no witness"; return PHX_E_STATE; }
+    c->repl_stats[0] = (int64_t)cnt[2]; c->repl_stats[1] = (int64_t)cnt[0]; c->repl_stats[2] = (int64_t)cnt[3]; c->repl_stats[3] = (int64_t)cnt[4];
+    c->repl_stats[4] = regrown ? 1 : 0;
+    try {
+        std::vector<int64_t> off(2 * R + 2);
+        int64_t nd = 0, ng = 0;
+        for (size_t k = 0; k < R; k++) { off[k] = nd; off[R + 1 + k] = ng; nd += c->h_rinfo[4 * k + 2]; ng += c->h_rinfo[4 * k + 3]; }
+        off[R] = nd; off[2 * R + 1] = ng;
+        c->h_rdoff.assign(off.begin(), off.begin() + (R + 1));
+        if ((rc = ensure(c, c->b_rdet, ((size_t)nd + 1) * 4)) || (rc = ensure(c, c->b_rgenes, ((size_t)ng + 1) * sizeof(phx_gene)))) return rc;
+        args();
+        HIPCHK(c, hipMemcpyAsync(c->b_rdoff.p, off.data(), (2 * R + 2) * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipEventRecord(ev[6], s));
+        phxk_repl_walk(&b, &g, &q, &r, 1, s);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(ev[7], s));
+        c->h_rrec.resize(R + 1); c->h_rdet.resize((size_t)nd + 1); c->h_rgenes.resize((size_t)ng + 1);
+        if (R) HIPCHK(c, hipMemcpyAsync(c->h_rrec.data(), c->b_rrec.p, R * sizeof(phx_gene_repl), hipMemcpyDeviceToHost, s));
+        if (nd) HIPCHK(c, hipMemcpyAsync(c->h_rdet.data(), c->b_rdet.p, (size_t)nd * 4, hipMemcpyDeviceToHost, s));
+        if (ng) HIPCHK(c, hipMemcpyAsync(c->h_rgenes.data(), c->b_rgenes.p, (size_t)ng * sizeof(phx_gene), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipEventRecord(ev[8], s));
+        HIPCHK(c, hipStreamSynchronize(s));
+    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_replacements_flat"; return PHX_E_NOMEM; }
+    auto span = [&](int k0, int k1) { float ms = 0; return hipEventElapsedTime(&ms, ev[k0], ev[k1]) == hipSuccess ? ms : 0.0f; };
+    c->repl_ms[0] = span(0, 1) + (regrown ? span(2, 3) : 0.0f);
+    c->repl_ms[1] = span(4, 5) + span(6, 7);
+    c->repl_ms[2] = span(7, 8);
+    c->repl_done = true;
+    return PHX_OK;
+}
+
+int phx_replacements_flat(phx_ctx *c, phx_gene_repl *rec, int64_t cap, phx_gene *genes, int64_t gene_cap, int64_t *offsets, int32_t *status,
+                          int64_t *total_out, int64_t *gene_total_out) {
+    if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
+    if (c->in_flight) { const int rs = phx_wait(c); if (rs) return rs; }
+    if (!c->ran) return PHX_E_STATE;
+    HIPCHK(c, hipSetDevice(c->device));
+    { const int rr = ensure_replacements(c); if (rr) return rr; }
+    // statuses, offsets and `called` exactly as the drop records have them
+    int64_t total = 0;
+    { const int rd = phx_drop_margins_flat(c, nullptr, 0, offsets, status, &total); if (rd) return rd; }
+    try {
+    std::vector<phx_gene_drop> drec((size_t)total + 1);
+    { const int rd = phx_drop_margins_flat(c, drec.data(), total, offsets, status, &total); if (rd) return rd; }
+    int64_t gt = 0;
+    for (int i = 0; i < c->n; i++) {
+        if (offsets[i + 1] == offsets[i]) continue;
+        for (int64_t k = c->droff[(size_t)i]; k < c->droff[(size_t)i + 1]; k++) if (c->h_rrec[k].called >= 0) gt += c->h_rrec[k].n_removed + c->h_rrec[k].n_added;
+    }
+    if (total_out) *total_out = total;
+    if (gene_total_out) *gene_total_out = gt;
+    if (!rec || !genes) return PHX_OK; // size query
+    if (cap < total || gene_cap < gt) return PHX_E_ARG;
+    int64_t go = 0;
+    for (int i = 0; i < c->n; i++) {
+        if (offsets[i + 1] == offsets[i]) continue;
+        phx_gene_repl *dst = rec + offsets[i];
+        const phx_gene_drop *dd = drec.data() + offsets[i];
+        for (int64_t k = c->droff[(size_t)i]; k < c->droff[(size_t)i + 1]; k++) {
+            const phx_gene_repl &x = c->h_rrec[k];
+            if (x.called < 0) continue;
+            *dst = x;
+            dst->called = dd->called;
+            dst->gene_off = go;
+            const int64_t ng = x.n_removed + x.n_added;
+            if (ng) memcpy(genes + go, c->h_rgenes.data() + x.gene_off, (size_t)ng * sizeof(phx_gene));
+            go += ng;
+            dst++; dd++;
+        }
+    }
+    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_replacements_flat"; return PHX_E_NOMEM; }
+    return PHX_OK;
+}
+
+int phx_tap_replacement(phx_ctx *c, int32_t contig, int32_t k, int32_t *path, int32_t cap, int32_t *n_path) {
+    if (!c || !n_path) return PHX_E_ARG;
+    *n_path = 0;
+    if (c->in_flight) { const int rs = phx_wait(c); if (rs) return rs; }
+    if (!c->ran) return PHX_E_STATE;
+    if (contig < 0 || contig >= c->n || k < 0) return PHX_E_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    { const int rr = ensure_replacements(c); if (rr) return rr; }
+    if (!drop_contig(c, (size_t)contig) || margins_status(c, contig) != 0) return PHX_E_ARG;
+    int64_t rk = -1;
+    for (int64_t q = c->droff[(size_t)contig], seen = 0; q < c->droff[(size_t)contig + 1]; q++)
+        if (c->h_rrec[q].called >= 0 && seen++ == k) { rk = q; break; }
+    if (rk < 0) return PHX_E_ARG;
+    if (!c->h_rrec[rk].bypass) return PHX_OK;
+    const DMeta &m = c->meta[(size_t)contig];
+    const int a = c->h_rinfo[4 * rk], b = c->h_rinfo[4 * rk + 1], nd = c->h_rinfo[4 * rk + 2];
+    const int len = (a + 1) + nd + (m.n_path - b);
+    *n_path = len;
+    if (!path) return PHX_OK;
+    if (cap < len) return PHX_E_ARG;
+    std::vector<int32_t> &P = c->h_rpath[(size_t)contig]; // (the contig's device path, fetched at its first tap of this run)
+    if (P.empty()) {
+        try { P.resize((size_t)m.n_path); } catch (const std::bad_alloc &) { c->err = "out of memory in phx_tap_replacement"; return PHX_E_NOMEM; }
+        HIPCHK(c, hipMemcpy(P.data(), (int32_t *)c->b_path.p + m.node_off, (size_t)m.n_path * 4, hipMemcpyDeviceToHost));
+    }
+    int32_t *o = path;
+    for (int t = 0; t <= a; t++) *o++ = P[(size_t)t];
+    for (int t = 0; t < nd; t++) *o++ = c->h_rdet[(size_t)c->h_rdoff[(size_t)rk] + t];
+    for (int t = b; t < m.n_path; t++) *o++ = P[(size_t)t];
+    return PHX_OK;
+}
+
+int phx_replacements_ms(phx_ctx *c, float *ms) {
+    if (!c || !ms) return PHX_E_ARG;
+    for (int k = 0; k < 3; k++) ms[k] = c->repl_ms[k];
+    return PHX_OK;
+}
+
+int phx_replacement_stats(phx_ctx *c, int64_t *out) {
+    if (!c || !out) return PHX_E_ARG;
+    for (int k = 0; k < 5; k++) out[k] = c->repl_stats[k];
     return PHX_OK;
 }
 

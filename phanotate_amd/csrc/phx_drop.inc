@@ -74,10 +74,11 @@ __device__ __forceinline__ WInt<NL> wave_min(WInt<NL> x) {
 __device__ __forceinline__ uint64_t ld_l2(const uint64_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // ---- 1. k_dp_tree<NL>: trees and labels, one workgroup per contig ----
-// DDrop.js / jt: the jump pointers (a node on P points at itself; -1: unreached), then first / last.  The doubling reads and writes js in
-// place: a value read mid-round is a later ancestor on the same chain, so the rounds only get shorter.  ceil(log2 V) + 1 rounds reach P from
-// any chain that reaches it at all; a node whose pointer is then still off P sits on a tight zero-length cycle of the chosen parents, and
-// the tree is rebuilt by layers: round r lets a node join through a tight edge to a node that joined before round r (P itself is layer 0),
+// DDrop.js / jt: the jump pointers (a node on P points at itself; -1: unreached), then first / last.  DDrop.ps / ts, when not null,
+// keep the one-hop parents / successors the labels were built from (the layered build: the node a node joined through).  The doubling
+// reads and writes js in place: a value read mid-round is a later ancestor on the same chain, so the rounds only get shorter.
+// ceil(log2 V) + 1 rounds reach P from any chain that reaches it at all; a node whose pointer is then still off P sits on a tight
+// zero-length cycle of the chosen parents, and the tree is rebuilt by layers: round r lets a node join through a tight edge to a node that joined before round r (P itself is layer 0),
 // which cannot close a cycle.  DDrop.layered forces the layered build (env PHX_DROP_LAYERED, the tests).
 template <int NL>
 __global__ __launch_bounds__(NT) void k_dp_tree(DBatch b, DMarg g, DDrop q) {
@@ -128,6 +129,7 @@ __global__ __launch_bounds__(NT) void k_dp_tree(DBatch b, DMarg g, DDrop q) {
             }
         }
         js[v] = ps; jt[v] = ts;
+        if (q.ps) { q.ps[no + v] = ps; q.ts[no + v] = ts; } // (the replacements' one-hop trees, §13)
         if (ps == -2) s_fail[0] = 1;
         if (ts == -2) s_fail[1] = 1;
     }
@@ -173,6 +175,7 @@ __global__ __launch_bounds__(NT) void k_dp_tree(DBatch b, DMarg g, DDrop q) {
                         const WInt<NL> du = wi_load<NL>(ds + (size_t)u * NL);
                         if (!wi_unreached<NL>(du) && wi_eq<NL>(wi_add<NL>(du, ew_decode<NL>(edge_wenc(sw, ew, e, gt))), dv)) {
                             first[v] = first[u]; js[v] = r; s_chg = 1;
+                            if (q.ps) q.ps[no + v] = u;
                             break;
                         }
                     }
@@ -187,7 +190,7 @@ __global__ __launch_bounds__(NT) void k_dp_tree(DBatch b, DMarg g, DDrop q) {
                         const WInt<NL> tz = wi_load<NL>(dt + (size_t)z * NL);
                         if (!wi_unreached<NL>(tz) && wi_eq<NL>(wi_add<NL>(tz, ew_decode<NL>(ow[e])), tv)) best = z;
                     }
-                    if (best >= 0) { last[v] = last[best]; jt[v] = r; s_chg = 1; }
+                    if (best >= 0) { last[v] = last[best]; jt[v] = r; s_chg = 1; if (q.ts) q.ts[no + v] = best; }
                 }
             }
         }

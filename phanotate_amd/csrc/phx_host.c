@@ -512,6 +512,108 @@ int phx_format_drops(int32_t n, const char *const *names, const phx_gene_drop *r
     return PHX_OK;
 }
 
+/* ---- --drop-replacements FILE: per contig the called genes of the device path with what replaces them (include/phx.h) ---- */
+typedef struct {
+    int32_t c0, c1;
+    const char *const *names;
+    const phx_gene_repl *rec;
+    const phx_gene *genes;
+    const int64_t *offsets;
+    const int32_t *status;
+    char *dst;
+    int64_t len;
+} rfmt_job;
+
+static char *put_gene_list(char *p, const phx_gene *g, int32_t n) {
+    if (n <= 0) { *p++ = '-'; return p; }
+    for (int32_t k = 0; k < n; k++) {
+        if (k) *p++ = ',';
+        if (g[k].frame == 4 || g[k].frame == -4) { memcpy(p, "tRNA:", 5); p += 5; }
+        p = put_int(p, g[k].strand < 0 ? g[k].right : g[k].left);
+        *p++ = '.'; *p++ = '.';
+        p = put_int(p, g[k].strand < 0 ? g[k].left : g[k].right);
+    }
+    return p;
+}
+
+static void *rfmt_work(void *arg) {
+    rfmt_job *j = (rfmt_job *)arg;
+    char *p = j->dst;
+    for (int32_t i = j->c0; i < j->c1; i++) {
+        if (j->status[i] < 0) continue;
+        const char *nm = j->names[i];
+        const size_t ln = strlen(nm);
+        memcpy(p, "#id:\t", 5); p += 5;
+        memcpy(p, nm, ln); p += ln;
+        *p++ = '\n';
+        memcpy(p, "#START\tSTOP\tFRAME\tCONTIG\tDROP\tREMOVED\tADDED\n", 44); p += 44;
+        for (int64_t k = j->offsets[i]; k < j->offsets[i + 1]; k++) {
+            const phx_gene_repl *g = &j->rec[k];
+            const int32_t a = g->strand < 0 ? g->right : g->left, z = g->strand < 0 ? g->left : g->right; /* as the tabular writer, locus.py:44-46 */
+            p = put_int(p, a); *p++ = '\t';
+            p = put_int(p, z); *p++ = '\t';
+            *p++ = (char)(44 - g->strand); *p++ = '\t';
+            memcpy(p, nm, ln); p += ln;
+            *p++ = '\t';
+            p += phx_snprintf_c(p, 25, "%E", g->drop);
+            *p++ = '\t';
+            p = put_gene_list(p, j->genes + g->gene_off, g->n_removed);
+            *p++ = '\t';
+            p = put_gene_list(p, j->genes + g->gene_off + g->n_removed, g->n_added);
+            *p++ = '\n';
+        }
+    }
+    j->len = p - j->dst;
+    return NULL;
+}
+
+int phx_format_replacements(int32_t n, const char *const *names, const phx_gene_repl *rec, const phx_gene *genes, const int64_t *offsets,
+                            const int32_t *status, char **text, int64_t *text_len) {
+    if (n < 0 || !text || !text_len || (n > 0 && (!names || !offsets || !status))) return PHX_E_ARG;
+    *text = NULL; *text_len = 0;
+    if (n > 0 && offsets[n] > offsets[0] && !rec) return PHX_E_ARG;
+    /* upper bound: header lines + per record two coordinates (11 each), strand, name, the drop (<= 24), per gene "tRNA:" and two
+     * coordinates (30), separators */
+    int64_t *bound = (int64_t *)malloc(sizeof(int64_t) * (size_t)(n + 1));
+    if (!bound) return PHX_E_NOMEM;
+    int64_t need = 1;
+    for (int32_t i = 0; i < n; i++) {
+        bound[i] = need;
+        if (status[i] < 0) continue;
+        if (offsets[i + 1] < offsets[i]) { free(bound); return PHX_E_ARG; }
+        const int64_t ln = (int64_t)strlen(names[i]);
+        need += 6 + ln + 1 + 44 + (offsets[i + 1] - offsets[i]) * (11 + 1 + 11 + 1 + 1 + 1 + ln + 1 + 24 + 1 + 1 + 1 + 1 + 1);
+        for (int64_t k = offsets[i]; k < offsets[i + 1]; k++) {
+            if (rec[k].n_removed < 0 || rec[k].n_added < 0 || ((rec[k].n_removed || rec[k].n_added) && (!genes || rec[k].gene_off < 0))) { free(bound); return PHX_E_ARG; }
+            need += 30 * ((int64_t)rec[k].n_removed + rec[k].n_added);
+        }
+    }
+    bound[n] = need;
+    char *b = (char *)malloc((size_t)need);
+    if (!b) { free(bound); return PHX_E_NOMEM; }
+    rfmt_job job[16];
+    const int T = need < (1 << 20) ? 1 : host_threads();
+    int nj = 0;
+    int32_t c = 0;
+    for (int t = 0; t < T && c < n; t++) {
+        const int64_t target = t + 1 == T ? need : bound[0] + (need - bound[0]) / T * (t + 1);
+        int32_t e = c;
+        while (e < n && (bound[e + 1] <= target || e == c)) e++;
+        if (t + 1 == T) e = n;
+        job[nj].c0 = c; job[nj].c1 = e; job[nj].names = names; job[nj].rec = rec; job[nj].genes = genes; job[nj].offsets = offsets; job[nj].status = status;
+        job[nj].dst = b + (bound[c] - 1); job[nj].len = 0;
+        nj++;
+        c = e;
+    }
+    if (nj) run_threads(rfmt_work, job, sizeof(rfmt_job), nj);
+    free(bound);
+    char *p = b;
+    for (int t = 0; t < nj; t++) { if (job[t].dst != p) memmove(p, job[t].dst, (size_t)job[t].len); p += job[t].len; }
+    *p = 0;
+    *text = b; *text_len = p - b;
+    return PHX_OK;
+}
+
 void phx_free_text(char *text) { free(text); }
 
 /* ---- bases packed for the link and for the kernels (phx_upload): residue-split bit planes ----

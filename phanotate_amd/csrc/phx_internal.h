@@ -358,6 +358,23 @@ struct DDrop {
     phx_gene_drop *rec;   // per record (called = -1: the pair is no CDS gene)
     unsigned long long *stats; // [4]: gene slots, slots with cross nodes, saturated slots rescanned, contigs built by layers
     int32_t layered;      // 1: every tree by layers (env PHX_DROP_LAYERED)
+    int32_t *ps, *ts;     // per node, or null: the one-hop parent of T_s / successor of T_t (a node on P: itself; -1: unreached) (§13)
+};
+// Drop replacements (phx_replace.inc), on demand after the drop margins: the context's lazily allocated buffers
+struct DRepl {
+    uint64_t *win;        // per record: the winner, x << 32 | z (step 3) or RP_CROSS | y << 32 | z (step 4); ~0: none
+    int32_t *xs;          // per record: the seed source x of a cross winner
+    int64_t *coff;        // per record: its delta chain y_0 .. y in chain
+    int32_t *cm;          //   ... and the chain's length
+    int32_t *chain;       // delta chains, placed by the counter cnt[0] up to ccap (beyond: counted only, the host grows it and reruns)
+    int64_t ccap;
+    int32_t *rnd;         // per node: the round the delta of cross list entry p settled in (0: its seed)
+    int32_t *info;        // per record [4]: a, b, m (the detour's length), its genes (n_removed + n_added)
+    const int64_t *doff, *goff; // per record: first detour node in det, first gene in genes
+    int32_t *det;         // the detours r_1 .. r_m
+    phx_gene *genes;      // removed, then added genes of every record
+    phx_gene_repl *rec;   // per record (called = -1: the pair is no CDS gene)
+    unsigned long long *cnt; // [2]: chain nodes placed, records with a bypass but no winner (0 unless a bug)
 };
 
 #ifdef __cplusplus
@@ -404,6 +421,9 @@ void phxk_margins(const DBatch *b, const DMarg *g, int nl_mask, void *stream); /
 void phxk_drop_trees(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream); // gene drop margins (phx_drop.inc): trees + labels,
 void phxk_drop_cand(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream);  //   candidates + sparse table,
 void phxk_drop_fix(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream);   //   saturated slots, cross nodes, records
+void phxk_repl_pick(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream); // drop replacements (phx_replace.inc): winners,
+void phxk_repl_cross(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream); //   cross winners and their delta chains,
+void phxk_repl_walk(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int fill, void *stream);    //   detour lengths (fill 0) / detours, genes, records (1)
 #ifdef __cplusplus
 }
 #endif

@@ -179,6 +179,7 @@ __device__ __forceinline__ int min_idx(int a, int b, int c) { return a > b ? (b 
 #include "phx_certify.inc"
 #include "phx_margins.inc"
 #include "phx_drop.inc"
+#include "phx_replace.inc"
 
 // ------------------------------------------------------------------------------------------------
 // launchers
@@ -385,6 +386,20 @@ void phxk_drop_fix(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask,
     DP_LAUNCH(k_dp_rescan, nl_mask);
     DP_LAUNCH(k_dp_cross, nl_mask);
     DP_LAUNCH(k_dp_rec, nl_mask);
+}
+// drop replacements (phx_replace.inc): a workgroup per contig
+#define RP_LAUNCH(K, NLM) do { \
+        if ((NLM) & 1) hipLaunchKernelGGL(K<2>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q, *r); \
+        if ((NLM) & 2) hipLaunchKernelGGL(K<4>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q, *r); \
+        if ((NLM) & 4) hipLaunchKernelGGL(K<8>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q, *r); \
+        if ((NLM) & 8) hipLaunchKernelGGL(K<17>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q, *r); \
+    } while (0)
+void phxk_repl_pick(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; RP_LAUNCH(k_rp_pick, nl_mask); }
+void phxk_repl_cross(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; RP_LAUNCH(k_rp_cross, nl_mask); }
+void phxk_repl_walk(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int fill, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (fill) hipLaunchKernelGGL(k_rp_walk<1>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q, *r);
+    else hipLaunchKernelGGL(k_rp_walk<0>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q, *r);
 }
 size_t phxk_sssp_lds_bytes(int V, int nl) { return sssp_lds_bytes(V, nl); }
 // one workgroup for up to 1024 contigs; larger batches in two passes of a workgroup per 256 contigs

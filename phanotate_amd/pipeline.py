@@ -59,6 +59,7 @@ class Pipeline:
         self.depth = max(1, int(depth))
         self._margins = False
         self._drops = False
+        self._repl = False
         self.lanes = []
         try:
             for j, d in enumerate(devs):
@@ -79,13 +80,15 @@ class Pipeline:
     def __exit__(self, *exc):
         self.close()
 
-    def run(self, batches, margins=False, drop_margins=False):
+    def run(self, batches, margins=False, drop_margins=False, replacements=False):
         """Generator over (status, offsets, genes) of every batch (Annotator.download_flat), in order.  While the caller consumes
         batch k, the batches behind it are already running.  margins=True: every item gains the batch's (status, offsets, records) of
         Annotator.margins(), fetched after the download on the same context; drop_margins=True: then the triple of
-        Annotator.drop_margins() (after the margins' when both are asked for)."""
+        Annotator.drop_margins() (after the margins' when both are asked for); replacements=True: then the quadruple of
+        Annotator.replacements()."""
         self._margins = bool(margins)
         self._drops = bool(drop_margins)
+        self._repl = bool(replacements)
         if len(self.lanes) == 1:
             yield from self._run_one(self.lanes[0], batches)
             return
@@ -95,8 +98,11 @@ class Pipeline:
         res = a.download_flat()
         if self._margins:
             res = res + (a.margins(),)
+        repl = a.replacements() if self._repl else None  # (first: the drops are then computed once, with the trees it needs)
         if self._drops:
             res = res + (a.drop_margins(),)
+        if self._repl:
+            res = res + (repl,)
         return res
 
     def _run_one(self, lane, batches):
