@@ -392,6 +392,35 @@ int phx_replacements_ms(phx_ctx *ctx, float *ms /* [3] */);
  * buffer had to grow (the cross winners were then computed a second time). */
 int phx_replacement_stats(phx_ctx *ctx, int64_t *out /* [5] */);
 
+/* ---- masked re-annotation, on demand after a run ----
+ * The general operation the margins above are special cases of: take a set F of candidate ORFs out of the resident device graph G and
+ * solve again.  G_F is G without the ORF edges of F (nodes, connectors, bridges and tRNA edges stay; an ORF without an edge in the graph
+ * is ignored), D_F the shortest source -> target distance in G_F in the contig's own limb class, delta = float(D_F - D) / 1000.0 as the
+ * margins round it (>= 0; +inf with PHX_S_NOPATH when G_F has no path).  The path is the one an in-place Bellman-Ford over
+ * Graph.iteredges order restricted to G_F leaves (strict <): with F empty the device path byte for byte, ties included.  The genes are
+ * that path's, in the record format and order of phx_download_flat with exactness off.  It is over the device's integers and the device
+ * graph (no certificate, no host re-solve), and it is not a re-run of the front end: GC-frame training and connector edges are those of
+ * the full ORF set.
+ *   forbid       one byte per ORF of the batch (non-zero: refused), contig i's at orf_offsets[i] .. orf_offsets[i+1], in phx_tap_orfs order
+ *   orf_offsets  [n+1]: must equal the cumulative ORF counts of the batch last run (the offsets phx_margins_flat reports), else PHX_E_ARG
+ *                and no kernel has run
+ *   flags        bit 0: solve every contig again, also one whose mask is empty (without it such a contig's result is copied from the run)
+ *   genes        NULL: size query (offsets, status, delta, total are filled in)
+ * status[i]: a run error (< 0) passes through without genes; PHX_S_OVERFLOW for a contig without device distances; PHX_S_NOPATH when the
+ * run had no path or G_F has none (0 genes, delta +inf; delta is +inf for every contig without a result); PHX_S_NEGCYCLE when a sweep or
+ * round cap ended the solve; else 0.  Neighbours are unaffected.  Buffers are allocated at the first call; the result is invalidated by
+ * the next upload or run; nothing phx_download*, the taps, the margins, the drops, the replacements or the certificate return changes. */
+int phx_reannotate_flat(phx_ctx *ctx, const uint8_t *forbid, const int64_t *orf_offsets /* [n+1] */, uint32_t flags, phx_gene *genes, int64_t cap,
+                        int64_t *offsets /* [n+1] */, int32_t *status /* [n] */, double *delta /* [n] */, int64_t *total);
+/* orf_offsets[n+1] of the batch last run as phx_reannotate_flat expects them: cumulative ORF counts, a contig with a run error or without
+ * device distances counting none (the offsets phx_margins_flat reports, without computing the margins or the certificate). */
+int phx_orf_offsets(phx_ctx *ctx, int64_t *orf_offsets /* [n+1] */);
+/* path and D_F of the last re-annotation, like phx_tap_path (a contig that was not solved again: the run's).  PHX_E_STATE without one. */
+int phx_tap_repath(phx_ctx *ctx, int32_t contig, int32_t *path, int32_t cap, int32_t *n_path, uint64_t *dist_limbs, int32_t cap_limbs);
+/* device time of the last re-annotation (HIP events around device work only), ms[3]: mask build, masked solve, in-order parents + path +
+ * genes + the copies to the host.  All 0 before the first. */
+int phx_reannotate_ms(phx_ctx *ctx, float *ms /* [3] */);
+
 /* -d/--dump of the reference (phanotate.py:58,61) for one contig of the batch last run: one line per edge of its graph,
  *     repr(source) TAB repr(target) TAB str(weight * 1000)                                   (edges.py:17-23, nodes.py:14-21)
  * in Graph.iteredges order, the weights as the reference's 28-digit Decimals (the chain replayed by csrc/phx_dec.c on the integers

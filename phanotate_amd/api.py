@@ -143,6 +143,7 @@ class Annotator:
         self._keep = (seqs, arr, lens)
         self._chk(self.L.phx_upload(self.h, n, arr, lens), "phx_upload")
         self.n = n
+        self._orf_offs = None
 
     def upload_raw(self, ptrs, lens, keep=None):
         """The same from raw addresses: ptrs uint64[n] (host memory that stays valid for the call), lens int64[n]."""
@@ -151,6 +152,7 @@ class Annotator:
         self._keep = (ptrs, lens, keep)
         self._chk(self.L.phx_upload(self.h, len(lens), C.cast(ptrs.ctypes.data, C.POINTER(C.c_char_p)), C.cast(lens.ctypes.data, C.POINTER(C.c_int64))), "phx_upload")
         self.n = len(lens)
+        self._orf_offs = None
 
     def attach(self, dev_ptr, offsets):
         """Concatenated ASCII already in HBM (e.g. a torch uint8 tensor's data_ptr()); offsets has n+1 entries."""
@@ -158,6 +160,7 @@ class Annotator:
         self._keep = (offs,)
         self._chk(self.L.phx_attach(self.h, len(offsets) - 1, C.c_void_p(int(dev_ptr)), offs), "phx_attach")
         self.n = len(offsets) - 1
+        self._orf_offs = None
 
     def set_trnas(self, trnas):
         """tRNA hits for the batch just uploaded: one list of (start, stop) per contig, as functions.add_trnas holds them
@@ -176,11 +179,13 @@ class Annotator:
 
     def run(self):
         self._chk(self.L.phx_run(self.h), "phx_run")
+        self._orf_offs = None
 
     def run_async(self):
         """Enqueue the run and return (phx_run_async); wait() — or any other call on this context — collects it.  With two
         contexts alternating, one batch's upload and kernels overlap the other's shortest-path kernel: see pipeline.Pipeline."""
         self._chk(self.L.phx_run_async(self.h), "phx_run_async")
+        self._orf_offs = None
 
     def wait(self):
         self._chk(self.L.phx_wait(self.h), "phx_wait")
@@ -426,6 +431,84 @@ class Annotator:
         out = (C.c_int64 * 5)()
         self._chk(self.L.phx_replacement_stats(self.h, out), "phx_replacement_stats")
         return dict(zip(("cross", "chain_nodes", "cross_kept", "cut", "regrown"), [int(x) for x in out]))
+
+    # ---- masked re-annotation ----
+    def orf_offsets(self):
+        """int64[n+1]: cumulative ORF counts of the batch last run, the offsets margins() reports (a contig with a run error or without
+        device distances counts no ORFs; phx_orf_offsets)."""
+        if getattr(self, "_orf_offs", None) is None:
+            offs = np.zeros(self.n + 1, np.int64)
+            self._chk(self.L.phx_orf_offsets(self.h, offs.ctypes.data_as(C.c_void_p)), "phx_orf_offsets")
+            self._orf_offs = offs
+        return self._orf_offs
+
+    def orf_index(self, i, left, right, strand):
+        """Index in orfs(i) of the ORF with these ends (left, right and strand as a gene record carries them: right includes the stop
+        codon).  KeyError when contig i has no such ORF."""
+        cache = getattr(self, "_orf_index", None)
+        if cache is None or cache[0] is not self.orf_offsets() or cache[1] != i:
+            o = self.orfs(i)
+            fwd = o["frame"] > 0
+            lo = np.where(fwd, o["start"], o["stop"])
+            hi = np.where(fwd, o["stop"], o["start"]) + 2
+            table = {}
+            for k, key in enumerate(zip(lo.tolist(), hi.tolist(), fwd.tolist())):
+                table.setdefault(key, k)
+            cache = self._orf_index = (self.orf_offsets(), i, table)
+        try:
+            return cache[2][(int(left), int(right), int(strand) > 0)]
+        except KeyError:
+            raise KeyError("contig %d has no ORF %d..%d on strand %+d" % (i, left, right, 1 if int(strand) > 0 else -1)) from None
+
+    def reannotate(self, forbid, solve_all=False):
+        """(status int32[n], offsets int64[n+1], genes structured array[total], delta float64[n]): the batch last run annotated again
+        without the ORFs of `forbid` — one array of indices into orfs(i) per contig, or None — on the resident device graph
+        (phx_reannotate_flat).  genes[offsets[i]:offsets[i+1]] are contig i's, in the format and order of download_flat(exact=False);
+        delta[i] = float(D_F - D) / 1000 (+inf: no path without them, status 1).  A contig with an empty mask keeps the run's result
+        unless solve_all.  Not a re-run of the front end: GC-frame training and connector edges are those of the full ORF set."""
+        n = self.n
+        if len(forbid) != n:
+            raise ValueError("one index array (or None) per contig of the batch")
+        oo = self.orf_offsets()
+        mask = np.zeros(max(int(oo[n]), 1), np.uint8)
+        for i, f in enumerate(forbid):
+            if f is None:
+                continue
+            idx = np.asarray(f, np.int64).reshape(-1)
+            if idx.size and (idx.min() < 0 or idx.max() >= oo[i + 1] - oo[i]):
+                raise IndexError("contig %d has %d ORFs" % (i, oo[i + 1] - oo[i]))
+            mask[oo[i] + idx] = 1
+        offs = np.zeros(n + 1, np.int64)
+        status = np.zeros(max(n, 1), np.int32)
+        delta = np.zeros(max(n, 1), np.float64)
+        total = C.c_int64(0)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        fl = 1 if solve_all else 0
+        self._chk(self.L.phx_reannotate_flat(self.h, vp(mask), vp(oo), fl, None, 0, vp(offs), vp(status), vp(delta), C.byref(total)), "phx_reannotate_flat")
+        genes = np.empty(max(int(total.value), 1), _lib.GENE_DT)
+        self._chk(self.L.phx_reannotate_flat(self.h, vp(mask), vp(oo), fl, vp(genes), len(genes), vp(offs), vp(status), vp(delta), C.byref(total)), "phx_reannotate_flat")
+        return status[:n], offs, genes[: int(total.value)], delta[:n]
+
+    def reannotated_path(self, i):
+        """(path as device node ids, D_F as a python int) of contig i in the last re-annotation, like path(i)."""
+        g = self.globals(i)
+        p = np.zeros(max(g.n_node, 1), np.int32)
+        n = C.c_int32()
+        limbs = np.zeros(32, np.uint64)
+        self._chk(self.L.phx_tap_repath(self.h, i, p.ctypes.data_as(C.c_void_p), len(p), C.byref(n), limbs.ctypes.data_as(C.c_void_p), 32), "phx_tap_repath")
+        nl = max(g.n_limbs, 1)
+        v = 0
+        for k in range(nl):
+            v |= int(limbs[k]) << (64 * k)
+        if v >> (64 * nl - 1):
+            v -= 1 << (64 * nl)
+        return p[: n.value].copy(), v
+
+    def reannotate_ms(self):
+        """Device time of the last re-annotation in ms: mask build, masked solve, path + genes + copy (phx_reannotate_ms)."""
+        ms = (C.c_float * 3)()
+        self._chk(self.L.phx_reannotate_ms(self.h, ms), "phx_reannotate_ms")
+        return dict(zip(("mask", "solve", "finish"), [float(x) for x in ms]))
 
     def drop_stats(self):
         """Counters of the last drop-margins computation (phx_drop_stats): gene slots, slots with cross nodes, saturated slots rescanned

@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <limits>
 #include <map>
 #include <string>
 #include <thread>
@@ -250,6 +251,21 @@ struct phx_ctx {
     hipEvent_t rev_ev[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     float repl_ms[3] = {0, 0, 0};
     int64_t repl_stats[5] = {0, 0, 0, 0, 0};
+    // masked re-annotation (phx_reannotate_flat): buffers allocated at the first call, the result kept until the next upload or run
+    DevBuf b_qmeta, b_qtot, b_qdist, b_qparent, b_qpath, b_qgenes, b_qgtot, b_qtie, b_qmask, b_qforb, b_qsel, b_qplan, b_qrec;
+    bool reann_done = false;          // h_q* hold the re-annotation of the run whose results the context holds, for the mask h_qforb / h_qflags
+    bool qgrp_done = false;           // qgrp holds that run's group records (tap order <-> device order of the ORFs)
+    std::vector<DGrp> qgrp;
+    std::vector<uint8_t> h_qforb;     // the mask last solved, tap order (one byte per ORF of the batch)
+    uint32_t h_qflags = 0;
+    std::vector<int32_t> h_qsel;      // per contig: solved again (else: the run's result stands)
+    std::vector<DReannRec> h_qrec;    // per contig that was solved again
+    std::vector<DGene> h_qgenes;      // the re-annotation's gene buffer as the device left it (records at h_qrec[i].gene_off)
+    std::vector<uint8_t> h_qdforb;    // the mask in device ORF order, and the totals read back: members, so that a copy enqueued before
+    DTotals h_qtot;                   //   an early error return never points at memory that has gone out of scope
+    uint32_t h_qgtot = 0;
+    hipEvent_t qev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    float reann_ms[3] = {0, 0, 0};
     float stage_ms[PHX_N_STAGES] = {0};
     int stage_n[PHX_N_STAGES] = {0};
     std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;
@@ -463,7 +479,7 @@ int set_batch_layout(phx_ctx *c, int32_t n, const int64_t *len_or_null, const in
     c->uploaded = false; c->ran = false; c->graph_valid = false; c->n = 0; // whatever fails below leaves the context without a batch
     c->meta_stale = false;
     c->has_trna = false; c->h_tnode.clear();
-    c->margins_done = false; c->rev_done = false; c->drops_done = false; c->drop_trees = false; c->repl_done = false;
+    c->margins_done = false; c->rev_done = false; c->drops_done = false; c->drop_trees = false; c->repl_done = false; c->reann_done = false; c->qgrp_done = false;
     if (n < 0) return PHX_E_ARG;
     if (!c->meta.assign((size_t)n)) { c->err = "hipHostMalloc failed"; return PHX_E_NOMEM; }
     c->ftab.clear(); c->vtotal = 0;
@@ -718,8 +734,10 @@ void phx_destroy(phx_ctx *c) {
                      &c->b_node, &c->b_parent, &c->b_inoff, &c->b_no, &c->b_npos, &c->b_ehit, &c->b_mreach, &c->b_olist, &c->b_dist, &c->b_esrc, &c->b_ew, &c->b_ewl, &c->b_path, &c->b_genes, &c->b_gtot, &c->b_tot, &c->b_lpart, &c->b_res, &c->b_sord, &c->b_gtab, &c->b_erank, &c->b_swin, &c->b_swrole, &c->b_sdist, &c->b_segw,
                      &c->b_mo, &c->b_md, &c->b_mw, &c->b_mdt, &c->b_mrec, &c->b_mstat,
                      &c->b_dpi, &c->b_djs, &c->b_djt, &c->b_dfi, &c->b_dla, &c->b_dslot, &c->b_dgtab, &c->b_doff, &c->b_dsx, &c->b_dcx, &c->b_dda, &c->b_ddb, &c->b_drec, &c->b_dstats,
-                     &c->b_dps, &c->b_dts, &c->b_rwin, &c->b_rxs, &c->b_rcoff, &c->b_rcm, &c->b_rchain, &c->b_rrnd, &c->b_rinfo, &c->b_rdoff, &c->b_rdet, &c->b_rgenes, &c->b_rrec, &c->b_rcnt};
+                     &c->b_dps, &c->b_dts, &c->b_rwin, &c->b_rxs, &c->b_rcoff, &c->b_rcm, &c->b_rchain, &c->b_rrnd, &c->b_rinfo, &c->b_rdoff, &c->b_rdet, &c->b_rgenes, &c->b_rrec, &c->b_rcnt,
+                     &c->b_qmeta, &c->b_qtot, &c->b_qdist, &c->b_qparent, &c->b_qpath, &c->b_qgenes, &c->b_qgtot, &c->b_qtie, &c->b_qmask, &c->b_qforb, &c->b_qsel, &c->b_qplan, &c->b_qrec};
     for (DevBuf *b : all) release(*b);
+    for (hipEvent_t e : c->qev) if (e) (void)hipEventDestroy(e);
     if (c->h_mrec) (void)hipHostFree(c->h_mrec);
     if (c->h_drec) (void)hipHostFree(c->h_drec);
     for (hipEvent_t e : c->mev) if (e) (void)hipEventDestroy(e);
@@ -1294,7 +1312,7 @@ int push_layout(phx_ctx *c) {
 int launch_once(phx_ctx *c, bool learn) {
     int rc;
     c->tapw_valid = false; c->cert_done = false; c->exact_done = false; c->exact_genes.clear(); c->exact_failed = 0; c->host_only.clear();
-    c->margins_done = false; c->rev_done = false; c->drops_done = false; c->drop_trees = false; c->repl_done = false;
+    c->margins_done = false; c->rev_done = false; c->drops_done = false; c->drop_trees = false; c->repl_done = false; c->reann_done = false; c->qgrp_done = false;
     hipStream_t s = c->stream;
     c->eager_now = c->eager_done && !c->meta0_dirty && !c->tiles_dirty; // the first launch after such an upload only: a repeated or retried run does everything
     c->eager_done = false;
@@ -2651,6 +2669,228 @@ int phx_replacements_ms(phx_ctx *c, float *ms) {
 int phx_replacement_stats(phx_ctx *c, int64_t *out) {
     if (!c || !out) return PHX_E_ARG;
     for (int k = 0; k < 5; k++) out[k] = c->repl_stats[k];
+    return PHX_OK;
+}
+
+
+// ---- masked re-annotation (phx_resolve.inc) ----
+// status of contig i's re-annotation before any kernel: a run error, PHX_S_OVERFLOW without device distances, else the run's status
+static int32_t reann_status(const phx_ctx *c, int i) {
+    const DMeta &m = c->meta[(size_t)i];
+    if (m.sssp_mode == 4 && m.n_node > 2 && m.status >= 0) return PHX_S_OVERFLOW;
+    const int32_t r = c->res[(size_t)i].status;
+    return r < 0 ? r : m.status; // (the device's own status: exactness does not enter)
+}
+static bool reann_contig(const phx_ctx *c, int i) { const DMeta &m = c->meta[(size_t)i]; return reann_status(c, i) >= 0 && m.n_node > 2; }
+
+// The re-annotation's view of the batch: the run's graph, outputs of its own (nothing the run's results live in is written).
+static void reann_batch(phx_ctx *c, DBatch *b, DReann *q) {
+    fill_batch(c, b);
+    b->meta = (DMeta *)c->b_qmeta.p; b->tot = (DTotals *)c->b_qtot.p;
+    b->res = nullptr; b->sord = nullptr; b->lpart = nullptr;
+    b->dist = (uint64_t *)c->b_qdist.p; b->parent = (int32_t *)c->b_qparent.p; b->path = (int32_t *)c->b_qpath.p;
+    b->genes = (DGene *)c->b_qgenes.p; b->genes_c = nullptr; b->gpack = 0; b->gene_total = (uint32_t *)c->b_qgtot.p;
+    b->tie = (uint8_t *)c->b_qtie.p; b->tie_cap = cap_of(c->b_qtie, 1, 0);
+    q->forb = (const uint8_t *)c->b_qforb.p; q->mask = (uint32_t *)c->b_qmask.p; q->sel = (const int32_t *)c->b_qsel.p;
+    q->gplan = (uint8_t *)c->b_qplan.p; q->dist0 = (const uint64_t *)c->b_dist.p; q->rec = (DReannRec *)c->b_qrec.p;
+}
+
+// Solves the contigs of h_qsel again without the ORFs of `forb` (tap order); the records into h_qrec, the genes into h_qgenes.
+static int reann_compute(phx_ctx *c, const uint8_t *forb, const int64_t *orf_offsets) {
+    const size_t n = (size_t)c->n, V = (size_t)c->tot_node, E = (size_t)c->tot_edge, N = (size_t)c->tot_orf, G = (size_t)c->tot_grp;
+    const size_t limbs = (size_t)std::max(c->n_limbs, 2);
+    if (!c->qgrp_done) {
+        c->qgrp.resize(G);
+        if (G) HIPCHK(c, hipMemcpy(c->qgrp.data(), c->b_grp.p, G * sizeof(DGrp), hipMemcpyDeviceToHost));
+        c->qgrp_done = true;
+    }
+    // the mask in device ORF order: the inverse of the permutation phx_margins_flat applies to its records
+    std::vector<uint8_t> &dforb = c->h_qdforb;
+    dforb.assign(N + 1, 0);
+    std::vector<int> order, ref_rank, ref_first;
+    std::vector<DGrp> grp;
+    int nlm = 0;
+    bool any = false;
+    for (size_t i = 0; i < n; i++) {
+        if (!c->h_qsel[i]) continue;
+        any = true;
+        const DMeta &m = c->meta[i];
+        nlm |= m.sssp_nl == 2 ? 1 : m.sssp_nl == 4 ? 2 : m.sssp_nl == 8 ? 4 : 8;
+        grp.assign(c->qgrp.begin() + m.grp_off, c->qgrp.begin() + m.grp_off + m.n_grp);
+        reference_order(grp, order, ref_rank, ref_first);
+        const uint8_t *from = forb + orf_offsets[i];
+        for (size_t rr = 0; rr < order.size(); rr++) {
+            const DGrp &g = grp[(size_t)order[rr]];
+            if (g.n > 0 && g.orf_begin >= 0 && (int64_t)g.orf_begin + g.n <= m.n_orf) memcpy(dforb.data() + m.orf_off + g.orf_begin, from, (size_t)g.n);
+            from += g.n;
+        }
+    }
+    c->h_qrec.assign(n, DReannRec{});
+    c->h_qgenes.clear();
+    if (!any) return PHX_OK;
+    int rc;
+    if ((rc = ensure(c, c->b_qmeta, (n + 1) * sizeof(DMeta))) || (rc = ensure(c, c->b_qtot, sizeof(DTotals))) || (rc = ensure(c, c->b_qdist, (V + 1) * limbs * 8)) ||
+        (rc = ensure(c, c->b_qparent, (V + 1) * 4)) || (rc = ensure(c, c->b_qpath, (V + 1) * 4)) || (rc = ensure(c, c->b_qgenes, (V + n + 1) * sizeof(DGene))) || // (a path has at most V / 2 pairs, one replaced by k_rs_inorder takes new slots)
+        (rc = ensure(c, c->b_qgtot, 16)) || (rc = ensure(c, c->b_qmask, (E / 32 + 2) * 4)) || (rc = ensure(c, c->b_qforb, N + 1)) || (rc = ensure(c, c->b_qsel, (n + 1) * 4)) ||
+        (rc = ensure(c, c->b_qplan, V / 32 + n + 2)) || (rc = ensure(c, c->b_qrec, (n + 1) * sizeof(DReannRec))))
+        return rc;
+    if (!c->b_qtie.p && (rc = ensure(c, c->b_qtie, (size_t)std::max<int64_t>(c->tie_seen, 1 << 20)))) return rc;
+    for (hipEvent_t &e : c->qev) if (!e) HIPCHK(c, hipEventCreate(&e));
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipMemcpyAsync(c->b_qforb.p, dforb.data(), N + 1, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->b_qsel.p, c->h_qsel.data(), n * 4, hipMemcpyHostToDevice, s));
+    DTotals &tot = c->h_qtot;
+    uint32_t &gtot = c->h_qgtot;
+    gtot = 0;
+    for (int attempt = 0;; attempt++) {
+        DBatch b;
+        DReann q;
+        reann_batch(c, &b, &q);
+        HIPCHK(c, hipEventRecord(c->qev[0], s));
+        HIPCHK(c, hipMemcpyAsync(c->b_qmeta.p, c->b_meta.p, n * sizeof(DMeta), hipMemcpyDeviceToDevice, s)); // the layout and the run's verdicts; the kernels write this copy
+        HIPCHK(c, hipMemsetAsync(c->b_qtot.p, 0, sizeof(DTotals), s));
+        HIPCHK(c, hipMemsetAsync(c->b_qgtot.p, 0, 16, s));
+        HIPCHK(c, hipMemsetAsync(c->b_qrec.p, 0, (n + 1) * sizeof(DReannRec), s));
+        HIPCHK(c, hipMemsetAsync(c->b_qmask.p, 0, (E / 32 + 2) * 4, s));
+        phxk_reann_mask(&b, &q, s);
+        HIPCHK(c, hipEventRecord(c->qev[1], s));
+        phxk_reann_solve(&b, &q, nlm, s);
+        HIPCHK(c, hipEventRecord(c->qev[2], s));
+        phxk_reann_finish(&b, &q, nlm, s);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(c->h_qrec.data(), c->b_qrec.p, n * sizeof(DReannRec), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipEventRecord(c->qev[3], s));
+        HIPCHK(c, hipMemcpyAsync(&tot, c->b_qtot.p, sizeof(DTotals), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(&gtot, c->b_qgtot.p, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        if (!(tot.overflow & 4)) break;
+        // k_rs_inorder's scratch was too small for the contigs with equal-length alternatives: grow it and solve again
+        if (attempt >= 2) { c->err = "re-annotation: the tie scratch did not settle"; return PHX_E_STATE; }
+        if ((rc = ensure(c, c->b_qtie, (size_t)tot.tie_need + (size_t)tot.tie_need / 4 + 4096))) return rc;
+    }
+    if ((size_t)gtot > V + n) { c->err = "re-annotation: gene records beyond the buffer"; return PHX_E_STATE; }
+    c->h_qgenes.resize(gtot);
+    HIPCHK(c, hipEventRecord(c->qev[4], s));
+    if (gtot) HIPCHK(c, hipMemcpyAsync(c->h_qgenes.data(), c->b_qgenes.p, (size_t)gtot * sizeof(DGene), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipEventRecord(c->qev[5], s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    float ms = 0, ms2 = 0;
+    if (hipEventElapsedTime(&ms, c->qev[0], c->qev[1]) == hipSuccess) c->reann_ms[0] = ms;
+    if (hipEventElapsedTime(&ms, c->qev[1], c->qev[2]) == hipSuccess) c->reann_ms[1] = ms;
+    if (hipEventElapsedTime(&ms, c->qev[2], c->qev[3]) == hipSuccess && hipEventElapsedTime(&ms2, c->qev[4], c->qev[5]) == hipSuccess) c->reann_ms[2] = ms + ms2;
+    for (size_t i = 0; i < n; i++) {
+        if (!c->h_qsel[i]) continue;
+        const DReannRec &r = c->h_qrec[i];
+        if (r.n_genes < 0 || r.gene_off < 0 || (uint64_t)r.gene_off + (uint64_t)r.n_genes > (uint64_t)gtot) { c->err = "re-annotation: a contig's gene records lie outside the buffer"; return PHX_E_STATE; }
+    }
+    return PHX_OK;
+}
+
+int phx_reannotate_flat(phx_ctx *c, const uint8_t *forbid, const int64_t *orf_offsets, uint32_t flags, phx_gene *genes, int64_t cap, int64_t *offsets, int32_t *status,
+                        double *delta, int64_t *total_out) {
+    if (!c || (c->n > 0 && (!offsets || !status || !delta || !orf_offsets))) return PHX_E_ARG;
+    if (c->in_flight) { const int rs = phx_wait(c); if (rs) return rs; }
+    if (!c->ran) return PHX_E_STATE;
+    HIPCHK(c, hipSetDevice(c->device));
+    { const int rf = fetch_meta(c); if (rf) return rf; }
+    try {
+    // the offsets must be the batch's cumulative ORF counts (what phx_margins_flat reports): nothing from the caller indexes device memory unchecked
+    int64_t acc = 0;
+    for (int i = 0; i < c->n; i++) {
+        if (orf_offsets[i] != acc) return PHX_E_ARG;
+        if (reann_status(c, i) >= 0) acc += c->meta[(size_t)i].n_orf;
+    }
+    if (c->n > 0 && orf_offsets[c->n] != acc) return PHX_E_ARG;
+    if (acc > 0 && !forbid) return PHX_E_ARG;
+    const size_t N = (size_t)acc;
+    if (!(c->reann_done && c->h_qflags == flags && c->h_qforb.size() == N && (N == 0 || memcmp(c->h_qforb.data(), forbid, N) == 0))) {
+        c->reann_done = false;
+        c->h_qsel.assign((size_t)c->n, 0);
+        for (int i = 0; i < c->n; i++) {
+            if (!reann_contig(c, i)) continue;
+            bool want = (flags & 1u) != 0;
+            for (int64_t k = orf_offsets[i]; k < orf_offsets[i + 1] && !want; k++) want = forbid[k] != 0;
+            c->h_qsel[(size_t)i] = want ? 1 : 0;
+        }
+        { const int rq = reann_compute(c, forbid, orf_offsets); if (rq) { (void)hipStreamSynchronize(c->stream); return rq; } } // (nothing of a failed solve stays in flight)
+        c->h_qforb.assign(forbid, forbid + N);
+        c->h_qflags = flags;
+        c->reann_done = true;
+    }
+    // the run's own genes for the contigs that were not solved again (the device's lists: no host re-solve enters)
+    int64_t hi = 0, total = 0;
+    for (int i = 0; i < c->n; i++) {
+        const int32_t st = reann_status(c, i);
+        offsets[i] = total; status[i] = st; delta[i] = std::numeric_limits<double>::infinity();
+        if (st < 0) continue;
+        if (c->h_qsel[(size_t)i]) {
+            const DReannRec &r = c->h_qrec[(size_t)i];
+            status[i] = r.status; delta[i] = r.delta;
+            if (r.status >= 0) total += r.n_genes;
+        } else {
+            if (st != PHX_S_NOPATH) delta[i] = 0.0;
+            const DRes &r = c->res[(size_t)i];
+            if (r.n_genes > 0) { total += r.n_genes; hi = std::max<int64_t>(hi, r.gene_off + r.n_genes); }
+        }
+    }
+    offsets[c->n] = total;
+    if (total_out) *total_out = total;
+    if (!genes) return PHX_OK; // size query
+    if (cap < total) return PHX_E_ARG;
+    if (hi) {
+        { const int rg = ensure_gene_stage(c, (size_t)hi); if (rg) return rg; }
+        HIPCHK(c, hipMemcpyAsync(c->h_genes, (const DGene *)c->b_genes.p + (gene_pack(c) ? gene_half(c) : 0), sizeof(DGene) * (size_t)hi, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    for (int i = 0; i < c->n; i++) {
+        const int64_t k = offsets[i + 1] - offsets[i];
+        if (k <= 0) continue;
+        const DGene *src = c->h_qsel[(size_t)i] ? c->h_qgenes.data() + c->h_qrec[(size_t)i].gene_off : c->h_genes + (size_t)c->res[(size_t)i].gene_off;
+        memcpy(genes + offsets[i], src, sizeof(phx_gene) * (size_t)k);
+    }
+    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_reannotate_flat"; return PHX_E_NOMEM; }
+    return PHX_OK;
+}
+
+int phx_orf_offsets(phx_ctx *c, int64_t *orf_offsets) {
+    if (!c || !orf_offsets) return PHX_E_ARG;
+    if (c->in_flight) { const int rs = phx_wait(c); if (rs) return rs; }
+    if (!c->ran) return PHX_E_STATE;
+    HIPCHK(c, hipSetDevice(c->device));
+    { const int rf = fetch_meta(c); if (rf) return rf; }
+    int64_t acc = 0;
+    for (int i = 0; i < c->n; i++) { orf_offsets[i] = acc; if (reann_status(c, i) >= 0) acc += c->meta[(size_t)i].n_orf; }
+    orf_offsets[c->n] = acc;
+    return PHX_OK;
+}
+
+int phx_tap_repath(phx_ctx *c, int32_t contig, int32_t *path, int32_t cap, int32_t *n_path, uint64_t *dist_limbs, int32_t cap_limbs) {
+    if (c && c->ran && !c->in_flight && !c->reann_done) return PHX_E_STATE; // no re-annotation of this run
+    TAP_PRE(c, contig);
+    if (!c->reann_done) return PHX_E_STATE;
+    if (!c->h_qsel[(size_t)contig]) { // the run's result stands
+        if (reann_status(c, contig) < 0) { if (n_path) *n_path = 0; return PHX_OK; }
+        return phx_tap_path(c, contig, path, cap, n_path, dist_limbs, cap_limbs);
+    }
+    const DReannRec &r = c->h_qrec[(size_t)contig];
+    if (n_path) *n_path = 0;
+    if (r.status < 0 || r.n_path <= 0) return PHX_OK;
+    if (n_path) *n_path = r.n_path;
+    if (path) {
+        if (cap < r.n_path) return PHX_E_ARG;
+        HIPCHK(c, hipMemcpy(path, (int32_t *)c->b_qpath.p + m.node_off, (size_t)r.n_path * 4, hipMemcpyDeviceToHost));
+    }
+    if (dist_limbs) {
+        if (cap_limbs < m.sssp_nl) return PHX_E_ARG;
+        const size_t tgt = (size_t)m.node_off * (size_t)c->n_limbs + ((size_t)m.n_node - 1) * (size_t)m.sssp_nl;
+        HIPCHK(c, hipMemcpy(dist_limbs, (uint64_t *)c->b_qdist.p + tgt, (size_t)m.sssp_nl * 8, hipMemcpyDeviceToHost));
+    }
+    return PHX_OK;
+}
+
+int phx_reannotate_ms(phx_ctx *c, float *ms) {
+    if (!c || !ms) return PHX_E_ARG;
+    for (int k = 0; k < 3; k++) ms[k] = c->reann_ms[k];
     return PHX_OK;
 }
 

@@ -182,9 +182,13 @@ __device__ void walk_path(const DBatch &b, DMeta *meta, IoShared<IO_T> *sh) {
     __syncthreads();
 }
 
-template <int NL, int IO_T>
-__device__ void inorder_contig(const DBatch &b, DMeta *meta, IoShared<IO_T> *sh) {
+// MASKED (phx_resolve.inc): `mask` holds one bit per in-edge slot of the batch (bit edge_off + e); a refused edge is no edge — it is never tight,
+// whatever the distances say.  The run's instantiations (MASKED = false) do not look at `mask`.
+template <int NL, int IO_T, bool MASKED = false>
+__device__ void inorder_contig(const DBatch &b, DMeta *meta, IoShared<IO_T> *sh, const uint32_t *mask = nullptr) {
     const int tid = threadIdx.x;
+    const uint64_t mbase = MASKED ? (uint64_t)meta->edge_off : 0ull;
+    auto refused = [&](uint32_t e) -> bool { const uint64_t x = mbase + e; return ((mask[x >> 5] >> (x & 31)) & 1u) != 0; };
     const int V = meta->n_node;
     const bool walked = meta->n_path >= 2; // else the solver's parents run in a circle (a zero-length cycle of tight edges): start from source and target alone
     const int n = walked ? meta->n_path : 2; // path[0] = source ... path[n-1] = target
@@ -201,6 +205,7 @@ __device__ void inorder_contig(const DBatch &b, DMeta *meta, IoShared<IO_T> *sh)
     int32_t *path = b.path + meta->node_off;
     const long long *gt = gtab_of(b, meta);
     auto tight = [&](uint32_t e, const WInt<NL> &dv) -> bool {
+        if constexpr (MASKED) { if (refused(e)) return false; }
         const uint32_t sw = esrc[e];
         const WInt<NL> du = wi_load<NL>(dist + (size_t)ESRC_NODE(sw) * NL);
         const WInt<NL> w = ewl ? wi_load<NL>(ewl + (size_t)e * NL) : ew_decode<NL>(edge_wenc(sw, ew, e, gt));
@@ -236,6 +241,7 @@ __device__ void inorder_contig(const DBatch &b, DMeta *meta, IoShared<IO_T> *sh)
                 j[q] = lo;
                 e[q] = sh->ef[lo] + (f - sh->e0[lo]);
                 on[q] = on[q] && e[q] != sh->pe[lo];
+                if constexpr (MASKED) { if (on[q] && refused(e[q])) on[q] = false; }
             }
             uint32_t u[4]; WInt<NL> w[4];
 #pragma unroll

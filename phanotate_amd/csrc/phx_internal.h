@@ -377,6 +377,23 @@ struct DRepl {
     unsigned long long *cnt; // [2]: chain nodes placed, records with a bypass but no winner (0 unless a bug)
 };
 
+// Masked re-annotation (phx_resolve.inc), on demand after a run: the context's lazily allocated buffers.  The kernels' DBatch is the run's
+// with meta / tot / dist / parent / path / genes / gene_total / tie replaced by buffers of the re-annotation's own.
+struct DReannRec { // per contig that was solved again: what the host reads
+    int32_t status, n_genes;
+    int64_t gene_off;  // first record in the re-annotation's gene buffer
+    double delta;      // float(D_F - D) / 1000.0; +inf: no path in G_F
+    int32_t n_path, tie;
+};
+struct DReann {
+    const uint8_t *forb;   // per ORF (at orf_off, device order): 1 = refused
+    uint32_t *mask;        // one bit per in-edge slot of the batch (bit edge_off + e), cleared per call
+    const int32_t *sel;    // per contig: 1 = solve it again
+    uint8_t *gplan;        // window plans beyond RS_PLAN_LDS windows: contig i at node_off / 32 + i
+    const uint64_t *dist0; // the run's distances (D)
+    DReannRec *rec;
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -424,6 +441,9 @@ void phxk_drop_fix(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask,
 void phxk_repl_pick(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream); // drop replacements (phx_replace.inc): winners,
 void phxk_repl_cross(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream); //   cross winners and their delta chains,
 void phxk_repl_walk(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int fill, void *stream);    //   detour lengths (fill 0) / detours, genes, records (1)
+void phxk_reann_mask(const DBatch *b, const DReann *q, void *stream);                 // masked re-annotation (phx_resolve.inc): the refused ORFs' in-edge bits,
+void phxk_reann_solve(const DBatch *b, const DReann *q, int nl_mask, void *stream);   //   the masked sweep (b: the re-annotation's view of the batch),
+void phxk_reann_finish(const DBatch *b, const DReann *q, int nl_mask, void *stream);  //   in-order parents on G_F, path, genes, delta
 #ifdef __cplusplus
 }
 #endif

@@ -180,6 +180,7 @@ __device__ __forceinline__ int min_idx(int a, int b, int c) { return a > b ? (b 
 #include "phx_margins.inc"
 #include "phx_drop.inc"
 #include "phx_replace.inc"
+#include "phx_resolve.inc"
 
 // ------------------------------------------------------------------------------------------------
 // launchers
@@ -402,6 +403,31 @@ void phxk_repl_walk(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl
     else hipLaunchKernelGGL(k_rp_walk<0>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q, *r);
 }
 size_t phxk_sssp_lds_bytes(int V, int nl) { return sssp_lds_bytes(V, nl); }
+// masked re-annotation (phx_resolve.inc): b is the re-annotation's view of the batch (outputs of its own)
+void phxk_reann_mask(const DBatch *b, const DReann *q, void *stream) { hipLaunchKernelGGL(k_rs_mask, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), 0, (hipStream_t)stream, *b, *q); }
+void phxk_reann_solve(const DBatch *b, const DReann *q, int nl_mask, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (nl_mask & 1) launch_rs_lds<2>(b, q, s);
+    if (nl_mask & 2) launch_rs_lds<4>(b, q, s);
+    if (nl_mask & 4) launch_rs_lds<8>(b, q, s);
+    if (nl_mask & 8) launch_rs_lds<17>(b, q, s);
+}
+void phxk_reann_finish(const DBatch *b, const DReann *q, int nl_mask, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 g(b->n_contig);
+    if (b->mean_len < 8192) { // as phxk_inorder: one wavefront per short contig
+        if (nl_mask & 1) hipLaunchKernelGGL((k_rs_inorder<2, 64>), g, dim3(64), 0, s, *b, *q);
+        if (nl_mask & 2) hipLaunchKernelGGL((k_rs_inorder<4, 64>), g, dim3(64), 0, s, *b, *q);
+        if (nl_mask & 4) hipLaunchKernelGGL((k_rs_inorder<8, 64>), g, dim3(64), 0, s, *b, *q);
+        if (nl_mask & 8) hipLaunchKernelGGL((k_rs_inorder<17, 64>), g, dim3(64), 0, s, *b, *q);
+    } else {
+        if (nl_mask & 1) hipLaunchKernelGGL((k_rs_inorder<2, IO_T_FULL>), g, dim3(IO_T_FULL), 0, s, *b, *q);
+        if (nl_mask & 2) hipLaunchKernelGGL((k_rs_inorder<4, IO_T_FULL>), g, dim3(IO_T_FULL), 0, s, *b, *q);
+        if (nl_mask & 4) hipLaunchKernelGGL((k_rs_inorder<8, IO_T_FULL>), g, dim3(IO_T_FULL), 0, s, *b, *q);
+        if (nl_mask & 8) hipLaunchKernelGGL((k_rs_inorder<17, IO_T_FULL>), g, dim3(IO_T_FULL), 0, s, *b, *q);
+    }
+    hipLaunchKernelGGL(k_rs_fin, dim3((unsigned)((b->n_contig + 63) / 64)), dim3(64), 0, s, *b, *q);
+}
 // one workgroup for up to 1024 contigs; larger batches in two passes of a workgroup per 256 contigs
 void phxk_layout1(const DBatch *b, void *stream) {
     if (b->n_contig <= LAYOUT_T) { hipLaunchKernelGGL(k_layout1, dim3(1), dim3(LAYOUT_T), 0, (hipStream_t)stream, *b); return; }
