@@ -1,0 +1,717 @@
+// phx_analyses.inc — the analyses of a finished run: per-ORF margins, gene drop margins, drop replacements, masked re-annotation.
+// Host code, included by phx_api.cpp inside its extern "C" block, behind the taps.  Each analysis is an ensure_* that computes once per
+// run on the context's stream (outside the captured run graph) and an entry point that lays the records out for the caller.
+
+// ---- what the analyses share ----
+// the bit of a limb class in the launchers' nl_mask (bit k: 2, 4, 8, 17 limbs)
+static inline int nl_class_bit(int sssp_nl) { return sssp_nl == 2 ? 1 : sssp_nl == 4 ? 2 : sssp_nl == 8 ? 4 : 8; }
+
+static int analysis_events(phx_ctx *c) { // phx_ctx::aev, created at the first analysis of a context
+    for (hipEvent_t &e : c->aev) if (!e) HIPCHK(c, hipEventCreate(&e));
+    return PHX_OK;
+}
+static float ev_ms(hipEvent_t a, hipEvent_t b) { float ms = 0; return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.0f; }
+
+// the run's group records on the host, once per run
+static int ensure_grp_host(phx_ctx *c) {
+    if (c->done.grp) return PHX_OK;
+    c->h_grp.resize((size_t)c->tot_grp);
+    if (c->tot_grp) HIPCHK(c, hipMemcpy(c->h_grp.data(), c->b_grp.p, (size_t)c->tot_grp * sizeof(DGrp), hipMemcpyDeviceToHost));
+    c->done.grp = true;
+    return PHX_OK;
+}
+// Contig i's groups in the reference's iter_orfs order (phx_tap_orfs: ascending DGrp.evkey; the ORFs of a group are contiguous in that
+// order and in the device's): fn(the group's first ORF in the contig's device order, its ORFs).  After ensure_grp_host; order: scratch.
+extern "C++" template <class F> static void each_group_in_reference_order(const phx_ctx *c, size_t i, std::vector<int> &order, F fn) {
+    const DGrp *grp = c->h_grp.data() + c->meta[i].grp_off;
+    reference_sort(grp, (size_t)c->meta[i].n_grp, order);
+    for (const int g : order) fn(grp[(size_t)g].orf_begin, grp[(size_t)g].n);
+}
+
+// the sorted keys of the CDS genes phx_download* deliver for contig i (after stage_run_genes): what `called` is looked up in
+static inline uint64_t gene_key(int32_t left, int32_t right, int32_t strand) { return ((uint64_t)(uint32_t)left << 33) | ((uint64_t)(uint32_t)right << 1) | (strand < 0 ? 1u : 0u); }
+static void called_keys(const phx_ctx *c, int i, std::vector<uint64_t> &keys) {
+    int64_t ng = 0;
+    const DGene *src = delivered_genes(c, i, &ng);
+    keys.clear();
+    for (int64_t k = 0; k < ng; k++) if (src[k].frame >= -3 && src[k].frame <= 3) keys.push_back(gene_key(src[k].left, src[k].right, src[k].strand)); // (tRNA path edges, frame +-4, are no ORFs)
+    std::sort(keys.begin(), keys.end());
+}
+static inline bool is_called(const std::vector<uint64_t> &keys, int32_t left, int32_t right, int32_t strand) { return std::binary_search(keys.begin(), keys.end(), gene_key(left, right, strand)); }
+
+// ---- per-ORF path margins (phx_margins.inc, DESIGN.md §11) ----
+// limb classes of the contigs that have device distances
+static int margins_nl_mask(const phx_ctx *c) {
+    int nlm = 0;
+    for (size_t i = 0; i < (size_t)c->n; i++) {
+        const DMeta &m = c->meta[i];
+        if (m.status < 0 || m.n_node <= 2 || m.sssp_mode == 4) continue;
+        nlm |= nl_class_bit(m.sssp_nl);
+    }
+    return nlm;
+}
+
+static void margins_args(phx_ctx *c, DMarg *g) {
+    g->out_off = (uint32_t *)c->b_mo.p; g->out_dst = (uint32_t *)c->b_md.p; g->out_w = (long long *)c->b_mw.p;
+    g->dist_t = (uint64_t *)c->b_mdt.p; g->rec = (phx_orf_margin *)c->b_mrec.p; g->mstat = (int32_t *)c->b_mstat.p;
+}
+
+// The shared part of the margins and the drop margins, once per run: the out-edge CSR, d_t and the reverse pass's per-contig verdicts
+// (c->mstat), kernel by kernel on the context's stream, outside the captured run graph.
+static int ensure_rev(phx_ctx *c) {
+    if (c->done.rev) return PHX_OK;
+    { const int rf = fetch_meta(c); if (rf) return rf; }
+    const size_t n = (size_t)c->n, V = (size_t)c->tot_node, E = (size_t)c->tot_edge, N = (size_t)c->tot_orf;
+    const size_t limbs = (size_t)std::max(c->n_limbs, 2);
+    const int nlm = margins_nl_mask(c);
+    int rc;
+    if ((rc = ensure(c, c->b_mo, (V + n + 1) * 4))) return rc;
+    if ((rc = ensure(c, c->b_md, (E + 1) * 4))) return rc;
+    if ((rc = ensure(c, c->b_mw, (E + 1) * 8))) return rc;
+    if ((rc = ensure(c, c->b_mdt, (V + 1) * limbs * 8))) return rc;
+    if ((rc = ensure(c, c->b_mrec, (N + 1) * sizeof(phx_orf_margin)))) return rc;
+    if ((rc = ensure(c, c->b_mstat, (n + 1) * 4))) return rc;
+    if ((rc = analysis_events(c))) return rc;
+    c->mstat.assign(n, 0);
+    DBatch b;
+    fill_batch(c, &b);
+    DMarg g;
+    margins_args(c, &g);
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipEventRecord(c->aev[0], s));
+    HIPCHK(c, hipMemsetAsync(c->b_mo.p, 0, (V + n + 1) * 4, s));
+    HIPCHK(c, hipMemsetAsync(c->b_mstat.p, 0, (n + 1) * 4, s));
+    phxk_margins_transpose(&b, &g, s);
+    HIPCHK(c, hipEventRecord(c->aev[1], s));
+    phxk_sssp_rev(&b, &g, nlm, s);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->aev[2], s));
+    if (n) HIPCHK(c, hipMemcpyAsync(c->mstat.data(), c->b_mstat.p, n * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    for (int k = 0; k < 2; k++) c->rev_ms[k] = ev_ms(c->aev[k], c->aev[k + 1]);
+    c->done.rev = true;
+    return PHX_OK;
+}
+
+// The device's records of every ORF of the batch (device order) into c->h_mrec, once per run, on top of ensure_rev.
+static int ensure_margins(phx_ctx *c) {
+    if (c->done.margins) return PHX_OK;
+    { const int rr = ensure_rev(c); if (rr) return rr; }
+    const size_t N = (size_t)c->tot_orf;
+    const int nlm = margins_nl_mask(c);
+    { const int rp = ensure_pinned(c, c->h_mrec, (N + 1) * sizeof(phx_orf_margin), (N + N / 4 + 1024) * sizeof(phx_orf_margin)); if (rp) return rp; }
+    DBatch b;
+    fill_batch(c, &b);
+    DMarg g;
+    margins_args(c, &g);
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipEventRecord(c->aev[2], s));
+    phxk_margins(&b, &g, nlm, s);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->aev[3], s));
+    if (N) HIPCHK(c, hipMemcpyAsync(c->h_mrec.p, c->b_mrec.p, N * sizeof(phx_orf_margin), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipEventRecord(c->aev[4], s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    c->margins_ms[0] = c->rev_ms[0]; c->margins_ms[1] = c->rev_ms[1];
+    for (int k = 2; k < 4; k++) c->margins_ms[k] = ev_ms(c->aev[k], c->aev[k + 1]);
+    c->done.margins = true;
+    return PHX_OK;
+}
+
+// status of contig i's margins (include/phx.h)
+static int32_t margins_status(const phx_ctx *c, int i) {
+    const int32_t r = c->res[(size_t)i].status;
+    if (r < 0) return r;
+    const DMeta &m = c->meta[(size_t)i];
+    if (m.sssp_mode == 4 && m.n_node > 2) return PHX_S_OVERFLOW;
+    if (c->mstat[(size_t)i]) return PHX_S_NEGCYCLE;
+    return r;
+}
+
+int phx_margins_flat(phx_ctx *c, phx_orf_margin *rec, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
+    if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
+    { const int ra = after_run(c); if (ra) return ra; }
+    { const int rx = ensure_exact(c); if (rx) return rx; } // `called` is against the genes phx_download* deliver
+    { const int rm = ensure_margins(c); if (rm) return rm; }
+    try {
+    int64_t total = 0;
+    for (int i = 0; i < c->n; i++) { offsets[i] = total; status[i] = margins_status(c, i); if (status[i] >= 0) total += c->meta[(size_t)i].n_orf; }
+    offsets[c->n] = total;
+    if (total_out) *total_out = total;
+    if (!rec) return PHX_OK; // size query
+    if (cap < total) return PHX_E_ARG;
+    { const int rg = stage_run_genes(c); if (rg) return rg; }
+    { const int rg = ensure_grp_host(c); if (rg) return rg; }
+    std::vector<uint64_t> keys;
+    std::vector<int> order;
+    for (int i = 0; i < c->n; i++) {
+        if (status[i] < 0) continue;
+        called_keys(c, i, keys);
+        // the device's records, in the reference's order
+        phx_orf_margin *dst = rec + offsets[i];
+        const phx_orf_margin *from = (const phx_orf_margin *)c->h_mrec.p + c->meta[(size_t)i].orf_off;
+        each_group_in_reference_order(c, (size_t)i, order, [&](int32_t first, int32_t k) {
+            if (k > 0) memcpy(dst, from + first, sizeof(phx_orf_margin) * (size_t)k);
+            dst += k;
+        });
+        for (int64_t k = offsets[i]; k < offsets[i + 1]; k++) rec[k].called = is_called(keys, rec[k].left, rec[k].right, rec[k].strand) ? 1 : 0;
+    }
+    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_margins_flat"; return PHX_E_NOMEM; }
+    return PHX_OK;
+}
+
+int phx_tap_dist_target(phx_ctx *c, int32_t contig, uint64_t *dist_limbs, int64_t cap_words) {
+    TAP_PRE(c, contig);
+    if (m.status < 0 || m.n_node <= 2 || m.sssp_mode == 4) return PHX_OK;
+    const size_t words = (size_t)m.n_node * (size_t)m.sssp_nl;
+    if (!dist_limbs || cap_words < (int64_t)words) return PHX_E_ARG;
+    { const int rm = ensure_rev(c); if (rm) return rm; }
+    HIPCHK(c, hipMemcpy(dist_limbs, (uint64_t *)c->b_mdt.p + (size_t)m.node_off * (size_t)c->n_limbs, words * 8, hipMemcpyDeviceToHost));
+    return PHX_OK;
+}
+
+int phx_margins_ms(phx_ctx *c, float *ms) {
+    if (!c || !ms) return PHX_E_ARG;
+    for (int k = 0; k < 4; k++) ms[k] = c->margins_ms[k];
+    return PHX_OK;
+}
+
+// ---- gene drop margins (phx_drop.inc, DESIGN.md §12) ----
+// the contigs the drop kernels cover (dp_contig) and their sparse-table size (k_dp_cand)
+static bool drop_contig(const phx_ctx *c, size_t i) {
+    const DMeta &m = c->meta[i];
+    return m.status >= 0 && m.n_node > 2 && m.sssp_mode != 4 && !c->mstat[i] && m.n_path >= 3;
+}
+static int64_t drop_cells(int n_path) { int lv = 1; while ((2 << (lv - 1)) <= n_path) lv++; return (int64_t)n_path * lv; }
+
+static void drop_args(phx_ctx *c, DDrop *q) {
+    const size_t n = (size_t)c->n;
+    q->pidx = (int32_t *)c->b_dpi.p; q->js = (int32_t *)c->b_djs.p; q->jt = (int32_t *)c->b_djt.p; q->first = (int32_t *)c->b_dfi.p; q->last = (int32_t *)c->b_dla.p;
+    q->slot = (uint64_t *)c->b_dslot.p; q->gtab = (uint64_t *)c->b_dgtab.p;
+    q->toff = (const int64_t *)c->b_doff.p; q->roff = (const int64_t *)c->b_doff.p + n;
+    q->sx = (uint64_t *)c->b_dsx.p; q->cx = (uint64_t *)c->b_dcx.p; q->da = (uint64_t *)c->b_dda.p; q->db = (uint64_t *)c->b_ddb.p;
+    q->rec = (phx_gene_drop *)c->b_drec.p; q->stats = (unsigned long long *)c->b_dstats.p;
+    const char *ly = getenv("PHX_DROP_LAYERED");
+    q->layered = ly && *ly && strcmp(ly, "0") != 0 ? 1 : 0;
+    q->ps = c->done.trees ? (int32_t *)c->b_dps.p : nullptr; q->ts = c->done.trees ? (int32_t *)c->b_dts.p : nullptr;
+}
+
+// The records of every pair of every device path into c->h_drec (at c->droff), once per run, on top of ensure_rev.  trees: the one-hop
+// trees too (DDrop.ps / ts, for the replacements); drops computed without them get k_dp_tree once more, which rewrites the same labels.
+static int ensure_drops(phx_ctx *c, bool trees = false) {
+    if (c->done.drops && (!trees || c->done.trees)) return PHX_OK;
+    if (c->done.drops) {
+        const size_t nv = ((size_t)c->tot_node + (size_t)c->n + 1) * 4;
+        int rc;
+        if ((rc = ensure(c, c->b_dps, nv)) || (rc = ensure(c, c->b_dts, nv)) || (rc = ensure(c, c->b_rcnt, 2 * RP_NCNT * 8))) return rc;
+        c->done.trees = true;
+        DBatch b;
+        fill_batch(c, &b);
+        DMarg g;
+        margins_args(c, &g);
+        DDrop q;
+        drop_args(c, &q);
+        q.stats = (unsigned long long *)c->b_rcnt.p + RP_NCNT; // (the drops' own counters stay as they were)
+        phxk_drop_trees(&b, &g, &q, margins_nl_mask(c), c->stream);
+        HIPCHK(c, hipGetLastError());
+        return PHX_OK;
+    }
+    if (trees) c->done.trees = true;
+    { const int rr = ensure_rev(c); if (rr) return rr; }
+    const size_t n = (size_t)c->n, V = (size_t)c->tot_node;
+    const size_t limbs = (size_t)std::max(c->n_limbs, 2);
+    const int nlm = margins_nl_mask(c);
+    std::vector<int64_t> off(2 * n + 2, 0); // toff[n], roff[n + 1]
+    c->droff.assign(n + 1, 0);
+    int64_t tcells = 0, R = 0;
+    for (size_t i = 0; i < n; i++) {
+        off[n + i] = R; c->droff[i] = R;
+        if (!drop_contig(c, i)) continue;
+        const int np = c->meta[i].n_path;
+        const int64_t cells = drop_cells(np);
+        if (cells > DP_TAB_LDS) { off[i] = tcells; tcells += cells; }
+        R += (np - 1) / 2;
+    }
+    off[2 * n] = R; c->droff[n] = R;
+    int rc;
+    const size_t nv = (V + n + 1) * 4;
+    if ((rc = ensure(c, c->b_dpi, nv)) || (rc = ensure(c, c->b_djs, nv)) || (rc = ensure(c, c->b_djt, nv)) || (rc = ensure(c, c->b_dfi, nv)) || (rc = ensure(c, c->b_dla, nv))) return rc;
+    if ((rc = ensure(c, c->b_dslot, (V + 1) * 8))) return rc;
+    if ((rc = ensure(c, c->b_dgtab, ((size_t)tcells + 1) * 8))) return rc;
+    if ((rc = ensure(c, c->b_doff, (2 * n + 2) * 8))) return rc;
+    if ((rc = ensure(c, c->b_dsx, ((size_t)R + 1) * limbs * 8)) || (rc = ensure(c, c->b_dcx, ((size_t)R + 1) * limbs * 8))) return rc;
+    if ((rc = ensure(c, c->b_dda, (V + 1) * limbs * 8)) || (rc = ensure(c, c->b_ddb, (V + 1) * limbs * 8))) return rc;
+    if ((rc = ensure(c, c->b_drec, ((size_t)R + 1) * sizeof(phx_gene_drop)))) return rc;
+    if ((rc = ensure(c, c->b_dstats, 4 * 8))) return rc;
+    if (c->done.trees && ((rc = ensure(c, c->b_dps, nv)) || (rc = ensure(c, c->b_dts, nv)))) return rc;
+    if ((rc = ensure_pinned(c, c->h_drec, ((size_t)R + 1) * sizeof(phx_gene_drop), ((size_t)R + (size_t)R / 4 + 1024) * sizeof(phx_gene_drop)))) return rc;
+    if ((rc = analysis_events(c))) return rc;
+    DBatch b;
+    fill_batch(c, &b);
+    DMarg g;
+    margins_args(c, &g);
+    DDrop q;
+    drop_args(c, &q);
+    hipStream_t s = c->stream;
+    unsigned long long st[4] = {0, 0, 0, 0};
+    HIPCHK(c, hipEventRecord(c->aev[0], s));
+    HIPCHK(c, hipMemcpyAsync(c->b_doff.p, off.data(), (2 * n + 2) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(c->b_dstats.p, 0, 4 * 8, s));
+    phxk_drop_trees(&b, &g, &q, nlm, s);
+    HIPCHK(c, hipEventRecord(c->aev[1], s));
+    phxk_drop_cand(&b, &g, &q, nlm, s);
+    HIPCHK(c, hipEventRecord(c->aev[2], s));
+    phxk_drop_fix(&b, &g, &q, nlm, s);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->aev[3], s));
+    if (R) HIPCHK(c, hipMemcpyAsync(c->h_drec.p, c->b_drec.p, (size_t)R * sizeof(phx_gene_drop), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipEventRecord(c->aev[4], s));
+    HIPCHK(c, hipMemcpyAsync(st, c->b_dstats.p, sizeof st, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    for (int k = 0; k < 4; k++) { c->drop_ms[k] = ev_ms(c->aev[k], c->aev[k + 1]); c->drop_stats[k] = (int64_t)st[k]; }
+    c->done.drops = true;
+    return PHX_OK;
+}
+
+int phx_drop_margins_flat(phx_ctx *c, phx_gene_drop *rec, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
+    if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
+    { const int ra = after_run(c); if (ra) return ra; }
+    { const int rx = ensure_exact(c); if (rx) return rx; } // `called` is against the genes phx_download* deliver
+    { const int rd = ensure_drops(c); if (rd) return rd; }
+    const phx_gene_drop *drec = (const phx_gene_drop *)c->h_drec.p;
+    try {
+    // the gene pairs of every contig with records (status 0): the pairs of the device path that are CDS genes
+    auto genes_of = [&](int i) -> int64_t {
+        int64_t k = 0;
+        for (int64_t r = c->droff[(size_t)i]; r < c->droff[(size_t)i + 1]; r++) k += drec[r].called >= 0;
+        return k;
+    };
+    int64_t total = 0;
+    for (int i = 0; i < c->n; i++) {
+        offsets[i] = total;
+        status[i] = margins_status(c, i);
+        if (status[i] == 0 && drop_contig(c, (size_t)i)) total += genes_of(i);
+    }
+    offsets[c->n] = total;
+    if (total_out) *total_out = total;
+    if (!rec) return PHX_OK; // size query
+    if (cap < total) return PHX_E_ARG;
+    { const int rg = stage_run_genes(c); if (rg) return rg; }
+    std::vector<uint64_t> keys;
+    for (int i = 0; i < c->n; i++) {
+        if (offsets[i + 1] == offsets[i]) continue;
+        called_keys(c, i, keys);
+        phx_gene_drop *dst = rec + offsets[i];
+        for (int64_t k = c->droff[(size_t)i]; k < c->droff[(size_t)i + 1]; k++) {
+            const phx_gene_drop &x = drec[k];
+            if (x.called < 0) continue;
+            *dst = x;
+            dst->called = is_called(keys, x.left, x.right, x.strand) ? 1 : 0;
+            dst++;
+        }
+    }
+    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_drop_margins_flat"; return PHX_E_NOMEM; }
+    return PHX_OK;
+}
+
+int phx_drop_ms(phx_ctx *c, float *ms) {
+    if (!c || !ms) return PHX_E_ARG;
+    for (int k = 0; k < 4; k++) ms[k] = c->drop_ms[k];
+    return PHX_OK;
+}
+
+int phx_drop_stats(phx_ctx *c, int64_t *out) {
+    if (!c || !out) return PHX_E_ARG;
+    for (int k = 0; k < 4; k++) out[k] = c->drop_stats[k];
+    return PHX_OK;
+}
+
+// ---- drop replacements (phx_replace.inc, DESIGN.md §13) ----
+// Every device record's replacement into c->h_rrec / h_rgenes / h_rdet, once per run, on top of ensure_drops (with the one-hop trees).
+static int ensure_replacements(phx_ctx *c) {
+    if (c->done.repl) return PHX_OK;
+    { const int rd = ensure_drops(c, true); if (rd) return rd; }
+    const size_t n = (size_t)c->n, V = (size_t)c->tot_node;
+    const size_t R = (size_t)c->droff[n];
+    const int nlm = margins_nl_mask(c);
+    int rc;
+    if ((rc = ensure(c, c->b_rwin, (R + 1) * 8)) || (rc = ensure(c, c->b_rxs, (R + 1) * 4)) || (rc = ensure(c, c->b_rcoff, (R + 1) * 8)) ||
+        (rc = ensure(c, c->b_rcm, (R + 1) * 4)) || (rc = ensure(c, c->b_rrnd, (V + n + 1) * 4)) || (rc = ensure(c, c->b_rinfo, (R + 1) * 16)) ||
+        (rc = ensure(c, c->b_rdoff, (2 * R + 2) * 8)) || (rc = ensure(c, c->b_rrec, (R + 1) * sizeof(phx_gene_repl))) || (rc = ensure(c, c->b_rcnt, 2 * RP_NCNT * 8)))
+        return rc;
+    if (!c->b_rchain.p) { // room for this many delta-chain nodes (env PHX_REPL_CHAIN_CAP, the tests: fewer, so that the regrowth below runs)
+        const char *cc = getenv("PHX_REPL_CHAIN_CAP");
+        c->rchain_cap = cc && *cc ? std::max<int64_t>(1, atoll(cc)) : (int64_t)V + 1;
+        if ((rc = ensure(c, c->b_rchain, ((size_t)c->rchain_cap + 1) * 4))) return rc;
+    }
+    if ((rc = analysis_events(c))) return rc;
+    try { c->h_rpath.assign(n, std::vector<int32_t>()); } catch (const std::bad_alloc &) { c->err = "out of memory in phx_replacements_flat"; return PHX_E_NOMEM; }
+    DBatch b;
+    fill_batch(c, &b);
+    DMarg g;
+    margins_args(c, &g);
+    DDrop q;
+    drop_args(c, &q);
+    DRepl r;
+    auto args = [&]() {
+        r.win = (uint64_t *)c->b_rwin.p; r.xs = (int32_t *)c->b_rxs.p; r.coff = (int64_t *)c->b_rcoff.p; r.cm = (int32_t *)c->b_rcm.p;
+        r.chain = (int32_t *)c->b_rchain.p; r.ccap = c->rchain_cap; // (b_rchain was ensured for rchain_cap + 1 entries)
+        r.rnd = (int32_t *)c->b_rrnd.p; r.info = (int32_t *)c->b_rinfo.p;
+        r.doff = (const int64_t *)c->b_rdoff.p; r.goff = (const int64_t *)c->b_rdoff.p + R + 1;
+        r.det = (int32_t *)c->b_rdet.p; r.genes = (phx_gene *)c->b_rgenes.p; r.rec = (phx_gene_repl *)c->b_rrec.p;
+        r.cnt = (unsigned long long *)c->b_rcnt.p;
+    };
+    args();
+    hipStream_t s = c->stream;
+    // The event pairs bracket device work only: the host's read-backs and offsets between the passes fall outside every pair.
+    unsigned long long cnt[RP_NCNT] = {0};
+    hipEvent_t *ev = c->aev;
+    bool regrown = false;
+    HIPCHK(c, hipEventRecord(ev[0], s));
+    HIPCHK(c, hipMemsetAsync(c->b_rcnt.p, 0, RP_NCNT * 8, s));
+    HIPCHK(c, hipMemsetAsync(c->b_rwin.p, 0xff, (R + 1) * 8, s));
+    phxk_repl_pick(&b, &g, &q, &r, nlm, s);
+    phxk_repl_cross(&b, &g, &q, &r, nlm, s);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev[1], s));
+    HIPCHK(c, hipMemcpyAsync(cnt, c->b_rcnt.p, sizeof cnt, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if ((int64_t)cnt[0] > r.ccap) { // the delta chains did not fit: room for all of them, and the cross winners once more
+        c->rchain_cap = (int64_t)cnt[0];
+        if ((rc = ensure(c, c->b_rchain, ((size_t)c->rchain_cap + 1) * 4))) return rc;
+        args();
+        regrown = true;
+        HIPCHK(c, hipEventRecord(ev[2], s));
+        HIPCHK(c, hipMemsetAsync(c->b_rcnt.p, 0, RP_NCNT * 8, s));
+        phxk_repl_cross(&b, &g, &q, &r, nlm, s);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(ev[3], s));
+        HIPCHK(c, hipMemcpyAsync(cnt, c->b_rcnt.p, sizeof cnt, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        if ((int64_t)cnt[0] > r.ccap) { c->err = "drop replacements: the delta chains outgrew their buffer twice"; return PHX_E_STATE; }
+    }
+    // counting pass, offsets, filling pass
+    HIPCHK(c, hipEventRecord(ev[4], s));
+    phxk_repl_walk(&b, &g, &q, &r, 0, s);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(ev[5], s));
+    c->h_rinfo.resize(4 * R + 4);
+    if (R) HIPCHK(c, hipMemcpyAsync(c->h_rinfo.data(), c->b_rinfo.p, R * 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(cnt, c->b_rcnt.p, sizeof cnt, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (cnt[1]) { c->err = "drop replacements: a slot with a bypass has no witness"; return PHX_E_STATE; }
+    c->repl_stats[0] = (int64_t)cnt[2]; c->repl_stats[1] = (int64_t)cnt[0]; c->repl_stats[2] = (int64_t)cnt[3]; c->repl_stats[3] = (int64_t)cnt[4];
+    c->repl_stats[4] = regrown ? 1 : 0;
+    try {
+        std::vector<int64_t> off(2 * R + 2);
+        int64_t nd = 0, ng = 0;
+        for (size_t k = 0; k < R; k++) { off[k] = nd; off[R + 1 + k] = ng; nd += c->h_rinfo[4 * k + 2]; ng += c->h_rinfo[4 * k + 3]; }
+        off[R] = nd; off[2 * R + 1] = ng;
+        c->h_rdoff.assign(off.begin(), off.begin() + (R + 1));
+        if ((rc = ensure(c, c->b_rdet, ((size_t)nd + 1) * 4)) || (rc = ensure(c, c->b_rgenes, ((size_t)ng + 1) * sizeof(phx_gene)))) return rc;
+        args();
+        HIPCHK(c, hipMemcpyAsync(c->b_rdoff.p, off.data(), (2 * R + 2) * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipEventRecord(ev[6], s));
+        phxk_repl_walk(&b, &g, &q, &r, 1, s);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(ev[7], s));
+        c->h_rrec.resize(R + 1); c->h_rdet.resize((size_t)nd + 1); c->h_rgenes.resize((size_t)ng + 1);
+        if (R) HIPCHK(c, hipMemcpyAsync(c->h_rrec.data(), c->b_rrec.p, R * sizeof(phx_gene_repl), hipMemcpyDeviceToHost, s));
+        if (nd) HIPCHK(c, hipMemcpyAsync(c->h_rdet.data(), c->b_rdet.p, (size_t)nd * 4, hipMemcpyDeviceToHost, s));
+        if (ng) HIPCHK(c, hipMemcpyAsync(c->h_rgenes.data(), c->b_rgenes.p, (size_t)ng * sizeof(phx_gene), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipEventRecord(ev[8], s));
+        HIPCHK(c, hipStreamSynchronize(s));
+    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_replacements_flat"; return PHX_E_NOMEM; }
+    auto span = [&](int k0, int k1) { return ev_ms(ev[k0], ev[k1]); };
+    c->repl_ms[0] = span(0, 1) + (regrown ? span(2, 3) : 0.0f);
+    c->repl_ms[1] = span(4, 5) + span(6, 7);
+    c->repl_ms[2] = span(7, 8);
+    c->done.repl = true;
+    return PHX_OK;
+}
+
+int phx_replacements_flat(phx_ctx *c, phx_gene_repl *rec, int64_t cap, phx_gene *genes, int64_t gene_cap, int64_t *offsets, int32_t *status,
+                          int64_t *total_out, int64_t *gene_total_out) {
+    if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
+    { const int ra = after_run(c); if (ra) return ra; }
+    { const int rr = ensure_replacements(c); if (rr) return rr; }
+    // statuses, offsets and `called` exactly as the drop records have them
+    int64_t total = 0;
+    { const int rd = phx_drop_margins_flat(c, nullptr, 0, offsets, status, &total); if (rd) return rd; }
+    try {
+    std::vector<phx_gene_drop> drec((size_t)total + 1);
+    { const int rd = phx_drop_margins_flat(c, drec.data(), total, offsets, status, &total); if (rd) return rd; }
+    int64_t gt = 0;
+    for (int i = 0; i < c->n; i++) {
+        if (offsets[i + 1] == offsets[i]) continue;
+        for (int64_t k = c->droff[(size_t)i]; k < c->droff[(size_t)i + 1]; k++) if (c->h_rrec[k].called >= 0) gt += c->h_rrec[k].n_removed + c->h_rrec[k].n_added;
+    }
+    if (total_out) *total_out = total;
+    if (gene_total_out) *gene_total_out = gt;
+    if (!rec || !genes) return PHX_OK; // size query
+    if (cap < total || gene_cap < gt) return PHX_E_ARG;
+    int64_t go = 0;
+    for (int i = 0; i < c->n; i++) {
+        if (offsets[i + 1] == offsets[i]) continue;
+        phx_gene_repl *dst = rec + offsets[i];
+        const phx_gene_drop *dd = drec.data() + offsets[i];
+        for (int64_t k = c->droff[(size_t)i]; k < c->droff[(size_t)i + 1]; k++) {
+            const phx_gene_repl &x = c->h_rrec[k];
+            if (x.called < 0) continue;
+            *dst = x;
+            dst->called = dd->called;
+            dst->gene_off = go;
+            const int64_t ng = x.n_removed + x.n_added;
+            if (ng) memcpy(genes + go, c->h_rgenes.data() + x.gene_off, (size_t)ng * sizeof(phx_gene));
+            go += ng;
+            dst++; dd++;
+        }
+    }
+    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_replacements_flat"; return PHX_E_NOMEM; }
+    return PHX_OK;
+}
+
+int phx_tap_replacement(phx_ctx *c, int32_t contig, int32_t k, int32_t *path, int32_t cap, int32_t *n_path) {
+    if (!c || !n_path) return PHX_E_ARG;
+    *n_path = 0;
+    { const int ra = after_run(c); if (ra) return ra; }
+    if (contig < 0 || contig >= c->n || k < 0) return PHX_E_ARG;
+    { const int rr = ensure_replacements(c); if (rr) return rr; }
+    if (!drop_contig(c, (size_t)contig) || margins_status(c, contig) != 0) return PHX_E_ARG;
+    int64_t rk = -1;
+    for (int64_t q = c->droff[(size_t)contig], seen = 0; q < c->droff[(size_t)contig + 1]; q++)
+        if (c->h_rrec[q].called >= 0 && seen++ == k) { rk = q; break; }
+    if (rk < 0) return PHX_E_ARG;
+    if (!c->h_rrec[rk].bypass) return PHX_OK;
+    const DMeta &m = c->meta[(size_t)contig];
+    const int a = c->h_rinfo[4 * rk], b = c->h_rinfo[4 * rk + 1], nd = c->h_rinfo[4 * rk + 2];
+    const int len = (a + 1) + nd + (m.n_path - b);
+    *n_path = len;
+    if (!path) return PHX_OK;
+    if (cap < len) return PHX_E_ARG;
+    std::vector<int32_t> &P = c->h_rpath[(size_t)contig]; // (the contig's device path, fetched at its first tap of this run)
+    if (P.empty()) {
+        try { P.resize((size_t)m.n_path); } catch (const std::bad_alloc &) { c->err = "out of memory in phx_tap_replacement"; return PHX_E_NOMEM; }
+        HIPCHK(c, hipMemcpy(P.data(), (int32_t *)c->b_path.p + m.node_off, (size_t)m.n_path * 4, hipMemcpyDeviceToHost));
+    }
+    int32_t *o = path;
+    for (int t = 0; t <= a; t++) *o++ = P[(size_t)t];
+    for (int t = 0; t < nd; t++) *o++ = c->h_rdet[(size_t)c->h_rdoff[(size_t)rk] + t];
+    for (int t = b; t < m.n_path; t++) *o++ = P[(size_t)t];
+    return PHX_OK;
+}
+
+int phx_replacements_ms(phx_ctx *c, float *ms) {
+    if (!c || !ms) return PHX_E_ARG;
+    for (int k = 0; k < 3; k++) ms[k] = c->repl_ms[k];
+    return PHX_OK;
+}
+
+int phx_replacement_stats(phx_ctx *c, int64_t *out) {
+    if (!c || !out) return PHX_E_ARG;
+    for (int k = 0; k < 5; k++) out[k] = c->repl_stats[k];
+    return PHX_OK;
+}
+
+// ---- masked re-annotation (phx_resolve.inc, DESIGN.md §14) ----
+// status of contig i's re-annotation before any kernel: a run error, PHX_S_OVERFLOW without device distances, else the run's status
+static int32_t reann_status(const phx_ctx *c, int i) {
+    const DMeta &m = c->meta[(size_t)i];
+    if (m.sssp_mode == 4 && m.n_node > 2 && m.status >= 0) return PHX_S_OVERFLOW;
+    const int32_t r = c->res[(size_t)i].status;
+    return r < 0 ? r : m.status; // (the device's own status: exactness does not enter)
+}
+static bool reann_contig(const phx_ctx *c, int i) { const DMeta &m = c->meta[(size_t)i]; return reann_status(c, i) >= 0 && m.n_node > 2; }
+
+// The re-annotation's view of the batch: the run's graph, outputs of its own (nothing the run's results live in is written).
+static void reann_batch(phx_ctx *c, DBatch *b, DReann *q) {
+    fill_batch(c, b);
+    b->meta = (DMeta *)c->b_qmeta.p; b->tot = (DTotals *)c->b_qtot.p;
+    b->res = nullptr; b->sord = nullptr; b->lpart = nullptr;
+    b->dist = (uint64_t *)c->b_qdist.p; b->parent = (int32_t *)c->b_qparent.p; b->path = (int32_t *)c->b_qpath.p;
+    b->genes = (DGene *)c->b_qgenes.p; b->genes_c = nullptr; b->gpack = 0; b->gene_total = (uint32_t *)c->b_qgtot.p;
+    b->tie = (uint8_t *)c->b_qtie.p; b->tie_cap = cap_of(c->b_qtie, 1, 0);
+    q->forb = (const uint8_t *)c->b_qforb.p; q->mask = (uint32_t *)c->b_qmask.p; q->sel = (const int32_t *)c->b_qsel.p;
+    q->gplan = (uint8_t *)c->b_qplan.p; q->dist0 = (const uint64_t *)c->b_dist.p; q->rec = (DReannRec *)c->b_qrec.p;
+}
+
+// Solves the contigs of h_qsel again without the ORFs of `forb` (tap order); the records into h_qrec, the genes into h_qgenes.
+static int reann_compute(phx_ctx *c, const uint8_t *forb, const int64_t *orf_offsets) {
+    const size_t n = (size_t)c->n, V = (size_t)c->tot_node, E = (size_t)c->tot_edge, N = (size_t)c->tot_orf;
+    const size_t limbs = (size_t)std::max(c->n_limbs, 2);
+    { const int rg = ensure_grp_host(c); if (rg) return rg; }
+    // the mask in device ORF order: the inverse of the permutation phx_margins_flat applies to its records
+    std::vector<uint8_t> &dforb = c->h_qdforb;
+    dforb.assign(N + 1, 0);
+    std::vector<int> order;
+    int nlm = 0;
+    bool any = false;
+    for (size_t i = 0; i < n; i++) {
+        if (!c->h_qsel[i]) continue;
+        any = true;
+        const DMeta &m = c->meta[i];
+        nlm |= nl_class_bit(m.sssp_nl);
+        const uint8_t *from = forb + orf_offsets[i];
+        each_group_in_reference_order(c, i, order, [&](int32_t first, int32_t k) {
+            if (k > 0 && first >= 0 && (int64_t)first + k <= m.n_orf) memcpy(dforb.data() + m.orf_off + first, from, (size_t)k);
+            from += k;
+        });
+    }
+    c->h_qrec.assign(n, DReannRec{});
+    c->h_qgenes.clear();
+    if (!any) return PHX_OK;
+    int rc;
+    if ((rc = ensure(c, c->b_qmeta, (n + 1) * sizeof(DMeta))) || (rc = ensure(c, c->b_qtot, sizeof(DTotals))) || (rc = ensure(c, c->b_qdist, (V + 1) * limbs * 8)) ||
+        (rc = ensure(c, c->b_qparent, (V + 1) * 4)) || (rc = ensure(c, c->b_qpath, (V + 1) * 4)) || (rc = ensure(c, c->b_qgenes, (V + n + 1) * sizeof(DGene))) || // (a path has at most V / 2 pairs, one replaced by k_rs_inorder takes new slots)
+        (rc = ensure(c, c->b_qgtot, 16)) || (rc = ensure(c, c->b_qmask, (E / 32 + 2) * 4)) || (rc = ensure(c, c->b_qforb, N + 1)) || (rc = ensure(c, c->b_qsel, (n + 1) * 4)) ||
+        (rc = ensure(c, c->b_qplan, V / 32 + n + 2)) || (rc = ensure(c, c->b_qrec, (n + 1) * sizeof(DReannRec))))
+        return rc;
+    if (!c->b_qtie.p && (rc = ensure(c, c->b_qtie, (size_t)std::max<int64_t>(c->tie_seen, 1 << 20)))) return rc;
+    if ((rc = analysis_events(c))) return rc;
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipMemcpyAsync(c->b_qforb.p, dforb.data(), N + 1, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->b_qsel.p, c->h_qsel.data(), n * 4, hipMemcpyHostToDevice, s));
+    DTotals &tot = c->h_qtot;
+    uint32_t &gtot = c->h_qgtot;
+    gtot = 0;
+    for (int attempt = 0;; attempt++) {
+        DBatch b;
+        DReann q;
+        reann_batch(c, &b, &q);
+        HIPCHK(c, hipEventRecord(c->aev[0], s));
+        HIPCHK(c, hipMemcpyAsync(c->b_qmeta.p, c->b_meta.p, n * sizeof(DMeta), hipMemcpyDeviceToDevice, s)); // the layout and the run's verdicts; the kernels write this copy
+        HIPCHK(c, hipMemsetAsync(c->b_qtot.p, 0, sizeof(DTotals), s));
+        HIPCHK(c, hipMemsetAsync(c->b_qgtot.p, 0, 16, s));
+        HIPCHK(c, hipMemsetAsync(c->b_qrec.p, 0, (n + 1) * sizeof(DReannRec), s));
+        HIPCHK(c, hipMemsetAsync(c->b_qmask.p, 0, (E / 32 + 2) * 4, s));
+        phxk_reann_mask(&b, &q, s);
+        HIPCHK(c, hipEventRecord(c->aev[1], s));
+        phxk_reann_solve(&b, &q, nlm, s);
+        HIPCHK(c, hipEventRecord(c->aev[2], s));
+        phxk_reann_finish(&b, &q, nlm, s);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(c->h_qrec.data(), c->b_qrec.p, n * sizeof(DReannRec), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipEventRecord(c->aev[3], s));
+        HIPCHK(c, hipMemcpyAsync(&tot, c->b_qtot.p, sizeof(DTotals), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(&gtot, c->b_qgtot.p, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        if (!(tot.overflow & 4)) break;
+        // k_rs_inorder's scratch was too small for the contigs with equal-length alternatives: grow it and solve again
+        if (attempt >= 2) { c->err = "re-annotation: the tie scratch did not settle"; return PHX_E_STATE; }
+        if ((rc = ensure(c, c->b_qtie, (size_t)tot.tie_need + (size_t)tot.tie_need / 4 + 4096))) return rc;
+    }
+    if ((size_t)gtot > V + n) { c->err = "re-annotation: gene records beyond the buffer"; return PHX_E_STATE; }
+    c->h_qgenes.resize(gtot);
+    HIPCHK(c, hipEventRecord(c->aev[4], s));
+    if (gtot) HIPCHK(c, hipMemcpyAsync(c->h_qgenes.data(), c->b_qgenes.p, (size_t)gtot * sizeof(DGene), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipEventRecord(c->aev[5], s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    c->reann_ms[0] = ev_ms(c->aev[0], c->aev[1]);
+    c->reann_ms[1] = ev_ms(c->aev[1], c->aev[2]);
+    c->reann_ms[2] = ev_ms(c->aev[2], c->aev[3]) + ev_ms(c->aev[4], c->aev[5]);
+    for (size_t i = 0; i < n; i++) {
+        if (!c->h_qsel[i]) continue;
+        const DReannRec &r = c->h_qrec[i];
+        if (r.n_genes < 0 || r.gene_off < 0 || (uint64_t)r.gene_off + (uint64_t)r.n_genes > (uint64_t)gtot) { c->err = "re-annotation: a contig's gene records lie outside the buffer"; return PHX_E_STATE; }
+    }
+    return PHX_OK;
+}
+
+int phx_reannotate_flat(phx_ctx *c, const uint8_t *forbid, const int64_t *orf_offsets, uint32_t flags, phx_gene *genes, int64_t cap, int64_t *offsets, int32_t *status,
+                        double *delta, int64_t *total_out) {
+    if (!c || (c->n > 0 && (!offsets || !status || !delta || !orf_offsets))) return PHX_E_ARG;
+    { const int ra = after_run(c); if (ra) return ra; }
+    { const int rf = fetch_meta(c); if (rf) return rf; }
+    try {
+    // the offsets must be the batch's cumulative ORF counts (what phx_margins_flat reports): nothing from the caller indexes device memory unchecked
+    int64_t acc = 0;
+    for (int i = 0; i < c->n; i++) {
+        if (orf_offsets[i] != acc) return PHX_E_ARG;
+        if (reann_status(c, i) >= 0) acc += c->meta[(size_t)i].n_orf;
+    }
+    if (c->n > 0 && orf_offsets[c->n] != acc) return PHX_E_ARG;
+    if (acc > 0 && !forbid) return PHX_E_ARG;
+    const size_t N = (size_t)acc;
+    if (!(c->done.reann && c->h_qflags == flags && c->h_qforb.size() == N && (N == 0 || memcmp(c->h_qforb.data(), forbid, N) == 0))) {
+        c->done.reann = false;
+        c->h_qsel.assign((size_t)c->n, 0);
+        for (int i = 0; i < c->n; i++) {
+            if (!reann_contig(c, i)) continue;
+            bool want = (flags & 1u) != 0;
+            for (int64_t k = orf_offsets[i]; k < orf_offsets[i + 1] && !want; k++) want = forbid[k] != 0;
+            c->h_qsel[(size_t)i] = want ? 1 : 0;
+        }
+        { const int rq = reann_compute(c, forbid, orf_offsets); if (rq) { (void)hipStreamSynchronize(c->stream); return rq; } } // (nothing of a failed solve stays in flight)
+        c->h_qforb.assign(forbid, forbid + N);
+        c->h_qflags = flags;
+        c->done.reann = true;
+    }
+    // the run's own genes for the contigs that were not solved again (the device's lists: no host re-solve enters)
+    int64_t total = 0;
+    for (int i = 0; i < c->n; i++) {
+        const int32_t st = reann_status(c, i);
+        offsets[i] = total; status[i] = st; delta[i] = std::numeric_limits<double>::infinity();
+        if (st < 0) continue;
+        if (c->h_qsel[(size_t)i]) {
+            const DReannRec &r = c->h_qrec[(size_t)i];
+            status[i] = r.status; delta[i] = r.delta;
+            if (r.status >= 0) total += r.n_genes;
+        } else {
+            if (st != PHX_S_NOPATH) delta[i] = 0.0;
+            if (c->res[(size_t)i].n_genes > 0) total += c->res[(size_t)i].n_genes;
+        }
+    }
+    offsets[c->n] = total;
+    if (total_out) *total_out = total;
+    if (!genes) return PHX_OK; // size query
+    if (cap < total) return PHX_E_ARG;
+    { const int rg = stage_run_genes(c, c->h_qsel.data()); if (rg) return rg; } // (of the contigs that were not solved again)
+    for (int i = 0; i < c->n; i++) {
+        const int64_t k = offsets[i + 1] - offsets[i];
+        if (k <= 0) continue;
+        const DGene *src = c->h_qsel[(size_t)i] ? c->h_qgenes.data() + c->h_qrec[(size_t)i].gene_off : (const DGene *)c->h_genes.p + (size_t)c->res[(size_t)i].gene_off;
+        memcpy(genes + offsets[i], src, sizeof(phx_gene) * (size_t)k);
+    }
+    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_reannotate_flat"; return PHX_E_NOMEM; }
+    return PHX_OK;
+}
+
+int phx_orf_offsets(phx_ctx *c, int64_t *orf_offsets) {
+    if (!c || !orf_offsets) return PHX_E_ARG;
+    { const int ra = after_run(c); if (ra) return ra; }
+    { const int rf = fetch_meta(c); if (rf) return rf; }
+    int64_t acc = 0;
+    for (int i = 0; i < c->n; i++) { orf_offsets[i] = acc; if (reann_status(c, i) >= 0) acc += c->meta[(size_t)i].n_orf; }
+    orf_offsets[c->n] = acc;
+    return PHX_OK;
+}
+
+int phx_tap_repath(phx_ctx *c, int32_t contig, int32_t *path, int32_t cap, int32_t *n_path, uint64_t *dist_limbs, int32_t cap_limbs) {
+    if (c && c->ran && !c->in_flight && !c->done.reann) return PHX_E_STATE; // no re-annotation of this run
+    TAP_PRE(c, contig);
+    if (!c->done.reann) return PHX_E_STATE;
+    if (!c->h_qsel[(size_t)contig]) { // the run's result stands
+        if (reann_status(c, contig) < 0) { if (n_path) *n_path = 0; return PHX_OK; }
+        return phx_tap_path(c, contig, path, cap, n_path, dist_limbs, cap_limbs);
+    }
+    const DReannRec &r = c->h_qrec[(size_t)contig];
+    if (n_path) *n_path = 0;
+    if (r.status < 0 || r.n_path <= 0) return PHX_OK;
+    if (n_path) *n_path = r.n_path;
+    if (path) {
+        if (cap < r.n_path) return PHX_E_ARG;
+        HIPCHK(c, hipMemcpy(path, (int32_t *)c->b_qpath.p + m.node_off, (size_t)r.n_path * 4, hipMemcpyDeviceToHost));
+    }
+    if (dist_limbs) {
+        if (cap_limbs < m.sssp_nl) return PHX_E_ARG;
+        const size_t tgt = (size_t)m.node_off * (size_t)c->n_limbs + ((size_t)m.n_node - 1) * (size_t)m.sssp_nl;
+        HIPCHK(c, hipMemcpy(dist_limbs, (uint64_t *)c->b_qdist.p + tgt, (size_t)m.sssp_nl * 8, hipMemcpyDeviceToHost));
+    }
+    return PHX_OK;
+}
+
+int phx_reannotate_ms(phx_ctx *c, float *ms) {
+    if (!c || !ms) return PHX_E_ARG;
+    for (int k = 0; k < 3; k++) ms[k] = c->reann_ms[k];
+    return PHX_OK;
+}

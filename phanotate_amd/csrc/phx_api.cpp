@@ -37,6 +37,13 @@ const char *kStageName[PHX_N_STAGES] = {"memset", "features", "orf_count", "orf_
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    DevBuf *next = nullptr; // phx_ctx::bufs: every buffer ensure() has allocated, for phx_destroy
+    bool listed = false;
+};
+// pinned host memory that grows on demand (ensure_pinned)
+struct PinBuf {
+    void *p = nullptr;
+    size_t cap = 0;
 };
 
 // per-contig records on the host, in pinned memory (they cross PCIe several times per run)
@@ -130,8 +137,7 @@ struct phx_ctx {
     int n_limbs = 0;
     MetaBuf meta;            // host copy of the per-contig records: the layout as the host set it; the device's values after fetch_meta()
     bool meta_stale = false; // a run has finished since c->meta was last fetched
-    DRes *res = nullptr;     // pinned: status / gene count / first gene of every contig after a run
-    size_t res_cap = 0;
+    DRes *res = nullptr;     // pinned (pin_res): status / gene count / first gene of every contig after a run
     std::vector<uint32_t> ftab; // k_features' tables: voff (n + 1: first virtual word = first record - 1 of every contig), then wfirst (per 62 virtual words: the contig of the first)
     uint32_t vtotal = 0;        // virtual words of the batch (records without the two pads)
     bool defcod = false;        // the codon tables are the reference's defaults
@@ -139,12 +145,14 @@ struct phx_ctx {
     hipEvent_t ev_upload = nullptr; bool upload_pending = false; // recorded behind the last copy of phx_upload
     hipEvent_t ev_layout = nullptr; bool layout_pending = false; // recorded behind push_layout's copies
     hipEvent_t ev_piece[2] = {nullptr, nullptr};                  // phx_upload: a piece's copy -> its k_features launch
-    void *h_tiles = nullptr; size_t h_tiles_cap = 0;             // pinned copy of ftab
+    PinBuf h_tiles;                                               // pinned copy of ftab
     bool eager_now = false;    // ... and this launch is that run (launch_once)
     bool eager_done = false;   // phx_upload has already reset the accumulators and run k_features for this batch: the next run starts behind them
     bool trna_clean = true;    // no phx_set_trnas with hits since the layout was set
     std::unique_ptr<StagePool> pool;
     // buffers
+    DevBuf *bufs = nullptr; // those that hold memory (ensure() lists a buffer at its first allocation, phx_destroy releases the list)
+    PinBuf pin_res, h_stage, h_genes, h_mrec, h_drec; // h_stage: H2D of the bases (records); h_genes: D2H of the gene records at link rate; h_mrec, h_drec: the margins' and the drops' device records
     DevBuf b_bridge, b_recs, b_meta, b_tiles, b_nbits, b_nbase, b_cbits, b_orf, b_ostat, b_oweight, b_owi, b_oflag, b_onode, b_grp, b_bits, b_cpre, b_bpre, b_item, b_iprev;
     DevBuf b_ewf, b_esrcf;   // fp64 weights and plain sources of the batch last run, recomputed for the edge tap (k_edges<true, true>)
     bool tapw_valid = false; // ... are those of the run whose results the context holds
@@ -186,9 +194,6 @@ struct phx_ctx {
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
     int graph_flags = -1;
-    void *h_stage = nullptr; // pinned staging for H2D of the bases (records)
-    size_t h_stage_cap = 0;
-    DGene *h_genes = nullptr; size_t h_genes_cap = 0; // pinned staging of the gene records (D2H at link rate)
     // profiling
     bool prof = false;
     uint32_t prof_mask = 0xffffffffu; // stages that are bracketed by events when prof is on
@@ -222,40 +227,42 @@ struct phx_ctx {
     bool plan_stream_off = false;  // ... after the first of them the solver is launched behind its planner again on this context
     // per-ORF margins (phx_margins_flat): buffers allocated at the first call, results kept until the next run
     DevBuf b_mo, b_md, b_mw, b_mdt, b_mrec, b_mstat;
-    bool margins_done = false;       // the records of the run whose results the context holds are in h_mrec / mstat
-    phx_orf_margin *h_mrec = nullptr; size_t h_mrec_cap = 0; // pinned: the device's records (device ORF order)
+    // What the analyses have computed for the run whose results the context holds: reset as a whole by a new batch layout and by every launch.
+    // (Buffers and capacities are no part of it: they outlive runs.)
+    struct RunDone {
+        bool rev = false;     // the margins' shared part: out-edge CSR, d_t, mstat
+        bool margins = false; // the ORF records are in h_mrec (device ORF order)
+        bool drops = false;   // the drop records are in h_drec (a record per pair of the path), at droff
+        bool trees = false;   // ... and the drop kernels kept the one-hop trees (b_dps / b_dts)
+        bool repl = false;    // h_rrec / h_rgenes / h_rdet
+        bool reann = false;   // h_q* hold the re-annotation for the mask h_qforb / h_qflags
+        bool grp = false;     // h_grp
+    } done;
+    std::vector<DGrp> h_grp;         // the run's group records (device order <-> reference order of the ORFs: each_group_in_reference_order)
+    // The analyses' timing events.  One set serves all four: an analysis records its first event only after the ensure_* it builds on has
+    // returned, and reads its spans behind its own stream synchronise, before it returns — no span is read after a later analysis has
+    // recorded over its events.
+    hipEvent_t aev[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     std::vector<int32_t> mstat;      // per contig: the reverse pass did not settle
-    std::vector<DGrp> mgrp;          // the group records (reference order of the ORFs)
-    hipEvent_t mev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     float margins_ms[4] = {0, 0, 0, 0};
-    bool rev_done = false;           // the margins' shared part (out-edge CSR, d_t, mstat) of the run whose results the context holds
-    float rev_ms[2] = {0, 0};        // ... its device time: out-edge CSR, reverse pass
+    float rev_ms[2] = {0, 0};        // device time of the shared part: out-edge CSR, reverse pass
     // gene drop margins (phx_drop_margins_flat): buffers allocated at the first call, results kept until the next run
     DevBuf b_dpi, b_djs, b_djt, b_dfi, b_dla, b_dslot, b_dgtab, b_doff, b_dsx, b_dcx, b_dda, b_ddb, b_drec, b_dstats;
-    bool drops_done = false;
-    phx_gene_drop *h_drec = nullptr; size_t h_drec_cap = 0; // pinned: the device's records (a record per pair of the path)
     std::vector<int64_t> droff;      // per contig (+1): first record in h_drec
-    hipEvent_t dev_[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     float drop_ms[4] = {0, 0, 0, 0};
     int64_t drop_stats[4] = {0, 0, 0, 0};
-    bool drop_trees = false;         // the drop kernels of the run kept the one-hop trees (b_dps / b_dts)
     // drop replacements (phx_replacements_flat): buffers allocated at the first call, results kept until the next run
     DevBuf b_dps, b_dts, b_rwin, b_rxs, b_rcoff, b_rcm, b_rchain, b_rrnd, b_rinfo, b_rdoff, b_rdet, b_rgenes, b_rrec, b_rcnt;
-    bool repl_done = false;
     std::vector<phx_gene_repl> h_rrec; // per device record (as h_drec); gene_off into h_rgenes
     std::vector<phx_gene> h_rgenes;
     std::vector<int32_t> h_rdet, h_rinfo; // the detours; per record a, b, m, genes
     std::vector<int64_t> h_rdoff;     // per record: first detour node in h_rdet
     std::vector<std::vector<int32_t>> h_rpath; // per contig: its device path, fetched by the first phx_tap_replacement of the run
     int64_t rchain_cap = 0;           // delta-chain nodes b_rchain has room for
-    hipEvent_t rev_ev[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     float repl_ms[3] = {0, 0, 0};
     int64_t repl_stats[5] = {0, 0, 0, 0, 0};
     // masked re-annotation (phx_reannotate_flat): buffers allocated at the first call, the result kept until the next upload or run
     DevBuf b_qmeta, b_qtot, b_qdist, b_qparent, b_qpath, b_qgenes, b_qgtot, b_qtie, b_qmask, b_qforb, b_qsel, b_qplan, b_qrec;
-    bool reann_done = false;          // h_q* hold the re-annotation of the run whose results the context holds, for the mask h_qforb / h_qflags
-    bool qgrp_done = false;           // qgrp holds that run's group records (tap order <-> device order of the ORFs)
-    std::vector<DGrp> qgrp;
     std::vector<uint8_t> h_qforb;     // the mask last solved, tap order (one byte per ORF of the batch)
     uint32_t h_qflags = 0;
     std::vector<int32_t> h_qsel;      // per contig: solved again (else: the run's result stands)
@@ -264,7 +271,6 @@ struct phx_ctx {
     std::vector<uint8_t> h_qdforb;    // the mask in device ORF order, and the totals read back: members, so that a copy enqueued before
     DTotals h_qtot;                   //   an early error return never points at memory that has gone out of scope
     uint32_t h_qgtot = 0;
-    hipEvent_t qev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     float reann_ms[3] = {0, 0, 0};
     float stage_ms[PHX_N_STAGES] = {0};
     int stage_n[PHX_N_STAGES] = {0};
@@ -290,6 +296,7 @@ int ensure(phx_ctx *c, DevBuf &b, size_t bytes) {
     c->graph_valid = false; // a buffer moves: the captured graph holds stale pointers
     if (b.p) HIPCHK(c, hipFree(b.p));
     b.p = nullptr; b.cap = 0;
+    if (!b.listed) { b.listed = true; b.next = c->bufs; c->bufs = &b; }
     size_t want = bytes + bytes / 8 + 4096;
     HIPCHK(c, hipMalloc(&b.p, want));
     b.cap = want;
@@ -301,6 +308,15 @@ int ensure(phx_ctx *c, DevBuf &b, size_t bytes) {
 void release(DevBuf &b) {
     if (b.p) (void)hipFree(b.p);
     b.p = nullptr; b.cap = 0;
+}
+// at least `need` bytes of pinned memory; what a buffer too small is replaced by is `grow_to` bytes (the caller's slack)
+int ensure_pinned(phx_ctx *c, PinBuf &b, size_t need, size_t grow_to) {
+    if (need <= b.cap) return PHX_OK;
+    if (b.p) HIPCHK(c, hipHostFree(b.p));
+    b.p = nullptr; b.cap = 0;
+    HIPCHK(c, hipHostMalloc(&b.p, grow_to, hipHostMallocDefault));
+    b.cap = grow_to;
+    return PHX_OK;
 }
 
 inline int code_of(char c) { return c == 'a' ? 0 : c == 'c' ? 1 : c == 't' ? 2 : c == 'g' ? 3 : -1; }
@@ -479,7 +495,7 @@ int set_batch_layout(phx_ctx *c, int32_t n, const int64_t *len_or_null, const in
     c->uploaded = false; c->ran = false; c->graph_valid = false; c->n = 0; // whatever fails below leaves the context without a batch
     c->meta_stale = false;
     c->has_trna = false; c->h_tnode.clear();
-    c->margins_done = false; c->rev_done = false; c->drops_done = false; c->drop_trees = false; c->repl_done = false; c->reann_done = false; c->qgrp_done = false;
+    c->done = phx_ctx::RunDone();
     if (n < 0) return PHX_E_ARG;
     if (!c->meta.assign((size_t)n)) { c->err = "hipHostMalloc failed"; return PHX_E_NOMEM; }
     c->ftab.clear(); c->vtotal = 0;
@@ -536,13 +552,9 @@ int ensure_position_buffers(phx_ctx *c) {
     if (sssp_ordered(c) && (rc = ensure(c, c->b_sord, (size_t)c->n * 4))) return rc;
     if ((rc = ensure(c, c->b_gtab, ((size_t)c->n + 1) * GT_N * 10))) return rc; // per contig: the weights of its coded gap edges (k_edges<true>)
     if ((rc = ensure(c, c->b_res, ((size_t)c->n + 1) * sizeof(DRes) + sizeof(DTotals)))) return rc; // (k_results appends the totals: one copy brings both to the host)
-    if (c->res_cap < (size_t)c->n + 1) {
-        if (c->res) (void)hipHostFree(c->res);
-        c->res = nullptr; c->res_cap = 0;
-        const size_t want = (size_t)c->n + (size_t)c->n / 4 + 16;
-        if (hipHostMalloc((void **)&c->res, want * sizeof(DRes) + sizeof(DTotals), hipHostMallocDefault) != hipSuccess) { c->res = nullptr; c->err = "hipHostMalloc failed"; return PHX_E_NOMEM; }
-        c->res_cap = want;
-    }
+    rc = ensure_pinned(c, c->pin_res, ((size_t)c->n + 1) * sizeof(DRes) + sizeof(DTotals), ((size_t)c->n + (size_t)c->n / 4 + 16) * sizeof(DRes) + sizeof(DTotals));
+    c->res = (DRes *)c->pin_res.p; // (null after a failure)
+    if (rc) return rc;
     if ((rc = ensure(c, c->b_bits, (size_t)(c->tot_words + 8) * 8))) return rc;
     { // prefix popcounts (k_bit_prefix): of the class bitmaps one record per PHX_PRE_G words — 6 planes of nw / G + 1 records of 32 bytes —, of the bases 2 nw + 2 entries of 16 bytes per contig
         const size_t W = (size_t)(c->tot_words / PHX_BITMAP_WORDS_PER_NW);
@@ -730,35 +742,20 @@ void phx_destroy(phx_ctx *c) {
     (void)hipSetDevice(c->device);
     c->in_flight = false;
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    DevBuf *all[] = {&c->b_eref, &c->b_cint, &c->b_csig, &c->b_meta0, &c->b_tie, &c->b_ekey, &c->b_tnode, &c->b_tedge, &c->b_tnid, &c->b_tbits, &c->b_win, &c->b_wrole, &c->b_bridge, &c->b_recs, &c->b_meta, &c->b_tiles, &c->b_nbits, &c->b_nbase, &c->b_cbits, &c->b_orf, &c->b_ostat, &c->b_oweight, &c->b_owi, &c->b_oflag, &c->b_ewf, &c->b_esrcf, &c->b_onode, &c->b_grp, &c->b_bits, &c->b_cpre, &c->b_bpre, &c->b_item, &c->b_iprev,
-                     &c->b_node, &c->b_parent, &c->b_inoff, &c->b_no, &c->b_npos, &c->b_ehit, &c->b_mreach, &c->b_olist, &c->b_dist, &c->b_esrc, &c->b_ew, &c->b_ewl, &c->b_path, &c->b_genes, &c->b_gtot, &c->b_tot, &c->b_lpart, &c->b_res, &c->b_sord, &c->b_gtab, &c->b_erank, &c->b_swin, &c->b_swrole, &c->b_sdist, &c->b_segw,
-                     &c->b_mo, &c->b_md, &c->b_mw, &c->b_mdt, &c->b_mrec, &c->b_mstat,
-                     &c->b_dpi, &c->b_djs, &c->b_djt, &c->b_dfi, &c->b_dla, &c->b_dslot, &c->b_dgtab, &c->b_doff, &c->b_dsx, &c->b_dcx, &c->b_dda, &c->b_ddb, &c->b_drec, &c->b_dstats,
-                     &c->b_dps, &c->b_dts, &c->b_rwin, &c->b_rxs, &c->b_rcoff, &c->b_rcm, &c->b_rchain, &c->b_rrnd, &c->b_rinfo, &c->b_rdoff, &c->b_rdet, &c->b_rgenes, &c->b_rrec, &c->b_rcnt,
-                     &c->b_qmeta, &c->b_qtot, &c->b_qdist, &c->b_qparent, &c->b_qpath, &c->b_qgenes, &c->b_qgtot, &c->b_qtie, &c->b_qmask, &c->b_qforb, &c->b_qsel, &c->b_qplan, &c->b_qrec};
-    for (DevBuf *b : all) release(*b);
-    for (hipEvent_t e : c->qev) if (e) (void)hipEventDestroy(e);
-    if (c->h_mrec) (void)hipHostFree(c->h_mrec);
-    if (c->h_drec) (void)hipHostFree(c->h_drec);
-    for (hipEvent_t e : c->mev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->dev_) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->rev_ev) if (e) (void)hipEventDestroy(e);
+    for (DevBuf *b = c->bufs; b; b = b->next) release(*b);
+    for (PinBuf *b : {&c->pin_res, &c->h_stage, &c->h_tiles, &c->h_genes, &c->h_mrec, &c->h_drec}) if (b->p) (void)hipHostFree(b->p);
+    for (hipEvent_t e : c->aev) if (e) (void)hipEventDestroy(e);
     if (c->graph_exec) (void)hipGraphExecDestroy(c->graph_exec);
     if (c->graph) (void)hipGraphDestroy(c->graph);
     if (c->h_tot) (void)hipHostFree(c->h_tot);
     if (c->d_params) (void)hipFree(c->d_params);
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    if (c->h_genes) (void)hipHostFree(c->h_genes);
     c->meta.release();
-    if (c->res) (void)hipHostFree(c->res);
-    c->res = nullptr; c->res_cap = 0;
     collect_timers(c);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     for (int a = 0; a < 4; a++) { if (c->aux[a] && !c->one_stream) (void)hipStreamDestroy(c->aux[a]); if (c->ev_join[a]) (void)hipEventDestroy(c->ev_join[a]); }
     if (c->ev_upload) (void)hipEventDestroy(c->ev_upload);
     if (c->ev_layout) (void)hipEventDestroy(c->ev_layout);
     for (int k = 0; k < 2; k++) if (c->ev_piece[k]) (void)hipEventDestroy(c->ev_piece[k]);
-    if (c->h_tiles) (void)hipHostFree(c->h_tiles);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_fork_plan) (void)hipEventDestroy(c->ev_fork_plan);
     if (c->ev_fork_nodes) (void)hipEventDestroy(c->ev_fork_nodes);
@@ -797,12 +794,7 @@ int phx_upload(phx_ctx *c, int32_t n, const char *const *seq, const int64_t *len
     // every letter anyway and writes — and PCIe moves — three bits per base.
     const size_t T = ((size_t)c->vtotal + 2) * 36;
     if ((rc = ensure(c, c->b_recs, T))) return rc;
-    if (c->h_stage_cap < T) {
-        if (c->h_stage) HIPCHK(c, hipHostFree(c->h_stage));
-        c->h_stage = nullptr; c->h_stage_cap = 0;
-        HIPCHK(c, hipHostMalloc(&c->h_stage, T + T / 8, hipHostMallocDefault));
-        c->h_stage_cap = T + T / 8;
-    }
+    if ((rc = ensure_pinned(c, c->h_stage, T, T + T / 8))) return rc;
     // Packed into pinned memory and sent in pieces of >= 4 Mbases (whole contigs; 2 MB copies reach ~45 of the link's 56 GB/s), so
     // that the DMA of one piece overlaps the packing of the next.  Large batches are packed by the context's worker threads, all of
     // them on the earliest unfinished piece (items of <= 96 Kbases, taken in order), so that the first copy starts after 1/threads
@@ -827,7 +819,7 @@ int phx_upload(phx_ctx *c, int32_t n, const char *const *seq, const int64_t *len
     struct Item { const char *in; int64_t n; uint32_t *out; int64_t nrec; int piece; };
     std::vector<Piece> pieces;
     std::vector<Item> items;
-    uint32_t *stage = (uint32_t *)c->h_stage;
+    uint32_t *stage = (uint32_t *)c->h_stage.p;
     {
         const int64_t piece = PHX_UPLOAD_PIECE / 96, chunk = 96 * 1024; // (records; letters)
         int64_t sent = 0; int first = 0; // record 0, the pad, goes with the first piece
@@ -848,7 +840,7 @@ int phx_upload(phx_ctx *c, int32_t n, const char *const *seq, const int64_t *len
     }
     auto send_piece = [&](const Piece &pc) {
         const size_t b0 = (size_t)pc.r0 * 36, b1 = (size_t)pc.r1 * 36;
-        hipError_t e = hipMemcpyAsync((char *)c->b_recs.p + b0, (char *)c->h_stage + b0, b1 - b0, hipMemcpyHostToDevice, c->stream);
+        hipError_t e = hipMemcpyAsync((char *)c->b_recs.p + b0, (char *)c->h_stage.p + b0, b1 - b0, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess && eager) { // this piece's records, as soon as its bases have landed
             hipEvent_t ev = c->ev_piece[n_sent & 1];
             const uint32_t v0 = c->ftab[(size_t)pc.i0], v1 = c->ftab[(size_t)pc.i1];
@@ -1291,13 +1283,8 @@ int push_layout(phx_ctx *c) {
     }
     if (c->tiles_dirty) { // once per batch layout
         const size_t tb = 4 * c->ftab.size();
-        if (c->h_tiles_cap < tb) {
-            if (c->h_tiles) HIPCHK(c, hipHostFree(c->h_tiles));
-            c->h_tiles = nullptr; c->h_tiles_cap = 0;
-            HIPCHK(c, hipHostMalloc(&c->h_tiles, tb + tb / 4 + 4096, hipHostMallocDefault));
-            c->h_tiles_cap = tb + tb / 4 + 4096;
-        }
-        if (tb) { memcpy(c->h_tiles, c->ftab.data(), tb); HIPCHK(c, hipMemcpyAsync(c->b_tiles.p, c->h_tiles, tb, hipMemcpyHostToDevice, s)); }
+        { const int rp = ensure_pinned(c, c->h_tiles, tb, tb + tb / 4 + 4096); if (rp) return rp; }
+        if (tb) { memcpy(c->h_tiles.p, c->ftab.data(), tb); HIPCHK(c, hipMemcpyAsync(c->b_tiles.p, c->h_tiles.p, tb, hipMemcpyHostToDevice, s)); }
         c->tiles_dirty = false; pushed = true;
     }
     if (pushed) { HIPCHK(c, hipEventRecord(c->ev_layout, s)); c->layout_pending = true; }
@@ -1312,7 +1299,7 @@ int push_layout(phx_ctx *c) {
 int launch_once(phx_ctx *c, bool learn) {
     int rc;
     c->tapw_valid = false; c->cert_done = false; c->exact_done = false; c->exact_genes.clear(); c->exact_failed = 0; c->host_only.clear();
-    c->margins_done = false; c->rev_done = false; c->drops_done = false; c->drop_trees = false; c->repl_done = false; c->reann_done = false; c->qgrp_done = false;
+    c->done = phx_ctx::RunDone();
     hipStream_t s = c->stream;
     c->eager_now = c->eager_done && !c->meta0_dirty && !c->tiles_dirty; // the first launch after such an upload only: a repeated or retried run does everything
     c->eager_done = false;
@@ -1522,38 +1509,47 @@ int phx_run(phx_ctx *c) {
     return PHX_OK;
 }
 
-static int ensure_gene_stage(phx_ctx *c, size_t n) {
-    if (n <= c->h_genes_cap) return PHX_OK;
-    if (c->h_genes) HIPCHK(c, hipHostFree(c->h_genes));
-    c->h_genes = nullptr; c->h_genes_cap = 0;
-    const size_t cap = n + n / 4 + 1024;
-    HIPCHK(c, hipHostMalloc((void **)&c->h_genes, cap * sizeof(DGene), hipHostMallocDefault));
-    c->h_genes_cap = cap;
+// What the entry points that read a run's results begin with: a run in flight is brought to its end, a context that has not run is
+// refused, the device is selected.  (Null and argument checks stay with the callers.)
+static int wait_in_flight(phx_ctx *c) { return c->in_flight ? phx_wait(c) : PHX_OK; }
+static int after_run(phx_ctx *c) {
+    { const int rs = wait_in_flight(c); if (rs) return rs; }
+    if (!c->ran) return PHX_E_STATE;
+    HIPCHK(c, hipSetDevice(c->device));
     return PHX_OK;
+}
+
+// The run's gene records on the host (c->h_genes.p; contig i's at DRes.gene_off), synchronised.  skip: contigs whose records are not wanted.
+static int stage_run_genes(phx_ctx *c, const int32_t *skip = nullptr) {
+    int64_t hi = 0;
+    for (int i = 0; i < c->n; i++) if (!skip || !skip[i]) hi = std::max<int64_t>(hi, c->res[i].gene_off + c->res[i].n_genes);
+    if (!hi) return PHX_OK;
+    { const int rp = ensure_pinned(c, c->h_genes, (size_t)hi * sizeof(DGene), ((size_t)hi + (size_t)hi / 4 + 1024) * sizeof(DGene)); if (rp) return rp; }
+    HIPCHK(c, hipMemcpyAsync(c->h_genes.p, (const DGene *)c->b_genes.p + (gene_pack(c) ? gene_half(c) : 0), sizeof(DGene) * (size_t)hi, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PHX_OK;
+}
+// the genes phx_download* deliver for contig i (after stage_run_genes): the host re-solve's list replaces the device's where there is one
+static const DGene *delivered_genes(const phx_ctx *c, int i, int64_t *n) {
+    const auto ex = c->exact_genes.find(i);
+    if (ex != c->exact_genes.end()) { *n = (int64_t)ex->second.size(); return ex->second.data(); }
+    *n = c->res[(size_t)i].n_genes;
+    return (const DGene *)c->h_genes.p + (size_t)c->res[(size_t)i].gene_off;
 }
 
 static int ensure_exact(phx_ctx *c); // certificate, and the host re-solve of what it leaves open (below, behind the taps it reads)
 
 int phx_download(phx_ctx *c, phx_result *out) {
     if (!c || (!out && c->n > 0)) return PHX_E_ARG;
-    if (c->in_flight) { const int rs = phx_wait(c); if (rs) return rs; }
-    if (!c->ran) return PHX_E_STATE;
-    HIPCHK(c, hipSetDevice(c->device));
+    { const int ra = after_run(c); if (ra) return ra; }
     { const int rx = ensure_exact(c); if (rx) return rx; }
-    int64_t total = 0;
-    for (int i = 0; i < c->n; i++) total = std::max<int64_t>(total, c->res[i].gene_off + c->res[i].n_genes);
-    { const int rg = ensure_gene_stage(c, (size_t)total); if (rg) return rg; }
-    if (total) {
-        HIPCHK(c, hipMemcpyAsync(c->h_genes, (const DGene *)c->b_genes.p + (gene_pack(c) ? gene_half(c) : 0), sizeof(DGene) * (size_t)total, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
+    { const int rg = stage_run_genes(c); if (rg) return rg; }
     for (int i = 0; i < c->n; i++) { out[i].status = 0; out[i].n_genes = 0; out[i].genes = nullptr; } // (so that a failure half-way leaves nothing dangling)
     for (int i = 0; i < c->n; i++) {
-        const DRes &m = c->res[(size_t)i];
-        out[i].status = m.status;
-        const auto ex = c->exact_genes.find(i); // solved again on the host: those genes
-        const DGene *src = ex != c->exact_genes.end() ? ex->second.data() : c->h_genes + (size_t)m.gene_off;
-        out[i].n_genes = m.status < 0 ? 0 : (ex != c->exact_genes.end() ? (int32_t)ex->second.size() : m.n_genes);
+        int64_t ng = 0;
+        const DGene *src = delivered_genes(c, i, &ng);
+        out[i].status = c->res[(size_t)i].status;
+        out[i].n_genes = out[i].status < 0 ? 0 : (int32_t)ng;
         out[i].genes = nullptr;
         if (out[i].n_genes > 0) {
             out[i].genes = (phx_gene *)malloc(sizeof(phx_gene) * (size_t)out[i].n_genes);
@@ -1571,18 +1567,15 @@ int phx_download(phx_ctx *c, phx_result *out) {
 
 int phx_download_flat(phx_ctx *c, phx_gene *genes, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
     if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
-    if (c->in_flight) { const int rs = phx_wait(c); if (rs) return rs; }
-    if (!c->ran) return PHX_E_STATE;
-    HIPCHK(c, hipSetDevice(c->device));
+    { const int ra = after_run(c); if (ra) return ra; }
     { const int rx = ensure_exact(c); if (rx) return rx; }
-    auto count_of = [&](int i) -> int64_t { // genes of contig i: the host re-solve's where there was one
-        const DRes &m = c->res[(size_t)i];
-        if (m.status < 0) return 0;
-        if (!c->exact_genes.empty()) { const auto ex = c->exact_genes.find(i); if (ex != c->exact_genes.end()) return (int64_t)ex->second.size(); }
-        return m.n_genes;
+    auto count_of = [&](int i) -> int64_t { // genes of contig i
+        int64_t ng = 0;
+        if (c->res[(size_t)i].status >= 0) (void)delivered_genes(c, i, &ng);
+        return ng;
     };
-    int64_t total = 0, hi = 0;
-    for (int i = 0; i < c->n; i++) { const DRes &m = c->res[(size_t)i]; total += count_of(i); hi = std::max<int64_t>(hi, m.gene_off + m.n_genes); }
+    int64_t total = 0;
+    for (int i = 0; i < c->n; i++) total += count_of(i);
     if (total_out) *total_out = total;
     if (!genes) { // size query
         int64_t o = 0;
@@ -1591,19 +1584,14 @@ int phx_download_flat(phx_ctx *c, phx_gene *genes, int64_t cap, int64_t *offsets
         return PHX_OK;
     }
     if (cap < total) return PHX_E_ARG;
-    { const int rg = ensure_gene_stage(c, (size_t)hi); if (rg) return rg; }
-    if (hi) {
-        HIPCHK(c, hipMemcpyAsync(c->h_genes, (const DGene *)c->b_genes.p + (gene_pack(c) ? gene_half(c) : 0), sizeof(DGene) * (size_t)hi, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
+    { const int rg = stage_run_genes(c); if (rg) return rg; }
     static_assert(sizeof(DGene) == sizeof(phx_gene), "device and ABI gene records have the same layout");
     int64_t o = 0;
     for (int i = 0; i < c->n; i++) {
-        const DRes &m = c->res[(size_t)i];
-        const int64_t k = count_of(i);
-        offsets[i] = o; status[i] = m.status;
-        const DGene *src = &c->h_genes[(size_t)m.gene_off];
-        if (!c->exact_genes.empty()) { const auto ex = c->exact_genes.find(i); if (ex != c->exact_genes.end()) src = ex->second.data(); }
+        int64_t k = 0;
+        const DGene *src = delivered_genes(c, i, &k);
+        offsets[i] = o; status[i] = c->res[(size_t)i].status;
+        if (status[i] < 0) k = 0;
         if (k) memcpy(genes + o, src, sizeof(phx_gene) * (size_t)k);
         o += k;
     }
@@ -1644,8 +1632,7 @@ static int ensure_cert(phx_ctx *c) {
 
 int phx_certified(phx_ctx *c, int8_t *cert) {
     if (!c || (!cert && c->n > 0)) return PHX_E_ARG;
-    if (c->in_flight) { const int rs = phx_wait(c); if (rs) return rs; }
-    if (!c->ran) return PHX_E_STATE;
+    { const int ra = after_run(c); if (ra) return ra; }
     { const int rc = c->exact ? ensure_exact(c) : ensure_cert(c); if (rc) return rc; }
     for (int i = 0; i < c->n; i++) { const DRes &m = c->res[(size_t)i]; cert[i] = (int8_t)(!c->certify ? -1 : (m.status < 0 ? 1 : m.cert)); }
     return PHX_OK;
@@ -1783,7 +1770,7 @@ int phx_pool_annotate(phx_pool *p, int32_t n, const char *const *seq, const int6
 
 int phx_set_exact(phx_ctx *c, int on) {
     if (!c) return PHX_E_ARG;
-    if (c->in_flight) { const int rs = phx_wait(c); if (rs) return rs; }
+    { const int rs = wait_in_flight(c); if (rs) return rs; }
     if (!on) { // the device's own lists again, for every contig
         for (auto &kv : c->exact_genes) if (c->res && kv.first < c->n) c->res[(size_t)kv.first].cert = 0;
         for (int i : c->host_only) if (c->res && i < c->n) c->res[(size_t)i].status = PHX_S_OVERFLOW; // (the device has no genes for them)
@@ -1809,10 +1796,8 @@ void phx_free_results(phx_result *res, int32_t n) {
 // ---- taps ----
 #define TAP_PRE(c, contig)                                            \
     if (!(c)) return PHX_E_ARG;                                       \
-    if ((c)->in_flight) { const int rs_ = phx_wait(c); if (rs_) return rs_; } \
-    if (!(c)->ran) return PHX_E_STATE;                                \
+    { const int ra_ = after_run(c); if (ra_) return ra_; }            \
     if ((contig) < 0 || (contig) >= (c)->n) return PHX_E_ARG;         \
-    HIPCHK(c, hipSetDevice((c)->device));                             \
     { const int rf_ = fetch_meta(c); if (rf_) return rf_; }           \
     const DMeta &m = (c)->meta[(size_t)(contig)];
 
@@ -1950,11 +1935,15 @@ int phx_tap_positions(phx_ctx *c, int32_t contig, uint8_t *cls, uint8_t *gcc, ui
 
 // Reference insertion order of the stop-groups = ascending DGrp.evkey.  ref_rank[g] = rank of device
 // group g, ref_first[g] = number of ORFs in the groups before it.
-static void reference_order(const std::vector<DGrp> &grp, std::vector<int> &order, std::vector<int> &ref_rank, std::vector<int> &ref_first) {
-    const size_t G = grp.size();
-    order.resize(G); ref_rank.resize(G); ref_first.resize(G);
+static void reference_sort(const DGrp *grp, size_t G, std::vector<int> &order) {
+    order.resize(G);
     for (size_t g = 0; g < G; g++) order[g] = (int)g;
     std::sort(order.begin(), order.end(), [&](int a, int b) { return grp[(size_t)a].evkey < grp[(size_t)b].evkey; });
+}
+static void reference_order(const std::vector<DGrp> &grp, std::vector<int> &order, std::vector<int> &ref_rank, std::vector<int> &ref_first) {
+    const size_t G = grp.size();
+    reference_sort(grp.data(), G, order);
+    ref_rank.resize(G); ref_first.resize(G);
     int acc = 0;
     for (size_t r = 0; r < G; r++) { ref_rank[(size_t)order[r]] = (int)r; ref_first[(size_t)order[r]] = acc; acc += grp[(size_t)order[r]].n; }
 }
@@ -2143,756 +2132,7 @@ int phx_tap_dist(phx_ctx *c, int32_t contig, uint64_t *dist_limbs, int64_t cap_w
     return PHX_OK;
 }
 
-// ---- per-ORF path margins (phx_margins.inc) ----
-// limb classes of the contigs that have device distances (bit k: 2, 4, 8, 17 limbs)
-static int margins_nl_mask(const phx_ctx *c) {
-    int nlm = 0;
-    for (size_t i = 0; i < (size_t)c->n; i++) {
-        const DMeta &m = c->meta[i];
-        if (m.status < 0 || m.n_node <= 2 || m.sssp_mode == 4) continue;
-        nlm |= m.sssp_nl == 2 ? 1 : m.sssp_nl == 4 ? 2 : m.sssp_nl == 8 ? 4 : 8;
-    }
-    return nlm;
-}
-
-static void margins_args(phx_ctx *c, DMarg *g) {
-    g->out_off = (uint32_t *)c->b_mo.p; g->out_dst = (uint32_t *)c->b_md.p; g->out_w = (long long *)c->b_mw.p;
-    g->dist_t = (uint64_t *)c->b_mdt.p; g->rec = (phx_orf_margin *)c->b_mrec.p; g->mstat = (int32_t *)c->b_mstat.p;
-}
-
-// The shared part of the margins and the drop margins, once per run: the out-edge CSR, d_t and the reverse pass's per-contig verdicts
-// (c->mstat), kernel by kernel on the context's stream, outside the captured run graph.
-static int ensure_rev(phx_ctx *c) {
-    if (c->rev_done) return PHX_OK;
-    { const int rf = fetch_meta(c); if (rf) return rf; }
-    const size_t n = (size_t)c->n, V = (size_t)c->tot_node, E = (size_t)c->tot_edge, N = (size_t)c->tot_orf;
-    const size_t limbs = (size_t)std::max(c->n_limbs, 2);
-    const int nlm = margins_nl_mask(c);
-    int rc;
-    if ((rc = ensure(c, c->b_mo, (V + n + 1) * 4))) return rc;
-    if ((rc = ensure(c, c->b_md, (E + 1) * 4))) return rc;
-    if ((rc = ensure(c, c->b_mw, (E + 1) * 8))) return rc;
-    if ((rc = ensure(c, c->b_mdt, (V + 1) * limbs * 8))) return rc;
-    if ((rc = ensure(c, c->b_mrec, (N + 1) * sizeof(phx_orf_margin)))) return rc;
-    if ((rc = ensure(c, c->b_mstat, (n + 1) * 4))) return rc;
-    for (hipEvent_t &e : c->mev) if (!e) HIPCHK(c, hipEventCreate(&e));
-    c->mstat.assign(n, 0);
-    DBatch b;
-    fill_batch(c, &b);
-    DMarg g;
-    margins_args(c, &g);
-    hipStream_t s = c->stream;
-    HIPCHK(c, hipEventRecord(c->mev[0], s));
-    HIPCHK(c, hipMemsetAsync(c->b_mo.p, 0, (V + n + 1) * 4, s));
-    HIPCHK(c, hipMemsetAsync(c->b_mstat.p, 0, (n + 1) * 4, s));
-    phxk_margins_transpose(&b, &g, s);
-    HIPCHK(c, hipEventRecord(c->mev[1], s));
-    phxk_sssp_rev(&b, &g, nlm, s);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->mev[2], s));
-    if (n) HIPCHK(c, hipMemcpyAsync(c->mstat.data(), c->b_mstat.p, n * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    for (int k = 0; k < 2; k++) { float ms = 0; if (hipEventElapsedTime(&ms, c->mev[k], c->mev[k + 1]) == hipSuccess) c->rev_ms[k] = ms; }
-    c->rev_done = true;
-    return PHX_OK;
-}
-
-// The device's records of every ORF of the batch (device order) into c->h_mrec, once per run, on top of ensure_rev.
-static int ensure_margins(phx_ctx *c) {
-    if (c->margins_done) return PHX_OK;
-    { const int rr = ensure_rev(c); if (rr) return rr; }
-    const size_t N = (size_t)c->tot_orf, G = (size_t)c->tot_grp;
-    const int nlm = margins_nl_mask(c);
-    if (c->h_mrec_cap < N + 1) {
-        if (c->h_mrec) HIPCHK(c, hipHostFree(c->h_mrec));
-        c->h_mrec = nullptr; c->h_mrec_cap = 0;
-        const size_t cap = N + N / 4 + 1024;
-        HIPCHK(c, hipHostMalloc((void **)&c->h_mrec, cap * sizeof(phx_orf_margin), hipHostMallocDefault));
-        c->h_mrec_cap = cap;
-    }
-    c->mgrp.resize(G);
-    DBatch b;
-    fill_batch(c, &b);
-    DMarg g;
-    margins_args(c, &g);
-    hipStream_t s = c->stream;
-    HIPCHK(c, hipEventRecord(c->mev[2], s));
-    phxk_margins(&b, &g, nlm, s);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->mev[3], s));
-    if (N) HIPCHK(c, hipMemcpyAsync(c->h_mrec, c->b_mrec.p, N * sizeof(phx_orf_margin), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipEventRecord(c->mev[4], s));
-    if (G) HIPCHK(c, hipMemcpyAsync(c->mgrp.data(), c->b_grp.p, G * sizeof(DGrp), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    c->margins_ms[0] = c->rev_ms[0]; c->margins_ms[1] = c->rev_ms[1];
-    for (int k = 2; k < 4; k++) { float ms = 0; if (hipEventElapsedTime(&ms, c->mev[k], c->mev[k + 1]) == hipSuccess) c->margins_ms[k] = ms; }
-    c->margins_done = true;
-    return PHX_OK;
-}
-
-// status of contig i's margins (include/phx.h)
-static int32_t margins_status(const phx_ctx *c, int i) {
-    const int32_t r = c->res[(size_t)i].status;
-    if (r < 0) return r;
-    const DMeta &m = c->meta[(size_t)i];
-    if (m.sssp_mode == 4 && m.n_node > 2) return PHX_S_OVERFLOW;
-    if (c->mstat[(size_t)i]) return PHX_S_NEGCYCLE;
-    return r;
-}
-
-int phx_margins_flat(phx_ctx *c, phx_orf_margin *rec, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
-    if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
-    if (c->in_flight) { const int rs = phx_wait(c); if (rs) return rs; }
-    if (!c->ran) return PHX_E_STATE;
-    HIPCHK(c, hipSetDevice(c->device));
-    { const int rx = ensure_exact(c); if (rx) return rx; } // `called` is against the genes phx_download* deliver
-    { const int rm = ensure_margins(c); if (rm) return rm; }
-    try {
-    int64_t total = 0;
-    for (int i = 0; i < c->n; i++) { offsets[i] = total; status[i] = margins_status(c, i); if (status[i] >= 0) total += c->meta[(size_t)i].n_orf; }
-    offsets[c->n] = total;
-    if (total_out) *total_out = total;
-    if (!rec) return PHX_OK; // size query
-    if (cap < total) return PHX_E_ARG;
-    // the delivered genes (as phx_download_flat: the host re-solve's where there was one)
-    int64_t hi = 0;
-    for (int i = 0; i < c->n; i++) { const DRes &m = c->res[(size_t)i]; hi = std::max<int64_t>(hi, m.gene_off + m.n_genes); }
-    { const int rg = ensure_gene_stage(c, (size_t)hi); if (rg) return rg; }
-    if (hi) {
-        HIPCHK(c, hipMemcpyAsync(c->h_genes, (const DGene *)c->b_genes.p + (gene_pack(c) ? gene_half(c) : 0), sizeof(DGene) * (size_t)hi, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    std::vector<uint64_t> keys;
-    auto key = [](int32_t left, int32_t right, int32_t strand) { return ((uint64_t)(uint32_t)left << 33) | ((uint64_t)(uint32_t)right << 1) | (strand < 0 ? 1u : 0u); };
-    std::vector<int> order, ref_rank, ref_first;
-    std::vector<DGrp> grp;
-    for (int i = 0; i < c->n; i++) {
-        if (status[i] < 0) continue;
-        const DMeta &m = c->meta[(size_t)i];
-        const DRes &r = c->res[(size_t)i];
-        const DGene *src = c->h_genes + (size_t)r.gene_off;
-        int64_t ng = r.n_genes;
-        const auto ex = c->exact_genes.find(i);
-        if (ex != c->exact_genes.end()) { src = ex->second.data(); ng = (int64_t)ex->second.size(); }
-        keys.clear();
-        for (int64_t k = 0; k < ng; k++) if (src[k].frame >= -3 && src[k].frame <= 3) keys.push_back(key(src[k].left, src[k].right, src[k].strand)); // (tRNA path edges, frame +-4, are no ORFs)
-        std::sort(keys.begin(), keys.end());
-        // device order -> the reference's iter_orfs order (phx_tap_orfs): groups by ascending DGrp.evkey, the ORFs of a group contiguous in both
-        grp.assign(c->mgrp.begin() + m.grp_off, c->mgrp.begin() + m.grp_off + m.n_grp);
-        reference_order(grp, order, ref_rank, ref_first);
-        phx_orf_margin *dst = rec + offsets[i];
-        const phx_orf_margin *from = c->h_mrec + m.orf_off;
-        for (size_t rr = 0; rr < order.size(); rr++) {
-            const DGrp &G = grp[(size_t)order[rr]];
-            if (G.n > 0) memcpy(dst, from + G.orf_begin, sizeof(phx_orf_margin) * (size_t)G.n);
-            dst += G.n;
-        }
-        for (int64_t k = offsets[i]; k < offsets[i + 1]; k++) rec[k].called = std::binary_search(keys.begin(), keys.end(), key(rec[k].left, rec[k].right, rec[k].strand)) ? 1 : 0;
-    }
-    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_margins_flat"; return PHX_E_NOMEM; }
-    return PHX_OK;
-}
-
-int phx_tap_dist_target(phx_ctx *c, int32_t contig, uint64_t *dist_limbs, int64_t cap_words) {
-    TAP_PRE(c, contig);
-    if (m.status < 0 || m.n_node <= 2 || m.sssp_mode == 4) return PHX_OK;
-    const size_t words = (size_t)m.n_node * (size_t)m.sssp_nl;
-    if (!dist_limbs || cap_words < (int64_t)words) return PHX_E_ARG;
-    { const int rm = ensure_rev(c); if (rm) return rm; }
-    HIPCHK(c, hipMemcpy(dist_limbs, (uint64_t *)c->b_mdt.p + (size_t)m.node_off * (size_t)c->n_limbs, words * 8, hipMemcpyDeviceToHost));
-    return PHX_OK;
-}
-
-int phx_margins_ms(phx_ctx *c, float *ms) {
-    if (!c || !ms) return PHX_E_ARG;
-    for (int k = 0; k < 4; k++) ms[k] = c->margins_ms[k];
-    return PHX_OK;
-}
-
-// ---- gene drop margins (phx_drop.inc) ----
-// the contigs the drop kernels cover (dp_contig) and their sparse-table size (k_dp_cand)
-static bool drop_contig(const phx_ctx *c, size_t i) {
-    const DMeta &m = c->meta[i];
-    return m.status >= 0 && m.n_node > 2 && m.sssp_mode != 4 && !c->mstat[i] && m.n_path >= 3;
-}
-static int64_t drop_cells(int n_path) { int lv = 1; while ((2 << (lv - 1)) <= n_path) lv++; return (int64_t)n_path * lv; }
-
-static void drop_args(phx_ctx *c, DDrop *q) {
-    const size_t n = (size_t)c->n;
-    q->pidx = (int32_t *)c->b_dpi.p; q->js = (int32_t *)c->b_djs.p; q->jt = (int32_t *)c->b_djt.p; q->first = (int32_t *)c->b_dfi.p; q->last = (int32_t *)c->b_dla.p;
-    q->slot = (uint64_t *)c->b_dslot.p; q->gtab = (uint64_t *)c->b_dgtab.p;
-    q->toff = (const int64_t *)c->b_doff.p; q->roff = (const int64_t *)c->b_doff.p + n;
-    q->sx = (uint64_t *)c->b_dsx.p; q->cx = (uint64_t *)c->b_dcx.p; q->da = (uint64_t *)c->b_dda.p; q->db = (uint64_t *)c->b_ddb.p;
-    q->rec = (phx_gene_drop *)c->b_drec.p; q->stats = (unsigned long long *)c->b_dstats.p;
-    const char *ly = getenv("PHX_DROP_LAYERED");
-    q->layered = ly && *ly && strcmp(ly, "0") != 0 ? 1 : 0;
-    q->ps = c->drop_trees ? (int32_t *)c->b_dps.p : nullptr; q->ts = c->drop_trees ? (int32_t *)c->b_dts.p : nullptr;
-}
-
-// The records of every pair of every device path into c->h_drec (at c->droff), once per run, on top of ensure_rev.  trees: the one-hop
-// trees too (DDrop.ps / ts, for the replacements); drops computed without them get k_dp_tree once more, which rewrites the same labels.
-static int ensure_drops(phx_ctx *c, bool trees = false) {
-    if (c->drops_done && (!trees || c->drop_trees)) return PHX_OK;
-    if (c->drops_done) {
-        const size_t nv = ((size_t)c->tot_node + (size_t)c->n + 1) * 4;
-        int rc;
-        if ((rc = ensure(c, c->b_dps, nv)) || (rc = ensure(c, c->b_dts, nv)) || (rc = ensure(c, c->b_rcnt, 2 * RP_NCNT * 8))) return rc;
-        c->drop_trees = true;
-        DBatch b;
-        fill_batch(c, &b);
-        DMarg g;
-        margins_args(c, &g);
-        DDrop q;
-        drop_args(c, &q);
-        q.stats = (unsigned long long *)c->b_rcnt.p + RP_NCNT; // (the drops' own counters stay as they were)
-        phxk_drop_trees(&b, &g, &q, margins_nl_mask(c), c->stream);
-        HIPCHK(c, hipGetLastError());
-        return PHX_OK;
-    }
-    if (trees) c->drop_trees = true;
-    { const int rr = ensure_rev(c); if (rr) return rr; }
-    const size_t n = (size_t)c->n, V = (size_t)c->tot_node;
-    const size_t limbs = (size_t)std::max(c->n_limbs, 2);
-    const int nlm = margins_nl_mask(c);
-    std::vector<int64_t> off(2 * n + 2, 0); // toff[n], roff[n + 1]
-    c->droff.assign(n + 1, 0);
-    int64_t tcells = 0, R = 0;
-    for (size_t i = 0; i < n; i++) {
-        off[n + i] = R; c->droff[i] = R;
-        if (!drop_contig(c, i)) continue;
-        const int np = c->meta[i].n_path;
-        const int64_t cells = drop_cells(np);
-        if (cells > DP_TAB_LDS) { off[i] = tcells; tcells += cells; }
-        R += (np - 1) / 2;
-    }
-    off[2 * n] = R; c->droff[n] = R;
-    int rc;
-    const size_t nv = (V + n + 1) * 4;
-    if ((rc = ensure(c, c->b_dpi, nv)) || (rc = ensure(c, c->b_djs, nv)) || (rc = ensure(c, c->b_djt, nv)) || (rc = ensure(c, c->b_dfi, nv)) || (rc = ensure(c, c->b_dla, nv))) return rc;
-    if ((rc = ensure(c, c->b_dslot, (V + 1) * 8))) return rc;
-    if ((rc = ensure(c, c->b_dgtab, ((size_t)tcells + 1) * 8))) return rc;
-    if ((rc = ensure(c, c->b_doff, (2 * n + 2) * 8))) return rc;
-    if ((rc = ensure(c, c->b_dsx, ((size_t)R + 1) * limbs * 8)) || (rc = ensure(c, c->b_dcx, ((size_t)R + 1) * limbs * 8))) return rc;
-    if ((rc = ensure(c, c->b_dda, (V + 1) * limbs * 8)) || (rc = ensure(c, c->b_ddb, (V + 1) * limbs * 8))) return rc;
-    if ((rc = ensure(c, c->b_drec, ((size_t)R + 1) * sizeof(phx_gene_drop)))) return rc;
-    if ((rc = ensure(c, c->b_dstats, 4 * 8))) return rc;
-    if (c->drop_trees && ((rc = ensure(c, c->b_dps, nv)) || (rc = ensure(c, c->b_dts, nv)))) return rc;
-    if (c->h_drec_cap < (size_t)R + 1) {
-        if (c->h_drec) HIPCHK(c, hipHostFree(c->h_drec));
-        c->h_drec = nullptr; c->h_drec_cap = 0;
-        const size_t cap = (size_t)R + (size_t)R / 4 + 1024;
-        HIPCHK(c, hipHostMalloc((void **)&c->h_drec, cap * sizeof(phx_gene_drop), hipHostMallocDefault));
-        c->h_drec_cap = cap;
-    }
-    for (hipEvent_t &e : c->dev_) if (!e) HIPCHK(c, hipEventCreate(&e));
-    DBatch b;
-    fill_batch(c, &b);
-    DMarg g;
-    margins_args(c, &g);
-    DDrop q;
-    drop_args(c, &q);
-    hipStream_t s = c->stream;
-    unsigned long long st[4] = {0, 0, 0, 0};
-    HIPCHK(c, hipEventRecord(c->dev_[0], s));
-    HIPCHK(c, hipMemcpyAsync(c->b_doff.p, off.data(), (2 * n + 2) * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemsetAsync(c->b_dstats.p, 0, 4 * 8, s));
-    phxk_drop_trees(&b, &g, &q, nlm, s);
-    HIPCHK(c, hipEventRecord(c->dev_[1], s));
-    phxk_drop_cand(&b, &g, &q, nlm, s);
-    HIPCHK(c, hipEventRecord(c->dev_[2], s));
-    phxk_drop_fix(&b, &g, &q, nlm, s);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->dev_[3], s));
-    if (R) HIPCHK(c, hipMemcpyAsync(c->h_drec, c->b_drec.p, (size_t)R * sizeof(phx_gene_drop), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipEventRecord(c->dev_[4], s));
-    HIPCHK(c, hipMemcpyAsync(st, c->b_dstats.p, sizeof st, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    for (int k = 0; k < 4; k++) { float ms = 0; if (hipEventElapsedTime(&ms, c->dev_[k], c->dev_[k + 1]) == hipSuccess) c->drop_ms[k] = ms; c->drop_stats[k] = (int64_t)st[k]; }
-    c->drops_done = true;
-    return PHX_OK;
-}
-
-int phx_drop_margins_flat(phx_ctx *c, phx_gene_drop *rec, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
-    if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
-    if (c->in_flight) { const int rs = phx_wait(c); if (rs) return rs; }
-    if (!c->ran) return PHX_E_STATE;
-    HIPCHK(c, hipSetDevice(c->device));
-    { const int rx = ensure_exact(c); if (rx) return rx; } // `called` is against the genes phx_download* deliver
-    { const int rd = ensure_drops(c); if (rd) return rd; }
-    try {
-    // the gene pairs of every contig with records (status 0): the pairs of the device path that are CDS genes
-    auto genes_of = [&](int i) -> int64_t {
-        int64_t k = 0;
-        for (int64_t r = c->droff[(size_t)i]; r < c->droff[(size_t)i + 1]; r++) k += c->h_drec[r].called >= 0;
-        return k;
-    };
-    int64_t total = 0;
-    for (int i = 0; i < c->n; i++) {
-        offsets[i] = total;
-        status[i] = margins_status(c, i);
-        if (status[i] == 0 && drop_contig(c, (size_t)i)) total += genes_of(i);
-    }
-    offsets[c->n] = total;
-    if (total_out) *total_out = total;
-    if (!rec) return PHX_OK; // size query
-    if (cap < total) return PHX_E_ARG;
-    // the delivered genes (as phx_download_flat: the host re-solve's where there was one)
-    int64_t hi = 0;
-    for (int i = 0; i < c->n; i++) { const DRes &m = c->res[(size_t)i]; hi = std::max<int64_t>(hi, m.gene_off + m.n_genes); }
-    { const int rg = ensure_gene_stage(c, (size_t)hi); if (rg) return rg; }
-    if (hi) {
-        HIPCHK(c, hipMemcpyAsync(c->h_genes, (const DGene *)c->b_genes.p + (gene_pack(c) ? gene_half(c) : 0), sizeof(DGene) * (size_t)hi, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    std::vector<uint64_t> keys;
-    auto key = [](int32_t left, int32_t right, int32_t strand) { return ((uint64_t)(uint32_t)left << 33) | ((uint64_t)(uint32_t)right << 1) | (strand < 0 ? 1u : 0u); };
-    for (int i = 0; i < c->n; i++) {
-        if (offsets[i + 1] == offsets[i]) continue;
-        const DRes &r = c->res[(size_t)i];
-        const DGene *src = c->h_genes + (size_t)r.gene_off;
-        int64_t ng = r.n_genes;
-        const auto ex = c->exact_genes.find(i);
-        if (ex != c->exact_genes.end()) { src = ex->second.data(); ng = (int64_t)ex->second.size(); }
-        keys.clear();
-        for (int64_t k = 0; k < ng; k++) if (src[k].frame >= -3 && src[k].frame <= 3) keys.push_back(key(src[k].left, src[k].right, src[k].strand));
-        std::sort(keys.begin(), keys.end());
-        phx_gene_drop *dst = rec + offsets[i];
-        for (int64_t k = c->droff[(size_t)i]; k < c->droff[(size_t)i + 1]; k++) {
-            const phx_gene_drop &x = c->h_drec[k];
-            if (x.called < 0) continue;
-            *dst = x;
-            dst->called = std::binary_search(keys.begin(), keys.end(), key(x.left, x.right, x.strand)) ? 1 : 0;
-            dst++;
-        }
-    }
-    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_drop_margins_flat"; return PHX_E_NOMEM; }
-    return PHX_OK;
-}
-
-int phx_drop_ms(phx_ctx *c, float *ms) {
-    if (!c || !ms) return PHX_E_ARG;
-    for (int k = 0; k < 4; k++) ms[k] = c->drop_ms[k];
-    return PHX_OK;
-}
-
-int phx_drop_stats(phx_ctx *c, int64_t *out) {
-    if (!c || !out) return PHX_E_ARG;
-    for (int k = 0; k < 4; k++) out[k] = c->drop_stats[k];
-    return PHX_OK;
-}
-
-// ---- drop replacements (phx_replace.inc) ----
-// Every device record's replacement into c->h_rrec / h_rgenes / h_rdet, once per run, on top of ensure_drops (with the one-hop trees).
-static int ensure_replacements(phx_ctx *c) {
-    if (c->repl_done) return PHX_OK;
-    { const int rd = ensure_drops(c, true); if (rd) return rd; }
-    const size_t n = (size_t)c->n, V = (size_t)c->tot_node;
-    const size_t R = (size_t)c->droff[n];
-    const int nlm = margins_nl_mask(c);
-    int rc;
-    if ((rc = ensure(c, c->b_rwin, (R + 1) * 8)) || (rc = ensure(c, c->b_rxs, (R + 1) * 4)) || (rc = ensure(c, c->b_rcoff, (R + 1) * 8)) ||
-        (rc = ensure(c, c->b_rcm, (R + 1) * 4)) || (rc = ensure(c, c->b_rrnd, (V + n + 1) * 4)) || (rc = ensure(c, c->b_rinfo, (R + 1) * 16)) ||
-        (rc = ensure(c, c->b_rdoff, (2 * R + 2) * 8)) || (rc = ensure(c, c->b_rrec, (R + 1) * sizeof(phx_gene_repl))) || (rc = ensure(c, c->b_rcnt, 2 * RP_NCNT * 8)))
-        return rc;
-    if (!c->b_rchain.p) { // room for this many delta-chain nodes (env PHX_REPL_CHAIN_CAP, the tests: fewer, so that the regrowth below runs)
-        const char *cc = getenv("PHX_REPL_CHAIN_CAP");
-        c->rchain_cap = cc && *cc ? std::max<int64_t>(1, atoll(cc)) : (int64_t)V + 1;
-        if ((rc = ensure(c, c->b_rchain, ((size_t)c->rchain_cap + 1) * 4))) return rc;
-    }
-    for (hipEvent_t &e : c->rev_ev) if (!e) HIPCHK(c, hipEventCreate(&e));
-    try { c->h_rpath.assign(n, std::vector<int32_t>()); } catch (const std::bad_alloc &) { c->err = "out of memory in phx_replacements_flat"; return PHX_E_NOMEM; }
-    DBatch b;
-    fill_batch(c, &b);
-    DMarg g;
-    margins_args(c, &g);
-    DDrop q;
-    drop_args(c, &q);
-    DRepl r;
-    auto args = [&]() {
-        r.win = (uint64_t *)c->b_rwin.p; r.xs = (int32_t *)c->b_rxs.p; r.coff = (int64_t *)c->b_rcoff.p; r.cm = (int32_t *)c->b_rcm.p;
-        r.chain = (int32_t *)c->b_rchain.p; r.ccap = c->rchain_cap; // (b_rchain was ensured for rchain_cap + 1 entries)
-        r.rnd = (int32_t *)c->b_rrnd.p; r.info = (int32_t *)c->b_rinfo.p;
-        r.doff = (const int64_t *)c->b_rdoff.p; r.goff = (const int64_t *)c->b_rdoff.p + R + 1;
-        r.det = (int32_t *)c->b_rdet.p; r.genes = (phx_gene *)c->b_rgenes.p; r.rec = (phx_gene_repl *)c->b_rrec.p;
-        r.cnt = (unsigned long long *)c->b_rcnt.p;
-    };
-    args();
-    hipStream_t s = c->stream;
-    // The event pairs bracket device work only: the host's read-backs and offsets between the passes fall outside every pair.
-    unsigned long long cnt[RP_NCNT] = {0};
-    hipEvent_t *ev = c->rev_ev;
-    bool regrown = false;
-    HIPCHK(c, hipEventRecord(ev[0], s));
-    HIPCHK(c, hipMemsetAsync(c->b_rcnt.p, 0, RP_NCNT * 8, s));
-    HIPCHK(c, hipMemsetAsync(c->b_rwin.p, 0xff, (R + 1) * 8, s));
-    phxk_repl_pick(&b, &g, &q, &r, nlm, s);
-    phxk_repl_cross(&b, &g, &q, &r, nlm, s);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(ev[1], s));
-    HIPCHK(c, hipMemcpyAsync(cnt, c->b_rcnt.p, sizeof cnt, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    if ((int64_t)cnt[0] > r.ccap) { // the delta chains did not fit: room for all of them, and the cross winners once more
-        c->rchain_cap = (int64_t)cnt[0];
-        if ((rc = ensure(c, c->b_rchain, ((size_t)c->rchain_cap + 1) * 4))) return rc;
-        args();
-        regrown = true;
-        HIPCHK(c, hipEventRecord(ev[2], s));
-        HIPCHK(c, hipMemsetAsync(c->b_rcnt.p, 0, RP_NCNT * 8, s));
-        phxk_repl_cross(&b, &g, &q, &r, nlm, s);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipEventRecord(ev[3], s));
-        HIPCHK(c, hipMemcpyAsync(cnt, c->b_rcnt.p, sizeof cnt, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        if ((int64_t)cnt[0] > r.ccap) { c->err = "drop replacements: the delta chains outgrew their buffer twice"; return PHX_E_STATE; }
-    }
-    // counting pass, offsets, filling pass
-    HIPCHK(c, hipEventRecord(ev[4], s));
-    phxk_repl_walk(&b, &g, &q, &r, 0, s);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(ev[5], s));
-    c->h_rinfo.resize(4 * R + 4);
-    if (R) HIPCHK(c, hipMemcpyAsync(c->h_rinfo.data(), c->b_rinfo.p, R * 16, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(cnt, c->b_rcnt.p, sizeof cnt, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    if (cnt[1]) { c->err = "drop replacements: a slot with a bypass has no witness"; return PHX_E_STATE; }
-    c->repl_stats[0] = (int64_t)cnt[2]; c->repl_stats[1] = (int64_t)cnt[0]; c->repl_stats[2] = (int64_t)cnt[3]; c->repl_stats[3] = (int64_t)cnt[4];
-    c->repl_stats[4] = regrown ? 1 : 0;
-    try {
-        std::vector<int64_t> off(2 * R + 2);
-        int64_t nd = 0, ng = 0;
-        for (size_t k = 0; k < R; k++) { off[k] = nd; off[R + 1 + k] = ng; nd += c->h_rinfo[4 * k + 2]; ng += c->h_rinfo[4 * k + 3]; }
-        off[R] = nd; off[2 * R + 1] = ng;
-        c->h_rdoff.assign(off.begin(), off.begin() + (R + 1));
-        if ((rc = ensure(c, c->b_rdet, ((size_t)nd + 1) * 4)) || (rc = ensure(c, c->b_rgenes, ((size_t)ng + 1) * sizeof(phx_gene)))) return rc;
-        args();
-        HIPCHK(c, hipMemcpyAsync(c->b_rdoff.p, off.data(), (2 * R + 2) * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipEventRecord(ev[6], s));
-        phxk_repl_walk(&b, &g, &q, &r, 1, s);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipEventRecord(ev[7], s));
-        c->h_rrec.resize(R + 1); c->h_rdet.resize((size_t)nd + 1); c->h_rgenes.resize((size_t)ng + 1);
-        if (R) HIPCHK(c, hipMemcpyAsync(c->h_rrec.data(), c->b_rrec.p, R * sizeof(phx_gene_repl), hipMemcpyDeviceToHost, s));
-        if (nd) HIPCHK(c, hipMemcpyAsync(c->h_rdet.data(), c->b_rdet.p, (size_t)nd * 4, hipMemcpyDeviceToHost, s));
-        if (ng) HIPCHK(c, hipMemcpyAsync(c->h_rgenes.data(), c->b_rgenes.p, (size_t)ng * sizeof(phx_gene), hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipEventRecord(ev[8], s));
-        HIPCHK(c, hipStreamSynchronize(s));
-    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_replacements_flat"; return PHX_E_NOMEM; }
-    auto span = [&](int k0, int k1) { float ms = 0; return hipEventElapsedTime(&ms, ev[k0], ev[k1]) == hipSuccess ? ms : 0.0f; };
-    c->repl_ms[0] = span(0, 1) + (regrown ? span(2, 3) : 0.0f);
-    c->repl_ms[1] = span(4, 5) + span(6, 7);
-    c->repl_ms[2] = span(7, 8);
-    c->repl_done = true;
-    return PHX_OK;
-}
-
-int phx_replacements_flat(phx_ctx *c, phx_gene_repl *rec, int64_t cap, phx_gene *genes, int64_t gene_cap, int64_t *offsets, int32_t *status,
-                          int64_t *total_out, int64_t *gene_total_out) {
-    if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
-    if (c->in_flight) { const int rs = phx_wait(c); if (rs) return rs; }
-    if (!c->ran) return PHX_E_STATE;
-    HIPCHK(c, hipSetDevice(c->device));
-    { const int rr = ensure_replacements(c); if (rr) return rr; }
-    // statuses, offsets and `called` exactly as the drop records have them
-    int64_t total = 0;
-    { const int rd = phx_drop_margins_flat(c, nullptr, 0, offsets, status, &total); if (rd) return rd; }
-    try {
-    std::vector<phx_gene_drop> drec((size_t)total + 1);
-    { const int rd = phx_drop_margins_flat(c, drec.data(), total, offsets, status, &total); if (rd) return rd; }
-    int64_t gt = 0;
-    for (int i = 0; i < c->n; i++) {
-        if (offsets[i + 1] == offsets[i]) continue;
-        for (int64_t k = c->droff[(size_t)i]; k < c->droff[(size_t)i + 1]; k++) if (c->h_rrec[k].called >= 0) gt += c->h_rrec[k].n_removed + c->h_rrec[k].n_added;
-    }
-    if (total_out) *total_out = total;
-    if (gene_total_out) *gene_total_out = gt;
-    if (!rec || !genes) return PHX_OK; // size query
-    if (cap < total || gene_cap < gt) return PHX_E_ARG;
-    int64_t go = 0;
-    for (int i = 0; i < c->n; i++) {
-        if (offsets[i + 1] == offsets[i]) continue;
-        phx_gene_repl *dst = rec + offsets[i];
-        const phx_gene_drop *dd = drec.data() + offsets[i];
-        for (int64_t k = c->droff[(size_t)i]; k < c->droff[(size_t)i + 1]; k++) {
-            const phx_gene_repl &x = c->h_rrec[k];
-            if (x.called < 0) continue;
-            *dst = x;
-            dst->called = dd->called;
-            dst->gene_off = go;
-            const int64_t ng = x.n_removed + x.n_added;
-            if (ng) memcpy(genes + go, c->h_rgenes.data() + x.gene_off, (size_t)ng * sizeof(phx_gene));
-            go += ng;
-            dst++; dd++;
-        }
-    }
-    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_replacements_flat"; return PHX_E_NOMEM; }
-    return PHX_OK;
-}
-
-int phx_tap_replacement(phx_ctx *c, int32_t contig, int32_t k, int32_t *path, int32_t cap, int32_t *n_path) {
-    if (!c || !n_path) return PHX_E_ARG;
-    *n_path = 0;
-    if (c->in_flight) { const int rs = phx_wait(c); if (rs) return rs; }
-    if (!c->ran) return PHX_E_STATE;
-    if (contig < 0 || contig >= c->n || k < 0) return PHX_E_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    { const int rr = ensure_replacements(c); if (rr) return rr; }
-    if (!drop_contig(c, (size_t)contig) || margins_status(c, contig) != 0) return PHX_E_ARG;
-    int64_t rk = -1;
-    for (int64_t q = c->droff[(size_t)contig], seen = 0; q < c->droff[(size_t)contig + 1]; q++)
-        if (c->h_rrec[q].called >= 0 && seen++ == k) { rk = q; break; }
-    if (rk < 0) return PHX_E_ARG;
-    if (!c->h_rrec[rk].bypass) return PHX_OK;
-    const DMeta &m = c->meta[(size_t)contig];
-    const int a = c->h_rinfo[4 * rk], b = c->h_rinfo[4 * rk + 1], nd = c->h_rinfo[4 * rk + 2];
-    const int len = (a + 1) + nd + (m.n_path - b);
-    *n_path = len;
-    if (!path) return PHX_OK;
-    if (cap < len) return PHX_E_ARG;
-    std::vector<int32_t> &P = c->h_rpath[(size_t)contig]; // (the contig's device path, fetched at its first tap of this run)
-    if (P.empty()) {
-        try { P.resize((size_t)m.n_path); } catch (const std::bad_alloc &) { c->err = "out of memory in phx_tap_replacement"; return PHX_E_NOMEM; }
-        HIPCHK(c, hipMemcpy(P.data(), (int32_t *)c->b_path.p + m.node_off, (size_t)m.n_path * 4, hipMemcpyDeviceToHost));
-    }
-    int32_t *o = path;
-    for (int t = 0; t <= a; t++) *o++ = P[(size_t)t];
-    for (int t = 0; t < nd; t++) *o++ = c->h_rdet[(size_t)c->h_rdoff[(size_t)rk] + t];
-    for (int t = b; t < m.n_path; t++) *o++ = P[(size_t)t];
-    return PHX_OK;
-}
-
-int phx_replacements_ms(phx_ctx *c, float *ms) {
-    if (!c || !ms) return PHX_E_ARG;
-    for (int k = 0; k < 3; k++) ms[k] = c->repl_ms[k];
-    return PHX_OK;
-}
-
-int phx_replacement_stats(phx_ctx *c, int64_t *out) {
-    if (!c || !out) return PHX_E_ARG;
-    for (int k = 0; k < 5; k++) out[k] = c->repl_stats[k];
-    return PHX_OK;
-}
-
-
-// ---- masked re-annotation (phx_resolve.inc) ----
-// status of contig i's re-annotation before any kernel: a run error, PHX_S_OVERFLOW without device distances, else the run's status
-static int32_t reann_status(const phx_ctx *c, int i) {
-    const DMeta &m = c->meta[(size_t)i];
-    if (m.sssp_mode == 4 && m.n_node > 2 && m.status >= 0) return PHX_S_OVERFLOW;
-    const int32_t r = c->res[(size_t)i].status;
-    return r < 0 ? r : m.status; // (the device's own status: exactness does not enter)
-}
-static bool reann_contig(const phx_ctx *c, int i) { const DMeta &m = c->meta[(size_t)i]; return reann_status(c, i) >= 0 && m.n_node > 2; }
-
-// The re-annotation's view of the batch: the run's graph, outputs of its own (nothing the run's results live in is written).
-static void reann_batch(phx_ctx *c, DBatch *b, DReann *q) {
-    fill_batch(c, b);
-    b->meta = (DMeta *)c->b_qmeta.p; b->tot = (DTotals *)c->b_qtot.p;
-    b->res = nullptr; b->sord = nullptr; b->lpart = nullptr;
-    b->dist = (uint64_t *)c->b_qdist.p; b->parent = (int32_t *)c->b_qparent.p; b->path = (int32_t *)c->b_qpath.p;
-    b->genes = (DGene *)c->b_qgenes.p; b->genes_c = nullptr; b->gpack = 0; b->gene_total = (uint32_t *)c->b_qgtot.p;
-    b->tie = (uint8_t *)c->b_qtie.p; b->tie_cap = cap_of(c->b_qtie, 1, 0);
-    q->forb = (const uint8_t *)c->b_qforb.p; q->mask = (uint32_t *)c->b_qmask.p; q->sel = (const int32_t *)c->b_qsel.p;
-    q->gplan = (uint8_t *)c->b_qplan.p; q->dist0 = (const uint64_t *)c->b_dist.p; q->rec = (DReannRec *)c->b_qrec.p;
-}
-
-// Solves the contigs of h_qsel again without the ORFs of `forb` (tap order); the records into h_qrec, the genes into h_qgenes.
-static int reann_compute(phx_ctx *c, const uint8_t *forb, const int64_t *orf_offsets) {
-    const size_t n = (size_t)c->n, V = (size_t)c->tot_node, E = (size_t)c->tot_edge, N = (size_t)c->tot_orf, G = (size_t)c->tot_grp;
-    const size_t limbs = (size_t)std::max(c->n_limbs, 2);
-    if (!c->qgrp_done) {
-        c->qgrp.resize(G);
-        if (G) HIPCHK(c, hipMemcpy(c->qgrp.data(), c->b_grp.p, G * sizeof(DGrp), hipMemcpyDeviceToHost));
-        c->qgrp_done = true;
-    }
-    // the mask in device ORF order: the inverse of the permutation phx_margins_flat applies to its records
-    std::vector<uint8_t> &dforb = c->h_qdforb;
-    dforb.assign(N + 1, 0);
-    std::vector<int> order, ref_rank, ref_first;
-    std::vector<DGrp> grp;
-    int nlm = 0;
-    bool any = false;
-    for (size_t i = 0; i < n; i++) {
-        if (!c->h_qsel[i]) continue;
-        any = true;
-        const DMeta &m = c->meta[i];
-        nlm |= m.sssp_nl == 2 ? 1 : m.sssp_nl == 4 ? 2 : m.sssp_nl == 8 ? 4 : 8;
-        grp.assign(c->qgrp.begin() + m.grp_off, c->qgrp.begin() + m.grp_off + m.n_grp);
-        reference_order(grp, order, ref_rank, ref_first);
-        const uint8_t *from = forb + orf_offsets[i];
-        for (size_t rr = 0; rr < order.size(); rr++) {
-            const DGrp &g = grp[(size_t)order[rr]];
-            if (g.n > 0 && g.orf_begin >= 0 && (int64_t)g.orf_begin + g.n <= m.n_orf) memcpy(dforb.data() + m.orf_off + g.orf_begin, from, (size_t)g.n);
-            from += g.n;
-        }
-    }
-    c->h_qrec.assign(n, DReannRec{});
-    c->h_qgenes.clear();
-    if (!any) return PHX_OK;
-    int rc;
-    if ((rc = ensure(c, c->b_qmeta, (n + 1) * sizeof(DMeta))) || (rc = ensure(c, c->b_qtot, sizeof(DTotals))) || (rc = ensure(c, c->b_qdist, (V + 1) * limbs * 8)) ||
-        (rc = ensure(c, c->b_qparent, (V + 1) * 4)) || (rc = ensure(c, c->b_qpath, (V + 1) * 4)) || (rc = ensure(c, c->b_qgenes, (V + n + 1) * sizeof(DGene))) || // (a path has at most V / 2 pairs, one replaced by k_rs_inorder takes new slots)
-        (rc = ensure(c, c->b_qgtot, 16)) || (rc = ensure(c, c->b_qmask, (E / 32 + 2) * 4)) || (rc = ensure(c, c->b_qforb, N + 1)) || (rc = ensure(c, c->b_qsel, (n + 1) * 4)) ||
-        (rc = ensure(c, c->b_qplan, V / 32 + n + 2)) || (rc = ensure(c, c->b_qrec, (n + 1) * sizeof(DReannRec))))
-        return rc;
-    if (!c->b_qtie.p && (rc = ensure(c, c->b_qtie, (size_t)std::max<int64_t>(c->tie_seen, 1 << 20)))) return rc;
-    for (hipEvent_t &e : c->qev) if (!e) HIPCHK(c, hipEventCreate(&e));
-    hipStream_t s = c->stream;
-    HIPCHK(c, hipMemcpyAsync(c->b_qforb.p, dforb.data(), N + 1, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->b_qsel.p, c->h_qsel.data(), n * 4, hipMemcpyHostToDevice, s));
-    DTotals &tot = c->h_qtot;
-    uint32_t &gtot = c->h_qgtot;
-    gtot = 0;
-    for (int attempt = 0;; attempt++) {
-        DBatch b;
-        DReann q;
-        reann_batch(c, &b, &q);
-        HIPCHK(c, hipEventRecord(c->qev[0], s));
-        HIPCHK(c, hipMemcpyAsync(c->b_qmeta.p, c->b_meta.p, n * sizeof(DMeta), hipMemcpyDeviceToDevice, s)); // the layout and the run's verdicts; the kernels write this copy
-        HIPCHK(c, hipMemsetAsync(c->b_qtot.p, 0, sizeof(DTotals), s));
-        HIPCHK(c, hipMemsetAsync(c->b_qgtot.p, 0, 16, s));
-        HIPCHK(c, hipMemsetAsync(c->b_qrec.p, 0, (n + 1) * sizeof(DReannRec), s));
-        HIPCHK(c, hipMemsetAsync(c->b_qmask.p, 0, (E / 32 + 2) * 4, s));
-        phxk_reann_mask(&b, &q, s);
-        HIPCHK(c, hipEventRecord(c->qev[1], s));
-        phxk_reann_solve(&b, &q, nlm, s);
-        HIPCHK(c, hipEventRecord(c->qev[2], s));
-        phxk_reann_finish(&b, &q, nlm, s);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(c->h_qrec.data(), c->b_qrec.p, n * sizeof(DReannRec), hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipEventRecord(c->qev[3], s));
-        HIPCHK(c, hipMemcpyAsync(&tot, c->b_qtot.p, sizeof(DTotals), hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(&gtot, c->b_qgtot.p, 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        if (!(tot.overflow & 4)) break;
-        // k_rs_inorder's scratch was too small for the contigs with equal-length alternatives: grow it and solve again
-        if (attempt >= 2) { c->err = "re-annotation: the tie scratch did not settle"; return PHX_E_STATE; }
-        if ((rc = ensure(c, c->b_qtie, (size_t)tot.tie_need + (size_t)tot.tie_need / 4 + 4096))) return rc;
-    }
-    if ((size_t)gtot > V + n) { c->err = "re-annotation: gene records beyond the buffer"; return PHX_E_STATE; }
-    c->h_qgenes.resize(gtot);
-    HIPCHK(c, hipEventRecord(c->qev[4], s));
-    if (gtot) HIPCHK(c, hipMemcpyAsync(c->h_qgenes.data(), c->b_qgenes.p, (size_t)gtot * sizeof(DGene), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipEventRecord(c->qev[5], s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    float ms = 0, ms2 = 0;
-    if (hipEventElapsedTime(&ms, c->qev[0], c->qev[1]) == hipSuccess) c->reann_ms[0] = ms;
-    if (hipEventElapsedTime(&ms, c->qev[1], c->qev[2]) == hipSuccess) c->reann_ms[1] = ms;
-    if (hipEventElapsedTime(&ms, c->qev[2], c->qev[3]) == hipSuccess && hipEventElapsedTime(&ms2, c->qev[4], c->qev[5]) == hipSuccess) c->reann_ms[2] = ms + ms2;
-    for (size_t i = 0; i < n; i++) {
-        if (!c->h_qsel[i]) continue;
-        const DReannRec &r = c->h_qrec[i];
-        if (r.n_genes < 0 || r.gene_off < 0 || (uint64_t)r.gene_off + (uint64_t)r.n_genes > (uint64_t)gtot) { c->err = "re-annotation: a contig's gene records lie outside the buffer"; return PHX_E_STATE; }
-    }
-    return PHX_OK;
-}
-
-int phx_reannotate_flat(phx_ctx *c, const uint8_t *forbid, const int64_t *orf_offsets, uint32_t flags, phx_gene *genes, int64_t cap, int64_t *offsets, int32_t *status,
-                        double *delta, int64_t *total_out) {
-    if (!c || (c->n > 0 && (!offsets || !status || !delta || !orf_offsets))) return PHX_E_ARG;
-    if (c->in_flight) { const int rs = phx_wait(c); if (rs) return rs; }
-    if (!c->ran) return PHX_E_STATE;
-    HIPCHK(c, hipSetDevice(c->device));
-    { const int rf = fetch_meta(c); if (rf) return rf; }
-    try {
-    // the offsets must be the batch's cumulative ORF counts (what phx_margins_flat reports): nothing from the caller indexes device memory unchecked
-    int64_t acc = 0;
-    for (int i = 0; i < c->n; i++) {
-        if (orf_offsets[i] != acc) return PHX_E_ARG;
-        if (reann_status(c, i) >= 0) acc += c->meta[(size_t)i].n_orf;
-    }
-    if (c->n > 0 && orf_offsets[c->n] != acc) return PHX_E_ARG;
-    if (acc > 0 && !forbid) return PHX_E_ARG;
-    const size_t N = (size_t)acc;
-    if (!(c->reann_done && c->h_qflags == flags && c->h_qforb.size() == N && (N == 0 || memcmp(c->h_qforb.data(), forbid, N) == 0))) {
-        c->reann_done = false;
-        c->h_qsel.assign((size_t)c->n, 0);
-        for (int i = 0; i < c->n; i++) {
-            if (!reann_contig(c, i)) continue;
-            bool want = (flags & 1u) != 0;
-            for (int64_t k = orf_offsets[i]; k < orf_offsets[i + 1] && !want; k++) want = forbid[k] != 0;
-            c->h_qsel[(size_t)i] = want ? 1 : 0;
-        }
-        { const int rq = reann_compute(c, forbid, orf_offsets); if (rq) { (void)hipStreamSynchronize(c->stream); return rq; } } // (nothing of a failed solve stays in flight)
-        c->h_qforb.assign(forbid, forbid + N);
-        c->h_qflags = flags;
-        c->reann_done = true;
-    }
-    // the run's own genes for the contigs that were not solved again (the device's lists: no host re-solve enters)
-    int64_t hi = 0, total = 0;
-    for (int i = 0; i < c->n; i++) {
-        const int32_t st = reann_status(c, i);
-        offsets[i] = total; status[i] = st; delta[i] = std::numeric_limits<double>::infinity();
-        if (st < 0) continue;
-        if (c->h_qsel[(size_t)i]) {
-            const DReannRec &r = c->h_qrec[(size_t)i];
-            status[i] = r.status; delta[i] = r.delta;
-            if (r.status >= 0) total += r.n_genes;
-        } else {
-            if (st != PHX_S_NOPATH) delta[i] = 0.0;
-            const DRes &r = c->res[(size_t)i];
-            if (r.n_genes > 0) { total += r.n_genes; hi = std::max<int64_t>(hi, r.gene_off + r.n_genes); }
-        }
-    }
-    offsets[c->n] = total;
-    if (total_out) *total_out = total;
-    if (!genes) return PHX_OK; // size query
-    if (cap < total) return PHX_E_ARG;
-    if (hi) {
-        { const int rg = ensure_gene_stage(c, (size_t)hi); if (rg) return rg; }
-        HIPCHK(c, hipMemcpyAsync(c->h_genes, (const DGene *)c->b_genes.p + (gene_pack(c) ? gene_half(c) : 0), sizeof(DGene) * (size_t)hi, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    for (int i = 0; i < c->n; i++) {
-        const int64_t k = offsets[i + 1] - offsets[i];
-        if (k <= 0) continue;
-        const DGene *src = c->h_qsel[(size_t)i] ? c->h_qgenes.data() + c->h_qrec[(size_t)i].gene_off : c->h_genes + (size_t)c->res[(size_t)i].gene_off;
-        memcpy(genes + offsets[i], src, sizeof(phx_gene) * (size_t)k);
-    }
-    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_reannotate_flat"; return PHX_E_NOMEM; }
-    return PHX_OK;
-}
-
-int phx_orf_offsets(phx_ctx *c, int64_t *orf_offsets) {
-    if (!c || !orf_offsets) return PHX_E_ARG;
-    if (c->in_flight) { const int rs = phx_wait(c); if (rs) return rs; }
-    if (!c->ran) return PHX_E_STATE;
-    HIPCHK(c, hipSetDevice(c->device));
-    { const int rf = fetch_meta(c); if (rf) return rf; }
-    int64_t acc = 0;
-    for (int i = 0; i < c->n; i++) { orf_offsets[i] = acc; if (reann_status(c, i) >= 0) acc += c->meta[(size_t)i].n_orf; }
-    orf_offsets[c->n] = acc;
-    return PHX_OK;
-}
-
-int phx_tap_repath(phx_ctx *c, int32_t contig, int32_t *path, int32_t cap, int32_t *n_path, uint64_t *dist_limbs, int32_t cap_limbs) {
-    if (c && c->ran && !c->in_flight && !c->reann_done) return PHX_E_STATE; // no re-annotation of this run
-    TAP_PRE(c, contig);
-    if (!c->reann_done) return PHX_E_STATE;
-    if (!c->h_qsel[(size_t)contig]) { // the run's result stands
-        if (reann_status(c, contig) < 0) { if (n_path) *n_path = 0; return PHX_OK; }
-        return phx_tap_path(c, contig, path, cap, n_path, dist_limbs, cap_limbs);
-    }
-    const DReannRec &r = c->h_qrec[(size_t)contig];
-    if (n_path) *n_path = 0;
-    if (r.status < 0 || r.n_path <= 0) return PHX_OK;
-    if (n_path) *n_path = r.n_path;
-    if (path) {
-        if (cap < r.n_path) return PHX_E_ARG;
-        HIPCHK(c, hipMemcpy(path, (int32_t *)c->b_qpath.p + m.node_off, (size_t)r.n_path * 4, hipMemcpyDeviceToHost));
-    }
-    if (dist_limbs) {
-        if (cap_limbs < m.sssp_nl) return PHX_E_ARG;
-        const size_t tgt = (size_t)m.node_off * (size_t)c->n_limbs + ((size_t)m.n_node - 1) * (size_t)m.sssp_nl;
-        HIPCHK(c, hipMemcpy(dist_limbs, (uint64_t *)c->b_qdist.p + tgt, (size_t)m.sssp_nl * 8, hipMemcpyDeviceToHost));
-    }
-    return PHX_OK;
-}
-
-int phx_reannotate_ms(phx_ctx *c, float *ms) {
-    if (!c || !ms) return PHX_E_ARG;
-    for (int k = 0; k < 3; k++) ms[k] = c->reann_ms[k];
-    return PHX_OK;
-}
+#include "phx_analyses.inc"
 
 // ---- the solver alone ----
 } // extern "C" (the replay is C++)
@@ -3001,8 +2241,7 @@ int phx_dump_text(phx_ctx *c, int32_t contig, char **text, int64_t *text_len) {
     if (!c || !text) return PHX_E_ARG;
     *text = nullptr;
     if (text_len) *text_len = 0;
-    if (c->in_flight) { const int rs = phx_wait(c); if (rs) return rs; }
-    if (!c->ran) return PHX_E_STATE;
+    { const int ra = after_run(c); if (ra) return ra; }
     if (contig < 0 || contig >= c->n) return PHX_E_ARG;
     ExactIn in;
     { const int rc = exact_fetch(c, contig, in); if (rc) return rc; }
@@ -3131,19 +2370,19 @@ int phx_get_stage_ms(phx_ctx *c, float *ms, int32_t *launches, int reset) {
 const char *phx_stage_name(int k) { return k >= 0 && k < PHX_N_STAGES ? kStageName[k] : ""; }
 int64_t phx_seg_runs(phx_ctx *c) {
     if (!c) return 0;
-    if (c->in_flight && phx_wait(c)) return 0;
+    if (wait_in_flight(c)) return 0;
     return c->seg_runs;
 }
 int64_t phx_seg_fallbacks(phx_ctx *c) {
     if (!c) return 0;
-    if (c->in_flight && phx_wait(c)) return 0;
+    if (wait_in_flight(c)) return 0;
     return c->seg_fallbacks;
 }
 // development: the records of the segments of contig `i` in the run last made — 8 ints each: windows | done flag, solver status, first node, end node, solver time
 // (10 ns ticks), phases, packs, step-backs; returns the number of records written (0: the run did not use segments)
 int phx_seg_stats(phx_ctx *c, int32_t i, int32_t *out, int32_t cap_records) {
     if (!c || !out) return 0;
-    if (c->in_flight && phx_wait(c)) return 0;
+    if (wait_in_flight(c)) return 0;
     if (i < 0 || i >= c->n || !c->ran || !c->pend_seg || !c->b_segw.p) return 0;
     if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return 0;
     const int K = c->pend_seg_k;
@@ -3154,19 +2393,19 @@ int phx_seg_stats(phx_ctx *c, int32_t i, int32_t *out, int32_t cap_records) {
 }
 int64_t phx_front_runs(phx_ctx *c) {
     if (!c) return PHX_E_ARG;
-    if (c->in_flight) { const int rs = phx_wait(c); if (rs) return rs; }
+    { const int rs = wait_in_flight(c); if (rs) return rs; }
     return c->front_off ? -c->front_runs - 1 : c->front_runs;
 }
 
 int64_t phx_plan_timeouts(phx_ctx *c) {
     if (!c) return PHX_E_ARG;
-    if (c->in_flight) { const int rs = phx_wait(c); if (rs) return rs; }
+    { const int rs = wait_in_flight(c); if (rs) return rs; }
     return c->plan_timeouts;
 }
 
 int phx_batch_sizes(phx_ctx *c, int64_t *L, int64_t *n_orf, int64_t *n_node, int64_t *n_edge) {
     if (!c) return PHX_E_ARG;
-    if (c->in_flight) { const int rs = phx_wait(c); if (rs) return rs; }
+    { const int rs = wait_in_flight(c); if (rs) return rs; }
     if (L) *L = c->totalL;
     if (n_orf) *n_orf = c->tot_orf;
     if (n_node) *n_node = c->tot_node;

@@ -358,45 +358,27 @@ void phxk_margins_transpose(const DBatch *b, const DMarg *g, void *stream) {
     hipLaunchKernelGGL(k_mg_scan, dim3(b->n_contig), dim3(NT), 0, s, *b, *g);
     hipLaunchKernelGGL(k_mg_fill, dim3(b->n_contig, y), dim3(NT), 0, s, *b, *g);
 }
-void phxk_sssp_rev(const DBatch *b, const DMarg *g, int nl_mask, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (nl_mask & 1) hipLaunchKernelGGL(k_sssp_rev<2>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g);
-    if (nl_mask & 2) hipLaunchKernelGGL(k_sssp_rev<4>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g);
-    if (nl_mask & 4) hipLaunchKernelGGL(k_sssp_rev<8>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g);
-    if (nl_mask & 8) hipLaunchKernelGGL(k_sssp_rev<17>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g);
-}
-void phxk_margins(const DBatch *b, const DMarg *g, int nl_mask, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid(b->n_contig, ysplit(b, 8));
-    if (nl_mask & 1) hipLaunchKernelGGL(k_margins<2>, grid, dim3(NT), 0, s, *b, *g);
-    if (nl_mask & 2) hipLaunchKernelGGL(k_margins<4>, grid, dim3(NT), 0, s, *b, *g);
-    if (nl_mask & 4) hipLaunchKernelGGL(k_margins<8>, grid, dim3(NT), 0, s, *b, *g);
-    if (nl_mask & 8) hipLaunchKernelGGL(k_margins<17>, grid, dim3(NT), 0, s, *b, *g);
-}
-// gene drop margins (phx_drop.inc): a workgroup per contig, one launch per limb class and step
-#define DP_LAUNCH(K, NLM) do { \
-        if ((NLM) & 1) hipLaunchKernelGGL(K<2>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q); \
-        if ((NLM) & 2) hipLaunchKernelGGL(K<4>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q); \
-        if ((NLM) & 4) hipLaunchKernelGGL(K<8>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q); \
-        if ((NLM) & 8) hipLaunchKernelGGL(K<17>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q); \
+// K<n_limbs> on stream s for every limb class of NLM (bit k: 2, 4, 8, 17 limbs)
+#define NL_LAUNCH(K, NLM, GRID, BLOCK, ...) do { \
+        if ((NLM) & 1) hipLaunchKernelGGL(K<2>, GRID, BLOCK, 0, s, __VA_ARGS__); \
+        if ((NLM) & 2) hipLaunchKernelGGL(K<4>, GRID, BLOCK, 0, s, __VA_ARGS__); \
+        if ((NLM) & 4) hipLaunchKernelGGL(K<8>, GRID, BLOCK, 0, s, __VA_ARGS__); \
+        if ((NLM) & 8) hipLaunchKernelGGL(K<17>, GRID, BLOCK, 0, s, __VA_ARGS__); \
     } while (0)
-void phxk_drop_trees(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; DP_LAUNCH(k_dp_tree, nl_mask); }
-void phxk_drop_cand(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; DP_LAUNCH(k_dp_cand, nl_mask); }
+void phxk_sssp_rev(const DBatch *b, const DMarg *g, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH(k_sssp_rev, nl_mask, dim3(b->n_contig), dim3(NT), *b, *g); }
+void phxk_margins(const DBatch *b, const DMarg *g, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH(k_margins, nl_mask, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), *b, *g); }
+// gene drop margins (phx_drop.inc): a workgroup per contig, one launch per limb class and step
+void phxk_drop_trees(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH(k_dp_tree, nl_mask, dim3(b->n_contig), dim3(NT), *b, *g, *q); }
+void phxk_drop_cand(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH(k_dp_cand, nl_mask, dim3(b->n_contig), dim3(NT), *b, *g, *q); }
 void phxk_drop_fix(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream) {
     hipStream_t s = (hipStream_t)stream;
-    DP_LAUNCH(k_dp_rescan, nl_mask);
-    DP_LAUNCH(k_dp_cross, nl_mask);
-    DP_LAUNCH(k_dp_rec, nl_mask);
+    NL_LAUNCH(k_dp_rescan, nl_mask, dim3(b->n_contig), dim3(NT), *b, *g, *q);
+    NL_LAUNCH(k_dp_cross, nl_mask, dim3(b->n_contig), dim3(NT), *b, *g, *q);
+    NL_LAUNCH(k_dp_rec, nl_mask, dim3(b->n_contig), dim3(NT), *b, *g, *q);
 }
 // drop replacements (phx_replace.inc): a workgroup per contig
-#define RP_LAUNCH(K, NLM) do { \
-        if ((NLM) & 1) hipLaunchKernelGGL(K<2>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q, *r); \
-        if ((NLM) & 2) hipLaunchKernelGGL(K<4>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q, *r); \
-        if ((NLM) & 4) hipLaunchKernelGGL(K<8>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q, *r); \
-        if ((NLM) & 8) hipLaunchKernelGGL(K<17>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q, *r); \
-    } while (0)
-void phxk_repl_pick(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; RP_LAUNCH(k_rp_pick, nl_mask); }
-void phxk_repl_cross(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; RP_LAUNCH(k_rp_cross, nl_mask); }
+void phxk_repl_pick(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH(k_rp_pick, nl_mask, dim3(b->n_contig), dim3(NT), *b, *g, *q, *r); }
+void phxk_repl_cross(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH(k_rp_cross, nl_mask, dim3(b->n_contig), dim3(NT), *b, *g, *q, *r); }
 void phxk_repl_walk(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int fill, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     if (fill) hipLaunchKernelGGL(k_rp_walk<1>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q, *r);

@@ -46,6 +46,25 @@ def test_no_cpu_fallback():
     assert e.value.code == -10
 
 
+def test_null_context_is_refused():
+    """Every entry point that takes a context and returns a status refuses a NULL context with PHX_E_ARG, whatever else it is given."""
+    lib = _lib.lib()
+    skip = {"phx_create", "phx_create_ex", "phx_pool_create",  # the constructors
+            "phx_default_params", "phx_version", "phx_strerror", "phx_device_count", "phx_pack_planes",  # host functions without a context
+            "phx_dec_eval", "phx_synth_contig", "phx_stage_name",
+            "phx_last_error", "phx_pool_last_error"}  # a string, not a status
+    counters = {"phx_seg_runs", "phx_seg_fallbacks", "phx_seg_stats"}  # counts, not statuses: 0 without a context
+    seen = 0
+    for name in _lib.EXPORTS:
+        f = getattr(lib, name)
+        if name in skip or name.startswith(("phx_format_", "phx_fasta_", "phx_dd_", "phx_params_")) or f.restype is None:
+            continue
+        args = [None if isinstance(t, type) and issubclass(t, (C._Pointer, C.c_void_p, C.c_char_p)) else 0 for t in f.argtypes]
+        assert f(*args) == (0 if name in counters else -1), name
+        seen += 1
+    assert seen >= 40
+
+
 def test_bad_params_rejected():
     lib = _lib.lib()
     h = C.c_void_p()
