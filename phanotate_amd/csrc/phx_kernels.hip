@@ -191,6 +191,12 @@ static void launch_certify(const DBatch *b, int vcap, hipStream_t s) {
     hipLaunchKernelGGL(k_certify<NL>, dim3(b->n_contig), dim3(CERT_T), lds, s, *b, vcap);
     hipLaunchKernelGGL(k_certify_wide<NL>, dim3(b->n_contig), dim3(CERT_T), 0, s, *b);
 }
+// a workgroup of SW_THREADS per contig with `lds` bytes of dynamic LDS (k_sssp_lds, k_rs_lds: one instantiation per limb class)
+template <class... A>
+static void launch_lds(void (*k)(A...), size_t lds, const DBatch *b, hipStream_t s, A... args) {
+    (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(k, dim3(b->n_contig), dim3(SW_THREADS), lds, s, args...);
+}
 extern "C" {
 void phxk_features(const DBatch *b, uint32_t v_begin, uint32_t v_end, void *stream) {
     if (v_end <= v_begin) return;
@@ -365,6 +371,13 @@ void phxk_margins_transpose(const DBatch *b, const DMarg *g, void *stream) {
         if ((NLM) & 4) hipLaunchKernelGGL(K<8>, GRID, BLOCK, 0, s, __VA_ARGS__); \
         if ((NLM) & 8) hipLaunchKernelGGL(K<17>, GRID, BLOCK, 0, s, __VA_ARGS__); \
     } while (0)
+// ... the same for K<n_limbs, T>, a kernel of T threads
+#define NL_LAUNCH_T(K, T, NLM, GRID, ...) do { \
+        if ((NLM) & 1) hipLaunchKernelGGL((K<2, T>), GRID, dim3(T), 0, s, __VA_ARGS__); \
+        if ((NLM) & 2) hipLaunchKernelGGL((K<4, T>), GRID, dim3(T), 0, s, __VA_ARGS__); \
+        if ((NLM) & 4) hipLaunchKernelGGL((K<8, T>), GRID, dim3(T), 0, s, __VA_ARGS__); \
+        if ((NLM) & 8) hipLaunchKernelGGL((K<17, T>), GRID, dim3(T), 0, s, __VA_ARGS__); \
+    } while (0)
 void phxk_sssp_rev(const DBatch *b, const DMarg *g, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH(k_sssp_rev, nl_mask, dim3(b->n_contig), dim3(NT), *b, *g); }
 void phxk_margins(const DBatch *b, const DMarg *g, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH(k_margins, nl_mask, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), *b, *g); }
 // gene drop margins (phx_drop.inc): a workgroup per contig, one launch per limb class and step
@@ -389,25 +402,15 @@ size_t phxk_sssp_lds_bytes(int V, int nl) { return sssp_lds_bytes(V, nl); }
 void phxk_reann_mask(const DBatch *b, const DReann *q, void *stream) { hipLaunchKernelGGL(k_rs_mask, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), 0, (hipStream_t)stream, *b, *q); }
 void phxk_reann_solve(const DBatch *b, const DReann *q, int nl_mask, void *stream) {
     hipStream_t s = (hipStream_t)stream;
-    if (nl_mask & 1) launch_rs_lds<2>(b, q, s);
-    if (nl_mask & 2) launch_rs_lds<4>(b, q, s);
-    if (nl_mask & 4) launch_rs_lds<8>(b, q, s);
-    if (nl_mask & 8) launch_rs_lds<17>(b, q, s);
+    if (nl_mask & 1) launch_lds(k_rs_lds<2>, rs_lds_bytes<2>(), b, s, *b, *q);
+    if (nl_mask & 2) launch_lds(k_rs_lds<4>, rs_lds_bytes<4>(), b, s, *b, *q);
+    if (nl_mask & 4) launch_lds(k_rs_lds<8>, rs_lds_bytes<8>(), b, s, *b, *q);
+    if (nl_mask & 8) launch_lds(k_rs_lds<17>, rs_lds_bytes<17>(), b, s, *b, *q);
 }
 void phxk_reann_finish(const DBatch *b, const DReann *q, int nl_mask, void *stream) {
     hipStream_t s = (hipStream_t)stream;
-    const dim3 g(b->n_contig);
-    if (b->mean_len < 8192) { // as phxk_inorder: one wavefront per short contig
-        if (nl_mask & 1) hipLaunchKernelGGL((k_rs_inorder<2, 64>), g, dim3(64), 0, s, *b, *q);
-        if (nl_mask & 2) hipLaunchKernelGGL((k_rs_inorder<4, 64>), g, dim3(64), 0, s, *b, *q);
-        if (nl_mask & 4) hipLaunchKernelGGL((k_rs_inorder<8, 64>), g, dim3(64), 0, s, *b, *q);
-        if (nl_mask & 8) hipLaunchKernelGGL((k_rs_inorder<17, 64>), g, dim3(64), 0, s, *b, *q);
-    } else {
-        if (nl_mask & 1) hipLaunchKernelGGL((k_rs_inorder<2, IO_T_FULL>), g, dim3(IO_T_FULL), 0, s, *b, *q);
-        if (nl_mask & 2) hipLaunchKernelGGL((k_rs_inorder<4, IO_T_FULL>), g, dim3(IO_T_FULL), 0, s, *b, *q);
-        if (nl_mask & 4) hipLaunchKernelGGL((k_rs_inorder<8, IO_T_FULL>), g, dim3(IO_T_FULL), 0, s, *b, *q);
-        if (nl_mask & 8) hipLaunchKernelGGL((k_rs_inorder<17, IO_T_FULL>), g, dim3(IO_T_FULL), 0, s, *b, *q);
-    }
+    if (b->mean_len < 8192) NL_LAUNCH_T(k_rs_inorder, 64, nl_mask, dim3(b->n_contig), *b, *q); // as phxk_inorder: one wavefront per short contig
+    else NL_LAUNCH_T(k_rs_inorder, IO_T_FULL, nl_mask, dim3(b->n_contig), *b, *q);
     hipLaunchKernelGGL(k_rs_fin, dim3((unsigned)((b->n_contig + 63) / 64)), dim3(64), 0, s, *b, *q);
 }
 // one workgroup for up to 1024 contigs; larger batches in two passes of a workgroup per 256 contigs
@@ -496,18 +499,10 @@ void phxk_sssp(const DBatch *b, int nl, int mode, size_t lds_bytes, void *stream
         return;
     }
     switch (nl) {
-    case 2:
-        (void)hipFuncSetAttribute((const void *)k_sssp_lds<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        hipLaunchKernelGGL(k_sssp_lds<2>, g, dim3(SW_THREADS), lds_bytes, s, *b, mode, (int)lds_bytes); break;
-    case 4:
-        (void)hipFuncSetAttribute((const void *)k_sssp_lds<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        hipLaunchKernelGGL(k_sssp_lds<4>, g, dim3(SW_THREADS), lds_bytes, s, *b, mode, (int)lds_bytes); break;
-    case 8:
-        (void)hipFuncSetAttribute((const void *)k_sssp_lds<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        hipLaunchKernelGGL(k_sssp_lds<8>, g, dim3(SW_THREADS), lds_bytes, s, *b, mode, (int)lds_bytes); break;
-    default:
-        (void)hipFuncSetAttribute((const void *)k_sssp_lds<17>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        hipLaunchKernelGGL(k_sssp_lds<17>, g, dim3(SW_THREADS), lds_bytes, s, *b, mode, (int)lds_bytes); break;
+    case 2: launch_lds(k_sssp_lds<2>, lds_bytes, b, s, *b, mode, (int)lds_bytes); break;
+    case 4: launch_lds(k_sssp_lds<4>, lds_bytes, b, s, *b, mode, (int)lds_bytes); break;
+    case 8: launch_lds(k_sssp_lds<8>, lds_bytes, b, s, *b, mode, (int)lds_bytes); break;
+    default: launch_lds(k_sssp_lds<17>, lds_bytes, b, s, *b, mode, (int)lds_bytes); break;
     }
 }
 }

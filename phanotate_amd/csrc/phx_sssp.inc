@@ -333,7 +333,6 @@ __device__ __forceinline__ uint32_t u32_row_min(uint32_t x, int sub) {
 #ifndef SW_RING
 #define SW_RING 1024
 #endif
-#define SW_EPT ((SW_ECAP + SW_THREADS - 1) / SW_THREADS) // tile edges prefetched per thread
 #ifndef SW_RCA
 #define SW_RCA 1 // in-edges per lane of a close node kept in registers
 #endif
@@ -347,38 +346,54 @@ __device__ __forceinline__ uint32_t u32_row_min(uint32_t x, int sub) {
 __host__ __device__ inline size_t sssp_lds_bytes(int V, int nl) {
     return (size_t)(SW_RING + 1) * nl * 8 + (size_t)SW_ECAP * ((size_t)nl * 8 + 4) + (size_t)(V / SW_ADV + 1) + 64;
 }
-template <int NL>
-__global__ __launch_bounds__(SW_THREADS, NL == 2 ? SW_WPS : (NL == 4 ? 4 : 2)) void k_sssp_lds(DBatch b, int mode, int lds_given) { // (wide classes: a few contigs per batch, registers before occupancy)
-    if (b.tot->overflow) return;
+// What differs between the two kernels that run the sweep below:
+//   SwRun       the run (k_sssp_lds): rows are plain ew[e] (expand_contig has completed them), the mask is never read, gpack is honoured;
+//   RsCfg<NL>   the masked re-annotation (k_rs_lds, phx_resolve.inc): MASKED, its own ring and tile sizes per limb class.
+// MASKED: the rows come through edge_wenc (coded gap edges from the contig's gap table, nothing written to DBatch.ew); an explicit row
+// whose bit is set in `mask` (one bit per in-edge slot of the batch) is no edge; the plan lives in LDS up to RS_PLAN_LDS windows, else in
+// the caller's `gplan`; gene slots always come from the shared counter.
+struct SwRun { static constexpr int RING = SW_RING, ECAP = SW_ECAP; static constexpr bool MASKED = false; };
+#define RS_PLAN_LDS 2048 // window-plan bytes kept in LDS (contigs of up to 65 536 nodes); longer plans live in DReann.gplan
+
+// in-edge slot e (source word sw) is refused: coded rows never are (phx_resolve.inc: the bitmap holds bits of explicit rows only)
+template <class P>
+__device__ __forceinline__ bool rs_refused(const uint32_t *mask, uint64_t ebase, uint32_t sw, uint32_t e) {
+    if (!P::MASKED || ESRC_IS_GAP(sw)) return false;
+    const uint64_t x = ebase + e;
+    return ((mask[x >> 5] >> (x & 31)) & 1u) != 0;
+}
+template <class P>
+__device__ __forceinline__ long long sw_row(uint32_t sw, const long long *ew, uint32_t e, const long long *gt) { return P::MASKED ? edge_wenc(sw, ew, e, gt) : ew[e]; }
+
+// The sweep of one contig by one workgroup of SW_THREADS threads: distances to b.dist, lowest-index tight parents to b.parent, then the
+// path and the genes.  V = meta->n_node (the caller has read it; after expand_contig's fence a second read would be a second load).
+template <int NL, class P>
+__device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const int V, const uint32_t *mask, uint8_t *gplan) {
+    constexpr int RING = P::RING, ECAP = P::ECAP;
+    constexpr int EPT = (ECAP + SW_THREADS - 1) / SW_THREADS; // tile edges prefetched per thread
     extern __shared__ __align__(16) uint8_t smem[];
     __shared__ int s_flag[2];
     __shared__ int s_np, s_nclose, s_viol;
     __shared__ uint32_t s_off[2][SW_MAX + 1];
     __shared__ uint8_t s_list[SW_MAX];
-    DMeta *meta = &b.meta[blockIdx.x];
-    const int V = meta->n_node;
-    if (meta->status < 0 || V <= 2 || meta->sssp_nl != NL || meta->sssp_mode != mode) return;
-    if (sssp_lds_bytes(V, NL) > (size_t)lds_given) return; // launched with less LDS than this contig needs: left unsolved (sweeps == 0), the host launches again
-    if (meta->sweeps != 0) return; // solved by an earlier launch of this run (the launch that runs beside the wavefront kernel)
     const int tid = threadIdx.x;
-    expand_contig(b, meta, tid, (int)blockDim.x); // (coded gap edges: this kernel reads plain rows)
-    __syncthreads();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     const int SRC = V - 2, TGT = V - 1, ncds = V - 2;
     const uint32_t *in_off = b.in_off + meta->node_off + blockIdx.x;
     const uint32_t *esrc = b.esrc + meta->edge_off;
     const long long *ew = b.ew + meta->edge_off;
+    const long long *gt = P::MASKED ? gtab_of(b, meta) : nullptr;
+    const uint64_t ebase = (uint64_t)meta->edge_off;
     const DNode *nd = b.node + meta->node_off;
     uint64_t *gdist = b.dist + (size_t)meta->node_off * b.dist_stride;
-    // LDS carve: ring (SW_RING+1)*NL u64 (slot SW_RING = the constant 0 of the source) | tile weights SW_ECAP*NL u64 |
-    // tile source slots SW_ECAP u32 | window plan nW bytes.  After convergence the ring+tile area is reused for one
+    // LDS carve: ring (RING+1)*NL u64 (slot RING = the constant 0 of the source) | tile weights ECAP*NL u64 |
+    // tile source slots ECAP u32 | window plan nW bytes.  After convergence the ring+tile area is reused for one
     // parent per node.
     uint64_t *ring = (uint64_t *)smem;
-    uint64_t *tw = ring + (size_t)(SW_RING + 1) * NL;
-    uint32_t *tsrc = (uint32_t *)(tw + (size_t)SW_ECAP * NL);
-    uint8_t *plan = (uint8_t *)(tsrc + SW_ECAP);
-    const size_t lds_words = (size_t)(SW_RING + 1) * NL * 2 + (size_t)SW_ECAP * NL * 2 + SW_ECAP; // 32-bit words before the plan
+    uint64_t *tw = ring + (size_t)(RING + 1) * NL;
+    uint32_t *tsrc = (uint32_t *)(tw + (size_t)ECAP * NL);
+    const size_t lds_words = (size_t)(RING + 1) * NL * 2 + (size_t)ECAP * NL * 2 + ECAP; // 32-bit words before the plan
     const int nW = (V + SW_ADV - 1) / SW_ADV;
+    uint8_t *plan = !P::MASKED || nW <= RS_PLAN_LDS ? (uint8_t *)(tsrc + ECAP) : gplan + (size_t)(meta->node_off >> 5) + blockIdx.x; // (a contig's slice: >= V / 32 + 1 bytes)
     for (int v = tid; v < V; v += SW_THREADS) {
         WInt<NL> d;
 #pragma unroll
@@ -386,9 +401,9 @@ __global__ __launch_bounds__(SW_THREADS, NL == 2 ? SW_WPS : (NL == 4 ? 4 : 2)) v
         if (v != SRC) d.v[NL - 1] = WBIG_TOP;
         wi_store<NL>(gdist + (size_t)v * NL, d);
     }
-    if (tid < NL) ring[(size_t)SW_RING * NL + tid] = 0;
+    if (tid < NL) ring[(size_t)RING * NL + tid] = 0;
 #ifdef SW_CENSUS
-    if (tid == 0) { uint32_t c = atomicAdd(b.gene_total + 1, 1u) + 1; atomicMax(b.gene_total + 2, c); }
+    if (!P::MASKED && tid == 0) { uint32_t c = atomicAdd(b.gene_total + 1, 1u) + 1; atomicMax(b.gene_total + 2, c); }
 #endif
     if (tid == 0) { s_flag[0] = 0; s_flag[1] = 0; }
     // ---- plan: size of every window = SW_ADV nodes to advance by + the nodes of the next 500 bp (<= SW_MAX, tile cap) ----
@@ -397,7 +412,7 @@ __global__ __launch_bounds__(SW_THREADS, NL == 2 ? SW_WPS : (NL == 4 ? 4 : 2)) v
         const int vadv = v0 + SW_ADV < V ? v0 + SW_ADV : V;
         const int idx = v0 + lane;
         bool ok = idx < V;
-        if (ok && idx >= vadv) ok = idx < ncds && vadv - 1 < ncds && nd[idx].pos < nd[vadv - 1].pos + 500 && in_off[idx + 1] - in_off[v0] <= SW_ECAP;
+        if (ok && idx >= vadv) ok = idx < ncds && vadv - 1 < ncds && nd[idx].pos < nd[vadv - 1].pos + 500 && in_off[idx + 1] - in_off[v0] <= (uint32_t)ECAP;
         const uint64_t m = __ballot(ok);
         const int cnt = m == ~0ull ? 64 : __ffsll((long long)~m) - 1;
         if (lane == 0) plan[k] = (uint8_t)cnt; // >= vadv - v0 >= 1
@@ -412,18 +427,24 @@ __global__ __launch_bounds__(SW_THREADS, NL == 2 ? SW_WPS : (NL == 4 ? 4 : 2)) v
     uint32_t *gpe = (uint32_t *)(b.parent + meta->node_off);
     const bool ps_lds = (size_t)V <= lds_words; // else (very large contigs) the final walk chases parent edges in global memory
     uint32_t *psrc = (uint32_t *)smem;
+    WInt<NL> big; // the unreached pattern
+#pragma unroll
+    for (int i = 0; i < NL; i++) big.v[i] = 0;
+    big.v[NL - 1] = WBIG_TOP;
     while (again && !bad) {
-        int loaded = 0; // nodes [max(0, loaded - SW_RING), loaded) are in the ring
-        if (tid < NL) ring[(size_t)SW_RING * NL + tid] = 0; // the constant-zero slot (the LDS is reused by the pass below)
+        int loaded = 0; // nodes [max(0, loaded - RING), loaded) are in the ring
+        if (tid < NL) ring[(size_t)RING * NL + tid] = 0; // the constant-zero slot (the LDS is reused by the pass below)
         if (tid == 0) s_viol = 0;
         __syncthreads();
-        // registers that carry window k+1's data while window k iterates
-        uint32_t r_src[SW_EPT];
-        long long r_w[SW_EPT];
+        // registers that carry window k+1's data while window k iterates; bit j of r_mk: tile edge j of this thread is refused
+        uint32_t r_src[EPT];
+        long long r_w[EPT];
+        uint32_t r_mk = 0;
         uint32_t r_offn = 0;
         int r_type = 0;
         WInt<NL> r_ring;
-        // prologue: window 0
+        // prologue: window 0.  (The tile loop is written out here and in the window loop: shared through a call or a lambda it costs
+        // two VGPRs in the 256-bit class of both kernels and 8 bytes of scratch in k_rs_lds<17>.)
         {
             const int nw0 = plan[0];
             if (tid <= nw0) s_off[0][tid] = in_off[tid];
@@ -434,11 +455,13 @@ __global__ __launch_bounds__(SW_THREADS, NL == 2 ? SW_WPS : (NL == 4 ? 4 : 2)) v
             r_ring = wi_load<NL>(gdist + (size_t)(tid < nw0 ? tid : 0) * NL);
             r_offn = (nW > 1 && tid <= plan[1]) ? in_off[SW_ADV + tid] : 0u;
 #pragma unroll
-            for (int j = 0; j < SW_EPT; j++) {
+            for (int j = 0; j < EPT; j++) {
                 const int i = tid + j * SW_THREADS;
-                const bool on = nen <= SW_ECAP && i < nen;
-                r_src[j] = on ? ESRC_NODE(esrc[e0n + i]) : 0u;
-                r_w[j] = on ? ew[e0n + i] : 0ll;
+                const bool on = nen <= ECAP && i < nen;
+                const uint32_t sw = on ? esrc[e0n + i] : 0u;
+                r_src[j] = ESRC_NODE(sw);
+                r_w[j] = on ? sw_row<P>(sw, ew, e0n + i, gt) : 0ll;
+                if (on && rs_refused<P>(mask, ebase, sw, e0n + i)) r_mk |= 1u << j;
             }
         }
         for (int k = 0; k < nW && !bad; k++) {
@@ -446,8 +469,10 @@ __global__ __launch_bounds__(SW_THREADS, NL == 2 ? SW_WPS : (NL == 4 ? 4 : 2)) v
             const int v0 = k * SW_ADV;
             const int nwin = plan[k];
             const int v1 = v0 + nwin;
+            // MASKED (the plan may be in global memory): the next two sizes are read once, here; else where they are used
+            const int nwn1 = P::MASKED && k + 1 < nW ? plan[k + 1] : 0, nwn2 = P::MASKED && k + 2 < nW ? plan[k + 2] : 0;
             // ---- commit the prefetched registers of this window to LDS ----
-            if (k + 1 < nW && tid <= plan[k + 1]) s_off[cur ^ 1][tid] = r_offn;
+            if (k + 1 < nW && tid <= (P::MASKED ? nwn1 : plan[k + 1])) s_off[cur ^ 1][tid] = r_offn;
             if (tid < 64) { // split the window into close nodes (ORF-edge targets) and open nodes (connector targets)
                 const int t = NTYPE(r_type), f = NFRAME(r_type);
                 const bool isclose = tid < nwin && ((t == 1 && f > 0) || (t == 0 && f < 0));
@@ -459,23 +484,24 @@ __global__ __launch_bounds__(SW_THREADS, NL == 2 ? SW_WPS : (NL == 4 ? 4 : 2)) v
                 if (tid == 0) s_nclose = nc;
             }
             // nodes that enter the ring with this window bring their current distance from global memory
-            if (loaded + tid < v1) wi_store<NL>(ring + (size_t)((loaded + tid) & (SW_RING - 1)) * NL, r_ring);
+            if (loaded + tid < v1) wi_store<NL>(ring + (size_t)((loaded + tid) & (RING - 1)) * NL, r_ring);
             loaded = v1 > loaded ? v1 : loaded;
             const uint32_t e0 = s_off[cur][0];
             const int ne = (int)(s_off[cur][nwin] - e0);
-            const bool tiled = ne <= SW_ECAP; // false only if the SW_ADV advance nodes alone exceed the tile
+            const bool tiled = ne <= ECAP; // false only if the SW_ADV advance nodes alone exceed the tile
             if (tiled) {
 #pragma unroll
-                for (int j = 0; j < SW_EPT; j++) {
+                for (int j = 0; j < EPT; j++) {
                     const int i = tid + j * SW_THREADS;
                     if (i < ne) {
                         const uint32_t u = r_src[j];
                         WInt<NL> w = ew_decode<NL>(r_w[j]);
                         // source slot: a ring slot, or the constant-zero slot (the source node; and sources outside the
                         // ring, whose distance cannot change while this window iterates and is folded into the weight)
-                        uint32_t sl = SW_RING;
-                        if (u != (uint32_t)SRC) {
-                            if ((int)u < loaded && (int)u + SW_RING >= loaded) sl = u & (SW_RING - 1);
+                        uint32_t sl = RING;
+                        if (P::MASKED && ((r_mk >> j) & 1u)) w = big; // refused: no edge (0 + "unreached" never wins), so the phases pay nothing for the mask
+                        else if (u != (uint32_t)SRC) {
+                            if ((int)u < loaded && (int)u + RING >= loaded) sl = u & (RING - 1);
                             else w = wi_add<NL>(w, wi_load<NL>(gdist + (size_t)u * NL));
                         }
                         tsrc[i] = sl;
@@ -486,18 +512,21 @@ __global__ __launch_bounds__(SW_THREADS, NL == 2 ? SW_WPS : (NL == 4 ? 4 : 2)) v
             __syncthreads();
             // ---- put window k+1 in flight ----
             if (k + 1 < nW) {
-                const int v0n = v0 + SW_ADV, nwn = plan[k + 1], v1n = v0n + nwn;
+                const int v0n = v0 + SW_ADV, nwn = P::MASKED ? nwn1 : plan[k + 1], v1n = v0n + nwn;
                 const uint32_t e0n = s_off[cur ^ 1][0];
                 const int nen = (int)(s_off[cur ^ 1][nwn] - e0n);
                 r_type = tid < nwn ? nd[v0n + tid].info : 0;
                 r_ring = wi_load<NL>(gdist + (size_t)(loaded + tid < v1n ? loaded + tid : 0) * NL);
-                r_offn = (k + 2 < nW && tid <= plan[k + 2]) ? in_off[v0n + SW_ADV + tid] : 0u;
+                r_offn = (k + 2 < nW && tid <= (P::MASKED ? nwn2 : plan[k + 2])) ? in_off[v0n + SW_ADV + tid] : 0u;
+                r_mk = 0;
 #pragma unroll
-                for (int j = 0; j < SW_EPT; j++) {
+                for (int j = 0; j < EPT; j++) {
                     const int i = tid + j * SW_THREADS;
-                    const bool on = nen <= SW_ECAP && i < nen;
-                    r_src[j] = on ? ESRC_NODE(esrc[e0n + i]) : 0u;
-                    r_w[j] = on ? ew[e0n + i] : 0ll;
+                    const bool on = nen <= ECAP && i < nen;
+                    const uint32_t sw = on ? esrc[e0n + i] : 0u;
+                    r_src[j] = ESRC_NODE(sw);
+                    r_w[j] = on ? sw_row<P>(sw, ew, e0n + i, gt) : 0ll;
+                    if (on && rs_refused<P>(mask, ebase, sw, e0n + i)) r_mk |= 1u << j;
                 }
             }
 #ifdef SW_PROFILE
@@ -513,31 +542,25 @@ __global__ __launch_bounds__(SW_THREADS, NL == 2 ? SW_WPS : (NL == 4 ? 4 : 2)) v
             const int lA = actA ? s_list[node_l] : 0, lB = actB ? s_list[nclose + node_l] : 0;
             const int iaA = actA ? (int)(s_off[cur][lA] - e0) + sub : 0, ibA = actA ? (int)(s_off[cur][lA + 1] - e0) : 0;
             const int iaB = actB ? (int)(s_off[cur][lB] - e0) + sub : 0, ibB = actB ? (int)(s_off[cur][lB + 1] - e0) : 0;
-            uint64_t *slotA = ring + (size_t)((v0 + lA) & (SW_RING - 1)) * NL, *slotB = ring + (size_t)((v0 + lB) & (SW_RING - 1)) * NL;
+            uint64_t *slotA = ring + (size_t)((v0 + lA) & (RING - 1)) * NL, *slotB = ring + (size_t)((v0 + lB) & (RING - 1)) * NL;
             uint64_t *gA = gdist + (size_t)(v0 + lA) * NL, *gB = gdist + (size_t)(v0 + lB) * NL;
             // the first SW_RCA / SW_RCB in-edges of this lane stay in registers for all rounds of the window
             // (close nodes have 1-2 in-edges — the starts of one stop-group; open nodes ~14 — the connectors)
             uint32_t csA[SW_RCA], csB[SW_RCB];
             WInt<NL> cwA[SW_RCA], cwB[SW_RCB];
-            {
-                WInt<NL> big;
 #pragma unroll
-                for (int i = 0; i < NL; i++) big.v[i] = 0;
-                big.v[NL - 1] = WBIG_TOP;
+            for (int j = 0; j < SW_RCA; j++) {
+                const int ia = iaA + j * SW_LPN;
+                const bool oa = tiled && ia < ibA;
+                csA[j] = oa ? tsrc[ia] : (uint32_t)RING;
+                cwA[j] = oa ? wi_load<NL>(tw + (size_t)ia * NL) : big;
+            }
 #pragma unroll
-                for (int j = 0; j < SW_RCA; j++) {
-                    const int ia = iaA + j * SW_LPN;
-                    const bool oa = tiled && ia < ibA;
-                    csA[j] = oa ? tsrc[ia] : (uint32_t)SW_RING;
-                    cwA[j] = oa ? wi_load<NL>(tw + (size_t)ia * NL) : big;
-                }
-#pragma unroll
-                for (int j = 0; j < SW_RCB; j++) {
-                    const int ib = iaB + j * SW_LPN;
-                    const bool ob = tiled && ib < ibB;
-                    csB[j] = ob ? tsrc[ib] : (uint32_t)SW_RING;
-                    cwB[j] = ob ? wi_load<NL>(tw + (size_t)ib * NL) : big;
-                }
+            for (int j = 0; j < SW_RCB; j++) {
+                const int ib = iaB + j * SW_LPN;
+                const bool ob = tiled && ib < ibB;
+                csB[j] = ob ? tsrc[ib] : (uint32_t)RING;
+                cwB[j] = ob ? wi_load<NL>(tw + (size_t)ib * NL) : big;
             }
             // A phase that changes nothing ends the window: the next phase would read exactly what it read last time.
             // (Exception: the window's very first phase A — phase B has not seen this window's close nodes yet.)
@@ -549,10 +572,7 @@ __global__ __launch_bounds__(SW_THREADS, NL == 2 ? SW_WPS : (NL == 4 ? 4 : 2)) v
                 if ((tid & ~63) / SW_LPN < (ph ? nopen : nclose)) {
                     const int ia = ph ? iaB : iaA, ib = ph ? ibB : ibA;
                     uint64_t *myslot = ph ? slotB : slotA;
-                    WInt<NL> d0;
-#pragma unroll
-                    for (int i = 0; i < NL; i++) d0.v[i] = 0;
-                    d0.v[NL - 1] = WBIG_TOP;
+                    WInt<NL> d0 = big;
                     if (act) d0 = wi_load<NL>(myslot);
                     WInt<NL> best = d0;
                     if (tiled) {
@@ -577,12 +597,14 @@ __global__ __launch_bounds__(SW_THREADS, NL == 2 ? SW_WPS : (NL == 4 ? 4 : 2)) v
                         }
                     } else {
                         for (int i = ia; i < ib; i += SW_LPN) {
-                            const uint32_t u = ESRC_NODE(esrc[e0 + i]);
+                            const uint32_t sw = esrc[e0 + i];
+                            if (rs_refused<P>(mask, ebase, sw, e0 + i)) continue;
+                            const uint32_t u = ESRC_NODE(sw);
                             WInt<NL> du;
-                            if (u == (uint32_t)SRC) du = wi_load<NL>(ring + (size_t)SW_RING * NL);
-                            else if ((int)u < loaded && (int)u + SW_RING >= loaded) du = wi_load<NL>(ring + (size_t)(u & (SW_RING - 1)) * NL);
+                            if (u == (uint32_t)SRC) du = wi_load<NL>(ring + (size_t)RING * NL);
+                            else if ((int)u < loaded && (int)u + RING >= loaded) du = wi_load<NL>(ring + (size_t)(u & (RING - 1)) * NL);
                             else du = wi_load<NL>(gdist + (size_t)u * NL);
-                            best = wi_min_bf<NL>(best, wi_add<NL>(du, ew_decode<NL>(ew[e0 + i])));
+                            best = wi_min_bf<NL>(best, wi_add<NL>(du, ew_decode<NL>(sw_row<P>(sw, ew, e0 + i, gt))));
                         }
                     }
                     best = wi_row_min<NL>(best, sub);
@@ -608,7 +630,8 @@ __global__ __launch_bounds__(SW_THREADS, NL == 2 ? SW_WPS : (NL == 4 ? 4 : 2)) v
         // ---- verification + parents in one pass over every in-edge (distances from global memory) ----
         // A node that some in-edge could still improve means the sweep missed a backward dependency that reaches
         // beyond a window's look-ahead: sweep again.  Otherwise the distances are the fixed point and every node
-        // takes its tight in-edge with the lowest index as parent (canonical tie-break).
+        // takes its tight in-edge with the lowest index as parent (canonical tie-break).  A refused edge neither
+        // violates the fixed point nor becomes a parent.
         for (int vb = 0; vb < V; vb += SW_MAX) {
             const int v = vb + node_l;
             uint32_t be = PE_NONE;
@@ -617,7 +640,9 @@ __global__ __launch_bounds__(SW_THREADS, NL == 2 ? SW_WPS : (NL == 4 ? 4 : 2)) v
                 const WInt<NL> dv = wi_load<NL>(gdist + (size_t)v * NL);
                 const uint32_t e1 = in_off[v + 1];
                 for (uint32_t e = in_off[v] + sub; e < e1; e += SW_LPN) {
-                    const WInt<NL> cand = wi_add<NL>(wi_load<NL>(gdist + (size_t)ESRC_NODE(esrc[e]) * NL), ew_decode<NL>(ew[e]));
+                    const uint32_t sw = esrc[e];
+                    if (rs_refused<P>(mask, ebase, sw, e)) continue;
+                    const WInt<NL> cand = wi_add<NL>(wi_load<NL>(gdist + (size_t)ESRC_NODE(sw) * NL), ew_decode<NL>(sw_row<P>(sw, ew, e, gt)));
                     if (wi_lt_bf<NL>(cand, dv)) viol = true;
                     if (wi_eq<NL>(cand, dv) && e < be && !wi_unreached<NL>(dv)) be = e;
                 }
@@ -649,15 +674,15 @@ __global__ __launch_bounds__(SW_THREADS, NL == 2 ? SW_WPS : (NL == 4 ? 4 : 2)) v
                 meta->n_path = n + 1;
                 np = n / 2; // shortest_path[1:] taken two at a time (file_handling.pairwise)
                 meta->n_genes = np;
-                meta->gene_off = b.gpack ? (uint32_t)(meta->grp_off + meta->tn_off) : atomicAdd(b.gene_total, (uint32_t)np);
+                meta->gene_off = !P::MASKED && b.gpack ? (uint32_t)(meta->grp_off + meta->tn_off) : atomicAdd(b.gene_total, (uint32_t)np);
             }
         }
         s_np = np;
 #ifdef SW_CENSUS
-        atomicSub(b.gene_total + 1, 1u);
+        if (!P::MASKED) atomicSub(b.gene_total + 1, 1u);
 #endif
 #ifdef SW_PROFILE
-        { long long t = wall_clock64(); meta->pmax[0] = (uint32_t)t_setup; meta->pmin[0] = (uint32_t)t_iter; meta->sssp_why = (int32_t)(t - t_mark); }
+        if (!P::MASKED) { long long t = wall_clock64(); meta->pmax[0] = (uint32_t)t_setup; meta->pmin[0] = (uint32_t)t_iter; meta->sssp_why = (int32_t)(t - t_mark); }
 #endif
     }
     __syncthreads();
@@ -665,4 +690,16 @@ __global__ __launch_bounds__(SW_THREADS, NL == 2 ? SW_WPS : (NL == 4 ? 4 : 2)) v
     if (npairs > 0) emit_genes(b, meta, path, npairs, (size_t)meta->gene_off, tid, SW_THREADS);
 }
 
-
+template <int NL>
+__global__ __launch_bounds__(SW_THREADS, NL == 2 ? SW_WPS : (NL == 4 ? 4 : 2)) void k_sssp_lds(DBatch b, int mode, int lds_given) { // (wide classes: a few contigs per batch, registers before occupancy)
+    if (b.tot->overflow) return;
+    DMeta *meta = &b.meta[blockIdx.x];
+    const int V = meta->n_node;
+    if (meta->status < 0 || V <= 2 || meta->sssp_nl != NL || meta->sssp_mode != mode) return;
+    if (sssp_lds_bytes(V, NL) > (size_t)lds_given) return; // launched with less LDS than this contig needs: left unsolved (sweeps == 0), the host launches again
+    if (meta->sweeps != 0) return; // solved by an earlier launch of this run (the launch that runs beside the wavefront kernel)
+    expand_contig(b, meta, (int)threadIdx.x, (int)blockDim.x); // (coded gap edges: the sweep reads plain rows)
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    lds_sweep<NL, SwRun>(b, meta, V, nullptr, nullptr);
+}

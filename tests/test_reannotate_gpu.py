@@ -267,6 +267,30 @@ def test_masks_in_the_wide_classes(pa):
         ann.close()
 
 
+def test_an_untiled_window_in_the_run_and_under_a_mask(pa):
+    """One long ORF with some 1200 in-frame starts: its stop node has more in-edges than the in-edge tile of the windowed solver holds
+    (1024 rows; 512 in the 1088-bit class of the re-annotation), so the window's advance nodes alone exceed the tile and both k_sssp_lds
+    and k_rs_lds relax that window from global memory, row by row.  The run's distances are exact, the empty mask returns the run's bytes,
+    and without the long ORF's own called gene, whose edge is one of those rows, the result is the in-place Bellman-Ford's."""
+    from test_gpu_parity import check_exact_distances
+
+    ann = pa.Annotator(flags=("solver_no_wave",))  # k_sssp_lds is the only solver
+    st0, offs0, genes0 = run_batch(ann, [wide_contig(pa, 6000, 6000, density=0.2)])
+    assert st0[0] == 0
+    indeg = np.bincount(ann.edges(0)["dst"])
+    big = int(indeg.argmax())
+    assert indeg[big] > 1024, int(indeg[big])
+    check_exact_distances(ann, 0)
+    assert check_empty_mask(ann, 1) == 1
+    ref = Ref(ann, 0)
+    own = [g for g in genes0 if abs(int(g["frame"])) <= 3 and int(g["strand"]) == 1 and int(g["right"]) == int(ref.pos[big]) + 2]
+    assert len(own) == 1  # the called gene that ends at the node of many in-edges
+    forbid = ref.called(own)
+    st, offs, genes, delta = ann.reannotate([forbid])
+    check_against_ref(ann, ref, forbid, int(st[0]), genes, delta[0], ann.path(0)[1])
+    ann.close()
+
+
 # ---- 3. the tie rule under a mask ----
 def test_tie_rule_under_a_mask(pa):
     """Contigs with equal-length alternatives (globals.tie != 0), every called gene masked singly: the path is the in-place
