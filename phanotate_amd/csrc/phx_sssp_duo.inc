@@ -5,8 +5,9 @@
 // same wavefront also prepared every window — staged its in-edges, turned (source node, integer weight) into (ring slot, cached
 // weight) per lane, read the window and lane records: per 50 kb contig 85 us of conversion and ~60 us of bookkeeping beside 220 us
 // of phases, none of which depends on a distance.  Here the workgroup is two wavefronts:
-//   * the SOLVER wavefront runs the phases (the code of k_sssp_wave on 64-bit cached weights), and per window only copies the lane
-//     pack out of LDS;
+//   * the SOLVER wavefront is a WvSolver (phx_sssp_wave.inc) over WvNum<2> and WvCw64 — the ring and the relative ring, the base move, the
+//     lane-record decode, phase / phase64 and the phase loop, the pending results and parents, the step-back target, the tail and the
+//     hand-back are k_sssp_wave's, one definition —, and per window only copies the lane pack out of LDS;
 //   * the FEEDER wavefront runs one window ahead: it reads the window record, the lane records and the lanes' in-edges straight from
 //     global memory (no staging area), converts them in registers and, as soon as the solver has taken the previous pack, writes the
 //     next one to LDS: 20 cached (weight, source slot) pairs per lane, the lane records, a header.
@@ -18,7 +19,7 @@
 // weights beyond 2^51, sources that left the ring).
 // Every spin is bounded: a hand-shake that does not complete hands the contig to the workgroup kernel (sssp_why 6) instead of hanging.
 //
-// Differences to k_sssp_wave<2>: cached weights are 64 bits wide (the generic WvCw form) and the few in-edges that do not fit go to
+// Differences to k_sssp_wave<2>: cached weights are 64 bits wide (WvCw64) and the few in-edges that do not fit go to
 // the side list in LDS, as in the 256- / 512-bit kernels; a final source is folded into a constant only when it has left the ring
 // (its distance is in global memory, stored windows ago) or is the source node — the ring itself belongs to the solver.
 
@@ -73,6 +74,26 @@ __device__ __forceinline__ void duo_poke(uint32_t *p, uint32_t v) { __hip_atomic
 __device__ __forceinline__ void duo_release() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local"); }
 __device__ __forceinline__ void duo_acquire() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local"); }
 
+#ifdef DUO_PROFILE // the solver wavefront's clocks behind WvSolver's hook (tools/duo_balance.py reads what the kernel's tail copies to DMeta)
+struct DuoProf {
+    long long tp[4], tmark, t_begin, tab[2], tmark_ab;
+    int nab[3];
+    __device__ __forceinline__ void start() { for (int i = 0; i < 4; i++) tp[i] = 0; tab[0] = tab[1] = 0; nab[0] = nab[1] = nab[2] = 0; tmark = t_begin = tmark_ab = wall_clock64(); }
+    __device__ __forceinline__ void tick(int k) { const long long t_ = wall_clock64(); tp[k] += t_ - tmark; tmark = t_; }
+    __device__ __forceinline__ void fine(int) {}
+    __device__ __forceinline__ void rebase() {}
+    __device__ __forceinline__ void phase_done(int ph, bool, bool exact, int) {
+#ifdef DUO_PROFILE_AB
+        const long long t_ = wall_clock64(); tab[ph ? 1 : 0] += t_ - tmark_ab; tmark_ab = t_; nab[ph ? 1 : 0]++; if (exact) nab[2]++;
+#endif
+    }
+};
+#define DUO_TICK(k) S.prof.tick(k);
+#else
+typedef WvNoProf DuoProf;
+#define DUO_TICK(k)
+#endif
+
 // SEG (phx_sssp_seg.inc): a workgroup solves one SEGMENT [ns, ne) of a contig in a frame of its own — nodes left of ns (and, beyond the
 // first segment, the source node) count as unreached, the nodes of the first window start at distance 0 —, writes the distances to its
 // slice of DBatch.sdist and its status to DBatch.segw; parents and the contig's records are k_seg_merge's.
@@ -82,7 +103,8 @@ __global__ __launch_bounds__(128, 2) void k_sssp_duo(DBatch b) {
     typedef DuoDims<CFG> D;
     typedef WvNum<2> N;
     typedef N::T T;
-    typedef long long CW;
+    typedef WvCw64 C;
+    typedef C::CW CW;
     constexpr int NL = 2, CA = N::CA, CB = N::CB, WV_RING = D::RING, WV_OV = D::OV, WV_SLOTS = WV_RING + 2;
     static_assert(CA == 4 && CB == 16 && CA + CB == DUO_SLOTS, "the lane pack holds 4 + 16 cached in-edges");
     __shared__ __align__(16) uint8_t smem[duo_lds_bytes<CFG>()]; // static: the kernel's only LDS, so every address below is a compile-time constant + lane part
@@ -125,12 +147,12 @@ __global__ __launch_bounds__(128, 2) void k_sssp_duo(DBatch b) {
     if (!mb[DUO_GO]) return;
     const int V = meta->n_node;
     const int SRC = V - 2;
-    const uint32_t ZERO = (uint32_t)WV_RING * NL * 8, INF = (uint32_t)(WV_RING + 1) * NL * 8;
+    typedef WvSolver<N, C, WV_RING, WV_OV, !SEG, DuoProf> Solver;
+    constexpr uint32_t ZERO = Solver::ZERO, INF = Solver::INF;
     int seg_ns = 0, seg_ne = V; // the node range of this sweep
     size_t seg_w = 0;
     if constexpr (SEG) { int cs_; const SegRank rk(b, meta); seg_range(seg_geo(b, meta), rk, V, seg_s, seg_ns, cs_, seg_ne); seg_w = seg_win_off(b, meta, seg_s); } // (the same cut as the segment's planner)
     uint64_t *gdist = SEG ? b.sdist + ((size_t)seg_s * (size_t)b.sdist_nodes + (size_t)meta->node_off) * NL : b.dist + (size_t)meta->node_off * b.dist_stride;
-    auto narrow51 = [](long long w) { return (unsigned long long)(w + (1ll << 51)) < (1ull << 52); };
     constexpr uint32_t PADU_ = 0x3ffffffeu; // a source that is never loaded: pads a lane's in-edge list
 
 #ifdef DUO_HWID // development: where the hardware put the two wavefronts (tools/duo_hwid.py): HW_ID (wave 3:0, SIMD 5:4, CU 11:8, SH 12, SE 15:13) and XCC_ID
@@ -152,17 +174,7 @@ __global__ __launch_bounds__(128, 2) void k_sssp_duo(DBatch b) {
         const uint2 *wrole = SEG ? b.swrole + seg_w * WIN_ROLES : b.wrole + (size_t)meta->win_off * WIN_ROLES;
         int n_win = STREAM ? 0 : (int)mb[DUO_NWIN];
         bool plan_done = !STREAM;
-        auto wait_plan = [&](int need) -> int { // as in k_sssp_wave: 0 go on, 1 the planner gave the contig up, 2 no progress
-            for (int spins = 0;; spins++) {
-                const int p = __hip_atomic_load(SEG ? seg_rec : &meta->plan_prog, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-                if (p < 0) return 1;
-                n_win = p & (WV_PLAN_DONE - 1);
-                plan_done = (p & WV_PLAN_DONE) != 0;
-                if (plan_done || n_win >= need) return 0;
-                if (spins > WV_PLAN_SPINS) return 2;
-                __builtin_amdgcn_s_sleep(4);
-            }
-        };
+        auto wait_plan = [&](int need) { return wv_wait_plan(SEG ? seg_rec : &meta->plan_prog, need, n_win, plan_done); }; // (the word the planner this feeder follows publishes)
         int pseq = 0; // packs published
 #ifdef DUO_PROFILE
         long long ft[4] = {0, 0, 0, 0}, fmark = wall_clock64(); int f_ov = 0;
@@ -219,9 +231,9 @@ __global__ __launch_bounds__(128, 2) void k_sssp_duo(DBatch b) {
                 n_spill = __builtin_amdgcn_readfirstlane((int)r1.w);
                 if (v1 > loaded) loaded = v1;
                 ring_lo = loaded - WV_RING;
-                const int maxA = (int)((sumA >> 8) & 255u), maxB = (int)((sumB >> 8) & 255u);
-                const int cntA = (int)((rcA.x >> 19) & 31u), cntB = (int)((rcB.x >> 19) & 31u);
-                const uint32_t ebA = e0 + (rcA.y & 2047u), ebB = e0 + (rcB.y & 2047u);
+                const int maxA = wv_sum_maxcnt(sumA), maxB = wv_sum_maxcnt(sumB);
+                const int cntA = wv_role_cnt(rcA), cntB = wv_role_cnt(rcB);
+                const uint32_t ebA = e0 + (uint32_t)wv_role_ebase(rcA), ebB = e0 + (uint32_t)wv_role_ebase(rcB);
                 // the lanes' in-edges, all in flight together (slots past a lane's count read what follows: other lanes' in-edges, the next
                 // contig's, or the slack behind the arrays; they are masked below)
 #pragma unroll
@@ -313,7 +325,7 @@ __global__ __launch_bounds__(128, 2) void k_sssp_duo(DBatch b) {
                             const bool far = on && !isrc && (int)u[g] < ring_lo && !outside;
                             cs[t0 + g] = beyond ? INF : ((isrc || far) ? ZERO : (u[g] & (WV_RING - 1)) * NL * 8);
                             cw[t0 + g] = beyond ? 0ll : wt[g];
-                            if (on && !outside && (far || !narrow51(wt[g]))) slow |= 1u << (t0 + g);
+                            if (on && !outside && (far || !ew_narrow51(wt[g]))) slow |= 1u << (t0 + g);
                         }
                     }
                     return slow;
@@ -454,12 +466,9 @@ __global__ __launch_bounds__(128, 2) void k_sssp_duo(DBatch b) {
                 };
                 // the planner's spill entries of a head lane: in-edges beyond its helper lanes
                 auto spill = [&](const int cap, const uint2 rc) {
-                    const bool act = (rc.x >> 24) & 1u;
-                    const int ch = (int)((rc.x >> 7) & 63u);
-                    if (!act || ch != 0) return;
-                    const int nfollow = (int)((rc.x >> 13) & 63u);
-                    const int sp0 = (int)((rc.y >> 11) & 1023u), sp1 = sp0 + (int)((rc.y >> 21) & 1023u);
-                    const uint32_t spe = e0 + (rc.y & 2047u) + (uint32_t)((nfollow + 1) * cap);
+                    if (!wv_role_act(rc) || wv_role_ch(rc) != 0) return;
+                    const int sp0 = wv_role_sp0(rc), sp1 = sp0 + wv_role_spn(rc);
+                    const uint32_t spe = e0 + (uint32_t)wv_role_ebase(rc) + (uint32_t)((wv_role_nfollow(rc) + 1) * cap);
                     for (int i = sp0; i < sp1 && i < WV_OV; i++) {
                         const uint32_t sws = esrc[spe + (uint32_t)(i - sp0)];
                         const uint32_t u = ESRC_NODE(sws);
@@ -470,7 +479,7 @@ __global__ __launch_bounds__(128, 2) void k_sssp_duo(DBatch b) {
                         const bool far = !isrc && (int)u < ring_lo && !outside;
                         const uint32_t sl = beyond ? INF : ((isrc || far) ? ZERO : (u & (WV_RING - 1)) * NL * 8);
                         T wv = N::from_i64(beyond ? 0ll : wd);
-                        if (!outside && (far || !narrow51(wd))) {
+                        if (!outside && (far || !ew_narrow51(wd))) {
                             wv = EW_WIDE(wd) ? N::from_double(__longlong_as_double(wd | (1ll << 62))) : N::from_i64(wd);
                             if (far) {
                                 T d;
@@ -507,7 +516,7 @@ __global__ __launch_bounds__(128, 2) void k_sssp_duo(DBatch b) {
             }
             // ---------- the pack ----------
             {
-                const int maxA = (int)((sumA >> 8) & 255u), maxB = (int)((sumB >> 8) & 255u);
+                const int maxA = wv_sum_maxcnt(sumA), maxB = wv_sum_maxcnt(sumB);
                 if (maxA > 0) {
 #pragma unroll
                     for (int t = 0; t < CA; t++) pk_cw[t * 64 + lane] = (unsigned long long)cwA[t];
@@ -543,45 +552,18 @@ __global__ __launch_bounds__(128, 2) void k_sssp_duo(DBatch b) {
     // =========================================== the solver ===========================================
     __builtin_amdgcn_s_setprio(3); // the phases are the critical path: this wavefront goes first wherever it shares a SIMD with feeders (or another batch's kernels)
     int32_t *gpe = b.parent + meta->node_off; // parent edge of every node (contig-relative), -1: none (SEG: k_seg_merge picks them)
-    T base = N::zero();
-    for (int i = lane; i < WV_RING; i += 64) { N::store(ring + (size_t)i * NL * 8, N::big()); *(long long *)(rel + (size_t)i * 8) = WV_REL_BIG; }
-    if (lane == 0) {
-        N::store(ring + ZERO, N::zero()); *(long long *)(rel + ZERO / NL) = WV_REL(0);
-        N::store(ring + INF, N::big()); *(long long *)(rel + INF / NL) = WV_REL_BIG;
-    }
-    auto to_rel = [&](T d, bool &low) -> long long {
-        const T x = N::sub(d, base);
-        const long long xl = (long long)N::lo64(x);
-        const bool fits = N::is_i64(x) && xl < WV_NARROW && xl > -WV_NARROW;
-        low = !fits && N::negative(x);
-        return N::unreached(d) ? WV_REL_BIG : (fits ? WV_REL(xl) : WV_REL_WIDE);
-    };
-    int loaded = seg_ns, phases = 0, rollbacks = 0;
+    Solver S;
+    S.init(ring, rel, ov_w, ov_s, gdist, gpe, lane);
+    int loaded = seg_ns;
     const long long seg_t0 = SEG ? wall_clock64() : 0ll;
     bool seed = SEG && seg_s > 0; // (SEG) the nodes of the frame's first 500 bp start at 0: any frame will do, the paths behind them merge within the margin
-    bool wide = false, fail = false;
+    bool fail = false;
     int fail_code = 0;
     int seq = 0;      // packs taken or rejected
     int pend_rr = -1; // a step-back is pending: the next pack is the feeder's guess and is rejected
-    int pend_dv = -1, pend_av = -1, pend_bv = -1, pend_ae = -1, pend_be = -1;
-    T pend_d = N::zero();
-    auto flush_results = [&]() {
-        if (pend_dv >= 0) N::store(gdist + (size_t)pend_dv * NL, pend_d);
-        if (!SEG && pend_av >= 0) gpe[pend_av] = pend_ae;
-        if (!SEG && pend_bv >= 0) gpe[pend_bv] = pend_be;
-        pend_dv = -1; pend_av = -1; pend_bv = -1;
-    };
-    auto min64 = [](uint64_t a, uint64_t c) -> uint64_t { uint64_t r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(c)); return r; };
     bool abandoned = false;
 #ifdef DUO_PROFILE
-    long long tp[4] = {0, 0, 0, 0}, tmark = wall_clock64();
-#ifdef DUO_PROFILE_AB
-    long long tab[2] = {0, 0}; int nab[3] = {0, 0, 0};
-#endif
-    const long long t_begin = tmark;
-#define DUO_TICK(k) { const long long t_ = wall_clock64(); tp[k] += t_ - tmark; tmark = t_; }
-#else
-#define DUO_TICK(k)
+    S.prof.start();
 #endif
     wv_sync();
     while (true) {
@@ -610,11 +592,11 @@ __global__ __launch_bounds__(128, 2) void k_sssp_duo(DBatch b) {
         const int v0 = __builtin_amdgcn_readfirstlane(hdr[DUO_H_V0]), va = __builtin_amdgcn_readfirstlane(hdr[DUO_H_VA]), v1 = __builtin_amdgcn_readfirstlane(hdr[DUO_H_V1]);
         const uint32_t e0 = (uint32_t)__builtin_amdgcn_readfirstlane(hdr[DUO_H_E0]);
         const uint32_t sumA = (uint32_t)__builtin_amdgcn_readfirstlane(hdr[DUO_H_SUMA]), sumB = (uint32_t)__builtin_amdgcn_readfirstlane(hdr[DUO_H_SUMB]);
-        const bool has_spill = __builtin_amdgcn_readfirstlane(hdr[DUO_H_SPILL]) != 0;
-        const bool narrow_w = (flags & DUO_F_NARROW) != 0;
+        S.has_spill = __builtin_amdgcn_readfirstlane(hdr[DUO_H_SPILL]) != 0;
+        S.narrow_w = (flags & DUO_F_NARROW) != 0;
         const bool last = (flags & DUO_F_LAST) != 0;
         __builtin_amdgcn_s_waitcnt(0x0f70); // vmcnt(0): the results stored a window ago are in memory (the feeder may read them windows later)
-        flush_results();
+        S.flush_results();
         // ---- nodes that enter the ring ----
         int seed_end = loaded; // (SEG, first window of a frame without the source) the nodes of its first 500 bp start at distance 0
         if constexpr (SEG) {
@@ -635,54 +617,18 @@ __global__ __launch_bounds__(128, 2) void k_sssp_duo(DBatch b) {
         if (SRC >= loaded && SRC < v1 && lane == 0 && seg_s == 0) { // ... but the source node (the last but one node: one of the last windows)
             bool low;
             N::store(ring + (size_t)(SRC & (WV_RING - 1)) * NL * 8, N::zero());
-            *(long long *)(rel + (size_t)(SRC & (WV_RING - 1)) * 8) = to_rel(N::zero(), low);
+            *(long long *)(rel + (size_t)(SRC & (WV_RING - 1)) * 8) = S.to_rel(N::zero(), low);
         }
         if (v1 > loaded) loaded = v1;
         wv_sync();
-        if (wide) { // move the base to the lowest real distance in the ring (k_sssp_wave)
-            T mn = N::load(ring + ZERO);
-            for (int i = lane; i < WV_RING; i += 64) { const T d = N::load(ring + (size_t)i * NL * 8); mn = N::sel(N::lt(d, mn), d, mn); }
-            for (int st = 32; st >= 1; st >>= 1) {
-                const T c = N::map32(mn, [&](int x) { return __shfl_xor(x, st); });
-                mn = N::sel(N::lt(c, mn), c, mn);
-            }
-            base = mn;
-            bool low;
-            for (int i = lane; i < WV_RING + 1; i += 64) *(long long *)(rel + (size_t)i * 8) = to_rel(N::load(ring + (size_t)i * NL * 8), low);
-            wide = false;
-            wv_sync();
-        }
+        S.move_base();
         // ---- the lanes of the two phases: records and cached in-edges from the pack ----
-        struct Role {
-            int node, ch, nfollow, cnt, ebase, sp0, sp1, spe, pe, maxcnt, maxfollow, sd0, sd1;
-            bool head, nextf, watch;
-            uint32_t slot;
-        };
-        auto setup = [&](Role &R, const uint2 rc, const uint32_t summary, const int cap, const uint32_t sd) {
-            const bool act = (rc.x >> 24) & 1u;
-            const int o_j = (int)(rc.x & 127u);
-            R.node = act ? o_j : -1;
-            R.ch = (int)((rc.x >> 7) & 63u);
-            R.head = act && R.ch == 0;
-            R.nextf = wv_next(act ? R.ch : 0) >= 1;
-            R.watch = (rc.x >> 25) & 1u;
-            R.nfollow = (int)((rc.x >> 13) & 63u);
-            R.cnt = (int)((rc.x >> 19) & 31u);
-            R.ebase = (int)(rc.y & 2047u);
-            R.sp0 = (int)((rc.y >> 11) & 1023u);
-            R.sp1 = R.sp0 + (int)((rc.y >> 21) & 1023u);
-            R.spe = R.ebase + (R.nfollow + 1) * cap;
-            R.slot = (uint32_t)((v0 + o_j) & (WV_RING - 1)) * NL * 8;
-            R.pe = -1;
-            R.maxcnt = (int)((summary >> 8) & 255u);
-            R.maxfollow = (int)((summary >> 16) & 255u);
-            R.sd0 = (int)(sd & 0xffffu); R.sd1 = (int)(sd >> 16);
-        };
-        Role A, B;
-        CW cwA[CA], cwB[CB];
+        WvLane A, B;
+        CW cwA[CA], cwB[CB]; // (beside the lanes, not inside a WvRole: see there for what that cost)
         uint32_t csA[CA], csB[CB];
-        setup(A, s_role[lane], sumA, CA, pk_sd[lane]);
-        setup(B, s_role[64 + lane], sumB, CB, pk_sd[64 + lane]);
+        S.decode(A, s_role[lane], sumA, v0, CA);
+        S.decode(B, s_role[64 + lane], sumB, v0, CB);
+        { const uint32_t sa = pk_sd[lane], sb = pk_sd[64 + lane]; A.sd0 = (int)(sa & 0xffffu); A.sd1 = (int)(sa >> 16); B.sd0 = (int)(sb & 0xffffu); B.sd1 = (int)(sb >> 16); }
         if (A.maxcnt > 0) {
 #pragma unroll
             for (int t = 0; t < CA; t++) cwA[t] = (CW)pk_cw[t * 64 + lane];
@@ -711,247 +657,53 @@ __global__ __launch_bounds__(128, 2) void k_sssp_duo(DBatch b) {
         seq = want;
         DUO_TICK(1)
 
-        // ---- iterate to the fixed point (k_sssp_wave's phases on 64-bit cached weights) ----
-        auto phase = [&](Role &R, auto capc, const CW *cw, const uint32_t *cs) -> bool {
-            constexpr int cap = decltype(capc)::value;
-            T m = N::top();
-            int arg = 0;
-            constexpr int G = cap < 8 ? cap : 8;
-#pragma unroll
-            for (int t0 = 0; t0 < cap; t0 += G) {
-                if (t0 >= R.maxcnt) break;
-                T x[G];
-                int xa[G];
-#pragma unroll
-                for (int g = 0; g < G; g++) x[g] = N::load(ring + cs[t0 + g]);
-#pragma unroll
-                for (int g = 0; g < G; g++) xa[g] = t0 + g;
-                if (narrow_w) {
-#pragma unroll
-                    for (int g = 0; g < G; g++) {
-                        uint64_t lo = (uint64_t)cw[t0 + g];
-                        asm volatile("" : "+v"(lo));
-                        x[g] = N::add(x[g], N::from_i64((long long)lo >> 4));
-                    }
-                } else {
-#pragma unroll
-                    for (int g = 0; g < G; g++) x[g] = N::add(x[g], N::from_i64(cw[t0 + g]));
-                }
-#pragma unroll
-                for (int w = 1; w < G; w <<= 1)
-#pragma unroll
-                    for (int g = 0; g + w < G; g += 2 * w) {
-                        const bool l = N::lt(x[g + w], x[g]);
-                        x[g] = N::sel(l, x[g + w], x[g]);
-                        xa[g] = l ? xa[g + w] : xa[g];
-                    }
-                const bool l = N::lt(x[0], m);
-                m = N::sel(l, x[0], m);
-                arg = l ? xa[0] : arg;
-            }
-            if (!narrow_w) { // this lane's entries of the side list; an equal candidate wins if its slot is the lower one
-                for (int i = R.sd0; i < R.sd1; i++) {
-                    const uint32_t sv = ov_s[i];
-                    const int t = (int)(sv >> 24);
-                    const T c = N::add(N::load(ring + (sv & 0xffffffu)), N::load(ov_w + (size_t)i * NL * 8));
-                    const bool l = N::lt(c, m) || (!N::lt(m, c) && t < arg);
-                    m = N::sel(l, c, m);
-                    arg = l ? t : arg;
-                }
-            }
-            int e = R.ebase + arg;
-            if (R.maxfollow > 0) {
-                for (int st = 1; st <= R.maxfollow; st <<= 1) {
-                    const int src = (lane + st) & 63;
-                    const int och = __shfl(R.node >= 0 ? R.ch : 0, src);
-                    const T c = N::map32(m, [&](int x) { return __shfl(x, src); });
-                    const int ce = __shfl(e, src);
-                    const bool l = lane + st < 64 && och >= st && N::lt(c, m);
-                    m = N::sel(l, c, m);
-                    e = l ? ce : e;
-                }
-            }
-            if (has_spill) {
-                for (int i = R.sp0; i < R.sp1; i += 2) {
-                    const bool two = i + 1 < R.sp1;
-                    const uint32_t s0 = ov_s[i], s1 = two ? ov_s[i + 1] : INF;
-                    const T w0 = N::load(ov_w + (size_t)i * NL * 8), w1 = N::sel(two, N::load(ov_w + (size_t)(i + 1 < WV_OV ? i + 1 : i) * NL * 8), N::zero());
-                    const T c0 = N::add(N::load(ring + s0), w0), c1 = N::add(N::load(ring + s1), w1);
-                    bool l = N::lt(c0, m);
-                    m = N::sel(l, c0, m);
-                    e = l ? R.spe + (i - R.sp0) : e;
-                    l = N::lt(c1, m);
-                    m = N::sel(l, c1, m);
-                    e = l ? R.spe + (i + 1 - R.sp0) : e;
-                }
-            }
-            bool chg = false, widen = false;
-            if (R.head) {
-                R.pe = e;
-                const T d0 = N::load(ring + R.slot);
-                if (N::lt(m, d0) && !N::unreached(m)) {
-                    N::store(ring + R.slot, m); chg = true;
-                    *(long long *)(rel + R.slot / NL) = to_rel(m, widen);
-                }
-            }
-            wv_sync();
-            const bool any = __ballot(chg) != 0;
-            if (__ballot(widen)) wide = true;
-            return any;
-        };
-        uint64_t again_mask = 0;
-        auto phase64 = [&](Role &R, auto capc, const CW *cw, const uint32_t *cs) -> bool {
-            constexpr int cap = decltype(capc)::value;
-            uint64_t mm = 0x7000000000000000ull;
-            const long long d0 = *(const long long *)(rel + R.slot / NL);
-            uint64_t x[cap];
-#pragma unroll
-            for (int t = 0; t < cap; t++) x[t] = *(const uint64_t *)(rel + cs[t] / NL);
-#pragma unroll
-            for (int t = 0; t < cap; t++) x[t] += (uint64_t)cw[t];
-#pragma unroll
-            for (int w = 1; w < cap; w <<= 1)
-#pragma unroll
-                for (int t = 0; t + w < cap; t += 2 * w) x[t] = min64(x[t], x[t + w]);
-            mm = min64(mm, x[0]);
-            int e = R.ebase + (int)(mm & 15u);
-            long long m = (long long)mm >> 4;
-            if (R.maxfollow > 0 && R.maxfollow <= 4) {
-                for (int q = 0; q < R.maxfollow; q++) {
-                    const long long c = (long long)(((uint64_t)(uint32_t)wv_next_self((int)((uint64_t)m >> 32)) << 32) | (uint32_t)wv_next_self((int)m));
-                    const int ce = wv_next_self(e);
-                    const bool l = R.nextf && c < m;
-                    m = l ? c : m;
-                    e = l ? ce : e;
-                }
-            } else if (R.maxfollow > 0) {
-                for (int st = 1; st <= R.maxfollow; st <<= 1) {
-                    const int src = (lane + st) & 63;
-                    const int och = __shfl(R.node >= 0 ? R.ch : 0, src);
-                    const long long c = (long long)(((uint64_t)(uint32_t)__shfl((int)((uint64_t)m >> 32), src) << 32) | (uint32_t)__shfl((int)m, src));
-                    const int ce = __shfl(e, src);
-                    const bool l = lane + st < 64 && och >= st && c < m;
-                    m = l ? c : m;
-                    e = l ? ce : e;
-                }
-            }
-            if (has_spill) {
-                for (int i = R.sp0; i < R.sp1; i++) {
-                    const long long c0 = (long long)((*(const uint64_t *)(ov_w + (size_t)i * NL * 8) << 4) + *(const uint64_t *)(rel + ov_s[i] / NL)) >> 4;
-                    const bool l = c0 < m;
-                    m = l ? c0 : m;
-                    e = l ? R.spe + (i - R.sp0) : e;
-                }
-            }
-            const bool again = R.head && m >= WV_BIAS + WV_NARROW && m < WV_BIAS + WV_VAL_BIG - (1ll << 52);
-            const bool store = R.head && m < WV_BIAS + WV_NARROW && m < (d0 >> 4);
-            const long long v = m - WV_BIAS;
-            const bool fits = v > -WV_NARROW;
-            R.pe = R.head ? e : R.pe;
-            if (store) {
-                N::store(ring + R.slot, N::add(base, N::from_i64(v)));
-                *(long long *)(rel + R.slot / NL) = fits ? (long long)((uint64_t)m << 4) : WV_REL_WIDE;
-            }
-            const uint64_t cm = __ballot(store);
-            again_mask = __ballot(again);
-            wv_sync();
-            if (cm && __ballot(store && !fits)) wide = true;
-            return cm != 0;
-        };
-        {
-            int inner = 0;
+        // ---- iterate to the fixed point ----
 #ifdef DUO_PROFILE_AB
-            long long tmark_ab = wall_clock64();
+        S.prof.tmark_ab = wall_clock64();
 #endif
-            for (int ph = 0;; ph ^= 1) {
-                bool chg = false;
-                const bool n64 = narrow_w && !wide;
-                if (n64) chg = ph ? phase64(B, std::integral_constant<int, CB>(), cwB, csB) : phase64(A, std::integral_constant<int, CA>(), cwA, csA);
-                const bool exact = !n64 || again_mask != 0;
-                if (exact) chg |= ph ? phase(B, std::integral_constant<int, CB>(), cwB, csB) : phase(A, std::integral_constant<int, CA>(), cwA, csA);
-                phases++;
-#ifdef DUO_PROFILE_AB
-                { const long long t_ = wall_clock64(); tab[ph ? 1 : 0] += t_ - tmark_ab; tmark_ab = t_; nab[ph ? 1 : 0]++; if (exact) nab[2]++; }
-#endif
-                if (!chg && (ph == 1 || inner > 0)) break;
-                if (++inner > 4 * WV_WIN + 16) { fail = true; fail_code = 3; break; }
-            }
-            if (fail) break;
-        }
+        if (!S.iterate(A, cwA, csA, B, cwB, csB)) { fail = true; fail_code = 3; break; }
         DUO_TICK(2)
         // the phases of this pack are over: the spill / side list may be rewritten
         if (lane == 0) duo_poke(&mb[DUO_C_DONE], (uint32_t)seq);
 
         // ---- results of the advanced nodes (stored at the top of the next window) ----
-        pend_dv = v0 + lane < va ? v0 + lane : -1;
-        pend_d = N::load(ring + (size_t)((v0 + lane) & (WV_RING - 1)) * NL * 8);
-        auto parents = [&](Role &R, int &pv, int &pe) {
-            pv = (R.head && v0 + R.node < va) ? v0 + R.node : -1;
-            pe = (pv >= 0 && pv != SRC && R.pe >= 0 && !N::unreached(N::load(ring + (R.head ? R.slot : ZERO)))) ? (int)(e0 + (uint32_t)R.pe) : -1;
-        };
-        parents(A, pend_av, pend_ae);
-        parents(B, pend_bv, pend_be);
+        S.keep_results(A, B, v0, va, e0, SRC);
 
         // ---- did a close node that final nodes may depend on improve?  then step back (k_sssp_wave) ----
-        const bool trig = A.head && A.watch && N::lt(N::load(ring + A.slot), a_old);
+        const bool trig = S.watch_improved(A, a_old);
         const uint64_t tm = __ballot(trig);
         if (tm) {
-            if (++rollbacks > 4 * (V / WV_ADV + 4)) { fail = true; fail_code = 4; break; }
-            uint32_t mr = trig ? b.mreach[4 * (size_t)meta->node_off + (size_t)(v0 + A.node)] : ~0u;
-            for (int st = 32; st >= 1; st >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)mr, st); mr = o < mr ? o : mr; }
-            int rr = (int)mr < v0 ? (int)mr : v0;
-            if (meta->dense & 2) { // the table is incomplete for this contig: the first node less than 500 bp left of the improved one
-                const DNode *nd = b.node + meta->node_off;
-                const int tl = __ffsll((long long)tm) - 1;
-                const int xpos = nd[v0 + __shfl(A.node, tl)].pos;
-                rr = v0;
-                while (rr > 0) {
-                    const int q = rr - 1 - lane;
-                    const bool aff = q >= 0 && nd[q].pos > xpos - 500;
-                    const uint64_t am = __ballot(aff);
-                    if (am == ~0ull) { rr -= 64; continue; }
-                    rr -= am ? (__ffsll((long long)~am) - 1) : 0;
-                    break;
-                }
-            }
-            if (rr < seg_ns) rr = seg_ns;
-            pend_rr = rr;
+            if (++S.rollbacks > 4 * (V / WV_ADV + 4)) { fail = true; fail_code = 4; break; }
+            pend_rr = S.step_back_node(A, trig, tm, v0, b, meta, seg_ns);
             continue;
         }
         if (last) break;
     }
     if (lane == 0) duo_poke(&mb[DUO_C_EXIT], 1u);
     if (abandoned) return;
-    flush_results();
+    S.flush_results();
     if constexpr (SEG) {
         if (lane == 0) {
-            seg_rec[1] = fail ? (fail_code ? fail_code : 7) : 0; atomicAdd(&meta->sssp_iters, phases);
-            seg_rec[4] = (int32_t)(wall_clock64() - seg_t0); seg_rec[5] = phases; seg_rec[6] = seq; seg_rec[7] = rollbacks;
+            seg_rec[1] = fail ? (fail_code ? fail_code : 7) : 0; atomicAdd(&meta->sssp_iters, S.phases);
+            seg_rec[4] = (int32_t)(wall_clock64() - seg_t0); seg_rec[5] = S.phases; seg_rec[6] = seq; seg_rec[7] = S.rollbacks;
             if (fail && fail_code == 5) atomicAdd(&b.tot->plan_timeouts, 1); // (the planner it follows made no progress: the host stops launching solvers beside planners on this context)
         }
         return;
     }
     if (fail) { // hand the contig to the workgroup kernel
-        if (lane == 0) {
-            if (fail_code == 5) { if (atomicCAS(&meta->sssp_mode, D::MODE, meta->sssp_fb) == D::MODE) { meta->sssp_why = 5; atomicAdd(&b.tot->plan_timeouts, 1); } }
-            else if (STREAM) { if (atomicCAS(&meta->sssp_mode, D::MODE, meta->sssp_fb) == D::MODE) meta->sssp_why = fail_code; }
-            else { meta->sssp_mode = meta->sssp_fb; meta->sssp_why = fail_code; }
-        }
+        if (lane == 0) wv_hand_back(meta, b.tot, D::MODE, fail_code, STREAM);
         return;
     }
-    if (lane == 0) {
-        meta->sweeps = 1 + rollbacks;
 #ifdef DUO_PROFILE
-        DUO_TICK(3)
-        for (int q_ = 0; q_ < 4; q_++) meta->pmax[q_] = (uint32_t)tp[q_];
-        meta->bg[6] = (uint32_t)(wall_clock64() - t_begin); meta->bg[7] = (uint32_t)seq;
+    if (lane == 0) {
+        const DuoProf &P = S.prof;
+        S.prof.tick(3);
+        for (int q_ = 0; q_ < 4; q_++) meta->pmax[q_] = (uint32_t)P.tp[q_];
+        meta->bg[6] = (uint32_t)(wall_clock64() - P.t_begin); meta->bg[7] = (uint32_t)seq;
 #ifdef DUO_PROFILE_AB
-        meta->bg[0] = (uint32_t)tab[0]; meta->bg[1] = (uint32_t)tab[1]; meta->bg[2] = (uint32_t)nab[0]; meta->bg[3] = (uint32_t)nab[1]; meta->bg[4] = (uint32_t)nab[2];
+        meta->bg[0] = (uint32_t)P.tab[0]; meta->bg[1] = (uint32_t)P.tab[1]; meta->bg[2] = (uint32_t)P.nab[0]; meta->bg[3] = (uint32_t)P.nab[1]; meta->bg[4] = (uint32_t)P.nab[2];
 #endif
-#endif
-        meta->sssp_iters = phases;
-        meta->n_genes = 0; meta->gene_off = 0;
-        if (N::unreached(N::load(ring + (size_t)((V - 1) & (WV_RING - 1)) * NL * 8))) { meta->status = PHX_S_NOPATH; meta->n_path = 0; }
-        else meta->n_path = -2; // distances and parent edges are final; not walked yet (k_inorder)
     }
+#endif
+    S.finish(meta, V);
 }

@@ -260,30 +260,30 @@ __device__ __forceinline__ int wv_max(int x) {
     return __builtin_amdgcn_readlane((int)v, 63);
 }
 
-// A cached in-edge weight.  128-bit contigs keep it at the ring's width (two registers more than the 64-bit form, and a folded
-// source distance fits).  Wider contigs keep 64 bits — NL is then a property of the ring alone — and move the few in-edges that do
-// not fit (|W| >= 2^51, or a final distance folded in) to the side list in LDS, see gather.
-template <int NL> struct WvCw {
+// A cached in-edge weight, in one of two forms.  WvCw<2>, the form of k_sssp_wave's 128-bit contigs, keeps it at the ring's width (two registers
+// more per in-edge, and a folded source distance fits).  WvCw64 keeps 64 bits at any ring width — the wider contigs of k_sssp_wave, and
+// k_sssp_duo — and is a form with a SIDE list: the few in-edges that do not fit (|W| >= 2^51, or a final distance folded in) go to the side list
+// in LDS (k_sssp_wave: gather; k_sssp_duo: the feeder's side).
+struct WvCw64 {
     typedef long long CW;
+    static constexpr bool SIDE = true;
     static __device__ __forceinline__ CW from_i64(long long v) { return v; }
-    static __device__ __forceinline__ typename WvNum<NL>::T to_T(CW c) { return WvNum<NL>::from_i64(c); }
+    template <class N> static __device__ __forceinline__ typename N::T to_T(CW c) { return N::from_i64(c); }
     static __device__ __forceinline__ uint64_t lo(CW c) { return (uint64_t)c; }
     static __device__ __forceinline__ CW with_lo(CW, uint64_t l) { return (long long)l; }
 };
+template <int NL> struct WvCw : WvCw64 {};
 template <> struct WvCw<2> {
     typedef Wv2 CW;
+    static constexpr bool SIDE = false;
     static __device__ __forceinline__ CW from_i64(long long v) { return WvNum<2>::from_i64(v); }
-    static __device__ __forceinline__ Wv2 to_T(CW c) { return c; }
+    template <class N> static __device__ __forceinline__ Wv2 to_T(CW c) { return c; }
     static __device__ __forceinline__ uint64_t lo(CW c) { return c.lo; }
     static __device__ __forceinline__ CW with_lo(CW c, uint64_t l) { c.lo = l; return c; }
 };
-// the lanes of one phase: a lane works on (node, chunk) and keeps that chunk's in-edges in registers
-template <int NL, int CAP_>
-struct WvRole {
-    static constexpr int CAP = CAP_;
-    typename WvCw<NL>::CW cw[CAP];
-    uint32_t cs[CAP];   // byte offset of the source's distance in the ring
-    int sd0, sd1;       // (NL > 2) this lane's entries of the side list
+// the lanes of one phase: a lane works on (node, chunk of its in-edges)
+struct WvLane {
+    int sd0, sd1;       // (C::SIDE) this lane's entries of the side list
     int cnt;            // cached in-edges of this lane
     int ebase;          // window-relative index of this lane's first in-edge
     int node;           // window-relative node index, -1: lane idle in this phase
@@ -299,6 +299,15 @@ struct WvRole {
     int maxcnt;         // largest cnt of any lane (wave-uniform)
     int maxfollow;      // wave-uniform
 };
+// ... and keeps that chunk's in-edges in registers (C: the form of a cached weight).  k_sssp_wave's lanes are WvRoles; k_sssp_duo keeps
+// a WvLane and the two arrays beside it: as members of one object they cost its streamed instantiations 136-160 bytes of scratch per
+// lane (12 -> 172 / 148), so the phases of WvSolver take (lane, cw, cs)
+template <class C, int CAP_>
+struct WvRole : WvLane {
+    static constexpr int CAP = CAP_;
+    typename C::CW cw[CAP]; // cached weights,
+    uint32_t cs[CAP];       //   byte offsets of their sources' distances in the ring
+};
 // A lane's record as k_wave_plan stores it (WIN_ROLES per window: phase A lanes, then phase B lanes):
 //   x: node 0..6 | chunk 7..12 | helper lanes 13..18 | cached in-edges 19..23 | active 24 | watch 25
 //   y: first in-edge 0..10 | first spill entry 11..20 | spill entries 21..30
@@ -308,6 +317,18 @@ __device__ __forceinline__ uint2 wv_role_pack(bool act, int node, int ch, int nf
     r.y = !act ? 0u : ((uint32_t)ebase | (((uint32_t)sp0 & 1023u) << 11) | (((uint32_t)spn & 1023u) << 21));
     return r;
 }
+__device__ __forceinline__ int wv_role_node(uint2 rc) { return (int)(rc.x & 127u); }
+__device__ __forceinline__ int wv_role_ch(uint2 rc) { return (int)((rc.x >> 7) & 63u); }
+__device__ __forceinline__ int wv_role_nfollow(uint2 rc) { return (int)((rc.x >> 13) & 63u); }
+__device__ __forceinline__ int wv_role_cnt(uint2 rc) { return (int)((rc.x >> 19) & 31u); }
+__device__ __forceinline__ bool wv_role_act(uint2 rc) { return (rc.x >> 24) & 1u; }
+__device__ __forceinline__ bool wv_role_watch(uint2 rc) { return (rc.x >> 25) & 1u; }
+__device__ __forceinline__ int wv_role_ebase(uint2 rc) { return (int)(rc.y & 2047u); }
+__device__ __forceinline__ int wv_role_sp0(uint2 rc) { return (int)((rc.y >> 11) & 1023u); }
+__device__ __forceinline__ int wv_role_spn(uint2 rc) { return (int)((rc.y >> 21) & 1023u); }
+// a window record's per-phase summary word (k_wave_plan: lanes in use | largest cnt << 8 | most helper lanes << 16)
+__device__ __forceinline__ int wv_sum_maxcnt(uint32_t summary) { return (int)((summary >> 8) & 255u); }
+__device__ __forceinline__ int wv_sum_maxfollow(uint32_t summary) { return (int)((summary >> 16) & 255u); }
 
 // ------------------------------------------------------------------------------------------------
 // k_wave_plan: the part of k_sssp_wave's sweep that does not depend on distances: the sequence of windows and, per
@@ -586,6 +607,412 @@ __global__ __launch_bounds__(64) void k_wave_plan(DBatch b) {
     if (pub) { __builtin_amdgcn_s_waitcnt(0); publish(k | WV_PLAN_DONE); }
 }
 
+// ------------------------------------------------------------------------------------------------
+// WvSolver: the solver half of a window sweep — everything between "a window's lanes have their in-edges" and "its results are
+// stored" — once, for k_sssp_wave (which also prepares every window itself) and for the solver wavefront of k_sssp_duo (whose
+// feeder prepares them).  N: the ring's integers, C: the form of a cached weight, PARENTS: parent edges are stored (not for the
+// segments of phx_sssp_seg.inc), PROF: the profile hook.  All members are inlined into the one wavefront that owns the object;
+// the kernels keep what differs between them: where a window's records and in-edges come from, and who is told about a step-back.
+
+// polls a planner's progress word until windows [0, need) are published or it has finished.  0: go on; 1: the planner gave the contig
+// up (it has redirected it itself: leave); 2: no progress for >= 20 ms (the planner is not running beside this kernel: hand the
+// contig on rather than hang)
+__device__ __forceinline__ int wv_wait_plan(const int *word, int need, int &n_win, bool &plan_done) {
+    for (int spins = 0;; spins++) {
+        const int p = __hip_atomic_load(word, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+        if (p < 0) return 1;
+        n_win = p & (WV_PLAN_DONE - 1);
+        plan_done = (p & WV_PLAN_DONE) != 0;
+        if (plan_done || n_win >= need) return 0;
+        if (spins > WV_PLAN_SPINS) return 2;
+        __builtin_amdgcn_s_sleep(4);
+    }
+}
+// minimum of two positive 64-bit patterns (ordered like positive normal doubles)
+__device__ __forceinline__ uint64_t wv_min64(uint64_t a, uint64_t b) { uint64_t r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+// the profile hook of normal builds: nothing (-DWV_PROFILE / -DDUO_PROFILE builds put their clocks and counters behind the same names)
+struct WvNoProf {
+    __device__ __forceinline__ void tick(int) {}                        // a point between the parts of a window
+    __device__ __forceinline__ void fine(int) {}                        // a point inside a phase
+    __device__ __forceinline__ void rebase() {}                         // the base has moved
+    __device__ __forceinline__ void phase_done(int, bool, bool, int) {} // after a phase: A / B, ran in 64 bits, ran exact, its helper lanes
+};
+template <class N, class C, int RING, int OV, bool PARENTS, class PROF>
+struct WvSolver {
+    typedef typename N::T T;
+    static constexpr int NL = (int)(sizeof(T) / 8);
+    static constexpr uint32_t ZERO = (uint32_t)RING * NL * 8, INF = (uint32_t)(RING + 1) * NL * 8; // ring offsets of the constant 0 (source) and "unreached"
+    uint8_t *ring, *rel;  // exact distances of the last RING nodes; the same relative to `base` as 64-bit entries (slot i at byte 8 i)
+    uint8_t *ov_w;        // spill (+ side) list: weight,
+    uint32_t *ov_s;       //   ring offset of the source (| slot << 24 on the side list)
+    uint64_t *gdist;      // where distances go
+    int32_t *gpe;         // (PARENTS) where parent edges go (contig-relative, -1: none)
+    int lane;
+    T base;
+    bool wide;            // a distance far below `base` was stored: exact phases until the base has moved (next window)
+    bool has_spill, narrow_w; // of the window (uniform): some node has entries on the spill list; every cached weight is (w << 4) | slot, |w| < 2^51
+    uint64_t again_mask;  // heads of the last 64-bit phase that need the exact ring, see phase64
+    int phases, rollbacks;
+    int pend_dv, pend_av, pend_bv, pend_ae, pend_be; // results of the last window, not yet stored
+    T pend_d;
+    PROF prof;
+
+    __device__ __forceinline__ void init(uint8_t *ring_, uint8_t *rel_, uint8_t *ov_w_, uint32_t *ov_s_, uint64_t *gdist_, int32_t *gpe_, int lane_) {
+        ring = ring_; rel = rel_; ov_w = ov_w_; ov_s = ov_s_; gdist = gdist_; gpe = gpe_; lane = lane_;
+        base = N::zero();
+        wide = false; has_spill = false; narrow_w = false; again_mask = 0;
+        phases = 0; rollbacks = 0;
+        pend_dv = -1; pend_av = -1; pend_bv = -1; pend_ae = -1; pend_be = -1;
+        pend_d = N::zero();
+        for (int i = lane; i < RING; i += 64) { N::store(ring + (size_t)i * NL * 8, N::big()); *(long long *)(rel + (size_t)i * 8) = WV_REL_BIG; }
+        if (lane == 0) {
+            N::store(ring + ZERO, N::zero()); *(long long *)(rel + ZERO / NL) = WV_REL(0);
+            N::store(ring + INF, N::big()); *(long long *)(rel + INF / NL) = WV_REL_BIG;
+        }
+    }
+    // d (real or unreached) -> its entry in the relative ring; low: d lies more than 2^60 below base (the base must move)
+    __device__ __forceinline__ long long to_rel(T d, bool &low) const {
+        const T x = N::sub(d, base);
+        const long long xl = (long long)N::lo64(x);
+        const bool fits = N::is_i64(x) && xl < WV_NARROW && xl > -WV_NARROW;
+        low = !fits && N::negative(x);
+        return N::unreached(d) ? WV_REL_BIG : (fits ? WV_REL(xl) : WV_REL_WIDE);
+    }
+    // top of a window, once its nodes have entered the ring: if a phase has asked for it, move the base to the lowest real distance in
+    // the ring (and the source's 0): nothing lies below it afterwards
+    __device__ __forceinline__ void move_base() {
+        if (!wide) return;
+        T mn = N::load(ring + ZERO);
+        for (int i = lane; i < RING; i += 64) { const T d = N::load(ring + (size_t)i * NL * 8); mn = N::sel(N::lt(d, mn), d, mn); }
+        for (int st = 32; st >= 1; st >>= 1) {
+            const T c = N::map32(mn, [&](int w) { return __shfl_xor(w, st); });
+            mn = N::sel(N::lt(c, mn), c, mn);
+        }
+        base = mn;
+        prof.rebase();
+        bool low;
+        for (int i = lane; i < RING + 1; i += 64) *(long long *)(rel + (size_t)i * 8) = to_rel(N::load(ring + (size_t)i * NL * 8), low);
+        wide = false;
+        wv_sync();
+    }
+    // the lane of a phase (chunks of `cap` in-edges) from its record (k_wave_plan) and the window's summary word; its cached in-edges are the kernel's to fill
+    __device__ __forceinline__ void decode(WvLane &R, const uint2 rc, const uint32_t summary, const int v0, const int cap) const {
+        const bool act = wv_role_act(rc);
+        const int o_j = wv_role_node(rc);
+        R.node = act ? o_j : -1;
+        R.ch = wv_role_ch(rc);
+        R.head = act && R.ch == 0;
+        R.nextf = wv_next(act ? R.ch : 0) >= 1;
+        R.watch = wv_role_watch(rc);
+        R.nfollow = wv_role_nfollow(rc);
+        R.cnt = wv_role_cnt(rc);
+        R.ebase = wv_role_ebase(rc);
+        R.sp0 = wv_role_sp0(rc);
+        R.sp1 = R.sp0 + wv_role_spn(rc);
+        R.spe = R.ebase + (R.nfollow + 1) * cap;
+        R.slot = (uint32_t)((v0 + o_j) & (RING - 1)) * NL * 8;
+        R.pe = -1;
+        R.maxcnt = wv_sum_maxcnt(summary);
+        R.maxfollow = wv_sum_maxfollow(summary);
+        R.sd0 = 0; R.sd1 = 0;
+    }
+    // one phase on the exact ring: every node of the phase takes the minimum over all its in-edges
+    // (phase and phase64 are plain `inline`, like the lambdas they replace: the optimiser then simplifies each on its own before it inlines it into
+    //  its one call site.  Forced in first, the index array `xa` of the group minimum turns into chains of selects: +3 % instructions in all eleven kernels)
+    template <int cap>
+    __device__ inline bool phase(WvLane &R, const typename C::CW *cw, const uint32_t *cs) {
+        T m = N::top();
+        int arg = 0;
+        constexpr int G = cap < 8 ? cap : (NL > 2 ? 4 : 8); // distances are fetched G at a time: one LDS round trip per group
+#pragma unroll
+        for (int t0 = 0; t0 < cap; t0 += G) {
+            if (t0 >= R.maxcnt) break;
+            T x[G];
+            int xa[G];
+#pragma unroll
+            for (int g = 0; g < G; g++) x[g] = N::load(ring + cs[t0 + g]);
+#pragma unroll
+            for (int g = 0; g < G; g++) xa[g] = t0 + g;
+            if (narrow_w) { // (uniform) the cached weights are in the form of a narrow window
+#pragma unroll
+                for (int g = 0; g < G; g++) {
+                    uint64_t lo = C::lo(cw[t0 + g]);
+                    asm volatile("" : "+v"(lo)); // (keeps the shift inside this rare phase: hoisted out of the phase loop it costs every window)
+                    x[g] = N::add(x[g], N::from_i64((long long)lo >> 4));
+                }
+            } else {
+#pragma unroll
+                for (int g = 0; g < G; g++) x[g] = N::add(x[g], C::template to_T<N>(cw[t0 + g]));
+            }
+            // minimum of the group as a tree (independent compares); ties keep the lower index
+#pragma unroll
+            for (int w = 1; w < G; w <<= 1)
+#pragma unroll
+                for (int g = 0; g + w < G; g += 2 * w) {
+                    const bool l = N::lt(x[g + w], x[g]);
+                    x[g] = N::sel(l, x[g + w], x[g]);
+                    xa[g] = l ? xa[g + w] : xa[g];
+                }
+            const bool l = N::lt(x[0], m);
+            m = N::sel(l, x[0], m);
+            arg = l ? xa[0] : arg;
+        }
+        if constexpr (C::SIDE) {
+            if (!narrow_w) { // (uniform) this lane's entries of the side list; an equal candidate wins if its slot is the lower one
+                for (int i = R.sd0; i < R.sd1; i++) {
+                    const uint32_t sv = ov_s[i];
+                    const int t = (int)(sv >> 24);
+                    const T c = N::add(N::load(ring + (sv & 0xffffffu)), N::load(ov_w + (size_t)i * NL * 8));
+                    const bool l = N::lt(c, m) || (!N::lt(m, c) && t < arg);
+                    m = N::sel(l, c, m);
+                    arg = l ? t : arg;
+                }
+            }
+        }
+        prof.fine(6);
+        int e = R.ebase + arg;
+        if (R.maxfollow > 0) {
+            // segmented minimum over a head and the helper lanes that follow it: log2 steps, each lane takes the
+            // value `st` lanes to its right if that lane belongs to the same node (its chunk index is >= st);
+            // the left operand keeps ties, so the lowest in-edge index survives
+            for (int st = 1; st <= R.maxfollow; st <<= 1) {
+                const int src = (lane + st) & 63;
+                const int och = __shfl(R.node >= 0 ? R.ch : 0, src);
+                const T c = N::map32(m, [&](int w) { return __shfl(w, src); });
+                const int ce = __shfl(e, src);
+                const bool l = lane + st < 64 && och >= st && N::lt(c, m);
+                m = N::sel(l, c, m);
+                e = l ? ce : e;
+            }
+        }
+        prof.fine(7);
+        bool coop = false; // this lane's spill entries were taken by the whole wavefront (below)
+        if constexpr (NL >= 8) {
+            // A stop node behind a 9000-codon ORF collects an in-edge from every in-frame start (~450): beyond its 63 helper lanes ~200 entries sit on the
+            // spill list, and one lane walked them two at a time in every close-node phase of the window (~8 us each).  Lists of more than 8
+            // entries are reduced by all 64 lanes instead: a strided pass, then a butterfly on (value, edge index) — the lowest index among equals, as
+            // the walk in order finds it.
+            if (has_spill) {
+                uint64_t bigm = __ballot(R.head && R.sp1 - R.sp0 > 8);
+                while (bigm) {
+                    const int Ln = __ffsll((long long)bigm) - 1;
+                    bigm &= bigm - 1;
+                    const int s0 = __builtin_amdgcn_readlane(R.sp0, Ln), s1 = __builtin_amdgcn_readlane(R.sp1, Ln), spe0 = __builtin_amdgcn_readlane(R.spe, Ln);
+                    T mm = N::top();
+                    int ee = 0x7fffffff;
+                    for (int i = s0 + lane; i < s1; i += 64) {
+                        const T c = N::add(N::load(ring + ov_s[i]), N::load(ov_w + (size_t)i * NL * 8));
+                        const bool l = N::lt(c, mm);
+                        mm = N::sel(l, c, mm);
+                        ee = l ? spe0 + (i - s0) : ee;
+                    }
+                    for (int st = 32; st >= 1; st >>= 1) {
+                        const T c = N::map32(mm, [&](int w) { return __shfl_xor(w, st); });
+                        const int ce = __shfl_xor(ee, st);
+                        const bool l = N::lt(c, mm) || (!N::lt(mm, c) && ce < ee);
+                        mm = N::sel(l, c, mm);
+                        ee = l ? ce : ee;
+                    }
+                    if (lane == Ln) { const bool l = N::lt(mm, m); m = N::sel(l, mm, m); e = l ? ee : e; coop = true; }
+                }
+            }
+        }
+        if (has_spill) {
+            for (int i = coop ? R.sp1 : R.sp0; i < R.sp1; i += 2) { // spill list, two entries per pair of LDS round trips
+                const bool two = i + 1 < R.sp1;
+                const uint32_t s0 = ov_s[i], s1 = two ? ov_s[i + 1] : INF;
+                const T w0 = N::load(ov_w + (size_t)i * NL * 8), w1 = N::sel(two, N::load(ov_w + (size_t)(i + 1 < OV ? i + 1 : i) * NL * 8), N::zero());
+                const T c0 = N::add(N::load(ring + s0), w0), c1 = N::add(N::load(ring + s1), w1);
+                bool l = N::lt(c0, m);
+                m = N::sel(l, c0, m);
+                e = l ? R.spe + (i - R.sp0) : e;
+                l = N::lt(c1, m);
+                m = N::sel(l, c1, m);
+                e = l ? R.spe + (i + 1 - R.sp0) : e;
+            }
+        }
+        prof.fine(8);
+        bool chg = false, widen = false;
+        if (R.head) {
+            R.pe = e;
+            const T d0 = N::load(ring + R.slot);
+            // (a candidate over an unreached source is not a distance: the ring holds real distances or exactly big())
+            if (N::lt(m, d0) && !N::unreached(m)) {
+                N::store(ring + R.slot, m); chg = true;
+                *(long long *)(rel + R.slot / NL) = to_rel(m, widen);
+            }
+        }
+        wv_sync(); // the next phase reads what this one wrote
+        const bool any = __ballot(chg) != 0;
+        if (__ballot(widen)) wide = true;
+        prof.fine(9);
+        return any;
+    }
+    // The same phase on the relative ring, for windows whose cached weights are all narrow (|w| < 2^51) while no distance
+    // lies far below the base.  A candidate is entry + (w << 4) + slot: one 64-bit shift-add; the entries are positive and
+    // below 2^63, so as bit patterns they are ordered like positive normal doubles and the minimum of a lane's
+    // candidates is a chain of v_min_f64 - the winning slot rides in the low 4 bits, ties go to the lower slot.
+    // A candidate over an unreached source is >= WV_VAL_BIG - 2^51 and never stored; one over a WV_REL_WIDE source (a real
+    // distance more than 2^55 above the base) loses against every narrow candidate, and a node that has none but has such
+    // a source makes the phase run again on the exact ring (`again_mask`).  Otherwise: the same numbers.
+    template <int cap>
+    __device__ inline bool phase64(WvLane &R, const typename C::CW *cw, const uint32_t *cs) { // true: some distance improved
+        uint64_t mm = 0x7000000000000000ull;
+        // every load of the phase is in flight before the first use (unused slots point at the constant "unreached" entry)
+        const long long d0 = *(const long long *)(rel + R.slot / NL);
+        uint64_t x[cap];
+#pragma unroll
+        for (int t = 0; t < cap; t++) x[t] = *(const uint64_t *)(rel + cs[t] / NL);
+#pragma unroll
+        for (int t = 0; t < cap; t++) x[t] += C::lo(cw[t]);
+#pragma unroll
+        for (int w = 1; w < cap; w <<= 1)
+#pragma unroll
+            for (int t = 0; t + w < cap; t += 2 * w) x[t] = wv_min64(x[t], x[t + w]);
+        mm = wv_min64(mm, x[0]);
+        prof.fine(6);
+        int e = R.ebase + (int)(mm & 15u);
+        long long m = (long long)mm >> 4; // relative value + WV_BIAS
+        if (R.maxfollow > 0 && R.maxfollow <= 4) {
+            // few helper lanes: one DPP shift (lane i <- lane i+1) per helper instead of log-steps over ds_bpermute
+            for (int q = 0; q < R.maxfollow; q++) {
+                const long long c = (long long)(((uint64_t)(uint32_t)wv_next_self((int)((uint64_t)m >> 32)) << 32) | (uint32_t)wv_next_self((int)m));
+                const int ce = wv_next_self(e);
+                const bool l = R.nextf && c < m;
+                m = l ? c : m;
+                e = l ? ce : e;
+            }
+        } else if (R.maxfollow > 0) {
+            for (int st = 1; st <= R.maxfollow; st <<= 1) {
+                const int src = (lane + st) & 63;
+                const int och = __shfl(R.node >= 0 ? R.ch : 0, src);
+                const long long c = (long long)(((uint64_t)(uint32_t)__shfl((int)((uint64_t)m >> 32), src) << 32) | (uint32_t)__shfl((int)m, src));
+                const int ce = __shfl(e, src);
+                const bool l = lane + st < 64 && och >= st && c < m;
+                m = l ? c : m;
+                e = l ? ce : e;
+            }
+        }
+        prof.fine(7);
+        if (has_spill) {
+            for (int i = R.sp0; i < R.sp1; i++) {
+                const long long c0 = (long long)((*(const uint64_t *)(ov_w + (size_t)i * NL * 8) << 4) + *(const uint64_t *)(rel + ov_s[i] / NL)) >> 4;
+                const bool l = c0 < m;
+                m = l ? c0 : m;
+                e = l ? R.spe + (i - R.sp0) : e;
+            }
+        }
+        prof.fine(8);
+        // a head whose best candidate sits on a wide source, or is itself 2^55 or more above the base (its slot may hold
+        // a wide distance it cannot be compared with here): the phase is run again on the exact ring; what the other
+        // heads store meanwhile are valid improvements
+        const bool again = R.head && m >= WV_BIAS + WV_NARROW && m < WV_BIAS + WV_VAL_BIG - (1ll << 52);
+        // d0 real: compare; d0 unreached or wide (more than 2^55 above the base): any real candidate is lower.
+        // (lane predicates and votes straight from the compares: no flags carried out of a divergent region)
+        const bool store = R.head && m < WV_BIAS + WV_NARROW && m < (d0 >> 4);
+        const long long v = m - WV_BIAS;
+        const bool fits = v > -WV_NARROW;
+        R.pe = R.head ? e : R.pe;
+        if (store) {
+            N::store(ring + R.slot, N::add(base, N::from_i64(v)));
+            *(long long *)(rel + R.slot / NL) = fits ? (long long)((uint64_t)m << 4) : WV_REL_WIDE;
+        }
+        const uint64_t cm = __ballot(store);
+        again_mask = __ballot(again);
+        wv_sync();
+        if (cm && __ballot(store && !fits)) wide = true;
+        prof.fine(9);
+        return cm != 0;
+    }
+    // a window to its fixed point: phase A (close nodes), phase B (open nodes), ... until a phase changes nothing; in 64 bits while the
+    // window's weights are narrow and no distance lies far below the base.  false: no convergence (sssp_why 3)
+    template <int CA, int CB>
+    __device__ __forceinline__ bool iterate(WvLane &A, const typename C::CW (&cwA)[CA], const uint32_t (&csA)[CA], WvLane &B, const typename C::CW (&cwB)[CB], const uint32_t (&csB)[CB]) {
+        again_mask = 0;
+        int inner = 0;
+        for (int ph = 0;; ph ^= 1) {
+            bool chg = false;
+            const bool n64 = narrow_w && !wide;
+            if (n64) chg = ph ? phase64<CB>(B, cwB, csB) : phase64<CA>(A, cwA, csA);
+            const bool exact = !n64 || again_mask != 0; // run the exact phase
+            if (exact) chg |= ph ? phase<CB>(B, cwB, csB) : phase<CA>(A, cwA, csA);
+            prof.phase_done(ph, n64, exact, ph ? B.maxfollow : A.maxfollow);
+            phases++;
+            if (!chg && (ph == 1 || inner > 0)) return true;
+            if (++inner > 4 * WV_WIN + 16) return false;
+        }
+    }
+    // results of the advanced nodes [v0, va): distance, parent edge (contig-relative, the convention of k_sssp / k_sssp_lds; the walk
+    // at the end resolves it).  Kept in registers; flush_results stores them behind the next window's wait, when their stores cost nothing.
+    __device__ __forceinline__ void keep_results(const WvLane &A, const WvLane &B, const int v0, const int va, const uint32_t e0, const int SRC) {
+        pend_dv = v0 + lane < va ? v0 + lane : -1;
+        pend_d = N::load(ring + (size_t)((v0 + lane) & (RING - 1)) * NL * 8);
+        if constexpr (PARENTS) {
+            auto parents = [&](const auto &R, int &pv, int &pe) {
+                pv = (R.head && v0 + R.node < va) ? v0 + R.node : -1;
+                pe = (pv >= 0 && pv != SRC && R.pe >= 0 && !N::unreached(N::load(ring + (R.head ? R.slot : ZERO)))) ? (int)(e0 + (uint32_t)R.pe) : -1;
+            };
+            parents(A, pend_av, pend_ae);
+            parents(B, pend_bv, pend_be);
+        }
+    }
+    __device__ __forceinline__ void flush_results() {
+        if (pend_dv >= 0) N::store(gdist + (size_t)pend_dv * NL, pend_d);
+        if (PARENTS && pend_av >= 0) gpe[pend_av] = pend_ae;
+        if (PARENTS && pend_bv >= 0) gpe[pend_bv] = pend_be;
+        pend_dv = -1; pend_av = -1; pend_bv = -1;
+    }
+    // did a close node that final nodes may depend on improve in this window?  (a_old: its distance before the phases)  Then the sweep steps back
+    __device__ __forceinline__ bool watch_improved(const WvLane &A, const T a_old) const {
+#ifdef WV_NO_WATCH // development: how much the step-backs cost (results are then wrong where one was needed)
+        return false;
+#else
+        return A.head && A.watch && N::lt(N::load(ring + A.slot), a_old);
+#endif
+    }
+    // ... to this node, at least `lo`: the lowest final node an overlap edge out of an improved, watched node ends in (k_edges_scan recorded it)
+    __device__ __forceinline__ int step_back_node(const WvLane &A, const bool trig, const uint64_t tm, const int v0, const DBatch &b, const DMeta *meta, const int lo) const {
+        uint32_t mr = trig ? b.mreach[4 * (size_t)meta->node_off + (size_t)(v0 + A.node)] : ~0u;
+        for (int st = 32; st >= 1; st >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)mr, st); mr = o < mr ? o : mr; }
+        int rr = (int)mr < v0 ? (int)mr : v0;
+        if (meta->dense & 2) { // the table is incomplete for this contig: the first node less than 500 bp left of the improved one
+            const DNode *nd = b.node + meta->node_off;
+            const int tl = __ffsll((long long)tm) - 1;
+            const int xpos = nd[v0 + __shfl(A.node, tl)].pos; // a watched node is not the source / target
+            rr = v0;
+            while (rr > 0) {
+                const int q = rr - 1 - lane;
+                const bool aff = q >= 0 && nd[q].pos > xpos - 500;
+                const uint64_t am = __ballot(aff);
+                if (am == ~0ull) { rr -= 64; continue; }
+                rr -= am ? (__ffsll((long long)~am) - 1) : 0;
+                break;
+            }
+        }
+        return rr < lo ? lo : rr;
+    }
+    // the sweep is over: the contig's records (the path walk and the genes, phanotate.py:64-76, are left to k_inorder: one lane chasing
+    // parents while 63 idle cost every contig ~50 us of a latency-bound kernel; there the walk runs with a workgroup per contig at full occupancy)
+    __device__ __forceinline__ void finish(DMeta *meta, const int V) const {
+        if (lane != 0) return;
+        meta->sweeps = 1 + rollbacks;
+        meta->sssp_iters = phases;
+        meta->n_genes = 0; meta->gene_off = 0;
+        // the target's distance is still in the ring (it was advanced by the last window)
+        if (N::unreached(N::load(ring + (size_t)((V - 1) & (RING - 1)) * NL * 8))) { meta->status = PHX_S_NOPATH; meta->n_path = 0; }
+        else meta->n_path = -2; // distances and parent edges are final; not walked yet
+    }
+};
+// hands a contig to the kernel it falls back to (lane 0 calls).  Where somebody else may be redirecting the contig at this moment — the
+// planner a streamed kernel follows, or (code 5, a planner that made no progress) one that may yet wake up — a compare-and-swap: whoever
+// comes first decides
+__device__ __forceinline__ void wv_hand_back(DMeta *meta, DTotals *tot, const int mode, const int code, const bool streamed) {
+    if (code != 5 && !streamed) { meta->sssp_mode = meta->sssp_fb; meta->sssp_why = code; return; }
+    if (atomicCAS(&meta->sssp_mode, mode, meta->sssp_fb) != mode) return;
+    meta->sssp_why = code;
+    if (code == 5) atomicAdd(&tot->plan_timeouts, 1);
+}
+
 template <int NL, int CFG>
 constexpr size_t wv_lds_bytes() {
     typedef WvDims<NL, CFG> D;
@@ -595,6 +1022,36 @@ constexpr size_t wv_lds_bytes() {
 // four wavefronts of this kernel per CU (one per SIMD): 1024 contigs are resident at once only while 4 x LDS fits 160 KB
 static_assert(4 * wv_lds_bytes<2, 1>() <= 160 * 1024 && 4 * wv_lds_bytes<4, 1>() <= 160 * 1024 && wv_lds_bytes<8, 1>() <= 64 * 1024, "k_sssp_wave: LDS per wavefront");
 static_assert(4 * wv_lds_bytes<2, 0>() + 40 * 1024 + 64 <= 160 * 1024, "k_sssp_wave, tight configuration: a 40 KB workgroup fits beside four wavefronts");
+#ifdef WV_PROFILE // clocks and counters behind WvSolver's hook (tools/wave_balance.py reads what the kernel's tail copies to DMeta)
+struct WvProf {
+    long long tp[12], tmark, t_begin;
+    int n_p64, n_redo, n_p128, n_rebase, mfA, mfB, bigA, bigB;
+    __device__ __forceinline__ void start() { for (int i = 0; i < 12; i++) tp[i] = 0; tmark = t_begin = wall_clock64(); n_p64 = n_redo = n_p128 = n_rebase = mfA = mfB = bigA = bigB = 0; }
+    __device__ __forceinline__ void tick(int k) { const long long t_ = wall_clock64(); tp[k] += t_ - tmark; tmark = t_; }
+    __device__ __forceinline__ void fine(int k) { // ticks inside the phases (they cost about as much as a 64-bit phase's arithmetic)
+#ifdef WV_PROFILE_FINE
+        tick(k);
+#endif
+    }
+    __device__ __forceinline__ void rebase() { n_rebase++; }
+    __device__ __forceinline__ void phase_done(int ph, bool n64, bool exact, int maxfollow) {
+        n_p64 += n64; n_redo += n64 && exact; n_p128 += exact;
+#ifdef WV_PROFILE_AB
+        tick(ph ? 7 : 6);
+        if (ph) { mfB += maxfollow; bigB += maxfollow > 4; } else { mfA += maxfollow; bigA += maxfollow > 4; }
+#endif
+    }
+};
+#define WV_TICK(k) S.prof.tick(k);
+#else
+typedef WvNoProf WvProf;
+#define WV_TICK(k)
+#endif
+#ifdef WV_PROFILE_GATHER // ticks inside the gather: cached in-edges / slow conversions / spill list (reported in the slots of WV_PROFILE_FINE)
+#define WV_GTICK(k) WV_TICK(k)
+#else
+#define WV_GTICK(k)
+#endif
 // STREAM: the instantiation that follows its planner's progress counter (DBatch.plan_stream; a kernel of its own so that the other's
 // code — the benchmark batch's — is exactly what it was: with the test at run time the 1000-contig launch took 0.476-0.49 instead of 0.457-0.462 ms)
 template <int NL, int CFG, bool STREAM = false>
@@ -622,29 +1079,16 @@ __global__ __launch_bounds__(64, NL == 2 ? WV_WPE : 1) void k_sssp_wave(DBatch b
     const DWin *win = b.win + meta->win_off;
     const uint2 *wrole = b.wrole + (size_t)meta->win_off * WIN_ROLES;
     // DBatch.plan_stream (tight 128-bit configuration, small batches): the planner of this contig may still be running — n_win is then the
-    // number of windows it has published so far, wait_plan(need) polls DMeta.plan_prog until windows [0, need) are there or it has
-    // finished.  0: go on; 1: the planner gave the contig up (it has redirected it itself: leave); 2: no progress for >= 20 ms (the
-    // planner is not running beside this kernel: hand the contig to the workgroup kernel rather than hang)
+    // number of windows it has published so far, and wv_wait_plan polls DMeta.plan_prog.
     static_assert(!STREAM || (NL == 2 && CFG == 0) || ((NL == 4 || NL == 8) && CFG == 1), "the tight 128-bit configuration and the 256- / 512-bit kernels can follow their planner");
     constexpr bool streamed = STREAM;
     typename std::conditional<STREAM, int, const int>::type n_win = streamed ? 0 : meta->n_win;
     bool plan_done = !streamed;
-    auto wait_plan = [&](int need) -> int {
-        for (int spins = 0;; spins++) {
-            const int p = __hip_atomic_load(&meta->plan_prog, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-            if (p < 0) return 1;
-            if constexpr (STREAM) n_win = p & (WV_PLAN_DONE - 1);
-            plan_done = (p & WV_PLAN_DONE) != 0;
-            if (plan_done || n_win >= need) return 0;
-            if (spins > WV_PLAN_SPINS) return 2;
-            __builtin_amdgcn_s_sleep(4);
-        }
-    };
     if constexpr (streamed) {
-        const int w = wait_plan(1);
+        const int w = wv_wait_plan(&meta->plan_prog, 1, n_win, plan_done);
         if (w == 1) return;
         if (w == 2) { // (a compare-and-swap: the planner may be redirecting the contig itself at this moment — whoever comes first decides)
-            if (lane == 0 && atomicCAS(&meta->sssp_mode, D::MODE, meta->sssp_fb) == D::MODE) { meta->sssp_why = 5; atomicAdd(&b.tot->plan_timeouts, 1); }
+            if (lane == 0) wv_hand_back(meta, b.tot, D::MODE, 5, true);
             return;
         }
     }
@@ -661,46 +1105,16 @@ __global__ __launch_bounds__(64, NL == 2 ? WV_WPE : 1) void k_sssp_wave(DBatch b
     // WV_REL_BIG, any other as WV_REL_WIDE: all positive, ordered like the values, low 4 bits free for an in-edge slot.
     // Windows whose weights are narrow iterate on this ring (phase64); `ring` stays exact at all times.
     uint8_t *rel = (uint8_t *)(s_role + WIN_ROLES);
-    const uint32_t ZERO = (uint32_t)WV_RING * NL * 8, INF = (uint32_t)(WV_RING + 1) * NL * 8;
-    T base = N::zero();
-    for (int i = lane; i < WV_RING; i += 64) { N::store(ring + (size_t)i * NL * 8, N::big()); *(long long *)(rel + (size_t)i * 8) = WV_REL_BIG; }
-    if (lane == 0) {
-        N::store(ring + ZERO, N::zero()); *(long long *)(rel + ZERO / NL) = WV_REL(0);
-        N::store(ring + INF, N::big()); *(long long *)(rel + INF / NL) = WV_REL_BIG;
-    }
-    // d (real or unreached) -> its entry in the relative ring; low: d lies more than 2^60 below base (the base must move)
-    auto to_rel = [&](T d, bool &low) -> long long {
-        const T x = N::sub(d, base);
-        const long long xl = (long long)N::lo64(x);
-        const bool fits = N::is_i64(x) && xl < WV_NARROW && xl > -WV_NARROW;
-        low = !fits && N::negative(x);
-        return N::unreached(d) ? WV_REL_BIG : (fits ? WV_REL(xl) : WV_REL_WIDE);
-    };
+    typedef WvSolver<N, C, WV_RING, WV_OV, true, WvProf> Solver;
+    constexpr uint32_t ZERO = Solver::ZERO, INF = Solver::INF;
+    Solver S;
+    S.init(ring, rel, ov_w, ov_s, gdist, gpe, lane);
 
     int loaded = 0;
-    int phases = 0, rollbacks = 0;
-#ifdef WV_PROFILE
-    int n_p64 = 0, n_redo = 0, n_p128 = 0, n_rebase = 0, mfA = 0, mfB = 0, bigA = 0, bigB = 0;
-#endif
-    bool wide = false; // a distance far below `base` was stored: 128-bit phases until the base has moved (next window)
     bool fail = n_win <= 0;
     int fail_code = fail ? 1 : 0;
 #ifdef WV_PROFILE
-    long long tp[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tmark = wall_clock64();
-    const long long t_begin = tmark;
-#define WV_TICK(k) { const long long t_ = wall_clock64(); tp[k] += t_ - tmark; tmark = t_; }
-#else
-#define WV_TICK(k)
-#endif
-#ifdef WV_PROFILE_GATHER // ticks inside the gather: cached in-edges / slow conversions / spill list (reported in the slots of WV_PROFILE_FINE)
-#define WV_GTICK(k) WV_TICK(k)
-#else
-#define WV_GTICK(k)
-#endif
-#ifdef WV_PROFILE_FINE // ticks inside the phases (they cost about as much as a 64-bit phase's arithmetic)
-#define WV_FTICK(k) WV_TICK(k)
-#else
-#define WV_FTICK(k)
+    S.prof.start();
 #endif
 
     // window records: lane l keeps the record of window cbase + l
@@ -725,15 +1139,6 @@ __global__ __launch_bounds__(64, NL == 2 ? WV_WPE : 1) void k_sssp_wave(DBatch b
         wv_dma16(wrole + (size_t)k * WIN_ROLES + 2 * lane, s_role);
     };
 
-    // results of the last window, not yet stored
-    int pend_dv = -1, pend_av = -1, pend_bv = -1, pend_ae = -1, pend_be = -1;
-    T pend_d = N::zero();
-    auto flush_results = [&]() {
-        if (pend_dv >= 0) N::store(gdist + (size_t)pend_dv * NL, pend_d);
-        if (pend_av >= 0) gpe[pend_av] = pend_ae;
-        if (pend_bv >= 0) gpe[pend_bv] = pend_be;
-        pend_dv = -1; pend_av = -1; pend_bv = -1;
-    };
     int k = 0;
     if (!fail) { load_recs(0); stage(0); }
     while (!fail) {
@@ -743,73 +1148,35 @@ __global__ __launch_bounds__(64, NL == 2 ? WV_WPE : 1) void k_sssp_wave(DBatch b
         const int v0 = __builtin_amdgcn_readlane((int)wr0.x, l), va = __builtin_amdgcn_readlane((int)wr0.y, l), v1 = __builtin_amdgcn_readlane((int)wr0.z, l);
         const uint32_t e0 = (uint32_t)__builtin_amdgcn_readlane((int)wr0.w, l);
         const uint32_t sumA = (uint32_t)__builtin_amdgcn_readlane((int)wr1.y, l), sumB = (uint32_t)__builtin_amdgcn_readlane((int)wr1.z, l);
-        int sd_next = __builtin_amdgcn_readlane((int)wr1.w, l); // spill entries the planner laid out; (NL > 2) the side list of wide in-edges follows them
-        const bool has_spill = sd_next != 0; // some node of the window has in-edges on the spill list
+        int sd_next = __builtin_amdgcn_readlane((int)wr1.w, l); // spill entries the planner laid out; (C::SIDE) the side list of wide in-edges follows them
+        S.has_spill = sd_next != 0; // some node of the window has in-edges on the spill list
         __builtin_amdgcn_s_waitcnt(0); // the DMA of this window has landed
-        flush_results(); // the previous window's results leave now: their stores are old when the next wait comes
+        S.flush_results(); // the previous window's results leave now: their stores are old when the next wait comes
         WV_TICK(0)
         // ---- nodes that enter the ring ----
         for (int i = loaded + lane; i < v1; i += 64) {
             const T d = N::sel(i == SRC, N::zero(), N::big());
             bool low;
             N::store(ring + (size_t)(i & (WV_RING - 1)) * NL * 8, d);
-            *(long long *)(rel + (size_t)(i & (WV_RING - 1)) * 8) = to_rel(d, low);
+            *(long long *)(rel + (size_t)(i & (WV_RING - 1)) * 8) = S.to_rel(d, low);
         }
         if (v1 > loaded) loaded = v1;
         wv_sync();
-        if (wide) {
-            // move the base to the lowest real distance in the ring (and the source's 0): nothing lies below it afterwards
-            T mn = N::load(ring + ZERO);
-            for (int i = lane; i < WV_RING; i += 64) { const T d = N::load(ring + (size_t)i * NL * 8); mn = N::sel(N::lt(d, mn), d, mn); }
-            for (int st = 32; st >= 1; st >>= 1) {
-                const T c = N::map32(mn, [&](int w) { return __shfl_xor(w, st); });
-                mn = N::sel(N::lt(c, mn), c, mn);
-            }
-            base = mn;
-#ifdef WV_PROFILE
-            n_rebase++;
-#endif
-            bool low;
-            for (int i = lane; i < WV_RING + 1; i += 64) *(long long *)(rel + (size_t)i * 8) = to_rel(N::load(ring + (size_t)i * NL * 8), low);
-            wide = false;
-            wv_sync();
-        }
+        S.move_base();
         const int ring_lo = loaded - WV_RING;
 
-        // ---- lanes of a phase: one per (node, chunk), as laid out by k_wave_plan ----
-        auto setup = [&](auto &R, const uint2 rc, const uint32_t summary) {
-            constexpr int cap = std::remove_reference_t<decltype(R)>::CAP;
-            const bool act = (rc.x >> 24) & 1u;
-            const int o_j = (int)(rc.x & 127u);
-            R.node = act ? o_j : -1;
-            R.ch = (int)((rc.x >> 7) & 63u);
-            R.head = act && R.ch == 0;
-            R.nextf = wv_next(act ? R.ch : 0) >= 1;
-            R.watch = (rc.x >> 25) & 1u;
-            R.nfollow = (int)((rc.x >> 13) & 63u);
-            R.cnt = (int)((rc.x >> 19) & 31u);
-            R.ebase = (int)(rc.y & 2047u);
-            R.sp0 = (int)((rc.y >> 11) & 1023u);
-            R.sp1 = R.sp0 + (int)((rc.y >> 21) & 1023u);
-            R.spe = R.ebase + (R.nfollow + 1) * cap;
-            R.slot = (uint32_t)((v0 + o_j) & (WV_RING - 1)) * NL * 8;
-            R.pe = -1;
-            R.maxcnt = (int)((summary >> 8) & 255u);
-            R.maxfollow = (int)((summary >> 16) & 255u);
-        };
         // one in-edge: staged (source node, integer weight) -> (ring offset of the source, weight as a T).  The weights arrive as
         // integers (k_edges / k_score encode trunc(w * 1000) once, ew_encode): a narrow one (|W| < 2^51, nearly every edge) is its own
         // low half.  convert_fast is branch-free and covers |W| < 2^62 with the source in the ring (or the source node, or beyond
         // the window); it reports the rest (a source that left the ring, a weight kept as a double's bit pattern) so that the
         // caller fixes those up afterwards, off the common path.
-        auto narrow51 = [](long long w) { return (unsigned long long)(w + (1ll << 51)) < (1ull << 52); };
         auto convert_fast = [&](bool on, uint32_t u, long long wi, uint32_t &cs, CW &cw) -> bool {
             const bool isrc = u == (uint32_t)SRC;
             const bool beyond = !on || ((int)u >= loaded && !isrc); // padding / source beyond the window (look-ahead nodes only): not there yet
             const bool far = on && !isrc && (int)u < ring_lo;        // left the ring long ago: final, folded into the weight
             cs = beyond ? INF : ((isrc || far) ? ZERO : (u & (WV_RING - 1)) * NL * 8);
             cw = C::from_i64(beyond ? 0ll : wi);
-            return on && (far || !narrow51(wi));
+            return on && (far || !ew_narrow51(wi));
         };
         auto convert_slow = [&](uint32_t u, long long wi, T &cw) {
             T w = EW_WIDE(wi) ? N::from_double(__longlong_as_double(wi | (1ll << 62))) : N::from_i64(wi);
@@ -875,7 +1242,7 @@ __global__ __launch_bounds__(64, NL == 2 ? WV_WPE : 1) void k_sssp_wave(DBatch b
             R.sd0 = 0; R.sd1 = 0;
             if (__ballot(slow != 0)) {
                 wide_w = true;
-                if constexpr (NL == 2) {
+                if constexpr (!C::SIDE) {
 #pragma unroll
                     for (int t = 0; t < cap; t++)
                         if (__ballot((slow >> t) & 1)) {
@@ -933,14 +1300,14 @@ __global__ __launch_bounds__(64, NL == 2 ? WV_WPE : 1) void k_sssp_wave(DBatch b
                 }
             }
             WV_GTICK(7)
-            if (has_spill)
+            if (S.has_spill)
             for (int i = R.sp0; i < R.sp1 && i < WV_OV; i++) {
                 uint32_t sl; CW wl;
                 const int idx = R.spe + (i - R.sp0);
                 const uint32_t u = ESRC_NODE(st_src[idx]);
                 const long long wd = st_w[idx];
                 const bool slow_e = convert_fast(true, u, wd, sl, wl);
-                T w = C::to_T(wl);
+                T w = C::template to_T<N>(wl);
                 if (slow_e) { convert_slow(u, wd, w); wide_w = true; }
                 ov_s[i] = sl;
                 N::store(ov_w + (size_t)i * NL * 8, w);
@@ -948,18 +1315,19 @@ __global__ __launch_bounds__(64, NL == 2 ? WV_WPE : 1) void k_sssp_wave(DBatch b
             WV_GTICK(8)
             return __ballot(wide_w) != 0;
         };
-        WvRole<NL, CA> A;
-        WvRole<NL, CB> B;
-        setup(A, s_role[lane], sumA);
-        setup(B, s_role[64 + lane], sumB);
+        // ---- lanes of a phase: one per (node, chunk), as laid out by k_wave_plan ----
+        WvRole<C, CA> A;
+        WvRole<C, CB> B;
+        S.decode(A, s_role[lane], sumA, v0, CA);
+        S.decode(B, s_role[64 + lane], sumB, v0, CB);
         WV_TICK(1)
         const bool wide_a = gather(A);
         const bool wide_b = gather(B);
-        if (fail) break; // (NL > 2) the side list does not fit: the contig goes to the kernel it falls back to
-        const bool narrow_w = !wide_a && !wide_b; // every cached weight is a sign-extended |w| < 2^51
+        if (fail) break; // (C::SIDE) the side list does not fit: the contig goes to the kernel it falls back to
+        S.narrow_w = !wide_a && !wide_b; // every cached weight is a sign-extended |w| < 2^51
         // In such a window a lane keeps (w << 4) + in-edge slot in the low half of each cached weight: the 64-bit phases then
         // form a candidate with one add, and the (rare) exact phase of the window shifts back.
-        if (narrow_w) {
+        if (S.narrow_w) {
 #pragma unroll
             for (int t = 0; t < CA; t++) A.cw[t] = C::with_lo(A.cw[t], (C::lo(A.cw[t]) << 4) | (uint64_t)t);
 #pragma unroll
@@ -974,7 +1342,7 @@ __global__ __launch_bounds__(64, NL == 2 ? WV_WPE : 1) void k_sssp_wave(DBatch b
         if (!last) {
             if constexpr (STREAM) {
                 if (!plan_done && k + 2 > n_win) { // the record of window k+1 is not published yet
-                    const int w = wait_plan(k + 2);
+                    const int w = wv_wait_plan(&meta->plan_prog, k + 2, n_win, plan_done);
                     if (w == 1) { __builtin_amdgcn_s_waitcnt(0); return; } // the planner gave up after all: the contig is somebody else's now, nothing of this sweep is needed (no DMA may be in flight into LDS when the wavefront ends)
                     if (w == 2) { fail = true; fail_code = 5; break; }
                 }
@@ -986,275 +1354,19 @@ __global__ __launch_bounds__(64, NL == 2 ? WV_WPE : 1) void k_sssp_wave(DBatch b
 
         WV_TICK(3)
         // ---- iterate to the fixed point ----
-        auto phase = [&](auto &R) -> bool {
-            constexpr int cap = std::remove_reference_t<decltype(R)>::CAP;
-            T m = N::top();
-            int arg = 0;
-            constexpr int G = cap < 8 ? cap : (NL > 2 ? 4 : 8); // distances are fetched G at a time: one LDS round trip per group
-#pragma unroll
-            for (int t0 = 0; t0 < cap; t0 += G) {
-                if (t0 >= R.maxcnt) break;
-                T x[G];
-                int xa[G];
-#pragma unroll
-                for (int g = 0; g < G; g++) x[g] = N::load(ring + R.cs[t0 + g]);
-#pragma unroll
-                for (int g = 0; g < G; g++) xa[g] = t0 + g;
-                if (narrow_w) { // (uniform) the cached weights are in the form of a narrow window, see above
-#pragma unroll
-                    for (int g = 0; g < G; g++) {
-                        uint64_t lo = C::lo(R.cw[t0 + g]);
-                        asm volatile("" : "+v"(lo)); // (keeps the shift inside this rare phase: hoisted out of the phase loop it costs every window)
-                        x[g] = N::add(x[g], N::from_i64((long long)lo >> 4));
-                    }
-                } else {
-#pragma unroll
-                    for (int g = 0; g < G; g++) x[g] = N::add(x[g], C::to_T(R.cw[t0 + g]));
-                }
-                // minimum of the group as a tree (independent compares); ties keep the lower index
-#pragma unroll
-                for (int w = 1; w < G; w <<= 1)
-#pragma unroll
-                    for (int g = 0; g + w < G; g += 2 * w) {
-                        const bool l = N::lt(x[g + w], x[g]);
-                        x[g] = N::sel(l, x[g + w], x[g]);
-                        xa[g] = l ? xa[g + w] : xa[g];
-                    }
-                const bool l = N::lt(x[0], m);
-                m = N::sel(l, x[0], m);
-                arg = l ? xa[0] : arg;
-            }
-            if constexpr (NL > 2) {
-                if (!narrow_w) { // (uniform) this lane's entries of the side list; an equal candidate wins if its slot is the lower one
-                    for (int i = R.sd0; i < R.sd1; i++) {
-                        const uint32_t sv = ov_s[i];
-                        const int t = (int)(sv >> 24);
-                        const T c = N::add(N::load(ring + (sv & 0xffffffu)), N::load(ov_w + (size_t)i * NL * 8));
-                        const bool l = N::lt(c, m) || (!N::lt(m, c) && t < arg);
-                        m = N::sel(l, c, m);
-                        arg = l ? t : arg;
-                    }
-                }
-            }
-            WV_FTICK(6)
-            int e = R.ebase + arg;
-            if (R.maxfollow > 0) {
-                // segmented minimum over a head and the helper lanes that follow it: log2 steps, each lane takes the
-                // value `st` lanes to its right if that lane belongs to the same node (its chunk index is >= st);
-                // the left operand keeps ties, so the lowest in-edge index survives
-                for (int st = 1; st <= R.maxfollow; st <<= 1) {
-                    const int src = (lane + st) & 63;
-                    const int och = __shfl(R.node >= 0 ? R.ch : 0, src);
-                    const T c = N::map32(m, [&](int w) { return __shfl(w, src); });
-                    const int ce = __shfl(e, src);
-                    const bool l = lane + st < 64 && och >= st && N::lt(c, m);
-                    m = N::sel(l, c, m);
-                    e = l ? ce : e;
-                }
-            }
-            WV_FTICK(7)
-            bool coop = false; // this lane's spill entries were taken by the whole wavefront (below)
-            if constexpr (NL >= 8) {
-                // A stop node behind a 9000-codon ORF collects an in-edge from every in-frame start (~450): beyond its 63 helper lanes ~200 entries sit on the
-                // spill list, and one lane walked them two at a time in every close-node phase of the window (~8 us each).  Lists of more than 8
-                // entries are reduced by all 64 lanes instead: a strided pass, then a butterfly on (value, edge index) — the lowest index among equals, as
-                // the walk in order finds it.
-                if (has_spill) {
-                    uint64_t bigm = __ballot(R.head && R.sp1 - R.sp0 > 8);
-                    while (bigm) {
-                        const int Ln = __ffsll((long long)bigm) - 1;
-                        bigm &= bigm - 1;
-                        const int s0 = __builtin_amdgcn_readlane(R.sp0, Ln), s1 = __builtin_amdgcn_readlane(R.sp1, Ln), spe0 = __builtin_amdgcn_readlane(R.spe, Ln);
-                        T mm = N::top();
-                        int ee = 0x7fffffff;
-                        for (int i = s0 + lane; i < s1; i += 64) {
-                            const T c = N::add(N::load(ring + ov_s[i]), N::load(ov_w + (size_t)i * NL * 8));
-                            const bool l = N::lt(c, mm);
-                            mm = N::sel(l, c, mm);
-                            ee = l ? spe0 + (i - s0) : ee;
-                        }
-                        for (int st = 32; st >= 1; st >>= 1) {
-                            const T c = N::map32(mm, [&](int w) { return __shfl_xor(w, st); });
-                            const int ce = __shfl_xor(ee, st);
-                            const bool l = N::lt(c, mm) || (!N::lt(mm, c) && ce < ee);
-                            mm = N::sel(l, c, mm);
-                            ee = l ? ce : ee;
-                        }
-                        if (lane == Ln) { const bool l = N::lt(mm, m); m = N::sel(l, mm, m); e = l ? ee : e; coop = true; }
-                    }
-                }
-            }
-            if (has_spill) {
-                for (int i = coop ? R.sp1 : R.sp0; i < R.sp1; i += 2) { // spill list, two entries per pair of LDS round trips
-                    const bool two = i + 1 < R.sp1;
-                    const uint32_t s0 = ov_s[i], s1 = two ? ov_s[i + 1] : INF;
-                    const T w0 = N::load(ov_w + (size_t)i * NL * 8), w1 = N::sel(two, N::load(ov_w + (size_t)(i + 1 < WV_OV ? i + 1 : i) * NL * 8), N::zero());
-                    const T c0 = N::add(N::load(ring + s0), w0), c1 = N::add(N::load(ring + s1), w1);
-                    bool l = N::lt(c0, m);
-                    m = N::sel(l, c0, m);
-                    e = l ? R.spe + (i - R.sp0) : e;
-                    l = N::lt(c1, m);
-                    m = N::sel(l, c1, m);
-                    e = l ? R.spe + (i + 1 - R.sp0) : e;
-                }
-            }
-            WV_FTICK(8)
-            bool chg = false, widen = false;
-            if (R.head) {
-                R.pe = e;
-                const T d0 = N::load(ring + R.slot);
-                // (a candidate over an unreached source is not a distance: the ring holds real distances or exactly big())
-                if (N::lt(m, d0) && !N::unreached(m)) {
-                    N::store(ring + R.slot, m); chg = true;
-                    *(long long *)(rel + R.slot / NL) = to_rel(m, widen);
-                }
-            }
-            wv_sync(); // the next phase reads what this one wrote
-            const bool any = __ballot(chg) != 0;
-            if (__ballot(widen)) wide = true;
-            WV_FTICK(9)
-            return any;
-        };
-        // The same phase on the relative ring, for windows whose cached weights are all narrow (|w| < 2^51) while no distance
-        // lies far below the base.  A candidate is entry + (w << 4) + slot: one 64-bit shift-add; the entries are positive and
-        // below 2^63, so as bit patterns they are ordered like positive normal doubles and the minimum of a lane's
-        // candidates is a chain of v_min_f64 - the winning slot rides in the low 4 bits, ties go to the lower slot.
-        // A candidate over an unreached source is >= WV_VAL_BIG - 2^51 and never stored; one over a WV_REL_WIDE source (a real
-        // distance more than 2^55 above the base) loses against every narrow candidate, and a node that has none but has such
-        // a source makes the phase run again in 128 bits (`again_mask`).  Otherwise: the same numbers.
-        auto min64 = [](uint64_t a, uint64_t b) -> uint64_t { uint64_t r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; };
-        uint64_t again_mask = 0; // heads of the last 64-bit phase that need the exact ring, see `again`
-        auto phase64 = [&](auto &R) -> bool { // true: some distance improved
-            constexpr int cap = std::remove_reference_t<decltype(R)>::CAP;
-            uint64_t mm = 0x7000000000000000ull;
-            // every load of the phase is in flight before the first use (unused slots point at the constant "unreached" entry)
-            const long long d0 = *(const long long *)(rel + R.slot / NL);
-            uint64_t x[cap];
-#pragma unroll
-            for (int t = 0; t < cap; t++) x[t] = *(const uint64_t *)(rel + R.cs[t] / NL);
-#pragma unroll
-            for (int t = 0; t < cap; t++) x[t] += C::lo(R.cw[t]);
-#pragma unroll
-            for (int w = 1; w < cap; w <<= 1)
-#pragma unroll
-                for (int t = 0; t + w < cap; t += 2 * w) x[t] = min64(x[t], x[t + w]);
-            mm = min64(mm, x[0]);
-            WV_FTICK(6)
-            int e = R.ebase + (int)(mm & 15u);
-            long long m = (long long)mm >> 4; // relative value + WV_BIAS
-            if (R.maxfollow > 0 && R.maxfollow <= 4) {
-                // few helper lanes: one DPP shift (lane i <- lane i+1) per helper instead of log-steps over ds_bpermute
-                for (int q = 0; q < R.maxfollow; q++) {
-                    const long long c = (long long)(((uint64_t)(uint32_t)wv_next_self((int)((uint64_t)m >> 32)) << 32) | (uint32_t)wv_next_self((int)m));
-                    const int ce = wv_next_self(e);
-                    const bool l = R.nextf && c < m;
-                    m = l ? c : m;
-                    e = l ? ce : e;
-                }
-            } else if (R.maxfollow > 0) {
-                for (int st = 1; st <= R.maxfollow; st <<= 1) {
-                    const int src = (lane + st) & 63;
-                    const int och = __shfl(R.node >= 0 ? R.ch : 0, src);
-                    const long long c = (long long)(((uint64_t)(uint32_t)__shfl((int)((uint64_t)m >> 32), src) << 32) | (uint32_t)__shfl((int)m, src));
-                    const int ce = __shfl(e, src);
-                    const bool l = lane + st < 64 && och >= st && c < m;
-                    m = l ? c : m;
-                    e = l ? ce : e;
-                }
-            }
-            WV_FTICK(7)
-            if (has_spill) {
-                for (int i = R.sp0; i < R.sp1; i++) {
-                    const long long c0 = (long long)((*(const uint64_t *)(ov_w + (size_t)i * NL * 8) << 4) + *(const uint64_t *)(rel + ov_s[i] / NL)) >> 4;
-                    const bool l = c0 < m;
-                    m = l ? c0 : m;
-                    e = l ? R.spe + (i - R.sp0) : e;
-                }
-            }
-            WV_FTICK(8)
-            // a head whose best candidate sits on a wide source, or is itself 2^55 or more above the base (its slot may hold
-            // a wide distance it cannot be compared with here): the phase is run again on the exact ring; what the other
-            // heads store meanwhile are valid improvements
-            const bool again = R.head && m >= WV_BIAS + WV_NARROW && m < WV_BIAS + WV_VAL_BIG - (1ll << 52);
-            // d0 real: compare; d0 unreached or wide (more than 2^55 above the base): any real candidate is lower.
-            // (lane predicates and votes straight from the compares: no flags carried out of a divergent region)
-            const bool store = R.head && m < WV_BIAS + WV_NARROW && m < (d0 >> 4);
-            const long long v = m - WV_BIAS;
-            const bool fits = v > -WV_NARROW;
-            R.pe = R.head ? e : R.pe;
-            if (store) {
-                N::store(ring + R.slot, N::add(base, N::from_i64(v)));
-                *(long long *)(rel + R.slot / NL) = fits ? (long long)((uint64_t)m << 4) : WV_REL_WIDE;
-            }
-            const uint64_t cm = __ballot(store);
-            again_mask = __ballot(again);
-            wv_sync();
-            if (cm && __ballot(store && !fits)) wide = true;
-            WV_FTICK(9)
-            return cm != 0;
-        };
-        {
-            int inner = 0;
-            for (int ph = 0;; ph ^= 1) {
-                bool chg = false;
-                const bool n64 = narrow_w && !wide;
-                if (n64) chg = ph ? phase64(B) : phase64(A);
-                const bool exact = !n64 || again_mask != 0; // run the 128-bit phase
-#ifdef WV_PROFILE
-                n_p64 += n64; n_redo += n64 && exact; n_p128 += exact;
-#endif
-                if (exact) chg |= ph ? phase(B) : phase(A);
-#ifdef WV_PROFILE_AB
-                { const long long t_ = wall_clock64(); tp[ph ? 7 : 6] += t_ - tmark; tmark = t_; }
-                if (ph) { mfB += B.maxfollow; bigB += B.maxfollow > 4; } else { mfA += A.maxfollow; bigA += A.maxfollow > 4; }
-#endif
-                phases++;
-                if (!chg && (ph == 1 || inner > 0)) break;
-                if (++inner > 4 * WV_WIN + 16) { fail = true; fail_code = 3; break; }
-            }
-            if (fail) break;
-        }
+        if (!S.iterate(A, A.cw, A.cs, B, B.cw, B.cs)) { fail = true; fail_code = 3; break; }
 
         WV_TICK(4)
         // ---- results of the advanced nodes: distance, parent edge (contig-relative, the convention of k_sssp / k_sssp_lds;
         //      the walk at the end resolves it).  Kept in registers and stored after the next window's DMA wait. ----
-        pend_dv = v0 + lane < va ? v0 + lane : -1;
-        pend_d = N::load(ring + (size_t)((v0 + lane) & (WV_RING - 1)) * NL * 8);
-        auto parents = [&](auto &R, int &pv, int &pe) {
-            pv = (R.head && v0 + R.node < va) ? v0 + R.node : -1;
-            pe = (pv >= 0 && pv != SRC && R.pe >= 0 && !N::unreached(N::load(ring + (R.head ? R.slot : ZERO)))) ? (int)(e0 + (uint32_t)R.pe) : -1;
-        };
-        parents(A, pend_av, pend_ae);
-        parents(B, pend_bv, pend_be);
+        S.keep_results(A, B, v0, va, e0, SRC);
 
         // ---- did a close node that final nodes may depend on improve?  then step back ----
-#ifdef WV_NO_WATCH // development: how much the step-backs cost (results are then wrong where one was needed)
-        const bool trig = false;
-#else
-        const bool trig = A.head && A.watch && N::lt(N::load(ring + A.slot), a_old);
-#endif
+        const bool trig = S.watch_improved(A, a_old);
         const uint64_t tm = __ballot(trig);
         if (tm) {
-            if (++rollbacks > 4 * (V / WV_ADV + 4)) { fail = true; fail_code = 4; break; }
-            // the lowest final node an overlap edge out of an improved, watched node ends in (k_edges_scan recorded it)
-            uint32_t mr = trig ? b.mreach[4 * (size_t)meta->node_off + (size_t)(v0 + A.node)] : ~0u;
-            for (int st = 32; st >= 1; st >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)mr, st); mr = o < mr ? o : mr; }
-            int rr = (int)mr < v0 ? (int)mr : v0;
-            if (meta->dense & 2) { // the table is incomplete for this contig: the first node less than 500 bp left of the improved one
-                const DNode *nd = b.node + meta->node_off;
-                const int tl = __ffsll((long long)tm) - 1;
-                const int xpos = nd[v0 + __shfl(A.node, tl)].pos; // a watched node is not the source / target
-                rr = v0;
-                while (rr > 0) {
-                    const int q = rr - 1 - lane;
-                    const bool aff = q >= 0 && nd[q].pos > xpos - 500;
-                    const uint64_t am = __ballot(aff);
-                    if (am == ~0ull) { rr -= 64; continue; }
-                    rr -= am ? (__ffsll((long long)~am) - 1) : 0;
-                    break;
-                }
-            }
-            if (rr < 0) rr = 0;
+            if (++S.rollbacks > 4 * (V / WV_ADV + 4)) { fail = true; fail_code = 4; break; }
+            const int rr = S.step_back_node(A, trig, tm, v0, b, meta, 0);
             __builtin_amdgcn_s_waitcnt(0); // the DMA that is in flight lands in buffers we are about to reuse
             // the window that advances node rr: the last one that starts at or left of it
             int j = -1;
@@ -1273,34 +1385,25 @@ __global__ __launch_bounds__(64, NL == 2 ? WV_WPE : 1) void k_sssp_wave(DBatch b
         k++;
     }
 
-    flush_results();
+    S.flush_results();
     if (fail) { // hand the contig to the workgroup kernel
-        if (lane == 0) {
-            if (fail_code == 5) { if (atomicCAS(&meta->sssp_mode, D::MODE, meta->sssp_fb) == D::MODE) { meta->sssp_why = 5; atomicAdd(&b.tot->plan_timeouts, 1); } }
-            else { meta->sssp_mode = meta->sssp_fb; meta->sssp_why = fail_code; }
-        }
+        if (lane == 0) wv_hand_back(meta, b.tot, D::MODE, fail_code, streamed);
         return;
     }
 
-    // ---- the path walk and the genes (phanotate.py:64-76) are left to k_inorder: one lane chasing parents while 63 idle cost every
-    //      contig ~50 us of this latency-bound kernel; there the walk runs with a workgroup per contig at full occupancy ----
+#ifdef WV_PROFILE
     WV_TICK(5)
     if (lane == 0) {
-        meta->sweeps = 1 + rollbacks;
-#ifdef WV_PROFILE
-        WV_TICK(10)
-        for (int k = 0; k < 4; k++) meta->pmax[k] = (uint32_t)tp[k];
-        meta->tr[0] = n_p64; meta->tr[1] = n_redo; meta->tr[2] = n_p128; meta->tr[3] = n_rebase;
-        meta->tr[4] = mfA; meta->tr[5] = mfB; meta->tr[6] = bigA; meta->tr[7] = bigB;
-        meta->bg[5] = (uint32_t)tp[10];
-        meta->bg[6] = (uint32_t)(wall_clock64() - t_begin); meta->bg[7] = (uint32_t)n_win;
-        meta->pmin[0] = (uint32_t)(tp[4] + tp[6] + tp[7] + tp[8] + tp[9]); meta->pmin[1] = (uint32_t)tp[5];
-        meta->bg[0] = (uint32_t)tp[6]; meta->bg[1] = (uint32_t)tp[7]; meta->bg[2] = (uint32_t)tp[8]; meta->bg[3] = (uint32_t)tp[9]; meta->bg[4] = (uint32_t)tp[4];
-#endif
-        meta->sssp_iters = phases;
-        meta->n_genes = 0; meta->gene_off = 0;
-        // the target's distance is still in the ring (it was advanced by the last window)
-        if (N::unreached(N::load(ring + (size_t)((V - 1) & (WV_RING - 1)) * NL * 8))) { meta->status = PHX_S_NOPATH; meta->n_path = 0; }
-        else meta->n_path = -2; // distances and parent edges are final; not walked yet
+        const WvProf &P = S.prof;
+        S.prof.tick(10);
+        for (int k = 0; k < 4; k++) meta->pmax[k] = (uint32_t)P.tp[k];
+        meta->tr[0] = P.n_p64; meta->tr[1] = P.n_redo; meta->tr[2] = P.n_p128; meta->tr[3] = P.n_rebase;
+        meta->tr[4] = P.mfA; meta->tr[5] = P.mfB; meta->tr[6] = P.bigA; meta->tr[7] = P.bigB;
+        meta->bg[5] = (uint32_t)P.tp[10];
+        meta->bg[6] = (uint32_t)(wall_clock64() - P.t_begin); meta->bg[7] = (uint32_t)n_win;
+        meta->pmin[0] = (uint32_t)(P.tp[4] + P.tp[6] + P.tp[7] + P.tp[8] + P.tp[9]); meta->pmin[1] = (uint32_t)P.tp[5];
+        meta->bg[0] = (uint32_t)P.tp[6]; meta->bg[1] = (uint32_t)P.tp[7]; meta->bg[2] = (uint32_t)P.tp[8]; meta->bg[3] = (uint32_t)P.tp[9]; meta->bg[4] = (uint32_t)P.tp[4];
     }
+#endif
+    S.finish(meta, V);
 }
