@@ -37,7 +37,9 @@ extern "C" {
                          *        (additions, version unchanged) phx_orf_margin, phx_margins_flat, phx_tap_dist_target, phx_margins_ms, phx_format_margins;
  *        (additions, version unchanged) phx_gene_drop, phx_drop_margins_flat, phx_drop_ms, phx_drop_stats, phx_format_drops;
  *        (additions, version unchanged) phx_gene_repl, phx_replacements_flat, phx_tap_replacement, phx_replacements_ms,
- *        phx_replacement_stats, phx_format_replacements */
+ *        phx_replacement_stats, phx_format_replacements;
+ *        (additions, version unchanged) phx_reannotate_flat, phx_orf_offsets, phx_tap_repath, phx_reannotate_ms;
+ *        (addition, version unchanged: the suite pins 410) phx_constrain_flat — probe for the symbol, not for a version */
 #define PHX_MAX_CODONS 16
 
 /* library-level errors */
@@ -412,6 +414,25 @@ int phx_replacement_stats(phx_ctx *ctx, int64_t *out /* [5] */);
  * the next upload or run; nothing phx_download*, the taps, the margins, the drops, the replacements or the certificate return changes. */
 int phx_reannotate_flat(phx_ctx *ctx, const uint8_t *forbid, const int64_t *orf_offsets /* [n+1] */, uint32_t flags, phx_gene *genes, int64_t cap,
                         int64_t *offsets /* [n+1] */, int32_t *status /* [n] */, double *delta /* [n] */, int64_t *total);
+/* ---- pinned re-annotation: the best annotation that KEEPS chosen ORFs ----
+ * phx_reannotate_flat with a second set: F (forbid) is refused as above, R (require, disjoint from F) is to be kept.  R' = the ORFs of R whose
+ * edge exists in G_F.  Paths of G_F are ordered by (-c(P), W(P)), c(P) = edges of R' on P, W(P) the sum of W: the result is the minimum,
+ * i.e. the shortest path under W'(e) = W(e) - M [e in R'] for any M above every walk sum.  The device solves such a contig on one limb more
+ * than its class with M = 2^(64 NL) — the top limb of a distance is the count, the limbs below the W-sum, both exact; 128 / 256 / 512 / 1088
+ * bits become 192 / 320 / 576 / 1152, no class overflows — and picks the path by the in-order rule of §14 on W'.  With R empty it is
+ * phx_reannotate_flat byte for byte (the same kernels).
+ *   forbid, require  one byte per ORF each (non-zero: in the set), laid out as `forbid` above; either may be NULL (empty).  An ORF in both:
+ *                    PHX_E_ARG before any kernel.
+ *   delta[i]         float(W(P) - D) / 1000.0 (M does not enter), >= 0; +inf without a result
+ *   unmet[i]         |R| - c(P): the required ORFs of contig i the result does not call — without an edge in the graph, on no source ->
+ *                    target path, or not compatible with the rest of R (the genes are the best annotation that keeps as many as can be
+ *                    kept together).  All of R where there is no result.
+ * status[i] as above, and PHX_S_NEGCYCLE (no genes, delta +inf) when a cycle of G_F that the source reaches runs through an edge of R' (nodes are shared within
+ * stop groups): no path is best then.  The solver ends such a contig as soon as a distance counts more required edges than exist.
+ * The two calls share their buffers and their cached result (keyed on both sets and flags); phx_tap_repath and phx_reannotate_ms serve the
+ * last solve of either kind, and the distance phx_tap_repath reports is the W-sum W(P). */
+int phx_constrain_flat(phx_ctx *ctx, const uint8_t *forbid, const uint8_t *require, const int64_t *orf_offsets /* [n+1] */, uint32_t flags, phx_gene *genes,
+                       int64_t cap, int64_t *offsets /* [n+1] */, int32_t *status /* [n] */, double *delta /* [n] */, int32_t *unmet /* [n] */, int64_t *total);
 /* orf_offsets[n+1] of the batch last run as phx_reannotate_flat expects them: cumulative ORF counts, a contig with a run error or without
  * device distances counting none (the offsets phx_margins_flat reports, without computing the margins or the certificate). */
 int phx_orf_offsets(phx_ctx *ctx, int64_t *orf_offsets /* [n+1] */);

@@ -151,6 +151,7 @@ def lib():
         "phx_replacement_stats": (C.c_int, [vp, P(i64)]),
         "phx_format_replacements": (C.c_int, [i32, vp, vp, vp, vp, vp, P(vp), P(i64)]),
         "phx_reannotate_flat": (C.c_int, [vp, vp, vp, C.c_uint32, vp, i64, vp, vp, vp, P(i64)]),
+        "phx_constrain_flat": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, i64, vp, vp, vp, vp, P(i64)]),
         "phx_orf_offsets": (C.c_int, [vp, vp]),
         "phx_tap_repath": (C.c_int, [vp, i32, vp, i32, P(i32), vp, i32]),
         "phx_reannotate_ms": (C.c_int, [vp, P(C.c_float)]),
@@ -195,4 +196,4 @@ EXPORTS = ["phx_version", "phx_device_count", "phx_strerror", "phx_last_error", 
            "phx_drop_margins_flat", "phx_drop_ms", "phx_drop_stats", "phx_format_drops",
            "phx_replacements_flat", "phx_tap_replacement", "phx_replacements_ms", "phx_replacement_stats",
            "phx_format_replacements",
-           "phx_reannotate_flat", "phx_orf_offsets", "phx_tap_repath", "phx_reannotate_ms"]
+           "phx_reannotate_flat", "phx_constrain_flat", "phx_orf_offsets", "phx_tap_repath", "phx_reannotate_ms"]

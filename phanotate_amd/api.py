@@ -489,8 +489,48 @@ class Annotator:
         self._chk(self.L.phx_reannotate_flat(self.h, vp(mask), vp(oo), fl, vp(genes), len(genes), vp(offs), vp(status), vp(delta), C.byref(total)), "phx_reannotate_flat")
         return status[:n], offs, genes[: int(total.value)], delta[:n]
 
+    def _orf_mask(self, sets):
+        """One byte per ORF of the batch from one index array (or None) per contig."""
+        n = self.n
+        if len(sets) != n:
+            raise ValueError("one index array (or None) per contig of the batch")
+        oo = self.orf_offsets()
+        mask = np.zeros(max(int(oo[n]), 1), np.uint8)
+        for i, f in enumerate(sets):
+            if f is None:
+                continue
+            idx = np.asarray(f, np.int64).reshape(-1)
+            if idx.size and (idx.min() < 0 or idx.max() >= oo[i + 1] - oo[i]):
+                raise IndexError("contig %d has %d ORFs" % (i, oo[i + 1] - oo[i]))
+            mask[oo[i] + idx] = 1
+        return mask
+
+    def constrain(self, forbid=None, require=None, solve_all=False):
+        """(status int32[n], offsets int64[n+1], genes structured array[total], delta float64[n], unmet int32[n]): the batch last run
+        annotated again without the ORFs of `forbid` and keeping those of `require` — each one array of indices into orfs(i) per contig,
+        or None — on the resident device graph (phx_constrain_flat).  The result calls as many required ORFs as can be
+        called together and is the best such annotation; unmet[i] counts the required ORFs of contig i it does not call (all of them where
+        there is no result); delta[i] = float(W(P) - D) / 1000.  A cycle through a required ORF's edge gives status 2 without genes.  An
+        ORF in both sets raises PhxError (PHX_E_ARG).  With nothing required it is reannotate(forbid)."""
+        n = self.n
+        oo = self.orf_offsets()
+        fmask = self._orf_mask([None] * n if forbid is None else forbid)
+        rmask = self._orf_mask([None] * n if require is None else require)
+        offs = np.zeros(n + 1, np.int64)
+        status = np.zeros(max(n, 1), np.int32)
+        delta = np.zeros(max(n, 1), np.float64)
+        unmet = np.zeros(max(n, 1), np.int32)
+        total = C.c_int64(0)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        fl = 1 if solve_all else 0
+        self._chk(self.L.phx_constrain_flat(self.h, vp(fmask), vp(rmask), vp(oo), fl, None, 0, vp(offs), vp(status), vp(delta), vp(unmet), C.byref(total)), "phx_constrain_flat")
+        genes = np.empty(max(int(total.value), 1), _lib.GENE_DT)
+        self._chk(self.L.phx_constrain_flat(self.h, vp(fmask), vp(rmask), vp(oo), fl, vp(genes), len(genes), vp(offs), vp(status), vp(delta), vp(unmet), C.byref(total)), "phx_constrain_flat")
+        return status[:n], offs, genes[: int(total.value)], delta[:n], unmet[:n]
+
     def reannotated_path(self, i):
-        """(path as device node ids, D_F as a python int) of contig i in the last re-annotation, like path(i)."""
+        """(path as device node ids, its length as a python int) of contig i in the last re-annotation or constrain(), like path(i): D_F, or
+        the W-sum W(P) after constrain()."""
         g = self.globals(i)
         p = np.zeros(max(g.n_node, 1), np.int32)
         n = C.c_int32()

@@ -44,7 +44,8 @@ def get_args(argv=None):
     p.add_argument("--drop-margins", metavar="FILE", default=None, help="also write every called gene with its drop margin, the cost of the best path without it (DESIGN.md §12), to FILE")
     p.add_argument("--drop-replacements", metavar="FILE", default=None, help="also write every called gene with what the best path without it calls instead (DESIGN.md §13) to FILE")
     p.add_argument("--forbid", metavar="FILE", default=None, help="ORFs to refuse in a second annotation (DESIGN.md §14): lines whose first four columns are START STOP FRAME CONTIG as the tabular output prints a gene; needs --reannotation")
-    p.add_argument("--reannotation", metavar="OUT", default=None, help="write the annotation without the ORFs of --forbid to OUT: the tabular block of every contig with a #delta: header line")
+    p.add_argument("--require", metavar="FILE", default=None, help="ORFs to keep in a second annotation (DESIGN.md §16), in the format of --forbid; alone or with --forbid; needs --reannotation, which then carries a #unmet: line per contig")
+    p.add_argument("--reannotation", metavar="OUT", default=None, help="write the annotation without the ORFs of --forbid (and keeping those of --require) to OUT: the tabular block of every contig with a #delta: header line")
     p.add_argument("--single-device-ranks", action="store_true", help=argparse.SUPPRESS)  # tests: every rank of a sharded launch on GPU `--device` (gloo-only group)
     args = p.parse_args(argv)
     if args.margins is not None and args.dump:
@@ -59,15 +60,19 @@ def get_args(argv=None):
         p.error("argument --drop-replacements: not allowed with argument -d/--dump")
     if args.drop_replacements is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         p.error("argument --drop-replacements: not available under a multi-rank launch")
-    for flag, val in (("--forbid", args.forbid), ("--reannotation", args.reannotation)):
+    for flag, val in (("--forbid", args.forbid), ("--require", args.require), ("--reannotation", args.reannotation)):
         if val is not None and args.dump:
             p.error("argument %s: not allowed with argument -d/--dump" % flag)
         if val is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
             p.error("argument %s: not available under a multi-rank launch" % flag)
-    if (args.forbid is None) != (args.reannotation is None):
+    if args.require is None and (args.forbid is None) != (args.reannotation is None):
         p.error("arguments --forbid and --reannotation: each needs the other")
+    if args.require is not None and args.reannotation is None:
+        p.error("argument --require: needs --reannotation")
     if args.forbid is not None and int(args.gpus) > 1:  # the re-annotation works on the batch resident on one context
         p.error("argument --forbid: not available with --gpus above 1")
+    if args.require is not None and int(args.gpus) > 1:
+        p.error("argument --require: not available with --gpus above 1")
     return args
 
 
@@ -75,8 +80,8 @@ class ForbidError(ValueError):
     """A line of --forbid that cannot be used; the message quotes it."""
 
 
-def parse_forbid(lines):
-    """--forbid FILE: [(left, right, strand, contig name, the line)] for every line that is not empty or a '#' line.  The first four
+def parse_forbid(lines, flag="--forbid"):
+    """--forbid FILE (--require FILE: `flag` names it in the messages): [(left, right, strand, contig name, the line)] for every line that is not empty or a '#' line.  The first four
     columns are START STOP FRAME CONTIG as write_tabular prints a gene (START > STOP on the reverse strand); further columns are ignored."""
     out = []
     for raw in lines:
@@ -89,13 +94,13 @@ def parse_forbid(lines):
                 raise ValueError
             a, z = int(col[0]), int(col[1])
         except ValueError:
-            raise ForbidError("--forbid: not START STOP FRAME CONTIG: %r" % line) from None
+            raise ForbidError("%s: not START STOP FRAME CONTIG: %r" % (flag, line)) from None
         strand = 1 if col[2].strip() == "+" else -1
         out.append((min(a, z), max(a, z), strand, col[3].strip(), line))
     return out
 
 
-def resolve_forbid(entries, names, lookup):
+def resolve_forbid(entries, names, lookup, flag="--forbid"):
     """Per contig of `names` the ORF indices the entries of parse_forbid name (None: none); lookup(i, left, right, strand) is
     Annotator.orf_index.  A line that names no ORF of its contig raises ForbidError quoting the line."""
     where = {}
@@ -107,15 +112,16 @@ def resolve_forbid(entries, names, lookup):
             i = where[contig]
             k = lookup(i, left, right, strand)
         except KeyError:
-            raise ForbidError("--forbid: no such ORF in its contig: %r" % line) from None
+            raise ForbidError("%s: no such ORF in its contig: %r" % (flag, line)) from None
         if out[i] is None:
             out[i] = []
         out[i].append(k)
     return out
 
 
-def format_reannotation(names, status, offsets, genes, delta):
-    """--reannotation OUT: per contig with status >= 0 the block write_tabular prints, with "#delta:\t<repr(delta)>" behind its #id line."""
+def format_reannotation(names, status, offsets, genes, delta, unmet=None):
+    """--reannotation OUT: per contig with status >= 0 the block write_tabular prints, with "#delta:\t<repr(delta)>" behind its #id line
+    and, with --require (unmet given), "#unmet:\t<count>" behind that."""
     import io
 
     from .writers import write_tabular
@@ -127,7 +133,7 @@ def format_reannotation(names, status, offsets, genes, delta):
         one = io.StringIO()
         write_tabular(one, nm, genes[offsets[i]:offsets[i + 1]])
         head, rest = one.getvalue().split("\n", 1)
-        buf.write(head + "\n#delta:\t" + repr(float(delta[i])) + "\n" + rest)
+        buf.write(head + "\n#delta:\t" + repr(float(delta[i])) + "\n" + ("" if unmet is None else "#unmet:\t%d\n" % int(unmet[i])) + rest)
     return buf.getvalue()
 
 
@@ -327,16 +333,19 @@ def main(argv=None):
     margin_parts = []  # --margins: (status, offsets, records) of every batch, in order
     drop_parts = []  # --drop-margins: the same of the drop margins
     repl_parts = []  # --drop-replacements: (status, offsets, records, genes) of every batch, in order
-    reann_parts = []  # --reannotation: (status, offsets, genes, delta) of every batch, in order
-    forbid_entries = None
-    if args.forbid is not None:
-        try:
+    reann_parts = []  # --reannotation: (status, offsets, genes, delta[, unmet]) of every batch, in order
+    forbid_entries = require_entries = None
+    try:
+        if args.forbid is not None:
             with open(args.forbid) as fh:
                 forbid_entries = parse_forbid(fh)
-        except (OSError, ForbidError) as e:
-            drop_context()
-            sys.stderr.write("Error: %s\n" % e)
-            return 2
+        if args.require is not None:
+            with open(args.require) as fh:
+                require_entries = parse_forbid(fh, "--require")
+    except (OSError, ForbidError) as e:
+        drop_context()
+        sys.stderr.write("Error: %s\n" % e)
+        return 2
     mine = list(range(n_total)) if world == 1 else partition(fa.lens.tolist(), world)[rank]
 
     def annotate_flat(idx):  # this rank's contigs, in batches of --batch-bases, straight from the C buffer of the FASTA reader
@@ -357,7 +366,7 @@ def main(argv=None):
             if lo >= len(idx):
                 break
         t_parts["batches"] = len(cuts)
-        if forbid_entries is not None:  # the re-annotation works on the batch resident on one context: the batches one after the other
+        if forbid_entries is not None or require_entries is not None:  # the re-annotation works on the batch resident on one context: the batches one after the other
             parts = []
             for lo, hi in cuts:
                 t0 = time.perf_counter()
@@ -376,7 +385,11 @@ def main(argv=None):
                     drop_parts.append(ann.drop_margins())
                 names = [fa.names[int(i)] for i in idx[lo:hi]]
                 here = set(names)
-                reann_parts.append(ann.reannotate(resolve_forbid([e for e in forbid_entries if e[3] in here], names, ann.orf_index)))
+                refused = resolve_forbid([e for e in forbid_entries or [] if e[3] in here], names, ann.orf_index)
+                if require_entries is None:
+                    reann_parts.append(ann.reannotate(refused))
+                else:
+                    reann_parts.append(ann.constrain(refused, resolve_forbid([e for e in require_entries if e[3] in here], names, ann.orf_index, "--require")))
                 t_parts["upload_s"] += t1 - t0; t_parts["run_s"] += t2 - t1; t_parts["download_s"] += t3 - t2
         elif len(cuts) == 1 and n_gpu == 1:
             lo, hi = cuts[0]
@@ -425,12 +438,12 @@ def main(argv=None):
         counts = np.concatenate([np.diff(p[1]) for p in parts])
         return st, np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), genes
 
-    if forbid_entries is not None:
-        known = set(fa.names)
-        for e in forbid_entries:
+    known = set(fa.names)
+    for flag, entries in (("--forbid", forbid_entries), ("--require", require_entries)):
+        for e in entries or []:
             if e[3] not in known:
                 drop_context()
-                sys.stderr.write("Error: --forbid: no such ORF in its contig: %r\n" % e[4])
+                sys.stderr.write("Error: %s: no such ORF in its contig: %r\n" % (flag, e[4]))
                 return 2
     try:
         merged = run_sharded_flat(mine, annotate_flat, rank, world, dist, mine=(mine, n_total))
@@ -492,7 +505,8 @@ def main(argv=None):
             q_counts = np.concatenate([np.diff(m[1]) for m in reann_parts])
             q_offsets = np.concatenate([[0], np.cumsum(q_counts)]).astype(np.int64)
             with open(args.reannotation, "w") as fh:
-                fh.write(format_reannotation(fa.names, q_status, q_offsets, np.concatenate([m[2] for m in reann_parts]), np.concatenate([m[3] for m in reann_parts])))
+                fh.write(format_reannotation(fa.names, q_status, q_offsets, np.concatenate([m[2] for m in reann_parts]), np.concatenate([m[3] for m in reann_parts]),
+                                             np.concatenate([m[4] for m in reann_parts]) if args.require is not None else None))
     t_end = time.perf_counter()
     if os.environ.get("PHX_CLI_TIMING") and rank == 0:
         sys.stderr.write("PHX_CLI_TIMING " + json.dumps({"parse_s": round(t_parsed - t_start, 4), "gpu_s": round(t_gpu - t_parsed, 4), "format_s": round(t_fmt - t_gpu, 4),

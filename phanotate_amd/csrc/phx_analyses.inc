@@ -531,11 +531,15 @@ static void reann_batch(phx_ctx *c, DBatch *b, DReann *q) {
     b->dist = (uint64_t *)c->b_qdist.p; b->parent = (int32_t *)c->b_qparent.p; b->path = (int32_t *)c->b_qpath.p;
     b->genes = (DGene *)c->b_qgenes.p; b->genes_c = nullptr; b->gpack = 0; b->gene_total = (uint32_t *)c->b_qgtot.p;
     b->tie = (uint8_t *)c->b_qtie.p; b->tie_cap = cap_of(c->b_qtie, 1, 0);
-    q->forb = (const uint8_t *)c->b_qforb.p; q->mask = (uint32_t *)c->b_qmask.p; q->sel = (const int32_t *)c->b_qsel.p;
-    q->gplan = (uint8_t *)c->b_qplan.p; q->dist0 = (const uint64_t *)c->b_dist.p; q->rec = (DReannRec *)c->b_qrec.p;
+    b->dist_stride = c->qstride; // (one limb wider than the run's when a contig is solved under the required policy, §16)
+    const size_t n1 = (size_t)c->n + 1, mw = (size_t)c->tot_edge / 32 + 2;
+    q->forb = (const uint8_t *)c->b_qforb.p; q->mask = (uint32_t *)c->b_qmask.p; q->req = q->mask + mw;
+    q->sel = (const int32_t *)c->b_qsel.p; q->pin = q->sel + n1; q->nreq = q->sel + 2 * n1; q->kreq = (int32_t *)c->b_qsel.p + 3 * n1;
+    q->gplan = (uint8_t *)c->b_qplan.p; q->dist0 = (const uint64_t *)c->b_dist.p; q->stride0 = c->n_limbs; q->rec = (DReannRec *)c->b_qrec.p;
 }
 
-// Solves the contigs of h_qsel again without the ORFs of `forb` (tap order); the records into h_qrec, the genes into h_qgenes.
+// Solves the contigs of h_qsel again (1: masked, 2: under the required policy) with the ORFs of `forb` (tap order; 1 = refused, 2 = required,
+// h_qnreq of them per contig); the records into h_qrec, the genes into h_qgenes.
 static int reann_compute(phx_ctx *c, const uint8_t *forb, const int64_t *orf_offsets) {
     const size_t n = (size_t)c->n, V = (size_t)c->tot_node, E = (size_t)c->tot_edge, N = (size_t)c->tot_orf;
     const size_t limbs = (size_t)std::max(c->n_limbs, 2);
@@ -544,13 +548,16 @@ static int reann_compute(phx_ctx *c, const uint8_t *forb, const int64_t *orf_off
     std::vector<uint8_t> &dforb = c->h_qdforb;
     dforb.assign(N + 1, 0);
     std::vector<int> order;
-    int nlm = 0;
+    int nlm = 0, pinm = 0;
     bool any = false;
+    std::vector<int32_t> &dsel = c->h_qdsel; // what the kernels read: sel | pin | nreq | kreq (zero), n + 1 entries each
+    dsel.assign(4 * (n + 1), 0);
     for (size_t i = 0; i < n; i++) {
         if (!c->h_qsel[i]) continue;
         any = true;
         const DMeta &m = c->meta[i];
-        nlm |= nl_class_bit(m.sssp_nl);
+        if (c->h_qsel[i] == 2) { pinm |= nl_class_bit(m.sssp_nl); dsel[n + 1 + i] = 1; dsel[2 * (n + 1) + i] = c->h_qnreq[i]; }
+        else { nlm |= nl_class_bit(m.sssp_nl); dsel[i] = 1; }
         const uint8_t *from = forb + orf_offsets[i];
         each_group_in_reference_order(c, i, order, [&](int32_t first, int32_t k) {
             if (k > 0 && first >= 0 && (int64_t)first + k <= m.n_orf) memcpy(dforb.data() + m.orf_off + first, from, (size_t)k);
@@ -561,16 +568,18 @@ static int reann_compute(phx_ctx *c, const uint8_t *forb, const int64_t *orf_off
     c->h_qgenes.clear();
     if (!any) return PHX_OK;
     int rc;
-    if ((rc = ensure(c, c->b_qmeta, (n + 1) * sizeof(DMeta))) || (rc = ensure(c, c->b_qtot, sizeof(DTotals))) || (rc = ensure(c, c->b_qdist, (V + 1) * limbs * 8)) ||
+    c->qstride = (int)limbs + (pinm ? 1 : 0);
+    const size_t mw = E / 32 + 2; // words of one bitmap; the required ORFs' follows the refused ORFs' in b_qmask
+    if ((rc = ensure(c, c->b_qmeta, (n + 1) * sizeof(DMeta))) || (rc = ensure(c, c->b_qtot, sizeof(DTotals))) || (rc = ensure(c, c->b_qdist, (V + 1) * (size_t)c->qstride * 8)) ||
         (rc = ensure(c, c->b_qparent, (V + 1) * 4)) || (rc = ensure(c, c->b_qpath, (V + 1) * 4)) || (rc = ensure(c, c->b_qgenes, (V + n + 1) * sizeof(DGene))) || // (a path has at most V / 2 pairs, one replaced by k_rs_inorder takes new slots)
-        (rc = ensure(c, c->b_qgtot, 16)) || (rc = ensure(c, c->b_qmask, (E / 32 + 2) * 4)) || (rc = ensure(c, c->b_qforb, N + 1)) || (rc = ensure(c, c->b_qsel, (n + 1) * 4)) ||
+        (rc = ensure(c, c->b_qgtot, 16)) || (rc = ensure(c, c->b_qmask, 2 * mw * 4)) || (rc = ensure(c, c->b_qforb, N + 1)) || (rc = ensure(c, c->b_qsel, 4 * (n + 1) * 4)) ||
         (rc = ensure(c, c->b_qplan, V / 32 + n + 2)) || (rc = ensure(c, c->b_qrec, (n + 1) * sizeof(DReannRec))))
         return rc;
     if (!c->b_qtie.p && (rc = ensure(c, c->b_qtie, (size_t)std::max<int64_t>(c->tie_seen, 1 << 20)))) return rc;
     if ((rc = analysis_events(c))) return rc;
     hipStream_t s = c->stream;
     HIPCHK(c, hipMemcpyAsync(c->b_qforb.p, dforb.data(), N + 1, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->b_qsel.p, c->h_qsel.data(), n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->b_qsel.p, dsel.data(), 4 * (n + 1) * 4, hipMemcpyHostToDevice, s));
     DTotals &tot = c->h_qtot;
     uint32_t &gtot = c->h_qgtot;
     gtot = 0;
@@ -583,12 +592,13 @@ static int reann_compute(phx_ctx *c, const uint8_t *forb, const int64_t *orf_off
         HIPCHK(c, hipMemsetAsync(c->b_qtot.p, 0, sizeof(DTotals), s));
         HIPCHK(c, hipMemsetAsync(c->b_qgtot.p, 0, 16, s));
         HIPCHK(c, hipMemsetAsync(c->b_qrec.p, 0, (n + 1) * sizeof(DReannRec), s));
-        HIPCHK(c, hipMemsetAsync(c->b_qmask.p, 0, (E / 32 + 2) * 4, s));
+        HIPCHK(c, hipMemsetAsync(c->b_qmask.p, 0, (pinm ? 2 : 1) * mw * 4, s));
+        if (pinm && attempt) HIPCHK(c, hipMemsetAsync((int32_t *)c->b_qsel.p + 3 * (n + 1), 0, (n + 1) * 4, s)); // k_rs_mask counts again
         phxk_reann_mask(&b, &q, s);
         HIPCHK(c, hipEventRecord(c->aev[1], s));
-        phxk_reann_solve(&b, &q, nlm, s);
+        phxk_reann_solve(&b, &q, nlm, pinm, s);
         HIPCHK(c, hipEventRecord(c->aev[2], s));
-        phxk_reann_finish(&b, &q, nlm, s);
+        phxk_reann_finish(&b, &q, nlm, pinm, s);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(c->h_qrec.data(), c->b_qrec.p, n * sizeof(DReannRec), hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipEventRecord(c->aev[3], s));
@@ -617,8 +627,10 @@ static int reann_compute(phx_ctx *c, const uint8_t *forb, const int64_t *orf_off
     return PHX_OK;
 }
 
-int phx_reannotate_flat(phx_ctx *c, const uint8_t *forbid, const int64_t *orf_offsets, uint32_t flags, phx_gene *genes, int64_t cap, int64_t *offsets, int32_t *status,
-                        double *delta, int64_t *total_out) {
+// phx_reannotate_flat (require and unmet null, forbid needed) and phx_constrain_flat (either set may be null: empty) are one solve on one set
+// of buffers; the cached result is keyed on both sets (h_qforb holds 1 = refused, 2 = required per ORF).
+static int reann_flat(phx_ctx *c, const char *who, bool need_forbid, const uint8_t *forbid, const uint8_t *require, const int64_t *orf_offsets, uint32_t flags, phx_gene *genes,
+                      int64_t cap, int64_t *offsets, int32_t *status, double *delta, int32_t *unmet, int64_t *total_out) {
     if (!c || (c->n > 0 && (!offsets || !status || !delta || !orf_offsets))) return PHX_E_ARG;
     { const int ra = after_run(c); if (ra) return ra; }
     { const int rf = fetch_meta(c); if (rf) return rf; }
@@ -630,19 +642,28 @@ int phx_reannotate_flat(phx_ctx *c, const uint8_t *forbid, const int64_t *orf_of
         if (reann_status(c, i) >= 0) acc += c->meta[(size_t)i].n_orf;
     }
     if (c->n > 0 && orf_offsets[c->n] != acc) return PHX_E_ARG;
-    if (acc > 0 && !forbid) return PHX_E_ARG;
+    if (acc > 0 && need_forbid && !forbid) return PHX_E_ARG;
     const size_t N = (size_t)acc;
-    if (!(c->done.reann && c->h_qflags == flags && c->h_qforb.size() == N && (N == 0 || memcmp(c->h_qforb.data(), forbid, N) == 0))) {
+    std::vector<uint8_t> &code = c->h_qcode; // per ORF: 1 = refused, 2 = required
+    code.assign(N, 0);
+    for (size_t k = 0; k < N; k++) {
+        const bool f = forbid && forbid[k], r = require && require[k];
+        if (f && r) { c->err = std::string(who) + ": an ORF is both refused and required"; return PHX_E_ARG; } // before any kernel
+        code[k] = f ? 1 : (r ? 2 : 0);
+    }
+    if (!(c->done.reann && c->h_qflags == flags && c->h_qforb == code)) {
         c->done.reann = false;
         c->h_qsel.assign((size_t)c->n, 0);
+        c->h_qnreq.assign((size_t)c->n, 0);
         for (int i = 0; i < c->n; i++) {
+            int32_t nf = 0, nr = 0;
+            for (int64_t k = orf_offsets[i]; k < orf_offsets[i + 1]; k++) { nf += code[(size_t)k] == 1; nr += code[(size_t)k] == 2; }
+            c->h_qnreq[(size_t)i] = nr;
             if (!reann_contig(c, i)) continue;
-            bool want = (flags & 1u) != 0;
-            for (int64_t k = orf_offsets[i]; k < orf_offsets[i + 1] && !want; k++) want = forbid[k] != 0;
-            c->h_qsel[(size_t)i] = want ? 1 : 0;
+            c->h_qsel[(size_t)i] = nr ? 2 : ((flags & 1u) != 0 || nf ? 1 : 0);
         }
-        { const int rq = reann_compute(c, forbid, orf_offsets); if (rq) { (void)hipStreamSynchronize(c->stream); return rq; } } // (nothing of a failed solve stays in flight)
-        c->h_qforb.assign(forbid, forbid + N);
+        { const int rq = reann_compute(c, code.data(), orf_offsets); if (rq) { (void)hipStreamSynchronize(c->stream); return rq; } } // (nothing of a failed solve stays in flight)
+        c->h_qforb = code;
         c->h_qflags = flags;
         c->done.reann = true;
     }
@@ -651,10 +672,12 @@ int phx_reannotate_flat(phx_ctx *c, const uint8_t *forbid, const int64_t *orf_of
     for (int i = 0; i < c->n; i++) {
         const int32_t st = reann_status(c, i);
         offsets[i] = total; status[i] = st; delta[i] = std::numeric_limits<double>::infinity();
+        if (unmet) unmet[i] = c->h_qnreq[(size_t)i]; // (no result: every required ORF is unmet)
         if (st < 0) continue;
         if (c->h_qsel[(size_t)i]) {
             const DReannRec &r = c->h_qrec[(size_t)i];
             status[i] = r.status; delta[i] = r.delta;
+            if (unmet) unmet[i] = r.unmet;
             if (r.status >= 0) total += r.n_genes;
         } else {
             if (st != PHX_S_NOPATH) delta[i] = 0.0;
@@ -672,8 +695,19 @@ int phx_reannotate_flat(phx_ctx *c, const uint8_t *forbid, const int64_t *orf_of
         const DGene *src = c->h_qsel[(size_t)i] ? c->h_qgenes.data() + c->h_qrec[(size_t)i].gene_off : (const DGene *)c->h_genes.p + (size_t)c->res[(size_t)i].gene_off;
         memcpy(genes + offsets[i], src, sizeof(phx_gene) * (size_t)k);
     }
-    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_reannotate_flat"; return PHX_E_NOMEM; }
+    } catch (const std::bad_alloc &) { c->err = std::string("out of memory in ") + who; return PHX_E_NOMEM; }
     return PHX_OK;
+}
+
+int phx_reannotate_flat(phx_ctx *c, const uint8_t *forbid, const int64_t *orf_offsets, uint32_t flags, phx_gene *genes, int64_t cap, int64_t *offsets, int32_t *status,
+                        double *delta, int64_t *total_out) {
+    return reann_flat(c, "phx_reannotate_flat", true, forbid, nullptr, orf_offsets, flags, genes, cap, offsets, status, delta, nullptr, total_out);
+}
+
+int phx_constrain_flat(phx_ctx *c, const uint8_t *forbid, const uint8_t *require, const int64_t *orf_offsets, uint32_t flags, phx_gene *genes, int64_t cap, int64_t *offsets,
+                       int32_t *status, double *delta, int32_t *unmet, int64_t *total_out) {
+    if (!c || (c->n > 0 && !unmet)) return PHX_E_ARG;
+    return reann_flat(c, "phx_constrain_flat", false, forbid, require, orf_offsets, flags, genes, cap, offsets, status, delta, unmet, total_out);
 }
 
 int phx_orf_offsets(phx_ctx *c, int64_t *orf_offsets) {
@@ -704,7 +738,8 @@ int phx_tap_repath(phx_ctx *c, int32_t contig, int32_t *path, int32_t cap, int32
     }
     if (dist_limbs) {
         if (cap_limbs < m.sssp_nl) return PHX_E_ARG;
-        const size_t tgt = (size_t)m.node_off * (size_t)c->n_limbs + ((size_t)m.n_node - 1) * (size_t)m.sssp_nl;
+        // (a contig solved under the required policy keeps one limb more per node: the W-sum is the low sssp_nl limbs of its distance)
+        const size_t tgt = (size_t)m.node_off * (size_t)c->qstride + ((size_t)m.n_node - 1) * (size_t)(m.sssp_nl + (c->h_qsel[(size_t)contig] == 2 ? 1 : 0));
         HIPCHK(c, hipMemcpy(dist_limbs, (uint64_t *)c->b_qdist.p + tgt, (size_t)m.sssp_nl * 8, hipMemcpyDeviceToHost));
     }
     return PHX_OK;

@@ -184,11 +184,14 @@ __device__ void walk_path(const DBatch &b, DMeta *meta, IoShared<IO_T> *sh) {
 
 // MASKED (phx_resolve.inc): `mask` holds one bit per in-edge slot of the batch (bit edge_off + e); a refused edge is no edge — it is never tight,
 // whatever the distances say.  The run's instantiations (MASKED = false) do not look at `mask`.
-template <int NL, int IO_T, bool MASKED = false>
-__device__ void inorder_contig(const DBatch &b, DMeta *meta, IoShared<IO_T> *sh, const uint32_t *mask = nullptr) {
+// REQ (the pinned re-annotation, DESIGN.md §16; with MASKED, on one limb more than the contig's class): an edge whose bit is set in `req` weighs
+// W - 2^(64 (NL - 1)), as in the sweep that made the distances (lds_sweep under RcCfg).
+template <int NL, int IO_T, bool MASKED = false, bool REQ = false>
+__device__ void inorder_contig(const DBatch &b, DMeta *meta, IoShared<IO_T> *sh, const uint32_t *mask = nullptr, const uint32_t *req = nullptr) {
     const int tid = threadIdx.x;
     const uint64_t mbase = MASKED ? (uint64_t)meta->edge_off : 0ull;
     auto refused = [&](uint32_t e) -> bool { const uint64_t x = mbase + e; return ((mask[x >> 5] >> (x & 31)) & 1u) != 0; };
+    auto required = [&](uint32_t e) -> bool { const uint64_t x = mbase + e; return ((req[x >> 5] >> (x & 31)) & 1u) != 0; };
     const int V = meta->n_node;
     const bool walked = meta->n_path >= 2; // else the solver's parents run in a circle (a zero-length cycle of tight edges): start from source and target alone
     const int n = walked ? meta->n_path : 2; // path[0] = source ... path[n-1] = target
@@ -208,7 +211,8 @@ __device__ void inorder_contig(const DBatch &b, DMeta *meta, IoShared<IO_T> *sh,
         if constexpr (MASKED) { if (refused(e)) return false; }
         const uint32_t sw = esrc[e];
         const WInt<NL> du = wi_load<NL>(dist + (size_t)ESRC_NODE(sw) * NL);
-        const WInt<NL> w = ewl ? wi_load<NL>(ewl + (size_t)e * NL) : ew_decode<NL>(edge_wenc(sw, ew, e, gt));
+        WInt<NL> w = ewl ? wi_load<NL>(ewl + (size_t)e * NL) : ew_decode<NL>(edge_wenc(sw, ew, e, gt));
+        if constexpr (REQ) { if (required(e)) w.v[NL - 1] -= 1ull; }
         return !wi_unreached<NL>(du) && wi_eq<NL>(wi_add<NL>(du, w), dv);
     };
     // ---- 1. does any node of the path have a tight in-edge besides its parent edge? ----
@@ -250,6 +254,7 @@ __device__ void inorder_contig(const DBatch &b, DMeta *meta, IoShared<IO_T> *sh,
                 const uint32_t sw = esrc[ee];
                 u[q] = ESRC_NODE(sw);
                 w[q] = ewl ? wi_load<NL>(ewl + (size_t)ee * NL) : ew_decode<NL>(edge_wenc(sw, ew, ee, gt));
+                if constexpr (REQ) { if (required(ee)) w[q].v[NL - 1] -= 1ull; }
             }
 #pragma unroll
             for (int q = 0; q < 4; q++) {

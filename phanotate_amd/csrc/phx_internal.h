@@ -384,14 +384,21 @@ struct DReannRec { // per contig that was solved again: what the host reads
     int64_t gene_off;  // first record in the re-annotation's gene buffer
     double delta;      // float(D_F - D) / 1000.0; +inf: no path in G_F
     int32_t n_path, tie;
+    int32_t unmet, pad_;   // required ORFs the result does not call (all of them where there is no result)
 };
 struct DReann {
-    const uint8_t *forb;   // per ORF (at orf_off, device order): 1 = refused
+    const uint8_t *forb;   // per ORF (at orf_off, device order): 1 = refused, 2 = required (pinned re-annotation, §16)
     uint32_t *mask;        // one bit per in-edge slot of the batch (bit edge_off + e), cleared per call
-    const int32_t *sel;    // per contig: 1 = solve it again
+    const int32_t *sel;    // per contig: 1 = solve it again (no required ORF)
     uint8_t *gplan;        // window plans beyond RS_PLAN_LDS windows: contig i at node_off / 32 + i
     const uint64_t *dist0; // the run's distances (D)
     DReannRec *rec;
+    // the pinned re-annotation (§16); behind the fields above, whose places in the kernels' argument block stay
+    uint32_t *req;         // as `mask`, for the required ORFs' edges (only touched when a contig has some)
+    const int32_t *pin;    // per contig: 1 = solve it again under the required policy, on one limb more (never with sel)
+    const int32_t *nreq;   // per contig: required ORFs (|R|)
+    int32_t *kreq;         // per contig: required ORFs whose edge exists (k_rs_mask counts them): the bound of the solver's cycle guard
+    int32_t stride0;       // limbs per node of dist0 (the run's DBatch.dist_stride; the re-annotation's own may be one wider)
 };
 
 #ifdef __cplusplus
@@ -442,8 +449,8 @@ void phxk_repl_pick(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl
 void phxk_repl_cross(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream); //   cross winners and their delta chains,
 void phxk_repl_walk(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int fill, void *stream);    //   detour lengths (fill 0) / detours, genes, records (1)
 void phxk_reann_mask(const DBatch *b, const DReann *q, void *stream);                 // masked re-annotation (phx_resolve.inc): the refused ORFs' in-edge bits,
-void phxk_reann_solve(const DBatch *b, const DReann *q, int nl_mask, void *stream);   //   the masked sweep (b: the re-annotation's view of the batch),
-void phxk_reann_finish(const DBatch *b, const DReann *q, int nl_mask, void *stream);  //   in-order parents on G_F, path, genes, delta
+void phxk_reann_solve(const DBatch *b, const DReann *q, int nl_mask, int pin_mask, void *stream);   //   the masked sweep (b: the re-annotation's view of the batch; pin_mask: the classes with required ORFs),
+void phxk_reann_finish(const DBatch *b, const DReann *q, int nl_mask, int pin_mask, void *stream);  //   in-order parents on G_F, path, genes, delta
 #ifdef __cplusplus
 }
 #endif

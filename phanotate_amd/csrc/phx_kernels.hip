@@ -400,17 +400,24 @@ void phxk_repl_walk(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl
 size_t phxk_sssp_lds_bytes(int V, int nl) { return sssp_lds_bytes(V, nl); }
 // masked re-annotation (phx_resolve.inc): b is the re-annotation's view of the batch (outputs of its own)
 void phxk_reann_mask(const DBatch *b, const DReann *q, void *stream) { hipLaunchKernelGGL(k_rs_mask, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), 0, (hipStream_t)stream, *b, *q); }
-void phxk_reann_solve(const DBatch *b, const DReann *q, int nl_mask, void *stream) {
+void phxk_reann_solve(const DBatch *b, const DReann *q, int nl_mask, int pin_mask, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     if (nl_mask & 1) launch_lds(k_rs_lds<2>, rs_lds_bytes<2>(), b, s, *b, *q);
     if (nl_mask & 2) launch_lds(k_rs_lds<4>, rs_lds_bytes<4>(), b, s, *b, *q);
     if (nl_mask & 4) launch_lds(k_rs_lds<8>, rs_lds_bytes<8>(), b, s, *b, *q);
     if (nl_mask & 8) launch_lds(k_rs_lds<17>, rs_lds_bytes<17>(), b, s, *b, *q);
+    // pin_mask: the classes of the contigs with required ORFs (solved on one limb more, §16)
+    if (pin_mask & 1) launch_lds(k_rc_lds<2>, rc_lds_bytes<3>(), b, s, *b, *q);
+    if (pin_mask & 2) launch_lds(k_rc_lds<4>, rc_lds_bytes<5>(), b, s, *b, *q);
+    if (pin_mask & 4) launch_lds(k_rc_lds<8>, rc_lds_bytes<9>(), b, s, *b, *q);
+    if (pin_mask & 8) launch_lds(k_rc_lds<17>, rc_lds_bytes<18>(), b, s, *b, *q);
 }
-void phxk_reann_finish(const DBatch *b, const DReann *q, int nl_mask, void *stream) {
+void phxk_reann_finish(const DBatch *b, const DReann *q, int nl_mask, int pin_mask, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     if (b->mean_len < 8192) NL_LAUNCH_T(k_rs_inorder, 64, nl_mask, dim3(b->n_contig), *b, *q); // as phxk_inorder: one wavefront per short contig
     else NL_LAUNCH_T(k_rs_inorder, IO_T_FULL, nl_mask, dim3(b->n_contig), *b, *q);
+    if (b->mean_len < 8192) NL_LAUNCH_T(k_rc_inorder, 64, pin_mask, dim3(b->n_contig), *b, *q);
+    else NL_LAUNCH_T(k_rc_inorder, IO_T_FULL, pin_mask, dim3(b->n_contig), *b, *q);
     hipLaunchKernelGGL(k_rs_fin, dim3((unsigned)((b->n_contig + 63) / 64)), dim3(64), 0, s, *b, *q);
 }
 // one workgroup for up to 1024 contigs; larger batches in two passes of a workgroup per 256 contigs

@@ -12,20 +12,23 @@
 //                  G_F, on the rows as the graph stage left them (no k_edges_expand).  What MASKED means is said at the policy there.
 //   k_rs_inorder   inorder_contig<NL, IO_T, MASKED = true>: the reference's parent rule on G_F.
 //   k_rs_fin       per contig: status, delta = float(D_F - D) / 1000.0, the record the host reads.
+// The pinned re-annotation (§16: keep a chosen set of ORFs) is the same chain for the contigs that have required ORFs: k_rs_mask sets their
+// edges' bits in a second bitmap and counts them, k_rc_lds / k_rc_inorder run the sweep and the parent rule under the REQ policy on one limb
+// more, k_rs_fin splits the target's distance into the count of required edges and the W-sum.
 // The bitmap only ever holds bits of explicit rows: an ORF edge runs open -> close and a coded gap edge (a connector) close -> open, so no
 // ORF shares both ends with a coded row, and k_rs_mask skips coded rows besides.  k_rs_lds therefore tests explicit rows only, and the
 // masked inorder_contig, which tests every row, sees the same graph.
 // Bounds: the sweep and round caps of k_sssp_lds (PHX_S_NEGCYCLE), no waiting between workgroups, no index from the caller on the device
 // (the host checks the offsets; `forb` is one byte per ORF of the batch, `sel` one int per contig).
 
-template <int NL> struct RsCfg { static constexpr int RING = 1024, ECAP = 1024; static constexpr bool MASKED = true; };
-template <> struct RsCfg<17> { static constexpr int RING = 256, ECAP = 512; static constexpr bool MASKED = true; }; // 1088 bits: 109 KB of LDS instead of 283
+template <int NL> struct RsCfg { static constexpr int RING = 1024, ECAP = 1024; static constexpr bool MASKED = true, REQ = false; };
+template <> struct RsCfg<17> { static constexpr int RING = 256, ECAP = 512; static constexpr bool MASKED = true, REQ = false; }; // 1088 bits: 109 KB of LDS instead of 283
 template <int NL>
 __host__ __device__ constexpr size_t rs_lds_bytes() { return (size_t)(RsCfg<NL>::RING + 1) * NL * 8 + (size_t)RsCfg<NL>::ECAP * ((size_t)NL * 8 + 4) + RS_PLAN_LDS + 64; }
 
 __global__ __launch_bounds__(NT) void k_rs_mask(DBatch b, DReann q) {
     const DMeta *meta = &b.meta[blockIdx.x];
-    if (!q.sel[blockIdx.x] || !mg_contig(meta)) return;
+    if (!(q.sel[blockIdx.x] | q.pin[blockIdx.x]) || !mg_contig(meta)) return;
     const DOrf *orf = b.orf + meta->orf_off;
     const DGrp *grp = b.grp + meta->grp_off;
     const int32_t *onode = b.onode + meta->orf_off;
@@ -35,14 +38,19 @@ __global__ __launch_bounds__(NT) void k_rs_mask(DBatch b, DReann q) {
     const uint64_t ebase = (uint64_t)meta->edge_off;
     const int V = meta->n_node;
     for (int k = (int)blockIdx.y * NT + (int)threadIdx.x; k < meta->n_orf; k += (int)gridDim.y * NT) {
-        if (!forb[k]) continue;
+        const uint8_t f = forb[k];
+        if (!f) continue;
         const DOrf o = orf[k];
         const int sn = onode[k], tn = grp[o.grp].node;
         const bool fwd = o.frame > 0;
         const int u = fwd ? sn : tn, v = fwd ? tn : sn; // start -> stop on the forward strand, stop -> start on the reverse (functions.py:310-316)
         if (u < 0 || v < 0 || u >= V || v >= V) continue;
         for (uint32_t x = in_off[v], x1 = in_off[v + 1]; x < x1; x++)
-            if (!ESRC_IS_GAP(esrc[x]) && ESRC_NODE(esrc[x]) == (uint32_t)u) { atomicOr(&q.mask[(ebase + x) >> 5], 1u << ((ebase + x) & 31)); break; } // (no such edge: the ORF is ignored)
+            if (!ESRC_IS_GAP(esrc[x]) && ESRC_NODE(esrc[x]) == (uint32_t)u) { // (no such edge: the ORF is ignored)
+                atomicOr(&(f == 2 ? q.req : q.mask)[(ebase + x) >> 5], 1u << ((ebase + x) & 31));
+                if (f == 2) atomicAdd(&q.kreq[blockIdx.x], 1); // k of §16: the required edges that exist
+                break;
+            }
     }
 }
 
@@ -68,6 +76,42 @@ __global__ __launch_bounds__(IO_T) void k_rs_inorder(DBatch b, DReann q) {
     inorder_contig<NL, IO_T, true>(b, meta, &sh, q.mask);
 }
 
+// ---- the pinned re-annotation (DESIGN.md §16): the contigs with required ORFs, DReann.pin ----
+// A contig of limb class NL is solved in NL + 1 limbs with M = 2^(64 NL): a required edge weighs W - M, so the top limb of a distance is
+// minus the count of required edges on its path (less one while the W-sum below is negative: rq_count) and the low NL limbs are the W-sum
+// in the contig's own class, which obeys the layout's bound as before.  Counts are <= V < 2^30, far from the unreached pattern's 2^62.
+// The ring of the 320-bit solve is halved (66 KB of LDS, two workgroups per CU, where 1024 entries would leave one).
+template <int NL1> struct RcCfg { static constexpr int RING = 1024, ECAP = 1024; static constexpr bool MASKED = true, REQ = true; };
+template <> struct RcCfg<5> { static constexpr int RING = 512, ECAP = 1024; static constexpr bool MASKED = true, REQ = true; };
+template <> struct RcCfg<18> { static constexpr int RING = 256, ECAP = 512; static constexpr bool MASKED = true, REQ = true; };
+template <int NL1>
+__host__ __device__ constexpr size_t rc_lds_bytes() { return (size_t)(RcCfg<NL1>::RING + 1) * NL1 * 8 + (size_t)RcCfg<NL1>::ECAP * ((size_t)NL1 * 8 + 4) + RS_PLAN_LDS + 64; }
+
+// NL: the contig's class; the sweep runs on NL + 1 limbs
+template <int NL>
+__global__ __launch_bounds__(SW_THREADS, NL == 2 ? 4 : 2) void k_rc_lds(DBatch b, DReann q) {
+    DMeta *meta = &b.meta[blockIdx.x];
+    const int V = meta->n_node;
+    if (!q.pin[blockIdx.x] || !mg_contig(meta) || meta->sssp_nl != NL) return;
+    lds_sweep<NL + 1, RcCfg<NL + 1>>(b, meta, V, q.mask, q.gplan, q.req, q.kreq[blockIdx.x]);
+}
+
+template <int NL, int IO_T>
+__global__ __launch_bounds__(IO_T) void k_rc_inorder(DBatch b, DReann q) {
+    __shared__ IoShared<IO_T> sh;
+    DMeta *meta = &b.meta[blockIdx.x];
+    if (!q.pin[blockIdx.x] || meta->sssp_nl != NL) return;
+    if (threadIdx.x == 0) { sh.flag = 0; meta->tie = 0; }
+    __syncthreads();
+    if (!mg_contig(meta)) return;
+    if (meta->n_path < 2 && meta->n_path != -1) return;
+    inorder_contig<NL + 1, IO_T, true, true>(b, meta, &sh, q.mask, q.req);
+}
+
+// the count of required edges on the best path: the top limb of the NL + 1 limbs at df
+template <int NL>
+__device__ int64_t rc_count(const uint64_t *df) { return rq_count<NL + 1>(wi_load<NL + 1>(df)); }
+
 template <int NL>
 __device__ double rs_delta(const uint64_t *df, const uint64_t *d0) {
     const WInt<NL> DF = wi_load<NL>(df), D = wi_load<NL>(d0);
@@ -77,15 +121,19 @@ __device__ double rs_delta(const uint64_t *df, const uint64_t *d0) {
 // a thread per contig: the record the host reads
 __global__ __launch_bounds__(64) void k_rs_fin(DBatch b, DReann q) {
     const int c = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (c >= b.n_contig || !q.sel[c]) return;
+    if (c >= b.n_contig || !(q.sel[c] | q.pin[c])) return;
     const DMeta *meta = &b.meta[c];
     DReannRec r;
+    const bool pinned = q.pin[c] != 0;
     r.status = meta->status; r.n_genes = 0; r.gene_off = 0; r.n_path = 0; r.tie = meta->tie; r.delta = __builtin_inf();
+    r.unmet = pinned ? q.nreq[c] : 0; r.pad_ = 0;
     if (meta->status >= 0 && meta->status != PHX_S_NOPATH && meta->n_path >= 2) {
         const int V = meta->n_node, nl = meta->sssp_nl;
-        const size_t t = (size_t)meta->node_off * b.dist_stride + (size_t)(V - 1) * nl;
-        const uint64_t *df = b.dist + t, *d0 = q.dist0 + t;
+        // the target's distance: the re-annotation's in its own stride (and one limb more when pinned: the W-sum is its low nl limbs), the run's in the run's
+        const uint64_t *df = b.dist + (size_t)meta->node_off * b.dist_stride + (size_t)(V - 1) * (nl + (pinned ? 1 : 0));
+        const uint64_t *d0 = q.dist0 + (size_t)meta->node_off * q.stride0 + (size_t)(V - 1) * nl;
         r.delta = nl == 2 ? rs_delta<2>(df, d0) : nl == 4 ? rs_delta<4>(df, d0) : nl == 8 ? rs_delta<8>(df, d0) : rs_delta<17>(df, d0);
+        if (pinned) r.unmet -= (int32_t)(nl == 2 ? rc_count<2>(df) : nl == 4 ? rc_count<4>(df) : nl == 8 ? rc_count<8>(df) : rc_count<17>(df));
         r.n_genes = meta->n_genes; r.gene_off = meta->gene_off; r.n_path = meta->n_path;
     }
     q.rec[c] = r;

@@ -352,7 +352,11 @@ __host__ __device__ inline size_t sssp_lds_bytes(int V, int nl) {
 // MASKED: the rows come through edge_wenc (coded gap edges from the contig's gap table, nothing written to DBatch.ew); an explicit row
 // whose bit is set in `mask` (one bit per in-edge slot of the batch) is no edge; the plan lives in LDS up to RS_PLAN_LDS windows, else in
 // the caller's `gplan`; gene slots always come from the shared counter.
-struct SwRun { static constexpr int RING = SW_RING, ECAP = SW_ECAP; static constexpr bool MASKED = false; };
+// REQ (the pinned re-annotation, RcCfg in phx_resolve.inc; always MASKED too): the sweep runs on one limb more than the contig's class, an
+// explicit row whose bit is set in `req` carries W - 2^(64 (NL - 1)) — the top limb of a distance is then minus the number of required edges
+// behind it, the limbs below the W-sum (rq_count) —, and a distance that counts more than `kreq` required edges ends the solve: only a cycle
+// through a required edge produces one (DESIGN.md §16).
+struct SwRun { static constexpr int RING = SW_RING, ECAP = SW_ECAP; static constexpr bool MASKED = false, REQ = false; };
 #define RS_PLAN_LDS 2048 // window-plan bytes kept in LDS (contigs of up to 65 536 nodes); longer plans live in DReann.gplan
 
 // in-edge slot e (source word sw) is refused: coded rows never are (phx_resolve.inc: the bitmap holds bits of explicit rows only)
@@ -362,13 +366,33 @@ __device__ __forceinline__ bool rs_refused(const uint32_t *mask, uint64_t ebase,
     const uint64_t x = ebase + e;
     return ((mask[x >> 5] >> (x & 31)) & 1u) != 0;
 }
+// in-edge slot e is required (REQ only; a bit of `req` as one of `mask`, explicit rows only)
+template <class P>
+__device__ __forceinline__ bool rs_required(const uint32_t *req, uint64_t ebase, uint32_t sw, uint32_t e) {
+    if (!P::REQ || ESRC_IS_GAP(sw)) return false;
+    const uint64_t x = ebase + e;
+    return ((req[x >> 5] >> (x & 31)) & 1u) != 0;
+}
+// required edges counted by a distance of NL limbs under REQ: minus its top limb, less the borrow of a negative W-sum in the limbs below
+template <int NL>
+__device__ __forceinline__ int64_t rq_count(const WInt<NL> &d) { return -(int64_t)(d.v[NL - 1] + (d.v[NL - 2] >> 63)); }
 template <class P>
 __device__ __forceinline__ long long sw_row(uint32_t sw, const long long *ew, uint32_t e, const long long *gt) { return P::MASKED ? edge_wenc(sw, ew, e, gt) : ew[e]; }
+// the integer of in-edge slot e as the sweep adds it: W, under REQ W - 2^(64 (NL - 1)) for a required row
+template <int NL, class P>
+__device__ __forceinline__ WInt<NL> sw_weight(uint32_t sw, const long long *ew, uint32_t e, const long long *gt, const uint32_t *req, uint64_t ebase) {
+    if constexpr (!P::REQ) return ew_decode<NL>(sw_row<P>(sw, ew, e, gt));
+    else {
+        WInt<NL> w = ew_decode<NL>(sw_row<P>(sw, ew, e, gt));
+        if (rs_required<P>(req, ebase, sw, e)) w.v[NL - 1] -= 1ull;
+        return w;
+    }
+}
 
 // The sweep of one contig by one workgroup of SW_THREADS threads: distances to b.dist, lowest-index tight parents to b.parent, then the
 // path and the genes.  V = meta->n_node (the caller has read it; after expand_contig's fence a second read would be a second load).
 template <int NL, class P>
-__device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const int V, const uint32_t *mask, uint8_t *gplan) {
+__device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const int V, const uint32_t *mask, uint8_t *gplan, const uint32_t *req = nullptr, const int kreq = 0) {
     constexpr int RING = P::RING, ECAP = P::ECAP;
     constexpr int EPT = (ECAP + SW_THREADS - 1) / SW_THREADS; // tile edges prefetched per thread
     extern __shared__ __align__(16) uint8_t smem[];
@@ -436,7 +460,7 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const in
         if (tid < NL) ring[(size_t)RING * NL + tid] = 0; // the constant-zero slot (the LDS is reused by the pass below)
         if (tid == 0) s_viol = 0;
         __syncthreads();
-        // registers that carry window k+1's data while window k iterates; bit j of r_mk: tile edge j of this thread is refused
+        // registers that carry window k+1's data while window k iterates; bit j of r_mk: tile edge j of this thread is refused, bit 16 + j: required
         uint32_t r_src[EPT];
         long long r_w[EPT];
         uint32_t r_mk = 0;
@@ -462,6 +486,7 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const in
                 r_src[j] = ESRC_NODE(sw);
                 r_w[j] = on ? sw_row<P>(sw, ew, e0n + i, gt) : 0ll;
                 if (on && rs_refused<P>(mask, ebase, sw, e0n + i)) r_mk |= 1u << j;
+                if (P::REQ && on && rs_required<P>(req, ebase, sw, e0n + i)) r_mk |= 0x10000u << j;
             }
         }
         for (int k = 0; k < nW && !bad; k++) {
@@ -499,6 +524,7 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const in
                         // source slot: a ring slot, or the constant-zero slot (the source node; and sources outside the
                         // ring, whose distance cannot change while this window iterates and is folded into the weight)
                         uint32_t sl = RING;
+                        if (P::REQ && ((r_mk >> (16 + j)) & 1u)) w.v[NL - 1] -= 1ull; // required: W - M, so the phases pay nothing for it either
                         if (P::MASKED && ((r_mk >> j) & 1u)) w = big; // refused: no edge (0 + "unreached" never wins), so the phases pay nothing for the mask
                         else if (u != (uint32_t)SRC) {
                             if ((int)u < loaded && (int)u + RING >= loaded) sl = u & (RING - 1);
@@ -527,6 +553,7 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const in
                     r_src[j] = ESRC_NODE(sw);
                     r_w[j] = on ? sw_row<P>(sw, ew, e0n + i, gt) : 0ll;
                     if (on && rs_refused<P>(mask, ebase, sw, e0n + i)) r_mk |= 1u << j;
+                    if (P::REQ && on && rs_required<P>(req, ebase, sw, e0n + i)) r_mk |= 0x10000u << j;
                 }
             }
 #ifdef SW_PROFILE
@@ -604,14 +631,17 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const in
                             if (u == (uint32_t)SRC) du = wi_load<NL>(ring + (size_t)RING * NL);
                             else if ((int)u < loaded && (int)u + RING >= loaded) du = wi_load<NL>(ring + (size_t)(u & (RING - 1)) * NL);
                             else du = wi_load<NL>(gdist + (size_t)u * NL);
-                            best = wi_min_bf<NL>(best, wi_add<NL>(du, ew_decode<NL>(sw_row<P>(sw, ew, e0 + i, gt))));
+                            best = wi_min_bf<NL>(best, wi_add<NL>(du, sw_weight<NL, P>(sw, ew, e0 + i, gt, req, ebase)));
                         }
                     }
                     best = wi_row_min<NL>(best, sub);
-                    if (act && sub == SW_LPN - 1 && wi_lt_bf<NL>(best, d0)) {
+                    // (REQ: an unreached node stays at the unreached pattern — relaxed among themselves, the nodes of a cycle through a required
+                    // edge that no path from the source reaches would go down by M a turn for ever; such a cycle is no cycle of the solve)
+                    if (act && sub == SW_LPN - 1 && wi_lt_bf<NL>(best, d0) && !(P::REQ && wi_unreached<NL>(best))) {
                         wi_store<NL>(myslot, best);
                         wi_store<NL>(ph ? gB : gA, best); // write-through
                         s_flag[it & 1] = 1;
+                        if (P::REQ && rq_count<NL>(best) > (int64_t)kreq) s_viol = 2; // more required edges than there are: a cycle through one
                     }
                 }
                 if (tid == 0) s_flag[(it + 1) & 1] = 0;
@@ -621,6 +651,7 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const in
                 if (!chg && (ph == 1 || inner > 0)) break;
                 if (++inner > 2 * SW_MAX + 16) { bad = true; break; }
             }
+            if (P::REQ && s_viol == 2) bad = true; // (read behind the phase's barrier; the next write is behind the next window's)
 #ifdef SW_PROFILE
             { long long t = wall_clock64(); t_iter += t - t_mark; t_mark = t; }
 #endif
@@ -642,8 +673,8 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const in
                 for (uint32_t e = in_off[v] + sub; e < e1; e += SW_LPN) {
                     const uint32_t sw = esrc[e];
                     if (rs_refused<P>(mask, ebase, sw, e)) continue;
-                    const WInt<NL> cand = wi_add<NL>(wi_load<NL>(gdist + (size_t)ESRC_NODE(sw) * NL), ew_decode<NL>(sw_row<P>(sw, ew, e, gt)));
-                    if (wi_lt_bf<NL>(cand, dv)) viol = true;
+                    const WInt<NL> cand = wi_add<NL>(wi_load<NL>(gdist + (size_t)ESRC_NODE(sw) * NL), sw_weight<NL, P>(sw, ew, e, gt, req, ebase));
+                    if (wi_lt_bf<NL>(cand, dv) && !(P::REQ && wi_unreached<NL>(cand))) viol = true;
                     if (wi_eq<NL>(cand, dv) && e < be && !wi_unreached<NL>(dv)) be = e;
                 }
             }
