@@ -39,7 +39,8 @@ extern "C" {
  *        (additions, version unchanged) phx_gene_repl, phx_replacements_flat, phx_tap_replacement, phx_replacements_ms,
  *        phx_replacement_stats, phx_format_replacements;
  *        (additions, version unchanged) phx_reannotate_flat, phx_orf_offsets, phx_tap_repath, phx_reannotate_ms;
- *        (addition, version unchanged: the suite pins 410) phx_constrain_flat — probe for the symbol, not for a version */
+ *        (addition, version unchanged: the suite pins 410) phx_constrain_flat — probe for the symbol, not for a version;
+ *        (additions, version unchanged) phx_scenarios_flat, phx_scenarios_ms, phx_scenario_chunks, phx_tap_scenario_path — probe for the symbol */
 #define PHX_MAX_CODONS 16
 
 /* library-level errors */
@@ -441,6 +442,39 @@ int phx_tap_repath(phx_ctx *ctx, int32_t contig, int32_t *path, int32_t cap, int
 /* device time of the last re-annotation (HIP events around device work only), ms[3]: mask build, masked solve, in-order parents + path +
  * genes + the copies to the host.  All 0 before the first. */
 int phx_reannotate_ms(phx_ctx *ctx, float *ms /* [3] */);
+
+/* ---- scenario batches: many masked re-annotations of the batch last run in one call ----
+ * n_scen scenarios, each a contig of the batch last run and a set F of its ORFs, solved side by side on the resident graph, one
+ * workgroup per scenario.  Scenario j is, by definition, the masked re-annotation above applied to contig scen_contig[j] with F = its
+ * listed ORFs: status[j], delta[j] and genes[offsets[j] .. offsets[j+1]) are byte for byte what phx_reannotate_flat returns for that
+ * contig when the mask holds exactly F on that contig and bit 0 of its flags is set — format, order, tie rule, PHX_S_NOPATH with +inf,
+ * PHX_S_OVERFLOW and a run error passed through.  Scenarios are independent of each other: several may name the same contig and may
+ * overlap; an empty list is solved like any other (the device path); duplicates inside a list are allowed.  Only refused sets: there
+ * are no required ORFs per scenario.
+ *   scen_contig  [n_scen]: contig of the batch last run
+ *   scen_off     [n_scen+1]: scenario j lists scen_orf[scen_off[j] .. scen_off[j+1]); starts at 0, non-decreasing
+ *   scen_orf     indices into phx_tap_orfs order of the scenario's contig
+ *   orf_offsets  [n+1]: as phx_reannotate_flat (must equal phx_orf_offsets)
+ *   flags        reserved: pass 0
+ *   genes        NULL: size query (offsets, status, delta, total are filled in); the fetch with the same arguments reuses the solve
+ * PHX_E_ARG before any kernel for wrong orf_offsets, a contig outside [0, n), an ORF index outside its contig's count, or scen_off
+ * not starting at 0 or decreasing: nothing from the caller indexes device memory unchecked.  PHX_E_STATE before a run; the result is
+ * invalidated by the next upload or run.  The scenarios are solved in chunks under a device-memory budget (an internal default;
+ * PHX_SCEN_BYTES in the environment, read by phx_create*, overrides it); the result does not depend on the chunking, and a scenario
+ * larger than the budget is solved alone.  The solve owns its buffers: nothing phx_download*, the taps, the margins, the drops, the
+ * replacements, phx_reannotate_flat's cached result or the certificate return changes. */
+int phx_scenarios_flat(phx_ctx *ctx, int64_t n_scen, const int32_t *scen_contig /* [n_scen] */, const int64_t *scen_off /* [n_scen+1] */,
+                       const int32_t *scen_orf, const int64_t *orf_offsets /* [n+1] */, uint32_t flags, phx_gene *genes, int64_t cap,
+                       int64_t *offsets /* [n_scen+1] */, int32_t *status /* [n_scen] */, double *delta /* [n_scen] */, int64_t *total);
+/* device time of the last scenario solve, summed over its chunks, ms[3]: slot records + bitmap slices, masked solve, in-order parents +
+ * path + genes + the copies to the host.  All 0 before the first. */
+int phx_scenarios_ms(phx_ctx *ctx, float *ms /* [3] */);
+/* path and D_F of scenario `scen` of the last scenario solve, like phx_tap_repath (n_path 0: no path, or a scenario whose contig was not
+ * solved).  The slices of the last chunk are the ones still on the device: PHX_E_STATE for a scenario of an earlier chunk (with the default
+ * budget a call is one chunk), and without a scenario solve of this run. */
+int phx_tap_scenario_path(phx_ctx *ctx, int64_t scen, int32_t *path, int32_t cap, int32_t *n_path, uint64_t *dist_limbs, int32_t cap_limbs);
+/* chunks the last scenario solve was split into (0 before the first, and when no scenario needed the device; PHX_E_ARG without a context) */
+int64_t phx_scenario_chunks(phx_ctx *ctx);
 
 /* -d/--dump of the reference (phanotate.py:58,61) for one contig of the batch last run: one line per edge of its graph,
  *     repr(source) TAB repr(target) TAB str(weight * 1000)                                   (edges.py:17-23, nodes.py:14-21)

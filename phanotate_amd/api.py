@@ -528,6 +528,111 @@ class Annotator:
         self._chk(self.L.phx_constrain_flat(self.h, vp(fmask), vp(rmask), vp(oo), fl, vp(genes), len(genes), vp(offs), vp(status), vp(delta), vp(unmet), C.byref(total)), "phx_constrain_flat")
         return status[:n], offs, genes[: int(total.value)], delta[:n], unmet[:n]
 
+    # ---- scenario batches ----
+    @staticmethod
+    def _scenario_arrays(scen, n, oo):
+        """(contig int32[S], off int64[S+1], orf int32[P]) of a sequence of (contig, index array); IndexError / ValueError as _orf_mask."""
+        S = len(scen)
+        contig = np.zeros(max(S, 1), np.int32)
+        off = np.zeros(S + 1, np.int64)
+        lists = []
+        for j, item in enumerate(scen):
+            try:
+                i, f = item
+            except (TypeError, ValueError):
+                raise ValueError("a scenario is a (contig, index array) pair") from None
+            i = int(i)
+            if i < 0 or i >= n:
+                raise IndexError("scenario %d names contig %d of a batch of %d" % (j, i, n))
+            idx = np.zeros(0, np.int64) if f is None else np.asarray(f, np.int64).reshape(-1)
+            if idx.size and (idx.min() < 0 or idx.max() >= oo[i + 1] - oo[i]):
+                raise IndexError("contig %d has %d ORFs" % (i, oo[i + 1] - oo[i]))
+            contig[j] = i
+            off[j + 1] = off[j] + idx.size
+            lists.append(idx)
+        orf = np.concatenate(lists).astype(np.int32) if lists else np.zeros(0, np.int32)
+        return contig, off, np.ascontiguousarray(orf if orf.size else np.zeros(1, np.int32))
+
+    def scenarios(self, scen):
+        """(status int32[S], offsets int64[S+1], genes structured array[total], delta float64[S]): S masked re-annotations of the batch
+        last run in one call (phx_scenarios_flat).  `scen` is a sequence of (contig, array of indices into orfs(contig)); scenario j is
+        reannotate() of that contig without exactly those ORFs — status[j], delta[j] and genes[offsets[j]:offsets[j+1]] are byte for
+        byte that call's for the contig — solved side by side on the resident graph, one workgroup per scenario.  Scenarios are
+        independent: the same contig may be named many times, lists may overlap, be empty (the device path) or hold duplicates."""
+        n = self.n
+        oo = self.orf_offsets()
+        contig, off, orf = self._scenario_arrays(scen, n, oo)
+        S = len(scen)
+        offs = np.zeros(S + 1, np.int64)
+        status = np.zeros(max(S, 1), np.int32)
+        delta = np.zeros(max(S, 1), np.float64)
+        total = C.c_int64(0)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._chk(self.L.phx_scenarios_flat(self.h, S, vp(contig), vp(off), vp(orf), vp(oo), 0, None, 0, vp(offs), vp(status), vp(delta), C.byref(total)), "phx_scenarios_flat")
+        genes = np.empty(max(int(total.value), 1), _lib.GENE_DT)
+        self._chk(self.L.phx_scenarios_flat(self.h, S, vp(contig), vp(off), vp(orf), vp(oo), 0, vp(genes), len(genes), vp(offs), vp(status), vp(delta), C.byref(total)), "phx_scenarios_flat")
+        return status[:S], offs, genes[: int(total.value)], delta[:S]
+
+    def scenarios_ms(self):
+        """Device time of the last scenario solve in ms, summed over its chunks: slot records + bitmaps, masked solve, path + genes + copy
+        (phx_scenarios_ms)."""
+        ms = (C.c_float * 3)()
+        self._chk(self.L.phx_scenarios_ms(self.h, ms), "phx_scenarios_ms")
+        return dict(zip(("mask", "solve", "finish"), [float(x) for x in ms]))
+
+    def scenario_chunks(self):
+        """Chunks the last scenario solve was split into under the device-memory budget (phx_scenario_chunks)."""
+        return int(self.L.phx_scenario_chunks(self.h))
+
+    def scenario_path(self, j, contig):
+        """(path as device node ids, its length D_F as a python int) of scenario j of the last scenarios() call, like reannotated_path;
+        `contig` is the scenario's contig.  Served while the scenario's chunk is resident (phx_tap_scenario_path)."""
+        g = self.globals(contig)
+        p = np.zeros(max(g.n_node, 1), np.int32)
+        n = C.c_int32()
+        limbs = np.zeros(32, np.uint64)
+        self._chk(self.L.phx_tap_scenario_path(self.h, int(j), p.ctypes.data_as(C.c_void_p), len(p), C.byref(n), limbs.ctypes.data_as(C.c_void_p), 32), "phx_tap_scenario_path")
+        nl = max(g.n_limbs, 1)
+        v = 0
+        for k in range(nl):
+            v |= int(limbs[k]) << (64 * k)
+        if v >> (64 * nl - 1):
+            v -= 1 << (64 * nl)
+        return p[: n.value].copy(), v
+
+    def start_drops(self):
+        """(status int32[n], offsets int64[n+1], records structured array[total] of _lib.START_DT, scen_offsets int64[total+1], genes):
+        for every record of drop_margins() (same order, offsets and statuses) the best annotation when the called gene's own start ORF
+        is refused while the other starts of its stop stay allowed — one scenario per called gene, all in one scenarios() call.
+        drop = the scenario's delta (+inf: no path remains); restart = the index in orfs(i) of the ORF of the same stop and strand the
+        new annotation calls, -1 when the stop is no longer called; genes[scen_offsets[k]:scen_offsets[k+1]] is record k's full new
+        annotation."""
+        st, offs, drec = self.drop_margins()
+        n = self.n
+        scen = []
+        for i in range(n):
+            for r in drec[offs[i]:offs[i + 1]]:
+                scen.append((i, [self.orf_index(i, r["left"], r["right"], r["strand"])]))
+        sstat, soffs, genes, delta = self.scenarios(scen)
+        rec = np.zeros(len(scen), _lib.START_DT)
+        k = 0
+        for i in range(n):
+            for r in drec[offs[i]:offs[i + 1]]:
+                o = rec[k]
+                o["left"], o["right"], o["strand"] = r["left"], r["right"], r["strand"]
+                o["orf"] = scen[k][1][0]
+                o["drop"] = delta[k]
+                o["status"] = sstat[k]
+                o["restart"] = -1
+                fwd = r["strand"] > 0
+                for g in genes[soffs[k]:soffs[k + 1]]:  # the gene of the same stop and strand, if the new annotation still calls the stop
+                    if abs(int(g["frame"])) <= 3 and (g["strand"] > 0) == fwd and (g["right"] == r["right"] if fwd else g["left"] == r["left"]):
+                        o["restart"] = self.orf_index(i, g["left"], g["right"], g["strand"])
+                        o["restart_left"], o["restart_right"] = g["left"], g["right"]
+                        break
+                k += 1
+        return st, offs, rec, soffs, genes
+
     def reannotated_path(self, i):
         """(path as device node ids, its length as a python int) of contig i in the last re-annotation or constrain(), like path(i): D_F, or
         the W-sum W(P) after constrain()."""

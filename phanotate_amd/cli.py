@@ -43,6 +43,7 @@ def get_args(argv=None):
     p.add_argument("--margins", metavar="FILE", default=None, help="also write every ORF some source-to-target path runs through, with its path margin (DESIGN.md §11), to FILE")
     p.add_argument("--drop-margins", metavar="FILE", default=None, help="also write every called gene with its drop margin, the cost of the best path without it (DESIGN.md §12), to FILE")
     p.add_argument("--drop-replacements", metavar="FILE", default=None, help="also write every called gene with what the best path without it calls instead (DESIGN.md §13) to FILE")
+    p.add_argument("--start-drops", metavar="FILE", default=None, help="also write every called gene with the cost of refusing its start and the start the best annotation then takes for its stop (DESIGN.md §17) to FILE")
     p.add_argument("--forbid", metavar="FILE", default=None, help="ORFs to refuse in a second annotation (DESIGN.md §14): lines whose first four columns are START STOP FRAME CONTIG as the tabular output prints a gene; needs --reannotation")
     p.add_argument("--require", metavar="FILE", default=None, help="ORFs to keep in a second annotation (DESIGN.md §16), in the format of --forbid; alone or with --forbid; needs --reannotation, which then carries a #unmet: line per contig")
     p.add_argument("--reannotation", metavar="OUT", default=None, help="write the annotation without the ORFs of --forbid (and keeping those of --require) to OUT: the tabular block of every contig with a #delta: header line")
@@ -60,6 +61,12 @@ def get_args(argv=None):
         p.error("argument --drop-replacements: not allowed with argument -d/--dump")
     if args.drop_replacements is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         p.error("argument --drop-replacements: not available under a multi-rank launch")
+    if args.start_drops is not None and args.dump:
+        p.error("argument --start-drops: not allowed with argument -d/--dump")
+    if args.start_drops is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        p.error("argument --start-drops: not available under a multi-rank launch")
+    if args.start_drops is not None and int(args.gpus) > 1:  # the scenarios work on the batch resident on one context
+        p.error("argument --start-drops: not available with --gpus above 1")
     for flag, val in (("--forbid", args.forbid), ("--require", args.require), ("--reannotation", args.reannotation)):
         if val is not None and args.dump:
             p.error("argument %s: not allowed with argument -d/--dump" % flag)
@@ -134,6 +141,29 @@ def format_reannotation(names, status, offsets, genes, delta, unmet=None):
         write_tabular(one, nm, genes[offsets[i]:offsets[i + 1]])
         head, rest = one.getvalue().split("\n", 1)
         buf.write(head + "\n#delta:\t" + repr(float(delta[i])) + "\n" + ("" if unmet is None else "#unmet:\t%d\n" % int(unmet[i])) + rest)
+    return buf.getvalue()
+
+
+def format_start_drops(names, status, offsets, records):
+    """--start-drops FILE: per contig with status >= 0 "#id:\t<name>", the header, one row per called gene of the device path in path
+    order (the records of Annotator.start_drops()): the gene's START STOP FRAME as the tabular output prints them, repr(drop), and the
+    START STOP of the ORF of the same stop the new annotation calls, or "-" when the stop is no longer called."""
+    import io
+
+    buf = io.StringIO()
+    for i, nm in enumerate(names):
+        if status[i] < 0:
+            continue
+        buf.write("#id:\t" + nm + "\n#START\tSTOP\tFRAME\tDROP\tRESTART\n")
+        for r in records[offsets[i]:offsets[i + 1]]:
+            rev = r["strand"] < 0
+            left, right = (int(r["right"]), int(r["left"])) if rev else (int(r["left"]), int(r["right"]))  # locus.py:44-46
+            if r["restart"] >= 0:
+                a, b = (int(r["restart_right"]), int(r["restart_left"])) if rev else (int(r["restart_left"]), int(r["restart_right"]))
+                tail = "%d\t%d" % (a, b)
+            else:
+                tail = "-"
+            buf.write("%d\t%d\t%s\t%s\t%s\n" % (left, right, chr(44 - (-1 if rev else 1)), repr(float(r["drop"])), tail))
     return buf.getvalue()
 
 
@@ -333,6 +363,7 @@ def main(argv=None):
     margin_parts = []  # --margins: (status, offsets, records) of every batch, in order
     drop_parts = []  # --drop-margins: the same of the drop margins
     repl_parts = []  # --drop-replacements: (status, offsets, records, genes) of every batch, in order
+    start_parts = []  # --start-drops: (status, offsets, records) of every batch, in order
     reann_parts = []  # --reannotation: (status, offsets, genes, delta[, unmet]) of every batch, in order
     forbid_entries = require_entries = None
     try:
@@ -366,7 +397,7 @@ def main(argv=None):
             if lo >= len(idx):
                 break
         t_parts["batches"] = len(cuts)
-        if forbid_entries is not None or require_entries is not None:  # the re-annotation works on the batch resident on one context: the batches one after the other
+        if forbid_entries is not None or require_entries is not None or args.start_drops is not None:  # the re-annotation and the scenarios work on the batch resident on one context: the batches one after the other
             parts = []
             for lo, hi in cuts:
                 t0 = time.perf_counter()
@@ -383,10 +414,14 @@ def main(argv=None):
                     repl_parts.append(ann.replacements())
                 if args.drop_margins is not None:
                     drop_parts.append(ann.drop_margins())
+                if args.start_drops is not None:
+                    start_parts.append(ann.start_drops()[:3])
                 names = [fa.names[int(i)] for i in idx[lo:hi]]
                 here = set(names)
                 refused = resolve_forbid([e for e in forbid_entries or [] if e[3] in here], names, ann.orf_index)
-                if require_entries is None:
+                if forbid_entries is None and require_entries is None:
+                    pass
+                elif require_entries is None:
                     reann_parts.append(ann.reannotate(refused))
                 else:
                     reann_parts.append(ann.constrain(refused, resolve_forbid([e for e in require_entries if e[3] in here], names, ann.orf_index, "--require")))
@@ -500,6 +535,12 @@ def main(argv=None):
                 r_genes.append(m[3])
             with open(args.drop_replacements, "wb") as fh:
                 fh.write(format_replacements(fa.names, r_status, r_offsets, np.concatenate(r_records), np.concatenate(r_genes)))
+        if args.start_drops is not None:
+            s_status = np.concatenate([m[0] for m in start_parts])
+            s_counts = np.concatenate([np.diff(m[1]) for m in start_parts])
+            s_offsets = np.concatenate([[0], np.cumsum(s_counts)]).astype(np.int64)
+            with open(args.start_drops, "w") as fh:
+                fh.write(format_start_drops(fa.names, s_status, s_offsets, np.concatenate([m[2] for m in start_parts])))
         if args.reannotation is not None:
             q_status = np.concatenate([m[0] for m in reann_parts])
             q_counts = np.concatenate([np.diff(m[1]) for m in reann_parts])

@@ -750,3 +750,249 @@ int phx_reannotate_ms(phx_ctx *c, float *ms) {
     for (int k = 0; k < 3; k++) ms[k] = c->reann_ms[k];
     return PHX_OK;
 }
+
+// ---- scenario batches (phx_resolve.inc, DESIGN.md §17) ----
+// h_srec[j].status before the solve: the scenario gets a slot / its contig is not solved again and the run's verdict stands (neither is a status the device reports)
+static const int32_t SC_SLOT = -99, SC_NOSLOT = -100;
+// Device bytes of one slot of contig i: distances, parent, path, bitmap slice, window plan, gene records, the record copy.
+static size_t scen_slot_bytes(const phx_ctx *c, int i) {
+    const DMeta &m = c->meta[(size_t)i];
+    const size_t V = (size_t)m.n_node, E = (size_t)m.n_edge;
+    return V * ((size_t)m.sssp_nl * 8 + 4 + 4) + (E / 32 + 3) * 4 + (V / 32 + 2) + (V + 1) * sizeof(DGene) + sizeof(DMeta) + sizeof(DScSlot) + sizeof(DReannRec);
+}
+
+// Solves the scenarios with a slot (h_srec[j].status == SC_SLOT) in chunks under the budget; records into h_srec, genes into h_sgenes.
+// perm: per contig named, tap index -> ORF in the contig's device order (-1: no such ORF in the device's groups).
+static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const int64_t *scen_off, const int32_t *scen_orf,
+                        const std::vector<std::vector<int32_t>> &perm) {
+    int rc;
+    hipStream_t s = c->stream;
+    c->scen_chunks = 0;
+    c->scen_ms[0] = c->scen_ms[1] = c->scen_ms[2] = 0;
+    c->h_sgenes.clear();
+    c->h_sslot.assign((size_t)S, DScSlot{});
+    c->h_schunk_of.assign((size_t)S, 0);
+    if ((rc = analysis_events(c))) return rc;
+    std::vector<DScSlot> slots;
+    std::vector<int2> pairs;
+    std::vector<int64_t> which; // scenario of every slot of the chunk
+    for (int64_t j0 = 0; j0 < S;) {
+        // ---- the chunk: scenarios j0 .. j1 with a slot, as many as the budget holds (at least one) ----
+        slots.clear(); pairs.clear(); which.clear();
+        size_t bytes = 0, nodes = 0, words = 0, mwords = 0, plan = 0;
+        int nlm = 0;
+        int64_t j1 = j0;
+        for (; j1 < S; j1++) {
+            if (c->h_srec[(size_t)j1].status != SC_SLOT) continue;
+            const int i = scen_contig[j1];
+            const DMeta &m = c->meta[(size_t)i];
+            const size_t need = scen_slot_bytes(c, i);
+            if (!slots.empty() && bytes + need > (size_t)c->scen_budget) break;
+            bytes += need;
+            DScSlot sl;
+            sl.contig = i; sl.pad_ = 0;
+            sl.node0 = (int64_t)nodes; sl.dist0 = (int64_t)words; sl.mask0 = (int64_t)mwords; sl.plan0 = (int64_t)plan;
+            nodes += (size_t)m.n_node;
+            words += ((size_t)m.n_node * (size_t)m.sssp_nl + 1) & ~(size_t)1;
+            mwords += (((size_t)m.edge_off & 31) + (size_t)m.n_edge) / 32 + 2;
+            plan += (size_t)m.n_node / 32 + 2;
+            nlm |= nl_class_bit(m.sssp_nl);
+            const std::vector<int32_t> &pm = perm[(size_t)i];
+            for (int64_t k = scen_off[j1]; k < scen_off[j1 + 1]; k++) {
+                const int32_t d = pm[(size_t)scen_orf[k]];
+                if (d >= 0) pairs.push_back(make_int2((int)slots.size(), d));
+            }
+            slots.push_back(sl);
+            which.push_back(j1);
+        }
+        j0 = j1;
+        const size_t ns = slots.size();
+        if (!ns) break;
+        c->scen_chunks++;
+        if ((rc = ensure(c, c->b_sc_slot, ns * sizeof(DScSlot))) || (rc = ensure(c, c->b_sc_pair, (pairs.size() + 1) * sizeof(int2))) ||
+            (rc = ensure(c, c->b_sc_meta, ns * sizeof(DMeta))) || (rc = ensure(c, c->b_sc_dist, (words + 2) * 8)) || (rc = ensure(c, c->b_sc_parent, (nodes + 1) * 4)) ||
+            (rc = ensure(c, c->b_sc_path, (nodes + 1) * 4)) || (rc = ensure(c, c->b_sc_mask, (mwords + 2) * 4)) || (rc = ensure(c, c->b_sc_plan, plan + 2)) ||
+            (rc = ensure(c, c->b_sc_genes, (nodes + ns + 1) * sizeof(DGene))) || (rc = ensure(c, c->b_sc_rec, ns * sizeof(DReannRec))) ||
+            (rc = ensure(c, c->b_sc_tot, sizeof(DTotals))) || (rc = ensure(c, c->b_sc_gtot, 16)))
+            return rc;
+        if (!c->b_sc_tie.p && (rc = ensure(c, c->b_sc_tie, (size_t)std::max<int64_t>(c->tie_seen, 1 << 20)))) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->b_sc_slot.p, slots.data(), ns * sizeof(DScSlot), hipMemcpyHostToDevice, s));
+        if (!pairs.empty()) HIPCHK(c, hipMemcpyAsync(c->b_sc_pair.p, pairs.data(), pairs.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+        c->h_schunk.assign(ns, DReannRec{});
+        DTotals &tot = c->h_stot;
+        uint32_t &gtot = c->h_sgtot;
+        gtot = 0;
+        float ms[3] = {0, 0, 0};
+        for (int attempt = 0;; attempt++) {
+            // the slots' view of the batch: the run's graph and records (read only), totals / genes / counter / tie scratch of the scenarios' own
+            DBatch b;
+            DScen q;
+            fill_batch(c, &b);
+            b.tot = (DTotals *)c->b_sc_tot.p; b.res = nullptr; b.sord = nullptr; b.lpart = nullptr;
+            b.genes = (DGene *)c->b_sc_genes.p; b.genes_c = nullptr; b.gpack = 0; b.gene_total = (uint32_t *)c->b_sc_gtot.p;
+            b.tie = (uint8_t *)c->b_sc_tie.p; b.tie_cap = cap_of(c->b_sc_tie, 1, 0);
+            q.slot = (const DScSlot *)c->b_sc_slot.p; q.pair = (const int2 *)c->b_sc_pair.p; q.n_pair = (int64_t)pairs.size(); q.n_slot = (int32_t)ns;
+            q.stride0 = c->n_limbs; q.meta = (DMeta *)c->b_sc_meta.p; q.dist = (uint64_t *)c->b_sc_dist.p; q.parent = (int32_t *)c->b_sc_parent.p;
+            q.path = (int32_t *)c->b_sc_path.p; q.mask = (uint32_t *)c->b_sc_mask.p; q.gplan = (uint8_t *)c->b_sc_plan.p;
+            q.dist0 = (const uint64_t *)c->b_dist.p; q.rec = (DReannRec *)c->b_sc_rec.p;
+            HIPCHK(c, hipEventRecord(c->aev[0], s));
+            HIPCHK(c, hipMemsetAsync(c->b_sc_tot.p, 0, sizeof(DTotals), s));
+            HIPCHK(c, hipMemsetAsync(c->b_sc_gtot.p, 0, 16, s));
+            HIPCHK(c, hipMemsetAsync(c->b_sc_mask.p, 0, (mwords + 2) * 4, s));
+            phxk_scen_mask(&b, &q, s);
+            HIPCHK(c, hipEventRecord(c->aev[1], s));
+            phxk_scen_solve(&b, &q, nlm, s);
+            HIPCHK(c, hipEventRecord(c->aev[2], s));
+            phxk_scen_finish(&b, &q, nlm, s);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipMemcpyAsync(c->h_schunk.data(), c->b_sc_rec.p, ns * sizeof(DReannRec), hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipEventRecord(c->aev[3], s));
+            HIPCHK(c, hipMemcpyAsync(&tot, c->b_sc_tot.p, sizeof(DTotals), hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipMemcpyAsync(&gtot, c->b_sc_gtot.p, 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipStreamSynchronize(s));
+            ms[0] = ev_ms(c->aev[0], c->aev[1]); ms[1] = ev_ms(c->aev[1], c->aev[2]); ms[2] = ev_ms(c->aev[2], c->aev[3]);
+            if (!(tot.overflow & 4)) break;
+            // the tie scratch was too small for the slots with equal-length alternatives: grow it and solve the chunk again (as reann_compute)
+            if (attempt >= 2) { c->err = "scenarios: the tie scratch did not settle"; return PHX_E_STATE; }
+            if ((rc = ensure(c, c->b_sc_tie, (size_t)tot.tie_need + (size_t)tot.tie_need / 4 + 4096))) return rc;
+        }
+        if ((size_t)gtot > nodes + ns) { c->err = "scenarios: gene records beyond the buffer"; return PHX_E_STATE; }
+        const size_t base = c->h_sgenes.size();
+        c->h_sgenes.resize(base + gtot);
+        HIPCHK(c, hipEventRecord(c->aev[4], s));
+        if (gtot) HIPCHK(c, hipMemcpyAsync(c->h_sgenes.data() + base, c->b_sc_genes.p, (size_t)gtot * sizeof(DGene), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipEventRecord(c->aev[5], s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        c->scen_ms[0] += ms[0]; c->scen_ms[1] += ms[1]; c->scen_ms[2] += ms[2] + ev_ms(c->aev[4], c->aev[5]);
+        for (size_t k = 0; k < ns; k++) {
+            DReannRec r = c->h_schunk[k];
+            if (r.n_genes < 0 || r.gene_off < 0 || (uint64_t)r.gene_off + (uint64_t)r.n_genes > (uint64_t)gtot) { c->err = "scenarios: a slot's gene records lie outside the buffer"; return PHX_E_STATE; }
+            r.gene_off += (int64_t)base;
+            c->h_srec[(size_t)which[k]] = r;
+            c->h_sslot[(size_t)which[k]] = slots[k];
+            c->h_schunk_of[(size_t)which[k]] = c->scen_chunks;
+        }
+    }
+    return PHX_OK;
+}
+
+int phx_scenarios_flat(phx_ctx *c, int64_t n_scen, const int32_t *scen_contig, const int64_t *scen_off, const int32_t *scen_orf, const int64_t *orf_offsets,
+                       uint32_t flags, phx_gene *genes, int64_t cap, int64_t *offsets, int32_t *status, double *delta, int64_t *total_out) {
+    (void)flags; // reserved
+    if (!c || n_scen < 0 || !offsets || !scen_off || (n_scen > 0 && (!status || !delta || !scen_contig)) || (c->n > 0 && !orf_offsets)) return PHX_E_ARG;
+    { const int ra = after_run(c); if (ra) return ra; }
+    { const int rf = fetch_meta(c); if (rf) return rf; }
+    try {
+    // ---- argument checks, all before any kernel: nothing from the caller indexes device memory unchecked ----
+    int64_t acc = 0;
+    for (int i = 0; i < c->n; i++) {
+        if (orf_offsets[i] != acc) return PHX_E_ARG;
+        if (reann_status(c, i) >= 0) acc += c->meta[(size_t)i].n_orf;
+    }
+    if (c->n > 0 && orf_offsets[c->n] != acc) return PHX_E_ARG;
+    if (scen_off[0] != 0) return PHX_E_ARG;
+    const size_t S = (size_t)n_scen;
+    for (size_t j = 0; j < S; j++) {
+        if (scen_off[j + 1] < scen_off[j]) return PHX_E_ARG;
+        const int32_t i = scen_contig[j];
+        if (i < 0 || i >= c->n) return PHX_E_ARG;
+        if (scen_off[j + 1] > scen_off[j] && !scen_orf) return PHX_E_ARG;
+        const int64_t cnt = orf_offsets[i + 1] - orf_offsets[i];
+        for (int64_t k = scen_off[j]; k < scen_off[j + 1]; k++) if (scen_orf[k] < 0 || (int64_t)scen_orf[k] >= cnt) return PHX_E_ARG;
+    }
+    const size_t P = (size_t)scen_off[S];
+    const bool same = c->done.scen && c->h_skey_contig.size() == S && c->h_skey_orf.size() == P &&
+                      std::equal(scen_contig, scen_contig + S, c->h_skey_contig.begin()) && std::equal(scen_off, scen_off + S + 1, c->h_skey_off.begin()) &&
+                      std::equal(scen_orf, scen_orf + P, c->h_skey_orf.begin());
+    if (!same) {
+        c->done.scen = false;
+        { const int rg = ensure_grp_host(c); if (rg) return rg; }
+        // tap order -> device ORF order of every contig named: the inverse of the permutation phx_margins_flat applies (as reann_compute)
+        std::vector<std::vector<int32_t>> perm((size_t)c->n);
+        std::vector<int> order;
+        DReannRec none{};
+        none.status = SC_NOSLOT; none.delta = std::numeric_limits<double>::infinity();
+        c->h_srec.assign(S, none);
+        for (size_t j = 0; j < S; j++) {
+            const int i = scen_contig[j];
+            if (!reann_contig(c, i)) continue; // (the run's verdict stands: a run error, no device distances, an empty graph)
+            c->h_srec[j].status = SC_SLOT;
+            std::vector<int32_t> &pm = perm[(size_t)i];
+            if (!pm.empty() || scen_off[j + 1] == scen_off[j]) continue;
+            const DMeta &m = c->meta[(size_t)i];
+            pm.assign((size_t)m.n_orf, -1);
+            size_t t = 0;
+            each_group_in_reference_order(c, (size_t)i, order, [&](int32_t first, int32_t k) {
+                for (int32_t x = 0; x < k && t + (size_t)x < pm.size(); x++) pm[t + (size_t)x] = first >= 0 && (int64_t)first + k <= m.n_orf ? first + x : -1;
+                t += (size_t)(k > 0 ? k : 0);
+            });
+        }
+        { const int rq = scen_compute(c, n_scen, scen_contig, scen_off, scen_orf, perm); if (rq) { (void)hipStreamSynchronize(c->stream); return rq; } }
+        c->h_skey_contig.assign(scen_contig, scen_contig + S);
+        c->h_skey_off.assign(scen_off, scen_off + S + 1);
+        c->h_skey_orf.assign(scen_orf, scen_orf + P);
+        c->done.scen = true;
+    }
+    // ---- the caller's layout: per scenario what phx_reannotate_flat reports for its contig ----
+    int64_t total = 0;
+    bool run_genes = false;
+    for (size_t j = 0; j < S; j++) {
+        const int i = scen_contig[j];
+        const int32_t st = reann_status(c, i);
+        offsets[j] = total; status[j] = st; delta[j] = std::numeric_limits<double>::infinity();
+        if (st < 0) continue;
+        const DReannRec &r = c->h_srec[j];
+        if (r.status != SC_NOSLOT) {
+            status[j] = r.status; delta[j] = r.delta;
+            if (r.status >= 0) total += r.n_genes;
+        } else { // not solved again: the run's result, as the sibling delivers it
+            if (st != PHX_S_NOPATH) delta[j] = 0.0;
+            if (c->res[(size_t)i].n_genes > 0) { total += c->res[(size_t)i].n_genes; run_genes = true; }
+        }
+    }
+    offsets[S] = total;
+    if (total_out) *total_out = total;
+    if (!genes) return PHX_OK; // size query
+    if (cap < total) return PHX_E_ARG;
+    if (run_genes) { const int rg = stage_run_genes(c); if (rg) return rg; }
+    for (size_t j = 0; j < S; j++) {
+        const int64_t k = offsets[j + 1] - offsets[j];
+        if (k <= 0) continue;
+        const DReannRec &r = c->h_srec[j];
+        const DGene *src = r.status != SC_NOSLOT ? c->h_sgenes.data() + r.gene_off : (const DGene *)c->h_genes.p + (size_t)c->res[(size_t)scen_contig[j]].gene_off;
+        memcpy(genes + offsets[j], src, sizeof(phx_gene) * (size_t)k);
+    }
+    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_scenarios_flat"; return PHX_E_NOMEM; }
+    return PHX_OK;
+}
+
+int phx_tap_scenario_path(phx_ctx *c, int64_t scen, int32_t *path, int32_t cap, int32_t *n_path, uint64_t *dist_limbs, int32_t cap_limbs) {
+    if (!c || !n_path) return PHX_E_ARG;
+    *n_path = 0;
+    { const int ra = after_run(c); if (ra) return ra; }
+    if (!c->done.scen) return PHX_E_STATE;
+    if (scen < 0 || (size_t)scen >= c->h_srec.size()) return PHX_E_ARG;
+    const DReannRec &r = c->h_srec[(size_t)scen];
+    if (r.status == SC_NOSLOT || r.status < 0 || r.n_path <= 0) return PHX_OK; // no slot, or no path
+    if (c->h_schunk_of[(size_t)scen] != c->scen_chunks) return PHX_E_STATE; // its chunk's slices have been reused
+    const DScSlot &sl = c->h_sslot[(size_t)scen];
+    const DMeta &m = c->meta[(size_t)sl.contig];
+    *n_path = r.n_path;
+    if (path) {
+        if (cap < r.n_path) return PHX_E_ARG;
+        HIPCHK(c, hipMemcpy(path, (int32_t *)c->b_sc_path.p + sl.node0, (size_t)r.n_path * 4, hipMemcpyDeviceToHost));
+    }
+    if (dist_limbs) {
+        if (cap_limbs < m.sssp_nl) return PHX_E_ARG;
+        HIPCHK(c, hipMemcpy(dist_limbs, (uint64_t *)c->b_sc_dist.p + sl.dist0 + ((size_t)m.n_node - 1) * (size_t)m.sssp_nl, (size_t)m.sssp_nl * 8, hipMemcpyDeviceToHost));
+    }
+    return PHX_OK;
+}
+
+int phx_scenarios_ms(phx_ctx *c, float *ms) {
+    if (!c || !ms) return PHX_E_ARG;
+    for (int k = 0; k < 3; k++) ms[k] = c->scen_ms[k];
+    return PHX_OK;
+}
+
+int64_t phx_scenario_chunks(phx_ctx *c) { return c ? c->scen_chunks : (int64_t)PHX_E_ARG; } // (as phx_plan_timeouts: a NULL context is refused)

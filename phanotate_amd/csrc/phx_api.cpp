@@ -236,6 +236,7 @@ struct phx_ctx {
         bool trees = false;   // ... and the drop kernels kept the one-hop trees (b_dps / b_dts)
         bool repl = false;    // h_rrec / h_rgenes / h_rdet
         bool reann = false;   // h_q* hold the re-annotation for the mask h_qforb / h_qflags
+        bool scen = false;    // h_s* hold the scenario batch h_skey
         bool grp = false;     // h_grp
     } done;
     std::vector<DGrp> h_grp;         // the run's group records (device order <-> reference order of the ORFs: each_group_in_reference_order)
@@ -276,6 +277,20 @@ struct phx_ctx {
     DTotals h_qtot;                   //   an early error return never points at memory that has gone out of scope
     uint32_t h_qgtot = 0;
     float reann_ms[3] = {0, 0, 0};
+    // scenario batches (phx_scenarios_flat): buffers of their own, allocated at the first call; the result kept until the next upload or run
+    DevBuf b_sc_slot, b_sc_pair, b_sc_meta, b_sc_dist, b_sc_parent, b_sc_path, b_sc_mask, b_sc_plan, b_sc_genes, b_sc_rec, b_sc_tot, b_sc_gtot, b_sc_tie;
+    int64_t scen_budget = (int64_t)2 << 30; // device bytes of a chunk's slots (env PHX_SCEN_BYTES at phx_create)
+    int64_t scen_chunks = 0;                // chunks of the last solve
+    std::vector<int32_t> h_skey_contig, h_skey_orf; // the scenarios last solved (the cache key)
+    std::vector<int64_t> h_skey_off;
+    std::vector<DReannRec> h_srec;    // per scenario (status SC_NOSLOT: the run's verdict stands); gene_off into h_sgenes
+    std::vector<DGene> h_sgenes;
+    std::vector<DScSlot> h_sslot;     // per scenario: its slot (phx_tap_scenario_path) and
+    std::vector<int64_t> h_schunk_of; //   the chunk that solved it (1-based; 0: no slot) — the last chunk's slices are still on the device
+    std::vector<DReannRec> h_schunk;  // a chunk's records, its totals and gene count as read back (members: see h_qdforb)
+    DTotals h_stot;
+    uint32_t h_sgtot = 0;
+    float scen_ms[3] = {0, 0, 0};
     float stage_ms[PHX_N_STAGES] = {0};
     int stage_n[PHX_N_STAGES] = {0};
     std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;
@@ -701,6 +716,7 @@ int phx_create_ex(const phx_params *params, int device, void *stream, uint32_t f
     { const char *e = getenv("PHX_NO_SEG"); c->seg_on = !(flags & PHX_CREATE_NO_SEG) && !(e && e[0] == '1'); }
     { const char *e = getenv("PHX_SEG_MAX_N"); if (e && atoi(e) >= 0) c->seg_max_n = atoi(e); }
     { const char *e = getenv("PHX_SEG_MARGIN_BP"); if (e && atoi(e) > 0) c->seg_margin_bp = atoi(e); }
+    { const char *e = getenv("PHX_SCEN_BYTES"); if (e && atoll(e) > 0) c->scen_budget = atoll(e); }
     c->cert_wide = (flags & PHX_CREATE_CERT_WIDE) != 0;
     c->poison = (flags & PHX_CREATE_POISON) != 0;
     c->cert_scale = (flags & PHX_CREATE_CERT_TIGHT) ? 68719476736.0 : 1.0; // 2^36

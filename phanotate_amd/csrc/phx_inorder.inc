@@ -186,8 +186,9 @@ __device__ void walk_path(const DBatch &b, DMeta *meta, IoShared<IO_T> *sh) {
 // whatever the distances say.  The run's instantiations (MASKED = false) do not look at `mask`.
 // REQ (the pinned re-annotation, DESIGN.md §16; with MASKED, on one limb more than the contig's class): an edge whose bit is set in `req` weighs
 // W - 2^(64 (NL - 1)), as in the sweep that made the distances (lds_sweep under RcCfg).
+// ci: the contig's index in the batch (blockIdx.x where a workgroup is a contig; a scenario slot passes its slot's contig).
 template <int NL, int IO_T, bool MASKED = false, bool REQ = false>
-__device__ void inorder_contig(const DBatch &b, DMeta *meta, IoShared<IO_T> *sh, const uint32_t *mask = nullptr, const uint32_t *req = nullptr) {
+__device__ void inorder_contig(const DBatch &b, DMeta *meta, const uint32_t ci, IoShared<IO_T> *sh, const uint32_t *mask = nullptr, const uint32_t *req = nullptr) {
     const int tid = threadIdx.x;
     const uint64_t mbase = MASKED ? (uint64_t)meta->edge_off : 0ull;
     auto refused = [&](uint32_t e) -> bool { const uint64_t x = mbase + e; return ((mask[x >> 5] >> (x & 31)) & 1u) != 0; };
@@ -195,7 +196,7 @@ __device__ void inorder_contig(const DBatch &b, DMeta *meta, IoShared<IO_T> *sh,
     const int V = meta->n_node;
     const bool walked = meta->n_path >= 2; // else the solver's parents run in a circle (a zero-length cycle of tight edges): start from source and target alone
     const int n = walked ? meta->n_path : 2; // path[0] = source ... path[n-1] = target
-    const uint32_t *in_off = b.in_off + meta->node_off + blockIdx.x;
+    const uint32_t *in_off = b.in_off + meta->node_off + ci;
     const uint32_t *esrc = b.esrc + meta->edge_off;
     const long long *ew = b.ew + meta->edge_off;
     const uint64_t *ewl = b.ewl ? b.ewl + (size_t)meta->edge_off * NL : nullptr;
@@ -206,7 +207,7 @@ __device__ void inorder_contig(const DBatch &b, DMeta *meta, IoShared<IO_T> *sh,
     const DGrp *grp = b.grp ? b.grp + meta->grp_off : nullptr;
     const DTNode *tn = b.tnode ? b.tnode + meta->tn_off : nullptr;
     int32_t *path = b.path + meta->node_off;
-    const long long *gt = gtab_of(b, meta);
+    const long long *gt = gtab_at(b, ci);
     auto tight = [&](uint32_t e, const WInt<NL> &dv) -> bool {
         if constexpr (MASKED) { if (refused(e)) return false; }
         const uint32_t sw = esrc[e];
@@ -411,5 +412,5 @@ __global__ __launch_bounds__(IO_T) void k_inorder(DBatch b) {
     if (meta->n_path == -2) walk_path<NL, IO_T>(b, meta, &sh); // solved by k_sssp_wave: not walked yet
     __syncthreads();
     if (meta->n_path < 2 && meta->n_path != -1) return; // no path; -1: the walk along the lowest-index parents cycled
-    inorder_contig<NL, IO_T>(b, meta, &sh);
+    inorder_contig<NL, IO_T>(b, meta, blockIdx.x, &sh);
 }

@@ -401,6 +401,32 @@ struct DReann {
     int32_t stride0;       // limbs per node of dist0 (the run's DBatch.dist_stride; the re-annotation's own may be one wider)
 };
 
+// Scenario batches (phx_resolve.inc): S masked re-annotations side by side, one workgroup per scenario slot.  A slot is one
+// (contig, refused set); the graph arrays are the run's, shared by all slots of a contig; every output is the slot's own.
+struct DScSlot {
+    int32_t contig;      // contig of the batch last run
+    int32_t pad_;
+    int64_t node0;       // first entry of the slot's slices of DScen.parent / path (n_node entries each)
+    int64_t dist0;       // first 64-bit word of the slot's distances (n_node x the contig's limbs)
+    int64_t mask0;       // first word of the slot's bitmap slice: in-edge slot e is bit (edge_off & 31) + e of the slice, so that the
+                         //   slice shifted back by edge_off >> 5 words is indexed by edge_off + e like DReann.mask
+    int64_t plan0;       // first byte of the slot's global window plan (n_node / 32 + 2 bytes)
+};
+struct DScen {
+    const DScSlot *slot; // per slot of the chunk
+    const int2 *pair;    // the listed (slot, ORF in the contig's device order) pairs of the chunk
+    int64_t n_pair;
+    int32_t n_slot;
+    int32_t stride0;     // limbs per node of dist0
+    DMeta *meta;         // per slot: a copy of its contig's record (k_sc_meta), written by the shared solver code
+    uint64_t *dist;
+    int32_t *parent, *path;
+    uint32_t *mask;      // the bitmap slices, cleared per chunk
+    uint8_t *gplan;
+    const uint64_t *dist0; // the run's distances (D)
+    DReannRec *rec;      // per slot: what the host reads
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -451,6 +477,9 @@ void phxk_repl_walk(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl
 void phxk_reann_mask(const DBatch *b, const DReann *q, void *stream);                 // masked re-annotation (phx_resolve.inc): the refused ORFs' in-edge bits,
 void phxk_reann_solve(const DBatch *b, const DReann *q, int nl_mask, int pin_mask, void *stream);   //   the masked sweep (b: the re-annotation's view of the batch; pin_mask: the classes with required ORFs),
 void phxk_reann_finish(const DBatch *b, const DReann *q, int nl_mask, int pin_mask, void *stream);  //   in-order parents on G_F, path, genes, delta
+void phxk_scen_mask(const DBatch *b, const DScen *q, void *stream);                 // scenario batches (phx_resolve.inc): the slots' records and bitmap slices (b: the run's batch),
+void phxk_scen_solve(const DBatch *b, const DScen *q, int nl_mask, void *stream);   //   the masked sweep, a workgroup per slot (b: the run's graph, tot / genes / gene_total / tie the scenarios' own),
+void phxk_scen_finish(const DBatch *b, const DScen *q, int nl_mask, void *stream);  //   in-order parents, path, genes, delta per slot
 #ifdef __cplusplus
 }
 #endif

@@ -153,6 +153,7 @@ __device__ __forceinline__ EWt make_ew(double w, double c) {
 // the encoded integer weight of edge e (contig-relative) whose source word is sw: a coded gap edge (ESRC_F_GAP) has it in the contig's gap table
 __device__ __forceinline__ long long edge_wenc(uint32_t sw, const long long *ew, uint32_t e, const long long *gt) { return ESRC_IS_GAP(sw) ? gt[ESRC_GAP_CODE(sw)] : ew[e]; }
 __device__ __forceinline__ const long long *gtab_of(const DBatch &b, const DMeta *meta) { return b.gtab ? b.gtab + (size_t)(meta - b.meta) * GT_N : nullptr; } // (phx_solve: no table, no coded edge)
+__device__ __forceinline__ const long long *gtab_at(const DBatch &b, uint32_t ci) { return b.gtab ? b.gtab + (size_t)ci * GT_N : nullptr; } // ... by the contig's index (where `meta` is not an entry of b.meta: scenario slots)
 
 // functions.py:174-178: both strands are counted, so Pa == Pt and Pg == Pc.
 __device__ __forceinline__ double contig_pstop(uint32_t gc, int L) {
@@ -419,6 +420,33 @@ void phxk_reann_finish(const DBatch *b, const DReann *q, int nl_mask, int pin_ma
     if (b->mean_len < 8192) NL_LAUNCH_T(k_rc_inorder, 64, pin_mask, dim3(b->n_contig), *b, *q);
     else NL_LAUNCH_T(k_rc_inorder, IO_T_FULL, pin_mask, dim3(b->n_contig), *b, *q);
     hipLaunchKernelGGL(k_rs_fin, dim3((unsigned)((b->n_contig + 63) / 64)), dim3(64), 0, s, *b, *q);
+}
+// scenario batches: the grids are the chunk's slots (pairs for k_sc_mask), not the batch's contigs
+void phxk_scen_mask(const DBatch *b, const DScen *q, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (q->n_slot <= 0) return;
+    hipLaunchKernelGGL(k_sc_meta, dim3((unsigned)q->n_slot), dim3(64), 0, s, *b, *q);
+    if (q->n_pair > 0) hipLaunchKernelGGL(k_sc_mask, dim3((unsigned)((q->n_pair + NT - 1) / NT)), dim3(NT), 0, s, *b, *q);
+}
+extern "C++" template <int NL>
+static void launch_sc_lds(const DBatch *b, const DScen *q, hipStream_t s) {
+    (void)hipFuncSetAttribute((const void *)k_sc_lds<NL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rs_lds_bytes<NL>());
+    hipLaunchKernelGGL(k_sc_lds<NL>, dim3((unsigned)q->n_slot), dim3(SW_THREADS), rs_lds_bytes<NL>(), s, *b, *q);
+}
+void phxk_scen_solve(const DBatch *b, const DScen *q, int nl_mask, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (q->n_slot <= 0) return;
+    if (nl_mask & 1) launch_sc_lds<2>(b, q, s);
+    if (nl_mask & 2) launch_sc_lds<4>(b, q, s);
+    if (nl_mask & 4) launch_sc_lds<8>(b, q, s);
+    if (nl_mask & 8) launch_sc_lds<17>(b, q, s);
+}
+void phxk_scen_finish(const DBatch *b, const DScen *q, int nl_mask, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (q->n_slot <= 0) return;
+    if (b->mean_len < 8192) NL_LAUNCH_T(k_sc_inorder, 64, nl_mask, dim3((unsigned)q->n_slot), *b, *q); // as phxk_reann_finish
+    else NL_LAUNCH_T(k_sc_inorder, IO_T_FULL, nl_mask, dim3((unsigned)q->n_slot), *b, *q);
+    hipLaunchKernelGGL(k_sc_fin, dim3((unsigned)((q->n_slot + 63) / 64)), dim3(64), 0, s, *b, *q);
 }
 // one workgroup for up to 1024 contigs; larger batches in two passes of a workgroup per 256 contigs
 void phxk_layout1(const DBatch *b, void *stream) {

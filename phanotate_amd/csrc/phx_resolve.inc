@@ -61,7 +61,7 @@ __global__ __launch_bounds__(SW_THREADS, NL == 2 ? 5 : (NL == 4 ? 4 : 2)) void k
     DMeta *meta = &b.meta[blockIdx.x];
     const int V = meta->n_node;
     if (!q.sel[blockIdx.x] || !mg_contig(meta) || meta->sssp_nl != NL) return; // (no `overflow` test: the totals are the re-annotation's own, zeroed per call)
-    lds_sweep<NL, RsCfg<NL>>(b, meta, V, q.mask, q.gplan);
+    lds_sweep<NL, RsCfg<NL>>(b, meta, blockIdx.x, V, q.mask, q.gplan);
 }
 
 template <int NL, int IO_T>
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(IO_T) void k_rs_inorder(DBatch b, DReann q) {
     __syncthreads();
     if (!mg_contig(meta)) return; // (a cycle of negative length: the solver has set the status)
     if (meta->n_path < 2 && meta->n_path != -1) return; // no path; -1: the walk along the lowest-index parents cycled
-    inorder_contig<NL, IO_T, true>(b, meta, &sh, q.mask);
+    inorder_contig<NL, IO_T, true>(b, meta, blockIdx.x, &sh, q.mask);
 }
 
 // ---- the pinned re-annotation (DESIGN.md §16): the contigs with required ORFs, DReann.pin ----
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(SW_THREADS, NL == 2 ? 4 : 2) void k_rc_lds(DBatch b
     DMeta *meta = &b.meta[blockIdx.x];
     const int V = meta->n_node;
     if (!q.pin[blockIdx.x] || !mg_contig(meta) || meta->sssp_nl != NL) return;
-    lds_sweep<NL + 1, RcCfg<NL + 1>>(b, meta, V, q.mask, q.gplan, q.req, q.kreq[blockIdx.x]);
+    lds_sweep<NL + 1, RcCfg<NL + 1>>(b, meta, blockIdx.x, V, q.mask, q.gplan, q.req, q.kreq[blockIdx.x]);
 }
 
 template <int NL, int IO_T>
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(IO_T) void k_rc_inorder(DBatch b, DReann q) {
     __syncthreads();
     if (!mg_contig(meta)) return;
     if (meta->n_path < 2 && meta->n_path != -1) return;
-    inorder_contig<NL + 1, IO_T, true, true>(b, meta, &sh, q.mask, q.req);
+    inorder_contig<NL + 1, IO_T, true, true>(b, meta, blockIdx.x, &sh, q.mask, q.req);
 }
 
 // the count of required edges on the best path: the top limb of the NL + 1 limbs at df
@@ -137,4 +137,110 @@ __global__ __launch_bounds__(64) void k_rs_fin(DBatch b, DReann q) {
         r.n_genes = meta->n_genes; r.gene_off = meta->gene_off; r.n_path = meta->n_path;
     }
     q.rec[c] = r;
+}
+
+// ---- scenario batches (DESIGN.md §17): S masked re-annotations of the batch last run side by side, one workgroup per scenario slot ----
+// A slot is one (contig, refused set).  Its kernels are the masked re-annotation's device functions — lds_sweep under RsCfg, inorder_contig
+// with MASKED, emit_genes — entered with the slot's contig as their contig index (`ci`: the in_off row, the gap table and the global plan
+// slice hang on it) and with the slot's view of the batch: the graph arrays are the run's, read only and shared by all slots of a contig;
+// the per-contig record is the slot's own copy (DScen.meta), and the output pointers of the by-value DBatch are moved to where the
+// contig's `node_off` lands on the slot's slices of dist / parent / path — what reann_batch does for the re-annotation as a whole, per
+// slot.  Bitmap and plan pointers are shifted the same way (bit edge_off + e, byte node_off / 32 + ci).  Gene records come from the
+// chunk's shared counter as in §14; the tie scratch from the chunk's bump allocator (DTotals.tie_need).
+
+// a thread block per slot: the slot's copy of its contig's record, as the run left it
+__global__ __launch_bounds__(64) void k_sc_meta(DBatch b, DScen q) {
+    const int s = (int)blockIdx.x;
+    const int c = q.slot[s].contig;
+    if (c < 0 || c >= b.n_contig) return; // (the host has checked it)
+    const uint64_t *from = (const uint64_t *)&b.meta[c];
+    uint64_t *to = (uint64_t *)&q.meta[s];
+    static_assert(sizeof(DMeta) % 8 == 0, "DMeta is copied in 64-bit words");
+    for (int k = (int)threadIdx.x; k < (int)(sizeof(DMeta) / 8); k += 64) to[k] = from[k];
+}
+
+// a thread per listed (slot, ORF) pair: the ORF's edge, found as k_rs_mask finds it, sets its bit in the slot's bitmap slice
+__global__ __launch_bounds__(NT) void k_sc_mask(DBatch b, DScen q) {
+    const int64_t p = (int64_t)blockIdx.x * NT + (int64_t)threadIdx.x;
+    if (p >= q.n_pair) return;
+    const int2 pr = q.pair[p];
+    if (pr.x < 0 || pr.x >= q.n_slot) return;
+    const DScSlot sl = q.slot[pr.x];
+    if (sl.contig < 0 || sl.contig >= b.n_contig) return;
+    const DMeta *meta = &b.meta[sl.contig];
+    const int k = pr.y;
+    if (!mg_contig(meta) || k < 0 || k >= meta->n_orf) return;
+    const DOrf o = b.orf[meta->orf_off + k];
+    const int V = meta->n_node;
+    const int sn = b.onode[meta->orf_off + k], tn = b.grp[meta->grp_off + o.grp].node;
+    const bool fwd = o.frame > 0;
+    const int u = fwd ? sn : tn, v = fwd ? tn : sn;
+    if (u < 0 || v < 0 || u >= V || v >= V) return;
+    const uint32_t *in_off = b.in_off + meta->node_off + sl.contig;
+    const uint32_t *esrc = b.esrc + meta->edge_off;
+    const uint64_t lo = (uint64_t)meta->edge_off & 31u; // the slice keeps edge_off's position in a word
+    for (uint32_t x = in_off[v], x1 = in_off[v + 1]; x < x1; x++)
+        if (!ESRC_IS_GAP(esrc[x]) && ESRC_NODE(esrc[x]) == (uint32_t)u) { // (no such edge: the ORF is ignored)
+            atomicOr(&q.mask[sl.mask0 + (int64_t)((lo + x) >> 5)], 1u << ((lo + x) & 31));
+            break;
+        }
+}
+
+// The slot's view of the batch (above).  Returns the slot's record; *ci its contig, *mask and *gplan what lds_sweep / inorder_contig index
+// with edge_off + e and node_off / 32 + ci.
+__device__ __forceinline__ DMeta *sc_view(DBatch &b, const DScen &q, uint32_t *ci, const uint32_t **mask, uint8_t **gplan) {
+    const DScSlot sl = q.slot[blockIdx.x];
+    DMeta *meta = &q.meta[blockIdx.x];
+    const int64_t node_off = meta->node_off;
+    b.dist = q.dist + (sl.dist0 - node_off * b.dist_stride);
+    b.parent = q.parent + (sl.node0 - node_off);
+    b.path = q.path + (sl.node0 - node_off);
+    *ci = (uint32_t)sl.contig;
+    *mask = q.mask + (sl.mask0 - (meta->edge_off >> 5));
+    *gplan = q.gplan + (sl.plan0 - (node_off >> 5) - (int64_t)sl.contig);
+    return meta;
+}
+
+template <int NL>
+__global__ __launch_bounds__(SW_THREADS, NL == 2 ? 5 : (NL == 4 ? 4 : 2)) void k_sc_lds(DBatch b, DScen q) { // (the bounds of k_rs_lds)
+    const uint32_t *mask;
+    uint8_t *gplan;
+    uint32_t ci;
+    DMeta *meta = sc_view(b, q, &ci, &mask, &gplan);
+    const int V = meta->n_node;
+    if (!mg_contig(meta) || meta->sssp_nl != NL) return;
+    lds_sweep<NL, RsCfg<NL>>(b, meta, ci, V, mask, gplan);
+}
+
+template <int NL, int IO_T>
+__global__ __launch_bounds__(IO_T) void k_sc_inorder(DBatch b, DScen q) {
+    __shared__ IoShared<IO_T> sh;
+    const uint32_t *mask;
+    uint8_t *gplan;
+    uint32_t ci;
+    DMeta *meta = sc_view(b, q, &ci, &mask, &gplan);
+    if (meta->sssp_nl != NL) return;
+    if (threadIdx.x == 0) { sh.flag = 0; meta->tie = 0; }
+    __syncthreads();
+    if (!mg_contig(meta)) return;
+    if (meta->n_path < 2 && meta->n_path != -1) return;
+    inorder_contig<NL, IO_T, true>(b, meta, ci, &sh, mask);
+}
+
+// a thread per slot: the record the host reads (k_rs_fin's, without the pinned part)
+__global__ __launch_bounds__(64) void k_sc_fin(DBatch b, DScen q) {
+    const int s = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (s >= q.n_slot) return;
+    const DMeta *meta = &q.meta[s];
+    DReannRec r;
+    r.status = meta->status; r.n_genes = 0; r.gene_off = 0; r.n_path = 0; r.tie = meta->tie; r.delta = __builtin_inf();
+    r.unmet = 0; r.pad_ = 0;
+    if (meta->status >= 0 && meta->status != PHX_S_NOPATH && meta->n_path >= 2) {
+        const int V = meta->n_node, nl = meta->sssp_nl;
+        const uint64_t *df = q.dist + q.slot[s].dist0 + (size_t)(V - 1) * nl;
+        const uint64_t *d0 = q.dist0 + (size_t)meta->node_off * q.stride0 + (size_t)(V - 1) * nl;
+        r.delta = nl == 2 ? rs_delta<2>(df, d0) : nl == 4 ? rs_delta<4>(df, d0) : nl == 8 ? rs_delta<8>(df, d0) : rs_delta<17>(df, d0);
+        r.n_genes = meta->n_genes; r.gene_off = meta->gene_off; r.n_path = meta->n_path;
+    }
+    q.rec[s] = r;
 }

@@ -389,10 +389,11 @@ __device__ __forceinline__ WInt<NL> sw_weight(uint32_t sw, const long long *ew, 
     }
 }
 
-// The sweep of one contig by one workgroup of SW_THREADS threads: distances to b.dist, lowest-index tight parents to b.parent, then the
+// The sweep of one contig by one workgroup of SW_THREADS threads (ci: the contig's index in the batch — blockIdx.x where a workgroup is a
+// contig; a scenario slot's workgroup passes its slot's contig, phx_resolve.inc): distances to b.dist, lowest-index tight parents to b.parent, then the
 // path and the genes.  V = meta->n_node (the caller has read it; after expand_contig's fence a second read would be a second load).
 template <int NL, class P>
-__device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const int V, const uint32_t *mask, uint8_t *gplan, const uint32_t *req = nullptr, const int kreq = 0) {
+__device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const uint32_t ci, const int V, const uint32_t *mask, uint8_t *gplan, const uint32_t *req = nullptr, const int kreq = 0) {
     constexpr int RING = P::RING, ECAP = P::ECAP;
     constexpr int EPT = (ECAP + SW_THREADS - 1) / SW_THREADS; // tile edges prefetched per thread
     extern __shared__ __align__(16) uint8_t smem[];
@@ -402,10 +403,10 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const in
     __shared__ uint8_t s_list[SW_MAX];
     const int tid = threadIdx.x;
     const int SRC = V - 2, TGT = V - 1, ncds = V - 2;
-    const uint32_t *in_off = b.in_off + meta->node_off + blockIdx.x;
+    const uint32_t *in_off = b.in_off + meta->node_off + ci;
     const uint32_t *esrc = b.esrc + meta->edge_off;
     const long long *ew = b.ew + meta->edge_off;
-    const long long *gt = P::MASKED ? gtab_of(b, meta) : nullptr;
+    const long long *gt = P::MASKED ? gtab_at(b, ci) : nullptr;
     const uint64_t ebase = (uint64_t)meta->edge_off;
     const DNode *nd = b.node + meta->node_off;
     uint64_t *gdist = b.dist + (size_t)meta->node_off * b.dist_stride;
@@ -417,7 +418,7 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const in
     uint32_t *tsrc = (uint32_t *)(tw + (size_t)ECAP * NL);
     const size_t lds_words = (size_t)(RING + 1) * NL * 2 + (size_t)ECAP * NL * 2 + ECAP; // 32-bit words before the plan
     const int nW = (V + SW_ADV - 1) / SW_ADV;
-    uint8_t *plan = !P::MASKED || nW <= RS_PLAN_LDS ? (uint8_t *)(tsrc + ECAP) : gplan + (size_t)(meta->node_off >> 5) + blockIdx.x; // (a contig's slice: >= V / 32 + 1 bytes)
+    uint8_t *plan = !P::MASKED || nW <= RS_PLAN_LDS ? (uint8_t *)(tsrc + ECAP) : gplan + (size_t)(meta->node_off >> 5) + ci; // (a contig's slice: >= V / 32 + 1 bytes)
     for (int v = tid; v < V; v += SW_THREADS) {
         WInt<NL> d;
 #pragma unroll
@@ -732,5 +733,5 @@ __global__ __launch_bounds__(SW_THREADS, NL == 2 ? SW_WPS : (NL == 4 ? 4 : 2)) v
     expand_contig(b, meta, (int)threadIdx.x, (int)blockDim.x); // (coded gap edges: the sweep reads plain rows)
     __syncthreads();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    lds_sweep<NL, SwRun>(b, meta, V, nullptr, nullptr);
+    lds_sweep<NL, SwRun>(b, meta, blockIdx.x, V, nullptr, nullptr);
 }
