@@ -40,7 +40,8 @@ extern "C" {
  *        phx_replacement_stats, phx_format_replacements;
  *        (additions, version unchanged) phx_reannotate_flat, phx_orf_offsets, phx_tap_repath, phx_reannotate_ms;
  *        (addition, version unchanged: the suite pins 410) phx_constrain_flat — probe for the symbol, not for a version;
- *        (additions, version unchanged) phx_scenarios_flat, phx_scenarios_ms, phx_scenario_chunks, phx_tap_scenario_path — probe for the symbol */
+ *        (additions, version unchanged) phx_scenarios_flat, phx_scenarios_ms, phx_scenario_chunks, phx_tap_scenario_path — probe for the symbol;
+ *        (addition, version unchanged) phx_pinned_scenarios_flat — probe for the symbol */
 #define PHX_MAX_CODONS 16
 
 /* library-level errors */
@@ -449,8 +450,8 @@ int phx_reannotate_ms(phx_ctx *ctx, float *ms /* [3] */);
  * listed ORFs: status[j], delta[j] and genes[offsets[j] .. offsets[j+1]) are byte for byte what phx_reannotate_flat returns for that
  * contig when the mask holds exactly F on that contig and bit 0 of its flags is set — format, order, tie rule, PHX_S_NOPATH with +inf,
  * PHX_S_OVERFLOW and a run error passed through.  Scenarios are independent of each other: several may name the same contig and may
- * overlap; an empty list is solved like any other (the device path); duplicates inside a list are allowed.  Only refused sets: there
- * are no required ORFs per scenario.
+ * overlap; an empty list is solved like any other (the device path); duplicates inside a list are allowed.  Only refused sets here:
+ * phx_pinned_scenarios_flat below takes required ORFs per scenario as well.
  *   scen_contig  [n_scen]: contig of the batch last run
  *   scen_off     [n_scen+1]: scenario j lists scen_orf[scen_off[j] .. scen_off[j+1]); starts at 0, non-decreasing
  *   scen_orf     indices into phx_tap_orfs order of the scenario's contig
@@ -466,7 +467,26 @@ int phx_reannotate_ms(phx_ctx *ctx, float *ms /* [3] */);
 int phx_scenarios_flat(phx_ctx *ctx, int64_t n_scen, const int32_t *scen_contig /* [n_scen] */, const int64_t *scen_off /* [n_scen+1] */,
                        const int32_t *scen_orf, const int64_t *orf_offsets /* [n+1] */, uint32_t flags, phx_gene *genes, int64_t cap,
                        int64_t *offsets /* [n_scen+1] */, int32_t *status /* [n_scen] */, double *delta /* [n_scen] */, int64_t *total);
-/* device time of the last scenario solve, summed over its chunks, ms[3]: slot records + bitmap slices, masked solve, in-order parents +
+/* ---- pinned scenario batches: many pinned re-annotations of the batch last run in one call ----
+ * phx_scenarios_flat with a second list per scenario: scenario j refuses F_j = forbid_orf[forbid_off[j] .. forbid_off[j+1]) and requires
+ * R_j = require_orf[require_off[j] .. require_off[j+1]), both indices in phx_tap_orfs order of contig scen_contig[j].  It is, by
+ * definition, phx_constrain_flat applied to that contig with exactly these two sets and bit 0 of its flags set: status[j], delta[j],
+ * unmet[j] and genes[offsets[j] .. offsets[j+1]) are byte for byte that call's for the contig — PHX_S_NOPATH with +inf, PHX_S_NEGCYCLE
+ * (no genes, +inf, unmet = |R_j|) when a cycle the source reaches runs through a required edge, PHX_S_OVERFLOW and a run error passed
+ * through, unmet = |R_j| wherever there is no result.  |R_j| counts ORFs: duplicates inside a list are allowed and count once.  A scenario
+ * with R_j empty is phx_scenarios_flat's scenario byte for byte (the same kernels), unmet 0.  Scenarios are independent: the same ORF may
+ * be refused in one and required in another; the same ORF in both lists of ONE scenario is PHX_E_ARG before any kernel.
+ * Calling convention (size query with genes NULL, then the fetch), argument checks (on both lists), state rules, chunking and the
+ * device-memory budget are those of phx_scenarios_flat; require_off and unmet must not be NULL.  The two calls are one solve on one set
+ * of buffers with one cached result keyed on both lists: phx_scenarios_ms, phx_scenario_chunks and phx_tap_scenario_path report on the
+ * last scenario solve of either kind, and for a scenario with required ORFs the distance phx_tap_scenario_path reports is the W-sum W(P)
+ * in the contig's own limbs, as phx_tap_repath does after phx_constrain_flat. */
+int phx_pinned_scenarios_flat(phx_ctx *ctx, int64_t n_scen, const int32_t *scen_contig /* [n_scen] */, const int64_t *forbid_off /* [n_scen+1] */,
+                              const int32_t *forbid_orf, const int64_t *require_off /* [n_scen+1] */, const int32_t *require_orf,
+                              const int64_t *orf_offsets /* [n+1] */, uint32_t flags /* reserved: 0 */, phx_gene *genes, int64_t cap,
+                              int64_t *offsets /* [n_scen+1] */, int32_t *status /* [n_scen] */, double *delta /* [n_scen] */, int32_t *unmet /* [n_scen] */,
+                              int64_t *total);
+/* device time of the last scenario solve (of either kind), summed over its chunks, ms[3]: slot records + bitmap slices, masked solve, in-order parents +
  * path + genes + the copies to the host.  All 0 before the first. */
 int phx_scenarios_ms(phx_ctx *ctx, float *ms /* [3] */);
 /* path and D_F of scenario `scen` of the last scenario solve, like phx_tap_repath (n_path 0: no path, or a scenario whose contig was not

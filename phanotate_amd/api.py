@@ -574,7 +574,7 @@ class Annotator:
         return status[:S], offs, genes[: int(total.value)], delta[:S]
 
     def scenarios_ms(self):
-        """Device time of the last scenario solve in ms, summed over its chunks: slot records + bitmaps, masked solve, path + genes + copy
+        """Device time of the last scenario solve (scenarios() or pinned_scenarios()) in ms, summed over its chunks: slot records + bitmaps, masked solve, path + genes + copy
         (phx_scenarios_ms)."""
         ms = (C.c_float * 3)()
         self._chk(self.L.phx_scenarios_ms(self.h, ms), "phx_scenarios_ms")
@@ -585,8 +585,9 @@ class Annotator:
         return int(self.L.phx_scenario_chunks(self.h))
 
     def scenario_path(self, j, contig):
-        """(path as device node ids, its length D_F as a python int) of scenario j of the last scenarios() call, like reannotated_path;
-        `contig` is the scenario's contig.  Served while the scenario's chunk is resident (phx_tap_scenario_path)."""
+        """(path as device node ids, its length D_F as a python int) of scenario j of the last scenarios() or pinned_scenarios() call, like
+        reannotated_path (a scenario with required ORFs: the W-sum W(P)); `contig` is the scenario's contig.  Served while the scenario's
+        chunk is resident (phx_tap_scenario_path)."""
         g = self.globals(contig)
         p = np.zeros(max(g.n_node, 1), np.int32)
         n = C.c_int32()
@@ -631,6 +632,92 @@ class Annotator:
                         o["restart_left"], o["restart_right"] = g["left"], g["right"]
                         break
                 k += 1
+        return st, offs, rec, soffs, genes
+
+    # ---- pinned scenario batches ----
+    @staticmethod
+    def _pinned_scenario_arrays(scen, n, oo):
+        """(contig int32[S], forbid_off int64[S+1], forbid_orf int32[], require_off int64[S+1], require_orf int32[]) of a sequence of
+        (contig, forbid, require) — index arrays or None; IndexError / ValueError as _scenario_arrays."""
+        try:
+            triples = [(i, f, r) for i, f, r in scen]
+        except (TypeError, ValueError):
+            raise ValueError("a pinned scenario is a (contig, forbid, require) triple") from None
+        contig, foff, forf = Annotator._scenario_arrays([(i, f) for i, f, _ in triples], n, oo)
+        _, roff, rorf = Annotator._scenario_arrays([(i, r) for i, _, r in triples], n, oo)
+        return contig, foff, forf, roff, rorf
+
+    def pinned_scenarios(self, scen):
+        """(status int32[S], offsets int64[S+1], genes structured array[total], delta float64[S], unmet int32[S]): S pinned
+        re-annotations of the batch last run in one call (phx_pinned_scenarios_flat).  `scen` is a sequence of (contig,
+        forbid, require), each list an array of indices into orfs(contig) or None; scenario j is constrain() of that contig with exactly
+        those two sets — status[j], delta[j], unmet[j] and genes[offsets[j]:offsets[j+1]] are byte for byte that call's for the contig —
+        solved side by side on the resident graph, one workgroup per scenario.  Scenarios are independent (the same contig may be named
+        many times, lists may overlap between scenarios, be empty or hold duplicates); an ORF in both lists of one scenario raises
+        PhxError (PHX_E_ARG).  As in constrain(), a required ORF whose edge lies on a cycle the source reaches gives status -9
+        (PHX_S_NEGCYCLE) without genes — not rare among short overlapping ORFs; refusing an edge of the cycle takes it away.  A scenario
+        that requires nothing is scenarios()' scenario."""
+        n = self.n
+        oo = self.orf_offsets()
+        scen = list(scen)
+        contig, foff, forf, roff, rorf = self._pinned_scenario_arrays(scen, n, oo)
+        S = len(scen)
+        offs = np.zeros(S + 1, np.int64)
+        status = np.zeros(max(S, 1), np.int32)
+        delta = np.zeros(max(S, 1), np.float64)
+        unmet = np.zeros(max(S, 1), np.int32)
+        total = C.c_int64(0)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        call = lambda g, cap: self._chk(self.L.phx_pinned_scenarios_flat(self.h, S, vp(contig), vp(foff), vp(forf), vp(roff), vp(rorf), vp(oo), 0, g, cap, vp(offs), vp(status),
+                                                                            vp(delta), vp(unmet), C.byref(total)), "phx_pinned_scenarios_flat")
+        call(None, 0)
+        genes = np.empty(max(int(total.value), 1), _lib.GENE_DT)
+        call(vp(genes), len(genes))
+        return status[:S], offs, genes[: int(total.value)], delta[:S], unmet[:S]
+
+    def alt_starts(self, max_alts=None):
+        """(status int32[n], offsets int64[n+1], records structured array[total] of _lib.ALT_DT, scen_offsets int64[total+1], genes):
+        for every record of drop_margins() (the called CDS genes in path order; status as drop_margins() reports it) and every OTHER ORF
+        of the gene's stop group, in the order of orfs(i) (at most max_alts per gene when given), the best annotation that keeps that ORF
+        — one pinned scenario each, requiring the alternative and refusing nothing, all in one pinned_scenarios() call.  The records of
+        contig i are records[offsets[i]:offsets[i+1]]; delta = the scenario's delta (the alternative's margin bit for bit where status
+        and unmet are 0), status -9 where the alternative's edge lies on a cycle, unmet 1 where the alternative cannot be called (no
+        edge, or on no source-to-target path); n_removed / n_added count the genes of the run's annotation (the device path's) missing
+        from the new one and the reverse; genes[scen_offsets[k]:scen_offsets[k+1]] is record k's full new annotation."""
+        st, doffs, drec = self.drop_margins()
+        n = self.n
+        scen, head = [], []
+        offs = np.zeros(n + 1, np.int64)
+        for i in range(n):
+            if doffs[i + 1] > doffs[i]:
+                group = self.orfs(i)["group"]
+            for r in drec[doffs[i]:doffs[i + 1]]:
+                k = self.orf_index(i, r["left"], r["right"], r["strand"])
+                alts = [int(a) for a in np.nonzero(group == group[k])[0] if a != k]
+                for a in alts if max_alts is None else alts[: max(int(max_alts), 0)]:
+                    scen.append((i, None, [a]))
+                    head.append((i, r, k, a))
+            offs[i + 1] = len(scen)
+        sstat, soffs, genes, delta, unmet = self.pinned_scenarios(scen)
+        self._chk(self.L.phx_set_exact(self.h, 0), "phx_set_exact")  # the device's own lists, as download_flat(exact=False)
+        try:
+            _, roffs, rgenes = self._download_flat()
+        finally:
+            self._chk(self.L.phx_set_exact(self.h, 1), "phx_set_exact")
+        key = lambda g: (int(g["left"]), int(g["right"]), int(g["strand"]), int(g["frame"]))
+        rec = np.zeros(len(scen), _lib.ALT_DT)
+        have, have_of, orfs_of = None, -1, None
+        for x, (i, r, k, a) in enumerate(head):
+            if have_of != i:
+                have, have_of, orfs_of = {key(g) for g in rgenes[roffs[i]:roffs[i + 1]]}, i, self.orfs(i)
+            o = rec[x]
+            o["left"], o["right"], o["strand"], o["orf"], o["alt"] = r["left"], r["right"], r["strand"], k, a
+            ao = orfs_of[a]
+            fwd = ao["frame"] > 0
+            o["alt_left"], o["alt_right"] = (ao["start"], ao["stop"] + 2) if fwd else (ao["stop"], ao["start"] + 2)
+            o["status"], o["delta"], o["unmet"] = sstat[x], delta[x], unmet[x]
+            new = {key(g) for g in genes[soffs[x]:soffs[x + 1]]}
+            o["n_removed"], o["n_added"] = len(have - new), len(new - have)
         return st, offs, rec, soffs, genes
 
     def reannotated_path(self, i):

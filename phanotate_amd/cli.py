@@ -44,6 +44,7 @@ def get_args(argv=None):
     p.add_argument("--drop-margins", metavar="FILE", default=None, help="also write every called gene with its drop margin, the cost of the best path without it (DESIGN.md §12), to FILE")
     p.add_argument("--drop-replacements", metavar="FILE", default=None, help="also write every called gene with what the best path without it calls instead (DESIGN.md §13) to FILE")
     p.add_argument("--start-drops", metavar="FILE", default=None, help="also write every called gene with the cost of refusing its start and the start the best annotation then takes for its stop (DESIGN.md §17) to FILE")
+    p.add_argument("--alt-starts", metavar="FILE", default=None, help="also write, for every called gene and every other start of its stop, the cost of the best annotation that takes that start instead (DESIGN.md §18) to FILE")
     p.add_argument("--forbid", metavar="FILE", default=None, help="ORFs to refuse in a second annotation (DESIGN.md §14): lines whose first four columns are START STOP FRAME CONTIG as the tabular output prints a gene; needs --reannotation")
     p.add_argument("--require", metavar="FILE", default=None, help="ORFs to keep in a second annotation (DESIGN.md §16), in the format of --forbid; alone or with --forbid; needs --reannotation, which then carries a #unmet: line per contig")
     p.add_argument("--reannotation", metavar="OUT", default=None, help="write the annotation without the ORFs of --forbid (and keeping those of --require) to OUT: the tabular block of every contig with a #delta: header line")
@@ -67,6 +68,12 @@ def get_args(argv=None):
         p.error("argument --start-drops: not available under a multi-rank launch")
     if args.start_drops is not None and int(args.gpus) > 1:  # the scenarios work on the batch resident on one context
         p.error("argument --start-drops: not available with --gpus above 1")
+    if args.alt_starts is not None and args.dump:
+        p.error("argument --alt-starts: not allowed with argument -d/--dump")
+    if args.alt_starts is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        p.error("argument --alt-starts: not available under a multi-rank launch")
+    if args.alt_starts is not None and int(args.gpus) > 1:  # the scenarios work on the batch resident on one context
+        p.error("argument --alt-starts: not available with --gpus above 1")
     for flag, val in (("--forbid", args.forbid), ("--require", args.require), ("--reannotation", args.reannotation)):
         if val is not None and args.dump:
             p.error("argument %s: not allowed with argument -d/--dump" % flag)
@@ -164,6 +171,36 @@ def format_start_drops(names, status, offsets, records):
             else:
                 tail = "-"
             buf.write("%d\t%d\t%s\t%s\t%s\n" % (left, right, chr(44 - (-1 if rev else 1)), repr(float(r["drop"])), tail))
+    return buf.getvalue()
+
+
+def format_alt_starts(names, status, offsets, records):
+    """--alt-starts FILE: per contig with status >= 0 "#id:\t<name>", the header, one row per record of Annotator.alt_starts() (a called
+    gene of the device path and another start of its stop, required in its place): the gene's START STOP FRAME as the tabular output
+    prints them, the alternative's START, DELTA — repr(delta), or "cycle" (the alternative's edge lies on a cycle: PHX_S_NEGCYCLE),
+    "unmet" (the alternative cannot be called) or "inf" (no path) —, and the genes the run's annotation loses and gains."""
+    import io
+
+    import numpy as np
+
+    buf = io.StringIO()
+    for i, nm in enumerate(names):
+        if status[i] < 0:
+            continue
+        buf.write("#id:\t" + nm + "\n#START\tSTOP\tFRAME\tALT\tDELTA\tREMOVED\tADDED\n")
+        for r in records[offsets[i]:offsets[i + 1]]:
+            rev = r["strand"] < 0
+            left, right = (int(r["right"]), int(r["left"])) if rev else (int(r["left"]), int(r["right"]))  # locus.py:44-46
+            alt = int(r["alt_right"]) if rev else int(r["alt_left"])
+            if r["status"] == -9:
+                delta = "cycle"
+            elif r["unmet"] != 0:
+                delta = "unmet"
+            elif r["status"] != 0 or not np.isfinite(r["delta"]):
+                delta = "inf"
+            else:
+                delta = repr(float(r["delta"]))
+            buf.write("%d\t%d\t%s\t%d\t%s\t%d\t%d\n" % (left, right, chr(44 - (-1 if rev else 1)), alt, delta, int(r["n_removed"]), int(r["n_added"])))
     return buf.getvalue()
 
 
@@ -364,6 +401,7 @@ def main(argv=None):
     drop_parts = []  # --drop-margins: the same of the drop margins
     repl_parts = []  # --drop-replacements: (status, offsets, records, genes) of every batch, in order
     start_parts = []  # --start-drops: (status, offsets, records) of every batch, in order
+    alt_parts = []  # --alt-starts: the same of Annotator.alt_starts()
     reann_parts = []  # --reannotation: (status, offsets, genes, delta[, unmet]) of every batch, in order
     forbid_entries = require_entries = None
     try:
@@ -397,7 +435,7 @@ def main(argv=None):
             if lo >= len(idx):
                 break
         t_parts["batches"] = len(cuts)
-        if forbid_entries is not None or require_entries is not None or args.start_drops is not None:  # the re-annotation and the scenarios work on the batch resident on one context: the batches one after the other
+        if forbid_entries is not None or require_entries is not None or args.start_drops is not None or args.alt_starts is not None:  # the re-annotation and the scenarios work on the batch resident on one context: the batches one after the other
             parts = []
             for lo, hi in cuts:
                 t0 = time.perf_counter()
@@ -416,6 +454,8 @@ def main(argv=None):
                     drop_parts.append(ann.drop_margins())
                 if args.start_drops is not None:
                     start_parts.append(ann.start_drops()[:3])
+                if args.alt_starts is not None:
+                    alt_parts.append(ann.alt_starts()[:3])
                 names = [fa.names[int(i)] for i in idx[lo:hi]]
                 here = set(names)
                 refused = resolve_forbid([e for e in forbid_entries or [] if e[3] in here], names, ann.orf_index)
@@ -541,6 +581,12 @@ def main(argv=None):
             s_offsets = np.concatenate([[0], np.cumsum(s_counts)]).astype(np.int64)
             with open(args.start_drops, "w") as fh:
                 fh.write(format_start_drops(fa.names, s_status, s_offsets, np.concatenate([m[2] for m in start_parts])))
+        if args.alt_starts is not None:
+            a_status = np.concatenate([m[0] for m in alt_parts])
+            a_counts = np.concatenate([np.diff(m[1]) for m in alt_parts])
+            a_offsets = np.concatenate([[0], np.cumsum(a_counts)]).astype(np.int64)
+            with open(args.alt_starts, "w") as fh:
+                fh.write(format_alt_starts(fa.names, a_status, a_offsets, np.concatenate([m[2] for m in alt_parts])))
         if args.reannotation is not None:
             q_status = np.concatenate([m[0] for m in reann_parts])
             q_counts = np.concatenate([np.diff(m[1]) for m in reann_parts])

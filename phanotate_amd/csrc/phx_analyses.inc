@@ -751,19 +751,23 @@ int phx_reannotate_ms(phx_ctx *c, float *ms) {
     return PHX_OK;
 }
 
-// ---- scenario batches (phx_resolve.inc, DESIGN.md §17) ----
+// ---- scenario batches (phx_resolve.inc, DESIGN.md §17), with required ORFs per scenario (§18) ----
 // h_srec[j].status before the solve: the scenario gets a slot / its contig is not solved again and the run's verdict stands (neither is a status the device reports)
 static const int32_t SC_SLOT = -99, SC_NOSLOT = -100;
-// Device bytes of one slot of contig i: distances, parent, path, bitmap slice, window plan, gene records, the record copy.
-static size_t scen_slot_bytes(const phx_ctx *c, int i) {
+// Device bytes of one slot of contig i: distances, parent, path, bitmap slice, window plan, gene records, the record copy; a pinned slot
+// (§18) has one limb more per node, a second bitmap slice and its entries of DScen.req0 / nreq / kreq.
+static size_t scen_slot_bytes(const phx_ctx *c, int i, bool pinned = false) {
     const DMeta &m = c->meta[(size_t)i];
     const size_t V = (size_t)m.n_node, E = (size_t)m.n_edge;
-    return V * ((size_t)m.sssp_nl * 8 + 4 + 4) + (E / 32 + 3) * 4 + (V / 32 + 2) + (V + 1) * sizeof(DGene) + sizeof(DMeta) + sizeof(DScSlot) + sizeof(DReannRec);
+    return V * ((size_t)m.sssp_nl * 8 + 4 + 4) + (E / 32 + 3) * 4 + (V / 32 + 2) + (V + 1) * sizeof(DGene) + sizeof(DMeta) + sizeof(DScSlot) + sizeof(DReannRec) +
+           (pinned ? V * 8 + (E / 32 + 3) * 4 + 16 : 0);
 }
 
 // Solves the scenarios with a slot (h_srec[j].status == SC_SLOT) in chunks under the budget; records into h_srec, genes into h_sgenes.
-// perm: per contig named, tap index -> ORF in the contig's device order (-1: no such ORF in the device's groups).
-static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const int64_t *scen_off, const int32_t *scen_orf,
+// perm: per contig named, tap index -> ORF in the contig's device order (-1: no such ORF in the device's groups).  req_off / req_orf: the
+// required lists without duplicates; a scenario with a non-empty one gets a pinned slot.  In a chunk's slot table the pinned slots follow
+// the plain ones (the slices keep the scenarios' order): k_sc_* get the head of the table, k_scp_* its tail.
+static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const int64_t *scen_off, const int32_t *scen_orf, const int64_t *req_off, const int32_t *req_orf,
                         const std::vector<std::vector<int32_t>> &perm) {
     int rc;
     hipStream_t s = c->stream;
@@ -773,51 +777,73 @@ static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const
     c->h_sslot.assign((size_t)S, DScSlot{});
     c->h_schunk_of.assign((size_t)S, 0);
     if ((rc = analysis_events(c))) return rc;
-    std::vector<DScSlot> slots;
-    std::vector<int2> pairs;
-    std::vector<int64_t> which; // scenario of every slot of the chunk
+    std::vector<DScSlot> slots, pslots; // plain, pinned
+    std::vector<int2> pairs, rpairs;    // (a pinned slot's index: -1 - its place among the pinned ones, until the chunk is closed)
+    std::vector<int64_t> which, pwhich; // scenario of every slot of the chunk
+    std::vector<int64_t> preq0;         // per pinned slot: DScen.req0
+    std::vector<int32_t> pnreq;         //   ... and nreq
+    std::vector<uint8_t> &pin = c->h_spin; // what the kernels read per slot: req0 (int64), nreq, kreq (int32)
     for (int64_t j0 = 0; j0 < S;) {
         // ---- the chunk: scenarios j0 .. j1 with a slot, as many as the budget holds (at least one) ----
-        slots.clear(); pairs.clear(); which.clear();
-        size_t bytes = 0, nodes = 0, words = 0, mwords = 0, plan = 0;
-        int nlm = 0;
+        slots.clear(); pslots.clear(); pairs.clear(); rpairs.clear(); which.clear(); pwhich.clear(); preq0.clear(); pnreq.clear();
+        size_t bytes = 0, nodes = 0, words = 0, mwords = 0, rwords = 0, plan = 0;
+        int nlm = 0, pinm = 0;
         int64_t j1 = j0;
         for (; j1 < S; j1++) {
             if (c->h_srec[(size_t)j1].status != SC_SLOT) continue;
             const int i = scen_contig[j1];
             const DMeta &m = c->meta[(size_t)i];
-            const size_t need = scen_slot_bytes(c, i);
-            if (!slots.empty() && bytes + need > (size_t)c->scen_budget) break;
+            const int32_t nreq = (int32_t)(req_off[j1 + 1] - req_off[j1]);
+            const bool pinned = nreq > 0;
+            const size_t need = scen_slot_bytes(c, i, pinned);
+            if (!(slots.empty() && pslots.empty()) && bytes + need > (size_t)c->scen_budget) break;
             bytes += need;
             DScSlot sl;
-            sl.contig = i; sl.pad_ = 0;
+            sl.contig = i; sl.pinned = pinned ? 1 : 0;
             sl.node0 = (int64_t)nodes; sl.dist0 = (int64_t)words; sl.mask0 = (int64_t)mwords; sl.plan0 = (int64_t)plan;
+            const size_t mw = (((size_t)m.edge_off & 31) + (size_t)m.n_edge) / 32 + 2;
             nodes += (size_t)m.n_node;
-            words += ((size_t)m.n_node * (size_t)m.sssp_nl + 1) & ~(size_t)1;
-            mwords += (((size_t)m.edge_off & 31) + (size_t)m.n_edge) / 32 + 2;
+            words += ((size_t)m.n_node * (size_t)(m.sssp_nl + (pinned ? 1 : 0)) + 1) & ~(size_t)1;
+            mwords += mw;
             plan += (size_t)m.n_node / 32 + 2;
-            nlm |= nl_class_bit(m.sssp_nl);
+            (pinned ? pinm : nlm) |= nl_class_bit(m.sssp_nl);
+            const int id = pinned ? -1 - (int)pslots.size() : (int)slots.size();
             const std::vector<int32_t> &pm = perm[(size_t)i];
             for (int64_t k = scen_off[j1]; k < scen_off[j1 + 1]; k++) {
                 const int32_t d = pm[(size_t)scen_orf[k]];
-                if (d >= 0) pairs.push_back(make_int2((int)slots.size(), d));
+                if (d >= 0) pairs.push_back(make_int2(id, d));
             }
-            slots.push_back(sl);
-            which.push_back(j1);
+            for (int64_t k = req_off[j1]; k < req_off[j1 + 1]; k++) {
+                const int32_t d = pm[(size_t)req_orf[k]];
+                if (d >= 0) rpairs.push_back(make_int2(id, d));
+            }
+            if (pinned) { preq0.push_back((int64_t)rwords); pnreq.push_back(nreq); rwords += mw; pslots.push_back(sl); pwhich.push_back(j1); }
+            else { slots.push_back(sl); which.push_back(j1); }
         }
         j0 = j1;
-        const size_t ns = slots.size();
+        const size_t n_plain = slots.size(), n_pin = pslots.size(), ns = n_plain + n_pin;
         if (!ns) break;
+        slots.insert(slots.end(), pslots.begin(), pslots.end());
+        which.insert(which.end(), pwhich.begin(), pwhich.end());
+        for (int2 &pr : pairs) if (pr.x < 0) pr.x = (int)n_plain + (-1 - pr.x);
+        for (int2 &pr : rpairs) pr.x = (int)n_plain + (-1 - pr.x);
+        pin.assign(ns * 16, 0);
+        for (size_t k = 0; k < n_pin; k++) {
+            memcpy(pin.data() + (n_plain + k) * 8, &preq0[k], 8);
+            memcpy(pin.data() + ns * 8 + (n_plain + k) * 4, &pnreq[k], 4);
+        }
         c->scen_chunks++;
-        if ((rc = ensure(c, c->b_sc_slot, ns * sizeof(DScSlot))) || (rc = ensure(c, c->b_sc_pair, (pairs.size() + 1) * sizeof(int2))) ||
+        if ((rc = ensure(c, c->b_sc_slot, ns * sizeof(DScSlot))) || (rc = ensure(c, c->b_sc_pair, (pairs.size() + rpairs.size() + 1) * sizeof(int2))) ||
             (rc = ensure(c, c->b_sc_meta, ns * sizeof(DMeta))) || (rc = ensure(c, c->b_sc_dist, (words + 2) * 8)) || (rc = ensure(c, c->b_sc_parent, (nodes + 1) * 4)) ||
-            (rc = ensure(c, c->b_sc_path, (nodes + 1) * 4)) || (rc = ensure(c, c->b_sc_mask, (mwords + 2) * 4)) || (rc = ensure(c, c->b_sc_plan, plan + 2)) ||
+            (rc = ensure(c, c->b_sc_path, (nodes + 1) * 4)) || (rc = ensure(c, c->b_sc_mask, (mwords + 2 + rwords + 2) * 4)) || (rc = ensure(c, c->b_sc_plan, plan + 2)) ||
             (rc = ensure(c, c->b_sc_genes, (nodes + ns + 1) * sizeof(DGene))) || (rc = ensure(c, c->b_sc_rec, ns * sizeof(DReannRec))) ||
-            (rc = ensure(c, c->b_sc_tot, sizeof(DTotals))) || (rc = ensure(c, c->b_sc_gtot, 16)))
+            (rc = ensure(c, c->b_sc_tot, sizeof(DTotals))) || (rc = ensure(c, c->b_sc_gtot, 16)) || (n_pin && (rc = ensure(c, c->b_sc_pin, ns * 16))))
             return rc;
         if (!c->b_sc_tie.p && (rc = ensure(c, c->b_sc_tie, (size_t)std::max<int64_t>(c->tie_seen, 1 << 20)))) return rc;
         HIPCHK(c, hipMemcpyAsync(c->b_sc_slot.p, slots.data(), ns * sizeof(DScSlot), hipMemcpyHostToDevice, s));
         if (!pairs.empty()) HIPCHK(c, hipMemcpyAsync(c->b_sc_pair.p, pairs.data(), pairs.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+        if (!rpairs.empty()) HIPCHK(c, hipMemcpyAsync((int2 *)c->b_sc_pair.p + pairs.size(), rpairs.data(), rpairs.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+        if (n_pin) HIPCHK(c, hipMemcpyAsync(c->b_sc_pin.p, pin.data(), ns * 16, hipMemcpyHostToDevice, s));
         c->h_schunk.assign(ns, DReannRec{});
         DTotals &tot = c->h_stot;
         uint32_t &gtot = c->h_sgtot;
@@ -835,15 +861,28 @@ static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const
             q.stride0 = c->n_limbs; q.meta = (DMeta *)c->b_sc_meta.p; q.dist = (uint64_t *)c->b_sc_dist.p; q.parent = (int32_t *)c->b_sc_parent.p;
             q.path = (int32_t *)c->b_sc_path.p; q.mask = (uint32_t *)c->b_sc_mask.p; q.gplan = (uint8_t *)c->b_sc_plan.p;
             q.dist0 = (const uint64_t *)c->b_dist.p; q.rec = (DReannRec *)c->b_sc_rec.p;
+            q.req = nullptr; q.req0 = nullptr; q.nreq = nullptr; q.kreq = nullptr; q.rpair = nullptr; q.n_rpair = 0;
+            if (n_pin) {
+                q.req = q.mask + (mwords + 2); q.req0 = (const int64_t *)c->b_sc_pin.p; q.nreq = (const int32_t *)((const uint8_t *)c->b_sc_pin.p + ns * 8);
+                q.kreq = (int32_t *)((uint8_t *)c->b_sc_pin.p + ns * 12); q.rpair = q.pair + pairs.size(); q.n_rpair = (int64_t)rpairs.size();
+            }
+            DScen qa = q, qb = q; // the plain head and the pinned tail of the slot table
+            qa.n_slot = (int32_t)n_plain;
+            qb.n_slot = (int32_t)n_pin; qb.slot += n_plain; qb.meta += n_plain; qb.rec += n_plain;
+            if (n_pin) { qb.req0 += n_plain; qb.nreq += n_plain; qb.kreq += n_plain; }
             HIPCHK(c, hipEventRecord(c->aev[0], s));
             HIPCHK(c, hipMemsetAsync(c->b_sc_tot.p, 0, sizeof(DTotals), s));
             HIPCHK(c, hipMemsetAsync(c->b_sc_gtot.p, 0, 16, s));
-            HIPCHK(c, hipMemsetAsync(c->b_sc_mask.p, 0, (mwords + 2) * 4, s));
+            HIPCHK(c, hipMemsetAsync(c->b_sc_mask.p, 0, (mwords + 2 + (n_pin ? rwords + 2 : 0)) * 4, s));
+            if (n_pin) HIPCHK(c, hipMemsetAsync(q.kreq, 0, ns * 4, s)); // k_scp_mask counts again (also on a tie-scratch retry)
             phxk_scen_mask(&b, &q, s);
+            if (n_pin) phxk_scen_pin_mask(&b, &q, s);
             HIPCHK(c, hipEventRecord(c->aev[1], s));
-            phxk_scen_solve(&b, &q, nlm, s);
+            phxk_scen_solve(&b, &qa, nlm, s);
+            if (n_pin) phxk_scen_pin_solve(&b, &qb, pinm, s);
             HIPCHK(c, hipEventRecord(c->aev[2], s));
-            phxk_scen_finish(&b, &q, nlm, s);
+            phxk_scen_finish(&b, &qa, nlm, s);
+            if (n_pin) phxk_scen_pin_finish(&b, &qb, pinm, s);
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, hipMemcpyAsync(c->h_schunk.data(), c->b_sc_rec.p, ns * sizeof(DReannRec), hipMemcpyDeviceToHost, s));
             HIPCHK(c, hipEventRecord(c->aev[3], s));
@@ -876,9 +915,11 @@ static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const
     return PHX_OK;
 }
 
-int phx_scenarios_flat(phx_ctx *c, int64_t n_scen, const int32_t *scen_contig, const int64_t *scen_off, const int32_t *scen_orf, const int64_t *orf_offsets,
-                       uint32_t flags, phx_gene *genes, int64_t cap, int64_t *offsets, int32_t *status, double *delta, int64_t *total_out) {
-    (void)flags; // reserved
+// phx_scenarios_flat (no required lists: require_off, require_orf and unmet null) and phx_pinned_scenarios_flat are one solve on one set of
+// buffers; the cached result is keyed on both lists (as reann_flat serves phx_reannotate_flat and phx_constrain_flat).
+static int scen_flat(phx_ctx *c, const char *who, int64_t n_scen, const int32_t *scen_contig, const int64_t *scen_off, const int32_t *scen_orf, const int64_t *req_off_in,
+                     const int32_t *req_orf_in, const int64_t *orf_offsets, phx_gene *genes, int64_t cap, int64_t *offsets, int32_t *status, double *delta, int32_t *unmet,
+                     int64_t *total_out) {
     if (!c || n_scen < 0 || !offsets || !scen_off || (n_scen > 0 && (!status || !delta || !scen_contig)) || (c->n > 0 && !orf_offsets)) return PHX_E_ARG;
     { const int ra = after_run(c); if (ra) return ra; }
     { const int rf = fetch_meta(c); if (rf) return rf; }
@@ -890,20 +931,45 @@ int phx_scenarios_flat(phx_ctx *c, int64_t n_scen, const int32_t *scen_contig, c
         if (reann_status(c, i) >= 0) acc += c->meta[(size_t)i].n_orf;
     }
     if (c->n > 0 && orf_offsets[c->n] != acc) return PHX_E_ARG;
-    if (scen_off[0] != 0) return PHX_E_ARG;
     const size_t S = (size_t)n_scen;
-    for (size_t j = 0; j < S; j++) {
-        if (scen_off[j + 1] < scen_off[j]) return PHX_E_ARG;
-        const int32_t i = scen_contig[j];
-        if (i < 0 || i >= c->n) return PHX_E_ARG;
-        if (scen_off[j + 1] > scen_off[j] && !scen_orf) return PHX_E_ARG;
-        const int64_t cnt = orf_offsets[i + 1] - orf_offsets[i];
-        for (int64_t k = scen_off[j]; k < scen_off[j + 1]; k++) if (scen_orf[k] < 0 || (int64_t)scen_orf[k] >= cnt) return PHX_E_ARG;
+    for (int pass = 0; pass < 2; pass++) { // the refused lists, then the required ones
+        const int64_t *off = pass ? req_off_in : scen_off;
+        const int32_t *orf = pass ? req_orf_in : scen_orf;
+        if (!off) continue;
+        if (off[0] != 0) return PHX_E_ARG;
+        for (size_t j = 0; j < S; j++) {
+            if (off[j + 1] < off[j]) return PHX_E_ARG;
+            const int32_t i = scen_contig[j];
+            if (i < 0 || i >= c->n) return PHX_E_ARG;
+            if (off[j + 1] > off[j] && !orf) return PHX_E_ARG;
+            const int64_t cnt = orf_offsets[i + 1] - orf_offsets[i];
+            for (int64_t k = off[j]; k < off[j + 1]; k++) if (orf[k] < 0 || (int64_t)orf[k] >= cnt) return PHX_E_ARG;
+        }
+    }
+    // the required lists without duplicates (|R| counts ORFs), and no ORF of a scenario in both of its lists
+    std::vector<int64_t> &rq_off = c->h_srq_off;
+    std::vector<int32_t> &rq_orf = c->h_srq_orf;
+    rq_off.assign(S + 1, 0);
+    rq_orf.clear();
+    if (req_off_in) {
+        std::vector<int32_t> f;
+        for (size_t j = 0; j < S; j++) {
+            const size_t r0 = rq_orf.size();
+            rq_orf.insert(rq_orf.end(), req_orf_in + req_off_in[j], req_orf_in + req_off_in[j + 1]);
+            std::sort(rq_orf.begin() + (ptrdiff_t)r0, rq_orf.end());
+            rq_orf.erase(std::unique(rq_orf.begin() + (ptrdiff_t)r0, rq_orf.end()), rq_orf.end());
+            rq_off[j + 1] = (int64_t)rq_orf.size();
+            if (rq_orf.size() == r0 || scen_off[j + 1] == scen_off[j]) continue;
+            f.assign(scen_orf + scen_off[j], scen_orf + scen_off[j + 1]);
+            std::sort(f.begin(), f.end());
+            for (size_t k = r0; k < rq_orf.size(); k++)
+                if (std::binary_search(f.begin(), f.end(), rq_orf[k])) { c->err = std::string(who) + ": an ORF is both refused and required in one scenario"; return PHX_E_ARG; } // before any kernel
+        }
     }
     const size_t P = (size_t)scen_off[S];
     const bool same = c->done.scen && c->h_skey_contig.size() == S && c->h_skey_orf.size() == P &&
                       std::equal(scen_contig, scen_contig + S, c->h_skey_contig.begin()) && std::equal(scen_off, scen_off + S + 1, c->h_skey_off.begin()) &&
-                      std::equal(scen_orf, scen_orf + P, c->h_skey_orf.begin());
+                      std::equal(scen_orf, scen_orf + P, c->h_skey_orf.begin()) && c->h_skey_roff == rq_off && c->h_skey_rorf == rq_orf;
     if (!same) {
         c->done.scen = false;
         { const int rg = ensure_grp_host(c); if (rg) return rg; }
@@ -918,7 +984,7 @@ int phx_scenarios_flat(phx_ctx *c, int64_t n_scen, const int32_t *scen_contig, c
             if (!reann_contig(c, i)) continue; // (the run's verdict stands: a run error, no device distances, an empty graph)
             c->h_srec[j].status = SC_SLOT;
             std::vector<int32_t> &pm = perm[(size_t)i];
-            if (!pm.empty() || scen_off[j + 1] == scen_off[j]) continue;
+            if (!pm.empty() || (scen_off[j + 1] == scen_off[j] && rq_off[j + 1] == rq_off[j])) continue;
             const DMeta &m = c->meta[(size_t)i];
             pm.assign((size_t)m.n_orf, -1);
             size_t t = 0;
@@ -927,23 +993,27 @@ int phx_scenarios_flat(phx_ctx *c, int64_t n_scen, const int32_t *scen_contig, c
                 t += (size_t)(k > 0 ? k : 0);
             });
         }
-        { const int rq = scen_compute(c, n_scen, scen_contig, scen_off, scen_orf, perm); if (rq) { (void)hipStreamSynchronize(c->stream); return rq; } }
+        { const int rq = scen_compute(c, n_scen, scen_contig, scen_off, scen_orf, rq_off.data(), rq_orf.data(), perm); if (rq) { (void)hipStreamSynchronize(c->stream); return rq; } }
         c->h_skey_contig.assign(scen_contig, scen_contig + S);
         c->h_skey_off.assign(scen_off, scen_off + S + 1);
         c->h_skey_orf.assign(scen_orf, scen_orf + P);
+        c->h_skey_roff = rq_off;
+        c->h_skey_rorf = rq_orf;
         c->done.scen = true;
     }
-    // ---- the caller's layout: per scenario what phx_reannotate_flat reports for its contig ----
+    // ---- the caller's layout: per scenario what phx_reannotate_flat / phx_constrain_flat reports for its contig ----
     int64_t total = 0;
     bool run_genes = false;
     for (size_t j = 0; j < S; j++) {
         const int i = scen_contig[j];
         const int32_t st = reann_status(c, i);
         offsets[j] = total; status[j] = st; delta[j] = std::numeric_limits<double>::infinity();
+        if (unmet) unmet[j] = (int32_t)(rq_off[j + 1] - rq_off[j]); // (no result: every required ORF is unmet)
         if (st < 0) continue;
         const DReannRec &r = c->h_srec[j];
         if (r.status != SC_NOSLOT) {
             status[j] = r.status; delta[j] = r.delta;
+            if (unmet) unmet[j] = r.unmet;
             if (r.status >= 0) total += r.n_genes;
         } else { // not solved again: the run's result, as the sibling delivers it
             if (st != PHX_S_NOPATH) delta[j] = 0.0;
@@ -962,8 +1032,23 @@ int phx_scenarios_flat(phx_ctx *c, int64_t n_scen, const int32_t *scen_contig, c
         const DGene *src = r.status != SC_NOSLOT ? c->h_sgenes.data() + r.gene_off : (const DGene *)c->h_genes.p + (size_t)c->res[(size_t)scen_contig[j]].gene_off;
         memcpy(genes + offsets[j], src, sizeof(phx_gene) * (size_t)k);
     }
-    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_scenarios_flat"; return PHX_E_NOMEM; }
+    } catch (const std::bad_alloc &) { c->err = std::string("out of memory in ") + who; return PHX_E_NOMEM; }
     return PHX_OK;
+}
+
+int phx_scenarios_flat(phx_ctx *c, int64_t n_scen, const int32_t *scen_contig, const int64_t *scen_off, const int32_t *scen_orf, const int64_t *orf_offsets,
+                       uint32_t flags, phx_gene *genes, int64_t cap, int64_t *offsets, int32_t *status, double *delta, int64_t *total_out) {
+    (void)flags; // reserved
+    return scen_flat(c, "phx_scenarios_flat", n_scen, scen_contig, scen_off, scen_orf, nullptr, nullptr, orf_offsets, genes, cap, offsets, status, delta, nullptr, total_out);
+}
+
+int phx_pinned_scenarios_flat(phx_ctx *c, int64_t n_scen, const int32_t *scen_contig, const int64_t *forbid_off, const int32_t *forbid_orf, const int64_t *require_off,
+                              const int32_t *require_orf, const int64_t *orf_offsets, uint32_t flags, phx_gene *genes, int64_t cap, int64_t *offsets, int32_t *status,
+                              double *delta, int32_t *unmet, int64_t *total_out) {
+    (void)flags; // reserved
+    if (!c || !require_off || (n_scen > 0 && !unmet)) return PHX_E_ARG;
+    return scen_flat(c, "phx_pinned_scenarios_flat", n_scen, scen_contig, forbid_off, forbid_orf, require_off, require_orf, orf_offsets, genes, cap, offsets, status, delta, unmet,
+                     total_out);
 }
 
 int phx_tap_scenario_path(phx_ctx *c, int64_t scen, int32_t *path, int32_t cap, int32_t *n_path, uint64_t *dist_limbs, int32_t cap_limbs) {
@@ -984,7 +1069,8 @@ int phx_tap_scenario_path(phx_ctx *c, int64_t scen, int32_t *path, int32_t cap, 
     }
     if (dist_limbs) {
         if (cap_limbs < m.sssp_nl) return PHX_E_ARG;
-        HIPCHK(c, hipMemcpy(dist_limbs, (uint64_t *)c->b_sc_dist.p + sl.dist0 + ((size_t)m.n_node - 1) * (size_t)m.sssp_nl, (size_t)m.sssp_nl * 8, hipMemcpyDeviceToHost));
+        // (a pinned slot keeps one limb more per node: the W-sum is the low sssp_nl limbs of its distance, as phx_tap_repath reports it)
+        HIPCHK(c, hipMemcpy(dist_limbs, (uint64_t *)c->b_sc_dist.p + sl.dist0 + ((size_t)m.n_node - 1) * (size_t)(m.sssp_nl + (sl.pinned ? 1 : 0)), (size_t)m.sssp_nl * 8, hipMemcpyDeviceToHost));
     }
     return PHX_OK;
 }

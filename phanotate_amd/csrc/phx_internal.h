@@ -405,9 +405,9 @@ struct DReann {
 // (contig, refused set); the graph arrays are the run's, shared by all slots of a contig; every output is the slot's own.
 struct DScSlot {
     int32_t contig;      // contig of the batch last run
-    int32_t pad_;
+    int32_t pinned;      // 1: a slot with required ORFs (§18): NL + 1 limbs per node at dist0 and a required slice (DScen.req0); else 0
     int64_t node0;       // first entry of the slot's slices of DScen.parent / path (n_node entries each)
-    int64_t dist0;       // first 64-bit word of the slot's distances (n_node x the contig's limbs)
+    int64_t dist0;       // first 64-bit word of the slot's distances (n_node x the contig's limbs; a pinned slot: one limb more)
     int64_t mask0;       // first word of the slot's bitmap slice: in-edge slot e is bit (edge_off & 31) + e of the slice, so that the
                          //   slice shifted back by edge_off >> 5 words is indexed by edge_off + e like DReann.mask
     int64_t plan0;       // first byte of the slot's global window plan (n_node / 32 + 2 bytes)
@@ -425,6 +425,13 @@ struct DScen {
     uint8_t *gplan;
     const uint64_t *dist0; // the run's distances (D)
     DReannRec *rec;      // per slot: what the host reads
+    // pinned scenarios (§18); behind the fields above, whose places in the argument block of k_sc_* stay
+    uint32_t *req;       // the required bitmap slices of the pinned slots, cleared per chunk
+    const int64_t *req0; // per slot: first word of its required slice in req (the bit rule of mask0)
+    const int32_t *nreq; // per slot: required ORFs (|R|)
+    int32_t *kreq;       // per slot: required ORFs whose edge exists (k_scp_mask counts them): the bound of the solver's cycle guard
+    const int2 *rpair;   // the required (slot, ORF in the contig's device order) pairs of the chunk
+    int64_t n_rpair;
 };
 
 #ifdef __cplusplus
@@ -480,6 +487,9 @@ void phxk_reann_finish(const DBatch *b, const DReann *q, int nl_mask, int pin_ma
 void phxk_scen_mask(const DBatch *b, const DScen *q, void *stream);                 // scenario batches (phx_resolve.inc): the slots' records and bitmap slices (b: the run's batch),
 void phxk_scen_solve(const DBatch *b, const DScen *q, int nl_mask, void *stream);   //   the masked sweep, a workgroup per slot (b: the run's graph, tot / genes / gene_total / tie the scenarios' own),
 void phxk_scen_finish(const DBatch *b, const DScen *q, int nl_mask, void *stream);  //   in-order parents, path, genes, delta per slot
+void phxk_scen_pin_mask(const DBatch *b, const DScen *q, void *stream);                 // pinned scenarios (§18): the required slices and counts (q: the whole slot table),
+void phxk_scen_pin_solve(const DBatch *b, const DScen *q, int pin_mask, void *stream);  //   the sweep under the required policy (q: the table's pinned tail; pin_mask: its classes),
+void phxk_scen_pin_finish(const DBatch *b, const DScen *q, int pin_mask, void *stream); //   in-order parents, path, genes, delta and unmet per pinned slot
 #ifdef __cplusplus
 }
 #endif

@@ -448,6 +448,31 @@ void phxk_scen_finish(const DBatch *b, const DScen *q, int nl_mask, void *stream
     else NL_LAUNCH_T(k_sc_inorder, IO_T_FULL, nl_mask, dim3((unsigned)q->n_slot), *b, *q);
     hipLaunchKernelGGL(k_sc_fin, dim3((unsigned)((q->n_slot + 63) / 64)), dim3(64), 0, s, *b, *q);
 }
+// pinned scenarios: the solve and the finish get the pinned tail of the slot table
+void phxk_scen_pin_mask(const DBatch *b, const DScen *q, void *stream) {
+    if (q->n_slot <= 0 || q->n_rpair <= 0) return;
+    hipLaunchKernelGGL(k_scp_mask, dim3((unsigned)((q->n_rpair + NT - 1) / NT)), dim3(NT), 0, (hipStream_t)stream, *b, *q);
+}
+extern "C++" template <int NL>
+static void launch_scp_lds(const DBatch *b, const DScen *q, hipStream_t s) {
+    (void)hipFuncSetAttribute((const void *)k_scp_lds<NL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rc_lds_bytes<NL + 1>());
+    hipLaunchKernelGGL(k_scp_lds<NL>, dim3((unsigned)q->n_slot), dim3(SW_THREADS), rc_lds_bytes<NL + 1>(), s, *b, *q);
+}
+void phxk_scen_pin_solve(const DBatch *b, const DScen *q, int pin_mask, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (q->n_slot <= 0) return;
+    if (pin_mask & 1) launch_scp_lds<2>(b, q, s);
+    if (pin_mask & 2) launch_scp_lds<4>(b, q, s);
+    if (pin_mask & 4) launch_scp_lds<8>(b, q, s);
+    if (pin_mask & 8) launch_scp_lds<17>(b, q, s);
+}
+void phxk_scen_pin_finish(const DBatch *b, const DScen *q, int pin_mask, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (q->n_slot <= 0) return;
+    if (b->mean_len < 8192) NL_LAUNCH_T(k_scp_inorder, 64, pin_mask, dim3((unsigned)q->n_slot), *b, *q); // as phxk_scen_finish
+    else NL_LAUNCH_T(k_scp_inorder, IO_T_FULL, pin_mask, dim3((unsigned)q->n_slot), *b, *q);
+    hipLaunchKernelGGL(k_scp_fin, dim3((unsigned)((q->n_slot + 63) / 64)), dim3(64), 0, s, *b, *q);
+}
 // one workgroup for up to 1024 contigs; larger batches in two passes of a workgroup per 256 contigs
 void phxk_layout1(const DBatch *b, void *stream) {
     if (b->n_contig <= LAYOUT_T) { hipLaunchKernelGGL(k_layout1, dim3(1), dim3(LAYOUT_T), 0, (hipStream_t)stream, *b); return; }

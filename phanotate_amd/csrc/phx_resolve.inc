@@ -244,3 +244,86 @@ __global__ __launch_bounds__(64) void k_sc_fin(DBatch b, DScen q) {
     }
     q.rec[s] = r;
 }
+
+// ---- pinned scenario batches (DESIGN.md §18): the slots with required ORFs, solved under the REQ policy on one limb more ----
+// The host puts the pinned slots behind the plain ones in a chunk's slot table and hands these kernels the table's tail (DScen.slot, meta,
+// rec, req0, nreq, kreq moved to the first pinned slot, n_slot the pinned slots), so that blockIdx.x is a pinned slot here as it is a plain
+// one in k_sc_*, whose grids end where these begin.  The distance slice of a pinned slot holds n_node x (NL + 1) words; its refused slice
+// is set by k_sc_mask like any slot's, its required slice (DScen.req at req0, the same bit rule) by k_scp_mask.
+
+// a thread per required (slot, ORF) pair of the chunk (slot: its index in the whole table): the ORF's edge, found as k_sc_mask finds it,
+// sets its bit in the slot's required slice and counts for the slot's kreq, the k of the solver's cycle guard
+__global__ __launch_bounds__(NT) void k_scp_mask(DBatch b, DScen q) {
+    const int64_t p = (int64_t)blockIdx.x * NT + (int64_t)threadIdx.x;
+    if (p >= q.n_rpair) return;
+    const int2 pr = q.rpair[p];
+    if (pr.x < 0 || pr.x >= q.n_slot) return;
+    const DScSlot sl = q.slot[pr.x];
+    if (!sl.pinned || sl.contig < 0 || sl.contig >= b.n_contig) return;
+    const DMeta *meta = &b.meta[sl.contig];
+    const int k = pr.y;
+    if (!mg_contig(meta) || k < 0 || k >= meta->n_orf) return;
+    const DOrf o = b.orf[meta->orf_off + k];
+    const int V = meta->n_node;
+    const int sn = b.onode[meta->orf_off + k], tn = b.grp[meta->grp_off + o.grp].node;
+    const bool fwd = o.frame > 0;
+    const int u = fwd ? sn : tn, v = fwd ? tn : sn;
+    if (u < 0 || v < 0 || u >= V || v >= V) return;
+    const uint32_t *in_off = b.in_off + meta->node_off + sl.contig;
+    const uint32_t *esrc = b.esrc + meta->edge_off;
+    const uint64_t lo = (uint64_t)meta->edge_off & 31u;
+    for (uint32_t x = in_off[v], x1 = in_off[v + 1]; x < x1; x++)
+        if (!ESRC_IS_GAP(esrc[x]) && ESRC_NODE(esrc[x]) == (uint32_t)u) { // (no such edge: the ORF stays unmet)
+            const uint32_t bit = 1u << ((lo + x) & 31);
+            if (!(atomicOr(&q.req[q.req0[pr.x] + (int64_t)((lo + x) >> 5)], bit) & bit)) atomicAdd(&q.kreq[pr.x], 1); // (an ORF listed twice counts once)
+            break;
+        }
+}
+
+// the slot's required slice, shifted by sc_view's rule
+__device__ __forceinline__ const uint32_t *scp_req(const DScen &q, const DMeta *meta) { return q.req + (q.req0[blockIdx.x] - (meta->edge_off >> 5)); }
+
+template <int NL>
+__global__ __launch_bounds__(SW_THREADS, NL == 2 ? 4 : 2) void k_scp_lds(DBatch b, DScen q) { // (the bounds of k_rc_lds)
+    const uint32_t *mask;
+    uint8_t *gplan;
+    uint32_t ci;
+    DMeta *meta = sc_view(b, q, &ci, &mask, &gplan);
+    const int V = meta->n_node;
+    if (!mg_contig(meta) || meta->sssp_nl != NL) return;
+    lds_sweep<NL + 1, RcCfg<NL + 1>>(b, meta, ci, V, mask, gplan, scp_req(q, meta), q.kreq[blockIdx.x]);
+}
+
+template <int NL, int IO_T>
+__global__ __launch_bounds__(IO_T) void k_scp_inorder(DBatch b, DScen q) {
+    __shared__ IoShared<IO_T> sh;
+    const uint32_t *mask;
+    uint8_t *gplan;
+    uint32_t ci;
+    DMeta *meta = sc_view(b, q, &ci, &mask, &gplan);
+    if (meta->sssp_nl != NL) return;
+    if (threadIdx.x == 0) { sh.flag = 0; meta->tie = 0; }
+    __syncthreads();
+    if (!mg_contig(meta)) return;
+    if (meta->n_path < 2 && meta->n_path != -1) return;
+    inorder_contig<NL + 1, IO_T, true, true>(b, meta, ci, &sh, mask, scp_req(q, meta));
+}
+
+// a thread per pinned slot: the record the host reads (k_rs_fin's pinned part, per slot)
+__global__ __launch_bounds__(64) void k_scp_fin(DBatch b, DScen q) {
+    const int s = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (s >= q.n_slot) return;
+    const DMeta *meta = &q.meta[s];
+    DReannRec r;
+    r.status = meta->status; r.n_genes = 0; r.gene_off = 0; r.n_path = 0; r.tie = meta->tie; r.delta = __builtin_inf();
+    r.unmet = q.nreq[s]; r.pad_ = 0;
+    if (meta->status >= 0 && meta->status != PHX_S_NOPATH && meta->n_path >= 2) {
+        const int V = meta->n_node, nl = meta->sssp_nl;
+        const uint64_t *df = q.dist + q.slot[s].dist0 + (size_t)(V - 1) * (nl + 1); // the W-sum is the low nl limbs
+        const uint64_t *d0 = q.dist0 + (size_t)meta->node_off * q.stride0 + (size_t)(V - 1) * nl;
+        r.delta = nl == 2 ? rs_delta<2>(df, d0) : nl == 4 ? rs_delta<4>(df, d0) : nl == 8 ? rs_delta<8>(df, d0) : rs_delta<17>(df, d0);
+        r.unmet -= (int32_t)(nl == 2 ? rc_count<2>(df) : nl == 4 ? rc_count<4>(df) : nl == 8 ? rc_count<8>(df) : rc_count<17>(df));
+        r.n_genes = meta->n_genes; r.gene_off = meta->gene_off; r.n_path = meta->n_path;
+    }
+    q.rec[s] = r;
+}
