@@ -40,6 +40,7 @@ extern "C" {
  *        phx_replacement_stats, phx_format_replacements;
  *        (additions, version unchanged) phx_reannotate_flat, phx_orf_offsets, phx_tap_repath, phx_reannotate_ms;
  *        (addition, version unchanged: the suite pins 410) phx_constrain_flat — probe for the symbol, not for a version;
+ *        (addition, version unchanged) phx_evidence_flat — likewise;
  *        (additions, version unchanged) phx_scenarios_flat, phx_scenarios_ms, phx_scenario_chunks, phx_tap_scenario_path — probe for the symbol;
  *        (addition, version unchanged) phx_pinned_scenarios_flat — probe for the symbol */
 #define PHX_MAX_CODONS 16
@@ -435,6 +436,21 @@ int phx_reannotate_flat(phx_ctx *ctx, const uint8_t *forbid, const int64_t *orf_
  * last solve of either kind, and the distance phx_tap_repath reports is the W-sum W(P). */
 int phx_constrain_flat(phx_ctx *ctx, const uint8_t *forbid, const uint8_t *require, const int64_t *orf_offsets /* [n+1] */, uint32_t flags, phx_gene *genes,
                        int64_t cap, int64_t *offsets /* [n+1] */, int32_t *status /* [n] */, double *delta /* [n] */, int32_t *unmet /* [n] */, int64_t *total);
+/* ---- evidence-weighted re-annotation: a bonus or a penalty per ORF ----
+ * phx_reannotate_flat with soft evidence beside the refused set: B(k), a signed integer in the solver's units (1/1000 of a SCORE unit; 0: no
+ * evidence, negative: support, positive: doubt), is added to the weight of ORF k's edge.  G_{F,B} is G_F with those weights, D_B its
+ * shortest source -> target distance in the contig's own limb class, the path the in-order rule of §14 on the new integers, delta =
+ * float(D_B - D) / 1000.0, which may be negative.  With every B zero it is phx_reannotate_flat byte for byte (the same kernels).
+ *   bias         one int64 per ORF of the batch, laid out as `forbid`; NULL: all zero.  |B| > 2^52: PHX_E_ARG before any kernel
+ *   forbid       as above; may be NULL (empty).  A refused ORF's bias is ignored
+ *   flags, genes, orf_offsets and the state rules as phx_reannotate_flat
+ * status[i] as there; PHX_S_NEGCYCLE (no genes, delta +inf) now also when bonuses make a cycle that the source reaches negative — no path is
+ * best then, and the reference's in-place Bellman-Ford does not settle either; PHX_S_OVERFLOW (no genes, delta +inf) also when the layout's
+ * bound plus the sum of |B| over the contig's biased edges no longer fits the contig's limb class (there is no promotion to a wider one).
+ * The three calls share their buffers and their cached result (keyed on the sets, the bias and the flags); phx_tap_repath, whose distance
+ * is then D_B, and phx_reannotate_ms serve the last solve of any kind.  (Addition, version unchanged: probe for the symbol.) */
+int phx_evidence_flat(phx_ctx *ctx, const int64_t *bias, const uint8_t *forbid, const int64_t *orf_offsets /* [n+1] */, uint32_t flags, phx_gene *genes, int64_t cap,
+                      int64_t *offsets /* [n+1] */, int32_t *status /* [n] */, double *delta /* [n] */, int64_t *total);
 /* orf_offsets[n+1] of the batch last run as phx_reannotate_flat expects them: cumulative ORF counts, a contig with a run error or without
  * device distances counting none (the offsets phx_margins_flat reports, without computing the margins or the certificate). */
 int phx_orf_offsets(phx_ctx *ctx, int64_t *orf_offsets /* [n+1] */);

@@ -528,6 +528,45 @@ class Annotator:
         self._chk(self.L.phx_constrain_flat(self.h, vp(fmask), vp(rmask), vp(oo), fl, vp(genes), len(genes), vp(offs), vp(status), vp(delta), vp(unmet), C.byref(total)), "phx_constrain_flat")
         return status[:n], offs, genes[: int(total.value)], delta[:n], unmet[:n]
 
+    def evidence(self, bias, forbid=None, solve_all=False):
+        """(status int32[n], offsets int64[n+1], genes structured array[total], delta float64[n]), as reannotate() returns them: the batch
+        last run annotated again with a bonus or a penalty on chosen ORFs (phx_evidence_flat).  `bias` holds, per contig,
+        None or a dict or sequence of (index into orfs(i), b) pairs, b a float in SCORE units: negative is support, positive is doubt.  The
+        solver adds B = math.trunc(b * 1000.0) to the ORF's edge (its units are 1/1000 of a SCORE unit, so what b holds beyond three
+        decimals is cut off, towards zero); an ORF listed twice gets the sum of its B.  `forbid` is reannotate()'s.  delta[i] =
+        float(D_B - D) / 1000 may be negative.  Bonuses that make a cycle negative give status -9 without genes.  A non-finite b or
+        |B| > 2^52 raises ValueError.  With no bias at all it is reannotate(forbid)."""
+        import math
+
+        n = self.n
+        if len(bias) != n:
+            raise ValueError("one dict or sequence of (ORF index, bias) pairs (or None) per contig of the batch")
+        oo = self.orf_offsets()
+        fmask = self._orf_mask([None] * n if forbid is None else forbid)
+        B = np.zeros(max(int(oo[n]), 1), np.int64)
+        for i, pairs in enumerate(bias):
+            if pairs is None:
+                continue
+            for k, b in (pairs.items() if hasattr(pairs, "items") else pairs):
+                k, b = int(k), float(b)
+                if not 0 <= k < oo[i + 1] - oo[i]:
+                    raise IndexError("contig %d has %d ORFs" % (i, oo[i + 1] - oo[i]))
+                if not math.isfinite(b) or abs(b) * 1000.0 >= 2.0 ** 60:
+                    raise ValueError("contig %d, ORF %d: the bias %r is not a finite number of SCORE units within 2^52 / 1000" % (i, k, b))
+                B[oo[i] + k] += math.trunc(b * 1000.0)
+        if np.abs(B).max() > 1 << 52:
+            raise ValueError("a bias beyond 2^52 / 1000 SCORE units")
+        offs = np.zeros(n + 1, np.int64)
+        status = np.zeros(max(n, 1), np.int32)
+        delta = np.zeros(max(n, 1), np.float64)
+        total = C.c_int64(0)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        fl = 1 if solve_all else 0
+        self._chk(self.L.phx_evidence_flat(self.h, vp(B), vp(fmask), vp(oo), fl, None, 0, vp(offs), vp(status), vp(delta), C.byref(total)), "phx_evidence_flat")
+        genes = np.empty(max(int(total.value), 1), _lib.GENE_DT)
+        self._chk(self.L.phx_evidence_flat(self.h, vp(B), vp(fmask), vp(oo), fl, vp(genes), len(genes), vp(offs), vp(status), vp(delta), C.byref(total)), "phx_evidence_flat")
+        return status[:n], offs, genes[: int(total.value)], delta[:n]
+
     # ---- scenario batches (DESIGN.md §17) ----
     @staticmethod
     def _scenario_arrays(scen, n, oo):
@@ -721,8 +760,8 @@ class Annotator:
         return st, offs, rec, soffs, genes
 
     def reannotated_path(self, i):
-        """(path as device node ids, its length as a python int) of contig i in the last re-annotation or constrain(), like path(i): D_F, or
-        the W-sum W(P) after constrain()."""
+        """(path as device node ids, its length as a python int) of contig i in the last re-annotation, constrain() or evidence(), like
+        path(i): D_F, the W-sum W(P) after constrain(), D_B after evidence()."""
         g = self.globals(i)
         p = np.zeros(max(g.n_node, 1), np.int32)
         n = C.c_int32()

@@ -47,7 +47,8 @@ def get_args(argv=None):
     p.add_argument("--alt-starts", metavar="FILE", default=None, help="also write, for every called gene and every other start of its stop, the cost of the best annotation that takes that start instead (DESIGN.md §18) to FILE")
     p.add_argument("--forbid", metavar="FILE", default=None, help="ORFs to refuse in a second annotation (DESIGN.md §14): lines whose first four columns are START STOP FRAME CONTIG as the tabular output prints a gene; needs --reannotation")
     p.add_argument("--require", metavar="FILE", default=None, help="ORFs to keep in a second annotation (DESIGN.md §16), in the format of --forbid; alone or with --forbid; needs --reannotation, which then carries a #unmet: line per contig")
-    p.add_argument("--reannotation", metavar="OUT", default=None, help="write the annotation without the ORFs of --forbid (and keeping those of --require) to OUT: the tabular block of every contig with a #delta: header line")
+    p.add_argument("--evidence", metavar="FILE", default=None, help="per-ORF bonuses and penalties for a second annotation (DESIGN.md §19), in the format of --forbid with a fifth column BIAS: a finite number of SCORE units added to the ORF's weight (negative: support; an ORF named twice gets the sum); alone or with --forbid, not with --require; needs --reannotation, whose #delta: may then be negative")
+    p.add_argument("--reannotation", metavar="OUT", default=None, help="write the annotation without the ORFs of --forbid (keeping those of --require, or under the biases of --evidence) to OUT: the tabular block of every contig with a #delta: header line")
     p.add_argument("--single-device-ranks", action="store_true", help=argparse.SUPPRESS)  # tests: every rank of a sharded launch on GPU `--device` (gloo-only group)
     args = p.parse_args(argv)
     if args.margins is not None and args.dump:
@@ -74,12 +75,18 @@ def get_args(argv=None):
         p.error("argument --alt-starts: not available under a multi-rank launch")
     if args.alt_starts is not None and int(args.gpus) > 1:  # the scenarios work on the batch resident on one context
         p.error("argument --alt-starts: not available with --gpus above 1")
-    for flag, val in (("--forbid", args.forbid), ("--require", args.require), ("--reannotation", args.reannotation)):
+    for flag, val in (("--forbid", args.forbid), ("--require", args.require), ("--evidence", args.evidence), ("--reannotation", args.reannotation)):
         if val is not None and args.dump:
             p.error("argument %s: not allowed with argument -d/--dump" % flag)
         if val is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
             p.error("argument %s: not available under a multi-rank launch" % flag)
-    if args.require is None and (args.forbid is None) != (args.reannotation is None):
+    if args.evidence is not None and args.require is not None:  # (required sets and biases in one solve: DESIGN.md §19, Limits)
+        p.error("argument --evidence: not allowed with argument --require")
+    if args.evidence is not None and args.reannotation is None:
+        p.error("argument --evidence: needs --reannotation")
+    if args.evidence is not None and int(args.gpus) > 1:
+        p.error("argument --evidence: not available with --gpus above 1")
+    if args.require is None and args.evidence is None and (args.forbid is None) != (args.reannotation is None):
         p.error("arguments --forbid and --reannotation: each needs the other")
     if args.require is not None and args.reannotation is None:
         p.error("argument --require: needs --reannotation")
@@ -130,6 +137,44 @@ def resolve_forbid(entries, names, lookup, flag="--forbid"):
         if out[i] is None:
             out[i] = []
         out[i].append(k)
+    return out
+
+
+def parse_evidence(lines, flag="--evidence"):
+    """--evidence FILE: parse_forbid's entries with a sixth member, the BIAS of the line's fifth column: a finite float in SCORE units
+    (negative: support).  A line without one, or with one that is no finite number, raises ForbidError quoting the line."""
+    import math
+
+    out = []
+    for entry in parse_forbid(lines, flag):
+        line = entry[4]
+        col = line.split("\t") if "\t" in line else line.split()
+        try:
+            b = float(col[4])
+            if not math.isfinite(b):
+                raise ValueError
+        except (IndexError, ValueError):
+            raise ForbidError("%s: no finite BIAS in the fifth column: %r" % (flag, line)) from None
+        out.append(entry + (b,))
+    return out
+
+
+def resolve_evidence(entries, names, lookup, flag="--evidence"):
+    """Per contig of `names` the (ORF index, BIAS) pairs the entries of parse_evidence name (None: none), as Annotator.evidence takes them:
+    an ORF named twice appears twice and gets the sum there.  Errors as resolve_forbid."""
+    where = {}
+    for i, nm in enumerate(names):
+        where.setdefault(nm, i)
+    out = [None] * len(names)
+    for left, right, strand, contig, line, b in entries:
+        try:
+            i = where[contig]
+            k = lookup(i, left, right, strand)
+        except KeyError:
+            raise ForbidError("%s: no such ORF in its contig: %r" % (flag, line)) from None
+        if out[i] is None:
+            out[i] = []
+        out[i].append((k, b))
     return out
 
 
@@ -403,8 +448,11 @@ def main(argv=None):
     start_parts = []  # --start-drops: (status, offsets, records) of every batch, in order
     alt_parts = []  # --alt-starts: the same of Annotator.alt_starts()
     reann_parts = []  # --reannotation: (status, offsets, genes, delta[, unmet]) of every batch, in order
-    forbid_entries = require_entries = None
+    forbid_entries = require_entries = evidence_entries = None
     try:
+        if args.evidence is not None:
+            with open(args.evidence) as fh:
+                evidence_entries = parse_evidence(fh)
         if args.forbid is not None:
             with open(args.forbid) as fh:
                 forbid_entries = parse_forbid(fh)
@@ -435,7 +483,7 @@ def main(argv=None):
             if lo >= len(idx):
                 break
         t_parts["batches"] = len(cuts)
-        if forbid_entries is not None or require_entries is not None or args.start_drops is not None or args.alt_starts is not None:  # the re-annotation and the scenarios work on the batch resident on one context: the batches one after the other
+        if forbid_entries is not None or require_entries is not None or evidence_entries is not None or args.start_drops is not None or args.alt_starts is not None:  # the re-annotation and the scenarios work on the batch resident on one context: the batches one after the other
             parts = []
             for lo, hi in cuts:
                 t0 = time.perf_counter()
@@ -459,7 +507,9 @@ def main(argv=None):
                 names = [fa.names[int(i)] for i in idx[lo:hi]]
                 here = set(names)
                 refused = resolve_forbid([e for e in forbid_entries or [] if e[3] in here], names, ann.orf_index)
-                if forbid_entries is None and require_entries is None:
+                if evidence_entries is not None:
+                    reann_parts.append(ann.evidence(resolve_evidence([e for e in evidence_entries if e[3] in here], names, ann.orf_index), refused))
+                elif forbid_entries is None and require_entries is None:
                     pass
                 elif require_entries is None:
                     reann_parts.append(ann.reannotate(refused))
@@ -514,7 +564,7 @@ def main(argv=None):
         return st, np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), genes
 
     known = set(fa.names)
-    for flag, entries in (("--forbid", forbid_entries), ("--require", require_entries)):
+    for flag, entries in (("--forbid", forbid_entries), ("--require", require_entries), ("--evidence", evidence_entries)):
         for e in entries or []:
             if e[3] not in known:
                 drop_context()

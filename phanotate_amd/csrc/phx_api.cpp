@@ -264,13 +264,17 @@ struct phx_ctx {
     int64_t repl_stats[5] = {0, 0, 0, 0, 0};
     // masked re-annotation (phx_reannotate_flat): buffers allocated at the first call, the result kept until the next upload or run
     DevBuf b_qmeta, b_qtot, b_qdist, b_qparent, b_qpath, b_qgenes, b_qgtot, b_qtie, b_qmask, b_qforb, b_qsel, b_qplan, b_qrec;
+    DevBuf b_qbias, b_qbval, b_qbsum; // evidence-weighted re-annotation (phx_evidence_flat): B per ORF, B per in-edge slot, the sums of |B| per contig; allocated at its first call
+    std::vector<int64_t> h_qbias;     // the bias last solved with, tap order (empty: none, the key of the two calls without one)
+    std::vector<int64_t> h_qbcur;     // ... of the call at hand
+    std::vector<int64_t> h_qdbias;    // the bias in device ORF order (a member: see h_qdforb)
     std::vector<uint8_t> h_qforb;     // the sets last solved, tap order (one byte per ORF of the batch: 1 = refused, 2 = required)
     std::vector<uint8_t> h_qcode;     // ... of the call at hand
     std::vector<int32_t> h_qnreq;     // per contig: required ORFs (|R|)
-    std::vector<int32_t> h_qdsel;     // the per-contig arrays the kernels read (DReann.sel / pin / nreq / kreq)
+    std::vector<int32_t> h_qdsel;     // the per-contig arrays the kernels read (DReann.sel / pin / nreq / kreq / evs)
     int qstride = 2;                  // limbs per node of b_qdist: the run's, one more when a contig was solved under the required policy
     uint32_t h_qflags = 0;
-    std::vector<int32_t> h_qsel;      // per contig: solved again (1; 2: under the required policy), else the run's result stands
+    std::vector<int32_t> h_qsel;      // per contig: solved again (1; 2: under the required policy; 3: under the bias policy), else the run's result stands
     std::vector<DReannRec> h_qrec;    // per contig that was solved again
     std::vector<DGene> h_qgenes;      // the re-annotation's gene buffer as the device left it (records at h_qrec[i].gene_off)
     std::vector<uint8_t> h_qdforb;    // the mask in device ORF order, and the totals read back: members, so that a copy enqueued before

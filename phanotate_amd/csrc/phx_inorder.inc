@@ -186,13 +186,16 @@ __device__ void walk_path(const DBatch &b, DMeta *meta, IoShared<IO_T> *sh) {
 // whatever the distances say.  The run's instantiations (MASKED = false) do not look at `mask`.
 // REQ (the pinned re-annotation, DESIGN.md §16; with MASKED, on one limb more than the contig's class): an edge whose bit is set in `req` weighs
 // W - 2^(64 (NL - 1)), as in the sweep that made the distances (lds_sweep under RcCfg).
+// BIAS (the evidence-weighted re-annotation, DESIGN.md §19; with MASKED): an edge whose bit is set in `bbit` weighs W + B, B the word of its
+// in-edge slot in `bval`, as in the sweep that made the distances (lds_sweep under EvCfg): a row is tight iff d[u] + W + B == d[v].
 // ci: the contig's index in the batch (blockIdx.x where a workgroup is a contig; a scenario slot passes its slot's contig).
-template <int NL, int IO_T, bool MASKED = false, bool REQ = false>
-__device__ void inorder_contig(const DBatch &b, DMeta *meta, const uint32_t ci, IoShared<IO_T> *sh, const uint32_t *mask = nullptr, const uint32_t *req = nullptr) {
+template <int NL, int IO_T, bool MASKED = false, bool REQ = false, bool BIAS = false>
+__device__ void inorder_contig(const DBatch &b, DMeta *meta, const uint32_t ci, IoShared<IO_T> *sh, const uint32_t *mask = nullptr, const uint32_t *req = nullptr, const uint32_t *bbit = nullptr, const long long *bval = nullptr) {
     const int tid = threadIdx.x;
     const uint64_t mbase = MASKED ? (uint64_t)meta->edge_off : 0ull;
     auto refused = [&](uint32_t e) -> bool { const uint64_t x = mbase + e; return ((mask[x >> 5] >> (x & 31)) & 1u) != 0; };
     auto required = [&](uint32_t e) -> bool { const uint64_t x = mbase + e; return ((req[x >> 5] >> (x & 31)) & 1u) != 0; };
+    auto biased = [&](uint32_t e) -> bool { const uint64_t x = mbase + e; return ((bbit[x >> 5] >> (x & 31)) & 1u) != 0; };
     const int V = meta->n_node;
     const bool walked = meta->n_path >= 2; // else the solver's parents run in a circle (a zero-length cycle of tight edges): start from source and target alone
     const int n = walked ? meta->n_path : 2; // path[0] = source ... path[n-1] = target
@@ -214,6 +217,7 @@ __device__ void inorder_contig(const DBatch &b, DMeta *meta, const uint32_t ci, 
         const WInt<NL> du = wi_load<NL>(dist + (size_t)ESRC_NODE(sw) * NL);
         WInt<NL> w = ewl ? wi_load<NL>(ewl + (size_t)e * NL) : ew_decode<NL>(edge_wenc(sw, ew, e, gt));
         if constexpr (REQ) { if (required(e)) w.v[NL - 1] -= 1ull; }
+        if constexpr (BIAS) { if (biased(e)) w = wi_add<NL>(w, ew_decode<NL>(bval[mbase + e])); }
         return !wi_unreached<NL>(du) && wi_eq<NL>(wi_add<NL>(du, w), dv);
     };
     // ---- 1. does any node of the path have a tight in-edge besides its parent edge? ----
@@ -256,6 +260,7 @@ __device__ void inorder_contig(const DBatch &b, DMeta *meta, const uint32_t ci, 
                 u[q] = ESRC_NODE(sw);
                 w[q] = ewl ? wi_load<NL>(ewl + (size_t)ee * NL) : ew_decode<NL>(edge_wenc(sw, ew, ee, gt));
                 if constexpr (REQ) { if (required(ee)) w[q].v[NL - 1] -= 1ull; }
+                if constexpr (BIAS) { if (biased(ee)) w[q] = wi_add<NL>(w[q], ew_decode<NL>(bval[mbase + ee])); }
             }
 #pragma unroll
             for (int q = 0; q < 4; q++) {

@@ -399,6 +399,12 @@ struct DReann {
     const int32_t *nreq;   // per contig: required ORFs (|R|)
     int32_t *kreq;         // per contig: required ORFs whose edge exists (k_rs_mask counts them): the bound of the solver's cycle guard
     int32_t stride0;       // limbs per node of dist0 (the run's DBatch.dist_stride; the re-annotation's own may be one wider)
+    // the evidence-weighted re-annotation (§19); behind the fields above, whose places in the kernels' argument block stay
+    const int32_t *evs;    // per contig: 1 = solve it again under the bias policy, in its own limb class (never with sel or pin)
+    const long long *bias; // per ORF (at orf_off, device order): B in 1/1000 SCORE units, 0 = no evidence
+    uint32_t *bbit;        // as `mask`: the in-edge slots that carry a bias (only touched when a contig has some)
+    long long *bval;       // per in-edge slot of the batch (at edge_off + e): B; never cleared, read only where the slot's bit is set
+    unsigned long long *bsum; // per contig [2]: the sums of |B| & 0xffffffff and of |B| >> 32 over its biased edges, zeroed per call
 };
 
 // Scenario batches (phx_resolve.inc): S masked re-annotations side by side, one workgroup per scenario slot.  A slot is one
@@ -484,6 +490,9 @@ void phxk_repl_walk(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl
 void phxk_reann_mask(const DBatch *b, const DReann *q, void *stream);                 // masked re-annotation (phx_resolve.inc): the refused ORFs' in-edge bits,
 void phxk_reann_solve(const DBatch *b, const DReann *q, int nl_mask, int pin_mask, void *stream);   //   the masked sweep (b: the re-annotation's view of the batch; pin_mask: the classes with required ORFs),
 void phxk_reann_finish(const DBatch *b, const DReann *q, int nl_mask, int pin_mask, void *stream);  //   in-order parents on G_F, path, genes, delta
+void phxk_evid_mask(const DBatch *b, const DReann *q, void *stream);                // evidence-weighted re-annotation (§19): the biased ORFs' words, bits and sums,
+void phxk_evid_solve(const DBatch *b, const DReann *q, int ev_mask, void *stream);  //   the sweep under the bias policy (ev_mask: the classes with biased ORFs),
+void phxk_evid_finish(const DBatch *b, const DReann *q, int ev_mask, void *stream); //   in-order parents on G_{F,B}, path, genes, delta
 void phxk_scen_mask(const DBatch *b, const DScen *q, void *stream);                 // scenario batches (phx_resolve.inc): the slots' records and bitmap slices (b: the run's batch),
 void phxk_scen_solve(const DBatch *b, const DScen *q, int nl_mask, void *stream);   //   the masked sweep, a workgroup per slot (b: the run's graph, tot / genes / gene_total / tie the scenarios' own),
 void phxk_scen_finish(const DBatch *b, const DScen *q, int nl_mask, void *stream);  //   in-order parents, path, genes, delta per slot

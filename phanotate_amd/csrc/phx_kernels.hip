@@ -421,6 +421,21 @@ void phxk_reann_finish(const DBatch *b, const DReann *q, int nl_mask, int pin_ma
     else NL_LAUNCH_T(k_rc_inorder, IO_T_FULL, pin_mask, dim3(b->n_contig), *b, *q);
     hipLaunchKernelGGL(k_rs_fin, dim3((unsigned)((b->n_contig + 63) / 64)), dim3(64), 0, s, *b, *q);
 }
+// evidence-weighted re-annotation: the contigs of DReann.evs, beside the two above on the same view of the batch
+void phxk_evid_mask(const DBatch *b, const DReann *q, void *stream) { hipLaunchKernelGGL(k_ev_mask, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), 0, (hipStream_t)stream, *b, *q); }
+void phxk_evid_solve(const DBatch *b, const DReann *q, int ev_mask, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (ev_mask & 1) launch_lds(k_ev_lds<2>, rs_lds_bytes<2>(), b, s, *b, *q);
+    if (ev_mask & 2) launch_lds(k_ev_lds<4>, rs_lds_bytes<4>(), b, s, *b, *q);
+    if (ev_mask & 4) launch_lds(k_ev_lds<8>, rs_lds_bytes<8>(), b, s, *b, *q);
+    if (ev_mask & 8) launch_lds(k_ev_lds<17>, rs_lds_bytes<17>(), b, s, *b, *q);
+}
+void phxk_evid_finish(const DBatch *b, const DReann *q, int ev_mask, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (b->mean_len < 8192) NL_LAUNCH_T(k_ev_inorder, 64, ev_mask, dim3(b->n_contig), *b, *q); // as phxk_reann_finish
+    else NL_LAUNCH_T(k_ev_inorder, IO_T_FULL, ev_mask, dim3(b->n_contig), *b, *q);
+    hipLaunchKernelGGL(k_ev_fin, dim3((unsigned)((b->n_contig + 63) / 64)), dim3(64), 0, s, *b, *q);
+}
 // scenario batches: the grids are the chunk's slots (pairs for k_sc_mask), not the batch's contigs
 void phxk_scen_mask(const DBatch *b, const DScen *q, void *stream) {
     hipStream_t s = (hipStream_t)stream;

@@ -131,6 +131,27 @@ __global__ __launch_bounds__(LMB_T) void k_layout1_b(DBatch b) { b_layout1_b(b, 
 
 
 
+// Bits the path sums of one contig need.  A tentative distance is the length of a walk that uses every ORF edge at most once (a shortest
+// path is simple; longer walks never win), so |dist| <= B = sum |w_orf| + (V/2) * max |w_connector| + extra.  The connector bound follows
+// functions.py:26-46: overlap < 500 bp, gap <= 300 bp or bridge pow(.)+length; terminals are smaller still.  A candidate d(u)+w needs one
+// more bit, the sign another, the "unreached" pattern sits two bits higher; one bit covers the rounding of the fp64 sum.
+// extra: 0 for the layout; the evidence-weighted re-annotation (phx_resolve.inc, DESIGN.md §19) passes the sum of |B| over the contig's
+// biased edges — each is used at most once as well.
+__device__ __forceinline__ int contig_sum_bits(const DBatch &b, const DMeta *m, double extra) {
+    if (m->maxexp >= 2000) return 4096;
+    const double pst = contig_pstop(m->gc, m->L);
+    double cmax = 1.0 / pow(1.0 - pst, 500.0);
+    const double c2 = 1.0 / pow(1.0 - pst, 100.0);
+    cmax = (cmax > c2 ? cmax : c2) + 20.0;
+    const double c3 = (double)m->L + 21.0;
+    cmax = (cmax > c3 ? cmax : c3) * 1000.0;
+    double bound = m->wsum + 20000.0 * (double)(b.tnode ? m->n_tedge : 0) + 0.5 * (double)(m->n_node > 2 ? m->n_node : 2) * cmax;
+    if (extra > 0.0) bound += extra;
+    int eb = 0;
+    (void)frexp(bound, &eb);
+    return (eb > m->maxexp ? eb : m->maxexp) + 5;
+}
+
 // integer class and solver of one contig (accumulators of the workgroup: widest class, kernel mask, largest node count, LDS needs);
 // returns its edge count
 __device__ __forceinline__ int64_t layout2_contig(const DBatch &b, DMeta *m, bool force_global, bool no_wave, int *s_nl, int *s_mask, int *s_vmax, unsigned long long *s_lds) {
@@ -139,24 +160,7 @@ __device__ __forceinline__ int64_t layout2_contig(const DBatch &b, DMeta *m, boo
         if (m->status < 0) m->n_edge = 0;
         else {
             ne = m->n_edge;
-            // A tentative distance is the length of a walk that uses every ORF edge at most once (a shortest path is
-            // simple; longer walks never win), so |dist| <= B = sum |w_orf| + (V/2) * max |w_connector|.  The connector
-            // bound follows functions.py:26-46: overlap < 500 bp, gap <= 300 bp or bridge pow(.)+length; terminals are
-            // smaller still.  A candidate d(u)+w needs one more bit, the sign another, the "unreached" pattern sits two
-            // bits higher; one bit covers the rounding of the fp64 sum.
-            int bits = 4096;
-            if (m->maxexp < 2000) {
-                const double pst = contig_pstop(m->gc, m->L);
-                double cmax = 1.0 / pow(1.0 - pst, 500.0);
-                const double c2 = 1.0 / pow(1.0 - pst, 100.0);
-                cmax = (cmax > c2 ? cmax : c2) + 20.0;
-                const double c3 = (double)m->L + 21.0;
-                cmax = (cmax > c3 ? cmax : c3) * 1000.0;
-                const double bound = m->wsum + 20000.0 * (double)(b.tnode ? m->n_tedge : 0) + 0.5 * (double)(m->n_node > 2 ? m->n_node : 2) * cmax;
-                int eb = 0;
-                (void)frexp(bound, &eb);
-                bits = (eb > m->maxexp ? eb : m->maxexp) + 5;
-            }
+            const int bits = contig_sum_bits(b, m, 0.0);
             if (bits > 17 * 64) {
                 // beyond the widest integer kernel (an ORF weight beyond ~1e300: fp64 itself gives up): no device kernel solves this contig.
                 // Its graph is still built — nodes, edge rows, flags —, k_results reports PHX_S_OVERFLOW, and phx_download* solve it on

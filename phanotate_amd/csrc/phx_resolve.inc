@@ -15,14 +15,17 @@
 // The pinned re-annotation (§16: keep a chosen set of ORFs) is the same chain for the contigs that have required ORFs: k_rs_mask sets their
 // edges' bits in a second bitmap and counts them, k_rc_lds / k_rc_inorder run the sweep and the parent rule under the REQ policy on one limb
 // more, k_rs_fin splits the target's distance into the count of required edges and the W-sum.
+// The evidence-weighted re-annotation (§19: a signed integer B per ORF added to its edge) is the chain a third time, for the contigs that
+// have biased ORFs: k_ev_mask writes B to the edge's slot and sets its bit in a third bitmap, k_ev_lds / k_ev_inorder run the sweep and the
+// parent rule under the BIAS policy in the contig's own class, k_ev_fin writes the record.
 // The bitmap only ever holds bits of explicit rows: an ORF edge runs open -> close and a coded gap edge (a connector) close -> open, so no
 // ORF shares both ends with a coded row, and k_rs_mask skips coded rows besides.  k_rs_lds therefore tests explicit rows only, and the
 // masked inorder_contig, which tests every row, sees the same graph.
 // Bounds: the sweep and round caps of k_sssp_lds (PHX_S_NEGCYCLE), no waiting between workgroups, no index from the caller on the device
 // (the host checks the offsets; `forb` is one byte per ORF of the batch, `sel` one int per contig).
 
-template <int NL> struct RsCfg { static constexpr int RING = 1024, ECAP = 1024; static constexpr bool MASKED = true, REQ = false; };
-template <> struct RsCfg<17> { static constexpr int RING = 256, ECAP = 512; static constexpr bool MASKED = true, REQ = false; }; // 1088 bits: 109 KB of LDS instead of 283
+template <int NL> struct RsCfg { static constexpr int RING = 1024, ECAP = 1024; static constexpr bool MASKED = true, REQ = false, BIAS = false; };
+template <> struct RsCfg<17> { static constexpr int RING = 256, ECAP = 512; static constexpr bool MASKED = true, REQ = false, BIAS = false; }; // 1088 bits: 109 KB of LDS instead of 283
 template <int NL>
 __host__ __device__ constexpr size_t rs_lds_bytes() { return (size_t)(RsCfg<NL>::RING + 1) * NL * 8 + (size_t)RsCfg<NL>::ECAP * ((size_t)NL * 8 + 4) + RS_PLAN_LDS + 64; }
 
@@ -81,9 +84,9 @@ __global__ __launch_bounds__(IO_T) void k_rs_inorder(DBatch b, DReann q) {
 // minus the count of required edges on its path (less one while the W-sum below is negative: rq_count) and the low NL limbs are the W-sum
 // in the contig's own class, which obeys the layout's bound as before.  Counts are <= V < 2^30, far from the unreached pattern's 2^62.
 // The ring of the 320-bit solve is halved (66 KB of LDS, two workgroups per CU, where 1024 entries would leave one).
-template <int NL1> struct RcCfg { static constexpr int RING = 1024, ECAP = 1024; static constexpr bool MASKED = true, REQ = true; };
-template <> struct RcCfg<5> { static constexpr int RING = 512, ECAP = 1024; static constexpr bool MASKED = true, REQ = true; };
-template <> struct RcCfg<18> { static constexpr int RING = 256, ECAP = 512; static constexpr bool MASKED = true, REQ = true; };
+template <int NL1> struct RcCfg { static constexpr int RING = 1024, ECAP = 1024; static constexpr bool MASKED = true, REQ = true, BIAS = false; };
+template <> struct RcCfg<5> { static constexpr int RING = 512, ECAP = 1024; static constexpr bool MASKED = true, REQ = true, BIAS = false; };
+template <> struct RcCfg<18> { static constexpr int RING = 256, ECAP = 512; static constexpr bool MASKED = true, REQ = true, BIAS = false; };
 template <int NL1>
 __host__ __device__ constexpr size_t rc_lds_bytes() { return (size_t)(RcCfg<NL1>::RING + 1) * NL1 * 8 + (size_t)RcCfg<NL1>::ECAP * ((size_t)NL1 * 8 + 4) + RS_PLAN_LDS + 64; }
 
@@ -134,6 +137,100 @@ __global__ __launch_bounds__(64) void k_rs_fin(DBatch b, DReann q) {
         const uint64_t *d0 = q.dist0 + (size_t)meta->node_off * q.stride0 + (size_t)(V - 1) * nl;
         r.delta = nl == 2 ? rs_delta<2>(df, d0) : nl == 4 ? rs_delta<4>(df, d0) : nl == 8 ? rs_delta<8>(df, d0) : rs_delta<17>(df, d0);
         if (pinned) r.unmet -= (int32_t)(nl == 2 ? rc_count<2>(df) : nl == 4 ? rc_count<4>(df) : nl == 8 ? rc_count<8>(df) : rc_count<17>(df));
+        r.n_genes = meta->n_genes; r.gene_off = meta->gene_off; r.n_path = meta->n_path;
+    }
+    q.rec[c] = r;
+}
+
+// ---- the evidence-weighted re-annotation (DESIGN.md §19): the contigs with biased ORFs, DReann.evs ----
+// The same chain once more under the BIAS policy, in the contig's own limb class: a biased ORF edge weighs W + B, B a signed 64-bit integer
+// of the caller's (|B| <= 2^52, the host has checked it).  The values live in one word per in-edge slot of the batch (DReann.bval), never
+// cleared: a word is read only where the slot's bit is set in DReann.bbit, which is cleared per call as `mask` and `req` are.  A bonus can
+// make a cycle negative; the sweep's caps then end the solve as PHX_S_NEGCYCLE, exactly when the source reaches such a cycle (an unreached
+// node is never relaxed).  The ring and tile sizes are k_rs_lds'.
+template <int NL> struct EvCfg { static constexpr int RING = RsCfg<NL>::RING, ECAP = RsCfg<NL>::ECAP; static constexpr bool MASKED = true, REQ = false, BIAS = true; };
+
+// a thread per ORF of a contig that is solved under the bias policy: a refused or biased ORF finds its edge as in k_rs_mask; a refused one
+// sets the slot's bit in `mask` (refusal wins over a bias), a biased one writes B to the slot's word, sets the slot's bit in `bbit` and
+// adds |B| to the contig's sum — in two halves, which a contig's ORFs (< 2^31) cannot overflow
+__global__ __launch_bounds__(NT) void k_ev_mask(DBatch b, DReann q) {
+    const DMeta *meta = &b.meta[blockIdx.x];
+    if (!q.evs[blockIdx.x] || !mg_contig(meta)) return;
+    const DOrf *orf = b.orf + meta->orf_off;
+    const DGrp *grp = b.grp + meta->grp_off;
+    const int32_t *onode = b.onode + meta->orf_off;
+    const uint8_t *forb = q.forb + meta->orf_off;
+    const long long *bias = q.bias + meta->orf_off;
+    const uint32_t *in_off = b.in_off + meta->node_off + blockIdx.x;
+    const uint32_t *esrc = b.esrc + meta->edge_off;
+    const uint64_t ebase = (uint64_t)meta->edge_off;
+    const int V = meta->n_node;
+    for (int k = (int)blockIdx.y * NT + (int)threadIdx.x; k < meta->n_orf; k += (int)gridDim.y * NT) {
+        const uint8_t f = forb[k];
+        const long long B = bias[k];
+        if (f != 1 && B == 0) continue;
+        const DOrf o = orf[k];
+        const int sn = onode[k], tn = grp[o.grp].node;
+        const bool fwd = o.frame > 0;
+        const int u = fwd ? sn : tn, v = fwd ? tn : sn;
+        if (u < 0 || v < 0 || u >= V || v >= V) continue;
+        for (uint32_t x = in_off[v], x1 = in_off[v + 1]; x < x1; x++)
+            if (!ESRC_IS_GAP(esrc[x]) && ESRC_NODE(esrc[x]) == (uint32_t)u) { // (no such edge: the ORF is ignored)
+                if (f == 1) atomicOr(&q.mask[(ebase + x) >> 5], 1u << ((ebase + x) & 31));
+                else {
+                    const unsigned long long a = (unsigned long long)(B < 0 ? -B : B);
+                    q.bval[ebase + x] = B;
+                    atomicOr(&q.bbit[(ebase + x) >> 5], 1u << ((ebase + x) & 31));
+                    atomicAdd(&q.bsum[2 * blockIdx.x], a & 0xffffffffull);
+                    atomicAdd(&q.bsum[2 * blockIdx.x + 1], a >> 32);
+                }
+                break;
+            }
+    }
+}
+
+// (the launch bounds of k_rs_lds)
+template <int NL>
+__global__ __launch_bounds__(SW_THREADS, NL == 2 ? 5 : (NL == 4 ? 4 : 2)) void k_ev_lds(DBatch b, DReann q) {
+    DMeta *meta = &b.meta[blockIdx.x];
+    const int V = meta->n_node;
+    if (!q.evs[blockIdx.x] || !mg_contig(meta) || meta->sssp_nl != NL) return;
+    // the layout's bound plus the sum of |B|: beyond the contig's class there is no promotion, the contig ends before its sweep
+    const double extra = (double)q.bsum[2 * blockIdx.x + 1] * 4294967296.0 + (double)q.bsum[2 * blockIdx.x];
+    if (contig_sum_bits(b, meta, extra) > 64 * NL) {
+        __syncthreads(); // (every thread has read the status)
+        if (threadIdx.x == 0) { meta->status = PHX_S_OVERFLOW; meta->n_genes = 0; meta->n_path = 0; meta->gene_off = 0; }
+        return;
+    }
+    lds_sweep<NL, EvCfg<NL>>(b, meta, blockIdx.x, V, q.mask, q.gplan, nullptr, 0, q.bbit, q.bval);
+}
+
+template <int NL, int IO_T>
+__global__ __launch_bounds__(IO_T) void k_ev_inorder(DBatch b, DReann q) {
+    __shared__ IoShared<IO_T> sh;
+    DMeta *meta = &b.meta[blockIdx.x];
+    if (!q.evs[blockIdx.x] || meta->sssp_nl != NL) return;
+    if (threadIdx.x == 0) { sh.flag = 0; meta->tie = 0; }
+    __syncthreads();
+    if (!mg_contig(meta)) return; // (a cycle of negative length, or the biased bound beyond the class: the solver has set the status)
+    if (meta->n_path < 2 && meta->n_path != -1) return;
+    inorder_contig<NL, IO_T, true, false, true>(b, meta, blockIdx.x, &sh, q.mask, nullptr, q.bbit, q.bval);
+}
+
+// a thread per contig: the record the host reads (k_rs_fin's; delta = float(D_B - D) / 1000.0 may be negative, wi_to_double_rn rounds the
+// magnitude to nearest-even and puts the sign back, which is what float() of a negative python integer does)
+__global__ __launch_bounds__(64) void k_ev_fin(DBatch b, DReann q) {
+    const int c = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (c >= b.n_contig || !q.evs[c]) return;
+    const DMeta *meta = &b.meta[c];
+    DReannRec r;
+    r.status = meta->status; r.n_genes = 0; r.gene_off = 0; r.n_path = 0; r.tie = meta->tie; r.delta = __builtin_inf();
+    r.unmet = 0; r.pad_ = 0;
+    if (meta->status >= 0 && meta->status != PHX_S_NOPATH && meta->n_path >= 2) {
+        const int V = meta->n_node, nl = meta->sssp_nl;
+        const uint64_t *df = b.dist + (size_t)meta->node_off * b.dist_stride + (size_t)(V - 1) * nl;
+        const uint64_t *d0 = q.dist0 + (size_t)meta->node_off * q.stride0 + (size_t)(V - 1) * nl;
+        r.delta = nl == 2 ? rs_delta<2>(df, d0) : nl == 4 ? rs_delta<4>(df, d0) : nl == 8 ? rs_delta<8>(df, d0) : rs_delta<17>(df, d0);
         r.n_genes = meta->n_genes; r.gene_off = meta->gene_off; r.n_path = meta->n_path;
     }
     q.rec[c] = r;

@@ -356,7 +356,10 @@ __host__ __device__ inline size_t sssp_lds_bytes(int V, int nl) {
 // explicit row whose bit is set in `req` carries W - 2^(64 (NL - 1)) — the top limb of a distance is then minus the number of required edges
 // behind it, the limbs below the W-sum (rq_count) —, and a distance that counts more than `kreq` required edges ends the solve: only a cycle
 // through a required edge produces one (DESIGN.md §16).
-struct SwRun { static constexpr int RING = SW_RING, ECAP = SW_ECAP; static constexpr bool MASKED = false, REQ = false; };
+// BIAS (the evidence-weighted re-annotation, EvCfg in phx_resolve.inc; always MASKED, never REQ): an explicit row whose bit is set in `bbit`
+// carries W + B, B the signed 64-bit word of its in-edge slot in `bval` (read only where the bit is set; DESIGN.md §19).  A bonus can make a
+// cycle negative: the sweep and round caps end such a solve, and an unreached node stays at the unreached pattern as under REQ.
+struct SwRun { static constexpr int RING = SW_RING, ECAP = SW_ECAP; static constexpr bool MASKED = false, REQ = false, BIAS = false; };
 #define RS_PLAN_LDS 2048 // window-plan bytes kept in LDS (contigs of up to 65 536 nodes); longer plans live in DReann.gplan
 
 // in-edge slot e (source word sw) is refused: coded rows never are (phx_resolve.inc: the bitmap holds bits of explicit rows only)
@@ -373,18 +376,27 @@ __device__ __forceinline__ bool rs_required(const uint32_t *req, uint64_t ebase,
     const uint64_t x = ebase + e;
     return ((req[x >> 5] >> (x & 31)) & 1u) != 0;
 }
+// in-edge slot e carries a bias (BIAS only; a bit of `bbit` as one of `mask`, explicit rows only)
+template <class P>
+__device__ __forceinline__ bool rs_biased(const uint32_t *bbit, uint64_t ebase, uint32_t sw, uint32_t e) {
+    if (!P::BIAS || ESRC_IS_GAP(sw)) return false;
+    const uint64_t x = ebase + e;
+    return ((bbit[x >> 5] >> (x & 31)) & 1u) != 0;
+}
 // required edges counted by a distance of NL limbs under REQ: minus its top limb, less the borrow of a negative W-sum in the limbs below
 template <int NL>
 __device__ __forceinline__ int64_t rq_count(const WInt<NL> &d) { return -(int64_t)(d.v[NL - 1] + (d.v[NL - 2] >> 63)); }
 template <class P>
 __device__ __forceinline__ long long sw_row(uint32_t sw, const long long *ew, uint32_t e, const long long *gt) { return P::MASKED ? edge_wenc(sw, ew, e, gt) : ew[e]; }
-// the integer of in-edge slot e as the sweep adds it: W, under REQ W - 2^(64 (NL - 1)) for a required row
+// the integer of in-edge slot e as the sweep adds it: W, under REQ W - 2^(64 (NL - 1)) for a required row, under BIAS W + B for a biased one
+// (|B| <= 2^52, so ew_decode reads it as the plain integer it is)
 template <int NL, class P>
-__device__ __forceinline__ WInt<NL> sw_weight(uint32_t sw, const long long *ew, uint32_t e, const long long *gt, const uint32_t *req, uint64_t ebase) {
-    if constexpr (!P::REQ) return ew_decode<NL>(sw_row<P>(sw, ew, e, gt));
+__device__ __forceinline__ WInt<NL> sw_weight(uint32_t sw, const long long *ew, uint32_t e, const long long *gt, const uint32_t *req, uint64_t ebase, const uint32_t *bbit = nullptr, const long long *bval = nullptr) {
+    if constexpr (!P::REQ && !P::BIAS) return ew_decode<NL>(sw_row<P>(sw, ew, e, gt));
     else {
         WInt<NL> w = ew_decode<NL>(sw_row<P>(sw, ew, e, gt));
         if (rs_required<P>(req, ebase, sw, e)) w.v[NL - 1] -= 1ull;
+        if constexpr (P::BIAS) { if (rs_biased<P>(bbit, ebase, sw, e)) w = wi_add<NL>(w, ew_decode<NL>(bval[ebase + e])); }
         return w;
     }
 }
@@ -393,7 +405,7 @@ __device__ __forceinline__ WInt<NL> sw_weight(uint32_t sw, const long long *ew, 
 // contig; a scenario slot's workgroup passes its slot's contig, phx_resolve.inc): distances to b.dist, lowest-index tight parents to b.parent, then the
 // path and the genes.  V = meta->n_node (the caller has read it; after expand_contig's fence a second read would be a second load).
 template <int NL, class P>
-__device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const uint32_t ci, const int V, const uint32_t *mask, uint8_t *gplan, const uint32_t *req = nullptr, const int kreq = 0) {
+__device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const uint32_t ci, const int V, const uint32_t *mask, uint8_t *gplan, const uint32_t *req = nullptr, const int kreq = 0, const uint32_t *bbit = nullptr, const long long *bval = nullptr) {
     constexpr int RING = P::RING, ECAP = P::ECAP;
     constexpr int EPT = (ECAP + SW_THREADS - 1) / SW_THREADS; // tile edges prefetched per thread
     extern __shared__ __align__(16) uint8_t smem[];
@@ -461,7 +473,7 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const ui
         if (tid < NL) ring[(size_t)RING * NL + tid] = 0; // the constant-zero slot (the LDS is reused by the pass below)
         if (tid == 0) s_viol = 0;
         __syncthreads();
-        // registers that carry window k+1's data while window k iterates; bit j of r_mk: tile edge j of this thread is refused, bit 16 + j: required
+        // registers that carry window k+1's data while window k iterates; bit j of r_mk: tile edge j of this thread is refused, bit 16 + j: required (REQ) or biased (BIAS: never both policies)
         uint32_t r_src[EPT];
         long long r_w[EPT];
         uint32_t r_mk = 0;
@@ -488,6 +500,7 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const ui
                 r_w[j] = on ? sw_row<P>(sw, ew, e0n + i, gt) : 0ll;
                 if (on && rs_refused<P>(mask, ebase, sw, e0n + i)) r_mk |= 1u << j;
                 if (P::REQ && on && rs_required<P>(req, ebase, sw, e0n + i)) r_mk |= 0x10000u << j;
+                if (P::BIAS && on && rs_biased<P>(bbit, ebase, sw, e0n + i)) r_mk |= 0x10000u << j;
             }
         }
         for (int k = 0; k < nW && !bad; k++) {
@@ -526,6 +539,7 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const ui
                         // ring, whose distance cannot change while this window iterates and is folded into the weight)
                         uint32_t sl = RING;
                         if (P::REQ && ((r_mk >> (16 + j)) & 1u)) w.v[NL - 1] -= 1ull; // required: W - M, so the phases pay nothing for it either
+                        if constexpr (P::BIAS) { if ((r_mk >> (16 + j)) & 1u) w = wi_add<NL>(w, ew_decode<NL>(bval[ebase + e0 + i])); } // biased: W + B, likewise
                         if (P::MASKED && ((r_mk >> j) & 1u)) w = big; // refused: no edge (0 + "unreached" never wins), so the phases pay nothing for the mask
                         else if (u != (uint32_t)SRC) {
                             if ((int)u < loaded && (int)u + RING >= loaded) sl = u & (RING - 1);
@@ -555,6 +569,7 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const ui
                     r_w[j] = on ? sw_row<P>(sw, ew, e0n + i, gt) : 0ll;
                     if (on && rs_refused<P>(mask, ebase, sw, e0n + i)) r_mk |= 1u << j;
                     if (P::REQ && on && rs_required<P>(req, ebase, sw, e0n + i)) r_mk |= 0x10000u << j;
+                    if (P::BIAS && on && rs_biased<P>(bbit, ebase, sw, e0n + i)) r_mk |= 0x10000u << j;
                 }
             }
 #ifdef SW_PROFILE
@@ -632,13 +647,14 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const ui
                             if (u == (uint32_t)SRC) du = wi_load<NL>(ring + (size_t)RING * NL);
                             else if ((int)u < loaded && (int)u + RING >= loaded) du = wi_load<NL>(ring + (size_t)(u & (RING - 1)) * NL);
                             else du = wi_load<NL>(gdist + (size_t)u * NL);
-                            best = wi_min_bf<NL>(best, wi_add<NL>(du, sw_weight<NL, P>(sw, ew, e0 + i, gt, req, ebase)));
+                            best = wi_min_bf<NL>(best, wi_add<NL>(du, sw_weight<NL, P>(sw, ew, e0 + i, gt, req, ebase, bbit, bval)));
                         }
                     }
                     best = wi_row_min<NL>(best, sub);
                     // (REQ: an unreached node stays at the unreached pattern — relaxed among themselves, the nodes of a cycle through a required
                     // edge that no path from the source reaches would go down by M a turn for ever; such a cycle is no cycle of the solve)
-                    if (act && sub == SW_LPN - 1 && wi_lt_bf<NL>(best, d0) && !(P::REQ && wi_unreached<NL>(best))) {
+                    // (BIAS: the same for a cycle that a bonus has made negative and the source does not reach — it is no cycle of the solve either)
+                    if (act && sub == SW_LPN - 1 && wi_lt_bf<NL>(best, d0) && !((P::REQ || P::BIAS) && wi_unreached<NL>(best))) {
                         wi_store<NL>(myslot, best);
                         wi_store<NL>(ph ? gB : gA, best); // write-through
                         s_flag[it & 1] = 1;
@@ -674,8 +690,8 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const ui
                 for (uint32_t e = in_off[v] + sub; e < e1; e += SW_LPN) {
                     const uint32_t sw = esrc[e];
                     if (rs_refused<P>(mask, ebase, sw, e)) continue;
-                    const WInt<NL> cand = wi_add<NL>(wi_load<NL>(gdist + (size_t)ESRC_NODE(sw) * NL), sw_weight<NL, P>(sw, ew, e, gt, req, ebase));
-                    if (wi_lt_bf<NL>(cand, dv) && !(P::REQ && wi_unreached<NL>(cand))) viol = true;
+                    const WInt<NL> cand = wi_add<NL>(wi_load<NL>(gdist + (size_t)ESRC_NODE(sw) * NL), sw_weight<NL, P>(sw, ew, e, gt, req, ebase, bbit, bval));
+                    if (wi_lt_bf<NL>(cand, dv) && !((P::REQ || P::BIAS) && wi_unreached<NL>(cand))) viol = true;
                     if (wi_eq<NL>(cand, dv) && e < be && !wi_unreached<NL>(dv)) be = e;
                 }
             }
