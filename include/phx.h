@@ -42,7 +42,8 @@ extern "C" {
  *        (addition, version unchanged: the suite pins 410) phx_constrain_flat — probe for the symbol, not for a version;
  *        (addition, version unchanged) phx_evidence_flat — likewise;
  *        (additions, version unchanged) phx_scenarios_flat, phx_scenarios_ms, phx_scenario_chunks, phx_tap_scenario_path — probe for the symbol;
- *        (addition, version unchanged) phx_pinned_scenarios_flat — probe for the symbol */
+ *        (addition, version unchanged) phx_pinned_scenarios_flat — probe for the symbol;
+ *        (addition, version unchanged) phx_evidence_scenarios_flat — probe for the symbol */
 #define PHX_MAX_CODONS 16
 
 /* library-level errors */
@@ -502,7 +503,25 @@ int phx_pinned_scenarios_flat(phx_ctx *ctx, int64_t n_scen, const int32_t *scen_
                               const int64_t *orf_offsets /* [n+1] */, uint32_t flags /* reserved: 0 */, phx_gene *genes, int64_t cap,
                               int64_t *offsets /* [n_scen+1] */, int32_t *status /* [n_scen] */, double *delta /* [n_scen] */, int32_t *unmet /* [n_scen] */,
                               int64_t *total);
-/* device time of the last scenario solve (of either kind), summed over its chunks, ms[3]: slot records + bitmap slices, masked solve, in-order parents +
+/* ---- evidence scenario batches: many evidence-weighted re-annotations of the batch last run in one call ----
+ * phx_scenarios_flat with a list of (ORF, B) pairs per scenario: scenario j refuses F_j = forbid_orf[forbid_off[j] .. forbid_off[j+1]) and
+ * biases ORF bias_orf[k] by bias_val[k] for k in [bias_off[j], bias_off[j+1]), indices in phx_tap_orfs order of contig scen_contig[j], B a
+ * signed integer in the solver's units.  The bias of an ORF is the sum of the B of its pairs; a refused ORF's bias is ignored.  It is, by
+ * definition, phx_evidence_flat applied to that contig with exactly that bias, that refused set and bit 0 of its flags set: status[j],
+ * delta[j] (which may be negative) and genes[offsets[j] .. offsets[j+1]) are byte for byte that call's for the contig — PHX_S_NOPATH with
+ * +inf, PHX_S_NEGCYCLE (no genes, +inf), PHX_S_OVERFLOW from the limb-class test and a run error passed through.  A scenario whose summed
+ * biases are all zero is phx_scenarios_flat's scenario byte for byte (the same kernels).  Scenarios are independent; they may repeat a
+ * contig, overlap, be empty and hold duplicates.
+ * Calling convention, argument checks (on both lists: both offset arrays start at 0 and never decrease), state rules, chunking and the
+ * device-memory budget are those of phx_scenarios_flat; bias_off must not be NULL, and a summed |B| > 2^52 is PHX_E_ARG before any kernel.
+ * It is one solve with the two calls above on one set of buffers, with one cached result keyed on the refused lists and the merged bias
+ * lists: phx_scenarios_ms, phx_scenario_chunks and phx_tap_scenario_path, whose distance is then D_B, report on the last scenario solve of
+ * any kind.  No required list per scenario.  (Addition, version unchanged: probe for the symbol.) */
+int phx_evidence_scenarios_flat(phx_ctx *ctx, int64_t n_scen, const int32_t *scen_contig /* [n_scen] */, const int64_t *forbid_off /* [n_scen+1] */,
+                                const int32_t *forbid_orf, const int64_t *bias_off /* [n_scen+1] */, const int32_t *bias_orf, const int64_t *bias_val,
+                                const int64_t *orf_offsets /* [n+1] */, uint32_t flags /* reserved: 0 */, phx_gene *genes, int64_t cap,
+                                int64_t *offsets /* [n_scen+1] */, int32_t *status /* [n_scen] */, double *delta /* [n_scen] */, int64_t *total);
+/* device time of the last scenario solve (of any kind), summed over its chunks, ms[3]: slot records + bitmap slices, masked solve, in-order parents +
  * path + genes + the copies to the host.  All 0 before the first. */
 int phx_scenarios_ms(phx_ctx *ctx, float *ms /* [3] */);
 /* path and D_F of scenario `scen` of the last scenario solve, like phx_tap_repath (n_path 0: no path, or a scenario whose contig was not

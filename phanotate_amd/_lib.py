@@ -59,6 +59,11 @@ START_DT = np.dtype([("left", "i4"), ("right", "i4"), ("strand", "i4"), ("orf", 
 # index; its ends beside it), the cost of that (delta), status and unmet of the pinned scenario, and how many genes the run's annotation loses / gains
 ALT_DT = np.dtype([("left", "i4"), ("right", "i4"), ("strand", "i4"), ("orf", "i4"), ("alt", "i4"), ("alt_left", "i4"), ("alt_right", "i4"), ("status", "i4"),
                    ("delta", "f8"), ("unmet", "i4"), ("n_removed", "i4"), ("n_added", "i4")], align=True)
+# Annotator.evidence_scan(): the ORF (orf: its index in orfs(i); left, right, strand: its ends as a gene's) biased alone by `bias` SCORE units, status and
+# delta of that scenario, whether the run's device genes hold the ORF (was_called) and whether the new ones do (called), and how many genes the run's
+# annotation loses / gains
+EVSCAN_DT = np.dtype([("left", "i4"), ("right", "i4"), ("strand", "i4"), ("orf", "i4"), ("bias", "f8"), ("status", "i4"), ("was_called", "i4"),
+                      ("delta", "f8"), ("called", "i4"), ("n_removed", "i4"), ("n_added", "i4")], align=True)
 EDGE_DT = np.dtype([("src", "i4"), ("dst", "i4"), ("w", "f8"), ("inexact", "i4"), ("pad", "i4"), ("d1", "f8"), ("d2", "f8"), ("err", "f8")], align=True)
 
 _lib = None
@@ -166,6 +171,7 @@ def lib():
         "phx_reannotate_ms": (C.c_int, [vp, P(C.c_float)]),
         "phx_scenarios_flat": (C.c_int, [vp, i64, vp, vp, vp, vp, C.c_uint32, vp, i64, vp, vp, vp, P(i64)]),
         "phx_pinned_scenarios_flat": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, i64, vp, vp, vp, vp, P(i64)]),
+        "phx_evidence_scenarios_flat": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, i64, vp, vp, vp, P(i64)]),
         "phx_scenarios_ms": (C.c_int, [vp, P(C.c_float)]),
         "phx_scenario_chunks": (C.c_int64, [vp]),
         "phx_tap_scenario_path": (C.c_int, [vp, i64, vp, i32, P(i32), vp, i32]),
@@ -211,4 +217,5 @@ EXPORTS = ["phx_version", "phx_device_count", "phx_strerror", "phx_last_error", 
            "phx_replacements_flat", "phx_tap_replacement", "phx_replacements_ms", "phx_replacement_stats",
            "phx_format_replacements",
            "phx_reannotate_flat", "phx_constrain_flat", "phx_evidence_flat", "phx_orf_offsets", "phx_tap_repath", "phx_reannotate_ms",
-           "phx_scenarios_flat", "phx_scenarios_ms", "phx_scenario_chunks", "phx_tap_scenario_path", "phx_pinned_scenarios_flat"]
+           "phx_scenarios_flat", "phx_scenarios_ms", "phx_scenario_chunks", "phx_tap_scenario_path", "phx_pinned_scenarios_flat",
+           "phx_evidence_scenarios_flat"]

@@ -613,7 +613,7 @@ class Annotator:
         return status[:S], offs, genes[: int(total.value)], delta[:S]
 
     def scenarios_ms(self):
-        """Device time of the last scenario solve (scenarios() or pinned_scenarios()) in ms, summed over its chunks: slot records + bitmaps, masked solve, path + genes + copy
+        """Device time of the last scenario solve (scenarios(), pinned_scenarios() or evidence_scenarios()) in ms, summed over its chunks: slot records + bitmaps, masked solve, path + genes + copy
         (phx_scenarios_ms)."""
         ms = (C.c_float * 3)()
         self._chk(self.L.phx_scenarios_ms(self.h, ms), "phx_scenarios_ms")
@@ -624,8 +624,8 @@ class Annotator:
         return int(self.L.phx_scenario_chunks(self.h))
 
     def scenario_path(self, j, contig):
-        """(path as device node ids, its length D_F as a python int) of scenario j of the last scenarios() or pinned_scenarios() call, like
-        reannotated_path (a scenario with required ORFs: the W-sum W(P)); `contig` is the scenario's contig.  Served while the scenario's
+        """(path as device node ids, its length D_F as a python int) of scenario j of the last scenarios(), pinned_scenarios() or evidence_scenarios()
+        call, like reannotated_path (a scenario with required ORFs: the W-sum W(P); one with biased ORFs: D_B); `contig` is the scenario's contig.  Served while the scenario's
         chunk is resident (phx_tap_scenario_path)."""
         g = self.globals(contig)
         p = np.zeros(max(g.n_node, 1), np.int32)
@@ -758,6 +758,107 @@ class Annotator:
             new = {key(g) for g in genes[soffs[x]:soffs[x + 1]]}
             o["n_removed"], o["n_added"] = len(have - new), len(new - have)
         return st, offs, rec, soffs, genes
+
+    # ---- evidence scenario batches ----
+    @staticmethod
+    def _bias_units(i, k, b):
+        """B = math.trunc(b * 1000.0) of evidence(), with its refusals."""
+        import math
+
+        b = float(b)
+        if not math.isfinite(b) or abs(b) * 1000.0 >= 2.0 ** 60:
+            raise ValueError("contig %d, ORF %d: the bias %r is not a finite number of SCORE units within 2^52 / 1000" % (i, k, b))
+        return math.trunc(b * 1000.0)
+
+    def evidence_scenarios(self, scen):
+        """(status int32[S], offsets int64[S+1], genes structured array[total], delta float64[S]): S evidence-weighted re-annotations of
+        the batch last run in one call (phx_evidence_scenarios_flat).  `scen` is a sequence of (contig, bias, forbid):
+        `bias` what evidence() takes for one contig — None, or a dict or sequence of (index into orfs(contig), b) pairs, b a float in SCORE
+        units, B = math.trunc(b * 1000.0), an ORF listed twice gets the sum of its B —, `forbid` an array of indices or None.  Scenario j
+        is evidence(..., solve_all=True) of that contig with exactly that bias and that refused set — status[j], delta[j] and
+        genes[offsets[j]:offsets[j+1]] are byte for byte that call's for the contig — solved side by side on the resident graph, one
+        workgroup per scenario.  Scenarios are independent (the same contig may be named many times, lists may overlap, be empty or hold
+        duplicates); one without a bias is scenarios()' scenario.  IndexError and ValueError as evidence()."""
+        n = self.n
+        oo = self.orf_offsets()
+        try:
+            triples = [(i, b, f) for i, b, f in scen]
+        except (TypeError, ValueError):
+            raise ValueError("an evidence scenario is a (contig, bias, forbid) triple") from None
+        contig, foff, forf = self._scenario_arrays([(i, f) for i, _, f in triples], n, oo)
+        S = len(triples)
+        boff = np.zeros(S + 1, np.int64)
+        borf, bval = [], []
+        for j, (i, pairs, _) in enumerate(triples):
+            i = int(i)
+            sums = {}
+            for k, b in (() if pairs is None else pairs.items() if hasattr(pairs, "items") else pairs):
+                k = int(k)
+                if not 0 <= k < oo[i + 1] - oo[i]:
+                    raise IndexError("contig %d has %d ORFs" % (i, oo[i + 1] - oo[i]))
+                B = self._bias_units(i, k, b)
+                sums[k] = sums.get(k, 0) + B
+                borf.append(k)  # (the pairs as given: the library merges them)
+                bval.append(B)
+            if any(abs(v) > 1 << 52 for v in sums.values()):
+                raise ValueError("a bias beyond 2^52 / 1000 SCORE units")
+            boff[j + 1] = len(borf)
+        borf = np.ascontiguousarray(borf if borf else [0], np.int32)
+        bval = np.ascontiguousarray(bval if bval else [0], np.int64)
+        offs = np.zeros(S + 1, np.int64)
+        status = np.zeros(max(S, 1), np.int32)
+        delta = np.zeros(max(S, 1), np.float64)
+        total = C.c_int64(0)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        call = lambda g, cap: self._chk(self.L.phx_evidence_scenarios_flat(self.h, S, vp(contig), vp(foff), vp(forf), vp(boff), vp(borf), vp(bval), vp(oo), 0, g, cap, vp(offs),
+                                                                              vp(status), vp(delta), C.byref(total)), "phx_evidence_scenarios_flat")
+        call(None, 0)
+        genes = np.empty(max(int(total.value), 1), _lib.GENE_DT)
+        call(vp(genes), len(genes))
+        return status[:S], offs, genes[: int(total.value)], delta[:S]
+
+    def evidence_scan(self, hits):
+        """(status int32[n], offsets int64[n+1], records structured array[total] of _lib.EVSCAN_DT, scen_offsets int64[total+1], genes):
+        `hits` holds, per contig, None or a sequence of (index into orfs(i), b) pairs as evidence() takes them; every pair is taken on its
+        own — one scenario that biases that ORF alone and refuses nothing — and all run in one evidence_scenarios() call.  The records of
+        contig i are records[offsets[i]:offsets[i+1]], in the order of its pairs; status[i] is the run's verdict for the contig.  A
+        record holds the ORF (its index and its ends as a gene's), the bias as given, status and delta of its scenario, was_called /
+        called (the ORF among the run's device genes / among the new ones) and n_removed / n_added as alt_starts() counts them;
+        genes[scen_offsets[k]:scen_offsets[k+1]] is record k's full new annotation."""
+        n = self.n
+        if len(hits) != n:
+            raise ValueError("one sequence of (ORF index, bias) pairs (or None) per contig of the batch")
+        scen, head = [], []
+        offs = np.zeros(n + 1, np.int64)
+        for i, pairs in enumerate(hits):
+            for k, b in (() if pairs is None else pairs.items() if hasattr(pairs, "items") else pairs):
+                scen.append((i, [(int(k), b)], None))
+                head.append((i, int(k), float(b)))
+            offs[i + 1] = len(scen)
+        sstat, soffs, genes, delta = self.evidence_scenarios(scen)
+        self._chk(self.L.phx_set_exact(self.h, 0), "phx_set_exact")  # the device's own lists, as download_flat(exact=False)
+        try:
+            st, roffs, rgenes = self._download_flat()
+        finally:
+            self._chk(self.L.phx_set_exact(self.h, 1), "phx_set_exact")
+        key = lambda g: (int(g["left"]), int(g["right"]), int(g["strand"]), int(g["frame"]))
+        rec = np.zeros(len(scen), _lib.EVSCAN_DT)
+        have, have_of, orfs_of = None, -1, None
+        for x, (i, k, b) in enumerate(head):
+            if have_of != i:
+                have, have_of, orfs_of = {key(g) for g in rgenes[roffs[i]:roffs[i + 1]]}, i, self.orfs(i)
+            o = rec[x]
+            ao = orfs_of[k]
+            fwd = ao["frame"] > 0
+            o["left"], o["right"] = (ao["start"], ao["stop"] + 2) if fwd else (ao["stop"], ao["start"] + 2)
+            o["strand"], o["orf"], o["bias"] = (1 if fwd else -1), k, b
+            o["status"], o["delta"] = sstat[x], delta[x]
+            me = (int(o["left"]), int(o["right"]), bool(fwd))
+            new = {key(g) for g in genes[soffs[x]:soffs[x + 1]]}
+            o["was_called"] = int(any((g[0], g[1], g[2] > 0) == me and abs(g[3]) <= 3 for g in have))
+            o["called"] = int(any((g[0], g[1], g[2] > 0) == me and abs(g[3]) <= 3 for g in new))
+            o["n_removed"], o["n_added"] = len(have - new), len(new - have)
+        return np.asarray(st[:n], np.int32), offs, rec, soffs, genes
 
     def reannotated_path(self, i):
         """(path as device node ids, its length as a python int) of contig i in the last re-annotation, constrain() or evidence(), like

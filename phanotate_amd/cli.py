@@ -48,6 +48,7 @@ def get_args(argv=None):
     p.add_argument("--forbid", metavar="FILE", default=None, help="ORFs to refuse in a second annotation (DESIGN.md §14): lines whose first four columns are START STOP FRAME CONTIG as the tabular output prints a gene; needs --reannotation")
     p.add_argument("--require", metavar="FILE", default=None, help="ORFs to keep in a second annotation (DESIGN.md §16), in the format of --forbid; alone or with --forbid; needs --reannotation, which then carries a #unmet: line per contig")
     p.add_argument("--evidence", metavar="FILE", default=None, help="per-ORF bonuses and penalties for a second annotation (DESIGN.md §19), in the format of --forbid with a fifth column BIAS: a finite number of SCORE units added to the ORF's weight (negative: support; an ORF named twice gets the sum); alone or with --forbid, not with --require; needs --reannotation, whose #delta: may then be negative")
+    p.add_argument("--evidence-scan", metavar=("FILE", "OUT"), nargs=2, default=None, help="also take every line of FILE (the format of --evidence) on its own: write to OUT, per line, the cost and the effect of the best annotation under that one bias (DESIGN.md §20); independent of --evidence / --reannotation")
     p.add_argument("--reannotation", metavar="OUT", default=None, help="write the annotation without the ORFs of --forbid (keeping those of --require, or under the biases of --evidence) to OUT: the tabular block of every contig with a #delta: header line")
     p.add_argument("--single-device-ranks", action="store_true", help=argparse.SUPPRESS)  # tests: every rank of a sharded launch on GPU `--device` (gloo-only group)
     args = p.parse_args(argv)
@@ -75,6 +76,12 @@ def get_args(argv=None):
         p.error("argument --alt-starts: not available under a multi-rank launch")
     if args.alt_starts is not None and int(args.gpus) > 1:  # the scenarios work on the batch resident on one context
         p.error("argument --alt-starts: not available with --gpus above 1")
+    if args.evidence_scan is not None and args.dump:
+        p.error("argument --evidence-scan: not allowed with argument -d/--dump")
+    if args.evidence_scan is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        p.error("argument --evidence-scan: not available under a multi-rank launch")
+    if args.evidence_scan is not None and int(args.gpus) > 1:  # the scenarios work on the batch resident on one context
+        p.error("argument --evidence-scan: not available with --gpus above 1")
     for flag, val in (("--forbid", args.forbid), ("--require", args.require), ("--evidence", args.evidence), ("--reannotation", args.reannotation)):
         if val is not None and args.dump:
             p.error("argument %s: not allowed with argument -d/--dump" % flag)
@@ -176,6 +183,34 @@ def resolve_evidence(entries, names, lookup, flag="--evidence"):
             out[i] = []
         out[i].append((k, b))
     return out
+
+
+def format_evidence_scan(names, status, offsets, records):
+    """--evidence-scan FILE OUT: per contig with status >= 0 "#id:\t<name>", the header, one row per record of Annotator.evidence_scan()
+    (a line of FILE, taken on its own): the ORF's START STOP FRAME as the tabular output prints a gene, repr(bias), DELTA — repr(delta),
+    or "cycle" (the bonus makes a cycle negative: PHX_S_NEGCYCLE) or "inf" (no path, or no result) —, whether the new annotation calls the
+    ORF (1 / 0), and the genes the run's annotation loses and gains."""
+    import io
+
+    import numpy as np
+
+    buf = io.StringIO()
+    for i, nm in enumerate(names):
+        if status[i] < 0:
+            continue
+        buf.write("#id:\t" + nm + "\n#START\tSTOP\tFRAME\tBIAS\tDELTA\tCALLED\tREMOVED\tADDED\n")
+        for r in records[offsets[i]:offsets[i + 1]]:
+            rev = r["strand"] < 0
+            left, right = (int(r["right"]), int(r["left"])) if rev else (int(r["left"]), int(r["right"]))  # locus.py:44-46
+            if r["status"] == -9:
+                delta = "cycle"
+            elif r["status"] != 0 or not np.isfinite(r["delta"]):
+                delta = "inf"
+            else:
+                delta = repr(float(r["delta"]))
+            buf.write("%d\t%d\t%s\t%s\t%s\t%d\t%d\t%d\n" % (left, right, chr(44 - (-1 if rev else 1)), repr(float(r["bias"])), delta, int(r["called"]), int(r["n_removed"]),
+                                                          int(r["n_added"])))
+    return buf.getvalue()
 
 
 def format_reannotation(names, status, offsets, genes, delta, unmet=None):
@@ -448,8 +483,12 @@ def main(argv=None):
     start_parts = []  # --start-drops: (status, offsets, records) of every batch, in order
     alt_parts = []  # --alt-starts: the same of Annotator.alt_starts()
     reann_parts = []  # --reannotation: (status, offsets, genes, delta[, unmet]) of every batch, in order
-    forbid_entries = require_entries = evidence_entries = None
+    scan_parts = []  # --evidence-scan: (status, offsets, records) of Annotator.evidence_scan() of every batch, in order
+    forbid_entries = require_entries = evidence_entries = scan_entries = None
     try:
+        if args.evidence_scan is not None:
+            with open(args.evidence_scan[0]) as fh:
+                scan_entries = parse_evidence(fh, "--evidence-scan")
         if args.evidence is not None:
             with open(args.evidence) as fh:
                 evidence_entries = parse_evidence(fh)
@@ -483,7 +522,7 @@ def main(argv=None):
             if lo >= len(idx):
                 break
         t_parts["batches"] = len(cuts)
-        if forbid_entries is not None or require_entries is not None or evidence_entries is not None or args.start_drops is not None or args.alt_starts is not None:  # the re-annotation and the scenarios work on the batch resident on one context: the batches one after the other
+        if forbid_entries is not None or require_entries is not None or evidence_entries is not None or args.start_drops is not None or args.alt_starts is not None or scan_entries is not None:  # the re-annotation and the scenarios work on the batch resident on one context: the batches one after the other
             parts = []
             for lo, hi in cuts:
                 t0 = time.perf_counter()
@@ -506,6 +545,8 @@ def main(argv=None):
                     alt_parts.append(ann.alt_starts()[:3])
                 names = [fa.names[int(i)] for i in idx[lo:hi]]
                 here = set(names)
+                if scan_entries is not None:
+                    scan_parts.append(ann.evidence_scan(resolve_evidence([e for e in scan_entries if e[3] in here], names, ann.orf_index, "--evidence-scan"))[:3])
                 refused = resolve_forbid([e for e in forbid_entries or [] if e[3] in here], names, ann.orf_index)
                 if evidence_entries is not None:
                     reann_parts.append(ann.evidence(resolve_evidence([e for e in evidence_entries if e[3] in here], names, ann.orf_index), refused))
@@ -564,7 +605,7 @@ def main(argv=None):
         return st, np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), genes
 
     known = set(fa.names)
-    for flag, entries in (("--forbid", forbid_entries), ("--require", require_entries), ("--evidence", evidence_entries)):
+    for flag, entries in (("--forbid", forbid_entries), ("--require", require_entries), ("--evidence", evidence_entries), ("--evidence-scan", scan_entries)):
         for e in entries or []:
             if e[3] not in known:
                 drop_context()
@@ -637,6 +678,12 @@ def main(argv=None):
             a_offsets = np.concatenate([[0], np.cumsum(a_counts)]).astype(np.int64)
             with open(args.alt_starts, "w") as fh:
                 fh.write(format_alt_starts(fa.names, a_status, a_offsets, np.concatenate([m[2] for m in alt_parts])))
+        if args.evidence_scan is not None:
+            e_status = np.concatenate([m[0] for m in scan_parts])
+            e_counts = np.concatenate([np.diff(m[1]) for m in scan_parts])
+            e_offsets = np.concatenate([[0], np.cumsum(e_counts)]).astype(np.int64)
+            with open(args.evidence_scan[1], "w") as fh:
+                fh.write(format_evidence_scan(fa.names, e_status, e_offsets, np.concatenate([m[2] for m in scan_parts])))
         if args.reannotation is not None:
             q_status = np.concatenate([m[0] for m in reann_parts])
             q_counts = np.concatenate([np.diff(m[1]) for m in reann_parts])

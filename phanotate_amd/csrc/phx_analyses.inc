@@ -786,24 +786,27 @@ int phx_reannotate_ms(phx_ctx *c, float *ms) {
     return PHX_OK;
 }
 
-// ---- scenario batches (phx_resolve.inc, DESIGN.md §17), with required ORFs per scenario (§18) ----
+// ---- scenario batches (phx_resolve.inc, DESIGN.md §17), with required ORFs (§18) or biased ORFs (§20) per scenario ----
 // h_srec[j].status before the solve: the scenario gets a slot / its contig is not solved again and the run's verdict stands (neither is a status the device reports)
 static const int32_t SC_SLOT = -99, SC_NOSLOT = -100;
 // Device bytes of one slot of contig i: distances, parent, path, bitmap slice, window plan, gene records, the record copy; a pinned slot
-// (§18) has one limb more per node, a second bitmap slice and its entries of DScen.req0 / nreq / kreq.
-static size_t scen_slot_bytes(const phx_ctx *c, int i, bool pinned = false) {
+// (§18) has one limb more per node, a second bitmap slice and its entries of DScen.req0 / nreq / kreq; a biased slot (§20) with n_bias
+// listed ORFs has a bias slice, its DScBias and per ORF a triple, a list pair and a staging pair of 16 bytes each.
+static size_t scen_slot_bytes(const phx_ctx *c, int i, bool pinned = false, size_t n_bias = 0) {
     const DMeta &m = c->meta[(size_t)i];
     const size_t V = (size_t)m.n_node, E = (size_t)m.n_edge;
     return V * ((size_t)m.sssp_nl * 8 + 4 + 4) + (E / 32 + 3) * 4 + (V / 32 + 2) + (V + 1) * sizeof(DGene) + sizeof(DMeta) + sizeof(DScSlot) + sizeof(DReannRec) +
-           (pinned ? V * 8 + (E / 32 + 3) * 4 + 16 : 0);
+           (pinned ? V * 8 + (E / 32 + 3) * 4 + 16 : 0) + (n_bias ? (E / 32 + 3) * 4 + sizeof(DScBias) + n_bias * 48 : 0);
 }
 
 // Solves the scenarios with a slot (h_srec[j].status == SC_SLOT) in chunks under the budget; records into h_srec, genes into h_sgenes.
 // perm: per contig named, tap index -> ORF in the contig's device order (-1: no such ORF in the device's groups).  req_off / req_orf: the
 // required lists without duplicates; a scenario with a non-empty one gets a pinned slot.  In a chunk's slot table the pinned slots follow
-// the plain ones (the slices keep the scenarios' order): k_sc_* get the head of the table, k_scp_* its tail.
+// the plain ones (the slices keep the scenarios' order): k_sc_* get the head of the table, k_scp_* its tail.  bs_off / bs_orf / bs_val: the
+// merged bias lists (no duplicates, no zero, no ORF the scenario refuses); a scenario with a non-empty one gets a biased slot (never with a
+// required list: no entry point takes both), and the biased slots follow the pinned ones: k_sce_* get that tail.
 static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const int64_t *scen_off, const int32_t *scen_orf, const int64_t *req_off, const int32_t *req_orf,
-                        const std::vector<std::vector<int32_t>> &perm) {
+                        const int64_t *bs_off, const int32_t *bs_orf, const int64_t *bs_val, const std::vector<std::vector<int32_t>> &perm) {
     int rc;
     hipStream_t s = c->stream;
     c->scen_chunks = 0;
@@ -812,17 +815,22 @@ static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const
     c->h_sslot.assign((size_t)S, DScSlot{});
     c->h_schunk_of.assign((size_t)S, 0);
     if ((rc = analysis_events(c))) return rc;
-    std::vector<DScSlot> slots, pslots; // plain, pinned
-    std::vector<int2> pairs, rpairs;    // (a pinned slot's index: -1 - its place among the pinned ones, until the chunk is closed)
-    std::vector<int64_t> which, pwhich; // scenario of every slot of the chunk
+    const int EV0 = 1 << 30;            // a chunk has fewer slots
+    std::vector<DScSlot> slots, pslots, eslots; // plain, pinned, biased
+    std::vector<int2> pairs, rpairs;    // (a pinned slot's index: -1 - its place among the pinned ones, a biased slot's: EV0 + its place among the biased ones, until the chunk is closed)
+    std::vector<int64_t> which, pwhich, ewhich; // scenario of every slot of the chunk
+    std::vector<DScBias> ebs;           // per biased slot: its DScBias
+    std::vector<DScTrip> &trips = c->h_strip; // the chunk's triples and the table's DScBias as uploaded (members: see h_qdforb)
+    std::vector<DScBias> &bsv = c->h_sbs;
     std::vector<int64_t> preq0;         // per pinned slot: DScen.req0
     std::vector<int32_t> pnreq;         //   ... and nreq
     std::vector<uint8_t> &pin = c->h_spin; // what the kernels read per slot: req0 (int64), nreq, kreq (int32)
     for (int64_t j0 = 0; j0 < S;) {
         // ---- the chunk: scenarios j0 .. j1 with a slot, as many as the budget holds (at least one) ----
         slots.clear(); pslots.clear(); pairs.clear(); rpairs.clear(); which.clear(); pwhich.clear(); preq0.clear(); pnreq.clear();
-        size_t bytes = 0, nodes = 0, words = 0, mwords = 0, rwords = 0, plan = 0;
-        int nlm = 0, pinm = 0;
+        eslots.clear(); ewhich.clear(); ebs.clear(); trips.clear();
+        size_t bytes = 0, nodes = 0, words = 0, mwords = 0, rwords = 0, bwords = 0, plan = 0;
+        int nlm = 0, pinm = 0, evm = 0;
         int64_t j1 = j0;
         for (; j1 < S; j1++) {
             if (c->h_srec[(size_t)j1].status != SC_SLOT) continue;
@@ -830,8 +838,11 @@ static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const
             const DMeta &m = c->meta[(size_t)i];
             const int32_t nreq = (int32_t)(req_off[j1 + 1] - req_off[j1]);
             const bool pinned = nreq > 0;
-            const size_t need = scen_slot_bytes(c, i, pinned);
-            if (!(slots.empty() && pslots.empty()) && bytes + need > (size_t)c->scen_budget) break;
+            const size_t nbias = pinned ? 0 : (size_t)(bs_off[j1 + 1] - bs_off[j1]);
+            const bool biased = nbias > 0;
+            const size_t need = scen_slot_bytes(c, i, pinned, nbias);
+            const size_t have = slots.size() + pslots.size() + eslots.size();
+            if (have && (bytes + need > (size_t)c->scen_budget || have + 1 >= (size_t)EV0)) break;
             bytes += need;
             DScSlot sl;
             sl.contig = i; sl.pinned = pinned ? 1 : 0;
@@ -841,8 +852,8 @@ static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const
             words += ((size_t)m.n_node * (size_t)(m.sssp_nl + (pinned ? 1 : 0)) + 1) & ~(size_t)1;
             mwords += mw;
             plan += (size_t)m.n_node / 32 + 2;
-            (pinned ? pinm : nlm) |= nl_class_bit(m.sssp_nl);
-            const int id = pinned ? -1 - (int)pslots.size() : (int)slots.size();
+            (pinned ? pinm : biased ? evm : nlm) |= nl_class_bit(m.sssp_nl);
+            const int id = pinned ? -1 - (int)pslots.size() : biased ? EV0 + (int)eslots.size() : (int)slots.size();
             const std::vector<int32_t> &pm = perm[(size_t)i];
             for (int64_t k = scen_off[j1]; k < scen_off[j1 + 1]; k++) {
                 const int32_t d = pm[(size_t)scen_orf[k]];
@@ -853,15 +864,31 @@ static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const
                 if (d >= 0) rpairs.push_back(make_int2(id, d));
             }
             if (pinned) { preq0.push_back((int64_t)rwords); pnreq.push_back(nreq); rwords += mw; pslots.push_back(sl); pwhich.push_back(j1); }
-            else { slots.push_back(sl); which.push_back(j1); }
+            else if (biased) {
+                DScBias e{};
+                e.bbit0 = (int64_t)bwords; e.list0 = (int64_t)trips.size();
+                for (int64_t k = bs_off[j1]; k < bs_off[j1 + 1]; k++) {
+                    const int32_t d = pm[(size_t)bs_orf[k]];
+                    if (d >= 0) trips.push_back(DScTrip{id, d, (long long)bs_val[k]});
+                }
+                e.n_trip = (int32_t)(trips.size() - (size_t)e.list0);
+                bwords += mw; ebs.push_back(e); eslots.push_back(sl); ewhich.push_back(j1);
+            } else { slots.push_back(sl); which.push_back(j1); }
         }
         j0 = j1;
-        const size_t n_plain = slots.size(), n_pin = pslots.size(), ns = n_plain + n_pin;
+        const size_t n_plain = slots.size(), n_pin = pslots.size(), n_ev = eslots.size(), ns = n_plain + n_pin + n_ev, n_head = n_plain + n_pin;
         if (!ns) break;
         slots.insert(slots.end(), pslots.begin(), pslots.end());
+        slots.insert(slots.end(), eslots.begin(), eslots.end());
         which.insert(which.end(), pwhich.begin(), pwhich.end());
-        for (int2 &pr : pairs) if (pr.x < 0) pr.x = (int)n_plain + (-1 - pr.x);
+        which.insert(which.end(), ewhich.begin(), ewhich.end());
+        for (int2 &pr : pairs) pr.x = pr.x < 0 ? (int)n_plain + (-1 - pr.x) : pr.x >= EV0 ? (int)n_head + (pr.x - EV0) : pr.x;
         for (int2 &pr : rpairs) pr.x = (int)n_plain + (-1 - pr.x);
+        for (DScTrip &t : trips) t.slot = (int)n_head + (t.slot - EV0);
+        int max_list = 0; // the longest list of the chunk: how many workgroups k_sce_sort gives a slot
+        for (const DScBias &e : ebs) max_list = std::max(max_list, (int)e.n_trip);
+        bsv.assign(n_ev ? ns : 0, DScBias{});
+        std::copy(ebs.begin(), ebs.end(), bsv.begin() + (ptrdiff_t)(n_ev ? n_head : 0));
         pin.assign(ns * 16, 0);
         for (size_t k = 0; k < n_pin; k++) {
             memcpy(pin.data() + (n_plain + k) * 8, &preq0[k], 8);
@@ -870,15 +897,18 @@ static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const
         c->scen_chunks++;
         if ((rc = ensure(c, c->b_sc_slot, ns * sizeof(DScSlot))) || (rc = ensure(c, c->b_sc_pair, (pairs.size() + rpairs.size() + 1) * sizeof(int2))) ||
             (rc = ensure(c, c->b_sc_meta, ns * sizeof(DMeta))) || (rc = ensure(c, c->b_sc_dist, (words + 2) * 8)) || (rc = ensure(c, c->b_sc_parent, (nodes + 1) * 4)) ||
-            (rc = ensure(c, c->b_sc_path, (nodes + 1) * 4)) || (rc = ensure(c, c->b_sc_mask, (mwords + 2 + rwords + 2) * 4)) || (rc = ensure(c, c->b_sc_plan, plan + 2)) ||
+            (rc = ensure(c, c->b_sc_path, (nodes + 1) * 4)) || (rc = ensure(c, c->b_sc_mask, (mwords + 2 + rwords + 2 + bwords + 2) * 4)) || (rc = ensure(c, c->b_sc_plan, plan + 2)) ||
             (rc = ensure(c, c->b_sc_genes, (nodes + ns + 1) * sizeof(DGene))) || (rc = ensure(c, c->b_sc_rec, ns * sizeof(DReannRec))) ||
-            (rc = ensure(c, c->b_sc_tot, sizeof(DTotals))) || (rc = ensure(c, c->b_sc_gtot, 16)) || (n_pin && (rc = ensure(c, c->b_sc_pin, ns * 16))))
+            (rc = ensure(c, c->b_sc_tot, sizeof(DTotals))) || (rc = ensure(c, c->b_sc_gtot, 16)) || (n_pin && (rc = ensure(c, c->b_sc_pin, ns * 16))) ||
+            (n_ev && ((rc = ensure(c, c->b_sc_bs, ns * sizeof(DScBias))) || (rc = ensure(c, c->b_sc_trip, (trips.size() + 1) * sizeof(DScTrip))) ||
+                      (rc = ensure(c, c->b_sc_blist, 2 * (trips.size() + 1) * 16)))))
             return rc;
         if (!c->b_sc_tie.p && (rc = ensure(c, c->b_sc_tie, (size_t)std::max<int64_t>(c->tie_seen, 1 << 20)))) return rc;
         HIPCHK(c, hipMemcpyAsync(c->b_sc_slot.p, slots.data(), ns * sizeof(DScSlot), hipMemcpyHostToDevice, s));
         if (!pairs.empty()) HIPCHK(c, hipMemcpyAsync(c->b_sc_pair.p, pairs.data(), pairs.size() * sizeof(int2), hipMemcpyHostToDevice, s));
         if (!rpairs.empty()) HIPCHK(c, hipMemcpyAsync((int2 *)c->b_sc_pair.p + pairs.size(), rpairs.data(), rpairs.size() * sizeof(int2), hipMemcpyHostToDevice, s));
         if (n_pin) HIPCHK(c, hipMemcpyAsync(c->b_sc_pin.p, pin.data(), ns * 16, hipMemcpyHostToDevice, s));
+        if (!trips.empty()) HIPCHK(c, hipMemcpyAsync(c->b_sc_trip.p, trips.data(), trips.size() * sizeof(DScTrip), hipMemcpyHostToDevice, s));
         c->h_schunk.assign(ns, DReannRec{});
         DTotals &tot = c->h_stot;
         uint32_t &gtot = c->h_sgtot;
@@ -901,23 +931,34 @@ static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const
                 q.req = q.mask + (mwords + 2); q.req0 = (const int64_t *)c->b_sc_pin.p; q.nreq = (const int32_t *)((const uint8_t *)c->b_sc_pin.p + ns * 8);
                 q.kreq = (int32_t *)((uint8_t *)c->b_sc_pin.p + ns * 12); q.rpair = q.pair + pairs.size(); q.n_rpair = (int64_t)rpairs.size();
             }
-            DScen qa = q, qb = q; // the plain head and the pinned tail of the slot table
+            q.bbit = nullptr; q.bs = nullptr; q.blist = nullptr; q.bstage = nullptr; q.trip = nullptr; q.n_trip = 0;
+            if (n_ev) {
+                q.bbit = q.mask + (mwords + 2 + rwords + 2); q.bs = (DScBias *)c->b_sc_bs.p; q.blist = (long long *)c->b_sc_blist.p;
+                q.bstage = q.blist + 2 * (trips.size() + 1); q.trip = (const DScTrip *)c->b_sc_trip.p; q.n_trip = (int64_t)trips.size();
+            }
+            DScen qa = q, qb = q, qe = q; // the plain head, the pinned middle and the biased tail of the slot table
+            qe.n_slot = (int32_t)n_ev; qe.slot += n_head; qe.meta += n_head; qe.rec += n_head;
+            if (n_ev) qe.bs += n_head;
             qa.n_slot = (int32_t)n_plain;
             qb.n_slot = (int32_t)n_pin; qb.slot += n_plain; qb.meta += n_plain; qb.rec += n_plain;
             if (n_pin) { qb.req0 += n_plain; qb.nreq += n_plain; qb.kreq += n_plain; }
             HIPCHK(c, hipEventRecord(c->aev[0], s));
             HIPCHK(c, hipMemsetAsync(c->b_sc_tot.p, 0, sizeof(DTotals), s));
             HIPCHK(c, hipMemsetAsync(c->b_sc_gtot.p, 0, 16, s));
-            HIPCHK(c, hipMemsetAsync(c->b_sc_mask.p, 0, (mwords + 2 + (n_pin ? rwords + 2 : 0)) * 4, s));
+            HIPCHK(c, hipMemsetAsync(c->b_sc_mask.p, 0, (mwords + 2 + (n_pin || n_ev ? rwords + 2 : 0) + (n_ev ? bwords + 2 : 0)) * 4, s));
+            if (n_ev) HIPCHK(c, hipMemcpyAsync(c->b_sc_bs.p, bsv.data(), ns * sizeof(DScBias), hipMemcpyHostToDevice, s)); // (counts and sums at zero: k_sce_mask appends again, also on a tie-scratch retry)
             if (n_pin) HIPCHK(c, hipMemsetAsync(q.kreq, 0, ns * 4, s)); // k_scp_mask counts again (also on a tie-scratch retry)
             phxk_scen_mask(&b, &q, s);
             if (n_pin) phxk_scen_pin_mask(&b, &q, s);
+            if (n_ev) phxk_scen_ev_mask(&b, &q, &qe, max_list, s);
             HIPCHK(c, hipEventRecord(c->aev[1], s));
             phxk_scen_solve(&b, &qa, nlm, s);
             if (n_pin) phxk_scen_pin_solve(&b, &qb, pinm, s);
+            if (n_ev) phxk_scen_ev_solve(&b, &qe, evm, s);
             HIPCHK(c, hipEventRecord(c->aev[2], s));
             phxk_scen_finish(&b, &qa, nlm, s);
             if (n_pin) phxk_scen_pin_finish(&b, &qb, pinm, s);
+            if (n_ev) phxk_scen_ev_finish(&b, &qe, evm, s);
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, hipMemcpyAsync(c->h_schunk.data(), c->b_sc_rec.p, ns * sizeof(DReannRec), hipMemcpyDeviceToHost, s));
             HIPCHK(c, hipEventRecord(c->aev[3], s));
@@ -950,10 +991,11 @@ static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const
     return PHX_OK;
 }
 
-// phx_scenarios_flat (no required lists: require_off, require_orf and unmet null) and phx_pinned_scenarios_flat are one solve on one set of
-// buffers; the cached result is keyed on both lists (as reann_flat serves phx_reannotate_flat and phx_constrain_flat).
+// phx_scenarios_flat (no required lists: require_off, require_orf and unmet null), phx_pinned_scenarios_flat and phx_evidence_scenarios_flat
+// (bias lists instead of required ones) are one solve on one set of buffers; the cached result is keyed on all the lists (as reann_flat
+// serves phx_reannotate_flat, phx_constrain_flat and phx_evidence_flat).
 static int scen_flat(phx_ctx *c, const char *who, int64_t n_scen, const int32_t *scen_contig, const int64_t *scen_off, const int32_t *scen_orf, const int64_t *req_off_in,
-                     const int32_t *req_orf_in, const int64_t *orf_offsets, phx_gene *genes, int64_t cap, int64_t *offsets, int32_t *status, double *delta, int32_t *unmet,
+                     const int32_t *req_orf_in, const int64_t *bias_off_in, const int32_t *bias_orf_in, const int64_t *bias_val_in, const int64_t *orf_offsets, phx_gene *genes, int64_t cap, int64_t *offsets, int32_t *status, double *delta, int32_t *unmet,
                      int64_t *total_out) {
     if (!c || n_scen < 0 || !offsets || !scen_off || (n_scen > 0 && (!status || !delta || !scen_contig)) || (c->n > 0 && !orf_offsets)) return PHX_E_ARG;
     { const int ra = after_run(c); if (ra) return ra; }
@@ -967,10 +1009,11 @@ static int scen_flat(phx_ctx *c, const char *who, int64_t n_scen, const int32_t 
     }
     if (c->n > 0 && orf_offsets[c->n] != acc) return PHX_E_ARG;
     const size_t S = (size_t)n_scen;
-    for (int pass = 0; pass < 2; pass++) { // the refused lists, then the required ones
-        const int64_t *off = pass ? req_off_in : scen_off;
-        const int32_t *orf = pass ? req_orf_in : scen_orf;
+    for (int pass = 0; pass < 3; pass++) { // the refused lists, then the required ones, then the biased ones
+        const int64_t *off = pass == 2 ? bias_off_in : pass ? req_off_in : scen_off;
+        const int32_t *orf = pass == 2 ? bias_orf_in : pass ? req_orf_in : scen_orf;
         if (!off) continue;
+        if (pass == 2 && off[S] > 0 && !bias_val_in) return PHX_E_ARG;
         if (off[0] != 0) return PHX_E_ARG;
         for (size_t j = 0; j < S; j++) {
             if (off[j + 1] < off[j]) return PHX_E_ARG;
@@ -1001,8 +1044,34 @@ static int scen_flat(phx_ctx *c, const char *who, int64_t n_scen, const int32_t 
                 if (std::binary_search(f.begin(), f.end(), rq_orf[k])) { c->err = std::string(who) + ": an ORF is both refused and required in one scenario"; return PHX_E_ARG; } // before any kernel
         }
     }
+    // the bias lists merged (§20): per scenario one entry per ORF in ascending order, its B the sum of the ORF's pairs; zero sums and the
+    // ORFs the scenario refuses are dropped, so the device never arbitrates
+    std::vector<int64_t> &bs_off = c->h_sbs_off, &bs_val = c->h_sbs_val;
+    std::vector<int32_t> &bs_orf = c->h_sbs_orf;
+    bs_off.assign(S + 1, 0);
+    bs_orf.clear(); bs_val.clear();
+    if (bias_off_in) {
+        std::vector<std::pair<int32_t, int64_t>> pb;
+        std::vector<int32_t> f;
+        for (size_t j = 0; j < S; j++) {
+            pb.clear();
+            for (int64_t k = bias_off_in[j]; k < bias_off_in[j + 1]; k++) pb.emplace_back(bias_orf_in[k], bias_val_in[k]);
+            std::sort(pb.begin(), pb.end());
+            f.assign(scen_orf + scen_off[j], scen_orf + scen_off[j + 1]);
+            std::sort(f.begin(), f.end());
+            for (size_t k = 0; k < pb.size();) {
+                __int128 sum = 0;
+                size_t k1 = k;
+                for (; k1 < pb.size() && pb[k1].first == pb[k].first; k1++) sum += pb[k1].second;
+                if (sum > (__int128)PHX_BIAS_MAX || sum < -(__int128)PHX_BIAS_MAX) { c->err = std::string(who) + ": a bias beyond 2^52"; return PHX_E_ARG; } // before any kernel
+                if (sum != 0 && !std::binary_search(f.begin(), f.end(), pb[k].first)) { bs_orf.push_back(pb[k].first); bs_val.push_back((int64_t)sum); }
+                k = k1;
+            }
+            bs_off[j + 1] = (int64_t)bs_orf.size();
+        }
+    }
     const size_t P = (size_t)scen_off[S];
-    const bool same = c->done.scen && c->h_skey_contig.size() == S && c->h_skey_orf.size() == P &&
+    const bool same = c->h_skey_boff == bs_off && c->h_skey_borf == bs_orf && c->h_skey_bval == bs_val && c->done.scen && c->h_skey_contig.size() == S && c->h_skey_orf.size() == P &&
                       std::equal(scen_contig, scen_contig + S, c->h_skey_contig.begin()) && std::equal(scen_off, scen_off + S + 1, c->h_skey_off.begin()) &&
                       std::equal(scen_orf, scen_orf + P, c->h_skey_orf.begin()) && c->h_skey_roff == rq_off && c->h_skey_rorf == rq_orf;
     if (!same) {
@@ -1019,7 +1088,7 @@ static int scen_flat(phx_ctx *c, const char *who, int64_t n_scen, const int32_t 
             if (!reann_contig(c, i)) continue; // (the run's verdict stands: a run error, no device distances, an empty graph)
             c->h_srec[j].status = SC_SLOT;
             std::vector<int32_t> &pm = perm[(size_t)i];
-            if (!pm.empty() || (scen_off[j + 1] == scen_off[j] && rq_off[j + 1] == rq_off[j])) continue;
+            if (!pm.empty() || (scen_off[j + 1] == scen_off[j] && rq_off[j + 1] == rq_off[j] && bs_off[j + 1] == bs_off[j])) continue;
             const DMeta &m = c->meta[(size_t)i];
             pm.assign((size_t)m.n_orf, -1);
             size_t t = 0;
@@ -1028,12 +1097,13 @@ static int scen_flat(phx_ctx *c, const char *who, int64_t n_scen, const int32_t 
                 t += (size_t)(k > 0 ? k : 0);
             });
         }
-        { const int rq = scen_compute(c, n_scen, scen_contig, scen_off, scen_orf, rq_off.data(), rq_orf.data(), perm); if (rq) { (void)hipStreamSynchronize(c->stream); return rq; } }
+        { const int rq = scen_compute(c, n_scen, scen_contig, scen_off, scen_orf, rq_off.data(), rq_orf.data(), bs_off.data(), bs_orf.data(), bs_val.data(), perm); if (rq) { (void)hipStreamSynchronize(c->stream); return rq; } }
         c->h_skey_contig.assign(scen_contig, scen_contig + S);
         c->h_skey_off.assign(scen_off, scen_off + S + 1);
         c->h_skey_orf.assign(scen_orf, scen_orf + P);
         c->h_skey_roff = rq_off;
         c->h_skey_rorf = rq_orf;
+        c->h_skey_boff = bs_off; c->h_skey_borf = bs_orf; c->h_skey_bval = bs_val;
         c->done.scen = true;
     }
     // ---- the caller's layout: per scenario what phx_reannotate_flat / phx_constrain_flat reports for its contig ----
@@ -1074,7 +1144,7 @@ static int scen_flat(phx_ctx *c, const char *who, int64_t n_scen, const int32_t 
 int phx_scenarios_flat(phx_ctx *c, int64_t n_scen, const int32_t *scen_contig, const int64_t *scen_off, const int32_t *scen_orf, const int64_t *orf_offsets,
                        uint32_t flags, phx_gene *genes, int64_t cap, int64_t *offsets, int32_t *status, double *delta, int64_t *total_out) {
     (void)flags; // reserved
-    return scen_flat(c, "phx_scenarios_flat", n_scen, scen_contig, scen_off, scen_orf, nullptr, nullptr, orf_offsets, genes, cap, offsets, status, delta, nullptr, total_out);
+    return scen_flat(c, "phx_scenarios_flat", n_scen, scen_contig, scen_off, scen_orf, nullptr, nullptr, nullptr, nullptr, nullptr, orf_offsets, genes, cap, offsets, status, delta, nullptr, total_out);
 }
 
 int phx_pinned_scenarios_flat(phx_ctx *c, int64_t n_scen, const int32_t *scen_contig, const int64_t *forbid_off, const int32_t *forbid_orf, const int64_t *require_off,
@@ -1082,8 +1152,17 @@ int phx_pinned_scenarios_flat(phx_ctx *c, int64_t n_scen, const int32_t *scen_co
                               double *delta, int32_t *unmet, int64_t *total_out) {
     (void)flags; // reserved
     if (!c || !require_off || (n_scen > 0 && !unmet)) return PHX_E_ARG;
-    return scen_flat(c, "phx_pinned_scenarios_flat", n_scen, scen_contig, forbid_off, forbid_orf, require_off, require_orf, orf_offsets, genes, cap, offsets, status, delta, unmet,
-                     total_out);
+    return scen_flat(c, "phx_pinned_scenarios_flat", n_scen, scen_contig, forbid_off, forbid_orf, require_off, require_orf, nullptr, nullptr, nullptr, orf_offsets, genes, cap, offsets,
+                     status, delta, unmet, total_out);
+}
+
+int phx_evidence_scenarios_flat(phx_ctx *c, int64_t n_scen, const int32_t *scen_contig, const int64_t *forbid_off, const int32_t *forbid_orf, const int64_t *bias_off,
+                                const int32_t *bias_orf, const int64_t *bias_val, const int64_t *orf_offsets, uint32_t flags, phx_gene *genes, int64_t cap, int64_t *offsets,
+                                int32_t *status, double *delta, int64_t *total_out) {
+    (void)flags; // reserved
+    if (!c || !bias_off) return PHX_E_ARG;
+    return scen_flat(c, "phx_evidence_scenarios_flat", n_scen, scen_contig, forbid_off, forbid_orf, nullptr, nullptr, bias_off, bias_orf, bias_val, orf_offsets, genes, cap, offsets,
+                     status, delta, nullptr, total_out);
 }
 
 int phx_tap_scenario_path(phx_ctx *c, int64_t scen, int32_t *path, int32_t cap, int32_t *n_path, uint64_t *dist_limbs, int32_t cap_limbs) {

@@ -282,7 +282,7 @@ struct phx_ctx {
     uint32_t h_qgtot = 0;
     float reann_ms[3] = {0, 0, 0};
     // scenario batches (phx_scenarios_flat): buffers of their own, allocated at the first call; the result kept until the next upload or run
-    DevBuf b_sc_slot, b_sc_pair, b_sc_meta, b_sc_dist, b_sc_parent, b_sc_path, b_sc_mask, b_sc_plan, b_sc_genes, b_sc_rec, b_sc_tot, b_sc_gtot, b_sc_tie, b_sc_pin;
+    DevBuf b_sc_slot, b_sc_pair, b_sc_meta, b_sc_dist, b_sc_parent, b_sc_path, b_sc_mask, b_sc_plan, b_sc_genes, b_sc_rec, b_sc_tot, b_sc_gtot, b_sc_tie, b_sc_pin, b_sc_bs, b_sc_trip, b_sc_blist;
     int64_t scen_budget = (int64_t)2 << 30; // device bytes of a chunk's slots (env PHX_SCEN_BYTES at phx_create)
     int64_t scen_chunks = 0;                // chunks of the last solve
     std::vector<int32_t> h_skey_contig, h_skey_orf; // the scenarios last solved (the cache key)
@@ -290,6 +290,10 @@ struct phx_ctx {
     std::vector<int64_t> h_skey_roff, h_srq_off;   // ... and their required lists without duplicates (§18: all empty for phx_scenarios_flat); of the call at hand
     std::vector<int32_t> h_skey_rorf, h_srq_orf;
     std::vector<uint8_t> h_spin;      // a chunk's DScen.req0 / nreq / kreq as uploaded (a member: see h_qdforb)
+    std::vector<int64_t> h_skey_boff, h_sbs_off, h_skey_bval, h_sbs_val; // ... and their merged bias lists (§20: all empty for the two calls without); of the call at hand
+    std::vector<int32_t> h_skey_borf, h_sbs_orf;
+    std::vector<DScTrip> h_strip;     // a chunk's triples and DScBias as uploaded (members: see h_qdforb)
+    std::vector<DScBias> h_sbs;
     std::vector<DReannRec> h_srec;    // per scenario (status SC_NOSLOT: the run's verdict stands); gene_off into h_sgenes
     std::vector<DGene> h_sgenes;
     std::vector<DScSlot> h_sslot;     // per scenario: its slot (phx_tap_scenario_path) and

@@ -188,9 +188,10 @@ __device__ void walk_path(const DBatch &b, DMeta *meta, IoShared<IO_T> *sh) {
 // W - 2^(64 (NL - 1)), as in the sweep that made the distances (lds_sweep under RcCfg).
 // BIAS (the evidence-weighted re-annotation, DESIGN.md §19; with MASKED): an edge whose bit is set in `bbit` weighs W + B, B the word of its
 // in-edge slot in `bval`, as in the sweep that made the distances (lds_sweep under EvCfg): a row is tight iff d[u] + W + B == d[v].
+// BLIST (a biased scenario slot, DESIGN.md §20; with BIAS): `bval` is the slot's sorted list of nbl (in-edge slot, B) pairs (bias_at, phx_sssp.inc).
 // ci: the contig's index in the batch (blockIdx.x where a workgroup is a contig; a scenario slot passes its slot's contig).
-template <int NL, int IO_T, bool MASKED = false, bool REQ = false, bool BIAS = false>
-__device__ void inorder_contig(const DBatch &b, DMeta *meta, const uint32_t ci, IoShared<IO_T> *sh, const uint32_t *mask = nullptr, const uint32_t *req = nullptr, const uint32_t *bbit = nullptr, const long long *bval = nullptr) {
+template <int NL, int IO_T, bool MASKED = false, bool REQ = false, bool BIAS = false, bool BLIST = false>
+__device__ void inorder_contig(const DBatch &b, DMeta *meta, const uint32_t ci, IoShared<IO_T> *sh, const uint32_t *mask = nullptr, const uint32_t *req = nullptr, const uint32_t *bbit = nullptr, const long long *bval = nullptr, const int nbl = 0) {
     const int tid = threadIdx.x;
     const uint64_t mbase = MASKED ? (uint64_t)meta->edge_off : 0ull;
     auto refused = [&](uint32_t e) -> bool { const uint64_t x = mbase + e; return ((mask[x >> 5] >> (x & 31)) & 1u) != 0; };
@@ -217,7 +218,12 @@ __device__ void inorder_contig(const DBatch &b, DMeta *meta, const uint32_t ci, 
         const WInt<NL> du = wi_load<NL>(dist + (size_t)ESRC_NODE(sw) * NL);
         WInt<NL> w = ewl ? wi_load<NL>(ewl + (size_t)e * NL) : ew_decode<NL>(edge_wenc(sw, ew, e, gt));
         if constexpr (REQ) { if (required(e)) w.v[NL - 1] -= 1ull; }
-        if constexpr (BIAS) { if (biased(e)) w = wi_add<NL>(w, ew_decode<NL>(bval[mbase + e])); }
+        if constexpr (BIAS) {
+            if (biased(e)) {
+                if constexpr (BLIST) w = wi_add<NL>(w, ew_decode<NL>(bias_at<true>(bval, mbase + e, nbl)));
+                else w = wi_add<NL>(w, ew_decode<NL>(bval[mbase + e])); // (bias_at<false>, written out: through the call k_ev_inorder came out with other scalar registers than it had)
+            }
+        }
         return !wi_unreached<NL>(du) && wi_eq<NL>(wi_add<NL>(du, w), dv);
     };
     // ---- 1. does any node of the path have a tight in-edge besides its parent edge? ----
@@ -260,7 +266,12 @@ __device__ void inorder_contig(const DBatch &b, DMeta *meta, const uint32_t ci, 
                 u[q] = ESRC_NODE(sw);
                 w[q] = ewl ? wi_load<NL>(ewl + (size_t)ee * NL) : ew_decode<NL>(edge_wenc(sw, ew, ee, gt));
                 if constexpr (REQ) { if (required(ee)) w[q].v[NL - 1] -= 1ull; }
-                if constexpr (BIAS) { if (biased(ee)) w[q] = wi_add<NL>(w[q], ew_decode<NL>(bval[mbase + ee])); }
+                if constexpr (BIAS) {
+                    if (biased(ee)) {
+                        if constexpr (BLIST) w[q] = wi_add<NL>(w[q], ew_decode<NL>(bias_at<true>(bval, mbase + ee, nbl)));
+                        else w[q] = wi_add<NL>(w[q], ew_decode<NL>(bval[mbase + ee]));
+                    }
+                }
             }
 #pragma unroll
             for (int q = 0; q < 4; q++) {

@@ -418,6 +418,17 @@ struct DScSlot {
                          //   slice shifted back by edge_off >> 5 words is indexed by edge_off + e like DReann.mask
     int64_t plan0;       // first byte of the slot's global window plan (n_node / 32 + 2 bytes)
 };
+struct DScBias { // per biased slot (§20): the host writes the places and zeroes the rest per solve
+    int64_t bbit0;       // first word of the slot's bias slice in DScen.bbit (the bit rule of DScSlot.mask0)
+    int64_t list0;       // first pair of the slot's list in DScen.blist, and of its staging area in DScen.bstage
+    int32_t n_trip;      // triples listed for the slot: the capacity of its list
+    int32_t cnt;         // pairs appended by k_sce_mask (a triple whose ORF has no edge appends none): the list's length
+    unsigned long long bsum[2]; // the sums of |B| & 0xffffffff and of |B| >> 32 over the slot's list (§19's bsum)
+};
+struct DScTrip { // one (slot, ORF, B) triple: the host has merged duplicates, dropped zero sums and the ORFs its scenario refuses
+    int32_t slot, orf;   // slot of the chunk's table, ORF in the contig's device order
+    long long B;
+};
 struct DScen {
     const DScSlot *slot; // per slot of the chunk
     const int2 *pair;    // the listed (slot, ORF in the contig's device order) pairs of the chunk
@@ -438,6 +449,13 @@ struct DScen {
     int32_t *kreq;       // per slot: required ORFs whose edge exists (k_scp_mask counts them): the bound of the solver's cycle guard
     const int2 *rpair;   // the required (slot, ORF in the contig's device order) pairs of the chunk
     int64_t n_rpair;
+    // evidence scenarios (§20); behind the fields above, whose places in the argument blocks of k_sc_* and k_scp_* stay
+    uint32_t *bbit;      // the bias bitmap slices of the biased slots, cleared per chunk
+    DScBias *bs;         // per slot: where its bias slice and list lie, and what k_sce_mask counted and summed (biased slots only)
+    long long *blist;    // the slots' lists: (in-edge slot of the batch: edge_off + e, B) pairs, 16 bytes each, sorted by in-edge slot (k_sce_sort)
+    long long *bstage;   // as blist: where k_sce_mask appends the pairs of a slot with more than one triple, unsorted
+    const DScTrip *trip; // the listed (slot, ORF, B) triples of the chunk
+    int64_t n_trip;
 };
 
 #ifdef __cplusplus
@@ -499,6 +517,9 @@ void phxk_scen_finish(const DBatch *b, const DScen *q, int nl_mask, void *stream
 void phxk_scen_pin_mask(const DBatch *b, const DScen *q, void *stream);                 // pinned scenarios (§18): the required slices and counts (q: the whole slot table),
 void phxk_scen_pin_solve(const DBatch *b, const DScen *q, int pin_mask, void *stream);  //   the sweep under the required policy (q: the table's pinned tail; pin_mask: its classes),
 void phxk_scen_pin_finish(const DBatch *b, const DScen *q, int pin_mask, void *stream); //   in-order parents, path, genes, delta and unmet per pinned slot
+void phxk_scen_ev_mask(const DBatch *b, const DScen *q, const DScen *tail, int max_list, void *stream); // evidence scenarios (§20): the bias slices, lists and sums (q: the whole slot table), the lists sorted (tail: the biased tail; max_list: its longest list),
+void phxk_scen_ev_solve(const DBatch *b, const DScen *q, int ev_mask, void *stream);    //   the sweep under the bias policy with the sparse lookup (q: the table's biased tail; ev_mask: its classes),
+void phxk_scen_ev_finish(const DBatch *b, const DScen *q, int ev_mask, void *stream);   //   in-order parents, path, genes, delta per biased slot
 #ifdef __cplusplus
 }
 #endif

@@ -488,6 +488,33 @@ void phxk_scen_pin_finish(const DBatch *b, const DScen *q, int pin_mask, void *s
     else NL_LAUNCH_T(k_scp_inorder, IO_T_FULL, pin_mask, dim3((unsigned)q->n_slot), *b, *q);
     hipLaunchKernelGGL(k_scp_fin, dim3((unsigned)((q->n_slot + 63) / 64)), dim3(64), 0, s, *b, *q);
 }
+// evidence scenarios: the solve and the finish get the biased tail of the slot table
+void phxk_scen_ev_mask(const DBatch *b, const DScen *q, const DScen *tail, int max_list, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (q->n_slot <= 0 || tail->n_slot <= 0 || q->n_trip <= 0) return;
+    hipLaunchKernelGGL(k_sce_mask, dim3((unsigned)((q->n_trip + NT - 1) / NT)), dim3(NT), 0, s, *b, *q);
+    if (max_list > 1) hipLaunchKernelGGL(k_sce_sort, dim3((unsigned)tail->n_slot, (unsigned)std::min((max_list + NT - 1) / NT, 16)), dim3(NT), 0, s, *tail); // (up to 16 workgroups share the longest list)
+}
+extern "C++" template <int NL>
+static void launch_sce_lds(const DBatch *b, const DScen *q, hipStream_t s) {
+    (void)hipFuncSetAttribute((const void *)k_sce_lds<NL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rs_lds_bytes<NL>());
+    hipLaunchKernelGGL(k_sce_lds<NL>, dim3((unsigned)q->n_slot), dim3(SW_THREADS), rs_lds_bytes<NL>(), s, *b, *q);
+}
+void phxk_scen_ev_solve(const DBatch *b, const DScen *q, int ev_mask, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (q->n_slot <= 0) return;
+    if (ev_mask & 1) launch_sce_lds<2>(b, q, s);
+    if (ev_mask & 2) launch_sce_lds<4>(b, q, s);
+    if (ev_mask & 4) launch_sce_lds<8>(b, q, s);
+    if (ev_mask & 8) launch_sce_lds<17>(b, q, s);
+}
+void phxk_scen_ev_finish(const DBatch *b, const DScen *q, int ev_mask, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (q->n_slot <= 0) return;
+    if (b->mean_len < 8192) NL_LAUNCH_T(k_sce_inorder, 64, ev_mask, dim3((unsigned)q->n_slot), *b, *q); // as phxk_scen_finish
+    else NL_LAUNCH_T(k_sce_inorder, IO_T_FULL, ev_mask, dim3((unsigned)q->n_slot), *b, *q);
+    hipLaunchKernelGGL(k_sc_fin, dim3((unsigned)((q->n_slot + 63) / 64)), dim3(64), 0, s, *b, *q); // (a biased slot's record is a plain slot's)
+}
 // one workgroup for up to 1024 contigs; larger batches in two passes of a workgroup per 256 contigs
 void phxk_layout1(const DBatch *b, void *stream) {
     if (b->n_contig <= LAYOUT_T) { hipLaunchKernelGGL(k_layout1, dim3(1), dim3(LAYOUT_T), 0, (hipStream_t)stream, *b); return; }

@@ -24,8 +24,8 @@
 // Bounds: the sweep and round caps of k_sssp_lds (PHX_S_NEGCYCLE), no waiting between workgroups, no index from the caller on the device
 // (the host checks the offsets; `forb` is one byte per ORF of the batch, `sel` one int per contig).
 
-template <int NL> struct RsCfg { static constexpr int RING = 1024, ECAP = 1024; static constexpr bool MASKED = true, REQ = false, BIAS = false; };
-template <> struct RsCfg<17> { static constexpr int RING = 256, ECAP = 512; static constexpr bool MASKED = true, REQ = false, BIAS = false; }; // 1088 bits: 109 KB of LDS instead of 283
+template <int NL> struct RsCfg { static constexpr int RING = 1024, ECAP = 1024; static constexpr bool MASKED = true, REQ = false, BIAS = false, BLIST = false; };
+template <> struct RsCfg<17> { static constexpr int RING = 256, ECAP = 512; static constexpr bool MASKED = true, REQ = false, BIAS = false, BLIST = false; }; // 1088 bits: 109 KB of LDS instead of 283
 template <int NL>
 __host__ __device__ constexpr size_t rs_lds_bytes() { return (size_t)(RsCfg<NL>::RING + 1) * NL * 8 + (size_t)RsCfg<NL>::ECAP * ((size_t)NL * 8 + 4) + RS_PLAN_LDS + 64; }
 
@@ -84,9 +84,9 @@ __global__ __launch_bounds__(IO_T) void k_rs_inorder(DBatch b, DReann q) {
 // minus the count of required edges on its path (less one while the W-sum below is negative: rq_count) and the low NL limbs are the W-sum
 // in the contig's own class, which obeys the layout's bound as before.  Counts are <= V < 2^30, far from the unreached pattern's 2^62.
 // The ring of the 320-bit solve is halved (66 KB of LDS, two workgroups per CU, where 1024 entries would leave one).
-template <int NL1> struct RcCfg { static constexpr int RING = 1024, ECAP = 1024; static constexpr bool MASKED = true, REQ = true, BIAS = false; };
-template <> struct RcCfg<5> { static constexpr int RING = 512, ECAP = 1024; static constexpr bool MASKED = true, REQ = true, BIAS = false; };
-template <> struct RcCfg<18> { static constexpr int RING = 256, ECAP = 512; static constexpr bool MASKED = true, REQ = true, BIAS = false; };
+template <int NL1> struct RcCfg { static constexpr int RING = 1024, ECAP = 1024; static constexpr bool MASKED = true, REQ = true, BIAS = false, BLIST = false; };
+template <> struct RcCfg<5> { static constexpr int RING = 512, ECAP = 1024; static constexpr bool MASKED = true, REQ = true, BIAS = false, BLIST = false; };
+template <> struct RcCfg<18> { static constexpr int RING = 256, ECAP = 512; static constexpr bool MASKED = true, REQ = true, BIAS = false, BLIST = false; };
 template <int NL1>
 __host__ __device__ constexpr size_t rc_lds_bytes() { return (size_t)(RcCfg<NL1>::RING + 1) * NL1 * 8 + (size_t)RcCfg<NL1>::ECAP * ((size_t)NL1 * 8 + 4) + RS_PLAN_LDS + 64; }
 
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(64) void k_rs_fin(DBatch b, DReann q) {
 // cleared: a word is read only where the slot's bit is set in DReann.bbit, which is cleared per call as `mask` and `req` are.  A bonus can
 // make a cycle negative; the sweep's caps then end the solve as PHX_S_NEGCYCLE, exactly when the source reaches such a cycle (an unreached
 // node is never relaxed).  The ring and tile sizes are k_rs_lds'.
-template <int NL> struct EvCfg { static constexpr int RING = RsCfg<NL>::RING, ECAP = RsCfg<NL>::ECAP; static constexpr bool MASKED = true, REQ = false, BIAS = true; };
+template <int NL> struct EvCfg { static constexpr int RING = RsCfg<NL>::RING, ECAP = RsCfg<NL>::ECAP; static constexpr bool MASKED = true, REQ = false, BIAS = true, BLIST = false; };
 
 // a thread per ORF of a contig that is solved under the bias policy: a refused or biased ORF finds its edge as in k_rs_mask; a refused one
 // sets the slot's bit in `mask` (refusal wins over a bias), a biased one writes B to the slot's word, sets the slot's bit in `bbit` and
@@ -324,7 +324,8 @@ __global__ __launch_bounds__(IO_T) void k_sc_inorder(DBatch b, DScen q) {
     inorder_contig<NL, IO_T, true>(b, meta, ci, &sh, mask);
 }
 
-// a thread per slot: the record the host reads (k_rs_fin's, without the pinned part)
+// a thread per slot: the record the host reads (k_rs_fin's, without the pinned part).  Also launched on the biased tail of the slot table
+// (§20, phxk_scen_ev_finish): a biased slot's record is this one word for word, so a change here changes those slots too.
 __global__ __launch_bounds__(64) void k_sc_fin(DBatch b, DScen q) {
     const int s = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (s >= q.n_slot) return;
@@ -424,3 +425,116 @@ __global__ __launch_bounds__(64) void k_scp_fin(DBatch b, DScen q) {
     }
     q.rec[s] = r;
 }
+
+// ---- evidence scenarios (DESIGN.md §20): the slots with biased ORFs, solved under the BIAS policy with a sparse list per slot ----
+// The host puts the biased slots behind the plain and the pinned ones in a chunk's slot table and hands the solve and the finish the table's
+// tail (DScen.slot, meta, rec, bs moved to the first biased slot, n_slot the biased slots), as §18 does for the pinned ones.  A biased slot
+// keeps no word per in-edge slot (a dense slice would be 8 E bytes, more than everything else the slot owns): it has a bias bitmap slice
+// (DScen.bbit at DScBias.bbit0, the bit rule of mask0) and a list of (in-edge slot of the batch, B) pairs sorted by in-edge slot, which the shared code
+// searches where the slot's bit is set (bias_at under BLIST, phx_sssp.inc).  Its refused slice is set by k_sc_mask like any slot's.
+template <int NL> struct EsCfg { static constexpr int RING = EvCfg<NL>::RING, ECAP = EvCfg<NL>::ECAP; static constexpr bool MASKED = true, REQ = false, BIAS = true, BLIST = true; };
+
+// a thread per (slot, ORF, B) triple of the chunk (slot: its index in the whole table): the ORF's edge, found as k_sc_mask finds it, sets
+// its bit in the slot's bias slice, appends (in-edge slot, B) to the slot's list and adds |B| to the slot's sums as k_ev_mask does.  A
+// slot with one triple needs no sorting and appends to its list proper, any other to its staging area.
+__global__ __launch_bounds__(NT) void k_sce_mask(DBatch b, DScen q) {
+    const int64_t p = (int64_t)blockIdx.x * NT + (int64_t)threadIdx.x;
+    if (p >= q.n_trip) return;
+    const DScTrip tr = q.trip[p];
+    if (tr.slot < 0 || tr.slot >= q.n_slot) return;
+    const DScSlot sl = q.slot[tr.slot];
+    if (sl.contig < 0 || sl.contig >= b.n_contig) return;
+    const DMeta *meta = &b.meta[sl.contig];
+    const int k = tr.orf;
+    if (!mg_contig(meta) || k < 0 || k >= meta->n_orf) return;
+    const DOrf o = b.orf[meta->orf_off + k];
+    const int V = meta->n_node;
+    const int sn = b.onode[meta->orf_off + k], tn = b.grp[meta->grp_off + o.grp].node;
+    const bool fwd = o.frame > 0;
+    const int u = fwd ? sn : tn, v = fwd ? tn : sn;
+    if (u < 0 || v < 0 || u >= V || v >= V) return;
+    const uint32_t *in_off = b.in_off + meta->node_off + sl.contig;
+    const uint32_t *esrc = b.esrc + meta->edge_off;
+    const uint64_t lo = (uint64_t)meta->edge_off & 31u;
+    DScBias *bs = &q.bs[tr.slot];
+    for (uint32_t x = in_off[v], x1 = in_off[v + 1]; x < x1; x++)
+        if (!ESRC_IS_GAP(esrc[x]) && ESRC_NODE(esrc[x]) == (uint32_t)u) { // (no such edge: the ORF is ignored)
+            const int at = atomicAdd(&bs->cnt, 1);
+            if (at >= bs->n_trip) break; // (the host sized the list by the slot's triples)
+            atomicOr(&q.bbit[bs->bbit0 + (int64_t)((lo + x) >> 5)], 1u << ((lo + x) & 31));
+            long long *to = (bs->n_trip == 1 ? q.blist : q.bstage) + 2 * (bs->list0 + at);
+            to[0] = (long long)((uint64_t)meta->edge_off + x); to[1] = tr.B; // (the batch's in-edge slot, as the shared code counts them)
+            const unsigned long long a = (unsigned long long)(tr.B < 0 ? -tr.B : tr.B);
+            atomicAdd(&bs->bsum[0], a & 0xffffffffull);
+            atomicAdd(&bs->bsum[1], a >> 32);
+            break;
+        }
+}
+
+// pairs a biased slot's list holds: what k_sce_mask appended, never beyond the list
+__device__ __forceinline__ int sce_count(const DScBias &bs) { return bs.cnt < bs.n_trip ? bs.cnt : bs.n_trip; }
+
+// the staged pairs of a biased slot into its list in ascending order of their in-edge slot.  A pair's place is the number of pairs in
+// front of it (an equal in-edge slot: the one staged earlier), found by counting — a list is at most a contig's ORFs.  gridDim.y
+// workgroups share a slot's pairs, NT at a time; the keys they count over pass through LDS in tiles of NT.
+__global__ __launch_bounds__(NT) void k_sce_sort(DScen q) {
+    __shared__ long long s_key[NT];
+    const DScBias bs = q.bs[blockIdx.x];
+    if (bs.n_trip <= 1) return; // (k_sce_mask wrote the list itself)
+    const int n = sce_count(bs);
+    const int tid = (int)threadIdx.x;
+    const long long *from = q.bstage + 2 * bs.list0;
+    long long *to = q.blist + 2 * bs.list0;
+    for (int i0 = (int)blockIdx.y * NT; i0 < n; i0 += (int)gridDim.y * NT) { // (i0, n: the same in every thread, so are the barriers)
+        const int i = i0 + tid;
+        const long long key = i < n ? from[2 * i] : 0ll;
+        int at = 0;
+        for (int j0 = 0; j0 < n; j0 += NT) {
+            __syncthreads();
+            if (j0 + tid < n) s_key[tid] = from[2 * (j0 + tid)];
+            __syncthreads();
+            const int m = n - j0 < NT ? n - j0 : NT;
+            for (int j = 0; j < m; j++) { const long long kj = s_key[j]; at += kj < key || (kj == key && j0 + j < i); }
+        }
+        if (i < n) { to[2 * at] = key; to[2 * at + 1] = from[2 * i + 1]; }
+    }
+}
+
+// the slot's bias slice, shifted by sc_view's rule, and its list
+__device__ __forceinline__ const uint32_t *sce_bbit(const DScen &q, const DScBias &bs, const DMeta *meta) { return q.bbit + (bs.bbit0 - (meta->edge_off >> 5)); }
+
+template <int NL>
+__global__ __launch_bounds__(SW_THREADS, NL == 2 ? 5 : (NL == 4 ? 4 : 2)) void k_sce_lds(DBatch b, DScen q) { // (the bounds of k_ev_lds)
+    const uint32_t *mask;
+    uint8_t *gplan;
+    uint32_t ci;
+    DMeta *meta = sc_view(b, q, &ci, &mask, &gplan);
+    const int V = meta->n_node;
+    if (!mg_contig(meta) || meta->sssp_nl != NL) return;
+    const DScBias bs = q.bs[blockIdx.x];
+    // k_ev_lds' limb-class test on the slot's sums
+    const double extra = (double)bs.bsum[1] * 4294967296.0 + (double)bs.bsum[0];
+    if (contig_sum_bits(b, meta, extra) > 64 * NL) {
+        __syncthreads(); // (every thread has read the status)
+        if (threadIdx.x == 0) { meta->status = PHX_S_OVERFLOW; meta->n_genes = 0; meta->n_path = 0; meta->gene_off = 0; }
+        return;
+    }
+    lds_sweep<NL, EsCfg<NL>>(b, meta, ci, V, mask, gplan, nullptr, 0, sce_bbit(q, bs, meta), q.blist + 2 * bs.list0, sce_count(bs));
+}
+
+template <int NL, int IO_T>
+__global__ __launch_bounds__(IO_T) void k_sce_inorder(DBatch b, DScen q) {
+    __shared__ IoShared<IO_T> sh;
+    const uint32_t *mask;
+    uint8_t *gplan;
+    uint32_t ci;
+    DMeta *meta = sc_view(b, q, &ci, &mask, &gplan);
+    if (meta->sssp_nl != NL) return;
+    if (threadIdx.x == 0) { sh.flag = 0; meta->tie = 0; }
+    __syncthreads();
+    if (!mg_contig(meta)) return; // (a cycle of negative length, or the biased bound beyond the class: the solver has set the status)
+    if (meta->n_path < 2 && meta->n_path != -1) return;
+    const DScBias bs = q.bs[blockIdx.x];
+    inorder_contig<NL, IO_T, true, false, true, true>(b, meta, ci, &sh, mask, nullptr, sce_bbit(q, bs, meta), q.blist + 2 * bs.list0, sce_count(bs));
+}
+// (the record of a biased slot is k_ev_fin's through the slot view, which is k_sc_fin's word for word: the finish launches k_sc_fin on the tail)

@@ -359,7 +359,9 @@ __host__ __device__ inline size_t sssp_lds_bytes(int V, int nl) {
 // BIAS (the evidence-weighted re-annotation, EvCfg in phx_resolve.inc; always MASKED, never REQ): an explicit row whose bit is set in `bbit`
 // carries W + B, B the signed 64-bit word of its in-edge slot in `bval` (read only where the bit is set; DESIGN.md §19).  A bonus can make a
 // cycle negative: the sweep and round caps end such a solve, and an unreached node stays at the unreached pattern as under REQ.
-struct SwRun { static constexpr int RING = SW_RING, ECAP = SW_ECAP; static constexpr bool MASKED = false, REQ = false, BIAS = false; };
+// BLIST (a biased scenario slot, EsCfg in phx_resolve.inc; always BIAS): `bval` is not a word per in-edge slot but the slot's own list of
+// (in-edge slot of the batch, B) pairs, sorted by in-edge slot, `nbl` of them (DESIGN.md §20); bias_at below is the one place that knows.
+struct SwRun { static constexpr int RING = SW_RING, ECAP = SW_ECAP; static constexpr bool MASKED = false, REQ = false, BIAS = false, BLIST = false; };
 #define RS_PLAN_LDS 2048 // window-plan bytes kept in LDS (contigs of up to 65 536 nodes); longer plans live in DReann.gplan
 
 // in-edge slot e (source word sw) is refused: coded rows never are (phx_resolve.inc: the bitmap holds bits of explicit rows only)
@@ -383,6 +385,17 @@ __device__ __forceinline__ bool rs_biased(const uint32_t *bbit, uint64_t ebase, 
     const uint64_t x = ebase + e;
     return ((bbit[x >> 5] >> (x & 31)) & 1u) != 0;
 }
+// B of in-edge slot x of the batch (edge_off + e), whose bias bit the caller has seen set.  !BLIST: word x of the batch-wide array.  BLIST:
+// a binary search of the nbl sorted (in-edge slot, B) pairs at `bval`; a set bit without a pair (the list never lacks one) would read as B = 0.
+template <bool BLIST>
+__device__ __forceinline__ long long bias_at(const long long *bval, uint64_t x, int nbl) {
+    if constexpr (!BLIST) return bval[x];
+    else {
+        int lo = 0, hi = nbl; // the first pair whose in-edge slot is >= x
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if ((uint64_t)bval[2 * mid] < x) lo = mid + 1; else hi = mid; }
+        return lo < nbl && (uint64_t)bval[2 * lo] == x ? bval[2 * lo + 1] : 0ll;
+    }
+}
 // required edges counted by a distance of NL limbs under REQ: minus its top limb, less the borrow of a negative W-sum in the limbs below
 template <int NL>
 __device__ __forceinline__ int64_t rq_count(const WInt<NL> &d) { return -(int64_t)(d.v[NL - 1] + (d.v[NL - 2] >> 63)); }
@@ -391,12 +404,12 @@ __device__ __forceinline__ long long sw_row(uint32_t sw, const long long *ew, ui
 // the integer of in-edge slot e as the sweep adds it: W, under REQ W - 2^(64 (NL - 1)) for a required row, under BIAS W + B for a biased one
 // (|B| <= 2^52, so ew_decode reads it as the plain integer it is)
 template <int NL, class P>
-__device__ __forceinline__ WInt<NL> sw_weight(uint32_t sw, const long long *ew, uint32_t e, const long long *gt, const uint32_t *req, uint64_t ebase, const uint32_t *bbit = nullptr, const long long *bval = nullptr) {
+__device__ __forceinline__ WInt<NL> sw_weight(uint32_t sw, const long long *ew, uint32_t e, const long long *gt, const uint32_t *req, uint64_t ebase, const uint32_t *bbit = nullptr, const long long *bval = nullptr, const int nbl = 0) {
     if constexpr (!P::REQ && !P::BIAS) return ew_decode<NL>(sw_row<P>(sw, ew, e, gt));
     else {
         WInt<NL> w = ew_decode<NL>(sw_row<P>(sw, ew, e, gt));
         if (rs_required<P>(req, ebase, sw, e)) w.v[NL - 1] -= 1ull;
-        if constexpr (P::BIAS) { if (rs_biased<P>(bbit, ebase, sw, e)) w = wi_add<NL>(w, ew_decode<NL>(bval[ebase + e])); }
+        if constexpr (P::BIAS) { if (rs_biased<P>(bbit, ebase, sw, e)) w = wi_add<NL>(w, ew_decode<NL>(bias_at<P::BLIST>(bval, ebase + e, nbl))); }
         return w;
     }
 }
@@ -405,7 +418,7 @@ __device__ __forceinline__ WInt<NL> sw_weight(uint32_t sw, const long long *ew, 
 // contig; a scenario slot's workgroup passes its slot's contig, phx_resolve.inc): distances to b.dist, lowest-index tight parents to b.parent, then the
 // path and the genes.  V = meta->n_node (the caller has read it; after expand_contig's fence a second read would be a second load).
 template <int NL, class P>
-__device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const uint32_t ci, const int V, const uint32_t *mask, uint8_t *gplan, const uint32_t *req = nullptr, const int kreq = 0, const uint32_t *bbit = nullptr, const long long *bval = nullptr) {
+__device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const uint32_t ci, const int V, const uint32_t *mask, uint8_t *gplan, const uint32_t *req = nullptr, const int kreq = 0, const uint32_t *bbit = nullptr, const long long *bval = nullptr, const int nbl = 0) {
     constexpr int RING = P::RING, ECAP = P::ECAP;
     constexpr int EPT = (ECAP + SW_THREADS - 1) / SW_THREADS; // tile edges prefetched per thread
     extern __shared__ __align__(16) uint8_t smem[];
@@ -539,7 +552,7 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const ui
                         // ring, whose distance cannot change while this window iterates and is folded into the weight)
                         uint32_t sl = RING;
                         if (P::REQ && ((r_mk >> (16 + j)) & 1u)) w.v[NL - 1] -= 1ull; // required: W - M, so the phases pay nothing for it either
-                        if constexpr (P::BIAS) { if ((r_mk >> (16 + j)) & 1u) w = wi_add<NL>(w, ew_decode<NL>(bval[ebase + e0 + i])); } // biased: W + B, likewise
+                        if constexpr (P::BIAS && !P::BLIST) { if ((r_mk >> (16 + j)) & 1u) w = wi_add<NL>(w, ew_decode<NL>(bias_at<false>(bval, ebase + e0 + i, nbl))); } // biased: W + B, likewise
                         if (P::MASKED && ((r_mk >> j) & 1u)) w = big; // refused: no edge (0 + "unreached" never wins), so the phases pay nothing for the mask
                         else if (u != (uint32_t)SRC) {
                             if ((int)u < loaded && (int)u + RING >= loaded) sl = u & (RING - 1);
@@ -547,6 +560,19 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const ui
                         }
                         tsrc[i] = sl;
                         wi_store<NL>(tw + (size_t)i * NL, w);
+                    }
+                }
+                // BLIST: B comes from a search of the slot's list, kept out of the unrolled loop above and done here, where the
+                // prefetched rows are no longer live — a thread with a biased row in its part of the tile (rare: a scenario biases
+                // a few ORFs) adds B to the entry it has just written; a refused row stays no edge
+                if constexpr (P::BLIST) {
+                    if (r_mk >> 16) {
+#pragma nounroll
+                        for (int j = 0; j < EPT; j++) {
+                            const int i = tid + j * SW_THREADS;
+                            if (i < ne && ((r_mk >> (16 + j)) & 1u) && !((r_mk >> j) & 1u))
+                                wi_store<NL>(tw + (size_t)i * NL, wi_add<NL>(wi_load<NL>(tw + (size_t)i * NL), ew_decode<NL>(bias_at<true>(bval, ebase + e0 + i, nbl))));
+                        }
                     }
                 }
             }
@@ -647,7 +673,7 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const ui
                             if (u == (uint32_t)SRC) du = wi_load<NL>(ring + (size_t)RING * NL);
                             else if ((int)u < loaded && (int)u + RING >= loaded) du = wi_load<NL>(ring + (size_t)(u & (RING - 1)) * NL);
                             else du = wi_load<NL>(gdist + (size_t)u * NL);
-                            best = wi_min_bf<NL>(best, wi_add<NL>(du, sw_weight<NL, P>(sw, ew, e0 + i, gt, req, ebase, bbit, bval)));
+                            best = wi_min_bf<NL>(best, wi_add<NL>(du, sw_weight<NL, P>(sw, ew, e0 + i, gt, req, ebase, bbit, bval, nbl)));
                         }
                     }
                     best = wi_row_min<NL>(best, sub);
@@ -690,7 +716,7 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const ui
                 for (uint32_t e = in_off[v] + sub; e < e1; e += SW_LPN) {
                     const uint32_t sw = esrc[e];
                     if (rs_refused<P>(mask, ebase, sw, e)) continue;
-                    const WInt<NL> cand = wi_add<NL>(wi_load<NL>(gdist + (size_t)ESRC_NODE(sw) * NL), sw_weight<NL, P>(sw, ew, e, gt, req, ebase, bbit, bval));
+                    const WInt<NL> cand = wi_add<NL>(wi_load<NL>(gdist + (size_t)ESRC_NODE(sw) * NL), sw_weight<NL, P>(sw, ew, e, gt, req, ebase, bbit, bval, nbl));
                     if (wi_lt_bf<NL>(cand, dv) && !((P::REQ || P::BIAS) && wi_unreached<NL>(cand))) viol = true;
                     if (wi_eq<NL>(cand, dv) && e < be && !wi_unreached<NL>(dv)) be = e;
                 }
