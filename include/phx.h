@@ -43,7 +43,8 @@ extern "C" {
  *        (addition, version unchanged) phx_evidence_flat — likewise;
  *        (additions, version unchanged) phx_scenarios_flat, phx_scenarios_ms, phx_scenario_chunks, phx_tap_scenario_path — probe for the symbol;
  *        (addition, version unchanged) phx_pinned_scenarios_flat — probe for the symbol;
- *        (addition, version unchanged) phx_evidence_scenarios_flat — probe for the symbol */
+ *        (addition, version unchanged) phx_evidence_scenarios_flat — probe for the symbol;
+ *        (additions, version unchanged) phx_remargins_flat, phx_remargins_ms, phx_tap_redist — probe for the symbol */
 #define PHX_MAX_CODONS 16
 
 /* library-level errors */
@@ -460,6 +461,40 @@ int phx_tap_repath(phx_ctx *ctx, int32_t contig, int32_t *path, int32_t cap, int
 /* device time of the last re-annotation (HIP events around device work only), ms[3]: mask build, masked solve, in-order parents + path +
  * genes + the copies to the host.  All 0 before the first. */
 int phx_reannotate_ms(phx_ctx *ctx, float *ms /* [3] */);
+
+/* ---- re-annotation margins: per-ORF path margins under a mask or bias ----
+ * The margins of phx_margins_flat on the graph of the last re-annotation of the batch last run — phx_reannotate_flat or phx_evidence_flat,
+ * or phx_constrain_flat where no ORF is required: how sure every other call is, given this evidence.  For a contig that was solved again
+ * under the refused set F and the bias B, G' = G_{F,B} is the graph of §14 / §19, and
+ *   d_s'(v)  the re-solve's distance source -> v;  R the nodes it reached;
+ *   d_t'(v)  the shortest v -> target distance in the subgraph of G' induced by R, exact, in the contig's limb class; "unreached" when no
+ *            such path exists.  A node outside R is never given a value: a cycle of negative length the source does not reach is none of
+ *            the forward solve's, and a cycle with one node in R lies in R entirely, so the restricted pass settles whenever the solve did;
+ *   D'       = d_s'(target).
+ * For ORF k with edge e = (u -> v) in G':  Delta'(k) = d_s'(u) + W(e) + B(k) + d_t'(v) - D', an integer >= 0; margin = float(Delta') / 1000.0
+ * as phx_margins_flat rounds it, through = 1.  through = 0 and margin = +inf when the ORF is refused, has no edge, u or v is unreached on
+ * its side, or D' is unreached.  called = 1 iff the ORF is among the genes the re-annotation call returns for the contig (the device's
+ * lists; no host re-solve enters).  The smallest further bonus that gets an uncalled ORF called on top of this evidence is its margin here
+ * (§19's theorem on G').  Delta' fits the contig's own limbs: phx_evidence_flat lets a contig through only if the layout's bound on
+ * simple-path sums plus the sum of |B| fits its class with 5 spare bits, and d_s', d_t', |W + B| and D' each obey that bound.
+ * Records as phx_margins_flat (rec == NULL: size query; phx_tap_orfs order).  status[i]:
+ *   a run error (< 0) or PHX_S_OVERFLOW without device distances: that status, no records (as phx_margins_flat);
+ *   a contig that was not solved again: phx_margins_flat's status and records, with `called` as above;
+ *   solved again with a status < 0 (PHX_S_NEGCYCLE, PHX_S_OVERFLOW from the biased bound): that status, no records;
+ *   solved again, PHX_S_NOPATH: status 1, every record through = 0 and +inf;  solved again, status 0: the records as defined.
+ *   PHX_S_NEGCYCLE (no records) also if the reverse pass hits its caps (the lemma above says it never does; the caps stay).
+ * PHX_E_STATE, before any kernel, without a re-annotation of this run, and when a contig of the last one was solved under the required
+ * policy (margins under an infinite bonus are a different definition).  Computed at the first call after a re-annotation solve (on top
+ * of phx_margins_flat's shared part), kept until the next solve or run; a re-annotation call that hits its cache keeps it.  Nothing the
+ * other entry points return changes.  (Additions, version unchanged: probe for the symbol.) */
+int phx_remargins_flat(phx_ctx *ctx, phx_orf_margin *rec, int64_t cap, int64_t *offsets /* [n+1] */, int32_t *status /* [n] */, int64_t *total);
+/* device time of the last computation of the re-annotation margins (HIP events), ms[4]: apply (the refused / biased out-edges), the
+ * conditioned reverse pass, records, the copy to the host.  All 0 before the first. */
+int phx_remargins_ms(phx_ctx *ctx, float *ms /* [4] */);
+/* d_s' (which 0) or d_t' (which 1) of every node of a contig of the last re-annotation, like phx_tap_dist (sssp_nl words per node; an
+ * unreached node has a top word >= 2^61).  A contig that was not solved again: the run's vectors (phx_tap_dist / phx_tap_dist_target);
+ * one whose re-solve left no such vector (an error; no path for d_t'): every node unreached.  PHX_E_STATE as phx_remargins_flat. */
+int phx_tap_redist(phx_ctx *ctx, int32_t contig, int32_t which, uint64_t *dist_limbs, int64_t cap_words);
 
 /* ---- scenario batches: many masked re-annotations of the batch last run in one call ----
  * n_scen scenarios, each a contig of the batch last run and a set F of its ORFs, solved side by side on the resident graph, one

@@ -876,6 +876,48 @@ class Annotator:
             v -= 1 << (64 * nl)
         return p[: n.value].copy(), v
 
+    def remargins(self):
+        """(status int32[n], offsets int64[n+1], records structured array[total] of _lib.MARGIN_DT), as margins() returns them: the path
+        margin of every CDS ORF on the graph of the last reannotate() or evidence() (or constrain() without required ORFs) of the batch
+        last run (phx_remargins_flat).  margin = float(d_s'(u) + W + B + d_t'(v) - D') / 1000 on the refused / biased graph:
+        0 for the ORFs the re-annotation calls, the smallest further bonus that gets an uncalled ORF called, +inf with through = 0 for a
+        refused ORF and where no path runs through the ORF.  called = 1 for the genes the re-annotation returned.  A contig that was not
+        solved again has the records of margins().  PhxError (PHX_E_STATE) without a re-annotation of this run and after constrain()
+        with required ORFs."""
+        n = self.n
+        offs = np.zeros(n + 1, np.int64)
+        status = np.zeros(max(n, 1), np.int32)
+        total = C.c_int64(0)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._chk(self.L.phx_remargins_flat(self.h, None, 0, vp(offs), vp(status), C.byref(total)), "phx_remargins_flat")
+        rec = np.empty(max(int(total.value), 1), _lib.MARGIN_DT)
+        self._chk(self.L.phx_remargins_flat(self.h, vp(rec), len(rec), vp(offs), vp(status), C.byref(total)), "phx_remargins_flat")
+        return status[:n], offs, rec[: int(total.value)]
+
+    def remargins_ms(self):
+        """Device time of the last re-annotation margins in ms: apply, conditioned reverse pass, records, copy to the host (phx_remargins_ms)."""
+        ms = (C.c_float * 4)()
+        self._chk(self.L.phx_remargins_ms(self.h, ms), "phx_remargins_ms")
+        return dict(zip(("apply", "reverse", "margins", "download"), [float(x) for x in ms]))
+
+    def redist(self, i, to_target=False):
+        """Exact distances of every node of contig i on the last re-annotation's graph as python ints (None: unreached), device node
+        order: d_s' from the source, or with to_target d_t' to the target within the nodes the re-solve reached (phx_tap_redist).  A
+        contig that was not solved again gives dist(i) / dist_to_target(i)."""
+        g = self.globals(i)
+        nl, V = max(g.n_limbs, 1), max(g.n_node, 0)
+        a = np.zeros((max(V, 1), nl), np.uint64)
+        self._chk(self.L.phx_tap_redist(self.h, i, 1 if to_target else 0, a.ctypes.data_as(C.c_void_p), a.size), "phx_tap_redist")
+        out = []
+        for v in range(V):
+            x = 0
+            for k in range(nl):
+                x |= int(a[v, k]) << (64 * k)
+            if x >> (64 * nl - 1):
+                x -= 1 << (64 * nl)
+            out.append(None if x >= 1 << (64 * nl - 3) else x)
+        return out
+
     def reannotate_ms(self):
         """Device time of the last re-annotation in ms: mask build, masked solve, path + genes + copy (phx_reannotate_ms)."""
         ms = (C.c_float * 3)()

@@ -50,6 +50,7 @@ def get_args(argv=None):
     p.add_argument("--evidence", metavar="FILE", default=None, help="per-ORF bonuses and penalties for a second annotation (DESIGN.md §19), in the format of --forbid with a fifth column BIAS: a finite number of SCORE units added to the ORF's weight (negative: support; an ORF named twice gets the sum); alone or with --forbid, not with --require; needs --reannotation, whose #delta: may then be negative")
     p.add_argument("--evidence-scan", metavar=("FILE", "OUT"), nargs=2, default=None, help="also take every line of FILE (the format of --evidence) on its own: write to OUT, per line, the cost and the effect of the best annotation under that one bias (DESIGN.md §20); independent of --evidence / --reannotation")
     p.add_argument("--reannotation", metavar="OUT", default=None, help="write the annotation without the ORFs of --forbid (keeping those of --require, or under the biases of --evidence) to OUT: the tabular block of every contig with a #delta: header line")
+    p.add_argument("--remargins", metavar="FILE", default=None, help="also write every ORF with its path margin on the graph of the second annotation (under --forbid / --evidence; DESIGN.md §21) to FILE, in the format of --margins; needs --reannotation, not with --require")
     p.add_argument("--single-device-ranks", action="store_true", help=argparse.SUPPRESS)  # tests: every rank of a sharded launch on GPU `--device` (gloo-only group)
     args = p.parse_args(argv)
     if args.margins is not None and args.dump:
@@ -82,6 +83,16 @@ def get_args(argv=None):
         p.error("argument --evidence-scan: not available under a multi-rank launch")
     if args.evidence_scan is not None and int(args.gpus) > 1:  # the scenarios work on the batch resident on one context
         p.error("argument --evidence-scan: not available with --gpus above 1")
+    if args.remargins is not None and args.dump:
+        p.error("argument --remargins: not allowed with argument -d/--dump")
+    if args.remargins is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        p.error("argument --remargins: not available under a multi-rank launch")
+    if args.remargins is not None and int(args.gpus) > 1:  # the re-annotation works on the batch resident on one context
+        p.error("argument --remargins: not available with --gpus above 1")
+    if args.remargins is not None and args.require is not None:  # (margins under required ORFs: DESIGN.md §21, Limits)
+        p.error("argument --remargins: not allowed with argument --require")
+    if args.remargins is not None and args.reannotation is None:
+        p.error("argument --remargins: needs --reannotation")
     for flag, val in (("--forbid", args.forbid), ("--require", args.require), ("--evidence", args.evidence), ("--reannotation", args.reannotation)):
         if val is not None and args.dump:
             p.error("argument %s: not allowed with argument -d/--dump" % flag)
@@ -483,6 +494,7 @@ def main(argv=None):
     start_parts = []  # --start-drops: (status, offsets, records) of every batch, in order
     alt_parts = []  # --alt-starts: the same of Annotator.alt_starts()
     reann_parts = []  # --reannotation: (status, offsets, genes, delta[, unmet]) of every batch, in order
+    remargin_parts = []  # --remargins: (status, offsets, records) of Annotator.remargins() of every batch, in order
     scan_parts = []  # --evidence-scan: (status, offsets, records) of Annotator.evidence_scan() of every batch, in order
     forbid_entries = require_entries = evidence_entries = scan_entries = None
     try:
@@ -556,6 +568,8 @@ def main(argv=None):
                     reann_parts.append(ann.reannotate(refused))
                 else:
                     reann_parts.append(ann.constrain(refused, resolve_forbid([e for e in require_entries if e[3] in here], names, ann.orf_index, "--require")))
+                if args.remargins is not None:  # (behind the batch's re-annotation: the margins are that solve's)
+                    remargin_parts.append(ann.remargins())
                 t_parts["upload_s"] += t1 - t0; t_parts["run_s"] += t2 - t1; t_parts["download_s"] += t3 - t2
         elif len(cuts) == 1 and n_gpu == 1:
             lo, hi = cuts[0]
@@ -646,6 +660,12 @@ def main(argv=None):
             m_records = np.concatenate([m[2] for m in margin_parts])
             with open(args.margins, "wb") as fh:
                 fh.write(format_margins(fa.names, m_status, m_offsets, m_records))
+        if args.remargins is not None:
+            x_status = np.concatenate([m[0] for m in remargin_parts])
+            x_counts = np.concatenate([np.diff(m[1]) for m in remargin_parts])
+            x_offsets = np.concatenate([[0], np.cumsum(x_counts)]).astype(np.int64)
+            with open(args.remargins, "wb") as fh:
+                fh.write(format_margins(fa.names, x_status, x_offsets, np.concatenate([m[2] for m in remargin_parts])))
         if args.drop_margins is not None:
             d_status = np.concatenate([m[0] for m in drop_parts])
             d_counts = np.concatenate([np.diff(m[1]) for m in drop_parts])

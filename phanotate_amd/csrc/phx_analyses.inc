@@ -1,4 +1,4 @@
-// phx_analyses.inc — the analyses of a finished run: per-ORF margins, gene drop margins, drop replacements, masked re-annotation.
+// phx_analyses.inc — the analyses of a finished run: per-ORF margins, gene drop margins, drop replacements, masked re-annotation and its margins.
 // Host code, included by phx_api.cpp inside its extern "C" block, behind the taps.  Each analysis is an ensure_* that computes once per
 // run on the context's stream (outside the captured run graph) and an entry point that lays the records out for the caller.
 
@@ -682,6 +682,7 @@ static int reann_flat(phx_ctx *c, const char *who, bool need_forbid, const uint8
     }
     if (!(c->done.reann && c->h_qflags == flags && c->h_qforb == code && c->h_qbias == bcur)) {
         c->done.reann = false;
+        c->done.remarg = false; // (the re-annotation margins are this solve's)
         c->h_qsel.assign((size_t)c->n, 0);
         c->h_qnreq.assign((size_t)c->n, 0);
         for (int i = 0; i < c->n; i++) {
@@ -783,6 +784,149 @@ int phx_tap_repath(phx_ctx *c, int32_t contig, int32_t *path, int32_t cap, int32
 int phx_reannotate_ms(phx_ctx *c, float *ms) {
     if (!c || !ms) return PHX_E_ARG;
     for (int k = 0; k < 3; k++) ms[k] = c->reann_ms[k];
+    return PHX_OK;
+}
+
+// ---- re-annotation margins (phx_margins.inc, DESIGN.md §21): per-ORF path margins on the last re-annotation's graph G_{F,B} ----
+// PHX_OK when the context holds a re-annotation the margins are defined for
+#define WINF_TOP_HOST 0x7fffffffffffffffull // the solver's "unreached" top limb (WINF_TOP, phx_sssp.inc)
+static int remarg_state(phx_ctx *c, const char *who) {
+    if (!c->done.reann) { c->err = std::string(who) + ": no re-annotation of this run (call phx_reannotate_flat or phx_evidence_flat first)"; return PHX_E_STATE; }
+    for (int i = 0; i < c->n; i++)
+        if (c->h_qsel[(size_t)i] == 2) { c->err = std::string(who) + ": the last re-annotation solved a contig under the required policy; margins under required ORFs are not defined here"; return PHX_E_STATE; }
+    return PHX_OK;
+}
+
+// The records of every ORF of the contigs that were solved again (device order) into c->h_xrec and the pass's verdicts into c->xmstat, once
+// per re-annotation solve, on top of ensure_margins: that gives the out-edge CSR, the run's records for the contigs that were not solved
+// again and the run's mstat.  Reads what the solve left resident (b_qforb, b_qbias, b_qmask, b_qbval, b_qdist: nothing between a
+// re-annotation and this call writes them — only reann_compute does, and the scenario batches own b_sc_*); writes only b_x*.
+static int ensure_remargins(phx_ctx *c) {
+    if (c->done.remarg) return PHX_OK;
+    { const int rm = ensure_margins(c); if (rm) return rm; }
+    const size_t n = (size_t)c->n, V = (size_t)c->tot_node, E = (size_t)c->tot_edge, N = (size_t)c->tot_orf;
+    const size_t limbs = (size_t)std::max(c->n_limbs, 2);
+    const size_t mw = E / 32 + 2; // words of one bitmap over the out-edge positions
+    int rev_nlm = 0, rec_nlm = 0;
+    bool biased = false;
+    c->h_xsel.assign(n + 1, 0);
+    c->xmstat.assign(n + 1, 0);
+    for (size_t i = 0; i < n; i++) {
+        if (!c->h_qsel[i] || !reann_contig(c, (int)i)) continue;
+        const int32_t st = c->h_qrec[i].status;
+        if (st < 0) continue;
+        c->h_xsel[i] = st == 0 ? 1 : 2; // (PHX_S_NOPATH: records only, D' is unreached)
+        rec_nlm |= nl_class_bit(c->meta[i].sssp_nl);
+        if (st == 0) { rev_nlm |= nl_class_bit(c->meta[i].sssp_nl); biased = biased || c->h_qsel[i] == 3; }
+    }
+    for (int k = 0; k < 4; k++) c->remarg_ms[k] = 0;
+    if (!rec_nlm) { c->done.remarg = true; return PHX_OK; }
+    int rc;
+    if ((rc = ensure(c, c->b_xsel, (n + 1) * 4)) || (rc = ensure(c, c->b_xbit, 2 * mw * 4)) || (biased && (rc = ensure(c, c->b_xbval, (E + 1) * 8))) ||
+        (rc = ensure(c, c->b_xdt, (V + 1) * limbs * 8)) || (rc = ensure(c, c->b_xrec, (N + 1) * sizeof(phx_orf_margin))) || (rc = ensure(c, c->b_xmstat, (n + 1) * 4)))
+        return rc;
+    if ((rc = analysis_events(c))) return rc;
+    try { c->h_xrec.resize(N + 1); } catch (const std::bad_alloc &) { c->err = "out of memory in phx_remargins_flat"; return PHX_E_NOMEM; }
+    DBatch b;
+    fill_batch(c, &b);
+    DMarg g;
+    margins_args(c, &g);
+    DBatch qb;
+    DReann q;
+    reann_batch(c, &qb, &q);
+    DRmarg r;
+    r.sel = (const int32_t *)c->b_xsel.p; r.ds = (const uint64_t *)c->b_qdist.p; r.ds_stride = c->qstride;
+    r.fbit = (uint32_t *)c->b_xbit.p; r.bbit = r.fbit + mw; r.bval = (long long *)c->b_xbval.p;
+    r.dist_t = (uint64_t *)c->b_xdt.p; r.rec = (phx_orf_margin *)c->b_xrec.p; r.mstat = (int32_t *)c->b_xmstat.p;
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipMemcpyAsync(c->b_xsel.p, c->h_xsel.data(), (n + 1) * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipEventRecord(c->aev[0], s));
+    HIPCHK(c, hipMemsetAsync(c->b_xbit.p, 0, 2 * mw * 4, s));
+    HIPCHK(c, hipMemsetAsync(c->b_xmstat.p, 0, (n + 1) * 4, s));
+    if (rev_nlm) phxk_remarg_apply(&b, &g, &q, &r, s);
+    HIPCHK(c, hipEventRecord(c->aev[1], s));
+    if (rev_nlm) phxk_remarg_rev(&b, &g, &q, &r, rev_nlm, s);
+    HIPCHK(c, hipEventRecord(c->aev[2], s));
+    phxk_remarg_records(&b, &g, &q, &r, rec_nlm, s);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->aev[3], s));
+    if (N) HIPCHK(c, hipMemcpyAsync(c->h_xrec.data(), c->b_xrec.p, N * sizeof(phx_orf_margin), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(c->xmstat.data(), c->b_xmstat.p, n * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipEventRecord(c->aev[4], s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    for (int k = 0; k < 4; k++) c->remarg_ms[k] = ev_ms(c->aev[k], c->aev[k + 1]);
+    c->done.remarg = true;
+    return PHX_OK;
+}
+
+// status of contig i's re-annotation margins (include/phx.h)
+static int32_t remargins_status(const phx_ctx *c, int i) {
+    if (!c->h_qsel[(size_t)i]) return margins_status(c, i);
+    const int32_t r = c->res[(size_t)i].status;
+    if (r < 0) return r;
+    const int32_t q = c->h_qrec[(size_t)i].status;
+    if (q != 0) return q;
+    return c->xmstat[(size_t)i] ? PHX_S_NEGCYCLE : 0;
+}
+
+int phx_remargins_flat(phx_ctx *c, phx_orf_margin *rec, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
+    if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
+    { const int ra = after_run(c); if (ra) return ra; }
+    { const int rs = remarg_state(c, "phx_remargins_flat"); if (rs) return rs; } // before any kernel
+    { const int rm = ensure_remargins(c); if (rm) return rm; }
+    try {
+    int64_t total = 0;
+    for (int i = 0; i < c->n; i++) { offsets[i] = total; status[i] = remargins_status(c, i); if (status[i] >= 0) total += c->meta[(size_t)i].n_orf; }
+    offsets[c->n] = total;
+    if (total_out) *total_out = total;
+    if (!rec) return PHX_OK; // size query
+    if (cap < total) return PHX_E_ARG;
+    { const int rg = stage_run_genes(c, c->h_qsel.data()); if (rg) return rg; } // (of the contigs that were not solved again)
+    { const int rg = ensure_grp_host(c); if (rg) return rg; }
+    std::vector<uint64_t> keys;
+    std::vector<int> order;
+    for (int i = 0; i < c->n; i++) {
+        if (status[i] < 0) continue;
+        // `called`: the genes the re-annotation call returns for the contig — the device's lists, no host re-solve enters
+        const bool again = c->h_qsel[(size_t)i] != 0;
+        const DGene *src = again ? c->h_qgenes.data() + c->h_qrec[(size_t)i].gene_off : (const DGene *)c->h_genes.p + (size_t)c->res[(size_t)i].gene_off;
+        const int64_t ng = again ? (int64_t)c->h_qrec[(size_t)i].n_genes : (int64_t)std::max(c->res[(size_t)i].n_genes, 0);
+        keys.clear();
+        for (int64_t k = 0; k < ng; k++) if (src[k].frame >= -3 && src[k].frame <= 3) keys.push_back(gene_key(src[k].left, src[k].right, src[k].strand));
+        std::sort(keys.begin(), keys.end());
+        phx_orf_margin *dst = rec + offsets[i];
+        const phx_orf_margin *from = (again ? c->h_xrec.data() : (const phx_orf_margin *)c->h_mrec.p) + c->meta[(size_t)i].orf_off;
+        each_group_in_reference_order(c, (size_t)i, order, [&](int32_t first, int32_t k) {
+            if (k > 0) memcpy(dst, from + first, sizeof(phx_orf_margin) * (size_t)k);
+            dst += k;
+        });
+        for (int64_t k = offsets[i]; k < offsets[i + 1]; k++) rec[k].called = is_called(keys, rec[k].left, rec[k].right, rec[k].strand) ? 1 : 0;
+    }
+    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_remargins_flat"; return PHX_E_NOMEM; }
+    return PHX_OK;
+}
+
+int phx_tap_redist(phx_ctx *c, int32_t contig, int32_t which, uint64_t *dist_limbs, int64_t cap_words) {
+    TAP_PRE(c, contig);
+    if (which != 0 && which != 1) return PHX_E_ARG;
+    { const int rs = remarg_state(c, "phx_tap_redist"); if (rs) return rs; }
+    if (!c->h_qsel[(size_t)contig]) return which ? phx_tap_dist_target(c, contig, dist_limbs, cap_words) : phx_tap_dist(c, contig, dist_limbs, cap_words); // the run's vectors stand
+    const size_t nl = (size_t)m.sssp_nl, words = (size_t)m.n_node * nl;
+    if (!dist_limbs || cap_words < (int64_t)words) return PHX_E_ARG;
+    if (which) { const int rm = ensure_remargins(c); if (rm) return rm; }
+    const bool have = which ? (c->h_xsel[(size_t)contig] == 1 && !c->xmstat[(size_t)contig]) : c->h_qrec[(size_t)contig].status >= 0;
+    if (!have) { // no such vector (the re-solve ended with an error; no path, so no d_t'): every node unreached
+        for (size_t v = 0; v < (size_t)m.n_node; v++) for (size_t k = 0; k < nl; k++) dist_limbs[v * nl + k] = k + 1 == nl ? WINF_TOP_HOST : 0;
+        return PHX_OK;
+    }
+    const uint64_t *from = which ? (const uint64_t *)c->b_xdt.p + (size_t)m.node_off * (size_t)c->n_limbs : (const uint64_t *)c->b_qdist.p + (size_t)m.node_off * (size_t)c->qstride;
+    HIPCHK(c, hipMemcpy(dist_limbs, from, words * 8, hipMemcpyDeviceToHost));
+    return PHX_OK;
+}
+
+int phx_remargins_ms(phx_ctx *c, float *ms) {
+    if (!c || !ms) return PHX_E_ARG;
+    for (int k = 0; k < 4; k++) ms[k] = c->remarg_ms[k];
     return PHX_OK;
 }
 

@@ -458,6 +458,20 @@ struct DScen {
     int64_t n_trip;
 };
 
+// Re-annotation margins (phx_margins.inc), on demand after a re-annotation: the context's lazily allocated buffers.  The
+// kernels read the run's DBatch and DMarg (graph, out-edge CSR) and what the re-annotation left resident (DReann); they write only here.
+struct DRmarg {
+    const int32_t *sel;    // per contig: 1 = solved again with status 0 (apply, reverse pass, records), 2 = solved again without a path (records only), 0 = not covered
+    const uint64_t *ds;    // the re-solve's distances d_s' (the re-annotation's dist buffer), ds_stride words per node reserved, the contig's limbs per node used
+    int32_t ds_stride;
+    uint32_t *fbit;        // one bit per out-edge position of the batch (bit edge_off + e, the CSR's order): refused; cleared per call
+    uint32_t *bbit;        // likewise: the position carries a bias
+    long long *bval;       // per out-edge position: B; never cleared, read only where the position's bit is set in bbit
+    uint64_t *dist_t;      // d_t' of every node, laid out like DMarg.dist_t
+    phx_orf_margin *rec;   // per ORF (at orf_off, device order); `called` is set on the host
+    int32_t *mstat;        // per contig: 1 the conditioned reverse pass hit its caps; zeroed by the host
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -511,6 +525,9 @@ void phxk_reann_finish(const DBatch *b, const DReann *q, int nl_mask, int pin_ma
 void phxk_evid_mask(const DBatch *b, const DReann *q, void *stream);                // evidence-weighted re-annotation (§19): the biased ORFs' words, bits and sums,
 void phxk_evid_solve(const DBatch *b, const DReann *q, int ev_mask, void *stream);  //   the sweep under the bias policy (ev_mask: the classes with biased ORFs),
 void phxk_evid_finish(const DBatch *b, const DReann *q, int ev_mask, void *stream); //   in-order parents on G_{F,B}, path, genes, delta
+void phxk_remarg_apply(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, void *stream);               // re-annotation margins (§21; b: the run's batch): the refused / biased out-edge positions,
+void phxk_remarg_rev(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, int nl_mask, void *stream);     //   the conditioned reverse pass (nl_mask: the classes among DRmarg.sel == 1),
+void phxk_remarg_records(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, int nl_mask, void *stream); //   the ORF records (nl_mask: the classes among DRmarg.sel != 0)
 void phxk_scen_mask(const DBatch *b, const DScen *q, void *stream);                 // scenario batches (phx_resolve.inc): the slots' records and bitmap slices (b: the run's batch),
 void phxk_scen_solve(const DBatch *b, const DScen *q, int nl_mask, void *stream);   //   the masked sweep, a workgroup per slot (b: the run's graph, tot / genes / gene_total / tie the scenarios' own),
 void phxk_scen_finish(const DBatch *b, const DScen *q, int nl_mask, void *stream);  //   in-order parents, path, genes, delta per slot

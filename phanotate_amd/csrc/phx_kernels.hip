@@ -381,6 +381,17 @@ void phxk_margins_transpose(const DBatch *b, const DMarg *g, void *stream) {
     } while (0)
 void phxk_sssp_rev(const DBatch *b, const DMarg *g, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH(k_sssp_rev, nl_mask, dim3(b->n_contig), dim3(NT), *b, *g); }
 void phxk_margins(const DBatch *b, const DMarg *g, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH(k_margins, nl_mask, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), *b, *g); }
+// re-annotation margins (phx_margins.inc, §21): k_sssp_rev and k_margins under MgCond, whose DMarg part is the run's (the out-edge CSR)
+static MgCond mg_cond_args(const DMarg *g, const DReann *q, const DRmarg *r) { MgCond c; static_cast<DMarg &>(c) = *g; c.q = *q; c.r = *r; return c; }
+#define NL_LAUNCH_COND(K, NLM, GRID, BLOCK, ...) do { \
+        if ((NLM) & 1) hipLaunchKernelGGL((K<2, MgCond>), GRID, BLOCK, 0, s, __VA_ARGS__); \
+        if ((NLM) & 2) hipLaunchKernelGGL((K<4, MgCond>), GRID, BLOCK, 0, s, __VA_ARGS__); \
+        if ((NLM) & 4) hipLaunchKernelGGL((K<8, MgCond>), GRID, BLOCK, 0, s, __VA_ARGS__); \
+        if ((NLM) & 8) hipLaunchKernelGGL((K<17, MgCond>), GRID, BLOCK, 0, s, __VA_ARGS__); \
+    } while (0)
+void phxk_remarg_apply(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, void *stream) { hipLaunchKernelGGL(k_rmg_apply, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), 0, (hipStream_t)stream, *b, *g, *q, *r); }
+void phxk_remarg_rev(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH_COND(k_sssp_rev, nl_mask, dim3(b->n_contig), dim3(NT), *b, mg_cond_args(g, q, r)); }
+void phxk_remarg_records(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH_COND(k_margins, nl_mask, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), *b, mg_cond_args(g, q, r)); }
 // gene drop margins (phx_drop.inc): a workgroup per contig, one launch per limb class and step
 void phxk_drop_trees(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH(k_dp_tree, nl_mask, dim3(b->n_contig), dim3(NT), *b, *g, *q); }
 void phxk_drop_cand(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH(k_dp_cand, nl_mask, dim3(b->n_contig), dim3(NT), *b, *g, *q); }

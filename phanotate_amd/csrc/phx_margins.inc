@@ -1,4 +1,4 @@
-// phx_margins.inc — per-ORF path margins: the out-edge CSR, k_sssp_rev<NL> and k_margins (included by phx_kernels.hip).
+// phx_margins.inc — per-ORF path margins: the out-edge CSR, k_sssp_rev<NL> and k_margins; the re-annotation margins: k_rmg_apply and both under MgCond (included by phx_kernels.hip).
 // ------------------------------------------------------------------------------------------------
 // On demand after a run (phx_margins_flat / phx_tap_dist_target), never inside it.  With d_s the distances the run left in DBatch.dist
 // and d_t(v) the exact distance from v TO the target, an ORF edge e = (u -> v) of weight W gets
@@ -73,26 +73,51 @@ __global__ __launch_bounds__(NT) void k_mg_fill(DBatch b, DMarg g) {
 // the fixed point of min-plus relaxation, which is the exact distance vector (the values are lengths of walks to the target throughout).
 // No parents, no tie rule: only the values are asked for.  Bounds like k_sssp: a chunk that does not settle in NT + 8 rounds, or more than
 // V + 2 sweeps, is a cycle of negative length (DMarg.mstat = 1: the host reports PHX_S_NEGCYCLE for the contig's margins).
+
+// The policy of k_sssp_rev and k_margins is the type of their second argument.  DMarg: the run's graph, the kernels as §11 describes them.
+// MgCond (the re-annotation margins, DESIGN.md §21): the graph G' = G_{F,B} of the last re-annotation, restricted to R, the nodes its solve
+// reached.  Everything the policy adds sits behind if constexpr (mg_cond<G>): the DMarg instantiations are the code they were without it.
+//   k_sssp_rev  `r.ds` holds the re-solve's d_s' (the contig's NL limbs per node); a node outside R is never relaxed and so never gets a
+//               value — the reverse counterpart of §16's "an unreached node is never relaxed", which lets the pass settle whenever the
+//               forward solve did (a cycle with one node in R lies in R entirely).  Out-edge position e of the batch (edge_off + e, the
+//               CSR's own order) is skipped where its bit is set in r.fbit (refused) and weighs W + B where it is set in r.bbit
+//               (B = r.bval[edge_off + e], |B| <= 2^52: ew_decode reads it as the plain integer it is).  Values go to r.dist_t, the
+//               verdict to r.mstat; the run's dist_t / mstat (shared with §12 / §13) are not touched.  Contigs: r.sel == 1.
+//   k_margins   d_s' from r.ds, d_t' from r.dist_t, D' = d_s'(target); the ORF's in-edge slot is tested in DReann.mask (refused: through =
+//               0) and, for a contig solved under the bias policy (DReann.evs), carries DReann.bval where its bit is set in DReann.bbit.
+//               Contigs: r.sel != 0 whose reverse pass settled (sel 2 — the re-solve found no path —: D' is unreached, every record through = 0).
+struct MgCond : DMarg { DReann q; DRmarg r; };
+template <class G> constexpr bool mg_cond = !std::is_same<G, DMarg>::value;
+__device__ __forceinline__ bool mg_bit(const uint32_t *bits, uint64_t x) { return (bits[x >> 5] >> (x & 31)) & 1u; } // bit x of a bitmap over the batch's edges
 __device__ __forceinline__ int mg_node(int i, int V) { return i == 0 ? V - 1 : (i == V - 1 ? V - 2 : V - 2 - i); } // sweep index -> node id
 __device__ __forceinline__ int mg_idx(int v, int V) { return v == V - 1 ? 0 : (v == V - 2 ? V - 1 : V - 2 - v); }  // node id -> sweep index
-template <int NL>
-__global__ __launch_bounds__(NT) void k_sssp_rev(DBatch b, DMarg g) {
+template <int NL, class G = DMarg>
+__global__ __launch_bounds__(NT) void k_sssp_rev(DBatch b, G g) {
+    constexpr bool COND = mg_cond<G>;
     __shared__ int s_flag[2];
     __shared__ int s_hi, s_lo_next, s_hi_next;
     __shared__ uint64_t s_d[NT * NL]; // the current chunk's values, by sweep index - c0
     const DMeta *meta = &b.meta[blockIdx.x];
     if (!mg_contig(meta) || meta->sssp_nl != NL) return;
+    if constexpr (COND) { if (g.r.sel[blockIdx.x] != 1) return; }
     const int V = meta->n_node, TGT = V - 1;
     const uint32_t *oo = g.out_off + meta->node_off + blockIdx.x;
     const uint32_t *od = g.out_dst + meta->edge_off;
     const long long *ow = g.out_w + meta->edge_off;
     const uint32_t *in_off = b.in_off + meta->node_off + blockIdx.x;
     const uint32_t *esrc = b.esrc + meta->edge_off;
-    uint64_t *dt = g.dist_t + (size_t)meta->node_off * b.dist_stride;
+    uint64_t *dt;
+    if constexpr (COND) dt = g.r.dist_t + (size_t)meta->node_off * b.dist_stride;
+    else dt = g.dist_t + (size_t)meta->node_off * b.dist_stride;
+    [[maybe_unused]] const uint64_t *ds = nullptr;
+    [[maybe_unused]] const uint64_t ebase = (uint64_t)meta->edge_off;
+    if constexpr (COND) ds = g.r.ds + (size_t)meta->node_off * g.r.ds_stride;
     const int tid = threadIdx.x;
     for (int v = tid; v < V; v += NT) {
         WInt<NL> d = wi_inf<NL>();
-        if (v == TGT) {
+        bool zero = v == TGT;
+        if constexpr (COND) zero = zero && !wi_unreached<NL>(wi_load<NL>(ds + (size_t)v * NL)); // (the target outside R: nothing gets a value)
+        if (zero) {
 #pragma unroll
             for (int i = 0; i < NL; i++) d.v[i] = 0;
         }
@@ -107,7 +132,16 @@ __global__ __launch_bounds__(NT) void k_sssp_rev(DBatch b, DMarg g) {
             const int i = c0 + tid;
             const int v = i < V ? mg_node(i, V) : -1;
             const bool relax = v >= 0 && v != TGT;
-            const uint32_t e0 = relax ? oo[v] : 0u, e1 = relax ? oo[v + 1] : 0u;
+            uint32_t e0 = relax ? oo[v] : 0u, e1 = relax ? oo[v + 1] : 0u;
+            // COND: a node outside R never gets a value (it keeps no out-edges here); `special`: some out-edge position in the bitmap words
+            // that cover the node's range is refused or biased — only then are the bitmaps read per edge (the refused and biased edges
+            // of a re-annotation are a handful per contig, so nearly every node takes the loops as the plain pass has them)
+            [[maybe_unused]] bool special = false;
+            if constexpr (COND) {
+                if (relax && wi_unreached<NL>(wi_load<NL>(ds + (size_t)v * NL))) e1 = e0;
+                if (e1 > e0)
+                    for (uint64_t x = (ebase + e0) >> 5, x1 = (ebase + e1 - 1) >> 5; x <= x1; x++) special = special || (g.r.fbit[x] | g.r.bbit[x]) != 0u;
+            }
             // nothing outside the chunk changes while it iterates: the out-edges that leave it are folded in once, the ones inside it
             // read the chunk's values from LDS
             WInt<NL> cur = wi_inf<NL>();
@@ -116,9 +150,11 @@ __global__ __launch_bounds__(NT) void k_sssp_rev(DBatch b, DMarg g) {
             for (uint32_t e = e0; e < e1; e++) {
                 const uint32_t p = (uint32_t)(mg_idx((int)od[e], V) - c0);
                 if (p < (uint32_t)NT) continue;
+                if constexpr (COND) { if (special && mg_bit(g.r.fbit, ebase + e)) continue; }
                 const WInt<NL> dv = wi_load<NL>(dt + (size_t)od[e] * NL);
                 if (wi_is_inf<NL>(dv)) continue;
-                const WInt<NL> cand = wi_add<NL>(dv, ew_decode<NL>(ow[e]));
+                WInt<NL> cand = wi_add<NL>(dv, ew_decode<NL>(ow[e]));
+                if constexpr (COND) { if (special && mg_bit(g.r.bbit, ebase + e)) cand = wi_add<NL>(cand, ew_decode<NL>(g.r.bval[ebase + e])); }
                 if (wi_lt<NL>(cand, best)) best = cand;
             }
             wi_store<NL>(s_d + (size_t)tid * NL, best);
@@ -130,9 +166,11 @@ __global__ __launch_bounds__(NT) void k_sssp_rev(DBatch b, DMarg g) {
                 for (uint32_t e = e0; e < e1; e++) {
                     const uint32_t p = (uint32_t)(mg_idx((int)od[e], V) - c0);
                     if (p >= (uint32_t)NT) continue;
+                    if constexpr (COND) { if (special && mg_bit(g.r.fbit, ebase + e)) continue; }
                     const WInt<NL> dv = wi_load<NL>(s_d + (size_t)p * NL);
                     if (wi_is_inf<NL>(dv)) continue;
-                    const WInt<NL> cand = wi_add<NL>(dv, ew_decode<NL>(ow[e]));
+                    WInt<NL> cand = wi_add<NL>(dv, ew_decode<NL>(ow[e]));
+                    if constexpr (COND) { if (special && mg_bit(g.r.bbit, ebase + e)) cand = wi_add<NL>(cand, ew_decode<NL>(g.r.bval[ebase + e])); }
                     if (wi_lt<NL>(cand, best)) { best = cand; improved = true; }
                 }
                 __syncthreads(); // every read of this iteration is done
@@ -165,7 +203,8 @@ __global__ __launch_bounds__(NT) void k_sssp_rev(DBatch b, DMarg g) {
         __syncthreads();
         if (++sweeps > V + 2) { bad = true; break; }
     }
-    if (tid == 0 && bad) g.mstat[blockIdx.x] = 1;
+    if constexpr (COND) { if (tid == 0 && bad) g.r.mstat[blockIdx.x] = 1; }
+    else { if (tid == 0 && bad) g.mstat[blockIdx.x] = 1; }
 }
 
 // ---- k_margins: one thread per ORF (its start node, LINK_START) ----
@@ -202,10 +241,12 @@ __device__ __forceinline__ double wi_to_double_rn(WInt<NL> x) {
     return neg ? -r : r;
 }
 
-template <int NL>
-__global__ __launch_bounds__(NT) void k_margins(DBatch b, DMarg g) {
+template <int NL, class G = DMarg>
+__global__ __launch_bounds__(NT) void k_margins(DBatch b, G g) {
+    constexpr bool COND = mg_cond<G>;
     const DMeta *meta = &b.meta[blockIdx.x];
-    if (!mg_contig(meta) || meta->sssp_nl != NL || g.mstat[blockIdx.x]) return;
+    if constexpr (COND) { if (!g.r.sel[blockIdx.x] || !mg_contig(meta) || meta->sssp_nl != NL || g.r.mstat[blockIdx.x]) return; }
+    else { if (!mg_contig(meta) || meta->sssp_nl != NL || g.mstat[blockIdx.x]) return; }
     const int V = meta->n_node;
     const DOrf *orf = b.orf + meta->orf_off;
     const DGrp *grp = b.grp + meta->grp_off;
@@ -216,9 +257,13 @@ __global__ __launch_bounds__(NT) void k_margins(DBatch b, DMarg g) {
     const uint32_t *esrc = b.esrc + meta->edge_off;
     const long long *ew = b.ew + meta->edge_off;
     const long long *gt = gtab_of(b, meta);
-    const uint64_t *ds = b.dist + (size_t)meta->node_off * b.dist_stride;
-    const uint64_t *dt = g.dist_t + (size_t)meta->node_off * b.dist_stride;
-    phx_orf_margin *rec = g.rec + meta->orf_off;
+    const uint64_t *ds, *dt;
+    phx_orf_margin *rec;
+    if constexpr (COND) { ds = g.r.ds + (size_t)meta->node_off * g.r.ds_stride; dt = g.r.dist_t + (size_t)meta->node_off * b.dist_stride; rec = g.r.rec + meta->orf_off; }
+    else { ds = b.dist + (size_t)meta->node_off * b.dist_stride; dt = g.dist_t + (size_t)meta->node_off * b.dist_stride; rec = g.rec + meta->orf_off; }
+    [[maybe_unused]] const uint64_t ebase = (uint64_t)meta->edge_off;
+    [[maybe_unused]] bool biased = false;
+    if constexpr (COND) biased = g.q.evs[blockIdx.x] != 0;
     const WInt<NL> D = wi_load<NL>(ds + (size_t)(V - 1) * NL);
     const bool d_ok = !wi_unreached<NL>(D);
     for (int k = (int)blockIdx.y * NT + (int)threadIdx.x; k < meta->n_orf; k += (int)gridDim.y * NT) {
@@ -239,15 +284,59 @@ __global__ __launch_bounds__(NT) void k_margins(DBatch b, DMarg g) {
         uint32_t e = 0xffffffffu;
         for (uint32_t x = in_off[v], x1 = in_off[v + 1]; x < x1; x++)
             if (ESRC_NODE(esrc[x]) == (uint32_t)u) { e = x; break; }
+        if constexpr (COND) { if (e != 0xffffffffu && mg_bit(g.q.mask, ebase + e)) e = 0xffffffffu; } // a refused ORF: no path of G' runs through it
         if (e != 0xffffffffu && d_ok) {
             const WInt<NL> du = wi_load<NL>(ds + (size_t)u * NL), dv = wi_load<NL>(dt + (size_t)v * NL);
             if (!wi_unreached<NL>(du) && !wi_unreached<NL>(dv)) {
-                const WInt<NL> w = ew_decode<NL>(edge_wenc(esrc[e], ew, e, gt)); // the edge's own integer, not one recomputed from oweight
+                WInt<NL> w = ew_decode<NL>(edge_wenc(esrc[e], ew, e, gt)); // the edge's own integer, not one recomputed from oweight
+                if constexpr (COND) { if (biased && mg_bit(g.q.bbit, ebase + e)) w = wi_add<NL>(w, ew_decode<NL>(g.q.bval[ebase + e])); }
                 const WInt<NL> delta = wi_add<NL>(wi_add<NL>(du, w), wi_add<NL>(dv, wi_neg<NL>(D)));
                 r.through = 1;
                 r.margin = wi_to_double_rn<NL>(delta) / 1000.0; // one correctly rounded division, as float(delta) / 1000.0
             }
         }
         rec[k] = r;
+    }
+}
+
+// ---- re-annotation margins (DESIGN.md §21): what k_sssp_rev<NL, MgCond> reads ----
+// On demand after phx_reannotate_flat / phx_evidence_flat (phx_remargins_flat), on the context's stream.  The DBatch is the run's (graph and
+// layout, read only), DReann what the re-annotation left resident, DRmarg the feature's own buffers.  A thread per ORF of the contigs with
+// DRmarg.sel == 1: a refused or biased ORF (DReann.forb / bias, device ORF order) finds its out-edge in the CSR — the graph stage refuses
+// parallel edges, so the head v is unique in u's range — and sets that position's bit in fbit or bbit; a bias writes B to the position's
+// word.  Refusal wins over a bias, as in k_ev_mask.  An ORF without an edge is ignored.  Every index is checked against the contig's own
+// ranges before use.  The CSR itself is only read.
+__global__ __launch_bounds__(NT) void k_rmg_apply(DBatch b, DMarg g, DReann q, DRmarg r) {
+    const DMeta *meta = &b.meta[blockIdx.x];
+    if (r.sel[blockIdx.x] != 1 || !mg_contig(meta)) return;
+    const DOrf *orf = b.orf + meta->orf_off;
+    const DGrp *grp = b.grp + meta->grp_off;
+    const int32_t *onode = b.onode + meta->orf_off;
+    const uint8_t *forb = q.forb + meta->orf_off;
+    const bool biased = q.evs[blockIdx.x] != 0;
+    const long long *bias = biased ? q.bias + meta->orf_off : nullptr;
+    const uint32_t *oo = g.out_off + meta->node_off + blockIdx.x;
+    const uint32_t *od = g.out_dst + meta->edge_off;
+    const uint64_t ebase = (uint64_t)meta->edge_off;
+    const int V = meta->n_node;
+    const uint32_t E = (uint32_t)meta->n_edge;
+    for (int k = (int)blockIdx.y * NT + (int)threadIdx.x; k < meta->n_orf; k += (int)gridDim.y * NT) {
+        const uint8_t f = forb[k];
+        const long long B = biased ? bias[k] : 0ll;
+        if (f != 1 && B == 0) continue;
+        const DOrf o = orf[k];
+        if (o.grp < 0 || o.grp >= meta->n_grp) continue;
+        const int sn = onode[k], tn = grp[o.grp].node;
+        const bool fwd = o.frame > 0;
+        const int u = fwd ? sn : tn, v = fwd ? tn : sn; // start -> stop on the forward strand, stop -> start on the reverse (functions.py:310-316)
+        if (u < 0 || v < 0 || u >= V || v >= V) continue;
+        uint32_t x = oo[u], x1 = oo[u + 1];
+        if (x1 > E) x1 = E; // (the CSR's own offsets: never beyond the contig's edges)
+        for (; x < x1; x++)
+            if (od[x] == (uint32_t)v) { // (no such edge: the ORF is ignored)
+                if (f == 1) atomicOr(&r.fbit[(ebase + x) >> 5], 1u << ((ebase + x) & 31));
+                else { r.bval[ebase + x] = B; atomicOr(&r.bbit[(ebase + x) >> 5], 1u << ((ebase + x) & 31)); }
+                break;
+            }
     }
 }
