@@ -41,6 +41,7 @@ extern "C" {
  *        (additions, version unchanged) phx_reannotate_flat, phx_orf_offsets, phx_tap_repath, phx_reannotate_ms;
  *        (addition, version unchanged: the suite pins 410) phx_constrain_flat — probe for the symbol, not for a version;
  *        (addition, version unchanged) phx_evidence_flat — likewise;
+ *        (addition, version unchanged) phx_curate_flat — likewise;
  *        (additions, version unchanged) phx_scenarios_flat, phx_scenarios_ms, phx_scenario_chunks, phx_tap_scenario_path — probe for the symbol;
  *        (addition, version unchanged) phx_pinned_scenarios_flat — probe for the symbol;
  *        (addition, version unchanged) phx_evidence_scenarios_flat — probe for the symbol;
@@ -453,6 +454,21 @@ int phx_constrain_flat(phx_ctx *ctx, const uint8_t *forbid, const uint8_t *requi
  * is then D_B, and phx_reannotate_ms serve the last solve of any kind.  (Addition, version unchanged: probe for the symbol.) */
 int phx_evidence_flat(phx_ctx *ctx, const int64_t *bias, const uint8_t *forbid, const int64_t *orf_offsets /* [n+1] */, uint32_t flags, phx_gene *genes, int64_t cap,
                       int64_t *offsets /* [n+1] */, int32_t *status /* [n] */, double *delta /* [n] */, int64_t *total);
+/* ---- combined re-annotation: required, refused and biased ORFs in one solve ----
+ * phx_constrain_flat on phx_evidence_flat's graph: among the paths of G_{F,B} those that use the most edges of the required set are
+ * compared by S(P), the sum of W + B over the path — the shortest path under W(e) + B(e) - M·[e required], M above every walk sum.  An ORF
+ * may be required and biased; a refused ORF's bias is ignored; an ORF both refused and required, or |B| > 2^52, is PHX_E_ARG before any
+ * kernel.  delta = float(S(P) - D) / 1000.0 (may be negative), unmet[i] = |R| - (required ORFs the path calls), |R| where there is no result;
+ * phx_tap_repath reports S(P).  Any of bias, forbid and require may be NULL (empty).
+ * status[i] as phx_constrain_flat and phx_evidence_flat: PHX_S_NEGCYCLE (no genes, delta +inf) when the source reaches a cycle through a
+ * required ORF's edge or one that the biases make negative; PHX_S_OVERFLOW when the layout's bound plus the sum of |B| does not fit the
+ * contig's limb class.
+ * Reductions, byte for byte and per contig: every B zero is phx_constrain_flat, nothing required is phx_evidence_flat (unmet 0), both is
+ * phx_reannotate_flat — a contig runs the combined kernels only when it has a required and a biased ORF.  The calls share their buffers and
+ * their cached result (keyed on the three arrays and the flags).  phx_remargins_flat is PHX_E_STATE after a solve with a contig that had
+ * required ORFs, as after phx_constrain_flat.  (Addition, version unchanged: probe for the symbol.) */
+int phx_curate_flat(phx_ctx *ctx, const int64_t *bias, const uint8_t *forbid, const uint8_t *require, const int64_t *orf_offsets /* [n+1] */, uint32_t flags, phx_gene *genes,
+                    int64_t cap, int64_t *offsets /* [n+1] */, int32_t *status /* [n] */, double *delta /* [n] */, int32_t *unmet /* [n] */, int64_t *total);
 /* orf_offsets[n+1] of the batch last run as phx_reannotate_flat expects them: cumulative ORF counts, a contig with a run error or without
  * device distances counting none (the offsets phx_margins_flat reports, without computing the margins or the certificate). */
 int phx_orf_offsets(phx_ctx *ctx, int64_t *orf_offsets /* [n+1] */);

@@ -166,6 +166,7 @@ def lib():
         "phx_reannotate_flat": (C.c_int, [vp, vp, vp, C.c_uint32, vp, i64, vp, vp, vp, P(i64)]),
         "phx_constrain_flat": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, i64, vp, vp, vp, vp, P(i64)]),
         "phx_evidence_flat": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, i64, vp, vp, vp, P(i64)]),
+        "phx_curate_flat": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, vp, i64, vp, vp, vp, vp, P(i64)]),
         "phx_orf_offsets": (C.c_int, [vp, vp]),
         "phx_tap_repath": (C.c_int, [vp, i32, vp, i32, P(i32), vp, i32]),
         "phx_reannotate_ms": (C.c_int, [vp, P(C.c_float)]),
@@ -219,7 +220,7 @@ EXPORTS = ["phx_version", "phx_device_count", "phx_strerror", "phx_last_error", 
            "phx_drop_margins_flat", "phx_drop_ms", "phx_drop_stats", "phx_format_drops",
            "phx_replacements_flat", "phx_tap_replacement", "phx_replacements_ms", "phx_replacement_stats",
            "phx_format_replacements",
-           "phx_reannotate_flat", "phx_constrain_flat", "phx_evidence_flat", "phx_orf_offsets", "phx_tap_repath", "phx_reannotate_ms",
+           "phx_reannotate_flat", "phx_constrain_flat", "phx_evidence_flat", "phx_curate_flat", "phx_orf_offsets", "phx_tap_repath", "phx_reannotate_ms",
            "phx_scenarios_flat", "phx_scenarios_ms", "phx_scenario_chunks", "phx_tap_scenario_path", "phx_pinned_scenarios_flat",
            "phx_evidence_scenarios_flat",
            "phx_remargins_flat", "phx_remargins_ms", "phx_tap_redist"]

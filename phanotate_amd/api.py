@@ -528,21 +528,13 @@ class Annotator:
         self._chk(self.L.phx_constrain_flat(self.h, vp(fmask), vp(rmask), vp(oo), fl, vp(genes), len(genes), vp(offs), vp(status), vp(delta), vp(unmet), C.byref(total)), "phx_constrain_flat")
         return status[:n], offs, genes[: int(total.value)], delta[:n], unmet[:n]
 
-    def evidence(self, bias, forbid=None, solve_all=False):
-        """(status int32[n], offsets int64[n+1], genes structured array[total], delta float64[n]), as reannotate() returns them: the batch
-        last run annotated again with a bonus or a penalty on chosen ORFs (phx_evidence_flat, DESIGN.md §19).  `bias` holds, per contig,
-        None or a dict or sequence of (index into orfs(i), b) pairs, b a float in SCORE units: negative is support, positive is doubt.  The
-        solver adds B = math.trunc(b * 1000.0) to the ORF's edge (its units are 1/1000 of a SCORE unit, so what b holds beyond three
-        decimals is cut off, towards zero); an ORF listed twice gets the sum of its B.  `forbid` is reannotate()'s.  delta[i] =
-        float(D_B - D) / 1000 may be negative.  Bonuses that make a cycle negative give status -9 without genes.  A non-finite b or
-        |B| > 2^52 raises ValueError.  With no bias at all it is reannotate(forbid)."""
+    def _bias_array(self, bias, oo):
+        """One int64 per ORF of the batch from evidence()'s `bias`: B = math.trunc(b * 1000.0) per listed ORF, summed over repeats."""
         import math
 
         n = self.n
         if len(bias) != n:
             raise ValueError("one dict or sequence of (ORF index, bias) pairs (or None) per contig of the batch")
-        oo = self.orf_offsets()
-        fmask = self._orf_mask([None] * n if forbid is None else forbid)
         B = np.zeros(max(int(oo[n]), 1), np.int64)
         for i, pairs in enumerate(bias):
             if pairs is None:
@@ -556,6 +548,20 @@ class Annotator:
                 B[oo[i] + k] += math.trunc(b * 1000.0)
         if np.abs(B).max() > 1 << 52:
             raise ValueError("a bias beyond 2^52 / 1000 SCORE units")
+        return B
+
+    def evidence(self, bias, forbid=None, solve_all=False):
+        """(status int32[n], offsets int64[n+1], genes structured array[total], delta float64[n]), as reannotate() returns them: the batch
+        last run annotated again with a bonus or a penalty on chosen ORFs (phx_evidence_flat, DESIGN.md §19).  `bias` holds, per contig,
+        None or a dict or sequence of (index into orfs(i), b) pairs, b a float in SCORE units: negative is support, positive is doubt.  The
+        solver adds B = math.trunc(b * 1000.0) to the ORF's edge (its units are 1/1000 of a SCORE unit, so what b holds beyond three
+        decimals is cut off, towards zero); an ORF listed twice gets the sum of its B.  `forbid` is reannotate()'s.  delta[i] =
+        float(D_B - D) / 1000 may be negative.  Bonuses that make a cycle negative give status -9 without genes.  A non-finite b or
+        |B| > 2^52 raises ValueError.  With no bias at all it is reannotate(forbid)."""
+        n = self.n
+        oo = self.orf_offsets()
+        fmask = self._orf_mask([None] * n if forbid is None else forbid)
+        B = self._bias_array(bias, oo)
         offs = np.zeros(n + 1, np.int64)
         status = np.zeros(max(n, 1), np.int32)
         delta = np.zeros(max(n, 1), np.float64)
@@ -566,6 +572,31 @@ class Annotator:
         genes = np.empty(max(int(total.value), 1), _lib.GENE_DT)
         self._chk(self.L.phx_evidence_flat(self.h, vp(B), vp(fmask), vp(oo), fl, vp(genes), len(genes), vp(offs), vp(status), vp(delta), C.byref(total)), "phx_evidence_flat")
         return status[:n], offs, genes[: int(total.value)], delta[:n]
+
+    def curate(self, bias=None, forbid=None, require=None, solve_all=False):
+        """(status int32[n], offsets int64[n+1], genes structured array[total], delta float64[n], unmet int32[n]), as constrain() returns
+        them: the batch last run annotated again keeping the ORFs of `require`, without those of `forbid`, and with evidence()'s `bias` on
+        chosen ORFs, all in one solve (phx_curate_flat).  The result calls as many required ORFs as can be called together
+        and, among those annotations, is the best under the biased weights; an ORF may be required and biased, a refused ORF's bias is
+        ignored.  delta[i] = float(S(P) - D) / 1000 may be negative; unmet[i] as in constrain().  A cycle through a required ORF's edge, or
+        one that the biases make negative, gives status -9 without genes.  An ORF in both sets raises PhxError (PHX_E_ARG); a bad bias
+        raises as in evidence().  Without a bias it is constrain(forbid, require), without a required set evidence(bias, forbid)."""
+        n = self.n
+        oo = self.orf_offsets()
+        fmask = self._orf_mask([None] * n if forbid is None else forbid)
+        rmask = self._orf_mask([None] * n if require is None else require)
+        B = self._bias_array([None] * n if bias is None else bias, oo)
+        offs = np.zeros(n + 1, np.int64)
+        status = np.zeros(max(n, 1), np.int32)
+        delta = np.zeros(max(n, 1), np.float64)
+        unmet = np.zeros(max(n, 1), np.int32)
+        total = C.c_int64(0)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        fl = 1 if solve_all else 0
+        self._chk(self.L.phx_curate_flat(self.h, vp(B), vp(fmask), vp(rmask), vp(oo), fl, None, 0, vp(offs), vp(status), vp(delta), vp(unmet), C.byref(total)), "phx_curate_flat")
+        genes = np.empty(max(int(total.value), 1), _lib.GENE_DT)
+        self._chk(self.L.phx_curate_flat(self.h, vp(B), vp(fmask), vp(rmask), vp(oo), fl, vp(genes), len(genes), vp(offs), vp(status), vp(delta), vp(unmet), C.byref(total)), "phx_curate_flat")
+        return status[:n], offs, genes[: int(total.value)], delta[:n], unmet[:n]
 
     # ---- scenario batches (DESIGN.md §17) ----
     @staticmethod
@@ -861,8 +892,8 @@ class Annotator:
         return np.asarray(st[:n], np.int32), offs, rec, soffs, genes
 
     def reannotated_path(self, i):
-        """(path as device node ids, its length as a python int) of contig i in the last re-annotation, constrain() or evidence(), like
-        path(i): D_F, the W-sum W(P) after constrain(), D_B after evidence()."""
+        """(path as device node ids, its length as a python int) of contig i in the last re-annotation, constrain(), evidence() or curate(), like
+        path(i): D_F, the W-sum W(P) after constrain(), D_B after evidence(), S(P) after curate()."""
         g = self.globals(i)
         p = np.zeros(max(g.n_node, 1), np.int32)
         n = C.c_int32()

@@ -538,9 +538,10 @@ static void reann_batch(phx_ctx *c, DBatch *b, DReann *q) {
     q->gplan = (uint8_t *)c->b_qplan.p; q->dist0 = (const uint64_t *)c->b_dist.p; q->stride0 = c->n_limbs; q->rec = (DReannRec *)c->b_qrec.p;
     q->evs = q->sel + 4 * n1; q->bbit = q->mask + 2 * mw; // (the evidence buffers exist once a call has biased a contig; no kernel reads them before)
     q->bias = (const long long *)c->b_qbias.p; q->bval = (long long *)c->b_qbval.p; q->bsum = (unsigned long long *)c->b_qbsum.p;
+    q->rce = q->sel + 5 * n1;
 }
 
-// Solves the contigs of h_qsel again (1: masked, 2: under the required policy, 3: under the bias policy) with the ORFs of `forb` (tap order;
+// Solves the contigs of h_qsel again (1: masked, 2: under the required policy, 3: under the bias policy, 4: under both, §22) with the ORFs of `forb` (tap order;
 // 1 = refused, 2 = required, h_qnreq of them per contig) and the integers of `bias` (tap order; null: none); the records into h_qrec, the
 // genes into h_qgenes.
 static int reann_compute(phx_ctx *c, const uint8_t *forb, const int64_t *bias, const int64_t *orf_offsets) {
@@ -551,10 +552,10 @@ static int reann_compute(phx_ctx *c, const uint8_t *forb, const int64_t *bias, c
     std::vector<uint8_t> &dforb = c->h_qdforb;
     dforb.assign(N + 1, 0);
     std::vector<int> order;
-    int nlm = 0, pinm = 0, evm = 0;
+    int nlm = 0, pinm = 0, evm = 0, rcem = 0;
     bool any = false;
-    std::vector<int32_t> &dsel = c->h_qdsel; // what the kernels read: sel | pin | nreq | kreq (zero) | evs, n + 1 entries each
-    dsel.assign(5 * (n + 1), 0);
+    std::vector<int32_t> &dsel = c->h_qdsel; // what the kernels read: sel | pin | nreq | kreq (zero) | evs | rce, n + 1 entries each
+    dsel.assign(6 * (n + 1), 0);
     std::vector<int64_t> &dbias = c->h_qdbias;
     if (bias) dbias.assign(N + 1, 0);
     for (size_t i = 0; i < n; i++) {
@@ -563,6 +564,7 @@ static int reann_compute(phx_ctx *c, const uint8_t *forb, const int64_t *bias, c
         const DMeta &m = c->meta[i];
         if (c->h_qsel[i] == 2) { pinm |= nl_class_bit(m.sssp_nl); dsel[n + 1 + i] = 1; dsel[2 * (n + 1) + i] = c->h_qnreq[i]; }
         else if (c->h_qsel[i] == 3) { evm |= nl_class_bit(m.sssp_nl); dsel[4 * (n + 1) + i] = 1; }
+        else if (c->h_qsel[i] == 4) { rcem |= nl_class_bit(m.sssp_nl); dsel[5 * (n + 1) + i] = 1; dsel[2 * (n + 1) + i] = c->h_qnreq[i]; }
         else { nlm |= nl_class_bit(m.sssp_nl); dsel[i] = 1; }
         const uint8_t *from = forb + orf_offsets[i];
         const int64_t *bfrom = bias ? bias + orf_offsets[i] : nullptr;
@@ -579,20 +581,20 @@ static int reann_compute(phx_ctx *c, const uint8_t *forb, const int64_t *bias, c
     c->h_qgenes.clear();
     if (!any) return PHX_OK;
     int rc;
-    c->qstride = (int)limbs + (pinm ? 1 : 0);
+    c->qstride = (int)limbs + ((pinm | rcem) ? 1 : 0);
     const size_t mw = E / 32 + 2; // words of one bitmap; the required ORFs' follows the refused ORFs' in b_qmask
     if ((rc = ensure(c, c->b_qmeta, (n + 1) * sizeof(DMeta))) || (rc = ensure(c, c->b_qtot, sizeof(DTotals))) || (rc = ensure(c, c->b_qdist, (V + 1) * (size_t)c->qstride * 8)) ||
         (rc = ensure(c, c->b_qparent, (V + 1) * 4)) || (rc = ensure(c, c->b_qpath, (V + 1) * 4)) || (rc = ensure(c, c->b_qgenes, (V + n + 1) * sizeof(DGene))) || // (a path has at most V / 2 pairs, one replaced by k_rs_inorder takes new slots)
-        (rc = ensure(c, c->b_qgtot, 16)) || (rc = ensure(c, c->b_qmask, 3 * mw * 4)) || (rc = ensure(c, c->b_qforb, N + 1)) || (rc = ensure(c, c->b_qsel, 5 * (n + 1) * 4)) ||
+        (rc = ensure(c, c->b_qgtot, 16)) || (rc = ensure(c, c->b_qmask, 3 * mw * 4)) || (rc = ensure(c, c->b_qforb, N + 1)) || (rc = ensure(c, c->b_qsel, 6 * (n + 1) * 4)) ||
         (rc = ensure(c, c->b_qplan, V / 32 + n + 2)) || (rc = ensure(c, c->b_qrec, (n + 1) * sizeof(DReannRec))))
         return rc;
     if (!c->b_qtie.p && (rc = ensure(c, c->b_qtie, (size_t)std::max<int64_t>(c->tie_seen, 1 << 20)))) return rc;
-    if (evm && ((rc = ensure(c, c->b_qbias, (N + 1) * 8)) || (rc = ensure(c, c->b_qbval, (E + 1) * 8)) || (rc = ensure(c, c->b_qbsum, 2 * (n + 1) * 8)))) return rc;
+    if ((evm | rcem) && ((rc = ensure(c, c->b_qbias, (N + 1) * 8)) || (rc = ensure(c, c->b_qbval, (E + 1) * 8)) || (rc = ensure(c, c->b_qbsum, 2 * (n + 1) * 8)))) return rc;
     if ((rc = analysis_events(c))) return rc;
     hipStream_t s = c->stream;
     HIPCHK(c, hipMemcpyAsync(c->b_qforb.p, dforb.data(), N + 1, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->b_qsel.p, dsel.data(), 5 * (n + 1) * 4, hipMemcpyHostToDevice, s));
-    if (evm) HIPCHK(c, hipMemcpyAsync(c->b_qbias.p, dbias.data(), (N + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->b_qsel.p, dsel.data(), 6 * (n + 1) * 4, hipMemcpyHostToDevice, s));
+    if (evm | rcem) HIPCHK(c, hipMemcpyAsync(c->b_qbias.p, dbias.data(), (N + 1) * 8, hipMemcpyHostToDevice, s));
     DTotals &tot = c->h_qtot;
     uint32_t &gtot = c->h_qgtot;
     gtot = 0;
@@ -605,17 +607,20 @@ static int reann_compute(phx_ctx *c, const uint8_t *forb, const int64_t *bias, c
         HIPCHK(c, hipMemsetAsync(c->b_qtot.p, 0, sizeof(DTotals), s));
         HIPCHK(c, hipMemsetAsync(c->b_qgtot.p, 0, 16, s));
         HIPCHK(c, hipMemsetAsync(c->b_qrec.p, 0, (n + 1) * sizeof(DReannRec), s));
-        HIPCHK(c, hipMemsetAsync(c->b_qmask.p, 0, (evm ? 3 : pinm ? 2 : 1) * mw * 4, s));
-        if (pinm && attempt) HIPCHK(c, hipMemsetAsync((int32_t *)c->b_qsel.p + 3 * (n + 1), 0, (n + 1) * 4, s)); // k_rs_mask counts again
-        if (evm) HIPCHK(c, hipMemsetAsync(c->b_qbsum.p, 0, 2 * (n + 1) * 8, s)); // (k_ev_mask sums again)
+        HIPCHK(c, hipMemsetAsync(c->b_qmask.p, 0, ((evm | rcem) ? 3 : pinm ? 2 : 1) * mw * 4, s));
+        if ((pinm | rcem) && attempt) HIPCHK(c, hipMemsetAsync((int32_t *)c->b_qsel.p + 3 * (n + 1), 0, (n + 1) * 4, s)); // k_rs_mask counts again
+        if (evm | rcem) HIPCHK(c, hipMemsetAsync(c->b_qbsum.p, 0, 2 * (n + 1) * 8, s)); // (k_ev_mask and k_rce_mask sum again)
         if (nlm | pinm) phxk_reann_mask(&b, &q, s);
         if (evm) phxk_evid_mask(&b, &q, s);
+        if (rcem) phxk_curate_mask(&b, &q, s);
         HIPCHK(c, hipEventRecord(c->aev[1], s));
         phxk_reann_solve(&b, &q, nlm, pinm, s);
         if (evm) phxk_evid_solve(&b, &q, evm, s);
+        if (rcem) phxk_curate_solve(&b, &q, rcem, s);
         HIPCHK(c, hipEventRecord(c->aev[2], s));
         if (nlm | pinm) phxk_reann_finish(&b, &q, nlm, pinm, s);
         if (evm) phxk_evid_finish(&b, &q, evm, s);
+        if (rcem) phxk_curate_finish(&b, &q, rcem, s);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(c->h_qrec.data(), c->b_qrec.p, n * sizeof(DReannRec), hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipEventRecord(c->aev[3], s));
@@ -644,8 +649,8 @@ static int reann_compute(phx_ctx *c, const uint8_t *forb, const int64_t *bias, c
     return PHX_OK;
 }
 
-// phx_reannotate_flat (require and unmet null, forbid needed), phx_constrain_flat (either set may be null: empty) and phx_evidence_flat (bias
-// and forbid may be null, require is) are one solve on one set of buffers; the cached result is keyed on both sets (h_qforb holds 1 = refused,
+// phx_reannotate_flat (require and unmet null, forbid needed), phx_constrain_flat (either set may be null: empty), phx_evidence_flat (bias
+// and forbid may be null, require is) and phx_curate_flat (any of the three may be null) are one solve on one set of buffers; the cached result is keyed on both sets (h_qforb holds 1 = refused,
 // 2 = required per ORF) and on the bias (h_qbias; empty when every B is zero, which makes the call phx_reannotate_flat).
 #define PHX_BIAS_MAX (1ll << 52) // |B| beyond it is PHX_E_ARG: the sum of a contig's |B| stays below 2^83, and ew_decode never reads a B as a wide row
 static int reann_flat(phx_ctx *c, const char *who, bool need_forbid, const uint8_t *forbid, const uint8_t *require, const int64_t *bias, const int64_t *orf_offsets, uint32_t flags, phx_gene *genes,
@@ -686,11 +691,14 @@ static int reann_flat(phx_ctx *c, const char *who, bool need_forbid, const uint8
         c->h_qsel.assign((size_t)c->n, 0);
         c->h_qnreq.assign((size_t)c->n, 0);
         for (int i = 0; i < c->n; i++) {
-            int32_t nf = 0, nr = 0, nb = 0;
-            for (int64_t k = orf_offsets[i]; k < orf_offsets[i + 1]; k++) { nf += code[(size_t)k] == 1; nr += code[(size_t)k] == 2; nb += !bcur.empty() && bcur[(size_t)k] != 0; }
+            int32_t nf = 0, nr = 0, nb = 0, nbk = 0; // (nbk: the biases that count beside a required set — a refused ORF's is ignored)
+            for (int64_t k = orf_offsets[i]; k < orf_offsets[i + 1]; k++) {
+                const bool bk = !bcur.empty() && bcur[(size_t)k] != 0;
+                nf += code[(size_t)k] == 1; nr += code[(size_t)k] == 2; nb += bk; nbk += bk && code[(size_t)k] != 1;
+            }
             c->h_qnreq[(size_t)i] = nr;
             if (!reann_contig(c, i)) continue;
-            c->h_qsel[(size_t)i] = nr ? 2 : (nb ? 3 : ((flags & 1u) != 0 || nf ? 1 : 0)); // (a bias never comes with a required set: phx_evidence_flat has none)
+            c->h_qsel[(size_t)i] = nr ? (nbk ? 4 : 2) : (nb ? 3 : ((flags & 1u) != 0 || nf ? 1 : 0)); // (4: required and biased ORFs in one contig, phx_curate_flat alone brings both)
         }
         { const int rq = reann_compute(c, code.data(), bcur.empty() ? nullptr : bcur.data(), orf_offsets); if (rq) { (void)hipStreamSynchronize(c->stream); return rq; } } // (nothing of a failed solve stays in flight)
         c->h_qbias = bcur;
@@ -746,6 +754,12 @@ int phx_evidence_flat(phx_ctx *c, const int64_t *bias, const uint8_t *forbid, co
     return reann_flat(c, "phx_evidence_flat", false, forbid, nullptr, bias, orf_offsets, flags, genes, cap, offsets, status, delta, nullptr, total_out);
 }
 
+int phx_curate_flat(phx_ctx *c, const int64_t *bias, const uint8_t *forbid, const uint8_t *require, const int64_t *orf_offsets, uint32_t flags, phx_gene *genes, int64_t cap,
+                    int64_t *offsets, int32_t *status, double *delta, int32_t *unmet, int64_t *total_out) {
+    if (!c || (c->n > 0 && !unmet)) return PHX_E_ARG;
+    return reann_flat(c, "phx_curate_flat", false, forbid, require, bias, orf_offsets, flags, genes, cap, offsets, status, delta, unmet, total_out);
+}
+
 int phx_orf_offsets(phx_ctx *c, int64_t *orf_offsets) {
     if (!c || !orf_offsets) return PHX_E_ARG;
     { const int ra = after_run(c); if (ra) return ra; }
@@ -775,7 +789,7 @@ int phx_tap_repath(phx_ctx *c, int32_t contig, int32_t *path, int32_t cap, int32
     if (dist_limbs) {
         if (cap_limbs < m.sssp_nl) return PHX_E_ARG;
         // (a contig solved under the required policy keeps one limb more per node: the W-sum is the low sssp_nl limbs of its distance)
-        const size_t tgt = (size_t)m.node_off * (size_t)c->qstride + ((size_t)m.n_node - 1) * (size_t)(m.sssp_nl + (c->h_qsel[(size_t)contig] == 2 ? 1 : 0));
+        const size_t tgt = (size_t)m.node_off * (size_t)c->qstride + ((size_t)m.n_node - 1) * (size_t)(m.sssp_nl + (c->h_qsel[(size_t)contig] == 2 || c->h_qsel[(size_t)contig] == 4 ? 1 : 0));
         HIPCHK(c, hipMemcpy(dist_limbs, (uint64_t *)c->b_qdist.p + tgt, (size_t)m.sssp_nl * 8, hipMemcpyDeviceToHost));
     }
     return PHX_OK;
@@ -793,7 +807,7 @@ int phx_reannotate_ms(phx_ctx *c, float *ms) {
 static int remarg_state(phx_ctx *c, const char *who) {
     if (!c->done.reann) { c->err = std::string(who) + ": no re-annotation of this run (call phx_reannotate_flat or phx_evidence_flat first)"; return PHX_E_STATE; }
     for (int i = 0; i < c->n; i++)
-        if (c->h_qsel[(size_t)i] == 2) { c->err = std::string(who) + ": the last re-annotation solved a contig under the required policy; margins under required ORFs are not defined here"; return PHX_E_STATE; }
+        if (c->h_qsel[(size_t)i] == 2 || c->h_qsel[(size_t)i] == 4) { c->err = std::string(who) + ": the last re-annotation solved a contig under the required policy; margins under required ORFs are not defined here"; return PHX_E_STATE; }
     return PHX_OK;
 }
 

@@ -272,10 +272,10 @@ struct phx_ctx {
     std::vector<uint8_t> h_qforb;     // the sets last solved, tap order (one byte per ORF of the batch: 1 = refused, 2 = required)
     std::vector<uint8_t> h_qcode;     // ... of the call at hand
     std::vector<int32_t> h_qnreq;     // per contig: required ORFs (|R|)
-    std::vector<int32_t> h_qdsel;     // the per-contig arrays the kernels read (DReann.sel / pin / nreq / kreq / evs)
+    std::vector<int32_t> h_qdsel;     // the per-contig arrays the kernels read (DReann.sel / pin / nreq / kreq / evs / rce)
     int qstride = 2;                  // limbs per node of b_qdist: the run's, one more when a contig was solved under the required policy
     uint32_t h_qflags = 0;
-    std::vector<int32_t> h_qsel;      // per contig: solved again (1; 2: under the required policy; 3: under the bias policy), else the run's result stands
+    std::vector<int32_t> h_qsel;      // per contig: solved again (1; 2: under the required policy; 3: under the bias policy; 4: under both), else the run's result stands
     std::vector<DReannRec> h_qrec;    // per contig that was solved again
     std::vector<DGene> h_qgenes;      // the re-annotation's gene buffer as the device left it (records at h_qrec[i].gene_off)
     std::vector<uint8_t> h_qdforb;    // the mask in device ORF order, and the totals read back: members, so that a copy enqueued before

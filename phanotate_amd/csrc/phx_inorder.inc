@@ -189,6 +189,8 @@ __device__ void walk_path(const DBatch &b, DMeta *meta, IoShared<IO_T> *sh) {
 // BIAS (the evidence-weighted re-annotation, DESIGN.md §19; with MASKED): an edge whose bit is set in `bbit` weighs W + B, B the word of its
 // in-edge slot in `bval`, as in the sweep that made the distances (lds_sweep under EvCfg): a row is tight iff d[u] + W + B == d[v].
 // BLIST (a biased scenario slot, DESIGN.md §20; with BIAS): `bval` is the slot's sorted list of nbl (in-edge slot, B) pairs (bias_at, phx_sssp.inc).
+// REQ and BIAS together (the combined re-annotation, DESIGN.md §22; k_rce_inorder): the two are independent — a row that is required and biased
+// weighs W + B - 2^(64 (NL - 1)), so it is tight iff d[u] + W + B - M == d[v].
 // ci: the contig's index in the batch (blockIdx.x where a workgroup is a contig; a scenario slot passes its slot's contig).
 template <int NL, int IO_T, bool MASKED = false, bool REQ = false, bool BIAS = false, bool BLIST = false>
 __device__ void inorder_contig(const DBatch &b, DMeta *meta, const uint32_t ci, IoShared<IO_T> *sh, const uint32_t *mask = nullptr, const uint32_t *req = nullptr, const uint32_t *bbit = nullptr, const long long *bval = nullptr, const int nbl = 0) {

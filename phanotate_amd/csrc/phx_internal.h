@@ -405,6 +405,8 @@ struct DReann {
     uint32_t *bbit;        // as `mask`: the in-edge slots that carry a bias (only touched when a contig has some)
     long long *bval;       // per in-edge slot of the batch (at edge_off + e): B; never cleared, read only where the slot's bit is set
     unsigned long long *bsum; // per contig [2]: the sums of |B| & 0xffffffff and of |B| >> 32 over its biased edges, zeroed per call
+    // the combined re-annotation (§22); behind the fields above, whose places in the kernels' argument block stay
+    const int32_t *rce;    // per contig: 1 = solve it again under the required and the bias policy together, on one limb more (never with sel, pin or evs)
 };
 
 // Scenario batches (phx_resolve.inc): S masked re-annotations side by side, one workgroup per scenario slot.  A slot is one
@@ -528,6 +530,9 @@ void phxk_evid_finish(const DBatch *b, const DReann *q, int ev_mask, void *strea
 void phxk_remarg_apply(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, void *stream);               // re-annotation margins (§21; b: the run's batch): the refused / biased out-edge positions,
 void phxk_remarg_rev(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, int nl_mask, void *stream);     //   the conditioned reverse pass (nl_mask: the classes among DRmarg.sel == 1),
 void phxk_remarg_records(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, int nl_mask, void *stream); //   the ORF records (nl_mask: the classes among DRmarg.sel != 0)
+void phxk_curate_mask(const DBatch *b, const DReann *q, void *stream);                 // combined re-annotation (§22): the refused, required and biased ORFs' marks,
+void phxk_curate_solve(const DBatch *b, const DReann *q, int rce_mask, void *stream);  //   the sweep under both policies (rce_mask: the classes with required and biased ORFs),
+void phxk_curate_finish(const DBatch *b, const DReann *q, int rce_mask, void *stream); //   in-order parents, path, genes, delta, unmet
 void phxk_scen_mask(const DBatch *b, const DScen *q, void *stream);                 // scenario batches (phx_resolve.inc): the slots' records and bitmap slices (b: the run's batch),
 void phxk_scen_solve(const DBatch *b, const DScen *q, int nl_mask, void *stream);   //   the masked sweep, a workgroup per slot (b: the run's graph, tot / genes / gene_total / tie the scenarios' own),
 void phxk_scen_finish(const DBatch *b, const DScen *q, int nl_mask, void *stream);  //   in-order parents, path, genes, delta per slot

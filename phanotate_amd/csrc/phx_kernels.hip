@@ -447,6 +447,21 @@ void phxk_evid_finish(const DBatch *b, const DReann *q, int ev_mask, void *strea
     else NL_LAUNCH_T(k_ev_inorder, IO_T_FULL, ev_mask, dim3(b->n_contig), *b, *q);
     hipLaunchKernelGGL(k_ev_fin, dim3((unsigned)((b->n_contig + 63) / 64)), dim3(64), 0, s, *b, *q);
 }
+// combined re-annotation: the contigs of DReann.rce, beside the three above on the same view of the batch
+void phxk_curate_mask(const DBatch *b, const DReann *q, void *stream) { hipLaunchKernelGGL(k_rce_mask, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), 0, (hipStream_t)stream, *b, *q); }
+void phxk_curate_solve(const DBatch *b, const DReann *q, int rce_mask, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (rce_mask & 1) launch_lds(k_rce_lds<2>, rc_lds_bytes<3>(), b, s, *b, *q);
+    if (rce_mask & 2) launch_lds(k_rce_lds<4>, rc_lds_bytes<5>(), b, s, *b, *q);
+    if (rce_mask & 4) launch_lds(k_rce_lds<8>, rc_lds_bytes<9>(), b, s, *b, *q);
+    if (rce_mask & 8) launch_lds(k_rce_lds<17>, rc_lds_bytes<18>(), b, s, *b, *q);
+}
+void phxk_curate_finish(const DBatch *b, const DReann *q, int rce_mask, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (b->mean_len < 8192) NL_LAUNCH_T(k_rce_inorder, 64, rce_mask, dim3(b->n_contig), *b, *q); // as phxk_reann_finish
+    else NL_LAUNCH_T(k_rce_inorder, IO_T_FULL, rce_mask, dim3(b->n_contig), *b, *q);
+    hipLaunchKernelGGL(k_rce_fin, dim3((unsigned)((b->n_contig + 63) / 64)), dim3(64), 0, s, *b, *q);
+}
 // scenario batches: the grids are the chunk's slots (pairs for k_sc_mask), not the batch's contigs
 void phxk_scen_mask(const DBatch *b, const DScen *q, void *stream) {
     hipStream_t s = (hipStream_t)stream;

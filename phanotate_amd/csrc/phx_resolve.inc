@@ -18,6 +18,8 @@
 // The evidence-weighted re-annotation (§19: a signed integer B per ORF added to its edge) is the chain a third time, for the contigs that
 // have biased ORFs: k_ev_mask writes B to the edge's slot and sets its bit in a third bitmap, k_ev_lds / k_ev_inorder run the sweep and the
 // parent rule under the BIAS policy in the contig's own class, k_ev_fin writes the record.
+// The combined re-annotation (§22: required and biased ORFs in one solve) is the chain a fourth time, for the contigs that have both:
+// k_rce_mask, k_rce_lds / k_rce_inorder under REQ and BIAS together on one limb more, k_rce_fin.
 // The bitmap only ever holds bits of explicit rows: an ORF edge runs open -> close and a coded gap edge (a connector) close -> open, so no
 // ORF shares both ends with a coded row, and k_rs_mask skips coded rows besides.  k_rs_lds therefore tests explicit rows only, and the
 // masked inorder_contig, which tests every row, sees the same graph.
@@ -231,6 +233,103 @@ __global__ __launch_bounds__(64) void k_ev_fin(DBatch b, DReann q) {
         const uint64_t *df = b.dist + (size_t)meta->node_off * b.dist_stride + (size_t)(V - 1) * nl;
         const uint64_t *d0 = q.dist0 + (size_t)meta->node_off * q.stride0 + (size_t)(V - 1) * nl;
         r.delta = nl == 2 ? rs_delta<2>(df, d0) : nl == 4 ? rs_delta<4>(df, d0) : nl == 8 ? rs_delta<8>(df, d0) : rs_delta<17>(df, d0);
+        r.n_genes = meta->n_genes; r.gene_off = meta->gene_off; r.n_path = meta->n_path;
+    }
+    q.rec[c] = r;
+}
+
+// ---- the combined re-annotation (DESIGN.md §22): the contigs with required AND biased ORFs, DReann.rce ----
+// Both policies in one solve: a row weighs W + B - M·[required], M = 2^(64 NL), on NL + 1 limbs as in §16.  The low NL limbs of a distance
+// hold a sum of W + B, which k_rce_lds bounds by §19's limb test before the sweep, so M exceeds every walk sum and the top limb is the
+// count of required edges as before (rq_count).  Both ends stay guarded: the count guard ends a solve whose source reaches a cycle through a
+// required edge, the sweep and round caps one whose biases make a reachable cycle negative.  The ring and tile sizes are k_rc_lds'.
+template <int NL1> struct RcEvCfg { static constexpr int RING = RcCfg<NL1>::RING, ECAP = RcCfg<NL1>::ECAP; static constexpr bool MASKED = true, REQ = true, BIAS = true, BLIST = false; };
+
+// a thread per ORF of a contig that is solved under both policies: k_rs_mask's and k_ev_mask's marks in one pass.  A refused ORF sets its
+// slot's bit in `mask` and nothing else; a required one sets the bit in `req` and counts for kreq; a biased one (required or not) writes B,
+// sets the bit in `bbit` and adds |B| to the contig's sums.  Only explicit rows are marked; `forb` and `bias` are indexed by the contig's own
+// ORFs, u and v are checked against V.
+__global__ __launch_bounds__(NT) void k_rce_mask(DBatch b, DReann q) {
+    const DMeta *meta = &b.meta[blockIdx.x];
+    if (!q.rce[blockIdx.x] || !mg_contig(meta)) return;
+    const DOrf *orf = b.orf + meta->orf_off;
+    const DGrp *grp = b.grp + meta->grp_off;
+    const int32_t *onode = b.onode + meta->orf_off;
+    const uint8_t *forb = q.forb + meta->orf_off;
+    const long long *bias = q.bias + meta->orf_off;
+    const uint32_t *in_off = b.in_off + meta->node_off + blockIdx.x;
+    const uint32_t *esrc = b.esrc + meta->edge_off;
+    const uint64_t ebase = (uint64_t)meta->edge_off;
+    const int V = meta->n_node;
+    for (int k = (int)blockIdx.y * NT + (int)threadIdx.x; k < meta->n_orf; k += (int)gridDim.y * NT) {
+        const uint8_t f = forb[k];
+        const long long B = bias[k];
+        if (!f && B == 0) continue;
+        const DOrf o = orf[k];
+        const int sn = onode[k], tn = grp[o.grp].node;
+        const bool fwd = o.frame > 0;
+        const int u = fwd ? sn : tn, v = fwd ? tn : sn;
+        if (u < 0 || v < 0 || u >= V || v >= V) continue;
+        for (uint32_t x = in_off[v], x1 = in_off[v + 1]; x < x1; x++)
+            if (!ESRC_IS_GAP(esrc[x]) && ESRC_NODE(esrc[x]) == (uint32_t)u) { // (no such edge: the ORF is ignored, a required one stays unmet)
+                const uint32_t bit = 1u << ((ebase + x) & 31);
+                if (f == 1) { atomicOr(&q.mask[(ebase + x) >> 5], bit); break; } // refusal wins over a bias
+                if (f == 2) { atomicOr(&q.req[(ebase + x) >> 5], bit); atomicAdd(&q.kreq[blockIdx.x], 1); }
+                if (B != 0) {
+                    const unsigned long long a = (unsigned long long)(B < 0 ? -B : B);
+                    q.bval[ebase + x] = B;
+                    atomicOr(&q.bbit[(ebase + x) >> 5], bit);
+                    atomicAdd(&q.bsum[2 * blockIdx.x], a & 0xffffffffull);
+                    atomicAdd(&q.bsum[2 * blockIdx.x + 1], a >> 32);
+                }
+                break;
+            }
+    }
+}
+
+// NL: the contig's class; the sweep runs on NL + 1 limbs behind k_ev_lds' limb test (the launch bounds of k_rc_lds)
+template <int NL>
+__global__ __launch_bounds__(SW_THREADS, NL == 2 ? 4 : 2) void k_rce_lds(DBatch b, DReann q) {
+    DMeta *meta = &b.meta[blockIdx.x];
+    const int V = meta->n_node;
+    if (!q.rce[blockIdx.x] || !mg_contig(meta) || meta->sssp_nl != NL) return;
+    // the sums of W + B must fit the contig's own class: M = 2^(64 NL) then exceeds every one of them
+    const double extra = (double)q.bsum[2 * blockIdx.x + 1] * 4294967296.0 + (double)q.bsum[2 * blockIdx.x];
+    if (contig_sum_bits(b, meta, extra) > 64 * NL) {
+        __syncthreads(); // (every thread has read the status)
+        if (threadIdx.x == 0) { meta->status = PHX_S_OVERFLOW; meta->n_genes = 0; meta->n_path = 0; meta->gene_off = 0; }
+        return;
+    }
+    lds_sweep<NL + 1, RcEvCfg<NL + 1>>(b, meta, blockIdx.x, V, q.mask, q.gplan, q.req, q.kreq[blockIdx.x], q.bbit, q.bval);
+}
+
+template <int NL, int IO_T>
+__global__ __launch_bounds__(IO_T) void k_rce_inorder(DBatch b, DReann q) {
+    __shared__ IoShared<IO_T> sh;
+    DMeta *meta = &b.meta[blockIdx.x];
+    if (!q.rce[blockIdx.x] || meta->sssp_nl != NL) return;
+    if (threadIdx.x == 0) { sh.flag = 0; meta->tie = 0; }
+    __syncthreads();
+    if (!mg_contig(meta)) return; // (a cycle, or the biased bound beyond the class: the solver has set the status)
+    if (meta->n_path < 2 && meta->n_path != -1) return;
+    inorder_contig<NL + 1, IO_T, true, true, true>(b, meta, blockIdx.x, &sh, q.mask, q.req, q.bbit, q.bval);
+}
+
+// a thread per contig: the record the host reads — delta from the low nl limbs of the target's distance (a sum of W + B, so it may be
+// negative as in k_ev_fin), unmet from the top limb (k_rs_fin's pinned part)
+__global__ __launch_bounds__(64) void k_rce_fin(DBatch b, DReann q) {
+    const int c = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (c >= b.n_contig || !q.rce[c]) return;
+    const DMeta *meta = &b.meta[c];
+    DReannRec r;
+    r.status = meta->status; r.n_genes = 0; r.gene_off = 0; r.n_path = 0; r.tie = meta->tie; r.delta = __builtin_inf();
+    r.unmet = q.nreq[c]; r.pad_ = 0;
+    if (meta->status >= 0 && meta->status != PHX_S_NOPATH && meta->n_path >= 2) {
+        const int V = meta->n_node, nl = meta->sssp_nl;
+        const uint64_t *df = b.dist + (size_t)meta->node_off * b.dist_stride + (size_t)(V - 1) * (nl + 1);
+        const uint64_t *d0 = q.dist0 + (size_t)meta->node_off * q.stride0 + (size_t)(V - 1) * nl;
+        r.delta = nl == 2 ? rs_delta<2>(df, d0) : nl == 4 ? rs_delta<4>(df, d0) : nl == 8 ? rs_delta<8>(df, d0) : rs_delta<17>(df, d0);
+        r.unmet -= (int32_t)(nl == 2 ? rc_count<2>(df) : nl == 4 ? rc_count<4>(df) : nl == 8 ? rc_count<8>(df) : rc_count<17>(df));
         r.n_genes = meta->n_genes; r.gene_off = meta->gene_off; r.n_path = meta->n_path;
     }
     q.rec[c] = r;

@@ -359,6 +359,9 @@ __host__ __device__ inline size_t sssp_lds_bytes(int V, int nl) {
 // BIAS (the evidence-weighted re-annotation, EvCfg in phx_resolve.inc; always MASKED, never REQ): an explicit row whose bit is set in `bbit`
 // carries W + B, B the signed 64-bit word of its in-edge slot in `bval` (read only where the bit is set; DESIGN.md §19).  A bonus can make a
 // cycle negative: the sweep and round caps end such a solve, and an unreached node stays at the unreached pattern as under REQ.
+// REQ and BIAS together (the combined re-annotation, RcEvCfg in phx_resolve.inc; MASKED, never BLIST; DESIGN.md §22): a row weighs W + B - M·[required],
+// on one limb more as under REQ; the count guard and the caps are both active.  The tile path then carries three flags per prefetched row — refused
+// and required in r_mk as under REQ, biased in a register of its own (r_mb), which no other policy has.
 // BLIST (a biased scenario slot, EsCfg in phx_resolve.inc; always BIAS): `bval` is not a word per in-edge slot but the slot's own list of
 // (in-edge slot of the batch, B) pairs, sorted by in-edge slot, `nbl` of them (DESIGN.md §20); bias_at below is the one place that knows.
 struct SwRun { static constexpr int RING = SW_RING, ECAP = SW_ECAP; static constexpr bool MASKED = false, REQ = false, BIAS = false, BLIST = false; };
@@ -421,6 +424,8 @@ template <int NL, class P>
 __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const uint32_t ci, const int V, const uint32_t *mask, uint8_t *gplan, const uint32_t *req = nullptr, const int kreq = 0, const uint32_t *bbit = nullptr, const long long *bval = nullptr, const int nbl = 0) {
     constexpr int RING = P::RING, ECAP = P::ECAP;
     constexpr int EPT = (ECAP + SW_THREADS - 1) / SW_THREADS; // tile edges prefetched per thread
+    static_assert(EPT <= 16, "r_mk and r_mb hold 16 flags per field");
+    static_assert(!(P::REQ && P::BLIST), "a list-biased slot with required ORFs: under REQ bits 16.. of r_mk are the required flags, which the BLIST block below reads as biased ones");
     extern __shared__ __align__(16) uint8_t smem[];
     __shared__ int s_flag[2];
     __shared__ int s_np, s_nclose, s_viol;
@@ -486,10 +491,12 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const ui
         if (tid < NL) ring[(size_t)RING * NL + tid] = 0; // the constant-zero slot (the LDS is reused by the pass below)
         if (tid == 0) s_viol = 0;
         __syncthreads();
-        // registers that carry window k+1's data while window k iterates; bit j of r_mk: tile edge j of this thread is refused, bit 16 + j: required (REQ) or biased (BIAS: never both policies)
+        // registers that carry window k+1's data while window k iterates; bit j of r_mk: tile edge j of this thread is refused, bit 16 + j: required (REQ) or biased (BIAS
+        // alone); under REQ and BIAS together bit 16 + j is the required flag and bit j of r_mb the biased one
         uint32_t r_src[EPT];
         long long r_w[EPT];
         uint32_t r_mk = 0;
+        [[maybe_unused]] uint32_t r_mb = 0;
         uint32_t r_offn = 0;
         int r_type = 0;
         WInt<NL> r_ring;
@@ -513,7 +520,8 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const ui
                 r_w[j] = on ? sw_row<P>(sw, ew, e0n + i, gt) : 0ll;
                 if (on && rs_refused<P>(mask, ebase, sw, e0n + i)) r_mk |= 1u << j;
                 if (P::REQ && on && rs_required<P>(req, ebase, sw, e0n + i)) r_mk |= 0x10000u << j;
-                if (P::BIAS && on && rs_biased<P>(bbit, ebase, sw, e0n + i)) r_mk |= 0x10000u << j;
+                if constexpr (P::REQ && P::BIAS) { if (on && rs_biased<P>(bbit, ebase, sw, e0n + i)) r_mb |= 1u << j; }
+                else if (P::BIAS && on && rs_biased<P>(bbit, ebase, sw, e0n + i)) r_mk |= 0x10000u << j;
             }
         }
         for (int k = 0; k < nW && !bad; k++) {
@@ -551,8 +559,13 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const ui
                         // source slot: a ring slot, or the constant-zero slot (the source node; and sources outside the
                         // ring, whose distance cannot change while this window iterates and is folded into the weight)
                         uint32_t sl = RING;
-                        if (P::REQ && ((r_mk >> (16 + j)) & 1u)) w.v[NL - 1] -= 1ull; // required: W - M, so the phases pay nothing for it either
-                        if constexpr (P::BIAS && !P::BLIST) { if ((r_mk >> (16 + j)) & 1u) w = wi_add<NL>(w, ew_decode<NL>(bias_at<false>(bval, ebase + e0 + i, nbl))); } // biased: W + B, likewise
+                        if constexpr (P::REQ && P::BIAS) { // both: B first, then the top limb (W + B - M)
+                            if ((r_mb >> j) & 1u) w = wi_add<NL>(w, ew_decode<NL>(bias_at<false>(bval, ebase + e0 + i, nbl)));
+                            if ((r_mk >> (16 + j)) & 1u) w.v[NL - 1] -= 1ull;
+                        } else {
+                            if (P::REQ && ((r_mk >> (16 + j)) & 1u)) w.v[NL - 1] -= 1ull; // required: W - M, so the phases pay nothing for it either
+                            if constexpr (P::BIAS && !P::BLIST) { if ((r_mk >> (16 + j)) & 1u) w = wi_add<NL>(w, ew_decode<NL>(bias_at<false>(bval, ebase + e0 + i, nbl))); } // biased: W + B, likewise
+                        }
                         if (P::MASKED && ((r_mk >> j) & 1u)) w = big; // refused: no edge (0 + "unreached" never wins), so the phases pay nothing for the mask
                         else if (u != (uint32_t)SRC) {
                             if ((int)u < loaded && (int)u + RING >= loaded) sl = u & (RING - 1);
@@ -565,6 +578,7 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const ui
                 // BLIST: B comes from a search of the slot's list, kept out of the unrolled loop above and done here, where the
                 // prefetched rows are no longer live — a thread with a biased row in its part of the tile (rare: a scenario biases
                 // a few ORFs) adds B to the entry it has just written; a refused row stays no edge
+                // (bits 16.. of r_mk are the biased flags here: a BLIST policy is never REQ, see the static_assert above)
                 if constexpr (P::BLIST) {
                     if (r_mk >> 16) {
 #pragma nounroll
@@ -586,6 +600,7 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const ui
                 r_ring = wi_load<NL>(gdist + (size_t)(loaded + tid < v1n ? loaded + tid : 0) * NL);
                 r_offn = (k + 2 < nW && tid <= (P::MASKED ? nwn2 : plan[k + 2])) ? in_off[v0n + SW_ADV + tid] : 0u;
                 r_mk = 0;
+                if constexpr (P::REQ && P::BIAS) r_mb = 0;
 #pragma unroll
                 for (int j = 0; j < EPT; j++) {
                     const int i = tid + j * SW_THREADS;
@@ -595,7 +610,8 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const ui
                     r_w[j] = on ? sw_row<P>(sw, ew, e0n + i, gt) : 0ll;
                     if (on && rs_refused<P>(mask, ebase, sw, e0n + i)) r_mk |= 1u << j;
                     if (P::REQ && on && rs_required<P>(req, ebase, sw, e0n + i)) r_mk |= 0x10000u << j;
-                    if (P::BIAS && on && rs_biased<P>(bbit, ebase, sw, e0n + i)) r_mk |= 0x10000u << j;
+                    if constexpr (P::REQ && P::BIAS) { if (on && rs_biased<P>(bbit, ebase, sw, e0n + i)) r_mb |= 1u << j; }
+                    else if (P::BIAS && on && rs_biased<P>(bbit, ebase, sw, e0n + i)) r_mk |= 0x10000u << j;
                 }
             }
 #ifdef SW_PROFILE
