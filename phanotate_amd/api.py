@@ -466,28 +466,7 @@ class Annotator:
         (phx_reannotate_flat).  genes[offsets[i]:offsets[i+1]] are contig i's, in the format and order of download_flat(exact=False);
         delta[i] = float(D_F - D) / 1000 (+inf: no path without them, status 1).  A contig with an empty mask keeps the run's result
         unless solve_all.  Not a re-run of the front end: GC-frame training and connector edges are those of the full ORF set."""
-        n = self.n
-        if len(forbid) != n:
-            raise ValueError("one index array (or None) per contig of the batch")
-        oo = self.orf_offsets()
-        mask = np.zeros(max(int(oo[n]), 1), np.uint8)
-        for i, f in enumerate(forbid):
-            if f is None:
-                continue
-            idx = np.asarray(f, np.int64).reshape(-1)
-            if idx.size and (idx.min() < 0 or idx.max() >= oo[i + 1] - oo[i]):
-                raise IndexError("contig %d has %d ORFs" % (i, oo[i + 1] - oo[i]))
-            mask[oo[i] + idx] = 1
-        offs = np.zeros(n + 1, np.int64)
-        status = np.zeros(max(n, 1), np.int32)
-        delta = np.zeros(max(n, 1), np.float64)
-        total = C.c_int64(0)
-        vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        fl = 1 if solve_all else 0
-        self._chk(self.L.phx_reannotate_flat(self.h, vp(mask), vp(oo), fl, None, 0, vp(offs), vp(status), vp(delta), C.byref(total)), "phx_reannotate_flat")
-        genes = np.empty(max(int(total.value), 1), _lib.GENE_DT)
-        self._chk(self.L.phx_reannotate_flat(self.h, vp(mask), vp(oo), fl, vp(genes), len(genes), vp(offs), vp(status), vp(delta), C.byref(total)), "phx_reannotate_flat")
-        return status[:n], offs, genes[: int(total.value)], delta[:n]
+        return self._resolve(self.L.phx_reannotate_flat, "phx_reannotate_flat", (self._orf_mask(forbid),), solve_all, False)
 
     def _orf_mask(self, sets):
         """One byte per ORF of the batch from one index array (or None) per contig."""
@@ -505,6 +484,25 @@ class Annotator:
             mask[oo[i] + idx] = 1
         return mask
 
+    def _resolve(self, fn, name, arrays, solve_all, with_unmet):
+        """The size query and the fill of one re-annotation entry point: fn(handle, *arrays, orf offsets, flags, genes, capacity, offsets,
+        status, delta[, unmet], total).  Returns (status, offsets, genes, delta[, unmet]) cut to the batch."""
+        n = self.n
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        offs = np.zeros(n + 1, np.int64)
+        status = np.zeros(max(n, 1), np.int32)
+        delta = np.zeros(max(n, 1), np.float64)
+        unmet = np.zeros(max(n, 1), np.int32)
+        total = C.c_int64(0)
+        oo = self.orf_offsets()
+        head = (self.h,) + tuple(vp(a) for a in arrays) + (vp(oo), 1 if solve_all else 0)
+        tail = (vp(offs), vp(status), vp(delta)) + ((vp(unmet),) if with_unmet else ()) + (C.byref(total),)
+        self._chk(fn(*head, None, 0, *tail), name)
+        genes = np.empty(max(int(total.value), 1), _lib.GENE_DT)
+        self._chk(fn(*head, vp(genes), len(genes), *tail), name)
+        out = (status[:n], offs, genes[: int(total.value)], delta[:n])
+        return out + (unmet[:n],) if with_unmet else out
+
     def constrain(self, forbid=None, require=None, solve_all=False):
         """(status int32[n], offsets int64[n+1], genes structured array[total], delta float64[n], unmet int32[n]): the batch last run
         annotated again without the ORFs of `forbid` and keeping those of `require` — each one array of indices into orfs(i) per contig,
@@ -513,20 +511,9 @@ class Annotator:
         there is no result); delta[i] = float(W(P) - D) / 1000.  A cycle through a required ORF's edge gives status 2 without genes.  An
         ORF in both sets raises PhxError (PHX_E_ARG).  With nothing required it is reannotate(forbid)."""
         n = self.n
-        oo = self.orf_offsets()
         fmask = self._orf_mask([None] * n if forbid is None else forbid)
         rmask = self._orf_mask([None] * n if require is None else require)
-        offs = np.zeros(n + 1, np.int64)
-        status = np.zeros(max(n, 1), np.int32)
-        delta = np.zeros(max(n, 1), np.float64)
-        unmet = np.zeros(max(n, 1), np.int32)
-        total = C.c_int64(0)
-        vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        fl = 1 if solve_all else 0
-        self._chk(self.L.phx_constrain_flat(self.h, vp(fmask), vp(rmask), vp(oo), fl, None, 0, vp(offs), vp(status), vp(delta), vp(unmet), C.byref(total)), "phx_constrain_flat")
-        genes = np.empty(max(int(total.value), 1), _lib.GENE_DT)
-        self._chk(self.L.phx_constrain_flat(self.h, vp(fmask), vp(rmask), vp(oo), fl, vp(genes), len(genes), vp(offs), vp(status), vp(delta), vp(unmet), C.byref(total)), "phx_constrain_flat")
-        return status[:n], offs, genes[: int(total.value)], delta[:n], unmet[:n]
+        return self._resolve(self.L.phx_constrain_flat, "phx_constrain_flat", (fmask, rmask), solve_all, True)
 
     def _bias_array(self, bias, oo):
         """One int64 per ORF of the batch from evidence()'s `bias`: B = math.trunc(b * 1000.0) per listed ORF, summed over repeats."""
@@ -559,19 +546,9 @@ class Annotator:
         float(D_B - D) / 1000 may be negative.  Bonuses that make a cycle negative give status -9 without genes.  A non-finite b or
         |B| > 2^52 raises ValueError.  With no bias at all it is reannotate(forbid)."""
         n = self.n
-        oo = self.orf_offsets()
         fmask = self._orf_mask([None] * n if forbid is None else forbid)
-        B = self._bias_array(bias, oo)
-        offs = np.zeros(n + 1, np.int64)
-        status = np.zeros(max(n, 1), np.int32)
-        delta = np.zeros(max(n, 1), np.float64)
-        total = C.c_int64(0)
-        vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        fl = 1 if solve_all else 0
-        self._chk(self.L.phx_evidence_flat(self.h, vp(B), vp(fmask), vp(oo), fl, None, 0, vp(offs), vp(status), vp(delta), C.byref(total)), "phx_evidence_flat")
-        genes = np.empty(max(int(total.value), 1), _lib.GENE_DT)
-        self._chk(self.L.phx_evidence_flat(self.h, vp(B), vp(fmask), vp(oo), fl, vp(genes), len(genes), vp(offs), vp(status), vp(delta), C.byref(total)), "phx_evidence_flat")
-        return status[:n], offs, genes[: int(total.value)], delta[:n]
+        B = self._bias_array(bias, self.orf_offsets())
+        return self._resolve(self.L.phx_evidence_flat, "phx_evidence_flat", (B, fmask), solve_all, False)
 
     def curate(self, bias=None, forbid=None, require=None, solve_all=False):
         """(status int32[n], offsets int64[n+1], genes structured array[total], delta float64[n], unmet int32[n]), as constrain() returns
@@ -582,21 +559,10 @@ class Annotator:
         one that the biases make negative, gives status -9 without genes.  An ORF in both sets raises PhxError (PHX_E_ARG); a bad bias
         raises as in evidence().  Without a bias it is constrain(forbid, require), without a required set evidence(bias, forbid)."""
         n = self.n
-        oo = self.orf_offsets()
         fmask = self._orf_mask([None] * n if forbid is None else forbid)
         rmask = self._orf_mask([None] * n if require is None else require)
-        B = self._bias_array([None] * n if bias is None else bias, oo)
-        offs = np.zeros(n + 1, np.int64)
-        status = np.zeros(max(n, 1), np.int32)
-        delta = np.zeros(max(n, 1), np.float64)
-        unmet = np.zeros(max(n, 1), np.int32)
-        total = C.c_int64(0)
-        vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        fl = 1 if solve_all else 0
-        self._chk(self.L.phx_curate_flat(self.h, vp(B), vp(fmask), vp(rmask), vp(oo), fl, None, 0, vp(offs), vp(status), vp(delta), vp(unmet), C.byref(total)), "phx_curate_flat")
-        genes = np.empty(max(int(total.value), 1), _lib.GENE_DT)
-        self._chk(self.L.phx_curate_flat(self.h, vp(B), vp(fmask), vp(rmask), vp(oo), fl, vp(genes), len(genes), vp(offs), vp(status), vp(delta), vp(unmet), C.byref(total)), "phx_curate_flat")
-        return status[:n], offs, genes[: int(total.value)], delta[:n], unmet[:n]
+        B = self._bias_array([None] * n if bias is None else bias, self.orf_offsets())
+        return self._resolve(self.L.phx_curate_flat, "phx_curate_flat", (B, fmask, rmask), solve_all, True)
 
     # ---- scenario batches (DESIGN.md §17) ----
     @staticmethod

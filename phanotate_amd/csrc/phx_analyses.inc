@@ -523,22 +523,27 @@ static int32_t reann_status(const phx_ctx *c, int i) {
 }
 static bool reann_contig(const phx_ctx *c, int i) { const DMeta &m = c->meta[(size_t)i]; return reann_status(c, i) >= 0 && m.n_node > 2; }
 
-// The re-annotation's view of the batch: the run's graph, outputs of its own (nothing the run's results live in is written).
-static void reann_batch(phx_ctx *c, DBatch *b, DReann *q) {
+// A re-solve's view of the batch: the run's graph, read only, with totals, gene records, gene counter and tie scratch of the solve's own
+// (reann_batch for the re-annotation, scen_compute for a chunk of scenario slots) — nothing the run's results live in is written.
+static void resolve_batch(phx_ctx *c, DBatch *b, const DevBuf &tot, const DevBuf &genes, const DevBuf &gtot, const DevBuf &tie) {
     fill_batch(c, b);
-    b->meta = (DMeta *)c->b_qmeta.p; b->tot = (DTotals *)c->b_qtot.p;
-    b->res = nullptr; b->sord = nullptr; b->lpart = nullptr;
+    b->tot = (DTotals *)tot.p; b->res = nullptr; b->sord = nullptr; b->lpart = nullptr;
+    b->genes = (DGene *)genes.p; b->genes_c = nullptr; b->gpack = 0; b->gene_total = (uint32_t *)gtot.p;
+    b->tie = (uint8_t *)tie.p; b->tie_cap = cap_of(tie, 1, 0);
+}
+// The re-annotation's: records, distances, parents and paths of its own besides.  b_qsel holds mode | nreq | kreq, n + 1 entries each;
+// b_qmask the refused, the required and the biased bitmap (the evidence buffers exist once a call has biased a contig; no kernel reads them before).
+static void reann_batch(phx_ctx *c, DBatch *b, DReann *q) {
+    resolve_batch(c, b, c->b_qtot, c->b_qgenes, c->b_qgtot, c->b_qtie);
+    b->meta = (DMeta *)c->b_qmeta.p;
     b->dist = (uint64_t *)c->b_qdist.p; b->parent = (int32_t *)c->b_qparent.p; b->path = (int32_t *)c->b_qpath.p;
-    b->genes = (DGene *)c->b_qgenes.p; b->genes_c = nullptr; b->gpack = 0; b->gene_total = (uint32_t *)c->b_qgtot.p;
-    b->tie = (uint8_t *)c->b_qtie.p; b->tie_cap = cap_of(c->b_qtie, 1, 0);
     b->dist_stride = c->qstride; // (one limb wider than the run's when a contig is solved under the required policy, §16)
     const size_t n1 = (size_t)c->n + 1, mw = (size_t)c->tot_edge / 32 + 2;
-    q->forb = (const uint8_t *)c->b_qforb.p; q->mask = (uint32_t *)c->b_qmask.p; q->req = q->mask + mw;
-    q->sel = (const int32_t *)c->b_qsel.p; q->pin = q->sel + n1; q->nreq = q->sel + 2 * n1; q->kreq = (int32_t *)c->b_qsel.p + 3 * n1;
+    q->mode = (const int32_t *)c->b_qsel.p; q->nreq = q->mode + n1; q->kreq = (int32_t *)c->b_qsel.p + 2 * n1;
+    q->forb = (const uint8_t *)c->b_qforb.p; q->bias = (const long long *)c->b_qbias.p;
+    q->mask = (uint32_t *)c->b_qmask.p; q->req = q->mask + mw; q->bbit = q->mask + 2 * mw;
+    q->bval = (long long *)c->b_qbval.p; q->bsum = (unsigned long long *)c->b_qbsum.p;
     q->gplan = (uint8_t *)c->b_qplan.p; q->dist0 = (const uint64_t *)c->b_dist.p; q->stride0 = c->n_limbs; q->rec = (DReannRec *)c->b_qrec.p;
-    q->evs = q->sel + 4 * n1; q->bbit = q->mask + 2 * mw; // (the evidence buffers exist once a call has biased a contig; no kernel reads them before)
-    q->bias = (const long long *)c->b_qbias.p; q->bval = (long long *)c->b_qbval.p; q->bsum = (unsigned long long *)c->b_qbsum.p;
-    q->rce = q->sel + 5 * n1;
 }
 
 // Solves the contigs of h_qsel again (1: masked, 2: under the required policy, 3: under the bias policy, 4: under both, §22) with the ORFs of `forb` (tap order;
@@ -552,20 +557,21 @@ static int reann_compute(phx_ctx *c, const uint8_t *forb, const int64_t *bias, c
     std::vector<uint8_t> &dforb = c->h_qdforb;
     dforb.assign(N + 1, 0);
     std::vector<int> order;
-    int nlm = 0, pinm = 0, evm = 0, rcem = 0;
-    bool any = false;
-    std::vector<int32_t> &dsel = c->h_qdsel; // what the kernels read: sel | pin | nreq | kreq (zero) | evs | rce, n + 1 entries each
-    dsel.assign(6 * (n + 1), 0);
+    int nlm[RE_MODES] = {0, 0, 0, 0, 0}; // per mode: the limb classes of its contigs
+    bool any = false, any_req = false, any_bias = false;
+    std::vector<int32_t> &dsel = c->h_qdsel; // what the kernels read: mode | nreq | kreq (zero), n + 1 entries each
+    dsel.assign(3 * (n + 1), 0);
     std::vector<int64_t> &dbias = c->h_qdbias;
     if (bias) dbias.assign(N + 1, 0);
     for (size_t i = 0; i < n; i++) {
         if (!c->h_qsel[i]) continue;
         any = true;
         const DMeta &m = c->meta[i];
-        if (c->h_qsel[i] == 2) { pinm |= nl_class_bit(m.sssp_nl); dsel[n + 1 + i] = 1; dsel[2 * (n + 1) + i] = c->h_qnreq[i]; }
-        else if (c->h_qsel[i] == 3) { evm |= nl_class_bit(m.sssp_nl); dsel[4 * (n + 1) + i] = 1; }
-        else if (c->h_qsel[i] == 4) { rcem |= nl_class_bit(m.sssp_nl); dsel[5 * (n + 1) + i] = 1; dsel[2 * (n + 1) + i] = c->h_qnreq[i]; }
-        else { nlm |= nl_class_bit(m.sssp_nl); dsel[i] = 1; }
+        const int mode = c->h_qsel[i];
+        nlm[mode] |= nl_class_bit(m.sssp_nl);
+        dsel[i] = mode;
+        if (re_mode_req(mode)) { any_req = true; dsel[n + 1 + i] = c->h_qnreq[i]; }
+        any_bias = any_bias || re_mode_bias(mode);
         const uint8_t *from = forb + orf_offsets[i];
         const int64_t *bfrom = bias ? bias + orf_offsets[i] : nullptr;
         each_group_in_reference_order(c, i, order, [&](int32_t first, int32_t k) {
@@ -581,20 +587,20 @@ static int reann_compute(phx_ctx *c, const uint8_t *forb, const int64_t *bias, c
     c->h_qgenes.clear();
     if (!any) return PHX_OK;
     int rc;
-    c->qstride = (int)limbs + ((pinm | rcem) ? 1 : 0);
+    c->qstride = (int)limbs + (any_req ? 1 : 0);
     const size_t mw = E / 32 + 2; // words of one bitmap; the required ORFs' follows the refused ORFs' in b_qmask
     if ((rc = ensure(c, c->b_qmeta, (n + 1) * sizeof(DMeta))) || (rc = ensure(c, c->b_qtot, sizeof(DTotals))) || (rc = ensure(c, c->b_qdist, (V + 1) * (size_t)c->qstride * 8)) ||
         (rc = ensure(c, c->b_qparent, (V + 1) * 4)) || (rc = ensure(c, c->b_qpath, (V + 1) * 4)) || (rc = ensure(c, c->b_qgenes, (V + n + 1) * sizeof(DGene))) || // (a path has at most V / 2 pairs, one replaced by k_rs_inorder takes new slots)
-        (rc = ensure(c, c->b_qgtot, 16)) || (rc = ensure(c, c->b_qmask, 3 * mw * 4)) || (rc = ensure(c, c->b_qforb, N + 1)) || (rc = ensure(c, c->b_qsel, 6 * (n + 1) * 4)) ||
+        (rc = ensure(c, c->b_qgtot, 16)) || (rc = ensure(c, c->b_qmask, 3 * mw * 4)) || (rc = ensure(c, c->b_qforb, N + 1)) || (rc = ensure(c, c->b_qsel, 3 * (n + 1) * 4)) ||
         (rc = ensure(c, c->b_qplan, V / 32 + n + 2)) || (rc = ensure(c, c->b_qrec, (n + 1) * sizeof(DReannRec))))
         return rc;
     if (!c->b_qtie.p && (rc = ensure(c, c->b_qtie, (size_t)std::max<int64_t>(c->tie_seen, 1 << 20)))) return rc;
-    if ((evm | rcem) && ((rc = ensure(c, c->b_qbias, (N + 1) * 8)) || (rc = ensure(c, c->b_qbval, (E + 1) * 8)) || (rc = ensure(c, c->b_qbsum, 2 * (n + 1) * 8)))) return rc;
+    if (any_bias && ((rc = ensure(c, c->b_qbias, (N + 1) * 8)) || (rc = ensure(c, c->b_qbval, (E + 1) * 8)) || (rc = ensure(c, c->b_qbsum, 2 * (n + 1) * 8)))) return rc;
     if ((rc = analysis_events(c))) return rc;
     hipStream_t s = c->stream;
     HIPCHK(c, hipMemcpyAsync(c->b_qforb.p, dforb.data(), N + 1, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->b_qsel.p, dsel.data(), 6 * (n + 1) * 4, hipMemcpyHostToDevice, s));
-    if (evm | rcem) HIPCHK(c, hipMemcpyAsync(c->b_qbias.p, dbias.data(), (N + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->b_qsel.p, dsel.data(), 3 * (n + 1) * 4, hipMemcpyHostToDevice, s));
+    if (any_bias) HIPCHK(c, hipMemcpyAsync(c->b_qbias.p, dbias.data(), (N + 1) * 8, hipMemcpyHostToDevice, s));
     DTotals &tot = c->h_qtot;
     uint32_t &gtot = c->h_qgtot;
     gtot = 0;
@@ -607,20 +613,14 @@ static int reann_compute(phx_ctx *c, const uint8_t *forb, const int64_t *bias, c
         HIPCHK(c, hipMemsetAsync(c->b_qtot.p, 0, sizeof(DTotals), s));
         HIPCHK(c, hipMemsetAsync(c->b_qgtot.p, 0, 16, s));
         HIPCHK(c, hipMemsetAsync(c->b_qrec.p, 0, (n + 1) * sizeof(DReannRec), s));
-        HIPCHK(c, hipMemsetAsync(c->b_qmask.p, 0, ((evm | rcem) ? 3 : pinm ? 2 : 1) * mw * 4, s));
-        if ((pinm | rcem) && attempt) HIPCHK(c, hipMemsetAsync((int32_t *)c->b_qsel.p + 3 * (n + 1), 0, (n + 1) * 4, s)); // k_rs_mask counts again
-        if (evm | rcem) HIPCHK(c, hipMemsetAsync(c->b_qbsum.p, 0, 2 * (n + 1) * 8, s)); // (k_ev_mask and k_rce_mask sum again)
-        if (nlm | pinm) phxk_reann_mask(&b, &q, s);
-        if (evm) phxk_evid_mask(&b, &q, s);
-        if (rcem) phxk_curate_mask(&b, &q, s);
+        HIPCHK(c, hipMemsetAsync(c->b_qmask.p, 0, (any_bias ? 3 : any_req ? 2 : 1) * mw * 4, s));
+        if (any_req && attempt) HIPCHK(c, hipMemsetAsync((int32_t *)c->b_qsel.p + 2 * (n + 1), 0, (n + 1) * 4, s)); // k_rs_mask counts again
+        if (any_bias) HIPCHK(c, hipMemsetAsync(c->b_qbsum.p, 0, 2 * (n + 1) * 8, s)); // (... and sums again)
+        phxk_reann_mask(&b, &q, s);
         HIPCHK(c, hipEventRecord(c->aev[1], s));
-        phxk_reann_solve(&b, &q, nlm, pinm, s);
-        if (evm) phxk_evid_solve(&b, &q, evm, s);
-        if (rcem) phxk_curate_solve(&b, &q, rcem, s);
+        phxk_reann_solve(&b, &q, nlm, s);
         HIPCHK(c, hipEventRecord(c->aev[2], s));
-        if (nlm | pinm) phxk_reann_finish(&b, &q, nlm, pinm, s);
-        if (evm) phxk_evid_finish(&b, &q, evm, s);
-        if (rcem) phxk_curate_finish(&b, &q, rcem, s);
+        phxk_reann_finish(&b, &q, nlm, s);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(c->h_qrec.data(), c->b_qrec.p, n * sizeof(DReannRec), hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipEventRecord(c->aev[3], s));
@@ -789,7 +789,7 @@ int phx_tap_repath(phx_ctx *c, int32_t contig, int32_t *path, int32_t cap, int32
     if (dist_limbs) {
         if (cap_limbs < m.sssp_nl) return PHX_E_ARG;
         // (a contig solved under the required policy keeps one limb more per node: the W-sum is the low sssp_nl limbs of its distance)
-        const size_t tgt = (size_t)m.node_off * (size_t)c->qstride + ((size_t)m.n_node - 1) * (size_t)(m.sssp_nl + (c->h_qsel[(size_t)contig] == 2 || c->h_qsel[(size_t)contig] == 4 ? 1 : 0));
+        const size_t tgt = (size_t)m.node_off * (size_t)c->qstride + ((size_t)m.n_node - 1) * (size_t)(m.sssp_nl + (re_mode_req(c->h_qsel[(size_t)contig]) ? 1 : 0));
         HIPCHK(c, hipMemcpy(dist_limbs, (uint64_t *)c->b_qdist.p + tgt, (size_t)m.sssp_nl * 8, hipMemcpyDeviceToHost));
     }
     return PHX_OK;
@@ -807,7 +807,7 @@ int phx_reannotate_ms(phx_ctx *c, float *ms) {
 static int remarg_state(phx_ctx *c, const char *who) {
     if (!c->done.reann) { c->err = std::string(who) + ": no re-annotation of this run (call phx_reannotate_flat or phx_evidence_flat first)"; return PHX_E_STATE; }
     for (int i = 0; i < c->n; i++)
-        if (c->h_qsel[(size_t)i] == 2 || c->h_qsel[(size_t)i] == 4) { c->err = std::string(who) + ": the last re-annotation solved a contig under the required policy; margins under required ORFs are not defined here"; return PHX_E_STATE; }
+        if (re_mode_req(c->h_qsel[(size_t)i])) { c->err = std::string(who) + ": the last re-annotation solved a contig under the required policy; margins under required ORFs are not defined here"; return PHX_E_STATE; }
     return PHX_OK;
 }
 
@@ -831,7 +831,7 @@ static int ensure_remargins(phx_ctx *c) {
         if (st < 0) continue;
         c->h_xsel[i] = st == 0 ? 1 : 2; // (PHX_S_NOPATH: records only, D' is unreached)
         rec_nlm |= nl_class_bit(c->meta[i].sssp_nl);
-        if (st == 0) { rev_nlm |= nl_class_bit(c->meta[i].sssp_nl); biased = biased || c->h_qsel[i] == 3; }
+        if (st == 0) { rev_nlm |= nl_class_bit(c->meta[i].sssp_nl); biased = biased || re_mode_bias(c->h_qsel[i]); }
     }
     for (int k = 0; k < 4; k++) c->remarg_ms[k] = 0;
     if (!rec_nlm) { c->done.remarg = true; return PHX_OK; }
@@ -960,9 +960,9 @@ static size_t scen_slot_bytes(const phx_ctx *c, int i, bool pinned = false, size
 // Solves the scenarios with a slot (h_srec[j].status == SC_SLOT) in chunks under the budget; records into h_srec, genes into h_sgenes.
 // perm: per contig named, tap index -> ORF in the contig's device order (-1: no such ORF in the device's groups).  req_off / req_orf: the
 // required lists without duplicates; a scenario with a non-empty one gets a pinned slot.  In a chunk's slot table the pinned slots follow
-// the plain ones (the slices keep the scenarios' order): k_sc_* get the head of the table, k_scp_* its tail.  bs_off / bs_orf / bs_val: the
+// the plain ones (the slices keep the scenarios' order): the solve's kernels get the table range by range (phxk_scen_solve).  bs_off / bs_orf / bs_val: the
 // merged bias lists (no duplicates, no zero, no ORF the scenario refuses); a scenario with a non-empty one gets a biased slot (never with a
-// required list: no entry point takes both), and the biased slots follow the pinned ones: k_sce_* get that tail.
+// required list: no entry point takes both), and the biased slots follow the pinned ones.
 static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const int64_t *scen_off, const int32_t *scen_orf, const int64_t *req_off, const int32_t *req_orf,
                         const int64_t *bs_off, const int32_t *bs_orf, const int64_t *bs_val, const std::vector<std::vector<int32_t>> &perm) {
     int rc;
@@ -1076,10 +1076,7 @@ static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const
             // the slots' view of the batch: the run's graph and records (read only), totals / genes / counter / tie scratch of the scenarios' own
             DBatch b;
             DScen q;
-            fill_batch(c, &b);
-            b.tot = (DTotals *)c->b_sc_tot.p; b.res = nullptr; b.sord = nullptr; b.lpart = nullptr;
-            b.genes = (DGene *)c->b_sc_genes.p; b.genes_c = nullptr; b.gpack = 0; b.gene_total = (uint32_t *)c->b_sc_gtot.p;
-            b.tie = (uint8_t *)c->b_sc_tie.p; b.tie_cap = cap_of(c->b_sc_tie, 1, 0);
+            resolve_batch(c, &b, c->b_sc_tot, c->b_sc_genes, c->b_sc_gtot, c->b_sc_tie);
             q.slot = (const DScSlot *)c->b_sc_slot.p; q.pair = (const int2 *)c->b_sc_pair.p; q.n_pair = (int64_t)pairs.size(); q.n_slot = (int32_t)ns;
             q.stride0 = c->n_limbs; q.meta = (DMeta *)c->b_sc_meta.p; q.dist = (uint64_t *)c->b_sc_dist.p; q.parent = (int32_t *)c->b_sc_parent.p;
             q.path = (int32_t *)c->b_sc_path.p; q.mask = (uint32_t *)c->b_sc_mask.p; q.gplan = (uint8_t *)c->b_sc_plan.p;
@@ -1094,29 +1091,18 @@ static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const
                 q.bbit = q.mask + (mwords + 2 + rwords + 2); q.bs = (DScBias *)c->b_sc_bs.p; q.blist = (long long *)c->b_sc_blist.p;
                 q.bstage = q.blist + 2 * (trips.size() + 1); q.trip = (const DScTrip *)c->b_sc_trip.p; q.n_trip = (int64_t)trips.size();
             }
-            DScen qa = q, qb = q, qe = q; // the plain head, the pinned middle and the biased tail of the slot table
-            qe.n_slot = (int32_t)n_ev; qe.slot += n_head; qe.meta += n_head; qe.rec += n_head;
-            if (n_ev) qe.bs += n_head;
-            qa.n_slot = (int32_t)n_plain;
-            qb.n_slot = (int32_t)n_pin; qb.slot += n_plain; qb.meta += n_plain; qb.rec += n_plain;
-            if (n_pin) { qb.req0 += n_plain; qb.nreq += n_plain; qb.kreq += n_plain; }
+            const int n_range[3] = {(int)n_plain, (int)n_pin, (int)n_ev}, nlms[3] = {nlm, pinm, evm}; // the plain head, the pinned middle and the biased tail of the slot table
             HIPCHK(c, hipEventRecord(c->aev[0], s));
             HIPCHK(c, hipMemsetAsync(c->b_sc_tot.p, 0, sizeof(DTotals), s));
             HIPCHK(c, hipMemsetAsync(c->b_sc_gtot.p, 0, 16, s));
             HIPCHK(c, hipMemsetAsync(c->b_sc_mask.p, 0, (mwords + 2 + (n_pin || n_ev ? rwords + 2 : 0) + (n_ev ? bwords + 2 : 0)) * 4, s));
             if (n_ev) HIPCHK(c, hipMemcpyAsync(c->b_sc_bs.p, bsv.data(), ns * sizeof(DScBias), hipMemcpyHostToDevice, s)); // (counts and sums at zero: k_sce_mask appends again, also on a tie-scratch retry)
             if (n_pin) HIPCHK(c, hipMemsetAsync(q.kreq, 0, ns * 4, s)); // k_scp_mask counts again (also on a tie-scratch retry)
-            phxk_scen_mask(&b, &q, s);
-            if (n_pin) phxk_scen_pin_mask(&b, &q, s);
-            if (n_ev) phxk_scen_ev_mask(&b, &q, &qe, max_list, s);
+            phxk_scen_mask(&b, &q, n_range, max_list, s);
             HIPCHK(c, hipEventRecord(c->aev[1], s));
-            phxk_scen_solve(&b, &qa, nlm, s);
-            if (n_pin) phxk_scen_pin_solve(&b, &qb, pinm, s);
-            if (n_ev) phxk_scen_ev_solve(&b, &qe, evm, s);
+            phxk_scen_solve(&b, &q, n_range, nlms, s);
             HIPCHK(c, hipEventRecord(c->aev[2], s));
-            phxk_scen_finish(&b, &qa, nlm, s);
-            if (n_pin) phxk_scen_pin_finish(&b, &qb, pinm, s);
-            if (n_ev) phxk_scen_ev_finish(&b, &qe, evm, s);
+            phxk_scen_finish(&b, &q, n_range, nlms, s);
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, hipMemcpyAsync(c->h_schunk.data(), c->b_sc_rec.p, ns * sizeof(DReannRec), hipMemcpyDeviceToHost, s));
             HIPCHK(c, hipEventRecord(c->aev[3], s));

@@ -272,7 +272,7 @@ struct phx_ctx {
     std::vector<uint8_t> h_qforb;     // the sets last solved, tap order (one byte per ORF of the batch: 1 = refused, 2 = required)
     std::vector<uint8_t> h_qcode;     // ... of the call at hand
     std::vector<int32_t> h_qnreq;     // per contig: required ORFs (|R|)
-    std::vector<int32_t> h_qdsel;     // the per-contig arrays the kernels read (DReann.sel / pin / nreq / kreq / evs / rce)
+    std::vector<int32_t> h_qdsel;     // the per-contig arrays the kernels read (DReann.mode / nreq / kreq)
     int qstride = 2;                  // limbs per node of b_qdist: the run's, one more when a contig was solved under the required policy
     uint32_t h_qflags = 0;
     std::vector<int32_t> h_qsel;      // per contig: solved again (1; 2: under the required policy; 3: under the bias policy; 4: under both), else the run's result stands

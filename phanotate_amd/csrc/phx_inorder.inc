@@ -182,18 +182,16 @@ __device__ void walk_path(const DBatch &b, DMeta *meta, IoShared<IO_T> *sh) {
     __syncthreads();
 }
 
-// MASKED (phx_resolve.inc): `mask` holds one bit per in-edge slot of the batch (bit edge_off + e); a refused edge is no edge — it is never tight,
-// whatever the distances say.  The run's instantiations (MASKED = false) do not look at `mask`.
-// REQ (the pinned re-annotation, DESIGN.md §16; with MASKED, on one limb more than the contig's class): an edge whose bit is set in `req` weighs
-// W - 2^(64 (NL - 1)), as in the sweep that made the distances (lds_sweep under RcCfg).
-// BIAS (the evidence-weighted re-annotation, DESIGN.md §19; with MASKED): an edge whose bit is set in `bbit` weighs W + B, B the word of its
-// in-edge slot in `bval`, as in the sweep that made the distances (lds_sweep under EvCfg): a row is tight iff d[u] + W + B == d[v].
-// BLIST (a biased scenario slot, DESIGN.md §20; with BIAS): `bval` is the slot's sorted list of nbl (in-edge slot, B) pairs (bias_at, phx_sssp.inc).
-// REQ and BIAS together (the combined re-annotation, DESIGN.md §22; k_rce_inorder): the two are independent — a row that is required and biased
-// weighs W + B - 2^(64 (NL - 1)), so it is tight iff d[u] + W + B - M == d[v].
+// P: the policy of the sweep that made the distances (phx_sssp.inc: SwRun for the run, whose instantiations look at none of the pointers
+// below; RePol for a re-solve, phx_resolve.inc).  A row is tight iff d[u] + w == d[v] with w as that sweep added it:
+// MASKED: `mask` holds one bit per in-edge slot of the batch (bit edge_off + e); a refused edge is no edge — it is never tight, whatever the
+// distances say.  REQ (on one limb more than the contig's class): a row whose bit is set in `req` weighs W - 2^(64 (NL - 1)).  BIAS: a row
+// whose bit is set in `bbit` weighs W + B, B the word of its in-edge slot in `bval` — under BLIST the entry of the solve's sorted list of
+// nbl (in-edge slot, B) pairs (bias_at, phx_sssp.inc).  REQ and BIAS are independent: a row that is both weighs W + B - 2^(64 (NL - 1)).
 // ci: the contig's index in the batch (blockIdx.x where a workgroup is a contig; a scenario slot passes its slot's contig).
-template <int NL, int IO_T, bool MASKED = false, bool REQ = false, bool BIAS = false, bool BLIST = false>
+template <int NL, int IO_T, class P = SwRun>
 __device__ void inorder_contig(const DBatch &b, DMeta *meta, const uint32_t ci, IoShared<IO_T> *sh, const uint32_t *mask = nullptr, const uint32_t *req = nullptr, const uint32_t *bbit = nullptr, const long long *bval = nullptr, const int nbl = 0) {
+    constexpr bool MASKED = P::MASKED, REQ = P::REQ, BIAS = P::BIAS, BLIST = P::BLIST;
     const int tid = threadIdx.x;
     const uint64_t mbase = MASKED ? (uint64_t)meta->edge_off : 0ull;
     auto refused = [&](uint32_t e) -> bool { const uint64_t x = mbase + e; return ((mask[x >> 5] >> (x & 31)) & 1u) != 0; };
@@ -223,7 +221,7 @@ __device__ void inorder_contig(const DBatch &b, DMeta *meta, const uint32_t ci, 
         if constexpr (BIAS) {
             if (biased(e)) {
                 if constexpr (BLIST) w = wi_add<NL>(w, ew_decode<NL>(bias_at<true>(bval, mbase + e, nbl)));
-                else w = wi_add<NL>(w, ew_decode<NL>(bval[mbase + e])); // (bias_at<false>, written out: through the call k_ev_inorder came out with other scalar registers than it had)
+                else w = wi_add<NL>(w, ew_decode<NL>(bval[mbase + e])); // (bias_at<false>, written out: through the call the biased k_rs_inorder came out with other scalar registers than it had)
             }
         }
         return !wi_unreached<NL>(du) && wi_eq<NL>(wi_add<NL>(du, w), dv);

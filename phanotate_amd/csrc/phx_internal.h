@@ -377,7 +377,7 @@ struct DRepl {
     unsigned long long *cnt; // [2]: chain nodes placed, records with a bypass but no winner (0 unless a bug)
 };
 
-// Masked re-annotation (phx_resolve.inc), on demand after a run: the context's lazily allocated buffers.  The kernels' DBatch is the run's
+// Re-annotation (phx_resolve.inc), on demand after a run: the context's lazily allocated buffers.  The kernels' DBatch is the run's
 // with meta / tot / dist / parent / path / genes / gene_total / tie replaced by buffers of the re-annotation's own.
 struct DReannRec { // per contig that was solved again: what the host reads
     int32_t status, n_genes;
@@ -386,27 +386,26 @@ struct DReannRec { // per contig that was solved again: what the host reads
     int32_t n_path, tie;
     int32_t unmet, pad_;   // required ORFs the result does not call (all of them where there is no result)
 };
-struct DReann {
-    const uint8_t *forb;   // per ORF (at orf_off, device order): 1 = refused, 2 = required (pinned re-annotation, §16)
-    uint32_t *mask;        // one bit per in-edge slot of the batch (bit edge_off + e), cleared per call
-    const int32_t *sel;    // per contig: 1 = solve it again (no required ORF)
+// A contig's mode: 0 = the run's result stands, else it is solved again — 1 masked (§14), 2 under the required policy on one limb more
+// (§16), 3 under the bias policy in its own limb class (§19), 4 under both on one limb more (§22).  RePol<REQ, BIAS>::MODE on the device.
+#define RE_MODES 5
+static inline __host__ __device__ bool re_mode_req(int mode) { return mode == 2 || mode == 4; }
+static inline __host__ __device__ bool re_mode_bias(int mode) { return mode >= 3; }
+struct DReann { // (the order is the kernels' argument block: a field that moves moves their scalar loads)
+    const uint8_t *forb;   // per ORF (at orf_off, device order): 1 = refused, 2 = required
+    uint32_t *mask;        // one bit per in-edge slot of the batch (bit edge_off + e), cleared per call: the refused ORFs' edges
+    const int32_t *mode;   // per contig: its mode
     uint8_t *gplan;        // window plans beyond RS_PLAN_LDS windows: contig i at node_off / 32 + i
     const uint64_t *dist0; // the run's distances (D)
     DReannRec *rec;
-    // the pinned re-annotation (§16); behind the fields above, whose places in the kernels' argument block stay
-    uint32_t *req;         // as `mask`, for the required ORFs' edges (only touched when a contig has some)
-    const int32_t *pin;    // per contig: 1 = solve it again under the required policy, on one limb more (never with sel)
+    uint32_t *req;         // as `mask`: the required ORFs' edges (only touched when a contig has some)
     const int32_t *nreq;   // per contig: required ORFs (|R|)
     int32_t *kreq;         // per contig: required ORFs whose edge exists (k_rs_mask counts them): the bound of the solver's cycle guard
     int32_t stride0;       // limbs per node of dist0 (the run's DBatch.dist_stride; the re-annotation's own may be one wider)
-    // the evidence-weighted re-annotation (§19); behind the fields above, whose places in the kernels' argument block stay
-    const int32_t *evs;    // per contig: 1 = solve it again under the bias policy, in its own limb class (never with sel or pin)
-    const long long *bias; // per ORF (at orf_off, device order): B in 1/1000 SCORE units, 0 = no evidence
+    const long long *bias; // per ORF (at orf_off, device order): B in 1/1000 SCORE units, 0 = no evidence (read for the modes with a bias only)
     uint32_t *bbit;        // as `mask`: the in-edge slots that carry a bias (only touched when a contig has some)
     long long *bval;       // per in-edge slot of the batch (at edge_off + e): B; never cleared, read only where the slot's bit is set
     unsigned long long *bsum; // per contig [2]: the sums of |B| & 0xffffffff and of |B| >> 32 over its biased edges, zeroed per call
-    // the combined re-annotation (§22); behind the fields above, whose places in the kernels' argument block stay
-    const int32_t *rce;    // per contig: 1 = solve it again under the required and the bias policy together, on one limb more (never with sel, pin or evs)
 };
 
 // Scenario batches (phx_resolve.inc): S masked re-annotations side by side, one workgroup per scenario slot.  A slot is one
@@ -444,14 +443,14 @@ struct DScen {
     uint8_t *gplan;
     const uint64_t *dist0; // the run's distances (D)
     DReannRec *rec;      // per slot: what the host reads
-    // pinned scenarios (§18); behind the fields above, whose places in the argument block of k_sc_* stay
+    // pinned scenarios (§18)
     uint32_t *req;       // the required bitmap slices of the pinned slots, cleared per chunk
     const int64_t *req0; // per slot: first word of its required slice in req (the bit rule of mask0)
     const int32_t *nreq; // per slot: required ORFs (|R|)
     int32_t *kreq;       // per slot: required ORFs whose edge exists (k_scp_mask counts them): the bound of the solver's cycle guard
     const int2 *rpair;   // the required (slot, ORF in the contig's device order) pairs of the chunk
     int64_t n_rpair;
-    // evidence scenarios (§20); behind the fields above, whose places in the argument blocks of k_sc_* and k_scp_* stay
+    // evidence scenarios (§20)
     uint32_t *bbit;      // the bias bitmap slices of the biased slots, cleared per chunk
     DScBias *bs;         // per slot: where its bias slice and list lie, and what k_sce_mask counted and summed (biased slots only)
     long long *blist;    // the slots' lists: (in-edge slot of the batch: edge_off + e, B) pairs, 16 bytes each, sorted by in-edge slot (k_sce_sort)
@@ -521,27 +520,18 @@ void phxk_drop_fix(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask,
 void phxk_repl_pick(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream); // drop replacements (phx_replace.inc): winners,
 void phxk_repl_cross(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream); //   cross winners and their delta chains,
 void phxk_repl_walk(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int fill, void *stream);    //   detour lengths (fill 0) / detours, genes, records (1)
-void phxk_reann_mask(const DBatch *b, const DReann *q, void *stream);                 // masked re-annotation (phx_resolve.inc): the refused ORFs' in-edge bits,
-void phxk_reann_solve(const DBatch *b, const DReann *q, int nl_mask, int pin_mask, void *stream);   //   the masked sweep (b: the re-annotation's view of the batch; pin_mask: the classes with required ORFs),
-void phxk_reann_finish(const DBatch *b, const DReann *q, int nl_mask, int pin_mask, void *stream);  //   in-order parents on G_F, path, genes, delta
-void phxk_evid_mask(const DBatch *b, const DReann *q, void *stream);                // evidence-weighted re-annotation (§19): the biased ORFs' words, bits and sums,
-void phxk_evid_solve(const DBatch *b, const DReann *q, int ev_mask, void *stream);  //   the sweep under the bias policy (ev_mask: the classes with biased ORFs),
-void phxk_evid_finish(const DBatch *b, const DReann *q, int ev_mask, void *stream); //   in-order parents on G_{F,B}, path, genes, delta
+// re-annotation (phx_resolve.inc).  b: the re-annotation's view of the batch; nl_masks[RE_MODES]: per mode, the limb classes of its contigs
+void phxk_reann_mask(const DBatch *b, const DReann *q, void *stream);                         // the refused, required and biased ORFs' marks,
+void phxk_reann_solve(const DBatch *b, const DReann *q, const int *nl_masks, void *stream);   //   the sweep under each mode's policy,
+void phxk_reann_finish(const DBatch *b, const DReann *q, const int *nl_masks, void *stream);  //   in-order parents, path, genes; delta and unmet
 void phxk_remarg_apply(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, void *stream);               // re-annotation margins (§21; b: the run's batch): the refused / biased out-edge positions,
 void phxk_remarg_rev(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, int nl_mask, void *stream);     //   the conditioned reverse pass (nl_mask: the classes among DRmarg.sel == 1),
 void phxk_remarg_records(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, int nl_mask, void *stream); //   the ORF records (nl_mask: the classes among DRmarg.sel != 0)
-void phxk_curate_mask(const DBatch *b, const DReann *q, void *stream);                 // combined re-annotation (§22): the refused, required and biased ORFs' marks,
-void phxk_curate_solve(const DBatch *b, const DReann *q, int rce_mask, void *stream);  //   the sweep under both policies (rce_mask: the classes with required and biased ORFs),
-void phxk_curate_finish(const DBatch *b, const DReann *q, int rce_mask, void *stream); //   in-order parents, path, genes, delta, unmet
-void phxk_scen_mask(const DBatch *b, const DScen *q, void *stream);                 // scenario batches (phx_resolve.inc): the slots' records and bitmap slices (b: the run's batch),
-void phxk_scen_solve(const DBatch *b, const DScen *q, int nl_mask, void *stream);   //   the masked sweep, a workgroup per slot (b: the run's graph, tot / genes / gene_total / tie the scenarios' own),
-void phxk_scen_finish(const DBatch *b, const DScen *q, int nl_mask, void *stream);  //   in-order parents, path, genes, delta per slot
-void phxk_scen_pin_mask(const DBatch *b, const DScen *q, void *stream);                 // pinned scenarios (§18): the required slices and counts (q: the whole slot table),
-void phxk_scen_pin_solve(const DBatch *b, const DScen *q, int pin_mask, void *stream);  //   the sweep under the required policy (q: the table's pinned tail; pin_mask: its classes),
-void phxk_scen_pin_finish(const DBatch *b, const DScen *q, int pin_mask, void *stream); //   in-order parents, path, genes, delta and unmet per pinned slot
-void phxk_scen_ev_mask(const DBatch *b, const DScen *q, const DScen *tail, int max_list, void *stream); // evidence scenarios (§20): the bias slices, lists and sums (q: the whole slot table), the lists sorted (tail: the biased tail; max_list: its longest list),
-void phxk_scen_ev_solve(const DBatch *b, const DScen *q, int ev_mask, void *stream);    //   the sweep under the bias policy with the sparse lookup (q: the table's biased tail; ev_mask: its classes),
-void phxk_scen_ev_finish(const DBatch *b, const DScen *q, int ev_mask, void *stream);   //   in-order parents, path, genes, delta per biased slot
+// scenario batches (§17, §18, §20).  b: the run's graph, tot / genes / gene_total / tie the scenarios' own; q: the chunk's whole slot table;
+// n_range[3]: its plain, pinned and biased slots, in that order; nl_masks[3]: per range, the limb classes of its slots
+void phxk_scen_mask(const DBatch *b, const DScen *q, const int *n_range, int max_list, void *stream);     // the slots' records, slices, counts and lists (max_list: the longest bias list),
+void phxk_scen_solve(const DBatch *b, const DScen *q, const int *n_range, const int *nl_masks, void *stream);  //   the sweep, a workgroup per slot, under each range's policy,
+void phxk_scen_finish(const DBatch *b, const DScen *q, const int *n_range, const int *nl_masks, void *stream); //   in-order parents, path, genes; delta and unmet per slot
 #ifdef __cplusplus
 }
 #endif

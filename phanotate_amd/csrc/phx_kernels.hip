@@ -192,11 +192,51 @@ static void launch_certify(const DBatch *b, int vcap, hipStream_t s) {
     hipLaunchKernelGGL(k_certify<NL>, dim3(b->n_contig), dim3(CERT_T), lds, s, *b, vcap);
     hipLaunchKernelGGL(k_certify_wide<NL>, dim3(b->n_contig), dim3(CERT_T), 0, s, *b);
 }
-// a workgroup of SW_THREADS per contig with `lds` bytes of dynamic LDS (k_sssp_lds, k_rs_lds: one instantiation per limb class)
+// `grid` workgroups of SW_THREADS with `lds` bytes of dynamic LDS (k_sssp_lds, k_rs_lds, k_sc_lds: one instantiation per limb class)
 template <class... A>
-static void launch_lds(void (*k)(A...), size_t lds, const DBatch *b, hipStream_t s, A... args) {
+static void launch_lds(void (*k)(A...), size_t lds, unsigned grid, hipStream_t s, A... args) {
     (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k, dim3(b->n_contig), dim3(SW_THREADS), lds, s, args...);
+    hipLaunchKernelGGL(k, dim3(grid), dim3(SW_THREADS), lds, s, args...);
+}
+// The re-annotation's two solver kernels by what they are launched on: DReann — the batch, a workgroup per contig —, DScen — a range of a
+// chunk's slot table, a workgroup per slot (phx_resolve.inc).
+template <int NL, class Pol> static auto re_lds_kernel(const DReann *) { return k_rs_lds<NL, Pol>; }
+template <int NL, class Pol> static auto re_lds_kernel(const DScen *) { return k_sc_lds<NL, Pol>; }
+template <int NL, int T, class Pol> static auto re_inorder_kernel(const DReann *) { return k_rs_inorder<NL, T, Pol>; }
+template <int NL, int T, class Pol> static auto re_inorder_kernel(const DScen *) { return k_sc_inorder<NL, T, Pol>; }
+// the sweep under Pol for every limb class of nlm (bit k: 2, 4, 8, 17 limbs), `grid` workgroups
+template <class Pol, class Q>
+static void re_solve(const DBatch *b, const Q *q, unsigned grid, int nlm, hipStream_t s) {
+    if (!grid) return;
+    if (nlm & 1) launch_lds(re_lds_kernel<2, Pol>(q), ReSw<2, Pol>::LDS, grid, s, *b, *q);
+    if (nlm & 2) launch_lds(re_lds_kernel<4, Pol>(q), ReSw<4, Pol>::LDS, grid, s, *b, *q);
+    if (nlm & 4) launch_lds(re_lds_kernel<8, Pol>(q), ReSw<8, Pol>::LDS, grid, s, *b, *q);
+    if (nlm & 8) launch_lds(re_lds_kernel<17, Pol>(q), ReSw<17, Pol>::LDS, grid, s, *b, *q);
+}
+// ... and the in-order pass: as phxk_inorder, one wavefront per short contig, else 256 threads
+template <int T, class Pol, class Q>
+static void re_inorder_t(const DBatch *b, const Q *q, unsigned grid, int nlm, hipStream_t s) {
+    if (nlm & 1) hipLaunchKernelGGL((re_inorder_kernel<2, T, Pol>(q)), dim3(grid), dim3(T), 0, s, *b, *q);
+    if (nlm & 2) hipLaunchKernelGGL((re_inorder_kernel<4, T, Pol>(q)), dim3(grid), dim3(T), 0, s, *b, *q);
+    if (nlm & 4) hipLaunchKernelGGL((re_inorder_kernel<8, T, Pol>(q)), dim3(grid), dim3(T), 0, s, *b, *q);
+    if (nlm & 8) hipLaunchKernelGGL((re_inorder_kernel<17, T, Pol>(q)), dim3(grid), dim3(T), 0, s, *b, *q);
+}
+template <class Pol, class Q>
+static void re_inorder_launch(const DBatch *b, const Q *q, unsigned grid, int nlm, hipStream_t s) {
+    if (!grid) return;
+    if (b->mean_len < 8192) re_inorder_t<64, Pol>(b, q, grid, nlm, s);
+    else re_inorder_t<IO_T_FULL, Pol>(b, q, grid, nlm, s);
+}
+// Range r of a chunk's slot table (0 plain, 1 pinned, 2 biased; n_range: their slot counts) as a table of its own, so that blockIdx.x is a
+// slot of the range: the per-slot arrays moved to the range's first slot.  The pair and triple lists stay the whole table's.
+static DScen scen_range(const DScen &q, const int *n_range, int r) {
+    DScen t = q;
+    const int first = (r > 0 ? n_range[0] : 0) + (r > 1 ? n_range[1] : 0);
+    t.n_slot = n_range[r];
+    t.slot += first; t.meta += first; t.rec += first;
+    if (t.req0) { t.req0 += first; t.nreq += first; t.kreq += first; }
+    if (t.bs) t.bs += first;
+    return t;
 }
 extern "C" {
 void phxk_features(const DBatch *b, uint32_t v_begin, uint32_t v_end, void *stream) {
@@ -372,13 +412,6 @@ void phxk_margins_transpose(const DBatch *b, const DMarg *g, void *stream) {
         if ((NLM) & 4) hipLaunchKernelGGL(K<8>, GRID, BLOCK, 0, s, __VA_ARGS__); \
         if ((NLM) & 8) hipLaunchKernelGGL(K<17>, GRID, BLOCK, 0, s, __VA_ARGS__); \
     } while (0)
-// ... the same for K<n_limbs, T>, a kernel of T threads
-#define NL_LAUNCH_T(K, T, NLM, GRID, ...) do { \
-        if ((NLM) & 1) hipLaunchKernelGGL((K<2, T>), GRID, dim3(T), 0, s, __VA_ARGS__); \
-        if ((NLM) & 2) hipLaunchKernelGGL((K<4, T>), GRID, dim3(T), 0, s, __VA_ARGS__); \
-        if ((NLM) & 4) hipLaunchKernelGGL((K<8, T>), GRID, dim3(T), 0, s, __VA_ARGS__); \
-        if ((NLM) & 8) hipLaunchKernelGGL((K<17, T>), GRID, dim3(T), 0, s, __VA_ARGS__); \
-    } while (0)
 void phxk_sssp_rev(const DBatch *b, const DMarg *g, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH(k_sssp_rev, nl_mask, dim3(b->n_contig), dim3(NT), *b, *g); }
 void phxk_margins(const DBatch *b, const DMarg *g, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH(k_margins, nl_mask, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), *b, *g); }
 // re-annotation margins (phx_margins.inc, §21): k_sssp_rev and k_margins under MgCond, whose DMarg part is the run's (the out-edge CSR)
@@ -410,136 +443,51 @@ void phxk_repl_walk(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl
     else hipLaunchKernelGGL(k_rp_walk<0>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q, *r);
 }
 size_t phxk_sssp_lds_bytes(int V, int nl) { return sssp_lds_bytes(V, nl); }
-// masked re-annotation (phx_resolve.inc): b is the re-annotation's view of the batch (outputs of its own)
+// re-annotation (phx_resolve.inc): b is the re-annotation's view of the batch (outputs of its own)
 void phxk_reann_mask(const DBatch *b, const DReann *q, void *stream) { hipLaunchKernelGGL(k_rs_mask, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), 0, (hipStream_t)stream, *b, *q); }
-void phxk_reann_solve(const DBatch *b, const DReann *q, int nl_mask, int pin_mask, void *stream) {
+void phxk_reann_solve(const DBatch *b, const DReann *q, const int *nl_masks, void *stream) {
     hipStream_t s = (hipStream_t)stream;
-    if (nl_mask & 1) launch_lds(k_rs_lds<2>, rs_lds_bytes<2>(), b, s, *b, *q);
-    if (nl_mask & 2) launch_lds(k_rs_lds<4>, rs_lds_bytes<4>(), b, s, *b, *q);
-    if (nl_mask & 4) launch_lds(k_rs_lds<8>, rs_lds_bytes<8>(), b, s, *b, *q);
-    if (nl_mask & 8) launch_lds(k_rs_lds<17>, rs_lds_bytes<17>(), b, s, *b, *q);
-    // pin_mask: the classes of the contigs with required ORFs (solved on one limb more, §16)
-    if (pin_mask & 1) launch_lds(k_rc_lds<2>, rc_lds_bytes<3>(), b, s, *b, *q);
-    if (pin_mask & 2) launch_lds(k_rc_lds<4>, rc_lds_bytes<5>(), b, s, *b, *q);
-    if (pin_mask & 4) launch_lds(k_rc_lds<8>, rc_lds_bytes<9>(), b, s, *b, *q);
-    if (pin_mask & 8) launch_lds(k_rc_lds<17>, rc_lds_bytes<18>(), b, s, *b, *q);
+    const unsigned g = (unsigned)b->n_contig;
+    re_solve<RePol<false, false>>(b, q, g, nl_masks[1], s);
+    re_solve<RePol<true, false>>(b, q, g, nl_masks[2], s);
+    re_solve<RePol<false, true>>(b, q, g, nl_masks[3], s);
+    re_solve<RePol<true, true>>(b, q, g, nl_masks[4], s);
 }
-void phxk_reann_finish(const DBatch *b, const DReann *q, int nl_mask, int pin_mask, void *stream) {
+void phxk_reann_finish(const DBatch *b, const DReann *q, const int *nl_masks, void *stream) {
     hipStream_t s = (hipStream_t)stream;
-    if (b->mean_len < 8192) NL_LAUNCH_T(k_rs_inorder, 64, nl_mask, dim3(b->n_contig), *b, *q); // as phxk_inorder: one wavefront per short contig
-    else NL_LAUNCH_T(k_rs_inorder, IO_T_FULL, nl_mask, dim3(b->n_contig), *b, *q);
-    if (b->mean_len < 8192) NL_LAUNCH_T(k_rc_inorder, 64, pin_mask, dim3(b->n_contig), *b, *q);
-    else NL_LAUNCH_T(k_rc_inorder, IO_T_FULL, pin_mask, dim3(b->n_contig), *b, *q);
-    hipLaunchKernelGGL(k_rs_fin, dim3((unsigned)((b->n_contig + 63) / 64)), dim3(64), 0, s, *b, *q);
+    const unsigned g = (unsigned)b->n_contig;
+    re_inorder_launch<RePol<false, false>>(b, q, g, nl_masks[1], s);
+    re_inorder_launch<RePol<true, false>>(b, q, g, nl_masks[2], s);
+    re_inorder_launch<RePol<false, true>>(b, q, g, nl_masks[3], s);
+    re_inorder_launch<RePol<true, true>>(b, q, g, nl_masks[4], s);
+    hipLaunchKernelGGL(k_rs_fin, dim3((g + 63) / 64), dim3(64), 0, s, *b, *q);
 }
-// evidence-weighted re-annotation: the contigs of DReann.evs, beside the two above on the same view of the batch
-void phxk_evid_mask(const DBatch *b, const DReann *q, void *stream) { hipLaunchKernelGGL(k_ev_mask, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), 0, (hipStream_t)stream, *b, *q); }
-void phxk_evid_solve(const DBatch *b, const DReann *q, int ev_mask, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (ev_mask & 1) launch_lds(k_ev_lds<2>, rs_lds_bytes<2>(), b, s, *b, *q);
-    if (ev_mask & 2) launch_lds(k_ev_lds<4>, rs_lds_bytes<4>(), b, s, *b, *q);
-    if (ev_mask & 4) launch_lds(k_ev_lds<8>, rs_lds_bytes<8>(), b, s, *b, *q);
-    if (ev_mask & 8) launch_lds(k_ev_lds<17>, rs_lds_bytes<17>(), b, s, *b, *q);
-}
-void phxk_evid_finish(const DBatch *b, const DReann *q, int ev_mask, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (b->mean_len < 8192) NL_LAUNCH_T(k_ev_inorder, 64, ev_mask, dim3(b->n_contig), *b, *q); // as phxk_reann_finish
-    else NL_LAUNCH_T(k_ev_inorder, IO_T_FULL, ev_mask, dim3(b->n_contig), *b, *q);
-    hipLaunchKernelGGL(k_ev_fin, dim3((unsigned)((b->n_contig + 63) / 64)), dim3(64), 0, s, *b, *q);
-}
-// combined re-annotation: the contigs of DReann.rce, beside the three above on the same view of the batch
-void phxk_curate_mask(const DBatch *b, const DReann *q, void *stream) { hipLaunchKernelGGL(k_rce_mask, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), 0, (hipStream_t)stream, *b, *q); }
-void phxk_curate_solve(const DBatch *b, const DReann *q, int rce_mask, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (rce_mask & 1) launch_lds(k_rce_lds<2>, rc_lds_bytes<3>(), b, s, *b, *q);
-    if (rce_mask & 2) launch_lds(k_rce_lds<4>, rc_lds_bytes<5>(), b, s, *b, *q);
-    if (rce_mask & 4) launch_lds(k_rce_lds<8>, rc_lds_bytes<9>(), b, s, *b, *q);
-    if (rce_mask & 8) launch_lds(k_rce_lds<17>, rc_lds_bytes<18>(), b, s, *b, *q);
-}
-void phxk_curate_finish(const DBatch *b, const DReann *q, int rce_mask, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (b->mean_len < 8192) NL_LAUNCH_T(k_rce_inorder, 64, rce_mask, dim3(b->n_contig), *b, *q); // as phxk_reann_finish
-    else NL_LAUNCH_T(k_rce_inorder, IO_T_FULL, rce_mask, dim3(b->n_contig), *b, *q);
-    hipLaunchKernelGGL(k_rce_fin, dim3((unsigned)((b->n_contig + 63) / 64)), dim3(64), 0, s, *b, *q);
-}
-// scenario batches: the grids are the chunk's slots (pairs for k_sc_mask), not the batch's contigs
-void phxk_scen_mask(const DBatch *b, const DScen *q, void *stream) {
+// scenario batches: the grids are a range's slots (pairs and triples for the mask kernels), not the batch's contigs
+void phxk_scen_mask(const DBatch *b, const DScen *q, const int *n_range, int max_list, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     if (q->n_slot <= 0) return;
     hipLaunchKernelGGL(k_sc_meta, dim3((unsigned)q->n_slot), dim3(64), 0, s, *b, *q);
     if (q->n_pair > 0) hipLaunchKernelGGL(k_sc_mask, dim3((unsigned)((q->n_pair + NT - 1) / NT)), dim3(NT), 0, s, *b, *q);
-}
-extern "C++" template <int NL>
-static void launch_sc_lds(const DBatch *b, const DScen *q, hipStream_t s) {
-    (void)hipFuncSetAttribute((const void *)k_sc_lds<NL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rs_lds_bytes<NL>());
-    hipLaunchKernelGGL(k_sc_lds<NL>, dim3((unsigned)q->n_slot), dim3(SW_THREADS), rs_lds_bytes<NL>(), s, *b, *q);
-}
-void phxk_scen_solve(const DBatch *b, const DScen *q, int nl_mask, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (q->n_slot <= 0) return;
-    if (nl_mask & 1) launch_sc_lds<2>(b, q, s);
-    if (nl_mask & 2) launch_sc_lds<4>(b, q, s);
-    if (nl_mask & 4) launch_sc_lds<8>(b, q, s);
-    if (nl_mask & 8) launch_sc_lds<17>(b, q, s);
-}
-void phxk_scen_finish(const DBatch *b, const DScen *q, int nl_mask, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (q->n_slot <= 0) return;
-    if (b->mean_len < 8192) NL_LAUNCH_T(k_sc_inorder, 64, nl_mask, dim3((unsigned)q->n_slot), *b, *q); // as phxk_reann_finish
-    else NL_LAUNCH_T(k_sc_inorder, IO_T_FULL, nl_mask, dim3((unsigned)q->n_slot), *b, *q);
-    hipLaunchKernelGGL(k_sc_fin, dim3((unsigned)((q->n_slot + 63) / 64)), dim3(64), 0, s, *b, *q);
-}
-// pinned scenarios: the solve and the finish get the pinned tail of the slot table
-void phxk_scen_pin_mask(const DBatch *b, const DScen *q, void *stream) {
-    if (q->n_slot <= 0 || q->n_rpair <= 0) return;
-    hipLaunchKernelGGL(k_scp_mask, dim3((unsigned)((q->n_rpair + NT - 1) / NT)), dim3(NT), 0, (hipStream_t)stream, *b, *q);
-}
-extern "C++" template <int NL>
-static void launch_scp_lds(const DBatch *b, const DScen *q, hipStream_t s) {
-    (void)hipFuncSetAttribute((const void *)k_scp_lds<NL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rc_lds_bytes<NL + 1>());
-    hipLaunchKernelGGL(k_scp_lds<NL>, dim3((unsigned)q->n_slot), dim3(SW_THREADS), rc_lds_bytes<NL + 1>(), s, *b, *q);
-}
-void phxk_scen_pin_solve(const DBatch *b, const DScen *q, int pin_mask, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (q->n_slot <= 0) return;
-    if (pin_mask & 1) launch_scp_lds<2>(b, q, s);
-    if (pin_mask & 2) launch_scp_lds<4>(b, q, s);
-    if (pin_mask & 4) launch_scp_lds<8>(b, q, s);
-    if (pin_mask & 8) launch_scp_lds<17>(b, q, s);
-}
-void phxk_scen_pin_finish(const DBatch *b, const DScen *q, int pin_mask, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (q->n_slot <= 0) return;
-    if (b->mean_len < 8192) NL_LAUNCH_T(k_scp_inorder, 64, pin_mask, dim3((unsigned)q->n_slot), *b, *q); // as phxk_scen_finish
-    else NL_LAUNCH_T(k_scp_inorder, IO_T_FULL, pin_mask, dim3((unsigned)q->n_slot), *b, *q);
-    hipLaunchKernelGGL(k_scp_fin, dim3((unsigned)((q->n_slot + 63) / 64)), dim3(64), 0, s, *b, *q);
-}
-// evidence scenarios: the solve and the finish get the biased tail of the slot table
-void phxk_scen_ev_mask(const DBatch *b, const DScen *q, const DScen *tail, int max_list, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (q->n_slot <= 0 || tail->n_slot <= 0 || q->n_trip <= 0) return;
+    if (n_range[1] > 0 && q->n_rpair > 0) hipLaunchKernelGGL(k_scp_mask, dim3((unsigned)((q->n_rpair + NT - 1) / NT)), dim3(NT), 0, s, *b, *q);
+    if (n_range[2] <= 0 || q->n_trip <= 0) return;
     hipLaunchKernelGGL(k_sce_mask, dim3((unsigned)((q->n_trip + NT - 1) / NT)), dim3(NT), 0, s, *b, *q);
-    if (max_list > 1) hipLaunchKernelGGL(k_sce_sort, dim3((unsigned)tail->n_slot, (unsigned)std::min((max_list + NT - 1) / NT, 16)), dim3(NT), 0, s, *tail); // (up to 16 workgroups share the longest list)
+    if (max_list > 1) hipLaunchKernelGGL(k_sce_sort, dim3((unsigned)n_range[2], (unsigned)std::min((max_list + NT - 1) / NT, 16)), dim3(NT), 0, s, scen_range(*q, n_range, 2)); // (up to 16 workgroups share the longest list)
 }
-extern "C++" template <int NL>
-static void launch_sce_lds(const DBatch *b, const DScen *q, hipStream_t s) {
-    (void)hipFuncSetAttribute((const void *)k_sce_lds<NL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rs_lds_bytes<NL>());
-    hipLaunchKernelGGL(k_sce_lds<NL>, dim3((unsigned)q->n_slot), dim3(SW_THREADS), rs_lds_bytes<NL>(), s, *b, *q);
+void phxk_scen_solve(const DBatch *b, const DScen *q, const int *n_range, const int *nl_masks, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const DScen plain = scen_range(*q, n_range, 0), pinned = scen_range(*q, n_range, 1), biased = scen_range(*q, n_range, 2);
+    re_solve<RePol<false, false>>(b, &plain, (unsigned)n_range[0], nl_masks[0], s);
+    re_solve<RePol<true, false>>(b, &pinned, (unsigned)n_range[1], nl_masks[1], s);
+    re_solve<RePol<false, true, true>>(b, &biased, (unsigned)n_range[2], nl_masks[2], s);
 }
-void phxk_scen_ev_solve(const DBatch *b, const DScen *q, int ev_mask, void *stream) {
+void phxk_scen_finish(const DBatch *b, const DScen *q, const int *n_range, const int *nl_masks, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     if (q->n_slot <= 0) return;
-    if (ev_mask & 1) launch_sce_lds<2>(b, q, s);
-    if (ev_mask & 2) launch_sce_lds<4>(b, q, s);
-    if (ev_mask & 4) launch_sce_lds<8>(b, q, s);
-    if (ev_mask & 8) launch_sce_lds<17>(b, q, s);
-}
-void phxk_scen_ev_finish(const DBatch *b, const DScen *q, int ev_mask, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (q->n_slot <= 0) return;
-    if (b->mean_len < 8192) NL_LAUNCH_T(k_sce_inorder, 64, ev_mask, dim3((unsigned)q->n_slot), *b, *q); // as phxk_scen_finish
-    else NL_LAUNCH_T(k_sce_inorder, IO_T_FULL, ev_mask, dim3((unsigned)q->n_slot), *b, *q);
-    hipLaunchKernelGGL(k_sc_fin, dim3((unsigned)((q->n_slot + 63) / 64)), dim3(64), 0, s, *b, *q); // (a biased slot's record is a plain slot's)
+    const DScen plain = scen_range(*q, n_range, 0), pinned = scen_range(*q, n_range, 1), biased = scen_range(*q, n_range, 2);
+    re_inorder_launch<RePol<false, false>>(b, &plain, (unsigned)n_range[0], nl_masks[0], s);
+    re_inorder_launch<RePol<true, false>>(b, &pinned, (unsigned)n_range[1], nl_masks[1], s);
+    re_inorder_launch<RePol<false, true, true>>(b, &biased, (unsigned)n_range[2], nl_masks[2], s);
+    hipLaunchKernelGGL(k_sc_fin, dim3((unsigned)((q->n_slot + 63) / 64)), dim3(64), 0, s, *b, *q);
 }
 // one workgroup for up to 1024 contigs; larger batches in two passes of a workgroup per 256 contigs
 void phxk_layout1(const DBatch *b, void *stream) {
@@ -627,10 +575,10 @@ void phxk_sssp(const DBatch *b, int nl, int mode, size_t lds_bytes, void *stream
         return;
     }
     switch (nl) {
-    case 2: launch_lds(k_sssp_lds<2>, lds_bytes, b, s, *b, mode, (int)lds_bytes); break;
-    case 4: launch_lds(k_sssp_lds<4>, lds_bytes, b, s, *b, mode, (int)lds_bytes); break;
-    case 8: launch_lds(k_sssp_lds<8>, lds_bytes, b, s, *b, mode, (int)lds_bytes); break;
-    default: launch_lds(k_sssp_lds<17>, lds_bytes, b, s, *b, mode, (int)lds_bytes); break;
+    case 2: launch_lds(k_sssp_lds<2>, lds_bytes, (unsigned)b->n_contig, s, *b, mode, (int)lds_bytes); break;
+    case 4: launch_lds(k_sssp_lds<4>, lds_bytes, (unsigned)b->n_contig, s, *b, mode, (int)lds_bytes); break;
+    case 8: launch_lds(k_sssp_lds<8>, lds_bytes, (unsigned)b->n_contig, s, *b, mode, (int)lds_bytes); break;
+    default: launch_lds(k_sssp_lds<17>, lds_bytes, (unsigned)b->n_contig, s, *b, mode, (int)lds_bytes); break;
     }
 }
 }

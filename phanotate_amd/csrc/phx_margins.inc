@@ -84,7 +84,7 @@ __global__ __launch_bounds__(NT) void k_mg_fill(DBatch b, DMarg g) {
 //               (B = r.bval[edge_off + e], |B| <= 2^52: ew_decode reads it as the plain integer it is).  Values go to r.dist_t, the
 //               verdict to r.mstat; the run's dist_t / mstat (shared with §12 / §13) are not touched.  Contigs: r.sel == 1.
 //   k_margins   d_s' from r.ds, d_t' from r.dist_t, D' = d_s'(target); the ORF's in-edge slot is tested in DReann.mask (refused: through =
-//               0) and, for a contig solved under the bias policy (DReann.evs), carries DReann.bval where its bit is set in DReann.bbit.
+//               0) and, for a contig solved under the bias policy (DReann.mode), carries DReann.bval where its bit is set in DReann.bbit.
 //               Contigs: r.sel != 0 whose reverse pass settled (sel 2 — the re-solve found no path —: D' is unreached, every record through = 0).
 struct MgCond : DMarg { DReann q; DRmarg r; };
 template <class G> constexpr bool mg_cond = !std::is_same<G, DMarg>::value;
@@ -263,7 +263,7 @@ __global__ __launch_bounds__(NT) void k_margins(DBatch b, G g) {
     else { ds = b.dist + (size_t)meta->node_off * b.dist_stride; dt = g.dist_t + (size_t)meta->node_off * b.dist_stride; rec = g.rec + meta->orf_off; }
     [[maybe_unused]] const uint64_t ebase = (uint64_t)meta->edge_off;
     [[maybe_unused]] bool biased = false;
-    if constexpr (COND) biased = g.q.evs[blockIdx.x] != 0;
+    if constexpr (COND) biased = re_mode_bias(g.q.mode[blockIdx.x]);
     const WInt<NL> D = wi_load<NL>(ds + (size_t)(V - 1) * NL);
     const bool d_ok = !wi_unreached<NL>(D);
     for (int k = (int)blockIdx.y * NT + (int)threadIdx.x; k < meta->n_orf; k += (int)gridDim.y * NT) {
@@ -304,7 +304,7 @@ __global__ __launch_bounds__(NT) void k_margins(DBatch b, G g) {
 // layout, read only), DReann what the re-annotation left resident, DRmarg the feature's own buffers.  A thread per ORF of the contigs with
 // DRmarg.sel == 1: a refused or biased ORF (DReann.forb / bias, device ORF order) finds its out-edge in the CSR — the graph stage refuses
 // parallel edges, so the head v is unique in u's range — and sets that position's bit in fbit or bbit; a bias writes B to the position's
-// word.  Refusal wins over a bias, as in k_ev_mask.  An ORF without an edge is ignored.  Every index is checked against the contig's own
+// word.  Refusal wins over a bias, as in k_rs_mask.  An ORF without an edge is ignored.  Every index is checked against the contig's own
 // ranges before use.  The CSR itself is only read.
 __global__ __launch_bounds__(NT) void k_rmg_apply(DBatch b, DMarg g, DReann q, DRmarg r) {
     const DMeta *meta = &b.meta[blockIdx.x];
@@ -313,7 +313,7 @@ __global__ __launch_bounds__(NT) void k_rmg_apply(DBatch b, DMarg g, DReann q, D
     const DGrp *grp = b.grp + meta->grp_off;
     const int32_t *onode = b.onode + meta->orf_off;
     const uint8_t *forb = q.forb + meta->orf_off;
-    const bool biased = q.evs[blockIdx.x] != 0;
+    const bool biased = re_mode_bias(q.mode[blockIdx.x]);
     const long long *bias = biased ? q.bias + meta->orf_off : nullptr;
     const uint32_t *oo = g.out_off + meta->node_off + blockIdx.x;
     const uint32_t *od = g.out_dst + meta->edge_off;

@@ -346,24 +346,23 @@ __device__ __forceinline__ uint32_t u32_row_min(uint32_t x, int sub) {
 __host__ __device__ inline size_t sssp_lds_bytes(int V, int nl) {
     return (size_t)(SW_RING + 1) * nl * 8 + (size_t)SW_ECAP * ((size_t)nl * 8 + 4) + (size_t)(V / SW_ADV + 1) + 64;
 }
-// What differs between the two kernels that run the sweep below:
-//   SwRun       the run (k_sssp_lds): rows are plain ew[e] (expand_contig has completed them), the mask is never read, gpack is honoured;
-//   RsCfg<NL>   the masked re-annotation (k_rs_lds, phx_resolve.inc): MASKED, its own ring and tile sizes per limb class.
+// What differs between the kernels that run the sweep below is its policy P: ring and tile sizes (RING, ECAP) and four switches.
+//   SwRun            the run (k_sssp_lds): rows are plain ew[e] (expand_contig has completed them), no mark is ever read, gpack is honoured;
+//   ReSw<NL, RePol>  a re-solve (k_rs_lds, k_sc_lds; phx_resolve.inc, which says what the switches mean to the caller): always MASKED.
 // MASKED: the rows come through edge_wenc (coded gap edges from the contig's gap table, nothing written to DBatch.ew); an explicit row
 // whose bit is set in `mask` (one bit per in-edge slot of the batch) is no edge; the plan lives in LDS up to RS_PLAN_LDS windows, else in
 // the caller's `gplan`; gene slots always come from the shared counter.
-// REQ (the pinned re-annotation, RcCfg in phx_resolve.inc; always MASKED too): the sweep runs on one limb more than the contig's class, an
-// explicit row whose bit is set in `req` carries W - 2^(64 (NL - 1)) — the top limb of a distance is then minus the number of required edges
-// behind it, the limbs below the W-sum (rq_count) —, and a distance that counts more than `kreq` required edges ends the solve: only a cycle
-// through a required edge produces one (DESIGN.md §16).
-// BIAS (the evidence-weighted re-annotation, EvCfg in phx_resolve.inc; always MASKED, never REQ): an explicit row whose bit is set in `bbit`
-// carries W + B, B the signed 64-bit word of its in-edge slot in `bval` (read only where the bit is set; DESIGN.md §19).  A bonus can make a
-// cycle negative: the sweep and round caps end such a solve, and an unreached node stays at the unreached pattern as under REQ.
-// REQ and BIAS together (the combined re-annotation, RcEvCfg in phx_resolve.inc; MASKED, never BLIST; DESIGN.md §22): a row weighs W + B - M·[required],
-// on one limb more as under REQ; the count guard and the caps are both active.  The tile path then carries three flags per prefetched row — refused
-// and required in r_mk as under REQ, biased in a register of its own (r_mb), which no other policy has.
-// BLIST (a biased scenario slot, EsCfg in phx_resolve.inc; always BIAS): `bval` is not a word per in-edge slot but the slot's own list of
-// (in-edge slot of the batch, B) pairs, sorted by in-edge slot, `nbl` of them (DESIGN.md §20); bias_at below is the one place that knows.
+// REQ: the sweep runs on one limb more than the contig's class, an explicit row whose bit is set in `req` carries W - 2^(64 (NL - 1)) — the
+// top limb of a distance is then minus the number of required edges behind it, the limbs below the W-sum (rq_count) —, and a distance that
+// counts more than `kreq` required edges ends the solve: only a cycle through a required edge produces one (DESIGN.md §16).
+// BIAS: an explicit row whose bit is set in `bbit` carries W + B, B the signed 64-bit word of its in-edge slot in `bval` (read only where
+// the bit is set; DESIGN.md §19).  A bonus can make a cycle negative: the sweep and round caps end such a solve, and an unreached node
+// stays at the unreached pattern as under REQ.
+// REQ and BIAS together (never BLIST; DESIGN.md §22): a row weighs W + B - M·[required], on one limb more as under REQ; the count guard and
+// the caps are both active.  The tile path then carries three flags per prefetched row — refused and required in r_mk as under REQ, biased
+// in a register of its own (r_mb), which no other policy has.
+// BLIST (always BIAS): `bval` is not a word per in-edge slot but the solve's own list of (in-edge slot of the batch, B) pairs, sorted by
+// in-edge slot, `nbl` of them (DESIGN.md §20); bias_at below is the one place that knows.
 struct SwRun { static constexpr int RING = SW_RING, ECAP = SW_ECAP; static constexpr bool MASKED = false, REQ = false, BIAS = false, BLIST = false; };
 #define RS_PLAN_LDS 2048 // window-plan bytes kept in LDS (contigs of up to 65 536 nodes); longer plans live in DReann.gplan
 

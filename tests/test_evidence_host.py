@@ -79,7 +79,7 @@ def test_cli_refusals_of_evidence_need_no_device(tmp_path):
     assert r.returncode == 2 and b"multi-rank" in r.stderr
 
 
-# ---- the overflow rule (phx_layout.inc contig_sum_bits, k_ev_mask's sums, k_ev_lds' test), restated ----
+# ---- the overflow rule (phx_layout.inc contig_sum_bits, k_rs_mask's sums, the limb test of k_rs_lds under the bias policy), restated ----
 
 B_MAX = 1 << 52  # phx_evidence_flat refuses |B| beyond it
 
@@ -91,7 +91,7 @@ def sum_bits(bound, extra, maxexp):
 
 
 def device_extra(bs):
-    """The sum of |B| as k_ev_mask adds it up (two 64-bit counters, the low and the high 32 bits of every |B|) and k_ev_lds reads it."""
+    """The sum of |B| as k_rs_mask adds it up (two 64-bit counters, the low and the high 32 bits of every |B|) and k_rs_lds reads it under the bias policy."""
     lo = sum(abs(b) & 0xFFFFFFFF for b in bs)
     hi = sum(abs(b) >> 32 for b in bs)
     assert lo < 1 << 64 and hi < 1 << 64

@@ -11,7 +11,7 @@ Two measurements, medians over the steps, one JSON line each:
           (summed phx_reannotate_ms and wall time).  The deltas must be equal.  Beside it one scenario with a penalty on every ORF of
           Lambda: the longest list the contig can give, sorted by counting in one workgroup (full_list_device_ms, "mask" holds the sort).
   batch   N synthetic contigs of L bp resident, S scenarios per contig (each puts a bonus of 2.5 SCORE units on one uncalled ORF; another
-          ORF every step, so that no cached result is handed out): solve ms per 1000 slot-solves against the biased solve (k_ev_lds) of
+          ORF every step, so that no cached result is handed out): solve ms per 1000 slot-solves against the biased solve (k_rs_lds under the bias policy) of
           evidence() on the same contigs in the same session (one ORF per contig biased, as tools/evidence_time.py measures it), and the
           bytes of a biased slot against a dense slice of one word per in-edge slot.
 
@@ -166,7 +166,7 @@ def main():
         r = batch(a.steps, a.n, a.len, a.per_contig)
         print(json.dumps(r), flush=True)
         if not r["within_bound"]:
-            missed.append("batch: the solve per 1000 slots is beyond k_ev_lds' per 1000 contigs plus 15 %")
+            missed.append("batch: the solve per 1000 slots is beyond the biased k_rs_lds' per 1000 contigs plus 15 %")
     if missed:  # the two bounds are requirements (Cost)
         sys.exit("; ".join(missed))
 

@@ -7,7 +7,7 @@ Three measurements, one JSON line each (medians over the steps in the first two)
 
   batch   N synthetic contigs of L bp, resident (default: the bench batch, 1000 x 50 kb).  Per step one uncalled ORF per contig gets a
           bonus of 2.5 SCORE units (another ORF every step, so that no cached result is handed out) and every contig is solved again
-          under the bias policy (k_ev_mask, k_ev_lds, k_ev_inorder); then, as tools/reannotate_time.py does, one called gene per contig is
+          under the bias policy (k_rs_mask, k_rs_lds, k_rs_inorder); then, as tools/reannotate_time.py does, one called gene per contig is
           refused and every contig solved again under the masked policy (k_rs_lds).  Device times by the library's HIP events
           (phx_reannotate_ms serves both): mask, solve, finish.  bound_ms = the sibling's solve time plus 15 %.
   lone    the same two questions on the Lambda contig alone (tests/golden/NC_001416.1).

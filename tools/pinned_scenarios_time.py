@@ -10,7 +10,7 @@ Two measurements, medians over the steps, one JSON line each:
           loop on the same context (summed phx_reannotate_ms and wall time).
   batch   N synthetic contigs of L bp resident, S pinned scenarios per contig (each requires one uncalled ORF some path runs through;
           another one every step, so that no cached result is handed out): solve ms per 1000 slot-solves against the pinned solve
-          (k_rc_lds) of constrain() on the same 1000 contigs in the same session — tools/constrain_time.py's figure, measured here on
+          (k_rs_lds under the required policy) of constrain() on the same 1000 contigs in the same session — tools/constrain_time.py's figure, measured here on
           the same context as well — whose kernel this build leaves instruction for instruction as it was."""
 import argparse
 import gzip

@@ -10,7 +10,7 @@ Two measurements, one JSON line each (medians over the steps):
           is solved again with one called gene refused and one uncalled ORF penalised by 2.5 SCORE units (another pair every step), and the
           margins of that re-annotation are computed (k_rmg_apply, k_sssp_rev<NL, MgCond>, k_margins<NL, MgCond>).  Device times by the
           library's HIP events: apply / reverse / records / copy (phx_remargins_ms) next to transpose / reverse / records / copy
-          (phx_margins_ms), and k_ev_mask's time on the same inputs (phx_reannotate_ms) next to k_rmg_apply's.
+          (phx_margins_ms), and k_rs_mask's time on the same inputs, under the bias mode, (phx_reannotate_ms) next to k_rmg_apply's.
           bound_ms = the unconditioned reverse pass plus 15 %.
   lone    the same on the Lambda contig alone (tests/golden/NC_001416.1).
 
@@ -72,7 +72,7 @@ def measure(what, seqs, steps):
     return {"what": what, "steps": steps, "remargins_device_ms": c, "margins_device_ms": p, "remargins_wall_ms": round(med(wall), 4),
             "bound_ms": round(1.15 * p["reverse"], 4), "within_bound": bool(c["reverse"] <= 1.15 * p["reverse"]),
             "reverse_ratio": round(c["reverse"] / p["reverse"], 4) if p["reverse"] else None,
-            "apply_ms": c["apply"], "k_ev_mask_ms": round(med([x["mask"] for x in ev]), 4),
+            "apply_ms": c["apply"], "k_rs_mask_ms": round(med([x["mask"] for x in ev]), 4),
             "settled": int((status == 0).sum()), "nodes": V, "edges": E,
             "extra_device_bytes": {"bitmaps": 2 * (E // 32 + 2) * 4, "bias_words": 8 * (E + 1), "dist_t": 8 * limbs * (V + 1), "records": 40 * (N + 1), "per_contig": 8 * (n + 1)}}
 
