@@ -45,7 +45,8 @@ extern "C" {
  *        (additions, version unchanged) phx_scenarios_flat, phx_scenarios_ms, phx_scenario_chunks, phx_tap_scenario_path — probe for the symbol;
  *        (addition, version unchanged) phx_pinned_scenarios_flat — probe for the symbol;
  *        (addition, version unchanged) phx_evidence_scenarios_flat — probe for the symbol;
- *        (additions, version unchanged) phx_remargins_flat, phx_remargins_ms, phx_tap_redist — probe for the symbol */
+ *        (additions, version unchanged) phx_remargins_flat, phx_remargins_ms, phx_tap_redist — probe for the symbol;
+ *        (additions, version unchanged) phx_pinmargins_flat, phx_pinmargins_ms, phx_tap_pindist — probe for the symbol */
 #define PHX_MAX_CODONS 16
 
 /* library-level errors */
@@ -511,6 +512,31 @@ int phx_remargins_ms(phx_ctx *ctx, float *ms /* [4] */);
  * unreached node has a top word >= 2^61).  A contig that was not solved again: the run's vectors (phx_tap_dist / phx_tap_dist_target);
  * one whose re-solve left no such vector (an error; no path for d_t'): every node unreached.  PHX_E_STATE as phx_remargins_flat. */
 int phx_tap_redist(phx_ctx *ctx, int32_t contig, int32_t which, uint64_t *dist_limbs, int64_t cap_words);
+
+/* ---- pinned margins: per-ORF path margins under required ORFs ----
+ * phx_remargins_flat for every re-annotation of the batch last run, phx_constrain_flat and phx_curate_flat with required ORFs included.  A
+ * contig solved again under F, B and R has W'(e) = W(e) + B(e) - M·[e required and present], M = 2^(64 NL) for its limb class NL, and
+ *   d_s'(v)  the solve's distance, NL + 1 limbs: the top limb is minus the number of required edges behind v;  R_n the nodes it reached;
+ *   d_t'(v)  the exact shortest v -> target distance under W' in the subgraph induced by R_n, NL + 1 limbs;  D' = d_s'(target).
+ * For ORF k with edge e = (u -> v):  Delta''(k) = d_s'(u) + W'(e) + d_t'(v) - D' >= 0 = lost·M + s with s the low NL limbs read as the
+ * class's two's complement:  lost[k] >= 0 is the number of kept required ORFs that the best path through k gives up, margin =
+ * float(s) / 1000.0 as phx_margins_flat rounds it — negative margins occur where lost > 0 (a path that drops a pin can be cheaper); the
+ * order is (lost, margin) >= (0, 0.0), which a called gene has.  through = 0, margin +inf, lost 0 as phx_remargins_flat has them.
+ * Requiring one more ORF k (through = 1, neither refused nor required) on top of F, B, R gives the smaller of the present optimum and
+ * (kept - lost + 1 required ORFs, sum + s): with lost = 0 an uncalled k gets called, unmet does not grow and delta grows by margin —
+ * unless k lies on a cycle the source reaches (PHX_S_NEGCYCLE).
+ * rec and lost are parallel, cap entries each (rec == NULL: size query; with rec, lost is needed); phx_tap_orfs order; status[i] as
+ * phx_remargins_flat's table with "solved again" covering every mode.  A contig that was not solved under the required policy has
+ * phx_remargins_flat's records (those of the same call without the other contigs' required ORFs) and lost 0; when no contig was, the
+ * three arrays are phx_remargins_flat's byte for byte.  PHX_E_STATE only without a re-annotation of this run.  Computed at the first call
+ * after a re-annotation solve, kept until the next solve or run.  phx_remargins_flat and phx_tap_redist keep refusing a solve with
+ * required ORFs.  (Additions, version unchanged: probe for the symbol.) */
+int phx_pinmargins_flat(phx_ctx *ctx, phx_orf_margin *rec, int32_t *lost, int64_t cap, int64_t *offsets /* [n+1] */, int32_t *status /* [n] */, int64_t *total);
+/* device time of the last computation of the pinned margins (HIP events), ms[4]: apply, reverse pass, records, copy — both kernel sets. */
+int phx_pinmargins_ms(phx_ctx *ctx, float *ms /* [4] */);
+/* phx_tap_redist for every re-annotation: *words_per_node (may be NULL) is sssp_nl + 1 for a contig solved under the required policy —
+ * the top word carries the count, an unreached node has a top word >= 2^61 — and sssp_nl otherwise. */
+int phx_tap_pindist(phx_ctx *ctx, int32_t contig, int32_t which, uint64_t *dist_limbs, int64_t cap_words, int32_t *words_per_node);
 
 /* ---- scenario batches: many masked re-annotations of the batch last run in one call ----
  * n_scen scenarios, each a contig of the batch last run and a set F of its ORFs, solved side by side on the resident graph, one

@@ -915,6 +915,59 @@ class Annotator:
             out.append(None if x >= 1 << (64 * nl - 3) else x)
         return out
 
+    def pinmargins(self):
+        """(status int32[n], offsets int64[n+1], records structured array[total] of _lib.MARGIN_DT, lost int32[total]): remargins() for
+        every re-annotation of the batch last run, constrain() and curate() with required ORFs included (phx_pinmargins_flat, DESIGN.md
+        §24).  For a contig solved with required ORFs, lost[k] is the number of kept required ORFs the best path through ORF k gives up
+        and margin the change of the path sum on that path in SCORE units — it may be negative where lost > 0; the order is (lost,
+        margin) >= (0, 0.0), which a called gene has.  Requiring an uncalled ORF with lost 0 as well gets it called, keeps unmet and
+        raises delta by its margin.  Elsewhere the records are remargins()' and lost is 0.  PhxError (PHX_E_STATE) only without a
+        re-annotation of this run."""
+        n = self.n
+        offs = np.zeros(n + 1, np.int64)
+        status = np.zeros(max(n, 1), np.int32)
+        total = C.c_int64(0)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._chk(self.L.phx_pinmargins_flat(self.h, None, None, 0, vp(offs), vp(status), C.byref(total)), "phx_pinmargins_flat")
+        rec = np.empty(max(int(total.value), 1), _lib.MARGIN_DT)
+        lost = np.zeros(max(int(total.value), 1), np.int32)
+        self._chk(self.L.phx_pinmargins_flat(self.h, vp(rec), vp(lost), len(rec), vp(offs), vp(status), C.byref(total)), "phx_pinmargins_flat")
+        return status[:n], offs, rec[: int(total.value)], lost[: int(total.value)]
+
+    def pinmargins_ms(self):
+        """Device time of the last pinned margins in ms: apply, reverse pass, records, copy to the host (phx_pinmargins_ms)."""
+        ms = (C.c_float * 4)()
+        self._chk(self.L.phx_pinmargins_ms(self.h, ms), "phx_pinmargins_ms")
+        return dict(zip(("apply", "reverse", "margins", "download"), [float(x) for x in ms]))
+
+    def pindist(self, i, to_target=False):
+        """redist(i, to_target) for every re-annotation (phx_tap_pindist).  A contig solved with required ORFs gives per node None
+        (unreached) or (S, count): the sum of W + B and the number of required ORFs on the best path from the source (to the target
+        within the nodes the re-solve reached), best meaning most required ORFs first.  Any other contig gives redist()'s plain ints."""
+        g = self.globals(i)
+        nl, V = max(g.n_limbs, 1), max(g.n_node, 0)
+        a = np.zeros((max(V, 1), nl + 1), np.uint64)
+        wpn = C.c_int32(0)
+        self._chk(self.L.phx_tap_pindist(self.h, i, 1 if to_target else 0, a.ctypes.data_as(C.c_void_p), a.size, C.byref(wpn)), "phx_tap_pindist")
+        w = min(int(wpn.value) or nl, nl + 1)
+        a = a.reshape(-1)[: V * w].reshape(V, w) if V else a[:0]
+        out = []
+        for v in range(V):
+            x = 0
+            for k in range(w):
+                x |= int(a[v, k]) << (64 * k)
+            if x >> (64 * w - 1):
+                x -= 1 << (64 * w)
+            if x >= 1 << (64 * w - 3):
+                out.append(None)
+            elif w <= nl:
+                out.append(x)
+            else:  # x = S - count * M, |S| < M / 2
+                M = 1 << (64 * nl)
+                count = (-x + M // 2) // M
+                out.append((x + count * M, count))
+        return out
+
     def reannotate_ms(self):
         """Device time of the last re-annotation in ms: mask build, masked solve, path + genes + copy (phx_reannotate_ms)."""
         ms = (C.c_float * 3)()

@@ -51,6 +51,7 @@ def get_args(argv=None):
     p.add_argument("--evidence-scan", metavar=("FILE", "OUT"), nargs=2, default=None, help="also take every line of FILE (the format of --evidence) on its own: write to OUT, per line, the cost and the effect of the best annotation under that one bias (DESIGN.md §20); independent of --evidence / --reannotation")
     p.add_argument("--reannotation", metavar="OUT", default=None, help="write the annotation without the ORFs of --forbid (keeping those of --require, or under the biases of --evidence) to OUT: the tabular block of every contig with a #delta: header line")
     p.add_argument("--remargins", metavar="FILE", default=None, help="also write every ORF with its path margin on the graph of the second annotation (under --forbid / --evidence; DESIGN.md §21) to FILE, in the format of --margins; needs --reannotation, not with --require")
+    p.add_argument("--pin-margins", metavar="FILE", default=None, help="also write every ORF with its path margin and the kept ORFs of --require that the best path through it gives up (DESIGN.md §24) to FILE: the format of --margins with a LOST column behind MARGIN; needs --require and --reannotation")
     p.add_argument("--single-device-ranks", action="store_true", help=argparse.SUPPRESS)  # tests: every rank of a sharded launch on GPU `--device` (gloo-only group)
     args = p.parse_args(argv)
     if args.margins is not None and args.dump:
@@ -93,6 +94,16 @@ def get_args(argv=None):
         p.error("argument --remargins: not allowed with argument --require")
     if args.remargins is not None and args.reannotation is None:
         p.error("argument --remargins: needs --reannotation")
+    if args.pin_margins is not None and args.dump:
+        p.error("argument --pin-margins: not allowed with argument -d/--dump")
+    if args.pin_margins is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        p.error("argument --pin-margins: not available under a multi-rank launch")
+    if args.pin_margins is not None and int(args.gpus) > 1:  # the re-annotation works on the batch resident on one context
+        p.error("argument --pin-margins: not available with --gpus above 1")
+    if args.pin_margins is not None and args.require is None:
+        p.error("argument --pin-margins: needs --require")
+    if args.pin_margins is not None and args.reannotation is None:
+        p.error("argument --pin-margins: needs --reannotation")
     for flag, val in (("--forbid", args.forbid), ("--require", args.require), ("--evidence", args.evidence), ("--reannotation", args.reannotation)):
         if val is not None and args.dump:
             p.error("argument %s: not allowed with argument -d/--dump" % flag)
@@ -113,6 +124,23 @@ def get_args(argv=None):
     if args.require is not None and int(args.gpus) > 1:
         p.error("argument --require: not available with --gpus above 1")
     return args
+
+
+def format_pin_margins(names, status, offsets, records, lost):
+    """--pin-margins FILE for a run of contigs, as bytes: format_margins' block with a LOST column behind MARGIN — per contig with status
+    >= 0 "#id:\t<name>", the header, one row per ORF with through == 1 (START STOP FRAME CONTIG SCORE MARGIN LOST CALLED), ordered by
+    left, right, strand.  `lost` is parallel to `records` (Annotator.pinmargins())."""
+    out = []
+    for i, nm in enumerate(names):
+        if status[i] < 0:
+            continue
+        out.append("#id:\t%s\n#START\tSTOP\tFRAME\tCONTIG\tSCORE\tMARGIN\tLOST\tCALLED\n" % nm)
+        rec, lo = records[offsets[i]:offsets[i + 1]], lost[offsets[i]:offsets[i + 1]]
+        rows = sorted((int(r["left"]), int(r["right"]), int(r["strand"]), k) for k, r in enumerate(rec) if r["through"])
+        for left, right, strand, k in rows:
+            a, z = (right, left) if strand < 0 else (left, right)  # as the tabular writer
+            out.append("%d\t%d\t%s\t%s\t%E\t%E\t%d\t%d\n" % (a, z, "-" if strand < 0 else "+", nm, float(rec["score"][k]), float(rec["margin"][k]), int(lo[k]), 1 if rec["called"][k] else 0))
+    return "".join(out).encode()
 
 
 class ForbidError(ValueError):
@@ -495,6 +523,7 @@ def main(argv=None):
     alt_parts = []  # --alt-starts: the same of Annotator.alt_starts()
     reann_parts = []  # --reannotation: (status, offsets, genes, delta[, unmet]) of every batch, in order
     remargin_parts = []  # --remargins: (status, offsets, records) of Annotator.remargins() of every batch, in order
+    pin_parts = []  # --pin-margins: (status, offsets, records, lost) of Annotator.pinmargins() of every batch, in order
     scan_parts = []  # --evidence-scan: (status, offsets, records) of Annotator.evidence_scan() of every batch, in order
     forbid_entries = require_entries = evidence_entries = scan_entries = None
     try:
@@ -570,6 +599,8 @@ def main(argv=None):
                     reann_parts.append(ann.constrain(refused, resolve_forbid([e for e in require_entries if e[3] in here], names, ann.orf_index, "--require")))
                 if args.remargins is not None:  # (behind the batch's re-annotation: the margins are that solve's)
                     remargin_parts.append(ann.remargins())
+                if args.pin_margins is not None:  # (likewise)
+                    pin_parts.append(ann.pinmargins())
                 t_parts["upload_s"] += t1 - t0; t_parts["run_s"] += t2 - t1; t_parts["download_s"] += t3 - t2
         elif len(cuts) == 1 and n_gpu == 1:
             lo, hi = cuts[0]
@@ -666,6 +697,12 @@ def main(argv=None):
             x_offsets = np.concatenate([[0], np.cumsum(x_counts)]).astype(np.int64)
             with open(args.remargins, "wb") as fh:
                 fh.write(format_margins(fa.names, x_status, x_offsets, np.concatenate([m[2] for m in remargin_parts])))
+        if args.pin_margins is not None:
+            p_status = np.concatenate([m[0] for m in pin_parts])
+            p_counts = np.concatenate([np.diff(m[1]) for m in pin_parts])
+            p_offsets = np.concatenate([[0], np.cumsum(p_counts)]).astype(np.int64)
+            with open(args.pin_margins, "wb") as fh:
+                fh.write(format_pin_margins(fa.names, p_status, p_offsets, np.concatenate([m[2] for m in pin_parts]), np.concatenate([m[3] for m in pin_parts])))
         if args.drop_margins is not None:
             d_status = np.concatenate([m[0] for m in drop_parts])
             d_counts = np.concatenate([np.diff(m[1]) for m in drop_parts])

@@ -688,6 +688,7 @@ static int reann_flat(phx_ctx *c, const char *who, bool need_forbid, const uint8
     if (!(c->done.reann && c->h_qflags == flags && c->h_qforb == code && c->h_qbias == bcur)) {
         c->done.reann = false;
         c->done.remarg = false; // (the re-annotation margins are this solve's)
+        c->done.pinmarg = false;
         c->h_qsel.assign((size_t)c->n, 0);
         c->h_qnreq.assign((size_t)c->n, 0);
         for (int i = 0; i < c->n; i++) {
@@ -826,7 +827,7 @@ static int ensure_remargins(phx_ctx *c) {
     c->h_xsel.assign(n + 1, 0);
     c->xmstat.assign(n + 1, 0);
     for (size_t i = 0; i < n; i++) {
-        if (!c->h_qsel[i] || !reann_contig(c, (int)i)) continue;
+        if (!c->h_qsel[i] || !reann_contig(c, (int)i) || re_mode_req(c->h_qsel[i])) continue; // (a contig solved under the required policy: ensure_pinmargins')
         const int32_t st = c->h_qrec[i].status;
         if (st < 0) continue;
         c->h_xsel[i] = st == 0 ? 1 : 2; // (PHX_S_NOPATH: records only, D' is unreached)
@@ -883,47 +884,18 @@ static int32_t remargins_status(const phx_ctx *c, int i) {
     return c->xmstat[(size_t)i] ? PHX_S_NEGCYCLE : 0;
 }
 
+static int remargins_out(phx_ctx *c, const char *who, phx_orf_margin *rec, int32_t *lost, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out);
 int phx_remargins_flat(phx_ctx *c, phx_orf_margin *rec, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
     if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
     { const int ra = after_run(c); if (ra) return ra; }
     { const int rs = remarg_state(c, "phx_remargins_flat"); if (rs) return rs; } // before any kernel
     { const int rm = ensure_remargins(c); if (rm) return rm; }
-    try {
-    int64_t total = 0;
-    for (int i = 0; i < c->n; i++) { offsets[i] = total; status[i] = remargins_status(c, i); if (status[i] >= 0) total += c->meta[(size_t)i].n_orf; }
-    offsets[c->n] = total;
-    if (total_out) *total_out = total;
-    if (!rec) return PHX_OK; // size query
-    if (cap < total) return PHX_E_ARG;
-    { const int rg = stage_run_genes(c, c->h_qsel.data()); if (rg) return rg; } // (of the contigs that were not solved again)
-    { const int rg = ensure_grp_host(c); if (rg) return rg; }
-    std::vector<uint64_t> keys;
-    std::vector<int> order;
-    for (int i = 0; i < c->n; i++) {
-        if (status[i] < 0) continue;
-        // `called`: the genes the re-annotation call returns for the contig — the device's lists, no host re-solve enters
-        const bool again = c->h_qsel[(size_t)i] != 0;
-        const DGene *src = again ? c->h_qgenes.data() + c->h_qrec[(size_t)i].gene_off : (const DGene *)c->h_genes.p + (size_t)c->res[(size_t)i].gene_off;
-        const int64_t ng = again ? (int64_t)c->h_qrec[(size_t)i].n_genes : (int64_t)std::max(c->res[(size_t)i].n_genes, 0);
-        keys.clear();
-        for (int64_t k = 0; k < ng; k++) if (src[k].frame >= -3 && src[k].frame <= 3) keys.push_back(gene_key(src[k].left, src[k].right, src[k].strand));
-        std::sort(keys.begin(), keys.end());
-        phx_orf_margin *dst = rec + offsets[i];
-        const phx_orf_margin *from = (again ? c->h_xrec.data() : (const phx_orf_margin *)c->h_mrec.p) + c->meta[(size_t)i].orf_off;
-        each_group_in_reference_order(c, (size_t)i, order, [&](int32_t first, int32_t k) {
-            if (k > 0) memcpy(dst, from + first, sizeof(phx_orf_margin) * (size_t)k);
-            dst += k;
-        });
-        for (int64_t k = offsets[i]; k < offsets[i + 1]; k++) rec[k].called = is_called(keys, rec[k].left, rec[k].right, rec[k].strand) ? 1 : 0;
-    }
-    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_remargins_flat"; return PHX_E_NOMEM; }
-    return PHX_OK;
+    return remargins_out(c, "phx_remargins_flat", rec, nullptr, cap, offsets, status, total_out);
 }
 
-int phx_tap_redist(phx_ctx *c, int32_t contig, int32_t which, uint64_t *dist_limbs, int64_t cap_words) {
-    TAP_PRE(c, contig);
-    if (which != 0 && which != 1) return PHX_E_ARG;
-    { const int rs = remarg_state(c, "phx_tap_redist"); if (rs) return rs; }
+// d_s' / d_t' of a contig that was not solved under the required policy (the caller has checked the state and `which`)
+static int tap_redist_plain(phx_ctx *c, int32_t contig, int32_t which, uint64_t *dist_limbs, int64_t cap_words) {
+    const DMeta &m = c->meta[(size_t)contig];
     if (!c->h_qsel[(size_t)contig]) return which ? phx_tap_dist_target(c, contig, dist_limbs, cap_words) : phx_tap_dist(c, contig, dist_limbs, cap_words); // the run's vectors stand
     const size_t nl = (size_t)m.sssp_nl, words = (size_t)m.n_node * nl;
     if (!dist_limbs || cap_words < (int64_t)words) return PHX_E_ARG;
@@ -938,9 +910,170 @@ int phx_tap_redist(phx_ctx *c, int32_t contig, int32_t which, uint64_t *dist_lim
     return PHX_OK;
 }
 
+int phx_tap_redist(phx_ctx *c, int32_t contig, int32_t which, uint64_t *dist_limbs, int64_t cap_words) {
+    TAP_PRE(c, contig);
+    (void)m;
+    if (which != 0 && which != 1) return PHX_E_ARG;
+    { const int rs = remarg_state(c, "phx_tap_redist"); if (rs) return rs; }
+    return tap_redist_plain(c, contig, which, dist_limbs, cap_words);
+}
+
 int phx_remargins_ms(phx_ctx *c, float *ms) {
     if (!c || !ms) return PHX_E_ARG;
     for (int k = 0; k < 4; k++) ms[k] = c->remarg_ms[k];
+    return PHX_OK;
+}
+
+// ---- pinned margins (phx_margins.inc, DESIGN.md §24): the re-annotation margins where ORFs were required ----
+// On top of ensure_remargins, which covers the contigs solved again without a required ORF (modes 1 and 3, the MgCond kernels): the
+// contigs solved under the required policy (modes 2 and 4) run the MgPin kernels on one limb more, into buffers of their own (b_p*),
+// allocated at the first call that has such a contig.  Records into c->h_prec, `lost` into c->h_plost (device order), the pass's verdicts
+// into c->pmstat, once per re-annotation solve.  pinmarg_ms: the device time of both parts as computed for this solve.
+static int ensure_pinmargins(phx_ctx *c) {
+    if (c->done.pinmarg) return PHX_OK;
+    const bool fresh = !c->done.remarg;
+    { const int rm = ensure_remargins(c); if (rm) return rm; }
+    const size_t n = (size_t)c->n, V = (size_t)c->tot_node, E = (size_t)c->tot_edge, N = (size_t)c->tot_orf;
+    const size_t limbs = (size_t)std::max(c->n_limbs, 2);
+    const size_t mw = E / 32 + 2; // words of one bitmap over the out-edge positions
+    int rev_nlm = 0, rec_nlm = 0;
+    bool biased = false;
+    c->h_psel.assign(n + 1, 0);
+    c->pmstat.assign(n + 1, 0);
+    for (size_t i = 0; i < n; i++) {
+        if (!re_mode_req(c->h_qsel[i]) || !reann_contig(c, (int)i)) continue;
+        const int32_t st = c->h_qrec[i].status;
+        if (st < 0) continue;
+        c->h_psel[i] = st == 0 ? 1 : 2; // (PHX_S_NOPATH: records only, D' is unreached)
+        rec_nlm |= nl_class_bit(c->meta[i].sssp_nl);
+        if (st == 0) { rev_nlm |= nl_class_bit(c->meta[i].sssp_nl); biased = biased || re_mode_bias(c->h_qsel[i]); }
+    }
+    for (int k = 0; k < 4; k++) c->pinmarg_ms[k] = fresh ? c->remarg_ms[k] : 0;
+    if (!rec_nlm) { c->done.pinmarg = true; return PHX_OK; }
+    int rc;
+    if ((rc = ensure(c, c->b_psel, (n + 1) * 4)) || (rc = ensure(c, c->b_pbit, 3 * mw * 4)) || (biased && (rc = ensure(c, c->b_pbval, (E + 1) * 8))) ||
+        (rc = ensure(c, c->b_pdt, (V + 1) * (limbs + 1) * 8)) || (rc = ensure(c, c->b_prec, (N + 1) * sizeof(phx_orf_margin))) || (rc = ensure(c, c->b_plost, (N + 1) * 4)) ||
+        (rc = ensure(c, c->b_pmstat, (n + 1) * 4)))
+        return rc;
+    if ((rc = analysis_events(c))) return rc;
+    try { c->h_prec.resize(N + 1); c->h_plost.resize(N + 1); } catch (const std::bad_alloc &) { c->err = "out of memory in phx_pinmargins_flat"; return PHX_E_NOMEM; }
+    DBatch b;
+    fill_batch(c, &b);
+    DMarg g;
+    margins_args(c, &g);
+    DBatch qb;
+    DReann q;
+    reann_batch(c, &qb, &q);
+    DPmarg r;
+    r.sel = (const int32_t *)c->b_psel.p; r.ds = (const uint64_t *)c->b_qdist.p; r.ds_stride = c->qstride; r.dt_stride = b.dist_stride + 1;
+    r.fbit = (uint32_t *)c->b_pbit.p; r.bbit = r.fbit + mw; r.rbit = r.fbit + 2 * mw; r.bval = (long long *)c->b_pbval.p;
+    r.dist_t = (uint64_t *)c->b_pdt.p; r.rec = (phx_orf_margin *)c->b_prec.p; r.lost = (int32_t *)c->b_plost.p; r.mstat = (int32_t *)c->b_pmstat.p;
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipMemcpyAsync(c->b_psel.p, c->h_psel.data(), (n + 1) * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipEventRecord(c->aev[0], s));
+    HIPCHK(c, hipMemsetAsync(c->b_pbit.p, 0, 3 * mw * 4, s));
+    HIPCHK(c, hipMemsetAsync(c->b_pmstat.p, 0, (n + 1) * 4, s));
+    if (rev_nlm) phxk_pinmarg_apply(&b, &g, &q, &r, s);
+    HIPCHK(c, hipEventRecord(c->aev[1], s));
+    if (rev_nlm) phxk_pinmarg_rev(&b, &g, &q, &r, rev_nlm, s);
+    HIPCHK(c, hipEventRecord(c->aev[2], s));
+    phxk_pinmarg_records(&b, &g, &q, &r, rec_nlm, s);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->aev[3], s));
+    if (N) HIPCHK(c, hipMemcpyAsync(c->h_prec.data(), c->b_prec.p, N * sizeof(phx_orf_margin), hipMemcpyDeviceToHost, s));
+    if (N) HIPCHK(c, hipMemcpyAsync(c->h_plost.data(), c->b_plost.p, N * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(c->pmstat.data(), c->b_pmstat.p, n * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipEventRecord(c->aev[4], s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    for (int k = 0; k < 4; k++) c->pinmarg_ms[k] += ev_ms(c->aev[k], c->aev[k + 1]);
+    c->done.pinmarg = true;
+    return PHX_OK;
+}
+
+// status of contig i's pinned margins (include/phx.h): phx_remargins_flat's, "solved again" covering every mode
+static int32_t pinmargins_status(const phx_ctx *c, int i) {
+    if (!re_mode_req(c->h_qsel[(size_t)i])) return remargins_status(c, i);
+    const int32_t r = c->res[(size_t)i].status;
+    if (r < 0) return r;
+    const int32_t q = c->h_qrec[(size_t)i].status;
+    if (q != 0) return q;
+    return c->pmstat[(size_t)i] ? PHX_S_NEGCYCLE : 0;
+}
+
+// The layout of phx_remargins_flat and phx_pinmargins_flat, behind their ensure_*: offsets and statuses, then the records in reference
+// order with `called` set.  lost: null for phx_remargins_flat (no contig was solved under the required policy then), else parallel to rec.
+static int remargins_out(phx_ctx *c, const char *who, phx_orf_margin *rec, int32_t *lost, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
+    try {
+    int64_t total = 0;
+    for (int i = 0; i < c->n; i++) { offsets[i] = total; status[i] = pinmargins_status(c, i); if (status[i] >= 0) total += c->meta[(size_t)i].n_orf; }
+    offsets[c->n] = total;
+    if (total_out) *total_out = total;
+    if (!rec) return PHX_OK; // size query
+    if (cap < total) return PHX_E_ARG;
+    { const int rg = stage_run_genes(c, c->h_qsel.data()); if (rg) return rg; } // (of the contigs that were not solved again)
+    { const int rg = ensure_grp_host(c); if (rg) return rg; }
+    std::vector<uint64_t> keys;
+    std::vector<int> order;
+    for (int i = 0; i < c->n; i++) {
+        if (status[i] < 0) continue;
+        // `called`: the genes the re-annotation call returns for the contig — the device's lists, no host re-solve enters
+        const int mode = c->h_qsel[(size_t)i];
+        const bool again = mode != 0, pinned = re_mode_req(mode);
+        const DGene *src = again ? c->h_qgenes.data() + c->h_qrec[(size_t)i].gene_off : (const DGene *)c->h_genes.p + (size_t)c->res[(size_t)i].gene_off;
+        const int64_t ng = again ? (int64_t)c->h_qrec[(size_t)i].n_genes : (int64_t)std::max(c->res[(size_t)i].n_genes, 0);
+        keys.clear();
+        for (int64_t k = 0; k < ng; k++) if (src[k].frame >= -3 && src[k].frame <= 3) keys.push_back(gene_key(src[k].left, src[k].right, src[k].strand));
+        std::sort(keys.begin(), keys.end());
+        phx_orf_margin *dst = rec + offsets[i];
+        int32_t *ldst = lost ? lost + offsets[i] : nullptr;
+        const phx_orf_margin *from = (pinned ? c->h_prec.data() : again ? c->h_xrec.data() : (const phx_orf_margin *)c->h_mrec.p) + c->meta[(size_t)i].orf_off;
+        const int32_t *lfrom = pinned ? c->h_plost.data() + c->meta[(size_t)i].orf_off : nullptr;
+        each_group_in_reference_order(c, (size_t)i, order, [&](int32_t first, int32_t k) { // (records and `lost` are permuted together)
+            if (k > 0) {
+                memcpy(dst, from + first, sizeof(phx_orf_margin) * (size_t)k);
+                if (ldst && lfrom) memcpy(ldst, lfrom + first, 4 * (size_t)k);
+                else if (ldst) memset(ldst, 0, 4 * (size_t)k);
+                dst += k;
+                if (ldst) ldst += k;
+            }
+        });
+        for (int64_t k = offsets[i]; k < offsets[i + 1]; k++) rec[k].called = is_called(keys, rec[k].left, rec[k].right, rec[k].strand) ? 1 : 0;
+    }
+    } catch (const std::bad_alloc &) { c->err = std::string("out of memory in ") + who; return PHX_E_NOMEM; }
+    return PHX_OK;
+}
+
+int phx_pinmargins_flat(phx_ctx *c, phx_orf_margin *rec, int32_t *lost, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
+    if (!c || (c->n > 0 && (!offsets || !status)) || (rec && !lost)) return PHX_E_ARG;
+    { const int ra = after_run(c); if (ra) return ra; }
+    if (!c->done.reann) { c->err = "phx_pinmargins_flat: no re-annotation of this run (call phx_constrain_flat or phx_curate_flat first)"; return PHX_E_STATE; } // before any kernel
+    { const int rm = ensure_pinmargins(c); if (rm) return rm; }
+    return remargins_out(c, "phx_pinmargins_flat", rec, lost, cap, offsets, status, total_out);
+}
+
+int phx_tap_pindist(phx_ctx *c, int32_t contig, int32_t which, uint64_t *dist_limbs, int64_t cap_words, int32_t *words_per_node) {
+    TAP_PRE(c, contig);
+    if (which != 0 && which != 1) return PHX_E_ARG;
+    if (!c->done.reann) { c->err = "phx_tap_pindist: no re-annotation of this run (call phx_constrain_flat or phx_curate_flat first)"; return PHX_E_STATE; }
+    const bool pinned = re_mode_req(c->h_qsel[(size_t)contig]);
+    if (words_per_node) *words_per_node = m.sssp_nl + (pinned ? 1 : 0);
+    if (!pinned) return tap_redist_plain(c, contig, which, dist_limbs, cap_words);
+    const size_t nl = (size_t)m.sssp_nl + 1, words = (size_t)m.n_node * nl;
+    if (!dist_limbs || cap_words < (int64_t)words) return PHX_E_ARG;
+    if (which) { const int rm = ensure_pinmargins(c); if (rm) return rm; }
+    const bool have = which ? (c->h_psel[(size_t)contig] == 1 && !c->pmstat[(size_t)contig]) : c->h_qrec[(size_t)contig].status >= 0;
+    if (!have) { // no such vector (the re-solve ended with an error; no path, so no d_t'): every node unreached
+        for (size_t v = 0; v < (size_t)m.n_node; v++) for (size_t k = 0; k < nl; k++) dist_limbs[v * nl + k] = k + 1 == nl ? WINF_TOP_HOST : 0;
+        return PHX_OK;
+    }
+    const uint64_t *from = which ? (const uint64_t *)c->b_pdt.p + (size_t)m.node_off * (size_t)(c->n_limbs + 1) : (const uint64_t *)c->b_qdist.p + (size_t)m.node_off * (size_t)c->qstride;
+    HIPCHK(c, hipMemcpy(dist_limbs, from, words * 8, hipMemcpyDeviceToHost));
+    return PHX_OK;
+}
+
+int phx_pinmargins_ms(phx_ctx *c, float *ms) {
+    if (!c || !ms) return PHX_E_ARG;
+    for (int k = 0; k < 4; k++) ms[k] = c->pinmarg_ms[k];
     return PHX_OK;
 }
 

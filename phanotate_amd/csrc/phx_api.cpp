@@ -238,6 +238,7 @@ struct phx_ctx {
         bool reann = false;   // h_q* hold the re-annotation for the mask h_qforb / h_qflags
         bool scen = false;    // h_s* hold the scenario batch h_skey
         bool remarg = false;  // h_xrec / xmstat hold the margins of the re-annotation h_q* hold (also reset by every re-annotation solve)
+        bool pinmarg = false; // h_prec / h_plost / pmstat hold the pinned margins of the re-annotation h_q* hold (reset wherever remarg is)
         bool grp = false;     // h_grp
     } done;
     std::vector<DGrp> h_grp;         // the run's group records (device order <-> reference order of the ORFs: each_group_in_reference_order)
@@ -288,6 +289,13 @@ struct phx_ctx {
     std::vector<int32_t> xmstat;      // per contig: the conditioned reverse pass hit its caps
     std::vector<phx_orf_margin> h_xrec; // the device's records of the contigs in h_xsel (device ORF order, at orf_off)
     float remarg_ms[4] = {0, 0, 0, 0};
+    // pinned margins (phx_pinmargins_flat): the same for the contigs solved under the required policy, values one limb wider; allocated at the first call that has such a contig
+    DevBuf b_psel, b_pbit, b_pbval, b_pdt, b_prec, b_plost, b_pmstat;
+    std::vector<int32_t> h_psel;      // per contig: DPmarg.sel as uploaded
+    std::vector<int32_t> pmstat;      // per contig: the pinned reverse pass hit its caps
+    std::vector<phx_orf_margin> h_prec; // the device's records of the contigs in h_psel (device ORF order, at orf_off) ...
+    std::vector<int32_t> h_plost;     // ... and their `lost`
+    float pinmarg_ms[4] = {0, 0, 0, 0};
     // scenario batches (phx_scenarios_flat): buffers of their own, allocated at the first call; the result kept until the next upload or run
     DevBuf b_sc_slot, b_sc_pair, b_sc_meta, b_sc_dist, b_sc_parent, b_sc_path, b_sc_mask, b_sc_plan, b_sc_genes, b_sc_rec, b_sc_tot, b_sc_gtot, b_sc_tie, b_sc_pin, b_sc_bs, b_sc_trip, b_sc_blist;
     int64_t scen_budget = (int64_t)2 << 30; // device bytes of a chunk's slots (env PHX_SCEN_BYTES at phx_create)

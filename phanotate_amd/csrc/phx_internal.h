@@ -473,6 +473,23 @@ struct DRmarg {
     int32_t *mstat;        // per contig: 1 the conditioned reverse pass hit its caps; zeroed by the host
 };
 
+// Pinned margins (phx_margins.inc), on demand after a re-annotation that solved a contig under the required policy: DRmarg for
+// those contigs, in buffers of their own.  Values have the contig's limbs + 1.
+struct DPmarg {
+    const int32_t *sel;    // per contig: 1 = solved again under the required policy with status 0, 2 = likewise without a path (records only), 0 = not covered
+    const uint64_t *ds;    // the re-solve's distances d_s', ds_stride words per node reserved, the contig's limbs + 1 per node used
+    int32_t ds_stride;
+    int32_t dt_stride;     // words per node reserved in dist_t (the batch's widest class + 1)
+    uint32_t *fbit;        // one bit per out-edge position of the batch (bit edge_off + e, the CSR's order): refused; cleared per call
+    uint32_t *bbit;        // likewise: the position carries a bias
+    uint32_t *rbit;        // likewise: required (W - M)
+    long long *bval;       // per out-edge position: B; never cleared, read only where the position's bit is set in bbit
+    uint64_t *dist_t;      // d_t' of every node: contig at node_off * dt_stride, the contig's limbs + 1 per node
+    phx_orf_margin *rec;   // per ORF (at orf_off, device order); `called` is set on the host
+    int32_t *lost;         // per ORF, parallel to rec: the kept pins the best path through the ORF gives up
+    int32_t *mstat;        // per contig: 1 the reverse pass hit its caps; zeroed by the host
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -527,6 +544,9 @@ void phxk_reann_finish(const DBatch *b, const DReann *q, const int *nl_masks, vo
 void phxk_remarg_apply(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, void *stream);               // re-annotation margins (§21; b: the run's batch): the refused / biased out-edge positions,
 void phxk_remarg_rev(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, int nl_mask, void *stream);     //   the conditioned reverse pass (nl_mask: the classes among DRmarg.sel == 1),
 void phxk_remarg_records(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, int nl_mask, void *stream); //   the ORF records (nl_mask: the classes among DRmarg.sel != 0)
+void phxk_pinmarg_apply(const DBatch *b, const DMarg *g, const DReann *q, const DPmarg *r, void *stream);               // pinned margins (§24): the same three steps under MgPin,
+void phxk_pinmarg_rev(const DBatch *b, const DMarg *g, const DReann *q, const DPmarg *r, int nl_mask, void *stream);     //   for the contigs solved under the required policy
+void phxk_pinmarg_records(const DBatch *b, const DMarg *g, const DReann *q, const DPmarg *r, int nl_mask, void *stream); //   (nl_mask: the contigs' own classes; the kernels work on one limb more)
 // scenario batches (§17, §18, §20).  b: the run's graph, tot / genes / gene_total / tie the scenarios' own; q: the chunk's whole slot table;
 // n_range[3]: its plain, pinned and biased slots, in that order; nl_masks[3]: per range, the limb classes of its slots
 void phxk_scen_mask(const DBatch *b, const DScen *q, const int *n_range, int max_list, void *stream);     // the slots' records, slices, counts and lists (max_list: the longest bias list),

@@ -425,6 +425,17 @@ static MgCond mg_cond_args(const DMarg *g, const DReann *q, const DRmarg *r) { M
 void phxk_remarg_apply(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, void *stream) { hipLaunchKernelGGL(k_rmg_apply, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), 0, (hipStream_t)stream, *b, *g, *q, *r); }
 void phxk_remarg_rev(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH_COND(k_sssp_rev, nl_mask, dim3(b->n_contig), dim3(NT), *b, mg_cond_args(g, q, r)); }
 void phxk_remarg_records(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH_COND(k_margins, nl_mask, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), *b, mg_cond_args(g, q, r)); }
+// pinned margins (§24): the same under MgPin, for the contigs solved under the required policy
+static MgPin mg_pin_args(const DMarg *g, const DReann *q, const DPmarg *r) { MgPin c; static_cast<DMarg &>(c) = *g; c.q = *q; c.r = *r; return c; }
+#define NL_LAUNCH_PIN(K, NLM, GRID, BLOCK, ...) do { \
+        if ((NLM) & 1) hipLaunchKernelGGL((K<2, MgPin>), GRID, BLOCK, 0, s, __VA_ARGS__); \
+        if ((NLM) & 2) hipLaunchKernelGGL((K<4, MgPin>), GRID, BLOCK, 0, s, __VA_ARGS__); \
+        if ((NLM) & 4) hipLaunchKernelGGL((K<8, MgPin>), GRID, BLOCK, 0, s, __VA_ARGS__); \
+        if ((NLM) & 8) hipLaunchKernelGGL((K<17, MgPin>), GRID, BLOCK, 0, s, __VA_ARGS__); \
+    } while (0)
+void phxk_pinmarg_apply(const DBatch *b, const DMarg *g, const DReann *q, const DPmarg *r, void *stream) { hipLaunchKernelGGL(k_pmg_apply, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), 0, (hipStream_t)stream, *b, *g, *q, *r); }
+void phxk_pinmarg_rev(const DBatch *b, const DMarg *g, const DReann *q, const DPmarg *r, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH_PIN(k_sssp_rev, nl_mask, dim3(b->n_contig), dim3(NT), *b, mg_pin_args(g, q, r)); }
+void phxk_pinmarg_records(const DBatch *b, const DMarg *g, const DReann *q, const DPmarg *r, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH_PIN(k_margins, nl_mask, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), *b, mg_pin_args(g, q, r)); }
 // gene drop margins (phx_drop.inc): a workgroup per contig, one launch per limb class and step
 void phxk_drop_trees(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH(k_dp_tree, nl_mask, dim3(b->n_contig), dim3(NT), *b, *g, *q); }
 void phxk_drop_cand(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH(k_dp_cand, nl_mask, dim3(b->n_contig), dim3(NT), *b, *g, *q); }

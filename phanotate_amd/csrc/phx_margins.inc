@@ -1,4 +1,4 @@
-// phx_margins.inc — per-ORF path margins: the out-edge CSR, k_sssp_rev<NL> and k_margins; the re-annotation margins: k_rmg_apply and both under MgCond (included by phx_kernels.hip).
+// phx_margins.inc — per-ORF path margins: the out-edge CSR, k_sssp_rev<NL> and k_margins; the re-annotation margins: k_rmg_apply and both under MgCond; the pinned margins: k_pmg_apply and both under MgPin (included by phx_kernels.hip).
 // ------------------------------------------------------------------------------------------------
 // On demand after a run (phx_margins_flat / phx_tap_dist_target), never inside it.  With d_s the distances the run left in DBatch.dist
 // and d_t(v) the exact distance from v TO the target, an ORF edge e = (u -> v) of weight W gets
@@ -87,16 +87,26 @@ __global__ __launch_bounds__(NT) void k_mg_fill(DBatch b, DMarg g) {
 //               0) and, for a contig solved under the bias policy (DReann.mode), carries DReann.bval where its bit is set in DReann.bbit.
 //               Contigs: r.sel != 0 whose reverse pass settled (sel 2 — the re-solve found no path —: D' is unreached, every record through = 0).
 struct MgCond : DMarg { DReann q; DRmarg r; };
+// MgPin (the pinned margins, DESIGN.md §24): MgCond for a contig solved under the required policy (DReann.mode 2 or 4).  Its d_s' has NL + 1
+// limbs per node, the top limb minus the count of required edges behind the node (§16); the pass and the records work on WInt<NL + 1>:
+//   k_sssp_rev  as under MgCond, and an out-edge position whose bit is set in r.rbit (required) weighs W + B - M, M = 2^(64 NL): one off the
+//               top limb.  d_t' goes to r.dist_t at r.dt_stride words per node reserved, NL + 1 used.
+//   k_margins   Delta'' = d_s'(u) + W' + d_t'(v) - D' in NL + 1 limbs; lost = the top limb plus the sign bit of limb NL - 1 (rq_count with
+//               the sign turned) to r.lost, margin = float(the low NL limbs as the class's two's complement) / 1000.0.  The ORF's in-edge
+//               slot is tested in DReann.req as well.
+struct MgPin : DMarg { DReann q; DPmarg r; };
 template <class G> constexpr bool mg_cond = !std::is_same<G, DMarg>::value;
+template <class G> constexpr bool mg_pin = std::is_same<G, MgPin>::value;
 __device__ __forceinline__ bool mg_bit(const uint32_t *bits, uint64_t x) { return (bits[x >> 5] >> (x & 31)) & 1u; } // bit x of a bitmap over the batch's edges
 __device__ __forceinline__ int mg_node(int i, int V) { return i == 0 ? V - 1 : (i == V - 1 ? V - 2 : V - 2 - i); } // sweep index -> node id
 __device__ __forceinline__ int mg_idx(int v, int V) { return v == V - 1 ? 0 : (v == V - 2 ? V - 1 : V - 2 - v); }  // node id -> sweep index
 template <int NL, class G = DMarg>
 __global__ __launch_bounds__(NT) void k_sssp_rev(DBatch b, G g) {
-    constexpr bool COND = mg_cond<G>;
+    constexpr bool COND = mg_cond<G>, PIN = mg_pin<G>;
+    constexpr int WL = NL + (PIN ? 1 : 0); // limbs of a value: one more under MgPin, whose top limb counts the required edges
     __shared__ int s_flag[2];
     __shared__ int s_hi, s_lo_next, s_hi_next;
-    __shared__ uint64_t s_d[NT * NL]; // the current chunk's values, by sweep index - c0
+    __shared__ uint64_t s_d[NT * WL]; // the current chunk's values, by sweep index - c0
     const DMeta *meta = &b.meta[blockIdx.x];
     if (!mg_contig(meta) || meta->sssp_nl != NL) return;
     if constexpr (COND) { if (g.r.sel[blockIdx.x] != 1) return; }
@@ -107,21 +117,22 @@ __global__ __launch_bounds__(NT) void k_sssp_rev(DBatch b, G g) {
     const uint32_t *in_off = b.in_off + meta->node_off + blockIdx.x;
     const uint32_t *esrc = b.esrc + meta->edge_off;
     uint64_t *dt;
-    if constexpr (COND) dt = g.r.dist_t + (size_t)meta->node_off * b.dist_stride;
+    if constexpr (PIN) dt = g.r.dist_t + (size_t)meta->node_off * g.r.dt_stride;
+    else if constexpr (COND) dt = g.r.dist_t + (size_t)meta->node_off * b.dist_stride;
     else dt = g.dist_t + (size_t)meta->node_off * b.dist_stride;
     [[maybe_unused]] const uint64_t *ds = nullptr;
     [[maybe_unused]] const uint64_t ebase = (uint64_t)meta->edge_off;
     if constexpr (COND) ds = g.r.ds + (size_t)meta->node_off * g.r.ds_stride;
     const int tid = threadIdx.x;
     for (int v = tid; v < V; v += NT) {
-        WInt<NL> d = wi_inf<NL>();
+        WInt<WL> d = wi_inf<WL>();
         bool zero = v == TGT;
-        if constexpr (COND) zero = zero && !wi_unreached<NL>(wi_load<NL>(ds + (size_t)v * NL)); // (the target outside R: nothing gets a value)
+        if constexpr (COND) zero = zero && !wi_unreached<WL>(wi_load<WL>(ds + (size_t)v * WL)); // (the target outside R: nothing gets a value)
         if (zero) {
 #pragma unroll
-            for (int i = 0; i < NL; i++) d.v[i] = 0;
+            for (int i = 0; i < WL; i++) d.v[i] = 0;
         }
-        wi_store<NL>(dt + (size_t)v * NL, d);
+        wi_store<WL>(dt + (size_t)v * WL, d);
     }
     if (tid == 0) { s_flag[0] = 0; s_flag[1] = 0; s_hi = 0; s_lo_next = V; s_hi_next = -1; }
     __syncthreads();
@@ -138,26 +149,31 @@ __global__ __launch_bounds__(NT) void k_sssp_rev(DBatch b, G g) {
             // of a re-annotation are a handful per contig, so nearly every node takes the loops as the plain pass has them)
             [[maybe_unused]] bool special = false;
             if constexpr (COND) {
-                if (relax && wi_unreached<NL>(wi_load<NL>(ds + (size_t)v * NL))) e1 = e0;
+                if (relax && wi_unreached<WL>(wi_load<WL>(ds + (size_t)v * WL))) e1 = e0;
                 if (e1 > e0)
                     for (uint64_t x = (ebase + e0) >> 5, x1 = (ebase + e1 - 1) >> 5; x <= x1; x++) special = special || (g.r.fbit[x] | g.r.bbit[x]) != 0u;
+                if constexpr (PIN) { // (the required out-edges are a handful as well: the same test covers them)
+                    if (e1 > e0)
+                        for (uint64_t x = (ebase + e0) >> 5, x1 = (ebase + e1 - 1) >> 5; x <= x1; x++) special = special || g.r.rbit[x] != 0u;
+                }
             }
             // nothing outside the chunk changes while it iterates: the out-edges that leave it are folded in once, the ones inside it
             // read the chunk's values from LDS
-            WInt<NL> cur = wi_inf<NL>();
-            if (v >= 0) cur = wi_load<NL>(dt + (size_t)v * NL);
-            WInt<NL> best = cur;
+            WInt<WL> cur = wi_inf<WL>();
+            if (v >= 0) cur = wi_load<WL>(dt + (size_t)v * WL);
+            WInt<WL> best = cur;
             for (uint32_t e = e0; e < e1; e++) {
                 const uint32_t p = (uint32_t)(mg_idx((int)od[e], V) - c0);
                 if (p < (uint32_t)NT) continue;
                 if constexpr (COND) { if (special && mg_bit(g.r.fbit, ebase + e)) continue; }
-                const WInt<NL> dv = wi_load<NL>(dt + (size_t)od[e] * NL);
-                if (wi_is_inf<NL>(dv)) continue;
-                WInt<NL> cand = wi_add<NL>(dv, ew_decode<NL>(ow[e]));
-                if constexpr (COND) { if (special && mg_bit(g.r.bbit, ebase + e)) cand = wi_add<NL>(cand, ew_decode<NL>(g.r.bval[ebase + e])); }
-                if (wi_lt<NL>(cand, best)) best = cand;
+                const WInt<WL> dv = wi_load<WL>(dt + (size_t)od[e] * WL);
+                if (wi_is_inf<WL>(dv)) continue;
+                WInt<WL> cand = wi_add<WL>(dv, ew_decode<WL>(ow[e]));
+                if constexpr (COND) { if (special && mg_bit(g.r.bbit, ebase + e)) cand = wi_add<WL>(cand, ew_decode<WL>(g.r.bval[ebase + e])); }
+                if constexpr (PIN) { if (special && mg_bit(g.r.rbit, ebase + e)) cand.v[WL - 1] -= 1ull; } // required: W - M, one off the top limb
+                if (wi_lt<WL>(cand, best)) best = cand;
             }
-            wi_store<NL>(s_d + (size_t)tid * NL, best);
+            wi_store<WL>(s_d + (size_t)tid * WL, best);
             __syncthreads();
             int inner = 0;
             bool chg = true;
@@ -167,22 +183,23 @@ __global__ __launch_bounds__(NT) void k_sssp_rev(DBatch b, G g) {
                     const uint32_t p = (uint32_t)(mg_idx((int)od[e], V) - c0);
                     if (p >= (uint32_t)NT) continue;
                     if constexpr (COND) { if (special && mg_bit(g.r.fbit, ebase + e)) continue; }
-                    const WInt<NL> dv = wi_load<NL>(s_d + (size_t)p * NL);
-                    if (wi_is_inf<NL>(dv)) continue;
-                    WInt<NL> cand = wi_add<NL>(dv, ew_decode<NL>(ow[e]));
-                    if constexpr (COND) { if (special && mg_bit(g.r.bbit, ebase + e)) cand = wi_add<NL>(cand, ew_decode<NL>(g.r.bval[ebase + e])); }
-                    if (wi_lt<NL>(cand, best)) { best = cand; improved = true; }
+                    const WInt<WL> dv = wi_load<WL>(s_d + (size_t)p * WL);
+                    if (wi_is_inf<WL>(dv)) continue;
+                    WInt<WL> cand = wi_add<WL>(dv, ew_decode<WL>(ow[e]));
+                    if constexpr (COND) { if (special && mg_bit(g.r.bbit, ebase + e)) cand = wi_add<WL>(cand, ew_decode<WL>(g.r.bval[ebase + e])); }
+                    if constexpr (PIN) { if (special && mg_bit(g.r.rbit, ebase + e)) cand.v[WL - 1] -= 1ull; }
+                    if (wi_lt<WL>(cand, best)) { best = cand; improved = true; }
                 }
                 __syncthreads(); // every read of this iteration is done
-                if (improved) { wi_store<NL>(s_d + (size_t)tid * NL, best); s_flag[it & 1] = 1; }
+                if (improved) { wi_store<WL>(s_d + (size_t)tid * WL, best); s_flag[it & 1] = 1; }
                 if (tid == 0) s_flag[(it + 1) & 1] = 0;
                 __syncthreads();
                 chg = s_flag[it & 1] != 0;
                 it++;
                 if (++inner > NT + 8) { bad = true; break; } // a chunk of NT nodes settles in <= NT rounds unless a cycle is negative
             }
-            if (v >= 0 && !wi_eq<NL>(best, cur)) { // improved: back to global memory, and the predecessors outside the chunk are open again
-                wi_store<NL>(dt + (size_t)v * NL, best);
+            if (v >= 0 && !wi_eq<WL>(best, cur)) { // improved: back to global memory, and the predecessors outside the chunk are open again
+                wi_store<WL>(dt + (size_t)v * WL, best);
                 int lo = V, hl = -1, hr = -1; // before this chunk (next sweep) / behind it (this sweep)
                 for (uint32_t e = in_off[v], x1 = in_off[v + 1]; e < x1; e++) {
                     const int p = mg_idx((int)ESRC_NODE(esrc[e]), V);
@@ -243,7 +260,8 @@ __device__ __forceinline__ double wi_to_double_rn(WInt<NL> x) {
 
 template <int NL, class G = DMarg>
 __global__ __launch_bounds__(NT) void k_margins(DBatch b, G g) {
-    constexpr bool COND = mg_cond<G>;
+    constexpr bool COND = mg_cond<G>, PIN = mg_pin<G>;
+    constexpr int WL = NL + (PIN ? 1 : 0);
     const DMeta *meta = &b.meta[blockIdx.x];
     if constexpr (COND) { if (!g.r.sel[blockIdx.x] || !mg_contig(meta) || meta->sssp_nl != NL || g.r.mstat[blockIdx.x]) return; }
     else { if (!mg_contig(meta) || meta->sssp_nl != NL || g.mstat[blockIdx.x]) return; }
@@ -259,13 +277,14 @@ __global__ __launch_bounds__(NT) void k_margins(DBatch b, G g) {
     const long long *gt = gtab_of(b, meta);
     const uint64_t *ds, *dt;
     phx_orf_margin *rec;
-    if constexpr (COND) { ds = g.r.ds + (size_t)meta->node_off * g.r.ds_stride; dt = g.r.dist_t + (size_t)meta->node_off * b.dist_stride; rec = g.r.rec + meta->orf_off; }
+    if constexpr (PIN) { ds = g.r.ds + (size_t)meta->node_off * g.r.ds_stride; dt = g.r.dist_t + (size_t)meta->node_off * g.r.dt_stride; rec = g.r.rec + meta->orf_off; }
+    else if constexpr (COND) { ds = g.r.ds + (size_t)meta->node_off * g.r.ds_stride; dt = g.r.dist_t + (size_t)meta->node_off * b.dist_stride; rec = g.r.rec + meta->orf_off; }
     else { ds = b.dist + (size_t)meta->node_off * b.dist_stride; dt = g.dist_t + (size_t)meta->node_off * b.dist_stride; rec = g.rec + meta->orf_off; }
     [[maybe_unused]] const uint64_t ebase = (uint64_t)meta->edge_off;
     [[maybe_unused]] bool biased = false;
     if constexpr (COND) biased = re_mode_bias(g.q.mode[blockIdx.x]);
-    const WInt<NL> D = wi_load<NL>(ds + (size_t)(V - 1) * NL);
-    const bool d_ok = !wi_unreached<NL>(D);
+    const WInt<WL> D = wi_load<WL>(ds + (size_t)(V - 1) * WL);
+    const bool d_ok = !wi_unreached<WL>(D);
     for (int k = (int)blockIdx.y * NT + (int)threadIdx.x; k < meta->n_orf; k += (int)gridDim.y * NT) {
         const DOrf o = orf[k];
         const int sn = onode[k], tn = grp[o.grp].node;
@@ -285,17 +304,27 @@ __global__ __launch_bounds__(NT) void k_margins(DBatch b, G g) {
         for (uint32_t x = in_off[v], x1 = in_off[v + 1]; x < x1; x++)
             if (ESRC_NODE(esrc[x]) == (uint32_t)u) { e = x; break; }
         if constexpr (COND) { if (e != 0xffffffffu && mg_bit(g.q.mask, ebase + e)) e = 0xffffffffu; } // a refused ORF: no path of G' runs through it
+        [[maybe_unused]] int32_t lost = 0;
         if (e != 0xffffffffu && d_ok) {
-            const WInt<NL> du = wi_load<NL>(ds + (size_t)u * NL), dv = wi_load<NL>(dt + (size_t)v * NL);
-            if (!wi_unreached<NL>(du) && !wi_unreached<NL>(dv)) {
-                WInt<NL> w = ew_decode<NL>(edge_wenc(esrc[e], ew, e, gt)); // the edge's own integer, not one recomputed from oweight
-                if constexpr (COND) { if (biased && mg_bit(g.q.bbit, ebase + e)) w = wi_add<NL>(w, ew_decode<NL>(g.q.bval[ebase + e])); }
-                const WInt<NL> delta = wi_add<NL>(wi_add<NL>(du, w), wi_add<NL>(dv, wi_neg<NL>(D)));
+            const WInt<WL> du = wi_load<WL>(ds + (size_t)u * WL), dv = wi_load<WL>(dt + (size_t)v * WL);
+            if (!wi_unreached<WL>(du) && !wi_unreached<WL>(dv)) {
+                WInt<WL> w = ew_decode<WL>(edge_wenc(esrc[e], ew, e, gt)); // the edge's own integer, not one recomputed from oweight
+                if constexpr (COND) { if (biased && mg_bit(g.q.bbit, ebase + e)) w = wi_add<WL>(w, ew_decode<WL>(g.q.bval[ebase + e])); }
+                if constexpr (PIN) { if (mg_bit(g.q.req, ebase + e)) w.v[WL - 1] -= 1ull; } // a required ORF: W' = W + B - M
+                const WInt<WL> delta = wi_add<WL>(wi_add<WL>(du, w), wi_add<WL>(dv, wi_neg<WL>(D)));
                 r.through = 1;
+                if constexpr (PIN) { // Delta'' = lost * M + s: the pins the best path through the ORF gives up, and the class's own signed sum
+                    lost = (int32_t)(int64_t)(delta.v[WL - 1] + (delta.v[NL - 1] >> 63));
+                    WInt<NL> sl;
+#pragma unroll
+                    for (int i = 0; i < NL; i++) sl.v[i] = delta.v[i];
+                    r.margin = wi_to_double_rn<NL>(sl) / 1000.0;
+                } else
                 r.margin = wi_to_double_rn<NL>(delta) / 1000.0; // one correctly rounded division, as float(delta) / 1000.0
             }
         }
         rec[k] = r;
+        if constexpr (PIN) g.r.lost[meta->orf_off + k] = lost;
     }
 }
 
@@ -336,6 +365,49 @@ __global__ __launch_bounds__(NT) void k_rmg_apply(DBatch b, DMarg g, DReann q, D
             if (od[x] == (uint32_t)v) { // (no such edge: the ORF is ignored)
                 if (f == 1) atomicOr(&r.fbit[(ebase + x) >> 5], 1u << ((ebase + x) & 31));
                 else { r.bval[ebase + x] = B; atomicOr(&r.bbit[(ebase + x) >> 5], 1u << ((ebase + x) & 31)); }
+                break;
+            }
+    }
+}
+
+// ---- pinned margins (DESIGN.md §24): what k_sssp_rev<NL, MgPin> reads ----
+// k_rmg_apply for the contigs with DPmarg.sel == 1 (solved again under the required policy, status 0), with code 2 of DReann.forb as well: a
+// required ORF sets its out-edge position's bit in rbit, and, as in k_rs_mask, keeps its bias beside it; a refused one sets fbit and nothing
+// else.  The same range checks.
+__global__ __launch_bounds__(NT) void k_pmg_apply(DBatch b, DMarg g, DReann q, DPmarg r) {
+    const DMeta *meta = &b.meta[blockIdx.x];
+    if (r.sel[blockIdx.x] != 1 || !mg_contig(meta)) return;
+    const DOrf *orf = b.orf + meta->orf_off;
+    const DGrp *grp = b.grp + meta->grp_off;
+    const int32_t *onode = b.onode + meta->orf_off;
+    const uint8_t *forb = q.forb + meta->orf_off;
+    const bool biased = re_mode_bias(q.mode[blockIdx.x]);
+    const long long *bias = biased ? q.bias + meta->orf_off : nullptr;
+    const uint32_t *oo = g.out_off + meta->node_off + blockIdx.x;
+    const uint32_t *od = g.out_dst + meta->edge_off;
+    const uint64_t ebase = (uint64_t)meta->edge_off;
+    const int V = meta->n_node;
+    const uint32_t E = (uint32_t)meta->n_edge;
+    for (int k = (int)blockIdx.y * NT + (int)threadIdx.x; k < meta->n_orf; k += (int)gridDim.y * NT) {
+        const uint8_t f = forb[k];
+        const long long B = biased ? bias[k] : 0ll;
+        if (f != 1 && f != 2 && B == 0) continue;
+        const DOrf o = orf[k];
+        if (o.grp < 0 || o.grp >= meta->n_grp) continue;
+        const int sn = onode[k], tn = grp[o.grp].node;
+        const bool fwd = o.frame > 0;
+        const int u = fwd ? sn : tn, v = fwd ? tn : sn; // start -> stop on the forward strand, stop -> start on the reverse (functions.py:310-316)
+        if (u < 0 || v < 0 || u >= V || v >= V) continue;
+        uint32_t x = oo[u], x1 = oo[u + 1];
+        if (x1 > E) x1 = E; // (the CSR's own offsets: never beyond the contig's edges)
+        for (; x < x1; x++)
+            if (od[x] == (uint32_t)v) { // (no such edge: the ORF is ignored)
+                const uint32_t bit = 1u << ((ebase + x) & 31);
+                if (f == 1) atomicOr(&r.fbit[(ebase + x) >> 5], bit);
+                else {
+                    if (f == 2) atomicOr(&r.rbit[(ebase + x) >> 5], bit);
+                    if (B != 0) { r.bval[ebase + x] = B; atomicOr(&r.bbit[(ebase + x) >> 5], bit); }
+                }
                 break;
             }
     }
