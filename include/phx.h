@@ -209,6 +209,7 @@ int phx_create(const phx_params *params, int device, void *stream, phx_ctx **out
 #define PHX_CREATE_CERT_WIDE 128u /* every contig through the certificate's general kernel (otherwise only contigs of more than 12288 nodes) */
 #define PHX_CREATE_NO_DUO 4096u /* 128-bit contigs are solved by k_sssp_wave<2> (one wavefront per contig) instead of k_sssp_duo (a feeder and a solver wavefront per contig) */
 #define PHX_CREATE_NO_SEG 8192u /* small batches solve every contig by one sweep (one wavefront pair), not by up to 16 segments side by side that k_seg_merge joins and proves (phx_sssp_seg.inc) */
+#define PHX_CREATE_NO_CHAIN 16384u /* nodes, node attributes, edge count and scan of a contig as four staged launches, not as the one launch with a workgroup per contig (k_graph_chain); env PHX_NO_CHAIN=1 does the same */
 #define PHX_CREATE_NO_FUSE 2048u /* batches of up to 4 contigs and 40 kb in all run their front end (ORF count ... edge fill) as the staged kernels of large batches, not as the one fused launch (k_front) */
 #define PHX_CREATE_NO_EXACT 1024u /* phx_download* hand out the device's gene lists as they are: no certificate is asked for and no contig is solved again on the host */
 int phx_create_ex(const phx_params *params, int device, void *stream, uint32_t flags, phx_ctx **out);
@@ -644,6 +645,9 @@ int64_t phx_plan_timeouts(phx_ctx *ctx);
  * Negative (-(runs) - 1): that kernel once waited ~4 ms at a grid barrier because its workgroups were not all resident (the GPU was
  * shared), the run was repeated with the staged kernels, and the context has used those since. */
 int64_t phx_front_runs(phx_ctx *ctx);
+/* Runs of this context whose nodes, node attributes, edge count and scan were the one launch k_graph_chain (steady-state runs of batches that are
+ * neither a few long contigs nor k_front's; 0 under PHX_CREATE_NO_CHAIN). */
+int64_t phx_chain_runs(phx_ctx *ctx);
 /* Runs of this context whose 128-bit contigs were solved in segments (batches of up to 32 contigs with a contig of 10 kb or more: a contig's
  * shortest path by up to 32 wavefront pairs side by side in frames of their own, joined by a constant each and PROVEN by one pass over the
  * edges — k_seg_join / k_seg_close, phx_sssp_seg.inc).  A contig whose segments cannot be joined or proven (about 2 % of random contigs:

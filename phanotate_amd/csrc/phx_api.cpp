@@ -125,7 +125,7 @@ struct phx_ctx {
     bool in_flight = false;      // phx_run_async has enqueued a run that phx_wait has not collected yet
     int pend_mask = 0;
     int64_t pend_lds[4] = {0, 0, 0, 0};
-    hipEvent_t ev_fork = nullptr, ev_fork_plan = nullptr, ev_fork_nodes = nullptr, ev_join_nodes = nullptr, ev_fork_pre = nullptr, ev_join_pre = nullptr, ev_fork_orf = nullptr, ev_join_orf = nullptr, ev_fork_score = nullptr, ev_join_score = nullptr, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev_fork = nullptr, ev_fork_plan = nullptr, ev_fork_pre = nullptr, ev_fork_stats = nullptr, ev_join_score = nullptr, ev_fork_oterm = nullptr, ev_join_oterm = nullptr, ev_fork_orf = nullptr, ev_join_orf = nullptr, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
     phx_params params;
     std::string err;
     // device constants
@@ -182,7 +182,7 @@ struct phx_ctx {
     DevBuf b_meta0;          // the per-contig records as a run starts (layout fields set, accumulators zero): copied over b_meta on the device at the start of every run
     bool meta0_dirty = true; // batch layout changed since b_meta0 was written
     int runs_on_layout = 0;  // completed runs since the batch layout last changed (a graph is captured from the second on)
-    DevBuf b_node, b_parent, b_inoff, b_no, b_npos, b_ehit, b_mreach, b_olist, b_dist, b_esrc, b_ew, b_ewl, b_path, b_genes, b_gtot, b_tot, b_lpart, b_res, b_sord, b_gtab, b_erank;
+    DevBuf b_node, b_parent, b_inoff, b_no, b_npos, b_olink, b_ehit, b_mreach, b_olist, b_dist, b_esrc, b_ew, b_ewl, b_path, b_genes, b_gtot, b_tot, b_lpart, b_res, b_sord, b_gtab, b_erank;
     DTotals *h_tot = nullptr; // pinned
     bool have_plan = false;    // a run completed on this context: its buffers, solver classes and LDS sizes are the first guess for the next
     int last_mask = 0;
@@ -203,7 +203,7 @@ struct phx_ctx {
     bool no_fuse = false;          // PHX_CREATE_NO_FUSE: small batches through the staged kernels as well
     bool duo = true;               // 128-bit contigs: k_sssp_duo (feeder + solver wavefront) instead of k_sssp_wave<2> (PHX_CREATE_NO_DUO, env PHX_NO_DUO=1: off)
     int front_spins = 8000;        // FRONT_SPINS of k_front (env PHX_FRONT_SPINS at phx_create)
-    bool side_score = true;        // k_score on a side stream beside k_node_attr and the edge count (env PHX_NO_SIDE_SCORE=1: in line)
+    bool chain = true;             // nodes, attributes, edge count and scan of a contig in one launch (k_graph_chain); PHX_CREATE_NO_CHAIN, env PHX_NO_CHAIN=1: the four staged launches
     int orf_stream = 1;            // which side stream k_edges_orf takes (env PHX_ORF_STREAM: 0..3; -1: the main stream, in front of the edge fill)
     bool orf_rows = true;          // the ORF edges' rows by k_edges_orf beside the edge fill (env PHX_NO_ORF_ROWS=1: by k_edges<true> itself)
     bool eager_cert = true;        // phx_run_async puts the certificate behind the run (env PHX_NO_EAGER_CERT=1: it does not)
@@ -211,6 +211,8 @@ struct phx_ctx {
     bool pend_front = false;       // the run in flight (or the captured graph) has k_front as its front end
     bool front_off = false;        // k_front once waited too long at a grid barrier on this context (its workgroups were not all resident): staged kernels from then on
     int64_t front_runs = 0;        // runs of this context whose front end was k_front (phx_front_runs)
+    bool pend_chain = false;       // the run in flight (or the captured graph) has k_graph_chain in it
+    int64_t chain_runs = 0;        // runs of this context with k_graph_chain (phx_chain_runs)
     // small batches: a contig's shortest path by up to 16 wavefront pairs side by side, joined and proven by k_seg_merge (phx_sssp_seg.inc)
     bool seg_on = true;            // PHX_CREATE_NO_SEG, env PHX_NO_SEG=1: off
     bool seg_off = false;          // a contig of this batch could not be joined or proven (it was solved by one sweep in the same run): one sweep per contig until the next batch is uploaded
@@ -424,9 +426,8 @@ struct StageTimer {
         str = on_stream ? on_stream : c->stream;
         if (on) { a = get_event(c); b = get_event(c); (void)hipEventRecord(a, str); }
     }
-    ~StageTimer() {
-        if (on) { (void)hipEventRecord(b, str); c->pending.push_back({st, {a, b}}); }
-    }
+    void stop() { if (on) { (void)hipEventRecord(b, str); c->pending.push_back({st, {a, b}}); on = false; } }
+    ~StageTimer() { stop(); }
 };
 void collect_timers(phx_ctx *c) {
     for (auto &p : c->pending) {
@@ -459,6 +460,7 @@ void current_caps(const phx_ctx *c, DCaps *k) {
     for (const DevBuf *q : {&c->b_parent, &c->b_path, &c->b_olist}) v = std::min(v, cap_of(*q, 4, 8));
     v = std::min(v, cap_of(c->b_no, 8, 8));
     v = std::min(v, cap_of(c->b_npos, 4, 8));
+    v = std::min(v, cap_of(c->b_olink, 4, 8));
     v = std::min(v, cap_of(c->b_ehit, 8, 8));
     v = std::min(v, cap_of(c->b_erank, 16, 8));
     v = std::min(v, cap_of(c->b_mreach, 16, 8));
@@ -498,6 +500,7 @@ void fill_batch(phx_ctx *c, DBatch *b) {
     b->in_off = (uint32_t *)c->b_inoff.p;
     b->no = (double *)c->b_no.p;
     b->npos = (int32_t *)c->b_npos.p;
+    b->olink = (int32_t *)c->b_olink.p;
     b->ehit = (uint64_t *)c->b_ehit.p;
     b->erank = (int4 *)c->b_erank.p;
     b->mreach = (uint32_t *)c->b_mreach.p;
@@ -711,7 +714,7 @@ int phx_params_from_flags(const char *start_codons, const char *stop_codons, int
 int phx_create(const phx_params *params, int device, void *stream, phx_ctx **out) { return phx_create_ex(params, device, stream, stream ? PHX_CREATE_USE_STREAM : 0u, out); }
 
 int phx_create_ex(const phx_params *params, int device, void *stream, uint32_t flags, phx_ctx **out) {
-    if (!out || (flags & ~(PHX_CREATE_USE_STREAM | PHX_CREATE_NO_GRAPH | PHX_CREATE_SIZE_EVERY_RUN | PHX_CREATE_SOLVER_GLOBAL | PHX_CREATE_SOLVER_NO_WAVE | PHX_CREATE_NO_CERTIFY | PHX_CREATE_CERT_TIGHT | PHX_CREATE_CERT_WIDE | PHX_CREATE_POISON | PHX_CREATE_ONE_STREAM | PHX_CREATE_NO_EXACT | PHX_CREATE_NO_FUSE | PHX_CREATE_NO_DUO | PHX_CREATE_NO_SEG)) || (stream && !(flags & PHX_CREATE_USE_STREAM))) return PHX_E_ARG;
+    if (!out || (flags & ~(PHX_CREATE_USE_STREAM | PHX_CREATE_NO_GRAPH | PHX_CREATE_SIZE_EVERY_RUN | PHX_CREATE_SOLVER_GLOBAL | PHX_CREATE_SOLVER_NO_WAVE | PHX_CREATE_NO_CERTIFY | PHX_CREATE_CERT_TIGHT | PHX_CREATE_CERT_WIDE | PHX_CREATE_POISON | PHX_CREATE_ONE_STREAM | PHX_CREATE_NO_EXACT | PHX_CREATE_NO_FUSE | PHX_CREATE_NO_DUO | PHX_CREATE_NO_SEG | PHX_CREATE_NO_CHAIN)) || (stream && !(flags & PHX_CREATE_USE_STREAM))) return PHX_E_ARG;
     *out = nullptr;
     int rc = check_params(params);
     if (rc) return rc;
@@ -737,7 +740,7 @@ int phx_create_ex(const phx_params *params, int device, void *stream, uint32_t f
     { const char *e = getenv("PHX_NO_EAGER_CERT"); c->eager_cert = !(e && e[0] == '1'); }
     { const char *e = getenv("PHX_NO_ORF_ROWS"); c->orf_rows = !(e && e[0] == '1'); }
     { const char *e = getenv("PHX_ORF_STREAM"); if (e && *e) { const int v = atoi(e); if (v >= -1 && v <= 3) c->orf_stream = v; } }
-    { const char *e = getenv("PHX_NO_SIDE_SCORE"); c->side_score = !(e && e[0] == '1'); }
+    { const char *e = getenv("PHX_NO_CHAIN"); c->chain = !(flags & PHX_CREATE_NO_CHAIN) && !(e && e[0] == '1'); }
     { const char *e = getenv("PHX_NO_DUO"); c->duo = !(flags & PHX_CREATE_NO_DUO) && !(e && e[0] == '1'); }
     { const char *e = getenv("PHX_NO_SEG"); c->seg_on = !(flags & PHX_CREATE_NO_SEG) && !(e && e[0] == '1'); }
     { const char *e = getenv("PHX_SEG_MAX_N"); if (e && atoi(e) >= 0) c->seg_max_n = atoi(e); }
@@ -764,10 +767,10 @@ int phx_create_ex(const phx_params *params, int device, void *stream, uint32_t f
     if (hipEventCreateWithFlags(&c->ev_upload, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_layout, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_piece[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_piece[1], hipEventDisableTiming) != hipSuccess) { c->err = "hipEventCreate failed"; return fail(PHX_E_HIP); }
     if (hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_fork_plan, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_fork_nodes, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_join_nodes, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_fork_pre, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_join_pre, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_fork_oterm, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_join_oterm, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_fork_pre, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_fork_orf, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_join_orf, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_fork_score, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_join_score, hipEventDisableTiming) != hipSuccess) { c->err = "hipEventCreate failed"; return fail(PHX_E_HIP); }
+        hipEventCreateWithFlags(&c->ev_fork_stats, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_join_score, hipEventDisableTiming) != hipSuccess) { c->err = "hipEventCreate failed"; return fail(PHX_E_HIP); }
     DParams dp;
     build_dparams(params, &dp);
     { // the reference's default codon tables (file_handling.py:51-53): k_features then uses their formulas instead of the table walk
@@ -804,18 +807,23 @@ void phx_destroy(phx_ctx *c) {
     for (int k = 0; k < 2; k++) if (c->ev_piece[k]) (void)hipEventDestroy(c->ev_piece[k]);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_fork_plan) (void)hipEventDestroy(c->ev_fork_plan);
-    if (c->ev_fork_nodes) (void)hipEventDestroy(c->ev_fork_nodes);
-    if (c->ev_join_nodes) (void)hipEventDestroy(c->ev_join_nodes);
+    if (c->ev_fork_oterm) (void)hipEventDestroy(c->ev_fork_oterm);
+    if (c->ev_join_oterm) (void)hipEventDestroy(c->ev_join_oterm);
     if (c->ev_fork_pre) (void)hipEventDestroy(c->ev_fork_pre);
     if (c->ev_fork_orf) (void)hipEventDestroy(c->ev_fork_orf);
-    if (c->ev_fork_score) (void)hipEventDestroy(c->ev_fork_score);
+    if (c->ev_fork_stats) (void)hipEventDestroy(c->ev_fork_stats);
     if (c->ev_join_score) (void)hipEventDestroy(c->ev_join_score);
     if (c->ev_join_orf) (void)hipEventDestroy(c->ev_join_orf);
-    if (c->ev_join_pre) (void)hipEventDestroy(c->ev_join_pre);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
+#ifndef PHX_SIDE_B_MIN
+#define PHX_SIDE_B_MIN 0 // batches of at least this many contigs run chain B (k_orf_stats, k_score) on its side stream (see enqueue_run)
+#endif
+#ifndef PHX_OTERM_SIDE_MIN
+#define PHX_OTERM_SIDE_MIN 600 // ... and k_node_oterm beside k_layout2 instead of in line in front of it
+#endif
 #ifndef PHX_PLAN_STREAM_MAX
 #define PHX_PLAN_STREAM_MAX 800 // batches of up to this many contigs: k_sssp_wave<2,0> runs beside k_wave_plan<2,0> (run_pipeline).  Beyond, the planner is done before the edge fill is (1000 x 50 kb: 0.35 against 0.43 ms) and there is nothing to gain (measured with 1024: +0.7 % on the step, +2 % on two batches in flight)
 #endif
@@ -1095,6 +1103,7 @@ int enqueue_run(phx_ctx *c, bool learn, int &mask, int64_t lds[4]) {
     const uint32_t front_stages = (1u << ST_ORF_COUNT) | (1u << ST_ORF_EMIT) | (1u << ST_ORF_STATS) | (1u << ST_SCORE) | (1u << ST_NODES) | (1u << ST_EDGE_COUNT) | (1u << ST_EDGE_FILL);
     const bool fuse = !learn && !(c->prof && (c->prof_mask & front_stages)) && !c->no_fuse && !c->front_off && phxk_front_blocks_y(&b) > 0;
     DTotals *ht = c->h_tot;
+    c->pend_chain = false;
     c->pend_front = fuse; // (stands for the replays of the graph this enqueue is captured into: finish_once counts the runs)
     if (fuse) {
         b.defer_overlap = c->max_len < (1 << 21) ? 1 : 0;
@@ -1103,11 +1112,18 @@ int enqueue_run(phx_ctx *c, bool learn, int &mask, int64_t lds[4]) {
         mask = c->last_mask;
         for (int k = 0; k < 4; k++) lds[k] = c->last_lds[k];
     } else {
-    // word-prefix popcounts of the bitmaps (for k_orf_stats) on a side stream, beside the ORF scan
-    HIPCHK(c, hipEventRecord(c->ev_fork_pre, s));
-    HIPCHK(c, hipStreamWaitEvent(c->aux[0], c->ev_fork_pre, 0));
-    phxk_bit_prefix(&b, c->aux[0]);
-    HIPCHK(c, hipEventRecord(c->ev_join_pre, c->aux[0]));
+    // Two chains lead from the ORF scan to k_layout2 and the edge fill, and each has a stream of its own:
+    //   A (this stream, behind k_orf<true>): nodes -> attributes -> edge count -> scan.  Needs the ORF and group records only; decides when k_layout2 starts.
+    //   B (aux[0]): prefix popcounts and gap table beside the ORF scan, then — behind k_orf<true> — ORF statistics -> ORF weights (k_layout2 waits for these:
+    //     its integer classes) -> the nodes' o1/o2 terms (behind the scan's stream position; the fill waits for these).
+    // No event wait inside A.  While the buffers are being sized, on one stream and without side streams: everything in line, in dependency order.
+    const bool side_b = !learn && !c->one_stream && c->aux[0] && c->aux[0] != s && c->n >= PHX_SIDE_B_MIN;
+    hipStream_t sb = side_b ? c->aux[0] : s;
+    if (side_b) {
+        HIPCHK(c, hipEventRecord(c->ev_fork_pre, s));
+        HIPCHK(c, hipStreamWaitEvent(sb, c->ev_fork_pre, 0));
+    }
+    phxk_bit_prefix(&b, sb);
     { StageTimer t(c, ST_ORF_COUNT); phxk_orf_count(&b, s); phxk_layout1(&b, s); }
     HIPCHK(c, hipGetLastError());
     if (learn) { // sync #1: totals of ORFs / groups / nodes -> buffers
@@ -1129,6 +1145,7 @@ int enqueue_run(phx_ctx *c, bool learn, int &mask, int64_t lds[4]) {
         if ((rc = ensure(c, c->b_inoff, (NV + (size_t)n + 1) * 4))) return rc;
         if ((rc = ensure(c, c->b_no, NV * 8))) return rc;
         if ((rc = ensure(c, c->b_npos, NV * 4))) return rc;
+        if ((rc = ensure(c, c->b_olink, NV * 4))) return rc;
         if ((rc = ensure(c, c->b_ehit, NV * 8))) return rc;
         if ((rc = ensure(c, c->b_erank, NV * 16))) return rc;
         if ((rc = ensure(c, c->b_mreach, NV * 16))) return rc;
@@ -1144,26 +1161,36 @@ int enqueue_run(phx_ctx *c, bool learn, int &mask, int64_t lds[4]) {
     }
     fill_batch(c, &b);
     { StageTimer t(c, ST_ORF_EMIT); phxk_orf_emit(&b, s); }
-    // nodes (coverage, ranks, records, order) beside the ORF statistics: both only read what k_orf<true> wrote
-    HIPCHK(c, hipEventRecord(c->ev_fork_nodes, s));
-    HIPCHK(c, hipStreamWaitEvent(c->aux[1], c->ev_fork_nodes, 0));
-    phxk_nodes(&b, c->aux[1]);
-    HIPCHK(c, hipEventRecord(c->ev_join_nodes, c->aux[1]));
-    { StageTimer t(c, ST_ORF_STATS); HIPCHK(c, hipStreamWaitEvent(s, c->ev_join_pre, 0)); phxk_orf_stats(&b, s); }
-    // the ORF weights are needed by k_layout2 (integer class) and by the edge fill, not by the node attributes or the edge count: beside them
-    // (large batches only: a side stream costs an event round trip — 10 us of a lone genome's 330 —, and with more streams than hardware queues a side
-    //  stream's kernel may sit behind another side stream's: behind the planner, which outlasts the edge fill below ~500 contigs — Lambda 0.34 -> 0.39 ms,
-    //  64 x 50 kb 0.78 -> 0.91 with k_edges_orf on its side stream, profiles/r06_side_streams_small.txt)
-    const bool big_batch = c->n >= 600;
-    const bool side_score = c->side_score && big_batch && !c->one_stream && c->aux[0] && !learn;
-    if (side_score) {
-        HIPCHK(c, hipEventRecord(c->ev_fork_score, s));
-        HIPCHK(c, hipStreamWaitEvent(c->aux[0], c->ev_fork_score, 0));
-        { StageTimer t(c, ST_SCORE, c->aux[0]); phxk_score(&b, c->aux[0]); }
-        HIPCHK(c, hipEventRecord(c->ev_join_score, c->aux[0]));
-    } else { StageTimer t(c, ST_SCORE); phxk_score(&b, s); }
-    { StageTimer t(c, ST_NODES); HIPCHK(c, hipStreamWaitEvent(s, c->ev_join_nodes, 0)); phxk_node_attr(&b, s); }
-    { StageTimer t(c, ST_EDGE_COUNT); phxk_edges_count(&b, s); if (side_score) HIPCHK(c, hipStreamWaitEvent(s, c->ev_join_score, 0)); phxk_layout2(&b, s); }
+    if (side_b) {
+        HIPCHK(c, hipEventRecord(c->ev_fork_stats, s));
+        HIPCHK(c, hipStreamWaitEvent(sb, c->ev_fork_stats, 0));
+    }
+    { StageTimer t(c, ST_ORF_STATS, sb); phxk_orf_stats(&b, sb); } // (the timers of chain B: on the stream it runs on, as ST_WAVE_PLAN)
+    { StageTimer t(c, ST_SCORE, sb); phxk_score(&b, sb); }
+    if (side_b) HIPCHK(c, hipEventRecord(c->ev_join_score, sb));
+    // one launch for chain A where a workgroup per contig runs the node stages anyway (not a few long contigs), unless one of its stages is being timed
+    const uint32_t chain_stages = (1u << ST_NODES) | (1u << ST_EDGE_COUNT);
+    const bool chained = c->chain && !learn && !(c->prof && (c->prof_mask & chain_stages)) && phxk_chain_ok(&b);
+    c->pend_chain = chained;
+    if (chained) phxk_graph_chain(&b, s);
+    else { StageTimer t(c, ST_NODES); phxk_nodes(&b, s); phxk_node_attr(&b, s); }
+    StageTimer t_count(c, ST_EDGE_COUNT);
+    if (!chained) phxk_edges_count(&b, s);
+    // the o1/o2 terms need the scan's stream position (k_node_attr's ORF indices) and k_orf_stats; only the fill reads them.  Large batches: beside
+    // k_layout2 on chain B's stream; below 600 contigs in line (on the side stream there too: Lambda 0.320 -> 0.334 ms, T4 0.419 -> 0.433, 64 x 50 kb 0.753 -> 0.769;
+    // chain B itself in line below 600 contigs: 0.362 / 0.462 / 0.787 — profiles/r07_a_ab_small_gates.txt)
+    const bool side_oterm = side_b && c->n >= PHX_OTERM_SIDE_MIN;
+    if (side_oterm) {
+        HIPCHK(c, hipEventRecord(c->ev_fork_oterm, s));
+        HIPCHK(c, hipStreamWaitEvent(sb, c->ev_fork_oterm, 0));
+        phxk_node_oterm(&b, sb);
+        HIPCHK(c, hipEventRecord(c->ev_join_oterm, sb));
+    }
+    if (side_b) HIPCHK(c, hipStreamWaitEvent(s, c->ev_join_score, 0));
+    if (!side_oterm) phxk_node_oterm(&b, s);
+    phxk_layout2(&b, s);
+    t_count.stop();
+    if (side_oterm) HIPCHK(c, hipStreamWaitEvent(s, c->ev_join_oterm, 0));
     HIPCHK(c, hipGetLastError());
     mask = c->last_mask;
     for (int k = 0; k < 4; k++) lds[k] = c->last_lds[k];
@@ -1445,6 +1472,7 @@ int finish_once(phx_ctx *c) {
     c->have_plan = true;
     c->runs_on_layout++;
     if (c->pend_front) c->front_runs++;
+    if (c->pend_chain) c->chain_runs++;
     return PHX_OK;
 }
 
@@ -2441,6 +2469,12 @@ int64_t phx_front_runs(phx_ctx *c) {
     if (!c) return PHX_E_ARG;
     { const int rs = wait_in_flight(c); if (rs) return rs; }
     return c->front_off ? -c->front_runs - 1 : c->front_runs;
+}
+
+int64_t phx_chain_runs(phx_ctx *c) {
+    if (!c) return PHX_E_ARG;
+    { const int rs = wait_in_flight(c); if (rs) return rs; }
+    return c->chain_runs;
 }
 
 int64_t phx_plan_timeouts(phx_ctx *c) {

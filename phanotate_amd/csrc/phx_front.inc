@@ -83,6 +83,7 @@ __global__ __launch_bounds__(NT, EDGE_WPS) void k_front(DBatch b) {
     if (by == 0) b_node_order(b, bx);
     FRONT_SYNC();
     b_node_attr(b, bx, by, gy);
+    b_node_oterm(b, bx, by, gy); // (the same thread per node: no barrier between them; b_orf_stats ran stages ago)
     FRONT_SYNC();
     b_edges<false, false>(b, bx, by, gy);
     FRONT_SYNC();

@@ -21,6 +21,7 @@ __device__ __forceinline__ LinkInfo link_info(uint32_t link, const DOrf *orf, co
 __device__ __forceinline__ int tnode_plane(int info) { return (NFRAME(info) > 0 ? 0 : 2) + (NTYPE(info) == 1 ? 1 : 0); }
 
 // coverage by the longest ORF of every stop-group (functions.py:321-330), 16 lanes per group, one atomicOr per word
+template <int T = NT> // T: threads of the workgroup (the staged kernels: NT; k_graph_chain: its own)
 __device__ __forceinline__ void b_node_cov(const DBatch &b, const int bx, const int by, const int gy) {
     if (b.tot->overflow) return; // a buffer of this run is too small: the host grows it and runs again
     DMeta *meta = &b.meta[bx];
@@ -32,13 +33,13 @@ __device__ __forceinline__ void b_node_cov(const DBatch &b, const int bx, const 
     if (b.tnode && by == 0) { // the nodes add_trnas inserts (functions.py:497-508): one bit per node in its (strand, type) plane
         unsigned long long *tb = (unsigned long long *)(b.tbits + meta->nbits_off / 3 * 4);
         const DTNode *tn = b.tnode + meta->tn_off;
-        for (int k = threadIdx.x; k < meta->n_tnode; k += NT) {
+        for (int k = threadIdx.x; k < meta->n_tnode; k += T) {
             const int q = tn[k].pos - 1;
             atomicOr(&tb[(size_t)tnode_plane(tn[k].info) * 3 * meta->nw + (q >> 6)], 1ull << (q & 63));
         }
     }
     const int sub = threadIdx.x & 15;
-    for (int g = (int)by * (NT / 16) + ((int)threadIdx.x >> 4); g < meta->n_grp; g += (int)gy * (NT / 16)) {
+    for (int g = (int)by * (T / 16) + ((int)threadIdx.x >> 4); g < meta->n_grp; g += (int)gy * (T / 16)) {
         const DGrp G = grp[g];
         const DOrf *r = &orf[G.orf_begin + G.n - 1];
         int mi = r->start < r->stop ? r->start : r->stop;
@@ -52,9 +53,10 @@ __global__ __launch_bounds__(NT) void k_node_cov(DBatch b) { b_node_cov(b, (int)
 
 
 // per-word node-rank bases, and the bridge events (a covered base more than 500 after the previous covered base)
+template <int T = NT>
 __device__ __forceinline__ void b_node_rank(const DBatch &b, const int bx) {
     if (b.tot->overflow) return; // a buffer of this run is too small: the host grows it and runs again
-    __shared__ uint32_t s_scan[NT / 64 + 1];
+    __shared__ uint32_t s_scan[T / 64 + 1];
     DMeta *meta = &b.meta[bx];
     const int tid = threadIdx.x;
     if (meta->status < 0) {
@@ -68,7 +70,7 @@ __device__ __forceinline__ void b_node_rank(const DBatch &b, const int bx) {
     auto ldcov = [&](int w) -> uint64_t { return __hip_atomic_load(&cov[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }; // written by L2 atomics (k_node_cov): read at L2
     if (tid == 0) meta->n_bridge = 0;
     __syncthreads();
-    const int per = (nwp + NT - 1) / NT;
+    const int per = (nwp + T - 1) / T;
     const int a = tid * per, e = a + per < nwp ? a + per : nwp;
     uint32_t cnt = 0, lastc = 0; // nodes in my words; last covered base in my words (0 = none; base 0 is never covered)
     for (int w = a; w < e; w++) {
@@ -78,8 +80,8 @@ __device__ __forceinline__ void b_node_rank(const DBatch &b, const int bx) {
         if (cw) lastc = (uint32_t)(w * 64 + 63 - __clzll((long long)cw));
     }
     uint32_t tot, mtot;
-    uint32_t ex = block_excl_scan<NT>(cnt, s_scan, &tot);
-    uint32_t pm = block_excl_max<NT>(lastc, s_scan, &mtot);
+    uint32_t ex = block_excl_scan<T>(cnt, s_scan, &tot);
+    uint32_t pm = block_excl_max<T>(lastc, s_scan, &mtot);
     for (int w = a; w < e; w++) {
         nbase[w] = ex;
         ex += (uint32_t)(__popcll(nbF[w]) + __popcll(nbR[w]));
@@ -139,6 +141,7 @@ __device__ __forceinline__ int node_rank_t(const uint64_t *nbF, const uint64_t *
 }
 
 // every ORF writes its start node, every stop-group its stop node (functions.py:311-318)
+template <int T = NT>
 __device__ __forceinline__ void b_node_build(const DBatch &b, const int bx, const int by, const int gy) {
     if (b.tot->overflow) return; // a buffer of this run is too small: the host grows it and runs again
     DMeta *meta = &b.meta[bx];
@@ -151,7 +154,7 @@ __device__ __forceinline__ void b_node_build(const DBatch &b, const int bx, cons
     int32_t *onode = b.onode + meta->orf_off;
     DGrp *grp = b.grp + meta->grp_off;
     DNode *nd = b.node + meta->node_off;
-    const int gtid = (int)by * NT + (int)threadIdx.x, gstride = (int)gy * NT;
+    const int gtid = (int)by * T + (int)threadIdx.x, gstride = (int)gy * T;
     if (tb) { // the tRNA nodes (not in the close-node bitmaps: the connect rules for them differ, see k_edges)
         const DTNode *tn = b.tnode + meta->tn_off;
         int32_t *tnid = b.tnid + meta->tn_off;
@@ -180,9 +183,10 @@ __global__ __launch_bounds__(NT) void k_node_build(DBatch b) { b_node_build(b, (
 // Node order for the edge kernels: the open nodes (targets of connector edges: ~14 in-edges each and ~27 candidates to
 // test) first, then the target, then the close nodes (1-2 ORF in-edges), so that a wavefront of k_edges works on nodes of
 // one kind instead of idling half its lanes.  One workgroup per contig walks the close-node bitmaps.
+template <int T = NT>
 __device__ __forceinline__ void b_node_order(const DBatch &b, const int bx) {
     if (b.tot->overflow) return;
-    __shared__ uint32_t s_scan[NT / 64 + 1];
+    __shared__ uint32_t s_scan[T / 64 + 1];
     DMeta *meta = &b.meta[bx];
     if (meta->status < 0 || meta->n_node < 2) { if (threadIdx.x == 0) meta->n_open = 0; return; }
     const int V = meta->n_node, ncds = V - 2, TGT = V - 1;
@@ -193,7 +197,7 @@ __device__ __forceinline__ void b_node_order(const DBatch &b, const int bx) {
     {
         uint64_t *wF = b.cbits + meta->cb_off, *wR = wF + meta->ncw;
         const DNode *nd = b.node + meta->node_off;
-        for (int v0 = 0; v0 < 64 * meta->ncw; v0 += NT) {
+        for (int v0 = 0; v0 < 64 * meta->ncw; v0 += T) {
             const int v = v0 + (int)threadIdx.x;
             bool fs = false, rs = false;
             if (v < ncds) {
@@ -206,7 +210,7 @@ __device__ __forceinline__ void b_node_order(const DBatch &b, const int bx) {
         __syncthreads();
     }
     const uint64_t *cF = b.cbits + meta->cb_off, *cR = cF + meta->ncw;
-    const int per = (nwd + NT - 1) / NT;
+    const int per = (nwd + T - 1) / T;
     const int a = (int)threadIdx.x * per, e = a + per < nwd ? a + per : nwd;
     uint32_t no_ = 0, nc_ = 0;
     for (int w = a; w < e; w++) {
@@ -215,8 +219,8 @@ __device__ __forceinline__ void b_node_order(const DBatch &b, const int bx) {
         no_ += (uint32_t)__popcll(~c & valid);
     }
     uint32_t to, tc;
-    uint32_t eo = block_excl_scan<NT>(no_, s_scan, &to);
-    uint32_t ec = block_excl_scan<NT>(nc_, s_scan, &tc);
+    uint32_t eo = block_excl_scan<T>(no_, s_scan, &to);
+    uint32_t ec = block_excl_scan<T>(nc_, s_scan, &tc);
     const int n_open = (int)to + 1; // + the target
     for (int w = a; w < e; w++) {
         const uint64_t valid = range_mask(w, 0, ncds - 1), c = (cF[w] | cR[w]) & valid;
@@ -285,42 +289,60 @@ __device__ __forceinline__ uint32_t other_strand_link(const DNode *nd, int v, in
     return 0u;
 }
 
-// other_end[pos] (last writer wins, orfs.py:19-30) and the o1/o2 term (functions.py:373-384), thread per node
+// other_end[pos] (last writer wins, orfs.py:19-30) and WHICH ORF gives the o1/o2 term (functions.py:373-384), thread per node.  Needs the ORF and
+// group records only, not their statistics: the term itself (one p_stop per node, read by the filling pass alone) follows in b_node_oterm, so that
+// the chain nodes -> attributes -> edge count -> scan never waits for k_orf_stats.
+template <int T = NT>
 __device__ __forceinline__ void b_node_attr(const DBatch &b, const int bx, const int by, const int gy) {
     if (b.tot->overflow) return; // a buffer of this run is too small: the host grows it and runs again
     DMeta *meta = &b.meta[bx];
     if (meta->status < 0 || meta->n_node <= 2) return;
     const int L = meta->L;
     const DOrf *orf = b.orf + meta->orf_off;
-    const DOrfStat *ostat = b.ostat + meta->orf_off;
     const DGrp *grp = b.grp + meta->grp_off;
     DNode *nd = b.node + meta->node_off;
-    double *no = b.no + meta->node_off;
+    int32_t *olink = b.olink + meta->node_off;
     int32_t *npos = b.npos + meta->node_off;
-    const double pgap = contig_pstop(meta->gc, L);
     const int run = meta->n_node - 2;
     if (by == 0 && threadIdx.x == 0) { npos[run] = 0; npos[run + 1] = L + 1; } // source, target
     const int Vn = meta->n_node;
     uint64_t *ehit0 = b.ehit + meta->node_off;
-    for (int v = (int)by * NT + (int)threadIdx.x; v < Vn; v += (int)gy * NT) ehit0[v] = 0ull; // (only open CDS nodes get verdict bits in k_edges<false>)
-    for (int v = (int)by * NT + (int)threadIdx.x; v < run; v += (int)gy * NT) {
+    for (int v = (int)by * T + (int)threadIdx.x; v < Vn; v += (int)gy * T) ehit0[v] = 0ull; // (only open CDS nodes get verdict bits in k_edges<false>)
+    for (int v = (int)by * T + (int)threadIdx.x; v < run; v += (int)gy * T) {
         DNode me = nd[v];
         npos[v] = me.pos;
         const int fr = NFRAME(me.info);
         const uint32_t lmine = me.link;
-        if (LINK_KIND(lmine) == LINK_TRNA) continue; // its other_end came with the node; the o1/o2 term is unused for tRNA pairs (functions.py:388-399)
+        if (LINK_KIND(lmine) == LINK_TRNA) { olink[v] = OLINK_NONE; continue; } // its other_end came with the node; the o1/o2 term is unused for tRNA pairs (functions.py:388-399)
         // the node of the other strand at the same position, if any, is my neighbour in the id order (forward first; tRNA nodes follow)
         uint32_t lother = 0;
         if (fr > 0) { if (v + 1 < run && nd[v + 1].pos == me.pos && LINK_KIND(nd[v + 1].link) != LINK_TRNA) lother = nd[v + 1].link; }
         else { if (v >= 1 && nd[v - 1].pos == me.pos && LINK_KIND(nd[v - 1].link) != LINK_TRNA) lother = nd[v - 1].link; }
         int oe;
         const int ok = o_link(lmine, lother, orf, grp, oe);
-        const double o = ok < 0 ? pgap : ostat[ok].pstop;
         me.other = oe;
         nd[v] = me; // whole records: coalesced 16-byte stores
-        no[v] = o;
+        olink[v] = ok; // (-1: pgap)
     }
 }
+// the o1/o2 term of every CDS node: p_stop of the ORF b_node_attr named (DBatch.olink), thread per node (the mapping of b_node_attr: k_front calls
+// the two in one stage).  Source and target keep the pgap of b_node_rank; tRNA nodes have no term.
+__device__ __forceinline__ void b_node_oterm(const DBatch &b, const int bx, const int by, const int gy) {
+    if (b.tot->overflow) return;
+    const DMeta *meta = &b.meta[bx];
+    if (meta->status < 0 || meta->n_node <= 2) return;
+    const DOrfStat *ostat = b.ostat + meta->orf_off;
+    const int32_t *olink = b.olink + meta->node_off;
+    double *no = b.no + meta->node_off;
+    const double pgap = contig_pstop(meta->gc, meta->L);
+    const int run = meta->n_node - 2;
+    for (int v = (int)by * NT + (int)threadIdx.x; v < run; v += (int)gy * NT) {
+        const int ok = olink[v];
+        if (ok == OLINK_NONE) continue;
+        no[v] = ok < 0 ? pgap : ostat[ok].pstop;
+    }
+}
+__global__ __launch_bounds__(NT) void k_node_oterm(DBatch b) { b_node_oterm(b, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.y); }
 __global__ __launch_bounds__(NT) void k_node_attr(DBatch b) { b_node_attr(b, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.y); }
 
 
@@ -417,36 +439,60 @@ __device__ __forceinline__ void finish_overlaps(uint4 *q, uint32_t *qn, uint32_t
 // DBatch.ewf / esrcf (phx_tap_edges; the run keeps integers only).
 // CODED (with FILL, not TAPW): gap edges may go out in the 4-byte coded form (ESRC_F_GAP; DBatch.gap_code says whether they do in this batch);
 // without it the kernel is the plain-row kernel of rounds 2-5, instruction for instruction.
-template <bool FILL, bool TAPW, bool CODED = false>
+// T: threads of the workgroup.  INWG: the stages in front ran in this very launch (k_graph_chain): what they left by L2 atomics is read at L2.
+// A value every lane holds alike, moved to scalar registers.  Behind stores of the same launch (k_graph_chain) the compiler reads a contig's record with
+// vector loads and keeps every offset and pointer made of it once per LANE: the counting pass then holds twenty pointers in forty VGPRs and spills.
+// ON = false (the staged kernels, whose loads of the record are scalar anyway): the value as it is.
+template <bool ON, class V>
+__device__ __forceinline__ V wg_uniform(V x) {
+    if constexpr (!ON) return x;
+    else if constexpr (sizeof(V) == 4) {
+        int w;
+        __builtin_memcpy(&w, &x, 4);
+        w = __builtin_amdgcn_readfirstlane(w);
+        __builtin_memcpy(&x, &w, 4);
+        return x;
+    } else {
+        static_assert(sizeof(V) == 8, "32- or 64-bit values");
+        int w[2];
+        __builtin_memcpy(w, &x, 8);
+        w[0] = __builtin_amdgcn_readfirstlane(w[0]);
+        w[1] = __builtin_amdgcn_readfirstlane(w[1]);
+        __builtin_memcpy(&x, w, 8);
+        return x;
+    }
+}
+template <bool FILL, bool TAPW, bool CODED = false, int T = NT, bool INWG = false>
 __device__ __forceinline__ void b_edges(const DBatch &b, const int bx, const int by, const int gy) {
     if (b.tot->overflow) return; // a buffer of this run is too small: the host grows it and runs again
     DMeta *meta = &b.meta[bx];
-    if (meta->status < 0 || meta->n_node <= 0) return;
-    const int L = meta->L;
-    const int V = meta->n_node, ncds = V - 2, SRC = V - 2, TGT = V - 1;
-    const DOrf *orf = b.orf + meta->orf_off;
-    const int32_t *onode = b.onode + meta->orf_off;
-    const double *oweight = b.oweight + meta->orf_off;
-    const long long *owi = b.owi + meta->orf_off;
-    const uint8_t *oflag = b.oflag + meta->orf_off;
+    auto U = [](auto x) { return wg_uniform<INWG>(x); }; // (the contig's record: see wg_uniform)
+    if (U(meta->status) < 0 || U(meta->n_node) <= 0) return;
+    const int L = U(meta->L);
+    const int V = U(meta->n_node), ncds = V - 2, SRC = V - 2, TGT = V - 1;
+    const DOrf *orf = b.orf + U(meta->orf_off);
+    const int32_t *onode = b.onode + U(meta->orf_off);
+    const double *oweight = b.oweight + U(meta->orf_off);
+    const long long *owi = b.owi + U(meta->orf_off);
+    const uint8_t *oflag = b.oflag + U(meta->orf_off);
     const double cc = CERT_C(b);
-    const DGrp *grp = b.grp + meta->grp_off;
-    const DNode *nd = b.node + meta->node_off;
-    const double *no = b.no + meta->node_off;
-    const int32_t *npos = b.npos + meta->node_off;
-    uint32_t *in_off = b.in_off + meta->node_off + bx; // V+1 entries per contig
-    uint64_t *ehit = b.ehit + meta->node_off;                   // per open node: which of its first 64 overlap candidates are edges
-    const int nwp = 3 * meta->nw;
-    const uint64_t *nbF = b.nbits + meta->nbits_off, *nbR = nbF + nwp;
-    const uint32_t *nbase = b.nbase + meta->nbits_off / 3;
-    const uint64_t *tb = (b.tnode && meta->n_tnode) ? b.tbits + meta->nbits_off / 3 * 4 : nullptr;
-    const int ntn = tb ? meta->n_tnode : 0;
-    const DTNode *tn = tb ? b.tnode + meta->tn_off : nullptr;
-    const int32_t *tnid = tb ? b.tnid + meta->tn_off : nullptr;
-    const uint64_t *cF = b.cbits + meta->cb_off, *cR = cF + meta->ncw; // close nodes by node id: forward stops / reverse starts (CDS only)
-    const double pgap = contig_pstop(meta->gc, L);
-    const int nbr = meta->n_bridge;
-    const DBridge *bridges = b.bridge + meta->bridge_off;
+    const DGrp *grp = b.grp + U(meta->grp_off);
+    const DNode *nd = b.node + U(meta->node_off);
+    const double *no = b.no + U(meta->node_off);
+    const int32_t *npos = b.npos + U(meta->node_off);
+    uint32_t *in_off = b.in_off + U(meta->node_off) + bx; // V+1 entries per contig
+    uint64_t *ehit = b.ehit + U(meta->node_off);                   // per open node: which of its first 64 overlap candidates are edges
+    const int nwp = 3 * U(meta->nw);
+    const uint64_t *nbF = b.nbits + U(meta->nbits_off), *nbR = nbF + nwp;
+    const uint32_t *nbase = b.nbase + U(meta->nbits_off) / 3;
+    const uint64_t *tb = (b.tnode && U(meta->n_tnode)) ? b.tbits + U(meta->nbits_off) / 3 * 4 : nullptr;
+    const int ntn = tb ? U(meta->n_tnode) : 0;
+    const DTNode *tn = tb ? b.tnode + U(meta->tn_off) : nullptr;
+    const int32_t *tnid = tb ? b.tnid + U(meta->tn_off) : nullptr;
+    const uint64_t *cF = b.cbits + U(meta->cb_off), *cR = cF + U(meta->ncw); // close nodes by node id: forward stops / reverse starts (CDS only)
+    const double pgap = contig_pstop(U(meta->gc), L);
+    const int nbr = INWG ? U(__hip_atomic_load(&meta->n_bridge, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) : meta->n_bridge; // (k_node_rank counts them by atomicAdd)
+    const DBridge *bridges = b.bridge + U(meta->bridge_off);
     bool parallel = false, dense = false, mr_partial = false;
     // score_gap depends only on (length, direction): tabulated once per workgroup, as the record the edge arrays take (encoded
     // integer + inexact flag), instead of one pow and one conversion per gap edge: same strand for length -2..497 (beyond 300 it
@@ -462,13 +508,13 @@ __device__ __forceinline__ void b_edges(const DBatch &b, const int bx, const int
         __syncthreads();
         const long long *gt = b.gtab + (size_t)bx * GT_N;
         const uint16_t *gf = b.gtabf + (size_t)bx * GT_N;
-        for (int i = threadIdx.x; i < GAPN + GAPD; i += NT) { s_gap[i] = (unsigned long long)gt[i]; s_gapf[i] = gf[i]; }
+        for (int i = threadIdx.x; i < GAPN + GAPD; i += T) { s_gap[i] = (unsigned long long)gt[i]; s_gapf[i] = gf[i]; }
         if (threadIdx.x == 0) { s_g100 = __longlong_as_double(gt[GT_N - 1]); s_anyf = (uint32_t)gt[GT_N - 2]; }
         __syncthreads();
     } else if (FILL) { // the tap variant: the fp64 weights themselves
         __syncthreads();
         const double g100 = pow(1.0 - pgap, 100.0);
-        for (int i = threadIdx.x; i < GAPN + GAPD; i += NT) {
+        for (int i = threadIdx.x; i < GAPN + GAPD; i += T) {
             const int length = (i < GAPN ? i : i - GAPN) - 2;
             double w = length > 300 ? g100 + (double)length : 1.0 / pow(1.0 - pgap, (double)length / 3.0);
             if (i >= GAPN) w += 20.0;
@@ -502,11 +548,11 @@ __device__ __forceinline__ void b_edges(const DBatch &b, const int bx, const int
     // (forward stop / reverse start) -> right open node (forward start / reverse stop), 0 < r-l < 500, score_gap(r-l-3, 'same')
     // on both strand combinations; no overlap edges.  The few tRNA nodes of a contig are scanned as a list.
     auto t_close = [&](int k) { const int i = tn[k].info; return (NTYPE(i) == 1 && NFRAME(i) > 0) || (NTYPE(i) == 0 && NFRAME(i) < 0); };
-    const int32_t *olist = b.olist + meta->node_off; // open nodes, target, close nodes (k_node_order); the source has no in-edge
+    const int32_t *olist = b.olist + U(meta->node_off); // open nodes, target, close nodes (k_node_order); the source has no in-edge
     if (!FILL && by == 0 && threadIdx.x == 0) in_off[SRC] = 0u;
     // (DBatch.orf_rows: the close CDS nodes — the tail of the list — get their rows from k_edges_orf, a thread per ORF)
-    const int n_list = (FILL && !TAPW && b.orf_rows) ? meta->n_open : V - 1;
-    for (int base = (int)by * NT; base < n_list; base += (int)gy * NT) {
+    const int n_list = (FILL && !TAPW && b.orf_rows) ? U(meta->n_open) : V - 1;
+    for (int base = (int)by * T; base < n_list; base += (int)gy * T) {
         const int li = base + (int)threadIdx.x;
         const int v = li < n_list ? olist[li] : V;
         EdgeSink sink;
@@ -515,8 +561,8 @@ __device__ __forceinline__ void b_edges(const DBatch &b, const int bx, const int
         sink.q = s_q; sink.qn = &s_qn; sink.row = 0; sink.cc = cc;
         if (FILL && v < V) {
             sink.row = in_off[v];
-            sink.esrc = (TAPW ? b.esrcf : b.esrc) + meta->edge_off + sink.row;
-            sink.ew = (TAPW ? (unsigned long long *)b.ewf : (unsigned long long *)b.ew) + meta->edge_off + sink.row;
+            sink.esrc = (TAPW ? b.esrcf : b.esrc) + U(meta->edge_off) + sink.row;
+            sink.ew = (TAPW ? (unsigned long long *)b.ewf : (unsigned long long *)b.ew) + U(meta->edge_off) + sink.row;
         }
         if (v < V && v != SRC) {
             if (v == TGT) {
@@ -536,8 +582,8 @@ __device__ __forceinline__ void b_edges(const DBatch &b, const int bx, const int
                 const bool open = (t == 0 && f > 0) || (t == 1 && f < 0);
                 if (LINK_KIND(nd[v].link) == LINK_TRNA) {
                     if (!open) { // the tRNA edge(s) that end here: weight -20 (functions.py:509)
-                        const DTEdge *te = b.tedge + meta->te_off;
-                        for (int k = 0; k < meta->n_tedge; k++)
+                        const DTEdge *te = b.tedge + U(meta->te_off);
+                        for (int k = 0; k < U(meta->n_tedge); k++)
                             if (tnid[te[k].dst] == v) emit_edge<FILL>(sink, tnid[te[k].src], trna_w);
                     } else {
                         if (pos <= 2000) { EWt w0 = gap(pos, false); w0.fl |= ESRC_F_OFFPATH; w0.code = -1; emit_edge<FILL>(sink, SRC, w0); } // functions.py:445-448 (explicit: the flag says it leaves the source node)
@@ -583,7 +629,7 @@ __device__ __forceinline__ void b_edges(const DBatch &b, const int bx, const int
                         if (t_close(k) && pos - tn[k].pos > 0 && pos - tn[k].pos < 500) emit_edge<FILL>(sink, FILL ? tnid[k] : 0, gap(pos - tn[k].pos - 3, false));
                     // ---- v as right node: gap edges from every close node l with 0 < r-l < 500 ----
                     int4 rk = make_int4(0, 0, 0, 0);
-                    if (EDGE_RANKS && FILL && !TAPW) rk = b.erank[meta->node_off + v];
+                    if (EDGE_RANKS && FILL && !TAPW) rk = b.erank[U(meta->node_off) + v];
                     if (!(EDGE_ABL & 1)) {
                         const int a = (EDGE_RANKS && FILL && !TAPW) ? rk.x : rank_lt(pos - 499), e = (EDGE_RANKS && FILL && !TAPW) ? rk.y : rank_lt(pos) - 1; // ids [a, e]
                         if (EDGE_RANKS && !FILL) { rk.x = a; rk.y = e; }
@@ -666,7 +712,7 @@ __device__ __forceinline__ void b_edges(const DBatch &b, const int bx, const int
                         const bool have = EDGE_RANKS && FILL && !TAPW;
                         const int a = have ? rk.z : rank_lt(pos + 1), e500 = FILL ? 0 : rank_lt(pos + 500) - 1;
                         const int e = have ? rk.w : (my_other < pos + 500 ? (my_other > pos + 1 ? rank_lt(my_other) - 1 : a - 1) : (FILL ? rank_lt(pos + 500) - 1 : e500)); // ids [a, e]
-                        if (EDGE_RANKS && !FILL) { rk.z = a; rk.w = e; b.erank[meta->node_off + v] = rk; }
+                        if (EDGE_RANKS && !FILL) { rk.z = a; rk.w = e; b.erank[U(meta->node_off) + v] = rk; }
                         uint64_t hm = FILL ? ehit[v] : 0ull;
                         int n_close_ahead = 0;
                         if (!FILL)
@@ -775,7 +821,7 @@ __device__ __forceinline__ void b_edges(const DBatch &b, const int bx, const int
         }
         if (!FILL && v < V) in_off[v] = (uint32_t)sink.n; // in-degree; k_edges_scan turns it into an offset
 
-        if (FILL && b.defer_overlap) finish_overlaps<TAPW>(s_q, &s_qn, (TAPW ? b.esrcf : b.esrc) + meta->edge_off, (TAPW ? (unsigned long long *)b.ewf : (unsigned long long *)b.ew) + meta->edge_off, cc);
+        if (FILL && b.defer_overlap) finish_overlaps<TAPW>(s_q, &s_qn, (TAPW ? b.esrcf : b.esrc) + U(meta->edge_off), (TAPW ? (unsigned long long *)b.ewf : (unsigned long long *)b.ew) + U(meta->edge_off), cc);
     }
     if (parallel) atomicMin(&meta->status, PHX_S_PARALLEL);
     if (!FILL && dense) atomicOr(&meta->dense, 1);
@@ -882,12 +928,14 @@ __global__ __launch_bounds__(NT) void k_edges_expand(DBatch b, int nl, int mode)
 #ifndef ES_T
 #define ES_T 512 // threads of a k_edges_scan workgroup (one per contig; 256: edge count + scan + layout 0.141 ms, 512: 0.134, 1024: 0.137)
 #endif
-template <int EST>
+// INWG: behind the counting pass in one launch (k_graph_chain): the status, which that pass lowers by atomicMin, is read at L2
+template <int EST, bool INWG = false>
 __device__ __forceinline__ void b_edges_scan(const DBatch &b, const int bx) {
     if (b.tot->overflow) return; // a buffer of this run is too small: the host grows it and runs again
     __shared__ uint32_t s_scan[EST / 64 + 1];
     DMeta *meta = &b.meta[bx];
-    if (meta->status < 0 || meta->n_node <= 0) {
+    const int status = INWG ? __hip_atomic_load(&meta->status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : meta->status;
+    if (status < 0 || meta->n_node <= 0) {
         if (threadIdx.x == 0) meta->n_edge = 0;
         return;
     }
@@ -943,3 +991,37 @@ __global__ __launch_bounds__(ES_T) void k_edges_scan(DBatch b) { b_edges_scan<ES
 __global__ __launch_bounds__(1024) void k_edges_scan_big(DBatch b) { b_edges_scan<1024>(b, (int)blockIdx.x); }
 
 
+
+// Nodes -> attributes -> edge count -> scan of one contig by ONE workgroup: the whole stretch between the ORF scan and k_layout2 needs the ORF and
+// group records only (since the o-term left b_node_attr) and a contig's stages depend on that contig's earlier stages alone, so the four launches
+// k_nodes_fused, k_node_attr, k_edges<false>, k_edges_scan are one, every contig proceeds on its own, and nothing waits for the slowest contig of
+// a stage three times over.  Between the bodies the workgroup-scope fence and barrier of k_nodes_fused (see there: never agent scope); a field a
+// stage in front changed by L2 atomics (n_bridge, status) is read at L2 (INWG).  No atomics on batch totals, no workgroup waits for another.
+#ifndef CHAIN_T
+#define CHAIN_T 512 // threads of its workgroup (1000 x 50 kb, step: 256: 1.572 ms, 512: 1.504, 1024: 1.571; the four staged launches on the same streams: 1.539)
+#endif
+#ifndef CHAIN_WPS
+#define CHAIN_WPS 8 // wavefronts per SIMD the register allocation must allow (64 VGPRs)
+#endif
+template <int T>
+__global__ __launch_bounds__(T, CHAIN_WPS) void k_graph_chain(DBatch b) {
+    const int bx = blockIdx.x;
+    auto stage_sync = [&]() {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __syncthreads();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    };
+    b_node_cov<T>(b, bx, 0, 1);
+    stage_sync();
+    b_node_rank<T>(b, bx);
+    stage_sync();
+    b_node_build<T>(b, bx, 0, 1);
+    stage_sync();
+    b_node_order<T>(b, bx);
+    stage_sync();
+    b_node_attr<T>(b, bx, 0, 1);
+    stage_sync();
+    b_edges<false, false, false, T, true>(b, bx, 0, 1);
+    stage_sync();
+    b_edges_scan<T, true>(b, bx);
+}

@@ -58,6 +58,7 @@ static inline __host__ __device__ uint32_t esrc_node(uint32_t x) { return x & ((
 #define LINK_TRNA (3u << 30)  // payload = index of the tRNA node (contig-relative, DBatch.tnode)
 #define LINK_IDX(x) ((x)&0x3fffffffu)
 #define LINK_KIND(x) ((x)&0xc0000000u)
+#define OLINK_NONE (-2)       // DBatch.olink of a tRNA node: it has no o1/o2 term
 
 // ninfo: bits0-1 type (0 start,1 stop,2 source,3 target), bits 8-15 frame as int8
 #define NINFO(type, frame) ((int32_t)(((uint32_t)(type)&3u) | (((uint32_t)(uint8_t)(int8_t)(frame)) << 8)))
@@ -264,7 +265,7 @@ struct DBatch {
     DBridge *bridge;    // per contig bridge_cap entries: the uncovered runs of functions.py:334 (k_node_rank -> k_edges)
     // per ORF / group
     DOrf *orf;
-    DOrfStat *ostat;    // k_orf_stats -> k_score, k_node_attr
+    DOrfStat *ostat;    // k_orf_stats -> k_score, k_node_oterm
     double *oweight;    // Orf.weight: k_score -> genes (and the tap variant of k_edges)
     long long *owi;     // the same as the solver's integer (ew_encode) and
     uint8_t *oflag;     //   its flags: bit 0 |W| >= 2^51, bit 1 inexact (k_score -> k_edges: bits 30 and 31 of esrc)
@@ -274,7 +275,9 @@ struct DBatch {
     DNode *node;        // position, type/frame, link to its ORF / group, other_end: one 16-byte record per node
     int32_t *parent;
     uint32_t *in_off;
-    double *no;
+    double *no;         // per CDS node the o1/o2 term (functions.py:373-384): p_stop of the ORF DBatch.olink names, or pgap (k_node_oterm -> k_edges<true>); source and target: pgap (k_node_rank)
+    int32_t *olink;     // per node: index of that ORF, -1: pgap, OLINK_NONE: a tRNA node, no term (k_node_attr -> k_node_oterm).  An array of its own, not the node's slot in `no`: 4 bytes
+                        //    written and read instead of 8, k_node_oterm needs no node record to tell a tRNA node, and `no` never holds anything but a double
     int32_t *npos;      // node positions alone (k_node_attr -> k_edges: its gap-edge loops need nothing else of a candidate, 4 instead of 16 bytes per look)
     DWin *win;          // k_wave_plan -> k_sssp_wave: window records,
     uint2 *wrole;       //   WIN_ROLES lane records per window
@@ -505,6 +508,9 @@ void phxk_orf_stats(const DBatch *b, void *stream);
 void phxk_score(const DBatch *b, void *stream);
 void phxk_nodes(const DBatch *b, void *stream);
 void phxk_node_attr(const DBatch *b, void *stream);
+void phxk_node_oterm(const DBatch *b, void *stream);
+int phxk_chain_ok(const DBatch *b);                           // the batch is one k_graph_chain takes (where k_nodes_fused is used)
+void phxk_graph_chain(const DBatch *b, void *stream);         // nodes, attributes, edge count and scan in one launch
 void phxk_edges_count(const DBatch *b, void *stream);
 void phxk_layout1(const DBatch *b, void *stream); // after orf_count: ORF / group / node offsets, totals
 void phxk_layout2(const DBatch *b, void *stream); // after edges_count: edge offsets, integer class and solver per contig, totals

@@ -284,22 +284,30 @@ void phxk_score(const DBatch *b, void *stream) {
 }
 // node stage, part 1: needs the ORF / group records of k_orf<true> only (not their statistics), so the launcher runs it
 // beside k_orf_stats / k_score
-void phxk_nodes(const DBatch *b, void *stream) {
+// one workgroup per contig runs the node bodies in a row — unless the batch is a few LONG contigs (T4: one 256-thread workgroup then takes
+// 111 us and k_node_attr waits for it; the staged kernels spread coverage and records over four workgroups per contig: 60 us)
+static bool nodes_per_contig(const DBatch *b) {
 #ifndef NODES_STAGED
-    // one workgroup per contig runs the four bodies in a row — unless the batch is a few LONG contigs (T4: one 256-thread workgroup then takes
-    // 111 us and k_node_attr waits for it; the staged kernels spread coverage and records over four workgroups per contig: 60 us)
-    if (!(b->n_contig <= 16 && b->mean_len >= 32768)) {
+    return !(b->n_contig <= 16 && b->mean_len >= 32768);
+#else
+    return false;
+#endif
+}
+int phxk_chain_ok(const DBatch *b) { return nodes_per_contig(b) ? 1 : 0; }
+void phxk_graph_chain(const DBatch *b, void *stream) { hipLaunchKernelGGL(k_graph_chain<CHAIN_T>, dim3(b->n_contig), dim3(CHAIN_T), 0, (hipStream_t)stream, *b); }
+void phxk_nodes(const DBatch *b, void *stream) {
+    if (nodes_per_contig(b)) {
         hipLaunchKernelGGL(k_nodes_fused, dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b);
         return;
     }
-#endif
     hipLaunchKernelGGL(k_node_cov, dim3(b->n_contig, ysplit(b, 4)), dim3(NT), 0, (hipStream_t)stream, *b);
     hipLaunchKernelGGL(k_node_rank, dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b);
     hipLaunchKernelGGL(k_node_build, dim3(b->n_contig, ysplit(b, 4)), dim3(NT), 0, (hipStream_t)stream, *b);
     hipLaunchKernelGGL(k_node_order, dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b);
 }
-// part 2: other_end and the p_stop attribute of every node (reads DOrf.pstop of k_orf_stats)
+// part 2: other_end of every node and which ORF's p_stop is its o1/o2 term; part 3, behind k_orf_stats: the term itself
 void phxk_node_attr(const DBatch *b, void *stream) { hipLaunchKernelGGL(k_node_attr, dim3(b->n_contig, ysplit(b, 4)), dim3(NT), 0, (hipStream_t)stream, *b); }
+void phxk_node_oterm(const DBatch *b, void *stream) { hipLaunchKernelGGL(k_node_oterm, dim3(b->n_contig, ysplit(b, 4)), dim3(NT), 0, (hipStream_t)stream, *b); }
 void phxk_edges_count(const DBatch *b, void *stream) {
     hipLaunchKernelGGL(k_edges<false>, dim3(b->n_contig, ysplit(b, 4)), dim3(NT), 0, (hipStream_t)stream, *b);
     if (b->n_contig <= 16 && b->mean_len >= 32768) hipLaunchKernelGGL(k_edges_scan_big, dim3(b->n_contig), dim3(1024), 0, (hipStream_t)stream, *b);
