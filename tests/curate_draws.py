@@ -25,15 +25,16 @@ def mix_seqs(pa):
 
 class OracleGraph:
     """One contig's graph from the CPU oracle: edges [(u, v, W)] in the oracle's edge order, W the exact integer trunc(w * 1000); the ORF
-    edges by (left, right, strand); the keys of the genes the oracle's own path calls.  None-like (ok False) where the oracle has no path."""
+    edges by (left, right, strand); the keys of the genes the oracle's own path calls.  None-like (ok False) where the oracle has no path.
+    `params` (oracle.make_params) and `trnas` (the hit list) go to oracle.run as they are; a tRNA node (frame +-4) is never an ORF's."""
 
-    def __init__(self, orc, seq):
-        r = orc.run(seq)
+    def __init__(self, orc, seq, params=None, trnas=None):
+        r = orc.run(seq, params, trnas=trnas)
         self.ok = r["status"] == 0 and "path" in r and len(r["path"]) >= 2 and not r["wide"]
         if not self.ok:
             return
         typ, frame, pos = r["node_type"].tolist(), r["node_frame"].tolist(), r["node_pos"].tolist()
-        self.V = len(typ)
+        self.V, self.type, self.frame = len(typ), typ, frame
         self.src, self.tgt = typ.index(2), typ.index(3)
         w = [orc.limbs_to_int(x) for x in r["edge_wint_limbs"]]
         self.edges = list(zip(r["edge_src"].tolist(), r["edge_dst"].tolist(), w))
