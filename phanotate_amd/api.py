@@ -33,6 +33,49 @@ def synth_contig(seed, L=50000):
     return buf.raw
 
 
+def _limbs_to_int(limbs, nl):
+    """The signed python int of nl 64-bit limbs, least significant first (two's complement across the limbs)."""
+    v = 0
+    for k in range(nl):
+        v |= int(limbs[k]) << (64 * k)
+    return v - (1 << (64 * nl)) if v >> (64 * nl - 1) else v
+
+
+def _dist_list(rows, nl):
+    """Per-node distances of a limb array (one row of w words per node) of a contig of nl limbs as python ints; None: unreached (a value
+    at or above 2^(64 w - 3)).  w == nl + 1 is a vector of a contig solved with required ORFs: x = S - count * 2^(64 nl), |S| < 2^(64 nl) / 2,
+    comes out as (S, count)."""
+    out = []
+    for row in rows:
+        w = len(row)
+        x = _limbs_to_int(row, w)
+        if x >= 1 << (64 * w - 3):
+            out.append(None)
+        elif w <= nl:
+            out.append(x)
+        else:
+            M = 1 << (64 * nl)
+            count = (-x + M // 2) // M
+            out.append((x + count * M, count))
+    return out
+
+
+def _vp(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+# the *_ms getters: library call -> the names of its spans
+_MS_KEYS = {
+    "phx_margins_ms": ("transpose", "reverse", "margins", "download"),
+    "phx_drop_ms": ("trees", "candidates", "fixups", "download"),
+    "phx_replacements_ms": ("argmin", "walk", "download"),
+    "phx_scenarios_ms": ("mask", "solve", "finish"),
+    "phx_remargins_ms": ("apply", "reverse", "margins", "download"),
+    "phx_pinmargins_ms": ("apply", "reverse", "margins", "download"),
+    "phx_reannotate_ms": ("mask", "solve", "finish"),
+}
+
+
 class Pool:
     """phx_pool: ONE call annotates a list of contigs over several GPUs from this process — a host thread and two contexts per device
     inside the library, batches round the devices, results in input order.  devices: GPU ordinals (one may repeat)."""
@@ -134,6 +177,74 @@ class Annotator:
         if rc:
             raise PhxError(rc, "%s: %s (%s)" % (what, self.L.phx_strerror(rc).decode(), self.L.phx_last_error(self.h).decode()))
 
+    def _ms(self, name):
+        keys = _MS_KEYS[name]
+        ms = (C.c_float * len(keys))()
+        self._chk(getattr(self.L, name)(self.h, ms), name)
+        return dict(zip(keys, [float(x) for x in ms]))
+
+    def _query_fill(self, fn, name, head, count, dts, layout="rc", per=(np.int32,)):
+        """The size query and the fill of one *_flat entry point: fn(handle, *head, <records>, offsets, *per-entry arrays, *totals).
+        `layout` spells the records' arguments — r: the next array of `dts`, c: the capacity of the arrays since the last c, which the
+        next total sizes (null and 0 in the size query).  `per`: dtypes of the arrays with one value per entry (status first), `count`
+        entries.  Returns (per-entry arrays cut to count, offsets, record arrays cut to their totals)."""
+        offs = np.zeros(count + 1, np.int64)
+        ent = [np.zeros(max(count, 1), dt) for dt in per]
+        totals = [C.c_int64(0) for _ in range(layout.count("c"))]
+        sized_by = [layout[:k].count("c") for k, ch in enumerate(layout) if ch == "r"]
+        recs = [None] * len(dts)
+        for fill in (False, True):
+            if fill:
+                recs = [np.empty(max(int(totals[t].value), 1), dt) for t, dt in zip(sized_by, dts)]
+            it = iter(recs)
+            block = []
+            for ch in layout:
+                if ch == "r":
+                    a = next(it)
+                    block.append(_vp(a) if fill else None)
+                else:
+                    block.append(len(a) if fill else 0)
+            self._chk(fn(self.h, *head, *block, _vp(offs), *[_vp(a) for a in ent], *[C.byref(t) for t in totals]), name)
+        return [a[:count] for a in ent], offs, [a[: int(totals[t].value)] for t, a in zip(sized_by, recs)]
+
+    def _tap_path(self, fn, name, g, *ids):
+        """(path as device node ids, its length as a python int) from one of the path taps of a contig with globals g."""
+        p = np.zeros(max(g.n_node, 1), np.int32)
+        n = C.c_int32()
+        limbs = np.zeros(32, np.uint64)
+        self._chk(fn(self.h, *ids, _vp(p), len(p), C.byref(n), _vp(limbs), 32), name)
+        return p[: n.value].copy(), _limbs_to_int(limbs, max(g.n_limbs, 1))
+
+    def _tap_dist(self, fn, name, i, *which, pinned=False):
+        """_dist_list of one of the distance taps of contig i; pinned: the tap may deliver one word more per node and says how many."""
+        g = self.globals(i)
+        nl, V = max(g.n_limbs, 1), max(g.n_node, 0)
+        a = np.zeros((max(V, 1), nl + (1 if pinned else 0)), np.uint64)
+        wpn = C.c_int32(0)
+        self._chk(fn(self.h, i, *which, _vp(a), a.size, *((C.byref(wpn),) if pinned else ())), name)
+        w = min(int(wpn.value) or nl, nl + 1) if pinned else nl
+        return _dist_list(a.reshape(-1)[: V * w].reshape(V, w), nl)
+
+    def _device_lists(self):
+        """download_flat(exact=False)'s arrays: the device's own lists for every contig."""
+        self._chk(self.L.phx_set_exact(self.h, 0), "phx_set_exact")
+        try:
+            return self._download_flat()
+        finally:
+            self._chk(self.L.phx_set_exact(self.h, 1), "phx_set_exact")
+
+    def _gene_changes(self, contigs, roffs, rgenes, soffs, genes):
+        """For every scenario x of contig contigs[x] whose new annotation is genes[soffs[x]:soffs[x+1]], against the run's device lists
+        (roffs, rgenes of _device_lists): (keys of the run's genes, keys of the new ones, orfs(contig), n_removed, n_added), a key being
+        (left, right, strand, frame)."""
+        key = lambda g: (int(g["left"]), int(g["right"]), int(g["strand"]), int(g["frame"]))
+        have, have_of, orfs_of = None, -1, None
+        for x, i in enumerate(contigs):
+            if have_of != i:
+                have, have_of, orfs_of = {key(g) for g in rgenes[roffs[i]:roffs[i + 1]]}, i, self.orfs(i)
+            new = {key(g) for g in genes[soffs[x]:soffs[x + 1]]}
+            yield have, new, orfs_of, len(have - new), len(new - have)
+
     # ---- the path ----
     def upload(self, seqs):
         seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
@@ -202,11 +313,7 @@ class Annotator:
         integers inside phx_download_flat (csrc/phx_exact.inc); its indices are then in self.resolved.  exact=False: the device's
         own lists for every contig (phx_set_exact; tests and measurements)."""
         if not exact:
-            self._chk(self.L.phx_set_exact(self.h, 0), "phx_set_exact")
-            try:
-                res = self._download_flat()
-            finally:
-                self._chk(self.L.phx_set_exact(self.h, 1), "phx_set_exact")
+            res = self._device_lists()
             self.resolved = []
             return res
         res = self._download_flat()
@@ -305,93 +412,40 @@ class Annotator:
         return a
 
     def path(self, i):
-        g = self.globals(i)
-        p = np.zeros(max(g.n_node, 1), np.int32)
-        n = C.c_int32()
-        limbs = np.zeros(32, np.uint64)
-        self._chk(self.L.phx_tap_path(self.h, i, p.ctypes.data_as(C.c_void_p), len(p), C.byref(n), limbs.ctypes.data_as(C.c_void_p), 32), "phx_tap_path")
-        nl = max(g.n_limbs, 1)
-        v = 0
-        for k in range(nl):
-            v |= int(limbs[k]) << (64 * k)
-        if v >> (64 * nl - 1):
-            v -= 1 << (64 * nl)
-        return p[: n.value].copy(), v
+        return self._tap_path(self.L.phx_tap_path, "phx_tap_path", self.globals(i), i)
 
     def dist(self, i):
         """Exact distance of every node from the source as python ints (None: unreached), device node order."""
-        g = self.globals(i)
-        nl, V = max(g.n_limbs, 1), max(g.n_node, 0)
-        a = np.zeros((max(V, 1), nl), np.uint64)
-        self._chk(self.L.phx_tap_dist(self.h, i, a.ctypes.data_as(C.c_void_p), a.size), "phx_tap_dist")
-        out = []
-        for v in range(V):
-            x = 0
-            for k in range(nl):
-                x |= int(a[v, k]) << (64 * k)
-            if x >> (64 * nl - 1):
-                x -= 1 << (64 * nl)
-            out.append(None if x >= 1 << (64 * nl - 3) else x)
-        return out
+        return self._tap_dist(self.L.phx_tap_dist, "phx_tap_dist", i)
 
     def dist_to_target(self, i):
         """Exact distance of every node TO the target as python ints (None: no path to the target), device node order
         (phx_tap_dist_target; the margins' reverse pass, computed on the first call after a run)."""
-        g = self.globals(i)
-        nl, V = max(g.n_limbs, 1), max(g.n_node, 0)
-        a = np.zeros((max(V, 1), nl), np.uint64)
-        self._chk(self.L.phx_tap_dist_target(self.h, i, a.ctypes.data_as(C.c_void_p), a.size), "phx_tap_dist_target")
-        out = []
-        for v in range(V):
-            x = 0
-            for k in range(nl):
-                x |= int(a[v, k]) << (64 * k)
-            if x >> (64 * nl - 1):
-                x -= 1 << (64 * nl)
-            out.append(None if x >= 1 << (64 * nl - 3) else x)
-        return out
+        return self._tap_dist(self.L.phx_tap_dist_target, "phx_tap_dist_target", i)
 
     def margins(self):
         """(status int32[n], offsets int64[n+1], records structured array[total] of _lib.MARGIN_DT): the path margin of every CDS ORF of
         the batch last run (phx_margins_flat).  The records of contig i are records[offsets[i]:offsets[i+1]], in the order of orfs(i);
         margin = float(d_s(u) + W + d_t(v) - D) / 1000 (0 for a called ORF of a certified contig, +inf where no path runs through the ORF);
         status as phx_margins_flat reports it (< 0: no records)."""
-        n = self.n
-        offs = np.zeros(n + 1, np.int64)
-        status = np.zeros(max(n, 1), np.int32)
-        total = C.c_int64(0)
-        vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        self._chk(self.L.phx_margins_flat(self.h, None, 0, vp(offs), vp(status), C.byref(total)), "phx_margins_flat")
-        rec = np.empty(max(int(total.value), 1), _lib.MARGIN_DT)
-        self._chk(self.L.phx_margins_flat(self.h, vp(rec), len(rec), vp(offs), vp(status), C.byref(total)), "phx_margins_flat")
-        return status[:n], offs, rec[: int(total.value)]
+        (status,), offs, (rec,) = self._query_fill(self.L.phx_margins_flat, "phx_margins_flat", (), self.n, (_lib.MARGIN_DT,))
+        return status, offs, rec
 
     def margins_ms(self):
         """Device time of the last margins computation in ms: out-edge CSR, reverse pass, records, copy to the host (phx_margins_ms)."""
-        ms = (C.c_float * 4)()
-        self._chk(self.L.phx_margins_ms(self.h, ms), "phx_margins_ms")
-        return dict(zip(("transpose", "reverse", "margins", "download"), [float(x) for x in ms]))
+        return self._ms("phx_margins_ms")
 
     def drop_margins(self):
         """(status int32[n], offsets int64[n+1], records structured array[total] of _lib.DROP_DT): the drop margin of every CDS gene of
         the device path of every contig of the batch last run (phx_drop_margins_flat), in path order.  drop = float(D_{-g} - D) / 1000,
         D_{-g} the shortest source -> target distance without the gene's stop node (+inf with bypass = 0 where no path avoids it);
         called = 1 for the genes download_flat() delivers; status as phx_drop_margins_flat reports it (!= 0: no records)."""
-        n = self.n
-        offs = np.zeros(n + 1, np.int64)
-        status = np.zeros(max(n, 1), np.int32)
-        total = C.c_int64(0)
-        vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        self._chk(self.L.phx_drop_margins_flat(self.h, None, 0, vp(offs), vp(status), C.byref(total)), "phx_drop_margins_flat")
-        rec = np.empty(max(int(total.value), 1), _lib.DROP_DT)
-        self._chk(self.L.phx_drop_margins_flat(self.h, vp(rec), len(rec), vp(offs), vp(status), C.byref(total)), "phx_drop_margins_flat")
-        return status[:n], offs, rec[: int(total.value)]
+        (status,), offs, (rec,) = self._query_fill(self.L.phx_drop_margins_flat, "phx_drop_margins_flat", (), self.n, (_lib.DROP_DT,))
+        return status, offs, rec
 
     def drop_ms(self):
         """Device time of the last drop-margins computation in ms: trees + labels, candidates, fixups, copy to the host (phx_drop_ms)."""
-        ms = (C.c_float * 4)()
-        self._chk(self.L.phx_drop_ms(self.h, ms), "phx_drop_ms")
-        return dict(zip(("trees", "candidates", "fixups", "download"), [float(x) for x in ms]))
+        return self._ms("phx_drop_ms")
 
     def replacements(self):
         """(status int32[n], offsets int64[n+1], records structured array[total] of _lib.REPL_DT, genes structured array of _lib.GENE_DT):
@@ -399,17 +453,8 @@ class Annotator:
         without the gene calls instead (phx_replacements_flat).  Record r's genes are genes[r.gene_off:][:r.n_removed]
         (the device path's genes the replacement drops, the gene itself among them), then the next r.n_added (the genes it calls
         instead), in path order."""
-        n = self.n
-        offs = np.zeros(n + 1, np.int64)
-        status = np.zeros(max(n, 1), np.int32)
-        total, gtotal = C.c_int64(), C.c_int64()
-        vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        self._chk(self.L.phx_replacements_flat(self.h, None, 0, None, 0, vp(offs), vp(status), C.byref(total), C.byref(gtotal)), "phx_replacements_flat")
-        rec = np.empty(max(int(total.value), 1), _lib.REPL_DT)
-        genes = np.empty(max(int(gtotal.value), 1), _lib.GENE_DT)
-        self._chk(self.L.phx_replacements_flat(self.h, vp(rec), len(rec), vp(genes), len(genes), vp(offs), vp(status), C.byref(total), C.byref(gtotal)),
-                  "phx_replacements_flat")
-        return status[:n], offs, rec[: int(total.value)], genes[: int(gtotal.value)]
+        (status,), offs, (rec, genes) = self._query_fill(self.L.phx_replacements_flat, "phx_replacements_flat", (), self.n, (_lib.REPL_DT, _lib.GENE_DT), "rcrc")
+        return status, offs, rec, genes
 
     def replacement_path(self, i, k):
         """R_g of record k of contig i (replacements()[2][offsets[i] + k]): device node ids, source first; empty when bypass = 0."""
@@ -421,9 +466,7 @@ class Annotator:
 
     def replacements_ms(self):
         """Device time of the last replacements computation in ms: argmin, walk + genes, copy to the host (phx_replacements_ms)."""
-        ms = (C.c_float * 3)()
-        self._chk(self.L.phx_replacements_ms(self.h, ms), "phx_replacements_ms")
-        return dict(zip(("argmin", "walk", "download"), [float(x) for x in ms]))
+        return self._ms("phx_replacements_ms")
 
     def replacement_stats(self):
         """Counters of the last replacements computation (phx_replacement_stats): slots won by a cross candidate, their delta-chain nodes,
@@ -487,21 +530,13 @@ class Annotator:
     def _resolve(self, fn, name, arrays, solve_all, with_unmet):
         """The size query and the fill of one re-annotation entry point: fn(handle, *arrays, orf offsets, flags, genes, capacity, offsets,
         status, delta[, unmet], total).  Returns (status, offsets, genes, delta[, unmet]) cut to the batch."""
-        n = self.n
-        vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        offs = np.zeros(n + 1, np.int64)
-        status = np.zeros(max(n, 1), np.int32)
-        delta = np.zeros(max(n, 1), np.float64)
-        unmet = np.zeros(max(n, 1), np.int32)
-        total = C.c_int64(0)
-        oo = self.orf_offsets()
-        head = (self.h,) + tuple(vp(a) for a in arrays) + (vp(oo), 1 if solve_all else 0)
-        tail = (vp(offs), vp(status), vp(delta)) + ((vp(unmet),) if with_unmet else ()) + (C.byref(total),)
-        self._chk(fn(*head, None, 0, *tail), name)
-        genes = np.empty(max(int(total.value), 1), _lib.GENE_DT)
-        self._chk(fn(*head, vp(genes), len(genes), *tail), name)
-        out = (status[:n], offs, genes[: int(total.value)], delta[:n])
-        return out + (unmet[:n],) if with_unmet else out
+        head = tuple(_vp(a) for a in arrays) + (_vp(self.orf_offsets()), 1 if solve_all else 0)
+        return self._genes_flat(fn, name, head, self.n, with_unmet)
+
+    def _genes_flat(self, fn, name, head, count, with_unmet):
+        """_query_fill for the entry points that deliver gene lists: (status, offsets, genes, delta[, unmet]) of `count` entries."""
+        ent, offs, (genes,) = self._query_fill(fn, name, head, count, (_lib.GENE_DT,), "rc", (np.int32, np.float64) + ((np.int32,) if with_unmet else ()))
+        return (ent[0], offs, genes) + tuple(ent[1:])
 
     def constrain(self, forbid=None, require=None, solve_all=False):
         """(status int32[n], offsets int64[n+1], genes structured array[total], delta float64[n], unmet int32[n]): the batch last run
@@ -517,22 +552,13 @@ class Annotator:
 
     def _bias_array(self, bias, oo):
         """One int64 per ORF of the batch from evidence()'s `bias`: B = math.trunc(b * 1000.0) per listed ORF, summed over repeats."""
-        import math
-
         n = self.n
         if len(bias) != n:
             raise ValueError("one dict or sequence of (ORF index, bias) pairs (or None) per contig of the batch")
         B = np.zeros(max(int(oo[n]), 1), np.int64)
         for i, pairs in enumerate(bias):
-            if pairs is None:
-                continue
-            for k, b in (pairs.items() if hasattr(pairs, "items") else pairs):
-                k, b = int(k), float(b)
-                if not 0 <= k < oo[i + 1] - oo[i]:
-                    raise IndexError("contig %d has %d ORFs" % (i, oo[i + 1] - oo[i]))
-                if not math.isfinite(b) or abs(b) * 1000.0 >= 2.0 ** 60:
-                    raise ValueError("contig %d, ORF %d: the bias %r is not a finite number of SCORE units within 2^52 / 1000" % (i, k, b))
-                B[oo[i] + k] += math.trunc(b * 1000.0)
+            for k, units in self._bias_pairs(i, pairs, oo[i + 1] - oo[i]):
+                B[oo[i] + k] += units
         if np.abs(B).max() > 1 << 52:
             raise ValueError("a bias beyond 2^52 / 1000 SCORE units")
         return B
@@ -599,22 +625,12 @@ class Annotator:
         oo = self.orf_offsets()
         contig, off, orf = self._scenario_arrays(scen, n, oo)
         S = len(scen)
-        offs = np.zeros(S + 1, np.int64)
-        status = np.zeros(max(S, 1), np.int32)
-        delta = np.zeros(max(S, 1), np.float64)
-        total = C.c_int64(0)
-        vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        self._chk(self.L.phx_scenarios_flat(self.h, S, vp(contig), vp(off), vp(orf), vp(oo), 0, None, 0, vp(offs), vp(status), vp(delta), C.byref(total)), "phx_scenarios_flat")
-        genes = np.empty(max(int(total.value), 1), _lib.GENE_DT)
-        self._chk(self.L.phx_scenarios_flat(self.h, S, vp(contig), vp(off), vp(orf), vp(oo), 0, vp(genes), len(genes), vp(offs), vp(status), vp(delta), C.byref(total)), "phx_scenarios_flat")
-        return status[:S], offs, genes[: int(total.value)], delta[:S]
+        return self._genes_flat(self.L.phx_scenarios_flat, "phx_scenarios_flat", (S, _vp(contig), _vp(off), _vp(orf), _vp(oo), 0), S, False)
 
     def scenarios_ms(self):
         """Device time of the last scenario solve (scenarios(), pinned_scenarios() or evidence_scenarios()) in ms, summed over its chunks: slot records + bitmaps, masked solve, path + genes + copy
         (phx_scenarios_ms)."""
-        ms = (C.c_float * 3)()
-        self._chk(self.L.phx_scenarios_ms(self.h, ms), "phx_scenarios_ms")
-        return dict(zip(("mask", "solve", "finish"), [float(x) for x in ms]))
+        return self._ms("phx_scenarios_ms")
 
     def scenario_chunks(self):
         """Chunks the last scenario solve was split into under the device-memory budget (phx_scenario_chunks)."""
@@ -624,18 +640,7 @@ class Annotator:
         """(path as device node ids, its length D_F as a python int) of scenario j of the last scenarios(), pinned_scenarios() or evidence_scenarios()
         call, like reannotated_path (a scenario with required ORFs: the W-sum W(P); one with biased ORFs: D_B); `contig` is the scenario's contig.  Served while the scenario's
         chunk is resident (phx_tap_scenario_path)."""
-        g = self.globals(contig)
-        p = np.zeros(max(g.n_node, 1), np.int32)
-        n = C.c_int32()
-        limbs = np.zeros(32, np.uint64)
-        self._chk(self.L.phx_tap_scenario_path(self.h, int(j), p.ctypes.data_as(C.c_void_p), len(p), C.byref(n), limbs.ctypes.data_as(C.c_void_p), 32), "phx_tap_scenario_path")
-        nl = max(g.n_limbs, 1)
-        v = 0
-        for k in range(nl):
-            v |= int(limbs[k]) << (64 * k)
-        if v >> (64 * nl - 1):
-            v -= 1 << (64 * nl)
-        return p[: n.value].copy(), v
+        return self._tap_path(self.L.phx_tap_scenario_path, "phx_tap_scenario_path", self.globals(contig), int(j))
 
     def start_drops(self):
         """(status int32[n], offsets int64[n+1], records structured array[total] of _lib.START_DT, scen_offsets int64[total+1], genes):
@@ -698,18 +703,8 @@ class Annotator:
         scen = list(scen)
         contig, foff, forf, roff, rorf = self._pinned_scenario_arrays(scen, n, oo)
         S = len(scen)
-        offs = np.zeros(S + 1, np.int64)
-        status = np.zeros(max(S, 1), np.int32)
-        delta = np.zeros(max(S, 1), np.float64)
-        unmet = np.zeros(max(S, 1), np.int32)
-        total = C.c_int64(0)
-        vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        call = lambda g, cap: self._chk(self.L.phx_pinned_scenarios_flat(self.h, S, vp(contig), vp(foff), vp(forf), vp(roff), vp(rorf), vp(oo), 0, g, cap, vp(offs), vp(status),
-                                                                            vp(delta), vp(unmet), C.byref(total)), "phx_pinned_scenarios_flat")
-        call(None, 0)
-        genes = np.empty(max(int(total.value), 1), _lib.GENE_DT)
-        call(vp(genes), len(genes))
-        return status[:S], offs, genes[: int(total.value)], delta[:S], unmet[:S]
+        head = (S, _vp(contig), _vp(foff), _vp(forf), _vp(roff), _vp(rorf), _vp(oo), 0)
+        return self._genes_flat(self.L.phx_pinned_scenarios_flat, "phx_pinned_scenarios_flat", head, S, True)
 
     def alt_starts(self, max_alts=None):
         """(status int32[n], offsets int64[n+1], records structured array[total] of _lib.ALT_DT, scen_offsets int64[total+1], genes):
@@ -735,25 +730,17 @@ class Annotator:
                     head.append((i, r, k, a))
             offs[i + 1] = len(scen)
         sstat, soffs, genes, delta, unmet = self.pinned_scenarios(scen)
-        self._chk(self.L.phx_set_exact(self.h, 0), "phx_set_exact")  # the device's own lists, as download_flat(exact=False)
-        try:
-            _, roffs, rgenes = self._download_flat()
-        finally:
-            self._chk(self.L.phx_set_exact(self.h, 1), "phx_set_exact")
-        key = lambda g: (int(g["left"]), int(g["right"]), int(g["strand"]), int(g["frame"]))
+        _, roffs, rgenes = self._device_lists()
         rec = np.zeros(len(scen), _lib.ALT_DT)
-        have, have_of, orfs_of = None, -1, None
-        for x, (i, r, k, a) in enumerate(head):
-            if have_of != i:
-                have, have_of, orfs_of = {key(g) for g in rgenes[roffs[i]:roffs[i + 1]]}, i, self.orfs(i)
+        changes = self._gene_changes([h[0] for h in head], roffs, rgenes, soffs, genes)
+        for x, ((i, r, k, a), (have, new, orfs_of, n_removed, n_added)) in enumerate(zip(head, changes)):
             o = rec[x]
             o["left"], o["right"], o["strand"], o["orf"], o["alt"] = r["left"], r["right"], r["strand"], k, a
             ao = orfs_of[a]
             fwd = ao["frame"] > 0
             o["alt_left"], o["alt_right"] = (ao["start"], ao["stop"] + 2) if fwd else (ao["stop"], ao["start"] + 2)
             o["status"], o["delta"], o["unmet"] = sstat[x], delta[x], unmet[x]
-            new = {key(g) for g in genes[soffs[x]:soffs[x + 1]]}
-            o["n_removed"], o["n_added"] = len(have - new), len(new - have)
+            o["n_removed"], o["n_added"] = n_removed, n_added
         return st, offs, rec, soffs, genes
 
     # ---- evidence scenario batches ----
@@ -766,6 +753,16 @@ class Annotator:
         if not math.isfinite(b) or abs(b) * 1000.0 >= 2.0 ** 60:
             raise ValueError("contig %d, ORF %d: the bias %r is not a finite number of SCORE units within 2^52 / 1000" % (i, k, b))
         return math.trunc(b * 1000.0)
+
+    @staticmethod
+    def _bias_pairs(i, pairs, n_orf):
+        """(ORF index, B) for every pair of contig i's `bias` as evidence() takes it — None, a dict or a sequence of (index, b) —, in the
+        order given: IndexError for an ORF the contig does not have, ValueError as _bias_units."""
+        for k, b in (() if pairs is None else pairs.items() if hasattr(pairs, "items") else pairs):
+            k = int(k)
+            if not 0 <= k < n_orf:
+                raise IndexError("contig %d has %d ORFs" % (i, n_orf))
+            yield k, Annotator._bias_units(i, k, b)
 
     def evidence_scenarios(self, scen):
         """(status int32[S], offsets int64[S+1], genes structured array[total], delta float64[S]): S evidence-weighted re-annotations of
@@ -789,11 +786,7 @@ class Annotator:
         for j, (i, pairs, _) in enumerate(triples):
             i = int(i)
             sums = {}
-            for k, b in (() if pairs is None else pairs.items() if hasattr(pairs, "items") else pairs):
-                k = int(k)
-                if not 0 <= k < oo[i + 1] - oo[i]:
-                    raise IndexError("contig %d has %d ORFs" % (i, oo[i + 1] - oo[i]))
-                B = self._bias_units(i, k, b)
+            for k, B in self._bias_pairs(i, pairs, oo[i + 1] - oo[i]):
                 sums[k] = sums.get(k, 0) + B
                 borf.append(k)  # (the pairs as given: the library merges them)
                 bval.append(B)
@@ -802,17 +795,8 @@ class Annotator:
             boff[j + 1] = len(borf)
         borf = np.ascontiguousarray(borf if borf else [0], np.int32)
         bval = np.ascontiguousarray(bval if bval else [0], np.int64)
-        offs = np.zeros(S + 1, np.int64)
-        status = np.zeros(max(S, 1), np.int32)
-        delta = np.zeros(max(S, 1), np.float64)
-        total = C.c_int64(0)
-        vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        call = lambda g, cap: self._chk(self.L.phx_evidence_scenarios_flat(self.h, S, vp(contig), vp(foff), vp(forf), vp(boff), vp(borf), vp(bval), vp(oo), 0, g, cap, vp(offs),
-                                                                              vp(status), vp(delta), C.byref(total)), "phx_evidence_scenarios_flat")
-        call(None, 0)
-        genes = np.empty(max(int(total.value), 1), _lib.GENE_DT)
-        call(vp(genes), len(genes))
-        return status[:S], offs, genes[: int(total.value)], delta[:S]
+        head = (S, _vp(contig), _vp(foff), _vp(forf), _vp(boff), _vp(borf), _vp(bval), _vp(oo), 0)
+        return self._genes_flat(self.L.phx_evidence_scenarios_flat, "phx_evidence_scenarios_flat", head, S, False)
 
     def evidence_scan(self, hits):
         """(status int32[n], offsets int64[n+1], records structured array[total] of _lib.EVSCAN_DT, scen_offsets int64[total+1], genes):
@@ -833,17 +817,10 @@ class Annotator:
                 head.append((i, int(k), float(b)))
             offs[i + 1] = len(scen)
         sstat, soffs, genes, delta = self.evidence_scenarios(scen)
-        self._chk(self.L.phx_set_exact(self.h, 0), "phx_set_exact")  # the device's own lists, as download_flat(exact=False)
-        try:
-            st, roffs, rgenes = self._download_flat()
-        finally:
-            self._chk(self.L.phx_set_exact(self.h, 1), "phx_set_exact")
-        key = lambda g: (int(g["left"]), int(g["right"]), int(g["strand"]), int(g["frame"]))
+        st, roffs, rgenes = self._device_lists()
         rec = np.zeros(len(scen), _lib.EVSCAN_DT)
-        have, have_of, orfs_of = None, -1, None
-        for x, (i, k, b) in enumerate(head):
-            if have_of != i:
-                have, have_of, orfs_of = {key(g) for g in rgenes[roffs[i]:roffs[i + 1]]}, i, self.orfs(i)
+        changes = self._gene_changes([h[0] for h in head], roffs, rgenes, soffs, genes)
+        for x, ((i, k, b), (have, new, orfs_of, n_removed, n_added)) in enumerate(zip(head, changes)):
             o = rec[x]
             ao = orfs_of[k]
             fwd = ao["frame"] > 0
@@ -851,27 +828,15 @@ class Annotator:
             o["strand"], o["orf"], o["bias"] = (1 if fwd else -1), k, b
             o["status"], o["delta"] = sstat[x], delta[x]
             me = (int(o["left"]), int(o["right"]), bool(fwd))
-            new = {key(g) for g in genes[soffs[x]:soffs[x + 1]]}
             o["was_called"] = int(any((g[0], g[1], g[2] > 0) == me and abs(g[3]) <= 3 for g in have))
             o["called"] = int(any((g[0], g[1], g[2] > 0) == me and abs(g[3]) <= 3 for g in new))
-            o["n_removed"], o["n_added"] = len(have - new), len(new - have)
+            o["n_removed"], o["n_added"] = n_removed, n_added
         return np.asarray(st[:n], np.int32), offs, rec, soffs, genes
 
     def reannotated_path(self, i):
         """(path as device node ids, its length as a python int) of contig i in the last re-annotation, constrain(), evidence() or curate(), like
         path(i): D_F, the W-sum W(P) after constrain(), D_B after evidence(), S(P) after curate()."""
-        g = self.globals(i)
-        p = np.zeros(max(g.n_node, 1), np.int32)
-        n = C.c_int32()
-        limbs = np.zeros(32, np.uint64)
-        self._chk(self.L.phx_tap_repath(self.h, i, p.ctypes.data_as(C.c_void_p), len(p), C.byref(n), limbs.ctypes.data_as(C.c_void_p), 32), "phx_tap_repath")
-        nl = max(g.n_limbs, 1)
-        v = 0
-        for k in range(nl):
-            v |= int(limbs[k]) << (64 * k)
-        if v >> (64 * nl - 1):
-            v -= 1 << (64 * nl)
-        return p[: n.value].copy(), v
+        return self._tap_path(self.L.phx_tap_repath, "phx_tap_repath", self.globals(i), i)
 
     def remargins(self):
         """(status int32[n], offsets int64[n+1], records structured array[total] of _lib.MARGIN_DT), as margins() returns them: the path
@@ -881,39 +846,18 @@ class Annotator:
         refused ORF and where no path runs through the ORF.  called = 1 for the genes the re-annotation returned.  A contig that was not
         solved again has the records of margins().  PhxError (PHX_E_STATE) without a re-annotation of this run and after constrain()
         with required ORFs."""
-        n = self.n
-        offs = np.zeros(n + 1, np.int64)
-        status = np.zeros(max(n, 1), np.int32)
-        total = C.c_int64(0)
-        vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        self._chk(self.L.phx_remargins_flat(self.h, None, 0, vp(offs), vp(status), C.byref(total)), "phx_remargins_flat")
-        rec = np.empty(max(int(total.value), 1), _lib.MARGIN_DT)
-        self._chk(self.L.phx_remargins_flat(self.h, vp(rec), len(rec), vp(offs), vp(status), C.byref(total)), "phx_remargins_flat")
-        return status[:n], offs, rec[: int(total.value)]
+        (status,), offs, (rec,) = self._query_fill(self.L.phx_remargins_flat, "phx_remargins_flat", (), self.n, (_lib.MARGIN_DT,))
+        return status, offs, rec
 
     def remargins_ms(self):
         """Device time of the last re-annotation margins in ms: apply, conditioned reverse pass, records, copy to the host (phx_remargins_ms)."""
-        ms = (C.c_float * 4)()
-        self._chk(self.L.phx_remargins_ms(self.h, ms), "phx_remargins_ms")
-        return dict(zip(("apply", "reverse", "margins", "download"), [float(x) for x in ms]))
+        return self._ms("phx_remargins_ms")
 
     def redist(self, i, to_target=False):
         """Exact distances of every node of contig i on the last re-annotation's graph as python ints (None: unreached), device node
         order: d_s' from the source, or with to_target d_t' to the target within the nodes the re-solve reached (phx_tap_redist).  A
         contig that was not solved again gives dist(i) / dist_to_target(i)."""
-        g = self.globals(i)
-        nl, V = max(g.n_limbs, 1), max(g.n_node, 0)
-        a = np.zeros((max(V, 1), nl), np.uint64)
-        self._chk(self.L.phx_tap_redist(self.h, i, 1 if to_target else 0, a.ctypes.data_as(C.c_void_p), a.size), "phx_tap_redist")
-        out = []
-        for v in range(V):
-            x = 0
-            for k in range(nl):
-                x |= int(a[v, k]) << (64 * k)
-            if x >> (64 * nl - 1):
-                x -= 1 << (64 * nl)
-            out.append(None if x >= 1 << (64 * nl - 3) else x)
-        return out
+        return self._tap_dist(self.L.phx_tap_redist, "phx_tap_redist", i, 1 if to_target else 0)
 
     def pinmargins(self):
         """(status int32[n], offsets int64[n+1], records structured array[total] of _lib.MARGIN_DT, lost int32[total]): remargins() for
@@ -923,56 +867,22 @@ class Annotator:
         margin) >= (0, 0.0), which a called gene has.  Requiring an uncalled ORF with lost 0 as well gets it called, keeps unmet and
         raises delta by its margin.  Elsewhere the records are remargins()' and lost is 0.  PhxError (PHX_E_STATE) only without a
         re-annotation of this run."""
-        n = self.n
-        offs = np.zeros(n + 1, np.int64)
-        status = np.zeros(max(n, 1), np.int32)
-        total = C.c_int64(0)
-        vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        self._chk(self.L.phx_pinmargins_flat(self.h, None, None, 0, vp(offs), vp(status), C.byref(total)), "phx_pinmargins_flat")
-        rec = np.empty(max(int(total.value), 1), _lib.MARGIN_DT)
-        lost = np.zeros(max(int(total.value), 1), np.int32)
-        self._chk(self.L.phx_pinmargins_flat(self.h, vp(rec), vp(lost), len(rec), vp(offs), vp(status), C.byref(total)), "phx_pinmargins_flat")
-        return status[:n], offs, rec[: int(total.value)], lost[: int(total.value)]
+        (status,), offs, (rec, lost) = self._query_fill(self.L.phx_pinmargins_flat, "phx_pinmargins_flat", (), self.n, (_lib.MARGIN_DT, np.int32), "rrc")
+        return status, offs, rec, lost
 
     def pinmargins_ms(self):
         """Device time of the last pinned margins in ms: apply, reverse pass, records, copy to the host (phx_pinmargins_ms)."""
-        ms = (C.c_float * 4)()
-        self._chk(self.L.phx_pinmargins_ms(self.h, ms), "phx_pinmargins_ms")
-        return dict(zip(("apply", "reverse", "margins", "download"), [float(x) for x in ms]))
+        return self._ms("phx_pinmargins_ms")
 
     def pindist(self, i, to_target=False):
         """redist(i, to_target) for every re-annotation (phx_tap_pindist).  A contig solved with required ORFs gives per node None
         (unreached) or (S, count): the sum of W + B and the number of required ORFs on the best path from the source (to the target
         within the nodes the re-solve reached), best meaning most required ORFs first.  Any other contig gives redist()'s plain ints."""
-        g = self.globals(i)
-        nl, V = max(g.n_limbs, 1), max(g.n_node, 0)
-        a = np.zeros((max(V, 1), nl + 1), np.uint64)
-        wpn = C.c_int32(0)
-        self._chk(self.L.phx_tap_pindist(self.h, i, 1 if to_target else 0, a.ctypes.data_as(C.c_void_p), a.size, C.byref(wpn)), "phx_tap_pindist")
-        w = min(int(wpn.value) or nl, nl + 1)
-        a = a.reshape(-1)[: V * w].reshape(V, w) if V else a[:0]
-        out = []
-        for v in range(V):
-            x = 0
-            for k in range(w):
-                x |= int(a[v, k]) << (64 * k)
-            if x >> (64 * w - 1):
-                x -= 1 << (64 * w)
-            if x >= 1 << (64 * w - 3):
-                out.append(None)
-            elif w <= nl:
-                out.append(x)
-            else:  # x = S - count * M, |S| < M / 2
-                M = 1 << (64 * nl)
-                count = (-x + M // 2) // M
-                out.append((x + count * M, count))
-        return out
+        return self._tap_dist(self.L.phx_tap_pindist, "phx_tap_pindist", i, 1 if to_target else 0, pinned=True)
 
     def reannotate_ms(self):
         """Device time of the last re-annotation in ms: mask build, masked solve, path + genes + copy (phx_reannotate_ms)."""
-        ms = (C.c_float * 3)()
-        self._chk(self.L.phx_reannotate_ms(self.h, ms), "phx_reannotate_ms")
-        return dict(zip(("mask", "solve", "finish"), [float(x) for x in ms]))
+        return self._ms("phx_reannotate_ms")
 
     def drop_stats(self):
         """Counters of the last drop-margins computation (phx_drop_stats): gene slots, slots with cross nodes, saturated slots rescanned
@@ -1004,12 +914,7 @@ class Annotator:
                                    n_limbs, source, target, path.ctypes.data_as(C.c_void_p), V, C.byref(n), dl.ctypes.data_as(C.c_void_p)), "phx_solve")
         if n.value == 0:
             return [], None
-        v = 0
-        for k in range(n_limbs):
-            v |= int(dl[k]) << (64 * k)
-        if v >> (64 * n_limbs - 1):
-            v -= 1 << (64 * n_limbs)
-        return path[: n.value].tolist(), v
+        return path[: n.value].tolist(), _limbs_to_int(dl, n_limbs)
 
     # ---- measurement ----
     def set_profiling(self, on=True):

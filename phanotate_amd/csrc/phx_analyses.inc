@@ -128,36 +128,13 @@ static int32_t margins_status(const phx_ctx *c, int i) {
     return r;
 }
 
+static int margins_out(phx_ctx *c, const char *who, bool again, phx_orf_margin *rec, int32_t *lost, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out);
 int phx_margins_flat(phx_ctx *c, phx_orf_margin *rec, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
     if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
     { const int ra = after_run(c); if (ra) return ra; }
     { const int rx = ensure_exact(c); if (rx) return rx; } // `called` is against the genes phx_download* deliver
     { const int rm = ensure_margins(c); if (rm) return rm; }
-    try {
-    int64_t total = 0;
-    for (int i = 0; i < c->n; i++) { offsets[i] = total; status[i] = margins_status(c, i); if (status[i] >= 0) total += c->meta[(size_t)i].n_orf; }
-    offsets[c->n] = total;
-    if (total_out) *total_out = total;
-    if (!rec) return PHX_OK; // size query
-    if (cap < total) return PHX_E_ARG;
-    { const int rg = stage_run_genes(c); if (rg) return rg; }
-    { const int rg = ensure_grp_host(c); if (rg) return rg; }
-    std::vector<uint64_t> keys;
-    std::vector<int> order;
-    for (int i = 0; i < c->n; i++) {
-        if (status[i] < 0) continue;
-        called_keys(c, i, keys);
-        // the device's records, in the reference's order
-        phx_orf_margin *dst = rec + offsets[i];
-        const phx_orf_margin *from = (const phx_orf_margin *)c->h_mrec.p + c->meta[(size_t)i].orf_off;
-        each_group_in_reference_order(c, (size_t)i, order, [&](int32_t first, int32_t k) {
-            if (k > 0) memcpy(dst, from + first, sizeof(phx_orf_margin) * (size_t)k);
-            dst += k;
-        });
-        for (int64_t k = offsets[i]; k < offsets[i + 1]; k++) rec[k].called = is_called(keys, rec[k].left, rec[k].right, rec[k].strand) ? 1 : 0;
-    }
-    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_margins_flat"; return PHX_E_NOMEM; }
-    return PHX_OK;
+    return margins_out(c, "phx_margins_flat", false, rec, nullptr, cap, offsets, status, total_out);
 }
 
 int phx_tap_dist_target(phx_ctx *c, int32_t contig, uint64_t *dist_limbs, int64_t cap_words) {
@@ -546,6 +523,63 @@ static void reann_batch(phx_ctx *c, DBatch *b, DReann *q) {
     q->gplan = (uint8_t *)c->b_qplan.p; q->dist0 = (const uint64_t *)c->b_dist.p; q->stride0 = c->n_limbs; q->rec = (DReannRec *)c->b_qrec.p;
 }
 
+// What one re-solve — the re-annotation's, or a chunk of scenario slots — owns on the device and reads back.
+struct ReSolve {
+    const char *what, *unit;             // the error texts' prefix ("re-annotation" / "scenarios") and what a record stands for
+    DevBuf &tot, &gtot, &tie, &rec, &genes;
+    DTotals &h_tot;                      // the totals and the gene count as read back: members of the context (see h_qdforb)
+    uint32_t &h_gtot;
+    DReannRec *h_rec;                    // the n_rec records as read back
+    size_t n_rec, gene_bound;            // ... and how many gene records the solve may write
+    std::vector<DGene> &h_genes;         // the gene records are appended here (gene_off of a record counts from where they start)
+};
+// One re-solve with its tie-scratch retry.  begin(attempt): the caller's views of the buffers (the tie scratch may have grown) and the reset
+// of whatever its mask kernels count or sum; launch(step): its mask (0), solve (1) and finish (2) kernels.  ms[3]: device time of mask,
+// solve and finish + gene copy of the attempt that settled.
+extern "C++" template <class Begin, class Launch> static int resolve_attempts(phx_ctx *c, const ReSolve &R, float *ms, Begin begin, Launch launch) {
+    int rc;
+    hipStream_t s = c->stream;
+    DTotals &tot = R.h_tot;
+    uint32_t &gtot = R.h_gtot;
+    gtot = 0;
+    for (int attempt = 0;; attempt++) {
+        HIPCHK(c, hipEventRecord(c->aev[0], s));
+        HIPCHK(c, hipMemsetAsync(R.tot.p, 0, sizeof(DTotals), s));
+        HIPCHK(c, hipMemsetAsync(R.gtot.p, 0, 16, s));
+        if ((rc = begin(attempt))) return rc;
+        launch(0);
+        HIPCHK(c, hipEventRecord(c->aev[1], s));
+        launch(1);
+        HIPCHK(c, hipEventRecord(c->aev[2], s));
+        launch(2);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(R.h_rec, R.rec.p, R.n_rec * sizeof(DReannRec), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipEventRecord(c->aev[3], s));
+        HIPCHK(c, hipMemcpyAsync(&tot, R.tot.p, sizeof(DTotals), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(&gtot, R.gtot.p, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        if (!(tot.overflow & 4)) break;
+        // the in-order pass's scratch was too small for the contigs with equal-length alternatives: grow it and solve again
+        if (attempt >= 2) { c->err = std::string(R.what) + ": the tie scratch did not settle"; return PHX_E_STATE; }
+        if ((rc = ensure(c, R.tie, (size_t)tot.tie_need + (size_t)tot.tie_need / 4 + 4096))) return rc;
+    }
+    if ((size_t)gtot > R.gene_bound) { c->err = std::string(R.what) + ": gene records beyond the buffer"; return PHX_E_STATE; }
+    const size_t base = R.h_genes.size();
+    R.h_genes.resize(base + gtot);
+    HIPCHK(c, hipEventRecord(c->aev[4], s));
+    if (gtot) HIPCHK(c, hipMemcpyAsync(R.h_genes.data() + base, R.genes.p, (size_t)gtot * sizeof(DGene), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipEventRecord(c->aev[5], s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    ms[0] = ev_ms(c->aev[0], c->aev[1]);
+    ms[1] = ev_ms(c->aev[1], c->aev[2]);
+    ms[2] = ev_ms(c->aev[2], c->aev[3]) + ev_ms(c->aev[4], c->aev[5]);
+    for (size_t k = 0; k < R.n_rec; k++) {
+        const DReannRec &r = R.h_rec[k];
+        if (r.n_genes < 0 || r.gene_off < 0 || (uint64_t)r.gene_off + (uint64_t)r.n_genes > (uint64_t)gtot) { c->err = std::string(R.what) + ": a " + R.unit + "'s gene records lie outside the buffer"; return PHX_E_STATE; }
+    }
+    return PHX_OK;
+}
+
 // Solves the contigs of h_qsel again (1: masked, 2: under the required policy, 3: under the bias policy, 4: under both, §22) with the ORFs of `forb` (tap order;
 // 1 = refused, 2 = required, h_qnreq of them per contig) and the integers of `bias` (tap order; null: none); the records into h_qrec, the
 // genes into h_qgenes.
@@ -601,53 +635,48 @@ static int reann_compute(phx_ctx *c, const uint8_t *forb, const int64_t *bias, c
     HIPCHK(c, hipMemcpyAsync(c->b_qforb.p, dforb.data(), N + 1, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(c->b_qsel.p, dsel.data(), 3 * (n + 1) * 4, hipMemcpyHostToDevice, s));
     if (any_bias) HIPCHK(c, hipMemcpyAsync(c->b_qbias.p, dbias.data(), (N + 1) * 8, hipMemcpyHostToDevice, s));
-    DTotals &tot = c->h_qtot;
-    uint32_t &gtot = c->h_qgtot;
-    gtot = 0;
-    for (int attempt = 0;; attempt++) {
-        DBatch b;
-        DReann q;
+    DBatch b;
+    DReann q;
+    const ReSolve R{"re-annotation", "contig", c->b_qtot, c->b_qgtot, c->b_qtie, c->b_qrec, c->b_qgenes, c->h_qtot, c->h_qgtot, c->h_qrec.data(), n, V + n, c->h_qgenes};
+    return resolve_attempts(c, R, c->reann_ms, [&](int attempt) -> int {
         reann_batch(c, &b, &q);
-        HIPCHK(c, hipEventRecord(c->aev[0], s));
         HIPCHK(c, hipMemcpyAsync(c->b_qmeta.p, c->b_meta.p, n * sizeof(DMeta), hipMemcpyDeviceToDevice, s)); // the layout and the run's verdicts; the kernels write this copy
-        HIPCHK(c, hipMemsetAsync(c->b_qtot.p, 0, sizeof(DTotals), s));
-        HIPCHK(c, hipMemsetAsync(c->b_qgtot.p, 0, 16, s));
         HIPCHK(c, hipMemsetAsync(c->b_qrec.p, 0, (n + 1) * sizeof(DReannRec), s));
         HIPCHK(c, hipMemsetAsync(c->b_qmask.p, 0, (any_bias ? 3 : any_req ? 2 : 1) * mw * 4, s));
         if (any_req && attempt) HIPCHK(c, hipMemsetAsync((int32_t *)c->b_qsel.p + 2 * (n + 1), 0, (n + 1) * 4, s)); // k_rs_mask counts again
         if (any_bias) HIPCHK(c, hipMemsetAsync(c->b_qbsum.p, 0, 2 * (n + 1) * 8, s)); // (... and sums again)
-        phxk_reann_mask(&b, &q, s);
-        HIPCHK(c, hipEventRecord(c->aev[1], s));
-        phxk_reann_solve(&b, &q, nlm, s);
-        HIPCHK(c, hipEventRecord(c->aev[2], s));
-        phxk_reann_finish(&b, &q, nlm, s);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(c->h_qrec.data(), c->b_qrec.p, n * sizeof(DReannRec), hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipEventRecord(c->aev[3], s));
-        HIPCHK(c, hipMemcpyAsync(&tot, c->b_qtot.p, sizeof(DTotals), hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(&gtot, c->b_qgtot.p, 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        if (!(tot.overflow & 4)) break;
-        // k_rs_inorder's scratch was too small for the contigs with equal-length alternatives: grow it and solve again
-        if (attempt >= 2) { c->err = "re-annotation: the tie scratch did not settle"; return PHX_E_STATE; }
-        if ((rc = ensure(c, c->b_qtie, (size_t)tot.tie_need + (size_t)tot.tie_need / 4 + 4096))) return rc;
-    }
-    if ((size_t)gtot > V + n) { c->err = "re-annotation: gene records beyond the buffer"; return PHX_E_STATE; }
-    c->h_qgenes.resize(gtot);
-    HIPCHK(c, hipEventRecord(c->aev[4], s));
-    if (gtot) HIPCHK(c, hipMemcpyAsync(c->h_qgenes.data(), c->b_qgenes.p, (size_t)gtot * sizeof(DGene), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipEventRecord(c->aev[5], s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    c->reann_ms[0] = ev_ms(c->aev[0], c->aev[1]);
-    c->reann_ms[1] = ev_ms(c->aev[1], c->aev[2]);
-    c->reann_ms[2] = ev_ms(c->aev[2], c->aev[3]) + ev_ms(c->aev[4], c->aev[5]);
-    for (size_t i = 0; i < n; i++) {
-        if (!c->h_qsel[i]) continue;
-        const DReannRec &r = c->h_qrec[i];
-        if (r.n_genes < 0 || r.gene_off < 0 || (uint64_t)r.gene_off + (uint64_t)r.n_genes > (uint64_t)gtot) { c->err = "re-annotation: a contig's gene records lie outside the buffer"; return PHX_E_STATE; }
-    }
-    return PHX_OK;
+        return PHX_OK;
+    }, [&](int step) {
+        if (step == 0) phxk_reann_mask(&b, &q, s);
+        else if (step == 1) phxk_reann_solve(&b, &q, nlm, s);
+        else phxk_reann_finish(&b, &q, nlm, s);
+    });
 }
+
+// The caller's orf_offsets must be the batch's cumulative ORF counts (what phx_margins_flat reports): nothing from the caller indexes device
+// memory unchecked.  *total: their sum.
+static bool orf_offsets_ok(const phx_ctx *c, const int64_t *orf_offsets, int64_t *total) {
+    int64_t acc = 0;
+    for (int i = 0; i < c->n; i++) {
+        if (orf_offsets[i] != acc) return false;
+        if (reann_status(c, i) >= 0) acc += c->meta[(size_t)i].n_orf;
+    }
+    *total = acc;
+    return c->n <= 0 || orf_offsets[c->n] == acc;
+}
+// One entry of a re-solve's layout for the caller: contig i's result under record r, or with r null — not solved again — the run's (the
+// device's lists: no host re-solve enters); n_req: the required ORFs named for it.  Returns the entry's gene count; resolve_genes: where they lie.
+static int64_t resolve_entry(const phx_ctx *c, int i, const DReannRec *r, int64_t n_req, int32_t *status, double *delta, int32_t *unmet) {
+    const int32_t st = reann_status(c, i);
+    *status = st; *delta = std::numeric_limits<double>::infinity();
+    if (unmet) *unmet = (int32_t)n_req; // (no result: every required ORF is unmet)
+    if (st < 0) return 0;
+    if (!r) { if (st != PHX_S_NOPATH) *delta = 0.0; return std::max(c->res[(size_t)i].n_genes, 0); }
+    *status = r->status; *delta = r->delta;
+    if (unmet) *unmet = r->unmet;
+    return r->status >= 0 ? r->n_genes : 0;
+}
+static const DGene *resolve_genes(const phx_ctx *c, int i, const DReannRec *r, const std::vector<DGene> &again) { return r ? again.data() + r->gene_off : (const DGene *)c->h_genes.p + (size_t)c->res[(size_t)i].gene_off; }
 
 // phx_reannotate_flat (require and unmet null, forbid needed), phx_constrain_flat (either set may be null: empty), phx_evidence_flat (bias
 // and forbid may be null, require is) and phx_curate_flat (any of the three may be null) are one solve on one set of buffers; the cached result is keyed on both sets (h_qforb holds 1 = refused,
@@ -659,13 +688,8 @@ static int reann_flat(phx_ctx *c, const char *who, bool need_forbid, const uint8
     { const int ra = after_run(c); if (ra) return ra; }
     { const int rf = fetch_meta(c); if (rf) return rf; }
     try {
-    // the offsets must be the batch's cumulative ORF counts (what phx_margins_flat reports): nothing from the caller indexes device memory unchecked
     int64_t acc = 0;
-    for (int i = 0; i < c->n; i++) {
-        if (orf_offsets[i] != acc) return PHX_E_ARG;
-        if (reann_status(c, i) >= 0) acc += c->meta[(size_t)i].n_orf;
-    }
-    if (c->n > 0 && orf_offsets[c->n] != acc) return PHX_E_ARG;
+    if (!orf_offsets_ok(c, orf_offsets, &acc)) return PHX_E_ARG;
     if (acc > 0 && need_forbid && !forbid) return PHX_E_ARG;
     const size_t N = (size_t)acc;
     std::vector<uint8_t> &code = c->h_qcode; // per ORF: 1 = refused, 2 = required
@@ -707,22 +731,12 @@ static int reann_flat(phx_ctx *c, const char *who, bool need_forbid, const uint8
         c->h_qflags = flags;
         c->done.reann = true;
     }
-    // the run's own genes for the contigs that were not solved again (the device's lists: no host re-solve enters)
+    // the run's own genes for the contigs that were not solved again
+    auto rec_of = [&](int i) { return c->h_qsel[(size_t)i] ? &c->h_qrec[(size_t)i] : nullptr; };
     int64_t total = 0;
     for (int i = 0; i < c->n; i++) {
-        const int32_t st = reann_status(c, i);
-        offsets[i] = total; status[i] = st; delta[i] = std::numeric_limits<double>::infinity();
-        if (unmet) unmet[i] = c->h_qnreq[(size_t)i]; // (no result: every required ORF is unmet)
-        if (st < 0) continue;
-        if (c->h_qsel[(size_t)i]) {
-            const DReannRec &r = c->h_qrec[(size_t)i];
-            status[i] = r.status; delta[i] = r.delta;
-            if (unmet) unmet[i] = r.unmet;
-            if (r.status >= 0) total += r.n_genes;
-        } else {
-            if (st != PHX_S_NOPATH) delta[i] = 0.0;
-            if (c->res[(size_t)i].n_genes > 0) total += c->res[(size_t)i].n_genes;
-        }
+        offsets[i] = total;
+        total += resolve_entry(c, i, rec_of(i), c->h_qnreq[(size_t)i], status + i, delta + i, unmet ? unmet + i : nullptr);
     }
     offsets[c->n] = total;
     if (total_out) *total_out = total;
@@ -732,8 +746,7 @@ static int reann_flat(phx_ctx *c, const char *who, bool need_forbid, const uint8
     for (int i = 0; i < c->n; i++) {
         const int64_t k = offsets[i + 1] - offsets[i];
         if (k <= 0) continue;
-        const DGene *src = c->h_qsel[(size_t)i] ? c->h_qgenes.data() + c->h_qrec[(size_t)i].gene_off : (const DGene *)c->h_genes.p + (size_t)c->res[(size_t)i].gene_off;
-        memcpy(genes + offsets[i], src, sizeof(phx_gene) * (size_t)k);
+        memcpy(genes + offsets[i], resolve_genes(c, i, rec_of(i), c->h_qgenes), sizeof(phx_gene) * (size_t)k);
     }
     } catch (const std::bad_alloc &) { c->err = std::string("out of memory in ") + who; return PHX_E_NOMEM; }
     return PHX_OK;
@@ -802,9 +815,26 @@ int phx_reannotate_ms(phx_ctx *c, float *ms) {
     return PHX_OK;
 }
 
-// ---- re-annotation margins (phx_margins.inc, DESIGN.md §21): per-ORF path margins on the last re-annotation's graph G_{F,B} ----
-// PHX_OK when the context holds a re-annotation the margins are defined for
+// ---- the conditioned margins (phx_margins.inc): per-ORF path margins on the last re-annotation's graph ----
+// Two policies share one driver.  The re-annotation margins (DESIGN.md §21) cover the contigs solved again without a required ORF (modes 1
+// and 3, the MgCond kernels, c->xm); the pinned margins (§24) the contigs solved under the required policy (modes 2 and 4, the MgPin
+// kernels on one limb more, c->pm, with a third bitmap and `lost`).
 #define WINF_TOP_HOST 0x7fffffffffffffffull // the solver's "unreached" top limb (WINF_TOP, phx_sssp.inc)
+struct CmPlain {
+    typedef DRmarg Rec;
+    static constexpr bool pinned = false;
+    static constexpr const char *who = "phx_remargins_flat";
+    static constexpr auto apply = phxk_remarg_apply;
+    static constexpr auto rev = phxk_remarg_rev, records = phxk_remarg_records;
+};
+struct CmPin {
+    typedef DPmarg Rec;
+    static constexpr bool pinned = true;
+    static constexpr const char *who = "phx_pinmargins_flat";
+    static constexpr auto apply = phxk_pinmarg_apply;
+    static constexpr auto rev = phxk_pinmarg_rev, records = phxk_pinmarg_records;
+};
+// PHX_OK when the context holds a re-annotation the re-annotation margins are defined for
 static int remarg_state(phx_ctx *c, const char *who) {
     if (!c->done.reann) { c->err = std::string(who) + ": no re-annotation of this run (call phx_reannotate_flat or phx_evidence_flat first)"; return PHX_E_STATE; }
     for (int i = 0; i < c->n; i++)
@@ -812,36 +842,41 @@ static int remarg_state(phx_ctx *c, const char *who) {
     return PHX_OK;
 }
 
-// The records of every ORF of the contigs that were solved again (device order) into c->h_xrec and the pass's verdicts into c->xmstat, once
-// per re-annotation solve, on top of ensure_margins: that gives the out-edge CSR, the run's records for the contigs that were not solved
-// again and the run's mstat.  Reads what the solve left resident (b_qforb, b_qbias, b_qmask, b_qbval, b_qdist: nothing between a
-// re-annotation and this call writes them — only reann_compute does, and the scenario batches own b_sc_*); writes only b_x*.
-static int ensure_remargins(phx_ctx *c) {
-    if (c->done.remarg) return PHX_OK;
-    { const int rm = ensure_margins(c); if (rm) return rm; }
+// The records of every ORF of the policy's contigs (device order) into m.h_rec (`lost` into m.h_lost) and the pass's verdicts into m.mstat,
+// once per re-annotation solve.  CmPlain builds on ensure_margins — that gives the out-edge CSR, the run's records for the contigs that were
+// not solved again and the run's mstat —, CmPin on CmPlain.  Reads what the solve left resident (b_qforb, b_qbias, b_qmask, b_qbval,
+// b_qdist: nothing between a re-annotation and this call writes them — only reann_compute does, and the scenario batches own b_sc_*);
+// writes only m's buffers.  m.ms: the device time; the pinned margins' is that of both parts as computed for this solve.
+extern "C++" template <class P> static int ensure_condmargins(phx_ctx *c) {
+    phx_ctx::CondMarg &m = P::pinned ? c->pm : c->xm;
+    bool &done = P::pinned ? c->done.pinmarg : c->done.remarg;
+    if (done) return PHX_OK;
+    const bool fresh = P::pinned && !c->done.remarg; // the re-annotation margins are computed by this same call
+    { const int rm = P::pinned ? ensure_condmargins<CmPlain>(c) : ensure_margins(c); if (rm) return rm; }
     const size_t n = (size_t)c->n, V = (size_t)c->tot_node, E = (size_t)c->tot_edge, N = (size_t)c->tot_orf;
-    const size_t limbs = (size_t)std::max(c->n_limbs, 2);
-    const size_t mw = E / 32 + 2; // words of one bitmap over the out-edge positions
+    const size_t limbs = (size_t)std::max(c->n_limbs, 2) + (P::pinned ? 1 : 0);
+    const size_t mw = E / 32 + 2, nbit = P::pinned ? 3 : 2; // words of one bitmap over the out-edge positions; refused, biased, required
     int rev_nlm = 0, rec_nlm = 0;
     bool biased = false;
-    c->h_xsel.assign(n + 1, 0);
-    c->xmstat.assign(n + 1, 0);
+    m.h_sel.assign(n + 1, 0);
+    m.mstat.assign(n + 1, 0);
     for (size_t i = 0; i < n; i++) {
-        if (!c->h_qsel[i] || !reann_contig(c, (int)i) || re_mode_req(c->h_qsel[i])) continue; // (a contig solved under the required policy: ensure_pinmargins')
+        if (!c->h_qsel[i] || re_mode_req(c->h_qsel[i]) != P::pinned || !reann_contig(c, (int)i)) continue;
         const int32_t st = c->h_qrec[i].status;
         if (st < 0) continue;
-        c->h_xsel[i] = st == 0 ? 1 : 2; // (PHX_S_NOPATH: records only, D' is unreached)
+        m.h_sel[i] = st == 0 ? 1 : 2; // (PHX_S_NOPATH: records only, D' is unreached)
         rec_nlm |= nl_class_bit(c->meta[i].sssp_nl);
         if (st == 0) { rev_nlm |= nl_class_bit(c->meta[i].sssp_nl); biased = biased || re_mode_bias(c->h_qsel[i]); }
     }
-    for (int k = 0; k < 4; k++) c->remarg_ms[k] = 0;
-    if (!rec_nlm) { c->done.remarg = true; return PHX_OK; }
+    for (int k = 0; k < 4; k++) m.ms[k] = fresh ? c->xm.ms[k] : 0;
+    if (!rec_nlm) { done = true; return PHX_OK; }
     int rc;
-    if ((rc = ensure(c, c->b_xsel, (n + 1) * 4)) || (rc = ensure(c, c->b_xbit, 2 * mw * 4)) || (biased && (rc = ensure(c, c->b_xbval, (E + 1) * 8))) ||
-        (rc = ensure(c, c->b_xdt, (V + 1) * limbs * 8)) || (rc = ensure(c, c->b_xrec, (N + 1) * sizeof(phx_orf_margin))) || (rc = ensure(c, c->b_xmstat, (n + 1) * 4)))
+    if ((rc = ensure(c, m.b_sel, (n + 1) * 4)) || (rc = ensure(c, m.b_bit, nbit * mw * 4)) || (biased && (rc = ensure(c, m.b_bval, (E + 1) * 8))) ||
+        (rc = ensure(c, m.b_dt, (V + 1) * limbs * 8)) || (rc = ensure(c, m.b_rec, (N + 1) * sizeof(phx_orf_margin))) || (P::pinned && (rc = ensure(c, m.b_lost, (N + 1) * 4))) ||
+        (rc = ensure(c, m.b_mstat, (n + 1) * 4)))
         return rc;
     if ((rc = analysis_events(c))) return rc;
-    try { c->h_xrec.resize(N + 1); } catch (const std::bad_alloc &) { c->err = "out of memory in phx_remargins_flat"; return PHX_E_NOMEM; }
+    try { m.h_rec.resize(N + 1); if (P::pinned) m.h_lost.resize(N + 1); } catch (const std::bad_alloc &) { c->err = std::string("out of memory in ") + P::who; return PHX_E_NOMEM; }
     DBatch b;
     fill_batch(c, &b);
     DMarg g;
@@ -849,185 +884,77 @@ static int ensure_remargins(phx_ctx *c) {
     DBatch qb;
     DReann q;
     reann_batch(c, &qb, &q);
-    DRmarg r;
-    r.sel = (const int32_t *)c->b_xsel.p; r.ds = (const uint64_t *)c->b_qdist.p; r.ds_stride = c->qstride;
-    r.fbit = (uint32_t *)c->b_xbit.p; r.bbit = r.fbit + mw; r.bval = (long long *)c->b_xbval.p;
-    r.dist_t = (uint64_t *)c->b_xdt.p; r.rec = (phx_orf_margin *)c->b_xrec.p; r.mstat = (int32_t *)c->b_xmstat.p;
+    typename P::Rec r;
+    r.sel = (const int32_t *)m.b_sel.p; r.ds = (const uint64_t *)c->b_qdist.p; r.ds_stride = c->qstride;
+    r.fbit = (uint32_t *)m.b_bit.p; r.bbit = r.fbit + mw; r.bval = (long long *)m.b_bval.p;
+    r.dist_t = (uint64_t *)m.b_dt.p; r.rec = (phx_orf_margin *)m.b_rec.p; r.mstat = (int32_t *)m.b_mstat.p;
+    if constexpr (P::pinned) { r.dt_stride = b.dist_stride + 1; r.rbit = r.fbit + 2 * mw; r.lost = (int32_t *)m.b_lost.p; }
     hipStream_t s = c->stream;
-    HIPCHK(c, hipMemcpyAsync(c->b_xsel.p, c->h_xsel.data(), (n + 1) * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(m.b_sel.p, m.h_sel.data(), (n + 1) * 4, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipEventRecord(c->aev[0], s));
-    HIPCHK(c, hipMemsetAsync(c->b_xbit.p, 0, 2 * mw * 4, s));
-    HIPCHK(c, hipMemsetAsync(c->b_xmstat.p, 0, (n + 1) * 4, s));
-    if (rev_nlm) phxk_remarg_apply(&b, &g, &q, &r, s);
+    HIPCHK(c, hipMemsetAsync(m.b_bit.p, 0, nbit * mw * 4, s));
+    HIPCHK(c, hipMemsetAsync(m.b_mstat.p, 0, (n + 1) * 4, s));
+    if (rev_nlm) P::apply(&b, &g, &q, &r, s);
     HIPCHK(c, hipEventRecord(c->aev[1], s));
-    if (rev_nlm) phxk_remarg_rev(&b, &g, &q, &r, rev_nlm, s);
+    if (rev_nlm) P::rev(&b, &g, &q, &r, rev_nlm, s);
     HIPCHK(c, hipEventRecord(c->aev[2], s));
-    phxk_remarg_records(&b, &g, &q, &r, rec_nlm, s);
+    P::records(&b, &g, &q, &r, rec_nlm, s);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->aev[3], s));
-    if (N) HIPCHK(c, hipMemcpyAsync(c->h_xrec.data(), c->b_xrec.p, N * sizeof(phx_orf_margin), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(c->xmstat.data(), c->b_xmstat.p, n * 4, hipMemcpyDeviceToHost, s));
+    if (N) HIPCHK(c, hipMemcpyAsync(m.h_rec.data(), m.b_rec.p, N * sizeof(phx_orf_margin), hipMemcpyDeviceToHost, s));
+    if (P::pinned && N) HIPCHK(c, hipMemcpyAsync(m.h_lost.data(), m.b_lost.p, N * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(m.mstat.data(), m.b_mstat.p, n * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipEventRecord(c->aev[4], s));
     HIPCHK(c, hipStreamSynchronize(s));
-    for (int k = 0; k < 4; k++) c->remarg_ms[k] = ev_ms(c->aev[k], c->aev[k + 1]);
-    c->done.remarg = true;
+    for (int k = 0; k < 4; k++) m.ms[k] += ev_ms(c->aev[k], c->aev[k + 1]);
+    done = true;
     return PHX_OK;
 }
 
-// status of contig i's re-annotation margins (include/phx.h)
-static int32_t remargins_status(const phx_ctx *c, int i) {
-    if (!c->h_qsel[(size_t)i]) return margins_status(c, i);
+// status of contig i's margins after a re-annotation (include/phx.h): the run's for a contig that was not solved again
+static int32_t condmargins_status(const phx_ctx *c, int i) {
+    const int mode = c->h_qsel[(size_t)i];
+    if (!mode) return margins_status(c, i);
     const int32_t r = c->res[(size_t)i].status;
     if (r < 0) return r;
     const int32_t q = c->h_qrec[(size_t)i].status;
     if (q != 0) return q;
-    return c->xmstat[(size_t)i] ? PHX_S_NEGCYCLE : 0;
+    return (re_mode_req(mode) ? c->pm : c->xm).mstat[(size_t)i] ? PHX_S_NEGCYCLE : 0;
 }
 
-static int remargins_out(phx_ctx *c, const char *who, phx_orf_margin *rec, int32_t *lost, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out);
-int phx_remargins_flat(phx_ctx *c, phx_orf_margin *rec, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
-    if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
-    { const int ra = after_run(c); if (ra) return ra; }
-    { const int rs = remarg_state(c, "phx_remargins_flat"); if (rs) return rs; } // before any kernel
-    { const int rm = ensure_remargins(c); if (rm) return rm; }
-    return remargins_out(c, "phx_remargins_flat", rec, nullptr, cap, offsets, status, total_out);
-}
-
-// d_s' / d_t' of a contig that was not solved under the required policy (the caller has checked the state and `which`)
-static int tap_redist_plain(phx_ctx *c, int32_t contig, int32_t which, uint64_t *dist_limbs, int64_t cap_words) {
-    const DMeta &m = c->meta[(size_t)contig];
-    if (!c->h_qsel[(size_t)contig]) return which ? phx_tap_dist_target(c, contig, dist_limbs, cap_words) : phx_tap_dist(c, contig, dist_limbs, cap_words); // the run's vectors stand
-    const size_t nl = (size_t)m.sssp_nl, words = (size_t)m.n_node * nl;
-    if (!dist_limbs || cap_words < (int64_t)words) return PHX_E_ARG;
-    if (which) { const int rm = ensure_remargins(c); if (rm) return rm; }
-    const bool have = which ? (c->h_xsel[(size_t)contig] == 1 && !c->xmstat[(size_t)contig]) : c->h_qrec[(size_t)contig].status >= 0;
-    if (!have) { // no such vector (the re-solve ended with an error; no path, so no d_t'): every node unreached
-        for (size_t v = 0; v < (size_t)m.n_node; v++) for (size_t k = 0; k < nl; k++) dist_limbs[v * nl + k] = k + 1 == nl ? WINF_TOP_HOST : 0;
-        return PHX_OK;
-    }
-    const uint64_t *from = which ? (const uint64_t *)c->b_xdt.p + (size_t)m.node_off * (size_t)c->n_limbs : (const uint64_t *)c->b_qdist.p + (size_t)m.node_off * (size_t)c->qstride;
-    HIPCHK(c, hipMemcpy(dist_limbs, from, words * 8, hipMemcpyDeviceToHost));
-    return PHX_OK;
-}
-
-int phx_tap_redist(phx_ctx *c, int32_t contig, int32_t which, uint64_t *dist_limbs, int64_t cap_words) {
-    TAP_PRE(c, contig);
-    (void)m;
-    if (which != 0 && which != 1) return PHX_E_ARG;
-    { const int rs = remarg_state(c, "phx_tap_redist"); if (rs) return rs; }
-    return tap_redist_plain(c, contig, which, dist_limbs, cap_words);
-}
-
-int phx_remargins_ms(phx_ctx *c, float *ms) {
-    if (!c || !ms) return PHX_E_ARG;
-    for (int k = 0; k < 4; k++) ms[k] = c->remarg_ms[k];
-    return PHX_OK;
-}
-
-// ---- pinned margins (phx_margins.inc, DESIGN.md §24): the re-annotation margins where ORFs were required ----
-// On top of ensure_remargins, which covers the contigs solved again without a required ORF (modes 1 and 3, the MgCond kernels): the
-// contigs solved under the required policy (modes 2 and 4) run the MgPin kernels on one limb more, into buffers of their own (b_p*),
-// allocated at the first call that has such a contig.  Records into c->h_prec, `lost` into c->h_plost (device order), the pass's verdicts
-// into c->pmstat, once per re-annotation solve.  pinmarg_ms: the device time of both parts as computed for this solve.
-static int ensure_pinmargins(phx_ctx *c) {
-    if (c->done.pinmarg) return PHX_OK;
-    const bool fresh = !c->done.remarg;
-    { const int rm = ensure_remargins(c); if (rm) return rm; }
-    const size_t n = (size_t)c->n, V = (size_t)c->tot_node, E = (size_t)c->tot_edge, N = (size_t)c->tot_orf;
-    const size_t limbs = (size_t)std::max(c->n_limbs, 2);
-    const size_t mw = E / 32 + 2; // words of one bitmap over the out-edge positions
-    int rev_nlm = 0, rec_nlm = 0;
-    bool biased = false;
-    c->h_psel.assign(n + 1, 0);
-    c->pmstat.assign(n + 1, 0);
-    for (size_t i = 0; i < n; i++) {
-        if (!re_mode_req(c->h_qsel[i]) || !reann_contig(c, (int)i)) continue;
-        const int32_t st = c->h_qrec[i].status;
-        if (st < 0) continue;
-        c->h_psel[i] = st == 0 ? 1 : 2; // (PHX_S_NOPATH: records only, D' is unreached)
-        rec_nlm |= nl_class_bit(c->meta[i].sssp_nl);
-        if (st == 0) { rev_nlm |= nl_class_bit(c->meta[i].sssp_nl); biased = biased || re_mode_bias(c->h_qsel[i]); }
-    }
-    for (int k = 0; k < 4; k++) c->pinmarg_ms[k] = fresh ? c->remarg_ms[k] : 0;
-    if (!rec_nlm) { c->done.pinmarg = true; return PHX_OK; }
-    int rc;
-    if ((rc = ensure(c, c->b_psel, (n + 1) * 4)) || (rc = ensure(c, c->b_pbit, 3 * mw * 4)) || (biased && (rc = ensure(c, c->b_pbval, (E + 1) * 8))) ||
-        (rc = ensure(c, c->b_pdt, (V + 1) * (limbs + 1) * 8)) || (rc = ensure(c, c->b_prec, (N + 1) * sizeof(phx_orf_margin))) || (rc = ensure(c, c->b_plost, (N + 1) * 4)) ||
-        (rc = ensure(c, c->b_pmstat, (n + 1) * 4)))
-        return rc;
-    if ((rc = analysis_events(c))) return rc;
-    try { c->h_prec.resize(N + 1); c->h_plost.resize(N + 1); } catch (const std::bad_alloc &) { c->err = "out of memory in phx_pinmargins_flat"; return PHX_E_NOMEM; }
-    DBatch b;
-    fill_batch(c, &b);
-    DMarg g;
-    margins_args(c, &g);
-    DBatch qb;
-    DReann q;
-    reann_batch(c, &qb, &q);
-    DPmarg r;
-    r.sel = (const int32_t *)c->b_psel.p; r.ds = (const uint64_t *)c->b_qdist.p; r.ds_stride = c->qstride; r.dt_stride = b.dist_stride + 1;
-    r.fbit = (uint32_t *)c->b_pbit.p; r.bbit = r.fbit + mw; r.rbit = r.fbit + 2 * mw; r.bval = (long long *)c->b_pbval.p;
-    r.dist_t = (uint64_t *)c->b_pdt.p; r.rec = (phx_orf_margin *)c->b_prec.p; r.lost = (int32_t *)c->b_plost.p; r.mstat = (int32_t *)c->b_pmstat.p;
-    hipStream_t s = c->stream;
-    HIPCHK(c, hipMemcpyAsync(c->b_psel.p, c->h_psel.data(), (n + 1) * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipEventRecord(c->aev[0], s));
-    HIPCHK(c, hipMemsetAsync(c->b_pbit.p, 0, 3 * mw * 4, s));
-    HIPCHK(c, hipMemsetAsync(c->b_pmstat.p, 0, (n + 1) * 4, s));
-    if (rev_nlm) phxk_pinmarg_apply(&b, &g, &q, &r, s);
-    HIPCHK(c, hipEventRecord(c->aev[1], s));
-    if (rev_nlm) phxk_pinmarg_rev(&b, &g, &q, &r, rev_nlm, s);
-    HIPCHK(c, hipEventRecord(c->aev[2], s));
-    phxk_pinmarg_records(&b, &g, &q, &r, rec_nlm, s);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->aev[3], s));
-    if (N) HIPCHK(c, hipMemcpyAsync(c->h_prec.data(), c->b_prec.p, N * sizeof(phx_orf_margin), hipMemcpyDeviceToHost, s));
-    if (N) HIPCHK(c, hipMemcpyAsync(c->h_plost.data(), c->b_plost.p, N * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(c->pmstat.data(), c->b_pmstat.p, n * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipEventRecord(c->aev[4], s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    for (int k = 0; k < 4; k++) c->pinmarg_ms[k] += ev_ms(c->aev[k], c->aev[k + 1]);
-    c->done.pinmarg = true;
-    return PHX_OK;
-}
-
-// status of contig i's pinned margins (include/phx.h): phx_remargins_flat's, "solved again" covering every mode
-static int32_t pinmargins_status(const phx_ctx *c, int i) {
-    if (!re_mode_req(c->h_qsel[(size_t)i])) return remargins_status(c, i);
-    const int32_t r = c->res[(size_t)i].status;
-    if (r < 0) return r;
-    const int32_t q = c->h_qrec[(size_t)i].status;
-    if (q != 0) return q;
-    return c->pmstat[(size_t)i] ? PHX_S_NEGCYCLE : 0;
-}
-
-// The layout of phx_remargins_flat and phx_pinmargins_flat, behind their ensure_*: offsets and statuses, then the records in reference
-// order with `called` set.  lost: null for phx_remargins_flat (no contig was solved under the required policy then), else parallel to rec.
-static int remargins_out(phx_ctx *c, const char *who, phx_orf_margin *rec, int32_t *lost, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
+// The layout of phx_margins_flat, phx_remargins_flat and phx_pinmargins_flat, behind their ensure_*: offsets and statuses, then the records
+// in reference order with `called` set.  again: false for the run's margins (no contig counts as solved again, `called` is against the genes
+// phx_download* deliver), else against the genes the re-annotation call returns — the device's lists, no host re-solve enters.  lost: null
+// but for phx_pinmargins_flat, else parallel to rec.
+static int margins_out(phx_ctx *c, const char *who, bool again, phx_orf_margin *rec, int32_t *lost, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
     try {
     int64_t total = 0;
-    for (int i = 0; i < c->n; i++) { offsets[i] = total; status[i] = pinmargins_status(c, i); if (status[i] >= 0) total += c->meta[(size_t)i].n_orf; }
+    for (int i = 0; i < c->n; i++) { offsets[i] = total; status[i] = again ? condmargins_status(c, i) : margins_status(c, i); if (status[i] >= 0) total += c->meta[(size_t)i].n_orf; }
     offsets[c->n] = total;
     if (total_out) *total_out = total;
     if (!rec) return PHX_OK; // size query
     if (cap < total) return PHX_E_ARG;
-    { const int rg = stage_run_genes(c, c->h_qsel.data()); if (rg) return rg; } // (of the contigs that were not solved again)
+    { const int rg = stage_run_genes(c, again ? c->h_qsel.data() : nullptr); if (rg) return rg; } // (of the contigs that were not solved again)
     { const int rg = ensure_grp_host(c); if (rg) return rg; }
     std::vector<uint64_t> keys;
     std::vector<int> order;
     for (int i = 0; i < c->n; i++) {
         if (status[i] < 0) continue;
-        // `called`: the genes the re-annotation call returns for the contig — the device's lists, no host re-solve enters
-        const int mode = c->h_qsel[(size_t)i];
-        const bool again = mode != 0, pinned = re_mode_req(mode);
-        const DGene *src = again ? c->h_qgenes.data() + c->h_qrec[(size_t)i].gene_off : (const DGene *)c->h_genes.p + (size_t)c->res[(size_t)i].gene_off;
-        const int64_t ng = again ? (int64_t)c->h_qrec[(size_t)i].n_genes : (int64_t)std::max(c->res[(size_t)i].n_genes, 0);
-        keys.clear();
-        for (int64_t k = 0; k < ng; k++) if (src[k].frame >= -3 && src[k].frame <= 3) keys.push_back(gene_key(src[k].left, src[k].right, src[k].strand));
-        std::sort(keys.begin(), keys.end());
+        const int mode = again ? c->h_qsel[(size_t)i] : 0;
+        const bool pinned = re_mode_req(mode);
+        if (!again) called_keys(c, i, keys);
+        else {
+            const DGene *src = resolve_genes(c, i, mode ? &c->h_qrec[(size_t)i] : nullptr, c->h_qgenes);
+            const int64_t ng = mode ? (int64_t)c->h_qrec[(size_t)i].n_genes : (int64_t)std::max(c->res[(size_t)i].n_genes, 0);
+            keys.clear();
+            for (int64_t k = 0; k < ng; k++) if (src[k].frame >= -3 && src[k].frame <= 3) keys.push_back(gene_key(src[k].left, src[k].right, src[k].strand));
+            std::sort(keys.begin(), keys.end());
+        }
+        // the device's records, in the reference's order
         phx_orf_margin *dst = rec + offsets[i];
         int32_t *ldst = lost ? lost + offsets[i] : nullptr;
-        const phx_orf_margin *from = (pinned ? c->h_prec.data() : again ? c->h_xrec.data() : (const phx_orf_margin *)c->h_mrec.p) + c->meta[(size_t)i].orf_off;
-        const int32_t *lfrom = pinned ? c->h_plost.data() + c->meta[(size_t)i].orf_off : nullptr;
+        const phx_orf_margin *from = (pinned ? c->pm.h_rec.data() : mode ? c->xm.h_rec.data() : (const phx_orf_margin *)c->h_mrec.p) + c->meta[(size_t)i].orf_off;
+        const int32_t *lfrom = pinned ? c->pm.h_lost.data() + c->meta[(size_t)i].orf_off : nullptr;
         each_group_in_reference_order(c, (size_t)i, order, [&](int32_t first, int32_t k) { // (records and `lost` are permuted together)
             if (k > 0) {
                 memcpy(dst, from + first, sizeof(phx_orf_margin) * (size_t)k);
@@ -1043,37 +970,68 @@ static int remargins_out(phx_ctx *c, const char *who, phx_orf_margin *rec, int32
     return PHX_OK;
 }
 
+int phx_remargins_flat(phx_ctx *c, phx_orf_margin *rec, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
+    if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
+    { const int ra = after_run(c); if (ra) return ra; }
+    { const int rs = remarg_state(c, "phx_remargins_flat"); if (rs) return rs; } // before any kernel
+    { const int rm = ensure_condmargins<CmPlain>(c); if (rm) return rm; }
+    return margins_out(c, "phx_remargins_flat", true, rec, nullptr, cap, offsets, status, total_out);
+}
+
 int phx_pinmargins_flat(phx_ctx *c, phx_orf_margin *rec, int32_t *lost, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
     if (!c || (c->n > 0 && (!offsets || !status)) || (rec && !lost)) return PHX_E_ARG;
     { const int ra = after_run(c); if (ra) return ra; }
     if (!c->done.reann) { c->err = "phx_pinmargins_flat: no re-annotation of this run (call phx_constrain_flat or phx_curate_flat first)"; return PHX_E_STATE; } // before any kernel
-    { const int rm = ensure_pinmargins(c); if (rm) return rm; }
-    return remargins_out(c, "phx_pinmargins_flat", rec, lost, cap, offsets, status, total_out);
+    { const int rm = ensure_condmargins<CmPin>(c); if (rm) return rm; }
+    return margins_out(c, "phx_pinmargins_flat", true, rec, lost, cap, offsets, status, total_out);
+}
+
+// d_s' / d_t' of a contig to the caller (who has checked the state and `which`), or every node unreached where there is no such vector.  A
+// contig solved under the required policy has one word more per node; one that was not solved again has the run's vectors.
+static int tap_redist(phx_ctx *c, int32_t contig, int32_t which, uint64_t *dist_limbs, int64_t cap_words) {
+    const DMeta &m = c->meta[(size_t)contig];
+    const int mode = c->h_qsel[(size_t)contig];
+    if (!mode) return which ? phx_tap_dist_target(c, contig, dist_limbs, cap_words) : phx_tap_dist(c, contig, dist_limbs, cap_words); // the run's vectors stand
+    const bool pinned = re_mode_req(mode);
+    const size_t nl = (size_t)m.sssp_nl + (pinned ? 1 : 0), words = (size_t)m.n_node * nl;
+    if (!dist_limbs || cap_words < (int64_t)words) return PHX_E_ARG;
+    if (which) { const int rm = pinned ? ensure_condmargins<CmPin>(c) : ensure_condmargins<CmPlain>(c); if (rm) return rm; }
+    const phx_ctx::CondMarg &cm = pinned ? c->pm : c->xm;
+    const bool have = which ? (cm.h_sel[(size_t)contig] == 1 && !cm.mstat[(size_t)contig]) : c->h_qrec[(size_t)contig].status >= 0;
+    if (!have) { // no such vector (the re-solve ended with an error; no path, so no d_t'): every node unreached
+        for (size_t v = 0; v < (size_t)m.n_node; v++) for (size_t k = 0; k < nl; k++) dist_limbs[v * nl + k] = k + 1 == nl ? WINF_TOP_HOST : 0;
+        return PHX_OK;
+    }
+    const uint64_t *from = which ? (const uint64_t *)cm.b_dt.p + (size_t)m.node_off * (size_t)(c->n_limbs + (pinned ? 1 : 0)) : (const uint64_t *)c->b_qdist.p + (size_t)m.node_off * (size_t)c->qstride;
+    HIPCHK(c, hipMemcpy(dist_limbs, from, words * 8, hipMemcpyDeviceToHost));
+    return PHX_OK;
+}
+
+int phx_tap_redist(phx_ctx *c, int32_t contig, int32_t which, uint64_t *dist_limbs, int64_t cap_words) {
+    TAP_PRE(c, contig);
+    (void)m;
+    if (which != 0 && which != 1) return PHX_E_ARG;
+    { const int rs = remarg_state(c, "phx_tap_redist"); if (rs) return rs; }
+    return tap_redist(c, contig, which, dist_limbs, cap_words);
 }
 
 int phx_tap_pindist(phx_ctx *c, int32_t contig, int32_t which, uint64_t *dist_limbs, int64_t cap_words, int32_t *words_per_node) {
     TAP_PRE(c, contig);
     if (which != 0 && which != 1) return PHX_E_ARG;
     if (!c->done.reann) { c->err = "phx_tap_pindist: no re-annotation of this run (call phx_constrain_flat or phx_curate_flat first)"; return PHX_E_STATE; }
-    const bool pinned = re_mode_req(c->h_qsel[(size_t)contig]);
-    if (words_per_node) *words_per_node = m.sssp_nl + (pinned ? 1 : 0);
-    if (!pinned) return tap_redist_plain(c, contig, which, dist_limbs, cap_words);
-    const size_t nl = (size_t)m.sssp_nl + 1, words = (size_t)m.n_node * nl;
-    if (!dist_limbs || cap_words < (int64_t)words) return PHX_E_ARG;
-    if (which) { const int rm = ensure_pinmargins(c); if (rm) return rm; }
-    const bool have = which ? (c->h_psel[(size_t)contig] == 1 && !c->pmstat[(size_t)contig]) : c->h_qrec[(size_t)contig].status >= 0;
-    if (!have) { // no such vector (the re-solve ended with an error; no path, so no d_t'): every node unreached
-        for (size_t v = 0; v < (size_t)m.n_node; v++) for (size_t k = 0; k < nl; k++) dist_limbs[v * nl + k] = k + 1 == nl ? WINF_TOP_HOST : 0;
-        return PHX_OK;
-    }
-    const uint64_t *from = which ? (const uint64_t *)c->b_pdt.p + (size_t)m.node_off * (size_t)(c->n_limbs + 1) : (const uint64_t *)c->b_qdist.p + (size_t)m.node_off * (size_t)c->qstride;
-    HIPCHK(c, hipMemcpy(dist_limbs, from, words * 8, hipMemcpyDeviceToHost));
+    if (words_per_node) *words_per_node = m.sssp_nl + (re_mode_req(c->h_qsel[(size_t)contig]) ? 1 : 0);
+    return tap_redist(c, contig, which, dist_limbs, cap_words);
+}
+
+int phx_remargins_ms(phx_ctx *c, float *ms) {
+    if (!c || !ms) return PHX_E_ARG;
+    for (int k = 0; k < 4; k++) ms[k] = c->xm.ms[k];
     return PHX_OK;
 }
 
 int phx_pinmargins_ms(phx_ctx *c, float *ms) {
     if (!c || !ms) return PHX_E_ARG;
-    for (int k = 0; k < 4; k++) ms[k] = c->pinmarg_ms[k];
+    for (int k = 0; k < 4; k++) ms[k] = c->pm.ms[k];
     return PHX_OK;
 }
 
@@ -1201,14 +1159,14 @@ static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const
         if (n_pin) HIPCHK(c, hipMemcpyAsync(c->b_sc_pin.p, pin.data(), ns * 16, hipMemcpyHostToDevice, s));
         if (!trips.empty()) HIPCHK(c, hipMemcpyAsync(c->b_sc_trip.p, trips.data(), trips.size() * sizeof(DScTrip), hipMemcpyHostToDevice, s));
         c->h_schunk.assign(ns, DReannRec{});
-        DTotals &tot = c->h_stot;
-        uint32_t &gtot = c->h_sgtot;
-        gtot = 0;
+        // the slots' view of the batch: the run's graph and records (read only), totals / genes / counter / tie scratch of the scenarios' own
+        DBatch b;
+        DScen q;
+        const int n_range[3] = {(int)n_plain, (int)n_pin, (int)n_ev}, nlms[3] = {nlm, pinm, evm}; // the plain head, the pinned middle and the biased tail of the slot table
+        const size_t base = c->h_sgenes.size();
+        const ReSolve R{"scenarios", "slot", c->b_sc_tot, c->b_sc_gtot, c->b_sc_tie, c->b_sc_rec, c->b_sc_genes, c->h_stot, c->h_sgtot, c->h_schunk.data(), ns, nodes + ns, c->h_sgenes};
         float ms[3] = {0, 0, 0};
-        for (int attempt = 0;; attempt++) {
-            // the slots' view of the batch: the run's graph and records (read only), totals / genes / counter / tie scratch of the scenarios' own
-            DBatch b;
-            DScen q;
+        rc = resolve_attempts(c, R, ms, [&](int) -> int {
             resolve_batch(c, &b, c->b_sc_tot, c->b_sc_genes, c->b_sc_gtot, c->b_sc_tie);
             q.slot = (const DScSlot *)c->b_sc_slot.p; q.pair = (const int2 *)c->b_sc_pair.p; q.n_pair = (int64_t)pairs.size(); q.n_slot = (int32_t)ns;
             q.stride0 = c->n_limbs; q.meta = (DMeta *)c->b_sc_meta.p; q.dist = (uint64_t *)c->b_sc_dist.p; q.parent = (int32_t *)c->b_sc_parent.p;
@@ -1224,41 +1182,19 @@ static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const
                 q.bbit = q.mask + (mwords + 2 + rwords + 2); q.bs = (DScBias *)c->b_sc_bs.p; q.blist = (long long *)c->b_sc_blist.p;
                 q.bstage = q.blist + 2 * (trips.size() + 1); q.trip = (const DScTrip *)c->b_sc_trip.p; q.n_trip = (int64_t)trips.size();
             }
-            const int n_range[3] = {(int)n_plain, (int)n_pin, (int)n_ev}, nlms[3] = {nlm, pinm, evm}; // the plain head, the pinned middle and the biased tail of the slot table
-            HIPCHK(c, hipEventRecord(c->aev[0], s));
-            HIPCHK(c, hipMemsetAsync(c->b_sc_tot.p, 0, sizeof(DTotals), s));
-            HIPCHK(c, hipMemsetAsync(c->b_sc_gtot.p, 0, 16, s));
             HIPCHK(c, hipMemsetAsync(c->b_sc_mask.p, 0, (mwords + 2 + (n_pin || n_ev ? rwords + 2 : 0) + (n_ev ? bwords + 2 : 0)) * 4, s));
             if (n_ev) HIPCHK(c, hipMemcpyAsync(c->b_sc_bs.p, bsv.data(), ns * sizeof(DScBias), hipMemcpyHostToDevice, s)); // (counts and sums at zero: k_sce_mask appends again, also on a tie-scratch retry)
             if (n_pin) HIPCHK(c, hipMemsetAsync(q.kreq, 0, ns * 4, s)); // k_scp_mask counts again (also on a tie-scratch retry)
-            phxk_scen_mask(&b, &q, n_range, max_list, s);
-            HIPCHK(c, hipEventRecord(c->aev[1], s));
-            phxk_scen_solve(&b, &q, n_range, nlms, s);
-            HIPCHK(c, hipEventRecord(c->aev[2], s));
-            phxk_scen_finish(&b, &q, n_range, nlms, s);
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipMemcpyAsync(c->h_schunk.data(), c->b_sc_rec.p, ns * sizeof(DReannRec), hipMemcpyDeviceToHost, s));
-            HIPCHK(c, hipEventRecord(c->aev[3], s));
-            HIPCHK(c, hipMemcpyAsync(&tot, c->b_sc_tot.p, sizeof(DTotals), hipMemcpyDeviceToHost, s));
-            HIPCHK(c, hipMemcpyAsync(&gtot, c->b_sc_gtot.p, 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(c, hipStreamSynchronize(s));
-            ms[0] = ev_ms(c->aev[0], c->aev[1]); ms[1] = ev_ms(c->aev[1], c->aev[2]); ms[2] = ev_ms(c->aev[2], c->aev[3]);
-            if (!(tot.overflow & 4)) break;
-            // the tie scratch was too small for the slots with equal-length alternatives: grow it and solve the chunk again (as reann_compute)
-            if (attempt >= 2) { c->err = "scenarios: the tie scratch did not settle"; return PHX_E_STATE; }
-            if ((rc = ensure(c, c->b_sc_tie, (size_t)tot.tie_need + (size_t)tot.tie_need / 4 + 4096))) return rc;
-        }
-        if ((size_t)gtot > nodes + ns) { c->err = "scenarios: gene records beyond the buffer"; return PHX_E_STATE; }
-        const size_t base = c->h_sgenes.size();
-        c->h_sgenes.resize(base + gtot);
-        HIPCHK(c, hipEventRecord(c->aev[4], s));
-        if (gtot) HIPCHK(c, hipMemcpyAsync(c->h_sgenes.data() + base, c->b_sc_genes.p, (size_t)gtot * sizeof(DGene), hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipEventRecord(c->aev[5], s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        c->scen_ms[0] += ms[0]; c->scen_ms[1] += ms[1]; c->scen_ms[2] += ms[2] + ev_ms(c->aev[4], c->aev[5]);
+            return PHX_OK;
+        }, [&](int step) {
+            if (step == 0) phxk_scen_mask(&b, &q, n_range, max_list, s);
+            else if (step == 1) phxk_scen_solve(&b, &q, n_range, nlms, s);
+            else phxk_scen_finish(&b, &q, n_range, nlms, s);
+        });
+        if (rc) return rc;
+        for (int k = 0; k < 3; k++) c->scen_ms[k] += ms[k];
         for (size_t k = 0; k < ns; k++) {
             DReannRec r = c->h_schunk[k];
-            if (r.n_genes < 0 || r.gene_off < 0 || (uint64_t)r.gene_off + (uint64_t)r.n_genes > (uint64_t)gtot) { c->err = "scenarios: a slot's gene records lie outside the buffer"; return PHX_E_STATE; }
             r.gene_off += (int64_t)base;
             c->h_srec[(size_t)which[k]] = r;
             c->h_sslot[(size_t)which[k]] = slots[k];
@@ -1280,11 +1216,7 @@ static int scen_flat(phx_ctx *c, const char *who, int64_t n_scen, const int32_t 
     try {
     // ---- argument checks, all before any kernel: nothing from the caller indexes device memory unchecked ----
     int64_t acc = 0;
-    for (int i = 0; i < c->n; i++) {
-        if (orf_offsets[i] != acc) return PHX_E_ARG;
-        if (reann_status(c, i) >= 0) acc += c->meta[(size_t)i].n_orf;
-    }
-    if (c->n > 0 && orf_offsets[c->n] != acc) return PHX_E_ARG;
+    if (!orf_offsets_ok(c, orf_offsets, &acc)) return PHX_E_ARG;
     const size_t S = (size_t)n_scen;
     for (int pass = 0; pass < 3; pass++) { // the refused lists, then the required ones, then the biased ones
         const int64_t *off = pass == 2 ? bias_off_in : pass ? req_off_in : scen_off;
@@ -1384,23 +1316,14 @@ static int scen_flat(phx_ctx *c, const char *who, int64_t n_scen, const int32_t 
         c->done.scen = true;
     }
     // ---- the caller's layout: per scenario what phx_reannotate_flat / phx_constrain_flat reports for its contig ----
+    auto rec_of = [&](size_t j) { return c->h_srec[j].status != SC_NOSLOT ? &c->h_srec[j] : nullptr; }; // (no slot: the run's result, as the sibling delivers it)
     int64_t total = 0;
     bool run_genes = false;
     for (size_t j = 0; j < S; j++) {
-        const int i = scen_contig[j];
-        const int32_t st = reann_status(c, i);
-        offsets[j] = total; status[j] = st; delta[j] = std::numeric_limits<double>::infinity();
-        if (unmet) unmet[j] = (int32_t)(rq_off[j + 1] - rq_off[j]); // (no result: every required ORF is unmet)
-        if (st < 0) continue;
-        const DReannRec &r = c->h_srec[j];
-        if (r.status != SC_NOSLOT) {
-            status[j] = r.status; delta[j] = r.delta;
-            if (unmet) unmet[j] = r.unmet;
-            if (r.status >= 0) total += r.n_genes;
-        } else { // not solved again: the run's result, as the sibling delivers it
-            if (st != PHX_S_NOPATH) delta[j] = 0.0;
-            if (c->res[(size_t)i].n_genes > 0) { total += c->res[(size_t)i].n_genes; run_genes = true; }
-        }
+        offsets[j] = total;
+        const int64_t k = resolve_entry(c, scen_contig[j], rec_of(j), rq_off[j + 1] - rq_off[j], status + j, delta + j, unmet ? unmet + j : nullptr);
+        run_genes = run_genes || (k > 0 && !rec_of(j));
+        total += k;
     }
     offsets[S] = total;
     if (total_out) *total_out = total;
@@ -1410,9 +1333,7 @@ static int scen_flat(phx_ctx *c, const char *who, int64_t n_scen, const int32_t 
     for (size_t j = 0; j < S; j++) {
         const int64_t k = offsets[j + 1] - offsets[j];
         if (k <= 0) continue;
-        const DReannRec &r = c->h_srec[j];
-        const DGene *src = r.status != SC_NOSLOT ? c->h_sgenes.data() + r.gene_off : (const DGene *)c->h_genes.p + (size_t)c->res[(size_t)scen_contig[j]].gene_off;
-        memcpy(genes + offsets[j], src, sizeof(phx_gene) * (size_t)k);
+        memcpy(genes + offsets[j], resolve_genes(c, scen_contig[j], rec_of(j), c->h_sgenes), sizeof(phx_gene) * (size_t)k);
     }
     } catch (const std::bad_alloc &) { c->err = std::string("out of memory in ") + who; return PHX_E_NOMEM; }
     return PHX_OK;

@@ -239,8 +239,8 @@ struct phx_ctx {
         bool repl = false;    // h_rrec / h_rgenes / h_rdet
         bool reann = false;   // h_q* hold the re-annotation for the mask h_qforb / h_qflags
         bool scen = false;    // h_s* hold the scenario batch h_skey
-        bool remarg = false;  // h_xrec / xmstat hold the margins of the re-annotation h_q* hold (also reset by every re-annotation solve)
-        bool pinmarg = false; // h_prec / h_plost / pmstat hold the pinned margins of the re-annotation h_q* hold (reset wherever remarg is)
+        bool remarg = false;  // xm.h_rec / xm.mstat hold the margins of the re-annotation h_q* hold (also reset by every re-annotation solve)
+        bool pinmarg = false; // pm.h_rec / pm.h_lost / pm.mstat hold the pinned margins of the re-annotation h_q* hold (reset wherever remarg is)
         bool grp = false;     // h_grp
     } done;
     std::vector<DGrp> h_grp;         // the run's group records (device order <-> reference order of the ORFs: each_group_in_reference_order)
@@ -285,19 +285,17 @@ struct phx_ctx {
     DTotals h_qtot;                   //   an early error return never points at memory that has gone out of scope
     uint32_t h_qgtot = 0;
     float reann_ms[3] = {0, 0, 0};
-    // re-annotation margins (phx_remargins_flat): buffers of their own, allocated at the first call; the result kept until the next re-annotation solve or run
-    DevBuf b_xsel, b_xbit, b_xbval, b_xdt, b_xrec, b_xmstat;
-    std::vector<int32_t> h_xsel;      // per contig: DRmarg.sel as uploaded
-    std::vector<int32_t> xmstat;      // per contig: the conditioned reverse pass hit its caps
-    std::vector<phx_orf_margin> h_xrec; // the device's records of the contigs in h_xsel (device ORF order, at orf_off)
-    float remarg_ms[4] = {0, 0, 0, 0};
-    // pinned margins (phx_pinmargins_flat): the same for the contigs solved under the required policy, values one limb wider; allocated at the first call that has such a contig
-    DevBuf b_psel, b_pbit, b_pbval, b_pdt, b_prec, b_plost, b_pmstat;
-    std::vector<int32_t> h_psel;      // per contig: DPmarg.sel as uploaded
-    std::vector<int32_t> pmstat;      // per contig: the pinned reverse pass hit its caps
-    std::vector<phx_orf_margin> h_prec; // the device's records of the contigs in h_psel (device ORF order, at orf_off) ...
-    std::vector<int32_t> h_plost;     // ... and their `lost`
-    float pinmarg_ms[4] = {0, 0, 0, 0};
+    // The conditioned margins (ensure_condmargins): buffers of their own, allocated at the first call that has a contig for them; the result
+    // kept until the next re-annotation solve or run.  xm: the re-annotation margins (phx_remargins_flat); pm: the pinned
+    // margins (phx_pinmargins_flat, §24) — the same for the contigs solved under the required policy, values one limb wider, with `lost`.
+    struct CondMarg {
+        DevBuf b_sel, b_bit, b_bval, b_dt, b_rec, b_lost, b_mstat;
+        std::vector<int32_t> h_sel;      // per contig: DRmarg.sel / DPmarg.sel as uploaded
+        std::vector<int32_t> mstat;      // per contig: the conditioned reverse pass hit its caps
+        std::vector<phx_orf_margin> h_rec; // the device's records of the contigs in h_sel (device ORF order, at orf_off) ...
+        std::vector<int32_t> h_lost;     // ... and their `lost` (pm alone)
+        float ms[4] = {0, 0, 0, 0};      // phx_remargins_ms / phx_pinmargins_ms
+    } xm, pm;
     // scenario batches (phx_scenarios_flat): buffers of their own, allocated at the first call; the result kept until the next upload or run
     DevBuf b_sc_slot, b_sc_pair, b_sc_meta, b_sc_dist, b_sc_parent, b_sc_path, b_sc_mask, b_sc_plan, b_sc_genes, b_sc_rec, b_sc_tot, b_sc_gtot, b_sc_tie, b_sc_pin, b_sc_bs, b_sc_trip, b_sc_blist;
     int64_t scen_budget = (int64_t)2 << 30; // device bytes of a chunk's slots (env PHX_SCEN_BYTES at phx_create)

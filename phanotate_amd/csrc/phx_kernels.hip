@@ -185,6 +185,16 @@ __device__ __forceinline__ int min_idx(int a, int b, int c) { return a > b ? (b 
 
 // ------------------------------------------------------------------------------------------------
 // launchers
+// fn(std::integral_constant<int, NL>) for every limb class of nlm (bit k: 2, 4, 8, 17 limbs), in that order: the one place that turns a
+// mask of classes into launches of K<NL>
+template <class F>
+static void each_limb_class(int nlm, F fn) {
+    if (nlm & 1) fn(std::integral_constant<int, 2>());
+    if (nlm & 2) fn(std::integral_constant<int, 4>());
+    if (nlm & 4) fn(std::integral_constant<int, 8>());
+    if (nlm & 8) fn(std::integral_constant<int, 17>());
+}
+static int limb_class_bit(int nl) { return nl == 2 ? 1 : nl == 4 ? 2 : nl == 8 ? 4 : 8; } // ... and the mask of the one class nl (any other count: 17 limbs)
 template <int NL>
 static void launch_certify(const DBatch *b, int vcap, hipStream_t s) {
     const size_t lds = (size_t)vcap * 12 + 16;
@@ -198,6 +208,21 @@ static void launch_lds(void (*k)(A...), size_t lds, unsigned grid, hipStream_t s
     (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(k, dim3(grid), dim3(SW_THREADS), lds, s, args...);
 }
+// k_sssp_wave<NL, CFG>, a wavefront per contig, with its dynamic LDS; beside: its variant that follows the counter of the planner it is
+// launched beside (FOLLOWS: the configuration has one — the roomy 128-bit one has not, and none is to be instantiated)
+template <int NL, int CFG, bool FOLLOWS>
+static void launch_wave(const DBatch *b, bool beside, hipStream_t s) {
+    const size_t lb = wv_lds_bytes<NL, CFG>();
+    (void)hipFuncSetAttribute((const void *)k_sssp_wave<NL, CFG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
+    if constexpr (FOLLOWS) {
+        if (beside) {
+            (void)hipFuncSetAttribute((const void *)k_sssp_wave<NL, CFG, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
+            hipLaunchKernelGGL((k_sssp_wave<NL, CFG, true>), dim3(b->n_contig), dim3(64), lb, s, *b);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((k_sssp_wave<NL, CFG>), dim3(b->n_contig), dim3(64), lb, s, *b);
+}
 // The re-annotation's two solver kernels by what they are launched on: DReann — the batch, a workgroup per contig —, DScen — a range of a
 // chunk's slot table, a workgroup per slot (phx_resolve.inc).
 template <int NL, class Pol> static auto re_lds_kernel(const DReann *) { return k_rs_lds<NL, Pol>; }
@@ -208,18 +233,12 @@ template <int NL, int T, class Pol> static auto re_inorder_kernel(const DScen *)
 template <class Pol, class Q>
 static void re_solve(const DBatch *b, const Q *q, unsigned grid, int nlm, hipStream_t s) {
     if (!grid) return;
-    if (nlm & 1) launch_lds(re_lds_kernel<2, Pol>(q), ReSw<2, Pol>::LDS, grid, s, *b, *q);
-    if (nlm & 2) launch_lds(re_lds_kernel<4, Pol>(q), ReSw<4, Pol>::LDS, grid, s, *b, *q);
-    if (nlm & 4) launch_lds(re_lds_kernel<8, Pol>(q), ReSw<8, Pol>::LDS, grid, s, *b, *q);
-    if (nlm & 8) launch_lds(re_lds_kernel<17, Pol>(q), ReSw<17, Pol>::LDS, grid, s, *b, *q);
+    each_limb_class(nlm, [&](auto nl) { launch_lds(re_lds_kernel<decltype(nl)::value, Pol>(q), ReSw<decltype(nl)::value, Pol>::LDS, grid, s, *b, *q); });
 }
 // ... and the in-order pass: as phxk_inorder, one wavefront per short contig, else 256 threads
 template <int T, class Pol, class Q>
 static void re_inorder_t(const DBatch *b, const Q *q, unsigned grid, int nlm, hipStream_t s) {
-    if (nlm & 1) hipLaunchKernelGGL((re_inorder_kernel<2, T, Pol>(q)), dim3(grid), dim3(T), 0, s, *b, *q);
-    if (nlm & 2) hipLaunchKernelGGL((re_inorder_kernel<4, T, Pol>(q)), dim3(grid), dim3(T), 0, s, *b, *q);
-    if (nlm & 4) hipLaunchKernelGGL((re_inorder_kernel<8, T, Pol>(q)), dim3(grid), dim3(T), 0, s, *b, *q);
-    if (nlm & 8) hipLaunchKernelGGL((re_inorder_kernel<17, T, Pol>(q)), dim3(grid), dim3(T), 0, s, *b, *q);
+    each_limb_class(nlm, [&](auto nl) { hipLaunchKernelGGL((re_inorder_kernel<decltype(nl)::value, T, Pol>(q)), dim3(grid), dim3(T), 0, s, *b, *q); });
 }
 template <class Pol, class Q>
 static void re_inorder_launch(const DBatch *b, const Q *q, unsigned grid, int nlm, hipStream_t s) {
@@ -323,7 +342,7 @@ void phxk_edges_tap(const DBatch *b, void *stream) { hipLaunchKernelGGL((k_edges
 // phx_solve: relaxation, path walk (no genes: DBatch.genes is null), in-order parents
 void phxk_sssp_only(const DBatch *b, int nl, void *stream) {
     phxk_sssp(b, nl, 0, 0, stream);
-    phxk_inorder(b, nl == 2 ? 1 : nl == 4 ? 2 : nl == 8 ? 4 : 8, stream);
+    phxk_inorder(b, limb_class_bit(nl), stream);
 }
 
 // nl_mask: bit k set = some contig of the batch has 2 / 4 / 8 / 17 limbs (k = 0..3)
@@ -335,17 +354,8 @@ void phxk_inorder(const DBatch *b, int nl_mask, void *stream) {
     const bool small = b->mean_len < 8192;
     const bool big = (b->n_contig <= 64 && b->mean_len >= 65536) || (b->n_contig <= 8 && b->mean_len >= 16384); // a handful of long contigs (or a few of any length: Lambda): the chip is empty, a contig's one workgroup may as well be a large one — and its path walk goes in strides
     if (big && (nl_mask & 1)) { hipLaunchKernelGGL((k_inorder<2, IO_T_BIG>), g, dim3(IO_T_BIG), 0, s, *b); nl_mask &= ~1; }
-    if (small) {
-        if (nl_mask & 1) hipLaunchKernelGGL((k_inorder<2, 64>), g, dim3(64), 0, s, *b);
-        if (nl_mask & 2) hipLaunchKernelGGL((k_inorder<4, 64>), g, dim3(64), 0, s, *b);
-        if (nl_mask & 4) hipLaunchKernelGGL((k_inorder<8, 64>), g, dim3(64), 0, s, *b);
-        if (nl_mask & 8) hipLaunchKernelGGL((k_inorder<17, 64>), g, dim3(64), 0, s, *b);
-    } else {
-        if (nl_mask & 1) hipLaunchKernelGGL((k_inorder<2, IO_T_FULL>), g, dim3(IO_T_FULL), 0, s, *b);
-        if (nl_mask & 2) hipLaunchKernelGGL((k_inorder<4, IO_T_FULL>), g, dim3(IO_T_FULL), 0, s, *b);
-        if (nl_mask & 4) hipLaunchKernelGGL((k_inorder<8, IO_T_FULL>), g, dim3(IO_T_FULL), 0, s, *b);
-        if (nl_mask & 8) hipLaunchKernelGGL((k_inorder<17, IO_T_FULL>), g, dim3(IO_T_FULL), 0, s, *b);
-    }
+    if (small) each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_inorder<decltype(nl)::value, 64>), g, dim3(64), 0, s, *b); });
+    else each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_inorder<decltype(nl)::value, IO_T_FULL>), g, dim3(IO_T_FULL), 0, s, *b); });
 }
 
 // vmax: the largest node count the batch is expected to hold (the last run's): sizes the LDS tables of k_certify (12 bytes per node, at
@@ -355,10 +365,7 @@ void phxk_certify(const DBatch *b, int nl_mask, int vmax, void *stream) {
     int vcap = ((vmax > 1024 ? vmax : 1024) + 255) & ~255;
     if (vcap > 12288) vcap = 12288;
     if (vmax < 0) vcap = 0; // (test switch: everything to k_certify_wide)
-    if (nl_mask & 1) launch_certify<2>(b, vcap, s);
-    if (nl_mask & 2) launch_certify<4>(b, vcap, s);
-    if (nl_mask & 4) launch_certify<8>(b, vcap, s);
-    if (nl_mask & 8) launch_certify<17>(b, vcap, s);
+    each_limb_class(nl_mask, [&](auto nl) { launch_certify<decltype(nl)::value>(b, vcap, s); });
 }
 
 void phxk_refine(const DBatch *b, void *stream) {
@@ -413,49 +420,55 @@ void phxk_margins_transpose(const DBatch *b, const DMarg *g, void *stream) {
     hipLaunchKernelGGL(k_mg_scan, dim3(b->n_contig), dim3(NT), 0, s, *b, *g);
     hipLaunchKernelGGL(k_mg_fill, dim3(b->n_contig, y), dim3(NT), 0, s, *b, *g);
 }
-// K<n_limbs> on stream s for every limb class of NLM (bit k: 2, 4, 8, 17 limbs)
-#define NL_LAUNCH(K, NLM, GRID, BLOCK, ...) do { \
-        if ((NLM) & 1) hipLaunchKernelGGL(K<2>, GRID, BLOCK, 0, s, __VA_ARGS__); \
-        if ((NLM) & 2) hipLaunchKernelGGL(K<4>, GRID, BLOCK, 0, s, __VA_ARGS__); \
-        if ((NLM) & 4) hipLaunchKernelGGL(K<8>, GRID, BLOCK, 0, s, __VA_ARGS__); \
-        if ((NLM) & 8) hipLaunchKernelGGL(K<17>, GRID, BLOCK, 0, s, __VA_ARGS__); \
-    } while (0)
-void phxk_sssp_rev(const DBatch *b, const DMarg *g, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH(k_sssp_rev, nl_mask, dim3(b->n_contig), dim3(NT), *b, *g); }
-void phxk_margins(const DBatch *b, const DMarg *g, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH(k_margins, nl_mask, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), *b, *g); }
-// re-annotation margins (phx_margins.inc, §21): k_sssp_rev and k_margins under MgCond, whose DMarg part is the run's (the out-edge CSR)
-static MgCond mg_cond_args(const DMarg *g, const DReann *q, const DRmarg *r) { MgCond c; static_cast<DMarg &>(c) = *g; c.q = *q; c.r = *r; return c; }
-#define NL_LAUNCH_COND(K, NLM, GRID, BLOCK, ...) do { \
-        if ((NLM) & 1) hipLaunchKernelGGL((K<2, MgCond>), GRID, BLOCK, 0, s, __VA_ARGS__); \
-        if ((NLM) & 2) hipLaunchKernelGGL((K<4, MgCond>), GRID, BLOCK, 0, s, __VA_ARGS__); \
-        if ((NLM) & 4) hipLaunchKernelGGL((K<8, MgCond>), GRID, BLOCK, 0, s, __VA_ARGS__); \
-        if ((NLM) & 8) hipLaunchKernelGGL((K<17, MgCond>), GRID, BLOCK, 0, s, __VA_ARGS__); \
-    } while (0)
-void phxk_remarg_apply(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, void *stream) { hipLaunchKernelGGL(k_rmg_apply, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), 0, (hipStream_t)stream, *b, *g, *q, *r); }
-void phxk_remarg_rev(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH_COND(k_sssp_rev, nl_mask, dim3(b->n_contig), dim3(NT), *b, mg_cond_args(g, q, r)); }
-void phxk_remarg_records(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH_COND(k_margins, nl_mask, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), *b, mg_cond_args(g, q, r)); }
-// pinned margins (§24): the same under MgPin, for the contigs solved under the required policy
-static MgPin mg_pin_args(const DMarg *g, const DReann *q, const DPmarg *r) { MgPin c; static_cast<DMarg &>(c) = *g; c.q = *q; c.r = *r; return c; }
-#define NL_LAUNCH_PIN(K, NLM, GRID, BLOCK, ...) do { \
-        if ((NLM) & 1) hipLaunchKernelGGL((K<2, MgPin>), GRID, BLOCK, 0, s, __VA_ARGS__); \
-        if ((NLM) & 2) hipLaunchKernelGGL((K<4, MgPin>), GRID, BLOCK, 0, s, __VA_ARGS__); \
-        if ((NLM) & 4) hipLaunchKernelGGL((K<8, MgPin>), GRID, BLOCK, 0, s, __VA_ARGS__); \
-        if ((NLM) & 8) hipLaunchKernelGGL((K<17, MgPin>), GRID, BLOCK, 0, s, __VA_ARGS__); \
-    } while (0)
-void phxk_pinmarg_apply(const DBatch *b, const DMarg *g, const DReann *q, const DPmarg *r, void *stream) { hipLaunchKernelGGL(k_pmg_apply, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), 0, (hipStream_t)stream, *b, *g, *q, *r); }
-void phxk_pinmarg_rev(const DBatch *b, const DMarg *g, const DReann *q, const DPmarg *r, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH_PIN(k_sssp_rev, nl_mask, dim3(b->n_contig), dim3(NT), *b, mg_pin_args(g, q, r)); }
-void phxk_pinmarg_records(const DBatch *b, const DMarg *g, const DReann *q, const DPmarg *r, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH_PIN(k_margins, nl_mask, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), *b, mg_pin_args(g, q, r)); }
+void phxk_sssp_rev(const DBatch *b, const DMarg *g, int nl_mask, void *stream) {
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL(k_sssp_rev<decltype(nl)::value>, dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, *g); });
+}
+void phxk_margins(const DBatch *b, const DMarg *g, int nl_mask, void *stream) {
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL(k_margins<decltype(nl)::value>, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), 0, (hipStream_t)stream, *b, *g); });
+}
+}
+// The conditioned margins (phx_margins.inc): k_sssp_rev and k_margins under a policy Mg whose DMarg part is the run's (the out-edge CSR) —
+// MgCond with DRmarg for the re-annotation margins (§21), MgPin with DPmarg for the contigs solved under the required policy (§24) —
+// behind the policy's own apply kernel.
+template <class Mg, class R> static Mg mg_args(const DMarg *g, const DReann *q, const R *r) { Mg c; static_cast<DMarg &>(c) = *g; c.q = *q; c.r = *r; return c; }
+static auto mg_apply_kernel(const DRmarg *) { return k_rmg_apply; }
+static auto mg_apply_kernel(const DPmarg *) { return k_pmg_apply; }
+template <class R> static void mg_apply(const DBatch *b, const DMarg *g, const DReann *q, const R *r, void *stream) {
+    hipLaunchKernelGGL(mg_apply_kernel(r), dim3(b->n_contig, ysplit(b, 8)), dim3(NT), 0, (hipStream_t)stream, *b, *g, *q, *r);
+}
+template <class Mg, class R> static void mg_rev(const DBatch *b, const DMarg *g, const DReann *q, const R *r, int nl_mask, void *stream) {
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_sssp_rev<decltype(nl)::value, Mg>), dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, mg_args<Mg>(g, q, r)); });
+}
+template <class Mg, class R> static void mg_records(const DBatch *b, const DMarg *g, const DReann *q, const R *r, int nl_mask, void *stream) {
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_margins<decltype(nl)::value, Mg>), dim3(b->n_contig, ysplit(b, 8)), dim3(NT), 0, (hipStream_t)stream, *b, mg_args<Mg>(g, q, r)); });
+}
+extern "C" {
+void phxk_remarg_apply(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, void *stream) { mg_apply(b, g, q, r, stream); }
+void phxk_remarg_rev(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, int nl_mask, void *stream) { mg_rev<MgCond>(b, g, q, r, nl_mask, stream); }
+void phxk_remarg_records(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, int nl_mask, void *stream) { mg_records<MgCond>(b, g, q, r, nl_mask, stream); }
+void phxk_pinmarg_apply(const DBatch *b, const DMarg *g, const DReann *q, const DPmarg *r, void *stream) { mg_apply(b, g, q, r, stream); }
+void phxk_pinmarg_rev(const DBatch *b, const DMarg *g, const DReann *q, const DPmarg *r, int nl_mask, void *stream) { mg_rev<MgPin>(b, g, q, r, nl_mask, stream); }
+void phxk_pinmarg_records(const DBatch *b, const DMarg *g, const DReann *q, const DPmarg *r, int nl_mask, void *stream) { mg_records<MgPin>(b, g, q, r, nl_mask, stream); }
 // gene drop margins (phx_drop.inc): a workgroup per contig, one launch per limb class and step
-void phxk_drop_trees(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH(k_dp_tree, nl_mask, dim3(b->n_contig), dim3(NT), *b, *g, *q); }
-void phxk_drop_cand(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH(k_dp_cand, nl_mask, dim3(b->n_contig), dim3(NT), *b, *g, *q); }
+void phxk_drop_trees(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream) {
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL(k_dp_tree<decltype(nl)::value>, dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, *g, *q); });
+}
+void phxk_drop_cand(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream) {
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL(k_dp_cand<decltype(nl)::value>, dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, *g, *q); });
+}
 void phxk_drop_fix(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream) {
     hipStream_t s = (hipStream_t)stream;
-    NL_LAUNCH(k_dp_rescan, nl_mask, dim3(b->n_contig), dim3(NT), *b, *g, *q);
-    NL_LAUNCH(k_dp_cross, nl_mask, dim3(b->n_contig), dim3(NT), *b, *g, *q);
-    NL_LAUNCH(k_dp_rec, nl_mask, dim3(b->n_contig), dim3(NT), *b, *g, *q);
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL(k_dp_rescan<decltype(nl)::value>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q); });
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL(k_dp_cross<decltype(nl)::value>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q); });
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL(k_dp_rec<decltype(nl)::value>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q); });
 }
 // drop replacements (phx_replace.inc): a workgroup per contig
-void phxk_repl_pick(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH(k_rp_pick, nl_mask, dim3(b->n_contig), dim3(NT), *b, *g, *q, *r); }
-void phxk_repl_cross(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream) { hipStream_t s = (hipStream_t)stream; NL_LAUNCH(k_rp_cross, nl_mask, dim3(b->n_contig), dim3(NT), *b, *g, *q, *r); }
+void phxk_repl_pick(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream) {
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL(k_rp_pick<decltype(nl)::value>, dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, *g, *q, *r); });
+}
+void phxk_repl_cross(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream) {
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL(k_rp_cross<decltype(nl)::value>, dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, *g, *q, *r); });
+}
 void phxk_repl_walk(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int fill, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     if (fill) hipLaunchKernelGGL(k_rp_walk<1>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q, *r);
@@ -552,53 +565,21 @@ void phxk_sssp(const DBatch *b, int nl, int mode, size_t lds_bytes, void *stream
             else if (b->seg) hipLaunchKernelGGL((k_sssp_duo<0, false, true>), dim3(b->n_contig * b->seg), t2, 0, s, *b); // a wavefront pair per segment (phx_sssp_seg.inc)
             else if (b->plan_stream == 2) hipLaunchKernelGGL((k_sssp_duo<0, true>), g, t2, 0, s, *b);
             else hipLaunchKernelGGL((k_sssp_duo<0, false>), g, t2, 0, s, *b);
-        } else if (nl == 2 && mode == 2) {
-            const size_t lb = wv_lds_bytes<2, 0>();
-            (void)hipFuncSetAttribute((const void *)k_sssp_wave<2, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
-            if (b->plan_stream == 2) { // small batches: beside k_wave_plan<2,0>, following its counter
-                (void)hipFuncSetAttribute((const void *)k_sssp_wave<2, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
-                hipLaunchKernelGGL((k_sssp_wave<2, 0, true>), g, dim3(64), lb, s, *b);
-            } else
-            hipLaunchKernelGGL((k_sssp_wave<2, 0>), g, dim3(64), lb, s, *b);
-        } else if (nl == 2) {
-            const size_t lb = wv_lds_bytes<2, 1>();
-            (void)hipFuncSetAttribute((const void *)k_sssp_wave<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
-            hipLaunchKernelGGL((k_sssp_wave<2, 1>), g, dim3(64), lb, s, *b);
-        } else if (nl == 4) {
-            const size_t lb = wv_lds_bytes<4, 1>();
-            (void)hipFuncSetAttribute((const void *)k_sssp_wave<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
-            if (b->plan_stream == 4) {
-                (void)hipFuncSetAttribute((const void *)k_sssp_wave<4, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
-                hipLaunchKernelGGL((k_sssp_wave<4, 1, true>), g, dim3(64), lb, s, *b);
-            } else
-            hipLaunchKernelGGL((k_sssp_wave<4, 1>), g, dim3(64), lb, s, *b);
-        } else {
-            const size_t lb = wv_lds_bytes<8, 1>();
-            (void)hipFuncSetAttribute((const void *)k_sssp_wave<8, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
-            if (b->plan_stream == 8) {
-                (void)hipFuncSetAttribute((const void *)k_sssp_wave<8, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
-                hipLaunchKernelGGL((k_sssp_wave<8, 1, true>), g, dim3(64), lb, s, *b);
-            } else
-            hipLaunchKernelGGL((k_sssp_wave<8, 1>), g, dim3(64), lb, s, *b);
-        }
+        } else if (nl == 2 && mode == 2) launch_wave<2, 0, true>(b, b->plan_stream == 2, s); // small batches: beside k_wave_plan<2,0>, following its counter
+        else if (nl == 2) launch_wave<2, 1, false>(b, false, s);
+        else if (nl == 4) launch_wave<4, 1, true>(b, b->plan_stream == 4, s);
+        else launch_wave<8, 1, true>(b, b->plan_stream == 8, s);
         return;
     }
     if (mode == 0) {
         dim3 gp((b->n_contig + 63) / 64), tp(64);
-        switch (nl) {
-        case 2: hipLaunchKernelGGL(k_sssp<2>, g, t, 0, s, *b); hipLaunchKernelGGL(k_path<2>, gp, tp, 0, s, *b); break;
-        case 4: hipLaunchKernelGGL(k_sssp<4>, g, t, 0, s, *b); hipLaunchKernelGGL(k_path<4>, gp, tp, 0, s, *b); break;
-        case 8: hipLaunchKernelGGL(k_sssp<8>, g, t, 0, s, *b); hipLaunchKernelGGL(k_path<8>, gp, tp, 0, s, *b); break;
-        default: hipLaunchKernelGGL(k_sssp<17>, g, t, 0, s, *b); hipLaunchKernelGGL(k_path<17>, gp, tp, 0, s, *b); break;
-        }
+        each_limb_class(limb_class_bit(nl), [&](auto c) {
+            hipLaunchKernelGGL(k_sssp<decltype(c)::value>, g, t, 0, s, *b);
+            hipLaunchKernelGGL(k_path<decltype(c)::value>, gp, tp, 0, s, *b);
+        });
         return;
     }
-    switch (nl) {
-    case 2: launch_lds(k_sssp_lds<2>, lds_bytes, (unsigned)b->n_contig, s, *b, mode, (int)lds_bytes); break;
-    case 4: launch_lds(k_sssp_lds<4>, lds_bytes, (unsigned)b->n_contig, s, *b, mode, (int)lds_bytes); break;
-    case 8: launch_lds(k_sssp_lds<8>, lds_bytes, (unsigned)b->n_contig, s, *b, mode, (int)lds_bytes); break;
-    default: launch_lds(k_sssp_lds<17>, lds_bytes, (unsigned)b->n_contig, s, *b, mode, (int)lds_bytes); break;
-    }
+    each_limb_class(limb_class_bit(nl), [&](auto c) { launch_lds(k_sssp_lds<decltype(c)::value>, lds_bytes, (unsigned)b->n_contig, s, *b, mode, (int)lds_bytes); });
 }
 }
 
