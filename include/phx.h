@@ -46,7 +46,8 @@ extern "C" {
  *        (addition, version unchanged) phx_pinned_scenarios_flat — probe for the symbol;
  *        (addition, version unchanged) phx_evidence_scenarios_flat — probe for the symbol;
  *        (additions, version unchanged) phx_remargins_flat, phx_remargins_ms, phx_tap_redist — probe for the symbol;
- *        (additions, version unchanged) phx_pinmargins_flat, phx_pinmargins_ms, phx_tap_pindist — probe for the symbol */
+ *        (additions, version unchanged) phx_pinmargins_flat, phx_pinmargins_ms, phx_tap_pindist — probe for the symbol;
+ *        (addition, version unchanged) phx_curate_scenarios_flat — probe for the symbol */
 #define PHX_MAX_CODONS 16
 
 /* library-level errors */
@@ -594,11 +595,33 @@ int phx_pinned_scenarios_flat(phx_ctx *ctx, int64_t n_scen, const int32_t *scen_
  * device-memory budget are those of phx_scenarios_flat; bias_off must not be NULL, and a summed |B| > 2^52 is PHX_E_ARG before any kernel.
  * It is one solve with the two calls above on one set of buffers, with one cached result keyed on the refused lists and the merged bias
  * lists: phx_scenarios_ms, phx_scenario_chunks and phx_tap_scenario_path, whose distance is then D_B, report on the last scenario solve of
- * any kind.  No required list per scenario.  (Addition, version unchanged: probe for the symbol.) */
+ * any kind.  No required list per scenario (since added: phx_curate_scenarios_flat below).  (Addition, version unchanged: probe for the symbol.) */
 int phx_evidence_scenarios_flat(phx_ctx *ctx, int64_t n_scen, const int32_t *scen_contig /* [n_scen] */, const int64_t *forbid_off /* [n_scen+1] */,
                                 const int32_t *forbid_orf, const int64_t *bias_off /* [n_scen+1] */, const int32_t *bias_orf, const int64_t *bias_val,
                                 const int64_t *orf_offsets /* [n+1] */, uint32_t flags /* reserved: 0 */, phx_gene *genes, int64_t cap,
                                 int64_t *offsets /* [n_scen+1] */, int32_t *status /* [n_scen] */, double *delta /* [n_scen] */, int64_t *total);
+/* ---- combined scenario batches: many combined re-annotations of the batch last run in one call ----
+ * All three lists per scenario: scenario j refuses F_j (forbid_*), requires R_j (require_*) and biases the ORFs of its (ORF, B) pairs
+ * (bias_*), each as in the two calls above.  It is, by definition, phx_curate_flat applied to contig scen_contig[j] with exactly that bias,
+ * that refused set, that required set and bit 0 of its flags set: status[j], delta[j], unmet[j] and genes[offsets[j] .. offsets[j+1]) are
+ * byte for byte that call's for the contig, and phx_tap_scenario_path returns the path and S(P) in the contig's own limbs as
+ * phx_tap_repath does after phx_curate_flat.  The order (-c(P), S(P)), the tie rule, PHX_S_NOPATH, PHX_S_NEGCYCLE of both kinds (a cycle
+ * the source reaches through a required edge, or one a bonus has made negative; never for a cycle the source does not reach),
+ * PHX_S_OVERFLOW from the limb-class test before the sweep and unmet = |R_j| wherever there is no result are those of DESIGN.md §22.
+ * An ORF may be required and biased, its bias then counts; a refused ORF's bias is ignored; duplicates in a required list count once,
+ * duplicate bias pairs are summed.  Per scenario the call reduces, by the same kernels and byte for byte, to
+ * phx_pinned_scenarios_flat's scenario when no summed bias outside F_j is non-zero, to phx_evidence_scenarios_flat's (unmet 0) when R_j
+ * is empty, and to phx_scenarios_flat's when both hold; one call may mix all four kinds.
+ * Calling convention, argument checks (on all three lists, all before any kernel; an ORF in F_j and R_j, or a summed |B| > 2^52, is
+ * PHX_E_ARG), state rules, chunking and the device-memory budget are those of the calls above; require_off, bias_off and unmet must not
+ * be NULL.  It is one solve with the three calls above on one set of buffers, with one cached result keyed on all three lists — a call
+ * is served from a sibling's cached result exactly when it reduces to it.  (Addition, version unchanged: probe for the symbol.) */
+int phx_curate_scenarios_flat(phx_ctx *ctx, int64_t n_scen, const int32_t *scen_contig /* [n_scen] */, const int64_t *forbid_off /* [n_scen+1] */,
+                              const int32_t *forbid_orf, const int64_t *require_off /* [n_scen+1] */, const int32_t *require_orf,
+                              const int64_t *bias_off /* [n_scen+1] */, const int32_t *bias_orf, const int64_t *bias_val,
+                              const int64_t *orf_offsets /* [n+1] */, uint32_t flags /* reserved: 0 */, phx_gene *genes, int64_t cap,
+                              int64_t *offsets /* [n_scen+1] */, int32_t *status /* [n_scen] */, double *delta /* [n_scen] */, int32_t *unmet /* [n_scen] */,
+                              int64_t *total);
 /* device time of the last scenario solve (of any kind), summed over its chunks, ms[3]: slot records + bitmap slices, masked solve, in-order parents +
  * path + genes + the copies to the host.  All 0 before the first. */
 int phx_scenarios_ms(phx_ctx *ctx, float *ms /* [3] */);

@@ -64,6 +64,12 @@ ALT_DT = np.dtype([("left", "i4"), ("right", "i4"), ("strand", "i4"), ("orf", "i
 # annotation loses / gains
 EVSCAN_DT = np.dtype([("left", "i4"), ("right", "i4"), ("strand", "i4"), ("orf", "i4"), ("bias", "f8"), ("status", "i4"), ("was_called", "i4"),
                       ("delta", "f8"), ("called", "i4"), ("n_removed", "i4"), ("n_added", "i4")], align=True)
+# Annotator.curated_scan(): EVSCAN_DT's fields for the ORF biased alone UNDER the contig's refused and required sets, plus unmet of that scenario and
+# status, delta and unmet of the contig's baseline scenario (the two sets, no bias).  was_called, n_removed and n_added are taken against the
+# baseline's genes, not the run's; delta stays relative to the run, as in every scenario
+CUSCAN_DT = np.dtype([("left", "i4"), ("right", "i4"), ("strand", "i4"), ("orf", "i4"), ("bias", "f8"), ("status", "i4"), ("was_called", "i4"),
+                      ("delta", "f8"), ("called", "i4"), ("n_removed", "i4"), ("n_added", "i4"), ("unmet", "i4"), ("base_status", "i4"),
+                      ("base_delta", "f8"), ("base_unmet", "i4")], align=True)
 EDGE_DT = np.dtype([("src", "i4"), ("dst", "i4"), ("w", "f8"), ("inexact", "i4"), ("pad", "i4"), ("d1", "f8"), ("d2", "f8"), ("err", "f8")], align=True)
 
 _lib = None
@@ -179,6 +185,7 @@ def lib():
         "phx_scenarios_flat": (C.c_int, [vp, i64, vp, vp, vp, vp, C.c_uint32, vp, i64, vp, vp, vp, P(i64)]),
         "phx_pinned_scenarios_flat": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, i64, vp, vp, vp, vp, P(i64)]),
         "phx_evidence_scenarios_flat": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, i64, vp, vp, vp, P(i64)]),
+        "phx_curate_scenarios_flat": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, i64, vp, vp, vp, vp, P(i64)]),
         "phx_scenarios_ms": (C.c_int, [vp, P(C.c_float)]),
         "phx_scenario_chunks": (C.c_int64, [vp]),
         "phx_tap_scenario_path": (C.c_int, [vp, i64, vp, i32, P(i32), vp, i32]),
@@ -226,6 +233,6 @@ EXPORTS = ["phx_version", "phx_device_count", "phx_strerror", "phx_last_error", 
            "phx_format_replacements",
            "phx_reannotate_flat", "phx_constrain_flat", "phx_evidence_flat", "phx_curate_flat", "phx_orf_offsets", "phx_tap_repath", "phx_reannotate_ms",
            "phx_scenarios_flat", "phx_scenarios_ms", "phx_scenario_chunks", "phx_tap_scenario_path", "phx_pinned_scenarios_flat",
-           "phx_evidence_scenarios_flat",
+           "phx_evidence_scenarios_flat", "phx_curate_scenarios_flat",
            "phx_remargins_flat", "phx_remargins_ms", "phx_tap_redist",
            "phx_pinmargins_flat", "phx_pinmargins_ms", "phx_tap_pindist"]

@@ -628,7 +628,7 @@ class Annotator:
         return self._genes_flat(self.L.phx_scenarios_flat, "phx_scenarios_flat", (S, _vp(contig), _vp(off), _vp(orf), _vp(oo), 0), S, False)
 
     def scenarios_ms(self):
-        """Device time of the last scenario solve (scenarios(), pinned_scenarios() or evidence_scenarios()) in ms, summed over its chunks: slot records + bitmaps, masked solve, path + genes + copy
+        """Device time of the last scenario solve (scenarios(), pinned_scenarios(), evidence_scenarios() or curate_scenarios()) in ms, summed over its chunks: slot records + bitmaps, masked solve, path + genes + copy
         (phx_scenarios_ms)."""
         return self._ms("phx_scenarios_ms")
 
@@ -637,8 +637,8 @@ class Annotator:
         return int(self.L.phx_scenario_chunks(self.h))
 
     def scenario_path(self, j, contig):
-        """(path as device node ids, its length D_F as a python int) of scenario j of the last scenarios(), pinned_scenarios() or evidence_scenarios()
-        call, like reannotated_path (a scenario with required ORFs: the W-sum W(P); one with biased ORFs: D_B); `contig` is the scenario's contig.  Served while the scenario's
+        """(path as device node ids, its length D_F as a python int) of scenario j of the last scenarios(), pinned_scenarios(), evidence_scenarios() or curate_scenarios()
+        call, like reannotated_path (a scenario with required ORFs: the W-sum W(P); one with biased ORFs: D_B; one with both: S(P)); `contig` is the scenario's contig.  Served while the scenario's
         chunk is resident (phx_tap_scenario_path)."""
         return self._tap_path(self.L.phx_tap_scenario_path, "phx_tap_scenario_path", self.globals(contig), int(j))
 
@@ -764,6 +764,24 @@ class Annotator:
                 raise IndexError("contig %d has %d ORFs" % (i, n_orf))
             yield k, Annotator._bias_units(i, k, b)
 
+    @staticmethod
+    def _scenario_bias_arrays(items, oo):
+        """(bias_off int64[S+1], bias_orf int32[], bias_val int64[]) of a sequence of (contig — checked by _scenario_arrays —, bias): the
+        pairs as given (the library merges them); IndexError and ValueError as _bias_pairs, ValueError for a summed |B| > 2^52."""
+        boff = np.zeros(len(items) + 1, np.int64)
+        borf, bval = [], []
+        for j, (i, pairs) in enumerate(items):
+            i = int(i)
+            sums = {}
+            for k, B in Annotator._bias_pairs(i, pairs, oo[i + 1] - oo[i]):
+                sums[k] = sums.get(k, 0) + B
+                borf.append(k)
+                bval.append(B)
+            if any(abs(v) > 1 << 52 for v in sums.values()):
+                raise ValueError("a bias beyond 2^52 / 1000 SCORE units")
+            boff[j + 1] = len(borf)
+        return boff, np.ascontiguousarray(borf if borf else [0], np.int32), np.ascontiguousarray(bval if bval else [0], np.int64)
+
     def evidence_scenarios(self, scen):
         """(status int32[S], offsets int64[S+1], genes structured array[total], delta float64[S]): S evidence-weighted re-annotations of
         the batch last run in one call (phx_evidence_scenarios_flat).  `scen` is a sequence of (contig, bias, forbid):
@@ -781,20 +799,7 @@ class Annotator:
             raise ValueError("an evidence scenario is a (contig, bias, forbid) triple") from None
         contig, foff, forf = self._scenario_arrays([(i, f) for i, _, f in triples], n, oo)
         S = len(triples)
-        boff = np.zeros(S + 1, np.int64)
-        borf, bval = [], []
-        for j, (i, pairs, _) in enumerate(triples):
-            i = int(i)
-            sums = {}
-            for k, B in self._bias_pairs(i, pairs, oo[i + 1] - oo[i]):
-                sums[k] = sums.get(k, 0) + B
-                borf.append(k)  # (the pairs as given: the library merges them)
-                bval.append(B)
-            if any(abs(v) > 1 << 52 for v in sums.values()):
-                raise ValueError("a bias beyond 2^52 / 1000 SCORE units")
-            boff[j + 1] = len(borf)
-        borf = np.ascontiguousarray(borf if borf else [0], np.int32)
-        bval = np.ascontiguousarray(bval if bval else [0], np.int64)
+        boff, borf, bval = self._scenario_bias_arrays([(i, b) for i, b, _ in triples], oo)
         head = (S, _vp(contig), _vp(foff), _vp(forf), _vp(boff), _vp(borf), _vp(bval), _vp(oo), 0)
         return self._genes_flat(self.L.phx_evidence_scenarios_flat, "phx_evidence_scenarios_flat", head, S, False)
 
@@ -832,6 +837,81 @@ class Annotator:
             o["called"] = int(any((g[0], g[1], g[2] > 0) == me and abs(g[3]) <= 3 for g in new))
             o["n_removed"], o["n_added"] = n_removed, n_added
         return np.asarray(st[:n], np.int32), offs, rec, soffs, genes
+
+    # ---- combined scenario batches ----
+    def curate_scenarios(self, scen):
+        """(status int32[S], offsets int64[S+1], genes structured array[total], delta float64[S], unmet int32[S]), as pinned_scenarios()
+        returns them: S combined re-annotations of the batch last run in one call (phx_curate_scenarios_flat).  `scen` is a
+        sequence of (contig, bias, forbid, require): `bias` what evidence_scenarios() takes, `forbid` and `require` arrays of indices into
+        orfs(contig) or None.  Scenario j is curate(..., solve_all=True) of that contig with exactly that bias and those two sets —
+        status[j], delta[j], unmet[j] and genes[offsets[j]:offsets[j+1]] are byte for byte that call's for the contig — solved side by
+        side on the resident graph, one workgroup per scenario.  Scenarios are independent; one without a bias is pinned_scenarios()'
+        scenario, one without required ORFs evidence_scenarios()', one with neither scenarios()'.  An ORF in both sets of one scenario
+        raises PhxError (PHX_E_ARG); IndexError and ValueError as evidence_scenarios() and pinned_scenarios()."""
+        n = self.n
+        oo = self.orf_offsets()
+        try:
+            quads = [(i, b, f, r) for i, b, f, r in scen]
+        except (TypeError, ValueError):
+            raise ValueError("a combined scenario is a (contig, bias, forbid, require) quadruple") from None
+        contig, foff, forf = self._scenario_arrays([(i, f) for i, _, f, _ in quads], n, oo)
+        _, roff, rorf = self._scenario_arrays([(i, r) for i, _, _, r in quads], n, oo)
+        S = len(quads)
+        boff, borf, bval = self._scenario_bias_arrays([(i, b) for i, b, _, _ in quads], oo)
+        head = (S, _vp(contig), _vp(foff), _vp(forf), _vp(roff), _vp(rorf), _vp(boff), _vp(borf), _vp(bval), _vp(oo), 0)
+        return self._genes_flat(self.L.phx_curate_scenarios_flat, "phx_curate_scenarios_flat", head, S, True)
+
+    def curated_scan(self, hits, forbid=None, require=None):
+        """(status int32[n], offsets int64[n+1], records structured array[total] of _lib.CUSCAN_DT, scen_offsets int64[total+1], genes,
+        base_offsets int64[n+1]): evidence_scan() under pins.  `hits` holds, per contig, what evidence_scan() takes; `forbid` and `require`
+        hold, per contig, what curate() takes.  For every contig with hits there is one baseline scenario — no bias, the contig's two sets
+        — and one scenario per hit — that ORF biased alone under the same two sets —, all in one curate_scenarios() call.  A record is
+        evidence_scan()'s plus unmet and the baseline's status, delta and unmet; was_called, n_removed and n_added are taken against the
+        BASELINE's genes ("given my pins, does this hit change the call"), delta stays relative to the run.
+        genes[scen_offsets[k]:scen_offsets[k+1]] is record k's full new annotation and genes[base_offsets[i]:base_offsets[i+1]] the
+        baseline annotation of contig i (empty for a contig without hits): the baselines' lists follow the records' in `genes`."""
+        n = self.n
+        if len(hits) != n or (forbid is not None and len(forbid) != n) or (require is not None and len(require) != n):
+            raise ValueError("one sequence of (ORF index, bias) pairs and one index array per set (or None) per contig of the batch")
+        sets = lambda i: (None if forbid is None else forbid[i], None if require is None else require[i])
+        scen, head = [], []
+        offs = np.zeros(n + 1, np.int64)
+        for i, pairs in enumerate(hits):
+            for k, b in (() if pairs is None else pairs.items() if hasattr(pairs, "items") else pairs):
+                scen.append((i, [(int(k), b)]) + sets(i))
+                head.append((i, int(k), float(b)))
+            offs[i + 1] = len(scen)
+        total = len(scen)
+        base_of = np.full(n, -1, np.int64)  # the contig's baseline scenario: behind the records', in contig order
+        for i in range(n):
+            if offs[i + 1] > offs[i]:
+                base_of[i] = len(scen)
+                scen.append((i, None) + sets(i))
+        sstat, soffs, genes, delta, unmet = self.curate_scenarios(scen)
+        st = self._device_lists()[0]
+        boffs = np.zeros(n + 1, np.int64)
+        boffs[0] = soffs[total]
+        for i in range(n):
+            boffs[i + 1] = soffs[base_of[i] + 1] if base_of[i] >= 0 else boffs[i]
+        key = lambda g: (int(g["left"]), int(g["right"]), int(g["strand"]), int(g["frame"]))
+        rec = np.zeros(total, _lib.CUSCAN_DT)
+        have, have_of, orfs_of = None, -1, None
+        for x, (i, k, b) in enumerate(head):
+            if have_of != i:
+                have, have_of, orfs_of = {key(g) for g in genes[boffs[i]:boffs[i + 1]]}, i, self.orfs(i)
+            new = {key(g) for g in genes[soffs[x]:soffs[x + 1]]}
+            o = rec[x]
+            ao = orfs_of[k]
+            fwd = ao["frame"] > 0
+            o["left"], o["right"] = (ao["start"], ao["stop"] + 2) if fwd else (ao["stop"], ao["start"] + 2)
+            o["strand"], o["orf"], o["bias"] = (1 if fwd else -1), k, b
+            o["status"], o["delta"], o["unmet"] = sstat[x], delta[x], unmet[x]
+            me = (int(o["left"]), int(o["right"]), bool(fwd))
+            o["was_called"] = int(any((g[0], g[1], g[2] > 0) == me and abs(g[3]) <= 3 for g in have))
+            o["called"] = int(any((g[0], g[1], g[2] > 0) == me and abs(g[3]) <= 3 for g in new))
+            o["n_removed"], o["n_added"] = len(have - new), len(new - have)
+            o["base_status"], o["base_delta"], o["base_unmet"] = sstat[base_of[i]], delta[base_of[i]], unmet[base_of[i]]
+        return np.asarray(st[:n], np.int32), offs, rec, np.ascontiguousarray(soffs[: total + 1]), genes, boffs
 
     def reannotated_path(self, i):
         """(path as device node ids, its length as a python int) of contig i in the last re-annotation, constrain(), evidence() or curate(), like

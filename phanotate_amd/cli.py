@@ -49,6 +49,7 @@ def get_args(argv=None):
     p.add_argument("--require", metavar="FILE", default=None, help="ORFs to keep in a second annotation (DESIGN.md §16), in the format of --forbid; alone or with --forbid; needs --reannotation, which then carries a #unmet: line per contig")
     p.add_argument("--evidence", metavar="FILE", default=None, help="per-ORF bonuses and penalties for a second annotation (DESIGN.md §19), in the format of --forbid with a fifth column BIAS: a finite number of SCORE units added to the ORF's weight (negative: support; an ORF named twice gets the sum); alone or with --forbid, not with --require; needs --reannotation, whose #delta: may then be negative")
     p.add_argument("--evidence-scan", metavar=("FILE", "OUT"), nargs=2, default=None, help="also take every line of FILE (the format of --evidence) on its own: write to OUT, per line, the cost and the effect of the best annotation under that one bias (DESIGN.md §20); independent of --evidence / --reannotation")
+    p.add_argument("--curated-scan", metavar=("FILE", "OUT"), nargs=2, default=None, help="also take every line of FILE (the format of --evidence) on its own UNDER the ORFs of --require and --forbid: write to OUT, per contig, the baseline under the two sets alone and, per line, the cost and the effect of that one bias against the baseline (DESIGN.md §27); needs --require and --reannotation")
     p.add_argument("--reannotation", metavar="OUT", default=None, help="write the annotation without the ORFs of --forbid (keeping those of --require, or under the biases of --evidence) to OUT: the tabular block of every contig with a #delta: header line")
     p.add_argument("--remargins", metavar="FILE", default=None, help="also write every ORF with its path margin on the graph of the second annotation (under --forbid / --evidence; DESIGN.md §21) to FILE, in the format of --margins; needs --reannotation, not with --require")
     p.add_argument("--pin-margins", metavar="FILE", default=None, help="also write every ORF with its path margin and the kept ORFs of --require that the best path through it gives up (DESIGN.md §24) to FILE: the format of --margins with a LOST column behind MARGIN; needs --require and --reannotation")
@@ -84,6 +85,14 @@ def get_args(argv=None):
         p.error("argument --evidence-scan: not available under a multi-rank launch")
     if args.evidence_scan is not None and int(args.gpus) > 1:  # the scenarios work on the batch resident on one context
         p.error("argument --evidence-scan: not available with --gpus above 1")
+    if args.curated_scan is not None and args.dump:
+        p.error("argument --curated-scan: not allowed with argument -d/--dump")
+    if args.curated_scan is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        p.error("argument --curated-scan: not available under a multi-rank launch")
+    if args.curated_scan is not None and int(args.gpus) > 1:  # the scenarios work on the batch resident on one context
+        p.error("argument --curated-scan: not available with --gpus above 1")
+    if args.curated_scan is not None and args.require is None:
+        p.error("argument --curated-scan: needs --require")
     if args.remargins is not None and args.dump:
         p.error("argument --remargins: not allowed with argument -d/--dump")
     if args.remargins is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -249,6 +258,35 @@ def format_evidence_scan(names, status, offsets, records):
                 delta = repr(float(r["delta"]))
             buf.write("%d\t%d\t%s\t%s\t%s\t%d\t%d\t%d\n" % (left, right, chr(44 - (-1 if rev else 1)), repr(float(r["bias"])), delta, int(r["called"]), int(r["n_removed"]),
                                                           int(r["n_added"])))
+    return buf.getvalue()
+
+
+def format_curated_scan(names, status, offsets, records):
+    """--curated-scan FILE OUT: per contig with status >= 0 "#id:\t<name>", for a contig with records "#base:\t<DELTA>\t<unmet>" — the
+    baseline under --require / --forbid alone, DELTA as below —, the header, and one row per record of Annotator.curated_scan() (a line of
+    FILE, taken on its own under the two sets): format_evidence_scan's columns, REMOVED and ADDED counted against the baseline's genes,
+    and UNMET, the required ORFs the new annotation does not call."""
+    import io
+
+    import numpy as np
+
+    def cost(st, delta):
+        return "cycle" if st == -9 else "inf" if st != 0 or not np.isfinite(delta) else repr(float(delta))
+
+    buf = io.StringIO()
+    for i, nm in enumerate(names):
+        if status[i] < 0:
+            continue
+        buf.write("#id:\t" + nm + "\n")
+        recs = records[offsets[i]:offsets[i + 1]]
+        if len(recs):
+            buf.write("#base:\t%s\t%d\n" % (cost(recs[0]["base_status"], recs[0]["base_delta"]), int(recs[0]["base_unmet"])))
+        buf.write("#START\tSTOP\tFRAME\tBIAS\tDELTA\tCALLED\tREMOVED\tADDED\tUNMET\n")
+        for r in recs:
+            rev = r["strand"] < 0
+            left, right = (int(r["right"]), int(r["left"])) if rev else (int(r["left"]), int(r["right"]))  # locus.py:44-46
+            buf.write("%d\t%d\t%s\t%s\t%s\t%d\t%d\t%d\t%d\n" % (left, right, chr(44 - (-1 if rev else 1)), repr(float(r["bias"])), cost(r["status"], r["delta"]), int(r["called"]),
+                                                                int(r["n_removed"]), int(r["n_added"]), int(r["unmet"])))
     return buf.getvalue()
 
 
@@ -525,8 +563,12 @@ def main(argv=None):
     remargin_parts = []  # --remargins: (status, offsets, records) of Annotator.remargins() of every batch, in order
     pin_parts = []  # --pin-margins: (status, offsets, records, lost) of Annotator.pinmargins() of every batch, in order
     scan_parts = []  # --evidence-scan: (status, offsets, records) of Annotator.evidence_scan() of every batch, in order
-    forbid_entries = require_entries = evidence_entries = scan_entries = None
+    cscan_parts = []  # --curated-scan: (status, offsets, records) of Annotator.curated_scan() of every batch, in order
+    forbid_entries = require_entries = evidence_entries = scan_entries = cscan_entries = None
     try:
+        if args.curated_scan is not None:
+            with open(args.curated_scan[0]) as fh:
+                cscan_entries = parse_evidence(fh, "--curated-scan")
         if args.evidence_scan is not None:
             with open(args.evidence_scan[0]) as fh:
                 scan_entries = parse_evidence(fh, "--evidence-scan")
@@ -597,6 +639,9 @@ def main(argv=None):
                     reann_parts.append(ann.reannotate(refused))
                 else:
                     reann_parts.append(ann.constrain(refused, resolve_forbid([e for e in require_entries if e[3] in here], names, ann.orf_index, "--require")))
+                if cscan_entries is not None:  # (a scenario batch of its own: the batch's re-annotation above stays the cached one)
+                    cscan_parts.append(ann.curated_scan(resolve_evidence([e for e in cscan_entries if e[3] in here], names, ann.orf_index, "--curated-scan"), refused,
+                                                        resolve_forbid([e for e in require_entries if e[3] in here], names, ann.orf_index, "--require"))[:3])
                 if args.remargins is not None:  # (behind the batch's re-annotation: the margins are that solve's)
                     remargin_parts.append(ann.remargins())
                 if args.pin_margins is not None:  # (likewise)
@@ -650,7 +695,7 @@ def main(argv=None):
         return st, np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), genes
 
     known = set(fa.names)
-    for flag, entries in (("--forbid", forbid_entries), ("--require", require_entries), ("--evidence", evidence_entries), ("--evidence-scan", scan_entries)):
+    for flag, entries in (("--forbid", forbid_entries), ("--require", require_entries), ("--evidence", evidence_entries), ("--evidence-scan", scan_entries), ("--curated-scan", cscan_entries)):
         for e in entries or []:
             if e[3] not in known:
                 drop_context()
@@ -741,6 +786,12 @@ def main(argv=None):
             e_offsets = np.concatenate([[0], np.cumsum(e_counts)]).astype(np.int64)
             with open(args.evidence_scan[1], "w") as fh:
                 fh.write(format_evidence_scan(fa.names, e_status, e_offsets, np.concatenate([m[2] for m in scan_parts])))
+        if args.curated_scan is not None:
+            c_status = np.concatenate([m[0] for m in cscan_parts])
+            c_counts = np.concatenate([np.diff(m[1]) for m in cscan_parts])
+            c_offsets = np.concatenate([[0], np.cumsum(c_counts)]).astype(np.int64)
+            with open(args.curated_scan[1], "w") as fh:
+                fh.write(format_curated_scan(fa.names, c_status, c_offsets, np.concatenate([m[2] for m in cscan_parts])))
         if args.reannotation is not None:
             q_status = np.concatenate([m[0] for m in reann_parts])
             q_counts = np.concatenate([np.diff(m[1]) for m in reann_parts])

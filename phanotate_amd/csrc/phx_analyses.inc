@@ -1035,12 +1035,13 @@ int phx_pinmargins_ms(phx_ctx *c, float *ms) {
     return PHX_OK;
 }
 
-// ---- scenario batches (phx_resolve.inc, DESIGN.md §17), with required ORFs (§18) or biased ORFs (§20) per scenario ----
+// ---- scenario batches (phx_resolve.inc, DESIGN.md §17), with required ORFs (§18), biased ORFs (§20) or both (§27) per scenario ----
 // h_srec[j].status before the solve: the scenario gets a slot / its contig is not solved again and the run's verdict stands (neither is a status the device reports)
 static const int32_t SC_SLOT = -99, SC_NOSLOT = -100;
 // Device bytes of one slot of contig i: distances, parent, path, bitmap slice, window plan, gene records, the record copy; a pinned slot
 // (§18) has one limb more per node, a second bitmap slice and its entries of DScen.req0 / nreq / kreq; a biased slot (§20) with n_bias
-// listed ORFs has a bias slice, its DScBias and per ORF a triple, a list pair and a staging pair of 16 bytes each.
+// listed ORFs has a bias slice, its DScBias and per ORF a triple, a list pair and a staging pair of 16 bytes each; a slot that is both (§27)
+// has both parts.
 static size_t scen_slot_bytes(const phx_ctx *c, int i, bool pinned = false, size_t n_bias = 0) {
     const DMeta &m = c->meta[(size_t)i];
     const size_t V = (size_t)m.n_node, E = (size_t)m.n_edge;
@@ -1052,8 +1053,9 @@ static size_t scen_slot_bytes(const phx_ctx *c, int i, bool pinned = false, size
 // perm: per contig named, tap index -> ORF in the contig's device order (-1: no such ORF in the device's groups).  req_off / req_orf: the
 // required lists without duplicates; a scenario with a non-empty one gets a pinned slot.  In a chunk's slot table the pinned slots follow
 // the plain ones (the slices keep the scenarios' order): the solve's kernels get the table range by range (phxk_scen_solve).  bs_off / bs_orf / bs_val: the
-// merged bias lists (no duplicates, no zero, no ORF the scenario refuses); a scenario with a non-empty one gets a biased slot (never with a
-// required list: no entry point takes both), and the biased slots follow the pinned ones.
+// merged bias lists (no duplicates, no zero, no ORF the scenario refuses); a scenario with a non-empty one gets a biased slot, and the
+// biased slots follow the pinned ones.  A scenario with both lists non-empty (phx_curate_scenarios_flat, §27) gets a slot that is pinned AND
+// biased — both parts of scen_slot_bytes — in a fourth range directly behind the biased one.
 static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const int64_t *scen_off, const int32_t *scen_orf, const int64_t *req_off, const int32_t *req_orf,
                         const int64_t *bs_off, const int32_t *bs_orf, const int64_t *bs_val, const std::vector<std::vector<int32_t>> &perm) {
     int rc;
@@ -1065,21 +1067,22 @@ static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const
     c->h_schunk_of.assign((size_t)S, 0);
     if ((rc = analysis_events(c))) return rc;
     const int EV0 = 1 << 30;            // a chunk has fewer slots
-    std::vector<DScSlot> slots, pslots, eslots; // plain, pinned, biased
-    std::vector<int2> pairs, rpairs;    // (a pinned slot's index: -1 - its place among the pinned ones, a biased slot's: EV0 + its place among the biased ones, until the chunk is closed)
-    std::vector<int64_t> which, pwhich, ewhich; // scenario of every slot of the chunk
-    std::vector<DScBias> ebs;           // per biased slot: its DScBias
+    std::vector<DScSlot> slots, pslots, eslots, bslots; // plain, pinned, biased, both
+    std::vector<int2> pairs, rpairs;    // (a pinned slot's index: -1 - its place among the pinned ones, a biased slot's: EV0 + its place among the biased ones, a "both" slot's: -1 - EV0 - its place among those, until the chunk is closed)
+    std::vector<int64_t> which, pwhich, ewhich, bwhich; // scenario of every slot of the chunk
+    std::vector<DScBias> ebs, bbs;      // per biased slot, per "both" slot: its DScBias
     std::vector<DScTrip> &trips = c->h_strip; // the chunk's triples and the table's DScBias as uploaded (members: see h_qdforb)
     std::vector<DScBias> &bsv = c->h_sbs;
-    std::vector<int64_t> preq0;         // per pinned slot: DScen.req0
-    std::vector<int32_t> pnreq;         //   ... and nreq
+    std::vector<int64_t> preq0, breq0;  // per pinned slot, per "both" slot: DScen.req0
+    std::vector<int32_t> pnreq, bnreq;  //   ... and nreq
     std::vector<uint8_t> &pin = c->h_spin; // what the kernels read per slot: req0 (int64), nreq, kreq (int32)
     for (int64_t j0 = 0; j0 < S;) {
         // ---- the chunk: scenarios j0 .. j1 with a slot, as many as the budget holds (at least one) ----
         slots.clear(); pslots.clear(); pairs.clear(); rpairs.clear(); which.clear(); pwhich.clear(); preq0.clear(); pnreq.clear();
         eslots.clear(); ewhich.clear(); ebs.clear(); trips.clear();
+        bslots.clear(); bwhich.clear(); bbs.clear(); breq0.clear(); bnreq.clear();
         size_t bytes = 0, nodes = 0, words = 0, mwords = 0, rwords = 0, bwords = 0, plan = 0;
-        int nlm = 0, pinm = 0, evm = 0;
+        int nlm = 0, pinm = 0, evm = 0, bom = 0;
         int64_t j1 = j0;
         for (; j1 < S; j1++) {
             if (c->h_srec[(size_t)j1].status != SC_SLOT) continue;
@@ -1087,10 +1090,10 @@ static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const
             const DMeta &m = c->meta[(size_t)i];
             const int32_t nreq = (int32_t)(req_off[j1 + 1] - req_off[j1]);
             const bool pinned = nreq > 0;
-            const size_t nbias = pinned ? 0 : (size_t)(bs_off[j1 + 1] - bs_off[j1]);
-            const bool biased = nbias > 0;
+            const size_t nbias = (size_t)(bs_off[j1 + 1] - bs_off[j1]);
+            const bool biased = nbias > 0, both = pinned && biased;
             const size_t need = scen_slot_bytes(c, i, pinned, nbias);
-            const size_t have = slots.size() + pslots.size() + eslots.size();
+            const size_t have = slots.size() + pslots.size() + eslots.size() + bslots.size();
             if (have && (bytes + need > (size_t)c->scen_budget || have + 1 >= (size_t)EV0)) break;
             bytes += need;
             DScSlot sl;
@@ -1101,8 +1104,8 @@ static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const
             words += ((size_t)m.n_node * (size_t)(m.sssp_nl + (pinned ? 1 : 0)) + 1) & ~(size_t)1;
             mwords += mw;
             plan += (size_t)m.n_node / 32 + 2;
-            (pinned ? pinm : biased ? evm : nlm) |= nl_class_bit(m.sssp_nl);
-            const int id = pinned ? -1 - (int)pslots.size() : biased ? EV0 + (int)eslots.size() : (int)slots.size();
+            (both ? bom : pinned ? pinm : biased ? evm : nlm) |= nl_class_bit(m.sssp_nl);
+            const int id = both ? -1 - EV0 - (int)bslots.size() : pinned ? -1 - (int)pslots.size() : biased ? EV0 + (int)eslots.size() : (int)slots.size();
             const std::vector<int32_t> &pm = perm[(size_t)i];
             for (int64_t k = scen_off[j1]; k < scen_off[j1 + 1]; k++) {
                 const int32_t d = pm[(size_t)scen_orf[k]];
@@ -1112,7 +1115,8 @@ static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const
                 const int32_t d = pm[(size_t)req_orf[k]];
                 if (d >= 0) rpairs.push_back(make_int2(id, d));
             }
-            if (pinned) { preq0.push_back((int64_t)rwords); pnreq.push_back(nreq); rwords += mw; pslots.push_back(sl); pwhich.push_back(j1); }
+            if (pinned) { (both ? breq0 : preq0).push_back((int64_t)rwords); (both ? bnreq : pnreq).push_back(nreq); rwords += mw; }
+            if (pinned && !both) { pslots.push_back(sl); pwhich.push_back(j1); }
             else if (biased) {
                 DScBias e{};
                 e.bbit0 = (int64_t)bwords; e.list0 = (int64_t)trips.size();
@@ -1121,27 +1125,41 @@ static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const
                     if (d >= 0) trips.push_back(DScTrip{id, d, (long long)bs_val[k]});
                 }
                 e.n_trip = (int32_t)(trips.size() - (size_t)e.list0);
-                bwords += mw; ebs.push_back(e); eslots.push_back(sl); ewhich.push_back(j1);
+                bwords += mw;
+                if (both) { bbs.push_back(e); bslots.push_back(sl); bwhich.push_back(j1); }
+                else { ebs.push_back(e); eslots.push_back(sl); ewhich.push_back(j1); }
             } else { slots.push_back(sl); which.push_back(j1); }
         }
         j0 = j1;
-        const size_t n_plain = slots.size(), n_pin = pslots.size(), n_ev = eslots.size(), ns = n_plain + n_pin + n_ev, n_head = n_plain + n_pin;
+        // the table: plain, pinned, biased, both.  n_pin and n_ev below count the slots WITH a required slice / WITH a list: a "both" slot is either
+        const size_t n_plain = slots.size(), n_pin1 = pslots.size(), n_ev1 = eslots.size(), n_bo = bslots.size(), n_head = n_plain + n_pin1, n_first3 = n_head + n_ev1, ns = n_first3 + n_bo;
+        const size_t n_pin = n_pin1 + n_bo, n_ev = n_ev1 + n_bo;
         if (!ns) break;
         slots.insert(slots.end(), pslots.begin(), pslots.end());
         slots.insert(slots.end(), eslots.begin(), eslots.end());
+        slots.insert(slots.end(), bslots.begin(), bslots.end());
         which.insert(which.end(), pwhich.begin(), pwhich.end());
         which.insert(which.end(), ewhich.begin(), ewhich.end());
-        for (int2 &pr : pairs) pr.x = pr.x < 0 ? (int)n_plain + (-1 - pr.x) : pr.x >= EV0 ? (int)n_head + (pr.x - EV0) : pr.x;
-        for (int2 &pr : rpairs) pr.x = (int)n_plain + (-1 - pr.x);
-        for (DScTrip &t : trips) t.slot = (int)n_head + (t.slot - EV0);
+        which.insert(which.end(), bwhich.begin(), bwhich.end());
+        // a slot's index in the table from its index until the chunk is closed
+        auto place = [&](int x) -> int { return x < -EV0 ? (int)n_first3 + (-1 - EV0 - x) : x < 0 ? (int)n_plain + (-1 - x) : x >= EV0 ? (int)n_head + (x - EV0) : x; };
+        for (int2 &pr : pairs) pr.x = place(pr.x);
+        for (int2 &pr : rpairs) pr.x = place(pr.x);
+        for (DScTrip &t : trips) t.slot = place(t.slot);
         int max_list = 0; // the longest list of the chunk: how many workgroups k_sce_sort gives a slot
         for (const DScBias &e : ebs) max_list = std::max(max_list, (int)e.n_trip);
+        for (const DScBias &e : bbs) max_list = std::max(max_list, (int)e.n_trip);
         bsv.assign(n_ev ? ns : 0, DScBias{});
         std::copy(ebs.begin(), ebs.end(), bsv.begin() + (ptrdiff_t)(n_ev ? n_head : 0));
+        std::copy(bbs.begin(), bbs.end(), bsv.begin() + (ptrdiff_t)(n_ev ? n_first3 : 0));
         pin.assign(ns * 16, 0);
-        for (size_t k = 0; k < n_pin; k++) {
+        for (size_t k = 0; k < n_pin1; k++) {
             memcpy(pin.data() + (n_plain + k) * 8, &preq0[k], 8);
             memcpy(pin.data() + ns * 8 + (n_plain + k) * 4, &pnreq[k], 4);
+        }
+        for (size_t k = 0; k < n_bo; k++) {
+            memcpy(pin.data() + (n_first3 + k) * 8, &breq0[k], 8);
+            memcpy(pin.data() + ns * 8 + (n_first3 + k) * 4, &bnreq[k], 4);
         }
         c->scen_chunks++;
         if ((rc = ensure(c, c->b_sc_slot, ns * sizeof(DScSlot))) || (rc = ensure(c, c->b_sc_pair, (pairs.size() + rpairs.size() + 1) * sizeof(int2))) ||
@@ -1162,7 +1180,7 @@ static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const
         // the slots' view of the batch: the run's graph and records (read only), totals / genes / counter / tie scratch of the scenarios' own
         DBatch b;
         DScen q;
-        const int n_range[3] = {(int)n_plain, (int)n_pin, (int)n_ev}, nlms[3] = {nlm, pinm, evm}; // the plain head, the pinned middle and the biased tail of the slot table
+        const int n_range[4] = {(int)n_plain, (int)n_pin1, (int)n_ev1, (int)n_bo}, nlms[4] = {nlm, pinm, evm, bom}; // the plain head, the pinned and the biased middle and the "both" tail of the slot table
         const size_t base = c->h_sgenes.size();
         const ReSolve R{"scenarios", "slot", c->b_sc_tot, c->b_sc_gtot, c->b_sc_tie, c->b_sc_rec, c->b_sc_genes, c->h_stot, c->h_sgtot, c->h_schunk.data(), ns, nodes + ns, c->h_sgenes};
         float ms[3] = {0, 0, 0};
@@ -1204,8 +1222,8 @@ static int scen_compute(phx_ctx *c, int64_t S, const int32_t *scen_contig, const
     return PHX_OK;
 }
 
-// phx_scenarios_flat (no required lists: require_off, require_orf and unmet null), phx_pinned_scenarios_flat and phx_evidence_scenarios_flat
-// (bias lists instead of required ones) are one solve on one set of buffers; the cached result is keyed on all the lists (as reann_flat
+// phx_scenarios_flat (no required lists: require_off, require_orf and unmet null), phx_pinned_scenarios_flat, phx_evidence_scenarios_flat
+// (bias lists instead of required ones) and phx_curate_scenarios_flat (all three lists) are one solve on one set of buffers; the cached result is keyed on all the lists (as reann_flat
 // serves phx_reannotate_flat, phx_constrain_flat and phx_evidence_flat).
 static int scen_flat(phx_ctx *c, const char *who, int64_t n_scen, const int32_t *scen_contig, const int64_t *scen_off, const int32_t *scen_orf, const int64_t *req_off_in,
                      const int32_t *req_orf_in, const int64_t *bias_off_in, const int32_t *bias_orf_in, const int64_t *bias_val_in, const int64_t *orf_offsets, phx_gene *genes, int64_t cap, int64_t *offsets, int32_t *status, double *delta, int32_t *unmet,
@@ -1361,6 +1379,16 @@ int phx_evidence_scenarios_flat(phx_ctx *c, int64_t n_scen, const int32_t *scen_
     if (!c || !bias_off) return PHX_E_ARG;
     return scen_flat(c, "phx_evidence_scenarios_flat", n_scen, scen_contig, forbid_off, forbid_orf, nullptr, nullptr, bias_off, bias_orf, bias_val, orf_offsets, genes, cap, offsets,
                      status, delta, nullptr, total_out);
+}
+
+// (§27) all three lists per scenario: a scenario with a required ORF and a surviving bias takes a "both" slot, any other reduces to its sibling's
+int phx_curate_scenarios_flat(phx_ctx *c, int64_t n_scen, const int32_t *scen_contig, const int64_t *forbid_off, const int32_t *forbid_orf, const int64_t *require_off,
+                              const int32_t *require_orf, const int64_t *bias_off, const int32_t *bias_orf, const int64_t *bias_val, const int64_t *orf_offsets, uint32_t flags,
+                              phx_gene *genes, int64_t cap, int64_t *offsets, int32_t *status, double *delta, int32_t *unmet, int64_t *total_out) {
+    (void)flags; // reserved
+    if (!c || !require_off || !bias_off || (n_scen > 0 && !unmet)) return PHX_E_ARG;
+    return scen_flat(c, "phx_curate_scenarios_flat", n_scen, scen_contig, forbid_off, forbid_orf, require_off, require_orf, bias_off, bias_orf, bias_val, orf_offsets, genes, cap,
+                     offsets, status, delta, unmet, total_out);
 }
 
 int phx_tap_scenario_path(phx_ctx *c, int64_t scen, int32_t *path, int32_t cap, int32_t *n_path, uint64_t *dist_limbs, int32_t cap_limbs) {

@@ -415,14 +415,14 @@ struct DReann { // (the order is the kernels' argument block: a field that moves
 // (contig, refused set); the graph arrays are the run's, shared by all slots of a contig; every output is the slot's own.
 struct DScSlot {
     int32_t contig;      // contig of the batch last run
-    int32_t pinned;      // 1: a slot with required ORFs (§18): NL + 1 limbs per node at dist0 and a required slice (DScen.req0); else 0
+    int32_t pinned;      // 1: a slot with required ORFs (§18; with a bias list as well: §27): NL + 1 limbs per node at dist0 and a required slice (DScen.req0); else 0
     int64_t node0;       // first entry of the slot's slices of DScen.parent / path (n_node entries each)
     int64_t dist0;       // first 64-bit word of the slot's distances (n_node x the contig's limbs; a pinned slot: one limb more)
     int64_t mask0;       // first word of the slot's bitmap slice: in-edge slot e is bit (edge_off & 31) + e of the slice, so that the
                          //   slice shifted back by edge_off >> 5 words is indexed by edge_off + e like DReann.mask
     int64_t plan0;       // first byte of the slot's global window plan (n_node / 32 + 2 bytes)
 };
-struct DScBias { // per biased slot (§20): the host writes the places and zeroes the rest per solve
+struct DScBias { // per biased slot (§20) and per slot that is pinned and biased (§27): the host writes the places and zeroes the rest per solve
     int64_t bbit0;       // first word of the slot's bias slice in DScen.bbit (the bit rule of DScSlot.mask0)
     int64_t list0;       // first pair of the slot's list in DScen.blist, and of its staging area in DScen.bstage
     int32_t n_trip;      // triples listed for the slot: the capacity of its list
@@ -446,14 +446,14 @@ struct DScen {
     uint8_t *gplan;
     const uint64_t *dist0; // the run's distances (D)
     DReannRec *rec;      // per slot: what the host reads
-    // pinned scenarios (§18)
+    // pinned scenarios (§18) and the pinned part of a "both" slot (§27)
     uint32_t *req;       // the required bitmap slices of the pinned slots, cleared per chunk
     const int64_t *req0; // per slot: first word of its required slice in req (the bit rule of mask0)
     const int32_t *nreq; // per slot: required ORFs (|R|)
     int32_t *kreq;       // per slot: required ORFs whose edge exists (k_scp_mask counts them): the bound of the solver's cycle guard
     const int2 *rpair;   // the required (slot, ORF in the contig's device order) pairs of the chunk
     int64_t n_rpair;
-    // evidence scenarios (§20)
+    // evidence scenarios (§20) and the biased part of a "both" slot (§27)
     uint32_t *bbit;      // the bias bitmap slices of the biased slots, cleared per chunk
     DScBias *bs;         // per slot: where its bias slice and list lie, and what k_sce_mask counted and summed (biased slots only)
     long long *blist;    // the slots' lists: (in-edge slot of the batch: edge_off + e, B) pairs, 16 bytes each, sorted by in-edge slot (k_sce_sort)

@@ -246,11 +246,12 @@ static void re_inorder_launch(const DBatch *b, const Q *q, unsigned grid, int nl
     if (b->mean_len < 8192) re_inorder_t<64, Pol>(b, q, grid, nlm, s);
     else re_inorder_t<IO_T_FULL, Pol>(b, q, grid, nlm, s);
 }
-// Range r of a chunk's slot table (0 plain, 1 pinned, 2 biased; n_range: their slot counts) as a table of its own, so that blockIdx.x is a
-// slot of the range: the per-slot arrays moved to the range's first slot.  The pair and triple lists stay the whole table's.
+// Range r of a chunk's slot table (0 plain, 1 pinned, 2 biased, 3 both: pinned and biased; n_range: their slot counts) as a table of its
+// own, so that blockIdx.x is a slot of the range: the per-slot arrays moved to the range's first slot.  The pair and triple lists stay the
+// whole table's.
 static DScen scen_range(const DScen &q, const int *n_range, int r) {
     DScen t = q;
-    const int first = (r > 0 ? n_range[0] : 0) + (r > 1 ? n_range[1] : 0);
+    const int first = (r > 0 ? n_range[0] : 0) + (r > 1 ? n_range[1] : 0) + (r > 2 ? n_range[2] : 0);
     t.n_slot = n_range[r];
     t.slot += first; t.meta += first; t.rec += first;
     if (t.req0) { t.req0 += first; t.nreq += first; t.kreq += first; }
@@ -500,25 +501,28 @@ void phxk_scen_mask(const DBatch *b, const DScen *q, const int *n_range, int max
     if (q->n_slot <= 0) return;
     hipLaunchKernelGGL(k_sc_meta, dim3((unsigned)q->n_slot), dim3(64), 0, s, *b, *q);
     if (q->n_pair > 0) hipLaunchKernelGGL(k_sc_mask, dim3((unsigned)((q->n_pair + NT - 1) / NT)), dim3(NT), 0, s, *b, *q);
-    if (n_range[1] > 0 && q->n_rpair > 0) hipLaunchKernelGGL(k_scp_mask, dim3((unsigned)((q->n_rpair + NT - 1) / NT)), dim3(NT), 0, s, *b, *q);
-    if (n_range[2] <= 0 || q->n_trip <= 0) return;
+    if (n_range[1] + n_range[3] > 0 && q->n_rpair > 0) hipLaunchKernelGGL(k_scp_mask, dim3((unsigned)((q->n_rpair + NT - 1) / NT)), dim3(NT), 0, s, *b, *q);
+    const int n_listed = n_range[2] + n_range[3]; // the "both" slots sit directly behind the biased ones: one launch sorts the lists of both ranges
+    if (n_listed <= 0 || q->n_trip <= 0) return;
     hipLaunchKernelGGL(k_sce_mask, dim3((unsigned)((q->n_trip + NT - 1) / NT)), dim3(NT), 0, s, *b, *q);
-    if (max_list > 1) hipLaunchKernelGGL(k_sce_sort, dim3((unsigned)n_range[2], (unsigned)std::min((max_list + NT - 1) / NT, 16)), dim3(NT), 0, s, scen_range(*q, n_range, 2)); // (up to 16 workgroups share the longest list)
+    if (max_list > 1) hipLaunchKernelGGL(k_sce_sort, dim3((unsigned)n_listed, (unsigned)std::min((max_list + NT - 1) / NT, 16)), dim3(NT), 0, s, scen_range(*q, n_range, 2)); // (up to 16 workgroups share the longest list)
 }
 void phxk_scen_solve(const DBatch *b, const DScen *q, const int *n_range, const int *nl_masks, void *stream) {
     hipStream_t s = (hipStream_t)stream;
-    const DScen plain = scen_range(*q, n_range, 0), pinned = scen_range(*q, n_range, 1), biased = scen_range(*q, n_range, 2);
+    const DScen plain = scen_range(*q, n_range, 0), pinned = scen_range(*q, n_range, 1), biased = scen_range(*q, n_range, 2), both = scen_range(*q, n_range, 3);
     re_solve<RePol<false, false>>(b, &plain, (unsigned)n_range[0], nl_masks[0], s);
     re_solve<RePol<true, false>>(b, &pinned, (unsigned)n_range[1], nl_masks[1], s);
     re_solve<RePol<false, true, true>>(b, &biased, (unsigned)n_range[2], nl_masks[2], s);
+    re_solve<RePol<true, true, true>>(b, &both, (unsigned)n_range[3], nl_masks[3], s);
 }
 void phxk_scen_finish(const DBatch *b, const DScen *q, const int *n_range, const int *nl_masks, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     if (q->n_slot <= 0) return;
-    const DScen plain = scen_range(*q, n_range, 0), pinned = scen_range(*q, n_range, 1), biased = scen_range(*q, n_range, 2);
+    const DScen plain = scen_range(*q, n_range, 0), pinned = scen_range(*q, n_range, 1), biased = scen_range(*q, n_range, 2), both = scen_range(*q, n_range, 3);
     re_inorder_launch<RePol<false, false>>(b, &plain, (unsigned)n_range[0], nl_masks[0], s);
     re_inorder_launch<RePol<true, false>>(b, &pinned, (unsigned)n_range[1], nl_masks[1], s);
     re_inorder_launch<RePol<false, true, true>>(b, &biased, (unsigned)n_range[2], nl_masks[2], s);
+    re_inorder_launch<RePol<true, true, true>>(b, &both, (unsigned)n_range[3], nl_masks[3], s);
     hipLaunchKernelGGL(k_sc_fin, dim3((unsigned)((q->n_slot + 63) / 64)), dim3(64), 0, s, *b, *q);
 }
 // one workgroup for up to 1024 contigs; larger batches in two passes of a workgroup per 256 contigs

@@ -1,5 +1,5 @@
 // phx_resolve.inc — re-annotation: the best path of a contig's graph with chosen ORFs refused, required or biased (included by phx_kernels.hip;
-// DESIGN.md §14, §16-§20, §22, §23).
+// DESIGN.md §14, §16-§20, §22, §23, §27).
 // ------------------------------------------------------------------------------------------------
 // On demand after a run, kernel by kernel on the context's stream; never in phx_run, the captured graph or the certificate path.
 // The kernels get TWO views of the batch: the graph (in_off / esrc / ew / gtab, nodes, ORFs, groups) is the run's, read only; every output
@@ -13,7 +13,7 @@
 //     no edge (§14).  REQ: a row whose bit is set in `req` weighs W - M, M = 2^(64 NL), on one limb more than the contig's class NL, so that
 //     the top limb of a distance counts the required edges behind it (§16).  BIAS: a row whose bit is set in `bbit` weighs W + B, B a signed
 //     integer of the caller's with |B| <= 2^52 (§19); REQ and BIAS together: W + B - M (§22).  BLIST: B comes from a sorted list of the
-//     solve's own instead of a word per in-edge slot of the batch (§20).  The policy's MODE (1 masked, 2 REQ, 3 BIAS, 4 both) is what the
+//     solve's own instead of a word per in-edge slot of the batch (§20; with REQ: a scenario slot that is pinned and biased, §27).  The policy's MODE (1 masked, 2 REQ, 3 BIAS, 4 both) is what the
 //     host writes per contig (DReann.mode); ReSw<NL, Pol> adds the ring, the tile and the occupancy of the sweep per limb class.
 //   a VIEW says where one workgroup's solve lives.  BatchView: the workgroup is a contig of the batch, its marks are DReann's batch-wide
 //     bitmaps, and it takes part when the contig's mode is the policy's.  SlotView: the workgroup is a scenario slot (§17), its contig record
@@ -147,7 +147,7 @@ __device__ __forceinline__ const uint32_t *sce_bbit(const DScen &q, const DScBia
 // pairs a biased slot's list holds: what k_sce_mask appended, never beyond the list
 __device__ __forceinline__ int sce_count(const DScBias &bs) { return bs.cnt < bs.n_trip ? bs.cnt : bs.n_trip; }
 
-// blockIdx.x is a slot of the range the launcher hands over (plain, pinned or biased: phx_kernels.hip, scen_range), whose policy is Pol
+// blockIdx.x is a slot of the range the launcher hands over (plain, pinned, biased or both: phx_kernels.hip, scen_range), whose policy is Pol
 template <class Pol>
 struct SlotView {
     static_assert(!Pol::BIAS || Pol::BLIST, "a biased slot keeps a list, no word per in-edge slot");
@@ -212,7 +212,7 @@ __global__ __launch_bounds__(IO_T) void k_rs_inorder(DBatch b, DReann q) {
     BatchView<Pol> v(b, q);
     RE_INORDER(v);
 }
-// the scenario slots (§17, §18, §20): a workgroup per slot of the range
+// the scenario slots (§17, §18, §20, §27): a workgroup per slot of the range
 template <int NL, class Pol>
 __global__ __launch_bounds__(SW_THREADS, (ReSw<NL, Pol>::OCC)) void k_sc_lds(DBatch b, DScen q) {
     SlotView<Pol> v(b, q);
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(64) void k_rs_fin(DBatch b, DReann q) {
     q.rec[c] = re_record(meta, b.dist + (size_t)meta->node_off * b.dist_stride, q.dist0 + (size_t)meta->node_off * q.stride0, re_mode_req(q.mode[c]) ? &q.nreq[c] : nullptr);
 }
 
-// a thread per slot of the whole table: plain, pinned or biased
+// a thread per slot of the whole table: plain, pinned, biased or both
 __global__ __launch_bounds__(64) void k_sc_fin(DBatch b, DScen q) {
     const int s = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (s >= q.n_slot) return;
@@ -273,12 +273,13 @@ __global__ __launch_bounds__(64) void k_sc_fin(DBatch b, DScen q) {
     q.rec[s] = re_record(meta, q.dist + q.slot[s].dist0, q.dist0 + (size_t)meta->node_off * q.stride0, q.slot[s].pinned ? &q.nreq[s] : nullptr);
 }
 
-// ---- the slots' marks (DESIGN.md §17, §18, §20) ----
+// ---- the slots' marks (DESIGN.md §17, §18, §20, §27) ----
 // A chunk's slot table holds the plain slots, then the pinned ones (required ORFs, solved under REQ: n_node x (NL + 1) words of distances
-// and a required slice, DScen.req at req0), then the biased ones (solved under BIAS with BLIST).  A biased slot keeps no word per in-edge
+// and a required slice, DScen.req at req0), then the biased ones (solved under BIAS with BLIST), then the ones that are both (pinned = 1 AND
+// a DScBias: everything a pinned and everything a biased slot owns, solved under REQ with BIAS and BLIST).  A biased slot keeps no word per in-edge
 // slot (a dense slice would be 8 E bytes, more than everything else the slot owns): it has a bias bitmap slice (DScen.bbit at DScBias.bbit0)
 // and a list of (in-edge slot of the batch, B) pairs sorted by in-edge slot, which the shared code searches where the slot's bit is set
-// (bias_at under BLIST, phx_sssp.inc).  The three mask kernels below get the whole table (a pair's or a triple's slot is its index in it);
+// (bias_at under BLIST, phx_sssp.inc).  The three mask kernels below get the whole table, so a "both" slot is marked by all three (a pair's or a triple's slot is its index in it);
 // a slot's refused slice is set by k_sc_mask whatever its range.  Gene records come from the chunk's shared counter as in §14; the tie
 // scratch from the chunk's bump allocator (DTotals.tie_need).
 
@@ -354,7 +355,8 @@ __global__ __launch_bounds__(NT) void k_sce_mask(DBatch b, DScen q) {
 
 // the staged pairs of a biased slot into its list in ascending order of their in-edge slot.  A pair's place is the number of pairs in
 // front of it (an equal in-edge slot: the one staged earlier), found by counting — a list is at most a contig's ORFs.  gridDim.y
-// workgroups share a slot's pairs, NT at a time; the keys they count over pass through LDS in tiles of NT.  q: the biased range.
+// workgroups share a slot's pairs, NT at a time; the keys they count over pass through LDS in tiles of NT.  q: the biased range with the
+// "both" range directly behind it (one launch sorts the lists of either).
 __global__ __launch_bounds__(NT) void k_sce_sort(DScen q) {
     __shared__ long long s_key[NT];
     const DScBias bs = q.bs[blockIdx.x];

@@ -358,7 +358,7 @@ __host__ __device__ inline size_t sssp_lds_bytes(int V, int nl) {
 // BIAS: an explicit row whose bit is set in `bbit` carries W + B, B the signed 64-bit word of its in-edge slot in `bval` (read only where
 // the bit is set; DESIGN.md §19).  A bonus can make a cycle negative: the sweep and round caps end such a solve, and an unreached node
 // stays at the unreached pattern as under REQ.
-// REQ and BIAS together (never BLIST; DESIGN.md §22): a row weighs W + B - M·[required], on one limb more as under REQ; the count guard and
+// REQ and BIAS together (DESIGN.md §22; with BLIST §27): a row weighs W + B - M·[required], on one limb more as under REQ; the count guard and
 // the caps are both active.  The tile path then carries three flags per prefetched row — refused and required in r_mk as under REQ, biased
 // in a register of its own (r_mb), which no other policy has.
 // BLIST (always BIAS): `bval` is not a word per in-edge slot but the solve's own list of (in-edge slot of the batch, B) pairs, sorted by
@@ -424,7 +424,6 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const ui
     constexpr int RING = P::RING, ECAP = P::ECAP;
     constexpr int EPT = (ECAP + SW_THREADS - 1) / SW_THREADS; // tile edges prefetched per thread
     static_assert(EPT <= 16, "r_mk and r_mb hold 16 flags per field");
-    static_assert(!(P::REQ && P::BLIST), "a list-biased slot with required ORFs: under REQ bits 16.. of r_mk are the required flags, which the BLIST block below reads as biased ones");
     extern __shared__ __align__(16) uint8_t smem[];
     __shared__ int s_flag[2];
     __shared__ int s_np, s_nclose, s_viol;
@@ -491,7 +490,7 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const ui
         if (tid == 0) s_viol = 0;
         __syncthreads();
         // registers that carry window k+1's data while window k iterates; bit j of r_mk: tile edge j of this thread is refused, bit 16 + j: required (REQ) or biased (BIAS
-        // alone); under REQ and BIAS together bit 16 + j is the required flag and bit j of r_mb the biased one
+        // alone); under REQ and BIAS together (with or without BLIST) bit 16 + j is the required flag and bit j of r_mb the biased one
         uint32_t r_src[EPT];
         long long r_w[EPT];
         uint32_t r_mk = 0;
@@ -558,8 +557,8 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const ui
                         // source slot: a ring slot, or the constant-zero slot (the source node; and sources outside the
                         // ring, whose distance cannot change while this window iterates and is folded into the weight)
                         uint32_t sl = RING;
-                        if constexpr (P::REQ && P::BIAS) { // both: B first, then the top limb (W + B - M)
-                            if ((r_mb >> j) & 1u) w = wi_add<NL>(w, ew_decode<NL>(bias_at<false>(bval, ebase + e0 + i, nbl)));
+                        if constexpr (P::REQ && P::BIAS) { // both: B first, then the top limb (W + B - M); under BLIST the block below adds B
+                            if constexpr (!P::BLIST) { if ((r_mb >> j) & 1u) w = wi_add<NL>(w, ew_decode<NL>(bias_at<false>(bval, ebase + e0 + i, nbl))); }
                             if ((r_mk >> (16 + j)) & 1u) w.v[NL - 1] -= 1ull;
                         } else {
                             if (P::REQ && ((r_mk >> (16 + j)) & 1u)) w.v[NL - 1] -= 1ull; // required: W - M, so the phases pay nothing for it either
@@ -577,13 +576,14 @@ __device__ __forceinline__ void lds_sweep(const DBatch &b, DMeta *meta, const ui
                 // BLIST: B comes from a search of the slot's list, kept out of the unrolled loop above and done here, where the
                 // prefetched rows are no longer live — a thread with a biased row in its part of the tile (rare: a scenario biases
                 // a few ORFs) adds B to the entry it has just written; a refused row stays no edge
-                // (bits 16.. of r_mk are the biased flags here: a BLIST policy is never REQ, see the static_assert above)
+                // (the biased flags: bits 16.. of r_mk, or r_mb under REQ, where those bits are the required flags — the entry then holds
+                // W - M on SNL limbs and takes B second; addition is modular, so that is §22's W + B - M; DESIGN.md §27)
                 if constexpr (P::BLIST) {
-                    if (r_mk >> 16) {
+                    if (P::REQ ? r_mb : r_mk >> 16) {
 #pragma nounroll
                         for (int j = 0; j < EPT; j++) {
                             const int i = tid + j * SW_THREADS;
-                            if (i < ne && ((r_mk >> (16 + j)) & 1u) && !((r_mk >> j) & 1u))
+                            if (i < ne && (((P::REQ ? r_mb >> j : r_mk >> (16 + j))) & 1u) && !((r_mk >> j) & 1u))
                                 wi_store<NL>(tw + (size_t)i * NL, wi_add<NL>(wi_load<NL>(tw + (size_t)i * NL), ew_decode<NL>(bias_at<true>(bval, ebase + e0 + i, nbl))));
                         }
                     }
