@@ -9,10 +9,11 @@ the batches go round the first N GPUs of the node — one process, one host thre
 contigs are then sharded across ranks (phanotate_amd.shard) and rank 0 writes the output in input order.
 """
 import argparse
+import collections
 import os
 import sys
 
-from . import __version__
+from . import __version__, _lib
 from .api import Annotator, make_params
 from .writers import FORMATS, write
 
@@ -55,84 +56,50 @@ def get_args(argv=None):
     p.add_argument("--pin-margins", metavar="FILE", default=None, help="also write every ORF with its path margin and the kept ORFs of --require that the best path through it gives up (DESIGN.md §24) to FILE: the format of --margins with a LOST column behind MARGIN; needs --require and --reannotation")
     p.add_argument("--single-device-ranks", action="store_true", help=argparse.SUPPRESS)  # tests: every rank of a sharded launch on GPU `--device` (gloo-only group)
     args = p.parse_args(argv)
-    if args.margins is not None and args.dump:
-        p.error("argument --margins: not allowed with argument -d/--dump")
-    if args.margins is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        p.error("argument --margins: not available under a multi-rank launch")
-    if args.drop_margins is not None and args.dump:
-        p.error("argument --drop-margins: not allowed with argument -d/--dump")
-    if args.drop_margins is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        p.error("argument --drop-margins: not available under a multi-rank launch")
-    if args.drop_replacements is not None and args.dump:
-        p.error("argument --drop-replacements: not allowed with argument -d/--dump")
-    if args.drop_replacements is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        p.error("argument --drop-replacements: not available under a multi-rank launch")
-    if args.start_drops is not None and args.dump:
-        p.error("argument --start-drops: not allowed with argument -d/--dump")
-    if args.start_drops is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        p.error("argument --start-drops: not available under a multi-rank launch")
-    if args.start_drops is not None and int(args.gpus) > 1:  # the scenarios work on the batch resident on one context
-        p.error("argument --start-drops: not available with --gpus above 1")
-    if args.alt_starts is not None and args.dump:
-        p.error("argument --alt-starts: not allowed with argument -d/--dump")
-    if args.alt_starts is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        p.error("argument --alt-starts: not available under a multi-rank launch")
-    if args.alt_starts is not None and int(args.gpus) > 1:  # the scenarios work on the batch resident on one context
-        p.error("argument --alt-starts: not available with --gpus above 1")
-    if args.evidence_scan is not None and args.dump:
-        p.error("argument --evidence-scan: not allowed with argument -d/--dump")
-    if args.evidence_scan is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        p.error("argument --evidence-scan: not available under a multi-rank launch")
-    if args.evidence_scan is not None and int(args.gpus) > 1:  # the scenarios work on the batch resident on one context
-        p.error("argument --evidence-scan: not available with --gpus above 1")
-    if args.curated_scan is not None and args.dump:
-        p.error("argument --curated-scan: not allowed with argument -d/--dump")
-    if args.curated_scan is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        p.error("argument --curated-scan: not available under a multi-rank launch")
-    if args.curated_scan is not None and int(args.gpus) > 1:  # the scenarios work on the batch resident on one context
-        p.error("argument --curated-scan: not available with --gpus above 1")
-    if args.curated_scan is not None and args.require is None:
-        p.error("argument --curated-scan: needs --require")
-    if args.remargins is not None and args.dump:
-        p.error("argument --remargins: not allowed with argument -d/--dump")
-    if args.remargins is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        p.error("argument --remargins: not available under a multi-rank launch")
-    if args.remargins is not None and int(args.gpus) > 1:  # the re-annotation works on the batch resident on one context
-        p.error("argument --remargins: not available with --gpus above 1")
-    if args.remargins is not None and args.require is not None:  # (margins under required ORFs: DESIGN.md §21, Limits)
-        p.error("argument --remargins: not allowed with argument --require")
-    if args.remargins is not None and args.reannotation is None:
-        p.error("argument --remargins: needs --reannotation")
-    if args.pin_margins is not None and args.dump:
-        p.error("argument --pin-margins: not allowed with argument -d/--dump")
-    if args.pin_margins is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        p.error("argument --pin-margins: not available under a multi-rank launch")
-    if args.pin_margins is not None and int(args.gpus) > 1:  # the re-annotation works on the batch resident on one context
-        p.error("argument --pin-margins: not available with --gpus above 1")
-    if args.pin_margins is not None and args.require is None:
-        p.error("argument --pin-margins: needs --require")
-    if args.pin_margins is not None and args.reannotation is None:
-        p.error("argument --pin-margins: needs --reannotation")
-    for flag, val in (("--forbid", args.forbid), ("--require", args.require), ("--evidence", args.evidence), ("--reannotation", args.reannotation)):
-        if val is not None and args.dump:
-            p.error("argument %s: not allowed with argument -d/--dump" % flag)
-        if val is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
-            p.error("argument %s: not available under a multi-rank launch" % flag)
-    if args.evidence is not None and args.require is not None:  # (required sets and biases in one solve: DESIGN.md §19, Limits)
-        p.error("argument --evidence: not allowed with argument --require")
-    if args.evidence is not None and args.reannotation is None:
-        p.error("argument --evidence: needs --reannotation")
-    if args.evidence is not None and int(args.gpus) > 1:
-        p.error("argument --evidence: not available with --gpus above 1")
-    if args.require is None and args.evidence is None and (args.forbid is None) != (args.reannotation is None):
-        p.error("arguments --forbid and --reannotation: each needs the other")
-    if args.require is not None and args.reannotation is None:
-        p.error("argument --require: needs --reannotation")
-    if args.forbid is not None and int(args.gpus) > 1:  # the re-annotation works on the batch resident on one context
-        p.error("argument --forbid: not available with --gpus above 1")
-    if args.require is not None and int(args.gpus) > 1:
-        p.error("argument --require: not available with --gpus above 1")
+    for applies, message in _refusals(args, int(os.environ.get("WORLD_SIZE", "1"))):
+        if applies:
+            p.error(message)
     return args
+
+
+# The relations between flags: (the flag a rule is about or None, whether it applies to args with that flag present, the message).
+_RULES = (
+    ("curated_scan", lambda a: a.require is None, "argument --curated-scan: needs --require"),
+    ("remargins", lambda a: a.require is not None, "argument --remargins: not allowed with argument --require"),  # (margins under required ORFs: DESIGN.md §21, Limits)
+    ("remargins", lambda a: a.reannotation is None, "argument --remargins: needs --reannotation"),
+    ("pin_margins", lambda a: a.require is None, "argument --pin-margins: needs --require"),
+    ("pin_margins", lambda a: a.reannotation is None, "argument --pin-margins: needs --reannotation"),
+    ("evidence", lambda a: a.require is not None, "argument --evidence: not allowed with argument --require"),  # (required sets and biases in one solve: DESIGN.md §19, Limits)
+    ("evidence", lambda a: a.reannotation is None, "argument --evidence: needs --reannotation"),
+    (None, lambda a: a.require is None and a.evidence is None and (a.forbid is None) != (a.reannotation is None), "arguments --forbid and --reannotation: each needs the other"),
+    ("require", lambda a: a.reannotation is None, "argument --require: needs --reannotation"),
+)
+# The flags of OUTPUTS and INPUTS in the order get_args looks at them.
+_CHECK_ORDER = ("margins", "drop_margins", "drop_replacements", "start_drops", "alt_starts", "evidence_scan", "curated_scan", "remargins", "pin_margins", "forbid", "require", "evidence", "reannotation")
+
+
+def _refusals(args, world):
+    """(applies, message) of every refusal of get_args.  THE ORDER IS CONTRACT: a user whose command line breaks several rules is told
+    the first one, and tests pin which.  Flag by flag in _CHECK_ORDER: -d/--dump, a multi-rank launch and, for a side
+    output, --gpus above 1 where it works on the batch resident on one context, then the rules of _RULES about it; behind all flags the
+    other rules, in their order, and last --gpus above 1 for the entry files (the re-annotation works on the resident batch too)."""
+    flags = {x.dest: x.flag for x in (*OUTPUTS.values(), *INPUTS.values())}
+    has = lambda dest: dest is None or getattr(args, dest) is not None
+    gpus = lambda dest: (int(args.gpus) > 1, "argument %s: not available with --gpus above 1" % flags[dest])
+    for dest in filter(has, _CHECK_ORDER):
+        yield args.dump, "argument %s: not allowed with argument -d/--dump" % flags[dest]
+        yield world > 1, "argument %s: not available under a multi-rank launch" % flags[dest]
+        if dest in OUTPUTS:
+            if OUTPUTS[dest].resident:
+                yield gpus(dest)
+            for about, applies, message in _RULES:
+                if about == dest:
+                    yield applies(args), message
+    for about, applies, message in _RULES:
+        if about not in OUTPUTS and has(about):
+            yield applies(args), message
+    for dest in filter(has, INPUTS):
+        yield gpus(dest)
 
 
 def format_pin_margins(names, status, offsets, records, lost):
@@ -140,16 +107,32 @@ def format_pin_margins(names, status, offsets, records, lost):
     >= 0 "#id:\t<name>", the header, one row per ORF with through == 1 (START STOP FRAME CONTIG SCORE MARGIN LOST CALLED), ordered by
     left, right, strand.  `lost` is parallel to `records` (Annotator.pinmargins())."""
     out = []
-    for i, nm in enumerate(names):
-        if status[i] < 0:
-            continue
+    for nm, cut in _blocks(names, status, offsets):
         out.append("#id:\t%s\n#START\tSTOP\tFRAME\tCONTIG\tSCORE\tMARGIN\tLOST\tCALLED\n" % nm)
-        rec, lo = records[offsets[i]:offsets[i + 1]], lost[offsets[i]:offsets[i + 1]]
-        rows = sorted((int(r["left"]), int(r["right"]), int(r["strand"]), k) for k, r in enumerate(rec) if r["through"])
-        for left, right, strand, k in rows:
-            a, z = (right, left) if strand < 0 else (left, right)  # as the tabular writer
-            out.append("%d\t%d\t%s\t%s\t%E\t%E\t%d\t%d\n" % (a, z, "-" if strand < 0 else "+", nm, float(rec["score"][k]), float(rec["margin"][k]), int(lo[k]), 1 if rec["called"][k] else 0))
+        rec, lo = records[cut], lost[cut]
+        for _, _, _, k in sorted((int(r["left"]), int(r["right"]), int(r["strand"]), k) for k, r in enumerate(rec) if r["through"]):
+            out.append("%d\t%d\t%s\t" % _ends(rec[k]) + "%s\t%E\t%E\t%d\t%d\n" % (nm, float(rec["score"][k]), float(rec["margin"][k]), int(lo[k]), 1 if rec["called"][k] else 0))
     return "".join(out).encode()
+
+
+def _blocks(names, status, offsets):
+    """(name, slice of its records) of every contig with status >= 0: the contigs the side outputs print a block for."""
+    for i, nm in enumerate(names):
+        if status[i] >= 0:
+            yield nm, slice(offsets[i], offsets[i + 1])
+
+
+def _ends(r):
+    """(START, STOP, FRAME) of a record as the tabular output prints a gene: START > STOP on the reverse strand (locus.py:44-46)."""
+    return (int(r["right"]), int(r["left"]), "-") if r["strand"] < 0 else (int(r["left"]), int(r["right"]), "+")
+
+
+def _delta(status, delta, unmet=0):
+    """The DELTA column: "cycle" (PHX_S_NEGCYCLE), then "unmet" (a required ORF cannot be called), then "inf" (no path, or no result),
+    else repr(delta)."""
+    import math
+
+    return "cycle" if status == -9 else "unmet" if unmet != 0 else "inf" if status != 0 or not math.isfinite(delta) else repr(float(delta))
 
 
 class ForbidError(ValueError):
@@ -179,11 +162,17 @@ def parse_forbid(lines, flag="--forbid"):
 def resolve_forbid(entries, names, lookup, flag="--forbid"):
     """Per contig of `names` the ORF indices the entries of parse_forbid name (None: none); lookup(i, left, right, strand) is
     Annotator.orf_index.  A line that names no ORF of its contig raises ForbidError quoting the line."""
+    return _resolve(entries, names, lookup, flag, lambda k, entry: k)
+
+
+def _resolve(entries, names, lookup, flag, item):
+    """The walk of resolve_forbid and resolve_evidence: item(ORF index, entry) is what a contig's list gains per entry."""
     where = {}
     for i, nm in enumerate(names):
         where.setdefault(nm, i)
     out = [None] * len(names)
-    for left, right, strand, contig, line in entries:
+    for entry in entries:
+        left, right, strand, contig, line = entry[:5]
         try:
             i = where[contig]
             k = lookup(i, left, right, strand)
@@ -191,7 +180,7 @@ def resolve_forbid(entries, names, lookup, flag="--forbid"):
             raise ForbidError("%s: no such ORF in its contig: %r" % (flag, line)) from None
         if out[i] is None:
             out[i] = []
-        out[i].append(k)
+        out[i].append(item(k, entry))
     return out
 
 
@@ -217,20 +206,7 @@ def parse_evidence(lines, flag="--evidence"):
 def resolve_evidence(entries, names, lookup, flag="--evidence"):
     """Per contig of `names` the (ORF index, BIAS) pairs the entries of parse_evidence name (None: none), as Annotator.evidence takes them:
     an ORF named twice appears twice and gets the sum there.  Errors as resolve_forbid."""
-    where = {}
-    for i, nm in enumerate(names):
-        where.setdefault(nm, i)
-    out = [None] * len(names)
-    for left, right, strand, contig, line, b in entries:
-        try:
-            i = where[contig]
-            k = lookup(i, left, right, strand)
-        except KeyError:
-            raise ForbidError("%s: no such ORF in its contig: %r" % (flag, line)) from None
-        if out[i] is None:
-            out[i] = []
-        out[i].append((k, b))
-    return out
+    return _resolve(entries, names, lookup, flag, lambda k, entry: (k, entry[5]))
 
 
 def format_evidence_scan(names, status, offsets, records):
@@ -240,24 +216,11 @@ def format_evidence_scan(names, status, offsets, records):
     ORF (1 / 0), and the genes the run's annotation loses and gains."""
     import io
 
-    import numpy as np
-
     buf = io.StringIO()
-    for i, nm in enumerate(names):
-        if status[i] < 0:
-            continue
+    for nm, cut in _blocks(names, status, offsets):
         buf.write("#id:\t" + nm + "\n#START\tSTOP\tFRAME\tBIAS\tDELTA\tCALLED\tREMOVED\tADDED\n")
-        for r in records[offsets[i]:offsets[i + 1]]:
-            rev = r["strand"] < 0
-            left, right = (int(r["right"]), int(r["left"])) if rev else (int(r["left"]), int(r["right"]))  # locus.py:44-46
-            if r["status"] == -9:
-                delta = "cycle"
-            elif r["status"] != 0 or not np.isfinite(r["delta"]):
-                delta = "inf"
-            else:
-                delta = repr(float(r["delta"]))
-            buf.write("%d\t%d\t%s\t%s\t%s\t%d\t%d\t%d\n" % (left, right, chr(44 - (-1 if rev else 1)), repr(float(r["bias"])), delta, int(r["called"]), int(r["n_removed"]),
-                                                          int(r["n_added"])))
+        for r in records[cut]:
+            buf.write("%d\t%d\t%s\t" % _ends(r) + "%s\t%s\t%d\t%d\t%d\n" % (repr(float(r["bias"])), _delta(r["status"], r["delta"]), int(r["called"]), int(r["n_removed"]), int(r["n_added"])))
     return buf.getvalue()
 
 
@@ -268,25 +231,16 @@ def format_curated_scan(names, status, offsets, records):
     and UNMET, the required ORFs the new annotation does not call."""
     import io
 
-    import numpy as np
-
-    def cost(st, delta):
-        return "cycle" if st == -9 else "inf" if st != 0 or not np.isfinite(delta) else repr(float(delta))
-
     buf = io.StringIO()
-    for i, nm in enumerate(names):
-        if status[i] < 0:
-            continue
+    for nm, cut in _blocks(names, status, offsets):
         buf.write("#id:\t" + nm + "\n")
-        recs = records[offsets[i]:offsets[i + 1]]
+        recs = records[cut]
         if len(recs):
-            buf.write("#base:\t%s\t%d\n" % (cost(recs[0]["base_status"], recs[0]["base_delta"]), int(recs[0]["base_unmet"])))
+            buf.write("#base:\t%s\t%d\n" % (_delta(recs[0]["base_status"], recs[0]["base_delta"]), int(recs[0]["base_unmet"])))
         buf.write("#START\tSTOP\tFRAME\tBIAS\tDELTA\tCALLED\tREMOVED\tADDED\tUNMET\n")
         for r in recs:
-            rev = r["strand"] < 0
-            left, right = (int(r["right"]), int(r["left"])) if rev else (int(r["left"]), int(r["right"]))  # locus.py:44-46
-            buf.write("%d\t%d\t%s\t%s\t%s\t%d\t%d\t%d\t%d\n" % (left, right, chr(44 - (-1 if rev else 1)), repr(float(r["bias"])), cost(r["status"], r["delta"]), int(r["called"]),
-                                                                int(r["n_removed"]), int(r["n_added"]), int(r["unmet"])))
+            buf.write("%d\t%d\t%s\t" % _ends(r) + "%s\t%s\t%d\t%d\t%d\t%d\n" % (repr(float(r["bias"])), _delta(r["status"], r["delta"]), int(r["called"]), int(r["n_removed"]), int(r["n_added"]),
+                                                                              int(r["unmet"])))
     return buf.getvalue()
 
 
@@ -298,7 +252,7 @@ def format_reannotation(names, status, offsets, genes, delta, unmet=None):
     from .writers import write_tabular
 
     buf = io.StringIO()
-    for i, nm in enumerate(names):
+    for i, nm in enumerate(names):  # (not _blocks: delta and unmet go by the contig's index)
         if status[i] < 0:
             continue
         one = io.StringIO()
@@ -315,19 +269,14 @@ def format_start_drops(names, status, offsets, records):
     import io
 
     buf = io.StringIO()
-    for i, nm in enumerate(names):
-        if status[i] < 0:
-            continue
+    for nm, cut in _blocks(names, status, offsets):
         buf.write("#id:\t" + nm + "\n#START\tSTOP\tFRAME\tDROP\tRESTART\n")
-        for r in records[offsets[i]:offsets[i + 1]]:
-            rev = r["strand"] < 0
-            left, right = (int(r["right"]), int(r["left"])) if rev else (int(r["left"]), int(r["right"]))  # locus.py:44-46
+        for r in records[cut]:
             if r["restart"] >= 0:
-                a, b = (int(r["restart_right"]), int(r["restart_left"])) if rev else (int(r["restart_left"]), int(r["restart_right"]))
-                tail = "%d\t%d" % (a, b)
+                tail = "%d\t%d" % ((int(r["restart_right"]), int(r["restart_left"])) if r["strand"] < 0 else (int(r["restart_left"]), int(r["restart_right"])))
             else:
                 tail = "-"
-            buf.write("%d\t%d\t%s\t%s\t%s\n" % (left, right, chr(44 - (-1 if rev else 1)), repr(float(r["drop"])), tail))
+            buf.write("%d\t%d\t%s\t" % _ends(r) + "%s\t%s\n" % (repr(float(r["drop"])), tail))
     return buf.getvalue()
 
 
@@ -338,26 +287,12 @@ def format_alt_starts(names, status, offsets, records):
     "unmet" (the alternative cannot be called) or "inf" (no path) —, and the genes the run's annotation loses and gains."""
     import io
 
-    import numpy as np
-
     buf = io.StringIO()
-    for i, nm in enumerate(names):
-        if status[i] < 0:
-            continue
+    for nm, cut in _blocks(names, status, offsets):
         buf.write("#id:\t" + nm + "\n#START\tSTOP\tFRAME\tALT\tDELTA\tREMOVED\tADDED\n")
-        for r in records[offsets[i]:offsets[i + 1]]:
-            rev = r["strand"] < 0
-            left, right = (int(r["right"]), int(r["left"])) if rev else (int(r["left"]), int(r["right"]))  # locus.py:44-46
-            alt = int(r["alt_right"]) if rev else int(r["alt_left"])
-            if r["status"] == -9:
-                delta = "cycle"
-            elif r["unmet"] != 0:
-                delta = "unmet"
-            elif r["status"] != 0 or not np.isfinite(r["delta"]):
-                delta = "inf"
-            else:
-                delta = repr(float(r["delta"]))
-            buf.write("%d\t%d\t%s\t%d\t%s\t%d\t%d\n" % (left, right, chr(44 - (-1 if rev else 1)), alt, delta, int(r["n_removed"]), int(r["n_added"])))
+        for r in records[cut]:
+            alt = int(r["alt_right"]) if r["strand"] < 0 else int(r["alt_left"])
+            buf.write("%d\t%d\t%s\t" % _ends(r) + "%d\t%s\t%d\t%d\n" % (alt, _delta(r["status"], r["delta"], r["unmet"]), int(r["n_removed"]), int(r["n_added"])))
     return buf.getvalue()
 
 
@@ -367,109 +302,147 @@ def dump_edges(out, ann, i, seq=None, start_codons="atg:0.85,gtg:0.10,ttg:0.05")
     out.write(ann.dump_text(i).decode())
 
 
-def format_tabular(names, status, offsets, genes):
-    """locus.py:39-56 for a run of contigs, as bytes (libphx's phx_format_tabular)."""
+def _format_c(fn, names, status, offsets, *arrays):
+    """The text one of libphx's phx_format_* functions prints for a run of contigs, as bytes.  fn(n, names, *arrays, offsets, status,
+    &text, &length): `arrays` holds (array, dtype or None) per record array, in the function's order."""
     import ctypes as C
 
     import numpy as np
-
-    from . import _lib
 
     L = _lib.lib()
     n = len(names)
     enc = [x.encode() for x in names]
     arr = (C.c_char_p * max(n, 1))(*enc)
-    status = np.ascontiguousarray(status, np.int32)
-    offsets = np.ascontiguousarray(offsets, np.int64)
-    genes = np.ascontiguousarray(genes)
+    held = [np.ascontiguousarray(a, dt) for a, dt in arrays] + [np.ascontiguousarray(offsets, np.int64), np.ascontiguousarray(status, np.int32)]
     text, tlen = C.c_void_p(), C.c_int64()
-    vp = lambda x: x.ctypes.data_as(C.c_void_p)
-    rc = L.phx_format_tabular(n, arr, vp(genes), vp(offsets), vp(status), C.byref(text), C.byref(tlen))
+    rc = getattr(L, fn)(n, arr, *[x.ctypes.data_as(C.c_void_p) for x in held], C.byref(text), C.byref(tlen))
     if rc:
-        raise _lib.PhxError(rc, "phx_format_tabular")
+        raise _lib.PhxError(rc, fn)
     out = C.string_at(text.value, tlen.value)
     L.phx_free_text(text)
     return out
+
+
+def format_tabular(names, status, offsets, genes):
+    """locus.py:39-56 for a run of contigs, as bytes (libphx's phx_format_tabular)."""
+    return _format_c("phx_format_tabular", names, status, offsets, (genes, None))
 
 
 def format_margins(names, status, offsets, records):
     """--margins FILE for a run of contigs, as bytes (libphx's phx_format_margins): per contig with status >= 0 "#id:\t<name>", the
     header, one row per ORF with through == 1 (START STOP FRAME CONTIG SCORE MARGIN CALLED), ordered by left, right, strand."""
-    import ctypes as C
-
-    import numpy as np
-
-    from . import _lib
-
-    L = _lib.lib()
-    n = len(names)
-    enc = [x.encode() for x in names]
-    arr = (C.c_char_p * max(n, 1))(*enc)
-    status = np.ascontiguousarray(status, np.int32)
-    offsets = np.ascontiguousarray(offsets, np.int64)
-    records = np.ascontiguousarray(records, _lib.MARGIN_DT)
-    text, tlen = C.c_void_p(), C.c_int64()
-    vp = lambda x: x.ctypes.data_as(C.c_void_p)
-    rc = L.phx_format_margins(n, arr, vp(records), vp(offsets), vp(status), C.byref(text), C.byref(tlen))
-    if rc:
-        raise _lib.PhxError(rc, "phx_format_margins")
-    out = C.string_at(text.value, tlen.value)
-    L.phx_free_text(text)
-    return out
+    return _format_c("phx_format_margins", names, status, offsets, (records, _lib.MARGIN_DT))
 
 
 def format_replacements(names, status, offsets, records, genes):
     """--drop-replacements FILE for a run of contigs, as bytes (libphx's phx_format_replacements): per contig with status >= 0
     "#id:\t<name>", the header, one row per called gene of the device path (START STOP FRAME CONTIG DROP REMOVED ADDED), in path order;
     records[k]["gene_off"] indexes genes."""
-    import ctypes as C
-
-    import numpy as np
-
-    from . import _lib
-
-    L = _lib.lib()
-    n = len(names)
-    enc = [x.encode() for x in names]
-    arr = (C.c_char_p * max(n, 1))(*enc)
-    status = np.ascontiguousarray(status, np.int32)
-    offsets = np.ascontiguousarray(offsets, np.int64)
-    records = np.ascontiguousarray(records, _lib.REPL_DT)
-    genes = np.ascontiguousarray(genes, _lib.GENE_DT)
-    text, tlen = C.c_void_p(), C.c_int64()
-    vp = lambda x: x.ctypes.data_as(C.c_void_p)
-    rc = L.phx_format_replacements(n, arr, vp(records), vp(genes), vp(offsets), vp(status), C.byref(text), C.byref(tlen))
-    if rc:
-        raise _lib.PhxError(rc, "phx_format_replacements")
-    out = C.string_at(text.value, tlen.value)
-    L.phx_free_text(text)
-    return out
+    return _format_c("phx_format_replacements", names, status, offsets, (records, _lib.REPL_DT), (genes, _lib.GENE_DT))
 
 
 def format_drops(names, status, offsets, records):
     """--drop-margins FILE for a run of contigs, as bytes (libphx's phx_format_drops): per contig with status >= 0 "#id:\t<name>", the
     header, one row per called gene of the device path (START STOP FRAME CONTIG SCORE DROP CALLED), in path order."""
-    import ctypes as C
+    return _format_c("phx_format_drops", names, status, offsets, (records, _lib.DROP_DT))
 
+
+def _merge(parts):
+    """(status, offsets, *arrays) of a run of batches from the same of every batch, in order: the statuses concatenated, the offsets
+    rebuilt from every batch's counts, each further array concatenated."""
     import numpy as np
 
-    from . import _lib
+    counts = np.concatenate([np.diff(p[1]) for p in parts])
+    return (np.concatenate([p[0] for p in parts]), np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)) + tuple(np.concatenate(a) for a in list(zip(*parts))[2:])
 
-    L = _lib.lib()
-    n = len(names)
-    enc = [x.encode() for x in names]
-    arr = (C.c_char_p * max(n, 1))(*enc)
-    status = np.ascontiguousarray(status, np.int32)
-    offsets = np.ascontiguousarray(offsets, np.int64)
-    records = np.ascontiguousarray(records, _lib.DROP_DT)
-    text, tlen = C.c_void_p(), C.c_int64()
-    vp = lambda x: x.ctypes.data_as(C.c_void_p)
-    rc = L.phx_format_drops(n, arr, vp(records), vp(offsets), vp(status), C.byref(text), C.byref(tlen))
-    if rc:
-        raise _lib.PhxError(rc, "phx_format_drops")
-    out = C.string_at(text.value, tlen.value)
-    L.phx_free_text(text)
-    return out
+
+def _merge_replacements(parts):
+    """_merge for Annotator.replacements(): each batch's gene_off counts from its own genes."""
+    shifted, g0 = [], 0
+    for status, offsets, records, genes in parts:
+        records = records.copy()
+        records["gene_off"] += g0
+        g0 += len(genes)
+        shifted.append((status, offsets, records, genes))
+    return _merge(shifted)
+
+
+class _Entries:
+    """The lines of the entry files that name contigs of the batch resident on `ann`, as ORF indices: entries(dest) is what the resolver
+    of INPUTS[dest] makes of them ([None] per contig for a file not given), worked out when a fetch first asks for it and kept for the
+    batch — Annotator.orf_index is pure, so the re-annotation and the curated scan share one walk over --forbid and --require."""
+
+    def __init__(self, ann, names, lines):
+        self.ann, self.names, self.here, self.lines, self.done = ann, names, set(names), lines, {}
+
+    def __call__(self, dest):
+        if dest not in self.done:
+            mine = [e for e in self.lines.get(dest, ()) if e[3] in self.here]
+            self.done[dest] = INPUTS[dest].resolve(mine, self.names, self.ann.orf_index, INPUTS[dest].flag)
+        return self.done[dest]
+
+
+def _reannotate(ann, entries):
+    """The batch's second annotation, for --reannotation: under --evidence, or --require, or --forbid alone."""
+    refused = entries("forbid")
+    if "evidence" in entries.lines:
+        return ann.evidence(entries("evidence"), refused)
+    if "require" in entries.lines:
+        return ann.constrain(refused, entries("require"))
+    return ann.reannotate(refused)
+
+
+def _path(args, dest, half):
+    """The path a flag names: its value, or for a flag of two values (FILE OUT) that half of it."""
+    value = getattr(args, dest)
+    return value if isinstance(value, str) else value[half]
+
+
+_In = collections.namedtuple("_In", "flag dest parse resolve")
+_Out = collections.namedtuple("_Out", "flag dest fmt mode fetch resident piped merge")
+
+
+def _dest(flag):  # as argparse names it
+    return flag[2:].replace("-", "_")
+
+
+def _out(flag, fmt, mode, fetch, resident=False, piped=None, merge=_merge):
+    return _Out(flag, _dest(flag), fmt, mode, fetch, resident, piped, merge)
+
+
+# The entry files, in the order main opens and parses them: the flag as the messages name it (for the two scans the FILE half of the
+# flag's value), the parser of its lines and the resolver of its lines to ORF indices.  Each works on the batch resident on one context.
+INPUTS = {_dest(flag): _In(flag, _dest(flag), parse, resolve) for flag, parse, resolve in (
+    ("--curated-scan", parse_evidence, resolve_evidence),
+    ("--evidence-scan", parse_evidence, resolve_evidence),
+    ("--evidence", parse_evidence, resolve_evidence),
+    ("--forbid", parse_forbid, resolve_forbid),
+    ("--require", parse_forbid, resolve_forbid),
+)}
+# The side outputs, in the order main writes their files (for the two scans to the OUT half of the flag's value).  fmt(names, *merge(what
+# fetch(ann, entries) returned per batch)) is the file's content and mode how it is opened; resident: it works on the batch resident on one
+# context, so no --gpus above 1 and the batches one after the other; piped: the keyword under which Pipeline.run collects it (None: it
+# cannot) — the rows with one stand in the order of the members an item of Pipeline.run gains.
+OUTPUTS = {o.dest: o for o in (
+    _out("--margins", format_margins, "wb", lambda ann, entries: ann.margins(), piped="margins"),
+    _out("--remargins", format_margins, "wb", lambda ann, entries: ann.remargins(), resident=True),
+    _out("--pin-margins", format_pin_margins, "wb", lambda ann, entries: ann.pinmargins(), resident=True),
+    _out("--drop-margins", format_drops, "wb", lambda ann, entries: ann.drop_margins(), piped="drop_margins"),
+    _out("--drop-replacements", format_replacements, "wb", lambda ann, entries: ann.replacements(), piped="replacements", merge=_merge_replacements),
+    _out("--start-drops", format_start_drops, "w", lambda ann, entries: ann.start_drops()[:3], resident=True),
+    _out("--alt-starts", format_alt_starts, "w", lambda ann, entries: ann.alt_starts()[:3], resident=True),
+    _out("--evidence-scan", format_evidence_scan, "w", lambda ann, entries: ann.evidence_scan(entries("evidence_scan"))[:3], resident=True),
+    _out("--curated-scan", format_curated_scan, "w", lambda ann, entries: ann.curated_scan(entries("curated_scan"), entries("forbid"), entries("require"))[:3], resident=True),
+    _out("--reannotation", format_reannotation, "w", _reannotate),  # (format_reannotation's unmet: the fifth member constrain() returns, so only with --require)
+)}
+# A batch's fetches, in this order.  THE ORDER IS CONTRACT: the replacements in front of the drop margins (the drops are then computed
+# once); the curated scan behind the batch's re-annotation, which thereby stays the cached one; remargins and pinmargins behind the
+# re-annotation, whose margins they are.  The entry files are resolved where a fetch first needs them, so a line that names no ORF is
+# reported in the order --evidence-scan, --forbid, --evidence or --require, --curated-scan.
+_FETCH_ORDER = ("margins", "drop_replacements", "drop_margins", "start_drops", "alt_starts", "evidence_scan", "reannotation", "curated_scan", "remargins", "pin_margins")
+# The entry files in the order main looks for a line that names a contig the FASTA file does not hold.
+_UNKNOWN_ORDER = ("forbid", "require", "evidence", "evidence_scan", "curated_scan")
+assert set(_CHECK_ORDER) == set(OUTPUTS) | set(INPUTS) and set(_FETCH_ORDER) == set(OUTPUTS) and set(_UNKNOWN_ORDER) == set(INPUTS)  # a new row takes its place in each order
 
 
 def main(argv=None):
@@ -554,33 +527,14 @@ def main(argv=None):
         return 0
 
     n_total = len(fa)
-    margin_parts = []  # --margins: (status, offsets, records) of every batch, in order
-    drop_parts = []  # --drop-margins: the same of the drop margins
-    repl_parts = []  # --drop-replacements: (status, offsets, records, genes) of every batch, in order
-    start_parts = []  # --start-drops: (status, offsets, records) of every batch, in order
-    alt_parts = []  # --alt-starts: the same of Annotator.alt_starts()
-    reann_parts = []  # --reannotation: (status, offsets, genes, delta[, unmet]) of every batch, in order
-    remargin_parts = []  # --remargins: (status, offsets, records) of Annotator.remargins() of every batch, in order
-    pin_parts = []  # --pin-margins: (status, offsets, records, lost) of Annotator.pinmargins() of every batch, in order
-    scan_parts = []  # --evidence-scan: (status, offsets, records) of Annotator.evidence_scan() of every batch, in order
-    cscan_parts = []  # --curated-scan: (status, offsets, records) of Annotator.curated_scan() of every batch, in order
-    forbid_entries = require_entries = evidence_entries = scan_entries = cscan_entries = None
+    outputs = [o for o in OUTPUTS.values() if getattr(args, o.dest) is not None]
+    parts = {o.dest: [] for o in outputs}  # per side output what its fetch returned for every batch, in order
+    lines = {}  # per entry file given: its parsed lines
     try:
-        if args.curated_scan is not None:
-            with open(args.curated_scan[0]) as fh:
-                cscan_entries = parse_evidence(fh, "--curated-scan")
-        if args.evidence_scan is not None:
-            with open(args.evidence_scan[0]) as fh:
-                scan_entries = parse_evidence(fh, "--evidence-scan")
-        if args.evidence is not None:
-            with open(args.evidence) as fh:
-                evidence_entries = parse_evidence(fh)
-        if args.forbid is not None:
-            with open(args.forbid) as fh:
-                forbid_entries = parse_forbid(fh)
-        if args.require is not None:
-            with open(args.require) as fh:
-                require_entries = parse_forbid(fh, "--require")
+        for i in INPUTS.values():
+            if getattr(args, i.dest) is not None:
+                with open(_path(args, i.dest, 0)) as fh:
+                    lines[i.dest] = i.parse(fh, i.flag)
     except (OSError, ForbidError) as e:
         drop_context()
         sys.stderr.write("Error: %s\n" % e)
@@ -605,8 +559,8 @@ def main(argv=None):
             if lo >= len(idx):
                 break
         t_parts["batches"] = len(cuts)
-        if forbid_entries is not None or require_entries is not None or evidence_entries is not None or args.start_drops is not None or args.alt_starts is not None or scan_entries is not None:  # the re-annotation and the scenarios work on the batch resident on one context: the batches one after the other
-            parts = []
+        if lines or any(o.resident for o in outputs) or (len(cuts) == 1 and n_gpu == 1):  # the batches one after the other, each resident on the caller's context
+            flat, fetches = [], sorted(outputs, key=lambda o: _FETCH_ORDER.index(o.dest))
             for lo, hi in cuts:
                 t0 = time.perf_counter()
                 ann.upload_raw(fa.ptrs[idx[lo:hi]], fa.lens[idx[lo:hi]], fa)
@@ -614,56 +568,13 @@ def main(argv=None):
                 t1 = time.perf_counter()
                 ann.run()
                 t2 = time.perf_counter()
-                parts.append(ann.download_flat())
+                flat.append(ann.download_flat())
                 t3 = time.perf_counter()
-                if args.margins is not None:  # the siblings on the same resident batch, as in the one-batch branch below
-                    margin_parts.append(ann.margins())
-                if args.drop_replacements is not None:
-                    repl_parts.append(ann.replacements())
-                if args.drop_margins is not None:
-                    drop_parts.append(ann.drop_margins())
-                if args.start_drops is not None:
-                    start_parts.append(ann.start_drops()[:3])
-                if args.alt_starts is not None:
-                    alt_parts.append(ann.alt_starts()[:3])
-                names = [fa.names[int(i)] for i in idx[lo:hi]]
-                here = set(names)
-                if scan_entries is not None:
-                    scan_parts.append(ann.evidence_scan(resolve_evidence([e for e in scan_entries if e[3] in here], names, ann.orf_index, "--evidence-scan"))[:3])
-                refused = resolve_forbid([e for e in forbid_entries or [] if e[3] in here], names, ann.orf_index)
-                if evidence_entries is not None:
-                    reann_parts.append(ann.evidence(resolve_evidence([e for e in evidence_entries if e[3] in here], names, ann.orf_index), refused))
-                elif forbid_entries is None and require_entries is None:
-                    pass
-                elif require_entries is None:
-                    reann_parts.append(ann.reannotate(refused))
-                else:
-                    reann_parts.append(ann.constrain(refused, resolve_forbid([e for e in require_entries if e[3] in here], names, ann.orf_index, "--require")))
-                if cscan_entries is not None:  # (a scenario batch of its own: the batch's re-annotation above stays the cached one)
-                    cscan_parts.append(ann.curated_scan(resolve_evidence([e for e in cscan_entries if e[3] in here], names, ann.orf_index, "--curated-scan"), refused,
-                                                        resolve_forbid([e for e in require_entries if e[3] in here], names, ann.orf_index, "--require"))[:3])
-                if args.remargins is not None:  # (behind the batch's re-annotation: the margins are that solve's)
-                    remargin_parts.append(ann.remargins())
-                if args.pin_margins is not None:  # (likewise)
-                    pin_parts.append(ann.pinmargins())
+                # (without an entry file no work per contig here: the plain run is the one the benchmark times)
+                entries = _Entries(ann, [fa.names[int(i)] for i in idx[lo:hi]], lines) if lines else None
+                for o in fetches:
+                    parts[o.dest].append(o.fetch(ann, entries))
                 t_parts["upload_s"] += t1 - t0; t_parts["run_s"] += t2 - t1; t_parts["download_s"] += t3 - t2
-        elif len(cuts) == 1 and n_gpu == 1:
-            lo, hi = cuts[0]
-            t0 = time.perf_counter()
-            ann.upload_raw(fa.ptrs[idx[lo:hi]], fa.lens[idx[lo:hi]], fa)
-            ann.set_trnas(trnas_of(idx[lo:hi]))
-            t1 = time.perf_counter()
-            ann.run()
-            t2 = time.perf_counter()
-            parts = [ann.download_flat()]
-            t3 = time.perf_counter()
-            if args.margins is not None:
-                margin_parts.append(ann.margins())
-            if args.drop_replacements is not None:  # (before the drop margins: they are then computed once)
-                repl_parts.append(ann.replacements())
-            if args.drop_margins is not None:
-                drop_parts.append(ann.drop_margins())
-            t_parts["upload_s"] += t1 - t0; t_parts["run_s"] += t2 - t1; t_parts["download_s"] += t3 - t2
         else:  # a stream of batches: two in flight per GPU, the batches round the GPUs (pipeline.Pipeline)
             from .pipeline import Pipeline
 
@@ -672,34 +583,22 @@ def main(argv=None):
             t1 = time.perf_counter()
             gen = ((fa.ptrs[idx[lo:hi]], fa.lens[idx[lo:hi]], fa, (lambda a=lo, b=hi: trnas_of(idx[a:b]))) for lo, hi in cuts)
             try:
-                parts = list(pipe.run(gen, margins=args.margins is not None, drop_margins=args.drop_margins is not None, replacements=args.drop_replacements is not None))
+                flat = list(pipe.run(gen, **{o.piped: o.dest in parts for o in OUTPUTS.values() if o.piped}))
                 t2 = time.perf_counter()
-                k = 3
-                if args.margins is not None:
-                    margin_parts.extend(p[k] for p in parts)
-                    k += 1
-                if args.drop_margins is not None:
-                    drop_parts.extend(p[k] for p in parts)
-                    k += 1
-                if args.drop_replacements is not None:
-                    repl_parts.extend(p[k] for p in parts)
-                parts = [p[:3] for p in parts]
+                for k, o in enumerate(outputs, 3):  # (all of them Pipeline.run's on this path, and OUTPUTS lists those in the order of an item's members)
+                    parts[o.dest].extend(p[k] for p in flat)
+                flat = [p[:3] for p in flat]
             finally:
                 pipe.close()
             t_parts["contexts_s"] = t1 - t0; t_parts["pipeline_s"] = t2 - t1; t_parts["gpus"] = n_gpu
-        if len(parts) == 1:
-            return parts[0]
-        st = np.concatenate([p[0] for p in parts])
-        genes = np.concatenate([p[2] for p in parts])
-        counts = np.concatenate([np.diff(p[1]) for p in parts])
-        return st, np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), genes
+        return flat[0] if len(flat) == 1 else _merge(flat)
 
     known = set(fa.names)
-    for flag, entries in (("--forbid", forbid_entries), ("--require", require_entries), ("--evidence", evidence_entries), ("--evidence-scan", scan_entries), ("--curated-scan", cscan_entries)):
-        for e in entries or []:
+    for dest in _UNKNOWN_ORDER:
+        for e in lines.get(dest, ()):
             if e[3] not in known:
                 drop_context()
-                sys.stderr.write("Error: %s: no such ORF in its contig: %r\n" % (flag, e[4]))
+                sys.stderr.write("Error: %s: no such ORF in its contig: %r\n" % (INPUTS[dest].flag, e[4]))
                 return 2
     try:
         merged = run_sharded_flat(mine, annotate_flat, rank, world, dist, mine=(mine, n_total))
@@ -729,76 +628,9 @@ def main(argv=None):
                     write(args.outfile, args.format, fa.names[i], fa.seq(i).decode(), genes[offsets[i] : offsets[i + 1]])
             t_fmt = time.perf_counter()
         args.outfile.flush()
-        if args.margins is not None:
-            m_status = np.concatenate([m[0] for m in margin_parts])
-            m_counts = np.concatenate([np.diff(m[1]) for m in margin_parts])
-            m_offsets = np.concatenate([[0], np.cumsum(m_counts)]).astype(np.int64)
-            m_records = np.concatenate([m[2] for m in margin_parts])
-            with open(args.margins, "wb") as fh:
-                fh.write(format_margins(fa.names, m_status, m_offsets, m_records))
-        if args.remargins is not None:
-            x_status = np.concatenate([m[0] for m in remargin_parts])
-            x_counts = np.concatenate([np.diff(m[1]) for m in remargin_parts])
-            x_offsets = np.concatenate([[0], np.cumsum(x_counts)]).astype(np.int64)
-            with open(args.remargins, "wb") as fh:
-                fh.write(format_margins(fa.names, x_status, x_offsets, np.concatenate([m[2] for m in remargin_parts])))
-        if args.pin_margins is not None:
-            p_status = np.concatenate([m[0] for m in pin_parts])
-            p_counts = np.concatenate([np.diff(m[1]) for m in pin_parts])
-            p_offsets = np.concatenate([[0], np.cumsum(p_counts)]).astype(np.int64)
-            with open(args.pin_margins, "wb") as fh:
-                fh.write(format_pin_margins(fa.names, p_status, p_offsets, np.concatenate([m[2] for m in pin_parts]), np.concatenate([m[3] for m in pin_parts])))
-        if args.drop_margins is not None:
-            d_status = np.concatenate([m[0] for m in drop_parts])
-            d_counts = np.concatenate([np.diff(m[1]) for m in drop_parts])
-            d_offsets = np.concatenate([[0], np.cumsum(d_counts)]).astype(np.int64)
-            d_records = np.concatenate([m[2] for m in drop_parts])
-            with open(args.drop_margins, "wb") as fh:
-                fh.write(format_drops(fa.names, d_status, d_offsets, d_records))
-        if args.drop_replacements is not None:
-            r_status = np.concatenate([m[0] for m in repl_parts])
-            r_counts = np.concatenate([np.diff(m[1]) for m in repl_parts])
-            r_offsets = np.concatenate([[0], np.cumsum(r_counts)]).astype(np.int64)
-            r_records, r_genes, g0 = [], [], 0
-            for m in repl_parts:  # (each batch's gene_off counts from its own genes)
-                rr = m[2].copy()
-                rr["gene_off"] += g0
-                g0 += len(m[3])
-                r_records.append(rr)
-                r_genes.append(m[3])
-            with open(args.drop_replacements, "wb") as fh:
-                fh.write(format_replacements(fa.names, r_status, r_offsets, np.concatenate(r_records), np.concatenate(r_genes)))
-        if args.start_drops is not None:
-            s_status = np.concatenate([m[0] for m in start_parts])
-            s_counts = np.concatenate([np.diff(m[1]) for m in start_parts])
-            s_offsets = np.concatenate([[0], np.cumsum(s_counts)]).astype(np.int64)
-            with open(args.start_drops, "w") as fh:
-                fh.write(format_start_drops(fa.names, s_status, s_offsets, np.concatenate([m[2] for m in start_parts])))
-        if args.alt_starts is not None:
-            a_status = np.concatenate([m[0] for m in alt_parts])
-            a_counts = np.concatenate([np.diff(m[1]) for m in alt_parts])
-            a_offsets = np.concatenate([[0], np.cumsum(a_counts)]).astype(np.int64)
-            with open(args.alt_starts, "w") as fh:
-                fh.write(format_alt_starts(fa.names, a_status, a_offsets, np.concatenate([m[2] for m in alt_parts])))
-        if args.evidence_scan is not None:
-            e_status = np.concatenate([m[0] for m in scan_parts])
-            e_counts = np.concatenate([np.diff(m[1]) for m in scan_parts])
-            e_offsets = np.concatenate([[0], np.cumsum(e_counts)]).astype(np.int64)
-            with open(args.evidence_scan[1], "w") as fh:
-                fh.write(format_evidence_scan(fa.names, e_status, e_offsets, np.concatenate([m[2] for m in scan_parts])))
-        if args.curated_scan is not None:
-            c_status = np.concatenate([m[0] for m in cscan_parts])
-            c_counts = np.concatenate([np.diff(m[1]) for m in cscan_parts])
-            c_offsets = np.concatenate([[0], np.cumsum(c_counts)]).astype(np.int64)
-            with open(args.curated_scan[1], "w") as fh:
-                fh.write(format_curated_scan(fa.names, c_status, c_offsets, np.concatenate([m[2] for m in cscan_parts])))
-        if args.reannotation is not None:
-            q_status = np.concatenate([m[0] for m in reann_parts])
-            q_counts = np.concatenate([np.diff(m[1]) for m in reann_parts])
-            q_offsets = np.concatenate([[0], np.cumsum(q_counts)]).astype(np.int64)
-            with open(args.reannotation, "w") as fh:
-                fh.write(format_reannotation(fa.names, q_status, q_offsets, np.concatenate([m[2] for m in reann_parts]), np.concatenate([m[3] for m in reann_parts]),
-                                             np.concatenate([m[4] for m in reann_parts]) if args.require is not None else None))
+        for o in outputs:
+            with open(_path(args, o.dest, 1), o.mode) as fh:
+                fh.write(o.fmt(fa.names, *o.merge(parts[o.dest])))
     t_end = time.perf_counter()
     if os.environ.get("PHX_CLI_TIMING") and rank == 0:
         sys.stderr.write("PHX_CLI_TIMING " + json.dumps({"parse_s": round(t_parsed - t_start, 4), "gpu_s": round(t_gpu - t_parsed, 4), "format_s": round(t_fmt - t_gpu, 4),
