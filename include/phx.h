@@ -47,7 +47,8 @@ extern "C" {
  *        (addition, version unchanged) phx_evidence_scenarios_flat — probe for the symbol;
  *        (additions, version unchanged) phx_remargins_flat, phx_remargins_ms, phx_tap_redist — probe for the symbol;
  *        (additions, version unchanged) phx_pinmargins_flat, phx_pinmargins_ms, phx_tap_pindist — probe for the symbol;
- *        (addition, version unchanged) phx_curate_scenarios_flat — probe for the symbol */
+ *        (addition, version unchanged) phx_curate_scenarios_flat — probe for the symbol;
+ *        (additions, version unchanged) phx_redrops_flat, phx_redrops_ms, phx_redrop_stats — probe for the symbol */
 #define PHX_MAX_CODONS 16
 
 /* library-level errors */
@@ -514,6 +515,33 @@ int phx_remargins_ms(phx_ctx *ctx, float *ms /* [4] */);
  * unreached node has a top word >= 2^61).  A contig that was not solved again: the run's vectors (phx_tap_dist / phx_tap_dist_target);
  * one whose re-solve left no such vector (an error; no path for d_t'): every node unreached.  PHX_E_STATE as phx_remargins_flat. */
 int phx_tap_redist(phx_ctx *ctx, int32_t contig, int32_t which, uint64_t *dist_limbs, int64_t cap_words);
+
+/* ---- re-annotation drop margins: the support of every call under a mask or bias ----
+ * phx_drop_margins_flat on the graph of the last re-annotation of the batch last run — the re-annotations phx_remargins_flat covers.  For a
+ * contig solved again under the refused set F and the bias B with status 0, G', R, d_s', d_t' and D' are phx_remargins_flat's and
+ * P' = p_0 ... p_K is the re-annotation's device path (phx_tap_repath).  A called gene is a CDS ORF edge of P', its stop node p_j as for
+ * phx_drop_margins_flat; D'_{-g} is the shortest source -> target distance under W' = W + B in G' without p_j, which is the D of
+ * phx_evidence_flat(B, F + every ORF of the gene's stop group).  drop = float(D'_{-g} - D') / 1000.0 as phx_drop_margins_flat rounds it,
+ * >= 0, bypass = 1; bypass = 0 and drop = +inf when no path of G' avoids the stop node.  score is what the re-annotation call's gene
+ * record carries (the ORF's weight without the bias); called = 1 iff the gene is among the genes that call returns for the contig (the
+ * device's lists; no host re-solve enters).  Every value fits the contig's own limbs (§29, with phx_evidence_flat's biased bound).
+ * Records as phx_drop_margins_flat (rec == NULL: size query), in path order.  status[i]:
+ *   a run error (< 0) or PHX_S_OVERFLOW without device distances: that status, no records;
+ *   a contig that was not solved again: phx_drop_margins_flat's status and records, byte for byte;
+ *   solved again with a status < 0: that status, no records;  solved again, PHX_S_NOPATH: status 1, no records (no gene is called);
+ *   solved again, status 0: the records as defined; PHX_S_NEGCYCLE without records if the conditioned reverse pass hit its caps.
+ * PHX_E_STATE, before any kernel, without a re-annotation of this run, and when a contig of the last one was solved under the required
+ * policy (drops under required ORFs, where the dropped gene may be a pin, are a different definition).  Computed at the first call after a
+ * re-annotation solve, on top of phx_remargins_flat's computation (and phx_drop_margins_flat's when a contig was not solved again), in
+ * buffers of its own; kept until the next solve or run.  Nothing the other entry points return changes.  (Additions, version unchanged:
+ * probe for the symbol.) */
+int phx_redrops_flat(phx_ctx *ctx, phx_gene_drop *rec, int64_t cap, int64_t *offsets /* [n+1] */, int32_t *status /* [n] */, int64_t *total);
+/* device time of the last computation of the re-annotation drop margins (HIP events), ms[4]: trees + labels, candidates + sparse table,
+ * fixups, the copy of the records to the host — the conditioned kernels alone (phx_remargins_ms and phx_drop_ms have the parts below
+ * them).  All 0 before the first. */
+int phx_redrops_ms(phx_ctx *ctx, float *ms /* [4] */);
+/* counters of the last computation, out[4], as phx_drop_stats, over the contigs that were solved again */
+int phx_redrop_stats(phx_ctx *ctx, int64_t *out /* [4] */);
 
 /* ---- pinned margins: per-ORF path margins under required ORFs ----
  * phx_remargins_flat for every re-annotation of the batch last run, phx_constrain_flat and phx_curate_flat with required ORFs included.  A

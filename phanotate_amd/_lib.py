@@ -179,6 +179,9 @@ def lib():
         "phx_remargins_flat": (C.c_int, [vp, vp, i64, vp, vp, P(i64)]),
         "phx_remargins_ms": (C.c_int, [vp, P(C.c_float)]),
         "phx_tap_redist": (C.c_int, [vp, i32, i32, vp, i64]),
+        "phx_redrops_flat": (C.c_int, [vp, vp, i64, vp, vp, P(i64)]),
+        "phx_redrops_ms": (C.c_int, [vp, P(C.c_float)]),
+        "phx_redrop_stats": (C.c_int, [vp, P(i64)]),
         "phx_pinmargins_flat": (C.c_int, [vp, vp, vp, i64, vp, vp, P(i64)]),
         "phx_pinmargins_ms": (C.c_int, [vp, P(C.c_float)]),
         "phx_tap_pindist": (C.c_int, [vp, i32, i32, vp, i64, P(i32)]),
@@ -235,4 +238,5 @@ EXPORTS = ["phx_version", "phx_device_count", "phx_strerror", "phx_last_error", 
            "phx_scenarios_flat", "phx_scenarios_ms", "phx_scenario_chunks", "phx_tap_scenario_path", "phx_pinned_scenarios_flat",
            "phx_evidence_scenarios_flat", "phx_curate_scenarios_flat",
            "phx_remargins_flat", "phx_remargins_ms", "phx_tap_redist",
-           "phx_pinmargins_flat", "phx_pinmargins_ms", "phx_tap_pindist"]
+           "phx_pinmargins_flat", "phx_pinmargins_ms", "phx_tap_pindist",
+           "phx_redrops_flat", "phx_redrops_ms", "phx_redrop_stats"]

@@ -72,6 +72,7 @@ _MS_KEYS = {
     "phx_scenarios_ms": ("mask", "solve", "finish"),
     "phx_remargins_ms": ("apply", "reverse", "margins", "download"),
     "phx_pinmargins_ms": ("apply", "reverse", "margins", "download"),
+    "phx_redrops_ms": ("trees", "candidates", "fixups", "download"),
     "phx_reannotate_ms": ("mask", "solve", "finish"),
 }
 
@@ -932,6 +933,27 @@ class Annotator:
     def remargins_ms(self):
         """Device time of the last re-annotation margins in ms: apply, conditioned reverse pass, records, copy to the host (phx_remargins_ms)."""
         return self._ms("phx_remargins_ms")
+
+    def redrops(self):
+        """(status int32[n], offsets int64[n+1], records structured array[total] of _lib.DROP_DT), as drop_margins() returns them: the
+        drop margin of every CDS gene of the last reannotate() or evidence() (or constrain() without required ORFs) of the batch last
+        run, in path order (phx_redrops_flat).  drop = float(D'_{-g} - D') / 1000 on the refused / biased graph: how much
+        worse the best annotation under the same mask and evidence becomes when nothing is called at the gene's stop — the delta
+        evidence() reports with the gene's whole stop group refused as well, minus the re-annotation's own; bypass = 0 and +inf when no
+        path avoids the stop.  called = 1 for the genes the re-annotation returned.  A contig that was not solved again has the records
+        of drop_margins().  PhxError (PHX_E_STATE) without a re-annotation of this run and after constrain() with required ORFs."""
+        (status,), offs, (rec,) = self._query_fill(self.L.phx_redrops_flat, "phx_redrops_flat", (), self.n, (_lib.DROP_DT,))
+        return status, offs, rec
+
+    def redrops_ms(self):
+        """Device time of the last re-annotation drop margins in ms: trees + labels, candidates, fixups, copy to the host (phx_redrops_ms)."""
+        return self._ms("phx_redrops_ms")
+
+    def redrop_stats(self):
+        """drop_stats() of the last re-annotation drop margins, over the contigs that were solved again (phx_redrop_stats)."""
+        out = (C.c_int64 * 4)()
+        self._chk(self.L.phx_redrop_stats(self.h, out), "phx_redrop_stats")
+        return dict(zip(("slots", "cross", "rescanned", "layered"), [int(x) for x in out]))
 
     def redist(self, i, to_target=False):
         """Exact distances of every node of contig i on the last re-annotation's graph as python ints (None: unreached), device node

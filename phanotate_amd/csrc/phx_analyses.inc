@@ -713,6 +713,7 @@ static int reann_flat(phx_ctx *c, const char *who, bool need_forbid, const uint8
         c->done.reann = false;
         c->done.remarg = false; // (the re-annotation margins are this solve's)
         c->done.pinmarg = false;
+        c->done.redrop = false;
         c->h_qsel.assign((size_t)c->n, 0);
         c->h_qnreq.assign((size_t)c->n, 0);
         for (int i = 0; i < c->n; i++) {
@@ -847,6 +848,12 @@ static int remarg_state(phx_ctx *c, const char *who) {
 // not solved again and the run's mstat —, CmPin on CmPlain.  Reads what the solve left resident (b_qforb, b_qbias, b_qmask, b_qbval,
 // b_qdist: nothing between a re-annotation and this call writes them — only reann_compute does, and the scenario batches own b_sc_*);
 // writes only m's buffers.  m.ms: the device time; the pinned margins' is that of both parts as computed for this solve.
+// the kernels' view of a policy's buffers (the fields DRmarg and DPmarg share; mw: words of one bitmap over the out-edge positions)
+extern "C++" template <class R> static void condmargins_args(const phx_ctx *c, const phx_ctx::CondMarg &m, size_t mw, R *r) {
+    r->sel = (const int32_t *)m.b_sel.p; r->ds = (const uint64_t *)c->b_qdist.p; r->ds_stride = c->qstride;
+    r->fbit = (uint32_t *)m.b_bit.p; r->bbit = r->fbit + mw; r->bval = (long long *)m.b_bval.p;
+    r->dist_t = (uint64_t *)m.b_dt.p; r->rec = (phx_orf_margin *)m.b_rec.p; r->mstat = (int32_t *)m.b_mstat.p;
+}
 extern "C++" template <class P> static int ensure_condmargins(phx_ctx *c) {
     phx_ctx::CondMarg &m = P::pinned ? c->pm : c->xm;
     bool &done = P::pinned ? c->done.pinmarg : c->done.remarg;
@@ -885,9 +892,7 @@ extern "C++" template <class P> static int ensure_condmargins(phx_ctx *c) {
     DReann q;
     reann_batch(c, &qb, &q);
     typename P::Rec r;
-    r.sel = (const int32_t *)m.b_sel.p; r.ds = (const uint64_t *)c->b_qdist.p; r.ds_stride = c->qstride;
-    r.fbit = (uint32_t *)m.b_bit.p; r.bbit = r.fbit + mw; r.bval = (long long *)m.b_bval.p;
-    r.dist_t = (uint64_t *)m.b_dt.p; r.rec = (phx_orf_margin *)m.b_rec.p; r.mstat = (int32_t *)m.b_mstat.p;
+    condmargins_args(c, m, mw, &r);
     if constexpr (P::pinned) { r.dt_stride = b.dist_stride + 1; r.rbit = r.fbit + 2 * mw; r.lost = (int32_t *)m.b_lost.p; }
     hipStream_t s = c->stream;
     HIPCHK(c, hipMemcpyAsync(m.b_sel.p, m.h_sel.data(), (n + 1) * 4, hipMemcpyHostToDevice, s));
@@ -922,6 +927,15 @@ static int32_t condmargins_status(const phx_ctx *c, int i) {
     return (re_mode_req(mode) ? c->pm : c->xm).mstat[(size_t)i] ? PHX_S_NEGCYCLE : 0;
 }
 
+// the sorted keys of the CDS genes the last re-annotation call returns for contig i (mode: its h_qsel; 0: the run's device list)
+static void resolve_keys(const phx_ctx *c, int i, int mode, std::vector<uint64_t> &keys) {
+    const DGene *src = resolve_genes(c, i, mode ? &c->h_qrec[(size_t)i] : nullptr, c->h_qgenes);
+    const int64_t ng = mode ? (int64_t)c->h_qrec[(size_t)i].n_genes : (int64_t)std::max(c->res[(size_t)i].n_genes, 0);
+    keys.clear();
+    for (int64_t k = 0; k < ng; k++) if (src[k].frame >= -3 && src[k].frame <= 3) keys.push_back(gene_key(src[k].left, src[k].right, src[k].strand));
+    std::sort(keys.begin(), keys.end());
+}
+
 // The layout of phx_margins_flat, phx_remargins_flat and phx_pinmargins_flat, behind their ensure_*: offsets and statuses, then the records
 // in reference order with `called` set.  again: false for the run's margins (no contig counts as solved again, `called` is against the genes
 // phx_download* deliver), else against the genes the re-annotation call returns — the device's lists, no host re-solve enters.  lost: null
@@ -943,13 +957,7 @@ static int margins_out(phx_ctx *c, const char *who, bool again, phx_orf_margin *
         const int mode = again ? c->h_qsel[(size_t)i] : 0;
         const bool pinned = re_mode_req(mode);
         if (!again) called_keys(c, i, keys);
-        else {
-            const DGene *src = resolve_genes(c, i, mode ? &c->h_qrec[(size_t)i] : nullptr, c->h_qgenes);
-            const int64_t ng = mode ? (int64_t)c->h_qrec[(size_t)i].n_genes : (int64_t)std::max(c->res[(size_t)i].n_genes, 0);
-            keys.clear();
-            for (int64_t k = 0; k < ng; k++) if (src[k].frame >= -3 && src[k].frame <= 3) keys.push_back(gene_key(src[k].left, src[k].right, src[k].strand));
-            std::sort(keys.begin(), keys.end());
-        }
+        else resolve_keys(c, i, mode, keys);
         // the device's records, in the reference's order
         phx_orf_margin *dst = rec + offsets[i];
         int32_t *ldst = lost ? lost + offsets[i] : nullptr;
@@ -1032,6 +1040,157 @@ int phx_remargins_ms(phx_ctx *c, float *ms) {
 int phx_pinmargins_ms(phx_ctx *c, float *ms) {
     if (!c || !ms) return PHX_E_ARG;
     for (int k = 0; k < 4; k++) ms[k] = c->pm.ms[k];
+    return PHX_OK;
+}
+
+// ---- re-annotation drop margins (phx_drop.inc under MgDrop, DESIGN.md §29) ----
+// the contigs the conditioned drop kernels cover (dp_on<MgDrop>), after ensure_condmargins<CmPlain>
+static bool redrop_contig(const phx_ctx *c, size_t i) { return c->h_qsel[i] && c->xm.h_sel[i] == 1 && !c->xm.mstat[i] && c->h_qrec[i].n_path >= 3; }
+
+// The records of every pair of every re-annotation path into c->h_rdrec (at c->rdroff), once per re-annotation solve.  On top of the
+// re-annotation margins (the out-edge bitmaps, d_t' and the pass's verdicts: their ORF records come with them, a launch and a copy beside
+// the reverse pass) and, when a contig was not solved again, of the run's drop margins.  Reads what the solve and its margins left resident;
+// writes only the b_rd* set: the run's drops and replacements stay as they are.
+static int ensure_redrops(phx_ctx *c) {
+    if (c->done.redrop) return PHX_OK;
+    { const int rm = ensure_condmargins<CmPlain>(c); if (rm) return rm; }
+    const size_t n = (size_t)c->n, V = (size_t)c->tot_node, E = (size_t)c->tot_edge;
+    bool unsolved = false;
+    for (size_t i = 0; i < n; i++) unsolved = unsolved || !c->h_qsel[i];
+    if (unsolved) { const int rd = ensure_drops(c); if (rd) return rd; }
+    const size_t limbs = (size_t)std::max(c->n_limbs, 2);
+    std::vector<int64_t> off(2 * n + 2, 0); // toff[n], roff[n + 1]
+    c->rdroff.assign(n + 1, 0);
+    int64_t tcells = 0, R = 0;
+    int nlm = 0;
+    for (size_t i = 0; i < n; i++) {
+        off[n + i] = R; c->rdroff[i] = R;
+        if (!redrop_contig(c, i)) continue;
+        nlm |= nl_class_bit(c->meta[i].sssp_nl);
+        const int np = c->h_qrec[i].n_path;
+        const int64_t cells = drop_cells(np);
+        if (cells > DP_TAB_LDS) { off[i] = tcells; tcells += cells; }
+        R += (np - 1) / 2;
+    }
+    off[2 * n] = R; c->rdroff[n] = R;
+    for (int k = 0; k < 4; k++) { c->redrop_ms[k] = 0; c->redrop_stats[k] = 0; }
+    if (!nlm) { c->done.redrop = true; return PHX_OK; }
+    int rc;
+    const size_t nv = (V + n + 1) * 4;
+    if ((rc = ensure(c, c->b_rdpi, nv)) || (rc = ensure(c, c->b_rdjs, nv)) || (rc = ensure(c, c->b_rdjt, nv)) || (rc = ensure(c, c->b_rdfi, nv)) || (rc = ensure(c, c->b_rdla, nv))) return rc;
+    if ((rc = ensure(c, c->b_rdslot, (V + 1) * 8))) return rc;
+    if ((rc = ensure(c, c->b_rdgtab, ((size_t)tcells + 1) * 8))) return rc;
+    if ((rc = ensure(c, c->b_rdtro, (2 * n + 2) * 8))) return rc;
+    if ((rc = ensure(c, c->b_rdsx, ((size_t)R + 1) * limbs * 8)) || (rc = ensure(c, c->b_rdcx, ((size_t)R + 1) * limbs * 8))) return rc;
+    if ((rc = ensure(c, c->b_rdda, (V + 1) * limbs * 8)) || (rc = ensure(c, c->b_rddb, (V + 1) * limbs * 8))) return rc;
+    if ((rc = ensure(c, c->b_rdrec, ((size_t)R + 1) * sizeof(phx_gene_drop)))) return rc;
+    if ((rc = ensure(c, c->b_rdstats, 4 * 8))) return rc;
+    if ((rc = analysis_events(c))) return rc;
+    try { c->h_rdrec.resize((size_t)R + 1); } catch (const std::bad_alloc &) { c->err = "out of memory in phx_redrops_flat"; return PHX_E_NOMEM; }
+    DBatch b;
+    fill_batch(c, &b);
+    DMarg g;
+    margins_args(c, &g);
+    DBatch qb;
+    DReann rq;
+    reann_batch(c, &qb, &rq);
+    DRmarg r;
+    condmargins_args(c, c->xm, E / 32 + 2, &r);
+    DDrop q;
+    q.pidx = (int32_t *)c->b_rdpi.p; q.js = (int32_t *)c->b_rdjs.p; q.jt = (int32_t *)c->b_rdjt.p; q.first = (int32_t *)c->b_rdfi.p; q.last = (int32_t *)c->b_rdla.p;
+    q.slot = (uint64_t *)c->b_rdslot.p; q.gtab = (uint64_t *)c->b_rdgtab.p;
+    q.toff = (const int64_t *)c->b_rdtro.p; q.roff = (const int64_t *)c->b_rdtro.p + n;
+    q.sx = (uint64_t *)c->b_rdsx.p; q.cx = (uint64_t *)c->b_rdcx.p; q.da = (uint64_t *)c->b_rdda.p; q.db = (uint64_t *)c->b_rddb.p;
+    q.rec = (phx_gene_drop *)c->b_rdrec.p; q.stats = (unsigned long long *)c->b_rdstats.p;
+    { DDrop env; drop_args(c, &env); q.layered = env.layered; } // (env PHX_DROP_LAYERED, read where the run's drops read it)
+    q.ps = nullptr; q.ts = nullptr;
+    const int32_t *qpath = (const int32_t *)c->b_qpath.p;
+    hipStream_t s = c->stream;
+    unsigned long long st[4] = {0, 0, 0, 0};
+    HIPCHK(c, hipEventRecord(c->aev[0], s));
+    HIPCHK(c, hipMemcpyAsync(c->b_rdtro.p, off.data(), (2 * n + 2) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(c->b_rdstats.p, 0, 4 * 8, s));
+    phxk_redrop_trees(&b, &g, &rq, &r, qpath, &q, nlm, s);
+    HIPCHK(c, hipEventRecord(c->aev[1], s));
+    phxk_redrop_cand(&b, &g, &rq, &r, qpath, &q, nlm, s);
+    HIPCHK(c, hipEventRecord(c->aev[2], s));
+    phxk_redrop_fix(&b, &g, &rq, &r, qpath, &q, nlm, s);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->aev[3], s));
+    if (R) HIPCHK(c, hipMemcpyAsync(c->h_rdrec.data(), c->b_rdrec.p, (size_t)R * sizeof(phx_gene_drop), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipEventRecord(c->aev[4], s));
+    HIPCHK(c, hipMemcpyAsync(st, c->b_rdstats.p, sizeof st, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    for (int k = 0; k < 4; k++) { c->redrop_ms[k] = ev_ms(c->aev[k], c->aev[k + 1]); c->redrop_stats[k] = (int64_t)st[k]; }
+    c->done.redrop = true;
+    return PHX_OK;
+}
+
+int phx_redrops_flat(phx_ctx *c, phx_gene_drop *rec, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
+    if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
+    { const int ra = after_run(c); if (ra) return ra; }
+    { const int rs = remarg_state(c, "phx_redrops_flat"); if (rs) return rs; } // before any kernel
+    { const int rd = ensure_redrops(c); if (rd) return rd; }
+    try {
+    // the contigs that were not solved again: the run's drop margins, as phx_drop_margins_flat lays them out
+    const size_t n = (size_t)c->n;
+    bool unsolved = false;
+    for (size_t i = 0; i < n; i++) unsolved = unsolved || !c->h_qsel[i];
+    std::vector<int64_t> off0(n + 1, 0);
+    std::vector<int32_t> st0(n, 0);
+    std::vector<phx_gene_drop> rec0;
+    if (unsolved) {
+        int64_t t0 = 0;
+        { const int rd = phx_drop_margins_flat(c, nullptr, 0, off0.data(), st0.data(), &t0); if (rd) return rd; }
+        if (rec) {
+            rec0.resize((size_t)t0 + 1);
+            const int rd = phx_drop_margins_flat(c, rec0.data(), t0, off0.data(), st0.data(), &t0);
+            if (rd) return rd;
+        }
+    }
+    auto genes_of = [&](size_t i) -> int64_t {
+        int64_t k = 0;
+        for (int64_t x = c->rdroff[i]; x < c->rdroff[i + 1]; x++) k += c->h_rdrec[(size_t)x].called >= 0;
+        return k;
+    };
+    int64_t total = 0;
+    for (size_t i = 0; i < n; i++) {
+        offsets[i] = total;
+        if (!c->h_qsel[i]) { status[i] = st0[i]; total += off0[i + 1] - off0[i]; continue; }
+        status[i] = condmargins_status(c, (int)i);
+        if (status[i] == 0 && redrop_contig(c, i)) total += genes_of(i);
+    }
+    offsets[n] = total;
+    if (total_out) *total_out = total;
+    if (!rec) return PHX_OK; // size query
+    if (cap < total) return PHX_E_ARG;
+    std::vector<uint64_t> keys;
+    for (size_t i = 0; i < n; i++) {
+        if (offsets[i + 1] == offsets[i]) continue;
+        phx_gene_drop *dst = rec + offsets[i];
+        if (!c->h_qsel[i]) { memcpy(dst, rec0.data() + off0[i], (size_t)(off0[i + 1] - off0[i]) * sizeof(phx_gene_drop)); continue; }
+        resolve_keys(c, (int)i, c->h_qsel[i], keys);
+        for (int64_t k = c->rdroff[i]; k < c->rdroff[i + 1]; k++) {
+            const phx_gene_drop &x = c->h_rdrec[(size_t)k];
+            if (x.called < 0) continue;
+            *dst = x;
+            dst->called = is_called(keys, x.left, x.right, x.strand) ? 1 : 0;
+            dst++;
+        }
+    }
+    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_redrops_flat"; return PHX_E_NOMEM; }
+    return PHX_OK;
+}
+
+int phx_redrops_ms(phx_ctx *c, float *ms) {
+    if (!c || !ms) return PHX_E_ARG;
+    for (int k = 0; k < 4; k++) ms[k] = c->redrop_ms[k];
+    return PHX_OK;
+}
+
+int phx_redrop_stats(phx_ctx *c, int64_t *out) {
+    if (!c || !out) return PHX_E_ARG;
+    for (int k = 0; k < 4; k++) out[k] = c->redrop_stats[k];
     return PHX_OK;
 }
 

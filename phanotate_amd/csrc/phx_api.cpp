@@ -241,6 +241,7 @@ struct phx_ctx {
         bool scen = false;    // h_s* hold the scenario batch h_skey
         bool remarg = false;  // xm.h_rec / xm.mstat hold the margins of the re-annotation h_q* hold (also reset by every re-annotation solve)
         bool pinmarg = false; // pm.h_rec / pm.h_lost / pm.mstat hold the pinned margins of the re-annotation h_q* hold (reset wherever remarg is)
+        bool redrop = false;  // h_rdrec holds the drop margins of the re-annotation h_q* hold, at rdroff (reset wherever remarg is)
         bool grp = false;     // h_grp
     } done;
     std::vector<DGrp> h_grp;         // the run's group records (device order <-> reference order of the ORFs: each_group_in_reference_order)
@@ -296,6 +297,13 @@ struct phx_ctx {
         std::vector<int32_t> h_lost;     // ... and their `lost` (pm alone)
         float ms[4] = {0, 0, 0, 0};      // phx_remargins_ms / phx_pinmargins_ms
     } xm, pm;
+    // re-annotation drop margins (phx_redrops_flat): a second DDrop set, allocated at the first call that has a contig for it; the
+    // result kept until the next re-annotation solve or run.  The run's own drops and replacements (b_d*, b_r*) are not touched.
+    DevBuf b_rdpi, b_rdjs, b_rdjt, b_rdfi, b_rdla, b_rdslot, b_rdgtab, b_rdtro, b_rdsx, b_rdcx, b_rdda, b_rddb, b_rdrec, b_rdstats;
+    std::vector<int64_t> rdroff;        // per contig (+1): first record in h_rdrec (a contig that is not covered: none)
+    std::vector<phx_gene_drop> h_rdrec; // a record per pair of the re-annotation's path
+    float redrop_ms[4] = {0, 0, 0, 0};
+    int64_t redrop_stats[4] = {0, 0, 0, 0};
     // scenario batches (phx_scenarios_flat): buffers of their own, allocated at the first call; the result kept until the next upload or run
     DevBuf b_sc_slot, b_sc_pair, b_sc_meta, b_sc_dist, b_sc_parent, b_sc_path, b_sc_mask, b_sc_plan, b_sc_genes, b_sc_rec, b_sc_tot, b_sc_gtot, b_sc_tie, b_sc_pin, b_sc_bs, b_sc_trip, b_sc_blist;
     int64_t scen_budget = (int64_t)2 << 30; // device bytes of a chunk's slots (env PHX_SCEN_BYTES at phx_create)

@@ -73,6 +73,73 @@ __device__ __forceinline__ WInt<NL> wave_min(WInt<NL> x) {
 }
 __device__ __forceinline__ uint64_t ld_l2(const uint64_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
+// The policy of the five kernels is the type of their second argument, as for k_sssp_rev and k_margins (phx_margins.inc).  DMarg: the run's
+// graph and path, the kernels as §12 describes them.  MgDrop (the re-annotation drop margins, DESIGN.md §29): MgCond — the graph G' = G_{F,B}
+// of the last re-annotation — and the re-annotation's device path P' (MgCond has every other input; the path is the one pointer it lacks, and
+// a field added to DRmarg or DDrop would move the argument blocks of kernels that exist).  Everything the policy adds sits behind
+// if constexpr (mg_cond<G>): the DMarg instantiations are the code they were without it.  Under MgDrop
+//   the path is g.path, its length DReannRec.n_path; d_s' comes from DRmarg.ds (ds_stride words per node reserved), d_t' from DRmarg.dist_t,
+//   D' = d_s'(target); the contigs are those with DRmarg.sel == 1 whose conditioned reverse pass settled;
+//   a node outside R (d_s' unreached) has no d_t' either — k_sssp_rev<NL, MgCond> never relaxes it — so it gets no label, no candidate,
+//   no place among the cross nodes: the values are those of G'[R];
+//   in-edge slot e (bit edge_off + e) is skipped where it is set in DReann.mask and weighs W + DReann.bval where it is set in DReann.bbit
+//   (read for a contig solved under the bias policy only: no call clears that bitmap before one biases a contig); out-edge position e is
+//   treated likewise through DRmarg.fbit / bbit / bval.  As in k_sssp_rev, the bitmaps are read per edge only for a node whose edge range
+//   shares a bitmap word with a refused or biased slot (`special`): a re-annotation's are a handful per contig.
+struct MgDrop : MgCond { const int32_t *path; };
+template <class G>
+__device__ __forceinline__ bool dp_on(const DBatch &b, const G &g, const DMeta *meta) {
+    if constexpr (mg_cond<G>) { const int i = (int)(meta - b.meta); return g.r.sel[i] == 1 && mg_contig(meta) && !g.r.mstat[i] && g.q.rec[i].n_path >= 3; }
+    else return dp_contig(b, g, meta);
+}
+template <class G>
+__device__ __forceinline__ int dp_npath(const DBatch &b, const G &g, const DMeta *meta) {
+    if constexpr (mg_cond<G>) return g.q.rec[meta - b.meta].n_path;
+    else return meta->n_path;
+}
+template <class G>
+__device__ __forceinline__ const int32_t *dp_path(const DBatch &b, const G &g, const DMeta *meta) {
+    if constexpr (mg_cond<G>) return g.path + meta->node_off;
+    else return b.path + meta->node_off;
+}
+template <class G>
+__device__ __forceinline__ const uint64_t *dp_ds(const DBatch &b, const G &g, const DMeta *meta) {
+    if constexpr (mg_cond<G>) return g.r.ds + (size_t)meta->node_off * g.r.ds_stride;
+    else return b.dist + (size_t)meta->node_off * b.dist_stride;
+}
+template <class G>
+__device__ __forceinline__ const uint64_t *dp_dt(const DBatch &b, const G &g, const DMeta *meta) {
+    if constexpr (mg_cond<G>) return g.r.dist_t + (size_t)meta->node_off * b.dist_stride;
+    else return g.dist_t + (size_t)meta->node_off * b.dist_stride;
+}
+// `special` of a node's in-edge slots / out-edge positions [e0, e1) (MgDrop only)
+template <class G>
+__device__ __forceinline__ bool dp_sp_in(const G &g, bool biased, uint64_t ebase, uint32_t e0, uint32_t e1) {
+    bool sp = false;
+    if (e1 > e0)
+        for (uint64_t x = (ebase + e0) >> 5, x1 = (ebase + e1 - 1) >> 5; x <= x1; x++) sp = sp || (g.q.mask[x] | (biased ? g.q.bbit[x] : 0u)) != 0u;
+    return sp;
+}
+template <class G>
+__device__ __forceinline__ bool dp_sp_out(const G &g, uint64_t ebase, uint32_t e0, uint32_t e1) {
+    bool sp = false;
+    if (e1 > e0)
+        for (uint64_t x = (ebase + e0) >> 5, x1 = (ebase + e1 - 1) >> 5; x <= x1; x++) sp = sp || (g.r.fbit[x] | g.r.bbit[x]) != 0u;
+    return sp;
+}
+// W' of in-edge slot x / out-edge position x of the batch, given W (the caller has skipped a refused one); under DMarg: W.  A call stands
+// where the weight stood, so that the DMarg code keeps its order of loads.
+template <int NL, class G>
+__device__ __forceinline__ WInt<NL> dp_w_in(const G &g, bool sp, bool biased, uint64_t x, WInt<NL> w) {
+    if constexpr (mg_cond<G>) { if (sp && biased && mg_bit(g.q.bbit, x)) w = wi_add<NL>(w, ew_decode<NL>(g.q.bval[x])); }
+    return w;
+}
+template <int NL, class G>
+__device__ __forceinline__ WInt<NL> dp_w_out(const G &g, bool sp, uint64_t x, WInt<NL> w) {
+    if constexpr (mg_cond<G>) { if (sp && mg_bit(g.r.bbit, x)) w = wi_add<NL>(w, ew_decode<NL>(g.r.bval[x])); }
+    return w;
+}
+
 // ---- 1. k_dp_tree<NL>: trees and labels, one workgroup per contig ----
 // DDrop.js / jt: the jump pointers (a node on P points at itself; -1: unreached), then first / last.  DDrop.ps / ts, when not null,
 // keep the one-hop parents / successors the labels were built from (the layered build: the node a node joined through).  The doubling
@@ -80,14 +147,15 @@ __device__ __forceinline__ uint64_t ld_l2(const uint64_t *p) { return __hip_atom
 // ceil(log2 V) + 1 rounds reach P from any chain that reaches it at all; a node whose pointer is then still off P sits on a tight
 // zero-length cycle of the chosen parents, and the tree is rebuilt by layers: round r lets a node join through a tight edge to a node that joined before round r (P itself is layer 0),
 // which cannot close a cycle.  DDrop.layered forces the layered build (env PHX_DROP_LAYERED, the tests).
-template <int NL>
-__global__ __launch_bounds__(NT) void k_dp_tree(DBatch b, DMarg g, DDrop q) {
+template <int NL, class G = DMarg>
+__global__ __launch_bounds__(NT) void k_dp_tree(DBatch b, G g, DDrop q) {
+    constexpr bool COND = mg_cond<G>;
     __shared__ int s_fail[2], s_chg;
     const DMeta *meta = &b.meta[blockIdx.x];
-    if (!dp_contig(b, g, meta) || meta->sssp_nl != NL) return;
-    const int V = meta->n_node, n = meta->n_path, tid = threadIdx.x;
+    if (!dp_on<G>(b, g, meta) || meta->sssp_nl != NL) return;
+    const int V = meta->n_node, n = dp_npath<G>(b, g, meta), tid = threadIdx.x;
     const size_t no = (size_t)meta->node_off;
-    const int32_t *path = b.path + no;
+    const int32_t *path = dp_path<G>(b, g, meta);
     const uint32_t *in_off = b.in_off + no + blockIdx.x;
     const uint32_t *esrc = b.esrc + meta->edge_off;
     const long long *ew = b.ew + meta->edge_off;
@@ -95,8 +163,11 @@ __global__ __launch_bounds__(NT) void k_dp_tree(DBatch b, DMarg g, DDrop q) {
     const uint32_t *oo = g.out_off + no + blockIdx.x;
     const uint32_t *od = g.out_dst + meta->edge_off;
     const long long *ow = g.out_w + meta->edge_off;
-    const uint64_t *ds = b.dist + no * b.dist_stride;
-    const uint64_t *dt = g.dist_t + no * b.dist_stride;
+    const uint64_t *ds = dp_ds<G>(b, g, meta);
+    const uint64_t *dt = dp_dt<G>(b, g, meta);
+    [[maybe_unused]] const uint64_t ebase = (uint64_t)meta->edge_off;
+    [[maybe_unused]] bool biased = false;
+    if constexpr (COND) biased = re_mode_bias(g.q.mode[blockIdx.x]);
     int32_t *pidx = q.pidx + no, *js = q.js + no, *jt = q.jt + no, *first = q.first + no, *last = q.last + no;
     for (int v = tid; v < V; v += NT) pidx[v] = -1;
     if (tid < 2) s_fail[tid] = q.layered;
@@ -111,20 +182,26 @@ __global__ __launch_bounds__(NT) void k_dp_tree(DBatch b, DMarg g, DDrop q) {
             const WInt<NL> dv = wi_load<NL>(ds + (size_t)v * NL);
             if (!wi_unreached<NL>(dv)) {
                 ps = -2; // (a reached node without a tight in-edge cannot occur: the layered build then leaves it out)
+                [[maybe_unused]] bool sp = false;
+                if constexpr (COND) sp = dp_sp_in(g, biased, ebase, in_off[v], in_off[v + 1]);
                 for (uint32_t e = in_off[v], e1 = in_off[v + 1]; e < e1; e++) {
                     const uint32_t sw = esrc[e];
+                    if constexpr (COND) { if (sp && mg_bit(g.q.mask, ebase + e)) continue; }
                     const WInt<NL> du = wi_load<NL>(ds + (size_t)ESRC_NODE(sw) * NL);
-                    if (!wi_unreached<NL>(du) && wi_eq<NL>(wi_add<NL>(du, ew_decode<NL>(edge_wenc(sw, ew, e, gt))), dv)) { ps = (int)ESRC_NODE(sw); break; }
+                    if (!wi_unreached<NL>(du) && wi_eq<NL>(wi_add<NL>(du, dp_w_in<NL>(g, sp, biased, ebase + e, ew_decode<NL>(edge_wenc(sw, ew, e, gt)))), dv)) { ps = (int)ESRC_NODE(sw); break; }
                 }
             }
             const WInt<NL> tv = wi_load<NL>(dt + (size_t)v * NL);
             if (!wi_unreached<NL>(tv)) {
                 ts = -2;
+                [[maybe_unused]] bool sp = false;
+                if constexpr (COND) sp = dp_sp_out(g, ebase, oo[v], oo[v + 1]);
                 for (uint32_t e = oo[v], e1 = oo[v + 1]; e < e1; e++) {
                     const int z = (int)od[e];
                     if (ts >= 0 && z >= ts) continue;
+                    if constexpr (COND) { if (sp && mg_bit(g.r.fbit, ebase + e)) continue; }
                     const WInt<NL> tz = wi_load<NL>(dt + (size_t)z * NL);
-                    if (!wi_unreached<NL>(tz) && wi_eq<NL>(wi_add<NL>(tz, ew_decode<NL>(ow[e])), tv)) ts = z;
+                    if (!wi_unreached<NL>(tz) && wi_eq<NL>(wi_add<NL>(tz, dp_w_out<NL>(g, sp, ebase + e, ew_decode<NL>(ow[e]))), tv)) ts = z;
                 }
             }
         }
@@ -167,13 +244,16 @@ __global__ __launch_bounds__(NT) void k_dp_tree(DBatch b, DMarg g, DDrop q) {
         for (int v = tid; v < V; v += NT) {
             if (fs && js[v] == 0x7fffffff) {
                 const WInt<NL> dv = wi_load<NL>(ds + (size_t)v * NL);
+                [[maybe_unused]] bool sp = false;
+                if constexpr (COND) { if (!wi_unreached<NL>(dv)) sp = dp_sp_in(g, biased, ebase, in_off[v], in_off[v + 1]); }
                 if (!wi_unreached<NL>(dv))
                     for (uint32_t e = in_off[v], e1 = in_off[v + 1]; e < e1; e++) {
                         const uint32_t sw = esrc[e];
                         const int u = (int)ESRC_NODE(sw);
                         if (js[u] >= r) continue;
+                        if constexpr (COND) { if (sp && mg_bit(g.q.mask, ebase + e)) continue; }
                         const WInt<NL> du = wi_load<NL>(ds + (size_t)u * NL);
-                        if (!wi_unreached<NL>(du) && wi_eq<NL>(wi_add<NL>(du, ew_decode<NL>(edge_wenc(sw, ew, e, gt))), dv)) {
+                        if (!wi_unreached<NL>(du) && wi_eq<NL>(wi_add<NL>(du, dp_w_in<NL>(g, sp, biased, ebase + e, ew_decode<NL>(edge_wenc(sw, ew, e, gt)))), dv)) {
                             first[v] = first[u]; js[v] = r; s_chg = 1;
                             if (q.ps) q.ps[no + v] = u;
                             break;
@@ -184,11 +264,14 @@ __global__ __launch_bounds__(NT) void k_dp_tree(DBatch b, DMarg g, DDrop q) {
                 const WInt<NL> tv = wi_load<NL>(dt + (size_t)v * NL);
                 if (!wi_unreached<NL>(tv)) {
                     int best = -1;
+                    [[maybe_unused]] bool sp = false;
+                    if constexpr (COND) sp = dp_sp_out(g, ebase, oo[v], oo[v + 1]);
                     for (uint32_t e = oo[v], e1 = oo[v + 1]; e < e1; e++) {
                         const int z = (int)od[e];
                         if ((best >= 0 && z >= best) || jt[z] >= r) continue;
+                        if constexpr (COND) { if (sp && mg_bit(g.r.fbit, ebase + e)) continue; }
                         const WInt<NL> tz = wi_load<NL>(dt + (size_t)z * NL);
-                        if (!wi_unreached<NL>(tz) && wi_eq<NL>(wi_add<NL>(tz, ew_decode<NL>(ow[e])), tv)) best = z;
+                        if (!wi_unreached<NL>(tz) && wi_eq<NL>(wi_add<NL>(tz, dp_w_out<NL>(g, sp, ebase + e, ew_decode<NL>(ow[e]))), tv)) best = z;
                     }
                     if (best >= 0) { last[v] = last[best]; jt[v] = r; s_chg = 1; if (q.ts) q.ts[no + v] = best; }
                 }
@@ -204,19 +287,23 @@ __global__ __launch_bounds__(NT) void k_dp_tree(DBatch b, DMarg g, DDrop q) {
 // Level k holds n entries; entry i covers slots [i, i + 2^k).  A candidate for the open range (first(x), last(z)) = slots [a, z] goes to
 // level floor(log2(z - a + 1)) at both ends.  The push-down gathers: level k-1 entry i takes the minimum of level k at i and at i - 2^(k-1).
 // The atomics stay per contig: in LDS up to DP_TAB_LDS entries, else in the contig's own slice of DDrop.gtab (read back through L2).
-template <int NL>
-__global__ __launch_bounds__(NT) void k_dp_cand(DBatch b, DMarg g, DDrop q) {
+template <int NL, class G = DMarg>
+__global__ __launch_bounds__(NT) void k_dp_cand(DBatch b, G g, DDrop q) {
+    constexpr bool COND = mg_cond<G>;
     __shared__ unsigned long long s_tab[DP_TAB_LDS];
     const DMeta *meta = &b.meta[blockIdx.x];
-    if (!dp_contig(b, g, meta) || meta->sssp_nl != NL) return;
-    const int V = meta->n_node, n = meta->n_path, tid = threadIdx.x;
+    if (!dp_on<G>(b, g, meta) || meta->sssp_nl != NL) return;
+    const int V = meta->n_node, n = dp_npath<G>(b, g, meta), tid = threadIdx.x;
     const size_t no = (size_t)meta->node_off;
     const uint32_t *in_off = b.in_off + no + blockIdx.x;
     const uint32_t *esrc = b.esrc + meta->edge_off;
     const long long *ew = b.ew + meta->edge_off;
     const long long *gt = gtab_of(b, meta);
-    const uint64_t *ds = b.dist + no * b.dist_stride;
-    const uint64_t *dt = g.dist_t + no * b.dist_stride;
+    const uint64_t *ds = dp_ds<G>(b, g, meta);
+    const uint64_t *dt = dp_dt<G>(b, g, meta);
+    [[maybe_unused]] const uint64_t ebase = (uint64_t)meta->edge_off;
+    [[maybe_unused]] bool biased = false;
+    if constexpr (COND) biased = re_mode_bias(g.q.mode[blockIdx.x]);
     const int32_t *first = q.first + no, *last = q.last + no;
     int lv = 1;
     while ((2 << (lv - 1)) <= n) lv++; // floor(log2 n) + 1
@@ -229,13 +316,16 @@ __global__ __launch_bounds__(NT) void k_dp_cand(DBatch b, DMarg g, DDrop q) {
         const int lz = last[z];
         if (lz < 2) continue; // (no slot strictly between first(x) >= 0 and last(z))
         const WInt<NL> tz = wi_add<NL>(wi_load<NL>(dt + (size_t)z * NL), negD);
+        [[maybe_unused]] bool sp = false;
+        if constexpr (COND) sp = dp_sp_in(g, biased, ebase, in_off[z], in_off[z + 1]);
         for (uint32_t e = in_off[z], e1 = in_off[z + 1]; e < e1; e++) {
             const uint32_t sw = esrc[e];
             const int x = (int)ESRC_NODE(sw);
             const int fx = first[x];
             if (fx < 0 || fx + 1 > lz - 1) continue;
+            if constexpr (COND) { if (sp && mg_bit(g.q.mask, ebase + e)) continue; }
             const int a = fx + 1, len = lz - 1 - a + 1;
-            const WInt<NL> c = wi_add<NL>(wi_add<NL>(wi_load<NL>(ds + (size_t)x * NL), ew_decode<NL>(edge_wenc(sw, ew, e, gt))), tz);
+            const WInt<NL> c = wi_add<NL>(wi_add<NL>(wi_load<NL>(ds + (size_t)x * NL), dp_w_in<NL>(g, sp, biased, ebase + e, ew_decode<NL>(edge_wenc(sw, ew, e, gt)))), tz);
             const unsigned long long key = wi_sat64<NL>(c);
             const int k = 31 - __clz(len);
             atomicMin(&tab[k * n + a], key);
@@ -257,20 +347,24 @@ __global__ __launch_bounds__(NT) void k_dp_cand(DBatch b, DMarg g, DDrop q) {
 }
 
 // ---- 3. k_dp_rescan<NL>: the gene slots whose range minimum saturated, exactly; a wavefront per slot ----
-template <int NL>
-__global__ __launch_bounds__(NT) void k_dp_rescan(DBatch b, DMarg g, DDrop q) {
+template <int NL, class G = DMarg>
+__global__ __launch_bounds__(NT) void k_dp_rescan(DBatch b, G g, DDrop q) {
+    constexpr bool COND = mg_cond<G>;
     const DMeta *meta = &b.meta[blockIdx.x];
-    if (!dp_contig(b, g, meta) || meta->sssp_nl != NL) return;
-    const int V = meta->n_node, np = (meta->n_path - 1) / 2;
+    if (!dp_on<G>(b, g, meta) || meta->sssp_nl != NL) return;
+    const int V = meta->n_node, np = (dp_npath<G>(b, g, meta) - 1) / 2;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const size_t no = (size_t)meta->node_off;
-    const int32_t *path = b.path + no;
+    const int32_t *path = dp_path<G>(b, g, meta);
     const uint32_t *in_off = b.in_off + no + blockIdx.x;
     const uint32_t *esrc = b.esrc + meta->edge_off;
     const long long *ew = b.ew + meta->edge_off;
     const long long *gt = gtab_of(b, meta);
-    const uint64_t *ds = b.dist + no * b.dist_stride;
-    const uint64_t *dt = g.dist_t + no * b.dist_stride;
+    const uint64_t *ds = dp_ds<G>(b, g, meta);
+    const uint64_t *dt = dp_dt<G>(b, g, meta);
+    [[maybe_unused]] const uint64_t ebase = (uint64_t)meta->edge_off;
+    [[maybe_unused]] bool biased = false;
+    if constexpr (COND) biased = re_mode_bias(g.q.mode[blockIdx.x]);
     const int32_t *first = q.first + no, *last = q.last + no;
     const uint64_t *slot = q.slot + no;
     const WInt<NL> negD = wi_neg<NL>(wi_load<NL>(ds + (size_t)(V - 1) * NL));
@@ -281,12 +375,15 @@ __global__ __launch_bounds__(NT) void k_dp_rescan(DBatch b, DMarg g, DDrop q) {
         for (int z = lane; z < V; z += 64) {
             if (last[z] <= j) continue;
             const WInt<NL> tz = wi_add<NL>(wi_load<NL>(dt + (size_t)z * NL), negD);
+            [[maybe_unused]] bool sp = false;
+            if constexpr (COND) sp = dp_sp_in(g, biased, ebase, in_off[z], in_off[z + 1]);
             for (uint32_t e = in_off[z], e1 = in_off[z + 1]; e < e1; e++) {
                 const uint32_t sw = esrc[e];
                 const int x = (int)ESRC_NODE(sw);
                 const int fx = first[x];
                 if (fx < 0 || fx >= j) continue;
-                const WInt<NL> c = wi_add<NL>(wi_add<NL>(wi_load<NL>(ds + (size_t)x * NL), ew_decode<NL>(edge_wenc(sw, ew, e, gt))), tz);
+                if constexpr (COND) { if (sp && mg_bit(g.q.mask, ebase + e)) continue; }
+                const WInt<NL> c = wi_add<NL>(wi_add<NL>(wi_load<NL>(ds + (size_t)x * NL), dp_w_in<NL>(g, sp, biased, ebase + e, ew_decode<NL>(edge_wenc(sw, ew, e, gt)))), tz);
                 if (wi_lt<NL>(c, best)) best = c;
             }
         }
@@ -303,16 +400,17 @@ __global__ __launch_bounds__(NT) void k_dp_rescan(DBatch b, DMarg g, DDrop q) {
 // node (DDrop.jt reused); Y_j is the part of the list with last(y) <= j <= first(y).  Per gene slot with Y_j non-empty: delta(y) seeded from
 // the edges x -> y with first(x) < j, Jacobi rounds within Y_j on two buffers (LDS up to DP_CROSS_LDS list entries, else DDrop.da / db),
 // then the edges y -> z with last(z) > j give delta(y) + W + d_t(z) - D.  Every gene slot gets its cross minimum (inf: none) in DDrop.cx.
-template <int NL>
-__global__ __launch_bounds__(NT) void k_dp_cross(DBatch b, DMarg g, DDrop q) {
+template <int NL, class G = DMarg>
+__global__ __launch_bounds__(NT) void k_dp_cross(DBatch b, G g, DDrop q) {
+    constexpr bool COND = mg_cond<G>;
     __shared__ uint64_t s_d[2][DP_CROSS_LDS * NL];
     __shared__ uint64_t s_red[NT / 64][NL];
     __shared__ int s_nc, s_any, s_chg;
     const DMeta *meta = &b.meta[blockIdx.x];
-    if (!dp_contig(b, g, meta) || meta->sssp_nl != NL) return;
-    const int V = meta->n_node, np = (meta->n_path - 1) / 2, tid = threadIdx.x;
+    if (!dp_on<G>(b, g, meta) || meta->sssp_nl != NL) return;
+    const int V = meta->n_node, np = (dp_npath<G>(b, g, meta) - 1) / 2, tid = threadIdx.x;
     const size_t no = (size_t)meta->node_off;
-    const int32_t *path = b.path + no;
+    const int32_t *path = dp_path<G>(b, g, meta);
     const uint32_t *in_off = b.in_off + no + blockIdx.x;
     const uint32_t *esrc = b.esrc + meta->edge_off;
     const long long *ew = b.ew + meta->edge_off;
@@ -320,8 +418,11 @@ __global__ __launch_bounds__(NT) void k_dp_cross(DBatch b, DMarg g, DDrop q) {
     const uint32_t *oo = g.out_off + no + blockIdx.x;
     const uint32_t *od = g.out_dst + meta->edge_off;
     const long long *ow = g.out_w + meta->edge_off;
-    const uint64_t *ds = b.dist + no * b.dist_stride;
-    const uint64_t *dt = g.dist_t + no * b.dist_stride;
+    const uint64_t *ds = dp_ds<G>(b, g, meta);
+    const uint64_t *dt = dp_dt<G>(b, g, meta);
+    [[maybe_unused]] const uint64_t ebase = (uint64_t)meta->edge_off;
+    [[maybe_unused]] bool biased = false;
+    if constexpr (COND) biased = re_mode_bias(g.q.mode[blockIdx.x]);
     const int32_t *first = q.first + no, *last = q.last + no, *pidx = q.pidx + no;
     int32_t *clist = q.js + no, *cpos = q.jt + no;
     uint64_t *cx = q.cx + (size_t)q.roff[blockIdx.x] * b.dist_stride;
@@ -353,13 +454,16 @@ __global__ __launch_bounds__(NT) void k_dp_cross(DBatch b, DMarg g, DDrop q) {
         for (int p = tid; p < nc; p += NT) {
             const int y = clist[p];
             WInt<NL> d = wi_inf<NL>();
+            [[maybe_unused]] bool sp = false;
+            if constexpr (COND) { if (in_y(y)) sp = dp_sp_in(g, biased, ebase, in_off[y], in_off[y + 1]); }
             if (in_y(y))
                 for (uint32_t e = in_off[y], e1 = in_off[y + 1]; e < e1; e++) {
                     const uint32_t sw = esrc[e];
                     const int x = (int)ESRC_NODE(sw);
                     const int fx = first[x];
                     if (fx < 0 || fx >= j) continue;
-                    const WInt<NL> c = wi_add<NL>(wi_load<NL>(ds + (size_t)x * NL), ew_decode<NL>(edge_wenc(sw, ew, e, gt)));
+                    if constexpr (COND) { if (sp && mg_bit(g.q.mask, ebase + e)) continue; }
+                    const WInt<NL> c = wi_add<NL>(wi_load<NL>(ds + (size_t)x * NL), dp_w_in<NL>(g, sp, biased, ebase + e, ew_decode<NL>(edge_wenc(sw, ew, e, gt))));
                     if (wi_lt<NL>(c, d)) d = c;
                 }
             wi_store<NL>(bufA + (size_t)p * NL, d);
@@ -373,14 +477,17 @@ __global__ __launch_bounds__(NT) void k_dp_cross(DBatch b, DMarg g, DDrop q) {
             for (int p = tid; p < nc; p += NT) {
                 const int y = clist[p];
                 WInt<NL> d = wi_load<NL>(cur + (size_t)p * NL);
+                [[maybe_unused]] bool sp = false;
+                if constexpr (COND) { if (in_y(y)) sp = dp_sp_in(g, biased, ebase, in_off[y], in_off[y + 1]); }
                 if (in_y(y))
                     for (uint32_t e = in_off[y], e1 = in_off[y + 1]; e < e1; e++) {
                         const uint32_t sw = esrc[e];
                         const int x = (int)ESRC_NODE(sw);
                         if (!in_y(x)) continue;
+                        if constexpr (COND) { if (sp && mg_bit(g.q.mask, ebase + e)) continue; }
                         const WInt<NL> dx = wi_load<NL>(cur + (size_t)cpos[x] * NL);
                         if (wi_is_inf<NL>(dx)) continue;
-                        const WInt<NL> c = wi_add<NL>(dx, ew_decode<NL>(edge_wenc(sw, ew, e, gt)));
+                        const WInt<NL> c = wi_add<NL>(dx, dp_w_in<NL>(g, sp, biased, ebase + e, ew_decode<NL>(edge_wenc(sw, ew, e, gt))));
                         if (wi_lt<NL>(c, d)) { d = c; s_chg = 1; }
                     }
                 wi_store<NL>(nxt + (size_t)p * NL, d);
@@ -398,10 +505,13 @@ __global__ __launch_bounds__(NT) void k_dp_cross(DBatch b, DMarg g, DDrop q) {
             if (!in_y(y)) continue;
             const WInt<NL> d = wi_load<NL>(cur + (size_t)p * NL);
             if (wi_is_inf<NL>(d)) continue;
+            [[maybe_unused]] bool sp = false;
+            if constexpr (COND) sp = dp_sp_out(g, ebase, oo[y], oo[y + 1]);
             for (uint32_t e = oo[y], e1 = oo[y + 1]; e < e1; e++) {
                 const int z = (int)od[e];
                 if (last[z] <= j) continue;
-                const WInt<NL> c = wi_add<NL>(wi_add<NL>(d, ew_decode<NL>(ow[e])), wi_add<NL>(wi_load<NL>(dt + (size_t)z * NL), negD));
+                if constexpr (COND) { if (sp && mg_bit(g.r.fbit, ebase + e)) continue; }
+                const WInt<NL> c = wi_add<NL>(wi_add<NL>(d, dp_w_out<NL>(g, sp, ebase + e, ew_decode<NL>(ow[e]))), wi_add<NL>(wi_load<NL>(dt + (size_t)z * NL), negD));
                 if (wi_lt<NL>(c, best)) best = c;
             }
         }
@@ -417,14 +527,14 @@ __global__ __launch_bounds__(NT) void k_dp_cross(DBatch b, DMarg g, DDrop q) {
 }
 
 // ---- 5. k_dp_rec<NL>: a record per pair of P (called = -1: no CDS gene, dropped by the host) ----
-template <int NL>
-__global__ __launch_bounds__(NT) void k_dp_rec(DBatch b, DMarg g, DDrop q) {
+template <int NL, class G = DMarg>
+__global__ __launch_bounds__(NT) void k_dp_rec(DBatch b, G g, DDrop q) {
     __shared__ int s_cnt;
     const DMeta *meta = &b.meta[blockIdx.x];
-    if (!dp_contig(b, g, meta) || meta->sssp_nl != NL) return;
-    const int np = (meta->n_path - 1) / 2, tid = threadIdx.x;
+    if (!dp_on<G>(b, g, meta) || meta->sssp_nl != NL) return;
+    const int np = (dp_npath<G>(b, g, meta) - 1) / 2, tid = threadIdx.x;
     const size_t no = (size_t)meta->node_off;
-    const int32_t *path = b.path + no;
+    const int32_t *path = dp_path<G>(b, g, meta);
     const DNode *nd = b.node + no;
     const double *oweight = b.oweight + meta->orf_off;
     const uint64_t *slot = q.slot + no;

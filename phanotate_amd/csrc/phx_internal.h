@@ -540,6 +540,11 @@ void phxk_margins(const DBatch *b, const DMarg *g, int nl_mask, void *stream); /
 void phxk_drop_trees(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream); // gene drop margins (phx_drop.inc): trees + labels,
 void phxk_drop_cand(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream);  //   candidates + sparse table,
 void phxk_drop_fix(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream);   //   saturated slots, cross nodes, records
+// re-annotation drop margins (§29; b: the run's batch, rq / r: what the re-annotation and its margins left resident, qpath: the re-annotation's
+// path buffer, q: the feature's own DDrop set; nl_mask: the classes among DRmarg.sel == 1): the three steps of the drop margins under MgDrop
+void phxk_redrop_trees(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, int nl_mask, void *stream);
+void phxk_redrop_cand(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, int nl_mask, void *stream);
+void phxk_redrop_fix(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, int nl_mask, void *stream);
 void phxk_repl_pick(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream); // drop replacements (phx_replace.inc): winners,
 void phxk_repl_cross(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream); //   cross winners and their delta chains,
 void phxk_repl_walk(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int fill, void *stream);    //   detour lengths (fill 0) / detours, genes, records (1)

@@ -463,6 +463,22 @@ void phxk_drop_fix(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask,
     each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL(k_dp_cross<decltype(nl)::value>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q); });
     each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL(k_dp_rec<decltype(nl)::value>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q); });
 }
+// re-annotation drop margins: the same five kernels under MgDrop — the run's graph and out-edge CSR, the re-annotation's
+// policy, d_s', d_t' and path (qpath: its path buffer, laid out like DBatch.path); q: a DDrop set of the feature's own
+static MgDrop dp_args(const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath) { MgDrop c = mg_args<MgDrop>(g, rq, r); c.path = qpath; return c; }
+void phxk_redrop_trees(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, int nl_mask, void *stream) {
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_tree<decltype(nl)::value, MgDrop>), dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, dp_args(g, rq, r, qpath), *q); });
+}
+void phxk_redrop_cand(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, int nl_mask, void *stream) {
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_cand<decltype(nl)::value, MgDrop>), dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, dp_args(g, rq, r, qpath), *q); });
+}
+void phxk_redrop_fix(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, int nl_mask, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const MgDrop c = dp_args(g, rq, r, qpath);
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_rescan<decltype(nl)::value, MgDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, c, *q); });
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_cross<decltype(nl)::value, MgDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, c, *q); });
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_rec<decltype(nl)::value, MgDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, c, *q); });
+}
 // drop replacements (phx_replace.inc): a workgroup per contig
 void phxk_repl_pick(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream) {
     each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL(k_rp_pick<decltype(nl)::value>, dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, *g, *q, *r); });
