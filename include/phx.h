@@ -48,7 +48,8 @@ extern "C" {
  *        (additions, version unchanged) phx_remargins_flat, phx_remargins_ms, phx_tap_redist — probe for the symbol;
  *        (additions, version unchanged) phx_pinmargins_flat, phx_pinmargins_ms, phx_tap_pindist — probe for the symbol;
  *        (addition, version unchanged) phx_curate_scenarios_flat — probe for the symbol;
- *        (additions, version unchanged) phx_redrops_flat, phx_redrops_ms, phx_redrop_stats — probe for the symbol */
+ *        (additions, version unchanged) phx_redrops_flat, phx_redrops_ms, phx_redrop_stats — probe for the symbol
+ *        (additions, version unchanged) phx_rereplacements_flat, phx_tap_rereplacement, phx_rereplacements_ms, phx_rereplacement_stats — probe for the symbol */
 #define PHX_MAX_CODONS 16
 
 /* library-level errors */
@@ -542,6 +543,28 @@ int phx_redrops_flat(phx_ctx *ctx, phx_gene_drop *rec, int64_t cap, int64_t *off
 int phx_redrops_ms(phx_ctx *ctx, float *ms /* [4] */);
 /* counters of the last computation, out[4], as phx_drop_stats, over the contigs that were solved again */
 int phx_redrop_stats(phx_ctx *ctx, int64_t *out /* [4] */);
+
+/* ---- re-annotation replacements: the best path without each call of a re-annotation ----
+ * phx_replacements_flat on the graph of the last re-annotation phx_redrops_flat is defined for.  For every record of phx_redrops_flat
+ * with bypass = 1 a replacement path R'_g: a simple source -> target path of G' — every edge an edge of the device graph, none an ORF edge
+ * the call refused — that does not visit the gene's stop node p_j, of weight exactly D'_{-g} under W' = W + B; it leaves the
+ * re-annotation's path P' (phx_tap_repath) at one node before p_j, rejoins it at one node behind, and no node of the detour lies on P'.
+ * Records are phx_gene_repl: drop / called / bypass bit-equal to phx_redrops_flat's, the removed and the added genes as for
+ * phx_replacements_flat, score what the re-annotation call's gene records carry (the ORF's weight without the bias, -20 for a tRNA pair).
+ * The bytes do not depend on the batch or on the create flags (tie rule of DESIGN.md §13).  Order, offsets, statuses and the PHX_E_STATE
+ * rule are phx_redrops_flat's; a contig that was not solved again gets phx_replacements_flat's records and genes, byte for byte but for
+ * gene_off.  Size query, argument checks and caps as phx_replacements_flat.  Computed at the first call after a re-annotation solve, on top
+ * of phx_redrops_flat's computation (and phx_replacements_flat's when a contig was not solved again), in buffers of its own; kept until the
+ * next solve or run.  Nothing the other entry points return changes.  (Additions, version unchanged: probe for the symbol.) */
+int phx_rereplacements_flat(phx_ctx *ctx, phx_gene_repl *rec, int64_t cap, phx_gene *genes, int64_t gene_cap, int64_t *offsets /* [n+1] */,
+                            int32_t *status /* [n] */, int64_t *total, int64_t *gene_total);
+/* R'_g of record k of contig `contig` (k counts the contig's records of phx_rereplacements_flat), as phx_tap_replacement: the prefix and
+ * the suffix are the re-annotation's path.  For a contig that was not solved again: phx_tap_replacement's result. */
+int phx_tap_rereplacement(phx_ctx *ctx, int32_t contig, int32_t k, int32_t *path, int32_t cap, int32_t *n_path);
+/* device time of the last computation, ms[3], and its counters, out[5], as phx_replacements_ms / phx_replacement_stats, over the contigs
+ * that were solved again.  All 0 before the first and when no contig was. */
+int phx_rereplacements_ms(phx_ctx *ctx, float *ms /* [3] */);
+int phx_rereplacement_stats(phx_ctx *ctx, int64_t *out /* [5] */);
 
 /* ---- pinned margins: per-ORF path margins under required ORFs ----
  * phx_remargins_flat for every re-annotation of the batch last run, phx_constrain_flat and phx_curate_flat with required ORFs included.  A

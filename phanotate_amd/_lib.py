@@ -182,6 +182,10 @@ def lib():
         "phx_redrops_flat": (C.c_int, [vp, vp, i64, vp, vp, P(i64)]),
         "phx_redrops_ms": (C.c_int, [vp, P(C.c_float)]),
         "phx_redrop_stats": (C.c_int, [vp, P(i64)]),
+        "phx_rereplacements_flat": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, P(i64), P(i64)]),
+        "phx_tap_rereplacement": (C.c_int, [vp, i32, i32, vp, i32, P(i32)]),
+        "phx_rereplacements_ms": (C.c_int, [vp, P(C.c_float)]),
+        "phx_rereplacement_stats": (C.c_int, [vp, P(i64)]),
         "phx_pinmargins_flat": (C.c_int, [vp, vp, vp, i64, vp, vp, P(i64)]),
         "phx_pinmargins_ms": (C.c_int, [vp, P(C.c_float)]),
         "phx_tap_pindist": (C.c_int, [vp, i32, i32, vp, i64, P(i32)]),
@@ -239,4 +243,5 @@ EXPORTS = ["phx_version", "phx_device_count", "phx_strerror", "phx_last_error", 
            "phx_evidence_scenarios_flat", "phx_curate_scenarios_flat",
            "phx_remargins_flat", "phx_remargins_ms", "phx_tap_redist",
            "phx_pinmargins_flat", "phx_pinmargins_ms", "phx_tap_pindist",
-           "phx_redrops_flat", "phx_redrops_ms", "phx_redrop_stats"]
+           "phx_redrops_flat", "phx_redrops_ms", "phx_redrop_stats",
+           "phx_rereplacements_flat", "phx_tap_rereplacement", "phx_rereplacements_ms", "phx_rereplacement_stats"]

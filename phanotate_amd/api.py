@@ -73,6 +73,7 @@ _MS_KEYS = {
     "phx_remargins_ms": ("apply", "reverse", "margins", "download"),
     "phx_pinmargins_ms": ("apply", "reverse", "margins", "download"),
     "phx_redrops_ms": ("trees", "candidates", "fixups", "download"),
+    "phx_rereplacements_ms": ("argmin", "walk", "download"),
     "phx_reannotate_ms": ("mask", "solve", "finish"),
 }
 
@@ -954,6 +955,34 @@ class Annotator:
         out = (C.c_int64 * 4)()
         self._chk(self.L.phx_redrop_stats(self.h, out), "phx_redrop_stats")
         return dict(zip(("slots", "cross", "rescanned", "layered"), [int(x) for x in out]))
+
+    def rereplacements(self):
+        """(status int32[n], offsets int64[n+1], records structured array[total] of _lib.REPL_DT, genes structured array of _lib.GENE_DT),
+        as replacements() returns them: for every record of redrops() (same order, statuses and offsets; drop, called and bypass
+        bit-equal) what the best path under the same mask and evidence calls instead when nothing is called at the gene's stop
+        (phx_rereplacements_flat).  The removed genes are genes of the re-annotation, the scores the ORFs' weights without
+        the bias.  A contig that was not solved again has the records of replacements().  PhxError (PHX_E_STATE) as redrops()."""
+        (status,), offs, (rec, genes) = self._query_fill(self.L.phx_rereplacements_flat, "phx_rereplacements_flat", (), self.n, (_lib.REPL_DT, _lib.GENE_DT), "rcrc")
+        return status, offs, rec, genes
+
+    def rereplacement_path(self, i, k):
+        """R'_g of record k of contig i (rereplacements()[2][offsets[i] + k]): device node ids, source first, the re-annotation's path
+        (reannotated_path(i)) around the detour; empty when bypass = 0.  A contig that was not solved again gives replacement_path(i, k)."""
+        n = C.c_int32()
+        self._chk(self.L.phx_tap_rereplacement(self.h, i, k, None, 0, C.byref(n)), "phx_tap_rereplacement")
+        p = np.zeros(max(n.value, 1), np.int32)
+        self._chk(self.L.phx_tap_rereplacement(self.h, i, k, p.ctypes.data_as(C.c_void_p), len(p), C.byref(n)), "phx_tap_rereplacement")
+        return p[: n.value].copy()
+
+    def rereplacements_ms(self):
+        """Device time of the last re-annotation replacements in ms: argmin, walk + genes, copy to the host (phx_rereplacements_ms)."""
+        return self._ms("phx_rereplacements_ms")
+
+    def rereplacement_stats(self):
+        """replacement_stats() of the last re-annotation replacements, over the contigs that were solved again (phx_rereplacement_stats)."""
+        out = (C.c_int64 * 5)()
+        self._chk(self.L.phx_rereplacement_stats(self.h, out), "phx_rereplacement_stats")
+        return dict(zip(("cross", "chain_nodes", "cross_kept", "cut", "regrown"), [int(x) for x in out]))
 
     def redist(self, i, to_target=False):
         """Exact distances of every node of contig i on the last re-annotation's graph as python ints (None: unreached), device node

@@ -54,6 +54,7 @@ def get_args(argv=None):
     p.add_argument("--reannotation", metavar="OUT", default=None, help="write the annotation without the ORFs of --forbid (keeping those of --require, or under the biases of --evidence) to OUT: the tabular block of every contig with a #delta: header line")
     p.add_argument("--remargins", metavar="FILE", default=None, help="also write every ORF with its path margin on the graph of the second annotation (under --forbid / --evidence; DESIGN.md §21) to FILE, in the format of --margins; needs --reannotation, not with --require")
     p.add_argument("--redrop-margins", metavar="FILE", default=None, help="also write every gene of the second annotation with its drop margin on that annotation's graph, the cost of the best path under the same --forbid / --evidence that calls nothing at its stop (DESIGN.md §29), to FILE, in the format of --drop-margins; needs --reannotation, not with --require")
+    p.add_argument("--redrop-replacements", metavar="FILE", default=None, help="also write every gene of the second annotation with what the best path under the same --forbid / --evidence that calls nothing at its stop calls instead (DESIGN.md §30) to FILE, in the format of --drop-replacements; needs --reannotation, not with --require")
     p.add_argument("--pin-margins", metavar="FILE", default=None, help="also write every ORF with its path margin and the kept ORFs of --require that the best path through it gives up (DESIGN.md §24) to FILE: the format of --margins with a LOST column behind MARGIN; needs --require and --reannotation")
     p.add_argument("--single-device-ranks", action="store_true", help=argparse.SUPPRESS)  # tests: every rank of a sharded launch on GPU `--device` (gloo-only group)
     args = p.parse_args(argv)
@@ -70,6 +71,8 @@ _RULES = (
     ("remargins", lambda a: a.reannotation is None, "argument --remargins: needs --reannotation"),
     ("redrop_margins", lambda a: a.require is not None, "argument --redrop-margins: not allowed with argument --require"),  # (drops under required ORFs: DESIGN.md §29, Limits)
     ("redrop_margins", lambda a: a.reannotation is None, "argument --redrop-margins: needs --reannotation"),
+    ("redrop_replacements", lambda a: a.require is not None, "argument --redrop-replacements: not allowed with argument --require"),  # (as --redrop-margins: DESIGN.md §30, Limits)
+    ("redrop_replacements", lambda a: a.reannotation is None, "argument --redrop-replacements: needs --reannotation"),
     ("pin_margins", lambda a: a.require is None, "argument --pin-margins: needs --require"),
     ("pin_margins", lambda a: a.reannotation is None, "argument --pin-margins: needs --reannotation"),
     ("evidence", lambda a: a.require is not None, "argument --evidence: not allowed with argument --require"),  # (required sets and biases in one solve: DESIGN.md §19, Limits)
@@ -78,7 +81,7 @@ _RULES = (
     ("require", lambda a: a.reannotation is None, "argument --require: needs --reannotation"),
 )
 # The flags of OUTPUTS and INPUTS in the order get_args looks at them.
-_CHECK_ORDER = ("margins", "drop_margins", "drop_replacements", "start_drops", "alt_starts", "evidence_scan", "curated_scan", "remargins", "redrop_margins", "pin_margins", "forbid", "require", "evidence", "reannotation")
+_CHECK_ORDER = ("margins", "drop_margins", "drop_replacements", "start_drops", "alt_starts", "evidence_scan", "curated_scan", "remargins", "redrop_margins", "redrop_replacements", "pin_margins", "forbid", "require", "evidence", "reannotation")
 
 
 def _refusals(args, world):
@@ -430,6 +433,7 @@ OUTPUTS = {o.dest: o for o in (
     _out("--margins", format_margins, "wb", lambda ann, entries: ann.margins(), piped="margins"),
     _out("--remargins", format_margins, "wb", lambda ann, entries: ann.remargins(), resident=True),
     _out("--redrop-margins", format_drops, "wb", lambda ann, entries: ann.redrops(), resident=True),
+    _out("--redrop-replacements", format_replacements, "wb", lambda ann, entries: ann.rereplacements(), resident=True, merge=_merge_replacements),
     _out("--pin-margins", format_pin_margins, "wb", lambda ann, entries: ann.pinmargins(), resident=True),
     _out("--drop-margins", format_drops, "wb", lambda ann, entries: ann.drop_margins(), piped="drop_margins"),
     _out("--drop-replacements", format_replacements, "wb", lambda ann, entries: ann.replacements(), piped="replacements", merge=_merge_replacements),
@@ -441,9 +445,10 @@ OUTPUTS = {o.dest: o for o in (
 )}
 # A batch's fetches, in this order.  THE ORDER IS CONTRACT: the replacements in front of the drop margins (the drops are then computed
 # once); the curated scan behind the batch's re-annotation, which thereby stays the cached one; remargins, the re-annotation's drop
-# margins and pinmargins behind the re-annotation, whose margins they are.  The entry files are resolved where a fetch first needs them, so a line that names no ORF is
+# margins, its replacements (behind its drop margins: an existing order; the trees are then built once more) and pinmargins
+# behind the re-annotation, whose margins they are.  The entry files are resolved where a fetch first needs them, so a line that names no ORF is
 # reported in the order --evidence-scan, --forbid, --evidence or --require, --curated-scan.
-_FETCH_ORDER = ("margins", "drop_replacements", "drop_margins", "start_drops", "alt_starts", "evidence_scan", "reannotation", "curated_scan", "remargins", "redrop_margins", "pin_margins")
+_FETCH_ORDER = ("margins", "drop_replacements", "drop_margins", "start_drops", "alt_starts", "evidence_scan", "reannotation", "curated_scan", "remargins", "redrop_margins", "redrop_replacements", "pin_margins")
 # The entry files in the order main looks for a line that names a contig the FASTA file does not hold.
 _UNKNOWN_ORDER = ("forbid", "require", "evidence", "evidence_scan", "curated_scan")
 assert set(_CHECK_ORDER) == set(OUTPUTS) | set(INPUTS) and set(_FETCH_ORDER) == set(OUTPUTS) and set(_UNKNOWN_ORDER) == set(INPUTS)  # a new row takes its place in each order

@@ -180,7 +180,7 @@ static int ensure_drops(phx_ctx *c, bool trees = false) {
     if (c->done.drops) {
         const size_t nv = ((size_t)c->tot_node + (size_t)c->n + 1) * 4;
         int rc;
-        if ((rc = ensure(c, c->b_dps, nv)) || (rc = ensure(c, c->b_dts, nv)) || (rc = ensure(c, c->b_rcnt, 2 * RP_NCNT * 8))) return rc;
+        if ((rc = ensure(c, c->b_dps, nv)) || (rc = ensure(c, c->b_dts, nv)) || (rc = ensure(c, c->rp.b_cnt, 2 * RP_NCNT * 8))) return rc;
         c->done.trees = true;
         DBatch b;
         fill_batch(c, &b);
@@ -188,7 +188,7 @@ static int ensure_drops(phx_ctx *c, bool trees = false) {
         margins_args(c, &g);
         DDrop q;
         drop_args(c, &q);
-        q.stats = (unsigned long long *)c->b_rcnt.p + RP_NCNT; // (the drops' own counters stay as they were)
+        q.stats = (unsigned long long *)c->rp.b_cnt.p + RP_NCNT; // (the drops' own counters stay as they were)
         phxk_drop_trees(&b, &g, &q, margins_nl_mask(c), c->stream);
         HIPCHK(c, hipGetLastError());
         return PHX_OK;
@@ -304,39 +304,32 @@ int phx_drop_stats(phx_ctx *c, int64_t *out) {
 }
 
 // ---- drop replacements (phx_replace.inc, DESIGN.md §13) ----
-// Every device record's replacement into c->h_rrec / h_rgenes / h_rdet, once per run, on top of ensure_drops (with the one-hop trees).
-static int ensure_replacements(phx_ctx *c) {
-    if (c->done.repl) return PHX_OK;
-    { const int rd = ensure_drops(c, true); if (rd) return rd; }
+// The replacement pass, once for both entry points (§13 on the run's graph, §30 on a re-annotation's): pick -> cross -> regrowth -> counting
+// walk -> offsets -> filling walk -> copies.  S: the DRepl set the pass writes and what it leaves on the host; R: the records of the DDrop set
+// the launchers read (one per pair of every covered path); launch(step, r): step 0 k_rp_pick, 1 k_rp_cross, 2 / 3 k_rp_walk counting / filling,
+// under the caller's policy; what / who: the feature and the entry point in the error texts.
+extern "C++" template <class L> static int replacement_pass(phx_ctx *c, phx_ctx::ReplSet &S, size_t R, const L &launch, const char *what, const char *who) {
     const size_t n = (size_t)c->n, V = (size_t)c->tot_node;
-    const size_t R = (size_t)c->droff[n];
-    const int nlm = margins_nl_mask(c);
     int rc;
-    if ((rc = ensure(c, c->b_rwin, (R + 1) * 8)) || (rc = ensure(c, c->b_rxs, (R + 1) * 4)) || (rc = ensure(c, c->b_rcoff, (R + 1) * 8)) ||
-        (rc = ensure(c, c->b_rcm, (R + 1) * 4)) || (rc = ensure(c, c->b_rrnd, (V + n + 1) * 4)) || (rc = ensure(c, c->b_rinfo, (R + 1) * 16)) ||
-        (rc = ensure(c, c->b_rdoff, (2 * R + 2) * 8)) || (rc = ensure(c, c->b_rrec, (R + 1) * sizeof(phx_gene_repl))) || (rc = ensure(c, c->b_rcnt, 2 * RP_NCNT * 8)))
+    if ((rc = ensure(c, S.b_win, (R + 1) * 8)) || (rc = ensure(c, S.b_xs, (R + 1) * 4)) || (rc = ensure(c, S.b_coff, (R + 1) * 8)) ||
+        (rc = ensure(c, S.b_cm, (R + 1) * 4)) || (rc = ensure(c, S.b_rnd, (V + n + 1) * 4)) || (rc = ensure(c, S.b_info, (R + 1) * 16)) ||
+        (rc = ensure(c, S.b_doff, (2 * R + 2) * 8)) || (rc = ensure(c, S.b_rec, (R + 1) * sizeof(phx_gene_repl))) || (rc = ensure(c, S.b_cnt, 2 * RP_NCNT * 8)))
         return rc;
-    if (!c->b_rchain.p) { // room for this many delta-chain nodes (env PHX_REPL_CHAIN_CAP, the tests: fewer, so that the regrowth below runs)
+    if (!S.b_chain.p) { // room for this many delta-chain nodes (env PHX_REPL_CHAIN_CAP, the tests: fewer, so that the regrowth below runs)
         const char *cc = getenv("PHX_REPL_CHAIN_CAP");
-        c->rchain_cap = cc && *cc ? std::max<int64_t>(1, atoll(cc)) : (int64_t)V + 1;
-        if ((rc = ensure(c, c->b_rchain, ((size_t)c->rchain_cap + 1) * 4))) return rc;
+        S.chain_cap = cc && *cc ? std::max<int64_t>(1, atoll(cc)) : (int64_t)V + 1;
+        if ((rc = ensure(c, S.b_chain, ((size_t)S.chain_cap + 1) * 4))) return rc;
     }
     if ((rc = analysis_events(c))) return rc;
-    try { c->h_rpath.assign(n, std::vector<int32_t>()); } catch (const std::bad_alloc &) { c->err = "out of memory in phx_replacements_flat"; return PHX_E_NOMEM; }
-    DBatch b;
-    fill_batch(c, &b);
-    DMarg g;
-    margins_args(c, &g);
-    DDrop q;
-    drop_args(c, &q);
+    try { S.h_path.assign(n, std::vector<int32_t>()); } catch (const std::bad_alloc &) { c->err = std::string("out of memory in ") + who; return PHX_E_NOMEM; }
     DRepl r;
     auto args = [&]() {
-        r.win = (uint64_t *)c->b_rwin.p; r.xs = (int32_t *)c->b_rxs.p; r.coff = (int64_t *)c->b_rcoff.p; r.cm = (int32_t *)c->b_rcm.p;
-        r.chain = (int32_t *)c->b_rchain.p; r.ccap = c->rchain_cap; // (b_rchain was ensured for rchain_cap + 1 entries)
-        r.rnd = (int32_t *)c->b_rrnd.p; r.info = (int32_t *)c->b_rinfo.p;
-        r.doff = (const int64_t *)c->b_rdoff.p; r.goff = (const int64_t *)c->b_rdoff.p + R + 1;
-        r.det = (int32_t *)c->b_rdet.p; r.genes = (phx_gene *)c->b_rgenes.p; r.rec = (phx_gene_repl *)c->b_rrec.p;
-        r.cnt = (unsigned long long *)c->b_rcnt.p;
+        r.win = (uint64_t *)S.b_win.p; r.xs = (int32_t *)S.b_xs.p; r.coff = (int64_t *)S.b_coff.p; r.cm = (int32_t *)S.b_cm.p;
+        r.chain = (int32_t *)S.b_chain.p; r.ccap = S.chain_cap; // (b_chain was ensured for chain_cap + 1 entries)
+        r.rnd = (int32_t *)S.b_rnd.p; r.info = (int32_t *)S.b_info.p;
+        r.doff = (const int64_t *)S.b_doff.p; r.goff = (const int64_t *)S.b_doff.p + R + 1;
+        r.det = (int32_t *)S.b_det.p; r.genes = (phx_gene *)S.b_genes.p; r.rec = (phx_gene_repl *)S.b_rec.p;
+        r.cnt = (unsigned long long *)S.b_cnt.p;
     };
     args();
     hipStream_t s = c->stream;
@@ -345,65 +338,130 @@ static int ensure_replacements(phx_ctx *c) {
     hipEvent_t *ev = c->aev;
     bool regrown = false;
     HIPCHK(c, hipEventRecord(ev[0], s));
-    HIPCHK(c, hipMemsetAsync(c->b_rcnt.p, 0, RP_NCNT * 8, s));
-    HIPCHK(c, hipMemsetAsync(c->b_rwin.p, 0xff, (R + 1) * 8, s));
-    phxk_repl_pick(&b, &g, &q, &r, nlm, s);
-    phxk_repl_cross(&b, &g, &q, &r, nlm, s);
+    HIPCHK(c, hipMemsetAsync(S.b_cnt.p, 0, RP_NCNT * 8, s));
+    HIPCHK(c, hipMemsetAsync(S.b_win.p, 0xff, (R + 1) * 8, s));
+    launch(0, r);
+    launch(1, r);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(ev[1], s));
-    HIPCHK(c, hipMemcpyAsync(cnt, c->b_rcnt.p, sizeof cnt, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(cnt, S.b_cnt.p, sizeof cnt, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     if ((int64_t)cnt[0] > r.ccap) { // the delta chains did not fit: room for all of them, and the cross winners once more
-        c->rchain_cap = (int64_t)cnt[0];
-        if ((rc = ensure(c, c->b_rchain, ((size_t)c->rchain_cap + 1) * 4))) return rc;
+        S.chain_cap = (int64_t)cnt[0];
+        if ((rc = ensure(c, S.b_chain, ((size_t)S.chain_cap + 1) * 4))) return rc;
         args();
         regrown = true;
         HIPCHK(c, hipEventRecord(ev[2], s));
-        HIPCHK(c, hipMemsetAsync(c->b_rcnt.p, 0, RP_NCNT * 8, s));
-        phxk_repl_cross(&b, &g, &q, &r, nlm, s);
+        HIPCHK(c, hipMemsetAsync(S.b_cnt.p, 0, RP_NCNT * 8, s));
+        launch(1, r);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipEventRecord(ev[3], s));
-        HIPCHK(c, hipMemcpyAsync(cnt, c->b_rcnt.p, sizeof cnt, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(cnt, S.b_cnt.p, sizeof cnt, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
-        if ((int64_t)cnt[0] > r.ccap) { c->err = "drop replacements: the delta chains outgrew their buffer twice"; return PHX_E_STATE; }
+        if ((int64_t)cnt[0] > r.ccap) { c->err = std::string(what) + ": the delta chains outgrew their buffer twice"; return PHX_E_STATE; }
     }
     // counting pass, offsets, filling pass
     HIPCHK(c, hipEventRecord(ev[4], s));
-    phxk_repl_walk(&b, &g, &q, &r, 0, s);
+    launch(2, r);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(ev[5], s));
-    c->h_rinfo.resize(4 * R + 4);
-    if (R) HIPCHK(c, hipMemcpyAsync(c->h_rinfo.data(), c->b_rinfo.p, R * 16, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(cnt, c->b_rcnt.p, sizeof cnt, hipMemcpyDeviceToHost, s));
+    S.h_info.resize(4 * R + 4);
+    if (R) HIPCHK(c, hipMemcpyAsync(S.h_info.data(), S.b_info.p, R * 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(cnt, S.b_cnt.p, sizeof cnt, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
-    if (cnt[1]) { c->err = "drop replacements: a slot with a bypass has no witness"; return PHX_E_STATE; }
-    c->repl_stats[0] = (int64_t)cnt[2]; c->repl_stats[1] = (int64_t)cnt[0]; c->repl_stats[2] = (int64_t)cnt[3]; c->repl_stats[3] = (int64_t)cnt[4];
-    c->repl_stats[4] = regrown ? 1 : 0;
+    if (cnt[1]) { c->err = std::string(what) + ": a slot with a bypass has no witness"; return PHX_E_STATE; }
+    S.stats[0] = (int64_t)cnt[2]; S.stats[1] = (int64_t)cnt[0]; S.stats[2] = (int64_t)cnt[3]; S.stats[3] = (int64_t)cnt[4];
+    S.stats[4] = regrown ? 1 : 0;
     try {
         std::vector<int64_t> off(2 * R + 2);
         int64_t nd = 0, ng = 0;
-        for (size_t k = 0; k < R; k++) { off[k] = nd; off[R + 1 + k] = ng; nd += c->h_rinfo[4 * k + 2]; ng += c->h_rinfo[4 * k + 3]; }
+        for (size_t k = 0; k < R; k++) { off[k] = nd; off[R + 1 + k] = ng; nd += S.h_info[4 * k + 2]; ng += S.h_info[4 * k + 3]; }
         off[R] = nd; off[2 * R + 1] = ng;
-        c->h_rdoff.assign(off.begin(), off.begin() + (R + 1));
-        if ((rc = ensure(c, c->b_rdet, ((size_t)nd + 1) * 4)) || (rc = ensure(c, c->b_rgenes, ((size_t)ng + 1) * sizeof(phx_gene)))) return rc;
+        S.h_doff.assign(off.begin(), off.begin() + (R + 1));
+        if ((rc = ensure(c, S.b_det, ((size_t)nd + 1) * 4)) || (rc = ensure(c, S.b_genes, ((size_t)ng + 1) * sizeof(phx_gene)))) return rc;
         args();
-        HIPCHK(c, hipMemcpyAsync(c->b_rdoff.p, off.data(), (2 * R + 2) * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(S.b_doff.p, off.data(), (2 * R + 2) * 8, hipMemcpyHostToDevice, s));
         HIPCHK(c, hipEventRecord(ev[6], s));
-        phxk_repl_walk(&b, &g, &q, &r, 1, s);
+        launch(3, r);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipEventRecord(ev[7], s));
-        c->h_rrec.resize(R + 1); c->h_rdet.resize((size_t)nd + 1); c->h_rgenes.resize((size_t)ng + 1);
-        if (R) HIPCHK(c, hipMemcpyAsync(c->h_rrec.data(), c->b_rrec.p, R * sizeof(phx_gene_repl), hipMemcpyDeviceToHost, s));
-        if (nd) HIPCHK(c, hipMemcpyAsync(c->h_rdet.data(), c->b_rdet.p, (size_t)nd * 4, hipMemcpyDeviceToHost, s));
-        if (ng) HIPCHK(c, hipMemcpyAsync(c->h_rgenes.data(), c->b_rgenes.p, (size_t)ng * sizeof(phx_gene), hipMemcpyDeviceToHost, s));
+        S.h_rec.resize(R + 1); S.h_det.resize((size_t)nd + 1); S.h_genes.resize((size_t)ng + 1);
+        if (R) HIPCHK(c, hipMemcpyAsync(S.h_rec.data(), S.b_rec.p, R * sizeof(phx_gene_repl), hipMemcpyDeviceToHost, s));
+        if (nd) HIPCHK(c, hipMemcpyAsync(S.h_det.data(), S.b_det.p, (size_t)nd * 4, hipMemcpyDeviceToHost, s));
+        if (ng) HIPCHK(c, hipMemcpyAsync(S.h_genes.data(), S.b_genes.p, (size_t)ng * sizeof(phx_gene), hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipEventRecord(ev[8], s));
         HIPCHK(c, hipStreamSynchronize(s));
-    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_replacements_flat"; return PHX_E_NOMEM; }
+    } catch (const std::bad_alloc &) { c->err = std::string("out of memory in ") + who; return PHX_E_NOMEM; }
     auto span = [&](int k0, int k1) { return ev_ms(ev[k0], ev[k1]); };
-    c->repl_ms[0] = span(0, 1) + (regrown ? span(2, 3) : 0.0f);
-    c->repl_ms[1] = span(4, 5) + span(6, 7);
-    c->repl_ms[2] = span(7, 8);
+    S.ms[0] = span(0, 1) + (regrown ? span(2, 3) : 0.0f);
+    S.ms[1] = span(4, 5) + span(6, 7);
+    S.ms[2] = span(7, 8);
+    return PHX_OK;
+}
+
+// Every device record's replacement into c->rp.h_rec / h_genes / h_det, once per run, on top of ensure_drops (with the one-hop trees).
+static int ensure_replacements(phx_ctx *c) {
+    if (c->done.repl) return PHX_OK;
+    { const int rd = ensure_drops(c, true); if (rd) return rd; }
+    const int nlm = margins_nl_mask(c);
+    DBatch b;
+    fill_batch(c, &b);
+    DMarg g;
+    margins_args(c, &g);
+    DDrop q;
+    drop_args(c, &q);
+    hipStream_t s = c->stream;
+    const int rc = replacement_pass(c, c->rp, (size_t)c->droff[(size_t)c->n], [&](int step, const DRepl &r) {
+        if (step == 0) phxk_repl_pick(&b, &g, &q, &r, nlm, s);
+        else if (step == 1) phxk_repl_cross(&b, &g, &q, &r, nlm, s);
+        else phxk_repl_walk(&b, &g, &q, &r, step - 2, s);
+    }, "drop replacements", "phx_replacements_flat");
+    if (rc) return rc;
     c->done.repl = true;
+    return PHX_OK;
+}
+
+// The layout both flat calls share: the records of contig i (device records [k0, k1) of S, those of CDS genes) to dst, `called` from the
+// drop records dd they go with, their genes appended to `genes` at *go, gene_off rebased.
+static void replacement_rows(const phx_ctx::ReplSet &S, int64_t k0, int64_t k1, const phx_gene_drop *dd, phx_gene_repl *dst, phx_gene *genes, int64_t *go) {
+    for (int64_t k = k0; k < k1; k++) {
+        const phx_gene_repl &x = S.h_rec[(size_t)k];
+        if (x.called < 0) continue;
+        *dst = x;
+        dst->called = dd->called;
+        dst->gene_off = *go;
+        const int64_t ng = x.n_removed + x.n_added;
+        if (ng) memcpy(genes + *go, S.h_genes.data() + x.gene_off, (size_t)ng * sizeof(phx_gene));
+        *go += ng;
+        dst++; dd++;
+    }
+}
+static int64_t replacement_genes(const phx_ctx::ReplSet &S, int64_t k0, int64_t k1) {
+    int64_t gt = 0;
+    for (int64_t k = k0; k < k1; k++) if (S.h_rec[(size_t)k].called >= 0) gt += S.h_rec[(size_t)k].n_removed + S.h_rec[(size_t)k].n_added;
+    return gt;
+}
+// The path of the k-th record of a contig, both taps: device records [k0, k1) of S, on the path of n_path nodes at dpath (device).
+static int replacement_tap(phx_ctx *c, phx_ctx::ReplSet &S, const char *who, int32_t contig, int64_t k0, int64_t k1, int32_t k, const int32_t *dpath, int np, int32_t *path, int32_t cap, int32_t *n_path) {
+    int64_t rk = -1;
+    for (int64_t q = k0, seen = 0; q < k1; q++)
+        if (S.h_rec[(size_t)q].called >= 0 && seen++ == k) { rk = q; break; }
+    if (rk < 0) return PHX_E_ARG;
+    if (!S.h_rec[(size_t)rk].bypass) return PHX_OK;
+    const int a = S.h_info[4 * rk], b = S.h_info[4 * rk + 1], nd = S.h_info[4 * rk + 2];
+    const int len = (a + 1) + nd + (np - b);
+    *n_path = len;
+    if (!path) return PHX_OK;
+    if (cap < len) return PHX_E_ARG;
+    std::vector<int32_t> &P = S.h_path[(size_t)contig]; // (the contig's device path, fetched at its first tap of this result)
+    if (P.empty()) {
+        try { P.resize((size_t)np); } catch (const std::bad_alloc &) { c->err = std::string("out of memory in ") + who; return PHX_E_NOMEM; }
+        HIPCHK(c, hipMemcpy(P.data(), dpath, (size_t)np * 4, hipMemcpyDeviceToHost));
+    }
+    int32_t *o = path;
+    for (int t = 0; t <= a; t++) *o++ = P[(size_t)t];
+    for (int t = 0; t < nd; t++) *o++ = S.h_det[(size_t)S.h_doff[(size_t)rk] + t];
+    for (int t = b; t < np; t++) *o++ = P[(size_t)t];
     return PHX_OK;
 }
 
@@ -419,31 +477,15 @@ int phx_replacements_flat(phx_ctx *c, phx_gene_repl *rec, int64_t cap, phx_gene 
     std::vector<phx_gene_drop> drec((size_t)total + 1);
     { const int rd = phx_drop_margins_flat(c, drec.data(), total, offsets, status, &total); if (rd) return rd; }
     int64_t gt = 0;
-    for (int i = 0; i < c->n; i++) {
-        if (offsets[i + 1] == offsets[i]) continue;
-        for (int64_t k = c->droff[(size_t)i]; k < c->droff[(size_t)i + 1]; k++) if (c->h_rrec[k].called >= 0) gt += c->h_rrec[k].n_removed + c->h_rrec[k].n_added;
-    }
+    for (int i = 0; i < c->n; i++)
+        if (offsets[i + 1] != offsets[i]) gt += replacement_genes(c->rp, c->droff[(size_t)i], c->droff[(size_t)i + 1]);
     if (total_out) *total_out = total;
     if (gene_total_out) *gene_total_out = gt;
     if (!rec || !genes) return PHX_OK; // size query
     if (cap < total || gene_cap < gt) return PHX_E_ARG;
     int64_t go = 0;
-    for (int i = 0; i < c->n; i++) {
-        if (offsets[i + 1] == offsets[i]) continue;
-        phx_gene_repl *dst = rec + offsets[i];
-        const phx_gene_drop *dd = drec.data() + offsets[i];
-        for (int64_t k = c->droff[(size_t)i]; k < c->droff[(size_t)i + 1]; k++) {
-            const phx_gene_repl &x = c->h_rrec[k];
-            if (x.called < 0) continue;
-            *dst = x;
-            dst->called = dd->called;
-            dst->gene_off = go;
-            const int64_t ng = x.n_removed + x.n_added;
-            if (ng) memcpy(genes + go, c->h_rgenes.data() + x.gene_off, (size_t)ng * sizeof(phx_gene));
-            go += ng;
-            dst++; dd++;
-        }
-    }
+    for (int i = 0; i < c->n; i++)
+        if (offsets[i + 1] != offsets[i]) replacement_rows(c->rp, c->droff[(size_t)i], c->droff[(size_t)i + 1], drec.data() + offsets[i], rec + offsets[i], genes, &go);
     } catch (const std::bad_alloc &) { c->err = "out of memory in phx_replacements_flat"; return PHX_E_NOMEM; }
     return PHX_OK;
 }
@@ -455,38 +497,19 @@ int phx_tap_replacement(phx_ctx *c, int32_t contig, int32_t k, int32_t *path, in
     if (contig < 0 || contig >= c->n || k < 0) return PHX_E_ARG;
     { const int rr = ensure_replacements(c); if (rr) return rr; }
     if (!drop_contig(c, (size_t)contig) || margins_status(c, contig) != 0) return PHX_E_ARG;
-    int64_t rk = -1;
-    for (int64_t q = c->droff[(size_t)contig], seen = 0; q < c->droff[(size_t)contig + 1]; q++)
-        if (c->h_rrec[q].called >= 0 && seen++ == k) { rk = q; break; }
-    if (rk < 0) return PHX_E_ARG;
-    if (!c->h_rrec[rk].bypass) return PHX_OK;
     const DMeta &m = c->meta[(size_t)contig];
-    const int a = c->h_rinfo[4 * rk], b = c->h_rinfo[4 * rk + 1], nd = c->h_rinfo[4 * rk + 2];
-    const int len = (a + 1) + nd + (m.n_path - b);
-    *n_path = len;
-    if (!path) return PHX_OK;
-    if (cap < len) return PHX_E_ARG;
-    std::vector<int32_t> &P = c->h_rpath[(size_t)contig]; // (the contig's device path, fetched at its first tap of this run)
-    if (P.empty()) {
-        try { P.resize((size_t)m.n_path); } catch (const std::bad_alloc &) { c->err = "out of memory in phx_tap_replacement"; return PHX_E_NOMEM; }
-        HIPCHK(c, hipMemcpy(P.data(), (int32_t *)c->b_path.p + m.node_off, (size_t)m.n_path * 4, hipMemcpyDeviceToHost));
-    }
-    int32_t *o = path;
-    for (int t = 0; t <= a; t++) *o++ = P[(size_t)t];
-    for (int t = 0; t < nd; t++) *o++ = c->h_rdet[(size_t)c->h_rdoff[(size_t)rk] + t];
-    for (int t = b; t < m.n_path; t++) *o++ = P[(size_t)t];
-    return PHX_OK;
+    return replacement_tap(c, c->rp, "phx_tap_replacement", contig, c->droff[(size_t)contig], c->droff[(size_t)contig + 1], k, (const int32_t *)c->b_path.p + m.node_off, m.n_path, path, cap, n_path);
 }
 
 int phx_replacements_ms(phx_ctx *c, float *ms) {
     if (!c || !ms) return PHX_E_ARG;
-    for (int k = 0; k < 3; k++) ms[k] = c->repl_ms[k];
+    for (int k = 0; k < 3; k++) ms[k] = c->rp.ms[k];
     return PHX_OK;
 }
 
 int phx_replacement_stats(phx_ctx *c, int64_t *out) {
     if (!c || !out) return PHX_E_ARG;
-    for (int k = 0; k < 5; k++) out[k] = c->repl_stats[k];
+    for (int k = 0; k < 5; k++) out[k] = c->rp.stats[k];
     return PHX_OK;
 }
 
@@ -714,6 +737,8 @@ static int reann_flat(phx_ctx *c, const char *who, bool need_forbid, const uint8
         c->done.remarg = false; // (the re-annotation margins are this solve's)
         c->done.pinmarg = false;
         c->done.redrop = false;
+        c->done.retrees = false;
+        c->done.rerepl = false;
         c->h_qsel.assign((size_t)c->n, 0);
         c->h_qnreq.assign((size_t)c->n, 0);
         for (int i = 0; i < c->n; i++) {
@@ -1047,14 +1072,56 @@ int phx_pinmargins_ms(phx_ctx *c, float *ms) {
 // the contigs the conditioned drop kernels cover (dp_on<MgDrop>), after ensure_condmargins<CmPlain>
 static bool redrop_contig(const phx_ctx *c, size_t i) { return c->h_qsel[i] && c->xm.h_sel[i] == 1 && !c->xm.mstat[i] && c->h_qrec[i].n_path >= 3; }
 
+// the kernels' view of the feature's own DDrop set (with the one-hop trees once they were asked for)
+static void redrop_args(phx_ctx *c, DDrop *q) {
+    const size_t n = (size_t)c->n;
+    q->pidx = (int32_t *)c->b_rdpi.p; q->js = (int32_t *)c->b_rdjs.p; q->jt = (int32_t *)c->b_rdjt.p; q->first = (int32_t *)c->b_rdfi.p; q->last = (int32_t *)c->b_rdla.p;
+    q->slot = (uint64_t *)c->b_rdslot.p; q->gtab = (uint64_t *)c->b_rdgtab.p;
+    q->toff = (const int64_t *)c->b_rdtro.p; q->roff = (const int64_t *)c->b_rdtro.p + n;
+    q->sx = (uint64_t *)c->b_rdsx.p; q->cx = (uint64_t *)c->b_rdcx.p; q->da = (uint64_t *)c->b_rdda.p; q->db = (uint64_t *)c->b_rddb.p;
+    q->rec = (phx_gene_drop *)c->b_rdrec.p; q->stats = (unsigned long long *)c->b_rdstats.p;
+    { DDrop env; drop_args(c, &env); q->layered = env.layered; } // (env PHX_DROP_LAYERED, read where the run's drops read it)
+    q->ps = c->done.retrees ? (int32_t *)c->b_rdps.p : nullptr; q->ts = c->done.retrees ? (int32_t *)c->b_rdts.p : nullptr;
+}
+// the conditioned kernels' view of what the last re-annotation and its margins left resident (after ensure_condmargins<CmPlain>)
+struct RedropView {
+    DBatch b, qb;
+    DMarg g;
+    DReann rq;
+    DRmarg r;
+    const int32_t *qpath;
+};
+static void redrop_view(phx_ctx *c, RedropView *v) {
+    fill_batch(c, &v->b);
+    margins_args(c, &v->g);
+    reann_batch(c, &v->qb, &v->rq);
+    condmargins_args(c, c->xm, (size_t)c->tot_edge / 32 + 2, &v->r);
+    v->qpath = (const int32_t *)c->b_qpath.p;
+}
 // The records of every pair of every re-annotation path into c->h_rdrec (at c->rdroff), once per re-annotation solve.  On top of the
 // re-annotation margins (the out-edge bitmaps, d_t' and the pass's verdicts: their ORF records come with them, a launch and a copy beside
 // the reverse pass) and, when a contig was not solved again, of the run's drop margins.  Reads what the solve and its margins left resident;
-// writes only the b_rd* set: the run's drops and replacements stay as they are.
-static int ensure_redrops(phx_ctx *c) {
-    if (c->done.redrop) return PHX_OK;
+// writes only the b_rd* set: the run's drops and replacements stay as they are.  trees: as ensure_drops' (b_rdps / b_rdts, for §30).
+static int ensure_redrops(phx_ctx *c, bool trees = false) {
+    if (c->done.redrop && (!trees || c->done.retrees)) return PHX_OK;
+    if (c->done.redrop) { // drops computed without the trees: k_dp_tree once more, which rewrites the same labels
+        c->done.retrees = true;
+        if (!c->redrop_nlm) return PHX_OK;
+        const size_t nv = ((size_t)c->tot_node + (size_t)c->n + 1) * 4;
+        int rc;
+        if ((rc = ensure(c, c->b_rdps, nv)) || (rc = ensure(c, c->b_rdts, nv)) || (rc = ensure(c, c->rr.b_cnt, 2 * RP_NCNT * 8))) return rc;
+        RedropView v;
+        redrop_view(c, &v);
+        DDrop q;
+        redrop_args(c, &q);
+        q.stats = (unsigned long long *)c->rr.b_cnt.p + RP_NCNT; // (the redrops' own counters stay as they were)
+        phxk_redrop_trees(&v.b, &v.g, &v.rq, &v.r, v.qpath, &q, c->redrop_nlm, c->stream);
+        HIPCHK(c, hipGetLastError());
+        return PHX_OK;
+    }
+    if (trees) c->done.retrees = true;
     { const int rm = ensure_condmargins<CmPlain>(c); if (rm) return rm; }
-    const size_t n = (size_t)c->n, V = (size_t)c->tot_node, E = (size_t)c->tot_edge;
+    const size_t n = (size_t)c->n, V = (size_t)c->tot_node;
     bool unsolved = false;
     for (size_t i = 0; i < n; i++) unsolved = unsolved || !c->h_qsel[i];
     if (unsolved) { const int rd = ensure_drops(c); if (rd) return rd; }
@@ -1074,6 +1141,7 @@ static int ensure_redrops(phx_ctx *c) {
     }
     off[2 * n] = R; c->rdroff[n] = R;
     for (int k = 0; k < 4; k++) { c->redrop_ms[k] = 0; c->redrop_stats[k] = 0; }
+    c->redrop_nlm = nlm;
     if (!nlm) { c->done.redrop = true; return PHX_OK; }
     int rc;
     const size_t nv = (V + n + 1) * 4;
@@ -1085,26 +1153,18 @@ static int ensure_redrops(phx_ctx *c) {
     if ((rc = ensure(c, c->b_rdda, (V + 1) * limbs * 8)) || (rc = ensure(c, c->b_rddb, (V + 1) * limbs * 8))) return rc;
     if ((rc = ensure(c, c->b_rdrec, ((size_t)R + 1) * sizeof(phx_gene_drop)))) return rc;
     if ((rc = ensure(c, c->b_rdstats, 4 * 8))) return rc;
+    if (c->done.retrees && ((rc = ensure(c, c->b_rdps, nv)) || (rc = ensure(c, c->b_rdts, nv)))) return rc;
     if ((rc = analysis_events(c))) return rc;
     try { c->h_rdrec.resize((size_t)R + 1); } catch (const std::bad_alloc &) { c->err = "out of memory in phx_redrops_flat"; return PHX_E_NOMEM; }
-    DBatch b;
-    fill_batch(c, &b);
-    DMarg g;
-    margins_args(c, &g);
-    DBatch qb;
-    DReann rq;
-    reann_batch(c, &qb, &rq);
-    DRmarg r;
-    condmargins_args(c, c->xm, E / 32 + 2, &r);
+    RedropView v;
+    redrop_view(c, &v);
+    const DBatch &b = v.b;
+    const DMarg &g = v.g;
+    const DReann &rq = v.rq;
+    const DRmarg &r = v.r;
     DDrop q;
-    q.pidx = (int32_t *)c->b_rdpi.p; q.js = (int32_t *)c->b_rdjs.p; q.jt = (int32_t *)c->b_rdjt.p; q.first = (int32_t *)c->b_rdfi.p; q.last = (int32_t *)c->b_rdla.p;
-    q.slot = (uint64_t *)c->b_rdslot.p; q.gtab = (uint64_t *)c->b_rdgtab.p;
-    q.toff = (const int64_t *)c->b_rdtro.p; q.roff = (const int64_t *)c->b_rdtro.p + n;
-    q.sx = (uint64_t *)c->b_rdsx.p; q.cx = (uint64_t *)c->b_rdcx.p; q.da = (uint64_t *)c->b_rdda.p; q.db = (uint64_t *)c->b_rddb.p;
-    q.rec = (phx_gene_drop *)c->b_rdrec.p; q.stats = (unsigned long long *)c->b_rdstats.p;
-    { DDrop env; drop_args(c, &env); q.layered = env.layered; } // (env PHX_DROP_LAYERED, read where the run's drops read it)
-    q.ps = nullptr; q.ts = nullptr;
-    const int32_t *qpath = (const int32_t *)c->b_qpath.p;
+    redrop_args(c, &q);
+    const int32_t *qpath = v.qpath;
     hipStream_t s = c->stream;
     unsigned long long st[4] = {0, 0, 0, 0};
     HIPCHK(c, hipEventRecord(c->aev[0], s));
@@ -1191,6 +1251,96 @@ int phx_redrops_ms(phx_ctx *c, float *ms) {
 int phx_redrop_stats(phx_ctx *c, int64_t *out) {
     if (!c || !out) return PHX_E_ARG;
     for (int k = 0; k < 4; k++) out[k] = c->redrop_stats[k];
+    return PHX_OK;
+}
+
+// ---- re-annotation replacements (phx_replace.inc under MgDrop, DESIGN.md §30) ----
+// Every record of h_rdrec gets its replacement into c->rr (h_rec / h_genes / h_det at rdroff's indices), once per re-annotation solve, on
+// top of ensure_redrops with the one-hop trees and, when a contig was not solved again, of the run's replacements.  Writes the rr set and
+// b_rdps / b_rdts only (and, as §13 does on its own set, the scratch the drop kernels left: js / jt / gtab of b_rd*).
+static int ensure_rereplacements(phx_ctx *c) {
+    if (c->done.rerepl) return PHX_OK;
+    { const int rd = ensure_redrops(c, true); if (rd) return rd; }
+    const size_t n = (size_t)c->n;
+    bool unsolved = false;
+    for (size_t i = 0; i < n; i++) unsolved = unsolved || !c->h_qsel[i];
+    if (unsolved) { const int rr = ensure_replacements(c); if (rr) return rr; }
+    phx_ctx::ReplSet &S = c->rr;
+    for (int k = 0; k < 3; k++) S.ms[k] = 0;
+    for (int k = 0; k < 5; k++) S.stats[k] = 0;
+    const int nlm = c->redrop_nlm;
+    if (!nlm) { c->done.rerepl = true; return PHX_OK; } // (no contig was solved again with a path: nothing is allocated)
+    RedropView v;
+    redrop_view(c, &v);
+    DDrop q;
+    redrop_args(c, &q);
+    hipStream_t s = c->stream;
+    const int rc = replacement_pass(c, S, (size_t)c->rdroff[n], [&](int step, const DRepl &r) {
+        if (step == 0) phxk_rerepl_pick(&v.b, &v.g, &v.rq, &v.r, v.qpath, &q, &r, nlm, s);
+        else if (step == 1) phxk_rerepl_cross(&v.b, &v.g, &v.rq, &v.r, v.qpath, &q, &r, nlm, s);
+        else phxk_rerepl_walk(&v.b, &v.g, &v.rq, &v.r, v.qpath, &q, &r, step - 2, s);
+    }, "re-annotation replacements", "phx_rereplacements_flat");
+    if (rc) return rc;
+    c->done.rerepl = true;
+    return PHX_OK;
+}
+
+int phx_rereplacements_flat(phx_ctx *c, phx_gene_repl *rec, int64_t cap, phx_gene *genes, int64_t gene_cap, int64_t *offsets, int32_t *status,
+                            int64_t *total_out, int64_t *gene_total_out) {
+    if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
+    { const int ra = after_run(c); if (ra) return ra; }
+    { const int rs = remarg_state(c, "phx_rereplacements_flat"); if (rs) return rs; } // before any kernel
+    { const int rr = ensure_rereplacements(c); if (rr) return rr; }
+    // statuses, offsets and `called` exactly as the re-annotation's drop records have them
+    int64_t total = 0;
+    { const int rd = phx_redrops_flat(c, nullptr, 0, offsets, status, &total); if (rd) return rd; }
+    try {
+    std::vector<phx_gene_drop> drec((size_t)total + 1);
+    { const int rd = phx_redrops_flat(c, drec.data(), total, offsets, status, &total); if (rd) return rd; }
+    // a contig that was not solved again: the run's records, as phx_replacements_flat lays them out
+    auto set_of = [&](int i, int64_t *k0, int64_t *k1) -> const phx_ctx::ReplSet & {
+        const bool again = c->h_qsel[(size_t)i] != 0;
+        const std::vector<int64_t> &ro = again ? c->rdroff : c->droff;
+        *k0 = ro[(size_t)i]; *k1 = ro[(size_t)i + 1];
+        return again ? c->rr : c->rp;
+    };
+    int64_t gt = 0, k0, k1;
+    for (int i = 0; i < c->n; i++)
+        if (offsets[i + 1] != offsets[i]) { const phx_ctx::ReplSet &S = set_of(i, &k0, &k1); gt += replacement_genes(S, k0, k1); }
+    if (total_out) *total_out = total;
+    if (gene_total_out) *gene_total_out = gt;
+    if (!rec || !genes) return PHX_OK; // size query
+    if (cap < total || gene_cap < gt) return PHX_E_ARG;
+    int64_t go = 0;
+    for (int i = 0; i < c->n; i++)
+        if (offsets[i + 1] != offsets[i]) { const phx_ctx::ReplSet &S = set_of(i, &k0, &k1); replacement_rows(S, k0, k1, drec.data() + offsets[i], rec + offsets[i], genes, &go); }
+    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_rereplacements_flat"; return PHX_E_NOMEM; }
+    return PHX_OK;
+}
+
+int phx_tap_rereplacement(phx_ctx *c, int32_t contig, int32_t k, int32_t *path, int32_t cap, int32_t *n_path) {
+    if (!c || !n_path) return PHX_E_ARG;
+    *n_path = 0;
+    { const int ra = after_run(c); if (ra) return ra; }
+    if (contig < 0 || contig >= c->n || k < 0) return PHX_E_ARG;
+    { const int rs = remarg_state(c, "phx_tap_rereplacement"); if (rs) return rs; }
+    if (!c->h_qsel[(size_t)contig]) return phx_tap_replacement(c, contig, k, path, cap, n_path); // the run's result stands
+    { const int rr = ensure_rereplacements(c); if (rr) return rr; }
+    if (!redrop_contig(c, (size_t)contig) || condmargins_status(c, contig) != 0) return PHX_E_ARG;
+    const DMeta &m = c->meta[(size_t)contig];
+    return replacement_tap(c, c->rr, "phx_tap_rereplacement", contig, c->rdroff[(size_t)contig], c->rdroff[(size_t)contig + 1], k, (const int32_t *)c->b_qpath.p + m.node_off,
+                           c->h_qrec[(size_t)contig].n_path, path, cap, n_path);
+}
+
+int phx_rereplacements_ms(phx_ctx *c, float *ms) {
+    if (!c || !ms) return PHX_E_ARG;
+    for (int k = 0; k < 3; k++) ms[k] = c->rr.ms[k];
+    return PHX_OK;
+}
+
+int phx_rereplacement_stats(phx_ctx *c, int64_t *out) {
+    if (!c || !out) return PHX_E_ARG;
+    for (int k = 0; k < 5; k++) out[k] = c->rr.stats[k];
     return PHX_OK;
 }
 

@@ -236,12 +236,14 @@ struct phx_ctx {
         bool margins = false; // the ORF records are in h_mrec (device ORF order)
         bool drops = false;   // the drop records are in h_drec (a record per pair of the path), at droff
         bool trees = false;   // ... and the drop kernels kept the one-hop trees (b_dps / b_dts)
-        bool repl = false;    // h_rrec / h_rgenes / h_rdet
+        bool repl = false;    // rp.h_rec / h_genes / h_det
         bool reann = false;   // h_q* hold the re-annotation for the mask h_qforb / h_qflags
         bool scen = false;    // h_s* hold the scenario batch h_skey
         bool remarg = false;  // xm.h_rec / xm.mstat hold the margins of the re-annotation h_q* hold (also reset by every re-annotation solve)
         bool pinmarg = false; // pm.h_rec / pm.h_lost / pm.mstat hold the pinned margins of the re-annotation h_q* hold (reset wherever remarg is)
         bool redrop = false;  // h_rdrec holds the drop margins of the re-annotation h_q* hold, at rdroff (reset wherever remarg is)
+        bool retrees = false; // ... and the drop kernels kept that graph's one-hop trees (b_rdps / b_rdts; reset wherever redrop is)
+        bool rerepl = false;  // rr.h_rec / h_genes / h_det hold the replacements of the re-annotation h_q* hold (reset wherever redrop is)
         bool grp = false;     // h_grp
     } done;
     std::vector<DGrp> h_grp;         // the run's group records (device order <-> reference order of the ORFs: each_group_in_reference_order)
@@ -258,15 +260,20 @@ struct phx_ctx {
     float drop_ms[4] = {0, 0, 0, 0};
     int64_t drop_stats[4] = {0, 0, 0, 0};
     // drop replacements (phx_replacements_flat): buffers allocated at the first call, results kept until the next run
-    DevBuf b_dps, b_dts, b_rwin, b_rxs, b_rcoff, b_rcm, b_rchain, b_rrnd, b_rinfo, b_rdoff, b_rdet, b_rgenes, b_rrec, b_rcnt;
-    std::vector<phx_gene_repl> h_rrec; // per device record (as h_drec); gene_off into h_rgenes
-    std::vector<phx_gene> h_rgenes;
-    std::vector<int32_t> h_rdet, h_rinfo; // the detours; per record a, b, m, genes
-    std::vector<int64_t> h_rdoff;     // per record: first detour node in h_rdet
-    std::vector<std::vector<int32_t>> h_rpath; // per contig: its device path, fetched by the first phx_tap_replacement of the run
-    int64_t rchain_cap = 0;           // delta-chain nodes b_rchain has room for
-    float repl_ms[3] = {0, 0, 0};
-    int64_t repl_stats[5] = {0, 0, 0, 0, 0};
+    // (rp: the run's set.  rr: the set of the re-annotation replacements, phx_rereplacements_flat, DESIGN.md §30 — allocated at the first call
+    // that has a solved-again contig for it, the result kept until the next re-annotation solve or run; rp is not touched by it.)
+    DevBuf b_dps, b_dts;
+    struct ReplSet {
+        DevBuf b_win, b_xs, b_coff, b_cm, b_chain, b_rnd, b_info, b_doff, b_det, b_genes, b_rec, b_cnt; // DRepl
+        std::vector<phx_gene_repl> h_rec; // per device record (as h_drec / h_rdrec); gene_off into h_genes
+        std::vector<phx_gene> h_genes;
+        std::vector<int32_t> h_det, h_info; // the detours; per record a, b, m, genes
+        std::vector<int64_t> h_doff;      // per record: first detour node in h_det
+        std::vector<std::vector<int32_t>> h_path; // per contig: its device path, fetched by the first path tap of the result
+        int64_t chain_cap = 0;            // delta-chain nodes b_chain has room for
+        float ms[3] = {0, 0, 0};
+        int64_t stats[5] = {0, 0, 0, 0, 0};
+    } rp, rr;
     // masked re-annotation (phx_reannotate_flat): buffers allocated at the first call, the result kept until the next upload or run
     DevBuf b_qmeta, b_qtot, b_qdist, b_qparent, b_qpath, b_qgenes, b_qgtot, b_qtie, b_qmask, b_qforb, b_qsel, b_qplan, b_qrec;
     DevBuf b_qbias, b_qbval, b_qbsum; // evidence-weighted re-annotation (phx_evidence_flat): B per ORF, B per in-edge slot, the sums of |B| per contig; allocated at its first call
@@ -300,6 +307,8 @@ struct phx_ctx {
     // re-annotation drop margins (phx_redrops_flat): a second DDrop set, allocated at the first call that has a contig for it; the
     // result kept until the next re-annotation solve or run.  The run's own drops and replacements (b_d*, b_r*) are not touched.
     DevBuf b_rdpi, b_rdjs, b_rdjt, b_rdfi, b_rdla, b_rdslot, b_rdgtab, b_rdtro, b_rdsx, b_rdcx, b_rdda, b_rddb, b_rdrec, b_rdstats;
+    DevBuf b_rdps, b_rdts;              // the one-hop trees of that graph, for the re-annotation replacements (§30)
+    int redrop_nlm = 0;                 // the limb classes among the contigs h_rdrec covers (0: none)
     std::vector<int64_t> rdroff;        // per contig (+1): first record in h_rdrec (a contig that is not covered: none)
     std::vector<phx_gene_drop> h_rdrec; // a record per pair of the re-annotation's path
     float redrop_ms[4] = {0, 0, 0, 0};

@@ -548,6 +548,10 @@ void phxk_redrop_fix(const DBatch *b, const DMarg *g, const DReann *rq, const DR
 void phxk_repl_pick(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream); // drop replacements (phx_replace.inc): winners,
 void phxk_repl_cross(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream); //   cross winners and their delta chains,
 void phxk_repl_walk(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int fill, void *stream);    //   detour lengths (fill 0) / detours, genes, records (1)
+// re-annotation replacements (§30; the arguments of phxk_redrop_*, q with DDrop.ps / ts, rr: the feature's own DRepl set): the three steps under MgDrop
+void phxk_rerepl_pick(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, const DRepl *rr, int nl_mask, void *stream);
+void phxk_rerepl_cross(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, const DRepl *rr, int nl_mask, void *stream);
+void phxk_rerepl_walk(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, const DRepl *rr, int fill, void *stream);
 // re-annotation (phx_resolve.inc).  b: the re-annotation's view of the batch; nl_masks[RE_MODES]: per mode, the limb classes of its contigs
 void phxk_reann_mask(const DBatch *b, const DReann *q, void *stream);                         // the refused, required and biased ORFs' marks,
 void phxk_reann_solve(const DBatch *b, const DReann *q, const int *nl_masks, void *stream);   //   the sweep under each mode's policy,

@@ -491,6 +491,19 @@ void phxk_repl_walk(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl
     if (fill) hipLaunchKernelGGL(k_rp_walk<1>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q, *r);
     else hipLaunchKernelGGL(k_rp_walk<0>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q, *r);
 }
+// re-annotation replacements: the same three kernels under MgDrop, on the DDrop set of the re-annotation drop margins (q, with
+// its one-hop trees) and a DRepl set of the feature's own (rr)
+void phxk_rerepl_pick(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, const DRepl *rr, int nl_mask, void *stream) {
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_rp_pick<decltype(nl)::value, MgDrop>), dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, dp_args(g, rq, r, qpath), *q, *rr); });
+}
+void phxk_rerepl_cross(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, const DRepl *rr, int nl_mask, void *stream) {
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_rp_cross<decltype(nl)::value, MgDrop>), dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, dp_args(g, rq, r, qpath), *q, *rr); });
+}
+void phxk_rerepl_walk(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, const DRepl *rr, int fill, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (fill) hipLaunchKernelGGL((k_rp_walk<1, MgDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, dp_args(g, rq, r, qpath), *q, *rr);
+    else hipLaunchKernelGGL((k_rp_walk<0, MgDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, dp_args(g, rq, r, qpath), *q, *rr);
+}
 size_t phxk_sssp_lds_bytes(int V, int nl) { return sssp_lds_bytes(V, nl); }
 // re-annotation (phx_resolve.inc): b is the re-annotation's view of the batch (outputs of its own)
 void phxk_reann_mask(const DBatch *b, const DReann *q, void *stream) { hipLaunchKernelGGL(k_rs_mask, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), 0, (hipStream_t)stream, *b, *q); }

@@ -15,6 +15,11 @@
 //      A counting pass (detour length, genes), the host's offsets, a filling pass (detour, removed and added genes, records).
 // Tie rule: (cost; a step-3 candidate before a cross candidate; source node id; head node id), contig-local ids: no batch, flag or CSR order
 // enters a witness (the layered trees may choose other tight parents).
+// The policy of the three kernels is the type of their second argument, as for the k_dp_* kernels (phx_drop.inc).  DMarg: the run's graph and
+// path.  MgDrop (the re-annotation replacements, DESIGN.md §30): the graph G' and the path P' of the last re-annotation, the labels and minima
+// of its drop margins (a second DDrop set, with its own one-hop trees), the outputs in a second DRepl set.  Every edge loop skips a refused
+// slot and adds the bias of a biased one exactly as k_dp_cand / k_dp_cross<NL, MgDrop> do, so the candidates are the same set; a node outside
+// R has no label and enters nothing.  k_rp_walk takes the path and its length from the policy and nothing else: a witness walks tree pointers.
 
 #define RP_CROSS (1ull << 63) // DRepl.win: a cross winner (y << 32 | z)
 #define RP_NONE (~0ull)
@@ -35,20 +40,24 @@ __device__ __forceinline__ void st_l2(uint64_t *p, uint64_t v) { __hip_atomic_st
 // Level 0 of the table holds M_j saturated to 64 bits at gene slots (DP_NONE: no bypass, which no candidate can cover) and 0 elsewhere
 // (never above a candidate); level k entry i the maximum of slots [i, i + 2^k).  In LDS up to DP_TAB_LDS entries, else the contig's slice of
 // DDrop.gtab (k_dp_cand is done with it).
-template <int NL>
-__global__ __launch_bounds__(NT) void k_rp_pick(DBatch b, DMarg g, DDrop q, DRepl r) {
+template <int NL, class G = DMarg>
+__global__ __launch_bounds__(NT) void k_rp_pick(DBatch b, G g, DDrop q, DRepl r) {
+    constexpr bool COND = mg_cond<G>;
     __shared__ unsigned long long s_tab[DP_TAB_LDS];
     const DMeta *meta = &b.meta[blockIdx.x];
-    if (!dp_contig(b, g, meta) || meta->sssp_nl != NL) return;
-    const int V = meta->n_node, n = meta->n_path, np = (n - 1) / 2, tid = threadIdx.x;
+    if (!dp_on<G>(b, g, meta) || meta->sssp_nl != NL) return;
+    const int V = meta->n_node, n = dp_npath<G>(b, g, meta), np = (n - 1) / 2, tid = threadIdx.x;
     const size_t no = (size_t)meta->node_off;
-    const int32_t *path = b.path + no;
+    const int32_t *path = dp_path<G>(b, g, meta);
     const uint32_t *in_off = b.in_off + no + blockIdx.x;
     const uint32_t *esrc = b.esrc + meta->edge_off;
     const long long *ew = b.ew + meta->edge_off;
     const long long *gt = gtab_of(b, meta);
-    const uint64_t *ds = b.dist + no * b.dist_stride;
-    const uint64_t *dt = g.dist_t + no * b.dist_stride;
+    const uint64_t *ds = dp_ds<G>(b, g, meta);
+    const uint64_t *dt = dp_dt<G>(b, g, meta);
+    [[maybe_unused]] const uint64_t ebase = (uint64_t)meta->edge_off;
+    [[maybe_unused]] bool biased = false;
+    if constexpr (COND) biased = re_mode_bias(g.q.mode[blockIdx.x]);
     const int32_t *first = q.first + no, *last = q.last + no;
     const int64_t r0 = q.roff[blockIdx.x];
     int lv = 1;
@@ -78,13 +87,16 @@ __global__ __launch_bounds__(NT) void k_rp_pick(DBatch b, DMarg g, DDrop q, DRep
         const int lz = last[z];
         if (lz < 2) continue;
         const WInt<NL> tz = wi_add<NL>(wi_load<NL>(dt + (size_t)z * NL), negD);
+        [[maybe_unused]] bool sp = false;
+        if constexpr (COND) sp = dp_sp_in(g, biased, ebase, in_off[z], in_off[z + 1]);
         for (uint32_t e = in_off[z], e1 = in_off[z + 1]; e < e1; e++) {
             const uint32_t sw = esrc[e];
             const int x = (int)ESRC_NODE(sw);
             const int fx = first[x];
             if (fx < 0 || fx + 1 > lz - 1) continue;
+            if constexpr (COND) { if (sp && mg_bit(g.q.mask, ebase + e)) continue; }
             const int a = fx + 1, e2 = lz - 1, k = 31 - __clz(e2 - a + 1);
-            const WInt<NL> c = wi_add<NL>(wi_add<NL>(wi_load<NL>(ds + (size_t)x * NL), ew_decode<NL>(edge_wenc(sw, ew, e, gt))), tz);
+            const WInt<NL> c = wi_add<NL>(wi_add<NL>(wi_load<NL>(ds + (size_t)x * NL), dp_w_in<NL>(g, sp, biased, ebase + e, ew_decode<NL>(edge_wenc(sw, ew, e, gt)))), tz);
             const uint64_t key = wi_sat64<NL>(c);
             const uint64_t m1 = ld_l2(&tab[k * n + a]), m2 = ld_l2(&tab[k * n + e2 - (1 << k) + 1]);
             if (key != (m1 > m2 ? m1 : m2)) continue; // not the range maximum: above every slot it covers
@@ -104,16 +116,17 @@ __global__ __launch_bounds__(NT) void k_rp_pick(DBatch b, DMarg g, DDrop q, DRep
 // The cross list as k_dp_cross builds it (DDrop.js / jt); per slot whose minimum only step 4 attains, the Jacobi rounds of k_dp_cross with
 // DRepl.rnd[p] = the last round that lowered delta(p) (0: the seed).  A node that settled in round r > 0 has a tight in-edge from a node
 // that settled before r, so the chain back from y ends at a seed.  The chain goes to DRepl.chain at an atomically reserved offset.
-template <int NL>
-__global__ __launch_bounds__(NT) void k_rp_cross(DBatch b, DMarg g, DDrop q, DRepl r) {
+template <int NL, class G = DMarg>
+__global__ __launch_bounds__(NT) void k_rp_cross(DBatch b, G g, DDrop q, DRepl r) {
+    constexpr bool COND = mg_cond<G>;
     __shared__ uint64_t s_d[2][DP_CROSS_LDS * NL];
     __shared__ int s_nc, s_chg;
     __shared__ unsigned long long s_key;
     const DMeta *meta = &b.meta[blockIdx.x];
-    if (!dp_contig(b, g, meta) || meta->sssp_nl != NL) return;
-    const int V = meta->n_node, np = (meta->n_path - 1) / 2, tid = threadIdx.x;
+    if (!dp_on<G>(b, g, meta) || meta->sssp_nl != NL) return;
+    const int V = meta->n_node, np = (dp_npath<G>(b, g, meta) - 1) / 2, tid = threadIdx.x;
     const size_t no = (size_t)meta->node_off;
-    const int32_t *path = b.path + no;
+    const int32_t *path = dp_path<G>(b, g, meta);
     const uint32_t *in_off = b.in_off + no + blockIdx.x;
     const uint32_t *esrc = b.esrc + meta->edge_off;
     const long long *ew = b.ew + meta->edge_off;
@@ -121,8 +134,11 @@ __global__ __launch_bounds__(NT) void k_rp_cross(DBatch b, DMarg g, DDrop q, DRe
     const uint32_t *oo = g.out_off + no + blockIdx.x;
     const uint32_t *od = g.out_dst + meta->edge_off;
     const long long *ow = g.out_w + meta->edge_off;
-    const uint64_t *ds = b.dist + no * b.dist_stride;
-    const uint64_t *dt = g.dist_t + no * b.dist_stride;
+    const uint64_t *ds = dp_ds<G>(b, g, meta);
+    const uint64_t *dt = dp_dt<G>(b, g, meta);
+    [[maybe_unused]] const uint64_t ebase = (uint64_t)meta->edge_off;
+    [[maybe_unused]] bool biased = false;
+    if constexpr (COND) biased = re_mode_bias(g.q.mode[blockIdx.x]);
     const int32_t *first = q.first + no, *last = q.last + no, *pidx = q.pidx + no;
     int32_t *clist = q.js + no, *cpos = q.jt + no, *rnd = r.rnd + no;
     const int64_t r0 = q.roff[blockIdx.x];
@@ -151,13 +167,16 @@ __global__ __launch_bounds__(NT) void k_rp_cross(DBatch b, DMarg g, DDrop q, DRe
         for (int p = tid; p < nc; p += NT) {
             const int y = clist[p];
             WInt<NL> d = wi_inf<NL>();
+            [[maybe_unused]] bool sp = false;
+            if constexpr (COND) { if (in_y(y)) sp = dp_sp_in(g, biased, ebase, in_off[y], in_off[y + 1]); }
             if (in_y(y))
                 for (uint32_t e = in_off[y], e1 = in_off[y + 1]; e < e1; e++) {
                     const uint32_t sw = esrc[e];
                     const int x = (int)ESRC_NODE(sw);
                     const int fx = first[x];
                     if (fx < 0 || fx >= j) continue;
-                    const WInt<NL> c = wi_add<NL>(wi_load<NL>(ds + (size_t)x * NL), ew_decode<NL>(edge_wenc(sw, ew, e, gt)));
+                    if constexpr (COND) { if (sp && mg_bit(g.q.mask, ebase + e)) continue; }
+                    const WInt<NL> c = wi_add<NL>(wi_load<NL>(ds + (size_t)x * NL), dp_w_in<NL>(g, sp, biased, ebase + e, ew_decode<NL>(edge_wenc(sw, ew, e, gt))));
                     if (wi_lt<NL>(c, d)) d = c;
                 }
             wi_store<NL>(bufA + (size_t)p * NL, d);
@@ -171,14 +190,17 @@ __global__ __launch_bounds__(NT) void k_rp_cross(DBatch b, DMarg g, DDrop q, DRe
             for (int p = tid; p < nc; p += NT) {
                 const int y = clist[p];
                 WInt<NL> d = wi_load<NL>(cur + (size_t)p * NL);
+                [[maybe_unused]] bool sp = false;
+                if constexpr (COND) { if (in_y(y)) sp = dp_sp_in(g, biased, ebase, in_off[y], in_off[y + 1]); }
                 if (in_y(y))
                     for (uint32_t e = in_off[y], e1 = in_off[y + 1]; e < e1; e++) {
                         const uint32_t sw = esrc[e];
                         const int x = (int)ESRC_NODE(sw);
                         if (!in_y(x)) continue;
+                        if constexpr (COND) { if (sp && mg_bit(g.q.mask, ebase + e)) continue; }
                         const WInt<NL> dx = wi_load<NL>(cur + (size_t)cpos[x] * NL);
                         if (wi_is_inf<NL>(dx)) continue;
-                        const WInt<NL> c = wi_add<NL>(dx, ew_decode<NL>(edge_wenc(sw, ew, e, gt)));
+                        const WInt<NL> c = wi_add<NL>(dx, dp_w_in<NL>(g, sp, biased, ebase + e, ew_decode<NL>(edge_wenc(sw, ew, e, gt))));
                         if (wi_lt<NL>(c, d)) { d = c; s_chg = 1; rnd[p] = rr; }
                     }
                 wi_store<NL>(nxt + (size_t)p * NL, d);
@@ -195,10 +217,13 @@ __global__ __launch_bounds__(NT) void k_rp_cross(DBatch b, DMarg g, DDrop q, DRe
             if (!in_y(y)) continue;
             const WInt<NL> d = wi_load<NL>(cur + (size_t)p * NL);
             if (wi_is_inf<NL>(d)) continue;
+            [[maybe_unused]] bool sp = false;
+            if constexpr (COND) sp = dp_sp_out(g, ebase, oo[y], oo[y + 1]);
             for (uint32_t e = oo[y], e1 = oo[y + 1]; e < e1; e++) {
                 const int z = (int)od[e];
                 if (last[z] <= j) continue;
-                const WInt<NL> c = wi_add<NL>(wi_add<NL>(d, ew_decode<NL>(ow[e])), wi_add<NL>(wi_load<NL>(dt + (size_t)z * NL), negD));
+                if constexpr (COND) { if (sp && mg_bit(g.r.fbit, ebase + e)) continue; }
+                const WInt<NL> c = wi_add<NL>(wi_add<NL>(d, dp_w_out<NL>(g, sp, ebase + e, ew_decode<NL>(ow[e]))), wi_add<NL>(wi_load<NL>(dt + (size_t)z * NL), negD));
                 if (wi_eq<NL>(c, m)) atomicMin(&s_key, (unsigned long long)(((uint64_t)y << 32) | (uint32_t)z));
             }
         }
@@ -211,19 +236,22 @@ __global__ __launch_bounds__(NT) void k_rp_cross(DBatch b, DMarg g, DDrop q, DRe
                     const int pv = cpos[v], rv = rnd[pv];
                     const WInt<NL> dv = wi_load<NL>(cur + (size_t)pv * NL);
                     int best = -1;
+                    [[maybe_unused]] bool sp = false;
+                    if constexpr (COND) sp = dp_sp_in(g, biased, ebase, in_off[v], in_off[v + 1]);
                     for (uint32_t e = in_off[v], e1 = in_off[v + 1]; e < e1; e++) {
                         const uint32_t sw = esrc[e];
                         const int u = (int)ESRC_NODE(sw);
                         if (best >= 0 && u >= best) continue;
+                        if constexpr (COND) { if (sp && mg_bit(g.q.mask, ebase + e)) continue; }
                         const long long we = edge_wenc(sw, ew, e, gt);
                         if (rv == 0) {
                             const int fu = first[u];
                             if (fu < 0 || fu >= j) continue;
-                            if (wi_eq<NL>(wi_add<NL>(wi_load<NL>(ds + (size_t)u * NL), ew_decode<NL>(we)), dv)) best = u;
+                            if (wi_eq<NL>(wi_add<NL>(wi_load<NL>(ds + (size_t)u * NL), dp_w_in<NL>(g, sp, biased, ebase + e, ew_decode<NL>(we))), dv)) best = u;
                         } else {
                             if (!in_y(u) || rnd[cpos[u]] >= rv) continue;
                             const WInt<NL> du = wi_load<NL>(cur + (size_t)cpos[u] * NL);
-                            if (!wi_is_inf<NL>(du) && wi_eq<NL>(wi_add<NL>(du, ew_decode<NL>(we)), dv)) best = u;
+                            if (!wi_is_inf<NL>(du) && wi_eq<NL>(wi_add<NL>(du, dp_w_in<NL>(g, sp, biased, ebase + e, ew_decode<NL>(we))), dv)) best = u;
                         }
                     }
                     return best;
@@ -311,13 +339,13 @@ __device__ int rp_walk(const int32_t *pidx, const int32_t *ps, const int32_t *ts
     return m;
 }
 
-template <int FILL>
-__global__ __launch_bounds__(NT) void k_rp_walk(DBatch b, DMarg g, DDrop q, DRepl r) {
+template <int FILL, class G = DMarg>
+__global__ __launch_bounds__(NT) void k_rp_walk(DBatch b, G g, DDrop q, DRepl r) {
     const DMeta *meta = &b.meta[blockIdx.x];
-    if (!dp_contig(b, g, meta)) return;
-    const int np = (meta->n_path - 1) / 2;
+    if (!dp_on<G>(b, g, meta)) return;
+    const int np = (dp_npath<G>(b, g, meta) - 1) / 2;
     const size_t no = (size_t)meta->node_off;
-    const int32_t *path = b.path + no;
+    const int32_t *path = dp_path<G>(b, g, meta);
     const int32_t *pidx = q.pidx + no, *ps = q.ps + no, *ts = q.ts + no, *last = q.last + no;
     const int64_t r0 = q.roff[blockIdx.x];
     for (int i = threadIdx.x; i < np; i += NT) {
