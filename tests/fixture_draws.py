@@ -20,7 +20,12 @@ class Fixture:
         self.case, self.params, self.trnas, self.error = case, golden_params(g), golden_trnas(g), str(g["error"])
 
     def graph(self, orc):
-        return cd.OracleGraph(orc, self.seq, orc.make_params(**self.params), self.trnas)
+        """The fixture's OracleGraph; where it has a path, with the nodes' positions as `pos` (drop_outcome names a pair's gene by them)."""
+        params = orc.make_params(**self.params)
+        g = cd.OracleGraph(orc, self.seq, params, self.trnas)
+        if g.ok:
+            g.pos = orc.run(self.seq, params, trnas=self.trnas)["node_pos"].tolist()
+        return g
 
 
 def enough(graph):
@@ -91,6 +96,34 @@ def directed(graph, genes, hits):
     return dict(forbid=[called[0]], require=[near[0]], bias={near[1]: -BONUS})
 
 
+def directed_removed(graph, first):
+    """The second directed draw of a tRNA fixture, from the oracle's graph and the first one: it puts a tRNA gene on the removed side of a
+    drop.  The first draw's refused gene stays refused; P' is the path of that mask.  If P' calls a tRNA gene t and uncalled reachable ORFs
+    lie over t's interval, the nearest of them (the first draw's required ORF) gets a bonus one unit short of its path margin under the
+    mask — P' stays the best path by one unit and keeps t, while the detour around a called gene next to t may take the ORF, which leaves
+    no room for t.  Nothing is required: only the mask and the evidence solve are run.  None where P' calls no tRNA gene or that ORF does
+    not lie over the first one it calls."""
+    from test_evidence_gpu import settle
+
+    k = first["require"][0]
+    mask = dict(forbid=first["forbid"], require=[], bias={})
+    edges, _ = cd.weights(graph.edges, graph.orf_edge, mask, 0)
+    dist, par = settle(graph.V, edges, graph.src)
+    if dist is None or dist[graph.tgt] is None:
+        return None
+    on_path = [g for g in pair_genes(graph, walk_back(graph, edges, par)) if abs(g[3]) == 4]
+    if not on_path or max(k[0], on_path[0][0]) > min(k[1], on_path[0][1]):
+        return None
+    M = cd.big_m(graph.edges, mask) << 2
+    through, pinned = cd.weights(graph.edges, graph.orf_edge, dict(mask, require=[k]), M)
+    dk = settle(graph.V, through, graph.src)[0]
+    if dk is None or dk[graph.tgt] is None:
+        return None
+    margin = dk[graph.tgt] + M - dist[graph.tgt]
+    assert len(pinned) == 1 and 1 < margin < M // 2  # (the path through k holds it once; it is uncalled under the mask)
+    return dict(forbid=list(first["forbid"]), require=[], bias={k: 1 - margin})
+
+
 def draws(orc, fx, graph):
     """The fixture's draws: the five seeded ones of curate_draws.mixes over this graph alone, then the directed one of a tRNA fixture."""
     out = [row[0] for row in cd.mixes([graph])]
@@ -100,6 +133,12 @@ def draws(orc, fx, graph):
         assert d is not None
         out.append(d)
     return out
+
+
+def removed_draw(orc, fx, graph):
+    """The second directed draw of a tRNA fixture (directed_removed), which only the drops and replacements of its mask and evidence
+    solves are run on; None where the fixture has none."""
+    return directed_removed(graph, draws(orc, fx, graph)[-1]) if fx.trnas else None
 
 
 def solve_args(d, kind):
@@ -128,3 +167,58 @@ def oracle_outcome(graph, d, kind, settle):
         v = u
     assert kept == (-dist[graph.tgt] + M // 2) // M
     return "ok", kept, trna
+
+
+def walk_back(graph, edges, par):
+    """The source -> target node list of a settled solve."""
+    path, v = [graph.tgt], graph.tgt
+    while v != graph.src:
+        v = edges[par[v]][0]
+        path.append(v)
+        assert len(path) <= graph.V
+    return path[::-1]
+
+
+def pair_genes(graph, path):
+    """The pairs (path[2i+1], path[2i+2]) of a path, in order, as (left, right, strand, frame, stop node); frame +-4: a tRNA pair, whose
+    last entry is None."""
+    out = []
+    for i in range((len(path) - 1) // 2):
+        a, b = path[2 * i + 1], path[2 * i + 2]
+        f = graph.frame[a]
+        stop = None if abs(f) > 3 else b if f > 0 else a
+        assert graph.frame[b] == f and (stop is None or graph.type[stop] == 1)
+        out.append((graph.pos[a], graph.pos[b] + 2, -1 if f < 0 else 1, f, stop))
+    return out
+
+
+def drop_outcome(graph, d, kind, settle):
+    """The drops of the mask or the evidence solve of a draw on the oracle's graph under `settle`: (moved, rows).  `moved`: the solve's path
+    P' is not the run's own.  One row per pair of P', in path order: ("trna", gene) for a tRNA pair, which gets no record, and
+    ("cds", gene, bypass, drop, removed, added) for a CDS gene — the graph without the gene's stop node is settled again; `bypass`: it
+    still has a source -> target path, `drop` D'_{-g} - D' in the solver's units (None without a bypass), `removed` the genes of P' that
+    path does not hold and `added` the ones it holds and P' does not, both in path order.  A gene is (left, right, strand, frame)."""
+    assert kind in ("mask", "evidence")
+    forbid, require, bias = solve_args(d, kind)
+    edges, pinned = cd.weights(graph.edges, graph.orf_edge, dict(forbid=forbid, require=require, bias=bias), 0)
+    assert not pinned
+    dist, par = settle(graph.V, edges, graph.src)
+    assert dist is not None and dist[graph.tgt] is not None  # (the host test counts both kinds as settling with a path on every draw)
+    path = walk_back(graph, edges, par)
+    own = settle(graph.V, graph.edges, graph.src)
+    assert own[0][graph.tgt] == graph.D
+    rows, mine = [], pair_genes(graph, path)
+    for g in mine:
+        if g[4] is None:
+            rows.append(("trna", g[:4]))
+            continue
+        left = [e for e in edges if g[4] not in e[:2]]
+        dist2, par2 = settle(graph.V, left, graph.src)
+        assert dist2 is not None  # (taking edges away makes no cycle negative)
+        if dist2[graph.tgt] is None:
+            rows.append(("cds", g[:4], False, None, [], []))
+            continue
+        other = [x[:4] for x in pair_genes(graph, walk_back(graph, left, par2))]
+        assert dist2[graph.tgt] >= dist[graph.tgt] and g[:4] not in other
+        rows.append(("cds", g[:4], True, dist2[graph.tgt] - dist[graph.tgt], [x[:4] for x in mine if x[:4] not in other], [x for x in other if x not in [y[:4] for y in mine]]))
+    return path != walk_back(graph, graph.edges, own[1]), rows

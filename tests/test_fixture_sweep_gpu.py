@@ -1,21 +1,24 @@
 """The newer re-annotation families on the golden fixtures, on the device: evidence(), curate(), scenarios(), pinned_scenarios(),
-evidence_scenarios(), remargins() / redist(), pinmargins() / pindist(), start_drops(), alt_starts() and evidence_scan() on graphs with tRNA
-nodes, IUPAC letters, bridged runs and under the fixtures' own codon sets, weights and minlen.  Each usable fixture (tests/fixture_draws.py)
-is one context and one run; its draws are the ones tests/test_fixture_sweep_host.py counts on the CPU oracle's graphs.  The yardsticks are
-the existing ones, over the device's own tapped edges: CuRef / check of tests/test_curate_gpu.py, pin_ref / check_pin of
-tests/test_pinmargins_gpu.py and EvRef / check_contig (py_dt_in_R) of tests/test_remargins_gpu.py.  Every comparison is integer-exact or byte
-for byte."""
+evidence_scenarios(), remargins() / redist(), pinmargins() / pindist(), redrops(), rereplacements() / rereplacement_path(), start_drops(),
+alt_starts() and evidence_scan() on graphs with tRNA nodes, IUPAC letters, bridged runs and under the fixtures' own codon sets, weights and
+minlen.  Each usable fixture (tests/fixture_draws.py) is one context and one run; its draws are the ones tests/test_fixture_sweep_host.py
+counts on the CPU oracle's graphs.  The yardsticks are the existing ones, over the device's own tapped edges: CuRef / check of
+tests/test_curate_gpu.py, pin_ref / check_pin of tests/test_pinmargins_gpu.py, EvRef / check_contig (py_dt_in_R) of
+tests/test_remargins_gpu.py, check_contig of tests/test_redrops_gpu.py and check_records of tests/test_rereplace_gpu.py — the last two on
+every record of every mask and evidence solve, without sampling.  Every comparison is integer-exact or byte for byte."""
 import numpy as np
 import pytest
 
 from test_constrain_gpu import gene_tuples, run_batch
 from test_curate_gpu import CuRef, DeviceGraph, check, contig_bytes, curate, evidence
-from test_evidence_gpu import EvRef, score
-from test_fixture_sweep_host import BATCHED, TRNA, USABLE
+from test_evidence_gpu import NEGCYCLE, EvRef, score
+from test_fixture_sweep_host import BATCHED, REMOVED, TRNA, USABLE
 from test_pinmargins_gpu import check_pin
 from test_remargins_gpu import check_contig
 
 import fixture_draws as fd
+import test_redrops_gpu as rd
+import test_rereplace_gpu as rr
 
 pytestmark = pytest.mark.gpu
 
@@ -99,7 +102,43 @@ class Lone:
         self.count = {k: dict(ok=0, cycle=0, nopath=0, kept=0) for k in fd.KINDS}
         self.with_trna = 0  # checked solves whose path holds a tRNA gene
         self.single = {}  # (kind, draw) -> (contig_bytes, margin_bytes)
+        self.drops = {}  # ("mask" | "evidence", draw) -> check_drops' counts
+        self.drop_bytes = {}  # ("mask" | "evidence", draw) -> drop_bytes
+        self.refused = 0  # pin and full solves after which redrops() and rereplacements() raised PHX_E_STATE
         self.draws = []
+
+
+def drop_bytes(ann, dr, rp, i):
+    """Contig i of redrops() and rereplacements(): the records' bytes of both and every record's witness path."""
+    return rd.out_bytes(dr, i), rr.contig_bytes(rp, i), [ann.rereplacement_path(i, k).tobytes() for k in range(int(rp[1][i + 1] - rp[1][i]))]
+
+
+def check_drops(ann, ev, F, bias, genes, j):
+    """redrops() and rereplacements() of the lone contig's resident mask or evidence solve — the drops first on an even draw, the
+    replacements first on an odd one, where they build the trees themselves.  Every field of every drop record against
+    test_redrops_gpu.check_contig (drop: the yardstick's solve with the gene's stop group refused on top, integer-exact), every
+    replacement record, its witness path and its genes against test_rereplace_gpu.check_records without sampling.  Returns the counts
+    the floors read and drop_bytes."""
+    calls = (ann.redrops, ann.rereplacements)
+    got = [call() for call in (calls if j % 2 == 0 else calls[::-1])]
+    dr, rp = got if j % 2 == 0 else got[::-1]
+    assert rp[0].tobytes() == dr[0].tobytes() and rp[1].tobytes() == dr[1].tobytes() and dr[1].tolist() == [0, len(dr[2])] and len(rp[2]) == len(dr[2])
+    res = rd.check_contig(ann, ev, F, bias, int(dr[0][0]), dr[2], genes)
+    c = dict(status=int(dr[0][0]), records=len(dr[2]), compared=0, bypass=0, exact=0, trna_pairs=0, removed=0, added=0, splice=0)
+    if res not in (NEGCYCLE, None):
+        c["compared"], path = res[1], res[2]
+        c["trna_pairs"] = sum(abs(int(ev.frame[path[2 * k + 1]])) > 3 for k in range((len(path) - 1) // 2))
+        c["exact"], c["bypass"] = rr.check_records(ann, ev, F, bias, dr[2], rp[2], rp[3])
+        assert c["trna_pairs"] + c["compared"] == (len(path) - 1) // 2  # every pair of P' is a record or a tRNA pair
+        for r in rp[2]:
+            g = rp[3][int(r["gene_off"]): int(r["gene_off"]) + int(r["n_removed"]) + int(r["n_added"])]["frame"]
+            nr, na = int((np.abs(g[:int(r["n_removed"])]) == 4).sum()), int((np.abs(g[int(r["n_removed"]):]) == 4).sum())
+            c["removed"] += nr > 0
+            c["added"] += na > 0
+            c["splice"] += nr + na > 0
+    else:
+        assert len(rp[2]) == len(rp[3]) == 0
+    return c, drop_bytes(ann, dr, rp, 0)
 
 
 DONE = {}
@@ -139,9 +178,9 @@ def run_fixture(pa, oracle, case):
             out.with_trna += outcome(sol) == "ok" and any(abs(int(f)) == 4 for f in genes["frame"])
             out.single[(kind, j)] = (contig_bytes(ann, res, 0), margin_bytes(margins, 0))
 
-        for j, d in enumerate(out.draws):
-            F, R, B = indexed(ref, d)
-            # refused only, then refused + biased: remargins() and redist() both ways
+        def masked(j, F, B, counted=True):
+            """Refused only, then refused + biased: remargins() and redist() both ways, then the drops and replacements of that solve, every
+            record; they disturb nothing resident."""
             for kind, call, bias in (("mask", lambda: ann.reannotate([F]), None), ("evidence", lambda: evidence(ann, [B], [F]), B)):
                 res = call()
                 st, offs, genes, delta = res
@@ -149,7 +188,16 @@ def run_fixture(pa, oracle, case):
                 mg = ann.remargins()
                 assert int(mg[0][0]) == int(st[0])
                 check_contig(ann, ev, F, bias, int(mg[0][0]), mg[2], genes, nodes=True)
-                note(kind, j, sol, res, mg)
+                if counted:
+                    note(kind, j, sol, res, mg)
+                first = [x.tobytes() for x in mg]
+                out.drops[(kind, j)], out.drop_bytes[(kind, j)] = check_drops(ann, ev, F, bias, genes, j)
+                assert out.drops[(kind, j)]["status"] == int(st[0])
+                assert [x.tobytes() for x in ann.remargins()] == first, (kind, j)
+
+        for j, d in enumerate(out.draws):
+            F, R, B = indexed(ref, d)
+            masked(j, F, B)
             # refused + required, then all three: pinmargins() and pindist() both ways
             for kind, call, bias in (("pin", lambda: ann.constrain([F], [R]), None), ("full", lambda: curate(ann, [B], [F], [R]), B)):
                 res = call()
@@ -159,10 +207,24 @@ def run_fixture(pa, oracle, case):
                 assert int(pm[0][0]) == int(st[0])
                 check_pin(ann, ref, F, R, bias, int(pm[0][0]), pm[2], pm[3], genes, nodes=True)
                 note(kind, j, sol, res, pm)
+                if R:  # under required ORFs the drops are another definition: PHX_E_STATE, and nothing resident moves
+                    first = [x.tobytes() for x in pm]
+                    for refuses in (ann.redrops, ann.rereplacements):
+                        with pytest.raises(pa.PhxError) as e:
+                            refuses()
+                        assert e.value.code == -13 and "required" in str(e.value), (kind, j)
+                    assert [x.tobytes() for x in ann.pinmargins()] == first, (kind, j)
+                    out.refused += 1
+        extra = fd.removed_draw(oracle, fx, og)  # the second directed draw: a tRNA gene on the removed side of a drop
+        assert (extra is not None) == (case in REMOVED)
+        if extra is not None:
+            F, R, B = indexed(ref, extra)
+            masked(len(out.draws), F, B, counted=False)
         check_scenario_batches(ann, ref, out, D, run_bytes)
         check_derived_batches(ann, ref, out, called, D)
     finally:
         ann.close()
+        rd._solved.clear()  # (the yardstick's solves of this fixture, shared by check_contig and check_records)
     return out
 
 
@@ -228,11 +290,16 @@ def test_every_family_on_a_fixture_against_the_yardstick(pa, oracle, case):
     n = len(out.draws)
     assert n == 5 + (case in TRNA) and all(sum(c[w] for w in ("ok", "cycle", "nopath")) == n for c in out.count.values())  # no draw is left out
     print("%s: %s, %d solves with a tRNA gene on the path" % (case, {k: (c["ok"], c["cycle"], c["kept"]) for k, c in out.count.items()}, out.with_trna))
+    assert sorted(out.drops) == sorted((kind, j) for kind in ("mask", "evidence") for j in range(n + (case in REMOVED))) and out.refused == 2 * n
+    drops = {k: sum(c[k] for c in out.drops.values()) for k in ("records", "compared", "bypass", "exact", "trna_pairs", "removed", "added", "splice")}
+    print("%s: drops and replacements %s" % (case, drops))
+    assert drops["records"] == drops["compared"] and drops["bypass"] == drops["exact"]  # no record, and no witness' length, went unchecked
 
 
 # ---- 2. one batch, each contig with its own hit list ----
 def test_one_batch_with_trna_hits_equals_the_lone_fixtures(pa, oracle):
-    """The fixtures of the default parameter set side by side: tRNA nodes at a non-zero node and edge offset under BatchView and SlotView."""
+    """The fixtures of the default parameter set side by side: tRNA nodes at a non-zero node and edge offset under BatchView, SlotView and
+    MgDrop, whose refused and biased bits of small neighbours (edge_L200 has 14 edges) share 32-bit words."""
     lone = {case: sweep(pa, oracle, case) for case in BATCHED}
     fxs = [fd.Fixture(case) for case in BATCHED]
     assert all(fx.params == fxs[0].params for fx in fxs) and [fx.case for fx in fxs if fx.trnas] == TRNA
@@ -253,6 +320,17 @@ def test_one_batch_with_trna_hits_equals_the_lone_fixtures(pa, oracle):
     mg = ann.remargins()
     for i, fx in enumerate(fxs):
         assert (contig_bytes(ann, res, i), margin_bytes(mg, i)) == lone[fx.case].single[("evidence", 1)], fx.case
+    # ... and its drops and replacements under MgDrop: the bitmap words of neighbouring small contigs are shared; then draw 2's masks
+    dr, rp = ann.redrops(), ann.rereplacements()
+    for i, fx in enumerate(fxs):
+        assert drop_bytes(ann, dr, rp, i) == lone[fx.case].drop_bytes[("evidence", 1)], fx.case
+    assert [x.tobytes() for x in ann.remargins()] == [x.tobytes() for x in mg]
+    res = ann.reannotate(col(2, 0))
+    rp, dr = ann.rereplacements(), ann.redrops()
+    for i, fx in enumerate(fxs):
+        assert contig_bytes(ann, res, i) == lone[fx.case].single[("mask", 2)][0], fx.case
+        assert drop_bytes(ann, dr, rp, i) == lone[fx.case].drop_bytes[("mask", 2)], fx.case
+    assert sum(len(lone[fx.case].drop_bytes[("mask", 2)][2]) for fx in fxs) == len(dr[2]) >= n
     # one pinned and one evidence scenario call across all contigs, every draw of every fixture
     slots = [(i, j) for i in range(n) for j in range(len(idx[i]))]
     res = ann.pinned_scenarios([(i, idx[i][j][0], idx[i][j][1]) for i, j in slots])
@@ -290,6 +368,9 @@ def test_every_family_with_nothing_to_do_on_a_degenerate_fixture(pa, case):
         plain(call())
         no_records(ann.remargins())
         no_records(ann.pinmargins())
+        for out in (ann.redrops(), ann.rereplacements()):  # (none of these calls requires an ORF)
+            no_records(out)
+            assert out[1].tolist() == [0, 0]
         V = max(int(ann.globals(0).n_node), 0)
         for to_target in (False, True):
             assert len(ann.redist(0, to_target=to_target)) == len(ann.pindist(0, to_target=to_target)) == V
@@ -305,7 +386,9 @@ def test_every_family_with_nothing_to_do_on_a_degenerate_fixture(pa, case):
 def test_the_sweep_meets_its_floors(pa, oracle):
     """Conditions, not measurements: tests/test_fixture_sweep_host.py proves on the CPU that the yardstick alone meets them (170 draws of
     each kind; mask and evidence all settle; pin and full 153 settle and 17 meet a negative cycle; 202 required ORFs kept; at least 2 full
-    draws settle on every fixture).  The directed draws of the tRNA fixtures come on top."""
+    draws settle on every fixture).  The directed draws of the tRNA fixtures come on top.  The floors of redrops() and rereplacements()
+    sit a little below the host's counts, as 150 sits below 153: a tie the device breaks otherwise cannot fail them, and they hide nothing —
+    every record returned is compared in full whatever their number."""
     done = {case: sweep(pa, oracle, case) for case in USABLE}
     assert sorted(done) == sorted(USABLE) and len(done) == 34
     tot = {k: {w: sum(d.count[k][w] for d in done.values()) for w in ("ok", "cycle", "nopath", "kept")} for k in fd.KINDS}
@@ -315,3 +398,22 @@ def test_the_sweep_meets_its_floors(pa, oracle):
     for kind in ("mask", "evidence"):  # every draw is checked with status 0
         assert tot[kind]["ok"] == 170 + len(TRNA) and tot[kind]["cycle"] == tot[kind]["nopath"] == 0
     assert all(done[c].with_trna >= 1 for c in TRNA)
+    # redrops() and rereplacements().  The host test's counts, over the seeded and the first directed draws: 1080 mask and 1074 evidence
+    # records (seeded), at least 10 per fixture, 86 tRNA pairs on a P' without a record (trna_gap 48, trna_gap_left 36), 46 records whose
+    # genes hold a tRNA gene (trna_phiX174 22, trna_synth6k 24), all on the added side; the second directed draw has one on the removed side.
+    upto = lambda d, kinds, last, key: sum(c[key] for (kind, j), c in d.drops.items() if kind in kinds and j <= last)
+    both = ("mask", "evidence")
+    dtot = {kind: sum(upto(d, (kind,), 4, "compared") for d in done.values()) for kind in both}
+    pairs = {c: upto(done[c], both, 5, "trna_pairs") for c in TRNA}
+    splice = {c: upto(done[c], both, 5, "splice") for c in TRNA}
+    removed = {c: upto(done[c], both, 6, "removed") for c in TRNA}
+    print("drops and replacements on the device: records compared %s, tRNA pairs without a record %s, records with a tRNA gene %s, on the removed side %s"
+          % (dtot, pairs, splice, removed))
+    assert dtot["mask"] >= 1000 and dtot["evidence"] >= 1000
+    assert all(upto(d, both, 4, "compared") >= 10 for d in done.values())
+    assert all(c["status"] == 0 for d in done.values() for c in d.drops.values())
+    assert sum(pairs.values()) >= 80 and pairs["trna_gap"] >= 40 and pairs["trna_gap_left"] >= 30
+    assert sum(splice.values()) >= 40 and splice["trna_phiX174"] >= 20 and splice["trna_synth6k"] >= 20
+    assert all(removed[c] >= 1 for c in REMOVED)
+    assert all(c["records"] == c["compared"] and c["bypass"] == c["exact"] for d in done.values() for c in d.drops.values())  # no record went unchecked
+    assert all(len(d.drops) == 2 * (len(d.draws) + (c in REMOVED)) and d.refused == 2 * len(d.draws) for c, d in done.items())

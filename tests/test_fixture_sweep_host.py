@@ -14,6 +14,8 @@ USABLE = ["edge_L1000", "edge_L200", "edge_L4001", "edge_L4002", "edge_bridge", 
           "param_stop_rc_stop", "param_weights_3_1", "param_zero_weight", "phiX174", "synth6k_100", "synth6k_101", "synth6k_102", "synth6k_103",
           "trna_gap", "trna_gap_left", "trna_phiX174", "trna_synth6k"]
 TRNA = ["trna_gap", "trna_gap_left", "trna_phiX174", "trna_synth6k"]
+REMOVED = ["trna_phiX174"]  # the tRNA fixtures with a second directed draw (fixture_draws.directed_removed)
+SECOND_DROPS = ((2, 2, 14, 14, 2, 3), (1, 1, 2, 2))  # its drops: (solves, P' != P, records, bypass, tRNA pairs, tRNA splices), (records / tRNA genes removed, ... added)
 BATCHED = USABLE[:9] + USABLE[25:]  # the default parameter set: one batch, each contig with its own hit list
 
 
@@ -89,3 +91,78 @@ def test_how_the_draws_end_on_the_oracles_graphs(oracle, sweep):
     n4 = {"trna_gap": (4, 4), "trna_gap_left": (3, 3), "trna_phiX174": (1, 0), "trna_synth6k": (0, 0)}  # tRNA genes called: (mask / evidence, pin / full)
     for case, rows in directed.items():
         assert rows == [("mask", "ok", 0, n4[case][0]), ("evidence", "ok", 0, n4[case][0]), ("pin", "ok", 1, n4[case][1]), ("full", "ok", 1, n4[case][1])], (case, rows)
+
+
+def drop_counts(rows):
+    """Of one solve's fd.drop_outcome rows: records, with bypass, with a drop of 0, tRNA pairs without a record, records whose removed /
+    added / removed + added genes hold a tRNA gene, the tRNA genes on either side, records with more than one removed gene."""
+    c = dict(records=0, bypass=0, zero=0, trna_pairs=0, trna_removed=0, trna_added=0, trna_splice=0, removed_genes=0, added_genes=0, multi=0)
+    for r in rows:
+        if r[0] == "trna":
+            c["trna_pairs"] += 1
+            continue
+        nr, na = sum(abs(x[3]) == 4 for x in r[4]), sum(abs(x[3]) == 4 for x in r[5])
+        assert r[0] == "cds" and abs(r[1][3]) <= 3 and (not r[2] or r[1] in r[4])  # the dropped gene is among the removed ones
+        for key, x in (("records", 1), ("bypass", r[2]), ("zero", r[3] == 0), ("trna_removed", nr > 0), ("trna_added", na > 0), ("trna_splice", nr + na > 0),
+                       ("removed_genes", nr), ("added_genes", na), ("multi", len(r[4]) > 1)):
+            c[key] += int(x)
+    return c
+
+
+def test_how_the_drops_end_on_the_oracles_graphs(oracle, sweep):
+    """redrops() and rereplacements() on the CPU: after the mask and the evidence solve of every draw, each CDS gene of P' is dropped by
+    taking its stop node out of the oracle's graph (fixture_draws.drop_outcome, under test_evidence_gpu.settle).  Measured, and asserted
+    to the unit:
+
+                               solves  P' != P  records  with bypass  tRNA pairs on P'  records with a tRNA gene among removed + added
+        mask, seeded              170       78     1080         1080                35                                             20
+        evidence, seeded          170       86     1074         1074                35                                             20
+        directed (both kinds)       8        8       64           64                16                                              6
+        second directed (both)      2        2       14           14                 2                                              3
+
+    No drop is 0.  Per tRNA fixture, its seeded and first directed draws (records / tRNA pairs without a record / records with a tRNA gene
+    in the splice): trna_gap 84 / 48 / 0, trna_gap_left 92 / 36 / 0, trna_phiX174 84 / 2 / 22, trna_synth6k 114 / 0 / 24.  Every one of
+    those 46 splices has its tRNA gene on the added side (46 tRNA genes, one per record) and none on the removed side: on the two gap
+    fixtures no ORF lies over a hit, and where a seeded draw brings a tRNA gene in, it comes by the detour.  Records with more than one
+    removed gene: 286 (mask), 278 (evidence), 22 (directed).  The second directed draw of trna_phiX174 (fixture_draws.directed_removed)
+    reaches the removed side: (100, 627, +) refused, a bonus of 39159 units — its margin under that mask less one — on (9, 101, -), so
+    that P' keeps the tRNA gene 30..104; without the next gene (283, 627, +) the best path calls (9, 101, -) and the tRNA gene goes:
+    one record of the evidence solve with a tRNA gene on the removed side.  (The mask solve of that draw is the first directed draw's;
+    in both solves the last record's detour brings the tRNA gene 5290..5370 in: two records with one on the added side.)  No other tRNA
+    fixture has such a draw: on the gap fixtures no ORF lies over a called tRNA gene, and trna_synth6k's mask calls none."""
+    kinds = ("mask", "evidence")
+    zero = drop_counts([])
+    tot = {k: dict(zero, solves=0, moved=0) for k in kinds + ("directed", "second")}
+    per = {c: dict(zero) for c in TRNA}
+    fewest = {}
+    for fx, g in sweep:
+        ds, extra = fd.draws(oracle, fx, g), fd.removed_draw(oracle, fx, g)
+        assert (extra is not None) == (fx.case in REMOVED)
+        for j, d in enumerate(ds + [extra] * (extra is not None)):
+            for kind in kinds:
+                moved, rows = fd.drop_outcome(g, d, kind, settle)
+                c = drop_counts(rows)
+                t = tot[kind if j < cd.ROUNDS else "directed" if j == cd.ROUNDS else "second"]
+                t["solves"] += 1
+                t["moved"] += moved
+                for key, x in c.items():
+                    t[key] += x
+                    if fx.case in per and j <= cd.ROUNDS:
+                        per[fx.case][key] += x
+                if j < cd.ROUNDS:
+                    fewest[fx.case] = fewest.get(fx.case, 0) + c["records"]
+    print("drops on the oracle's graphs:", tot)
+    print("per tRNA fixture:", per)
+    row = lambda t: (t["solves"], t["moved"], t["records"], t["bypass"], t["trna_pairs"], t["trna_splice"])
+    assert row(tot["mask"]) == (170, 78, 1080, 1080, 35, 20)
+    assert row(tot["evidence"]) == (170, 86, 1074, 1074, 35, 20)
+    assert row(tot["directed"]) == (8, 8, 64, 64, 16, 6)
+    assert all(t["zero"] == 0 for t in tot.values())
+    assert {c: (p["records"], p["trna_pairs"], p["trna_splice"]) for c, p in per.items()} == dict(trna_gap=(84, 48, 0), trna_gap_left=(92, 36, 0), trna_phiX174=(84, 2, 22), trna_synth6k=(114, 0, 24))
+    assert min(fewest.values()) == 10 and max(fewest.values()) == 120 and fewest["param_stop_rc_stop"] == 10 and fewest["synth6k_102"] == 120
+    # measured when this test was written: the side of the tRNA genes, and the records that remove more than their own gene
+    side = lambda t: (t["trna_removed"], t["removed_genes"], t["trna_added"], t["added_genes"])
+    assert side(tot["mask"]) == (0, 0, 20, 20) and side(tot["evidence"]) == (0, 0, 20, 20) and side(tot["directed"]) == (0, 0, 6, 6)
+    assert (tot["mask"]["multi"], tot["evidence"]["multi"], tot["directed"]["multi"]) == (286, 278, 22)
+    assert all(p["trna_removed"] == 0 for p in per.values())  # ... hence the second directed draw
+    assert row(tot["second"]) == SECOND_DROPS[0] and side(tot["second"]) == SECOND_DROPS[1], tot["second"]
