@@ -11,6 +11,17 @@ static int analysis_events(phx_ctx *c) { // phx_ctx::aev, created at the first a
     return PHX_OK;
 }
 static float ev_ms(hipEvent_t a, hipEvent_t b) { float ms = 0; return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.0f; }
+// the *_ms and *_stats getters: N values of the context's, those at src(c)
+extern "C++" template <int N, class T, class F> static int values_out(const phx_ctx *c, T *out, F src) {
+    if (!c || !out) return PHX_E_ARG;
+    for (int k = 0; k < N; k++) out[k] = src(c)[k];
+    return PHX_OK;
+}
+// a contig of the last re-annotation call that was not solved again: the run's result stands for it
+static bool any_unsolved(const phx_ctx *c) {
+    for (size_t i = 0; i < (size_t)c->n; i++) if (!c->h_qsel[i]) return true;
+    return false;
+}
 
 // the run's group records on the host, once per run
 static int ensure_grp_host(phx_ctx *c) {
@@ -147,107 +158,136 @@ int phx_tap_dist_target(phx_ctx *c, int32_t contig, uint64_t *dist_limbs, int64_
     return PHX_OK;
 }
 
-int phx_margins_ms(phx_ctx *c, float *ms) {
-    if (!c || !ms) return PHX_E_ARG;
-    for (int k = 0; k < 4; k++) ms[k] = c->margins_ms[k];
-    return PHX_OK;
-}
+int phx_margins_ms(phx_ctx *c, float *ms) { return values_out<4>(c, ms, [](const phx_ctx *x) { return x->margins_ms; }); }
 
-// ---- gene drop margins (phx_drop.inc, DESIGN.md §12) ----
+// ---- gene drop margins (phx_drop.inc, DESIGN.md §12; on a re-annotation's graph §29) ----
 // the contigs the drop kernels cover (dp_contig) and their sparse-table size (k_dp_cand)
 static bool drop_contig(const phx_ctx *c, size_t i) {
     const DMeta &m = c->meta[i];
     return m.status >= 0 && m.n_node > 2 && m.sssp_mode != 4 && !c->mstat[i] && m.n_path >= 3;
 }
 static int64_t drop_cells(int n_path) { int lv = 1; while ((2 << (lv - 1)) <= n_path) lv++; return (int64_t)n_path * lv; }
+static int drop_layered() { const char *ly = getenv("PHX_DROP_LAYERED"); return ly && *ly && strcmp(ly, "0") != 0 ? 1 : 0; }
 
-static void drop_args(phx_ctx *c, DDrop *q) {
-    const size_t n = (size_t)c->n;
-    q->pidx = (int32_t *)c->b_dpi.p; q->js = (int32_t *)c->b_djs.p; q->jt = (int32_t *)c->b_djt.p; q->first = (int32_t *)c->b_dfi.p; q->last = (int32_t *)c->b_dla.p;
-    q->slot = (uint64_t *)c->b_dslot.p; q->gtab = (uint64_t *)c->b_dgtab.p;
-    q->toff = (const int64_t *)c->b_doff.p; q->roff = (const int64_t *)c->b_doff.p + n;
-    q->sx = (uint64_t *)c->b_dsx.p; q->cx = (uint64_t *)c->b_dcx.p; q->da = (uint64_t *)c->b_dda.p; q->db = (uint64_t *)c->b_ddb.p;
-    q->rec = (phx_gene_drop *)c->b_drec.p; q->stats = (unsigned long long *)c->b_dstats.p;
-    const char *ly = getenv("PHX_DROP_LAYERED");
-    q->layered = ly && *ly && strcmp(ly, "0") != 0 ? 1 : 0;
-    q->ps = c->done.trees ? (int32_t *)c->b_dps.p : nullptr; q->ts = c->done.trees ? (int32_t *)c->b_dts.p : nullptr;
+// the kernels' view of a set (after drop_pass laid it out: roff has n + 1 entries); trees: with the one-hop trees
+static void drop_args(const phx_ctx::DropSet &D, bool trees, DDrop *q) {
+    const int64_t *off = (const int64_t *)D.b_off.p;
+    q->pidx = (int32_t *)D.b_pi.p; q->js = (int32_t *)D.b_js.p; q->jt = (int32_t *)D.b_jt.p; q->first = (int32_t *)D.b_fi.p; q->last = (int32_t *)D.b_la.p;
+    q->slot = (uint64_t *)D.b_slot.p; q->gtab = (uint64_t *)D.b_gtab.p;
+    q->toff = off; q->roff = off ? off + (D.roff.size() - 1) : nullptr; // (no buffers: no contig is covered, and no kernel reads the set)
+    q->sx = (uint64_t *)D.b_sx.p; q->cx = (uint64_t *)D.b_cx.p; q->da = (uint64_t *)D.b_da.p; q->db = (uint64_t *)D.b_db.p;
+    q->rec = (phx_gene_drop *)D.b_rec.p; q->stats = (unsigned long long *)D.b_stats.p;
+    q->layered = drop_layered();
+    q->ps = trees ? (int32_t *)D.b_ps.p : nullptr; q->ts = trees ? (int32_t *)D.b_ts.p : nullptr;
 }
 
-// The records of every pair of every device path into c->h_drec (at c->droff), once per run, on top of ensure_rev.  trees: the one-hop
-// trees too (DDrop.ps / ts, for the replacements); drops computed without them get k_dp_tree once more, which rewrites the same labels.
-static int ensure_drops(phx_ctx *c, bool trees = false) {
-    if (c->done.drops && (!trees || c->done.trees)) return PHX_OK;
-    if (c->done.drops) {
-        const size_t nv = ((size_t)c->tot_node + (size_t)c->n + 1) * 4;
-        int rc;
-        if ((rc = ensure(c, c->b_dps, nv)) || (rc = ensure(c, c->b_dts, nv)) || (rc = ensure(c, c->rp.b_cnt, 2 * RP_NCNT * 8))) return rc;
-        c->done.trees = true;
-        DBatch b;
-        fill_batch(c, &b);
-        DMarg g;
-        margins_args(c, &g);
-        DDrop q;
-        drop_args(c, &q);
-        q.stats = (unsigned long long *)c->rp.b_cnt.p + RP_NCNT; // (the drops' own counters stay as they were)
-        phxk_drop_trees(&b, &g, &q, margins_nl_mask(c), c->stream);
-        HIPCHK(c, hipGetLastError());
+// The drop pass, once for both entry points (§12 on the run's graph, §29 on a re-annotation's): layout -> trees + labels -> candidates ->
+// fix-ups -> copies.  D: the set the pass writes and what it leaves on the host — the records of every pair of every covered path in D.h_rec
+// (at D.roff); covered(i): contig i's n_path, 0 when the kernels do not cover it; launch(step, q): step 0 k_dp_tree, 1 k_dp_cand, 2 the
+// fix-ups, under the caller's policy; done / has_trees: the caller's flags in RunDone.  trees: the one-hop trees too (DDrop.ps / ts, for the
+// replacements); a set computed without them gets k_dp_tree once more, which rewrites the same labels and counts into the second half of
+// S.b_cnt (S: the replacement set that goes with D), so that the pass's own counters stay as they were.
+extern "C++" template <class C, class L> static int drop_pass(phx_ctx *c, phx_ctx::DropSet &D, phx_ctx::ReplSet &S, bool &done, bool &has_trees, bool trees, const C &covered, const L &launch) {
+    const size_t n = (size_t)c->n, V = (size_t)c->tot_node, nv = (V + n + 1) * 4;
+    int rc;
+    DDrop q;
+    if (done) { // (asked for the trees alone)
+        if (D.nlm) {
+            if ((rc = ensure(c, D.b_ps, nv)) || (rc = ensure(c, D.b_ts, nv)) || (rc = ensure(c, S.b_cnt, 2 * RP_NCNT * 8))) return rc;
+            drop_args(D, true, &q);
+            q.stats = (unsigned long long *)S.b_cnt.p + RP_NCNT;
+            launch(0, q);
+            HIPCHK(c, hipGetLastError());
+        }
+        has_trees = true;
         return PHX_OK;
     }
-    if (trees) c->done.trees = true;
-    { const int rr = ensure_rev(c); if (rr) return rr; }
-    const size_t n = (size_t)c->n, V = (size_t)c->tot_node;
     const size_t limbs = (size_t)std::max(c->n_limbs, 2);
-    const int nlm = margins_nl_mask(c);
     std::vector<int64_t> off(2 * n + 2, 0); // toff[n], roff[n + 1]
-    c->droff.assign(n + 1, 0);
+    D.roff.assign(n + 1, 0);
+    D.nlm = 0;
     int64_t tcells = 0, R = 0;
     for (size_t i = 0; i < n; i++) {
-        off[n + i] = R; c->droff[i] = R;
-        if (!drop_contig(c, i)) continue;
-        const int np = c->meta[i].n_path;
+        off[n + i] = R; D.roff[i] = R;
+        const int np = covered(i);
+        if (!np) continue;
+        D.nlm |= nl_class_bit(c->meta[i].sssp_nl);
         const int64_t cells = drop_cells(np);
         if (cells > DP_TAB_LDS) { off[i] = tcells; tcells += cells; }
         R += (np - 1) / 2;
     }
-    off[2 * n] = R; c->droff[n] = R;
-    int rc;
-    const size_t nv = (V + n + 1) * 4;
-    if ((rc = ensure(c, c->b_dpi, nv)) || (rc = ensure(c, c->b_djs, nv)) || (rc = ensure(c, c->b_djt, nv)) || (rc = ensure(c, c->b_dfi, nv)) || (rc = ensure(c, c->b_dla, nv))) return rc;
-    if ((rc = ensure(c, c->b_dslot, (V + 1) * 8))) return rc;
-    if ((rc = ensure(c, c->b_dgtab, ((size_t)tcells + 1) * 8))) return rc;
-    if ((rc = ensure(c, c->b_doff, (2 * n + 2) * 8))) return rc;
-    if ((rc = ensure(c, c->b_dsx, ((size_t)R + 1) * limbs * 8)) || (rc = ensure(c, c->b_dcx, ((size_t)R + 1) * limbs * 8))) return rc;
-    if ((rc = ensure(c, c->b_dda, (V + 1) * limbs * 8)) || (rc = ensure(c, c->b_ddb, (V + 1) * limbs * 8))) return rc;
-    if ((rc = ensure(c, c->b_drec, ((size_t)R + 1) * sizeof(phx_gene_drop)))) return rc;
-    if ((rc = ensure(c, c->b_dstats, 4 * 8))) return rc;
-    if (c->done.trees && ((rc = ensure(c, c->b_dps, nv)) || (rc = ensure(c, c->b_dts, nv)))) return rc;
-    if ((rc = ensure_pinned(c, c->h_drec, ((size_t)R + 1) * sizeof(phx_gene_drop), ((size_t)R + (size_t)R / 4 + 1024) * sizeof(phx_gene_drop)))) return rc;
-    if ((rc = analysis_events(c))) return rc;
+    off[2 * n] = R; D.roff[n] = R;
+    for (int k = 0; k < 4; k++) { D.ms[k] = 0; D.stats[k] = 0; }
+    if (D.nlm) {
+        if ((rc = ensure(c, D.b_pi, nv)) || (rc = ensure(c, D.b_js, nv)) || (rc = ensure(c, D.b_jt, nv)) || (rc = ensure(c, D.b_fi, nv)) || (rc = ensure(c, D.b_la, nv))) return rc;
+        if ((rc = ensure(c, D.b_slot, (V + 1) * 8))) return rc;
+        if ((rc = ensure(c, D.b_gtab, ((size_t)tcells + 1) * 8))) return rc;
+        if ((rc = ensure(c, D.b_off, (2 * n + 2) * 8))) return rc;
+        if ((rc = ensure(c, D.b_sx, ((size_t)R + 1) * limbs * 8)) || (rc = ensure(c, D.b_cx, ((size_t)R + 1) * limbs * 8))) return rc;
+        if ((rc = ensure(c, D.b_da, (V + 1) * limbs * 8)) || (rc = ensure(c, D.b_db, (V + 1) * limbs * 8))) return rc;
+        if ((rc = ensure(c, D.b_rec, ((size_t)R + 1) * sizeof(phx_gene_drop)))) return rc;
+        if ((rc = ensure(c, D.b_stats, 4 * 8))) return rc;
+        if (trees && ((rc = ensure(c, D.b_ps, nv)) || (rc = ensure(c, D.b_ts, nv)))) return rc;
+        if ((rc = ensure_pinned(c, D.h_rec, ((size_t)R + 1) * sizeof(phx_gene_drop), ((size_t)R + (size_t)R / 4 + 1024) * sizeof(phx_gene_drop)))) return rc;
+        if ((rc = analysis_events(c))) return rc;
+        drop_args(D, trees, &q);
+        hipStream_t s = c->stream;
+        unsigned long long st[4] = {0, 0, 0, 0};
+        HIPCHK(c, hipEventRecord(c->aev[0], s));
+        HIPCHK(c, hipMemcpyAsync(D.b_off.p, off.data(), (2 * n + 2) * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemsetAsync(D.b_stats.p, 0, 4 * 8, s));
+        launch(0, q);
+        HIPCHK(c, hipEventRecord(c->aev[1], s));
+        launch(1, q);
+        HIPCHK(c, hipEventRecord(c->aev[2], s));
+        launch(2, q);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(c->aev[3], s));
+        if (R) HIPCHK(c, hipMemcpyAsync(D.h_rec.p, D.b_rec.p, (size_t)R * sizeof(phx_gene_drop), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipEventRecord(c->aev[4], s));
+        HIPCHK(c, hipMemcpyAsync(st, D.b_stats.p, sizeof st, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        for (int k = 0; k < 4; k++) { D.ms[k] = ev_ms(c->aev[k], c->aev[k + 1]); D.stats[k] = (int64_t)st[k]; }
+    } // (else no contig is covered: nothing is allocated or launched)
+    done = true;
+    has_trees = trees;
+    return PHX_OK;
+}
+
+// The run's set, once per run, on top of ensure_rev.
+static int ensure_drops(phx_ctx *c, bool trees = false) {
+    if (c->done.drops && (!trees || c->done.trees)) return PHX_OK;
+    { const int rr = ensure_rev(c); if (rr) return rr; }
+    const int nlm = margins_nl_mask(c);
     DBatch b;
     fill_batch(c, &b);
     DMarg g;
     margins_args(c, &g);
-    DDrop q;
-    drop_args(c, &q);
     hipStream_t s = c->stream;
-    unsigned long long st[4] = {0, 0, 0, 0};
-    HIPCHK(c, hipEventRecord(c->aev[0], s));
-    HIPCHK(c, hipMemcpyAsync(c->b_doff.p, off.data(), (2 * n + 2) * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemsetAsync(c->b_dstats.p, 0, 4 * 8, s));
-    phxk_drop_trees(&b, &g, &q, nlm, s);
-    HIPCHK(c, hipEventRecord(c->aev[1], s));
-    phxk_drop_cand(&b, &g, &q, nlm, s);
-    HIPCHK(c, hipEventRecord(c->aev[2], s));
-    phxk_drop_fix(&b, &g, &q, nlm, s);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->aev[3], s));
-    if (R) HIPCHK(c, hipMemcpyAsync(c->h_drec.p, c->b_drec.p, (size_t)R * sizeof(phx_gene_drop), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipEventRecord(c->aev[4], s));
-    HIPCHK(c, hipMemcpyAsync(st, c->b_dstats.p, sizeof st, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    for (int k = 0; k < 4; k++) { c->drop_ms[k] = ev_ms(c->aev[k], c->aev[k + 1]); c->drop_stats[k] = (int64_t)st[k]; }
-    c->done.drops = true;
-    return PHX_OK;
+    return drop_pass(c, c->dp, c->rp, c->done.drops, c->done.trees, trees, [&](size_t i) { return drop_contig(c, i) ? c->meta[i].n_path : 0; }, [&](int step, const DDrop &q) {
+        if (step == 0) phxk_drop_trees(&b, &g, &q, nlm, s);
+        else if (step == 1) phxk_drop_cand(&b, &g, &q, nlm, s);
+        else phxk_drop_fix(&b, &g, &q, nlm, s);
+    });
+}
+
+// What both flat calls lay out of a contig's device records [k0, k1) of D: those of CDS genes (the pairs of the path that are), in path
+// order, `called` from the sorted keys of the genes the contig's result delivers.
+static int64_t drop_count(const phx_ctx::DropSet &D, int64_t k0, int64_t k1) {
+    const phx_gene_drop *src = (const phx_gene_drop *)D.h_rec.p;
+    int64_t k = 0;
+    for (int64_t r = k0; r < k1; r++) k += src[r].called >= 0;
+    return k;
+}
+static void drop_rows(const phx_ctx::DropSet &D, int64_t k0, int64_t k1, const std::vector<uint64_t> &keys, phx_gene_drop *dst) {
+    const phx_gene_drop *src = (const phx_gene_drop *)D.h_rec.p;
+    for (int64_t k = k0; k < k1; k++) {
+        const phx_gene_drop &x = src[k];
+        if (x.called < 0) continue;
+        *dst = x;
+        dst->called = is_called(keys, x.left, x.right, x.strand) ? 1 : 0;
+        dst++;
+    }
 }
 
 int phx_drop_margins_flat(phx_ctx *c, phx_gene_drop *rec, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
@@ -255,19 +295,13 @@ int phx_drop_margins_flat(phx_ctx *c, phx_gene_drop *rec, int64_t cap, int64_t *
     { const int ra = after_run(c); if (ra) return ra; }
     { const int rx = ensure_exact(c); if (rx) return rx; } // `called` is against the genes phx_download* deliver
     { const int rd = ensure_drops(c); if (rd) return rd; }
-    const phx_gene_drop *drec = (const phx_gene_drop *)c->h_drec.p;
+    const phx_ctx::DropSet &D = c->dp;
     try {
-    // the gene pairs of every contig with records (status 0): the pairs of the device path that are CDS genes
-    auto genes_of = [&](int i) -> int64_t {
-        int64_t k = 0;
-        for (int64_t r = c->droff[(size_t)i]; r < c->droff[(size_t)i + 1]; r++) k += drec[r].called >= 0;
-        return k;
-    };
     int64_t total = 0;
-    for (int i = 0; i < c->n; i++) {
+    for (int i = 0; i < c->n; i++) { // records for every contig with status 0
         offsets[i] = total;
         status[i] = margins_status(c, i);
-        if (status[i] == 0 && drop_contig(c, (size_t)i)) total += genes_of(i);
+        if (status[i] == 0 && drop_contig(c, (size_t)i)) total += drop_count(D, D.roff[(size_t)i], D.roff[(size_t)i + 1]);
     }
     offsets[c->n] = total;
     if (total_out) *total_out = total;
@@ -278,30 +312,15 @@ int phx_drop_margins_flat(phx_ctx *c, phx_gene_drop *rec, int64_t cap, int64_t *
     for (int i = 0; i < c->n; i++) {
         if (offsets[i + 1] == offsets[i]) continue;
         called_keys(c, i, keys);
-        phx_gene_drop *dst = rec + offsets[i];
-        for (int64_t k = c->droff[(size_t)i]; k < c->droff[(size_t)i + 1]; k++) {
-            const phx_gene_drop &x = drec[k];
-            if (x.called < 0) continue;
-            *dst = x;
-            dst->called = is_called(keys, x.left, x.right, x.strand) ? 1 : 0;
-            dst++;
-        }
+        drop_rows(D, D.roff[(size_t)i], D.roff[(size_t)i + 1], keys, rec + offsets[i]);
     }
     } catch (const std::bad_alloc &) { c->err = "out of memory in phx_drop_margins_flat"; return PHX_E_NOMEM; }
     return PHX_OK;
 }
 
-int phx_drop_ms(phx_ctx *c, float *ms) {
-    if (!c || !ms) return PHX_E_ARG;
-    for (int k = 0; k < 4; k++) ms[k] = c->drop_ms[k];
-    return PHX_OK;
-}
+int phx_drop_ms(phx_ctx *c, float *ms) { return values_out<4>(c, ms, [](const phx_ctx *x) { return x->dp.ms; }); }
+int phx_drop_stats(phx_ctx *c, int64_t *out) { return values_out<4>(c, out, [](const phx_ctx *x) { return x->dp.stats; }); }
 
-int phx_drop_stats(phx_ctx *c, int64_t *out) {
-    if (!c || !out) return PHX_E_ARG;
-    for (int k = 0; k < 4; k++) out[k] = c->drop_stats[k];
-    return PHX_OK;
-}
 
 // ---- drop replacements (phx_replace.inc, DESIGN.md §13) ----
 // The replacement pass, once for both entry points (§13 on the run's graph, §30 on a re-annotation's): pick -> cross -> regrowth -> counting
@@ -409,9 +428,9 @@ static int ensure_replacements(phx_ctx *c) {
     DMarg g;
     margins_args(c, &g);
     DDrop q;
-    drop_args(c, &q);
+    drop_args(c->dp, true, &q);
     hipStream_t s = c->stream;
-    const int rc = replacement_pass(c, c->rp, (size_t)c->droff[(size_t)c->n], [&](int step, const DRepl &r) {
+    const int rc = replacement_pass(c, c->rp, (size_t)c->dp.roff[(size_t)c->n], [&](int step, const DRepl &r) {
         if (step == 0) phxk_repl_pick(&b, &g, &q, &r, nlm, s);
         else if (step == 1) phxk_repl_cross(&b, &g, &q, &r, nlm, s);
         else phxk_repl_walk(&b, &g, &q, &r, step - 2, s);
@@ -478,14 +497,14 @@ int phx_replacements_flat(phx_ctx *c, phx_gene_repl *rec, int64_t cap, phx_gene 
     { const int rd = phx_drop_margins_flat(c, drec.data(), total, offsets, status, &total); if (rd) return rd; }
     int64_t gt = 0;
     for (int i = 0; i < c->n; i++)
-        if (offsets[i + 1] != offsets[i]) gt += replacement_genes(c->rp, c->droff[(size_t)i], c->droff[(size_t)i + 1]);
+        if (offsets[i + 1] != offsets[i]) gt += replacement_genes(c->rp, c->dp.roff[(size_t)i], c->dp.roff[(size_t)i + 1]);
     if (total_out) *total_out = total;
     if (gene_total_out) *gene_total_out = gt;
     if (!rec || !genes) return PHX_OK; // size query
     if (cap < total || gene_cap < gt) return PHX_E_ARG;
     int64_t go = 0;
     for (int i = 0; i < c->n; i++)
-        if (offsets[i + 1] != offsets[i]) replacement_rows(c->rp, c->droff[(size_t)i], c->droff[(size_t)i + 1], drec.data() + offsets[i], rec + offsets[i], genes, &go);
+        if (offsets[i + 1] != offsets[i]) replacement_rows(c->rp, c->dp.roff[(size_t)i], c->dp.roff[(size_t)i + 1], drec.data() + offsets[i], rec + offsets[i], genes, &go);
     } catch (const std::bad_alloc &) { c->err = "out of memory in phx_replacements_flat"; return PHX_E_NOMEM; }
     return PHX_OK;
 }
@@ -498,20 +517,11 @@ int phx_tap_replacement(phx_ctx *c, int32_t contig, int32_t k, int32_t *path, in
     { const int rr = ensure_replacements(c); if (rr) return rr; }
     if (!drop_contig(c, (size_t)contig) || margins_status(c, contig) != 0) return PHX_E_ARG;
     const DMeta &m = c->meta[(size_t)contig];
-    return replacement_tap(c, c->rp, "phx_tap_replacement", contig, c->droff[(size_t)contig], c->droff[(size_t)contig + 1], k, (const int32_t *)c->b_path.p + m.node_off, m.n_path, path, cap, n_path);
+    return replacement_tap(c, c->rp, "phx_tap_replacement", contig, c->dp.roff[(size_t)contig], c->dp.roff[(size_t)contig + 1], k, (const int32_t *)c->b_path.p + m.node_off, m.n_path, path, cap, n_path);
 }
 
-int phx_replacements_ms(phx_ctx *c, float *ms) {
-    if (!c || !ms) return PHX_E_ARG;
-    for (int k = 0; k < 3; k++) ms[k] = c->rp.ms[k];
-    return PHX_OK;
-}
-
-int phx_replacement_stats(phx_ctx *c, int64_t *out) {
-    if (!c || !out) return PHX_E_ARG;
-    for (int k = 0; k < 5; k++) out[k] = c->rp.stats[k];
-    return PHX_OK;
-}
+int phx_replacements_ms(phx_ctx *c, float *ms) { return values_out<3>(c, ms, [](const phx_ctx *x) { return x->rp.ms; }); }
+int phx_replacement_stats(phx_ctx *c, int64_t *out) { return values_out<5>(c, out, [](const phx_ctx *x) { return x->rp.stats; }); }
 
 // ---- masked re-annotation (phx_resolve.inc, DESIGN.md §14) ----
 // status of contig i's re-annotation before any kernel: a run error, PHX_S_OVERFLOW without device distances, else the run's status
@@ -835,11 +845,7 @@ int phx_tap_repath(phx_ctx *c, int32_t contig, int32_t *path, int32_t cap, int32
     return PHX_OK;
 }
 
-int phx_reannotate_ms(phx_ctx *c, float *ms) {
-    if (!c || !ms) return PHX_E_ARG;
-    for (int k = 0; k < 3; k++) ms[k] = c->reann_ms[k];
-    return PHX_OK;
-}
+int phx_reannotate_ms(phx_ctx *c, float *ms) { return values_out<3>(c, ms, [](const phx_ctx *x) { return x->reann_ms; }); }
 
 // ---- the conditioned margins (phx_margins.inc): per-ORF path margins on the last re-annotation's graph ----
 // Two policies share one driver.  The re-annotation margins (DESIGN.md §21) cover the contigs solved again without a required ORF (modes 1
@@ -1056,33 +1062,13 @@ int phx_tap_pindist(phx_ctx *c, int32_t contig, int32_t which, uint64_t *dist_li
     return tap_redist(c, contig, which, dist_limbs, cap_words);
 }
 
-int phx_remargins_ms(phx_ctx *c, float *ms) {
-    if (!c || !ms) return PHX_E_ARG;
-    for (int k = 0; k < 4; k++) ms[k] = c->xm.ms[k];
-    return PHX_OK;
-}
-
-int phx_pinmargins_ms(phx_ctx *c, float *ms) {
-    if (!c || !ms) return PHX_E_ARG;
-    for (int k = 0; k < 4; k++) ms[k] = c->pm.ms[k];
-    return PHX_OK;
-}
+int phx_remargins_ms(phx_ctx *c, float *ms) { return values_out<4>(c, ms, [](const phx_ctx *x) { return x->xm.ms; }); }
+int phx_pinmargins_ms(phx_ctx *c, float *ms) { return values_out<4>(c, ms, [](const phx_ctx *x) { return x->pm.ms; }); }
 
 // ---- re-annotation drop margins (phx_drop.inc under MgDrop, DESIGN.md §29) ----
 // the contigs the conditioned drop kernels cover (dp_on<MgDrop>), after ensure_condmargins<CmPlain>
 static bool redrop_contig(const phx_ctx *c, size_t i) { return c->h_qsel[i] && c->xm.h_sel[i] == 1 && !c->xm.mstat[i] && c->h_qrec[i].n_path >= 3; }
 
-// the kernels' view of the feature's own DDrop set (with the one-hop trees once they were asked for)
-static void redrop_args(phx_ctx *c, DDrop *q) {
-    const size_t n = (size_t)c->n;
-    q->pidx = (int32_t *)c->b_rdpi.p; q->js = (int32_t *)c->b_rdjs.p; q->jt = (int32_t *)c->b_rdjt.p; q->first = (int32_t *)c->b_rdfi.p; q->last = (int32_t *)c->b_rdla.p;
-    q->slot = (uint64_t *)c->b_rdslot.p; q->gtab = (uint64_t *)c->b_rdgtab.p;
-    q->toff = (const int64_t *)c->b_rdtro.p; q->roff = (const int64_t *)c->b_rdtro.p + n;
-    q->sx = (uint64_t *)c->b_rdsx.p; q->cx = (uint64_t *)c->b_rdcx.p; q->da = (uint64_t *)c->b_rdda.p; q->db = (uint64_t *)c->b_rddb.p;
-    q->rec = (phx_gene_drop *)c->b_rdrec.p; q->stats = (unsigned long long *)c->b_rdstats.p;
-    { DDrop env; drop_args(c, &env); q->layered = env.layered; } // (env PHX_DROP_LAYERED, read where the run's drops read it)
-    q->ps = c->done.retrees ? (int32_t *)c->b_rdps.p : nullptr; q->ts = c->done.retrees ? (int32_t *)c->b_rdts.p : nullptr;
-}
 // the conditioned kernels' view of what the last re-annotation and its margins left resident (after ensure_condmargins<CmPlain>)
 struct RedropView {
     DBatch b, qb;
@@ -1098,92 +1084,21 @@ static void redrop_view(phx_ctx *c, RedropView *v) {
     condmargins_args(c, c->xm, (size_t)c->tot_edge / 32 + 2, &v->r);
     v->qpath = (const int32_t *)c->b_qpath.p;
 }
-// The records of every pair of every re-annotation path into c->h_rdrec (at c->rdroff), once per re-annotation solve.  On top of the
-// re-annotation margins (the out-edge bitmaps, d_t' and the pass's verdicts: their ORF records come with them, a launch and a copy beside
-// the reverse pass) and, when a contig was not solved again, of the run's drop margins.  Reads what the solve and its margins left resident;
-// writes only the b_rd* set: the run's drops and replacements stay as they are.  trees: as ensure_drops' (b_rdps / b_rdts, for §30).
+// The re-annotation's set, once per re-annotation solve.  On top of the re-annotation margins (the out-edge bitmaps, d_t' and the pass's
+// verdicts: their ORF records come with them, a launch and a copy beside the reverse pass) and, when a contig was not solved again, of the
+// run's drop margins.  Reads what the solve and its margins left resident; writes only c->rd.
 static int ensure_redrops(phx_ctx *c, bool trees = false) {
     if (c->done.redrop && (!trees || c->done.retrees)) return PHX_OK;
-    if (c->done.redrop) { // drops computed without the trees: k_dp_tree once more, which rewrites the same labels
-        c->done.retrees = true;
-        if (!c->redrop_nlm) return PHX_OK;
-        const size_t nv = ((size_t)c->tot_node + (size_t)c->n + 1) * 4;
-        int rc;
-        if ((rc = ensure(c, c->b_rdps, nv)) || (rc = ensure(c, c->b_rdts, nv)) || (rc = ensure(c, c->rr.b_cnt, 2 * RP_NCNT * 8))) return rc;
-        RedropView v;
-        redrop_view(c, &v);
-        DDrop q;
-        redrop_args(c, &q);
-        q.stats = (unsigned long long *)c->rr.b_cnt.p + RP_NCNT; // (the redrops' own counters stay as they were)
-        phxk_redrop_trees(&v.b, &v.g, &v.rq, &v.r, v.qpath, &q, c->redrop_nlm, c->stream);
-        HIPCHK(c, hipGetLastError());
-        return PHX_OK;
-    }
-    if (trees) c->done.retrees = true;
     { const int rm = ensure_condmargins<CmPlain>(c); if (rm) return rm; }
-    const size_t n = (size_t)c->n, V = (size_t)c->tot_node;
-    bool unsolved = false;
-    for (size_t i = 0; i < n; i++) unsolved = unsolved || !c->h_qsel[i];
-    if (unsolved) { const int rd = ensure_drops(c); if (rd) return rd; }
-    const size_t limbs = (size_t)std::max(c->n_limbs, 2);
-    std::vector<int64_t> off(2 * n + 2, 0); // toff[n], roff[n + 1]
-    c->rdroff.assign(n + 1, 0);
-    int64_t tcells = 0, R = 0;
-    int nlm = 0;
-    for (size_t i = 0; i < n; i++) {
-        off[n + i] = R; c->rdroff[i] = R;
-        if (!redrop_contig(c, i)) continue;
-        nlm |= nl_class_bit(c->meta[i].sssp_nl);
-        const int np = c->h_qrec[i].n_path;
-        const int64_t cells = drop_cells(np);
-        if (cells > DP_TAB_LDS) { off[i] = tcells; tcells += cells; }
-        R += (np - 1) / 2;
-    }
-    off[2 * n] = R; c->rdroff[n] = R;
-    for (int k = 0; k < 4; k++) { c->redrop_ms[k] = 0; c->redrop_stats[k] = 0; }
-    c->redrop_nlm = nlm;
-    if (!nlm) { c->done.redrop = true; return PHX_OK; }
-    int rc;
-    const size_t nv = (V + n + 1) * 4;
-    if ((rc = ensure(c, c->b_rdpi, nv)) || (rc = ensure(c, c->b_rdjs, nv)) || (rc = ensure(c, c->b_rdjt, nv)) || (rc = ensure(c, c->b_rdfi, nv)) || (rc = ensure(c, c->b_rdla, nv))) return rc;
-    if ((rc = ensure(c, c->b_rdslot, (V + 1) * 8))) return rc;
-    if ((rc = ensure(c, c->b_rdgtab, ((size_t)tcells + 1) * 8))) return rc;
-    if ((rc = ensure(c, c->b_rdtro, (2 * n + 2) * 8))) return rc;
-    if ((rc = ensure(c, c->b_rdsx, ((size_t)R + 1) * limbs * 8)) || (rc = ensure(c, c->b_rdcx, ((size_t)R + 1) * limbs * 8))) return rc;
-    if ((rc = ensure(c, c->b_rdda, (V + 1) * limbs * 8)) || (rc = ensure(c, c->b_rddb, (V + 1) * limbs * 8))) return rc;
-    if ((rc = ensure(c, c->b_rdrec, ((size_t)R + 1) * sizeof(phx_gene_drop)))) return rc;
-    if ((rc = ensure(c, c->b_rdstats, 4 * 8))) return rc;
-    if (c->done.retrees && ((rc = ensure(c, c->b_rdps, nv)) || (rc = ensure(c, c->b_rdts, nv)))) return rc;
-    if ((rc = analysis_events(c))) return rc;
-    try { c->h_rdrec.resize((size_t)R + 1); } catch (const std::bad_alloc &) { c->err = "out of memory in phx_redrops_flat"; return PHX_E_NOMEM; }
+    if (any_unsolved(c)) { const int rd = ensure_drops(c); if (rd) return rd; }
     RedropView v;
     redrop_view(c, &v);
-    const DBatch &b = v.b;
-    const DMarg &g = v.g;
-    const DReann &rq = v.rq;
-    const DRmarg &r = v.r;
-    DDrop q;
-    redrop_args(c, &q);
-    const int32_t *qpath = v.qpath;
     hipStream_t s = c->stream;
-    unsigned long long st[4] = {0, 0, 0, 0};
-    HIPCHK(c, hipEventRecord(c->aev[0], s));
-    HIPCHK(c, hipMemcpyAsync(c->b_rdtro.p, off.data(), (2 * n + 2) * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemsetAsync(c->b_rdstats.p, 0, 4 * 8, s));
-    phxk_redrop_trees(&b, &g, &rq, &r, qpath, &q, nlm, s);
-    HIPCHK(c, hipEventRecord(c->aev[1], s));
-    phxk_redrop_cand(&b, &g, &rq, &r, qpath, &q, nlm, s);
-    HIPCHK(c, hipEventRecord(c->aev[2], s));
-    phxk_redrop_fix(&b, &g, &rq, &r, qpath, &q, nlm, s);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->aev[3], s));
-    if (R) HIPCHK(c, hipMemcpyAsync(c->h_rdrec.data(), c->b_rdrec.p, (size_t)R * sizeof(phx_gene_drop), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipEventRecord(c->aev[4], s));
-    HIPCHK(c, hipMemcpyAsync(st, c->b_rdstats.p, sizeof st, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    for (int k = 0; k < 4; k++) { c->redrop_ms[k] = ev_ms(c->aev[k], c->aev[k + 1]); c->redrop_stats[k] = (int64_t)st[k]; }
-    c->done.redrop = true;
-    return PHX_OK;
+    return drop_pass(c, c->rd, c->rr, c->done.redrop, c->done.retrees, trees, [&](size_t i) { return redrop_contig(c, i) ? c->h_qrec[i].n_path : 0; }, [&](int step, const DDrop &q) {
+        if (step == 0) phxk_redrop_trees(&v.b, &v.g, &v.rq, &v.r, v.qpath, &q, c->rd.nlm, s);
+        else if (step == 1) phxk_redrop_cand(&v.b, &v.g, &v.rq, &v.r, v.qpath, &q, c->rd.nlm, s);
+        else phxk_redrop_fix(&v.b, &v.g, &v.rq, &v.r, v.qpath, &q, c->rd.nlm, s);
+    });
 }
 
 int phx_redrops_flat(phx_ctx *c, phx_gene_drop *rec, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
@@ -1191,15 +1106,14 @@ int phx_redrops_flat(phx_ctx *c, phx_gene_drop *rec, int64_t cap, int64_t *offse
     { const int ra = after_run(c); if (ra) return ra; }
     { const int rs = remarg_state(c, "phx_redrops_flat"); if (rs) return rs; } // before any kernel
     { const int rd = ensure_redrops(c); if (rd) return rd; }
+    const phx_ctx::DropSet &D = c->rd;
     try {
     // the contigs that were not solved again: the run's drop margins, as phx_drop_margins_flat lays them out
     const size_t n = (size_t)c->n;
-    bool unsolved = false;
-    for (size_t i = 0; i < n; i++) unsolved = unsolved || !c->h_qsel[i];
     std::vector<int64_t> off0(n + 1, 0);
     std::vector<int32_t> st0(n, 0);
     std::vector<phx_gene_drop> rec0;
-    if (unsolved) {
+    if (any_unsolved(c)) {
         int64_t t0 = 0;
         { const int rd = phx_drop_margins_flat(c, nullptr, 0, off0.data(), st0.data(), &t0); if (rd) return rd; }
         if (rec) {
@@ -1208,17 +1122,12 @@ int phx_redrops_flat(phx_ctx *c, phx_gene_drop *rec, int64_t cap, int64_t *offse
             if (rd) return rd;
         }
     }
-    auto genes_of = [&](size_t i) -> int64_t {
-        int64_t k = 0;
-        for (int64_t x = c->rdroff[i]; x < c->rdroff[i + 1]; x++) k += c->h_rdrec[(size_t)x].called >= 0;
-        return k;
-    };
     int64_t total = 0;
     for (size_t i = 0; i < n; i++) {
         offsets[i] = total;
         if (!c->h_qsel[i]) { status[i] = st0[i]; total += off0[i + 1] - off0[i]; continue; }
         status[i] = condmargins_status(c, (int)i);
-        if (status[i] == 0 && redrop_contig(c, i)) total += genes_of(i);
+        if (status[i] == 0 && redrop_contig(c, i)) total += drop_count(D, D.roff[i], D.roff[i + 1]);
     }
     offsets[n] = total;
     if (total_out) *total_out = total;
@@ -1230,52 +1139,34 @@ int phx_redrops_flat(phx_ctx *c, phx_gene_drop *rec, int64_t cap, int64_t *offse
         phx_gene_drop *dst = rec + offsets[i];
         if (!c->h_qsel[i]) { memcpy(dst, rec0.data() + off0[i], (size_t)(off0[i + 1] - off0[i]) * sizeof(phx_gene_drop)); continue; }
         resolve_keys(c, (int)i, c->h_qsel[i], keys);
-        for (int64_t k = c->rdroff[i]; k < c->rdroff[i + 1]; k++) {
-            const phx_gene_drop &x = c->h_rdrec[(size_t)k];
-            if (x.called < 0) continue;
-            *dst = x;
-            dst->called = is_called(keys, x.left, x.right, x.strand) ? 1 : 0;
-            dst++;
-        }
+        drop_rows(D, D.roff[i], D.roff[i + 1], keys, dst);
     }
     } catch (const std::bad_alloc &) { c->err = "out of memory in phx_redrops_flat"; return PHX_E_NOMEM; }
     return PHX_OK;
 }
 
-int phx_redrops_ms(phx_ctx *c, float *ms) {
-    if (!c || !ms) return PHX_E_ARG;
-    for (int k = 0; k < 4; k++) ms[k] = c->redrop_ms[k];
-    return PHX_OK;
-}
-
-int phx_redrop_stats(phx_ctx *c, int64_t *out) {
-    if (!c || !out) return PHX_E_ARG;
-    for (int k = 0; k < 4; k++) out[k] = c->redrop_stats[k];
-    return PHX_OK;
-}
+int phx_redrops_ms(phx_ctx *c, float *ms) { return values_out<4>(c, ms, [](const phx_ctx *x) { return x->rd.ms; }); }
+int phx_redrop_stats(phx_ctx *c, int64_t *out) { return values_out<4>(c, out, [](const phx_ctx *x) { return x->rd.stats; }); }
 
 // ---- re-annotation replacements (phx_replace.inc under MgDrop, DESIGN.md §30) ----
-// Every record of h_rdrec gets its replacement into c->rr (h_rec / h_genes / h_det at rdroff's indices), once per re-annotation solve, on
+// Every record of rd.h_rec gets its replacement into c->rr (h_rec / h_genes / h_det at rd.roff's indices), once per re-annotation solve, on
 // top of ensure_redrops with the one-hop trees and, when a contig was not solved again, of the run's replacements.  Writes the rr set and
-// b_rdps / b_rdts only (and, as §13 does on its own set, the scratch the drop kernels left: js / jt / gtab of b_rd*).
+// rd.b_ps / b_ts only (and, as §13 does on its own set, the scratch the drop kernels left: js / jt / gtab of rd).
 static int ensure_rereplacements(phx_ctx *c) {
     if (c->done.rerepl) return PHX_OK;
     { const int rd = ensure_redrops(c, true); if (rd) return rd; }
-    const size_t n = (size_t)c->n;
-    bool unsolved = false;
-    for (size_t i = 0; i < n; i++) unsolved = unsolved || !c->h_qsel[i];
-    if (unsolved) { const int rr = ensure_replacements(c); if (rr) return rr; }
+    if (any_unsolved(c)) { const int rr = ensure_replacements(c); if (rr) return rr; }
     phx_ctx::ReplSet &S = c->rr;
     for (int k = 0; k < 3; k++) S.ms[k] = 0;
     for (int k = 0; k < 5; k++) S.stats[k] = 0;
-    const int nlm = c->redrop_nlm;
+    const int nlm = c->rd.nlm;
     if (!nlm) { c->done.rerepl = true; return PHX_OK; } // (no contig was solved again with a path: nothing is allocated)
     RedropView v;
     redrop_view(c, &v);
     DDrop q;
-    redrop_args(c, &q);
+    drop_args(c->rd, true, &q);
     hipStream_t s = c->stream;
-    const int rc = replacement_pass(c, S, (size_t)c->rdroff[n], [&](int step, const DRepl &r) {
+    const int rc = replacement_pass(c, S, (size_t)c->rd.roff[(size_t)c->n], [&](int step, const DRepl &r) {
         if (step == 0) phxk_rerepl_pick(&v.b, &v.g, &v.rq, &v.r, v.qpath, &q, &r, nlm, s);
         else if (step == 1) phxk_rerepl_cross(&v.b, &v.g, &v.rq, &v.r, v.qpath, &q, &r, nlm, s);
         else phxk_rerepl_walk(&v.b, &v.g, &v.rq, &v.r, v.qpath, &q, &r, step - 2, s);
@@ -1300,7 +1191,7 @@ int phx_rereplacements_flat(phx_ctx *c, phx_gene_repl *rec, int64_t cap, phx_gen
     // a contig that was not solved again: the run's records, as phx_replacements_flat lays them out
     auto set_of = [&](int i, int64_t *k0, int64_t *k1) -> const phx_ctx::ReplSet & {
         const bool again = c->h_qsel[(size_t)i] != 0;
-        const std::vector<int64_t> &ro = again ? c->rdroff : c->droff;
+        const std::vector<int64_t> &ro = again ? c->rd.roff : c->dp.roff;
         *k0 = ro[(size_t)i]; *k1 = ro[(size_t)i + 1];
         return again ? c->rr : c->rp;
     };
@@ -1328,21 +1219,12 @@ int phx_tap_rereplacement(phx_ctx *c, int32_t contig, int32_t k, int32_t *path, 
     { const int rr = ensure_rereplacements(c); if (rr) return rr; }
     if (!redrop_contig(c, (size_t)contig) || condmargins_status(c, contig) != 0) return PHX_E_ARG;
     const DMeta &m = c->meta[(size_t)contig];
-    return replacement_tap(c, c->rr, "phx_tap_rereplacement", contig, c->rdroff[(size_t)contig], c->rdroff[(size_t)contig + 1], k, (const int32_t *)c->b_qpath.p + m.node_off,
+    return replacement_tap(c, c->rr, "phx_tap_rereplacement", contig, c->rd.roff[(size_t)contig], c->rd.roff[(size_t)contig + 1], k, (const int32_t *)c->b_qpath.p + m.node_off,
                            c->h_qrec[(size_t)contig].n_path, path, cap, n_path);
 }
 
-int phx_rereplacements_ms(phx_ctx *c, float *ms) {
-    if (!c || !ms) return PHX_E_ARG;
-    for (int k = 0; k < 3; k++) ms[k] = c->rr.ms[k];
-    return PHX_OK;
-}
-
-int phx_rereplacement_stats(phx_ctx *c, int64_t *out) {
-    if (!c || !out) return PHX_E_ARG;
-    for (int k = 0; k < 5; k++) out[k] = c->rr.stats[k];
-    return PHX_OK;
-}
+int phx_rereplacements_ms(phx_ctx *c, float *ms) { return values_out<3>(c, ms, [](const phx_ctx *x) { return x->rr.ms; }); }
+int phx_rereplacement_stats(phx_ctx *c, int64_t *out) { return values_out<5>(c, out, [](const phx_ctx *x) { return x->rr.stats; }); }
 
 // ---- scenario batches (phx_resolve.inc, DESIGN.md §17), with required ORFs (§18), biased ORFs (§20) or both (§27) per scenario ----
 // h_srec[j].status before the solve: the scenario gets a slot / its contig is not solved again and the run's verdict stands (neither is a status the device reports)
@@ -1724,10 +1606,6 @@ int phx_tap_scenario_path(phx_ctx *c, int64_t scen, int32_t *path, int32_t cap, 
     return PHX_OK;
 }
 
-int phx_scenarios_ms(phx_ctx *c, float *ms) {
-    if (!c || !ms) return PHX_E_ARG;
-    for (int k = 0; k < 3; k++) ms[k] = c->scen_ms[k];
-    return PHX_OK;
-}
+int phx_scenarios_ms(phx_ctx *c, float *ms) { return values_out<3>(c, ms, [](const phx_ctx *x) { return x->scen_ms; }); }
 
 int64_t phx_scenario_chunks(phx_ctx *c) { return c ? c->scen_chunks : (int64_t)PHX_E_ARG; } // (as phx_plan_timeouts: a NULL context is refused)

@@ -152,7 +152,7 @@ struct phx_ctx {
     std::unique_ptr<StagePool> pool;
     // buffers
     DevBuf *bufs = nullptr; // those that hold memory (ensure() lists a buffer at its first allocation, phx_destroy releases the list)
-    PinBuf pin_res, h_stage, h_genes, h_mrec, h_drec; // h_stage: H2D of the bases (records); h_genes: D2H of the gene records at link rate; h_mrec, h_drec: the margins' and the drops' device records
+    PinBuf pin_res, h_stage, h_genes, h_mrec; // h_stage: H2D of the bases (records); h_genes: D2H of the gene records at link rate; h_mrec: the margins' device records
     DevBuf b_bridge, b_recs, b_meta, b_tiles, b_nbits, b_nbase, b_cbits, b_orf, b_ostat, b_oweight, b_owi, b_oflag, b_onode, b_grp, b_bits, b_cpre, b_bpre, b_item, b_iprev;
     DevBuf b_ewf, b_esrcf;   // fp64 weights and plain sources of the batch last run, recomputed for the edge tap (k_edges<true, true>)
     bool tapw_valid = false; // ... are those of the run whose results the context holds
@@ -234,15 +234,15 @@ struct phx_ctx {
     struct RunDone {
         bool rev = false;     // the margins' shared part: out-edge CSR, d_t, mstat
         bool margins = false; // the ORF records are in h_mrec (device ORF order)
-        bool drops = false;   // the drop records are in h_drec (a record per pair of the path), at droff
-        bool trees = false;   // ... and the drop kernels kept the one-hop trees (b_dps / b_dts)
+        bool drops = false;   // the drop records are in dp.h_rec (a record per pair of the path), at dp.roff
+        bool trees = false;   // ... and the drop kernels kept the one-hop trees (dp.b_ps / b_ts)
         bool repl = false;    // rp.h_rec / h_genes / h_det
         bool reann = false;   // h_q* hold the re-annotation for the mask h_qforb / h_qflags
         bool scen = false;    // h_s* hold the scenario batch h_skey
         bool remarg = false;  // xm.h_rec / xm.mstat hold the margins of the re-annotation h_q* hold (also reset by every re-annotation solve)
         bool pinmarg = false; // pm.h_rec / pm.h_lost / pm.mstat hold the pinned margins of the re-annotation h_q* hold (reset wherever remarg is)
-        bool redrop = false;  // h_rdrec holds the drop margins of the re-annotation h_q* hold, at rdroff (reset wherever remarg is)
-        bool retrees = false; // ... and the drop kernels kept that graph's one-hop trees (b_rdps / b_rdts; reset wherever redrop is)
+        bool redrop = false;  // rd.h_rec holds the drop margins of the re-annotation h_q* hold, at rd.roff (reset wherever remarg is)
+        bool retrees = false; // ... and the drop kernels kept that graph's one-hop trees (rd.b_ps / b_ts; reset wherever redrop is)
         bool rerepl = false;  // rr.h_rec / h_genes / h_det hold the replacements of the re-annotation h_q* hold (reset wherever redrop is)
         bool grp = false;     // h_grp
     } done;
@@ -254,18 +254,24 @@ struct phx_ctx {
     std::vector<int32_t> mstat;      // per contig: the reverse pass did not settle
     float margins_ms[4] = {0, 0, 0, 0};
     float rev_ms[2] = {0, 0};        // device time of the shared part: out-edge CSR, reverse pass
-    // gene drop margins (phx_drop_margins_flat): buffers allocated at the first call, results kept until the next run
-    DevBuf b_dpi, b_djs, b_djt, b_dfi, b_dla, b_dslot, b_dgtab, b_doff, b_dsx, b_dcx, b_dda, b_ddb, b_drec, b_dstats;
-    std::vector<int64_t> droff;      // per contig (+1): first record in h_drec
-    float drop_ms[4] = {0, 0, 0, 0};
-    int64_t drop_stats[4] = {0, 0, 0, 0};
+    // The drop margins (drop_pass): a DDrop set with its host side, allocated at the first call that has a contig for it.  dp: the run's (phx_drop_margins_flat,
+    // DESIGN.md §12), kept until the next run; rd: the last re-annotation's (phx_redrops_flat, §29), kept until the next re-annotation solve or
+    // run — it reads the run's buffers and writes its own set only, so the run's cached drops and replacements stay as they are.
+    struct DropSet {
+        DevBuf b_pi, b_js, b_jt, b_fi, b_la, b_slot, b_gtab, b_off, b_sx, b_cx, b_da, b_db, b_rec, b_stats; // DDrop (b_off: toff[n], roff[n + 1])
+        DevBuf b_ps, b_ts;           // the one-hop trees, once the replacements asked for them (§13, §30)
+        std::vector<int64_t> roff;   // per contig (+1): first record in h_rec (a contig that is not covered: none)
+        PinBuf h_rec;                // a phx_gene_drop per pair of every covered path
+        int nlm = 0;                 // the limb classes among the covered contigs (0: none, and nothing was launched)
+        float ms[4] = {0, 0, 0, 0};
+        int64_t stats[4] = {0, 0, 0, 0};
+    } dp, rd;
     // drop replacements (phx_replacements_flat): buffers allocated at the first call, results kept until the next run
     // (rp: the run's set.  rr: the set of the re-annotation replacements, phx_rereplacements_flat, DESIGN.md §30 — allocated at the first call
     // that has a solved-again contig for it, the result kept until the next re-annotation solve or run; rp is not touched by it.)
-    DevBuf b_dps, b_dts;
     struct ReplSet {
         DevBuf b_win, b_xs, b_coff, b_cm, b_chain, b_rnd, b_info, b_doff, b_det, b_genes, b_rec, b_cnt; // DRepl
-        std::vector<phx_gene_repl> h_rec; // per device record (as h_drec / h_rdrec); gene_off into h_genes
+        std::vector<phx_gene_repl> h_rec; // per device record (as DropSet::h_rec); gene_off into h_genes
         std::vector<phx_gene> h_genes;
         std::vector<int32_t> h_det, h_info; // the detours; per record a, b, m, genes
         std::vector<int64_t> h_doff;      // per record: first detour node in h_det
@@ -304,15 +310,6 @@ struct phx_ctx {
         std::vector<int32_t> h_lost;     // ... and their `lost` (pm alone)
         float ms[4] = {0, 0, 0, 0};      // phx_remargins_ms / phx_pinmargins_ms
     } xm, pm;
-    // re-annotation drop margins (phx_redrops_flat): a second DDrop set, allocated at the first call that has a contig for it; the
-    // result kept until the next re-annotation solve or run.  The run's own drops and replacements (b_d*, b_r*) are not touched.
-    DevBuf b_rdpi, b_rdjs, b_rdjt, b_rdfi, b_rdla, b_rdslot, b_rdgtab, b_rdtro, b_rdsx, b_rdcx, b_rdda, b_rddb, b_rdrec, b_rdstats;
-    DevBuf b_rdps, b_rdts;              // the one-hop trees of that graph, for the re-annotation replacements (§30)
-    int redrop_nlm = 0;                 // the limb classes among the contigs h_rdrec covers (0: none)
-    std::vector<int64_t> rdroff;        // per contig (+1): first record in h_rdrec (a contig that is not covered: none)
-    std::vector<phx_gene_drop> h_rdrec; // a record per pair of the re-annotation's path
-    float redrop_ms[4] = {0, 0, 0, 0};
-    int64_t redrop_stats[4] = {0, 0, 0, 0};
     // scenario batches (phx_scenarios_flat): buffers of their own, allocated at the first call; the result kept until the next upload or run
     DevBuf b_sc_slot, b_sc_pair, b_sc_meta, b_sc_dist, b_sc_parent, b_sc_path, b_sc_mask, b_sc_plan, b_sc_genes, b_sc_rec, b_sc_tot, b_sc_gtot, b_sc_tie, b_sc_pin, b_sc_bs, b_sc_trip, b_sc_blist;
     int64_t scen_budget = (int64_t)2 << 30; // device bytes of a chunk's slots (env PHX_SCEN_BYTES at phx_create)
@@ -807,7 +804,7 @@ void phx_destroy(phx_ctx *c) {
     c->in_flight = false;
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (DevBuf *b = c->bufs; b; b = b->next) release(*b);
-    for (PinBuf *b : {&c->pin_res, &c->h_stage, &c->h_tiles, &c->h_genes, &c->h_mrec, &c->h_drec}) if (b->p) (void)hipHostFree(b->p);
+    for (PinBuf *b : {&c->pin_res, &c->h_stage, &c->h_tiles, &c->h_genes, &c->h_mrec, &c->dp.h_rec, &c->rd.h_rec}) if (b->p) (void)hipHostFree(b->p);
     for (hipEvent_t e : c->aev) if (e) (void)hipEventDestroy(e);
     if (c->graph_exec) (void)hipGraphExecDestroy(c->graph_exec);
     if (c->graph) (void)hipGraphDestroy(c->graph);

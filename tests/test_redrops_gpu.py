@@ -406,6 +406,47 @@ def test_redrops_disturb_nothing_are_cached_and_invalidated(pa):
         x.close()
 
 
+def test_the_two_drop_sets_stay_apart_across_orders_and_batches(pa):
+    """The run's drop set and the re-annotation's share one host pass (drop_pass) and must not share state.  One context, two batches (3
+    contigs, then 20: both sets grow); per batch one evidence() call that solves contig 0 alone again, then rereplacements() first — it
+    brings the re-annotation's set up with its trees and, through the contigs that were not solved again, the run's set without trees and
+    then with the late tree launch —, then the other analyses.  Everything equals, byte for byte and counter for counter, what a fresh
+    context gives in the plain order; the run's counters are the same before and after the re-annotation's pass."""
+
+    def the_evidence(ann, st0, offs0, genes0):
+        assert st0[0] == 0
+        cg = called_orfs(ann, 0, genes0[offs0[0]:offs0[1]])
+        k = next(k for k in range(len(ann.orfs(0))) if k not in cg)
+        n = ann.n
+        return [[(k, 1.5)]] + [None] * (n - 1), [[cg[len(cg) // 2]]] + [None] * (n - 1)
+
+    def flat(out):
+        return [x.tobytes() for x in out]
+
+    ann = pa.Annotator()
+    for seqs in (fuzz(41, 3), fuzz(42, 20)):
+        bias, forbid = the_evidence(ann, *run_batch(ann, seqs))
+        st = ann.evidence(bias, forbid)[0]
+        rr = ann.rereplacements()  # the first analysis call after the solve
+        got = dict(rr=flat(rr), rd=flat(ann.redrops()), rp=flat(ann.replacements()), dp=flat(ann.drop_margins()),
+                   stats=(ann.drop_stats(), ann.redrop_stats(), ann.replacement_stats(), ann.rereplacement_stats()))
+        offs = rr[1]
+        assert st[0] == 0 and rr[0][0] == 0 and offs[1] > offs[0] and offs[-1] > offs[1]  # contig 0 solved again, the run's records beside it
+        fresh = pa.Annotator()
+        assert flat(run_batch(fresh, seqs)) == flat(ann.download_flat(exact=False))
+        want = dict(dp=flat(fresh.drop_margins()), rp=flat(fresh.replacements()))
+        run_stats = (fresh.drop_stats(), fresh.replacement_stats())
+        fresh.evidence(bias, forbid)
+        want.update(rd=flat(fresh.redrops()), rr=flat(fresh.rereplacements()))
+        want["stats"] = (fresh.drop_stats(), fresh.redrop_stats(), fresh.replacement_stats(), fresh.rereplacement_stats())
+        assert run_stats == (want["stats"][0], want["stats"][2])  # the re-annotation's pass left the run's counters alone
+        for key in ("dp", "rp", "rd", "rr", "stats"):
+            assert got[key] == want[key], (len(seqs), key)
+        assert got["stats"][0]["slots"] > 0 and got["stats"][1]["slots"] > 0
+        fresh.close()
+    ann.close()
+
+
 # ---- 9. batch size and create flags ----
 def test_lone_contig_and_batch_of_300_give_the_same_bytes(pa):
     seqs = fuzz(23, 300)
