@@ -49,7 +49,8 @@ extern "C" {
  *        (additions, version unchanged) phx_pinmargins_flat, phx_pinmargins_ms, phx_tap_pindist — probe for the symbol;
  *        (addition, version unchanged) phx_curate_scenarios_flat — probe for the symbol;
  *        (additions, version unchanged) phx_redrops_flat, phx_redrops_ms, phx_redrop_stats — probe for the symbol
- *        (additions, version unchanged) phx_rereplacements_flat, phx_tap_rereplacement, phx_rereplacements_ms, phx_rereplacement_stats — probe for the symbol */
+ *        (additions, version unchanged) phx_rereplacements_flat, phx_tap_rereplacement, phx_rereplacements_ms, phx_rereplacement_stats — probe for the symbol
+ *        (additions, version unchanged) phx_pindrops_flat, phx_pindrops_ms, phx_pindrop_stats — probe for the symbol */
 #define PHX_MAX_CODONS 16
 
 /* library-level errors */
@@ -590,6 +591,30 @@ int phx_pinmargins_ms(phx_ctx *ctx, float *ms /* [4] */);
 /* phx_tap_redist for every re-annotation: *words_per_node (may be NULL) is sssp_nl + 1 for a contig solved under the required policy —
  * the top word carries the count, an unreached node has a top word >= 2^61 — and sssp_nl otherwise. */
 int phx_tap_pindist(phx_ctx *ctx, int32_t contig, int32_t which, uint64_t *dist_limbs, int64_t cap_words, int32_t *words_per_node);
+
+/* ---- pinned drop margins: the support of every call under required ORFs ----
+ * phx_redrops_flat for every re-annotation of the batch last run, phx_constrain_flat and phx_curate_flat with required ORFs included.  For
+ * a contig solved again under F, B and R with status 0, G', R_n, W', d_s', d_t' and D' are phx_pinmargins_flat's and P' = p_0 ... p_K is
+ * the re-annotation's device path.  A called gene is a CDS ORF edge of P', its stop node p_j as for phx_drop_margins_flat; D'_{-g} is the
+ * shortest source -> target distance under W' in G'[R_n] without p_j, in NL + 1 limbs, and Delta = D'_{-g} - D' >= 0 = lost·M + s, decoded
+ * as phx_pinmargins_flat decodes Delta'':  lost[k] >= 0 is the number of kept required ORFs that the best annotation without a gene at
+ * this stop gives up (net: a kept pin at the stop is lost, a required ORF that comes in instead counts against it), drop = float(s) / 1000.0 — negative drops occur where
+ * lost > 0; the order is (lost, drop) >= (0, 0.0).  No such path: bypass = 0, drop = +inf, lost = 0.  With grp the ORFs of the gene's stop
+ * group, D'_{-g} is the optimum of phx_curate_flat(B, F + grp, R - grp): lost = the difference of the two calls' (required - unmet), drop =
+ * the difference of their delta sums.  score and called as phx_redrops_flat; records in path order, a tRNA pair gets none.
+ * rec and lost are parallel, cap entries each (rec == NULL: size query; with rec, lost is needed).  status[i] as phx_redrops_flat's table
+ * with "solved again" covering every mode.  A contig that was solved again without a required ORF has phx_redrops_flat's records (those of
+ * the same call without the other contigs' required ORFs) and lost 0, one that was not solved again phx_drop_margins_flat's and lost 0;
+ * when no contig was solved under the required policy, the arrays are phx_redrops_flat's byte for byte.  PHX_E_STATE only without a
+ * re-annotation of this run.  Computed at the first call after a re-annotation solve, on top of phx_pinmargins_flat's computation, in
+ * buffers of its own; kept until the next solve or run.  Nothing the other entry points return changes: phx_redrops_flat,
+ * phx_rereplacements_flat and their taps keep refusing a solve with required ORFs.  (Additions, version unchanged: probe for the symbol.) */
+int phx_pindrops_flat(phx_ctx *ctx, phx_gene_drop *rec, int32_t *lost, int64_t cap, int64_t *offsets /* [n+1] */, int32_t *status /* [n] */, int64_t *total);
+/* device time of the last computation (HIP events), ms[4], as phx_redrops_ms: trees + labels, candidates + sparse table, fixups, the copy
+ * of the records — and its counters, out[4], as phx_drop_stats, both over the contigs that were solved again: the pinned kernels' over
+ * the contigs solved under the required policy plus phx_redrops_ms / phx_redrop_stats' over the others. */
+int phx_pindrops_ms(phx_ctx *ctx, float *ms /* [4] */);
+int phx_pindrop_stats(phx_ctx *ctx, int64_t *out /* [4] */);
 
 /* ---- scenario batches: many masked re-annotations of the batch last run in one call ----
  * n_scen scenarios, each a contig of the batch last run and a set F of its ORFs, solved side by side on the resident graph, one

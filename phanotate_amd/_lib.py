@@ -189,6 +189,9 @@ def lib():
         "phx_pinmargins_flat": (C.c_int, [vp, vp, vp, i64, vp, vp, P(i64)]),
         "phx_pinmargins_ms": (C.c_int, [vp, P(C.c_float)]),
         "phx_tap_pindist": (C.c_int, [vp, i32, i32, vp, i64, P(i32)]),
+        "phx_pindrops_flat": (C.c_int, [vp, vp, vp, i64, vp, vp, P(i64)]),
+        "phx_pindrops_ms": (C.c_int, [vp, P(C.c_float)]),
+        "phx_pindrop_stats": (C.c_int, [vp, P(i64)]),
         "phx_scenarios_flat": (C.c_int, [vp, i64, vp, vp, vp, vp, C.c_uint32, vp, i64, vp, vp, vp, P(i64)]),
         "phx_pinned_scenarios_flat": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, i64, vp, vp, vp, vp, P(i64)]),
         "phx_evidence_scenarios_flat": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, i64, vp, vp, vp, P(i64)]),
@@ -244,4 +247,5 @@ EXPORTS = ["phx_version", "phx_device_count", "phx_strerror", "phx_last_error", 
            "phx_remargins_flat", "phx_remargins_ms", "phx_tap_redist",
            "phx_pinmargins_flat", "phx_pinmargins_ms", "phx_tap_pindist",
            "phx_redrops_flat", "phx_redrops_ms", "phx_redrop_stats",
-           "phx_rereplacements_flat", "phx_tap_rereplacement", "phx_rereplacements_ms", "phx_rereplacement_stats"]
+           "phx_rereplacements_flat", "phx_tap_rereplacement", "phx_rereplacements_ms", "phx_rereplacement_stats",
+           "phx_pindrops_flat", "phx_pindrops_ms", "phx_pindrop_stats"]

@@ -73,6 +73,7 @@ _MS_KEYS = {
     "phx_remargins_ms": ("apply", "reverse", "margins", "download"),
     "phx_pinmargins_ms": ("apply", "reverse", "margins", "download"),
     "phx_redrops_ms": ("trees", "candidates", "fixups", "download"),
+    "phx_pindrops_ms": ("trees", "candidates", "fixups", "download"),
     "phx_rereplacements_ms": ("argmin", "walk", "download"),
     "phx_reannotate_ms": ("mask", "solve", "finish"),
 }
@@ -1004,6 +1005,27 @@ class Annotator:
     def pinmargins_ms(self):
         """Device time of the last pinned margins in ms: apply, reverse pass, records, copy to the host (phx_pinmargins_ms)."""
         return self._ms("phx_pinmargins_ms")
+
+    def pindrops(self):
+        """(status int32[n], offsets int64[n+1], records structured array[total] of _lib.DROP_DT, lost int32[total]): redrops() for every
+        re-annotation of the batch last run, constrain() and curate() with required ORFs included (phx_pindrops_flat).
+        For a contig solved with required ORFs, lost[k] is the number of kept required ORFs the best annotation without a gene at gene
+        k's stop gives up — net: a kept pin at the stop is lost, a required ORF that comes in instead counts against it — and drop the change of the path sum in SCORE units; it may
+        be negative where lost > 0; the order is (lost, drop) >= (0, 0.0).  It is what curate(bias, forbid + the ORFs of the gene's stop
+        group, require - them) returns, without that solve.  Elsewhere the records are redrops()' and lost is 0.  PhxError
+        (PHX_E_STATE) only without a re-annotation of this run."""
+        (status,), offs, (rec, lost) = self._query_fill(self.L.phx_pindrops_flat, "phx_pindrops_flat", (), self.n, (_lib.DROP_DT, np.int32), "rrc")
+        return status, offs, rec, lost
+
+    def pindrops_ms(self):
+        """Device time of the last pinned drop margins in ms: trees + labels, candidates, fixups, copy to the host (phx_pindrops_ms)."""
+        return self._ms("phx_pindrops_ms")
+
+    def pindrop_stats(self):
+        """drop_stats() of the last pinned drop margins, over the contigs that were solved again (phx_pindrop_stats)."""
+        out = (C.c_int64 * 4)()
+        self._chk(self.L.phx_pindrop_stats(self.h, out), "phx_pindrop_stats")
+        return dict(zip(("slots", "cross", "rescanned", "layered"), [int(x) for x in out]))
 
     def pindist(self, i, to_target=False):
         """redist(i, to_target) for every re-annotation (phx_tap_pindist).  A contig solved with required ORFs gives per node None

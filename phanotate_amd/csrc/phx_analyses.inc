@@ -202,7 +202,7 @@ extern "C++" template <class C, class L> static int drop_pass(phx_ctx *c, phx_ct
         has_trees = true;
         return PHX_OK;
     }
-    const size_t limbs = (size_t)std::max(c->n_limbs, 2);
+    const size_t limbs = (size_t)std::max(c->n_limbs, 2) + (size_t)D.wide; // (the pinned set: DPmarg.dt_stride words per record and node)
     std::vector<int64_t> off(2 * n + 2, 0); // toff[n], roff[n + 1]
     D.roff.assign(n + 1, 0);
     D.nlm = 0;
@@ -228,6 +228,10 @@ extern "C++" template <class C, class L> static int drop_pass(phx_ctx *c, phx_ct
         if ((rc = ensure(c, D.b_rec, ((size_t)R + 1) * sizeof(phx_gene_drop)))) return rc;
         if ((rc = ensure(c, D.b_stats, 4 * 8))) return rc;
         if (trees && ((rc = ensure(c, D.b_ps, nv)) || (rc = ensure(c, D.b_ts, nv)))) return rc;
+        if (D.wide) {
+            if ((rc = ensure(c, D.b_lost, ((size_t)R + 1) * 4))) return rc;
+            try { D.h_lost.resize((size_t)R + 1); } catch (const std::bad_alloc &) { c->err = "out of memory in the drop margins"; return PHX_E_NOMEM; }
+        }
         if ((rc = ensure_pinned(c, D.h_rec, ((size_t)R + 1) * sizeof(phx_gene_drop), ((size_t)R + (size_t)R / 4 + 1024) * sizeof(phx_gene_drop)))) return rc;
         if ((rc = analysis_events(c))) return rc;
         drop_args(D, trees, &q);
@@ -244,6 +248,7 @@ extern "C++" template <class C, class L> static int drop_pass(phx_ctx *c, phx_ct
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipEventRecord(c->aev[3], s));
         if (R) HIPCHK(c, hipMemcpyAsync(D.h_rec.p, D.b_rec.p, (size_t)R * sizeof(phx_gene_drop), hipMemcpyDeviceToHost, s));
+        if (R && D.wide) HIPCHK(c, hipMemcpyAsync(D.h_lost.data(), D.b_lost.p, (size_t)R * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipEventRecord(c->aev[4], s));
         HIPCHK(c, hipMemcpyAsync(st, D.b_stats.p, sizeof st, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
@@ -279,7 +284,8 @@ static int64_t drop_count(const phx_ctx::DropSet &D, int64_t k0, int64_t k1) {
     for (int64_t r = k0; r < k1; r++) k += src[r].called >= 0;
     return k;
 }
-static void drop_rows(const phx_ctx::DropSet &D, int64_t k0, int64_t k1, const std::vector<uint64_t> &keys, phx_gene_drop *dst) {
+// (lost: null, or where the rows' `lost` go — a set without one gives 0)
+static void drop_rows(const phx_ctx::DropSet &D, int64_t k0, int64_t k1, const std::vector<uint64_t> &keys, phx_gene_drop *dst, int32_t *lost = nullptr) {
     const phx_gene_drop *src = (const phx_gene_drop *)D.h_rec.p;
     for (int64_t k = k0; k < k1; k++) {
         const phx_gene_drop &x = src[k];
@@ -287,6 +293,7 @@ static void drop_rows(const phx_ctx::DropSet &D, int64_t k0, int64_t k1, const s
         *dst = x;
         dst->called = is_called(keys, x.left, x.right, x.strand) ? 1 : 0;
         dst++;
+        if (lost) *lost++ = D.wide ? D.h_lost[(size_t)k] : 0;
     }
 }
 
@@ -746,6 +753,8 @@ static int reann_flat(phx_ctx *c, const char *who, bool need_forbid, const uint8
         c->done.reann = false;
         c->done.remarg = false; // (the re-annotation margins are this solve's)
         c->done.pinmarg = false;
+        c->done.pindrop = false;
+        c->done.pintrees = false;
         c->done.redrop = false;
         c->done.retrees = false;
         c->done.rerepl = false;
@@ -1147,6 +1156,99 @@ int phx_redrops_flat(phx_ctx *c, phx_gene_drop *rec, int64_t cap, int64_t *offse
 
 int phx_redrops_ms(phx_ctx *c, float *ms) { return values_out<4>(c, ms, [](const phx_ctx *x) { return x->rd.ms; }); }
 int phx_redrop_stats(phx_ctx *c, int64_t *out) { return values_out<4>(c, out, [](const phx_ctx *x) { return x->rd.stats; }); }
+
+// ---- pinned drop margins (phx_drop.inc under MgPinDrop, DESIGN.md §32) ----
+// the contigs the pinned drop kernels cover (dp_on<MgPinDrop>), after ensure_condmargins<CmPin>
+static bool pindrop_contig(const phx_ctx *c, size_t i) { return re_mode_req(c->h_qsel[i]) && c->pm.h_sel[i] == 1 && !c->pm.mstat[i] && c->h_qrec[i].n_path >= 3; }
+
+// The pinned set, once per re-annotation solve.  On top of the pinned margins (the three out-edge bitmaps, d_t' on one limb more and the
+// pass's verdicts), of the re-annotation drop margins for the contigs solved again without a required ORF and, through them, of the run's
+// for the contigs that were not solved again.  Reads what the solve and its margins left resident; writes only c->pd.
+static int ensure_pindrops(phx_ctx *c) {
+    if (c->done.pindrop) return PHX_OK;
+    { const int rm = ensure_condmargins<CmPin>(c); if (rm) return rm; }
+    { const int rd = ensure_redrops(c); if (rd) return rd; }
+    phx_ctx::DropSet &D = c->pd;
+    D.wide = 1;
+    DBatch b, qb;
+    fill_batch(c, &b);
+    DMarg g;
+    margins_args(c, &g);
+    DReann rq;
+    reann_batch(c, &qb, &rq);
+    DPmarg r;
+    const size_t mw = (size_t)c->tot_edge / 32 + 2;
+    condmargins_args(c, c->pm, mw, &r);
+    r.dt_stride = b.dist_stride + 1; r.rbit = r.fbit + 2 * mw; r.lost = (int32_t *)c->pm.b_lost.p; // (as ensure_condmargins<CmPin> laid them out)
+    const int32_t *qpath = (const int32_t *)c->b_qpath.p;
+    hipStream_t s = c->stream;
+    return drop_pass(c, D, c->rr, c->done.pindrop, c->done.pintrees, false, [&](size_t i) { return pindrop_contig(c, i) ? c->h_qrec[i].n_path : 0; }, [&](int step, const DDrop &q) {
+        int32_t *lost = (int32_t *)D.b_lost.p;
+        if (step == 0) phxk_pindrop_trees(&b, &g, &rq, &r, qpath, lost, &q, D.nlm, s);
+        else if (step == 1) phxk_pindrop_cand(&b, &g, &rq, &r, qpath, lost, &q, D.nlm, s);
+        else phxk_pindrop_fix(&b, &g, &rq, &r, qpath, lost, &q, D.nlm, s);
+    });
+}
+
+int phx_pindrops_flat(phx_ctx *c, phx_gene_drop *rec, int32_t *lost, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
+    if (!c || (c->n > 0 && (!offsets || !status)) || (rec && !lost)) return PHX_E_ARG;
+    { const int ra = after_run(c); if (ra) return ra; }
+    if (!c->done.reann) { c->err = "phx_pindrops_flat: no re-annotation of this run (call phx_constrain_flat or phx_curate_flat first)"; return PHX_E_STATE; } // before any kernel
+    { const int rd = ensure_pindrops(c); if (rd) return rd; }
+    try {
+    // the contigs that were not solved again: the run's drop margins, as phx_drop_margins_flat lays them out
+    const size_t n = (size_t)c->n;
+    std::vector<int64_t> off0(n + 1, 0);
+    std::vector<int32_t> st0(n, 0);
+    std::vector<phx_gene_drop> rec0;
+    if (any_unsolved(c)) {
+        int64_t t0 = 0;
+        { const int rd = phx_drop_margins_flat(c, nullptr, 0, off0.data(), st0.data(), &t0); if (rd) return rd; }
+        if (rec) {
+            rec0.resize((size_t)t0 + 1);
+            const int rd = phx_drop_margins_flat(c, rec0.data(), t0, off0.data(), st0.data(), &t0);
+            if (rd) return rd;
+        }
+    }
+    auto set_of = [&](size_t i) -> const phx_ctx::DropSet & { return re_mode_req(c->h_qsel[i]) ? c->pd : c->rd; };
+    auto covered = [&](size_t i) { return re_mode_req(c->h_qsel[i]) ? pindrop_contig(c, i) : redrop_contig(c, i); };
+    int64_t total = 0;
+    for (size_t i = 0; i < n; i++) {
+        offsets[i] = total;
+        if (!c->h_qsel[i]) { status[i] = st0[i]; total += off0[i + 1] - off0[i]; continue; }
+        status[i] = condmargins_status(c, (int)i);
+        if (status[i] == 0 && covered(i)) { const phx_ctx::DropSet &D = set_of(i); total += drop_count(D, D.roff[i], D.roff[i + 1]); }
+    }
+    offsets[n] = total;
+    if (total_out) *total_out = total;
+    if (!rec) return PHX_OK; // size query
+    if (cap < total) return PHX_E_ARG;
+    std::vector<uint64_t> keys;
+    for (size_t i = 0; i < n; i++) {
+        if (offsets[i + 1] == offsets[i]) continue;
+        phx_gene_drop *dst = rec + offsets[i];
+        const size_t k = (size_t)(offsets[i + 1] - offsets[i]);
+        if (!c->h_qsel[i]) { memcpy(dst, rec0.data() + off0[i], k * sizeof(phx_gene_drop)); memset(lost + offsets[i], 0, k * 4); continue; }
+        resolve_keys(c, (int)i, c->h_qsel[i], keys);
+        const phx_ctx::DropSet &D = set_of(i);
+        drop_rows(D, D.roff[i], D.roff[i + 1], keys, dst, lost + offsets[i]); // (records and `lost` are dropped together)
+    }
+    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_pindrops_flat"; return PHX_E_NOMEM; }
+    return PHX_OK;
+}
+
+// device time and counters of the last phx_pindrops_flat over the contigs that were solved again: the pinned pass's, plus §29's for the
+// contigs solved again without a required ORF (a batch without a pinned contig: phx_redrops_ms / phx_redrop_stats)
+int phx_pindrops_ms(phx_ctx *c, float *ms) {
+    float v[4];
+    if (c) for (int k = 0; k < 4; k++) v[k] = c->pd.ms[k] + c->rd.ms[k];
+    return values_out<4>(c, ms, [&](const phx_ctx *) { return v; });
+}
+int phx_pindrop_stats(phx_ctx *c, int64_t *out) {
+    int64_t v[4];
+    if (c) for (int k = 0; k < 4; k++) v[k] = c->pd.stats[k] + c->rd.stats[k];
+    return values_out<4>(c, out, [&](const phx_ctx *) { return v; });
+}
 
 // ---- re-annotation replacements (phx_replace.inc under MgDrop, DESIGN.md §30) ----
 // Every record of rd.h_rec gets its replacement into c->rr (h_rec / h_genes / h_det at rd.roff's indices), once per re-annotation solve, on

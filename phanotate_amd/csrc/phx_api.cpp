@@ -243,6 +243,8 @@ struct phx_ctx {
         bool pinmarg = false; // pm.h_rec / pm.h_lost / pm.mstat hold the pinned margins of the re-annotation h_q* hold (reset wherever remarg is)
         bool redrop = false;  // rd.h_rec holds the drop margins of the re-annotation h_q* hold, at rd.roff (reset wherever remarg is)
         bool retrees = false; // ... and the drop kernels kept that graph's one-hop trees (rd.b_ps / b_ts; reset wherever redrop is)
+        bool pindrop = false; // pd.h_rec / pd.h_lost hold the pinned drop margins of the re-annotation h_q* hold, at pd.roff (reset wherever pinmarg is)
+        bool pintrees = false; // (drop_pass's second flag for the pd set: nothing asks for its one-hop trees)
         bool rerepl = false;  // rr.h_rec / h_genes / h_det hold the replacements of the re-annotation h_q* hold (reset wherever redrop is)
         bool grp = false;     // h_grp
     } done;
@@ -256,7 +258,9 @@ struct phx_ctx {
     float rev_ms[2] = {0, 0};        // device time of the shared part: out-edge CSR, reverse pass
     // The drop margins (drop_pass): a DDrop set with its host side, allocated at the first call that has a contig for it.  dp: the run's (phx_drop_margins_flat,
     // DESIGN.md §12), kept until the next run; rd: the last re-annotation's (phx_redrops_flat, §29), kept until the next re-annotation solve or
-    // run — it reads the run's buffers and writes its own set only, so the run's cached drops and replacements stay as they are.
+    // run — it reads the run's buffers and writes its own set only, so the run's cached drops and replacements stay as they are.  pd: the
+    // pinned drop margins' (phx_pindrops_flat, §32) — the contigs of the last re-annotation that were solved under the required policy; its
+    // limb buffers are at the pinned stride (`wide`: one word more per record and node) and `lost` goes beside the records; kept as rd is.
     struct DropSet {
         DevBuf b_pi, b_js, b_jt, b_fi, b_la, b_slot, b_gtab, b_off, b_sx, b_cx, b_da, b_db, b_rec, b_stats; // DDrop (b_off: toff[n], roff[n + 1])
         DevBuf b_ps, b_ts;           // the one-hop trees, once the replacements asked for them (§13, §30)
@@ -265,7 +269,10 @@ struct phx_ctx {
         int nlm = 0;                 // the limb classes among the covered contigs (0: none, and nothing was launched)
         float ms[4] = {0, 0, 0, 0};
         int64_t stats[4] = {0, 0, 0, 0};
-    } dp, rd;
+        int wide = 0;                // words per record / node of b_sx, b_cx, b_da, b_db beyond the batch's widest class (pd: 1, with b_lost / h_lost)
+        DevBuf b_lost;               // per device record: `lost` (pd alone)
+        std::vector<int32_t> h_lost;
+    } dp, rd, pd;
     // drop replacements (phx_replacements_flat): buffers allocated at the first call, results kept until the next run
     // (rp: the run's set.  rr: the set of the re-annotation replacements, phx_rereplacements_flat, DESIGN.md §30 — allocated at the first call
     // that has a solved-again contig for it, the result kept until the next re-annotation solve or run; rp is not touched by it.)
@@ -804,7 +811,7 @@ void phx_destroy(phx_ctx *c) {
     c->in_flight = false;
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (DevBuf *b = c->bufs; b; b = b->next) release(*b);
-    for (PinBuf *b : {&c->pin_res, &c->h_stage, &c->h_tiles, &c->h_genes, &c->h_mrec, &c->dp.h_rec, &c->rd.h_rec}) if (b->p) (void)hipHostFree(b->p);
+    for (PinBuf *b : {&c->pin_res, &c->h_stage, &c->h_tiles, &c->h_genes, &c->h_mrec, &c->dp.h_rec, &c->rd.h_rec, &c->pd.h_rec}) if (b->p) (void)hipHostFree(b->p);
     for (hipEvent_t e : c->aev) if (e) (void)hipEventDestroy(e);
     if (c->graph_exec) (void)hipGraphExecDestroy(c->graph_exec);
     if (c->graph) (void)hipGraphDestroy(c->graph);

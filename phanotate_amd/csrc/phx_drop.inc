@@ -44,30 +44,30 @@ __device__ __forceinline__ bool dp_gene(const DBatch &b, const DMeta *meta, cons
     return false;
 }
 
-template <int NL>
-__device__ __forceinline__ WInt<NL> wi_from_u64(uint64_t x) {
-    WInt<NL> r;
+template <int W>
+__device__ __forceinline__ WInt<W> wi_from_u64(uint64_t x) {
+    WInt<W> r;
     r.v[0] = x;
 #pragma unroll
-    for (int i = 1; i < NL; i++) r.v[i] = 0;
+    for (int i = 1; i < W; i++) r.v[i] = 0;
     return r;
 }
 // a non-negative candidate as a 64-bit key: itself below 2^63, else DP_SAT
-template <int NL>
-__device__ __forceinline__ uint64_t wi_sat64(const WInt<NL> &x) {
+template <int W>
+__device__ __forceinline__ uint64_t wi_sat64(const WInt<W> &x) {
     bool big = (x.v[0] >> 63) != 0;
 #pragma unroll
-    for (int i = 1; i < NL; i++) big = big || x.v[i] != 0;
+    for (int i = 1; i < W; i++) big = big || x.v[i] != 0;
     return big ? DP_SAT : x.v[0];
 }
 // minimum over the 64 lanes of a wavefront (every lane gets it)
-template <int NL>
-__device__ __forceinline__ WInt<NL> wave_min(WInt<NL> x) {
+template <int W>
+__device__ __forceinline__ WInt<W> wave_min(WInt<W> x) {
     for (int m = 32; m >= 1; m >>= 1) {
-        WInt<NL> y;
+        WInt<W> y;
 #pragma unroll
-        for (int i = 0; i < NL; i++) y.v[i] = (uint64_t)__shfl_xor((unsigned long long)x.v[i], m);
-        if (wi_lt<NL>(y, x)) x = y;
+        for (int i = 0; i < W; i++) y.v[i] = (uint64_t)__shfl_xor((unsigned long long)x.v[i], m);
+        if (wi_lt<W>(y, x)) x = y;
     }
     return x;
 }
@@ -87,6 +87,23 @@ __device__ __forceinline__ uint64_t ld_l2(const uint64_t *p) { return __hip_atom
 //   treated likewise through DRmarg.fbit / bbit / bval.  As in k_sssp_rev, the bitmaps are read per edge only for a node whose edge range
 //   shares a bitmap word with a refused or biased slot (`special`): a re-annotation's are a handful per contig.
 struct MgDrop : MgCond { const int32_t *path; };
+// MgPinDrop (the pinned drop margins, DESIGN.md §32): MgPin — a contig solved under the required policy (DReann.mode 2 or 4) — with the
+// re-annotation's device path and the place of `lost`, the two pointers MgPin lacks (no struct that exists grows).  It is a policy of its
+// own with a trait of its own: mg_pin<G> keeps meaning MgPin, and mg_cond<G> holds, so everything MgDrop adds applies.  What dp_pin<G> adds:
+//   a value has WL = NL + 1 limbs in all five kernels, the top limb minus the count of required edges (§16); d_s' comes from DPmarg.ds with
+//   NL + 1 limbs per node used, d_t' from DPmarg.dist_t at DPmarg.dt_stride words per node reserved;
+//   an in-edge slot set in DReann.req / an out-edge position set in DPmarg.rbit weighs W + B - M, M = 2^(64 NL): one off the top limb.  The
+//   req / rbit words are part of the per-node `special` test, so nearly every node keeps the plain loops;
+//   DDrop.sx / cx are indexed at DPmarg.dt_stride words per record and DDrop.da / db per node (dp_stride; the host sizes the set so);
+//   k_dp_rec decodes Delta = lost * M + s as k_margins<NL, MgPin> decodes Delta'': lost to MgPinDrop.lost (parallel to DDrop.rec), drop =
+//   float(s) / 1000.0 with s the low NL limbs as the class's two's complement (negative where lost > 0 and the low part went down).
+// wi_sat64 saturates whenever a limb above the first is non-zero, so every candidate with lost > 0 — and every one with lost = 0 and
+// s >= 2^63 — is DP_SAT in the sparse table, and a candidate that is not saturated has lost = 0 and s < 2^63: it is below each of them in
+// the (lost, s) order as well.  A slot whose minimum is not DP_SAT therefore holds its exact minimum; one that is DP_SAT is recomputed by
+// k_dp_rescan in WL limbs, where two's-complement order on lost * M + s is the lexicographic order.
+struct MgPinDrop : MgPin { const int32_t *path; int32_t *lost; };
+template <class G> constexpr bool dp_pin = std::is_same<G, MgPinDrop>::value;
+template <int NL, class G> constexpr int dp_wl = NL + (dp_pin<G> ? 1 : 0); // limbs of a value
 template <class G>
 __device__ __forceinline__ bool dp_on(const DBatch &b, const G &g, const DMeta *meta) {
     if constexpr (mg_cond<G>) { const int i = (int)(meta - b.meta); return g.r.sel[i] == 1 && mg_contig(meta) && !g.r.mstat[i] && g.q.rec[i].n_path >= 3; }
@@ -109,15 +126,26 @@ __device__ __forceinline__ const uint64_t *dp_ds(const DBatch &b, const G &g, co
 }
 template <class G>
 __device__ __forceinline__ const uint64_t *dp_dt(const DBatch &b, const G &g, const DMeta *meta) {
-    if constexpr (mg_cond<G>) return g.r.dist_t + (size_t)meta->node_off * b.dist_stride;
+    if constexpr (dp_pin<G>) return g.r.dist_t + (size_t)meta->node_off * g.r.dt_stride;
+    else if constexpr (mg_cond<G>) return g.r.dist_t + (size_t)meta->node_off * b.dist_stride;
     else return g.dist_t + (size_t)meta->node_off * b.dist_stride;
 }
-// `special` of a node's in-edge slots / out-edge positions [e0, e1) (MgDrop only)
+// words reserved per record of DDrop.sx / cx and per node of DDrop.da / db
+template <class G>
+__device__ __forceinline__ size_t dp_stride(const DBatch &b, const G &g) {
+    if constexpr (dp_pin<G>) return (size_t)g.r.dt_stride;
+    else return (size_t)b.dist_stride;
+}
+// `special` of a node's in-edge slots / out-edge positions [e0, e1) (MgDrop and MgPinDrop only)
 template <class G>
 __device__ __forceinline__ bool dp_sp_in(const G &g, bool biased, uint64_t ebase, uint32_t e0, uint32_t e1) {
     bool sp = false;
     if (e1 > e0)
         for (uint64_t x = (ebase + e0) >> 5, x1 = (ebase + e1 - 1) >> 5; x <= x1; x++) sp = sp || (g.q.mask[x] | (biased ? g.q.bbit[x] : 0u)) != 0u;
+    if constexpr (dp_pin<G>) { // (the required slots are a handful as well: the same test covers them)
+        if (e1 > e0)
+            for (uint64_t x = (ebase + e0) >> 5, x1 = (ebase + e1 - 1) >> 5; x <= x1; x++) sp = sp || g.q.req[x] != 0u;
+    }
     return sp;
 }
 template <class G>
@@ -125,18 +153,24 @@ __device__ __forceinline__ bool dp_sp_out(const G &g, uint64_t ebase, uint32_t e
     bool sp = false;
     if (e1 > e0)
         for (uint64_t x = (ebase + e0) >> 5, x1 = (ebase + e1 - 1) >> 5; x <= x1; x++) sp = sp || (g.r.fbit[x] | g.r.bbit[x]) != 0u;
+    if constexpr (dp_pin<G>) {
+        if (e1 > e0)
+            for (uint64_t x = (ebase + e0) >> 5, x1 = (ebase + e1 - 1) >> 5; x <= x1; x++) sp = sp || g.r.rbit[x] != 0u;
+    }
     return sp;
 }
 // W' of in-edge slot x / out-edge position x of the batch, given W (the caller has skipped a refused one); under DMarg: W.  A call stands
 // where the weight stood, so that the DMarg code keeps its order of loads.
-template <int NL, class G>
-__device__ __forceinline__ WInt<NL> dp_w_in(const G &g, bool sp, bool biased, uint64_t x, WInt<NL> w) {
-    if constexpr (mg_cond<G>) { if (sp && biased && mg_bit(g.q.bbit, x)) w = wi_add<NL>(w, ew_decode<NL>(g.q.bval[x])); }
+template <int W, class G>
+__device__ __forceinline__ WInt<W> dp_w_in(const G &g, bool sp, bool biased, uint64_t x, WInt<W> w) {
+    if constexpr (mg_cond<G>) { if (sp && biased && mg_bit(g.q.bbit, x)) w = wi_add<W>(w, ew_decode<W>(g.q.bval[x])); }
+    if constexpr (dp_pin<G>) { if (sp && mg_bit(g.q.req, x)) w.v[W - 1] -= 1ull; } // required: W' = W + B - M, one off the top limb
     return w;
 }
-template <int NL, class G>
-__device__ __forceinline__ WInt<NL> dp_w_out(const G &g, bool sp, uint64_t x, WInt<NL> w) {
-    if constexpr (mg_cond<G>) { if (sp && mg_bit(g.r.bbit, x)) w = wi_add<NL>(w, ew_decode<NL>(g.r.bval[x])); }
+template <int W, class G>
+__device__ __forceinline__ WInt<W> dp_w_out(const G &g, bool sp, uint64_t x, WInt<W> w) {
+    if constexpr (mg_cond<G>) { if (sp && mg_bit(g.r.bbit, x)) w = wi_add<W>(w, ew_decode<W>(g.r.bval[x])); }
+    if constexpr (dp_pin<G>) { if (sp && mg_bit(g.r.rbit, x)) w.v[W - 1] -= 1ull; }
     return w;
 }
 
@@ -150,6 +184,7 @@ __device__ __forceinline__ WInt<NL> dp_w_out(const G &g, bool sp, uint64_t x, WI
 template <int NL, class G = DMarg>
 __global__ __launch_bounds__(NT) void k_dp_tree(DBatch b, G g, DDrop q) {
     constexpr bool COND = mg_cond<G>;
+    constexpr int WL = dp_wl<NL, G>;
     __shared__ int s_fail[2], s_chg;
     const DMeta *meta = &b.meta[blockIdx.x];
     if (!dp_on<G>(b, g, meta) || meta->sssp_nl != NL) return;
@@ -179,20 +214,20 @@ __global__ __launch_bounds__(NT) void k_dp_tree(DBatch b, G g, DDrop q) {
         int ps = -1, ts = -1;
         if (pidx[v] >= 0) ps = ts = v;
         else {
-            const WInt<NL> dv = wi_load<NL>(ds + (size_t)v * NL);
-            if (!wi_unreached<NL>(dv)) {
+            const WInt<WL> dv = wi_load<WL>(ds + (size_t)v * WL);
+            if (!wi_unreached<WL>(dv)) {
                 ps = -2; // (a reached node without a tight in-edge cannot occur: the layered build then leaves it out)
                 [[maybe_unused]] bool sp = false;
                 if constexpr (COND) sp = dp_sp_in(g, biased, ebase, in_off[v], in_off[v + 1]);
                 for (uint32_t e = in_off[v], e1 = in_off[v + 1]; e < e1; e++) {
                     const uint32_t sw = esrc[e];
                     if constexpr (COND) { if (sp && mg_bit(g.q.mask, ebase + e)) continue; }
-                    const WInt<NL> du = wi_load<NL>(ds + (size_t)ESRC_NODE(sw) * NL);
-                    if (!wi_unreached<NL>(du) && wi_eq<NL>(wi_add<NL>(du, dp_w_in<NL>(g, sp, biased, ebase + e, ew_decode<NL>(edge_wenc(sw, ew, e, gt)))), dv)) { ps = (int)ESRC_NODE(sw); break; }
+                    const WInt<WL> du = wi_load<WL>(ds + (size_t)ESRC_NODE(sw) * WL);
+                    if (!wi_unreached<WL>(du) && wi_eq<WL>(wi_add<WL>(du, dp_w_in<WL>(g, sp, biased, ebase + e, ew_decode<WL>(edge_wenc(sw, ew, e, gt)))), dv)) { ps = (int)ESRC_NODE(sw); break; }
                 }
             }
-            const WInt<NL> tv = wi_load<NL>(dt + (size_t)v * NL);
-            if (!wi_unreached<NL>(tv)) {
+            const WInt<WL> tv = wi_load<WL>(dt + (size_t)v * WL);
+            if (!wi_unreached<WL>(tv)) {
                 ts = -2;
                 [[maybe_unused]] bool sp = false;
                 if constexpr (COND) sp = dp_sp_out(g, ebase, oo[v], oo[v + 1]);
@@ -200,8 +235,8 @@ __global__ __launch_bounds__(NT) void k_dp_tree(DBatch b, G g, DDrop q) {
                     const int z = (int)od[e];
                     if (ts >= 0 && z >= ts) continue;
                     if constexpr (COND) { if (sp && mg_bit(g.r.fbit, ebase + e)) continue; }
-                    const WInt<NL> tz = wi_load<NL>(dt + (size_t)z * NL);
-                    if (!wi_unreached<NL>(tz) && wi_eq<NL>(wi_add<NL>(tz, dp_w_out<NL>(g, sp, ebase + e, ew_decode<NL>(ow[e]))), tv)) ts = z;
+                    const WInt<WL> tz = wi_load<WL>(dt + (size_t)z * WL);
+                    if (!wi_unreached<WL>(tz) && wi_eq<WL>(wi_add<WL>(tz, dp_w_out<WL>(g, sp, ebase + e, ew_decode<WL>(ow[e]))), tv)) ts = z;
                 }
             }
         }
@@ -243,17 +278,17 @@ __global__ __launch_bounds__(NT) void k_dp_tree(DBatch b, G g, DDrop q) {
         __syncthreads();
         for (int v = tid; v < V; v += NT) {
             if (fs && js[v] == 0x7fffffff) {
-                const WInt<NL> dv = wi_load<NL>(ds + (size_t)v * NL);
+                const WInt<WL> dv = wi_load<WL>(ds + (size_t)v * WL);
                 [[maybe_unused]] bool sp = false;
-                if constexpr (COND) { if (!wi_unreached<NL>(dv)) sp = dp_sp_in(g, biased, ebase, in_off[v], in_off[v + 1]); }
-                if (!wi_unreached<NL>(dv))
+                if constexpr (COND) { if (!wi_unreached<WL>(dv)) sp = dp_sp_in(g, biased, ebase, in_off[v], in_off[v + 1]); }
+                if (!wi_unreached<WL>(dv))
                     for (uint32_t e = in_off[v], e1 = in_off[v + 1]; e < e1; e++) {
                         const uint32_t sw = esrc[e];
                         const int u = (int)ESRC_NODE(sw);
                         if (js[u] >= r) continue;
                         if constexpr (COND) { if (sp && mg_bit(g.q.mask, ebase + e)) continue; }
-                        const WInt<NL> du = wi_load<NL>(ds + (size_t)u * NL);
-                        if (!wi_unreached<NL>(du) && wi_eq<NL>(wi_add<NL>(du, dp_w_in<NL>(g, sp, biased, ebase + e, ew_decode<NL>(edge_wenc(sw, ew, e, gt)))), dv)) {
+                        const WInt<WL> du = wi_load<WL>(ds + (size_t)u * WL);
+                        if (!wi_unreached<WL>(du) && wi_eq<WL>(wi_add<WL>(du, dp_w_in<WL>(g, sp, biased, ebase + e, ew_decode<WL>(edge_wenc(sw, ew, e, gt)))), dv)) {
                             first[v] = first[u]; js[v] = r; s_chg = 1;
                             if (q.ps) q.ps[no + v] = u;
                             break;
@@ -261,8 +296,8 @@ __global__ __launch_bounds__(NT) void k_dp_tree(DBatch b, G g, DDrop q) {
                     }
             }
             if (ft && jt[v] == 0x7fffffff) {
-                const WInt<NL> tv = wi_load<NL>(dt + (size_t)v * NL);
-                if (!wi_unreached<NL>(tv)) {
+                const WInt<WL> tv = wi_load<WL>(dt + (size_t)v * WL);
+                if (!wi_unreached<WL>(tv)) {
                     int best = -1;
                     [[maybe_unused]] bool sp = false;
                     if constexpr (COND) sp = dp_sp_out(g, ebase, oo[v], oo[v + 1]);
@@ -270,8 +305,8 @@ __global__ __launch_bounds__(NT) void k_dp_tree(DBatch b, G g, DDrop q) {
                         const int z = (int)od[e];
                         if ((best >= 0 && z >= best) || jt[z] >= r) continue;
                         if constexpr (COND) { if (sp && mg_bit(g.r.fbit, ebase + e)) continue; }
-                        const WInt<NL> tz = wi_load<NL>(dt + (size_t)z * NL);
-                        if (!wi_unreached<NL>(tz) && wi_eq<NL>(wi_add<NL>(tz, dp_w_out<NL>(g, sp, ebase + e, ew_decode<NL>(ow[e]))), tv)) best = z;
+                        const WInt<WL> tz = wi_load<WL>(dt + (size_t)z * WL);
+                        if (!wi_unreached<WL>(tz) && wi_eq<WL>(wi_add<WL>(tz, dp_w_out<WL>(g, sp, ebase + e, ew_decode<WL>(ow[e]))), tv)) best = z;
                     }
                     if (best >= 0) { last[v] = last[best]; jt[v] = r; s_chg = 1; if (q.ts) q.ts[no + v] = best; }
                 }
@@ -290,6 +325,7 @@ __global__ __launch_bounds__(NT) void k_dp_tree(DBatch b, G g, DDrop q) {
 template <int NL, class G = DMarg>
 __global__ __launch_bounds__(NT) void k_dp_cand(DBatch b, G g, DDrop q) {
     constexpr bool COND = mg_cond<G>;
+    constexpr int WL = dp_wl<NL, G>;
     __shared__ unsigned long long s_tab[DP_TAB_LDS];
     const DMeta *meta = &b.meta[blockIdx.x];
     if (!dp_on<G>(b, g, meta) || meta->sssp_nl != NL) return;
@@ -311,11 +347,11 @@ __global__ __launch_bounds__(NT) void k_dp_cand(DBatch b, G g, DDrop q) {
     unsigned long long *tab = cells <= DP_TAB_LDS ? s_tab : (unsigned long long *)(q.gtab + q.toff[blockIdx.x]);
     for (int i = tid; i < cells; i += NT) tab[i] = DP_NONE;
     __syncthreads();
-    const WInt<NL> negD = wi_neg<NL>(wi_load<NL>(ds + (size_t)(V - 1) * NL));
+    const WInt<WL> negD = wi_neg<WL>(wi_load<WL>(ds + (size_t)(V - 1) * WL));
     for (int z = tid; z < V; z += NT) {
         const int lz = last[z];
         if (lz < 2) continue; // (no slot strictly between first(x) >= 0 and last(z))
-        const WInt<NL> tz = wi_add<NL>(wi_load<NL>(dt + (size_t)z * NL), negD);
+        const WInt<WL> tz = wi_add<WL>(wi_load<WL>(dt + (size_t)z * WL), negD);
         [[maybe_unused]] bool sp = false;
         if constexpr (COND) sp = dp_sp_in(g, biased, ebase, in_off[z], in_off[z + 1]);
         for (uint32_t e = in_off[z], e1 = in_off[z + 1]; e < e1; e++) {
@@ -325,8 +361,8 @@ __global__ __launch_bounds__(NT) void k_dp_cand(DBatch b, G g, DDrop q) {
             if (fx < 0 || fx + 1 > lz - 1) continue;
             if constexpr (COND) { if (sp && mg_bit(g.q.mask, ebase + e)) continue; }
             const int a = fx + 1, len = lz - 1 - a + 1;
-            const WInt<NL> c = wi_add<NL>(wi_add<NL>(wi_load<NL>(ds + (size_t)x * NL), dp_w_in<NL>(g, sp, biased, ebase + e, ew_decode<NL>(edge_wenc(sw, ew, e, gt)))), tz);
-            const unsigned long long key = wi_sat64<NL>(c);
+            const WInt<WL> c = wi_add<WL>(wi_add<WL>(wi_load<WL>(ds + (size_t)x * WL), dp_w_in<WL>(g, sp, biased, ebase + e, ew_decode<WL>(edge_wenc(sw, ew, e, gt)))), tz);
+            const unsigned long long key = wi_sat64<WL>(c);
             const int k = 31 - __clz(len);
             atomicMin(&tab[k * n + a], key);
             atomicMin(&tab[k * n + (lz - 1) - (1 << k) + 1], key);
@@ -350,6 +386,7 @@ __global__ __launch_bounds__(NT) void k_dp_cand(DBatch b, G g, DDrop q) {
 template <int NL, class G = DMarg>
 __global__ __launch_bounds__(NT) void k_dp_rescan(DBatch b, G g, DDrop q) {
     constexpr bool COND = mg_cond<G>;
+    constexpr int WL = dp_wl<NL, G>;
     const DMeta *meta = &b.meta[blockIdx.x];
     if (!dp_on<G>(b, g, meta) || meta->sssp_nl != NL) return;
     const int V = meta->n_node, np = (dp_npath<G>(b, g, meta) - 1) / 2;
@@ -367,14 +404,14 @@ __global__ __launch_bounds__(NT) void k_dp_rescan(DBatch b, G g, DDrop q) {
     if constexpr (COND) biased = re_mode_bias(g.q.mode[blockIdx.x]);
     const int32_t *first = q.first + no, *last = q.last + no;
     const uint64_t *slot = q.slot + no;
-    const WInt<NL> negD = wi_neg<NL>(wi_load<NL>(ds + (size_t)(V - 1) * NL));
+    const WInt<WL> negD = wi_neg<WL>(wi_load<WL>(ds + (size_t)(V - 1) * WL));
     for (int i = wv; i < np; i += NT / 64) {
         int j, k;
         if (!dp_gene(b, meta, path, i, &j, &k) || slot[j] != DP_SAT) continue;
-        WInt<NL> best = wi_inf<NL>();
+        WInt<WL> best = wi_inf<WL>();
         for (int z = lane; z < V; z += 64) {
             if (last[z] <= j) continue;
-            const WInt<NL> tz = wi_add<NL>(wi_load<NL>(dt + (size_t)z * NL), negD);
+            const WInt<WL> tz = wi_add<WL>(wi_load<WL>(dt + (size_t)z * WL), negD);
             [[maybe_unused]] bool sp = false;
             if constexpr (COND) sp = dp_sp_in(g, biased, ebase, in_off[z], in_off[z + 1]);
             for (uint32_t e = in_off[z], e1 = in_off[z + 1]; e < e1; e++) {
@@ -383,13 +420,13 @@ __global__ __launch_bounds__(NT) void k_dp_rescan(DBatch b, G g, DDrop q) {
                 const int fx = first[x];
                 if (fx < 0 || fx >= j) continue;
                 if constexpr (COND) { if (sp && mg_bit(g.q.mask, ebase + e)) continue; }
-                const WInt<NL> c = wi_add<NL>(wi_add<NL>(wi_load<NL>(ds + (size_t)x * NL), dp_w_in<NL>(g, sp, biased, ebase + e, ew_decode<NL>(edge_wenc(sw, ew, e, gt)))), tz);
-                if (wi_lt<NL>(c, best)) best = c;
+                const WInt<WL> c = wi_add<WL>(wi_add<WL>(wi_load<WL>(ds + (size_t)x * WL), dp_w_in<WL>(g, sp, biased, ebase + e, ew_decode<WL>(edge_wenc(sw, ew, e, gt)))), tz);
+                if (wi_lt<WL>(c, best)) best = c;
             }
         }
-        best = wave_min<NL>(best);
+        best = wave_min<WL>(best);
         if (lane == 0) {
-            wi_store<NL>(q.sx + ((size_t)q.roff[blockIdx.x] + i) * b.dist_stride, best);
+            wi_store<WL>(q.sx + ((size_t)q.roff[blockIdx.x] + i) * dp_stride<G>(b, g), best);
             atomicAdd(&q.stats[2], 1ull);
         }
     }
@@ -403,8 +440,9 @@ __global__ __launch_bounds__(NT) void k_dp_rescan(DBatch b, G g, DDrop q) {
 template <int NL, class G = DMarg>
 __global__ __launch_bounds__(NT) void k_dp_cross(DBatch b, G g, DDrop q) {
     constexpr bool COND = mg_cond<G>;
-    __shared__ uint64_t s_d[2][DP_CROSS_LDS * NL];
-    __shared__ uint64_t s_red[NT / 64][NL];
+    constexpr int WL = dp_wl<NL, G>;
+    __shared__ uint64_t s_d[2][DP_CROSS_LDS * WL];
+    __shared__ uint64_t s_red[NT / 64][WL];
     __shared__ int s_nc, s_any, s_chg;
     const DMeta *meta = &b.meta[blockIdx.x];
     if (!dp_on<G>(b, g, meta) || meta->sssp_nl != NL) return;
@@ -425,7 +463,7 @@ __global__ __launch_bounds__(NT) void k_dp_cross(DBatch b, G g, DDrop q) {
     if constexpr (COND) biased = re_mode_bias(g.q.mode[blockIdx.x]);
     const int32_t *first = q.first + no, *last = q.last + no, *pidx = q.pidx + no;
     int32_t *clist = q.js + no, *cpos = q.jt + no;
-    uint64_t *cx = q.cx + (size_t)q.roff[blockIdx.x] * b.dist_stride;
+    uint64_t *cx = q.cx + (size_t)q.roff[blockIdx.x] * dp_stride<G>(b, g);
     if (tid == 0) s_nc = 0;
     __syncthreads();
     for (int v = tid; v < V; v += NT) {
@@ -436,8 +474,8 @@ __global__ __launch_bounds__(NT) void k_dp_cross(DBatch b, G g, DDrop q) {
     }
     __syncthreads();
     const int nc = s_nc;
-    uint64_t *bufA = nc <= DP_CROSS_LDS ? s_d[0] : q.da + no * b.dist_stride, *bufB = nc <= DP_CROSS_LDS ? s_d[1] : q.db + no * b.dist_stride;
-    const WInt<NL> negD = wi_neg<NL>(wi_load<NL>(ds + (size_t)(V - 1) * NL));
+    uint64_t *bufA = nc <= DP_CROSS_LDS ? s_d[0] : q.da + no * dp_stride<G>(b, g), *bufB = nc <= DP_CROSS_LDS ? s_d[1] : q.db + no * dp_stride<G>(b, g);
+    const WInt<WL> negD = wi_neg<WL>(wi_load<WL>(ds + (size_t)(V - 1) * WL));
     for (int i = 0; i < np; i++) {
         int j, k;
         if (!dp_gene(b, meta, path, i, &j, &k)) continue; // (uniform over the workgroup)
@@ -447,13 +485,13 @@ __global__ __launch_bounds__(NT) void k_dp_cross(DBatch b, G g, DDrop q) {
         __syncthreads();
         const bool any = s_any != 0;
         __syncthreads(); // (read by all before thread 0 resets it)
-        if (!any) { if (tid == 0) wi_store<NL>(cx + (size_t)i * b.dist_stride, wi_inf<NL>()); continue; }
+        if (!any) { if (tid == 0) wi_store<WL>(cx + (size_t)i * dp_stride<G>(b, g), wi_inf<WL>()); continue; }
         if (tid == 0) atomicAdd(&q.stats[1], 1ull);
         auto in_y = [&](int y) { return cpos[y] >= 0 && last[y] <= j && j <= first[y]; };
         // seed
         for (int p = tid; p < nc; p += NT) {
             const int y = clist[p];
-            WInt<NL> d = wi_inf<NL>();
+            WInt<WL> d = wi_inf<WL>();
             [[maybe_unused]] bool sp = false;
             if constexpr (COND) { if (in_y(y)) sp = dp_sp_in(g, biased, ebase, in_off[y], in_off[y + 1]); }
             if (in_y(y))
@@ -463,10 +501,10 @@ __global__ __launch_bounds__(NT) void k_dp_cross(DBatch b, G g, DDrop q) {
                     const int fx = first[x];
                     if (fx < 0 || fx >= j) continue;
                     if constexpr (COND) { if (sp && mg_bit(g.q.mask, ebase + e)) continue; }
-                    const WInt<NL> c = wi_add<NL>(wi_load<NL>(ds + (size_t)x * NL), dp_w_in<NL>(g, sp, biased, ebase + e, ew_decode<NL>(edge_wenc(sw, ew, e, gt))));
-                    if (wi_lt<NL>(c, d)) d = c;
+                    const WInt<WL> c = wi_add<WL>(wi_load<WL>(ds + (size_t)x * WL), dp_w_in<WL>(g, sp, biased, ebase + e, ew_decode<WL>(edge_wenc(sw, ew, e, gt))));
+                    if (wi_lt<WL>(c, d)) d = c;
                 }
-            wi_store<NL>(bufA + (size_t)p * NL, d);
+            wi_store<WL>(bufA + (size_t)p * WL, d);
         }
         __syncthreads();
         // Jacobi within Y_j (no cycle of negative length: settles in |Y_j| rounds)
@@ -476,7 +514,7 @@ __global__ __launch_bounds__(NT) void k_dp_cross(DBatch b, G g, DDrop q) {
             __syncthreads();
             for (int p = tid; p < nc; p += NT) {
                 const int y = clist[p];
-                WInt<NL> d = wi_load<NL>(cur + (size_t)p * NL);
+                WInt<WL> d = wi_load<WL>(cur + (size_t)p * WL);
                 [[maybe_unused]] bool sp = false;
                 if constexpr (COND) { if (in_y(y)) sp = dp_sp_in(g, biased, ebase, in_off[y], in_off[y + 1]); }
                 if (in_y(y))
@@ -485,12 +523,12 @@ __global__ __launch_bounds__(NT) void k_dp_cross(DBatch b, G g, DDrop q) {
                         const int x = (int)ESRC_NODE(sw);
                         if (!in_y(x)) continue;
                         if constexpr (COND) { if (sp && mg_bit(g.q.mask, ebase + e)) continue; }
-                        const WInt<NL> dx = wi_load<NL>(cur + (size_t)cpos[x] * NL);
-                        if (wi_is_inf<NL>(dx)) continue;
-                        const WInt<NL> c = wi_add<NL>(dx, dp_w_in<NL>(g, sp, biased, ebase + e, ew_decode<NL>(edge_wenc(sw, ew, e, gt))));
-                        if (wi_lt<NL>(c, d)) { d = c; s_chg = 1; }
+                        const WInt<WL> dx = wi_load<WL>(cur + (size_t)cpos[x] * WL);
+                        if (wi_is_inf<WL>(dx)) continue;
+                        const WInt<WL> c = wi_add<WL>(dx, dp_w_in<WL>(g, sp, biased, ebase + e, ew_decode<WL>(edge_wenc(sw, ew, e, gt))));
+                        if (wi_lt<WL>(c, d)) { d = c; s_chg = 1; }
                     }
-                wi_store<NL>(nxt + (size_t)p * NL, d);
+                wi_store<WL>(nxt + (size_t)p * WL, d);
             }
             __syncthreads();
             uint64_t *t = cur; cur = nxt; nxt = t;
@@ -499,28 +537,28 @@ __global__ __launch_bounds__(NT) void k_dp_cross(DBatch b, G g, DDrop q) {
             if (!chg) break;
         }
         // leave Y_j
-        WInt<NL> best = wi_inf<NL>();
+        WInt<WL> best = wi_inf<WL>();
         for (int p = tid; p < nc; p += NT) {
             const int y = clist[p];
             if (!in_y(y)) continue;
-            const WInt<NL> d = wi_load<NL>(cur + (size_t)p * NL);
-            if (wi_is_inf<NL>(d)) continue;
+            const WInt<WL> d = wi_load<WL>(cur + (size_t)p * WL);
+            if (wi_is_inf<WL>(d)) continue;
             [[maybe_unused]] bool sp = false;
             if constexpr (COND) sp = dp_sp_out(g, ebase, oo[y], oo[y + 1]);
             for (uint32_t e = oo[y], e1 = oo[y + 1]; e < e1; e++) {
                 const int z = (int)od[e];
                 if (last[z] <= j) continue;
                 if constexpr (COND) { if (sp && mg_bit(g.r.fbit, ebase + e)) continue; }
-                const WInt<NL> c = wi_add<NL>(wi_add<NL>(d, dp_w_out<NL>(g, sp, ebase + e, ew_decode<NL>(ow[e]))), wi_add<NL>(wi_load<NL>(dt + (size_t)z * NL), negD));
-                if (wi_lt<NL>(c, best)) best = c;
+                const WInt<WL> c = wi_add<WL>(wi_add<WL>(d, dp_w_out<WL>(g, sp, ebase + e, ew_decode<WL>(ow[e]))), wi_add<WL>(wi_load<WL>(dt + (size_t)z * WL), negD));
+                if (wi_lt<WL>(c, best)) best = c;
             }
         }
-        best = wave_min<NL>(best);
-        if ((tid & 63) == 0) wi_store<NL>(s_red[tid >> 6], best);
+        best = wave_min<WL>(best);
+        if ((tid & 63) == 0) wi_store<WL>(s_red[tid >> 6], best);
         __syncthreads();
         if (tid == 0) {
-            for (int w = 1; w < NT / 64; w++) { const WInt<NL> o = wi_load<NL>(s_red[w]); if (wi_lt<NL>(o, best)) best = o; }
-            wi_store<NL>(cx + (size_t)i * b.dist_stride, best);
+            for (int w = 1; w < NT / 64; w++) { const WInt<WL> o = wi_load<WL>(s_red[w]); if (wi_lt<WL>(o, best)) best = o; }
+            wi_store<WL>(cx + (size_t)i * dp_stride<G>(b, g), best);
         }
         __syncthreads();
     }
@@ -529,6 +567,7 @@ __global__ __launch_bounds__(NT) void k_dp_cross(DBatch b, G g, DDrop q) {
 // ---- 5. k_dp_rec<NL>: a record per pair of P (called = -1: no CDS gene, dropped by the host) ----
 template <int NL, class G = DMarg>
 __global__ __launch_bounds__(NT) void k_dp_rec(DBatch b, G g, DDrop q) {
+    constexpr int WL = dp_wl<NL, G>;
     __shared__ int s_cnt;
     const DMeta *meta = &b.meta[blockIdx.x];
     if (!dp_on<G>(b, g, meta) || meta->sssp_nl != NL) return;
@@ -549,18 +588,29 @@ __global__ __launch_bounds__(NT) void k_dp_rec(DBatch b, G g, DDrop q) {
         r.frame = NFRAME(nd[a].info);
         r.strand = r.frame < 0 ? -1 : 1;
         r.score = 0.0; r.drop = __builtin_inf(); r.called = -1; r.bypass = 0;
+        [[maybe_unused]] int32_t lost = 0;
         int j, k;
         if (dp_gene(b, meta, path, i, &j, &k)) {
             cnt++;
             r.score = oweight[k];
             r.called = 0; // (the host's)
             const uint64_t s = slot[j];
-            WInt<NL> best = s == DP_SAT ? wi_load<NL>(q.sx + ((size_t)r0 + i) * b.dist_stride) : (s == DP_NONE ? wi_inf<NL>() : wi_from_u64<NL>(s));
-            const WInt<NL> c = wi_load<NL>(q.cx + ((size_t)r0 + i) * b.dist_stride);
-            if (wi_lt<NL>(c, best)) best = c;
-            if (!wi_is_inf<NL>(best)) { r.bypass = 1; r.drop = wi_to_double_rn<NL>(best) / 1000.0; }
+            WInt<WL> best = s == DP_SAT ? wi_load<WL>(q.sx + ((size_t)r0 + i) * dp_stride<G>(b, g)) : (s == DP_NONE ? wi_inf<WL>() : wi_from_u64<WL>(s));
+            const WInt<WL> c = wi_load<WL>(q.cx + ((size_t)r0 + i) * dp_stride<G>(b, g));
+            if (wi_lt<WL>(c, best)) best = c;
+            if constexpr (dp_pin<G>) { // Delta = lost * M + s: the kept pins the best annotation without this stop gives up, and the class's own signed sum
+                if (!wi_is_inf<WL>(best)) {
+                    lost = (int32_t)(int64_t)(best.v[WL - 1] + (best.v[NL - 1] >> 63));
+                    WInt<NL> sl;
+#pragma unroll
+                    for (int t = 0; t < NL; t++) sl.v[t] = best.v[t];
+                    r.bypass = 1; r.drop = wi_to_double_rn<NL>(sl) / 1000.0;
+                }
+            } else
+            if (!wi_is_inf<WL>(best)) { r.bypass = 1; r.drop = wi_to_double_rn<WL>(best) / 1000.0; }
         }
         q.rec[r0 + i] = r;
+        if constexpr (dp_pin<G>) g.lost[r0 + i] = lost;
     }
     if (cnt) atomicAdd(&s_cnt, cnt);
     __syncthreads();

@@ -545,6 +545,11 @@ void phxk_drop_fix(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask,
 void phxk_redrop_trees(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, int nl_mask, void *stream);
 void phxk_redrop_cand(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, int nl_mask, void *stream);
 void phxk_redrop_fix(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, int nl_mask, void *stream);
+// pinned drop margins (§32; r: what the pinned margins left resident, lost: one int32 per record of q; nl_mask: the classes among DPmarg.sel == 1,
+// the kernels work on one limb more): the three steps of the drop margins under MgPinDrop
+void phxk_pindrop_trees(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, int nl_mask, void *stream);
+void phxk_pindrop_cand(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, int nl_mask, void *stream);
+void phxk_pindrop_fix(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, int nl_mask, void *stream);
 void phxk_repl_pick(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream); // drop replacements (phx_replace.inc): winners,
 void phxk_repl_cross(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream); //   cross winners and their delta chains,
 void phxk_repl_walk(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int fill, void *stream);    //   detour lengths (fill 0) / detours, genes, records (1)

@@ -479,6 +479,22 @@ void phxk_redrop_fix(const DBatch *b, const DMarg *g, const DReann *rq, const DR
     each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_cross<decltype(nl)::value, MgDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, c, *q); });
     each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_rec<decltype(nl)::value, MgDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, c, *q); });
 }
+// pinned drop margins: the same five kernels under MgPinDrop, for the contigs solved under the required policy — values on one
+// limb more, DPmarg's d_t' and bitmaps; lost: one int32 per record of q, parallel to DDrop.rec (nl_mask: the contigs' own classes)
+static MgPinDrop pdp_args(const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost) { MgPinDrop c = mg_args<MgPinDrop>(g, rq, r); c.path = qpath; c.lost = lost; return c; }
+void phxk_pindrop_trees(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, int nl_mask, void *stream) {
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_tree<decltype(nl)::value, MgPinDrop>), dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, pdp_args(g, rq, r, qpath, lost), *q); });
+}
+void phxk_pindrop_cand(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, int nl_mask, void *stream) {
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_cand<decltype(nl)::value, MgPinDrop>), dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, pdp_args(g, rq, r, qpath, lost), *q); });
+}
+void phxk_pindrop_fix(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, int nl_mask, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const MgPinDrop c = pdp_args(g, rq, r, qpath, lost);
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_rescan<decltype(nl)::value, MgPinDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, c, *q); });
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_cross<decltype(nl)::value, MgPinDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, c, *q); });
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_rec<decltype(nl)::value, MgPinDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, c, *q); });
+}
 // drop replacements (phx_replace.inc): a workgroup per contig
 void phxk_repl_pick(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream) {
     each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL(k_rp_pick<decltype(nl)::value>, dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, *g, *q, *r); });
