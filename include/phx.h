@@ -50,7 +50,8 @@ extern "C" {
  *        (addition, version unchanged) phx_curate_scenarios_flat — probe for the symbol;
  *        (additions, version unchanged) phx_redrops_flat, phx_redrops_ms, phx_redrop_stats — probe for the symbol
  *        (additions, version unchanged) phx_rereplacements_flat, phx_tap_rereplacement, phx_rereplacements_ms, phx_rereplacement_stats — probe for the symbol
- *        (additions, version unchanged) phx_pindrops_flat, phx_pindrops_ms, phx_pindrop_stats — probe for the symbol */
+ *        (additions, version unchanged) phx_pindrops_flat, phx_pindrops_ms, phx_pindrop_stats — probe for the symbol
+ *        (additions, version unchanged) phx_pinreplacements_flat, phx_tap_pinreplacement, phx_pinreplacements_ms, phx_pinreplacement_stats — probe for the symbol */
 #define PHX_MAX_CODONS 16
 
 /* library-level errors */
@@ -615,6 +616,36 @@ int phx_pindrops_flat(phx_ctx *ctx, phx_gene_drop *rec, int32_t *lost, int64_t c
  * the contigs solved under the required policy plus phx_redrops_ms / phx_redrop_stats' over the others. */
 int phx_pindrops_ms(phx_ctx *ctx, float *ms /* [4] */);
 int phx_pindrop_stats(phx_ctx *ctx, int64_t *out /* [4] */);
+
+/* ---- pinned replacements: the best path without each call, under required ORFs ----
+ * phx_rereplacements_flat for every re-annotation of the batch last run, phx_constrain_flat and phx_curate_flat with required ORFs included.
+ * For every record of phx_pindrops_flat with bypass = 1 of a contig solved under the required policy (status 0) a replacement path R'_g: a
+ * simple source -> target path of G'[R_n] — every edge an edge of the device graph, none an ORF edge the call refused — that does not visit
+ * the gene's stop node p_j, of weight exactly D'_{-g} in NL + 1 limbs under W' = W + B - M·[required]: it carries (the required ORFs on P')
+ * - lost required ORF edges, and S(R'_g) - S(P') is the integer whose rounding is the record's drop.  It leaves the re-annotation's path
+ * P' (phx_tap_repath) at one node before p_j, rejoins it at one node behind, and no node of the detour lies on P'.  Records are
+ * phx_gene_repl, unchanged, with a parallel int32 lost[]: drop / called / bypass / lost bit-equal to phx_pindrops_flat's, the removed and
+ * the added genes as for phx_replacements_flat, score the ORF's weight without the bias (-20 for a tRNA pair).  The bytes do not depend
+ * on the batch or on the create flags (tie rule of DESIGN.md §13 with "cost" read in the (lost, s) order).  Order, offsets, statuses and the
+ * PHX_E_STATE rule (only without a re-annotation of this run) are phx_pindrops_flat's.  A contig that was solved again without a required
+ * ORF has phx_rereplacements_flat's records and genes (those of the same call without the other contigs' required ORFs) and lost 0, one
+ * that was not solved again phx_replacements_flat's and lost 0, byte for byte but for gene_off; when no contig was solved under the
+ * required policy, the arrays are phx_rereplacements_flat's.  rec and lost are parallel, cap entries each (rec or genes NULL: size query;
+ * with rec, lost is needed); caps as phx_rereplacements_flat.  Computed at the first call after a re-annotation solve, on top of
+ * phx_pindrops_flat's computation, in buffers of its own; kept until the next solve or run.  Nothing the other entry points return changes:
+ * phx_redrops_flat, phx_rereplacements_flat and their taps keep refusing a solve with required ORFs.  (Additions, version unchanged: probe
+ * for the symbol.) */
+int phx_pinreplacements_flat(phx_ctx *ctx, phx_gene_repl *rec, int32_t *lost, int64_t cap, phx_gene *genes, int64_t gene_cap, int64_t *offsets /* [n+1] */,
+                             int32_t *status /* [n] */, int64_t *total, int64_t *gene_total);
+/* R'_g of record k of contig `contig` (k counts the contig's records of phx_pinreplacements_flat), as phx_tap_rereplacement: the prefix and
+ * the suffix are the re-annotation's path.  A contig solved again without a required ORF gives what phx_tap_rereplacement gives for it,
+ * one that was not solved again phx_tap_replacement's result. */
+int phx_tap_pinreplacement(phx_ctx *ctx, int32_t contig, int32_t k, int32_t *path, int32_t cap, int32_t *n_path);
+/* device time of the last computation, ms[3], and its counters, out[5], as phx_replacements_ms / phx_replacement_stats, both over the
+ * contigs that were solved again: the pinned kernels' over the contigs solved under the required policy plus phx_rereplacements_ms /
+ * phx_rereplacement_stats' over the others. */
+int phx_pinreplacements_ms(phx_ctx *ctx, float *ms /* [3] */);
+int phx_pinreplacement_stats(phx_ctx *ctx, int64_t *out /* [5] */);
 
 /* ---- scenario batches: many masked re-annotations of the batch last run in one call ----
  * n_scen scenarios, each a contig of the batch last run and a set F of its ORFs, solved side by side on the resident graph, one

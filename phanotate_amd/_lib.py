@@ -192,6 +192,10 @@ def lib():
         "phx_pindrops_flat": (C.c_int, [vp, vp, vp, i64, vp, vp, P(i64)]),
         "phx_pindrops_ms": (C.c_int, [vp, P(C.c_float)]),
         "phx_pindrop_stats": (C.c_int, [vp, P(i64)]),
+        "phx_pinreplacements_flat": (C.c_int, [vp, vp, vp, i64, vp, i64, vp, vp, P(i64), P(i64)]),
+        "phx_tap_pinreplacement": (C.c_int, [vp, i32, i32, vp, i32, P(i32)]),
+        "phx_pinreplacements_ms": (C.c_int, [vp, P(C.c_float)]),
+        "phx_pinreplacement_stats": (C.c_int, [vp, P(i64)]),
         "phx_scenarios_flat": (C.c_int, [vp, i64, vp, vp, vp, vp, C.c_uint32, vp, i64, vp, vp, vp, P(i64)]),
         "phx_pinned_scenarios_flat": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, i64, vp, vp, vp, vp, P(i64)]),
         "phx_evidence_scenarios_flat": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, i64, vp, vp, vp, P(i64)]),
@@ -248,4 +252,5 @@ EXPORTS = ["phx_version", "phx_device_count", "phx_strerror", "phx_last_error", 
            "phx_pinmargins_flat", "phx_pinmargins_ms", "phx_tap_pindist",
            "phx_redrops_flat", "phx_redrops_ms", "phx_redrop_stats",
            "phx_rereplacements_flat", "phx_tap_rereplacement", "phx_rereplacements_ms", "phx_rereplacement_stats",
-           "phx_pindrops_flat", "phx_pindrops_ms", "phx_pindrop_stats"]
+           "phx_pindrops_flat", "phx_pindrops_ms", "phx_pindrop_stats",
+           "phx_pinreplacements_flat", "phx_tap_pinreplacement", "phx_pinreplacements_ms", "phx_pinreplacement_stats"]

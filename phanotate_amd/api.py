@@ -75,6 +75,7 @@ _MS_KEYS = {
     "phx_redrops_ms": ("trees", "candidates", "fixups", "download"),
     "phx_pindrops_ms": ("trees", "candidates", "fixups", "download"),
     "phx_rereplacements_ms": ("argmin", "walk", "download"),
+    "phx_pinreplacements_ms": ("argmin", "walk", "download"),
     "phx_reannotate_ms": ("mask", "solve", "finish"),
 }
 
@@ -1026,6 +1027,38 @@ class Annotator:
         out = (C.c_int64 * 4)()
         self._chk(self.L.phx_pindrop_stats(self.h, out), "phx_pindrop_stats")
         return dict(zip(("slots", "cross", "rescanned", "layered"), [int(x) for x in out]))
+
+    def pinreplacements(self):
+        """(status int32[n], offsets int64[n+1], records structured array[total] of _lib.REPL_DT, genes structured array of _lib.GENE_DT,
+        lost int32[total]): rereplacements() for every re-annotation of the batch last run, constrain() and curate() with required ORFs
+        included (phx_pinreplacements_flat).  For every record of pindrops() (same order, statuses and offsets; drop,
+        called, bypass and lost bit-equal) what the best annotation under the same mask, evidence and pins calls instead when nothing is
+        called at the gene's stop: the genes curate(bias, forbid + the ORFs of the gene's stop group, require - them) would return,
+        without that solve.  Where lost > 0 the replacement carries that many kept required ORFs fewer.  Elsewhere the records are
+        rereplacements()' (replacements()' for a contig that was not solved again) and lost is 0.  PhxError (PHX_E_STATE) only without a
+        re-annotation of this run."""
+        (status,), offs, (rec, lost, genes) = self._query_fill(self.L.phx_pinreplacements_flat, "phx_pinreplacements_flat", (), self.n,
+                                                               (_lib.REPL_DT, np.int32, _lib.GENE_DT), "rrcrc")
+        return status, offs, rec, genes, lost
+
+    def pinreplacement_path(self, i, k):
+        """R'_g of record k of contig i (pinreplacements()[2][offsets[i] + k]): device node ids, source first, the re-annotation's path
+        (reannotated_path(i)) around the detour; empty when bypass = 0.  A contig that was not solved again gives replacement_path(i, k)."""
+        n = C.c_int32()
+        self._chk(self.L.phx_tap_pinreplacement(self.h, i, k, None, 0, C.byref(n)), "phx_tap_pinreplacement")
+        p = np.zeros(max(n.value, 1), np.int32)
+        self._chk(self.L.phx_tap_pinreplacement(self.h, i, k, p.ctypes.data_as(C.c_void_p), len(p), C.byref(n)), "phx_tap_pinreplacement")
+        return p[: n.value].copy()
+
+    def pinreplacements_ms(self):
+        """Device time of the last pinned replacements in ms: argmin, walk + genes, copy to the host (phx_pinreplacements_ms)."""
+        return self._ms("phx_pinreplacements_ms")
+
+    def pinreplacement_stats(self):
+        """replacement_stats() of the last pinned replacements, over the contigs that were solved again (phx_pinreplacement_stats)."""
+        out = (C.c_int64 * 5)()
+        self._chk(self.L.phx_pinreplacement_stats(self.h, out), "phx_pinreplacement_stats")
+        return dict(zip(("cross", "chain_nodes", "cross_kept", "cut", "regrown"), [int(x) for x in out]))
 
     def pindist(self, i, to_target=False):
         """redist(i, to_target) for every re-annotation (phx_tap_pindist).  A contig solved with required ORFs gives per node None

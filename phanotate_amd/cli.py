@@ -57,6 +57,7 @@ def get_args(argv=None):
     p.add_argument("--redrop-replacements", metavar="FILE", default=None, help="also write every gene of the second annotation with what the best path under the same --forbid / --evidence that calls nothing at its stop calls instead (DESIGN.md §30) to FILE, in the format of --drop-replacements; needs --reannotation, not with --require")
     p.add_argument("--pin-margins", metavar="FILE", default=None, help="also write every ORF with its path margin and the kept ORFs of --require that the best path through it gives up (DESIGN.md §24) to FILE: the format of --margins with a LOST column behind MARGIN; needs --require and --reannotation")
     p.add_argument("--pin-drop-margins", metavar="FILE", default=None, help="also write every gene of the second annotation with its drop margin under the ORFs of --require — the cost of the best annotation that calls nothing at its stop, and the kept ORFs of --require that annotation gives up (DESIGN.md §32) — to FILE: the format of --drop-margins with a LOST column behind DROP; needs --require and --reannotation")
+    p.add_argument("--pin-drop-replacements", metavar="FILE", default=None, help="also write every gene of the second annotation with what the best annotation under the ORFs of --require that calls nothing at its stop calls instead, and the kept ORFs of --require it gives up (DESIGN.md §33), to FILE: the format of --drop-replacements with a LOST column behind DROP; needs --require and --reannotation")
     p.add_argument("--single-device-ranks", action="store_true", help=argparse.SUPPRESS)  # tests: every rank of a sharded launch on GPU `--device` (gloo-only group)
     args = p.parse_args(argv)
     for applies, message in _refusals(args, int(os.environ.get("WORLD_SIZE", "1"))):
@@ -78,13 +79,15 @@ _RULES = (
     ("pin_margins", lambda a: a.reannotation is None, "argument --pin-margins: needs --reannotation"),
     ("pin_drop_margins", lambda a: a.require is None, "argument --pin-drop-margins: needs --require"),
     ("pin_drop_margins", lambda a: a.reannotation is None, "argument --pin-drop-margins: needs --reannotation"),
+    ("pin_drop_replacements", lambda a: a.require is None, "argument --pin-drop-replacements: needs --require"),
+    ("pin_drop_replacements", lambda a: a.reannotation is None, "argument --pin-drop-replacements: needs --reannotation"),
     ("evidence", lambda a: a.require is not None, "argument --evidence: not allowed with argument --require"),  # (required sets and biases in one solve: DESIGN.md §19, Limits)
     ("evidence", lambda a: a.reannotation is None, "argument --evidence: needs --reannotation"),
     (None, lambda a: a.require is None and a.evidence is None and (a.forbid is None) != (a.reannotation is None), "arguments --forbid and --reannotation: each needs the other"),
     ("require", lambda a: a.reannotation is None, "argument --require: needs --reannotation"),
 )
 # The flags of OUTPUTS and INPUTS in the order get_args looks at them.
-_CHECK_ORDER = ("margins", "drop_margins", "drop_replacements", "start_drops", "alt_starts", "evidence_scan", "curated_scan", "remargins", "redrop_margins", "redrop_replacements", "pin_margins", "pin_drop_margins", "forbid", "require", "evidence", "reannotation")
+_CHECK_ORDER = ("margins", "drop_margins", "drop_replacements", "start_drops", "alt_starts", "evidence_scan", "curated_scan", "remargins", "redrop_margins", "redrop_replacements", "pin_margins", "pin_drop_margins", "pin_drop_replacements", "forbid", "require", "evidence", "reannotation")
 
 
 def _refusals(args, world):
@@ -134,6 +137,24 @@ def format_pin_drops(names, status, offsets, records, lost):
         rec, lo = records[cut], lost[cut]
         for k in range(len(rec)):
             out.append("%d\t%d\t%s\t" % _ends(rec[k]) + "%s\t%E\t%E\t%d\t%d\n" % (nm, float(rec["score"][k]), float(rec["drop"][k]), int(lo[k]), 1 if rec["called"][k] else 0))
+    return "".join(out).encode()
+
+
+def format_pin_replacements(names, status, offsets, records, genes, lost):
+    """--pin-drop-replacements FILE for a run of contigs, as bytes: format_replacements' block with a LOST column behind DROP — per contig
+    with status >= 0 "#id:\t<name>", the header, one row per called gene of the re-annotation's device path (START STOP FRAME CONTIG DROP
+    LOST REMOVED ADDED), in path order; records[k]["gene_off"] indexes genes, `lost` is parallel to `records`
+    (Annotator.pinreplacements())."""
+    def listed(gs):
+        return ",".join("%s%d..%d" % (("tRNA:" if abs(int(g["frame"])) == 4 else "",) + _ends(g)[:2]) for g in gs) or "-"
+
+    out = []
+    for nm, cut in _blocks(names, status, offsets):
+        out.append("#id:\t%s\n#START\tSTOP\tFRAME\tCONTIG\tDROP\tLOST\tREMOVED\tADDED\n" % nm)
+        rec, lo = records[cut], lost[cut]
+        for k in range(len(rec)):
+            g0, g1 = int(rec["gene_off"][k]), int(rec["gene_off"][k]) + int(rec["n_removed"][k])
+            out.append("%d\t%d\t%s\t" % _ends(rec[k]) + "%s\t%E\t%d\t%s\t%s\n" % (nm, float(rec["drop"][k]), int(lo[k]), listed(genes[g0:g1]), listed(genes[g1:g1 + int(rec["n_added"][k])])))
     return "".join(out).encode()
 
 
@@ -379,13 +400,13 @@ def _merge(parts):
 
 
 def _merge_replacements(parts):
-    """_merge for Annotator.replacements(): each batch's gene_off counts from its own genes."""
+    """_merge for Annotator.replacements(): each batch's gene_off counts from its own genes.  (Further arrays, pinreplacements()' lost, as _merge has them.)"""
     shifted, g0 = [], 0
-    for status, offsets, records, genes in parts:
+    for status, offsets, records, genes, *more in parts:
         records = records.copy()
         records["gene_off"] += g0
         g0 += len(genes)
-        shifted.append((status, offsets, records, genes))
+        shifted.append((status, offsets, records, genes, *more))
     return _merge(shifted)
 
 
@@ -452,6 +473,7 @@ OUTPUTS = {o.dest: o for o in (
     _out("--redrop-replacements", format_replacements, "wb", lambda ann, entries: ann.rereplacements(), resident=True, merge=_merge_replacements),
     _out("--pin-margins", format_pin_margins, "wb", lambda ann, entries: ann.pinmargins(), resident=True),
     _out("--pin-drop-margins", format_pin_drops, "wb", lambda ann, entries: ann.pindrops(), resident=True),
+    _out("--pin-drop-replacements", format_pin_replacements, "wb", lambda ann, entries: ann.pinreplacements(), resident=True, merge=_merge_replacements),
     _out("--drop-margins", format_drops, "wb", lambda ann, entries: ann.drop_margins(), piped="drop_margins"),
     _out("--drop-replacements", format_replacements, "wb", lambda ann, entries: ann.replacements(), piped="replacements", merge=_merge_replacements),
     _out("--start-drops", format_start_drops, "w", lambda ann, entries: ann.start_drops()[:3], resident=True),
@@ -463,9 +485,10 @@ OUTPUTS = {o.dest: o for o in (
 # A batch's fetches, in this order.  THE ORDER IS CONTRACT: the replacements in front of the drop margins (the drops are then computed
 # once); the curated scan behind the batch's re-annotation, which thereby stays the cached one; remargins, the re-annotation's drop
 # margins, its replacements (behind its drop margins: an existing order; the trees are then built once more), pinmargins
-# and the pinned drop margins (behind pinmargins, which they build on) behind the re-annotation, whose margins they are.  The entry files are resolved where a fetch first needs them, so a line that names no ORF is
+# and the pinned drop margins (behind pinmargins, which they build on) behind the re-annotation, whose margins they are, the pinned
+# replacements behind the pinned drop margins (as the re-annotation's: the trees are then built once more).  The entry files are resolved where a fetch first needs them, so a line that names no ORF is
 # reported in the order --evidence-scan, --forbid, --evidence or --require, --curated-scan.
-_FETCH_ORDER = ("margins", "drop_replacements", "drop_margins", "start_drops", "alt_starts", "evidence_scan", "reannotation", "curated_scan", "remargins", "redrop_margins", "redrop_replacements", "pin_margins", "pin_drop_margins")
+_FETCH_ORDER = ("margins", "drop_replacements", "drop_margins", "start_drops", "alt_starts", "evidence_scan", "reannotation", "curated_scan", "remargins", "redrop_margins", "redrop_replacements", "pin_margins", "pin_drop_margins", "pin_drop_replacements")
 # The entry files in the order main looks for a line that names a contig the FASTA file does not hold.
 _UNKNOWN_ORDER = ("forbid", "require", "evidence", "evidence_scan", "curated_scan")
 assert set(_CHECK_ORDER) == set(OUTPUTS) | set(INPUTS) and set(_FETCH_ORDER) == set(OUTPUTS) and set(_UNKNOWN_ORDER) == set(INPUTS)  # a new row takes its place in each order

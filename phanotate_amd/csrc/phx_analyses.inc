@@ -448,8 +448,9 @@ static int ensure_replacements(phx_ctx *c) {
 }
 
 // The layout both flat calls share: the records of contig i (device records [k0, k1) of S, those of CDS genes) to dst, `called` from the
-// drop records dd they go with, their genes appended to `genes` at *go, gene_off rebased.
-static void replacement_rows(const phx_ctx::ReplSet &S, int64_t k0, int64_t k1, const phx_gene_drop *dd, phx_gene_repl *dst, phx_gene *genes, int64_t *go) {
+// drop records dd they go with, their genes appended to `genes` at *go, gene_off rebased.  (lost: null, or where the rows' `lost` go — a set
+// without one gives 0)
+static void replacement_rows(const phx_ctx::ReplSet &S, int64_t k0, int64_t k1, const phx_gene_drop *dd, phx_gene_repl *dst, phx_gene *genes, int64_t *go, int32_t *lost = nullptr) {
     for (int64_t k = k0; k < k1; k++) {
         const phx_gene_repl &x = S.h_rec[(size_t)k];
         if (x.called < 0) continue;
@@ -460,6 +461,7 @@ static void replacement_rows(const phx_ctx::ReplSet &S, int64_t k0, int64_t k1, 
         if (ng) memcpy(genes + *go, S.h_genes.data() + x.gene_off, (size_t)ng * sizeof(phx_gene));
         *go += ng;
         dst++; dd++;
+        if (lost) *lost++ = S.h_lost.empty() ? 0 : S.h_lost[(size_t)k];
     }
 }
 static int64_t replacement_genes(const phx_ctx::ReplSet &S, int64_t k0, int64_t k1) {
@@ -755,6 +757,7 @@ static int reann_flat(phx_ctx *c, const char *who, bool need_forbid, const uint8
         c->done.pinmarg = false;
         c->done.pindrop = false;
         c->done.pintrees = false;
+        c->done.pinrepl = false;
         c->done.redrop = false;
         c->done.retrees = false;
         c->done.rerepl = false;
@@ -1161,32 +1164,41 @@ int phx_redrop_stats(phx_ctx *c, int64_t *out) { return values_out<4>(c, out, []
 // the contigs the pinned drop kernels cover (dp_on<MgPinDrop>), after ensure_condmargins<CmPin>
 static bool pindrop_contig(const phx_ctx *c, size_t i) { return re_mode_req(c->h_qsel[i]) && c->pm.h_sel[i] == 1 && !c->pm.mstat[i] && c->h_qrec[i].n_path >= 3; }
 
+// the pinned kernels' view of what the last re-annotation and its pinned margins left resident (after ensure_condmargins<CmPin>)
+struct PindropView {
+    DBatch b, qb;
+    DMarg g;
+    DReann rq;
+    DPmarg r;
+    const int32_t *qpath;
+};
+static void pindrop_view(phx_ctx *c, PindropView *v) {
+    fill_batch(c, &v->b);
+    margins_args(c, &v->g);
+    reann_batch(c, &v->qb, &v->rq);
+    const size_t mw = (size_t)c->tot_edge / 32 + 2;
+    condmargins_args(c, c->pm, mw, &v->r);
+    v->r.dt_stride = v->b.dist_stride + 1; v->r.rbit = v->r.fbit + 2 * mw; v->r.lost = (int32_t *)c->pm.b_lost.p; // (as ensure_condmargins<CmPin> laid them out)
+    v->qpath = (const int32_t *)c->b_qpath.p;
+}
 // The pinned set, once per re-annotation solve.  On top of the pinned margins (the three out-edge bitmaps, d_t' on one limb more and the
 // pass's verdicts), of the re-annotation drop margins for the contigs solved again without a required ORF and, through them, of the run's
-// for the contigs that were not solved again.  Reads what the solve and its margins left resident; writes only c->pd.
-static int ensure_pindrops(phx_ctx *c) {
-    if (c->done.pindrop) return PHX_OK;
+// for the contigs that were not solved again.  Reads what the solve and its margins left resident; writes only c->pd (trees: with the
+// one-hop trees pd.b_ps / b_ts, for the pinned replacements — a set computed without them gets k_dp_tree once more, counting into c->pr).
+static int ensure_pindrops(phx_ctx *c, bool trees = false) {
+    if (c->done.pindrop && (!trees || c->done.pintrees)) return PHX_OK;
     { const int rm = ensure_condmargins<CmPin>(c); if (rm) return rm; }
     { const int rd = ensure_redrops(c); if (rd) return rd; }
     phx_ctx::DropSet &D = c->pd;
     D.wide = 1;
-    DBatch b, qb;
-    fill_batch(c, &b);
-    DMarg g;
-    margins_args(c, &g);
-    DReann rq;
-    reann_batch(c, &qb, &rq);
-    DPmarg r;
-    const size_t mw = (size_t)c->tot_edge / 32 + 2;
-    condmargins_args(c, c->pm, mw, &r);
-    r.dt_stride = b.dist_stride + 1; r.rbit = r.fbit + 2 * mw; r.lost = (int32_t *)c->pm.b_lost.p; // (as ensure_condmargins<CmPin> laid them out)
-    const int32_t *qpath = (const int32_t *)c->b_qpath.p;
+    PindropView v;
+    pindrop_view(c, &v);
     hipStream_t s = c->stream;
-    return drop_pass(c, D, c->rr, c->done.pindrop, c->done.pintrees, false, [&](size_t i) { return pindrop_contig(c, i) ? c->h_qrec[i].n_path : 0; }, [&](int step, const DDrop &q) {
+    return drop_pass(c, D, c->pr, c->done.pindrop, c->done.pintrees, trees, [&](size_t i) { return pindrop_contig(c, i) ? c->h_qrec[i].n_path : 0; }, [&](int step, const DDrop &q) {
         int32_t *lost = (int32_t *)D.b_lost.p;
-        if (step == 0) phxk_pindrop_trees(&b, &g, &rq, &r, qpath, lost, &q, D.nlm, s);
-        else if (step == 1) phxk_pindrop_cand(&b, &g, &rq, &r, qpath, lost, &q, D.nlm, s);
-        else phxk_pindrop_fix(&b, &g, &rq, &r, qpath, lost, &q, D.nlm, s);
+        if (step == 0) phxk_pindrop_trees(&v.b, &v.g, &v.rq, &v.r, v.qpath, lost, &q, D.nlm, s);
+        else if (step == 1) phxk_pindrop_cand(&v.b, &v.g, &v.rq, &v.r, v.qpath, lost, &q, D.nlm, s);
+        else phxk_pindrop_fix(&v.b, &v.g, &v.rq, &v.r, v.qpath, lost, &q, D.nlm, s);
     });
 }
 
@@ -1327,6 +1339,108 @@ int phx_tap_rereplacement(phx_ctx *c, int32_t contig, int32_t k, int32_t *path, 
 
 int phx_rereplacements_ms(phx_ctx *c, float *ms) { return values_out<3>(c, ms, [](const phx_ctx *x) { return x->rr.ms; }); }
 int phx_rereplacement_stats(phx_ctx *c, int64_t *out) { return values_out<5>(c, out, [](const phx_ctx *x) { return x->rr.stats; }); }
+
+// ---- pinned replacements (phx_replace.inc under MgPinDrop, DESIGN.md §33) ----
+// Every record of pd.h_rec gets its replacement into c->pr (h_rec / h_genes / h_det at pd.roff's indices, `lost` from pd.h_lost beside them),
+// once per re-annotation solve, on top of ensure_pindrops with the one-hop trees and of the replacements of the contigs the pinned kernels do
+// not cover (§30's for modes 1 / 3, §13's for a contig that was not solved again).  Writes the pr set and pd.b_ps / b_ts only (and, as §13
+// does on its own set, the scratch the drop kernels left: js / jt / gtab of pd).
+// k_rp_walk follows DDrop.ps / ts until it meets a path node, so it may run only on trees k_dp_tree<NL, MgPinDrop> wrote for this solve: the
+// launch below is reached only with done.pintrees set by drop_pass and with both pointers of the DDrop it passes non-null — the flag is
+// reset with done.pindrop, and drop_args gives the pointers for `trees` alone.
+static int ensure_pinreplacements(phx_ctx *c) {
+    if (c->done.pinrepl) return PHX_OK;
+    { const int rd = ensure_pindrops(c, true); if (rd) return rd; }
+    { const int rr = ensure_rereplacements(c); if (rr) return rr; } // (modes 1 / 3; the run's replacements when a contig was not solved again; rr's times and counters are this solve's)
+    phx_ctx::ReplSet &S = c->pr;
+    for (int k = 0; k < 3; k++) S.ms[k] = 0;
+    for (int k = 0; k < 5; k++) S.stats[k] = 0;
+    S.h_lost.clear();
+    const int nlm = c->pd.nlm;
+    if (!nlm) { c->done.pinrepl = true; return PHX_OK; } // (no pinned contig with a path: nothing is allocated)
+    DDrop q;
+    drop_args(c->pd, true, &q);
+    if (!c->done.pindrop || !c->done.pintrees || !q.ps || !q.ts) { c->err = "pinned replacements: the pinned drop margins kept no one-hop trees"; return PHX_E_STATE; }
+    PindropView v;
+    pindrop_view(c, &v);
+    int32_t *lost = (int32_t *)c->pd.b_lost.p;
+    hipStream_t s = c->stream;
+    const size_t R = (size_t)c->pd.roff[(size_t)c->n];
+    const int rc = replacement_pass(c, S, R, [&](int step, const DRepl &r) {
+        if (step == 0) phxk_pinrepl_pick(&v.b, &v.g, &v.rq, &v.r, v.qpath, lost, &q, &r, nlm, s);
+        else if (step == 1) phxk_pinrepl_cross(&v.b, &v.g, &v.rq, &v.r, v.qpath, lost, &q, &r, nlm, s);
+        else phxk_pinrepl_walk(&v.b, &v.g, &v.rq, &v.r, v.qpath, lost, &q, &r, step - 2, s);
+    }, "pinned replacements", "phx_pinreplacements_flat");
+    if (rc) return rc;
+    try { S.h_lost.assign(c->pd.h_lost.begin(), c->pd.h_lost.begin() + (ptrdiff_t)R); } catch (const std::bad_alloc &) { c->err = "out of memory in phx_pinreplacements_flat"; return PHX_E_NOMEM; }
+    c->done.pinrepl = true;
+    return PHX_OK;
+}
+
+// the replacement set contig i's records are in, and their place in it: pr over pd's records (modes 2 / 4), rr over rd's (1 / 3), rp over dp's (0)
+static phx_ctx::ReplSet &pinrepl_set(phx_ctx *c, size_t i, int64_t *k0, int64_t *k1) {
+    const int mode = c->h_qsel[i];
+    const std::vector<int64_t> &ro = re_mode_req(mode) ? c->pd.roff : (mode ? c->rd.roff : c->dp.roff);
+    *k0 = ro[i]; *k1 = ro[i + 1];
+    return re_mode_req(mode) ? c->pr : (mode ? c->rr : c->rp);
+}
+
+int phx_pinreplacements_flat(phx_ctx *c, phx_gene_repl *rec, int32_t *lost, int64_t cap, phx_gene *genes, int64_t gene_cap, int64_t *offsets, int32_t *status,
+                             int64_t *total_out, int64_t *gene_total_out) {
+    if (!c || (c->n > 0 && (!offsets || !status)) || (rec && !lost)) return PHX_E_ARG;
+    { const int ra = after_run(c); if (ra) return ra; }
+    if (!c->done.reann) { c->err = "phx_pinreplacements_flat: no re-annotation of this run (call phx_constrain_flat or phx_curate_flat first)"; return PHX_E_STATE; } // before any kernel
+    { const int rr = ensure_pinreplacements(c); if (rr) return rr; }
+    // statuses, offsets, `called` and `lost` exactly as the pinned drop records have them
+    int64_t total = 0;
+    { const int rd = phx_pindrops_flat(c, nullptr, nullptr, 0, offsets, status, &total); if (rd) return rd; }
+    try {
+    std::vector<phx_gene_drop> drec((size_t)total + 1);
+    std::vector<int32_t> dlost((size_t)total + 1);
+    { const int rd = phx_pindrops_flat(c, drec.data(), dlost.data(), total, offsets, status, &total); if (rd) return rd; }
+    int64_t gt = 0, k0, k1;
+    for (int i = 0; i < c->n; i++)
+        if (offsets[i + 1] != offsets[i]) { const phx_ctx::ReplSet &S = pinrepl_set(c, (size_t)i, &k0, &k1); gt += replacement_genes(S, k0, k1); }
+    if (total_out) *total_out = total;
+    if (gene_total_out) *gene_total_out = gt;
+    if (!rec || !genes) return PHX_OK; // size query
+    if (cap < total || gene_cap < gt) return PHX_E_ARG;
+    int64_t go = 0;
+    for (int i = 0; i < c->n; i++)
+        if (offsets[i + 1] != offsets[i]) { const phx_ctx::ReplSet &S = pinrepl_set(c, (size_t)i, &k0, &k1); replacement_rows(S, k0, k1, drec.data() + offsets[i], rec + offsets[i], genes, &go, lost + offsets[i]); }
+    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_pinreplacements_flat"; return PHX_E_NOMEM; }
+    return PHX_OK;
+}
+
+int phx_tap_pinreplacement(phx_ctx *c, int32_t contig, int32_t k, int32_t *path, int32_t cap, int32_t *n_path) {
+    if (!c || !n_path) return PHX_E_ARG;
+    *n_path = 0;
+    { const int ra = after_run(c); if (ra) return ra; }
+    if (contig < 0 || contig >= c->n || k < 0) return PHX_E_ARG;
+    if (!c->done.reann) { c->err = "phx_tap_pinreplacement: no re-annotation of this run (call phx_constrain_flat or phx_curate_flat first)"; return PHX_E_STATE; }
+    const int mode = c->h_qsel[(size_t)contig];
+    if (!mode) return phx_tap_replacement(c, contig, k, path, cap, n_path); // the run's result stands
+    { const int rr = ensure_pinreplacements(c); if (rr) return rr; }
+    // (a contig of mode 1 / 3: §30's tap on the rr set — phx_tap_rereplacement itself refuses a solve that pinned another contig)
+    if (!(re_mode_req(mode) ? pindrop_contig(c, (size_t)contig) : redrop_contig(c, (size_t)contig)) || condmargins_status(c, contig) != 0) return PHX_E_ARG;
+    int64_t k0, k1;
+    phx_ctx::ReplSet &S = pinrepl_set(c, (size_t)contig, &k0, &k1);
+    const DMeta &m = c->meta[(size_t)contig];
+    return replacement_tap(c, S, "phx_tap_pinreplacement", contig, k0, k1, k, (const int32_t *)c->b_qpath.p + m.node_off, c->h_qrec[(size_t)contig].n_path, path, cap, n_path);
+}
+
+// device time and counters of the last phx_pinreplacements_flat over the contigs that were solved again: the pinned pass's, plus §30's for the
+// contigs solved again without a required ORF (a batch without a pinned contig: phx_rereplacements_ms / phx_rereplacement_stats)
+int phx_pinreplacements_ms(phx_ctx *c, float *ms) {
+    float v[3];
+    if (c) for (int k = 0; k < 3; k++) v[k] = c->pr.ms[k] + c->rr.ms[k];
+    return values_out<3>(c, ms, [&](const phx_ctx *) { return v; });
+}
+int phx_pinreplacement_stats(phx_ctx *c, int64_t *out) {
+    int64_t v[5];
+    if (c) for (int k = 0; k < 5; k++) v[k] = c->pr.stats[k] + c->rr.stats[k];
+    return values_out<5>(c, out, [&](const phx_ctx *) { return v; });
+}
 
 // ---- scenario batches (phx_resolve.inc, DESIGN.md §17), with required ORFs (§18), biased ORFs (§20) or both (§27) per scenario ----
 // h_srec[j].status before the solve: the scenario gets a slot / its contig is not solved again and the run's verdict stands (neither is a status the device reports)

@@ -557,6 +557,10 @@ void phxk_repl_walk(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl
 void phxk_rerepl_pick(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, const DRepl *rr, int nl_mask, void *stream);
 void phxk_rerepl_cross(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, const DRepl *rr, int nl_mask, void *stream);
 void phxk_rerepl_walk(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, const DRepl *rr, int fill, void *stream);
+// pinned replacements (§33; the arguments of phxk_pindrop_*, q with DDrop.ps / ts, pr: the feature's own DRepl set): the three steps under MgPinDrop
+void phxk_pinrepl_pick(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, const DRepl *pr, int nl_mask, void *stream);
+void phxk_pinrepl_cross(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, const DRepl *pr, int nl_mask, void *stream);
+void phxk_pinrepl_walk(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, const DRepl *pr, int fill, void *stream);
 // re-annotation (phx_resolve.inc).  b: the re-annotation's view of the batch; nl_masks[RE_MODES]: per mode, the limb classes of its contigs
 void phxk_reann_mask(const DBatch *b, const DReann *q, void *stream);                         // the refused, required and biased ORFs' marks,
 void phxk_reann_solve(const DBatch *b, const DReann *q, const int *nl_masks, void *stream);   //   the sweep under each mode's policy,

@@ -520,6 +520,20 @@ void phxk_rerepl_walk(const DBatch *b, const DMarg *g, const DReann *rq, const D
     if (fill) hipLaunchKernelGGL((k_rp_walk<1, MgDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, dp_args(g, rq, r, qpath), *q, *rr);
     else hipLaunchKernelGGL((k_rp_walk<0, MgDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, dp_args(g, rq, r, qpath), *q, *rr);
 }
+// pinned replacements: the same three kernels under MgPinDrop, on the DDrop set of the pinned drop margins (q, with its
+// one-hop trees: the walk follows DDrop.ps / ts and is launched only behind a k_dp_tree<NL, MgPinDrop> that wrote them) and a DRepl set of
+// the feature's own (pr); `lost` is k_dp_rec's and no kernel here writes it
+void phxk_pinrepl_pick(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, const DRepl *pr, int nl_mask, void *stream) {
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_rp_pick<decltype(nl)::value, MgPinDrop>), dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, pdp_args(g, rq, r, qpath, lost), *q, *pr); });
+}
+void phxk_pinrepl_cross(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, const DRepl *pr, int nl_mask, void *stream) {
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_rp_cross<decltype(nl)::value, MgPinDrop>), dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, pdp_args(g, rq, r, qpath, lost), *q, *pr); });
+}
+void phxk_pinrepl_walk(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, const DRepl *pr, int fill, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (fill) hipLaunchKernelGGL((k_rp_walk<1, MgPinDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, pdp_args(g, rq, r, qpath, lost), *q, *pr);
+    else hipLaunchKernelGGL((k_rp_walk<0, MgPinDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, pdp_args(g, rq, r, qpath, lost), *q, *pr);
+}
 size_t phxk_sssp_lds_bytes(int V, int nl) { return sssp_lds_bytes(V, nl); }
 // re-annotation (phx_resolve.inc): b is the re-annotation's view of the batch (outputs of its own)
 void phxk_reann_mask(const DBatch *b, const DReann *q, void *stream) { hipLaunchKernelGGL(k_rs_mask, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), 0, (hipStream_t)stream, *b, *q); }

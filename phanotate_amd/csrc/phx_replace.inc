@@ -20,18 +20,25 @@
 // of its drop margins (a second DDrop set, with its own one-hop trees), the outputs in a second DRepl set.  Every edge loop skips a refused
 // slot and adds the bias of a biased one exactly as k_dp_cand / k_dp_cross<NL, MgDrop> do, so the candidates are the same set; a node outside
 // R has no label and enters nothing.  k_rp_walk takes the path and its length from the policy and nothing else: a witness walks tree pointers.
+// MgPinDrop (the pinned replacements, DESIGN.md §33): the contigs solved under the required policy, the labels, minima and one-hop trees of
+// the pinned drop margins (the pd set), the outputs in a third DRepl set.  What dp_pin<G> adds is what it adds in phx_drop.inc: a value of
+// pick and cross has WL = NL + 1 limbs (d_s' / d_t' at WL words per node, the delta buffers, the slot minima at dp_stride words per record),
+// and dp_w_in / dp_w_out take one off the top limb of a required slot or position, so "cost" is the (lost, s) order of §32 in every compare.
+// The sparse table stays 64-bit: wi_sat64 is monotone in that order (lost > 0 saturates), and a saturated key is decided by the exact
+// compare at key == DP_SAT.  k_rp_walk reads node ids only and copies the drop record: `lost` stays where k_dp_rec wrote it.
 
 #define RP_CROSS (1ull << 63) // DRepl.win: a cross winner (y << 32 | z)
 #define RP_NONE (~0ull)
 
 // the exact minimum of gene slot j (record i) from the drop kernels' results: *s3 the step-3 part (inf: none), the return value min(s3, cx)
-template <int NL>
-__device__ __forceinline__ WInt<NL> rp_slot_min(const DBatch &b, const DDrop &q, size_t no, int64_t r0, int i, int j, WInt<NL> *s3) {
+// (W limbs per value, `stride` words reserved per record of DDrop.sx / cx: dp_wl / dp_stride of the caller's policy)
+template <int W>
+__device__ __forceinline__ WInt<W> rp_slot_min(const DDrop &q, size_t stride, size_t no, int64_t r0, int i, int j, WInt<W> *s3) {
     const uint64_t s = q.slot[no + j];
-    const WInt<NL> a = s == DP_SAT ? wi_load<NL>(q.sx + ((size_t)r0 + i) * b.dist_stride) : (s == DP_NONE ? wi_inf<NL>() : wi_from_u64<NL>(s));
-    const WInt<NL> c = wi_load<NL>(q.cx + ((size_t)r0 + i) * b.dist_stride);
+    const WInt<W> a = s == DP_SAT ? wi_load<W>(q.sx + ((size_t)r0 + i) * stride) : (s == DP_NONE ? wi_inf<W>() : wi_from_u64<W>(s));
+    const WInt<W> c = wi_load<W>(q.cx + ((size_t)r0 + i) * stride);
     *s3 = a;
-    return wi_lt<NL>(c, a) ? c : a;
+    return wi_lt<W>(c, a) ? c : a;
 }
 
 __device__ __forceinline__ void st_l2(uint64_t *p, uint64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -43,6 +50,7 @@ __device__ __forceinline__ void st_l2(uint64_t *p, uint64_t v) { __hip_atomic_st
 template <int NL, class G = DMarg>
 __global__ __launch_bounds__(NT) void k_rp_pick(DBatch b, G g, DDrop q, DRepl r) {
     constexpr bool COND = mg_cond<G>;
+    constexpr int WL = dp_wl<NL, G>;
     __shared__ unsigned long long s_tab[DP_TAB_LDS];
     const DMeta *meta = &b.meta[blockIdx.x];
     if (!dp_on<G>(b, g, meta) || meta->sssp_nl != NL) return;
@@ -69,9 +77,9 @@ __global__ __launch_bounds__(NT) void k_rp_pick(DBatch b, G g, DDrop q, DRepl r)
     for (int i = tid; i < np; i += NT) {
         int j, k;
         if (!dp_gene(b, meta, path, i, &j, &k)) continue;
-        WInt<NL> s3;
-        const WInt<NL> m = rp_slot_min<NL>(b, q, no, r0, i, j, &s3);
-        st_l2(&tab[j], wi_is_inf<NL>(m) ? DP_NONE : wi_sat64<NL>(m));
+        WInt<WL> s3;
+        const WInt<WL> m = rp_slot_min<WL>(q, dp_stride<G>(b, g), no, r0, i, j, &s3);
+        st_l2(&tab[j], wi_is_inf<WL>(m) ? DP_NONE : wi_sat64<WL>(m));
     }
     __syncthreads();
     for (int k = 1; k < lv; k++) {
@@ -82,11 +90,11 @@ __global__ __launch_bounds__(NT) void k_rp_pick(DBatch b, G g, DDrop q, DRepl r)
         }
         __syncthreads();
     }
-    const WInt<NL> negD = wi_neg<NL>(wi_load<NL>(ds + (size_t)(V - 1) * NL));
+    const WInt<WL> negD = wi_neg<WL>(wi_load<WL>(ds + (size_t)(V - 1) * WL));
     for (int z = tid; z < V; z += NT) {
         const int lz = last[z];
         if (lz < 2) continue;
-        const WInt<NL> tz = wi_add<NL>(wi_load<NL>(dt + (size_t)z * NL), negD);
+        const WInt<WL> tz = wi_add<WL>(wi_load<WL>(dt + (size_t)z * WL), negD);
         [[maybe_unused]] bool sp = false;
         if constexpr (COND) sp = dp_sp_in(g, biased, ebase, in_off[z], in_off[z + 1]);
         for (uint32_t e = in_off[z], e1 = in_off[z + 1]; e < e1; e++) {
@@ -96,8 +104,8 @@ __global__ __launch_bounds__(NT) void k_rp_pick(DBatch b, G g, DDrop q, DRepl r)
             if (fx < 0 || fx + 1 > lz - 1) continue;
             if constexpr (COND) { if (sp && mg_bit(g.q.mask, ebase + e)) continue; }
             const int a = fx + 1, e2 = lz - 1, k = 31 - __clz(e2 - a + 1);
-            const WInt<NL> c = wi_add<NL>(wi_add<NL>(wi_load<NL>(ds + (size_t)x * NL), dp_w_in<NL>(g, sp, biased, ebase + e, ew_decode<NL>(edge_wenc(sw, ew, e, gt)))), tz);
-            const uint64_t key = wi_sat64<NL>(c);
+            const WInt<WL> c = wi_add<WL>(wi_add<WL>(wi_load<WL>(ds + (size_t)x * WL), dp_w_in<WL>(g, sp, biased, ebase + e, ew_decode<WL>(edge_wenc(sw, ew, e, gt)))), tz);
+            const uint64_t key = wi_sat64<WL>(c);
             const uint64_t m1 = ld_l2(&tab[k * n + a]), m2 = ld_l2(&tab[k * n + e2 - (1 << k) + 1]);
             if (key != (m1 > m2 ? m1 : m2)) continue; // not the range maximum: above every slot it covers
             for (int jj = a; jj <= e2; jj++) {
@@ -105,7 +113,7 @@ __global__ __launch_bounds__(NT) void k_rp_pick(DBatch b, G g, DDrop q, DRepl r)
                 const int i = (jj - 1) >> 1;
                 int j, ko;
                 if (!dp_gene(b, meta, path, i, &j, &ko) || j != jj) continue;
-                if (key == DP_SAT) { WInt<NL> s3; if (!wi_eq<NL>(rp_slot_min<NL>(b, q, no, r0, i, j, &s3), c)) continue; }
+                if (key == DP_SAT) { WInt<WL> s3; if (!wi_eq<WL>(rp_slot_min<WL>(q, dp_stride<G>(b, g), no, r0, i, j, &s3), c)) continue; }
                 atomicMin((unsigned long long *)&r.win[r0 + i], (unsigned long long)(((uint64_t)x << 32) | (uint32_t)z));
             }
         }
@@ -119,7 +127,8 @@ __global__ __launch_bounds__(NT) void k_rp_pick(DBatch b, G g, DDrop q, DRepl r)
 template <int NL, class G = DMarg>
 __global__ __launch_bounds__(NT) void k_rp_cross(DBatch b, G g, DDrop q, DRepl r) {
     constexpr bool COND = mg_cond<G>;
-    __shared__ uint64_t s_d[2][DP_CROSS_LDS * NL];
+    constexpr int WL = dp_wl<NL, G>;
+    __shared__ uint64_t s_d[2][DP_CROSS_LDS * WL];
     __shared__ int s_nc, s_chg;
     __shared__ unsigned long long s_key;
     const DMeta *meta = &b.meta[blockIdx.x];
@@ -153,20 +162,20 @@ __global__ __launch_bounds__(NT) void k_rp_cross(DBatch b, G g, DDrop q, DRepl r
     __syncthreads();
     const int nc = s_nc;
     if (!nc) return;
-    uint64_t *bufA = nc <= DP_CROSS_LDS ? s_d[0] : q.da + no * b.dist_stride, *bufB = nc <= DP_CROSS_LDS ? s_d[1] : q.db + no * b.dist_stride;
-    const WInt<NL> negD = wi_neg<NL>(wi_load<NL>(ds + (size_t)(V - 1) * NL));
+    uint64_t *bufA = nc <= DP_CROSS_LDS ? s_d[0] : q.da + no * dp_stride<G>(b, g), *bufB = nc <= DP_CROSS_LDS ? s_d[1] : q.db + no * dp_stride<G>(b, g);
+    const WInt<WL> negD = wi_neg<WL>(wi_load<WL>(ds + (size_t)(V - 1) * WL));
     for (int i = 0; i < np; i++) {
         int j, k;
         if (!dp_gene(b, meta, path, i, &j, &k)) continue; // (uniform over the workgroup)
-        WInt<NL> s3;
-        const WInt<NL> m = rp_slot_min<NL>(b, q, no, r0, i, j, &s3);
-        if (wi_is_inf<NL>(m) || !wi_lt<NL>(m, s3)) continue; // a step-3 candidate attains it (or no bypass)
+        WInt<WL> s3;
+        const WInt<WL> m = rp_slot_min<WL>(q, dp_stride<G>(b, g), no, r0, i, j, &s3);
+        if (wi_is_inf<WL>(m) || !wi_lt<WL>(m, s3)) continue; // a step-3 candidate attains it (or no bypass)
         if (tid == 0) s_key = RP_NONE;
         __syncthreads();
         auto in_y = [&](int y) { return cpos[y] >= 0 && last[y] <= j && j <= first[y]; };
         for (int p = tid; p < nc; p += NT) {
             const int y = clist[p];
-            WInt<NL> d = wi_inf<NL>();
+            WInt<WL> d = wi_inf<WL>();
             [[maybe_unused]] bool sp = false;
             if constexpr (COND) { if (in_y(y)) sp = dp_sp_in(g, biased, ebase, in_off[y], in_off[y + 1]); }
             if (in_y(y))
@@ -176,10 +185,10 @@ __global__ __launch_bounds__(NT) void k_rp_cross(DBatch b, G g, DDrop q, DRepl r
                     const int fx = first[x];
                     if (fx < 0 || fx >= j) continue;
                     if constexpr (COND) { if (sp && mg_bit(g.q.mask, ebase + e)) continue; }
-                    const WInt<NL> c = wi_add<NL>(wi_load<NL>(ds + (size_t)x * NL), dp_w_in<NL>(g, sp, biased, ebase + e, ew_decode<NL>(edge_wenc(sw, ew, e, gt))));
-                    if (wi_lt<NL>(c, d)) d = c;
+                    const WInt<WL> c = wi_add<WL>(wi_load<WL>(ds + (size_t)x * WL), dp_w_in<WL>(g, sp, biased, ebase + e, ew_decode<WL>(edge_wenc(sw, ew, e, gt))));
+                    if (wi_lt<WL>(c, d)) d = c;
                 }
-            wi_store<NL>(bufA + (size_t)p * NL, d);
+            wi_store<WL>(bufA + (size_t)p * WL, d);
             rnd[p] = 0;
         }
         __syncthreads();
@@ -189,7 +198,7 @@ __global__ __launch_bounds__(NT) void k_rp_cross(DBatch b, G g, DDrop q, DRepl r
             __syncthreads();
             for (int p = tid; p < nc; p += NT) {
                 const int y = clist[p];
-                WInt<NL> d = wi_load<NL>(cur + (size_t)p * NL);
+                WInt<WL> d = wi_load<WL>(cur + (size_t)p * WL);
                 [[maybe_unused]] bool sp = false;
                 if constexpr (COND) { if (in_y(y)) sp = dp_sp_in(g, biased, ebase, in_off[y], in_off[y + 1]); }
                 if (in_y(y))
@@ -198,12 +207,12 @@ __global__ __launch_bounds__(NT) void k_rp_cross(DBatch b, G g, DDrop q, DRepl r
                         const int x = (int)ESRC_NODE(sw);
                         if (!in_y(x)) continue;
                         if constexpr (COND) { if (sp && mg_bit(g.q.mask, ebase + e)) continue; }
-                        const WInt<NL> dx = wi_load<NL>(cur + (size_t)cpos[x] * NL);
-                        if (wi_is_inf<NL>(dx)) continue;
-                        const WInt<NL> c = wi_add<NL>(dx, dp_w_in<NL>(g, sp, biased, ebase + e, ew_decode<NL>(edge_wenc(sw, ew, e, gt))));
-                        if (wi_lt<NL>(c, d)) { d = c; s_chg = 1; rnd[p] = rr; }
+                        const WInt<WL> dx = wi_load<WL>(cur + (size_t)cpos[x] * WL);
+                        if (wi_is_inf<WL>(dx)) continue;
+                        const WInt<WL> c = wi_add<WL>(dx, dp_w_in<WL>(g, sp, biased, ebase + e, ew_decode<WL>(edge_wenc(sw, ew, e, gt))));
+                        if (wi_lt<WL>(c, d)) { d = c; s_chg = 1; rnd[p] = rr; }
                     }
-                wi_store<NL>(nxt + (size_t)p * NL, d);
+                wi_store<WL>(nxt + (size_t)p * WL, d);
             }
             __syncthreads();
             uint64_t *t = cur; cur = nxt; nxt = t;
@@ -215,16 +224,16 @@ __global__ __launch_bounds__(NT) void k_rp_cross(DBatch b, G g, DDrop q, DRepl r
         for (int p = tid; p < nc; p += NT) {
             const int y = clist[p];
             if (!in_y(y)) continue;
-            const WInt<NL> d = wi_load<NL>(cur + (size_t)p * NL);
-            if (wi_is_inf<NL>(d)) continue;
+            const WInt<WL> d = wi_load<WL>(cur + (size_t)p * WL);
+            if (wi_is_inf<WL>(d)) continue;
             [[maybe_unused]] bool sp = false;
             if constexpr (COND) sp = dp_sp_out(g, ebase, oo[y], oo[y + 1]);
             for (uint32_t e = oo[y], e1 = oo[y + 1]; e < e1; e++) {
                 const int z = (int)od[e];
                 if (last[z] <= j) continue;
                 if constexpr (COND) { if (sp && mg_bit(g.r.fbit, ebase + e)) continue; }
-                const WInt<NL> c = wi_add<NL>(wi_add<NL>(d, dp_w_out<NL>(g, sp, ebase + e, ew_decode<NL>(ow[e]))), wi_add<NL>(wi_load<NL>(dt + (size_t)z * NL), negD));
-                if (wi_eq<NL>(c, m)) atomicMin(&s_key, (unsigned long long)(((uint64_t)y << 32) | (uint32_t)z));
+                const WInt<WL> c = wi_add<WL>(wi_add<WL>(d, dp_w_out<WL>(g, sp, ebase + e, ew_decode<WL>(ow[e]))), wi_add<WL>(wi_load<WL>(dt + (size_t)z * WL), negD));
+                if (wi_eq<WL>(c, m)) atomicMin(&s_key, (unsigned long long)(((uint64_t)y << 32) | (uint32_t)z));
             }
         }
         __syncthreads();
@@ -234,7 +243,7 @@ __global__ __launch_bounds__(NT) void k_rp_cross(DBatch b, G g, DDrop q, DRepl r
                 // back from y: a tight in-edge from an earlier-settled node of Y_j, the lowest id; then the seed edge x -> y_0, the lowest x
                 auto step = [&](int v) -> int {
                     const int pv = cpos[v], rv = rnd[pv];
-                    const WInt<NL> dv = wi_load<NL>(cur + (size_t)pv * NL);
+                    const WInt<WL> dv = wi_load<WL>(cur + (size_t)pv * WL);
                     int best = -1;
                     [[maybe_unused]] bool sp = false;
                     if constexpr (COND) sp = dp_sp_in(g, biased, ebase, in_off[v], in_off[v + 1]);
@@ -247,11 +256,11 @@ __global__ __launch_bounds__(NT) void k_rp_cross(DBatch b, G g, DDrop q, DRepl r
                         if (rv == 0) {
                             const int fu = first[u];
                             if (fu < 0 || fu >= j) continue;
-                            if (wi_eq<NL>(wi_add<NL>(wi_load<NL>(ds + (size_t)u * NL), dp_w_in<NL>(g, sp, biased, ebase + e, ew_decode<NL>(we))), dv)) best = u;
+                            if (wi_eq<WL>(wi_add<WL>(wi_load<WL>(ds + (size_t)u * WL), dp_w_in<WL>(g, sp, biased, ebase + e, ew_decode<WL>(we))), dv)) best = u;
                         } else {
                             if (!in_y(u) || rnd[cpos[u]] >= rv) continue;
-                            const WInt<NL> du = wi_load<NL>(cur + (size_t)cpos[u] * NL);
-                            if (!wi_is_inf<NL>(du) && wi_eq<NL>(wi_add<NL>(du, dp_w_in<NL>(g, sp, biased, ebase + e, ew_decode<NL>(we))), dv)) best = u;
+                            const WInt<WL> du = wi_load<WL>(cur + (size_t)cpos[u] * WL);
+                            if (!wi_is_inf<WL>(du) && wi_eq<WL>(wi_add<WL>(du, dp_w_in<WL>(g, sp, biased, ebase + e, ew_decode<WL>(we))), dv)) best = u;
                         }
                     }
                     return best;
