@@ -51,7 +51,8 @@ extern "C" {
  *        (additions, version unchanged) phx_redrops_flat, phx_redrops_ms, phx_redrop_stats — probe for the symbol
  *        (additions, version unchanged) phx_rereplacements_flat, phx_tap_rereplacement, phx_rereplacements_ms, phx_rereplacement_stats — probe for the symbol
  *        (additions, version unchanged) phx_pindrops_flat, phx_pindrops_ms, phx_pindrop_stats — probe for the symbol
- *        (additions, version unchanged) phx_pinreplacements_flat, phx_tap_pinreplacement, phx_pinreplacements_ms, phx_pinreplacement_stats — probe for the symbol */
+ *        (additions, version unchanged) phx_pinreplacements_flat, phx_tap_pinreplacement, phx_pinreplacements_ms, phx_pinreplacement_stats — probe for the symbol
+ *        (additions, version unchanged) phx_profile_slot, phx_profile_flat, phx_profile_ms — probe for the symbol */
 #define PHX_MAX_CODONS 16
 
 /* library-level errors */
@@ -374,6 +375,41 @@ int phx_drop_ms(phx_ctx *ctx, float *ms /* [4] */);
 /* counters of the last computation, out[4]: gene slots, slots with cross nodes (step 4 of DESIGN.md §12), saturated slots rescanned
  * exactly, contigs whose trees were built layer by layer (a zero-length cycle of tight edges, or env PHX_DROP_LAYERED=1) */
 int phx_drop_stats(phx_ctx *ctx, int64_t *out /* [4] */);
+
+/* ---- coding profiles, on demand after a run ----
+ * What each stretch of a contig costs as part of a forward gene, of a reverse gene, or between genes.  With W, d_s, d_t and D as for the
+ * margins, EVERY edge e = (u -> v) of the device graph — ORF edge, tRNA edge or connector (gap, overlap, bridge, source and target edges) —
+ * has Delta(e) = d_s(u) + W(e) + d_t(v) - D >= 0 and mu(e) = float(Delta(e)) / 1000.0 as phx_margins_flat rounds it (+inf when d_s(u) or
+ * d_t(v) is unreached).  As for the margins, Delta is the length of the best source -> target WALK forced through e, over D: the graph has
+ * backward (overlap) edges, so the forced walk may meet a node twice.
+ *   Slots.  A contig with V nodes (phx_tap_nodes order: the real nodes 0 .. m-1 position-sorted, m = V - 2, then source and target) has
+ *   m + 1 = V - 1 slots: slot 0 left of node 0, slot s between node s-1 and node s, slot m right of node m-1.  With rank(v) = v for a real
+ *   node, rank(source) = -1 and rank(target) = m, an edge with rank(u) < rank(v) covers the slots rank(u)+1 .. rank(v); any other edge
+ *   (overlap connectors, equal ranks) covers nothing.  Every source -> target path crosses every slot by at least one covering edge.
+ *   Tracks.  An edge whose tail is an open node (forward start or reverse stop; tRNA nodes alike) is a gene edge, of the strand of its
+ *   tail's frame; every other edge is a connector.  fwd / rev / gap of a slot: the minimum mu over the forward gene edges / reverse gene
+ *   edges / connectors that cover it, +inf where none does — how much worse the best annotation becomes when the stretch must lie inside a
+ *   forward gene / inside a reverse gene / between genes.  On a contig with status 0 the device path crosses every slot: min(fwd, rev,
+ *   gap) = 0.  The minimum of mu equals mu of the exact minimum Delta (rounding and division are monotone).
+ * lo / hi are NODE positions (phx_tap_nodes pos), not gene coordinates: a forward gene's record in phx_download* has right = its stop
+ * node's pos + 2 (right includes the stop codon), so a gene [left, right] covers the slots with left <= lo and hi <= right - 2.  lo == hi
+ * happens (both strands at one position, tRNA nodes); such a slot is still a record.
+ * As the margins, the profile is over the device's integers W and the device path, also on a phx_certified 2 contig. */
+typedef struct phx_profile_slot {
+    int32_t lo, hi;       /* phx_tap_nodes pos of the bounding nodes; slot 0: lo = 0 (the source's pos); last slot: hi = L + 1 (the target's) */
+    double fwd, rev, gap; /* >= 0, +inf: nothing of that kind covers the slot */
+} phx_profile_slot;
+/* Profiles of every contig of the batch last run, flat like phx_margins_flat (rec == NULL: size query): the n_node - 1 records of contig i
+ * are rec[offsets[i] .. offsets[i+1]), slot 0 first.  status[i] as phx_margins_flat: a run error (< 0), PHX_S_OVERFLOW (no device
+ * distances) and PHX_S_NEGCYCLE from the reverse pass without records; a contig without a graph (n_node <= 2): the run's status, no
+ * records; PHX_S_NOPATH: V - 1 records with all three values +inf; else 0.  The first call after a run computes them (the margins'
+ * out-edge CSR and reverse pass when they are not there yet, then one sparse table per contig and track: kernel by kernel on the context's
+ * stream, never inside phx_run; buffers allocated at the first call of a context); later calls reuse them, a new upload or run invalidates
+ * them.  phx_margins_flat, phx_drop_margins_flat and their timings are the same whichever call comes first. */
+int phx_profile_flat(phx_ctx *ctx, phx_profile_slot *rec, int64_t cap, int64_t *offsets /* [n+1] */, int32_t *status /* [n] */, int64_t *total);
+/* device time of the last computation of the profiles (HIP events), ms[3]: candidates + tables with their push-down (one launch per limb
+ * class: a table lives in LDS where it fits), the slots' bounds (records), the copy of the records to the host.  All 0 before the first. */
+int phx_profile_ms(phx_ctx *ctx, float *ms /* [3] */);
 
 /* ---- drop replacements, on demand after a run ----
  * For every record of phx_drop_margins_flat with bypass = 1 a replacement path R_g: a simple source -> target path of the device graph

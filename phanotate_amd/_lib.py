@@ -49,6 +49,7 @@ ORF_DT = np.dtype([("start", "i4"), ("stop", "i4"), ("frame", "i4"), ("length", 
 NODE_DT = np.dtype([("pos", "i4"), ("type", "i1"), ("frame", "i1"), ("pad", "i2"), ("other", "i4"), ("refidx", "i4"), ("o", "f8")], align=True)
 MARGIN_DT = np.dtype([("left", "i4"), ("right", "i4"), ("strand", "i4"), ("frame", "i4"), ("score", "f8"), ("margin", "f8"), ("called", "i4"), ("through", "i4")], align=True)
 DROP_DT = np.dtype([("left", "i4"), ("right", "i4"), ("strand", "i4"), ("frame", "i4"), ("score", "f8"), ("drop", "f8"), ("called", "i4"), ("bypass", "i4")], align=True)
+PROFILE_DT = np.dtype([("lo", "i4"), ("hi", "i4"), ("fwd", "f8"), ("rev", "f8"), ("gap", "f8")], align=True)  # phx_profile_slot
 REPL_DT = np.dtype([("left", "i4"), ("right", "i4"), ("strand", "i4"), ("frame", "i4"), ("drop", "f8"), ("called", "i4"), ("bypass", "i4"),
                     ("span_left", "i4"), ("span_right", "i4"), ("n_removed", "i4"), ("n_added", "i4"), ("gene_off", "i8")], align=True)
 # Annotator.start_drops(): the called gene (left, right, strand; orf: its index in orfs(i)), the cost of refusing its start, and the ORF of the same
@@ -163,6 +164,8 @@ def lib():
         "phx_drop_margins_flat": (C.c_int, [vp, vp, i64, vp, vp, P(i64)]),
         "phx_drop_ms": (C.c_int, [vp, P(C.c_float)]),
         "phx_drop_stats": (C.c_int, [vp, P(i64)]),
+        "phx_profile_flat": (C.c_int, [vp, vp, i64, vp, vp, P(i64)]),
+        "phx_profile_ms": (C.c_int, [vp, P(C.c_float)]),
         "phx_format_drops": (C.c_int, [i32, vp, vp, vp, vp, P(vp), P(i64)]),
         "phx_replacements_flat": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, P(i64), P(i64)]),
         "phx_tap_replacement": (C.c_int, [vp, i32, i32, vp, i32, P(i32)]),
@@ -232,6 +235,7 @@ def lib():
     assert MARGIN_DT.itemsize == 40
     assert DROP_DT.itemsize == 40
     assert REPL_DT.itemsize == 56
+    assert PROFILE_DT.itemsize == 32
     _lib = L
     return L
 
@@ -253,4 +257,5 @@ EXPORTS = ["phx_version", "phx_device_count", "phx_strerror", "phx_last_error", 
            "phx_redrops_flat", "phx_redrops_ms", "phx_redrop_stats",
            "phx_rereplacements_flat", "phx_tap_rereplacement", "phx_rereplacements_ms", "phx_rereplacement_stats",
            "phx_pindrops_flat", "phx_pindrops_ms", "phx_pindrop_stats",
-           "phx_pinreplacements_flat", "phx_tap_pinreplacement", "phx_pinreplacements_ms", "phx_pinreplacement_stats"]
+           "phx_pinreplacements_flat", "phx_tap_pinreplacement", "phx_pinreplacements_ms", "phx_pinreplacement_stats",
+           "phx_profile_flat", "phx_profile_ms"]

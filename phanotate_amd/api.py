@@ -69,6 +69,7 @@ _MS_KEYS = {
     "phx_margins_ms": ("transpose", "reverse", "margins", "download"),
     "phx_drop_ms": ("trees", "candidates", "fixups", "download"),
     "phx_replacements_ms": ("argmin", "walk", "download"),
+    "phx_profile_ms": ("tables", "records", "download"),
     "phx_scenarios_ms": ("mask", "solve", "finish"),
     "phx_remargins_ms": ("apply", "reverse", "margins", "download"),
     "phx_pinmargins_ms": ("apply", "reverse", "margins", "download"),
@@ -450,6 +451,20 @@ class Annotator:
     def drop_ms(self):
         """Device time of the last drop-margins computation in ms: trees + labels, candidates, fixups, copy to the host (phx_drop_ms)."""
         return self._ms("phx_drop_ms")
+
+    def profile(self):
+        """(status int32[n], offsets int64[n+1], records structured array[total] of _lib.PROFILE_DT): the coding profile of every contig of
+        the batch last run (phx_profile_flat).  The n_node - 1 records of contig i are records[offsets[i]:offsets[i+1]], one
+        per slot between neighbouring nodes of nodes(i) (lo, hi: their pos; 0 and L + 1 at the ends).  fwd / rev / gap: the smallest path
+        margin float(d_s(u) + W + d_t(v) - D) / 1000 over the forward gene edges / reverse gene edges / connectors that cover the slot, +inf
+        where none does — what it costs the best annotation to have the stretch inside a forward gene, inside a reverse gene, between genes.
+        status as phx_profile_flat reports it (< 0: no records; 1: no path, every value +inf)."""
+        (status,), offs, (rec,) = self._query_fill(self.L.phx_profile_flat, "phx_profile_flat", (), self.n, (_lib.PROFILE_DT,))
+        return status, offs, rec
+
+    def profile_ms(self):
+        """Device time of the last profile computation in ms: candidates + tables + push-down, the slots' bounds, copy to the host (phx_profile_ms)."""
+        return self._ms("phx_profile_ms")
 
     def replacements(self):
         """(status int32[n], offsets int64[n+1], records structured array[total] of _lib.REPL_DT, genes structured array of _lib.GENE_DT):

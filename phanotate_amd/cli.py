@@ -43,6 +43,7 @@ def get_args(argv=None):
     p.add_argument("--batch-bases", type=int, default=400_000_000, help="bases per GPU batch [4e8]")
     p.add_argument("--margins", metavar="FILE", default=None, help="also write every ORF some source-to-target path runs through, with its path margin (DESIGN.md §11), to FILE")
     p.add_argument("--drop-margins", metavar="FILE", default=None, help="also write every called gene with its drop margin, the cost of the best path without it (DESIGN.md §12), to FILE")
+    p.add_argument("--profile", metavar="FILE", default=None, help="also write the coding profile of every contig (DESIGN.md §34) to FILE: per stretch between neighbouring nodes of the graph, what it costs the best annotation to have it inside a forward gene, inside a reverse gene, or between genes")
     p.add_argument("--drop-replacements", metavar="FILE", default=None, help="also write every called gene with what the best path without it calls instead (DESIGN.md §13) to FILE")
     p.add_argument("--start-drops", metavar="FILE", default=None, help="also write every called gene with the cost of refusing its start and the start the best annotation then takes for its stop (DESIGN.md §17) to FILE")
     p.add_argument("--alt-starts", metavar="FILE", default=None, help="also write, for every called gene and every other start of its stop, the cost of the best annotation that takes that start instead (DESIGN.md §18) to FILE")
@@ -87,7 +88,7 @@ _RULES = (
     ("require", lambda a: a.reannotation is None, "argument --require: needs --reannotation"),
 )
 # The flags of OUTPUTS and INPUTS in the order get_args looks at them.
-_CHECK_ORDER = ("margins", "drop_margins", "drop_replacements", "start_drops", "alt_starts", "evidence_scan", "curated_scan", "remargins", "redrop_margins", "redrop_replacements", "pin_margins", "pin_drop_margins", "pin_drop_replacements", "forbid", "require", "evidence", "reannotation")
+_CHECK_ORDER = ("margins", "drop_margins", "drop_replacements", "start_drops", "alt_starts", "evidence_scan", "curated_scan", "remargins", "redrop_margins", "redrop_replacements", "pin_margins", "pin_drop_margins", "pin_drop_replacements", "profile", "forbid", "require", "evidence", "reannotation")
 
 
 def _refusals(args, world):
@@ -155,6 +156,29 @@ def format_pin_replacements(names, status, offsets, records, genes, lost):
         for k in range(len(rec)):
             g0, g1 = int(rec["gene_off"][k]), int(rec["gene_off"][k]) + int(rec["n_removed"][k])
             out.append("%d\t%d\t%s\t" % _ends(rec[k]) + "%s\t%E\t%d\t%s\t%s\n" % (nm, float(rec["drop"][k]), int(lo[k]), listed(genes[g0:g1]), listed(genes[g1:g1 + int(rec["n_added"][k])])))
+    return "".join(out).encode()
+
+
+def format_profile(names, status, offsets, records):
+    """--profile FILE for a run of contigs, as bytes: per contig with status >= 0 "#id:\t<name>", the header, then one row per stretch (LO HI
+    FWD REV GAP) from left to right.  LO / HI are node positions (Annotator.nodes() pos; 0 and L + 1 at the ends), the three numbers
+    Annotator.profile()'s fwd / rev / gap, printed as format_margins prints a margin (INF: nothing of that kind covers the stretch).  Slots
+    without extent (lo == hi) are left out; neighbouring slots with the same three values are one row."""
+    import numpy as np
+
+    out = []
+    for nm, cut in _blocks(names, status, offsets):
+        out.append("#id:\t%s\n#LO\tHI\tFWD\tREV\tGAP\n" % nm)
+        rec = records[cut]
+        rec = rec[rec["lo"] != rec["hi"]]
+        if not len(rec):
+            continue
+        first = np.ones(len(rec), bool)  # the first slot of every run of equal triples
+        first[1:] = (rec["fwd"][1:] != rec["fwd"][:-1]) | (rec["rev"][1:] != rec["rev"][:-1]) | (rec["gap"][1:] != rec["gap"][:-1])
+        a = np.flatnonzero(first)
+        z = np.append(a[1:], len(rec)) - 1
+        for i, j in zip(a.tolist(), z.tolist()):
+            out.append("%d\t%d\t%E\t%E\t%E\n" % (int(rec["lo"][i]), int(rec["hi"][j]), float(rec["fwd"][i]), float(rec["rev"][i]), float(rec["gap"][i])))
     return "".join(out).encode()
 
 
@@ -480,6 +504,7 @@ OUTPUTS = {o.dest: o for o in (
     _out("--alt-starts", format_alt_starts, "w", lambda ann, entries: ann.alt_starts()[:3], resident=True),
     _out("--evidence-scan", format_evidence_scan, "w", lambda ann, entries: ann.evidence_scan(entries("evidence_scan"))[:3], resident=True),
     _out("--curated-scan", format_curated_scan, "w", lambda ann, entries: ann.curated_scan(entries("curated_scan"), entries("forbid"), entries("require"))[:3], resident=True),
+    _out("--profile", format_profile, "wb", lambda ann, entries: ann.profile(), resident=True),  # (it needs nothing else and conflicts with nothing: no row in _RULES)
     _out("--reannotation", format_reannotation, "w", _reannotate),  # (format_reannotation's unmet: the fifth member constrain() returns, so only with --require)
 )}
 # A batch's fetches, in this order.  THE ORDER IS CONTRACT: the replacements in front of the drop margins (the drops are then computed
@@ -488,7 +513,7 @@ OUTPUTS = {o.dest: o for o in (
 # and the pinned drop margins (behind pinmargins, which they build on) behind the re-annotation, whose margins they are, the pinned
 # replacements behind the pinned drop margins (as the re-annotation's: the trees are then built once more).  The entry files are resolved where a fetch first needs them, so a line that names no ORF is
 # reported in the order --evidence-scan, --forbid, --evidence or --require, --curated-scan.
-_FETCH_ORDER = ("margins", "drop_replacements", "drop_margins", "start_drops", "alt_starts", "evidence_scan", "reannotation", "curated_scan", "remargins", "redrop_margins", "redrop_replacements", "pin_margins", "pin_drop_margins", "pin_drop_replacements")
+_FETCH_ORDER = ("margins", "drop_replacements", "drop_margins", "start_drops", "alt_starts", "evidence_scan", "reannotation", "curated_scan", "remargins", "redrop_margins", "redrop_replacements", "pin_margins", "pin_drop_margins", "pin_drop_replacements", "profile")
 # The entry files in the order main looks for a line that names a contig the FASTA file does not hold.
 _UNKNOWN_ORDER = ("forbid", "require", "evidence", "evidence_scan", "curated_scan")
 assert set(_CHECK_ORDER) == set(OUTPUTS) | set(INPUTS) and set(_FETCH_ORDER) == set(OUTPUTS) and set(_UNKNOWN_ORDER) == set(INPUTS)  # a new row takes its place in each order

@@ -328,6 +328,88 @@ int phx_drop_margins_flat(phx_ctx *c, phx_gene_drop *rec, int64_t cap, int64_t *
 int phx_drop_ms(phx_ctx *c, float *ms) { return values_out<4>(c, ms, [](const phx_ctx *x) { return x->dp.ms; }); }
 int phx_drop_stats(phx_ctx *c, int64_t *out) { return values_out<4>(c, out, [](const phx_ctx *x) { return x->dp.stats; }); }
 
+// ---- coding profiles (phx_profile.inc, DESIGN.md §34) ----
+// the contigs the profile kernels cover (pf_on): device distances and a settled reverse pass; a contig without a path is one of them
+static bool profile_contig(const phx_ctx *c, size_t i) {
+    const DMeta &m = c->meta[i];
+    return m.status >= 0 && m.n_node > 2 && m.sssp_mode != 4 && !c->mstat[i];
+}
+static int64_t profile_cells(int n_slot) { int lv = 1; while ((2 << (lv - 1)) <= n_slot) lv++; return (int64_t)n_slot * lv; } // one track's table (k_pf_cand)
+
+// The slots' records of every covered contig into c->pf.h_rec (at pf.roff), once per run, on top of ensure_rev: layout -> candidates,
+// tables and push-down -> bounds -> copy.  It writes its own set only: the margins' and the drop margins' buffers are read.
+static int ensure_profile(phx_ctx *c) {
+    if (c->done.profile) return PHX_OK;
+    { const int rr = ensure_rev(c); if (rr) return rr; }
+    phx_ctx::ProfSet &P = c->pf;
+    const size_t n = (size_t)c->n;
+    std::vector<int64_t> off(2 * n + 2, 0); // toff[n], roff[n + 1]
+    P.roff.assign(n + 1, 0);
+    int nlm = 0;
+    int64_t tcells = 0, R = 0;
+    for (size_t i = 0; i < n; i++) {
+        off[n + i] = R; P.roff[i] = R;
+        if (!profile_contig(c, i)) continue;
+        nlm |= nl_class_bit(c->meta[i].sssp_nl);
+        const int ns = c->meta[i].n_node - 1;
+        const int64_t cells = profile_cells(ns);
+        if (cells > PF_TAB_LDS) { off[i] = tcells; tcells += cells; }
+        R += ns;
+    }
+    off[2 * n] = R; P.roff[n] = R;
+    for (float &m : P.ms) m = 0;
+    if (nlm) {
+        int rc;
+        if ((rc = ensure(c, P.b_tab, ((size_t)tcells + 1) * 8))) return rc;
+        if ((rc = ensure(c, P.b_off, (2 * n + 2) * 8))) return rc;
+        if ((rc = ensure(c, P.b_rec, ((size_t)R + 1) * sizeof(phx_profile_slot)))) return rc;
+        if ((rc = ensure_pinned(c, P.h_rec, ((size_t)R + 1) * sizeof(phx_profile_slot), ((size_t)R + (size_t)R / 4 + 1024) * sizeof(phx_profile_slot)))) return rc;
+        if ((rc = analysis_events(c))) return rc;
+        DBatch b;
+        fill_batch(c, &b);
+        DMarg g;
+        margins_args(c, &g);
+        DProf q;
+        q.gtab = (uint64_t *)P.b_tab.p; q.toff = (const int64_t *)P.b_off.p; q.roff = q.toff + n; q.rec = (phx_profile_slot *)P.b_rec.p;
+        hipStream_t s = c->stream;
+        HIPCHK(c, hipEventRecord(c->aev[0], s));
+        HIPCHK(c, hipMemcpyAsync(P.b_off.p, off.data(), (2 * n + 2) * 8, hipMemcpyHostToDevice, s));
+        phxk_profile_cand(&b, &g, &q, nlm, s);
+        HIPCHK(c, hipEventRecord(c->aev[1], s));
+        phxk_profile_rec(&b, &g, &q, s);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(c->aev[2], s));
+        if (R) HIPCHK(c, hipMemcpyAsync(P.h_rec.p, P.b_rec.p, (size_t)R * sizeof(phx_profile_slot), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipEventRecord(c->aev[3], s));
+        HIPCHK(c, hipStreamSynchronize(s)); // (`off` is read by the copy until here)
+        for (int k = 0; k < 3; k++) P.ms[k] = ev_ms(c->aev[k], c->aev[k + 1]);
+    } // (else no contig is covered: nothing is allocated or launched)
+    c->done.profile = true;
+    return PHX_OK;
+}
+
+int phx_profile_flat(phx_ctx *c, phx_profile_slot *rec, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
+    if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
+    { const int ra = after_run(c); if (ra) return ra; }
+    { const int rp = ensure_profile(c); if (rp) return rp; }
+    const phx_ctx::ProfSet &P = c->pf;
+    int64_t total = 0;
+    for (int i = 0; i < c->n; i++) { // V - 1 records for every covered contig (status 0 or PHX_S_NOPATH)
+        offsets[i] = total;
+        status[i] = margins_status(c, i);
+        if (status[i] >= 0 && profile_contig(c, (size_t)i)) total += P.roff[(size_t)i + 1] - P.roff[(size_t)i];
+    }
+    offsets[c->n] = total;
+    if (total_out) *total_out = total;
+    if (!rec) return PHX_OK; // size query
+    if (cap < total) return PHX_E_ARG;
+    for (int i = 0; i < c->n; i++)
+        if (offsets[i + 1] > offsets[i]) memcpy(rec + offsets[i], (const phx_profile_slot *)P.h_rec.p + P.roff[(size_t)i], (size_t)(offsets[i + 1] - offsets[i]) * sizeof(phx_profile_slot));
+    return PHX_OK;
+}
+
+int phx_profile_ms(phx_ctx *c, float *ms) { return values_out<3>(c, ms, [](const phx_ctx *x) { return x->pf.ms; }); }
+
 
 // ---- drop replacements (phx_replace.inc, DESIGN.md §13) ----
 // The replacement pass, once for both entry points (§13 on the run's graph, §30 on a re-annotation's): pick -> cross -> regrowth -> counting

@@ -363,6 +363,14 @@ struct DDrop {
     int32_t layered;      // 1: every tree by layers (env PHX_DROP_LAYERED)
     int32_t *ps, *ts;     // per node, or null: the one-hop parent of T_s / successor of T_t (a node on P: itself; -1: unreached) (§13)
 };
+#define PF_TAB_LDS 4096 // sparse-table cells (slots x levels, one track at a time) k_pf_cand keeps in LDS (32 KB: up to 455 slots); beyond: the contig's slice of DProf.gtab
+// Coding profiles (phx_profile.inc), on demand after a run and the margins' shared part: the context's lazily allocated buffers
+struct DProf {
+    uint64_t *gtab;        // sparse tables of the contigs whose table does not fit in LDS, at toff (one track's table: the tracks take turns)
+    const int64_t *toff;   // per contig: offset of its table in gtab
+    const int64_t *roff;   // per contig: first record (one per slot: n_node - 1)
+    phx_profile_slot *rec; // per slot
+};
 // Drop replacements (phx_replace.inc), on demand after the drop margins: the context's lazily allocated buffers
 struct DRepl {
     uint64_t *win;        // per record: the winner, x << 32 | z (step 3) or RP_CROSS | y << 32 | z (step 4); ~0: none
@@ -550,6 +558,8 @@ void phxk_redrop_fix(const DBatch *b, const DMarg *g, const DReann *rq, const DR
 void phxk_pindrop_trees(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, int nl_mask, void *stream);
 void phxk_pindrop_cand(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, int nl_mask, void *stream);
 void phxk_pindrop_fix(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, int nl_mask, void *stream);
+void phxk_profile_cand(const DBatch *b, const DMarg *g, const DProf *q, int nl_mask, void *stream); // coding profiles (phx_profile.inc): candidates, tables and push-down per track,
+void phxk_profile_rec(const DBatch *b, const DMarg *g, const DProf *q, void *stream);                //   the slots' bounds
 void phxk_repl_pick(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream); // drop replacements (phx_replace.inc): winners,
 void phxk_repl_cross(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream); //   cross winners and their delta chains,
 void phxk_repl_walk(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int fill, void *stream);    //   detour lengths (fill 0) / detours, genes, records (1)

@@ -180,6 +180,7 @@ __device__ __forceinline__ int min_idx(int a, int b, int c) { return a > b ? (b 
 #include "phx_certify.inc"
 #include "phx_margins.inc"
 #include "phx_drop.inc"
+#include "phx_profile.inc"
 #include "phx_replace.inc"
 #include "phx_resolve.inc"
 
@@ -494,6 +495,13 @@ void phxk_pindrop_fix(const DBatch *b, const DMarg *g, const DReann *rq, const D
     each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_rescan<decltype(nl)::value, MgPinDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, c, *q); });
     each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_cross<decltype(nl)::value, MgPinDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, c, *q); });
     each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_rec<decltype(nl)::value, MgPinDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, c, *q); });
+}
+// coding profiles (phx_profile.inc): a workgroup per contig and limb class for the tables, then a thread per slot
+void phxk_profile_cand(const DBatch *b, const DMarg *g, const DProf *q, int nl_mask, void *stream) {
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL(k_pf_cand<decltype(nl)::value>, dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, *g, *q); });
+}
+void phxk_profile_rec(const DBatch *b, const DMarg *g, const DProf *q, void *stream) {
+    hipLaunchKernelGGL(k_pf_rec<DMarg>, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), 0, (hipStream_t)stream, *b, *g, *q);
 }
 // drop replacements (phx_replace.inc): a workgroup per contig
 void phxk_repl_pick(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream) {

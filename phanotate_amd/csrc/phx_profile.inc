@@ -1,0 +1,140 @@
+// phx_profile.inc — coding profiles: what each stretch of a contig costs as forward gene, as reverse gene or as gap (included by phx_kernels.hip, after phx_drop.inc).
+// ------------------------------------------------------------------------------------------------
+// On demand after a run and after the margins' shared part (out-edge CSR, d_t: phx_margins.inc), never inside a run.  For one contig with
+// V nodes (real nodes 0 .. m-1, m = V - 2, position-sorted; source V-2, target V-1) every edge e = (u -> v), ORF edge or connector, has
+//     Delta(e) = d_s(u) + W(e) + d_t(v) - D >= 0,   mu(e) = float(Delta(e)) / 1000.0 as k_margins rounds it (+inf: u or v unreached)
+// the length of the best source -> target walk forced through e, over the best path (DESIGN.md §34).  With rank(v) = v for a real node,
+// rank(source) = -1 and rank(target) = m, the contig has n = m + 1 slots (slot s between node s-1 and node s), and an edge with
+// rank(u) < rank(v) covers the slots rank(u)+1 .. rank(v).  Per slot and track — gene edges of the forward strand, of the reverse strand,
+// connectors — the record carries the minimum mu over the covering edges.
+//
+// The key of the range minimum is the bit pattern of mu itself: rounding to a double and the division are monotone in Delta, and the
+// patterns of non-negative doubles order like unsigned integers, so the minimum of the patterns is the pattern of mu(min Delta); +inf
+// (PF_NONE) is "no edge".  No saturation marker and no exact rescan (§12's) are needed.
+//
+// One table serves the three tracks one after the other: a track's table is n (floor(log2 n) + 1) cells, indexed as k_dp_cand's — level k
+// entry i covers the slots [i, i + 2^k); an edge goes to level floor(log2 len) at both ends of its range; the push-down gathers level k-1
+// entry i from level k at i and at i - 2^(k-1).  Up to PF_TAB_LDS cells the table is in LDS, beyond in the contig's own slice of
+// DProf.gtab (read back through L2): no atomic ever targets an address another contig uses.
+
+#define PF_NONE 0x7ff0000000000000ull // the pattern of +inf: nothing of the track covers the slot
+
+// the contigs the pass covers: device distances and a settled reverse pass (a contig without a path is covered: every value is +inf)
+template <class G>
+__device__ __forceinline__ bool pf_on(const DBatch &b, const G &g, const DMeta *meta) {
+    static_assert(!mg_cond<G>, "the profile is instantiated for the run's graph only (DESIGN.md §34, out of scope)");
+    return mg_contig(meta) && !g.mstat[meta - b.meta];
+}
+// rank of node v among the slots' bounds: source -1, real node v, target m
+__device__ __forceinline__ int pf_rank(int v, int V) { return v < V - 2 ? v : (v == V - 2 ? -1 : V - 2); }
+// track of an edge by its tail, as cbits and emit_genes tell an open node (forward start, reverse stop; tRNA nodes, frame +-4, alike):
+// 0 a gene edge of the forward strand, 1 of the reverse strand, 2 a connector
+__device__ __forceinline__ int pf_track(int32_t info) {
+    const int ty = NTYPE(info), fr = NFRAME(info);
+    if (ty == 0 && fr > 0) return 0;
+    if (ty == 1 && fr < 0) return 1;
+    return 2;
+}
+
+// a table cell as the workgroup's atomics left it (a global table: through L2, as k_dp_cand reads its own)
+__device__ __forceinline__ uint64_t pf_ld(const unsigned long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// ---- k_pf_cand<NL>: candidates, tables and push-down of the three tracks, one workgroup per contig ----
+// Every in-edge of every node, once per track: classified by its tail, skipped when it covers nothing, is not of the track at hand or has
+// mu = +inf; a coded gap edge reads the contig's gap table (edge_wenc).  The track's slot minima go to their field of the records.
+// Every index is checked against the contig's own ranges before use.
+// The body is instantiated once per placement of the table (pf_tracks: LDS or global memory), so that the LDS table is reached by LDS
+// instructions and the global one by global ones; a table index is formed in unsigned 32-bit arithmetic, complete before it meets the
+// base.  (As one body over a generic pointer the compiler split the source's rank -1 off the index: flat_atomic ... offset:8 on a base
+// register 8 bytes below an LDS table that starts at the bottom of the LDS aperture — an address outside every aperture.)
+template <int NL, class G, class T>
+__device__ __forceinline__ void pf_tracks(const DBatch &b, const G &g, const DProf &q, const DMeta *meta, T *tab, int lv) {
+    const int V = meta->n_node, n = V - 1, tid = threadIdx.x;
+    const uint32_t un = (uint32_t)n, cells = un * (uint32_t)lv;
+    const size_t no = (size_t)meta->node_off;
+    const DNode *nd = b.node + no;
+    const uint32_t *in_off = b.in_off + no + blockIdx.x;
+    const uint32_t *esrc = b.esrc + meta->edge_off;
+    const long long *ew = b.ew + meta->edge_off;
+    const long long *gt = gtab_of(b, meta);
+    const uint64_t *ds = dp_ds<G>(b, g, meta);
+    const uint64_t *dt = dp_dt<G>(b, g, meta);
+    const uint32_t E = (uint32_t)meta->n_edge;
+    double *val = (double *)(q.rec + q.roff[blockIdx.x]); // four doubles per record: (lo, hi), fwd, rev, gap
+    const WInt<NL> D = wi_load<NL>(ds + (size_t)(V - 1) * NL);
+    const bool d_ok = !wi_unreached<NL>(D);
+    const WInt<NL> negD = wi_neg<NL>(D);
+    for (int t = 0; t < 3; t++) {
+        for (uint32_t i = (uint32_t)tid; i < cells; i += NT) tab[i] = PF_NONE;
+        __syncthreads();
+        for (int v = tid; v < V && d_ok; v += NT) {
+            const int rv = pf_rank(v, V);
+            if (rv < 0) continue; // (the source: no in-edge, and nothing ends left of slot 0)
+            uint32_t e = in_off[v], e1 = in_off[v + 1];
+            if (e1 > E) e1 = E; // (the contig's own edges)
+            bool have = false;
+            WInt<NL> tz = negD;
+            for (; e < e1; e++) {
+                const uint32_t sw = esrc[e];
+                const int u = (int)ESRC_NODE(sw);
+                if (u >= V) continue;
+                const int ru = pf_rank(u, V);
+                if (ru >= rv || pf_track(nd[u].info) != t) continue; // covers nothing (overlap connectors, equal ranks) / another track's
+                if (!have) { // d_t(v) - D, at the first edge that asks for it
+                    const WInt<NL> dv = wi_load<NL>(dt + (size_t)v * NL);
+                    if (wi_unreached<NL>(dv)) break; // mu = +inf for every in-edge of v
+                    tz = wi_add<NL>(dv, negD);
+                    have = true;
+                }
+                const WInt<NL> du = wi_load<NL>(ds + (size_t)u * NL);
+                if (wi_unreached<NL>(du)) continue;
+                const WInt<NL> delta = wi_add<NL>(wi_add<NL>(du, ew_decode<NL>(edge_wenc(sw, ew, e, gt))), tz);
+                const unsigned long long key = (unsigned long long)__double_as_longlong(wi_to_double_rn<NL>(delta) / 1000.0);
+                const uint32_t a = (uint32_t)(ru + 1), z = (uint32_t)rv, k = 31u - (uint32_t)__clz((int)(z - a + 1u)); // slots [a, z], 0 <= a <= z <= n - 1; 2^k <= z - a + 1 <= n: k < lv
+                const uint32_t ia = k * un + a, iz = k * un + (z + 1u - (1u << k));                                     // (a <= z + 1 - 2^k <= z)
+                if (ia >= cells || iz >= cells) continue; // (cannot happen)
+                atomicMin(&tab[ia], key);
+                atomicMin(&tab[iz], key);
+            }
+        }
+        __syncthreads();
+        for (uint32_t k = (uint32_t)lv - 1u; k >= 1u; k--) {
+            const uint32_t h = 1u << (k - 1u);
+            for (uint32_t i = (uint32_t)tid; i < un; i += NT) {
+                uint64_t m = pf_ld(&tab[k * un + i]);
+                if (i >= h) { const uint64_t m2 = pf_ld(&tab[k * un + (i - h)]); m = m2 < m ? m2 : m; }
+                if (m != PF_NONE) atomicMin(&tab[(k - 1u) * un + i], (unsigned long long)m);
+            }
+            __syncthreads();
+        }
+        for (uint32_t i = (uint32_t)tid; i < un; i += NT) val[4 * (size_t)i + 1 + t] = __longlong_as_double((long long)pf_ld(&tab[i]));
+        __syncthreads(); // (every read of the table is done before the next track clears it)
+    }
+}
+template <int NL, class G = DMarg>
+__global__ __launch_bounds__(NT) void k_pf_cand(DBatch b, G g, DProf q) {
+    __shared__ unsigned long long s_tab[PF_TAB_LDS];
+    const DMeta *meta = &b.meta[blockIdx.x];
+    if (!pf_on<G>(b, g, meta) || meta->sssp_nl != NL) return;
+    const int n = meta->n_node - 1;
+    int lv = 1;
+    while ((2 << (lv - 1)) <= n) lv++; // floor(log2 n) + 1
+    if (n * lv <= PF_TAB_LDS) pf_tracks<NL, G>(b, g, q, meta, s_tab, lv); // (uniform over the workgroup)
+    else pf_tracks<NL, G>(b, g, q, meta, (unsigned long long *)(q.gtab + q.toff[blockIdx.x]), lv);
+}
+
+// ---- k_pf_rec: the bounds of every slot, a thread per slot ----
+// lo / hi: the positions of the nodes left and right of the slot (phx_tap_nodes pos); slot 0 starts at the source's (0), the last slot ends
+// at the target's (L + 1).
+template <class G = DMarg>
+__global__ __launch_bounds__(NT) void k_pf_rec(DBatch b, G g, DProf q) {
+    const DMeta *meta = &b.meta[blockIdx.x];
+    if (!pf_on<G>(b, g, meta)) return;
+    const int V = meta->n_node, n = V - 1;
+    const DNode *nd = b.node + meta->node_off;
+    phx_profile_slot *rec = q.rec + q.roff[blockIdx.x];
+    for (int i = (int)blockIdx.y * NT + (int)threadIdx.x; i < n; i += (int)gridDim.y * NT) {
+        rec[i].lo = nd[i == 0 ? V - 2 : i - 1].pos;
+        rec[i].hi = nd[i == n - 1 ? V - 1 : i].pos;
+    }
+}
