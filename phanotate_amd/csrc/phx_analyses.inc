@@ -160,12 +160,7 @@ int phx_tap_dist_target(phx_ctx *c, int32_t contig, uint64_t *dist_limbs, int64_
 
 int phx_margins_ms(phx_ctx *c, float *ms) { return values_out<4>(c, ms, [](const phx_ctx *x) { return x->margins_ms; }); }
 
-// ---- gene drop margins (phx_drop.inc, DESIGN.md §12; on a re-annotation's graph §29) ----
-// the contigs the drop kernels cover (dp_contig) and their sparse-table size (k_dp_cand)
-static bool drop_contig(const phx_ctx *c, size_t i) {
-    const DMeta &m = c->meta[i];
-    return m.status >= 0 && m.n_node > 2 && m.sssp_mode != 4 && !c->mstat[i] && m.n_path >= 3;
-}
+// ---- gene drop margins (phx_drop.inc, DESIGN.md §12; on a re-annotation's graph §29, §32): the pass and the rows; the families: below ----
 static int64_t drop_cells(int n_path) { int lv = 1; while ((2 << (lv - 1)) <= n_path) lv++; return (int64_t)n_path * lv; }
 static int drop_layered() { const char *ly = getenv("PHX_DROP_LAYERED"); return ly && *ly && strcmp(ly, "0") != 0 ? 1 : 0; }
 
@@ -181,7 +176,7 @@ static void drop_args(const phx_ctx::DropSet &D, bool trees, DDrop *q) {
     q->ps = trees ? (int32_t *)D.b_ps.p : nullptr; q->ts = trees ? (int32_t *)D.b_ts.p : nullptr;
 }
 
-// The drop pass, once for both entry points (§12 on the run's graph, §29 on a re-annotation's): layout -> trees + labels -> candidates ->
+// The drop pass, once for the three families (§12 on the run's graph, §29 and §32 on a re-annotation's): layout -> trees + labels -> candidates ->
 // fix-ups -> copies.  D: the set the pass writes and what it leaves on the host — the records of every pair of every covered path in D.h_rec
 // (at D.roff); covered(i): contig i's n_path, 0 when the kernels do not cover it; launch(step, q): step 0 k_dp_tree, 1 k_dp_cand, 2 the
 // fix-ups, under the caller's policy; done / has_trees: the caller's flags in RunDone.  trees: the one-hop trees too (DDrop.ps / ts, for the
@@ -259,24 +254,7 @@ extern "C++" template <class C, class L> static int drop_pass(phx_ctx *c, phx_ct
     return PHX_OK;
 }
 
-// The run's set, once per run, on top of ensure_rev.
-static int ensure_drops(phx_ctx *c, bool trees = false) {
-    if (c->done.drops && (!trees || c->done.trees)) return PHX_OK;
-    { const int rr = ensure_rev(c); if (rr) return rr; }
-    const int nlm = margins_nl_mask(c);
-    DBatch b;
-    fill_batch(c, &b);
-    DMarg g;
-    margins_args(c, &g);
-    hipStream_t s = c->stream;
-    return drop_pass(c, c->dp, c->rp, c->done.drops, c->done.trees, trees, [&](size_t i) { return drop_contig(c, i) ? c->meta[i].n_path : 0; }, [&](int step, const DDrop &q) {
-        if (step == 0) phxk_drop_trees(&b, &g, &q, nlm, s);
-        else if (step == 1) phxk_drop_cand(&b, &g, &q, nlm, s);
-        else phxk_drop_fix(&b, &g, &q, nlm, s);
-    });
-}
-
-// What both flat calls lay out of a contig's device records [k0, k1) of D: those of CDS genes (the pairs of the path that are), in path
+// What the flat calls lay out of a contig's device records [k0, k1) of D: those of CDS genes (the pairs of the path that are), in path
 // order, `called` from the sorted keys of the genes the contig's result delivers.
 static int64_t drop_count(const phx_ctx::DropSet &D, int64_t k0, int64_t k1) {
     const phx_gene_drop *src = (const phx_gene_drop *)D.h_rec.p;
@@ -296,37 +274,6 @@ static void drop_rows(const phx_ctx::DropSet &D, int64_t k0, int64_t k1, const s
         if (lost) *lost++ = D.wide ? D.h_lost[(size_t)k] : 0;
     }
 }
-
-int phx_drop_margins_flat(phx_ctx *c, phx_gene_drop *rec, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
-    if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
-    { const int ra = after_run(c); if (ra) return ra; }
-    { const int rx = ensure_exact(c); if (rx) return rx; } // `called` is against the genes phx_download* deliver
-    { const int rd = ensure_drops(c); if (rd) return rd; }
-    const phx_ctx::DropSet &D = c->dp;
-    try {
-    int64_t total = 0;
-    for (int i = 0; i < c->n; i++) { // records for every contig with status 0
-        offsets[i] = total;
-        status[i] = margins_status(c, i);
-        if (status[i] == 0 && drop_contig(c, (size_t)i)) total += drop_count(D, D.roff[(size_t)i], D.roff[(size_t)i + 1]);
-    }
-    offsets[c->n] = total;
-    if (total_out) *total_out = total;
-    if (!rec) return PHX_OK; // size query
-    if (cap < total) return PHX_E_ARG;
-    { const int rg = stage_run_genes(c); if (rg) return rg; }
-    std::vector<uint64_t> keys;
-    for (int i = 0; i < c->n; i++) {
-        if (offsets[i + 1] == offsets[i]) continue;
-        called_keys(c, i, keys);
-        drop_rows(D, D.roff[(size_t)i], D.roff[(size_t)i + 1], keys, rec + offsets[i]);
-    }
-    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_drop_margins_flat"; return PHX_E_NOMEM; }
-    return PHX_OK;
-}
-
-int phx_drop_ms(phx_ctx *c, float *ms) { return values_out<4>(c, ms, [](const phx_ctx *x) { return x->dp.ms; }); }
-int phx_drop_stats(phx_ctx *c, int64_t *out) { return values_out<4>(c, out, [](const phx_ctx *x) { return x->dp.stats; }); }
 
 // ---- coding profiles (phx_profile.inc, DESIGN.md §34) ----
 // the contigs the profile kernels cover (pf_on): device distances and a settled reverse pass; a contig without a path is one of them
@@ -412,7 +359,7 @@ int phx_profile_ms(phx_ctx *c, float *ms) { return values_out<3>(c, ms, [](const
 
 
 // ---- drop replacements (phx_replace.inc, DESIGN.md §13) ----
-// The replacement pass, once for both entry points (§13 on the run's graph, §30 on a re-annotation's): pick -> cross -> regrowth -> counting
+// The replacement pass, once for the three families (§13 on the run's graph, §30 and §33 on a re-annotation's): pick -> cross -> regrowth -> counting
 // walk -> offsets -> filling walk -> copies.  S: the DRepl set the pass writes and what it leaves on the host; R: the records of the DDrop set
 // the launchers read (one per pair of every covered path); launch(step, r): step 0 k_rp_pick, 1 k_rp_cross, 2 / 3 k_rp_walk counting / filling,
 // under the caller's policy; what / who: the feature and the entry point in the error texts.
@@ -507,32 +454,9 @@ extern "C++" template <class L> static int replacement_pass(phx_ctx *c, phx_ctx:
     return PHX_OK;
 }
 
-// Every device record's replacement into c->rp.h_rec / h_genes / h_det, once per run, on top of ensure_drops (with the one-hop trees).
-static int ensure_replacements(phx_ctx *c) {
-    if (c->done.repl) return PHX_OK;
-    { const int rd = ensure_drops(c, true); if (rd) return rd; }
-    const int nlm = margins_nl_mask(c);
-    DBatch b;
-    fill_batch(c, &b);
-    DMarg g;
-    margins_args(c, &g);
-    DDrop q;
-    drop_args(c->dp, true, &q);
-    hipStream_t s = c->stream;
-    const int rc = replacement_pass(c, c->rp, (size_t)c->dp.roff[(size_t)c->n], [&](int step, const DRepl &r) {
-        if (step == 0) phxk_repl_pick(&b, &g, &q, &r, nlm, s);
-        else if (step == 1) phxk_repl_cross(&b, &g, &q, &r, nlm, s);
-        else phxk_repl_walk(&b, &g, &q, &r, step - 2, s);
-    }, "drop replacements", "phx_replacements_flat");
-    if (rc) return rc;
-    c->done.repl = true;
-    return PHX_OK;
-}
-
-// The layout both flat calls share: the records of contig i (device records [k0, k1) of S, those of CDS genes) to dst, `called` from the
-// drop records dd they go with, their genes appended to `genes` at *go, gene_off rebased.  (lost: null, or where the rows' `lost` go — a set
-// without one gives 0)
-static void replacement_rows(const phx_ctx::ReplSet &S, int64_t k0, int64_t k1, const phx_gene_drop *dd, phx_gene_repl *dst, phx_gene *genes, int64_t *go, int32_t *lost = nullptr) {
+// The layout the flat calls share: the records of contig i (device records [k0, k1) of S, those of CDS genes) to dst, `called` from the
+// drop records dd they go with (whose `lost` is theirs too), their genes appended to `genes` at *go, gene_off rebased.
+static void replacement_rows(const phx_ctx::ReplSet &S, int64_t k0, int64_t k1, const phx_gene_drop *dd, phx_gene_repl *dst, phx_gene *genes, int64_t *go) {
     for (int64_t k = k0; k < k1; k++) {
         const phx_gene_repl &x = S.h_rec[(size_t)k];
         if (x.called < 0) continue;
@@ -543,7 +467,6 @@ static void replacement_rows(const phx_ctx::ReplSet &S, int64_t k0, int64_t k1, 
         if (ng) memcpy(genes + *go, S.h_genes.data() + x.gene_off, (size_t)ng * sizeof(phx_gene));
         *go += ng;
         dst++; dd++;
-        if (lost) *lost++ = S.h_lost.empty() ? 0 : S.h_lost[(size_t)k];
     }
 }
 static int64_t replacement_genes(const phx_ctx::ReplSet &S, int64_t k0, int64_t k1) {
@@ -551,7 +474,7 @@ static int64_t replacement_genes(const phx_ctx::ReplSet &S, int64_t k0, int64_t 
     for (int64_t k = k0; k < k1; k++) if (S.h_rec[(size_t)k].called >= 0) gt += S.h_rec[(size_t)k].n_removed + S.h_rec[(size_t)k].n_added;
     return gt;
 }
-// The path of the k-th record of a contig, both taps: device records [k0, k1) of S, on the path of n_path nodes at dpath (device).
+// The path of the k-th record of a contig, every tap: device records [k0, k1) of S, on the path of n_path nodes at dpath (device).
 static int replacement_tap(phx_ctx *c, phx_ctx::ReplSet &S, const char *who, int32_t contig, int64_t k0, int64_t k1, int32_t k, const int32_t *dpath, int np, int32_t *path, int32_t cap, int32_t *n_path) {
     int64_t rk = -1;
     for (int64_t q = k0, seen = 0; q < k1; q++)
@@ -574,45 +497,6 @@ static int replacement_tap(phx_ctx *c, phx_ctx::ReplSet &S, const char *who, int
     for (int t = b; t < np; t++) *o++ = P[(size_t)t];
     return PHX_OK;
 }
-
-int phx_replacements_flat(phx_ctx *c, phx_gene_repl *rec, int64_t cap, phx_gene *genes, int64_t gene_cap, int64_t *offsets, int32_t *status,
-                          int64_t *total_out, int64_t *gene_total_out) {
-    if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
-    { const int ra = after_run(c); if (ra) return ra; }
-    { const int rr = ensure_replacements(c); if (rr) return rr; }
-    // statuses, offsets and `called` exactly as the drop records have them
-    int64_t total = 0;
-    { const int rd = phx_drop_margins_flat(c, nullptr, 0, offsets, status, &total); if (rd) return rd; }
-    try {
-    std::vector<phx_gene_drop> drec((size_t)total + 1);
-    { const int rd = phx_drop_margins_flat(c, drec.data(), total, offsets, status, &total); if (rd) return rd; }
-    int64_t gt = 0;
-    for (int i = 0; i < c->n; i++)
-        if (offsets[i + 1] != offsets[i]) gt += replacement_genes(c->rp, c->dp.roff[(size_t)i], c->dp.roff[(size_t)i + 1]);
-    if (total_out) *total_out = total;
-    if (gene_total_out) *gene_total_out = gt;
-    if (!rec || !genes) return PHX_OK; // size query
-    if (cap < total || gene_cap < gt) return PHX_E_ARG;
-    int64_t go = 0;
-    for (int i = 0; i < c->n; i++)
-        if (offsets[i + 1] != offsets[i]) replacement_rows(c->rp, c->dp.roff[(size_t)i], c->dp.roff[(size_t)i + 1], drec.data() + offsets[i], rec + offsets[i], genes, &go);
-    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_replacements_flat"; return PHX_E_NOMEM; }
-    return PHX_OK;
-}
-
-int phx_tap_replacement(phx_ctx *c, int32_t contig, int32_t k, int32_t *path, int32_t cap, int32_t *n_path) {
-    if (!c || !n_path) return PHX_E_ARG;
-    *n_path = 0;
-    { const int ra = after_run(c); if (ra) return ra; }
-    if (contig < 0 || contig >= c->n || k < 0) return PHX_E_ARG;
-    { const int rr = ensure_replacements(c); if (rr) return rr; }
-    if (!drop_contig(c, (size_t)contig) || margins_status(c, contig) != 0) return PHX_E_ARG;
-    const DMeta &m = c->meta[(size_t)contig];
-    return replacement_tap(c, c->rp, "phx_tap_replacement", contig, c->dp.roff[(size_t)contig], c->dp.roff[(size_t)contig + 1], k, (const int32_t *)c->b_path.p + m.node_off, m.n_path, path, cap, n_path);
-}
-
-int phx_replacements_ms(phx_ctx *c, float *ms) { return values_out<3>(c, ms, [](const phx_ctx *x) { return x->rp.ms; }); }
-int phx_replacement_stats(phx_ctx *c, int64_t *out) { return values_out<5>(c, out, [](const phx_ctx *x) { return x->rp.stats; }); }
 
 // ---- masked re-annotation (phx_resolve.inc, DESIGN.md §14) ----
 // status of contig i's re-annotation before any kernel: a run error, PHX_S_OVERFLOW without device distances, else the run's status
@@ -1159,178 +1043,155 @@ int phx_tap_pindist(phx_ctx *c, int32_t contig, int32_t which, uint64_t *dist_li
 int phx_remargins_ms(phx_ctx *c, float *ms) { return values_out<4>(c, ms, [](const phx_ctx *x) { return x->xm.ms; }); }
 int phx_pinmargins_ms(phx_ctx *c, float *ms) { return values_out<4>(c, ms, [](const phx_ctx *x) { return x->pm.ms; }); }
 
-// ---- re-annotation drop margins (phx_drop.inc under MgDrop, DESIGN.md §29) ----
-// the contigs the conditioned drop kernels cover (dp_on<MgDrop>), after ensure_condmargins<CmPlain>
-static bool redrop_contig(const phx_ctx *c, size_t i) { return c->h_qsel[i] && c->xm.h_sel[i] == 1 && !c->xm.mstat[i] && c->h_qrec[i].n_path >= 3; }
+// ---- the three families of the drop margins and the drop replacements (DESIGN.md §35) ----
+// The run's (§12 / §13: policy DMarg on the run's graph, sets dp / rp), the re-annotation's (§29 / §30: MgDrop, rd / rr — the contigs solved
+// again without a required ORF) and the pinned (§32 / §33: MgPinDrop, pd / pr — the contigs solved under the required policy, values on one
+// limb more, `lost` beside the records).  The values are the `family` of phxk_drop_step and phxk_repl_step.
+enum { FAM_RUN = 0, FAM_RE = 1, FAM_PIN = 2 };
+struct FamilySets { // a family's two sets and its flags in RunDone
+    phx_ctx::DropSet &D;
+    phx_ctx::ReplSet &S;
+    bool &drops, &trees, &repl;
+};
+static FamilySets family_sets(phx_ctx *c, int f) {
+    if (f == FAM_RUN) return {c->dp, c->rp, c->done.drops, c->done.trees, c->done.repl};
+    if (f == FAM_RE) return {c->rd, c->rr, c->done.redrop, c->done.retrees, c->done.rerepl};
+    return {c->pd, c->pr, c->done.pindrop, c->done.pintrees, c->done.pinrepl};
+}
+// family f's kernels cover contig i (dp_on<G>; after the margins the family builds on: ensure_rev, ensure_condmargins<CmPlain> / <CmPin>)
+static bool family_covers(const phx_ctx *c, int f, size_t i) {
+    if (f == FAM_RUN) { const DMeta &m = c->meta[i]; return m.status >= 0 && m.n_node > 2 && m.sssp_mode != 4 && !c->mstat[i] && m.n_path >= 3; }
+    const phx_ctx::CondMarg &m = f == FAM_PIN ? c->pm : c->xm;
+    return (f == FAM_PIN ? re_mode_req(c->h_qsel[i]) : c->h_qsel[i] != 0) && m.h_sel[i] == 1 && !m.mstat[i] && c->h_qrec[i].n_path >= 3;
+}
+static int family_npath(const phx_ctx *c, int f, size_t i) { return f == FAM_RUN ? c->meta[i].n_path : c->h_qrec[i].n_path; } // contig i's n_path in f
+// the family whose sets hold contig i's records, for an entry point of level `top`: a contig that was not solved again keeps the run's.
+// (top FAM_RE never meets a pinned contig, whose sets it has not brought up: remarg_state refuses such a solve ahead of every caller — an
+// entry point of that level that skips the rule must not come here.)
+static int family_of(const phx_ctx *c, int top, size_t i) {
+    if (top == FAM_RUN || !c->h_qsel[i]) return FAM_RUN;
+    return re_mode_req(c->h_qsel[i]) ? FAM_PIN : FAM_RE;
+}
+static int32_t family_status(const phx_ctx *c, int f, int i) { return f == FAM_RUN ? margins_status(c, i) : condmargins_status(c, i); } // status of contig i's records in f
+// PHX_OK when the context holds a re-annotation the pinned entry points are defined for
+static int pin_state(phx_ctx *c, const char *who) {
+    if (!c->done.reann) { c->err = std::string(who) + ": no re-annotation of this run (call phx_constrain_flat or phx_curate_flat first)"; return PHX_E_STATE; }
+    return PHX_OK;
+}
 
-// the conditioned kernels' view of what the last re-annotation and its margins left resident (after ensure_condmargins<CmPlain>)
-struct RedropView {
+// family f's kernels' view of the run's batch and of what the last re-annotation and its margins left resident (after the margins f builds
+// on); v.lost is the launch's to set.  The view points into itself: it is filled in place and not copied.
+struct FamilyView {
     DBatch b, qb;
     DMarg g;
     DReann rq;
     DRmarg r;
-    const int32_t *qpath;
+    DPmarg p;
+    DCondView v; // (the run's family: all null)
 };
-static void redrop_view(phx_ctx *c, RedropView *v) {
-    fill_batch(c, &v->b);
-    margins_args(c, &v->g);
-    reann_batch(c, &v->qb, &v->rq);
-    condmargins_args(c, c->xm, (size_t)c->tot_edge / 32 + 2, &v->r);
-    v->qpath = (const int32_t *)c->b_qpath.p;
+static void cond_view(phx_ctx *c, int f, FamilyView *w) {
+    fill_batch(c, &w->b);
+    margins_args(c, &w->g);
+    w->v = DCondView{nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (f == FAM_RUN) return;
+    reann_batch(c, &w->qb, &w->rq);
+    const size_t mw = (size_t)c->tot_edge / 32 + 2;
+    w->v.rq = &w->rq; w->v.qpath = (const int32_t *)c->b_qpath.p;
+    if (f == FAM_RE) { condmargins_args(c, c->xm, mw, &w->r); w->v.r = &w->r; return; }
+    condmargins_args(c, c->pm, mw, &w->p);
+    w->p.dt_stride = w->b.dist_stride + 1; w->p.rbit = w->p.fbit + 2 * mw; w->p.lost = (int32_t *)c->pm.b_lost.p; // (as ensure_condmargins<CmPin> laid them out)
+    w->v.p = &w->p;
 }
-// The re-annotation's set, once per re-annotation solve.  On top of the re-annotation margins (the out-edge bitmaps, d_t' and the pass's
-// verdicts: their ORF records come with them, a launch and a copy beside the reverse pass) and, when a contig was not solved again, of the
-// run's drop margins.  Reads what the solve and its margins left resident; writes only c->rd.
-static int ensure_redrops(phx_ctx *c, bool trees = false) {
-    if (c->done.redrop && (!trees || c->done.retrees)) return PHX_OK;
-    { const int rm = ensure_condmargins<CmPlain>(c); if (rm) return rm; }
-    if (any_unsolved(c)) { const int rd = ensure_drops(c); if (rd) return rd; }
-    RedropView v;
-    redrop_view(c, &v);
+
+// Family f's drop set, once per run (the run's) or per re-annotation solve, on top of the margins it reads and of the sets the contigs it
+// does not cover are laid out from: the run's on ensure_rev; the re-annotation's on its margins (the out-edge bitmaps, d_t' and the pass's
+// verdicts) and, when a contig was not solved again, on the run's set; the pinned on the pinned margins and on the re-annotation's set.
+// Reads what the solve and its margins left resident; writes only f's own set (trees: with the one-hop trees b_ps / b_ts, for the
+// replacements — a set computed without them gets k_dp_tree once more, counting into f's replacement set).  The run's kernels are launched
+// for the limb classes of every contig that has device distances, the others for those of the contigs they cover.
+static int ensure_dropset(phx_ctx *c, int f, bool trees = false) {
+    const FamilySets F = family_sets(c, f);
+    if (F.drops && (!trees || F.trees)) return PHX_OK;
+    int rc;
+    if (f == FAM_RUN) rc = ensure_rev(c);
+    else if (f == FAM_RE) { rc = ensure_condmargins<CmPlain>(c); if (!rc && any_unsolved(c)) rc = ensure_dropset(c, FAM_RUN); }
+    else { rc = ensure_condmargins<CmPin>(c); if (!rc) rc = ensure_dropset(c, FAM_RE); }
+    if (rc) return rc;
+    if (f == FAM_PIN) F.D.wide = 1;
+    const int run_nlm = f == FAM_RUN ? margins_nl_mask(c) : 0;
+    FamilyView w;
+    cond_view(c, f, &w);
     hipStream_t s = c->stream;
-    return drop_pass(c, c->rd, c->rr, c->done.redrop, c->done.retrees, trees, [&](size_t i) { return redrop_contig(c, i) ? c->h_qrec[i].n_path : 0; }, [&](int step, const DDrop &q) {
-        if (step == 0) phxk_redrop_trees(&v.b, &v.g, &v.rq, &v.r, v.qpath, &q, c->rd.nlm, s);
-        else if (step == 1) phxk_redrop_cand(&v.b, &v.g, &v.rq, &v.r, v.qpath, &q, c->rd.nlm, s);
-        else phxk_redrop_fix(&v.b, &v.g, &v.rq, &v.r, v.qpath, &q, c->rd.nlm, s);
+    return drop_pass(c, F.D, F.S, F.drops, F.trees, trees, [&](size_t i) { return family_covers(c, f, i) ? family_npath(c, f, i) : 0; }, [&](int step, const DDrop &q) {
+        w.v.lost = (int32_t *)F.D.b_lost.p; // (the pinned set's, as the pass laid it out; no other set has one)
+        phxk_drop_step(f, step, &w.b, &w.g, &w.v, &q, f == FAM_RUN ? run_nlm : F.D.nlm, s);
     });
+}
+
+// The layout of phx_drop_margins_flat (top FAM_RUN), phx_redrops_flat (FAM_RE) and phx_pindrops_flat (FAM_PIN), behind their
+// ensure_dropset: offsets and statuses, then every contig's CDS records from the set of its family, in path order.  `called` of a contig at
+// the run's level is against the genes phx_download* deliver — so ensure_exact and stage_run_genes run when there is such a contig, and only
+// then —, of a contig that was solved again against the genes the re-annotation call returns.  lost: null, or parallel to rec (0 outside
+// the pinned set).
+static int drops_out(phx_ctx *c, const char *who, int top, phx_gene_drop *rec, int32_t *lost, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
+    const bool run_level = top == FAM_RUN || any_unsolved(c);
+    if (run_level) { const int rx = ensure_exact(c); if (rx) return rx; }
+    try {
+    int64_t total = 0;
+    for (int i = 0; i < c->n; i++) { // records for every contig with status 0
+        const int f = family_of(c, top, (size_t)i);
+        offsets[i] = total;
+        status[i] = family_status(c, f, i);
+        if (status[i] != 0 || !family_covers(c, f, (size_t)i)) continue;
+        const phx_ctx::DropSet &D = family_sets(c, f).D;
+        total += drop_count(D, D.roff[(size_t)i], D.roff[(size_t)i + 1]);
+    }
+    offsets[c->n] = total;
+    if (total_out) *total_out = total;
+    if (!rec) return PHX_OK; // size query
+    if (cap < total) return PHX_E_ARG;
+    if (run_level) { const int rg = stage_run_genes(c); if (rg) return rg; }
+    std::vector<uint64_t> keys;
+    for (int i = 0; i < c->n; i++) {
+        if (offsets[i + 1] == offsets[i]) continue;
+        const int f = family_of(c, top, (size_t)i);
+        if (f == FAM_RUN) called_keys(c, i, keys);
+        else resolve_keys(c, i, c->h_qsel[(size_t)i], keys);
+        const phx_ctx::DropSet &D = family_sets(c, f).D;
+        drop_rows(D, D.roff[(size_t)i], D.roff[(size_t)i + 1], keys, rec + offsets[i], lost ? lost + offsets[i] : nullptr); // (records and `lost` are dropped together)
+    }
+    } catch (const std::bad_alloc &) { c->err = std::string("out of memory in ") + who; return PHX_E_NOMEM; }
+    return PHX_OK;
+}
+
+int phx_drop_margins_flat(phx_ctx *c, phx_gene_drop *rec, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
+    if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
+    { const int ra = after_run(c); if (ra) return ra; }
+    { const int rx = ensure_exact(c); if (rx) return rx; } // (ahead of the drop kernels here, as ever; drops_out asks again and finds it done)
+    { const int rd = ensure_dropset(c, FAM_RUN); if (rd) return rd; }
+    return drops_out(c, "phx_drop_margins_flat", FAM_RUN, rec, nullptr, cap, offsets, status, total_out);
 }
 
 int phx_redrops_flat(phx_ctx *c, phx_gene_drop *rec, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
     if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
     { const int ra = after_run(c); if (ra) return ra; }
     { const int rs = remarg_state(c, "phx_redrops_flat"); if (rs) return rs; } // before any kernel
-    { const int rd = ensure_redrops(c); if (rd) return rd; }
-    const phx_ctx::DropSet &D = c->rd;
-    try {
-    // the contigs that were not solved again: the run's drop margins, as phx_drop_margins_flat lays them out
-    const size_t n = (size_t)c->n;
-    std::vector<int64_t> off0(n + 1, 0);
-    std::vector<int32_t> st0(n, 0);
-    std::vector<phx_gene_drop> rec0;
-    if (any_unsolved(c)) {
-        int64_t t0 = 0;
-        { const int rd = phx_drop_margins_flat(c, nullptr, 0, off0.data(), st0.data(), &t0); if (rd) return rd; }
-        if (rec) {
-            rec0.resize((size_t)t0 + 1);
-            const int rd = phx_drop_margins_flat(c, rec0.data(), t0, off0.data(), st0.data(), &t0);
-            if (rd) return rd;
-        }
-    }
-    int64_t total = 0;
-    for (size_t i = 0; i < n; i++) {
-        offsets[i] = total;
-        if (!c->h_qsel[i]) { status[i] = st0[i]; total += off0[i + 1] - off0[i]; continue; }
-        status[i] = condmargins_status(c, (int)i);
-        if (status[i] == 0 && redrop_contig(c, i)) total += drop_count(D, D.roff[i], D.roff[i + 1]);
-    }
-    offsets[n] = total;
-    if (total_out) *total_out = total;
-    if (!rec) return PHX_OK; // size query
-    if (cap < total) return PHX_E_ARG;
-    std::vector<uint64_t> keys;
-    for (size_t i = 0; i < n; i++) {
-        if (offsets[i + 1] == offsets[i]) continue;
-        phx_gene_drop *dst = rec + offsets[i];
-        if (!c->h_qsel[i]) { memcpy(dst, rec0.data() + off0[i], (size_t)(off0[i + 1] - off0[i]) * sizeof(phx_gene_drop)); continue; }
-        resolve_keys(c, (int)i, c->h_qsel[i], keys);
-        drop_rows(D, D.roff[i], D.roff[i + 1], keys, dst);
-    }
-    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_redrops_flat"; return PHX_E_NOMEM; }
-    return PHX_OK;
-}
-
-int phx_redrops_ms(phx_ctx *c, float *ms) { return values_out<4>(c, ms, [](const phx_ctx *x) { return x->rd.ms; }); }
-int phx_redrop_stats(phx_ctx *c, int64_t *out) { return values_out<4>(c, out, [](const phx_ctx *x) { return x->rd.stats; }); }
-
-// ---- pinned drop margins (phx_drop.inc under MgPinDrop, DESIGN.md §32) ----
-// the contigs the pinned drop kernels cover (dp_on<MgPinDrop>), after ensure_condmargins<CmPin>
-static bool pindrop_contig(const phx_ctx *c, size_t i) { return re_mode_req(c->h_qsel[i]) && c->pm.h_sel[i] == 1 && !c->pm.mstat[i] && c->h_qrec[i].n_path >= 3; }
-
-// the pinned kernels' view of what the last re-annotation and its pinned margins left resident (after ensure_condmargins<CmPin>)
-struct PindropView {
-    DBatch b, qb;
-    DMarg g;
-    DReann rq;
-    DPmarg r;
-    const int32_t *qpath;
-};
-static void pindrop_view(phx_ctx *c, PindropView *v) {
-    fill_batch(c, &v->b);
-    margins_args(c, &v->g);
-    reann_batch(c, &v->qb, &v->rq);
-    const size_t mw = (size_t)c->tot_edge / 32 + 2;
-    condmargins_args(c, c->pm, mw, &v->r);
-    v->r.dt_stride = v->b.dist_stride + 1; v->r.rbit = v->r.fbit + 2 * mw; v->r.lost = (int32_t *)c->pm.b_lost.p; // (as ensure_condmargins<CmPin> laid them out)
-    v->qpath = (const int32_t *)c->b_qpath.p;
-}
-// The pinned set, once per re-annotation solve.  On top of the pinned margins (the three out-edge bitmaps, d_t' on one limb more and the
-// pass's verdicts), of the re-annotation drop margins for the contigs solved again without a required ORF and, through them, of the run's
-// for the contigs that were not solved again.  Reads what the solve and its margins left resident; writes only c->pd (trees: with the
-// one-hop trees pd.b_ps / b_ts, for the pinned replacements — a set computed without them gets k_dp_tree once more, counting into c->pr).
-static int ensure_pindrops(phx_ctx *c, bool trees = false) {
-    if (c->done.pindrop && (!trees || c->done.pintrees)) return PHX_OK;
-    { const int rm = ensure_condmargins<CmPin>(c); if (rm) return rm; }
-    { const int rd = ensure_redrops(c); if (rd) return rd; }
-    phx_ctx::DropSet &D = c->pd;
-    D.wide = 1;
-    PindropView v;
-    pindrop_view(c, &v);
-    hipStream_t s = c->stream;
-    return drop_pass(c, D, c->pr, c->done.pindrop, c->done.pintrees, trees, [&](size_t i) { return pindrop_contig(c, i) ? c->h_qrec[i].n_path : 0; }, [&](int step, const DDrop &q) {
-        int32_t *lost = (int32_t *)D.b_lost.p;
-        if (step == 0) phxk_pindrop_trees(&v.b, &v.g, &v.rq, &v.r, v.qpath, lost, &q, D.nlm, s);
-        else if (step == 1) phxk_pindrop_cand(&v.b, &v.g, &v.rq, &v.r, v.qpath, lost, &q, D.nlm, s);
-        else phxk_pindrop_fix(&v.b, &v.g, &v.rq, &v.r, v.qpath, lost, &q, D.nlm, s);
-    });
+    { const int rd = ensure_dropset(c, FAM_RE); if (rd) return rd; }
+    return drops_out(c, "phx_redrops_flat", FAM_RE, rec, nullptr, cap, offsets, status, total_out);
 }
 
 int phx_pindrops_flat(phx_ctx *c, phx_gene_drop *rec, int32_t *lost, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
     if (!c || (c->n > 0 && (!offsets || !status)) || (rec && !lost)) return PHX_E_ARG;
     { const int ra = after_run(c); if (ra) return ra; }
-    if (!c->done.reann) { c->err = "phx_pindrops_flat: no re-annotation of this run (call phx_constrain_flat or phx_curate_flat first)"; return PHX_E_STATE; } // before any kernel
-    { const int rd = ensure_pindrops(c); if (rd) return rd; }
-    try {
-    // the contigs that were not solved again: the run's drop margins, as phx_drop_margins_flat lays them out
-    const size_t n = (size_t)c->n;
-    std::vector<int64_t> off0(n + 1, 0);
-    std::vector<int32_t> st0(n, 0);
-    std::vector<phx_gene_drop> rec0;
-    if (any_unsolved(c)) {
-        int64_t t0 = 0;
-        { const int rd = phx_drop_margins_flat(c, nullptr, 0, off0.data(), st0.data(), &t0); if (rd) return rd; }
-        if (rec) {
-            rec0.resize((size_t)t0 + 1);
-            const int rd = phx_drop_margins_flat(c, rec0.data(), t0, off0.data(), st0.data(), &t0);
-            if (rd) return rd;
-        }
-    }
-    auto set_of = [&](size_t i) -> const phx_ctx::DropSet & { return re_mode_req(c->h_qsel[i]) ? c->pd : c->rd; };
-    auto covered = [&](size_t i) { return re_mode_req(c->h_qsel[i]) ? pindrop_contig(c, i) : redrop_contig(c, i); };
-    int64_t total = 0;
-    for (size_t i = 0; i < n; i++) {
-        offsets[i] = total;
-        if (!c->h_qsel[i]) { status[i] = st0[i]; total += off0[i + 1] - off0[i]; continue; }
-        status[i] = condmargins_status(c, (int)i);
-        if (status[i] == 0 && covered(i)) { const phx_ctx::DropSet &D = set_of(i); total += drop_count(D, D.roff[i], D.roff[i + 1]); }
-    }
-    offsets[n] = total;
-    if (total_out) *total_out = total;
-    if (!rec) return PHX_OK; // size query
-    if (cap < total) return PHX_E_ARG;
-    std::vector<uint64_t> keys;
-    for (size_t i = 0; i < n; i++) {
-        if (offsets[i + 1] == offsets[i]) continue;
-        phx_gene_drop *dst = rec + offsets[i];
-        const size_t k = (size_t)(offsets[i + 1] - offsets[i]);
-        if (!c->h_qsel[i]) { memcpy(dst, rec0.data() + off0[i], k * sizeof(phx_gene_drop)); memset(lost + offsets[i], 0, k * 4); continue; }
-        resolve_keys(c, (int)i, c->h_qsel[i], keys);
-        const phx_ctx::DropSet &D = set_of(i);
-        drop_rows(D, D.roff[i], D.roff[i + 1], keys, dst, lost + offsets[i]); // (records and `lost` are dropped together)
-    }
-    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_pindrops_flat"; return PHX_E_NOMEM; }
-    return PHX_OK;
+    { const int rs = pin_state(c, "phx_pindrops_flat"); if (rs) return rs; } // before any kernel
+    { const int rd = ensure_dropset(c, FAM_PIN); if (rd) return rd; }
+    return drops_out(c, "phx_pindrops_flat", FAM_PIN, rec, lost, cap, offsets, status, total_out);
 }
 
+int phx_drop_ms(phx_ctx *c, float *ms) { return values_out<4>(c, ms, [](const phx_ctx *x) { return x->dp.ms; }); }
+int phx_drop_stats(phx_ctx *c, int64_t *out) { return values_out<4>(c, out, [](const phx_ctx *x) { return x->dp.stats; }); }
+int phx_redrops_ms(phx_ctx *c, float *ms) { return values_out<4>(c, ms, [](const phx_ctx *x) { return x->rd.ms; }); }
+int phx_redrop_stats(phx_ctx *c, int64_t *out) { return values_out<4>(c, out, [](const phx_ctx *x) { return x->rd.stats; }); }
 // device time and counters of the last phx_pindrops_flat over the contigs that were solved again: the pinned pass's, plus §29's for the
 // contigs solved again without a required ORF (a batch without a pinned contig: phx_redrops_ms / phx_redrop_stats)
 int phx_pindrops_ms(phx_ctx *c, float *ms) {
@@ -1344,32 +1205,70 @@ int phx_pindrop_stats(phx_ctx *c, int64_t *out) {
     return values_out<4>(c, out, [&](const phx_ctx *) { return v; });
 }
 
-// ---- re-annotation replacements (phx_replace.inc under MgDrop, DESIGN.md §30) ----
-// Every record of rd.h_rec gets its replacement into c->rr (h_rec / h_genes / h_det at rd.roff's indices), once per re-annotation solve, on
-// top of ensure_redrops with the one-hop trees and, when a contig was not solved again, of the run's replacements.  Writes the rr set and
-// rd.b_ps / b_ts only (and, as §13 does on its own set, the scratch the drop kernels left: js / jt / gtab of rd).
-static int ensure_rereplacements(phx_ctx *c) {
-    if (c->done.rerepl) return PHX_OK;
-    { const int rd = ensure_redrops(c, true); if (rd) return rd; }
-    if (any_unsolved(c)) { const int rr = ensure_replacements(c); if (rr) return rr; }
-    phx_ctx::ReplSet &S = c->rr;
-    for (int k = 0; k < 3; k++) S.ms[k] = 0;
-    for (int k = 0; k < 5; k++) S.stats[k] = 0;
-    const int nlm = c->rd.nlm;
-    if (!nlm) { c->done.rerepl = true; return PHX_OK; } // (no contig was solved again with a path: nothing is allocated)
-    RedropView v;
-    redrop_view(c, &v);
-    DDrop q;
-    drop_args(c->rd, true, &q);
-    hipStream_t s = c->stream;
-    const int rc = replacement_pass(c, S, (size_t)c->rd.roff[(size_t)c->n], [&](int step, const DRepl &r) {
-        if (step == 0) phxk_rerepl_pick(&v.b, &v.g, &v.rq, &v.r, v.qpath, &q, &r, nlm, s);
-        else if (step == 1) phxk_rerepl_cross(&v.b, &v.g, &v.rq, &v.r, v.qpath, &q, &r, nlm, s);
-        else phxk_rerepl_walk(&v.b, &v.g, &v.rq, &v.r, v.qpath, &q, &r, step - 2, s);
-    }, "re-annotation replacements", "phx_rereplacements_flat");
+// Family f's replacement set: every record of its drop set gets its replacement (h_rec / h_genes / h_det at the drop set's roff), once per
+// run or per re-annotation solve, on top of ensure_dropset with the one-hop trees and of the replacements of the contigs f does not cover
+// (the re-annotation's: the run's when a contig was not solved again; the pinned: the re-annotation's, whose times and counters are then
+// this solve's).  Writes f's set and its drop set's b_ps / b_ts only (and the scratch the drop kernels left there: js / jt / gtab).
+// k_rp_walk follows DDrop.ps / ts until it meets a path node, so it may run only on trees a k_dp_tree of the same family wrote for this
+// solve: the launch below is reached only with the family's `trees` flag set by drop_pass and with both pointers of the DDrop it passes
+// non-null — the flag is reset with the family's `drops`, and drop_args gives the pointers for `trees` alone.
+static int ensure_replset(phx_ctx *c, int f) {
+    static const char *const what[3] = {"drop replacements", "re-annotation replacements", "pinned replacements"};
+    static const char *const over[3] = {"drop margins", "re-annotation drop margins", "pinned drop margins"};
+    static const char *const who[3] = {"phx_replacements_flat", "phx_rereplacements_flat", "phx_pinreplacements_flat"};
+    const FamilySets F = family_sets(c, f);
+    if (F.repl) return PHX_OK;
+    int rc = ensure_dropset(c, f, true);
+    if (!rc && f == FAM_RE && any_unsolved(c)) rc = ensure_replset(c, FAM_RUN);
+    if (!rc && f == FAM_PIN) rc = ensure_replset(c, FAM_RE);
     if (rc) return rc;
-    c->done.rerepl = true;
+    for (int k = 0; k < 3; k++) F.S.ms[k] = 0;
+    for (int k = 0; k < 5; k++) F.S.stats[k] = 0;
+    if (!F.D.nlm) { F.repl = true; return PHX_OK; } // (f covers no contig: nothing is allocated or launched)
+    DDrop q;
+    drop_args(F.D, true, &q);
+    if (!F.drops || !F.trees || !q.ps || !q.ts) { c->err = std::string(what[f]) + ": the " + over[f] + " kept no one-hop trees"; return PHX_E_STATE; }
+    const int nlm = f == FAM_RUN ? margins_nl_mask(c) : F.D.nlm;
+    FamilyView w;
+    cond_view(c, f, &w);
+    w.v.lost = (int32_t *)F.D.b_lost.p; // (k_dp_rec's: no kernel here writes it)
+    hipStream_t s = c->stream;
+    rc = replacement_pass(c, F.S, (size_t)F.D.roff[(size_t)c->n], [&](int step, const DRepl &r) { phxk_repl_step(f, step, &w.b, &w.g, &w.v, &q, &r, nlm, s); }, what[f], who[f]);
+    if (rc) return rc;
+    F.repl = true;
     return PHX_OK;
+}
+
+// The layout of phx_replacements_flat, phx_rereplacements_flat and phx_pinreplacements_flat (top as drops_out's), behind their
+// ensure_replset: statuses, offsets, `called` and `lost` exactly as the drop records of the same level have them — one size query and one
+// fill of drops_out —, rows and genes from the replacement set of every contig's family.
+static int replacements_out(phx_ctx *c, const char *who, int top, phx_gene_repl *rec, int32_t *lost, int64_t cap, phx_gene *genes, int64_t gene_cap, int64_t *offsets, int32_t *status,
+                            int64_t *total_out, int64_t *gene_total_out) {
+    int64_t total = 0, gt = 0;
+    { const int rd = drops_out(c, who, top, nullptr, nullptr, 0, offsets, status, &total); if (rd) return rd; }
+    auto each_contig = [&](auto fn) { // fn(contig, its family's sets) for every contig with records
+        for (int i = 0; i < c->n; i++) if (offsets[i + 1] != offsets[i]) fn((size_t)i, family_sets(c, family_of(c, top, (size_t)i)));
+    };
+    each_contig([&](size_t i, const FamilySets &F) { gt += replacement_genes(F.S, F.D.roff[i], F.D.roff[i + 1]); });
+    if (total_out) *total_out = total;
+    if (gene_total_out) *gene_total_out = gt;
+    if (!rec || !genes) return PHX_OK; // size query
+    if (cap < total || gene_cap < gt) return PHX_E_ARG;
+    try {
+    std::vector<phx_gene_drop> drec((size_t)total + 1);
+    { const int rd = drops_out(c, who, top, drec.data(), lost, total, offsets, status, &total); if (rd) return rd; }
+    int64_t go = 0;
+    each_contig([&](size_t i, const FamilySets &F) { replacement_rows(F.S, F.D.roff[i], F.D.roff[i + 1], drec.data() + offsets[i], rec + offsets[i], genes, &go); });
+    } catch (const std::bad_alloc &) { c->err = std::string("out of memory in ") + who; return PHX_E_NOMEM; }
+    return PHX_OK;
+}
+
+int phx_replacements_flat(phx_ctx *c, phx_gene_repl *rec, int64_t cap, phx_gene *genes, int64_t gene_cap, int64_t *offsets, int32_t *status,
+                          int64_t *total_out, int64_t *gene_total_out) {
+    if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
+    { const int ra = after_run(c); if (ra) return ra; }
+    { const int rr = ensure_replset(c, FAM_RUN); if (rr) return rr; }
+    return replacements_out(c, "phx_replacements_flat", FAM_RUN, rec, nullptr, cap, genes, gene_cap, offsets, status, total_out, gene_total_out);
 }
 
 int phx_rereplacements_flat(phx_ctx *c, phx_gene_repl *rec, int64_t cap, phx_gene *genes, int64_t gene_cap, int64_t *offsets, int32_t *status,
@@ -1377,140 +1276,61 @@ int phx_rereplacements_flat(phx_ctx *c, phx_gene_repl *rec, int64_t cap, phx_gen
     if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
     { const int ra = after_run(c); if (ra) return ra; }
     { const int rs = remarg_state(c, "phx_rereplacements_flat"); if (rs) return rs; } // before any kernel
-    { const int rr = ensure_rereplacements(c); if (rr) return rr; }
-    // statuses, offsets and `called` exactly as the re-annotation's drop records have them
-    int64_t total = 0;
-    { const int rd = phx_redrops_flat(c, nullptr, 0, offsets, status, &total); if (rd) return rd; }
-    try {
-    std::vector<phx_gene_drop> drec((size_t)total + 1);
-    { const int rd = phx_redrops_flat(c, drec.data(), total, offsets, status, &total); if (rd) return rd; }
-    // a contig that was not solved again: the run's records, as phx_replacements_flat lays them out
-    auto set_of = [&](int i, int64_t *k0, int64_t *k1) -> const phx_ctx::ReplSet & {
-        const bool again = c->h_qsel[(size_t)i] != 0;
-        const std::vector<int64_t> &ro = again ? c->rd.roff : c->dp.roff;
-        *k0 = ro[(size_t)i]; *k1 = ro[(size_t)i + 1];
-        return again ? c->rr : c->rp;
-    };
-    int64_t gt = 0, k0, k1;
-    for (int i = 0; i < c->n; i++)
-        if (offsets[i + 1] != offsets[i]) { const phx_ctx::ReplSet &S = set_of(i, &k0, &k1); gt += replacement_genes(S, k0, k1); }
-    if (total_out) *total_out = total;
-    if (gene_total_out) *gene_total_out = gt;
-    if (!rec || !genes) return PHX_OK; // size query
-    if (cap < total || gene_cap < gt) return PHX_E_ARG;
-    int64_t go = 0;
-    for (int i = 0; i < c->n; i++)
-        if (offsets[i + 1] != offsets[i]) { const phx_ctx::ReplSet &S = set_of(i, &k0, &k1); replacement_rows(S, k0, k1, drec.data() + offsets[i], rec + offsets[i], genes, &go); }
-    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_rereplacements_flat"; return PHX_E_NOMEM; }
-    return PHX_OK;
-}
-
-int phx_tap_rereplacement(phx_ctx *c, int32_t contig, int32_t k, int32_t *path, int32_t cap, int32_t *n_path) {
-    if (!c || !n_path) return PHX_E_ARG;
-    *n_path = 0;
-    { const int ra = after_run(c); if (ra) return ra; }
-    if (contig < 0 || contig >= c->n || k < 0) return PHX_E_ARG;
-    { const int rs = remarg_state(c, "phx_tap_rereplacement"); if (rs) return rs; }
-    if (!c->h_qsel[(size_t)contig]) return phx_tap_replacement(c, contig, k, path, cap, n_path); // the run's result stands
-    { const int rr = ensure_rereplacements(c); if (rr) return rr; }
-    if (!redrop_contig(c, (size_t)contig) || condmargins_status(c, contig) != 0) return PHX_E_ARG;
-    const DMeta &m = c->meta[(size_t)contig];
-    return replacement_tap(c, c->rr, "phx_tap_rereplacement", contig, c->rd.roff[(size_t)contig], c->rd.roff[(size_t)contig + 1], k, (const int32_t *)c->b_qpath.p + m.node_off,
-                           c->h_qrec[(size_t)contig].n_path, path, cap, n_path);
-}
-
-int phx_rereplacements_ms(phx_ctx *c, float *ms) { return values_out<3>(c, ms, [](const phx_ctx *x) { return x->rr.ms; }); }
-int phx_rereplacement_stats(phx_ctx *c, int64_t *out) { return values_out<5>(c, out, [](const phx_ctx *x) { return x->rr.stats; }); }
-
-// ---- pinned replacements (phx_replace.inc under MgPinDrop, DESIGN.md §33) ----
-// Every record of pd.h_rec gets its replacement into c->pr (h_rec / h_genes / h_det at pd.roff's indices, `lost` from pd.h_lost beside them),
-// once per re-annotation solve, on top of ensure_pindrops with the one-hop trees and of the replacements of the contigs the pinned kernels do
-// not cover (§30's for modes 1 / 3, §13's for a contig that was not solved again).  Writes the pr set and pd.b_ps / b_ts only (and, as §13
-// does on its own set, the scratch the drop kernels left: js / jt / gtab of pd).
-// k_rp_walk follows DDrop.ps / ts until it meets a path node, so it may run only on trees k_dp_tree<NL, MgPinDrop> wrote for this solve: the
-// launch below is reached only with done.pintrees set by drop_pass and with both pointers of the DDrop it passes non-null — the flag is
-// reset with done.pindrop, and drop_args gives the pointers for `trees` alone.
-static int ensure_pinreplacements(phx_ctx *c) {
-    if (c->done.pinrepl) return PHX_OK;
-    { const int rd = ensure_pindrops(c, true); if (rd) return rd; }
-    { const int rr = ensure_rereplacements(c); if (rr) return rr; } // (modes 1 / 3; the run's replacements when a contig was not solved again; rr's times and counters are this solve's)
-    phx_ctx::ReplSet &S = c->pr;
-    for (int k = 0; k < 3; k++) S.ms[k] = 0;
-    for (int k = 0; k < 5; k++) S.stats[k] = 0;
-    S.h_lost.clear();
-    const int nlm = c->pd.nlm;
-    if (!nlm) { c->done.pinrepl = true; return PHX_OK; } // (no pinned contig with a path: nothing is allocated)
-    DDrop q;
-    drop_args(c->pd, true, &q);
-    if (!c->done.pindrop || !c->done.pintrees || !q.ps || !q.ts) { c->err = "pinned replacements: the pinned drop margins kept no one-hop trees"; return PHX_E_STATE; }
-    PindropView v;
-    pindrop_view(c, &v);
-    int32_t *lost = (int32_t *)c->pd.b_lost.p;
-    hipStream_t s = c->stream;
-    const size_t R = (size_t)c->pd.roff[(size_t)c->n];
-    const int rc = replacement_pass(c, S, R, [&](int step, const DRepl &r) {
-        if (step == 0) phxk_pinrepl_pick(&v.b, &v.g, &v.rq, &v.r, v.qpath, lost, &q, &r, nlm, s);
-        else if (step == 1) phxk_pinrepl_cross(&v.b, &v.g, &v.rq, &v.r, v.qpath, lost, &q, &r, nlm, s);
-        else phxk_pinrepl_walk(&v.b, &v.g, &v.rq, &v.r, v.qpath, lost, &q, &r, step - 2, s);
-    }, "pinned replacements", "phx_pinreplacements_flat");
-    if (rc) return rc;
-    try { S.h_lost.assign(c->pd.h_lost.begin(), c->pd.h_lost.begin() + (ptrdiff_t)R); } catch (const std::bad_alloc &) { c->err = "out of memory in phx_pinreplacements_flat"; return PHX_E_NOMEM; }
-    c->done.pinrepl = true;
-    return PHX_OK;
-}
-
-// the replacement set contig i's records are in, and their place in it: pr over pd's records (modes 2 / 4), rr over rd's (1 / 3), rp over dp's (0)
-static phx_ctx::ReplSet &pinrepl_set(phx_ctx *c, size_t i, int64_t *k0, int64_t *k1) {
-    const int mode = c->h_qsel[i];
-    const std::vector<int64_t> &ro = re_mode_req(mode) ? c->pd.roff : (mode ? c->rd.roff : c->dp.roff);
-    *k0 = ro[i]; *k1 = ro[i + 1];
-    return re_mode_req(mode) ? c->pr : (mode ? c->rr : c->rp);
+    { const int rr = ensure_replset(c, FAM_RE); if (rr) return rr; }
+    return replacements_out(c, "phx_rereplacements_flat", FAM_RE, rec, nullptr, cap, genes, gene_cap, offsets, status, total_out, gene_total_out);
 }
 
 int phx_pinreplacements_flat(phx_ctx *c, phx_gene_repl *rec, int32_t *lost, int64_t cap, phx_gene *genes, int64_t gene_cap, int64_t *offsets, int32_t *status,
                              int64_t *total_out, int64_t *gene_total_out) {
     if (!c || (c->n > 0 && (!offsets || !status)) || (rec && !lost)) return PHX_E_ARG;
     { const int ra = after_run(c); if (ra) return ra; }
-    if (!c->done.reann) { c->err = "phx_pinreplacements_flat: no re-annotation of this run (call phx_constrain_flat or phx_curate_flat first)"; return PHX_E_STATE; } // before any kernel
-    { const int rr = ensure_pinreplacements(c); if (rr) return rr; }
-    // statuses, offsets, `called` and `lost` exactly as the pinned drop records have them
-    int64_t total = 0;
-    { const int rd = phx_pindrops_flat(c, nullptr, nullptr, 0, offsets, status, &total); if (rd) return rd; }
-    try {
-    std::vector<phx_gene_drop> drec((size_t)total + 1);
-    std::vector<int32_t> dlost((size_t)total + 1);
-    { const int rd = phx_pindrops_flat(c, drec.data(), dlost.data(), total, offsets, status, &total); if (rd) return rd; }
-    int64_t gt = 0, k0, k1;
-    for (int i = 0; i < c->n; i++)
-        if (offsets[i + 1] != offsets[i]) { const phx_ctx::ReplSet &S = pinrepl_set(c, (size_t)i, &k0, &k1); gt += replacement_genes(S, k0, k1); }
-    if (total_out) *total_out = total;
-    if (gene_total_out) *gene_total_out = gt;
-    if (!rec || !genes) return PHX_OK; // size query
-    if (cap < total || gene_cap < gt) return PHX_E_ARG;
-    int64_t go = 0;
-    for (int i = 0; i < c->n; i++)
-        if (offsets[i + 1] != offsets[i]) { const phx_ctx::ReplSet &S = pinrepl_set(c, (size_t)i, &k0, &k1); replacement_rows(S, k0, k1, drec.data() + offsets[i], rec + offsets[i], genes, &go, lost + offsets[i]); }
-    } catch (const std::bad_alloc &) { c->err = "out of memory in phx_pinreplacements_flat"; return PHX_E_NOMEM; }
-    return PHX_OK;
+    { const int rs = pin_state(c, "phx_pinreplacements_flat"); if (rs) return rs; } // before any kernel
+    { const int rr = ensure_replset(c, FAM_PIN); if (rr) return rr; }
+    return replacements_out(c, "phx_pinreplacements_flat", FAM_PIN, rec, lost, cap, genes, gene_cap, offsets, status, total_out, gene_total_out);
 }
 
-int phx_tap_pinreplacement(phx_ctx *c, int32_t contig, int32_t k, int32_t *path, int32_t cap, int32_t *n_path) {
+// The three path taps.  The head they share: the arguments, *n_path = 0 and the run ...
+static int replacement_tap_pre(phx_ctx *c, int32_t contig, int32_t k, int32_t *n_path) {
     if (!c || !n_path) return PHX_E_ARG;
     *n_path = 0;
     { const int ra = after_run(c); if (ra) return ra; }
-    if (contig < 0 || contig >= c->n || k < 0) return PHX_E_ARG;
-    if (!c->done.reann) { c->err = "phx_tap_pinreplacement: no re-annotation of this run (call phx_constrain_flat or phx_curate_flat first)"; return PHX_E_STATE; }
-    const int mode = c->h_qsel[(size_t)contig];
-    if (!mode) return phx_tap_replacement(c, contig, k, path, cap, n_path); // the run's result stands
-    { const int rr = ensure_pinreplacements(c); if (rr) return rr; }
-    // (a contig of mode 1 / 3: §30's tap on the rr set — phx_tap_rereplacement itself refuses a solve that pinned another contig)
-    if (!(re_mode_req(mode) ? pindrop_contig(c, (size_t)contig) : redrop_contig(c, (size_t)contig)) || condmargins_status(c, contig) != 0) return PHX_E_ARG;
-    int64_t k0, k1;
-    phx_ctx::ReplSet &S = pinrepl_set(c, (size_t)contig, &k0, &k1);
-    const DMeta &m = c->meta[(size_t)contig];
-    return replacement_tap(c, S, "phx_tap_pinreplacement", contig, k0, k1, k, (const int32_t *)c->b_qpath.p + m.node_off, c->h_qrec[(size_t)contig].n_path, path, cap, n_path);
+    return contig < 0 || contig >= c->n || k < 0 ? PHX_E_ARG : PHX_OK;
+}
+// ... and, behind the entry point's state rule, the rest: a contig that was not solved again is the run's tap's (its result stands); any
+// other gets the replacements of level `top` and is read from its family's sets, on the re-annotation's path.
+static int replacement_path_out(phx_ctx *c, const char *who, int top, int32_t contig, int32_t k, int32_t *path, int32_t cap, int32_t *n_path) {
+    const size_t i = (size_t)contig;
+    const int f = family_of(c, top, i);
+    if (f != top && f == FAM_RUN) return phx_tap_replacement(c, contig, k, path, cap, n_path);
+    { const int rr = ensure_replset(c, top); if (rr) return rr; }
+    if (!family_covers(c, f, i) || family_status(c, f, contig) != 0) return PHX_E_ARG;
+    const FamilySets F = family_sets(c, f);
+    const int32_t *dpath = (const int32_t *)(f == FAM_RUN ? c->b_path.p : c->b_qpath.p) + c->meta[i].node_off;
+    return replacement_tap(c, F.S, who, contig, F.D.roff[i], F.D.roff[i + 1], k, dpath, family_npath(c, f, i), path, cap, n_path);
 }
 
+int phx_tap_replacement(phx_ctx *c, int32_t contig, int32_t k, int32_t *path, int32_t cap, int32_t *n_path) {
+    { const int rp = replacement_tap_pre(c, contig, k, n_path); if (rp) return rp; }
+    return replacement_path_out(c, "phx_tap_replacement", FAM_RUN, contig, k, path, cap, n_path);
+}
+
+int phx_tap_rereplacement(phx_ctx *c, int32_t contig, int32_t k, int32_t *path, int32_t cap, int32_t *n_path) {
+    { const int rp = replacement_tap_pre(c, contig, k, n_path); if (rp) return rp; }
+    { const int rs = remarg_state(c, "phx_tap_rereplacement"); if (rs) return rs; }
+    return replacement_path_out(c, "phx_tap_rereplacement", FAM_RE, contig, k, path, cap, n_path);
+}
+
+// (a contig of mode 1 / 3: §30's records in the rr set — phx_tap_rereplacement itself refuses a solve that pinned another contig)
+int phx_tap_pinreplacement(phx_ctx *c, int32_t contig, int32_t k, int32_t *path, int32_t cap, int32_t *n_path) {
+    { const int rp = replacement_tap_pre(c, contig, k, n_path); if (rp) return rp; }
+    { const int rs = pin_state(c, "phx_tap_pinreplacement"); if (rs) return rs; }
+    return replacement_path_out(c, "phx_tap_pinreplacement", FAM_PIN, contig, k, path, cap, n_path);
+}
+
+int phx_replacements_ms(phx_ctx *c, float *ms) { return values_out<3>(c, ms, [](const phx_ctx *x) { return x->rp.ms; }); }
+int phx_replacement_stats(phx_ctx *c, int64_t *out) { return values_out<5>(c, out, [](const phx_ctx *x) { return x->rp.stats; }); }
+int phx_rereplacements_ms(phx_ctx *c, float *ms) { return values_out<3>(c, ms, [](const phx_ctx *x) { return x->rr.ms; }); }
+int phx_rereplacement_stats(phx_ctx *c, int64_t *out) { return values_out<5>(c, out, [](const phx_ctx *x) { return x->rr.stats; }); }
 // device time and counters of the last phx_pinreplacements_flat over the contigs that were solved again: the pinned pass's, plus §30's for the
 // contigs solved again without a required ORF (a batch without a pinned contig: phx_rereplacements_ms / phx_rereplacement_stats)
 int phx_pinreplacements_ms(phx_ctx *c, float *ms) {

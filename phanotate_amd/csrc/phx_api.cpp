@@ -245,7 +245,7 @@ struct phx_ctx {
         bool retrees = false; // ... and the drop kernels kept that graph's one-hop trees (rd.b_ps / b_ts; reset wherever redrop is)
         bool pindrop = false; // pd.h_rec / pd.h_lost hold the pinned drop margins of the re-annotation h_q* hold, at pd.roff (reset wherever pinmarg is)
         bool pintrees = false; // ... and the drop kernels kept that graph's one-hop trees (pd.b_ps / b_ts: the pinned replacements ask for them; reset wherever pindrop is)
-        bool pinrepl = false;  // pr.h_rec / h_genes / h_det / h_lost hold the pinned replacements of the re-annotation h_q* hold (reset wherever pindrop is)
+        bool pinrepl = false;  // pr.h_rec / h_genes / h_det hold the pinned replacements of the re-annotation h_q* hold (reset wherever pindrop is)
         bool rerepl = false;  // rr.h_rec / h_genes / h_det hold the replacements of the re-annotation h_q* hold (reset wherever redrop is)
         bool profile = false; // pf.h_rec holds the slots' records of every covered contig, at pf.roff
         bool grp = false;     // h_grp
@@ -286,7 +286,7 @@ struct phx_ctx {
     // (rp: the run's set.  rr: the set of the re-annotation replacements, phx_rereplacements_flat, DESIGN.md §30 — allocated at the first call
     // that has a solved-again contig for it, the result kept until the next re-annotation solve or run; rp is not touched by it.  pr: the set
     // of the pinned replacements, phx_pinreplacements_flat, §33 — allocated at the first call that has a pinned contig for it, over the pd set's
-    // records, with their `lost` beside h_rec; kept as rr is, and neither rp nor rr is touched by it.)
+    // records (whose `lost` is the rows' too); kept as rr is, and neither rp nor rr is touched by it.)
     struct ReplSet {
         DevBuf b_win, b_xs, b_coff, b_cm, b_chain, b_rnd, b_info, b_doff, b_det, b_genes, b_rec, b_cnt; // DRepl
         std::vector<phx_gene_repl> h_rec; // per device record (as DropSet::h_rec); gene_off into h_genes
@@ -297,7 +297,6 @@ struct phx_ctx {
         int64_t chain_cap = 0;            // delta-chain nodes b_chain has room for
         float ms[3] = {0, 0, 0};
         int64_t stats[5] = {0, 0, 0, 0, 0};
-        std::vector<int32_t> h_lost;      // per device record: `lost` (pr alone; the other sets: empty, and every row's is 0)
     } rp, rr, pr;
     // masked re-annotation (phx_reannotate_flat): buffers allocated at the first call, the result kept until the next upload or run
     DevBuf b_qmeta, b_qtot, b_qdist, b_qparent, b_qpath, b_qgenes, b_qgtot, b_qtie, b_qmask, b_qforb, b_qsel, b_qplan, b_qrec;

@@ -501,6 +501,16 @@ struct DPmarg {
     int32_t *mstat;        // per contig: 1 the reverse pass hit its caps; zeroed by the host
 };
 
+// What the drop margins and replacements of a re-annotation's graph read beside the run's DMarg (host side: the launchers build MgDrop /
+// MgPinDrop from it, phx_drop.inc); all null for the run's own
+struct DCondView {
+    const DReann *rq;     // what the re-annotation left resident,
+    const DRmarg *r;      //   its margins (§29, §30)
+    const DPmarg *p;      //   or its pinned margins (§32, §33),
+    const int32_t *qpath; //   its path buffer (laid out like DBatch.path)
+    int32_t *lost;        // §32, §33: one int32 per record of the DDrop set, parallel to DDrop.rec
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -545,32 +555,15 @@ void phxk_results(const DBatch *b, void *stream);
 void phxk_margins_transpose(const DBatch *b, const DMarg *g, void *stream); // out_off (zeroed by the caller) / out_dst / out_w from in_off / esrc / ew
 void phxk_sssp_rev(const DBatch *b, const DMarg *g, int nl_mask, void *stream); // dist_t of every contig of the limb classes in nl_mask (bit k: 2, 4, 8, 17 limbs)
 void phxk_margins(const DBatch *b, const DMarg *g, int nl_mask, void *stream); // the ORF records // after every solver kernel of the run: parents as the reference's in-place Bellman-Ford leaves them
-void phxk_drop_trees(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream); // gene drop margins (phx_drop.inc): trees + labels,
-void phxk_drop_cand(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream);  //   candidates + sparse table,
-void phxk_drop_fix(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream);   //   saturated slots, cross nodes, records
-// re-annotation drop margins (§29; b: the run's batch, rq / r: what the re-annotation and its margins left resident, qpath: the re-annotation's
-// path buffer, q: the feature's own DDrop set; nl_mask: the classes among DRmarg.sel == 1): the three steps of the drop margins under MgDrop
-void phxk_redrop_trees(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, int nl_mask, void *stream);
-void phxk_redrop_cand(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, int nl_mask, void *stream);
-void phxk_redrop_fix(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, int nl_mask, void *stream);
-// pinned drop margins (§32; r: what the pinned margins left resident, lost: one int32 per record of q; nl_mask: the classes among DPmarg.sel == 1,
-// the kernels work on one limb more): the three steps of the drop margins under MgPinDrop
-void phxk_pindrop_trees(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, int nl_mask, void *stream);
-void phxk_pindrop_cand(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, int nl_mask, void *stream);
-void phxk_pindrop_fix(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, int nl_mask, void *stream);
+// gene drop margins (phx_drop.inc; §12, §29, §32): step 0 trees + labels, 1 candidates + sparse table, 2 saturated slots, cross nodes, records,
+// of `family` — 0 the run's (DMarg; v all null), 1 the re-annotation's (MgDrop: v->rq, r, qpath), 2 the pinned (MgPinDrop, on one limb more:
+// v->rq, p, qpath, lost).  b: the run's batch, q: the family's own DDrop set, nl_mask: the limb classes among the contigs the kernels cover.
+void phxk_drop_step(int family, int step, const DBatch *b, const DMarg *g, const DCondView *v, const DDrop *q, int nl_mask, void *stream);
 void phxk_profile_cand(const DBatch *b, const DMarg *g, const DProf *q, int nl_mask, void *stream); // coding profiles (phx_profile.inc): candidates, tables and push-down per track,
 void phxk_profile_rec(const DBatch *b, const DMarg *g, const DProf *q, void *stream);                //   the slots' bounds
-void phxk_repl_pick(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream); // drop replacements (phx_replace.inc): winners,
-void phxk_repl_cross(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream); //   cross winners and their delta chains,
-void phxk_repl_walk(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int fill, void *stream);    //   detour lengths (fill 0) / detours, genes, records (1)
-// re-annotation replacements (§30; the arguments of phxk_redrop_*, q with DDrop.ps / ts, rr: the feature's own DRepl set): the three steps under MgDrop
-void phxk_rerepl_pick(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, const DRepl *rr, int nl_mask, void *stream);
-void phxk_rerepl_cross(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, const DRepl *rr, int nl_mask, void *stream);
-void phxk_rerepl_walk(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, const DRepl *rr, int fill, void *stream);
-// pinned replacements (§33; the arguments of phxk_pindrop_*, q with DDrop.ps / ts, pr: the feature's own DRepl set): the three steps under MgPinDrop
-void phxk_pinrepl_pick(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, const DRepl *pr, int nl_mask, void *stream);
-void phxk_pinrepl_cross(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, const DRepl *pr, int nl_mask, void *stream);
-void phxk_pinrepl_walk(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, const DRepl *pr, int fill, void *stream);
+// drop replacements (phx_replace.inc; §13, §30, §33): step 0 winners, 1 cross winners and their delta chains, 2 detour lengths, 3 detours,
+// genes, records, of `family` — q: its DDrop set with DDrop.ps / ts, r: its own DRepl set (nl_mask: as phxk_drop_step; the walks take none)
+void phxk_repl_step(int family, int step, const DBatch *b, const DMarg *g, const DCondView *v, const DDrop *q, const DRepl *r, int nl_mask, void *stream);
 // re-annotation (phx_resolve.inc).  b: the re-annotation's view of the batch; nl_masks[RE_MODES]: per mode, the limb classes of its contigs
 void phxk_reann_mask(const DBatch *b, const DReann *q, void *stream);                         // the refused, required and biased ORFs' marks,
 void phxk_reann_solve(const DBatch *b, const DReann *q, const int *nl_masks, void *stream);   //   the sweep under each mode's policy,

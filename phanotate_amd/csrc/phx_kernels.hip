@@ -444,6 +444,39 @@ template <class Mg, class R> static void mg_rev(const DBatch *b, const DMarg *g,
 template <class Mg, class R> static void mg_records(const DBatch *b, const DMarg *g, const DReann *q, const R *r, int nl_mask, void *stream) {
     each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_margins<decltype(nl)::value, Mg>), dim3(b->n_contig, ysplit(b, 8)), dim3(NT), 0, (hipStream_t)stream, *b, mg_args<Mg>(g, q, r)); });
 }
+// The gene drop margins (phx_drop.inc) and the drop replacements (phx_replace.inc) under a policy G, a workgroup per contig and the argument
+// block by value: DMarg on the run's graph (§12, §13); MgDrop on a re-annotation's (§29, §30) — the run's graph and out-edge CSR, the
+// re-annotation's policy, d_s', d_t' and path (qpath: its path buffer, laid out like DBatch.path); MgPinDrop for the contigs solved under the
+// required policy (§32, §33) — values on one limb more, DPmarg's d_t' and bitmaps, `lost` one int32 per record of the DDrop set, parallel to
+// DDrop.rec, written by k_dp_rec alone.
+static MgDrop dp_args(const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath) { MgDrop c = mg_args<MgDrop>(g, rq, r); c.path = qpath; return c; }
+static MgPinDrop pdp_args(const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost) { MgPinDrop c = mg_args<MgPinDrop>(g, rq, r); c.path = qpath; c.lost = lost; return c; }
+// fn(the argument block of family 0: the run's, 1: the re-annotation's, 2: the pinned)
+template <class F> static void with_family(int family, const DMarg *g, const DCondView *v, F fn) {
+    if (family == 0) fn(*g);
+    else if (family == 1) fn(dp_args(g, v->rq, v->r, v->qpath));
+    else fn(pdp_args(g, v->rq, v->p, v->qpath, v->lost));
+}
+// step 0: trees + labels, 1: candidates + sparse table, 2: saturated slots, cross nodes, records; one launch per limb class and kernel
+template <class G> static void dp_step(int step, const DBatch *b, const G &args, const DDrop *q, int nl_mask, hipStream_t s) {
+    const dim3 grid(b->n_contig), block(NT);
+    if (step == 0) each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_tree<decltype(nl)::value, G>), grid, block, 0, s, *b, args, *q); });
+    else if (step == 1) each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_cand<decltype(nl)::value, G>), grid, block, 0, s, *b, args, *q); });
+    else {
+        each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_rescan<decltype(nl)::value, G>), grid, block, 0, s, *b, args, *q); });
+        each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_cross<decltype(nl)::value, G>), grid, block, 0, s, *b, args, *q); });
+        each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_rec<decltype(nl)::value, G>), grid, block, 0, s, *b, args, *q); });
+    }
+}
+// step 0: winners, 1: cross winners and their delta chains, 2: detour lengths, 3: detours, genes, records (the walks: one launch for every class)
+template <class G> static void rp_step(int step, const DBatch *b, const G &args, const DDrop *q, const DRepl *r, int nl_mask, hipStream_t s) {
+    const dim3 grid(b->n_contig), block(NT);
+    if (step == 0) each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_rp_pick<decltype(nl)::value, G>), grid, block, 0, s, *b, args, *q, *r); });
+    else if (step == 1) each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_rp_cross<decltype(nl)::value, G>), grid, block, 0, s, *b, args, *q, *r); });
+    // (k_rp_walk<1> is named ahead of <0>, as it always was: the order of instantiation is the order of the symbols in the code object)
+    else if (step == 3) hipLaunchKernelGGL((k_rp_walk<1, G>), grid, block, 0, s, *b, args, *q, *r);
+    else hipLaunchKernelGGL((k_rp_walk<0, G>), grid, block, 0, s, *b, args, *q, *r);
+}
 extern "C" {
 void phxk_remarg_apply(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, void *stream) { mg_apply(b, g, q, r, stream); }
 void phxk_remarg_rev(const DBatch *b, const DMarg *g, const DReann *q, const DRmarg *r, int nl_mask, void *stream) { mg_rev<MgCond>(b, g, q, r, nl_mask, stream); }
@@ -451,50 +484,9 @@ void phxk_remarg_records(const DBatch *b, const DMarg *g, const DReann *q, const
 void phxk_pinmarg_apply(const DBatch *b, const DMarg *g, const DReann *q, const DPmarg *r, void *stream) { mg_apply(b, g, q, r, stream); }
 void phxk_pinmarg_rev(const DBatch *b, const DMarg *g, const DReann *q, const DPmarg *r, int nl_mask, void *stream) { mg_rev<MgPin>(b, g, q, r, nl_mask, stream); }
 void phxk_pinmarg_records(const DBatch *b, const DMarg *g, const DReann *q, const DPmarg *r, int nl_mask, void *stream) { mg_records<MgPin>(b, g, q, r, nl_mask, stream); }
-// gene drop margins (phx_drop.inc): a workgroup per contig, one launch per limb class and step
-void phxk_drop_trees(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream) {
-    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL(k_dp_tree<decltype(nl)::value>, dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, *g, *q); });
-}
-void phxk_drop_cand(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream) {
-    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL(k_dp_cand<decltype(nl)::value>, dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, *g, *q); });
-}
-void phxk_drop_fix(const DBatch *b, const DMarg *g, const DDrop *q, int nl_mask, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL(k_dp_rescan<decltype(nl)::value>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q); });
-    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL(k_dp_cross<decltype(nl)::value>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q); });
-    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL(k_dp_rec<decltype(nl)::value>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q); });
-}
-// re-annotation drop margins: the same five kernels under MgDrop — the run's graph and out-edge CSR, the re-annotation's
-// policy, d_s', d_t' and path (qpath: its path buffer, laid out like DBatch.path); q: a DDrop set of the feature's own
-static MgDrop dp_args(const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath) { MgDrop c = mg_args<MgDrop>(g, rq, r); c.path = qpath; return c; }
-void phxk_redrop_trees(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, int nl_mask, void *stream) {
-    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_tree<decltype(nl)::value, MgDrop>), dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, dp_args(g, rq, r, qpath), *q); });
-}
-void phxk_redrop_cand(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, int nl_mask, void *stream) {
-    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_cand<decltype(nl)::value, MgDrop>), dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, dp_args(g, rq, r, qpath), *q); });
-}
-void phxk_redrop_fix(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, int nl_mask, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    const MgDrop c = dp_args(g, rq, r, qpath);
-    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_rescan<decltype(nl)::value, MgDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, c, *q); });
-    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_cross<decltype(nl)::value, MgDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, c, *q); });
-    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_rec<decltype(nl)::value, MgDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, c, *q); });
-}
-// pinned drop margins: the same five kernels under MgPinDrop, for the contigs solved under the required policy — values on one
-// limb more, DPmarg's d_t' and bitmaps; lost: one int32 per record of q, parallel to DDrop.rec (nl_mask: the contigs' own classes)
-static MgPinDrop pdp_args(const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost) { MgPinDrop c = mg_args<MgPinDrop>(g, rq, r); c.path = qpath; c.lost = lost; return c; }
-void phxk_pindrop_trees(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, int nl_mask, void *stream) {
-    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_tree<decltype(nl)::value, MgPinDrop>), dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, pdp_args(g, rq, r, qpath, lost), *q); });
-}
-void phxk_pindrop_cand(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, int nl_mask, void *stream) {
-    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_cand<decltype(nl)::value, MgPinDrop>), dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, pdp_args(g, rq, r, qpath, lost), *q); });
-}
-void phxk_pindrop_fix(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, int nl_mask, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    const MgPinDrop c = pdp_args(g, rq, r, qpath, lost);
-    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_rescan<decltype(nl)::value, MgPinDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, c, *q); });
-    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_cross<decltype(nl)::value, MgPinDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, c, *q); });
-    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_dp_rec<decltype(nl)::value, MgPinDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, c, *q); });
+// gene drop margins (§12), the re-annotation's (§29) and the pinned (§32): one step of family `family` on its DDrop set q
+void phxk_drop_step(int family, int step, const DBatch *b, const DMarg *g, const DCondView *v, const DDrop *q, int nl_mask, void *stream) {
+    with_family(family, g, v, [&](const auto &args) { dp_step(step, b, args, q, nl_mask, (hipStream_t)stream); });
 }
 // coding profiles (phx_profile.inc): a workgroup per contig and limb class for the tables, then a thread per slot
 void phxk_profile_cand(const DBatch *b, const DMarg *g, const DProf *q, int nl_mask, void *stream) {
@@ -503,44 +495,10 @@ void phxk_profile_cand(const DBatch *b, const DMarg *g, const DProf *q, int nl_m
 void phxk_profile_rec(const DBatch *b, const DMarg *g, const DProf *q, void *stream) {
     hipLaunchKernelGGL(k_pf_rec<DMarg>, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), 0, (hipStream_t)stream, *b, *g, *q);
 }
-// drop replacements (phx_replace.inc): a workgroup per contig
-void phxk_repl_pick(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream) {
-    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL(k_rp_pick<decltype(nl)::value>, dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, *g, *q, *r); });
-}
-void phxk_repl_cross(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int nl_mask, void *stream) {
-    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL(k_rp_cross<decltype(nl)::value>, dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, *g, *q, *r); });
-}
-void phxk_repl_walk(const DBatch *b, const DMarg *g, const DDrop *q, const DRepl *r, int fill, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (fill) hipLaunchKernelGGL(k_rp_walk<1>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q, *r);
-    else hipLaunchKernelGGL(k_rp_walk<0>, dim3(b->n_contig), dim3(NT), 0, s, *b, *g, *q, *r);
-}
-// re-annotation replacements: the same three kernels under MgDrop, on the DDrop set of the re-annotation drop margins (q, with
-// its one-hop trees) and a DRepl set of the feature's own (rr)
-void phxk_rerepl_pick(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, const DRepl *rr, int nl_mask, void *stream) {
-    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_rp_pick<decltype(nl)::value, MgDrop>), dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, dp_args(g, rq, r, qpath), *q, *rr); });
-}
-void phxk_rerepl_cross(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, const DRepl *rr, int nl_mask, void *stream) {
-    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_rp_cross<decltype(nl)::value, MgDrop>), dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, dp_args(g, rq, r, qpath), *q, *rr); });
-}
-void phxk_rerepl_walk(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const int32_t *qpath, const DDrop *q, const DRepl *rr, int fill, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (fill) hipLaunchKernelGGL((k_rp_walk<1, MgDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, dp_args(g, rq, r, qpath), *q, *rr);
-    else hipLaunchKernelGGL((k_rp_walk<0, MgDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, dp_args(g, rq, r, qpath), *q, *rr);
-}
-// pinned replacements: the same three kernels under MgPinDrop, on the DDrop set of the pinned drop margins (q, with its
-// one-hop trees: the walk follows DDrop.ps / ts and is launched only behind a k_dp_tree<NL, MgPinDrop> that wrote them) and a DRepl set of
-// the feature's own (pr); `lost` is k_dp_rec's and no kernel here writes it
-void phxk_pinrepl_pick(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, const DRepl *pr, int nl_mask, void *stream) {
-    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_rp_pick<decltype(nl)::value, MgPinDrop>), dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, pdp_args(g, rq, r, qpath, lost), *q, *pr); });
-}
-void phxk_pinrepl_cross(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, const DRepl *pr, int nl_mask, void *stream) {
-    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_rp_cross<decltype(nl)::value, MgPinDrop>), dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, pdp_args(g, rq, r, qpath, lost), *q, *pr); });
-}
-void phxk_pinrepl_walk(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const int32_t *qpath, int32_t *lost, const DDrop *q, const DRepl *pr, int fill, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (fill) hipLaunchKernelGGL((k_rp_walk<1, MgPinDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, pdp_args(g, rq, r, qpath, lost), *q, *pr);
-    else hipLaunchKernelGGL((k_rp_walk<0, MgPinDrop>), dim3(b->n_contig), dim3(NT), 0, s, *b, pdp_args(g, rq, r, qpath, lost), *q, *pr);
+// drop replacements (§13), the re-annotation's (§30) and the pinned (§33): one step of family `family` on its DDrop set q (with the one-hop
+// trees: the walk follows DDrop.ps / ts and is launched only behind a k_dp_tree of the same family that wrote them) and its DRepl set r
+void phxk_repl_step(int family, int step, const DBatch *b, const DMarg *g, const DCondView *v, const DDrop *q, const DRepl *r, int nl_mask, void *stream) {
+    with_family(family, g, v, [&](const auto &args) { rp_step(step, b, args, q, r, nl_mask, (hipStream_t)stream); });
 }
 size_t phxk_sssp_lds_bytes(int V, int nl) { return sssp_lds_bytes(V, nl); }
 // re-annotation (phx_resolve.inc): b is the re-annotation's view of the batch (outputs of its own)

@@ -536,6 +536,65 @@ def test_pinreplacements_disturb_nothing_are_cached_and_invalidated(pa):
     ann.close()
 
 
+def test_the_three_sets_stay_apart_across_orders_and_batches(pa):
+    """The run's sets, the re-annotation's and the pinned ones share one host layer and must not share state.  One context,
+    two batches (fuzz(40, 3), then fuzz(42, 20): every set grows — the sizes of tests/test_redrops_gpu.py's test of this shape, with seed 40
+    where that has 41, whose three contigs call 1, 1 and 118 genes: 40 is the nearest seed with two contigs of two calls); per batch one
+    curate() call that pins the first contig with two called genes (a called gene of its own required), solves the second such contig again without a pin (a called gene refused, an uncalled ORF penalised)
+    and leaves every other contig to the run.  pinreplacements() comes first — it brings the pinned sets up with their trees, behind them
+    the re-annotation's with theirs and the run's, first without trees and then with the late tree launch —, then the other analyses and
+    every pinned path tap; then evidence() with the same refusals and bias and no required ORF, redrops() and rereplacements().  Everything
+    equals, byte for byte and counter for counter, what a fresh context gives in the plain order; the run's counters read the same before
+    and after the upper families' passes."""
+    from test_evidence_gpu import called_orfs
+
+    def the_sets(ann, st0, offs0, genes0):
+        n = ann.n
+        cg = {i: called_orfs(ann, i, genes0[offs0[i]:offs0[i + 1]]) for i in range(n) if st0[i] == 0}
+        two = [i for i in sorted(cg) if len(cg[i]) >= 2][:2]
+        assert len(two) == 2
+        p, q = two
+        bias, forbid, require = [None] * n, [None] * n, [None] * n
+        require[p] = [cg[p][len(cg[p]) // 2]]
+        forbid[q] = [cg[q][len(cg[q]) // 2]]
+        bias[q] = [(next(k for k in range(len(ann.orfs(q))) if k not in cg[q]), 1.5)]
+        return p, q, bias, forbid, require
+
+    def taps(ann, offs):
+        return [ann.pinreplacement_path(i, k).tobytes() for i in range(ann.n) for k in range(int(offs[i + 1] - offs[i]))]
+
+    def six(ann):
+        return (ann.drop_stats(), ann.replacement_stats(), ann.redrop_stats(), ann.rereplacement_stats(), ann.pindrop_stats(), ann.pinreplacement_stats())
+
+    ann = pa.Annotator()
+    for seqs in (fuzz(40, 3), fuzz(42, 20)):
+        p, q, bias, forbid, require = the_sets(ann, *run_batch(ann, seqs))
+        st = ann.curate(bias, forbid, require)[0]
+        pr = ann.pinreplacements()  # the first analysis call after the solve
+        got = dict(pr=all_bytes(pr), pd=all_bytes(ann.pindrops()), rp=all_bytes(ann.replacements()), dp=all_bytes(ann.drop_margins()), taps=taps(ann, pr[1]), six=six(ann))
+        ann.evidence(bias, forbid)
+        got.update(rd=all_bytes(ann.redrops()), rr=all_bytes(ann.rereplacements()), six2=six(ann))
+        assert st[p] == 0 and st[q] == 0 and pr[0][p] == 0 and pr[0][q] == 0
+        assert (out_of(pr, p)[2] > 0).any()  # the pinned contig's records are the pinned set's
+        fresh = pa.Annotator()
+        assert all_bytes(run_batch(fresh, seqs)) == all_bytes(ann.download_flat(exact=False))
+        want = dict(dp=all_bytes(fresh.drop_margins()))
+        run = fresh.replacements()
+        want.update(rp=all_bytes(run))
+        run_stats = (fresh.drop_stats(), fresh.replacement_stats())
+        fresh.curate(bias, forbid, require)
+        want.update(pd=all_bytes(fresh.pindrops()), pr=all_bytes(fresh.pinreplacements()), taps=taps(fresh, pr[1]), six=six(fresh))
+        fresh.evidence(bias, forbid)
+        want.update(rd=all_bytes(fresh.redrops()), rr=all_bytes(fresh.rereplacements()), six2=six(fresh))
+        assert run_stats == want["six"][:2] == want["six2"][:2]  # the upper families' passes left the run's counters alone
+        for key in ("dp", "rp", "pd", "pr", "taps", "six", "rd", "rr", "six2"):
+            assert got[key] == want[key], (len(seqs), key)
+        assert pin_bytes(pr, q)[:3] != contig_bytes(run, q)  # the contig solved again without a pin: the re-annotation's records, not the run's
+        assert all(s["slots"] > 0 for s in (got["six"][0], got["six"][2], got["six"][4]))  # every drop set covered a contig
+        fresh.close()
+    ann.close()
+
+
 # ---- 11. batch size and create flags ----
 def test_lone_contig_and_batch_of_300_give_the_same_bytes(pa):
     seqs = fuzz(23, 300)
