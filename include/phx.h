@@ -52,7 +52,8 @@ extern "C" {
  *        (additions, version unchanged) phx_rereplacements_flat, phx_tap_rereplacement, phx_rereplacements_ms, phx_rereplacement_stats — probe for the symbol
  *        (additions, version unchanged) phx_pindrops_flat, phx_pindrops_ms, phx_pindrop_stats — probe for the symbol
  *        (additions, version unchanged) phx_pinreplacements_flat, phx_tap_pinreplacement, phx_pinreplacements_ms, phx_pinreplacement_stats — probe for the symbol
- *        (additions, version unchanged) phx_profile_slot, phx_profile_flat, phx_profile_ms — probe for the symbol */
+ *        (additions, version unchanged) phx_profile_slot, phx_profile_flat, phx_profile_ms — probe for the symbol
+ *        (additions, version unchanged) phx_reprofile_flat, phx_reprofile_ms — probe for the symbol */
 #define PHX_MAX_CODONS 16
 
 /* library-level errors */
@@ -603,6 +604,31 @@ int phx_tap_rereplacement(phx_ctx *ctx, int32_t contig, int32_t k, int32_t *path
  * that were solved again.  All 0 before the first and when no contig was. */
 int phx_rereplacements_ms(phx_ctx *ctx, float *ms /* [3] */);
 int phx_rereplacement_stats(phx_ctx *ctx, int64_t *out /* [5] */);
+
+/* ---- re-annotation profiles: the coding profile under a mask or bias ----
+ * phx_profile_flat on the graph of the last re-annotation of the batch last run — the re-annotations phx_remargins_flat covers: now that
+ * this hit is in, or this call refused, is the gap beside it still a gap?  For a contig solved again under the refused set F and the bias
+ * B, G', R, d_s', d_t' and D' are phx_remargins_flat's, and EVERY edge e = (u -> v) of G' — ORF edge, tRNA edge or connector — has
+ *   Delta'(e) = d_s'(u) + W(e) + B(e) + d_t'(v) - D' >= 0 (inside R),  mu(e) = float(Delta'(e)) / 1000.0 as phx_margins_flat rounds it.
+ * An edge takes no part when it is refused or when u or v is unreached on its side; when D' is unreached every value is +inf.  Slots,
+ * ranks, the three tracks, lo / hi and the record are phx_profile_flat's.  On a contig whose re-solve has status 0 the re-annotation's
+ * device path (phx_tap_repath) crosses every slot at Delta' = 0: min(fwd, rev, gap) = 0.
+ * Records as phx_profile_flat (rec == NULL: size query; the same argument checks).  status[i] is phx_remargins_flat's, with n_node - 1
+ * records wherever it is >= 0 and the contig has a graph:
+ *   a contig that was not solved again: phx_profile_flat's status and records, byte for byte;
+ *   solved again with a status < 0: that status, no records;  solved again, PHX_S_NOPATH: status 1, all three values +inf in every slot,
+ *   lo / hi filled;  solved again, status 0: the records as defined; PHX_S_NEGCYCLE without records if the conditioned reverse pass hit
+ *   its caps.
+ * PHX_E_STATE, before any kernel, without a re-annotation of this run, and when a contig of the last one was solved under the required
+ * policy (a profile under pins is a minimum over (lost, s) pairs: a different definition).  Computed at the first call after a
+ * re-annotation solve, on top of phx_remargins_flat's computation (and phx_profile_flat's when a contig was not solved again), in buffers
+ * of its own; kept until the next solve or run.  Nothing the other entry points return changes.  (Additions, version unchanged: probe for
+ * the symbol.) */
+int phx_reprofile_flat(phx_ctx *ctx, phx_profile_slot *rec, int64_t cap, int64_t *offsets /* [n+1] */, int32_t *status /* [n] */, int64_t *total);
+/* device time of the last computation of the re-annotation profiles (HIP events), ms[3], as phx_profile_ms: tables, bounds, copy — the
+ * conditioned kernels alone (phx_remargins_ms and phx_profile_ms have the parts below them).  All 0 before the first and when no contig
+ * was solved again. */
+int phx_reprofile_ms(phx_ctx *ctx, float *ms /* [3] */);
 
 /* ---- pinned margins: per-ORF path margins under required ORFs ----
  * phx_remargins_flat for every re-annotation of the batch last run, phx_constrain_flat and phx_curate_flat with required ORFs included.  A

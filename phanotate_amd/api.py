@@ -74,6 +74,7 @@ _MS_KEYS = {
     "phx_remargins_ms": ("apply", "reverse", "margins", "download"),
     "phx_pinmargins_ms": ("apply", "reverse", "margins", "download"),
     "phx_redrops_ms": ("trees", "candidates", "fixups", "download"),
+    "phx_reprofile_ms": ("tables", "records", "download"),
     "phx_pindrops_ms": ("trees", "candidates", "fixups", "download"),
     "phx_rereplacements_ms": ("argmin", "walk", "download"),
     "phx_pinreplacements_ms": ("argmin", "walk", "download"),
@@ -966,6 +967,21 @@ class Annotator:
     def redrops_ms(self):
         """Device time of the last re-annotation drop margins in ms: trees + labels, candidates, fixups, copy to the host (phx_redrops_ms)."""
         return self._ms("phx_redrops_ms")
+
+    def reprofile(self):
+        """(status int32[n], offsets int64[n+1], records structured array[total] of _lib.PROFILE_DT), as profile() returns them: the coding
+        profile of every contig on the graph of the last reannotate() or evidence() (or constrain() without required ORFs) of the batch
+        last run (phx_reprofile_flat).  fwd / rev / gap of a slot: the minimum over the forward gene edges / reverse gene
+        edges / connectors that cover it of float(d_s'(u) + W + B + d_t'(v) - D') / 1000 on the refused / biased graph — now that this
+        evidence is in, what it costs the best annotation under it to have the stretch inside a forward gene, inside a reverse gene, or
+        between genes; a refused ORF's edge takes no part.  A contig that was not solved again has the records of profile().  PhxError
+        (PHX_E_STATE) without a re-annotation of this run and after constrain() with required ORFs."""
+        (status,), offs, (rec,) = self._query_fill(self.L.phx_reprofile_flat, "phx_reprofile_flat", (), self.n, (_lib.PROFILE_DT,))
+        return status, offs, rec
+
+    def reprofile_ms(self):
+        """Device time of the last re-annotation profiles in ms: candidates + tables + push-down, the slots' bounds, copy to the host (phx_reprofile_ms)."""
+        return self._ms("phx_reprofile_ms")
 
     def redrop_stats(self):
         """drop_stats() of the last re-annotation drop margins, over the contigs that were solved again (phx_redrop_stats)."""

@@ -727,6 +727,7 @@ static int reann_flat(phx_ctx *c, const char *who, bool need_forbid, const uint8
         c->done.redrop = false;
         c->done.retrees = false;
         c->done.rerepl = false;
+        c->done.reprofile = false;
         c->h_qsel.assign((size_t)c->n, 0);
         c->h_qnreq.assign((size_t)c->n, 0);
         for (int i = 0; i < c->n; i++) {
@@ -1042,6 +1043,101 @@ int phx_tap_pindist(phx_ctx *c, int32_t contig, int32_t which, uint64_t *dist_li
 
 int phx_remargins_ms(phx_ctx *c, float *ms) { return values_out<4>(c, ms, [](const phx_ctx *x) { return x->xm.ms; }); }
 int phx_pinmargins_ms(phx_ctx *c, float *ms) { return values_out<4>(c, ms, [](const phx_ctx *x) { return x->pm.ms; }); }
+
+// ---- re-annotation profiles (phx_profile.inc under MgCond, DESIGN.md §36) ----
+// the contigs the conditioned profile kernels cover (pf_on<MgCond>; after ensure_condmargins<CmPlain>): solved again without an error, and
+// — where the re-solve found a path — with a conditioned reverse pass that settled
+static bool reprofile_contig(const phx_ctx *c, size_t i) {
+    if (!c->h_qsel[i]) return false;
+    const int32_t sel = c->xm.h_sel[i];
+    return sel != 0 && (sel == 2 || !c->xm.mstat[i]);
+}
+// The slots' records of every contig of the last re-annotation that was solved again into c->rpf.h_rec (at rpf.roff), once per
+// re-annotation solve, on top of its margins (the conditioned d_t' and the pass's verdicts) and, when a contig the run's profile covers was
+// not solved again, of the run's profile, whose records stand for it.  Reads what the solve and its margins left resident; writes its own
+// set only.
+static int ensure_reprofile(phx_ctx *c, const char *who) {
+    { const int rs = remarg_state(c, who); if (rs) return rs; } // before any kernel
+    if (c->done.reprofile) return PHX_OK;
+    { const int rm = ensure_condmargins<CmPlain>(c); if (rm) return rm; }
+    const size_t n = (size_t)c->n;
+    for (size_t i = 0; i < n; i++)
+        if (!c->h_qsel[i] && profile_contig(c, i)) { const int rp = ensure_profile(c); if (rp) return rp; break; }
+    phx_ctx::ProfSet &P = c->rpf;
+    std::vector<int64_t> off(2 * n + 2, 0); // toff[n], roff[n + 1]
+    P.roff.assign(n + 1, 0);
+    int nlm = 0;
+    int64_t tcells = 0, R = 0;
+    for (size_t i = 0; i < n; i++) {
+        off[n + i] = R; P.roff[i] = R;
+        if (!reprofile_contig(c, i)) continue;
+        nlm |= nl_class_bit(c->meta[i].sssp_nl);
+        const int ns = c->meta[i].n_node - 1;
+        const int64_t cells = profile_cells(ns);
+        if (cells > PF_TAB_LDS) { off[i] = tcells; tcells += cells; }
+        R += ns;
+    }
+    off[2 * n] = R; P.roff[n] = R;
+    for (float &m : P.ms) m = 0;
+    if (nlm) {
+        int rc;
+        if ((rc = ensure(c, P.b_tab, ((size_t)tcells + 1) * 8))) return rc;
+        if ((rc = ensure(c, P.b_off, (2 * n + 2) * 8))) return rc;
+        if ((rc = ensure(c, P.b_rec, ((size_t)R + 1) * sizeof(phx_profile_slot)))) return rc;
+        if ((rc = ensure_pinned(c, P.h_rec, ((size_t)R + 1) * sizeof(phx_profile_slot), ((size_t)R + (size_t)R / 4 + 1024) * sizeof(phx_profile_slot)))) return rc;
+        if ((rc = analysis_events(c))) return rc;
+        DBatch b, qb;
+        fill_batch(c, &b);
+        DMarg g;
+        margins_args(c, &g);
+        DReann rq;
+        reann_batch(c, &qb, &rq);
+        DRmarg r;
+        condmargins_args(c, c->xm, (size_t)c->tot_edge / 32 + 2, &r);
+        DProf q;
+        q.gtab = (uint64_t *)P.b_tab.p; q.toff = (const int64_t *)P.b_off.p; q.roff = q.toff + n; q.rec = (phx_profile_slot *)P.b_rec.p;
+        hipStream_t s = c->stream;
+        HIPCHK(c, hipEventRecord(c->aev[0], s));
+        HIPCHK(c, hipMemcpyAsync(P.b_off.p, off.data(), (2 * n + 2) * 8, hipMemcpyHostToDevice, s));
+        phxk_reprofile_cand(&b, &g, &rq, &r, &q, nlm, s);
+        HIPCHK(c, hipEventRecord(c->aev[1], s));
+        phxk_reprofile_rec(&b, &g, &rq, &r, &q, s);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(c->aev[2], s));
+        if (R) HIPCHK(c, hipMemcpyAsync(P.h_rec.p, P.b_rec.p, (size_t)R * sizeof(phx_profile_slot), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipEventRecord(c->aev[3], s));
+        HIPCHK(c, hipStreamSynchronize(s)); // (`off` is read by the copy until here)
+        for (int k = 0; k < 3; k++) P.ms[k] = ev_ms(c->aev[k], c->aev[k + 1]);
+    } // (else no contig was solved again to a result: nothing is allocated or launched)
+    c->done.reprofile = true;
+    return PHX_OK;
+}
+
+int phx_reprofile_flat(phx_ctx *c, phx_profile_slot *rec, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
+    if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
+    { const int ra = after_run(c); if (ra) return ra; }
+    { const int rp = ensure_reprofile(c, "phx_reprofile_flat"); if (rp) return rp; }
+    auto set_of = [&](int i) -> const phx_ctx::ProfSet * { // the set that holds contig i's records: the run's for a contig that was not solved again
+        if (!c->h_qsel[(size_t)i]) return profile_contig(c, (size_t)i) ? &c->pf : nullptr;
+        return reprofile_contig(c, (size_t)i) ? &c->rpf : nullptr;
+    };
+    int64_t total = 0;
+    for (int i = 0; i < c->n; i++) { // V - 1 records for every covered contig (status 0 or PHX_S_NOPATH)
+        offsets[i] = total;
+        status[i] = condmargins_status(c, i);
+        const phx_ctx::ProfSet *P = set_of(i);
+        if (status[i] >= 0 && P) total += P->roff[(size_t)i + 1] - P->roff[(size_t)i];
+    }
+    offsets[c->n] = total;
+    if (total_out) *total_out = total;
+    if (!rec) return PHX_OK; // size query
+    if (cap < total) return PHX_E_ARG;
+    for (int i = 0; i < c->n; i++)
+        if (offsets[i + 1] > offsets[i]) memcpy(rec + offsets[i], (const phx_profile_slot *)set_of(i)->h_rec.p + set_of(i)->roff[(size_t)i], (size_t)(offsets[i + 1] - offsets[i]) * sizeof(phx_profile_slot));
+    return PHX_OK;
+}
+
+int phx_reprofile_ms(phx_ctx *c, float *ms) { return values_out<3>(c, ms, [](const phx_ctx *x) { return x->rpf.ms; }); }
 
 // ---- the three families of the drop margins and the drop replacements (DESIGN.md §35) ----
 // The run's (§12 / §13: policy DMarg on the run's graph, sets dp / rp), the re-annotation's (§29 / §30: MgDrop, rd / rr — the contigs solved

@@ -561,6 +561,8 @@ void phxk_margins(const DBatch *b, const DMarg *g, int nl_mask, void *stream); /
 void phxk_drop_step(int family, int step, const DBatch *b, const DMarg *g, const DCondView *v, const DDrop *q, int nl_mask, void *stream);
 void phxk_profile_cand(const DBatch *b, const DMarg *g, const DProf *q, int nl_mask, void *stream); // coding profiles (phx_profile.inc): candidates, tables and push-down per track,
 void phxk_profile_rec(const DBatch *b, const DMarg *g, const DProf *q, void *stream);                //   the slots' bounds
+void phxk_reprofile_cand(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const DProf *q, int nl_mask, void *stream); // re-annotation profiles (§36): the same
+void phxk_reprofile_rec(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const DProf *q, void *stream);                //   two under MgCond
 // drop replacements (phx_replace.inc; §13, §30, §33): step 0 winners, 1 cross winners and their delta chains, 2 detour lengths, 3 detours,
 // genes, records, of `family` — q: its DDrop set with DDrop.ps / ts, r: its own DRepl set (nl_mask: as phxk_drop_step; the walks take none)
 void phxk_repl_step(int family, int step, const DBatch *b, const DMarg *g, const DCondView *v, const DDrop *q, const DRepl *r, int nl_mask, void *stream);

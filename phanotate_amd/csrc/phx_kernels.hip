@@ -495,6 +495,13 @@ void phxk_profile_cand(const DBatch *b, const DMarg *g, const DProf *q, int nl_m
 void phxk_profile_rec(const DBatch *b, const DMarg *g, const DProf *q, void *stream) {
     hipLaunchKernelGGL(k_pf_rec<DMarg>, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), 0, (hipStream_t)stream, *b, *g, *q);
 }
+// re-annotation profiles (§36): the same two under MgCond, on the graph and distances the last re-annotation and its margins left resident
+void phxk_reprofile_cand(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const DProf *q, int nl_mask, void *stream) {
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_pf_cand<decltype(nl)::value, MgCond>), dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, mg_args<MgCond>(g, rq, r), *q); });
+}
+void phxk_reprofile_rec(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const DProf *q, void *stream) {
+    hipLaunchKernelGGL(k_pf_rec<MgCond>, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), 0, (hipStream_t)stream, *b, mg_args<MgCond>(g, rq, r), *q);
+}
 // drop replacements (§13), the re-annotation's (§30) and the pinned (§33): one step of family `family` on its DDrop set q (with the one-hop
 // trees: the walk follows DDrop.ps / ts and is launched only behind a k_dp_tree of the same family that wrote them) and its DRepl set r
 void phxk_repl_step(int family, int step, const DBatch *b, const DMarg *g, const DCondView *v, const DDrop *q, const DRepl *r, int nl_mask, void *stream) {

@@ -1,4 +1,4 @@
-// phx_profile.inc — coding profiles: what each stretch of a contig costs as forward gene, as reverse gene or as gap (included by phx_kernels.hip, after phx_drop.inc).
+// phx_profile.inc — coding profiles: what each stretch of a contig costs as forward gene, as reverse gene or as gap; the re-annotation profiles: both kernels under MgCond (included by phx_kernels.hip, after phx_drop.inc).
 // ------------------------------------------------------------------------------------------------
 // On demand after a run and after the margins' shared part (out-edge CSR, d_t: phx_margins.inc), never inside a run.  For one contig with
 // V nodes (real nodes 0 .. m-1, m = V - 2, position-sorted; source V-2, target V-1) every edge e = (u -> v), ORF edge or connector, has
@@ -19,11 +19,20 @@
 
 #define PF_NONE 0x7ff0000000000000ull // the pattern of +inf: nothing of the track covers the slot
 
-// the contigs the pass covers: device distances and a settled reverse pass (a contig without a path is covered: every value is +inf)
+// The policy of the two kernels is the type of their second argument, as for k_sssp_rev and k_margins (phx_margins.inc).  DMarg: the run's
+// graph, the kernels as §34 describes them.  MgCond (the re-annotation profiles, DESIGN.md §36): the graph G' = G_{F,B} of the last
+// re-annotation, restricted to R — d_s' from DRmarg.ds, d_t' from DRmarg.dist_t (dp_ds / dp_dt), D' = d_s'(target); an in-edge slot whose bit
+// is set in DReann.mask is no edge of G', one whose bit is set in DReann.bbit weighs W + DReann.bval (a contig solved under the bias policy
+// only: dp_w_in), both read per edge only where the head node's slots share a bitmap word with such a slot (dp_sp_in).  A node outside R has
+// no d_s' and no d_t' (k_sssp_rev<NL, MgCond> never relaxes it): its edges take no part.  Delta' >= 0 inside R (§21's lemma), so the key
+// argument above carries over.  Everything the policy adds sits behind if constexpr (mg_cond<G>): the DMarg instantiations are the code they
+// were without it.
+// the contigs the pass covers: device distances and a settled reverse pass (a contig without a path is covered: every value is +inf); under
+// MgCond the contigs solved again (DRmarg.sel 1: with a path, and a conditioned reverse pass that settled; 2: without one, D' unreached)
 template <class G>
 __device__ __forceinline__ bool pf_on(const DBatch &b, const G &g, const DMeta *meta) {
-    static_assert(!mg_cond<G>, "the profile is instantiated for the run's graph only (DESIGN.md §34, out of scope)");
-    return mg_contig(meta) && !g.mstat[meta - b.meta];
+    if constexpr (mg_cond<G>) { const int i = (int)(meta - b.meta), sel = g.r.sel[i]; return sel != 0 && mg_contig(meta) && (sel == 2 || !g.r.mstat[i]); }
+    else return mg_contig(meta) && !g.mstat[meta - b.meta];
 }
 // rank of node v among the slots' bounds: source -1, real node v, target m
 __device__ __forceinline__ int pf_rank(int v, int V) { return v < V - 2 ? v : (v == V - 2 ? -1 : V - 2); }
@@ -60,6 +69,9 @@ __device__ __forceinline__ void pf_tracks(const DBatch &b, const G &g, const DPr
     const uint64_t *ds = dp_ds<G>(b, g, meta);
     const uint64_t *dt = dp_dt<G>(b, g, meta);
     const uint32_t E = (uint32_t)meta->n_edge;
+    [[maybe_unused]] const uint64_t ebase = (uint64_t)meta->edge_off;
+    [[maybe_unused]] bool biased = false;
+    if constexpr (mg_cond<G>) biased = re_mode_bias(g.q.mode[blockIdx.x]);
     double *val = (double *)(q.rec + q.roff[blockIdx.x]); // four doubles per record: (lo, hi), fwd, rev, gap
     const WInt<NL> D = wi_load<NL>(ds + (size_t)(V - 1) * NL);
     const bool d_ok = !wi_unreached<NL>(D);
@@ -74,10 +86,13 @@ __device__ __forceinline__ void pf_tracks(const DBatch &b, const G &g, const DPr
             if (e1 > E) e1 = E; // (the contig's own edges)
             bool have = false;
             WInt<NL> tz = negD;
+            [[maybe_unused]] bool sp = false;
+            if constexpr (mg_cond<G>) sp = dp_sp_in(g, biased, ebase, e, e1);
             for (; e < e1; e++) {
                 const uint32_t sw = esrc[e];
                 const int u = (int)ESRC_NODE(sw);
                 if (u >= V) continue;
+                if constexpr (mg_cond<G>) { if (sp && mg_bit(g.q.mask, ebase + e)) continue; } // refused: no edge of G'
                 const int ru = pf_rank(u, V);
                 if (ru >= rv || pf_track(nd[u].info) != t) continue; // covers nothing (overlap connectors, equal ranks) / another track's
                 if (!have) { // d_t(v) - D, at the first edge that asks for it
@@ -88,7 +103,7 @@ __device__ __forceinline__ void pf_tracks(const DBatch &b, const G &g, const DPr
                 }
                 const WInt<NL> du = wi_load<NL>(ds + (size_t)u * NL);
                 if (wi_unreached<NL>(du)) continue;
-                const WInt<NL> delta = wi_add<NL>(wi_add<NL>(du, ew_decode<NL>(edge_wenc(sw, ew, e, gt))), tz);
+                const WInt<NL> delta = wi_add<NL>(wi_add<NL>(du, dp_w_in<NL>(g, sp, biased, ebase + e, ew_decode<NL>(edge_wenc(sw, ew, e, gt)))), tz);
                 const unsigned long long key = (unsigned long long)__double_as_longlong(wi_to_double_rn<NL>(delta) / 1000.0);
                 const uint32_t a = (uint32_t)(ru + 1), z = (uint32_t)rv, k = 31u - (uint32_t)__clz((int)(z - a + 1u)); // slots [a, z], 0 <= a <= z <= n - 1; 2^k <= z - a + 1 <= n: k < lv
                 const uint32_t ia = k * un + a, iz = k * un + (z + 1u - (1u << k));                                     // (a <= z + 1 - 2^k <= z)
