@@ -53,7 +53,8 @@ extern "C" {
  *        (additions, version unchanged) phx_pindrops_flat, phx_pindrops_ms, phx_pindrop_stats — probe for the symbol
  *        (additions, version unchanged) phx_pinreplacements_flat, phx_tap_pinreplacement, phx_pinreplacements_ms, phx_pinreplacement_stats — probe for the symbol
  *        (additions, version unchanged) phx_profile_slot, phx_profile_flat, phx_profile_ms — probe for the symbol
- *        (additions, version unchanged) phx_reprofile_flat, phx_reprofile_ms — probe for the symbol */
+ *        (additions, version unchanged) phx_reprofile_flat, phx_reprofile_ms — probe for the symbol
+ *        (additions, version unchanged) phx_pinprofile_flat, phx_pinprofile_ms, phx_pinprofile_stats — probe for the symbol */
 #define PHX_MAX_CODONS 16
 
 /* library-level errors */
@@ -629,6 +630,38 @@ int phx_reprofile_flat(phx_ctx *ctx, phx_profile_slot *rec, int64_t cap, int64_t
  * conditioned kernels alone (phx_remargins_ms and phx_profile_ms have the parts below them).  All 0 before the first and when no contig
  * was solved again. */
 int phx_reprofile_ms(phx_ctx *ctx, float *ms /* [3] */);
+
+/* ---- pinned profiles: the coding profile under required ORFs ----
+ * phx_reprofile_flat for every re-annotation of the batch last run, phx_constrain_flat and phx_curate_flat with required ORFs included:
+ * now that these genes are pinned, is the gap beside them still a gap — and what does the stretch under a pin cost as anything but that
+ * gene, and how many pins would that give up?  For a contig solved again under the required policy (F, B and R), G', R_n, W', M, d_s',
+ * d_t' and D' are phx_pinmargins_flat's, and EVERY edge e = (u -> v) of G' — ORF edge, tRNA edge or connector — has
+ *   Delta''(e) = d_s'(u) + W'(e) + d_t'(v) - D' = lost(e)·M + s(e) >= 0   (NL + 1 limbs),
+ * decoded as phx_pinmargins_flat decodes it: lost the top limb plus the sign bit of limb NL - 1, s the low NL limbs as the class's two's
+ * complement, mu(e) = float(s) / 1000.0.  An edge takes no part when it is refused or when u or v is unreached on its side.  Slots, ranks,
+ * the three tracks, lo / hi and the record are phx_profile_flat's.  Per slot and track the result is the LEXICOGRAPHIC minimum of
+ * (lost(e), s(e)) over the covering edges of the track: mu of that minimum in the record's fwd / rev / gap, its lost in lost[3 k + 0 / 1 / 2]
+ * for record k.  A value may be negative where lost > 0 (a path that drops a pin can be cheaper); where no edge of the track covers the
+ * slot the value is +inf and lost 0.  On a contig whose re-solve has status 0 the minimum over the three tracks is (0, 0.0) in every slot.
+ * rec has cap entries, lost 3 * cap (rec == NULL: size query; with rec, lost is needed: PHX_E_ARG).  status[i] is phx_pinmargins_flat's:
+ *   a contig that was not solved again: phx_profile_flat's status and records, lost 0;
+ *   solved again without a required ORF: what phx_reprofile_flat returns for it after the same call without the other contigs' required
+ *   ORFs, lost 0;
+ *   solved under the required policy, status 0, the pinned reverse pass settled: n_node - 1 records as defined;  PHX_S_NOPATH: status 1,
+ *   every value +inf, lost 0, lo / hi filled;  a re-solve error: that status, no records;  the pinned reverse pass hit its caps:
+ *   PHX_S_NEGCYCLE, no records.
+ * When no contig of the last re-annotation was solved under the required policy the three arrays are phx_reprofile_flat's byte for byte
+ * and lost is all 0.  PHX_E_STATE, before any kernel, only without a re-annotation of this run; phx_reprofile_flat keeps refusing a solve
+ * with required ORFs.  Computed at the first call after a re-annotation solve, on top of phx_pinmargins_flat's computation, in buffers of
+ * its own; kept until the next solve or run.  Nothing the other entry points return changes.  (Additions, version unchanged: probe for
+ * the symbol.) */
+int phx_pinprofile_flat(phx_ctx *ctx, phx_profile_slot *rec, int32_t *lost /* [3 * cap] */, int64_t cap, int64_t *offsets /* [n+1] */, int32_t *status /* [n] */, int64_t *total);
+/* device time of the last computation of the pinned profiles (HIP events), ms[3]: tables, records, copy — the pinned kernels alone.  All 0
+ * before the first and when no contig was solved under the required policy. */
+int phx_pinprofile_ms(phx_ctx *ctx, float *ms /* [3] */);
+/* counters of the last computation, out[3]: contigs the pinned kernels covered; table rounds they ran (3 per contig, and one more per
+ * distinct lost > 0 that a track's slots hold); slots with lost > 0 on any track. */
+int phx_pinprofile_stats(phx_ctx *ctx, int64_t *out /* [3] */);
 
 /* ---- pinned margins: per-ORF path margins under required ORFs ----
  * phx_remargins_flat for every re-annotation of the batch last run, phx_constrain_flat and phx_curate_flat with required ORFs included.  A

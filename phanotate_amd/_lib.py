@@ -168,6 +168,9 @@ def lib():
         "phx_profile_ms": (C.c_int, [vp, P(C.c_float)]),
         "phx_reprofile_flat": (C.c_int, [vp, vp, i64, vp, vp, P(i64)]),
         "phx_reprofile_ms": (C.c_int, [vp, P(C.c_float)]),
+        "phx_pinprofile_flat": (C.c_int, [vp, vp, vp, i64, vp, vp, P(i64)]),
+        "phx_pinprofile_ms": (C.c_int, [vp, P(C.c_float)]),
+        "phx_pinprofile_stats": (C.c_int, [vp, P(i64)]),
         "phx_format_drops": (C.c_int, [i32, vp, vp, vp, vp, P(vp), P(i64)]),
         "phx_replacements_flat": (C.c_int, [vp, vp, i64, vp, i64, vp, vp, P(i64), P(i64)]),
         "phx_tap_replacement": (C.c_int, [vp, i32, i32, vp, i32, P(i32)]),
@@ -261,4 +264,5 @@ EXPORTS = ["phx_version", "phx_device_count", "phx_strerror", "phx_last_error", 
            "phx_pindrops_flat", "phx_pindrops_ms", "phx_pindrop_stats",
            "phx_pinreplacements_flat", "phx_tap_pinreplacement", "phx_pinreplacements_ms", "phx_pinreplacement_stats",
            "phx_profile_flat", "phx_profile_ms",
-           "phx_reprofile_flat", "phx_reprofile_ms"]
+           "phx_reprofile_flat", "phx_reprofile_ms",
+           "phx_pinprofile_flat", "phx_pinprofile_ms", "phx_pinprofile_stats"]

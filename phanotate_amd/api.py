@@ -75,6 +75,7 @@ _MS_KEYS = {
     "phx_pinmargins_ms": ("apply", "reverse", "margins", "download"),
     "phx_redrops_ms": ("trees", "candidates", "fixups", "download"),
     "phx_reprofile_ms": ("tables", "records", "download"),
+    "phx_pinprofile_ms": ("tables", "records", "download"),
     "phx_pindrops_ms": ("trees", "candidates", "fixups", "download"),
     "phx_rereplacements_ms": ("argmin", "walk", "download"),
     "phx_pinreplacements_ms": ("argmin", "walk", "download"),
@@ -982,6 +983,30 @@ class Annotator:
     def reprofile_ms(self):
         """Device time of the last re-annotation profiles in ms: candidates + tables + push-down, the slots' bounds, copy to the host (phx_reprofile_ms)."""
         return self._ms("phx_reprofile_ms")
+
+    def pinprofile(self):
+        """(status int32[n], offsets int64[n+1], records structured array[total] of _lib.PROFILE_DT, lost int32[total, 3]): reprofile()
+        for every re-annotation of the batch last run, constrain() and curate() with required ORFs included (phx_pinprofile_flat,
+        DESIGN.md §37).  For a contig solved with required ORFs every edge has Delta'' = lost * M + s as pinmargins() decodes it, and a
+        slot's fwd / rev / gap is float(s) / 1000 of the lexicographic minimum of (lost, s) over the forward gene edges / reverse gene
+        edges / connectors that cover it, lost[k] = (fwd, rev, gap) the kept required ORFs that minimum gives up — now that these genes
+        are pinned, what the stretch costs as forward gene, as reverse gene or as gap, and how many pins that would give up.  A value may
+        be negative where lost > 0; the order is (lost, value) >= (0, 0.0), which one track of every slot of a solved contig has.  +inf
+        with lost 0 where nothing of the track covers the slot.  Elsewhere the records are reprofile()'s (profile()'s for a contig that
+        was not solved again) and lost is 0.  PhxError (PHX_E_STATE) only without a re-annotation of this run."""
+        (status,), offs, (rec, lost) = self._query_fill(self.L.phx_pinprofile_flat, "phx_pinprofile_flat", (), self.n, (_lib.PROFILE_DT, np.dtype((np.int32, (3,)))), "rrc")
+        return status, offs, rec, lost.reshape(-1, 3)
+
+    def pinprofile_ms(self):
+        """Device time of the last pinned profiles in ms: candidates + tables + push-down over every round, the slots' bounds, copy to the host (phx_pinprofile_ms)."""
+        return self._ms("phx_pinprofile_ms")
+
+    def pinprofile_stats(self):
+        """Counters of the last pinned profiles (phx_pinprofile_stats): the contigs the pinned kernels covered, the table rounds they ran (3
+        per contig and one more per distinct lost > 0 among a track's slots), the slots with lost > 0 on any track."""
+        out = (C.c_int64 * 3)()
+        self._chk(self.L.phx_pinprofile_stats(self.h, out), "phx_pinprofile_stats")
+        return dict(zip(("contigs", "rounds", "lost_slots"), [int(x) for x in out]))
 
     def redrop_stats(self):
         """drop_stats() of the last re-annotation drop margins, over the contigs that were solved again (phx_redrop_stats)."""

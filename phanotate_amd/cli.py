@@ -159,25 +159,33 @@ def format_pin_replacements(names, status, offsets, records, genes, lost):
     return "".join(out).encode()
 
 
-def format_profile(names, status, offsets, records):
+def format_profile(names, status, offsets, records, lost=None):
     """--profile FILE for a run of contigs, as bytes: per contig with status >= 0 "#id:\t<name>", the header, then one row per stretch (LO HI
     FWD REV GAP) from left to right.  LO / HI are node positions (Annotator.nodes() pos; 0 and L + 1 at the ends), the three numbers
     Annotator.profile()'s fwd / rev / gap, printed as format_margins prints a margin (INF: nothing of that kind covers the stretch).  Slots
-    without extent (lo == hi) are left out; neighbouring slots with the same three values are one row."""
+    without extent (lo == hi) are left out; neighbouring slots with the same three values are one row.  With `lost` (int32[total, 3],
+    parallel to `records`: Annotator.pinprofile()) each of the three numbers is followed by a LOST column, the kept required ORFs that the
+    number gives up, and a row is one run of equal values and equal counts."""
     import numpy as np
 
     out = []
     for nm, cut in _blocks(names, status, offsets):
-        out.append("#id:\t%s\n#LO\tHI\tFWD\tREV\tGAP\n" % nm)
+        out.append(("#id:\t%s\n#LO\tHI\tFWD\tLOST\tREV\tLOST\tGAP\tLOST\n" if lost is not None else "#id:\t%s\n#LO\tHI\tFWD\tREV\tGAP\n") % nm)
         rec = records[cut]
+        ls = None if lost is None else np.asarray(lost).reshape(-1, 3)[cut][rec["lo"] != rec["hi"]]
         rec = rec[rec["lo"] != rec["hi"]]
         if not len(rec):
             continue
         first = np.ones(len(rec), bool)  # the first slot of every run of equal triples
         first[1:] = (rec["fwd"][1:] != rec["fwd"][:-1]) | (rec["rev"][1:] != rec["rev"][:-1]) | (rec["gap"][1:] != rec["gap"][:-1])
+        if ls is not None:
+            first[1:] |= (ls[1:] != ls[:-1]).any(axis=1)
         a = np.flatnonzero(first)
         z = np.append(a[1:], len(rec)) - 1
         for i, j in zip(a.tolist(), z.tolist()):
+            if ls is not None:
+                out.append("%d\t%d\t%E\t%d\t%E\t%d\t%E\t%d\n" % (int(rec["lo"][i]), int(rec["hi"][j]), float(rec["fwd"][i]), int(ls[i, 0]), float(rec["rev"][i]), int(ls[i, 1]), float(rec["gap"][i]), int(ls[i, 2])))
+                continue
             out.append("%d\t%d\t%E\t%E\t%E\n" % (int(rec["lo"][i]), int(rec["hi"][j]), float(rec["fwd"][i]), float(rec["rev"][i]), float(rec["gap"][i])))
     return "".join(out).encode()
 

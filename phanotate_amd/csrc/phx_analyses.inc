@@ -721,6 +721,7 @@ static int reann_flat(phx_ctx *c, const char *who, bool need_forbid, const uint8
         c->done.reann = false;
         c->done.remarg = false; // (the re-annotation margins are this solve's)
         c->done.pinmarg = false;
+        c->done.pinprofile = false;
         c->done.pindrop = false;
         c->done.pintrees = false;
         c->done.pinrepl = false;
@@ -1055,9 +1056,9 @@ static bool reprofile_contig(const phx_ctx *c, size_t i) {
 // The slots' records of every contig of the last re-annotation that was solved again into c->rpf.h_rec (at rpf.roff), once per
 // re-annotation solve, on top of its margins (the conditioned d_t' and the pass's verdicts) and, when a contig the run's profile covers was
 // not solved again, of the run's profile, whose records stand for it.  Reads what the solve and its margins left resident; writes its own
-// set only.
-static int ensure_reprofile(phx_ctx *c, const char *who) {
-    { const int rs = remarg_state(c, who); if (rs) return rs; } // before any kernel
+// set only.  (reprofile_pass: the pass itself, for a caller that has checked the state — the pinned profiles run it for the contigs solved
+// again without a required ORF beside pinned ones, where remarg_state refuses.)
+static int reprofile_pass(phx_ctx *c) {
     if (c->done.reprofile) return PHX_OK;
     { const int rm = ensure_condmargins<CmPlain>(c); if (rm) return rm; }
     const size_t n = (size_t)c->n;
@@ -1112,6 +1113,10 @@ static int ensure_reprofile(phx_ctx *c, const char *who) {
     c->done.reprofile = true;
     return PHX_OK;
 }
+static int ensure_reprofile(phx_ctx *c, const char *who) {
+    { const int rs = remarg_state(c, who); if (rs) return rs; } // before any kernel
+    return reprofile_pass(c);
+}
 
 int phx_reprofile_flat(phx_ctx *c, phx_profile_slot *rec, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
     if (!c || (c->n > 0 && (!offsets || !status))) return PHX_E_ARG;
@@ -1138,6 +1143,123 @@ int phx_reprofile_flat(phx_ctx *c, phx_profile_slot *rec, int64_t cap, int64_t *
 }
 
 int phx_reprofile_ms(phx_ctx *c, float *ms) { return values_out<3>(c, ms, [](const phx_ctx *x) { return x->rpf.ms; }); }
+
+// ---- pinned profiles (phx_profile.inc under MgPinProf, DESIGN.md §37) ----
+// the contigs the pinned profile kernels cover (pf_on<MgPinProf>; after ensure_condmargins<CmPin>): solved again under the required policy
+// without an error, and — where the re-solve found a path — with a pinned reverse pass that settled
+static bool pinprofile_contig(const phx_ctx *c, size_t i) {
+    if (!re_mode_req(c->h_qsel[i])) return false;
+    const int32_t sel = c->pm.h_sel[i];
+    return sel != 0 && (sel == 2 || !c->pm.mstat[i]);
+}
+// The slots' records and `lost` of every contig the last re-annotation solved under the required policy into c->ppf.h_rec / ppf_h_lost (at
+// ppf.roff), once per re-annotation solve, on top of the pinned margins (d_t' on one limb more, the pass's verdicts).  The contigs solved
+// again without a required ORF get the re-annotation profiles' pass (rpf), the others the run's profile (pf); both stand as they are.  Reads
+// what the solve and its margins left resident; writes its own set only.
+static int ensure_pinprofile(phx_ctx *c) {
+    if (!c->done.reann) { c->err = "phx_pinprofile_flat: no re-annotation of this run (call phx_constrain_flat or phx_curate_flat first)"; return PHX_E_STATE; } // before any kernel
+    { const int rm = ensure_condmargins<CmPin>(c); if (rm) return rm; }
+    { const int rp = reprofile_pass(c); if (rp) return rp; }
+    if (c->done.pinprofile) return PHX_OK;
+    const size_t n = (size_t)c->n;
+    phx_ctx::ProfSet &P = c->ppf;
+    std::vector<int64_t> off(2 * n + 2, 0); // toff[n], roff[n + 1]
+    P.roff.assign(n + 1, 0);
+    int nlm = 0;
+    int64_t tcells = 0, R = 0, covered = 0;
+    for (size_t i = 0; i < n; i++) {
+        off[n + i] = R; P.roff[i] = R;
+        if (!pinprofile_contig(c, i)) continue;
+        nlm |= nl_class_bit(c->meta[i].sssp_nl);
+        const int ns = c->meta[i].n_node - 1;
+        const int64_t cells = profile_cells(ns);
+        if (cells > PF_TAB_LDS) { off[i] = tcells; tcells += cells; }
+        R += ns;
+        covered++;
+    }
+    off[2 * n] = R; P.roff[n] = R;
+    for (float &m : P.ms) m = 0;
+    for (int64_t &v : c->ppf_stats) v = 0;
+    if (nlm) {
+        int rc;
+        if ((rc = ensure(c, P.b_tab, ((size_t)tcells + 1) * 8))) return rc;
+        if ((rc = ensure(c, P.b_off, (2 * n + 2) * 8))) return rc;
+        if ((rc = ensure(c, P.b_rec, ((size_t)R + 1) * sizeof(phx_profile_slot)))) return rc;
+        if ((rc = ensure(c, c->ppf_b_lost, (3 * (size_t)R + 1) * 4))) return rc;
+        if ((rc = ensure(c, c->ppf_b_rounds, (n + 1) * 4))) return rc;
+        if ((rc = ensure_pinned(c, P.h_rec, ((size_t)R + 1) * sizeof(phx_profile_slot), ((size_t)R + (size_t)R / 4 + 1024) * sizeof(phx_profile_slot)))) return rc;
+        if ((rc = ensure_pinned(c, c->ppf_h_lost, (3 * (size_t)R + 1) * 4, (3 * ((size_t)R + (size_t)R / 4) + 1024) * 4))) return rc;
+        if ((rc = analysis_events(c))) return rc;
+        try { c->ppf_h_rounds.assign(n + 1, 0); } catch (const std::bad_alloc &) { c->err = "out of memory in phx_pinprofile_flat"; return PHX_E_NOMEM; }
+        DBatch b, qb;
+        fill_batch(c, &b);
+        DMarg g;
+        margins_args(c, &g);
+        DReann rq;
+        reann_batch(c, &qb, &rq);
+        const size_t mw = (size_t)c->tot_edge / 32 + 2;
+        DPmarg r;
+        condmargins_args(c, c->pm, mw, &r);
+        r.dt_stride = b.dist_stride + 1; r.rbit = r.fbit + 2 * mw; r.lost = (int32_t *)c->pm.b_lost.p; // (as ensure_condmargins<CmPin> laid them out)
+        DProf q;
+        q.gtab = (uint64_t *)P.b_tab.p; q.toff = (const int64_t *)P.b_off.p; q.roff = q.toff + n; q.rec = (phx_profile_slot *)P.b_rec.p;
+        hipStream_t s = c->stream;
+        HIPCHK(c, hipEventRecord(c->aev[0], s));
+        HIPCHK(c, hipMemcpyAsync(P.b_off.p, off.data(), (2 * n + 2) * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemsetAsync(c->ppf_b_rounds.p, 0, (n + 1) * 4, s));
+        phxk_pinprofile_cand(&b, &g, &rq, &r, &q, (int32_t *)c->ppf_b_lost.p, (int32_t *)c->ppf_b_rounds.p, nlm, s);
+        HIPCHK(c, hipEventRecord(c->aev[1], s));
+        phxk_pinprofile_rec(&b, &g, &rq, &r, &q, s);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipEventRecord(c->aev[2], s));
+        if (R) HIPCHK(c, hipMemcpyAsync(P.h_rec.p, P.b_rec.p, (size_t)R * sizeof(phx_profile_slot), hipMemcpyDeviceToHost, s));
+        if (R) HIPCHK(c, hipMemcpyAsync(c->ppf_h_lost.p, c->ppf_b_lost.p, 3 * (size_t)R * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(c->ppf_h_rounds.data(), c->ppf_b_rounds.p, n * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipEventRecord(c->aev[3], s));
+        HIPCHK(c, hipStreamSynchronize(s)); // (`off` is read by the copy until here)
+        for (int k = 0; k < 3; k++) P.ms[k] = ev_ms(c->aev[k], c->aev[k + 1]);
+        c->ppf_stats[0] = covered;
+        for (size_t i = 0; i < n; i++) c->ppf_stats[1] += c->ppf_h_rounds[i];
+        const int32_t *hl = (const int32_t *)c->ppf_h_lost.p;
+        for (int64_t k = 0; k < R; k++) c->ppf_stats[2] += (hl[3 * k] | hl[3 * k + 1] | hl[3 * k + 2]) != 0; // (lost >= 0)
+    } // (else no contig was solved under the required policy to a result: nothing is allocated or launched)
+    c->done.pinprofile = true;
+    return PHX_OK;
+}
+
+int phx_pinprofile_flat(phx_ctx *c, phx_profile_slot *rec, int32_t *lost, int64_t cap, int64_t *offsets, int32_t *status, int64_t *total_out) {
+    if (!c || (c->n > 0 && (!offsets || !status)) || (rec && !lost)) return PHX_E_ARG;
+    { const int ra = after_run(c); if (ra) return ra; }
+    { const int rp = ensure_pinprofile(c); if (rp) return rp; }
+    auto set_of = [&](int i) -> const phx_ctx::ProfSet * { // the set that holds contig i's records (phx_reprofile_flat's two, and the pinned set)
+        if (!c->h_qsel[(size_t)i]) return profile_contig(c, (size_t)i) ? &c->pf : nullptr;
+        if (re_mode_req(c->h_qsel[(size_t)i])) return pinprofile_contig(c, (size_t)i) ? &c->ppf : nullptr;
+        return reprofile_contig(c, (size_t)i) ? &c->rpf : nullptr;
+    };
+    int64_t total = 0;
+    for (int i = 0; i < c->n; i++) { // V - 1 records for every covered contig (status 0 or PHX_S_NOPATH)
+        offsets[i] = total;
+        status[i] = condmargins_status(c, i);
+        const phx_ctx::ProfSet *P = set_of(i);
+        if (status[i] >= 0 && P) total += P->roff[(size_t)i + 1] - P->roff[(size_t)i];
+    }
+    offsets[c->n] = total;
+    if (total_out) *total_out = total;
+    if (!rec) return PHX_OK; // size query
+    if (cap < total) return PHX_E_ARG;
+    for (int i = 0; i < c->n; i++) {
+        const int64_t k = offsets[i + 1] - offsets[i];
+        if (k <= 0) continue;
+        const phx_ctx::ProfSet *P = set_of(i);
+        memcpy(rec + offsets[i], (const phx_profile_slot *)P->h_rec.p + P->roff[(size_t)i], (size_t)k * sizeof(phx_profile_slot));
+        if (P == &c->ppf) memcpy(lost + 3 * offsets[i], (const int32_t *)c->ppf_h_lost.p + 3 * P->roff[(size_t)i], 3 * (size_t)k * 4);
+        else memset(lost + 3 * offsets[i], 0, 3 * (size_t)k * 4);
+    }
+    return PHX_OK;
+}
+
+int phx_pinprofile_ms(phx_ctx *c, float *ms) { return values_out<3>(c, ms, [](const phx_ctx *x) { return x->ppf.ms; }); }
+int phx_pinprofile_stats(phx_ctx *c, int64_t *out) { return values_out<3>(c, out, [](const phx_ctx *x) { return x->ppf_stats; }); }
 
 // ---- the three families of the drop margins and the drop replacements (DESIGN.md §35) ----
 // The run's (§12 / §13: policy DMarg on the run's graph, sets dp / rp), the re-annotation's (§29 / §30: MgDrop, rd / rr — the contigs solved

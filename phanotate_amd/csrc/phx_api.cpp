@@ -249,6 +249,7 @@ struct phx_ctx {
         bool rerepl = false;  // rr.h_rec / h_genes / h_det hold the replacements of the re-annotation h_q* hold (reset wherever redrop is)
         bool profile = false; // pf.h_rec holds the slots' records of every covered contig, at pf.roff
         bool reprofile = false; // rpf.h_rec holds the slots' records of the contigs the re-annotation h_q* hold solved again, at rpf.roff (reset wherever remarg is)
+        bool pinprofile = false; // ppf.h_rec / ppf_h_lost hold the slots' records and `lost` of the contigs the re-annotation h_q* hold solved under the required policy, at ppf.roff (reset wherever pinmarg is)
         bool grp = false;     // h_grp
     } done;
     std::vector<DGrp> h_grp;         // the run's group records (device order <-> reference order of the ORFs: each_group_in_reference_order)
@@ -282,7 +283,14 @@ struct phx_ctx {
         std::vector<int64_t> roff;   // per contig (+1): first record in h_rec (a contig that is not covered: none)
         PinBuf h_rec;                // a phx_profile_slot per slot of every covered contig
         float ms[3] = {0, 0, 0};
-    } pf, rpf; // rpf: the last re-annotation's (phx_reprofile_flat, §36) — laid out for the contigs that were solved again only, kept until the next re-annotation solve or run; pf is not touched by it
+    } pf, rpf, ppf; // rpf: the last re-annotation's (phx_reprofile_flat, §36) — laid out for the contigs that were solved again only, kept until the next re-annotation solve or run; pf is not touched by it
+    // ppf: the pinned profiles' (phx_pinprofile_flat, §37) — laid out for the contigs solved under the required policy only, kept as rpf is; neither
+    // pf nor rpf is touched by it.  Beside it: `lost`, three int32 per slot parallel to ppf's records (device, and pinned host memory), and the
+    // table rounds k_pf_cand ran per contig.  Allocated at the first call that has a pinned contig.
+    DevBuf ppf_b_lost, ppf_b_rounds;
+    PinBuf ppf_h_lost;
+    std::vector<int32_t> ppf_h_rounds;
+    int64_t ppf_stats[3] = {0, 0, 0}; // phx_pinprofile_stats: pinned contigs covered, table rounds run, slots with lost > 0 on any track
     // drop replacements (phx_replacements_flat): buffers allocated at the first call, results kept until the next run
     // (rp: the run's set.  rr: the set of the re-annotation replacements, phx_rereplacements_flat, DESIGN.md §30 — allocated at the first call
     // that has a solved-again contig for it, the result kept until the next re-annotation solve or run; rp is not touched by it.  pr: the set
@@ -823,7 +831,7 @@ void phx_destroy(phx_ctx *c) {
     c->in_flight = false;
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (DevBuf *b = c->bufs; b; b = b->next) release(*b);
-    for (PinBuf *b : {&c->pin_res, &c->h_stage, &c->h_tiles, &c->h_genes, &c->h_mrec, &c->dp.h_rec, &c->rd.h_rec, &c->pd.h_rec, &c->pf.h_rec, &c->rpf.h_rec}) if (b->p) (void)hipHostFree(b->p);
+    for (PinBuf *b : {&c->pin_res, &c->h_stage, &c->h_tiles, &c->h_genes, &c->h_mrec, &c->dp.h_rec, &c->rd.h_rec, &c->pd.h_rec, &c->pf.h_rec, &c->rpf.h_rec, &c->ppf.h_rec, &c->ppf_h_lost}) if (b->p) (void)hipHostFree(b->p);
     for (hipEvent_t e : c->aev) if (e) (void)hipEventDestroy(e);
     if (c->graph_exec) (void)hipGraphExecDestroy(c->graph_exec);
     if (c->graph) (void)hipGraphDestroy(c->graph);

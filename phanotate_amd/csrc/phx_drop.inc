@@ -102,7 +102,8 @@ struct MgDrop : MgCond { const int32_t *path; };
 // the (lost, s) order as well.  A slot whose minimum is not DP_SAT therefore holds its exact minimum; one that is DP_SAT is recomputed by
 // k_dp_rescan in WL limbs, where two's-complement order on lost * M + s is the lexicographic order.
 struct MgPinDrop : MgPin { const int32_t *path; int32_t *lost; };
-template <class G> constexpr bool dp_pin = std::is_same<G, MgPinDrop>::value;
+struct MgPinProf; // (the pinned profiles' policy, phx_profile.inc: MgPin with pointers of its own; what dp_pin<G> adds below holds for it as well)
+template <class G> constexpr bool dp_pin = std::is_same<G, MgPinDrop>::value || std::is_same<G, MgPinProf>::value;
 template <int NL, class G> constexpr int dp_wl = NL + (dp_pin<G> ? 1 : 0); // limbs of a value
 template <class G>
 __device__ __forceinline__ bool dp_on(const DBatch &b, const G &g, const DMeta *meta) {

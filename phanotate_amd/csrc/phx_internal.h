@@ -563,6 +563,8 @@ void phxk_profile_cand(const DBatch *b, const DMarg *g, const DProf *q, int nl_m
 void phxk_profile_rec(const DBatch *b, const DMarg *g, const DProf *q, void *stream);                //   the slots' bounds
 void phxk_reprofile_cand(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const DProf *q, int nl_mask, void *stream); // re-annotation profiles (§36): the same
 void phxk_reprofile_rec(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const DProf *q, void *stream);                //   two under MgCond
+void phxk_pinprofile_cand(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const DProf *q, int32_t *lost, int32_t *rounds, int nl_mask, void *stream); // pinned profiles (§37): the same
+void phxk_pinprofile_rec(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const DProf *q, void *stream);                                              //   two under MgPinProf (lost: three int32 per slot, rounds: one per contig)
 // drop replacements (phx_replace.inc; §13, §30, §33): step 0 winners, 1 cross winners and their delta chains, 2 detour lengths, 3 detours,
 // genes, records, of `family` — q: its DDrop set with DDrop.ps / ts, r: its own DRepl set (nl_mask: as phxk_drop_step; the walks take none)
 void phxk_repl_step(int family, int step, const DBatch *b, const DMarg *g, const DCondView *v, const DDrop *q, const DRepl *r, int nl_mask, void *stream);

@@ -502,6 +502,15 @@ void phxk_reprofile_cand(const DBatch *b, const DMarg *g, const DReann *rq, cons
 void phxk_reprofile_rec(const DBatch *b, const DMarg *g, const DReann *rq, const DRmarg *r, const DProf *q, void *stream) {
     hipLaunchKernelGGL(k_pf_rec<MgCond>, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), 0, (hipStream_t)stream, *b, mg_args<MgCond>(g, rq, r), *q);
 }
+// pinned profiles (§37): the same two under MgPinProf, for the contigs solved under the required policy — values on one limb more, `lost`
+// three int32 per slot parallel to DProf.rec, `rounds` one int32 per contig, both written by k_pf_cand alone
+static MgPinProf ppf_args(const DMarg *g, const DReann *rq, const DPmarg *r, int32_t *lost, int32_t *rounds) { MgPinProf c = mg_args<MgPinProf>(g, rq, r); c.lost = lost; c.rounds = rounds; return c; }
+void phxk_pinprofile_cand(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const DProf *q, int32_t *lost, int32_t *rounds, int nl_mask, void *stream) {
+    each_limb_class(nl_mask, [&](auto nl) { hipLaunchKernelGGL((k_pf_cand<decltype(nl)::value, MgPinProf>), dim3(b->n_contig), dim3(NT), 0, (hipStream_t)stream, *b, ppf_args(g, rq, r, lost, rounds), *q); });
+}
+void phxk_pinprofile_rec(const DBatch *b, const DMarg *g, const DReann *rq, const DPmarg *r, const DProf *q, void *stream) {
+    hipLaunchKernelGGL(k_pf_rec<MgPinProf>, dim3(b->n_contig, ysplit(b, 8)), dim3(NT), 0, (hipStream_t)stream, *b, ppf_args(g, rq, r, nullptr, nullptr), *q);
+}
 // drop replacements (§13), the re-annotation's (§30) and the pinned (§33): one step of family `family` on its DDrop set q (with the one-hop
 // trees: the walk follows DDrop.ps / ts and is launched only behind a k_dp_tree of the same family that wrote them) and its DRepl set r
 void phxk_repl_step(int family, int step, const DBatch *b, const DMarg *g, const DCondView *v, const DDrop *q, const DRepl *r, int nl_mask, void *stream) {

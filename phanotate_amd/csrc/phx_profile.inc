@@ -1,4 +1,4 @@
-// phx_profile.inc — coding profiles: what each stretch of a contig costs as forward gene, as reverse gene or as gap; the re-annotation profiles: both kernels under MgCond (included by phx_kernels.hip, after phx_drop.inc).
+// phx_profile.inc — coding profiles: what each stretch of a contig costs as forward gene, as reverse gene or as gap; the re-annotation profiles: both kernels under MgCond; the pinned profiles: both under MgPinProf (included by phx_kernels.hip, after phx_drop.inc).
 // ------------------------------------------------------------------------------------------------
 // On demand after a run and after the margins' shared part (out-edge CSR, d_t: phx_margins.inc), never inside a run.  For one contig with
 // V nodes (real nodes 0 .. m-1, m = V - 2, position-sorted; source V-2, target V-1) every edge e = (u -> v), ORF edge or connector, has
@@ -27,8 +27,33 @@
 // no d_s' and no d_t' (k_sssp_rev<NL, MgCond> never relaxes it): its edges take no part.  Delta' >= 0 inside R (§21's lemma), so the key
 // argument above carries over.  Everything the policy adds sits behind if constexpr (mg_cond<G>): the DMarg instantiations are the code they
 // were without it.
+//
+// MgPinProf (the pinned profiles, DESIGN.md §37): MgPin — a contig solved under the required policy (DReann.mode 2 or 4) — with the place of
+// `lost` and of the contig's round count, the two pointers MgPin lacks (no struct that exists grows).  dp_pin<G> holds for it: d_s' from
+// DPmarg.ds on NL + 1 limbs, d_t' from DPmarg.dist_t at DPmarg.dt_stride, the DReann.req words inside dp_sp_in's test and one off the top limb
+// of a required slot (dp_w_in).  Every edge has Delta'' = lost * M + s >= 0 on WL = NL + 1 limbs, decoded as k_margins<NL, MgPin> decodes it;
+// per slot and track the record carries the lexicographic minimum of (lost, s): mu(s) in the record's field, lost in MgPinProf.lost, three
+// int32 per slot (fwd, rev, gap).  A 64-bit key cannot order the pairs, so a track takes 1 + (distinct lost > 0 among its slots) rounds over
+// the same table:
+//   round 0      every edge of the track.  lost = 0: s >= 0 (Delta'' >= 0), the key is §34's, the pattern of mu, at most PF_NONE (+inf).
+//                lost = l > 0: the marker PF_NONE + l — above every such pattern, ordered by l; "none" is PF_PNONE, above every marker.  After the
+//                push-down a slot whose key is a pattern holds its exact result (0, mu); one that holds a marker knows L(i) = l, the least
+//                lost among its covering edges, and gets (l, +inf) for now.
+//   round l      for each level l some slot of the track holds, ascending (the block-wide least L(i) above the level just done): the table
+//                is cleared, the edges with lost == l alone enter, keyed by pf_skey(mu) — the order-preserving map of a signed double —, and
+//                after the push-down the slots with L(i) = l take pf_sval(key).  Exact, because every covering edge of slot i has
+//                lost >= L(i): among the edges that entered, those covering i are exactly its covering edges of least lost, and rounding
+//                is monotone in s.
+// MgPinProf.rounds gets 3 + the level rounds of the three tracks.  All of it sits behind if constexpr (pf_pin<G>).
+struct MgPinProf : MgPin { int32_t *lost; int32_t *rounds; };
+template <class G> constexpr bool pf_pin = std::is_same<G, MgPinProf>::value;
+#define PF_PNONE 0xffffffffffffffffull // MgPinProf: nothing of the track (round 0) / of the level (later rounds) covers the slot
+// a signed double's pattern as an unsigned key of the same order (-0.0 below +0.0; no NaN enters), and back
+__device__ __forceinline__ unsigned long long pf_skey(double x) { const unsigned long long p = (unsigned long long)__double_as_longlong(x); return (p >> 63) ? ~p : (p | 0x8000000000000000ull); }
+__device__ __forceinline__ double pf_sval(unsigned long long k) { return __longlong_as_double((long long)((k >> 63) ? (k ^ 0x8000000000000000ull) : ~k)); }
 // the contigs the pass covers: device distances and a settled reverse pass (a contig without a path is covered: every value is +inf); under
-// MgCond the contigs solved again (DRmarg.sel 1: with a path, and a conditioned reverse pass that settled; 2: without one, D' unreached)
+// MgCond the contigs solved again (DRmarg.sel 1: with a path, and a conditioned reverse pass that settled; 2: without one, D' unreached);
+// under MgPinProf the same test on DPmarg.sel / mstat
 template <class G>
 __device__ __forceinline__ bool pf_on(const DBatch &b, const G &g, const DMeta *meta) {
     if constexpr (mg_cond<G>) { const int i = (int)(meta - b.meta), sel = g.r.sel[i]; return sel != 0 && mg_contig(meta) && (sel == 2 || !g.r.mstat[i]); }
@@ -58,6 +83,8 @@ __device__ __forceinline__ uint64_t pf_ld(const unsigned long long *p) { return 
 // register 8 bytes below an LDS table that starts at the bottom of the LDS aperture — an address outside every aperture.)
 template <int NL, class G, class T>
 __device__ __forceinline__ void pf_tracks(const DBatch &b, const G &g, const DProf &q, const DMeta *meta, T *tab, int lv) {
+    constexpr int WL = NL + (pf_pin<G> ? 1 : 0); // limbs of a value
+    constexpr unsigned long long NONE = pf_pin<G> ? PF_PNONE : PF_NONE;
     const int V = meta->n_node, n = V - 1, tid = threadIdx.x;
     const uint32_t un = (uint32_t)n, cells = un * (uint32_t)lv;
     const size_t no = (size_t)meta->node_off;
@@ -73,11 +100,17 @@ __device__ __forceinline__ void pf_tracks(const DBatch &b, const G &g, const DPr
     [[maybe_unused]] bool biased = false;
     if constexpr (mg_cond<G>) biased = re_mode_bias(g.q.mode[blockIdx.x]);
     double *val = (double *)(q.rec + q.roff[blockIdx.x]); // four doubles per record: (lo, hi), fwd, rev, gap
-    const WInt<NL> D = wi_load<NL>(ds + (size_t)(V - 1) * NL);
-    const bool d_ok = !wi_unreached<NL>(D);
-    const WInt<NL> negD = wi_neg<NL>(D);
-    for (int t = 0; t < 3; t++) {
-        for (uint32_t i = (uint32_t)tid; i < cells; i += NT) tab[i] = PF_NONE;
+    const WInt<WL> D = wi_load<WL>(ds + (size_t)(V - 1) * WL);
+    const bool d_ok = !wi_unreached<WL>(D);
+    const WInt<WL> negD = wi_neg<WL>(D);
+    [[maybe_unused]] int32_t *lost = nullptr; // MgPinProf: three per slot, parallel to the records
+    [[maybe_unused]] int rounds = 0;
+    if constexpr (pf_pin<G>) lost = g.lost + 3 * (size_t)q.roff[blockIdx.x];
+    [[maybe_unused]] int level = 0; // MgPinProf: the round's level (0: every edge of the track); a track is left when no level is pending
+    // One loop serves the tracks and, under MgPinProf, a track's rounds: the step stays on the track while a level is pending.  (A loop
+    // statement of its own around the rounds would change the DMarg and MgCond bodies: the compiler numbers a function's jump destinations.)
+    for (int t = 0; t < 3; t += pf_pin<G> && level > 0 ? 0 : 1) {
+        for (uint32_t i = (uint32_t)tid; i < cells; i += NT) tab[i] = NONE;
         __syncthreads();
         for (int v = tid; v < V && d_ok; v += NT) {
             const int rv = pf_rank(v, V);
@@ -85,7 +118,7 @@ __device__ __forceinline__ void pf_tracks(const DBatch &b, const G &g, const DPr
             uint32_t e = in_off[v], e1 = in_off[v + 1];
             if (e1 > E) e1 = E; // (the contig's own edges)
             bool have = false;
-            WInt<NL> tz = negD;
+            WInt<WL> tz = negD;
             [[maybe_unused]] bool sp = false;
             if constexpr (mg_cond<G>) sp = dp_sp_in(g, biased, ebase, e, e1);
             for (; e < e1; e++) {
@@ -96,15 +129,29 @@ __device__ __forceinline__ void pf_tracks(const DBatch &b, const G &g, const DPr
                 const int ru = pf_rank(u, V);
                 if (ru >= rv || pf_track(nd[u].info) != t) continue; // covers nothing (overlap connectors, equal ranks) / another track's
                 if (!have) { // d_t(v) - D, at the first edge that asks for it
-                    const WInt<NL> dv = wi_load<NL>(dt + (size_t)v * NL);
-                    if (wi_unreached<NL>(dv)) break; // mu = +inf for every in-edge of v
-                    tz = wi_add<NL>(dv, negD);
+                    const WInt<WL> dv = wi_load<WL>(dt + (size_t)v * WL);
+                    if (wi_unreached<WL>(dv)) break; // mu = +inf for every in-edge of v
+                    tz = wi_add<WL>(dv, negD);
                     have = true;
                 }
-                const WInt<NL> du = wi_load<NL>(ds + (size_t)u * NL);
-                if (wi_unreached<NL>(du)) continue;
-                const WInt<NL> delta = wi_add<NL>(wi_add<NL>(du, dp_w_in<NL>(g, sp, biased, ebase + e, ew_decode<NL>(edge_wenc(sw, ew, e, gt)))), tz);
-                const unsigned long long key = (unsigned long long)__double_as_longlong(wi_to_double_rn<NL>(delta) / 1000.0);
+                const WInt<WL> du = wi_load<WL>(ds + (size_t)u * WL);
+                if (wi_unreached<WL>(du)) continue;
+                const WInt<WL> delta = wi_add<WL>(wi_add<WL>(du, dp_w_in<WL>(g, sp, biased, ebase + e, ew_decode<WL>(edge_wenc(sw, ew, e, gt)))), tz);
+                unsigned long long key;
+                if constexpr (pf_pin<G>) { // Delta'' = lost * M + s, as k_margins<NL, MgPin> decodes it
+                    const int32_t el = (int32_t)(int64_t)(delta.v[WL - 1] + (delta.v[NL - 1] >> 63));
+                    if (level ? el != level : el > 0) {
+                        if (level) continue; // another level's
+                        key = PF_NONE + (unsigned long long)(uint32_t)el; // the marker of lost = el
+                    } else {
+                        WInt<NL> sl;
+#pragma unroll
+                        for (int i = 0; i < NL; i++) sl.v[i] = delta.v[i];
+                        const double mu = wi_to_double_rn<NL>(sl) / 1000.0;
+                        key = level ? pf_skey(mu) : (unsigned long long)__double_as_longlong(mu); // (lost = 0: s >= 0)
+                    }
+                } else
+                key = (unsigned long long)__double_as_longlong(wi_to_double_rn<NL>(delta) / 1000.0);
                 const uint32_t a = (uint32_t)(ru + 1), z = (uint32_t)rv, k = 31u - (uint32_t)__clz((int)(z - a + 1u)); // slots [a, z], 0 <= a <= z <= n - 1; 2^k <= z - a + 1 <= n: k < lv
                 const uint32_t ia = k * un + a, iz = k * un + (z + 1u - (1u << k));                                     // (a <= z + 1 - 2^k <= z)
                 if (ia >= cells || iz >= cells) continue; // (cannot happen)
@@ -118,13 +165,39 @@ __device__ __forceinline__ void pf_tracks(const DBatch &b, const G &g, const DPr
             for (uint32_t i = (uint32_t)tid; i < un; i += NT) {
                 uint64_t m = pf_ld(&tab[k * un + i]);
                 if (i >= h) { const uint64_t m2 = pf_ld(&tab[k * un + (i - h)]); m = m2 < m ? m2 : m; }
-                if (m != PF_NONE) atomicMin(&tab[(k - 1u) * un + i], (unsigned long long)m);
+                if (m != NONE) atomicMin(&tab[(k - 1u) * un + i], (unsigned long long)m);
             }
             __syncthreads();
         }
+        if constexpr (pf_pin<G>) {
+            __shared__ int s_next; // the least L(i) above `level` among the track's slots (a slot is its own thread's in every round)
+            if (tid == 0) s_next = 0x7fffffff;
+            __syncthreads();
+            int next = 0x7fffffff;
+            for (uint32_t i = (uint32_t)tid; i < un; i += NT) {
+                const unsigned long long k = pf_ld(&tab[i]);
+                int32_t L;
+                if (level == 0) { // a pattern: (0, mu), exact; a marker: (l, for now +inf); none: (0, +inf)
+                    L = k > PF_NONE && k != PF_PNONE ? (int32_t)(uint32_t)(k - PF_NONE) : 0;
+                    val[4 * (size_t)i + 1 + t] = __longlong_as_double((long long)(k < PF_NONE ? k : PF_NONE));
+                    lost[3 * (size_t)i + t] = L;
+                } else {
+                    L = lost[3 * (size_t)i + t];
+                    if (L == level && k != PF_PNONE) val[4 * (size_t)i + 1 + t] = pf_sval(k);
+                }
+                if (L > level && L < next) next = L;
+            }
+            if (next != 0x7fffffff) atomicMin(&s_next, next);
+            __syncthreads(); // (and every read of the table is done before the next round clears it)
+            level = s_next == 0x7fffffff ? 0 : s_next;
+            rounds++;
+            __syncthreads(); // (s_next is read before the next round resets it)
+        } else {
         for (uint32_t i = (uint32_t)tid; i < un; i += NT) val[4 * (size_t)i + 1 + t] = __longlong_as_double((long long)pf_ld(&tab[i]));
         __syncthreads(); // (every read of the table is done before the next track clears it)
+        }
     }
+    if constexpr (pf_pin<G>) { if (tid == 0) g.rounds[blockIdx.x] = rounds; }
 }
 template <int NL, class G = DMarg>
 __global__ __launch_bounds__(NT) void k_pf_cand(DBatch b, G g, DProf q) {
